@@ -3,7 +3,14 @@
 phoneme batches (BASELINE.json: batch-32, 256-phoneme utterances, 22.05 kHz).
 
   python bench.py --gpus N --steps K --warmup W [--preset high|medium] [--batch 32] [--tokens 256]
-                  [--total-batch 256]
+                  [--total-batch 256] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline.  `--full` adds everything else the line can
+report: the roofline and per-kernel figures, the CPU baseline, the medium preset, BASELINE config 4, one-utterance
+latency, the host-in/host-out, one-handle, split-schedule, padded-rendering and exact-arithmetic figures.
+`--dump-outputs DIR` writes what the last timed step computed (DIR/output.npy: the [B,1,1,S] float32 waveform,
+DIR/y_lengths.npy: the frame counts, as float64); every input and the device noise are seeded, so two runs with the
+same arguments compute the same step.
 
 One process per GPU.  `--gpus N` with N > 1 started by hand (no RANK in the environment) launches the N ranks itself
 (`python -m torch.distributed.run`, fresh child processes) and relays rank 0's line; under torchrun the ranks find
@@ -57,6 +64,17 @@ def git_head():
         return info["commit"] + ("+" if info.get("dirty") else "")
     except Exception:
         return None
+
+
+def voice_cache():
+    """Directory of the synthetic voices (bench.py and tests/test_gpu_fullsize.py share them): VITSMI_BENCH_CACHE, else one
+    of this user's in the system temp directory (the checkout may be read-only, and another user's directory may sit in the
+    way), under a subdirectory named by phoonnx_amd/synth.py's contents (a checkout with another generator writes anew)."""
+    import hashlib
+    import tempfile
+    base = os.environ.get("VITSMI_BENCH_CACHE") or os.path.join(tempfile.gettempdir(), f"vitsmi_bench_{os.getuid()}")
+    with open(os.path.join(ROOT, "phoonnx_amd", "synth.py"), "rb") as f:
+        return os.path.join(base, hashlib.sha256(f.read()).hexdigest()[:12])
 
 
 def source_sha():
@@ -310,14 +328,21 @@ def main():
                          "(BASELINE config 4: --preset medium --speakers 4 --batch 64 --mixed-lengths --gen-precision f16)")
     ap.add_argument("--mixed-lengths", action="store_true",
                     help="utterance lengths uniform in [tokens/4, tokens] (seed 1235), zero-padded, instead of all = tokens")
-    ap.add_argument("--prewarm-s", type=float, default=2.0,
-                    help="untimed passes for this many seconds before the W warm-up steps of a voice's first measurement "
-                         "(a fresh process' first passes touch the workspace for the first time; 0 = none)")
+    ap.add_argument("--prewarm-steps", type=int, default=48,
+                    help="untimed passes before the W warm-up steps of a voice's first measurement (a fresh process' first "
+                         "passes touch the workspace for the first time; 48 = ~2 s of the headline; 0 = none).  A count, not "
+                         "a time: the engine's device noise advances with every pass of a handle, so a fixed count makes "
+                         "every timed pass compute the same thing from run to run")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: roofline and per-kernel figures, the CPU baseline and the "
+                         "secondary measurements (--no-cpu-baseline / --no-roofline / --no-extras switch parts off again)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (at most 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the secondary measurements of the N=1 line (exact arithmetic, host-in/host-out, the medium "
-                         "preset, per-step percentiles)")
+                    help="skip the secondary measurements of the N=1 --full line (exact arithmetic, host-in/host-out, the "
+                         "medium preset, per-step percentiles)")
     ap.add_argument("--gen-precision", default="f16x3", choices=["f16x3", "bf16x6", "f16"],
                     help="arithmetic of the generator's convs (fp32 operands and results in every mode).  f16x3 (default): "
                          "two fp16 planes per operand, three MFMA products per fp32 product, error no larger than the "
@@ -346,6 +371,8 @@ def main():
                          "its step, and three sub-batches hide more of them than two (573 vs 534 M samples/s; four or "
                          "more handles per process fall off a cliff: 413 M)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0 or a.prewarm_steps < 0:
+        ap.error("--steps must be >= 1, --warmup and --prewarm-steps >= 0")
 
     if a.gpus > 1 and "RANK" not in os.environ:
         sys.exit(launch_ranks(a, sys.argv[1:]))
@@ -374,7 +401,7 @@ def main():
     from phoonnx_amd.sharding import arena_checksum, open_sharded
     from phoonnx_amd.synth import write_voice
 
-    cache = os.environ.get("VITSMI_BENCH_CACHE", "/tmp/vitsmi_bench")
+    cache = voice_cache()
 
     def voice_path(preset, speakers=1):
         p = os.path.join(cache, f"synth_{preset}{'' if speakers <= 1 else f'_spk{speakers}'}.onnx")
@@ -492,8 +519,9 @@ def main():
                                              alternate=schedule == "alternate").sum()) * hop
 
         # a fresh process' first passes are slow (first touch of ~60 GB of workspace, clock ramp: the first bench run on a fresh
-        # box measured 567 M samples/s where every later one measured 740-750 M): pre-warm for --prewarm-s seconds (untimed,
-        # like the model load), THEN the W warm-up steps and the K timed ones of the contract
+        # box measured 567 M samples/s where every later one measured 740-750 M): --prewarm-steps untimed passes (like the
+        # model load), THEN the W warm-up steps and the K timed ones of the contract.  A fixed count: a handle's device noise
+        # follows its number of passes, so the timed ones compute the same from run to run (--dump-outputs)
         # A batch's frame count depends on the predicted durations, i.e. on each pass' noise: the headline batch needs 13.6-15.4
         # GB of frame-domain workspace per handle from pass to pass, and a pass that needs more than any before it frees and
         # reallocates the slab (device-wide sync + hipMalloc of 15-45 GB: 0.3 ms to 5 s, measured) - inside the timed region
@@ -507,11 +535,9 @@ def main():
             pipe.sync()
             pipe.reserve(B, T, int(f_probe * 1.25) + 64,
                          whole_batch=(schedule == "alternate" or a.schedule == "alternate") and not (lockstep or len(pipe.parts) == 1))
-        if a.prewarm_s > 0 and not prewarmed.get(id(first)):
+        if a.prewarm_steps > 0 and not prewarmed.get(id(first)):
             prewarmed[id(first)] = True
-            t_pw = time.perf_counter()
-            while time.perf_counter() - t_pw < a.prewarm_s:
-                run_steps(2)
+            run_steps(a.prewarm_steps)
         if warmup > 0:
             run_steps(warmup)
         pipe.sync()
@@ -656,8 +682,39 @@ def main():
         stage["stage_marks_only"] = marks
         return roof, stage, rng_stats
 
+    def dump_last_step(pipe, B, steps, out_dir, cap_bytes):
+        """What the last of `steps` timed passes left on the device, as a caller of the path receives it: the waveform
+        [B,1,1,S] float32 (zeros behind each utterance's end) and the frame counts -> out_dir/<name>.npy.  Above
+        cap_bytes the waveform is replaced by a fixed, seeded sample of its elements (output_sample, at the flat indices
+        output_sample_index of a [B,1,1,S] array of shape output_shape)."""
+        bnd = pipe.bounds(B)
+        n = len(bnd) - 1
+        if a.lockstep or len(pipe.parts) == 1 or a.schedule != "alternate":
+            rows = [(pipe.parts[i], bnd[i], bnd[i + 1] - bnd[i]) for i in range(n)]  # (every pass split over the handles)
+        else:
+            rows = [(pipe.parts[(steps - 1) % n], 0, B)]                               # (whole passes dealt in turn)
+        ylen = np.zeros(B, np.int64)
+        for p, b0, nb in rows:
+            ylen[b0:b0 + nb] = p.last_y_lengths()
+        wave = np.empty((B, 1, 1, int(ylen.max()) * hop), np.float32)
+        for p, b0, nb in rows:
+            p._fetch(wave, b0, nb)
+        arrays = {"y_lengths": ylen.astype(np.float64)}
+        if wave.nbytes + ylen.nbytes <= cap_bytes:
+            arrays["output"] = wave
+        else:
+            k = (cap_bytes - ylen.nbytes - 4096) // 12
+            idx = np.unique(np.random.default_rng(0).integers(0, wave.size, k))
+            arrays.update(output_sample=wave.reshape(-1)[idx], output_sample_index=idx.astype(np.float64),
+                          output_shape=np.array(wave.shape, np.float64))
+        os.makedirs(out_dir, exist_ok=True)
+        for name, v in arrays.items():
+            np.save(os.path.join(out_dir, f"{name}{'' if world == 1 else f'_rank{rank}'}.npy"), v)
+
     # ---------------------------------------------------------------- the headline measurement
     dt, samples, pipe, inputs = measure(sess, a.preset, a.steps, a.warmup, a.parts, a.lockstep, 1234 + rank)
+    if a.dump_outputs:  # (before anything else runs a pass on these handles)
+        dump_last_step(pipe, B, a.steps, a.dump_outputs, 64_000_000 // world)
     tot = torch.tensor([dt, float(samples)], dtype=torch.float64, device="cuda")
     per_rank = None
     if dist:
@@ -680,10 +737,10 @@ def main():
         dt_max, samples_all = dt, float(samples)
 
     roofline = stage = f16_range = None
-    if rank == 0 and not a.no_roofline:
+    if rank == 0 and a.full and not a.no_roofline:
         roofline, stage, f16_range = roofline_of(sess, a.preset, inputs, max(3, min(a.steps, 5)))
 
-    extras = world == 1 and not a.no_extras
+    extras = world == 1 and a.full and not a.no_extras
     ids, lens, ids_h, lens_h, scales, sid, sid_h = inputs
     sid_ptr = None if sid is None else sid.data_ptr()
 
@@ -879,7 +936,7 @@ def main():
             config4 = {"error": f"{type(e).__name__}: {e}"}
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and a.speakers <= 1:  # (N = 1 only: the other ranks would sit in the final barrier)
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline and a.speakers <= 1:  # (N = 1 only: the other ranks would sit in the final barrier)
         try:
             cpu = cpu_baseline(voice, a.preset, T, scales, 1234, hop)
         except Exception as e:  # noqa: BLE001 - the baseline is a report, never the product
@@ -904,7 +961,7 @@ def main():
                                    f"{' (lengths uniform in [T/4, T], zero-padded)' if a.mixed_lengths else ''}, "
                                    f"scales=[0.667,{scales[1]:.2f},0.8], device Philox noise, seeded synthetic weights",
                        "preset": a.preset, "batch_per_gpu": B, "global_batch": a.total_batch or B * world, "tokens": a.tokens, "hop": hop,
-                       "pipeline_parts": n_parts, "prewarm_s": a.prewarm_s,
+                       "pipeline_parts": n_parts, "prewarm_steps": a.prewarm_steps, "full": a.full,
                        "pipeline_host": "lockstep" if (a.lockstep or n_parts == 1) else "one free-running host thread per part",
                        "pipeline_schedule": "lockstep: every pass split over the handles" if (a.lockstep or n_parts == 1) else
                                             ("whole passes dealt to the handles in turn (request-level pipelining)" if a.schedule == "alternate"

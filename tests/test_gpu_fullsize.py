@@ -7,11 +7,12 @@ import os
 import numpy as np
 import pytest
 
+from bench import voice_cache
 from conftest import zero_tails
 
 pytestmark = pytest.mark.gpu
 
-CACHE = os.environ.get("VITSMI_BENCH_CACHE", "/tmp/vitsmi_bench")
+CACHE = voice_cache()   # (bench.py's voices: the same files)
 
 
 _ORACLE_REF = {}

@@ -19,7 +19,7 @@ OUT=$R/gpurun_out/prof_${TAG}_${PRESET}_b${BATCH}
 mkdir -p "$OUT" "$R/profiles"
 cd /tmp && export TMPDIR=/tmp
 # (--parts 1: one handle / stream, as in the roofline block of the bench line, so that kernels do not overlap in the trace)
-BENCH="python3 $R/bench.py --preset $PRESET --steps 3 --warmup 1 --no-cpu-baseline --no-extras --parts 1 --batch $BATCH $EXTRA"
+BENCH="python3 $R/bench.py --full --preset $PRESET --steps 3 --warmup 1 --no-cpu-baseline --no-extras --parts 1 --batch $BATCH $EXTRA"
 T="timeout -k 10 240"
 $T rocprofv3 --kernel-trace --stats -d "$OUT/stats" -o s -- $BENCH > "$OUT/stats.log" 2>&1
 if [ "$BATCH" = 32 ]; then
