@@ -202,6 +202,36 @@ int vits_run_chunked(vits_handle *h, const int64_t *ids, const int64_t *lens, in
 int vits_run_vocoder_chunked(vits_handle *h, const float *z, int B, int F, const int64_t *sid, int chunk_frames,
                              vits_chunk_fn fn, void *user);
 
+/* ---- per-utterance synthesis settings ------------------------------------------------
+ * Row twins of vits_run_async / vits_run_device / vits_run_chunked: the same arguments, except that
+ *   scales  host float32 [B][3]: utterance b's own [noise_scale, length_scale, noise_w]
+ *           (models.py:111 noise_w, :702-704 length_scale, :718 noise_scale), also for vits_run_device_rows;
+ *   seeds   host uint64 [B], or NULL: utterance b's own 64-bit noise seed.
+ * Every value of `scales` must be finite (VITS_E_ARG naming the row, before anything is enqueued); otherwise a row
+ * accepts what the [3] vector accepts.  A row equal to the [3] vector with seeds = NULL gives the base function's results
+ * bit for bit.  Injected noise (vits_noise.noise_dp / noise_z) takes precedence over the seeds for that tensor.
+ *
+ * The per-utterance noise stream (seeds != NULL).  Utterance b's noise tensors are those a caller would inject as its
+ * row of noise_dp ([2, T], stream 1) and of noise_z ([inter, F], stream 2); element (ch, pos) of tensor `stream` is
+ *   (r0, r1, r2, r3) = Philox4x32-10(counter = (pos >> 2, ch, stream, 0), key = (lo32(seeds[b]), hi32(seeds[b])))
+ *                      (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85; 10 rounds)
+ *   u_i = (float)r_i + 0.5f, times 2^-32 (fp32);  u0 and u2 clamped to [1e-12, 1]
+ *   v = (sqrt(-2 ln u0) cos(2 pi u1), sqrt(-2 ln u0) sin(2 pi u1), sqrt(-2 ln u2) cos(2 pi u3), sqrt(-2 ln u2) sin(2 pi u3))
+ *   noise = v[pos & 3]
+ * i.e. a function of (seeds[b], stream, ch, pos) alone: the utterance's place in the batch, the batch's T and F, the
+ * handle and the number of calls it has served do not enter.  Its durations and frame count therefore depend on its own
+ * inputs only; so do its samples except the last vits_hparam "gen_rf_frames" frames, where the padded batch's generator
+ * still sees a longer neighbour's frames (as in vits_run).  Across batch layouts (other B, T) the encoder's sums may
+ * differ in their last bits: equal durations, samples within fp32 summation-order distance.  Without seeds, the noise is today's stream: one Philox draw
+ * over the whole [B, 2, T] / [B, inter, F] tensor, keyed by vits_noise.seed mixed with a per-handle run counter. */
+int vits_run_async_rows(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const float *scales,
+                        const int64_t *sid, const vits_noise *noise, const uint64_t *seeds);
+int vits_run_device_rows(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const float *scales,
+                         const int64_t *sid, const vits_noise *noise, const uint64_t *seeds, vits_output *out);
+int vits_run_chunked_rows(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const float *scales,
+                          const int64_t *sid, const vits_noise *noise, const uint64_t *seeds, int chunk_frames,
+                          vits_chunk_fn fn, void *user);
+
 /* Frame counts of the last run, from the host copy made by the mid-pipeline readback
  * (no synchronisation).  Writes min(n, B) values, returns B. */
 int vits_last_y_lengths(vits_handle *h, int64_t *buf, int n);

@@ -56,7 +56,7 @@ EXPORTS = [
     "vits_test_attention", "vits_test_attention16", "vits_bench_conv1d", "vits_test_conv1d_sx", "vits_test_conv1d_sx_planar", "vits_test_conv1d_sx_gate", "vits_test_set_sx_small_max",
     "vits_test_conv_transpose1d_sx",
     "vits_bench_conv1d_sx", "vits_test_conv_pair_sx", "vits_fetch_output", "vits_run_async", "vits_host_alloc", "vits_host_free",
-    "vits_launch_records",
+    "vits_launch_records", "vits_run_async_rows", "vits_run_device_rows", "vits_run_chunked_rows",
 ]
 
 
@@ -113,6 +113,10 @@ def load():
     lib.vits_run.argtypes = run_args
     lib.vits_run_device.argtypes = run_args
     lib.vits_run_async.argtypes = run_args[:-1]
+    # (row twins: scales host float32 [B][3], then a host uint64 [B] of seeds or NULL behind the noise)
+    lib.vits_run_async_rows.argtypes = run_args[:-1] + [vp]
+    lib.vits_run_device_rows.argtypes = run_args[:-1] + [vp, C.POINTER(VitsOutput)]
+    lib.vits_run_chunked_rows.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, C.POINTER(VitsNoise), vp, C.c_int, CHUNK_FN, vp]
     lib.vits_free_output.argtypes = [vp, C.POINTER(VitsOutput)]
     lib.vits_free_output.restype = None
     lib.vits_sync.argtypes = [vp]

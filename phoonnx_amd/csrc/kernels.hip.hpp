@@ -908,9 +908,19 @@ __global__ void ea_logw_kernel(const float *z, int ch, float m0, float logs0, co
     logw[(int64_t)b * T + t] = (z[((int64_t)b * 2 + ch) * T + t] - m0) * expf(-logs0) * mk;
 }
 
-__global__ void scale_kernel(const float *in, float *out, float s, int64_t n) {
+// Per-utterance synthesis settings: `rows` is the run's device [B][3] (noise_scale, length_scale, noise_w) or NULL, when
+// every utterance takes the call's scalar - the same fp32 operations either way.
+__device__ __forceinline__ float row_setting(const float *rows, int b, int col, float v) {
+    return rows ? rows[(int64_t)b * 3 + col] : v;
+}
+
+// out = in * s (s: column `col` of rows[i / row_elems] when rows != NULL); a zero scale writes +0.0
+__global__ void scale_kernel(const float *in, float *out, float s, const float *rows, int col, int64_t row_elems,
+                             int64_t n) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = in[i] * s;
+    if (i >= n) return;
+    const float sc = rows ? rows[(i / row_elems) * 3 + col] : s;
+    out[i] = sc == 0.f ? 0.f : in[i] * sc;
 }
 
 // x[b,c,t] = (x[b,c,t] + bias_b[b,c]) (DurationPredictor cond, models.py:153-155)
@@ -923,14 +933,16 @@ __global__ void add_bias_b_kernel(const float *in, float *out, const float *bias
 
 // ---- a9: durations (models.py:702-704): one block per utterance ----------------------------------
 // w = exp(logw)*mask*length_scale; w_ceil = ceil(w); cum = inclusive scan (ints); y_len = max(sum,1)
-__global__ void duration_kernel(const float *logw, const int *len, float length_scale, float *w_ceil, int *cum,
-                                int *y_len, int T) {
+// (length_scale: the utterance's row of `rows` when given)
+__global__ void duration_kernel(const float *logw, const int *len, float length_scale_all, const float *rows,
+                                float *w_ceil, int *cum, int *y_len, int T) {
     __shared__ int sh[256];
     __shared__ int carry_s;
     int b = blockIdx.x, tid = threadIdx.x;
     if (tid == 0) carry_s = 0;
     __syncthreads();
     const int L = len[b];
+    const float length_scale = row_setting(rows, b, 1, length_scale_all);
     for (int base = 0; base < T; base += 256) {
         int t = base + tid;
         int v = 0;
@@ -958,39 +970,110 @@ __global__ void duration_kernel(const float *logw, const int *len, float length_
     if (tid == 0) y_len[b] = carry_s < 1 ? 1 : carry_s;
 }
 
+// ---- noise: Philox4x32-10 counter RNG + Box-Muller (production path; parity uses injected noise) ---
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
+                                              uint32_t k1, uint32_t out[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; r++) {
+        uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
+        uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+// four standard normals from one Philox4x32-10 block: counter (c0, c1, c2, c3), key (lo32(key), hi32(key)), the four
+// words as uniforms in (0, 1] and two Box-Muller pairs
+__device__ __forceinline__ void philox_normal4(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint64_t key,
+                                               float v[4]) {
+    uint32_t r[4];
+    philox4x32_10(c0, c1, c2, c3, (uint32_t)key, (uint32_t)(key >> 32), r);
+    const float k = 2.3283064365386963e-10f;  // 2^-32
+    float u0 = ((float)r[0] + 0.5f) * k, u1 = ((float)r[1] + 0.5f) * k;
+    float u2 = ((float)r[2] + 0.5f) * k, u3 = ((float)r[3] + 0.5f) * k;
+    u0 = fminf(fmaxf(u0, 1e-12f), 1.0f);
+    u2 = fminf(fmaxf(u2, 1e-12f), 1.0f);
+    float ra = sqrtf(-2.0f * logf(u0)), rb = sqrtf(-2.0f * logf(u2));
+    v[0] = ra * cosf(6.283185307179586f * u1);
+    v[1] = ra * sinf(6.283185307179586f * u1);
+    v[2] = rb * cosf(6.283185307179586f * u3);
+    v[3] = rb * sinf(6.283185307179586f * u3);
+}
+
+// The per-utterance noise stream (vitsmi.h, vits_run_async_rows): element (ch, pos) of utterance b's noise tensor
+// `stream` (1: [2, T] duration noise, 2: [inter, F] prior noise) is v[pos & 3] of philox_normal4 with counter
+// (pos >> 2, ch, stream, 0) and key seeds[b] - a function of the utterance's own seed and the element's place only.
+// This kernel writes the duration noise: out[b, ch, pos] = that value * noise_w[b] (+0.0 where noise_w[b] is 0);
+// one thread per four positions (one Philox block).  grid (ceil(T / 4) / 64, channels, B)
+__global__ void fill_normal_rows_kernel(float *out, int T, const uint64_t *seeds, uint32_t stream, const float *rows,
+                                        int col) {
+    const int p4 = blockIdx.x * blockDim.x + threadIdx.x, ch = blockIdx.y, b = blockIdx.z;
+    if (p4 * 4 >= T) return;
+    const float sc = rows[(int64_t)b * 3 + col];
+    float v[4];
+    philox_normal4((uint32_t)p4, (uint32_t)ch, stream, 0u, seeds[b], v);
+    float *o = out + ((int64_t)b * gridDim.y + ch) * T;
+    for (int j = 0; j < 4; j++)
+        if (p4 * 4 + j < T) o[p4 * 4 + j] = sc == 0.f ? 0.f : v[j] * sc;
+}
+
 // ---- a9: expand prior by durations + sample (commons.py:116-129, models.py:711-718) --------------
 // z_p[b,c,f] = m_p[b,c,i(f)] + noise[b,c,f] * exp(logs_p[b,c,i(f)]) * noise_scale ; frames with no
 // token (f >= y_len[b]) see m=0, logs=0 exactly as the reference's masked path matmul gives.
 // m_p / logs_p are strided views (batch stride `bstride`, channel stride T).
-__global__ void expand_prior_strided_kernel(const float *m_p, const float *logs_p, int64_t bstride, const int *cum,
-                                            const int *len, const int *y_len, const float *noise,
-                                            int64_t noise_stride, float noise_scale, float *z_p, int C, int T, int F,
-                                            int Fnoise) {
-    // grid (F / 64, C / 16, B): 16 channels of one frame per thread (the token search is repeated per channel group:
-    // eight steps, against 16 x 3 loads)
-    int f = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.z;
-    if (f >= F) return;
+// noise_scale is the utterance's row of `rows` when given (a row whose noise_scale is 0 reads no noise: the noise-free
+// path's values); the noise is `noise` when given, else - with `seeds` - the utterance's own stream 2, drawn here.
+__global__ void expand_prior_strided_kernel(const float *__restrict__ m_p, const float *__restrict__ logs_p,
+                                            int64_t bstride, const int *cum, const int *len, const int *y_len,
+                                            const float *__restrict__ noise, int64_t noise_stride, float noise_scale_all,
+                                            const float *rows, const uint64_t *seeds, float *__restrict__ z_p, int C,
+                                            int T, int F, int Fnoise) {
+    // grid (F / 256, C / 4, B): 4 channels of four consecutive frames per thread - as many threads and outputs per thread
+    // as one frame x 16 channels, and one Philox block of the seeded stream per channel (the token search is repeated per
+    // channel group: eight steps for the first frame, a step or two onwards for the other three, against 4 x 12 loads)
+    const int f0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4, b = blockIdx.z;
+    if (f0 >= F) return;
     const int *cb = cum + (int64_t)b * T;
-    int tok = -1;
-    if (f < y_len[b]) {
-        int lo = 0, hi = T;  // smallest i with cum[i] > f
+    const int yl = y_len[b], L = len[b];
+    // tok = smallest i with cum[i] > f, if below len (cum is non-decreasing: the next frame's token is at or behind it);
+    // no search for frames behind the utterance's end, and the walk never passes len (behind it cum is the total)
+    int tok[4] = {-1, -1, -1, -1};
+    if (f0 < yl) {
+        int lo = 0, hi = T;
         while (lo < hi) {
             int mid = (lo + hi) >> 1;
-            if (cb[mid] > f) hi = mid;
+            if (cb[mid] > f0) hi = mid;
             else lo = mid + 1;
         }
-        if (lo < T && lo < len[b]) tok = lo;
-    }
-    const float *mb = m_p + (int64_t)b * bstride, *lb = logs_p + (int64_t)b * bstride;
-    const int c0 = blockIdx.y * 16, c1 = c0 + 16 < C ? c0 + 16 : C;
-    for (int c = c0; c < c1; c++) {
-        float mp = 0.f, lp = 0.f;
-        if (tok >= 0) {
-            mp = mb[(int64_t)c * T + tok];
-            lp = lb[(int64_t)c * T + tok];
+        for (int j = 0; j < 4 && f0 + j < yl; j++) {
+            while (lo < L && cb[lo] <= f0 + j) lo++;
+            tok[j] = lo < L ? lo : -1;
         }
-        float e = (noise && f < Fnoise) ? noise[((int64_t)b * C + c) * noise_stride + f] : 0.f;
-        z_p[((int64_t)b * C + c) * F + f] = mp + e * expf(lp) * noise_scale;
+    }
+    const float noise_scale = row_setting(rows, b, 0, noise_scale_all);
+    const bool draw = !noise && seeds && noise_scale != 0.f;
+    const uint64_t key = draw ? seeds[b] : 0;
+    const float *mb = m_p + (int64_t)b * bstride, *lb = logs_p + (int64_t)b * bstride;
+    const int c0 = blockIdx.y * 4, c1 = c0 + 4 < C ? c0 + 4 : C;
+    for (int c = c0; c < c1; c++) {
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        if (draw) philox_normal4((uint32_t)(f0 >> 2), (uint32_t)c, 2u, 0u, key, v);
+        float *zr = z_p + ((int64_t)b * C + c) * F;
+        const float *nr = noise ? noise + ((int64_t)b * C + c) * noise_stride : nullptr;
+        for (int j = 0; j < 4; j++) {
+            const int f = f0 + j;
+            if (f >= F) break;
+            float mp = 0.f, lp = 0.f;
+            if (tok[j] >= 0) {
+                mp = mb[(int64_t)c * T + tok[j]];
+                lp = lb[(int64_t)c * T + tok[j]];
+            }
+            float e = noise_scale == 0.f ? 0.f : nr ? (f < Fnoise ? nr[f] : 0.f) : v[j];
+            zr[f] = mp + e * expf(lp) * noise_scale;
+        }
     }
 }
 
@@ -1216,35 +1299,13 @@ __global__ __launch_bounds__(256) void post_conv_tanh_blocked_kernel(const float
     out[(int64_t)b * T + t] = t < NV ? tanhf(acc) : 0.f;
 }
 
-// ---- noise: Philox4x32-10 counter RNG + Box-Muller (production path; parity uses injected noise) ---
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
-                                              uint32_t k1, uint32_t out[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; r++) {
-        uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
-        uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
+// the flat stream of calls without per-utterance seeds: element i of the whole [n] tensor is v[i & 3] of
+// philox_normal4 with counter (lo32(i >> 2), hi32(i >> 2), lo32(stream_id), hi32(stream_id)) and key `seed`
 __global__ void fill_normal_kernel(float *out, int64_t n, uint64_t seed, uint64_t stream_id) {
     int64_t i4 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i4 * 4 >= n) return;
-    uint32_t r[4];
-    philox4x32_10((uint32_t)i4, (uint32_t)(i4 >> 32), (uint32_t)stream_id, (uint32_t)(stream_id >> 32),
-                  (uint32_t)seed, (uint32_t)(seed >> 32), r);
-    const float k = 2.3283064365386963e-10f;  // 2^-32
-    float u0 = ((float)r[0] + 0.5f) * k, u1 = ((float)r[1] + 0.5f) * k;
-    float u2 = ((float)r[2] + 0.5f) * k, u3 = ((float)r[3] + 0.5f) * k;
-    u0 = fminf(fmaxf(u0, 1e-12f), 1.0f);
-    u2 = fminf(fmaxf(u2, 1e-12f), 1.0f);
-    float ra = sqrtf(-2.0f * logf(u0)), rb = sqrtf(-2.0f * logf(u2));
-    float v[4] = {ra * cosf(6.283185307179586f * u1), ra * sinf(6.283185307179586f * u1),
-                  rb * cosf(6.283185307179586f * u3), rb * sinf(6.283185307179586f * u3)};
+    float v[4];
+    philox_normal4((uint32_t)i4, (uint32_t)(i4 >> 32), (uint32_t)stream_id, (uint32_t)(stream_id >> 32), seed, v);
     for (int j = 0; j < 4; j++)
         if (i4 * 4 + j < n) out[i4 * 4 + j] = v[j];
 }

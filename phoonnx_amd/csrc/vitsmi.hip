@@ -1049,11 +1049,30 @@ size_t tokens_ws_bytes(const Model &m, int B, int T) {
     need += al((size_t)B * pr_rows * T) + al((size_t)B * 2 * T) * 2 + al((size_t)B * T) * 4;
     need += al((size_t)B * (m.gin + m.dp_cond_rows + m.C0 + 16)) + (1 << 16);
     for (auto &cd : m.flow) need += al((size_t)B * 2 * m.flow_H * cd.n_wn);
+    need += al((size_t)B * 3) + al((size_t)B * 2);         // per-utterance settings and seeds (RunRows)
     return need;
 }
 
+// The synthesis settings of a run: the call's one [3] vector (noise_scale, length_scale, noise_w) for every utterance, or
+// (vits_run_*_rows) a host [B][3] row per utterance and optionally a host [B] of per-utterance noise seeds.  run_tokens
+// copies the rows and seeds into the token slab; kernels read them there (d_rows / d_seeds), or take the call's scalars
+// when d_rows is NULL.
+struct RunRows {
+    const float *scales = nullptr;  // host [3] (rows == false) or [B][3]
+    bool rows = false;
+    const uint64_t *seeds = nullptr;  // host [B] or NULL: the flat stream
+    const float *d_rows = nullptr;
+    const uint64_t *d_seeds = nullptr;
+    float at(int b, int col) const { return scales[(rows ? (int64_t)b * 3 : 0) + col]; }
+    bool any(int B, int col) const {  // some utterance's value is not 0
+        for (int b = 0; b < (rows ? B : 1); b++)
+            if (at(b, col) != 0.f) return true;
+        return false;
+    }
+};
+
 // ---- token-domain part: encoder + duration predictor + durations.  Leaves y_len on the host.
-int run_tokens(vits_handle *h, const int64_t *d_ids, const int64_t *d_lens, int B, int T, const float *scales,
+int run_tokens(vits_handle *h, const int64_t *d_ids, const int64_t *d_lens, int B, int T, RunRows &rr,
                const int64_t *d_sid, const float *d_noise_dp, uint64_t seed) {
     const Model &m = h->model;
     const int H = m.H, C = m.C;
@@ -1086,6 +1105,16 @@ int run_tokens(vits_handle *h, const int64_t *d_ids, const int64_t *d_lens, int 
     h->d_logw = slab_take<float>(s, (size_t)B * T);
     h->d_wceil = slab_take<float>(s, (size_t)B * T);
 
+    if (rr.rows) {
+        float *d_rows = slab_take<float>(s, (size_t)B * 3);
+        HIPCHECK(h, hipMemcpyAsync(d_rows, rr.scales, sizeof(float) * 3 * B, hipMemcpyHostToDevice, st));
+        rr.d_rows = d_rows;
+    }
+    if (rr.seeds) {
+        uint64_t *d_seeds = slab_take<uint64_t>(s, B);
+        HIPCHECK(h, hipMemcpyAsync(d_seeds, rr.seeds, sizeof(uint64_t) * B, hipMemcpyHostToDevice, st));
+        rr.d_seeds = d_seeds;
+    }
     lens_to_i32<<<(B + 63) / 64, 64, 0, st>>>(d_lens, h->d_len, B, T);
     const int *len = h->d_len;
     h->cur_stage = 0;
@@ -1168,7 +1197,7 @@ int run_tokens(vits_handle *h, const int64_t *d_ids, const int64_t *d_lens, int 
     // ---- duration predictor
     h->cur_stage = 1;
     stage_mark(h, 1);
-    const float noise_w = scales[2];
+    const float noise_w = rr.at(0, 2);
     if (m.use_sdp) {
         const int Cd = m.dp_pre.Cout;
         const int64_t sC = (int64_t)Cd * T;
@@ -1181,15 +1210,18 @@ int run_tokens(vits_handle *h, const int64_t *d_ids, const int64_t *d_lens, int 
         conv(c, m.dp_pre, x, sHT, T, hb, sC, 0, nullptr, nullptr, 0, dp_cond, m.dp_cond_rows);
         if (!ddsconv(c, m.dp_convs, hb, y, y2, len, Cd, T, &m.dp_proj, m.dp_proj16, cond))
             conv(c, m.dp_proj, hb, sC, T, cond, sC, EPI_MASK, len);
-        // z = randn * noise_scale_w (models.py:111)
+        // z = randn * noise_scale_w (models.py:111), per utterance: +0.0 where noise_w is 0
         int64_t nz = (int64_t)B * 2 * T;
-        if (noise_w == 0.f) {
+        if (!rr.any(B, 2)) {
             c.note(hipMemsetAsync(z, 0, nz * 4, st));
         } else if (d_noise_dp) {
-            scale_kernel<<<(unsigned)((nz + 255) / 256), 256, 0, st>>>(d_noise_dp, z, noise_w, nz);
+            scale_kernel<<<(unsigned)((nz + 255) / 256), 256, 0, st>>>(d_noise_dp, z, noise_w, rr.d_rows, 2, 2 * T, nz);
+        } else if (rr.d_seeds) {
+            fill_normal_rows_kernel<<<dim3((unsigned)(((T + 3) / 4 + 63) / 64), 2, B), 64, 0, st>>>(z, T, rr.d_seeds, 1u,
+                                                                                                rr.d_rows, 2);
         } else {
             fill_normal_kernel<<<(unsigned)((nz / 4 + 256) / 256), 256, 0, st>>>(z, nz, seed, 1);
-            scale_kernel<<<(unsigned)((nz + 255) / 256), 256, 0, st>>>(z, z, noise_w, nz);
+            scale_kernel<<<(unsigned)((nz + 255) / 256), 256, 0, st>>>(z, z, noise_w, rr.d_rows, 2, 2 * T, nz);
         }
         h->stats.total_launches += 2;
         int swapped = 0;  // logical channel 0 lives in physical channel `swapped`
@@ -1233,7 +1265,7 @@ int run_tokens(vits_handle *h, const int64_t *d_ids, const int64_t *d_lens, int 
         conv(c, m.dpp_proj, h2, sF, T, h->d_logw, T, PRO_MASK | EPI_MASK, len);
     }
     // ---- durations (models.py:702-704)
-    duration_kernel<<<B, 256, 0, st>>>(h->d_logw, len, scales[1], h->d_wceil, h->d_cum, h->d_ylen, T);
+    duration_kernel<<<B, 256, 0, st>>>(h->d_logw, len, rr.at(0, 1), rr.d_rows, h->d_wceil, h->d_cum, h->d_ylen, T);
     h->stats.total_launches++;
     c.note(hipGetLastError());
     if (c.err != hipSuccess) return fail(h, VITS_E_DEVICE, "kernel launch failed: %s", hipGetErrorString(c.err));
@@ -1784,7 +1816,7 @@ size_t frames_ws_bytes(const Model &m, int B, int F, int Fgen) {
     return need;
 }
 
-int run_frames(vits_handle *h, int B, int T, const float *scales, const int64_t *d_sid, const float *d_noise_z,
+int run_frames(vits_handle *h, int B, int T, const RunRows &rr, const int64_t *d_sid, const float *d_noise_z,
                int64_t noise_z_stride, uint64_t seed, const ChunkSink *sink = nullptr) {
     const Model &m = h->model;
     const int C = m.C, Freal = h->F, Hf = m.flow_H;
@@ -1829,14 +1861,14 @@ int run_frames(vits_handle *h, int B, int T, const float *scales, const int64_t 
             c.flow_frac = fr / ((double)B * F);
         }
     }
-    const float noise_scale = scales[0];
+    const float noise_scale = rr.at(0, 0);
     const float *nz = nullptr;
     int64_t nzs = F;
-    if (noise_scale != 0.f) {
+    if (rr.any(B, 0)) {
         if (d_noise_z) {
             nz = d_noise_z;
             nzs = noise_z_stride;
-        } else {
+        } else if (!rr.d_seeds) {
             float *g = slab_take<float>(s, nCF);
             fill_normal_kernel<<<(unsigned)((nCF / 4 + 256) / 256), 256, 0, st>>>(g, (int64_t)nCF, seed, 2);
             h->stats.total_launches++;
@@ -1844,9 +1876,11 @@ int run_frames(vits_handle *h, int B, int T, const float *scales, const int64_t 
         }
     }
     // m_p / logs_p are the two halves of the proj output: channel stride T, batch stride 2*C*T
-    expand_prior_strided_kernel<<<dim3((F + 63) / 64, (C + 15) / 16, B), 64, 0, st>>>(h->d_mp, h->d_logs, (int64_t)2 * C * T, h->d_cum,
-                                                                       len, ylen, nz, nzs, noise_scale, zp, C, T, F,
-                                                                       nz == d_noise_z ? Freal : F);
+    // (with per-utterance seeds and no injected noise, the kernel draws each utterance's prior noise itself)
+    expand_prior_strided_kernel<<<dim3((F + 255) / 256, (C + 3) / 4, B), 64, 0, st>>>(h->d_mp, h->d_logs, (int64_t)2 * C * T, h->d_cum,
+                                                                        len, ylen, nz, nzs, noise_scale, rr.d_rows,
+                                                                        nz ? nullptr : rr.d_seeds, zp, C, T, F,
+                                                                        nz == d_noise_z ? Freal : F);
     h->stats.total_launches++;
     if (c.flow_len) {
         // z = z_p * y_mask: the ragged flow leaves the frames behind an utterance's end alone, where the reference's couplings
@@ -2234,11 +2268,33 @@ int vits_reserve(vits_handle *h, int B, int T, int F) {
     return VITS_OK;
 }
 
+// the settings of a run: one [3] vector for the whole batch (the vits_run* entry points) ...
+static RunRows one_row(const float scales[3]) {
+    RunRows rr;
+    rr.scales = scales;
+    return rr;
+}
+
+// ... or a host [B][3] row and optionally a host [B] seed per utterance (vits_run_*_rows): every value finite, checked on
+// the host before anything is enqueued; otherwise the rows accept what the [3] vector does
+static int host_rows(vits_handle *h, const float *scales, int B, const uint64_t *seeds, RunRows &rr) {
+    if (!scales) return fail(h, VITS_E_ARG, "null argument");
+    for (int b = 0; b < B; b++) {
+        const float *r = scales + (int64_t)b * 3;
+        if (!std::isfinite(r[0]) || !std::isfinite(r[1]) || !std::isfinite(r[2]))
+            return fail(h, VITS_E_ARG, "scales row %d = [%g, %g, %g] is not finite", b, (double)r[0], (double)r[1], (double)r[2]);
+    }
+    rr.scales = scales;
+    rr.rows = true;
+    rr.seeds = seeds;
+    return VITS_OK;
+}
+
 static int run_device_locked(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T,
-                             const float scales[3], const int64_t *sid, const vits_noise *noise, vits_output *out,
+                             RunRows rr, const int64_t *sid, const vits_noise *noise, vits_output *out,
                              const ChunkSink *sink = nullptr) {
     if (B <= 0 || T <= 0) return fail(h, VITS_E_ARG, "empty batch or sequence (B=%d, T=%d)", B, T);
-    if (!ids || !lens || !scales || (!out && !sink)) return fail(h, VITS_E_ARG, "null argument");
+    if (!ids || !lens || !rr.scales || (!out && !sink)) return fail(h, VITS_E_ARG, "null argument");
     if (h->model.gin && !sid) return fail(h, VITS_E_ARG, "Missing speaker id");
     std::memset(&h->stats, 0, sizeof h->stats);
     h->conv_events_used = 0;
@@ -2250,9 +2306,9 @@ static int run_device_locked(vits_handle *h, const int64_t *ids, const int64_t *
     seed = seed * 0x9E3779B97F4A7C15ull + (++h->run_counter);
     // (run_tokens' one synchronisation also completes the previous run on this handle: its range verdict, if nobody
     // asked for it yet, is looked at there, before this run's guard slots are cleared)
-    if (int rc = run_tokens(h, ids, lens, B, T, scales, sid, noise ? noise->noise_dp : nullptr, seed)) return rc;
+    if (int rc = run_tokens(h, ids, lens, B, T, rr, sid, noise ? noise->noise_dp : nullptr, seed)) return rc;
     range_begin(h);
-    if (int rc = run_frames(h, B, T, scales, sid, noise ? noise->noise_z : nullptr, noise ? noise->noise_z_stride : 0,
+    if (int rc = run_frames(h, B, T, rr, sid, noise ? noise->noise_z : nullptr, noise ? noise->noise_z_stride : 0,
                             seed, sink))
         return rc;
     ylen_to_i64<<<(B + 63) / 64, 64, 0, h->stream>>>(h->d_ylen, h->d_ylen64, B);
@@ -2273,7 +2329,17 @@ int vits_run_device(vits_handle *h, const int64_t *ids, const int64_t *lens, int
     if (int rc = check_dev(h)) return rc;
     std::lock_guard<std::mutex> lk(h->mu);
     if (!out) return fail(h, VITS_E_ARG, "null argument");
-    return run_device_locked(h, ids, lens, B, T, scales, sid, noise, out);
+    return run_device_locked(h, ids, lens, B, T, one_row(scales), sid, noise, out);
+}
+
+int vits_run_device_rows(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const float *scales,
+                         const int64_t *sid, const vits_noise *noise, const uint64_t *seeds, vits_output *out) {
+    if (int rc = check_dev(h)) return rc;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!out) return fail(h, VITS_E_ARG, "null argument");
+    RunRows rr;
+    if (int rc = host_rows(h, scales, B, seeds, rr)) return rc;
+    return run_device_locked(h, ids, lens, B, T, rr, sid, noise, out);
 }
 
 int vits_last_y_lengths(vits_handle *h, int64_t *buf, int n) {
@@ -2373,12 +2439,12 @@ static int stage_inputs(vits_handle *h, const int64_t *ids, const int64_t *lens,
 
 // host inputs in; returns once everything is enqueued (the mid-pipeline frame-count readback has completed, and with it
 // the input copies: the caller's buffers are free)
-static int run_async_locked(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const float scales[3],
+static int run_async_locked(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const RunRows &rr,
                             const int64_t *sid, const vits_noise *noise, vits_output *dev) {
-    if (!scales) return fail(h, VITS_E_ARG, "null argument");
+    if (!rr.scales) return fail(h, VITS_E_ARG, "null argument");
     Staged sg;
     int rc = stage_inputs(h, ids, lens, B, T, sid, noise, sg);
-    if (rc == VITS_OK) rc = run_device_locked(h, sg.d_ids, sg.d_lens, B, T, scales, sg.d_sid, sg.has_noise ? &sg.dn : nullptr, dev);
+    if (rc == VITS_OK) rc = run_device_locked(h, sg.d_ids, sg.d_lens, B, T, rr, sg.d_sid, sg.has_noise ? &sg.dn : nullptr, dev);
     if (rc != VITS_OK) hipStreamSynchronize(h->stream);  // the staging slab is reused by the next call
     return rc;
 }
@@ -2388,7 +2454,17 @@ int vits_run_async(vits_handle *h, const int64_t *ids, const int64_t *lens, int 
     if (int rc = check_dev(h)) return rc;
     std::lock_guard<std::mutex> lk(h->mu);
     vits_output dev{};
-    return run_async_locked(h, ids, lens, B, T, scales, sid, noise, &dev);
+    return run_async_locked(h, ids, lens, B, T, one_row(scales), sid, noise, &dev);
+}
+
+int vits_run_async_rows(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const float *scales,
+                        const int64_t *sid, const vits_noise *noise, const uint64_t *seeds) {
+    if (int rc = check_dev(h)) return rc;
+    std::lock_guard<std::mutex> lk(h->mu);
+    RunRows rr;
+    if (int rc = host_rows(h, scales, B, seeds, rr)) return rc;
+    vits_output dev{};
+    return run_async_locked(h, ids, lens, B, T, rr, sid, noise, &dev);
 }
 
 int vits_run(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const float scales[3],
@@ -2397,7 +2473,7 @@ int vits_run(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int
     std::lock_guard<std::mutex> lk(h->mu);
     hipStream_t st = h->stream;
     vits_output dev{};
-    int rc = run_async_locked(h, ids, lens, B, T, scales, sid, noise, &dev);  // (out == NULL: run only)
+    int rc = run_async_locked(h, ids, lens, B, T, one_row(scales), sid, noise, &dev);  // (out == NULL: run only)
     if (rc == VITS_OK && !out) {
         // run only: the caller fetches what it needs afterwards (vits_last_pcm16, vits_last_y_lengths, vits_tap)
         if (hipStreamSynchronize(st) != hipSuccess)
@@ -2428,21 +2504,36 @@ int vits_run(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int
     return rc;
 }
 
-int vits_run_chunked(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const float scales[3],
-                     const int64_t *sid, const vits_noise *noise, int chunk_frames, vits_chunk_fn fn, void *user) {
-    if (int rc = check_dev(h)) return rc;
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (!scales || chunk_frames < 1) return fail(h, VITS_E_ARG, "bad chunked-run arguments");
+static int run_chunked_locked(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const RunRows &rr,
+                              const int64_t *sid, const vits_noise *noise, int chunk_frames, vits_chunk_fn fn, void *user) {
+    if (!rr.scales || chunk_frames < 1) return fail(h, VITS_E_ARG, "bad chunked-run arguments");
     Staged sg;
     int rc = stage_inputs(h, ids, lens, B, T, sid, noise, sg);
     const ChunkSink sink{chunk_frames, fn, user};
     if (rc == VITS_OK)
-        rc = run_device_locked(h, sg.d_ids, sg.d_lens, B, T, scales, sg.d_sid, sg.has_noise ? &sg.dn : nullptr, nullptr, &sink);
+        rc = run_device_locked(h, sg.d_ids, sg.d_lens, B, T, rr, sg.d_sid, sg.has_noise ? &sg.dn : nullptr, nullptr, &sink);
     if (hipStreamSynchronize(h->stream) != hipSuccess && rc == VITS_OK)
         rc = fail(h, VITS_E_DEVICE, "synchronisation failed: %s", hipGetErrorString(hipGetLastError()));
     // (chunks are handed out as they finish; a range violation is therefore reported after the fact)
     if (rc == VITS_OK) rc = range_check(h);
     return rc;
+}
+
+int vits_run_chunked(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const float scales[3],
+                     const int64_t *sid, const vits_noise *noise, int chunk_frames, vits_chunk_fn fn, void *user) {
+    if (int rc = check_dev(h)) return rc;
+    std::lock_guard<std::mutex> lk(h->mu);
+    return run_chunked_locked(h, ids, lens, B, T, one_row(scales), sid, noise, chunk_frames, fn, user);
+}
+
+int vits_run_chunked_rows(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const float *scales,
+                          const int64_t *sid, const vits_noise *noise, const uint64_t *seeds, int chunk_frames,
+                          vits_chunk_fn fn, void *user) {
+    if (int rc = check_dev(h)) return rc;
+    std::lock_guard<std::mutex> lk(h->mu);
+    RunRows rr;
+    if (int rc = host_rows(h, scales, B, seeds, rr)) return rc;
+    return run_chunked_locked(h, ids, lens, B, T, rr, sid, noise, chunk_frames, fn, user);
 }
 
 void vits_free_output(vits_handle *h, vits_output *out) {

@@ -141,6 +141,46 @@ class ModelMeta:
         self.graph_name = "vits"
 
 
+def _settings(scales, B, seeds=None):
+    """Per-utterance synthesis settings of a batch call: `scales` float32 [3] (every utterance) or [B, 3] (utterance b:
+    row b = [noise_scale, length_scale, noise_w]), `seeds` None or B integers in [0, 2^64) (each utterance's own noise
+    stream, vitsmi.h).  Returns (scales, seeds as uint64 [B] or None); raises SessionError before anything reaches the
+    device."""
+    scales = np.ascontiguousarray(scales)
+    if scales.dtype != np.float32 or scales.shape not in ((3,), (B, 3)):
+        raise SessionError("Unexpected input: 'scales' must be float32 of shape [3] or [batch_size, 3]")
+    if scales.ndim == 2:
+        bad = np.flatnonzero(~np.isfinite(scales).all(axis=1))
+        if bad.size:
+            raise SessionError(f"scales row {int(bad[0])} = {scales[bad[0]].tolist()} is not finite")
+    if seeds is None:
+        return scales, None
+    arr = np.asarray(seeds)
+    if arr.shape != (B,) or not (arr.dtype.kind in "iu" or (arr.dtype == object and all(isinstance(v, int) for v in arr))):
+        raise SessionError("Unexpected input: 'seeds' must be integers of shape [batch_size]")
+    if arr.dtype != np.uint64:
+        vals = [int(v) for v in arr]
+        if any(v < 0 or v >= 1 << 64 for v in vals):
+            raise SessionError("Unexpected input: 'seeds' must lie in [0, 2^64)")
+        arr = np.array(vals, dtype=np.uint64)
+    return scales, np.ascontiguousarray(arr)
+
+
+def _rows(scales, B):
+    """[3] -> [B, 3] (the row twins of the C ABI take one row per utterance)"""
+    return np.ascontiguousarray(np.broadcast_to(scales, (B, 3)) if scales.ndim == 1 else scales, np.float32)
+
+
+def _part(scales, seeds, b0, b1):
+    """The settings of rows [b0, b1) of a batch (a [3] vector is every part's)."""
+    return (scales[b0:b1] if np.ndim(scales) == 2 else scales), (None if seeds is None else seeds[b0:b1])
+
+
+def _device_settings(scales, B, seeds):
+    """run_device's [B, 3] rows or seeds, checked like synthesize_batch's (float32: run_device always converted scales)."""
+    return _settings(np.ascontiguousarray(scales, np.float32), B, seeds)
+
+
 class MiSession:
     def __init__(self, path_or_bytes, sess_options=None, providers=None, provider_options=None, device_id: int = 0,
                  arena_device_ptr: Optional[int] = None, arena_bytes: int = 0, host_only: bool = False,
@@ -309,6 +349,8 @@ class MiSession:
             if lg.dtype != np.int64 or lg.shape != (np.asarray(input_feed["input"]).shape[0],):
                 raise SessionError("Unexpected input: 'langid' must be int64 of shape [batch_size]")
         scales = input_feed["scales"] if "scales" in self._input_names else np.array([0.667, 1.0, 0.8], np.float32)
+        if np.shape(scales) != (3,):  # (the graph's declaration, get_inputs(); [B, 3] rows are synthesize_batch's extension)
+            raise SessionError("Unexpected input: 'scales' must be float32 of shape [3]")
         out = self.synthesize_batch(input_feed["input"], input_feed["input_lengths"], scales, input_feed.get("sid"))
         return [out["output"]]
 
@@ -318,19 +360,20 @@ class MiSession:
         RandomNormalLike nodes (models.py:111, :718)."""
         self._seed = int(seed)
 
-    def synthesize_batch(self, ids, lens, scales, sid=None, noise_dp=None, noise_z=None, taps=()):
+    def synthesize_batch(self, ids, lens, scales, sid=None, noise_dp=None, noise_z=None, taps=(), seeds=None):
         """One batched run.  Returns {"output": [B,1,1,S] float32, "y_lengths": int64 [B], taps...}.
-        noise_dp [B,2,T] / noise_z [B,inter,>=F] inject the graph's noise for parity runs."""
+        noise_dp [B,2,T] / noise_z [B,inter,>=F] inject the graph's noise for parity runs.
+        scales: float32 [3] for every utterance, or [B, 3] - utterance b's own [noise_scale, length_scale, noise_w];
+        seeds: None (the session's stream, set_seed) or B integers - utterance b's own noise stream, which does not
+        depend on the rest of the batch (vitsmi.h, vits_run_async_rows)."""
         ids = np.ascontiguousarray(ids)
         lens = np.ascontiguousarray(lens)
-        scales = np.ascontiguousarray(scales)
         if ids.dtype != np.int64 or lens.dtype != np.int64:
             raise SessionError("Unexpected input data type: 'input'/'input_lengths' must be tensor(int64)")
-        if scales.dtype != np.float32 or scales.shape != (3,):
-            raise SessionError("Unexpected input: 'scales' must be float32 of shape [3]")
         if ids.ndim != 2 or lens.ndim != 1 or lens.shape[0] != ids.shape[0]:
             raise SessionError(f"Invalid rank/shape for input: {ids.shape} / input_lengths: {lens.shape}")
         B, T = ids.shape
+        scales, seeds = _settings(scales, B, seeds)
         if sid is not None:
             sid = np.ascontiguousarray(sid)
             if sid.dtype != np.int64 or sid.shape != (B,):
@@ -350,24 +393,30 @@ class MiSession:
             noise.noise_z_stride = noise_z.shape[2]
         with self._locked():  # enqueue -> frame counts -> copy-out -> taps all use this handle's one workspace
             try:
-                self._begin(ids, lens, scales, sid, noise)
+                self._begin(ids, lens, scales, sid, noise, seeds)
                 ylen = self.last_y_lengths()
                 S = int(ylen.max()) * self.hparam("hop")
                 audio = _POOL.array((B, 1, 1, S)) if self.pinned_results else np.empty((B, 1, 1, S), np.float32)
                 self._fetch(audio, 0, B)
             except RangeError as exc:
                 self._fall_back_to_bf16x6(exc)
-                return self.synthesize_batch(ids, lens, scales, sid, noise_dp, noise_z, taps)
+                return self.synthesize_batch(ids, lens, scales, sid, noise_dp, noise_z, taps, seeds=seeds)
             res = {"output": audio, "y_lengths": ylen}
             for t in taps:
                 res[t] = self.tap(t)
             return res
 
-    def _begin(self, ids, lens, scales, sid, noise):
-        """vits_run_async: validated host arrays in, the whole path enqueued; frame counts are known on return."""
+    def _begin(self, ids, lens, scales, sid, noise, seeds=None):
+        """vits_run_async: validated host arrays in, the whole path enqueued; frame counts are known on return.
+        ([B, 3] scales or seeds: vits_run_async_rows.)"""
         B, T = ids.shape
-        rc = self._lib.vits_run_async(self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(scales), _ffi.ptr(sid),
-                                      C.byref(noise))
+        if scales.ndim == 1 and seeds is None:
+            rc = self._lib.vits_run_async(self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(scales), _ffi.ptr(sid),
+                                          C.byref(noise))
+        else:
+            rows = _rows(scales, B)
+            rc = self._lib.vits_run_async_rows(self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(rows), _ffi.ptr(sid),
+                                               C.byref(noise), _ffi.ptr(seeds))
         if rc != 0:
             self._raise("vits_run", rc)
 
@@ -469,17 +518,18 @@ class MiSession:
             stop.set()
             t.join()
 
-    def synthesize_stream(self, ids, lens, scales, sid=None, chunk_frames: int = 64, noise_dp=None, noise_z=None):
+    def synthesize_stream(self, ids, lens, scales, sid=None, chunk_frames: int = 64, noise_dp=None, noise_z=None,
+                          seeds=None):
         """The whole path with the waveform delivered in chunks of `chunk_frames` frames (hop samples each): yields
         (first_sample, float32 [B, n], total_samples).  Concatenated, the chunks are bit-identical to
         synthesize_batch(...)["output"][:, 0, 0, :]; frame counts afterwards from last_y_lengths().  Chunks are handed out
         as they finish, so a range violation of the f16x3 arithmetic cannot be repaired by a silent re-run: it raises
         RangeError at the end (no bf16x6 fallback here; reopen with gen_precision="bf16x6").  Closing the generator
-        early stops the engine after the chunk in flight."""
+        early stops the engine after the chunk in flight.  scales [3] or [B, 3] and seeds as synthesize_batch."""
         ids = np.ascontiguousarray(ids, np.int64)
         lens = np.ascontiguousarray(lens, np.int64)
-        scales = np.ascontiguousarray(scales, np.float32)
         B, T = ids.shape
+        scales, seeds = _settings(np.ascontiguousarray(scales, np.float32), B, seeds)
         sid = None if sid is None else np.ascontiguousarray(sid, np.int64)
         noise = _ffi.VitsNoise()
         noise.seed = self._seed
@@ -491,8 +541,13 @@ class MiSession:
             keep.append(np.ascontiguousarray(noise_z, np.float32))
             noise.noise_z = keep[-1].ctypes.data
             noise.noise_z_stride = keep[-1].shape[2]
-        return self._stream(lambda cb: self._lib.vits_run_chunked(
-            self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(scales), _ffi.ptr(sid), C.byref(noise),
+        if scales.ndim == 1 and seeds is None:
+            return self._stream(lambda cb: self._lib.vits_run_chunked(
+                self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(scales), _ffi.ptr(sid), C.byref(noise),
+                int(chunk_frames), cb, None))
+        rows = _rows(scales, B)
+        return self._stream(lambda cb: self._lib.vits_run_chunked_rows(
+            self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(rows), _ffi.ptr(sid), C.byref(noise), _ffi.ptr(seeds),
             int(chunk_frames), cb, None))
 
     def vocoder_stream(self, z, sid=None, chunk_frames: int = 64):
@@ -586,7 +641,8 @@ class MiSession:
 
     # device-resident run for the benchmark / sharded path: arguments are device pointers (ints)
     def run_device(self, ids_ptr, lens_ptr, B, T, scales, sid_ptr=None, noise_dp_ptr=None, noise_z_ptr=None,
-                   noise_z_stride=0):
+                   noise_z_stride=0, seeds=None):
+        """scales: host float32 [3] or [B, 3]; seeds: None or B host integers (as synthesize_batch)."""
         scales = np.ascontiguousarray(scales, np.float32)
         noise = _ffi.VitsNoise()
         noise.seed = self._seed
@@ -594,8 +650,15 @@ class MiSession:
         noise.noise_z = noise_z_ptr
         noise.noise_z_stride = noise_z_stride
         out = _ffi.VitsOutput()
-        rc = self._lib.vits_run_device(self._h, C.c_void_p(ids_ptr), C.c_void_p(lens_ptr), B, T, _ffi.ptr(scales),
-                                       C.c_void_p(sid_ptr) if sid_ptr else None, C.byref(noise), C.byref(out))
+        if scales.ndim == 1 and seeds is None:
+            rc = self._lib.vits_run_device(self._h, C.c_void_p(ids_ptr), C.c_void_p(lens_ptr), B, T, _ffi.ptr(scales),
+                                           C.c_void_p(sid_ptr) if sid_ptr else None, C.byref(noise), C.byref(out))
+        else:
+            scales, seeds = _device_settings(scales, B, seeds)
+            rows = _rows(scales, B)
+            rc = self._lib.vits_run_device_rows(self._h, C.c_void_p(ids_ptr), C.c_void_p(lens_ptr), B, T, _ffi.ptr(rows),
+                                                C.c_void_p(sid_ptr) if sid_ptr else None, C.byref(noise), _ffi.ptr(seeds),
+                                                C.byref(out))
         if rc != 0:
             self._raise("vits_run_device", rc)
         dims = tuple(out.dims[i] for i in range(4))
@@ -743,20 +806,25 @@ class PipelinedSession:
         n = min(len(self.parts), B)
         return [B * i // n for i in range(n + 1)]
 
-    def run_device(self, ids_ptr, lens_ptr, B, T, scales, sid_ptr=None):
+    def run_device(self, ids_ptr, lens_ptr, B, T, scales, sid_ptr=None, seeds=None):
         """Device pointers in (rows of one [B, T] int64 tensor / [B] tensors); enqueues every sub-batch on its own
         stream and returns [(first_row, rows, MiSession.run_device result)] - the waveform of a part stays in that
-        part's workspace.  Call sync() before reading."""
+        part's workspace.  Call sync() before reading.  scales (host) [3] or [B, 3] and seeds as MiSession.run_device:
+        each part gets its own rows."""
+        rows = seeds is not None or np.ndim(scales) == 2   # (else: every part is called exactly as before)
+        if rows:
+            scales, seeds = _device_settings(scales, B, seeds)
         out = []
         bnd = self.bounds(B)
         for i in range(len(bnd) - 1):
             b0, nb = bnd[i], bnd[i + 1] - bnd[i]
-            r = self.parts[i].run_device(ids_ptr + b0 * T * 8, lens_ptr + b0 * 8, nb, T, scales,
-                                         sid_ptr + b0 * 8 if sid_ptr else None)
+            sc, sd = _part(scales, seeds, b0, b0 + nb)
+            r = self.parts[i].run_device(ids_ptr + b0 * T * 8, lens_ptr + b0 * 8, nb, T, sc,
+                                         sid_ptr + b0 * 8 if sid_ptr else None, **({"seeds": sd} if rows else {}))
             out.append((b0, nb, r))
         return out
 
-    def run_device_steps(self, ids_ptr, lens_ptr, B, T, scales, steps, sid_ptr=None, alternate=False):
+    def run_device_steps(self, ids_ptr, lens_ptr, B, T, scales, steps, sid_ptr=None, alternate=False, seeds=None):
         """`steps` back-to-back passes over the same device-resident batch with one host thread per part, as two
         serving workers would run: a part goes on to its next pass without waiting for the other one, and part i
         starts once part i-1 has handed its first generator to the GPU, so that the small-grid stages of one part
@@ -766,8 +834,11 @@ class PipelinedSession:
         alternate=True: WHOLE passes are dealt to the parts in turn (pass k on part k mod n: request-level pipelining, each
         worker renders complete batches) - the generator keeps the full batch's grids (a sub-batch of 11 leaves the default
         voice's 128-channel stage at 283 workgroups on 512 slots), while pass k + 1's token and frame stages still fall
-        under pass k's generator on the other handle."""
+        under pass k's generator on the other handle.  scales [3] or [B, 3] and seeds as run_device."""
         import threading
+        rows = seeds is not None or np.ndim(scales) == 2   # (else: every part is called exactly as before)
+        if rows:
+            scales, seeds = _device_settings(scales, B, seeds)
         bnd = self.bounds(B)
         n = len(bnd) - 1
         out = np.zeros((steps, B), np.int64)
@@ -781,16 +852,17 @@ class PipelinedSession:
                     started[i - 1].wait()
                 if alternate:
                     for k in range(i, steps, n):
-                        self.parts[i].run_device(ids_ptr, lens_ptr, B, T, scales, sid_ptr)
+                        self.parts[i].run_device(ids_ptr, lens_ptr, B, T, scales, sid_ptr, **({"seeds": seeds} if rows else {}))
                         started[i].set()
                         out[k, :] = self.parts[i].last_y_lengths()
                         stamps[k] = time.perf_counter()
                     self.parts[i].sync()
                     return
                 b0, nb = bnd[i], bnd[i + 1] - bnd[i]
+                sc, sd = _part(scales, seeds, b0, b0 + nb)
                 for k in range(steps):
-                    self.parts[i].run_device(ids_ptr + b0 * T * 8, lens_ptr + b0 * 8, nb, T, scales,
-                                             sid_ptr + b0 * 8 if sid_ptr else None)
+                    self.parts[i].run_device(ids_ptr + b0 * T * 8, lens_ptr + b0 * 8, nb, T, sc,
+                                             sid_ptr + b0 * 8 if sid_ptr else None, **({"seeds": sd} if rows else {}))
                     started[i].set()
                     out[k, b0:b0 + nb] = self.parts[i].last_y_lengths()
                 self.parts[i].sync()
@@ -815,8 +887,9 @@ class PipelinedSession:
         n = len(self.bounds(B)) - 1
         return np.concatenate([self.parts[i].last_y_lengths() for i in range(n)])
 
-    def synthesize_batch(self, ids, lens, scales, sid=None):
-        """Host arrays in, host arrays out, like MiSession.synthesize_batch.  One worker thread per sub-batch (the C
+    def synthesize_batch(self, ids, lens, scales, sid=None, seeds=None):
+        """Host arrays in, host arrays out, like MiSession.synthesize_batch (scales [3] or [B, 3], seeds: each part gets its
+        own rows of both).  One worker thread per sub-batch (the C
         calls release the GIL): each enqueues its part (vits_run_async), learns its frame counts, meets the others at a
         barrier where the ONE [B,1,1,S_max] result array (pinned host memory) is sized, then waits for its own render
         and lets the DMA engine write its rows straight into that array (vits_fetch_output) - the copy-out of a part
@@ -824,20 +897,18 @@ class PipelinedSession:
         import threading
         ids = np.ascontiguousarray(ids)
         lens = np.ascontiguousarray(lens)
-        scales = np.ascontiguousarray(scales)
         if ids.dtype != np.int64 or lens.dtype != np.int64 or ids.ndim != 2 or lens.shape != (ids.shape[0],):
             raise SessionError("Unexpected input: 'input' int64 [B,T], 'input_lengths' int64 [B]")
-        if scales.dtype != np.float32 or scales.shape != (3,):
-            raise SessionError("Unexpected input: 'scales' must be float32 of shape [3]")
         B = ids.shape[0]
+        scales, seeds = _settings(scales, B, seeds)
         if sid is not None:
             sid = np.ascontiguousarray(sid)
             if sid.dtype != np.int64 or sid.shape != (B,):
                 raise SessionError("Unexpected input: 'sid' must be int64 of shape [batch_size]")
         with self._mu:
-            return self._synthesize_batch_locked(ids, lens, scales, sid, B)
+            return self._synthesize_batch_locked(ids, lens, scales, sid, B, seeds)
 
-    def _synthesize_batch_locked(self, ids, lens, scales, sid, B):
+    def _synthesize_batch_locked(self, ids, lens, scales, sid, B, seeds=None):
         import threading
         bnd = self.bounds(B)
         n = len(bnd) - 1
@@ -860,7 +931,8 @@ class PipelinedSession:
                 noise = _ffi.VitsNoise()
                 noise.seed = p._seed
                 with p._mu:  # (a part may also be used on its own, e.g. bench.py's measure(): same per-session lock)
-                    p._begin(ids[b0:b1], lens[b0:b1], scales, None if sid is None else sid[b0:b1], noise)
+                    sc, sd = _part(scales, seeds, b0, b1)
+                    p._begin(ids[b0:b1], lens[b0:b1], sc, None if sid is None else sid[b0:b1], noise, sd)
                     ylen[b0:b1] = p.last_y_lengths()
                     bar.wait()
                     p._fetch(box["out"], b0, b1 - b0)
@@ -882,7 +954,7 @@ class PipelinedSession:
             rng = [e for e in errors if isinstance(e, RangeError)]
             if rng:
                 self._fall_back(rng[0])
-                return self.synthesize_batch(ids, lens, scales, sid)
+                return self.synthesize_batch(ids, lens, scales, sid, seeds=seeds)
             raise errors[0]
         return {"output": box["out"], "y_lengths": ylen}
 

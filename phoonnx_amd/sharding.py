@@ -156,29 +156,50 @@ class ShardedSynthesizer:
         self.hop = self.session.hparam("hop")
 
     def synthesize(self, utterances: Sequence[Sequence[int]], scales, sids: Optional[Sequence[int]] = None,
-                   gather=False, dst: int = 0):
+                   gather=False, dst: int = 0, seeds: Optional[Sequence[int]] = None):
         """This rank's shard of the request, rendered.
+        scales: float32 [3] for every utterance or [N, 3] (row i: utterance i's [noise_scale, length_scale, noise_w]);
+        seeds: None or N integers (utterance i's own noise stream, MiSession.synthesize_batch) - both follow the utterances
+        to their ranks.
         gather=False: [(original index, waveform)] of this rank's utterances - results stay where they were made.
         gather=True:  every rank returns every utterance's waveform in the original order.
         gather="root": only rank `dst` does (the others return None) - what a front end that answers one client wants.
         The gathers move tensors, not pickles: one small all_gather of the sample counts, then ONE collective over flat
         fp32 buffers (every rank's valid samples back to back, padded to the longest rank) - on the device over RCCL/xGMI
         when the backend is nccl, on the host with gloo."""
+        # the request's arguments are checked whole, on every rank, before anything is dealt: a rank that failed alone here
+        # would leave its peers waiting in the gather's collectives
+        scales = np.asarray(scales, np.float32)
+        if scales.shape not in ((3,), (len(utterances), 3)):
+            raise ValueError(f"scales must be [3] or [{len(utterances)}, 3], got {list(scales.shape)}")
+        if seeds is not None:
+            if len(seeds) != len(utterances):
+                raise ValueError(f"seeds must hold one seed per utterance ({len(utterances)}), got {len(seeds)}")
+            bad = [i for i, v in enumerate(seeds) if not isinstance(v, (int, np.integer)) or not 0 <= int(v) < 1 << 64]
+            if bad:
+                raise ValueError(f"seeds[{bad[0]}] = {seeds[bad[0]]!r} is not an integer in [0, 2^64)")
+            seeds = np.asarray([int(v) for v in seeds], np.uint64)
         shards, inv = partition([len(u) for u in utterances], self.world)
         mine = shards[self.rank]
-        scales = np.asarray(scales, np.float32)
+        rows = scales.ndim == 2 or seeds is not None   # (else: the session is called exactly as before, four arguments)
+        if rows:   # this rank's utterances' own rows, in shard order
+            scales = scales if scales.ndim == 1 else np.ascontiguousarray(scales[mine])
+            seeds = None if seeds is None else np.ascontiguousarray(seeds[mine])
         # the device path speaks MiSession.run_device's result ({"data_ptr", "dims", "y_lengths_ptr"} of ONE handle): an
         # injected session (the documented contract is synthesize_batch + hparam only - PipelinedSession.run_device, for one,
         # returns a list of parts) takes the host path
         use_dev = bool(gather) and self.dist is not None and self.dist.get_backend() == "nccl" and isinstance(self.session, MiSession)
         if use_dev:
-            return self._gather_device(utterances, shards, mine, scales, sids, gather, dst)
+            return self._gather_device(utterances, shards, mine, scales, sids, gather, dst, seeds)
         local, failure = [], None
         try:
             if len(mine):
                 ids, lens = pad_batch([utterances[i] for i in mine])
                 sid = None if sids is None else np.asarray([sids[i] for i in mine], np.int64)
-                r = self.session.synthesize_batch(ids, lens, scales, sid)
+                if rows:
+                    r = self.session.synthesize_batch(ids, lens, scales, sid, seeds=seeds)
+                else:
+                    r = self.session.synthesize_batch(ids, lens, scales, sid)
                 for b in range(len(mine)):
                     n = int(r["y_lengths"][b]) * self.hop
                     local.append(r["output"][b, 0, 0, :n])
@@ -206,7 +227,7 @@ class ShardedSynthesizer:
             flat[:int(cnt.sum())] = torch.from_numpy(np.concatenate(local))
         return self._collect(flat, allcnt, shards, len(utterances), gather, dst)
 
-    def _gather_device(self, utterances, shards, mine, scales, sids, gather, dst):
+    def _gather_device(self, utterances, shards, mine, scales, sids, gather, dst, seeds=None):
         """nccl backend: the shard is rendered device to device (vits_run_device), its valid samples are packed back to back
         on the GPU straight out of the engine's output buffer, and that buffer goes into the collective - the waveform crosses
         PCIe once, on its way to whoever asked for it (the host path costs a D2H, an H2D and another D2H per rank)."""
@@ -228,7 +249,7 @@ class ShardedSynthesizer:
                 d_sid = None if sid is None else torch.from_numpy(sid).to(dev)
                 torch.cuda.synchronize(dev)   # (the engine runs on its own stream: the inputs are in place before it starts)
                 r = self.session.run_device(d_ids.data_ptr(), d_lens.data_ptr(), len(mine), ids.shape[1], scales,
-                                            None if d_sid is None else d_sid.data_ptr())
+                                            None if d_sid is None else d_sid.data_ptr(), seeds=seeds)
                 self.session.sync()           # ... and its output is complete before torch's stream reads it
                 B, S = int(r["dims"][0]), int(r["dims"][3])
                 out = torch.as_tensor(_DeviceArray(r["data_ptr"], (B, S)), device=dev)

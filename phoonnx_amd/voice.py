@@ -10,7 +10,9 @@ framing — including the reference's sentence-list duplication (voice.py:203-20
 reproduced by default and can be switched off with `dedupe_sentences=True`.
 
 Extensions: `synthesize(..., batch_sentences=True)` renders all
-sentences of a text in ONE batched engine call.
+sentences of a text in ONE batched engine call; `synthesize_requests()` renders the sentences
+of many requests, each with its own SynthesisConfig (and optionally its own noise seed), in
+shared batches.
 """
 import json
 import logging
@@ -18,7 +20,7 @@ import re
 import wave
 from dataclasses import dataclass
 from pathlib import Path
-from typing import Any, Iterable, List, Optional, Union
+from typing import Any, Iterable, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -30,6 +32,22 @@ LOG = logging.getLogger(__name__)
 
 _PHONEME_BLOCK = re.compile(r"(\[\[.*?\]\])")
 _MAX_WAV_VALUE = 32767.0
+_MASK64 = (1 << 64) - 1
+_GOLDEN64 = 0x9E3779B97F4A7C15
+
+
+def splitmix64(x: int) -> int:
+    """The splitmix64 output function of a 64-bit state (the generator's state after its increment)."""
+    z = x & _MASK64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _MASK64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _MASK64
+    return z ^ (z >> 31)
+
+
+def sentence_seed(request_seed: int, k: int) -> int:
+    """Noise seed of sentence k (0-based) of a request seeded with `request_seed`: output k + 1 of a splitmix64
+    generator started at request_seed, i.e. splitmix64(request_seed + (k + 1) * 0x9E3779B97F4A7C15 mod 2^64)."""
+    return splitmix64((int(request_seed) + (k + 1) * _GOLDEN64) & _MASK64)
 
 
 def config_from_metadata(meta: dict) -> dict:
@@ -212,6 +230,17 @@ class TTSVoice:
         single padded batch on the GPU instead of one engine call per sentence."""
         if syn_config is None:
             syn_config = SynthesisConfig()
+        all_ids = self._sentence_ids(text, syn_config)
+        if batch_sentences and len(all_ids) > 1 and hasattr(self.session, "synthesize_batch"):
+            audios = self.phoneme_ids_batch_to_audio(all_ids, syn_config)
+        else:
+            audios = (self.phoneme_ids_to_audio(ids, syn_config) for ids in all_ids)
+        for audio in audios:
+            yield AudioChunk(sample_rate=self.config.sample_rate, sample_width=2, sample_channels=1,
+                             audio_float_array=self._postprocess(audio, syn_config))
+
+    def _sentence_ids(self, text: str, syn_config: SynthesisConfig) -> List[List[int]]:
+        """synthesize()'s front end: phonetic spellings, diacritics, phonemize, ids - one non-empty id list per sentence."""
         LOG.debug("text=%s", text)
         if self.phonetic_spellings and syn_config.enable_phonetic_spellings:
             text = self.phonetic_spellings.apply(text)
@@ -220,14 +249,55 @@ class TTSVoice:
         sentence_phonemes = self.phonemize(text)
         LOG.debug("phonemes=%s", sentence_phonemes)
         all_ids = [self.phonemes_to_ids(p) for p in sentence_phonemes if p]
-        all_ids = [ids for ids in all_ids if ids]
-        if batch_sentences and len(all_ids) > 1 and hasattr(self.session, "synthesize_batch"):
-            audios = self.phoneme_ids_batch_to_audio(all_ids, syn_config)
-        else:
-            audios = (self.phoneme_ids_to_audio(ids, syn_config) for ids in all_ids)
-        for audio in audios:
-            yield AudioChunk(sample_rate=self.config.sample_rate, sample_width=2, sample_channels=1,
-                             audio_float_array=self._postprocess(audio, syn_config))
+        return [ids for ids in all_ids if ids]
+
+    def synthesize_requests(self, requests: Sequence[Tuple[str, Optional[SynthesisConfig]]],
+                            seeds: Optional[Sequence[int]] = None, max_batch: int = 32) -> List[List[AudioChunk]]:
+        """Extension: many independent requests (text, SynthesisConfig or None) rendered together.  Every sentence of
+        every request becomes one row of a batch with its request's own speaker, length / noise scales and (with `seeds`,
+        one integer per request) its own noise seed - sentence k of request r: sentence_seed(seeds[r], k); rows are sorted
+        by length and rendered max_batch at a time.  Returns, per request, what list(synthesize(text, cfg)) returns: one
+        AudioChunk per sentence, post-processed with that request's normalize_audio / volume.  With seeds, a request's
+        durations do not depend on which other requests share its batches (vitsmi.h, vits_run_async_rows).  A session
+        without synthesize_batch (the onnxruntime duck type) renders the requests one by one through synthesize()."""
+        if max_batch < 1:
+            raise ValueError(f"max_batch must be >= 1 (got {max_batch})")
+        if seeds is not None and len(seeds) != len(requests):
+            raise ValueError(f"seeds must hold one seed per request ({len(requests)}), got {len(seeds)}")
+        cfgs = [cfg if cfg is not None else SynthesisConfig() for _, cfg in requests]
+        expected = [i.name for i in self.session.get_inputs()]
+        if "sid" in expected:  # every request's speaker is checked before anything runs
+            n_spk = int(self.session.hparam("n_speakers")) if hasattr(self.session, "hparam") else self.config.num_speakers
+            for r, cfg in enumerate(cfgs):
+                spk = cfg.speaker_id or 0
+                if not 0 <= spk < max(n_spk, 1):
+                    raise ValueError(f"request {r}: speaker_id {spk} is out of range [0, {max(n_spk, 1)})")
+        if not hasattr(self.session, "synthesize_batch"):
+            return [list(self.synthesize(text, cfg)) for (text, _), cfg in zip(requests, cfgs)]
+        from .sharding import pad_batch
+        rows = []  # (request, sentence, ids)
+        for r, ((text, _), cfg) in enumerate(zip(requests, cfgs)):
+            rows.extend((r, k, ids) for k, ids in enumerate(self._sentence_ids(text, cfg)))
+        audio = {}
+        hop = self.session.hparam("hop")
+        order = sorted(range(len(rows)), key=lambda i: len(rows[i][2]))  # (stable: equal lengths keep request order)
+        for c0 in range(0, len(order), max_batch):
+            run = [rows[i] for i in order[c0:c0 + max_batch]]
+            ids, lens = pad_batch([ids for _, _, ids in run])
+            scales = np.stack([self._scales(cfgs[r]) for r, _, _ in run])
+            sid = np.asarray([cfgs[r].speaker_id or 0 for r, _, _ in run], np.int64) if "sid" in expected else None
+            if seeds is None:
+                out = self.session.synthesize_batch(ids, lens, scales, sid)
+            else:
+                row_seeds = np.asarray([sentence_seed(seeds[r], k) for r, k, _ in run], np.uint64)
+                out = self.session.synthesize_batch(ids, lens, scales, sid, seeds=row_seeds)
+            for b, (r, k, _) in enumerate(run):
+                audio[r, k] = out["output"][b, 0, 0, :int(out["y_lengths"][b]) * hop].copy()
+        result = [[] for _ in requests]
+        for r, k, _ in rows:  # (rows are in request, then sentence order)
+            result[r].append(AudioChunk(sample_rate=self.config.sample_rate, sample_width=2, sample_channels=1,
+                                        audio_float_array=self._postprocess(audio[r, k], cfgs[r])))
+        return result
 
     def synthesize_wav(self, text: str, wav_file: wave.Wave_write, syn_config: Optional[SynthesisConfig] = None,
                        set_wav_format: bool = True, batch_sentences: bool = False, device_pcm16: bool = False) -> None:
