@@ -232,9 +232,60 @@ int vits_run_chunked_rows(vits_handle *h, const int64_t *ids, const int64_t *len
                           const int64_t *sid, const vits_noise *noise, const uint64_t *seeds, int chunk_frames,
                           vits_chunk_fn fn, void *user);
 
+/* ---- timing control: forced durations and per-token rate ----------------------------------
+ * One definition of "duration": durations[b][t] is the integer number of frames token t of utterance b occupies - w_ceil of
+ * models.py:702-704 in a free run.  An utterance's frame count is max(1, sum_t durations[b][t]), and sample s belongs to
+ * frame s / hop (vits_hparam "hop").
+ *
+ * vits_controls carries everything a run can be steered with; vits_run_async_ctl / vits_run_chunked_ctl are
+ * vits_run_async_rows / vits_run_chunked_rows with the struct in the place of (scales, seeds).  With durations == NULL and
+ * token_rate == NULL they compute what those calls compute, bit for bit (they check lens[b] in [0, T] themselves, first).
+ *
+ * token_rate (host float32 [B][T]): a per-token multiplier on the predicted duration.  Token t < lens[b] of row b gets
+ *     w_ceil = ceilf(((expf(logw) * mask) * length_scale) * token_rate[b][t])
+ *   in exactly this order of fp32 operations.  So a rate of 1.0 everywhere gives the bits of a run without rates, and with
+ *   length_scale == 1.0 a rate r gives the bits the graph gives at length_scale = r.  Rates must be finite and >= 0; rate 0
+ *   drops the token (0 frames).  Positions behind lens[b] are ignored.
+ * durations (host int64 [B][T]): forced durations.  The duration predictor is NOT launched - neither the stochastic nor the
+ *   plain one: none of its convs, spline flows or noise - and one small kernel turns the array into what the free path
+ *   leaves behind (w_ceil as float, its inclusive prefix sums, the frame counts).  Everything behind it is the free path
+ *   unchanged: the frame-count readback, the expansion of the prior with rows and seeds, flow, generator, ragged tails and
+ *   chunking.  A forced run with the durations and seeds of a free run therefore returns that run's frame counts, z_p, z and
+ *   waveform bit for bit.  noise_dp, the rows' noise_w and length_scale are accepted and unused; positions behind lens[b]
+ *   are ignored (they read 0 afterwards).  After a forced run vits_tap("logw") returns VITS_E_ARG ("not computed in a
+ *   forced-duration run"), "w_ceil" gives the forced values, and vits_get_stats reports dp_flops == 0 and the launches
+ *   that were made.
+ * Validation happens on the host before anything is enqueued or allocated; the error is VITS_E_ARG and names row and
+ * token: a negative duration; a duration, or a running row sum, above the frames a forced run admits (below); a non-finite or
+ * negative rate;
+ * durations together with token_rate (contradictory).  A rejected call leaves the previous run's results readable.
+ * Not covered: the device-pointer entries (vits_run_device*), which keep their signatures. */
+/* Frames per utterance a forced run admits: min(VITS_MAX_FORCED_FRAMES, INT_MAX / hop).  The first keeps w_ceil exact in
+ * fp32 and the frame sums in int; the second keeps the utterance's SAMPLE count (frames * hop) in int as well (at hop 256:
+ * 8388607 frames).  A free run is not capped: its length is the model's. */
+#define VITS_MAX_FORCED_FRAMES (1 << 24)
+typedef struct {
+    const float *scales_rows;   /* host [B][3], as vits_run_async_rows; required */
+    const uint64_t *seeds;      /* host [B] or NULL */
+    const int64_t *durations;   /* host [B][T] or NULL: forced durations */
+    const float *token_rate;    /* host [B][T] or NULL: per-token multiplier on the predicted duration */
+} vits_controls;
+int vits_run_async_ctl(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
+                       const vits_noise *noise, const vits_controls *ctl);
+int vits_run_chunked_ctl(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
+                         const vits_noise *noise, const vits_controls *ctl, int chunk_frames, vits_chunk_fn fn, void *user);
+
 /* Frame counts of the last run, from the host copy made by the mid-pipeline readback
  * (no synchronisation).  Writes min(n, B) values, returns B. */
 int vits_last_y_lengths(vits_handle *h, int64_t *buf, int n);
+
+/* Durations [B][T] of the last run (free, rate-scaled or forced; the device-pointer runs included), from a host copy made
+ * by the same mid-pipeline readback: no synchronisation and no wait, valid as soon as vits_run_async* returns, and the
+ * consumer of a chunked run may call it from its callback while later chunks render.  Positions t >= lens[b] read 0;
+ * max(1, row sum) is vits_last_y_lengths.  Writes min(n_elems, B * T) values and returns B * T (buf may be NULL to ask for
+ * the size); VITS_E_ARG ("no completed run") before the first run, after a vits_reserve or a run that grew the token
+ * workspace without completing, and after vits_run_vocoder*, which has no tokens. */
+int vits_last_durations(vits_handle *h, int64_t *buf, size_t n_elems);
 
 /* synthesize()'s post-processing on the device, for the LAST run (phoonnx/voice.py:271-282 and AudioChunk,
  * voice.py:88-91): per utterance, over its y_lengths*hop valid samples: peak-normalise (if `normalize`),

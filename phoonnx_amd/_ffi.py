@@ -40,6 +40,10 @@ class VitsOpenOptions(C.Structure):
                 ("arena_bytes", C.c_size_t), ("host_only", C.c_int), ("layout_only", C.c_int)]
 
 
+class VitsControls(C.Structure):
+    _fields_ = [("scales_rows", C.c_void_p), ("seeds", C.c_void_p), ("durations", C.c_void_p), ("token_rate", C.c_void_p)]
+
+
 # int fn(void *user, const float *samples, int B, int64 first_sample, int64 n_samples, int64 total_samples)
 CHUNK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_int64, C.c_int64, C.c_int64)
 
@@ -57,6 +61,7 @@ EXPORTS = [
     "vits_test_conv_transpose1d_sx",
     "vits_bench_conv1d_sx", "vits_test_conv_pair_sx", "vits_fetch_output", "vits_run_async", "vits_host_alloc", "vits_host_free",
     "vits_launch_records", "vits_run_async_rows", "vits_run_device_rows", "vits_run_chunked_rows",
+    "vits_run_async_ctl", "vits_run_chunked_ctl", "vits_last_durations",
 ]
 
 
@@ -117,6 +122,11 @@ def load():
     lib.vits_run_async_rows.argtypes = run_args[:-1] + [vp]
     lib.vits_run_device_rows.argtypes = run_args[:-1] + [vp, C.POINTER(VitsOutput)]
     lib.vits_run_chunked_rows.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, C.POINTER(VitsNoise), vp, C.c_int, CHUNK_FN, vp]
+    # (controls twins: ids, lens, B, T, sid, noise, then the vits_controls struct in the place of scales / seeds)
+    lib.vits_run_async_ctl.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.POINTER(VitsNoise), C.POINTER(VitsControls)]
+    lib.vits_run_chunked_ctl.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.POINTER(VitsNoise), C.POINTER(VitsControls),
+                                         C.c_int, CHUNK_FN, vp]
+    lib.vits_last_durations.argtypes = [vp, i64p, C.c_size_t]
     lib.vits_free_output.argtypes = [vp, C.POINTER(VitsOutput)]
     lib.vits_free_output.restype = None
     lib.vits_sync.argtypes = [vp]

@@ -934,8 +934,10 @@ __global__ void add_bias_b_kernel(const float *in, float *out, const float *bias
 // ---- a9: durations (models.py:702-704): one block per utterance ----------------------------------
 // w = exp(logw)*mask*length_scale; w_ceil = ceil(w); cum = inclusive scan (ints); y_len = max(sum,1)
 // (length_scale: the utterance's row of `rows` when given)
+// token_rate (nullable, [B][T]): w_ceil = ceil(((exp(logw) * mask) * length_scale) * token_rate[b][t]) for t < len[b], in
+// exactly this order of fp32 operations (vitsmi.h, vits_controls); NULL is the code path without the last product.
 __global__ void duration_kernel(const float *logw, const int *len, float length_scale_all, const float *rows,
-                                float *w_ceil, int *cum, int *y_len, int T) {
+                                const float *token_rate, float *w_ceil, int *cum, int *y_len, int T) {
     __shared__ int sh[256];
     __shared__ int carry_s;
     int b = blockIdx.x, tid = threadIdx.x;
@@ -949,6 +951,7 @@ __global__ void duration_kernel(const float *logw, const int *len, float length_
         if (t < T) {
             float mk = t < L ? 1.f : 0.f;
             float w = expf(logw[(int64_t)b * T + t]) * mk * length_scale;
+            if (token_rate && t < L) w = w * token_rate[(int64_t)b * T + t];
             float c = ceilf(w);
             w_ceil[(int64_t)b * T + t] = c;
             v = (int)c;
@@ -968,6 +971,46 @@ __global__ void duration_kernel(const float *logw, const int *len, float length_
         __syncthreads();
     }
     if (tid == 0) y_len[b] = carry_s < 1 ? 1 : carry_s;
+}
+
+// Forced durations (vitsmi.h, vits_controls.durations): what duration_kernel leaves behind, from host-validated integer
+// durations instead of logw - w_ceil[b][t] = dur[b][t] for t < len[b] (0 behind), cum = its inclusive prefix sums,
+// y_len = max(sum, 1).  One workgroup of four waves per utterance, 256 tokens per pass: an integer scan inside each wave
+// by cross-lane moves (six shuffle steps), the four wave totals through LDS (two barriers per pass), the running total
+// of the passes in a register every thread keeps.  The host has checked 0 <= dur and sum <= VITS_MAX_FORCED_FRAMES, so
+// nothing here leaves `int` and every w_ceil is exact in fp32.
+__global__ __launch_bounds__(256) void forced_duration_kernel(const int64_t *dur, const int *len, float *w_ceil, int *cum,
+                                                              int *y_len, int T) {
+    __shared__ int wave_sum[4];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int L = len[b];
+    int carry = 0;
+    for (int base = 0; base < T; base += 256) {
+        const int t = base + tid;
+        const int v = t < L && t < T ? (int)dur[(int64_t)b * T + t] : 0;
+        int s = v;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int o = __shfl_up(s, off, 64);
+            if (lane >= off) s += o;
+        }
+        if (lane == 63) wave_sum[wv] = s;
+        __syncthreads();
+        int before = carry, total = 0;
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+            const int ws = wave_sum[w];
+            before += w < wv ? ws : 0;
+            total += ws;
+        }
+        if (t < T) {
+            w_ceil[(int64_t)b * T + t] = (float)v;
+            cum[(int64_t)b * T + t] = before + s;
+        }
+        carry += total;
+        __syncthreads();
+    }
+    if (tid == 0) y_len[b] = carry < 1 ? 1 : carry;
 }
 
 // ---- noise: Philox4x32-10 counter RNG + Box-Muller (production path; parity uses injected noise) ---

@@ -5,6 +5,7 @@
 //   text encoder -> (stochastic) duration predictor -> length regulator -> inverse coupling flow
 //   -> HiFi-GAN generator.  The only host synchronisation inside a run is the readback of the frame
 //   counts (data-dependent output length).
+#include <climits>
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -68,8 +69,14 @@ struct vits_handle {
     std::vector<int> h_ylen;
     char *h_in_pin = nullptr;      // pinned staging of a call's ids | lens | sid: one host-to-device copy instead of three
     size_t h_in_pin_bytes = 0;     // staged pageable ones
-    int *h_ylen_pin = nullptr;     // pinned landing buffer of the one mid-run readback (a pageable destination makes the copy a
-    int h_ylen_pin_n = 0;          // staged, synchronous one: the stream then waits for the host twice)
+    // vits_last_durations: the host copy of w_ceil [B][T].  It sits in front of y_len in the token slab, so the one mid-run
+    // readback fetches [w_ceil | y_len] in ONE copy - the same number of copies and synchronisations as the frame counts
+    // alone.  h_dur_B == 0: no token run to report (never ran, a workspace grew, a vocoder-only run).
+    std::vector<float> h_dur;
+    float *h_rb_pin = nullptr;     // pinned landing buffer of that readback: [B * T floats | B ints] (a pageable destination
+    size_t h_rb_pin_n = 0;         // makes the copy a staged, synchronous one: the stream then waits for the host twice)
+    int h_dur_B = 0, h_dur_T = 0;
+    bool last_forced = false;      // the last run took its durations from the caller: no logw to tap
     // stats
     int timing = 0;  // vits_set_timing: 0 off, 1 stage marks + events around every conv launch, 2 stage marks only
     vits_stats stats{};
@@ -214,6 +221,7 @@ void forget_results_in(vits_handle *h, const Slab &s) {
         h->d_emb = h->d_x = h->d_mp = h->d_logs = h->d_logw = h->d_wceil = nullptr;
         h->d_len = h->d_ylen = h->d_cum = nullptr;
         h->d_ylen64 = nullptr;
+        h->h_dur_B = h->h_dur_T = 0;
     } else if (&s == &h->frm) {
         h->d_zp = h->d_z = h->d_out = nullptr;
     }
@@ -1050,6 +1058,7 @@ size_t tokens_ws_bytes(const Model &m, int B, int T) {
     need += al((size_t)B * (m.gin + m.dp_cond_rows + m.C0 + 16)) + (1 << 16);
     for (auto &cd : m.flow) need += al((size_t)B * 2 * m.flow_H * cd.n_wn);
     need += al((size_t)B * 3) + al((size_t)B * 2);         // per-utterance settings and seeds (RunRows)
+    need += al((size_t)B * T * 2);                         // forced durations (int64) or per-token rates (vits_controls)
     return need;
 }
 
@@ -1061,8 +1070,13 @@ struct RunRows {
     const float *scales = nullptr;  // host [3] (rows == false) or [B][3]
     bool rows = false;
     const uint64_t *seeds = nullptr;  // host [B] or NULL: the flat stream
+    // vits_controls (validated on the host by host_controls): forced durations, or a per-token rate - never both
+    const int64_t *durations = nullptr;  // host [B][T] or NULL
+    const float *token_rate = nullptr;   // host [B][T] or NULL
     const float *d_rows = nullptr;
     const uint64_t *d_seeds = nullptr;
+    const int64_t *d_durations = nullptr;
+    const float *d_token_rate = nullptr;
     float at(int b, int col) const { return scales[(rows ? (int64_t)b * 3 : 0) + col]; }
     bool any(int B, int col) const {  // some utterance's value is not 0
         for (int b = 0; b < (rows ? B : 1); b++)
@@ -1090,7 +1104,6 @@ int run_tokens(vits_handle *h, const int64_t *d_ids, const int64_t *d_lens, int 
     hipStream_t st = h->stream;
 
     h->d_len = slab_take<int>(s, B);
-    h->d_ylen = slab_take<int>(s, B);
     h->d_ylen64 = slab_take<int64_t>(s, B);
     h->d_cum = slab_take<int>(s, (size_t)B * T);
     float *x = slab_take<float>(s, nHT), *att = slab_take<float>(s, nHT);
@@ -1103,7 +1116,8 @@ int run_tokens(vits_handle *h, const int64_t *d_ids, const int64_t *d_lens, int 
     float *stats = slab_take<float>(s, (size_t)B * 2 * C * T);
     h->d_x = x;
     h->d_logw = slab_take<float>(s, (size_t)B * T);
-    h->d_wceil = slab_take<float>(s, (size_t)B * T);
+    h->d_wceil = slab_take<float>(s, (size_t)B * T + B);  // [w_ceil | y_len]: one block, read back with one copy
+    h->d_ylen = reinterpret_cast<int *>(h->d_wceil + (size_t)B * T);
 
     if (rr.rows) {
         float *d_rows = slab_take<float>(s, (size_t)B * 3);
@@ -1115,6 +1129,18 @@ int run_tokens(vits_handle *h, const int64_t *d_ids, const int64_t *d_lens, int 
         HIPCHECK(h, hipMemcpyAsync(d_seeds, rr.seeds, sizeof(uint64_t) * B, hipMemcpyHostToDevice, st));
         rr.d_seeds = d_seeds;
     }
+    if (rr.durations) {
+        int64_t *d = slab_take<int64_t>(s, (size_t)B * T);
+        HIPCHECK(h, hipMemcpyAsync(d, rr.durations, sizeof(int64_t) * B * T, hipMemcpyHostToDevice, st));
+        rr.d_durations = d;
+    } else if (rr.token_rate) {
+        float *d = slab_take<float>(s, (size_t)B * T);
+        HIPCHECK(h, hipMemcpyAsync(d, rr.token_rate, sizeof(float) * B * T, hipMemcpyHostToDevice, st));
+        rr.d_token_rate = d;
+    }
+    const bool forced = rr.d_durations != nullptr;
+    h->last_forced = forced;
+    h->h_dur_B = h->h_dur_T = 0;
     lens_to_i32<<<(B + 63) / 64, 64, 0, st>>>(d_lens, h->d_len, B, T);
     const int *len = h->d_len;
     h->cur_stage = 0;
@@ -1186,8 +1212,8 @@ int run_tokens(vits_handle *h, const int64_t *d_ids, const int64_t *d_lens, int 
 
     // ---- speaker conditioning vectors
     float *dp_cond = nullptr;
-    if (m.gin) {
-        if (!d_sid) return fail(h, VITS_E_ARG, "Missing speaker id");
+    if (m.gin && !d_sid) return fail(h, VITS_E_ARG, "Missing speaker id");
+    if (m.gin && !forced) {
         dp_cond = slab_take<float>(s, (size_t)B * m.dp_cond_rows);
         cond_matvec_kernel<<<dim3((m.dp_cond_rows + 63) / 64, B), 64, 0, st>>>(
             c.P(m.emb_g), d_sid, m.n_speakers, c.P(m.dp_cond_w), c.P(m.dp_cond_b), dp_cond, m.dp_cond_rows, m.gin);
@@ -1198,7 +1224,11 @@ int run_tokens(vits_handle *h, const int64_t *d_ids, const int64_t *d_lens, int 
     h->cur_stage = 1;
     stage_mark(h, 1);
     const float noise_w = rr.at(0, 2);
-    if (m.use_sdp) {
+    if (forced) {
+        // forced durations: the duration predictor - stochastic or plain, its convs, spline flows and noise - is not
+        // launched at all, and there is no logw (tap "logw" says so)
+        h->d_logw = nullptr;
+    } else if (m.use_sdp) {
         const int Cd = m.dp_pre.Cout;
         const int64_t sC = (int64_t)Cd * T;
         float *hb = slab_take<float>(s, (size_t)B * Cd * T), *y = slab_take<float>(s, (size_t)B * Cd * T);
@@ -1265,22 +1295,37 @@ int run_tokens(vits_handle *h, const int64_t *d_ids, const int64_t *d_lens, int 
         conv(c, m.dpp_proj, h2, sF, T, h->d_logw, T, PRO_MASK | EPI_MASK, len);
     }
     // ---- durations (models.py:702-704)
-    duration_kernel<<<B, 256, 0, st>>>(h->d_logw, len, rr.at(0, 1), rr.d_rows, h->d_wceil, h->d_cum, h->d_ylen, T);
+    if (forced)
+        forced_duration_kernel<<<B, 256, 0, st>>>(rr.d_durations, len, h->d_wceil, h->d_cum, h->d_ylen, T);
+    else
+        duration_kernel<<<B, 256, 0, st>>>(h->d_logw, len, rr.at(0, 1), rr.d_rows, rr.d_token_rate, h->d_wceil, h->d_cum,
+                                           h->d_ylen, T);
     h->stats.total_launches++;
     c.note(hipGetLastError());
     if (c.err != hipSuccess) return fail(h, VITS_E_DEVICE, "kernel launch failed: %s", hipGetErrorString(c.err));
+    // the one data-dependent readback: the frame counts (output length) and, in the same copy, the durations themselves
+    const size_t nBT = (size_t)B * T, nrb = nBT + B;
     h->h_ylen.resize(B);
-    if (h->h_ylen_pin_n < B) {
-        if (h->h_ylen_pin) hipHostFree(h->h_ylen_pin);
-        h->h_ylen_pin = nullptr;
-        h->h_ylen_pin_n = 0;
-        const int cap = B < 64 ? 64 : B;
-        if (hipHostMalloc((void **)&h->h_ylen_pin, sizeof(int) * cap) == hipSuccess) h->h_ylen_pin_n = cap;
+    h->h_dur.resize(nBT);
+    if (h->h_rb_pin_n < nrb) {
+        if (h->h_rb_pin) hipHostFree(h->h_rb_pin);
+        h->h_rb_pin = nullptr;
+        h->h_rb_pin_n = 0;
+        const size_t cap = nrb < 16384 ? 16384 : nrb + nrb / 4;
+        if (hipHostMalloc((void **)&h->h_rb_pin, sizeof(float) * cap) == hipSuccess) h->h_rb_pin_n = cap;
     }
-    int *ydst = h->h_ylen_pin_n >= B ? h->h_ylen_pin : h->h_ylen.data();
-    HIPCHECK(h, hipMemcpyAsync(ydst, h->d_ylen, sizeof(int) * B, hipMemcpyDeviceToHost, st));
-    HIPCHECK(h, hipStreamSynchronize(st));  // the one data-dependent readback: output length
-    if (ydst != h->h_ylen.data()) std::memcpy(h->h_ylen.data(), ydst, sizeof(int) * B);
+    if (h->h_rb_pin_n >= nrb) {
+        HIPCHECK(h, hipMemcpyAsync(h->h_rb_pin, h->d_wceil, sizeof(float) * nrb, hipMemcpyDeviceToHost, st));
+        HIPCHECK(h, hipStreamSynchronize(st));
+        std::memcpy(h->h_dur.data(), h->h_rb_pin, sizeof(float) * nBT);
+        std::memcpy(h->h_ylen.data(), h->h_rb_pin + nBT, sizeof(int) * B);
+    } else {
+        HIPCHECK(h, hipMemcpyAsync(h->h_dur.data(), h->d_wceil, sizeof(float) * nBT, hipMemcpyDeviceToHost, st));
+        HIPCHECK(h, hipMemcpyAsync(h->h_ylen.data(), h->d_ylen, sizeof(int) * B, hipMemcpyDeviceToHost, st));
+        HIPCHECK(h, hipStreamSynchronize(st));
+    }
+    h->h_dur_B = B;
+    h->h_dur_T = T;
     if (h->range_pending) {  // an earlier asynchronous run whose range verdict nobody has looked at
         const vits_stats keep = h->stats;
         const int rr = range_check(h);
@@ -2148,7 +2193,7 @@ void vits_close(vits_handle *h) {
         hipSetDevice(h->device);
         if (h->stream) hipStreamSynchronize(h->stream);
         if (h->arena_owned && h->arena_dev) hipFree(h->arena_dev);
-        if (h->h_ylen_pin) hipHostFree(h->h_ylen_pin);
+        if (h->h_rb_pin) hipHostFree(h->h_rb_pin);
         if (h->h_in_pin) hipHostFree(h->h_in_pin);
         if (h->tok.base) hipFree(h->tok.base);
         if (h->frm.base) hipFree(h->frm.base);
@@ -2290,6 +2335,44 @@ static int host_rows(vits_handle *h, const float *scales, int B, const uint64_t 
     return VITS_OK;
 }
 
+// ... with vits_controls on top: forced durations or per-token rates, host [B][T].  Everything is checked here, on the
+// host, before anything is enqueued or allocated; a rejected call leaves the previous run's results readable.
+static int host_controls(vits_handle *h, const vits_controls *ctl, const int64_t *lens, int B, int T, RunRows &rr) {
+    if (!ctl) return fail(h, VITS_E_ARG, "null argument");
+    if (B <= 0 || T <= 0) return fail(h, VITS_E_ARG, "empty batch or sequence (B=%d, T=%d)", B, T);
+    if (!lens) return fail(h, VITS_E_ARG, "null argument");
+    if (int rc = host_rows(h, ctl->scales_rows, B, ctl->seeds, rr)) return rc;
+    if (ctl->durations && ctl->token_rate)
+        return fail(h, VITS_E_ARG, "durations and token_rate are contradictory: forced durations leave nothing to scale");
+    // frames per utterance of a forced run: VITS_MAX_FORCED_FRAMES, and no more than keep its SAMPLES (frames * hop) in int
+    const int64_t hop = h->model.hop > 0 ? h->model.hop : 1;
+    const int64_t max_frames = VITS_MAX_FORCED_FRAMES < INT_MAX / hop ? VITS_MAX_FORCED_FRAMES : INT_MAX / hop;
+    for (int b = 0; b < B; b++) {
+        if (lens[b] < 0 || lens[b] > T)
+            return fail(h, VITS_E_ARG, "input_lengths[%d]=%lld outside [0,%d]", b, (long long)lens[b], T);
+        const int L = (int)lens[b];
+        int64_t sum = 0;
+        for (int t = 0; t < L; t++) {
+            if (ctl->durations) {
+                const int64_t d = ctl->durations[(int64_t)b * T + t];
+                if (d < 0) return fail(h, VITS_E_ARG, "durations[%d,%d]=%lld is negative", b, t, (long long)d);
+                if (d > max_frames || (sum += d) > max_frames)
+                    return fail(h, VITS_E_ARG,
+                                "durations[%d,%d]=%lld: utterance %d would exceed the %lld frames a forced run admits "
+                                "(VITS_MAX_FORCED_FRAMES, INT_MAX / hop) at this token", b, t, (long long)d, b,
+                                (long long)max_frames);
+            } else if (ctl->token_rate) {
+                const float r = ctl->token_rate[(int64_t)b * T + t];
+                if (!std::isfinite(r) || r < 0.f)
+                    return fail(h, VITS_E_ARG, "token_rate[%d,%d]=%g is not a finite value >= 0", b, t, (double)r);
+            }
+        }
+    }
+    rr.durations = ctl->durations;
+    rr.token_rate = ctl->token_rate;
+    return VITS_OK;
+}
+
 static int run_device_locked(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T,
                              RunRows rr, const int64_t *sid, const vits_noise *noise, vits_output *out,
                              const ChunkSink *sink = nullptr) {
@@ -2347,6 +2430,14 @@ int vits_last_y_lengths(vits_handle *h, int64_t *buf, int n) {
     int B = (int)h->h_ylen.size();
     for (int b = 0; b < B && b < n && buf; b++) buf[b] = h->h_ylen[b];
     return B;
+}
+
+int vits_last_durations(vits_handle *h, int64_t *buf, size_t n_elems) {
+    if (!h) return VITS_E_ARG;
+    const size_t n = (size_t)h->h_dur_B * h->h_dur_T;
+    if (n == 0 || h->h_dur.size() < n) return fail(h, VITS_E_ARG, "no completed run to report durations of");
+    for (size_t i = 0; i < n && i < n_elems && buf; i++) buf[i] = (int64_t)h->h_dur[i];
+    return (int)n;
 }
 
 int vits_sync(vits_handle *h) {
@@ -2536,6 +2627,25 @@ int vits_run_chunked_rows(vits_handle *h, const int64_t *ids, const int64_t *len
     return run_chunked_locked(h, ids, lens, B, T, rr, sid, noise, chunk_frames, fn, user);
 }
 
+int vits_run_async_ctl(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
+                       const vits_noise *noise, const vits_controls *ctl) {
+    if (int rc = check_dev(h)) return rc;
+    std::lock_guard<std::mutex> lk(h->mu);
+    RunRows rr;
+    if (int rc = host_controls(h, ctl, lens, B, T, rr)) return rc;
+    vits_output dev{};
+    return run_async_locked(h, ids, lens, B, T, rr, sid, noise, &dev);
+}
+
+int vits_run_chunked_ctl(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
+                         const vits_noise *noise, const vits_controls *ctl, int chunk_frames, vits_chunk_fn fn, void *user) {
+    if (int rc = check_dev(h)) return rc;
+    std::lock_guard<std::mutex> lk(h->mu);
+    RunRows rr;
+    if (int rc = host_controls(h, ctl, lens, B, T, rr)) return rc;
+    return run_chunked_locked(h, ids, lens, B, T, rr, sid, noise, chunk_frames, fn, user);
+}
+
 void vits_free_output(vits_handle *h, vits_output *out) {
     if (!out) return;
     std::unique_lock<std::mutex> lk;
@@ -2611,6 +2721,7 @@ static int vocoder_common(vits_handle *h, const float *z, int B, int F, const in
     h->B = B;
     h->F = F;
     h->d_ylen = nullptr;  // (no frame counts: vits_last_pcm16 does not apply to a vocoder-only run)
+    h->h_dur_B = h->h_dur_T = 0;  // (no tokens: vits_last_durations has nothing to report)
     range_begin(h);
     int rc;
     if (sink) rc = render_chunks(h, c, dz, (int64_t)m.C * F, F, nullptr, B, F, dec_cond, s, *sink);
@@ -2679,6 +2790,8 @@ int vits_tap(vits_handle *h, const char *name, float *buf, size_t buf_elems, int
     else if (k == "z_p") { src = h->d_zp; C = m.C; L = F; cstride = h->Fpitch; bstride = (int64_t)C * cstride; }
     else if (k == "z") { src = h->d_z; C = m.C; L = F; cstride = h->Fpitch; bstride = (int64_t)C * cstride; }
     else return fail(h, VITS_E_ARG, "unknown tap %s", name);
+    if (k == "logw" && h->last_forced && h->d_wceil)
+        return fail(h, VITS_E_ARG, "logw is not computed in a forced-duration run");
     if (!src || B == 0) return fail(h, VITS_E_ARG, "no completed run to tap");
     if (nd == 2) { dims[0] = B; dims[1] = L; }
     else { dims[0] = B; dims[1] = C; dims[2] = L; }

@@ -131,6 +131,95 @@ def phonemes_to_ids(phonemes: Sequence[str],
     return out
 
 
+def phonemes_to_id_groups(phonemes: Sequence[str],
+                          id_map: Optional[Mapping[str, Union[int, Sequence[int]]]] = None,
+                          blank_token: Optional[str] = DEFAULT_BLANK_TOKEN,
+                          bos_token: Optional[str] = DEFAULT_BOS_TOKEN,
+                          eos_token: Optional[str] = DEFAULT_EOS_TOKEN,
+                          word_sep_token: Optional[str] = DEFAULT_BLANK_WORD_TOKEN,
+                          include_whitespace: Optional[bool] = True,
+                          blank_at_start: bool = True,
+                          blank_at_end: bool = True,
+                          blank_between: BlankBetween = BlankBetween.TOKENS_AND_WORDS) -> List[tuple]:
+    """The ids of phonemes_to_ids(...) for the same arguments, grouped by where they came from: a list of
+    (token, [ids]) whose concatenated id lists ARE that result (what per-phoneme timing is attached to).
+    token is the phoneme; for a multi-character hit the matched key; for bos, eos and word separators the special
+    token's own string.  Every inserted blank belongs to the entry in front of it; a blank with no entry in front (a
+    leading blank without bos) is an entry of its own, under the blank token.  Phonemes that produce no id produce no
+    entry.  Raises what phonemes_to_ids raises."""
+    if not phonemes:
+        return []
+    table = {k: (v if isinstance(v, list) else [v]) for k, v in (id_map or DEFAULT_IPA_PHONEME_ID_MAP).items()}
+    unknown = [len(table)]
+    blank = _special(blank_token, table, unknown)
+    eos = _special(eos_token, table, unknown)
+    bos = eos_token if isinstance(bos_token, int) else _special(bos_token, table, unknown)
+
+    have_blank = blank_token is not None
+    per_token = have_blank and blank_between in (BlankBetween.TOKENS, BlankBetween.TOKENS_AND_WORDS)
+    per_word = have_blank and blank_between in (BlankBetween.WORDS, BlankBetween.TOKENS_AND_WORDS)
+
+    groups: List[tuple] = []
+
+    def entry(token, ids):
+        groups.append((token, list(ids)))
+
+    def add_blank():
+        if groups:
+            groups[-1][1].extend(blank)
+        else:
+            entry(blank_token, blank)
+
+    if bos_token is not None:
+        entry(bos_token, bos)
+    if have_blank and blank_at_start:
+        add_blank()
+
+    multi = sorted((k for k in table if len(k) > 1), key=len, reverse=True)
+    n = len(phonemes)
+    pos = 0
+    while pos < n:
+        hit = next((m for m in multi if "".join(phonemes[pos:pos + len(m)]) == m), None)
+        if hit is not None:
+            entry(hit, table[hit])
+            pos += len(hit)
+            if per_token and pos < n:
+                add_blank()
+            continue
+        ph = phonemes[pos]
+        pos += 1
+        if ph not in table:
+            if not (ph == " " and not include_whitespace):
+                LOG.warning("Missing phoneme from id map: %s", ph)
+            continue
+        if ph == " ":
+            if include_whitespace:
+                entry(ph, table[ph])
+                if per_token:
+                    add_blank()
+            elif per_word:
+                entry(word_sep_token, table[word_sep_token])
+                if per_token:
+                    add_blank()
+            continue
+        entry(ph, table[ph])
+        if per_token and pos < n:
+            add_blank()
+
+    if have_blank and blank_at_end:
+        if not include_whitespace and word_sep_token and per_word:
+            if per_token:
+                add_blank()
+            entry(word_sep_token, table[word_sep_token])
+            if per_token:
+                add_blank()
+        else:
+            add_blank()
+    if eos_token is not None:
+        entry(eos_token, eos)
+    return groups
+
+
 def load_phoneme_ids(phonemes_file: TextIO) -> Dict[str, int]:
     """Parse `ID PHONEME` lines (`#` comments; a bare number is the id of the space)."""
     table: Dict[str, int] = {}

@@ -166,6 +166,58 @@ def _settings(scales, B, seeds=None):
     return scales, np.ascontiguousarray(arr)
 
 
+def _timing(durations, token_rate, lens, B, T):
+    """Timing controls of a batch call (vitsmi.h, vits_controls): `durations` None or integers [B, T] (forced: token t of
+    utterance b occupies durations[b, t] frames; the duration predictor does not run), `token_rate` None or floats [B, T]
+    (a multiplier on each token's predicted duration; finite, >= 0).  Positions behind lens[b] are ignored.  Returns
+    (int64 [B, T] or None, float32 [B, T] or None); raises SessionError naming the argument before anything reaches the
+    device (the engine checks the same, and the frame-count limits, once more)."""
+    if durations is None and token_rate is None:
+        return None, None
+    if durations is not None and token_rate is not None:
+        raise SessionError("Unexpected input: 'durations' and 'token_rate' are contradictory (forced durations leave "
+                           "nothing to scale): pass one of them")
+    valid = np.arange(T)[None, :] < np.clip(np.asarray(lens).reshape(-1, 1), 0, T)
+    if durations is not None:
+        d = np.asarray(durations)
+        if d.dtype.kind not in "iu":
+            raise SessionError(f"Unexpected input data type: 'durations' must be integers (frames per token), got {d.dtype}")
+        if d.shape != (B, T):
+            raise SessionError(f"Invalid shape for 'durations': {d.shape}, expected [batch_size, phonemes] = {(B, T)}")
+        if d.dtype == np.uint64:
+            d = np.minimum(d, np.uint64(1 << 62))   # (far above the engine's limit either way; keeps the sign bit clear)
+        d = np.ascontiguousarray(d, np.int64)
+        bad = np.argwhere((d < 0) & valid)
+        if bad.size:
+            b, t = (int(v) for v in bad[0])
+            raise SessionError(f"durations[{b},{t}]={int(d[b, t])} is negative")
+        return d, None
+    r = np.asarray(token_rate)
+    if r.dtype.kind != "f":
+        raise SessionError(f"Unexpected input data type: 'token_rate' must be floats, got {r.dtype}")
+    if r.shape != (B, T):
+        raise SessionError(f"Invalid shape for 'token_rate': {r.shape}, expected [batch_size, phonemes] = {(B, T)}")
+    r = np.ascontiguousarray(r, np.float32)
+    bad = np.argwhere(~(np.isfinite(r) & (r >= 0)) & valid)
+    if bad.size:
+        b, t = (int(v) for v in bad[0])
+        raise SessionError(f"token_rate[{b},{t}]={float(r[b, t])} is not a finite value >= 0")
+    return None, r
+
+
+def _controls(rows, seeds, durations, token_rate):
+    """The vits_controls struct over host arrays.  The struct holds bare addresses, so it also holds the arrays themselves
+    (`_keep`): whoever keeps the struct - a chunked run's closure, which runs on a worker thread after its caller has
+    returned - keeps the memory it points into."""
+    c = _ffi.VitsControls()
+    c._keep = (rows, seeds, durations, token_rate)
+    c.scales_rows = rows.ctypes.data
+    c.seeds = None if seeds is None else seeds.ctypes.data
+    c.durations = None if durations is None else durations.ctypes.data
+    c.token_rate = None if token_rate is None else token_rate.ctypes.data
+    return c
+
+
 def _rows(scales, B):
     """[3] -> [B, 3] (the row twins of the C ABI take one row per utterance)"""
     return np.ascontiguousarray(np.broadcast_to(scales, (B, 3)) if scales.ndim == 1 else scales, np.float32)
@@ -360,12 +412,17 @@ class MiSession:
         RandomNormalLike nodes (models.py:111, :718)."""
         self._seed = int(seed)
 
-    def synthesize_batch(self, ids, lens, scales, sid=None, noise_dp=None, noise_z=None, taps=(), seeds=None):
+    def synthesize_batch(self, ids, lens, scales, sid=None, noise_dp=None, noise_z=None, taps=(), seeds=None,
+                         durations=None, token_rate=None, return_durations=False):
         """One batched run.  Returns {"output": [B,1,1,S] float32, "y_lengths": int64 [B], taps...}.
         noise_dp [B,2,T] / noise_z [B,inter,>=F] inject the graph's noise for parity runs.
         scales: float32 [3] for every utterance, or [B, 3] - utterance b's own [noise_scale, length_scale, noise_w];
         seeds: None (the session's stream, set_seed) or B integers - utterance b's own noise stream, which does not
-        depend on the rest of the batch (vitsmi.h, vits_run_async_rows)."""
+        depend on the rest of the batch (vitsmi.h, vits_run_async_rows).
+        durations: None or integers [B, T] - forced frames per token: the duration predictor is not run, everything else is
+        (with a free run's durations and seeds: that run's audio bit for bit); token_rate: None or floats [B, T] - a
+        multiplier on each token's predicted duration (0 drops the token).  One or the other (vitsmi.h, vits_controls).
+        return_durations: adds "durations", int64 [B, T] - the frames each token occupies (last_durations())."""
         ids = np.ascontiguousarray(ids)
         lens = np.ascontiguousarray(lens)
         if ids.dtype != np.int64 or lens.dtype != np.int64:
@@ -374,6 +431,7 @@ class MiSession:
             raise SessionError(f"Invalid rank/shape for input: {ids.shape} / input_lengths: {lens.shape}")
         B, T = ids.shape
         scales, seeds = _settings(scales, B, seeds)
+        durations, token_rate = _timing(durations, token_rate, lens, B, T)
         if sid is not None:
             sid = np.ascontiguousarray(sid)
             if sid.dtype != np.int64 or sid.shape != (B,):
@@ -393,24 +451,33 @@ class MiSession:
             noise.noise_z_stride = noise_z.shape[2]
         with self._locked():  # enqueue -> frame counts -> copy-out -> taps all use this handle's one workspace
             try:
-                self._begin(ids, lens, scales, sid, noise, seeds)
+                self._begin(ids, lens, scales, sid, noise, seeds, durations, token_rate)
                 ylen = self.last_y_lengths()
+                dur = self.last_durations() if return_durations else None
                 S = int(ylen.max()) * self.hparam("hop")
                 audio = _POOL.array((B, 1, 1, S)) if self.pinned_results else np.empty((B, 1, 1, S), np.float32)
                 self._fetch(audio, 0, B)
             except RangeError as exc:
                 self._fall_back_to_bf16x6(exc)
-                return self.synthesize_batch(ids, lens, scales, sid, noise_dp, noise_z, taps, seeds=seeds)
+                return self.synthesize_batch(ids, lens, scales, sid, noise_dp, noise_z, taps, seeds=seeds,
+                                             durations=durations, token_rate=token_rate, return_durations=return_durations)
             res = {"output": audio, "y_lengths": ylen}
+            if return_durations:
+                res["durations"] = dur
             for t in taps:
                 res[t] = self.tap(t)
             return res
 
-    def _begin(self, ids, lens, scales, sid, noise, seeds=None):
-        """vits_run_async: validated host arrays in, the whole path enqueued; frame counts are known on return.
-        ([B, 3] scales or seeds: vits_run_async_rows.)"""
+    def _begin(self, ids, lens, scales, sid, noise, seeds=None, durations=None, token_rate=None):
+        """vits_run_async: validated host arrays in, the whole path enqueued; frame counts and durations are known on
+        return.  ([B, 3] scales or seeds: vits_run_async_rows; durations or token_rate: vits_run_async_ctl.)"""
         B, T = ids.shape
-        if scales.ndim == 1 and seeds is None:
+        if durations is not None or token_rate is not None:
+            rows = _rows(scales, B)
+            ctl = _controls(rows, seeds, durations, token_rate)
+            rc = self._lib.vits_run_async_ctl(self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(sid), C.byref(noise),
+                                              C.byref(ctl))
+        elif scales.ndim == 1 and seeds is None:
             rc = self._lib.vits_run_async(self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(scales), _ffi.ptr(sid),
                                           C.byref(noise))
         else:
@@ -519,21 +586,26 @@ class MiSession:
             t.join()
 
     def synthesize_stream(self, ids, lens, scales, sid=None, chunk_frames: int = 64, noise_dp=None, noise_z=None,
-                          seeds=None):
+                          seeds=None, durations=None, token_rate=None):
         """The whole path with the waveform delivered in chunks of `chunk_frames` frames (hop samples each): yields
         (first_sample, float32 [B, n], total_samples).  Concatenated, the chunks are bit-identical to
         synthesize_batch(...)["output"][:, 0, 0, :]; frame counts afterwards from last_y_lengths().  Chunks are handed out
         as they finish, so a range violation of the f16x3 arithmetic cannot be repaired by a silent re-run: it raises
         RangeError at the end (no bf16x6 fallback here; reopen with gen_precision="bf16x6").  Closing the generator
-        early stops the engine after the chunk in flight.  scales [3] or [B, 3] and seeds as synthesize_batch."""
+        early stops the engine after the chunk in flight.  scales [3] or [B, 3], seeds, durations and token_rate as
+        synthesize_batch.  The consumer may call last_durations() - like last_y_lengths() - from the first chunk on: the
+        timing of the whole utterance is known before most of its audio exists."""
         ids = np.ascontiguousarray(ids, np.int64)
         lens = np.ascontiguousarray(lens, np.int64)
         B, T = ids.shape
         scales, seeds = _settings(np.ascontiguousarray(scales, np.float32), B, seeds)
+        durations, token_rate = _timing(durations, token_rate, lens, B, T)
         sid = None if sid is None else np.ascontiguousarray(sid, np.int64)
         noise = _ffi.VitsNoise()
         noise.seed = self._seed
-        keep = []
+        # (the C call runs on _stream's worker thread after this function has returned: every host array it reads must
+        # belong to the closure - the converted noise arrays ride on the struct that points into them)
+        keep = noise._keep = []
         if noise_dp is not None:
             keep.append(np.ascontiguousarray(noise_dp, np.float32))
             noise.noise_dp = keep[-1].ctypes.data
@@ -541,6 +613,12 @@ class MiSession:
             keep.append(np.ascontiguousarray(noise_z, np.float32))
             noise.noise_z = keep[-1].ctypes.data
             noise.noise_z_stride = keep[-1].shape[2]
+        if durations is not None or token_rate is not None:
+            rows = _rows(scales, B)
+            ctl = _controls(rows, seeds, durations, token_rate)
+            return self._stream(lambda cb: self._lib.vits_run_chunked_ctl(
+                self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(sid), C.byref(noise), C.byref(ctl),
+                int(chunk_frames), cb, None))
         if scales.ndim == 1 and seeds is None:
             return self._stream(lambda cb: self._lib.vits_run_chunked(
                 self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(scales), _ffi.ptr(sid), C.byref(noise),
@@ -671,6 +749,22 @@ class MiSession:
             buf = np.zeros(max(n, 0), np.int64)
             if n > 0:
                 self._lib.vits_last_y_lengths(self._h, buf.ctypes.data_as(C.POINTER(C.c_int64)), n)
+            return buf
+
+    def last_durations(self) -> np.ndarray:
+        """int64 [B, T]: the frames each token of the last run occupies (w_ceil of models.py:702-704; forced runs: the
+        forced values; 0 behind lens[b]); max(1, row sums) = last_y_lengths().  Answered from host state like
+        last_y_lengths(): no wait, valid as soon as the run has been enqueued, and the consumer of synthesize_stream may
+        call it while chunks are still rendering."""
+        with self._locked(read_only=True):
+            n = self._lib.vits_last_durations(self._h, None, 0)
+            if n < 0:
+                raise SessionError(f"vits_last_durations failed [{n}]: {self._err()}")
+            B = self._lib.vits_last_y_lengths(self._h, None, 0)
+            buf = np.zeros((B, n // B), np.int64)
+            n = self._lib.vits_last_durations(self._h, buf.ctypes.data_as(C.POINTER(C.c_int64)), buf.size)
+            if n != buf.size:
+                raise SessionError(f"vits_last_durations: the run changed between two calls ({n} != {buf.size})")
             return buf
 
     def last_pcm16(self, normalize: bool = True, volume: float = 1.0, shape=None) -> np.ndarray:
@@ -887,9 +981,16 @@ class PipelinedSession:
         n = len(self.bounds(B)) - 1
         return np.concatenate([self.parts[i].last_y_lengths() for i in range(n)])
 
-    def synthesize_batch(self, ids, lens, scales, sid=None, seeds=None):
-        """Host arrays in, host arrays out, like MiSession.synthesize_batch (scales [3] or [B, 3], seeds: each part gets its
-        own rows of both).  One worker thread per sub-batch (the C
+    def last_durations(self, B) -> np.ndarray:
+        """int64 [B, T] of the last B-utterance batch: the parts' MiSession.last_durations() in request order."""
+        n = len(self.bounds(B)) - 1
+        return np.concatenate([self.parts[i].last_durations() for i in range(n)])
+
+    def synthesize_batch(self, ids, lens, scales, sid=None, seeds=None, durations=None, token_rate=None,
+                         return_durations=False, noise_dp=None, noise_z=None):
+        """Host arrays in, host arrays out, like MiSession.synthesize_batch (scales [3] or [B, 3], seeds, durations [B, T],
+        token_rate [B, T], injected noise_dp [B, 2, T] / noise_z [B, inter, >= F]: each part gets its own rows of all of
+        them; return_durations adds "durations" [B, T], the parts' rows in request order).  One worker thread per sub-batch (the C
         calls release the GIL): each enqueues its part (vits_run_async), learns its frame counts, meets the others at a
         barrier where the ONE [B,1,1,S_max] result array (pinned host memory) is sized, then waits for its own render
         and lets the DMA engine write its rows straight into that array (vits_fetch_output) - the copy-out of a part
@@ -901,15 +1002,27 @@ class PipelinedSession:
             raise SessionError("Unexpected input: 'input' int64 [B,T], 'input_lengths' int64 [B]")
         B = ids.shape[0]
         scales, seeds = _settings(scales, B, seeds)
+        durations, token_rate = _timing(durations, token_rate, lens, B, ids.shape[1])
         if sid is not None:
             sid = np.ascontiguousarray(sid)
             if sid.dtype != np.int64 or sid.shape != (B,):
                 raise SessionError("Unexpected input: 'sid' must be int64 of shape [batch_size]")
+        if noise_dp is not None:
+            noise_dp = np.ascontiguousarray(noise_dp, np.float32)
+            if noise_dp.shape != (B, 2, ids.shape[1]):
+                raise SessionError(f"noise_dp must be [B,2,T], got {noise_dp.shape}")
+        if noise_z is not None:
+            noise_z = np.ascontiguousarray(noise_z, np.float32)
+            if noise_z.ndim != 3 or noise_z.shape[0] != B or noise_z.shape[1] != self.hparam("inter"):
+                raise SessionError(f"noise_z must be [B,inter,F], got {noise_z.shape}")
         with self._mu:
-            return self._synthesize_batch_locked(ids, lens, scales, sid, B, seeds)
+            return self._synthesize_batch_locked(ids, lens, scales, sid, B, seeds, durations, token_rate, return_durations,
+                                                 noise_dp, noise_z)
 
-    def _synthesize_batch_locked(self, ids, lens, scales, sid, B, seeds=None):
+    def _synthesize_batch_locked(self, ids, lens, scales, sid, B, seeds=None, durations=None, token_rate=None,
+                                 return_durations=False, noise_dp=None, noise_z=None):
         import threading
+        dur = np.zeros(ids.shape, np.int64) if return_durations else None
         bnd = self.bounds(B)
         n = len(bnd) - 1
         hop = self.hparam("hop")
@@ -930,10 +1043,21 @@ class PipelinedSession:
             try:
                 noise = _ffi.VitsNoise()
                 noise.seed = p._seed
+                # (this part's rows of the injected noise: contiguous slices, alive until _begin has copied them)
+                nd = None if noise_dp is None else noise_dp[b0:b1]
+                nz = None if noise_z is None else noise_z[b0:b1]
+                if nd is not None:
+                    noise.noise_dp = nd.ctypes.data
+                if nz is not None:
+                    noise.noise_z, noise.noise_z_stride = nz.ctypes.data, nz.shape[2]
                 with p._mu:  # (a part may also be used on its own, e.g. bench.py's measure(): same per-session lock)
                     sc, sd = _part(scales, seeds, b0, b1)
-                    p._begin(ids[b0:b1], lens[b0:b1], sc, None if sid is None else sid[b0:b1], noise, sd)
+                    p._begin(ids[b0:b1], lens[b0:b1], sc, None if sid is None else sid[b0:b1], noise, sd,
+                             None if durations is None else durations[b0:b1],
+                             None if token_rate is None else token_rate[b0:b1])
                     ylen[b0:b1] = p.last_y_lengths()
+                    if dur is not None:
+                        dur[b0:b1] = p.last_durations()
                     bar.wait()
                     p._fetch(box["out"], b0, b1 - b0)
             except threading.BrokenBarrierError:
@@ -954,9 +1078,13 @@ class PipelinedSession:
             rng = [e for e in errors if isinstance(e, RangeError)]
             if rng:
                 self._fall_back(rng[0])
-                return self.synthesize_batch(ids, lens, scales, sid, seeds=seeds)
+                return self.synthesize_batch(ids, lens, scales, sid, seeds=seeds, durations=durations, token_rate=token_rate,
+                                             return_durations=return_durations, noise_dp=noise_dp, noise_z=noise_z)
             raise errors[0]
-        return {"output": box["out"], "y_lengths": ylen}
+        res = {"output": box["out"], "y_lengths": ylen}
+        if dur is not None:
+            res["durations"] = dur
+        return res
 
     def sync(self):
         for s in self.parts:

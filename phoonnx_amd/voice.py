@@ -12,7 +12,8 @@ reproduced by default and can be switched off with `dedupe_sentences=True`.
 Extensions: `synthesize(..., batch_sentences=True)` renders all
 sentences of a text in ONE batched engine call; `synthesize_requests()` renders the sentences
 of many requests, each with its own SynthesisConfig (and optionally its own noise seed), in
-shared batches.
+shared batches; `synthesize(..., alignments=True)` / `synthesize_requests(..., alignments=True)` attach per-phoneme
+timing (`AudioChunk.phoneme_alignments`) from the durations the engine reports (MiSession.last_durations).
 """
 import json
 import logging
@@ -25,7 +26,7 @@ from typing import Any, Iterable, List, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from .config import PhonemeType, SynthesisConfig, VoiceConfig
-from .phoneme_ids import BlankBetween, phonemes_to_ids
+from .phoneme_ids import BlankBetween, phonemes_to_id_groups, phonemes_to_ids
 from .phonemizers import get_phonemizer
 
 LOG = logging.getLogger(__name__)
@@ -109,6 +110,36 @@ def check_consistency(config_dict: dict, meta: dict, graph_speakers: int, graph_
 
 
 @dataclass
+class PhonemeAlignment:
+    """Where one phoneme (with the ids it produced, inserted blanks included) sits in its chunk's audio:
+    samples [start_sample, start_sample + num_samples)."""
+    phoneme: str
+    phoneme_ids: List[int]
+    start_sample: int
+    num_samples: int
+
+
+def build_alignments(groups: Sequence[Tuple[str, Sequence[int]]], durations: Sequence[int], hop: int,
+                     total_frames: Optional[int] = None) -> List[PhonemeAlignment]:
+    """(token, [ids]) groups (phonemes_to_id_groups) + the frames each id occupies (`durations`, one per id in group order;
+    longer, e.g. a padded batch row, is fine) + the samples per frame -> one PhonemeAlignment per group: cumulative
+    starts, num_samples = the group's frames * hop, so that they sum to sum(durations) * hop; a token of zero frames gets
+    0 samples.  total_frames: the utterance's frame count where it is known - the engine renders max(1, sum) frames, so
+    an utterance whose durations are all 0 still has one frame of audio, which then goes to the last entry."""
+    out: List[PhonemeAlignment] = []
+    pos = frames = 0
+    for token, ids in groups:
+        n = int(sum(int(d) for d in durations[pos:pos + len(ids)]))
+        out.append(PhonemeAlignment(phoneme=token, phoneme_ids=[int(i) for i in ids], start_sample=frames * hop,
+                                    num_samples=n * hop))
+        pos += len(ids)
+        frames += n
+    if out and total_frames is not None and total_frames > frames:
+        out[-1].num_samples += (int(total_frames) - frames) * hop
+    return out
+
+
+@dataclass
 class AudioChunk:
     """A chunk of raw audio: float samples in [-1, 1] plus their PCM16 rendering."""
     sample_rate: int
@@ -118,6 +149,8 @@ class AudioChunk:
     _audio_int16_array: Optional[np.ndarray] = None
     _audio_int16_bytes: Optional[bytes] = None
     _MAX_WAV_VALUE: float = _MAX_WAV_VALUE
+    # synthesize(..., alignments=True): per-phoneme timing of this chunk; num_samples sum to len(audio_float_array)
+    phoneme_alignments: Optional[List[PhonemeAlignment]] = None
 
     @property
     def audio_int16_array(self) -> np.ndarray:
@@ -214,6 +247,16 @@ class TTSVoice:
                                blank_at_end=c.blank_at_end,
                                blank_between=BlankBetween.TOKENS_AND_WORDS)  # voice.py:231 ignores config.blank_between
 
+    def phonemes_to_id_groups(self, phonemes: List[str]) -> List[Tuple[str, List[int]]]:
+        """phonemes_to_ids with the ids grouped by the phoneme they came from (phoneme_ids.phonemes_to_id_groups)."""
+        if self.config.phoneme_id_map is None:
+            raise ValueError("self.config.phoneme_id_map is None")
+        c = self.config
+        return phonemes_to_id_groups(phonemes, c.phoneme_id_map, blank_token=c.blank_token, bos_token=c.bos_token,
+                                     eos_token=c.eos_token, word_sep_token=c.word_sep_token,
+                                     include_whitespace=c.include_whitespace, blank_at_start=c.blank_at_start,
+                                     blank_at_end=c.blank_at_end, blank_between=BlankBetween.TOKENS_AND_WORDS)
+
     # ------------------------------------------------------------------ synthesis
     def _postprocess(self, audio: np.ndarray, syn_config: SynthesisConfig) -> np.ndarray:
         """voice.py:271-282: peak-normalise, volume, clip, float32."""
@@ -225,11 +268,16 @@ class TTSVoice:
         return np.clip(audio, -1.0, 1.0).astype(np.float32)
 
     def synthesize(self, text: str, syn_config: Optional[SynthesisConfig] = None,
-                   batch_sentences: bool = False) -> Iterable[AudioChunk]:
+                   batch_sentences: bool = False, alignments: bool = False) -> Iterable[AudioChunk]:
         """One AudioChunk per sentence.  `batch_sentences=True` (extension) renders all sentences in a
-        single padded batch on the GPU instead of one engine call per sentence."""
+        single padded batch on the GPU instead of one engine call per sentence.  `alignments=True` (extension) fills
+        AudioChunk.phoneme_alignments from the durations the engine reports; with a session that reports none (the
+        onnxruntime duck type) the field stays None."""
         if syn_config is None:
             syn_config = SynthesisConfig()
+        if alignments and hasattr(self.session, "last_durations") and hasattr(self.session, "synthesize_batch"):
+            yield from self._synthesize_aligned(text, syn_config, batch_sentences)
+            return
         all_ids = self._sentence_ids(text, syn_config)
         if batch_sentences and len(all_ids) > 1 and hasattr(self.session, "synthesize_batch"):
             audios = self.phoneme_ids_batch_to_audio(all_ids, syn_config)
@@ -239,8 +287,24 @@ class TTSVoice:
             yield AudioChunk(sample_rate=self.config.sample_rate, sample_width=2, sample_channels=1,
                              audio_float_array=self._postprocess(audio, syn_config))
 
-    def _sentence_ids(self, text: str, syn_config: SynthesisConfig) -> List[List[int]]:
-        """synthesize()'s front end: phonetic spellings, diacritics, phonemize, ids - one non-empty id list per sentence."""
+    def _synthesize_aligned(self, text: str, syn_config: SynthesisConfig, batch_sentences: bool) -> Iterable[AudioChunk]:
+        """synthesize() with per-phoneme timing: the same engine calls, asked for their durations as well."""
+        all_groups = self._sentence_groups(text, syn_config)
+        all_ids = [[i for _, ids in g for i in ids] for g in all_groups]
+        hop = self.session.hparam("hop")
+        if batch_sentences and len(all_ids) > 1:
+            rows = zip(*self.phoneme_ids_batch_to_audio(all_ids, syn_config, return_durations=True))
+        else:
+            # (a batch of one is what session.run issues, voice.py:374; the durations come back with the same call)
+            rows = ((a[0], d[0]) for a, d in (self.phoneme_ids_batch_to_audio([ids], syn_config, return_durations=True)
+                                              for ids in all_ids))
+        for groups, (audio, dur) in zip(all_groups, rows):
+            yield AudioChunk(sample_rate=self.config.sample_rate, sample_width=2, sample_channels=1,
+                             audio_float_array=self._postprocess(audio, syn_config),
+                             phoneme_alignments=build_alignments(groups, dur, hop, total_frames=len(audio) // hop))
+
+    def _sentence_phonemes(self, text: str, syn_config: SynthesisConfig) -> List[List[str]]:
+        """synthesize()'s front end up to the phonemes: phonetic spellings, diacritics, phonemize."""
         LOG.debug("text=%s", text)
         if self.phonetic_spellings and syn_config.enable_phonetic_spellings:
             text = self.phonetic_spellings.apply(text)
@@ -248,18 +312,29 @@ class TTSVoice:
             text = self.phonemizer.add_diacritics(text, self.config.lang_code)
         sentence_phonemes = self.phonemize(text)
         LOG.debug("phonemes=%s", sentence_phonemes)
-        all_ids = [self.phonemes_to_ids(p) for p in sentence_phonemes if p]
+        return sentence_phonemes
+
+    def _sentence_ids(self, text: str, syn_config: SynthesisConfig) -> List[List[int]]:
+        """synthesize()'s front end: phonetic spellings, diacritics, phonemize, ids - one non-empty id list per sentence."""
+        all_ids = [self.phonemes_to_ids(p) for p in self._sentence_phonemes(text, syn_config) if p]
         return [ids for ids in all_ids if ids]
 
+    def _sentence_groups(self, text: str, syn_config: SynthesisConfig) -> List[List[Tuple[str, List[int]]]]:
+        """_sentence_ids with every sentence's ids grouped by phoneme (flattened: exactly _sentence_ids' lists)."""
+        all_groups = [self.phonemes_to_id_groups(p) for p in self._sentence_phonemes(text, syn_config) if p]
+        return [g for g in all_groups if any(ids for _, ids in g)]
+
     def synthesize_requests(self, requests: Sequence[Tuple[str, Optional[SynthesisConfig]]],
-                            seeds: Optional[Sequence[int]] = None, max_batch: int = 32) -> List[List[AudioChunk]]:
+                            seeds: Optional[Sequence[int]] = None, max_batch: int = 32,
+                            alignments: bool = False) -> List[List[AudioChunk]]:
         """Extension: many independent requests (text, SynthesisConfig or None) rendered together.  Every sentence of
         every request becomes one row of a batch with its request's own speaker, length / noise scales and (with `seeds`,
         one integer per request) its own noise seed - sentence k of request r: sentence_seed(seeds[r], k); rows are sorted
         by length and rendered max_batch at a time.  Returns, per request, what list(synthesize(text, cfg)) returns: one
         AudioChunk per sentence, post-processed with that request's normalize_audio / volume.  With seeds, a request's
         durations do not depend on which other requests share its batches (vitsmi.h, vits_run_async_rows).  A session
-        without synthesize_batch (the onnxruntime duck type) renders the requests one by one through synthesize()."""
+        without synthesize_batch (the onnxruntime duck type) renders the requests one by one through synthesize().
+        alignments=True fills every chunk's phoneme_alignments as synthesize(text, cfg, alignments=True) does."""
         if max_batch < 1:
             raise ValueError(f"max_batch must be >= 1 (got {max_batch})")
         if seeds is not None and len(seeds) != len(requests):
@@ -273,12 +348,21 @@ class TTSVoice:
                 if not 0 <= spk < max(n_spk, 1):
                     raise ValueError(f"request {r}: speaker_id {spk} is out of range [0, {max(n_spk, 1)})")
         if not hasattr(self.session, "synthesize_batch"):
-            return [list(self.synthesize(text, cfg)) for (text, _), cfg in zip(requests, cfgs)]
+            return [list(self.synthesize(text, cfg, alignments=alignments)) for (text, _), cfg in zip(requests, cfgs)]
         from .sharding import pad_batch
+        want_dur = alignments and hasattr(self.session, "last_durations")
         rows = []  # (request, sentence, ids)
+        groups = {}
         for r, ((text, _), cfg) in enumerate(zip(requests, cfgs)):
-            rows.extend((r, k, ids) for k, ids in enumerate(self._sentence_ids(text, cfg)))
+            if want_dur:
+                for k, g in enumerate(self._sentence_groups(text, cfg)):
+                    groups[r, k] = g
+                    rows.append((r, k, [i for _, ids in g for i in ids]))
+            else:
+                rows.extend((r, k, ids) for k, ids in enumerate(self._sentence_ids(text, cfg)))
         audio = {}
+        aligned = {}
+        more = {"return_durations": True} if want_dur else {}
         hop = self.session.hparam("hop")
         order = sorted(range(len(rows)), key=lambda i: len(rows[i][2]))  # (stable: equal lengths keep request order)
         for c0 in range(0, len(order), max_batch):
@@ -287,16 +371,20 @@ class TTSVoice:
             scales = np.stack([self._scales(cfgs[r]) for r, _, _ in run])
             sid = np.asarray([cfgs[r].speaker_id or 0 for r, _, _ in run], np.int64) if "sid" in expected else None
             if seeds is None:
-                out = self.session.synthesize_batch(ids, lens, scales, sid)
+                out = self.session.synthesize_batch(ids, lens, scales, sid, **more)
             else:
                 row_seeds = np.asarray([sentence_seed(seeds[r], k) for r, k, _ in run], np.uint64)
-                out = self.session.synthesize_batch(ids, lens, scales, sid, seeds=row_seeds)
+                out = self.session.synthesize_batch(ids, lens, scales, sid, seeds=row_seeds, **more)
             for b, (r, k, _) in enumerate(run):
                 audio[r, k] = out["output"][b, 0, 0, :int(out["y_lengths"][b]) * hop].copy()
+                if want_dur:
+                    aligned[r, k] = build_alignments(groups[r, k], out["durations"][b], hop,
+                                                     total_frames=int(out["y_lengths"][b]))
         result = [[] for _ in requests]
         for r, k, _ in rows:  # (rows are in request, then sentence order)
             result[r].append(AudioChunk(sample_rate=self.config.sample_rate, sample_width=2, sample_channels=1,
-                                        audio_float_array=self._postprocess(audio[r, k], cfgs[r])))
+                                        audio_float_array=self._postprocess(audio[r, k], cfgs[r]),
+                                        phoneme_alignments=aligned.get((r, k))))
         return result
 
     def synthesize_wav(self, text: str, wav_file: wave.Wave_write, syn_config: Optional[SynthesisConfig] = None,
@@ -368,16 +456,39 @@ class TTSVoice:
         feed = {k: v for k, v in feed.items() if k in expected}  # voices differ in their inputs
         return self.session.run(None, feed)[0].squeeze()
 
-    def phoneme_ids_batch_to_audio(self, batch_ids: List[List[int]],
-                                   syn_config: Optional[SynthesisConfig] = None) -> List[np.ndarray]:
+    def phoneme_ids_batch_to_audio(self, batch_ids: List[List[int]], syn_config: Optional[SynthesisConfig] = None,
+                                   durations: Optional[Sequence[Sequence[int]]] = None,
+                                   token_rate: Optional[Sequence[Sequence[float]]] = None,
+                                   return_durations: bool = False):
         """Extension: all sequences in one padded batch; each waveform is trimmed to its own length
-        (y_lengths * hop), since the generator also renders the padding (models.py:720)."""
+        (y_lengths * hop), since the generator also renders the padding (models.py:720).
+        durations / token_rate: one sequence per utterance, as long as its ids - forced frames per id, or a multiplier on
+        each id's predicted duration (MiSession.synthesize_batch); padded like the ids.  return_durations: returns
+        (waveforms, [int64 array of frames per id, one per utterance]) instead of the waveforms alone."""
         if syn_config is None:
             syn_config = SynthesisConfig()
         from .sharding import pad_batch
         ids, lens = pad_batch(batch_ids)
         expected = [i.name for i in self.session.get_inputs()]
         sid = np.full((len(batch_ids),), syn_config.speaker_id or 0, np.int64) if "sid" in expected else None
-        out = self.session.synthesize_batch(ids, lens, self._scales(syn_config), sid)
+        more = {}
+        for name, seqs, dtype, fill in (("durations", durations, np.int64, 0), ("token_rate", token_rate, np.float32, 1.0)):
+            if seqs is None:
+                continue
+            if len(seqs) != len(batch_ids) or any(len(q) != len(i) for q, i in zip(seqs, batch_ids)):
+                raise ValueError(f"{name} must hold one value per phoneme id of every utterance")
+            arr = np.full(ids.shape, fill, dtype)
+            for b, q in enumerate(seqs):
+                q = np.asarray(q)
+                if name == "durations" and q.size and q.dtype.kind not in "iu":
+                    raise ValueError(f"durations must be integers (frames per phoneme id), got {q.dtype}")
+                arr[b, :len(q)] = q
+            more[name] = arr
+        if return_durations:
+            more["return_durations"] = True
+        out = self.session.synthesize_batch(ids, lens, self._scales(syn_config), sid, **more)
         hop = self.session.hparam("hop")
-        return [out["output"][b, 0, 0, :int(out["y_lengths"][b]) * hop].copy() for b in range(len(batch_ids))]
+        audios = [out["output"][b, 0, 0, :int(out["y_lengths"][b]) * hop].copy() for b in range(len(batch_ids))]
+        if return_durations:
+            return audios, [out["durations"][b, :len(i)].copy() for b, i in enumerate(batch_ids)]
+        return audios
