@@ -63,13 +63,30 @@ int g2p_generate(g2p_handle *h, const int64_t *input_ids, int S, int max_length,
 int g2p_generate_batch(g2p_handle *h, const int64_t *input_ids, const int *lens, int B, int max_length, int64_t start_id,
                        int64_t eos_id, int64_t *out_ids, int *n_out);
 
-/* Test hook: the decoder-STEP path (the kernels g2p_generate runs per token: matrix-vector products, one-query attention
- * over the key / value caches) with GIVEN decoder inputs instead of its own argmax fed back, returning the logits of every
- * step: logits[b][t] = what g2p_run returns at position t for decoder_input_ids[b][0 .. t].  B <= 4 inputs back to back in
- * input_ids (lens[b] each), decoder_input_ids [B][T] (column 0 = the start token), logits [B][T][vocab].  The greedy ids of a
- * randomly initialised model are nearly constant sequences; this compares the step path number by number. */
+/* Test hook (not part of the product surface): the decoder-STEP path (the kernels g2p_generate_batch runs per token) with
+ * GIVEN decoder inputs instead of its own argmax fed back, returning the logits of every step: logits[b][t] = what g2p_run
+ * returns at position t for decoder_input_ids[b][0 .. t].  B <= G2P_MAX_BATCH inputs back to back in input_ids (lens[b]
+ * each), decoder_input_ids [B][T] (column 0 = the start token), logits [B][T][vocab].  B <= 4 runs the matrix-vector step
+ * (NB = 1 / 2 / 4, one-query attention over the key / value caches); B > 4 the wide step (sequences as the columns of
+ * [C][NB] activations, NB = B rounded up to 8: the short-sequence linear kernels writing into the caches).  The greedy ids
+ * of a randomly initialised model are nearly constant sequences; this compares the step path number by number. */
 int g2p_test_forced_steps(g2p_handle *h, const int64_t *input_ids, const int *lens, int B, const int64_t *decoder_input_ids, int T,
                           float *logits);
+
+/* Test hook: the short-sequence Linear launch of the engine on host buffers, through the engine's own choice of kernel.
+ * y[j][row * y_rs + col * y_cs] = sum_k W[j][row][k] x[k][col] (+ res[j][same place]) for njobs (1 .. 3) matrices
+ * W[j] [out[j]][in] over one x [in][T] (pitch xp >= T).  res may be NULL, and so may its entries.  y[j] and res[j] hold
+ * (out[j] - 1) * y_rs + (T - 1) * y_cs + 1 floats; what the kernel does not write comes back unchanged.  The strides must
+ * give every (row, column) an element of its own.  mode 0: the kernel the engine would choose; 1: the generic kernel. */
+int g2p_test_linear(int device, int njobs, const float *const *W, const int *out, int in, const float *x, int T, int xp,
+                    const float *const *res, int64_t y_rs, int64_t y_cs, int mode, float *const *y);
+
+/* Test hook: the decoder step's matrix-vector launch for NB (1, 2 or 4) sequences, njobs (1 .. 3) matrices:
+ * y[j][b][row] = post * rs_b * sum_i W[j][row][i] g[i] x[b][i], rs_b = rsqrt(mean(x[b]^2) + eps) if g else 1 (g NULL: g[i] = 1);
+ * with W2[j]: y = act(that) * (the same with W2[j]); without: act applied if act >= 0 (0 gelu_new, 1 relu, 2 gelu erf);
+ * + res[j][b][row] if given.  x [NB][in], y[j] / res[j] [NB][out[j]]. */
+int g2p_test_step(int device, int NB, int njobs, const float *const *W, const float *const *W2, const int *out, int in,
+                  const float *x, const float *g, int act, float eps, float post, const float *const *res, float *const *y);
 
 #ifdef __cplusplus
 }

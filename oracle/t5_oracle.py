@@ -43,13 +43,25 @@ def relative_position_bucket(rel, bidirectional, num_buckets=32, max_distance=12
 
 
 def gelu_new(x):
-    return 0.5 * x * (1.0 + np.tanh(np.float32(math.sqrt(2.0 / math.pi)) * (x + np.float32(0.044715) * x * x * x)))
+    f = x.dtype.type   # (float32 constants for float32 input, as the graph has them; float64 for the float64 oracle)
+    return 0.5 * x * (1.0 + np.tanh(f(math.sqrt(2.0 / math.pi)) * (x + f(0.044715) * x * x * x)))
+
+
+_erf = np.vectorize(math.erf, otypes=[np.float64])
+
+
+def gelu_erf(x):
+    """torch.nn.functional.gelu (feed_forward_proj "gelu"): x Phi(x); erf in double, result in the dtype of x"""
+    return (0.5 * x * (1.0 + _erf(x.astype(np.float64) / math.sqrt(2.0)))).astype(x.dtype)
 
 
 class T5Oracle:
-    def __init__(self, onnx_path, max_distance=128, eps=1e-6):
+    def __init__(self, onnx_path, max_distance=128, eps=1e-6, dtype=np.float32):
+        """dtype np.float64: every weight and every intermediate in float64 (the relative-position buckets are integers
+        either way) - the high-precision reference the float32 engine is graded against."""
         self.model = OnnxModel(onnx_path)
-        self.max_distance, self.eps = max_distance, np.float32(eps)
+        self.dtype = np.dtype(dtype).type
+        self.max_distance, self.eps = max_distance, self.dtype(eps)
         w = {}
         for n in self.model.nodes:
             if not n.name:
@@ -59,26 +71,26 @@ class T5Oracle:
                 stack, blk, lay, mod, leaf, _ = m.groups()
                 t = self.model.tensor(n.inputs[1] if n.op == "MatMul" else n.inputs[0])
                 if t is not None:
-                    w[f"{stack}.{blk}.{lay}.{mod}.{leaf}"] = np.asarray(t, np.float32)
+                    w[f"{stack}.{blk}.{lay}.{mod}.{leaf}"] = np.asarray(t, self.dtype)
                 continue
             m = re.search(r"(encoder|decoder)/block\.(\d+)/layer\.(\d+)/layer_norm/Mul(_\d+)?$", n.name)
             if m and n.op == "Mul":
                 for i in n.inputs:
                     t = self.model.init.get(i)
                     if t is not None and t.ndim == 1:
-                        w[f"{m.group(1)}.{m.group(2)}.{m.group(3)}.layer_norm"] = np.asarray(t, np.float32)
+                        w[f"{m.group(1)}.{m.group(2)}.{m.group(3)}.layer_norm"] = np.asarray(t, self.dtype)
                 continue
             m = re.search(r"(encoder|decoder)/final_layer_norm/Mul(_\d+)?$", n.name)
             if m and n.op == "Mul":
                 for i in n.inputs:
                     t = self.model.init.get(i)
                     if t is not None and t.ndim == 1:
-                        w[f"{m.group(1)}.final_layer_norm"] = np.asarray(t, np.float32)
+                        w[f"{m.group(1)}.final_layer_norm"] = np.asarray(t, self.dtype)
                 continue
             if n.op == "Gather" and n.name.endswith("encoder/embed_tokens/Gather"):
-                w["shared"] = np.asarray(self.model.tensor(n.inputs[0]), np.float32)
+                w["shared"] = np.asarray(self.model.tensor(n.inputs[0]), self.dtype)
             if n.op == "MatMul" and n.name.endswith("lm_head/MatMul"):
-                w["lm_head"] = np.asarray(self.model.tensor(n.inputs[1]), np.float32)
+                w["lm_head"] = np.asarray(self.model.tensor(n.inputs[1]), self.dtype)
         self.w = w
         self.d_model = w["shared"].shape[1]
         self.n_enc = 1 + max(int(k.split(".")[1]) for k in w if k.startswith("encoder.") and k[8].isdigit())
@@ -94,10 +106,13 @@ class T5Oracle:
         lm = [n for n in self.model.nodes if n.op == "MatMul" and n.name.endswith("lm_head/MatMul")][0]
         p = prod.get(lm.inputs[0])
         self.tied = p is not None and p.op == "Mul" and "final_layer_norm" not in p.name
+        # feed-forward activation, by the nodes inside DenseReluDense (as the engine's reader tells them apart)
+        ops = {n.op for n in self.model.nodes if "DenseReluDense" in n.name}
+        self.act = "gelu_new" if "Tanh" in ops else ("gelu" if "Erf" in ops else "relu")
 
     def rms(self, x, g):
-        var = np.mean(x.astype(np.float32) ** 2, axis=-1, keepdims=True, dtype=np.float32)
-        return x * (1.0 / np.sqrt(var + self.eps)).astype(np.float32) * g
+        var = np.mean(x.astype(self.dtype) ** 2, axis=-1, keepdims=True, dtype=self.dtype)
+        return x * (1.0 / np.sqrt(var + self.eps)).astype(self.dtype) * g
 
     def attention(self, pfx, xq, xkv, bias):
         """xq [Tq, d], xkv [Tk, d], bias [heads, Tq, Tk] -> [Tq, d]   (no 1/sqrt(d) scaling in T5)"""
@@ -110,21 +125,22 @@ class T5Oracle:
         p = np.exp(s)
         p /= p.sum(-1, keepdims=True)
         o = (p @ v).transpose(1, 0, 2).reshape(-1, self.inner)
-        return (o @ w[pfx + ".o"]).astype(np.float32)
+        return (o @ w[pfx + ".o"]).astype(self.dtype)
 
     def ffn(self, pfx, x):
         w = self.w
-        if pfx + ".wi_0" in w:  # T5DenseGatedActDense, gated-gelu = gelu_new
-            h = gelu_new(x @ w[pfx + ".wi_0"]) * (x @ w[pfx + ".wi_1"])
-        else:                   # T5DenseActDense, relu
-            h = np.maximum(x @ w[pfx + ".wi"], 0)
-        return (h @ w[pfx + ".wo"]).astype(np.float32)
+        act = {"gelu_new": gelu_new, "gelu": gelu_erf, "relu": lambda a: np.maximum(a, 0)}[self.act]
+        if pfx + ".wi_0" in w:  # T5DenseGatedActDense
+            h = act(x @ w[pfx + ".wi_0"]) * (x @ w[pfx + ".wi_1"])
+        else:                   # T5DenseActDense
+            h = act(x @ w[pfx + ".wi"])
+        return (h @ w[pfx + ".wo"]).astype(self.dtype)
 
     def position_bias(self, stack, Tq, Tk, q_off=0):
         rel = np.arange(Tk)[None, :] - (np.arange(Tq)[:, None] + q_off)       # memory - context
         b = relative_position_bucket(rel, stack == "encoder", self.num_buckets, self.max_distance)
         table = self.w[f"{stack}.0.0.SelfAttention.relative_attention_bias"]   # [buckets, heads]; block 0's, shared
-        return table[b].transpose(2, 0, 1).astype(np.float32)
+        return table[b].transpose(2, 0, 1).astype(self.dtype)
 
     def encode(self, input_ids):
         x = self.w["shared"][np.asarray(input_ids, np.int64)]
@@ -134,13 +150,13 @@ class T5Oracle:
             x = x + self.attention(f"encoder.{b}.0.SelfAttention", self.rms(x, self.w[f"encoder.{b}.0.layer_norm"]),
                                    self.rms(x, self.w[f"encoder.{b}.0.layer_norm"]), bias)
             x = x + self.ffn(f"encoder.{b}.1.DenseReluDense", self.rms(x, self.w[f"encoder.{b}.1.layer_norm"]))
-        return self.rms(x, self.w["encoder.final_layer_norm"]).astype(np.float32)
+        return self.rms(x, self.w["encoder.final_layer_norm"]).astype(self.dtype)
 
     def decode(self, enc, decoder_input_ids):
         x = self.w["shared"][np.asarray(decoder_input_ids, np.int64)]
         T, S = x.shape[0], enc.shape[0]
-        bias = self.position_bias("decoder", T, T) + np.triu(np.full((T, T), -np.inf, np.float32), 1)[None]
-        zero = np.zeros((self.heads, T, S), np.float32)
+        bias = self.position_bias("decoder", T, T) + np.triu(np.full((T, T), -np.inf, self.dtype), 1)[None]
+        zero = np.zeros((self.heads, T, S), self.dtype)
         for b in range(self.n_dec):
             h = self.rms(x, self.w[f"decoder.{b}.0.layer_norm"])
             x = x + self.attention(f"decoder.{b}.0.SelfAttention", h, h, bias)
@@ -148,8 +164,8 @@ class T5Oracle:
             x = x + self.ffn(f"decoder.{b}.2.DenseReluDense", self.rms(x, self.w[f"decoder.{b}.2.layer_norm"]))
         x = self.rms(x, self.w["decoder.final_layer_norm"])
         if self.tied:
-            x = x * np.float32(self.d_model ** -0.5)
-        return (x @ self.w["lm_head"]).astype(np.float32)
+            x = x * self.dtype(self.d_model ** -0.5)
+        return (x @ self.w["lm_head"]).astype(self.dtype)
 
     def logits(self, input_ids, decoder_input_ids):
         """What `session.run(..., {"input_ids", "attention_mask", "decoder_input_ids"})[0]` returns for batch 1."""

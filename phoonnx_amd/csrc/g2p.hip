@@ -539,8 +539,10 @@ __device__ __forceinline__ void g2p_step_body(const G2PStepArgs &a, int blk, int
         // requested before the first FMA, so a row pays one or two memory latencies instead of one per KiB (the 3584-wide
         // output projection ran at 1.8 TB/s).  The loads are unconditional (a lane past the row's end re-reads the row's
         // last 16 bytes and its term is not added: a conditional load is a branch with a full wait at its join), and the
-        // launch-uniform options - second matrix, norm weights - select one of four branch-free variants.  Same sums in the
-        // same order (i ascending per lane).
+        // launch-uniform options - second matrix, norm weights - select one of four branch-free variants.  A lane adds its
+        // terms in the same order (i ascending) in every variant and for every NB; the NB instantiations are still not
+        // bit-identical per sequence (the compiler contracts each one's multiply-adds on its own: last-bit differences,
+        // tests/test_gpu_g2p_width.py grades each against float64).
         const int n4 = a.in >> 2;
         auto rows = [&](auto GATED, auto NORM) __attribute__((always_inline)) {
             constexpr bool gated = decltype(GATED)::value, norm = decltype(NORM)::value;
@@ -829,11 +831,48 @@ struct LinJob {
     const float *res;
     int64_t y_rs = 0, y_cs = 1;  // (0: the call's default row stride)
 };
-void linear(Run &r, std::initializer_list<LinJob> jobs, const float *x, int xp, int T, int64_t y_rs) {
-    // (the attribute belongs to the (function, device) pair: handles on different GPUs each set it, and no flag is
-    // shared between their threads; the call is idempotent and costs ~1 us)
-    G2PLinArgs a{};
+// Choose the kernel for filled arguments and launch it: the one place that decides, for the engine and for the test hook
+// (g2p_test_linear) alike.  `same_in`: every job contracts over a.in; `force_generic`: the A/B switch.
+hipError_t linear_launch(hipStream_t st, G2PLinArgs &a, bool same_in, bool force_generic) {
+    // (T <= 0 would make the branch-free kernel's column clamp `ncol - 1` index x[-1]; no ABI entry passes it)
+    if (a.njobs < 1 || a.njobs > 3 || a.in <= 0 || a.T <= 0 || a.xp < a.T) return hipErrorInvalidValue;
     int tiles = 0;
+    for (int j = 0; j < a.njobs; j++) tiles += a.job[j].tiles;
+    hipError_t err = hipSuccess;
+    auto note = [&](hipError_t e) {
+        if (err == hipSuccess && e != hipSuccess) err = e;
+    };
+    // (hipFuncSetAttribute below: the attribute belongs to the (function, device) pair - handles on different GPUs each set
+    // it, and no flag is shared between their threads; the call is idempotent and costs ~1 us)
+    // column tile: 128 wide.  (Narrower tiles on short grids - 32 columns at T = 80 - were measured slower: a
+    // workgroup's time is the latency of its weight rows, not its matrix work.)
+    a.cb = 8;
+    // The branch-free kernel serves the short column counts - the decoder step of 8 .. 32 sequences side by side: 0.67 -> 0.44 ms
+    // per step at 8 and 16 sequences - and loses to the generic one on wide tiles (encoder over 80 bytes x 4 inputs 4.4 -> 5.8 ms,
+    // x 64 inputs 48 -> 59 ms: at 5-8 column blocks its 190-230 registers and ~150 loads in flight per lane cost more than the
+    // generic kernel's serialised ones; profiles/r06_runs/g2p_linear_ab.txt), so those keep the generic kernel.
+    const bool whole = same_in && a.in % 16 == 0 && a.in >= 128 && a.T <= 32;  // (whole steps; every wave has at least one)
+    if (!whole || force_generic) {
+        note(hipFuncSetAttribute(reinterpret_cast<const void *>(g2p_linear_generic_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 64 * 1024));
+        g2p_linear_generic_kernel<<<dim3(tiles, (a.T + 16 * a.cb - 1) / (16 * a.cb)), 512, 64 * 1024, st>>>(a);
+        return err;
+    }
+    const int cb = (a.T + 15) / 16;  // 1 or 2
+    a.cb = cb;
+    const dim3 grid(tiles, 1);
+    if (cb == 1) {
+        note(hipFuncSetAttribute(reinterpret_cast<const void *>(g2p_linear_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+        g2p_linear_kernel<1><<<grid, 512, 64 * 1024, st>>>(a);
+    } else {
+        note(hipFuncSetAttribute(reinterpret_cast<const void *>(g2p_linear_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+        g2p_linear_kernel<2><<<grid, 512, 64 * 1024, st>>>(a);
+    }
+    return err;
+}
+void linear(Run &r, std::initializer_list<LinJob> jobs, const float *x, int xp, int T, int64_t y_rs) {
+    G2PLinArgs a{};
+    bool same_in = true;
     for (const LinJob &j : jobs) {
         G2PLinJob &d = a.job[a.njobs++];
         d.W = r.P(j.L->rowmajor);
@@ -843,38 +882,14 @@ void linear(Run &r, std::initializer_list<LinJob> jobs, const float *x, int xp, 
         d.tiles = (j.L->out + 15) / 16;
         d.y_rs = j.y_rs ? j.y_rs : y_rs;
         d.y_cs = j.y_cs;
-        tiles += d.tiles;
+        same_in = same_in && (a.njobs == 1 || j.L->in == a.in);
         a.in = j.L->in;
     }
     a.x = x;
     a.T = T;
     a.xp = xp;
-    // column tile: 128 wide.  (Narrower tiles on short grids - 32 columns at T = 80 - were measured slower: a
-    // workgroup's time is the latency of its weight rows, not its matrix work.)
-    a.cb = 8;
-    // The branch-free kernel serves the short column counts - the decoder step of 8 .. 32 sequences side by side: 0.67 -> 0.44 ms
-    // per step at 8 and 16 sequences - and loses to the generic one on wide tiles (encoder over 80 bytes x 4 inputs 4.4 -> 5.8 ms,
-    // x 64 inputs 48 -> 59 ms: at 5-8 column blocks its 190-230 registers and ~150 loads in flight per lane cost more than the
-    // generic kernel's serialised ones; profiles/r06_runs/g2p_linear_ab.txt), so those keep the generic kernel.
-    bool whole = a.in % 16 == 0 && a.in >= 128 && T <= 32;  // (whole steps; every wave has at least one)
-    for (const LinJob &j : jobs) whole = whole && j.L->in == a.in;
     static const bool generic_only = std::getenv("VITSMI_G2P_LINEAR_GENERIC") != nullptr;  // (A/B)
-    if (!whole || generic_only) {
-        r.note(hipFuncSetAttribute(reinterpret_cast<const void *>(g2p_linear_generic_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   64 * 1024));
-        g2p_linear_generic_kernel<<<dim3(tiles, (T + 16 * a.cb - 1) / (16 * a.cb)), 512, 64 * 1024, r.st>>>(a);
-        return;
-    }
-    const int cb = (T + 15) / 16;  // 1 or 2
-    a.cb = cb;
-    const dim3 grid(tiles, 1);
-    if (cb == 1) {
-        r.note(hipFuncSetAttribute(reinterpret_cast<const void *>(g2p_linear_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-        g2p_linear_kernel<1><<<grid, 512, 64 * 1024, r.st>>>(a);
-    } else {
-        r.note(hipFuncSetAttribute(reinterpret_cast<const void *>(g2p_linear_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-        g2p_linear_kernel<2><<<grid, 512, 64 * 1024, r.st>>>(a);
-    }
+    r.note(linear_launch(r.st, a, same_in, generic_only));
 }
 void linear(Run &r, const T5Linear &L, const float *x, int xp, int T, float *y, int yp, const float *res = nullptr) {
     linear(r, {{&L, y, res}}, x, xp, T, yp);
@@ -888,9 +903,21 @@ struct StepJob {
     int ys, yb;
     const float *res;
 };
+// The NB switch for filled arguments: shared by the engine and the test hook (g2p_test_step).
+hipError_t step_launch(hipStream_t st, int nb, const G2PStepArgs &a) {
+    if (a.njobs < 1 || a.njobs > 3 || a.in <= 0) return hipErrorInvalidValue;
+    int blocks = 0;
+    for (int j = 0; j < a.njobs; j++) blocks += a.job[j].blocks;
+    switch (nb) {
+        case 1: g2p_step_kernel<1><<<blocks, 256, 0, st>>>(a); break;
+        case 2: g2p_step_kernel<2><<<blocks, 256, 0, st>>>(a); break;
+        case 4: g2p_step_kernel<4><<<blocks, 256, 0, st>>>(a); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipSuccess;
+}
 void step(Run &r, int nb, std::initializer_list<StepJob> jobs, const float *x, int64_t g, int act = -1, float post = 1.f) {
     G2PStepArgs a{};
-    int blocks = 0;
     for (const StepJob &j : jobs) {
         G2PStepJob &d = a.job[a.njobs++];
         d.W = r.P(j.L->rowmajor);
@@ -901,7 +928,6 @@ void step(Run &r, int nb, std::initializer_list<StepJob> jobs, const float *x, i
         d.res = j.res;
         d.out = j.L->out;
         d.blocks = (j.L->out + 3) / 4;
-        blocks += d.blocks;
         a.in = j.L->in;
     }
     a.x = x;
@@ -909,12 +935,7 @@ void step(Run &r, int nb, std::initializer_list<StepJob> jobs, const float *x, i
     a.act = act;
     a.eps = r.h->model.eps;
     a.post = post;
-    switch (nb) {
-        case 1: g2p_step_kernel<1><<<blocks, 256, 0, r.st>>>(a); break;
-        case 2: g2p_step_kernel<2><<<blocks, 256, 0, r.st>>>(a); break;
-        case 4: g2p_step_kernel<4><<<blocks, 256, 0, r.st>>>(a); break;
-        default: g2p_step_kernel<4><<<blocks, 256, 0, r.st>>>(a); break;
-    }
+    r.note(step_launch(r.st, nb, a));
 }
 
 void rmsnorm(Run &r, const float *x, int xp, int64_t g, float *y, int yp, int T) {
@@ -1161,14 +1182,15 @@ int g2p_run(g2p_handle *h, const int64_t *input_ids, int S, const int64_t *mask,
 // forced / step_logits (g2p_test_forced_steps): the decoder inputs are GIVEN - forced[b][t], t < max_length, forced[b][0] the
 // start token - instead of fed back from the argmax, and the logits every step computes, [max_length][NB][vocab], are copied
 // out: the step path (matrix-vector kernels, one-query attention over the caches) as a function that can be compared with
-// g2p_run's logits for the same decoder_input_ids, number by number.  Narrow steps only (B <= 4).
+// g2p_run's logits for the same decoder_input_ids, number by number.  Narrow steps (B <= 4: logits [NB][vocab], copied) and
+// wide ones (logits [vocab][NB], transposed into the same [NB][vocab] record).
 static int generate_impl(g2p_handle *h, const int64_t *input_ids, const int *lens, int B, int max_length, int64_t start_id,
                          int64_t eos_id, int64_t *out_ids, int *n_out, const int64_t *forced, float *step_logits) {
     if (int rc = check_dev(h)) return rc;
     std::lock_guard<std::mutex> lk(h->mu);
     const G2PModel &m = h->model;
     if (!input_ids || !lens || !out_ids || !n_out || B <= 0 || max_length <= 0) return gfail(h, VITS_E_ARG, "bad g2p_generate arguments");
-    if (forced && (!step_logits || B > 4)) return gfail(h, VITS_E_ARG, "forced steps: at most 4 sequences, logits required");
+    if (forced && !step_logits) return gfail(h, VITS_E_ARG, "forced steps: logits required");
     if (B > G2P_MAX_BATCH) return gfail(h, VITS_E_ARG, "at most %d sequences per call", G2P_MAX_BATCH);
     if (max_length >= G2PModel::kMaxPos) return gfail(h, VITS_E_ARG, "sequence longer than %d", G2PModel::kMaxPos - 1);
     if (start_id < 0 || start_id >= m.vocab) return gfail(h, VITS_E_ARG, "start id out of range");
@@ -1179,6 +1201,8 @@ static int generate_impl(g2p_handle *h, const int64_t *input_ids, const int *len
         total += lens[b];
     }
     if (int rc = check_ids(h, input_ids, total, "input_ids")) return rc;
+    if (forced)
+        if (int rc = check_ids(h, forced, B * max_length, "decoder_input_ids")) return rc;
     // NB sequences run side by side (B rounded up to a size the step kernel is instantiated for; the spare ones decode
     // a one-token input and are ignored)
     int NB = 1;
@@ -1358,7 +1382,9 @@ static int generate_impl(g2p_handle *h, const int64_t *input_ids, const int *len
         rmsnorm(r, x1, NB, m.dec_final_ln, h1, NB, NB);
         if (m.scale_out) g2p_scale_kernel<<<(unsigned)(((size_t)D * NB + 255) / 256), 256, 0, st>>>(h1, (int64_t)D * NB, post);
         linear(r, m.lm_head, h1, NB, NB, lg, NB);
-        g2p_argmax_kernel<<<NB, 256, 0, st>>>(lg, m.vocab, NB, 0, 1, d_gen, TM, t + 1, h->tok_dev);
+        g2p_argmax_kernel<<<NB, 256, 0, st>>>(lg, m.vocab, NB, 0, 1, d_arg, TM, t + 1, h->tok_dev);
+        if (forced)  // [vocab][NB] -> this step's [NB][vocab]
+            g2p_transpose_kernel<<<dim3((m.vocab + 255) / 256, NB), 256, 0, st>>>(lg, d_steplog + (size_t)t * NB * m.vocab, m.vocab, NB);
         r.note(hipGetLastError());
         r.note(hipEventRecord(h->step_done[t & 1], st));
     };
@@ -1448,11 +1474,114 @@ int g2p_test_forced_steps(g2p_handle *h, const int64_t *input_ids, const int *le
                           float *logits) {
     if (!h) return VITS_E_ARG;
     if (!decoder_input_ids || !logits || T <= 0 || B <= 0) return gfail(h, VITS_E_ARG, "bad g2p_test_forced_steps arguments");
-    for (size_t i = 0; i < (size_t)B * T; i++)
-        if (decoder_input_ids[i] < 0 || decoder_input_ids[i] >= h->model.vocab) return gfail(h, VITS_E_ARG, "decoder id out of range");
+    if (B > G2P_MAX_BATCH) return gfail(h, VITS_E_ARG, "at most %d sequences per call", G2P_MAX_BATCH);
+    // (the ids are range-checked in generate_impl, behind check_dev and the handle's mutex)
     std::vector<int64_t> ids((size_t)B * T);
     std::vector<int> n(B);
     return generate_impl(h, input_ids, lens, B, T, decoder_input_ids[0], -1, ids.data(), n.data(), decoder_input_ids, logits);
+}
+
+// ---- kernel-level test hooks: host buffers in, host buffers out, through linear_launch / step_launch (the engine's choice of
+// kernel), on a stream of their own
+namespace {
+struct DevBufs {
+    std::vector<void *> p;
+    ~DevBufs() {
+        for (void *q : p) hipFree(q);
+    }
+    float *up(const float *host, size_t n, bool &ok) {
+        void *d = nullptr;
+        if (!ok || hipMalloc(&d, (n ? n : 1) * sizeof(float)) != hipSuccess) {
+            ok = false;
+            return nullptr;
+        }
+        p.push_back(d);
+        if (host && hipMemcpy(d, host, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) ok = false;
+        return static_cast<float *>(d);
+    }
+};
+}  // namespace
+
+int g2p_test_linear(int device, int njobs, const float *const *W, const int *out, int in, const float *x, int T, int xp,
+                    const float *const *res, int64_t y_rs, int64_t y_cs, int mode, float *const *y) {
+    if (njobs < 1 || njobs > 3 || !W || !out || !x || !y || in < 1 || T < 1 || xp < T || (mode != 0 && mode != 1))
+        return gfail(nullptr, VITS_E_ARG, "bad g2p_test_linear arguments");
+    if (in > (1 << 16) || T > (1 << 16)) return gfail(nullptr, VITS_E_ARG, "g2p_test_linear: in / T too large");
+    size_t ny[3] = {0, 0, 0};
+    for (int j = 0; j < njobs; j++) {
+        if (!W[j] || !y[j] || out[j] < 1 || out[j] > (1 << 20)) return gfail(nullptr, VITS_E_ARG, "bad g2p_test_linear job %d", j);
+        // every (row, column) its own element: columns inside a row, or rows inside a column (the cache layout)
+        const bool rows_outer = y_cs >= 1 && y_rs >= y_cs * (T - 1) + 1, cols_outer = y_rs >= 1 && y_cs >= y_rs * (out[j] - 1) + 1;
+        if (!rows_outer && !cols_outer) return gfail(nullptr, VITS_E_ARG, "g2p_test_linear: output strides overlap");
+        ny[j] = (size_t)((int64_t)(out[j] - 1) * y_rs + (int64_t)(T - 1) * y_cs + 1);
+        if (ny[j] > ((size_t)1 << 28)) return gfail(nullptr, VITS_E_ARG, "g2p_test_linear: output too large");
+    }
+    if (hipSetDevice(device) != hipSuccess) return gfail(nullptr, VITS_E_DEVICE, "hipSetDevice(%d) failed", device);
+    DevBufs B;
+    bool ok = true;
+    G2PLinArgs a{};
+    a.njobs = njobs;
+    a.in = in;
+    a.T = T;
+    a.xp = xp;
+    a.x = B.up(x, (size_t)in * xp, ok);
+    for (int j = 0; j < njobs; j++) {
+        G2PLinJob &d = a.job[j];
+        d.W = B.up(W[j], (size_t)out[j] * in, ok);
+        d.y = B.up(y[j], ny[j], ok);  // (what the kernel does not write comes back as it went in)
+        d.res = res && res[j] ? B.up(res[j], ny[j], ok) : nullptr;
+        d.out = out[j];
+        d.tiles = (out[j] + 15) / 16;
+        d.y_rs = y_rs;
+        d.y_cs = y_cs;
+    }
+    if (!ok) return gfail(nullptr, VITS_E_NOMEM, "g2p_test_linear: device buffers");
+    hipError_t e = linear_launch(nullptr, a, true, mode == 1);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    for (int j = 0; j < njobs && e == hipSuccess; j++) e = hipMemcpy(y[j], a.job[j].y, ny[j] * sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return gfail(nullptr, VITS_E_DEVICE, "g2p_test_linear failed: %s", hipGetErrorString(e));
+    return VITS_OK;
+}
+
+int g2p_test_step(int device, int NB, int njobs, const float *const *W, const float *const *W2, const int *out, int in,
+                  const float *x, const float *g, int act, float eps, float post, const float *const *res, float *const *y) {
+    if ((NB != 1 && NB != 2 && NB != 4) || njobs < 1 || njobs > 3 || !W || !out || !x || !y || in < 1 || in > (1 << 20) || act < -1 ||
+        act > 2 || !(eps >= 0.f))
+        return gfail(nullptr, VITS_E_ARG, "bad g2p_test_step arguments");
+    for (int j = 0; j < njobs; j++)
+        if (!W[j] || !y[j] || out[j] < 1 || out[j] > (1 << 20)) return gfail(nullptr, VITS_E_ARG, "bad g2p_test_step job %d", j);
+    if (hipSetDevice(device) != hipSuccess) return gfail(nullptr, VITS_E_DEVICE, "hipSetDevice(%d) failed", device);
+    DevBufs B;
+    bool ok = true;
+    G2PStepArgs a{};
+    a.njobs = njobs;
+    a.in = in;
+    a.act = act;
+    a.eps = eps;
+    a.post = post;
+    a.x = B.up(x, (size_t)NB * in, ok);
+    a.g = g ? B.up(g, (size_t)in, ok) : nullptr;
+    for (int j = 0; j < njobs; j++) {
+        G2PStepJob &d = a.job[j];
+        const size_t n = (size_t)NB * out[j];  // y / res: [NB][out]
+        d.W = B.up(W[j], (size_t)out[j] * in, ok);
+        d.W2 = W2 && W2[j] ? B.up(W2[j], (size_t)out[j] * in, ok) : nullptr;
+        d.y = B.up(y[j], n, ok);
+        d.res = res && res[j] ? B.up(res[j], n, ok) : nullptr;
+        d.ys = 1;
+        d.yb = out[j];
+        d.out = out[j];
+        d.blocks = (out[j] + 3) / 4;
+    }
+    if (!ok) return gfail(nullptr, VITS_E_NOMEM, "g2p_test_step: device buffers");
+    hipError_t e = step_launch(nullptr, NB, a);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    for (int j = 0; j < njobs && e == hipSuccess; j++)
+        e = hipMemcpy(y[j], a.job[j].y, (size_t)NB * out[j] * sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return gfail(nullptr, VITS_E_DEVICE, "g2p_test_step failed: %s", hipGetErrorString(e));
+    return VITS_OK;
 }
 
 int g2p_generate(g2p_handle *h, const int64_t *input_ids, int S, int max_length, int64_t start_id, int64_t eos_id,

@@ -226,9 +226,10 @@ class MiG2PSession:
 
 
     def forced_step_logits(self, inputs: Sequence[Sequence[int]], decoder_input_ids) -> np.ndarray:
-        """Test hook (g2p_test_forced_steps): the decoder-step kernels of `generate` driven with GIVEN decoder inputs
-        [B, T] (column 0 = the start token) for up to four inputs side by side -> the logits of every step, float32
-        [B, T, vocab]: position t equals what run() returns there for decoder_input_ids[:, :t + 1]."""
+        """Test hook (g2p_test_forced_steps): the decoder-step kernels of `generate` / `generate_batch` driven with GIVEN
+        decoder inputs [B, T] (column 0 = the start token) for up to MAX_BATCH inputs side by side (up to four: the
+        matrix-vector step; more: the wide step) -> the logits of every step, float32 [B, T, vocab]: position t equals
+        what run() returns there for decoder_input_ids[:, :t + 1]."""
         seqs = [np.ascontiguousarray(np.asarray(x, np.int64).reshape(-1)) for x in inputs]
         dec = np.ascontiguousarray(np.asarray(decoder_input_ids, np.int64))
         if dec.ndim != 2 or dec.shape[0] != len(seqs):
@@ -242,6 +243,71 @@ class MiG2PSession:
         if rc != 0:
             raise SessionError(f"g2p_test_forced_steps failed [{rc}]: {self._err()}")
         return out
+
+
+def _ptr_array(arrs):
+    """const float *const [n] of host arrays (None -> NULL); None for no array at all"""
+    if arrs is None:
+        return None
+    return (C.c_void_p * len(arrs))(*[None if a is None else a.ctypes.data for a in arrs])
+
+
+def test_linear(Ws, x, T=None, res=None, y_rs=None, y_cs=1, mode=0, fill=0.0, device_id=0):
+    """Kernel test (g2p_test_linear): the engine's short-sequence Linear launch.  Ws: 1 .. 3 float32 matrices [out_j, in];
+    x [in, xp] of which the first T columns count (default: all).  Output element (row, col) of job j at flat index
+    row * y_rs + col * y_cs (default y_rs = T: a plain [out_j, T] matrix); res: per job None or an array of the output's
+    flat size.  mode 0: the kernel the engine chooses, 1: the generic kernel.  Returns the flat float32 outputs, pre-filled
+    with `fill` (what the kernel does not write keeps it)."""
+    lib = _ffi.load()
+    Ws = [np.ascontiguousarray(w, np.float32) for w in Ws]
+    x = np.ascontiguousarray(x, np.float32)
+    n_in, xp = x.shape
+    T = xp if T is None else int(T)
+    y_rs = T if y_rs is None else int(y_rs)
+    outs = np.array([w.shape[0] for w in Ws], np.int32)
+    if any(w.ndim != 2 or w.shape[1] != n_in for w in Ws):
+        raise SessionError("test_linear: every W must be [out, in] with in = x.shape[0]")
+    sizes = [(int(o) - 1) * y_rs + (T - 1) * int(y_cs) + 1 for o in outs]
+    if min(sizes) < 1:
+        raise SessionError("test_linear: bad strides")
+    ys = [np.full(n, fill, np.float32) for n in sizes]
+    rs = None
+    if res is not None:
+        rs = [None if r is None else np.ascontiguousarray(r, np.float32).reshape(-1) for r in res]
+        if len(rs) != len(Ws) or any(r is not None and r.size != n for r, n in zip(rs, sizes)):
+            raise SessionError("test_linear: res must hold one entry per job, of the output's flat size")
+    rc = lib.g2p_test_linear(device_id, len(Ws), _ptr_array(Ws), _ffi.ptr(outs), n_in, _ffi.ptr(x), T, xp, _ptr_array(rs),
+                             y_rs, int(y_cs), int(mode), _ptr_array(ys))
+    if rc != 0:
+        raise SessionError(f"g2p_test_linear failed [{rc}]: {lib.g2p_last_error(None).decode()}")
+    return ys
+
+
+def test_step(Ws, x, W2s=None, g=None, act=-1, eps=1e-6, post=1.0, res=None, device_id=0):
+    """Kernel test (g2p_test_step): the decoder step's matrix-vector launch for x [NB, in], NB in 1 / 2 / 4, and 1 .. 3
+    matrices [out_j, in] (W2s: per job None or the gate's second matrix; g: RMS-norm weights [in] or None; res: per job
+    None or [NB, out_j]).  Returns float32 [NB, out_j] per job."""
+    lib = _ffi.load()
+    Ws = [np.ascontiguousarray(w, np.float32) for w in Ws]
+    x = np.ascontiguousarray(x, np.float32)
+    NB, n_in = x.shape
+    if any(w.ndim != 2 or w.shape[1] != n_in for w in Ws):
+        raise SessionError("test_step: every W must be [out, in] with in = x.shape[1]")
+    outs = np.array([w.shape[0] for w in Ws], np.int32)
+    cast = lambda lst, shapes: None if lst is None else [
+        None if a is None else np.ascontiguousarray(a, np.float32).reshape(sh) for a, sh in zip(lst, shapes)]
+    W2 = cast(W2s, [w.shape for w in Ws])
+    rs = cast(res, [(NB, int(o)) for o in outs])
+    gv = None if g is None else np.ascontiguousarray(g, np.float32).reshape(n_in)
+    ys = [np.zeros((NB, int(o)), np.float32) for o in outs]
+    rc = lib.g2p_test_step(device_id, NB, len(Ws), _ptr_array(Ws), _ptr_array(W2), _ffi.ptr(outs), n_in, _ffi.ptr(x),
+                           _ffi.ptr(gv), int(act), float(eps), float(post), _ptr_array(rs), _ptr_array(ys))
+    if rc != 0:
+        raise SessionError(f"g2p_test_step failed [{rc}]: {lib.g2p_last_error(None).decode()}")
+    return ys
+
+
+test_linear.__test__ = test_step.__test__ = False  # (helpers, not test cases)
 
 
 class ByT5Phonemizer(SimplePhonemizer):

@@ -1,4 +1,5 @@
-"""Synthetic VITS voices for benchmarking and full-size parity tests.
+"""Synthetic VITS voices for benchmarking and full-size parity tests (write_voice), and synthetic ByT5 G2P models for the
+G2P engine's full-width tests (write_t5, at the end).
 
 The reference tree ships no trained voice and the GPU box has no network, so `bench.py`
 and the full-size tests need `.onnx` files with the exact structure `export_onnx.py`
@@ -271,6 +272,139 @@ def write_voice(path, preset="medium", seed=1234, extra_inputs=(), **over):
            "phoneme_id_map": {chr(97 + i): i + 1 for i in range(26)}}
     with open(path + ".json", "w") as f:
         json.dump(cfg, f)
+    return hp
+
+
+# ---------------------------------------------------------------- ByT5 G2P models
+T5_BASE = dict(d_model=1472, d_kv=64, num_heads=6, d_ff=3584, num_layers=12, num_decoder_layers=4, vocab_size=384,
+               feed_forward_proj="gated-gelu", tied=False, num_buckets=32)   # g2p-mbyt5-12l (the ByT5-small shape)
+
+
+def _t5_path(mod):
+    """'encoder.block.3.layer.0.SelfAttention' -> '/encoder/block.3/layer.0/SelfAttention' (the exporter's node scopes)"""
+    out = ""
+    for part in mod.split("."):
+        out += ("." if part.isdigit() else "/") + part
+    return out
+
+
+def write_t5(path, seed=1234, **geometry):
+    """Write `<path>`: a T5ForConditionalGeneration graph with seeded random weights, as far as the two readers of this
+    project (phoonnx_amd/csrc/model.cpp G2PModel::build, oracle/t5_oracle.py) look at one - the nodes that carry parameters
+    under the names the torchscript exporter gives them (`/encoder/block.N/layer.M/SelfAttention/q/MatMul` with an anonymous
+    transposed `onnx::MatMul_K` initializer, `.../layer_norm/Mul_1`, `.../relative_attention_bias/Gather` in block 0 of each
+    stack, `/encoder/embed_tokens/Gather`, `/lm_head/MatMul`), the nodes that tell the feed-forward families apart (`Tanh` /
+    `Erf` / `Relu` under `DenseReluDense/act`) and, for tied embeddings, the `Mul` by d_model^-0.5 in front of lm_head.
+    Inputs input_ids, attention_mask, decoder_input_ids; output logits.  The G2P models themselves are downloads
+    (mul.py:25-29); this gives the tests their widths without one.
+
+    geometry: d_model, d_kv, num_heads, d_ff, num_layers, num_decoder_layers, vocab_size, num_buckets,
+    feed_forward_proj in ("gated-gelu", "relu", "gelu"), tied.  Defaults: the ByT5-small shape.
+
+    Weights: normal, standard deviations of transformers' T5 initialisation (factor 1) - embedding 1; q (d_model d_kv)^-1/2;
+    k, v d_model^-1/2; o (num_heads d_kv)^-1/2; wi, wi_0, wi_1 d_model^-1/2; wo d_ff^-1/2 - which keeps the residual stream
+    O(1 .. 10) at any width.  Three departures, so that nothing is a no-op and logits stay O(30): layer-norm weights are
+    1 + 0.1 noise (not 1), relative-attention biases have standard deviation 0.5 (not d_model^-1/2: next to scores of
+    standard deviation 1 that would vanish at width 1472), an untied lm_head has 8 d_model^-1/2 (not 1: logits of standard
+    deviation sqrt(d_model)); a tied lm_head is the embedding table.  Returns the geometry dict."""
+    hp = dict(T5_BASE)
+    unknown = set(geometry) - set(hp)
+    if unknown:
+        raise ValueError(f"write_t5: unknown options {sorted(unknown)}")
+    hp.update(geometry)
+    D, dk, H, FF, V = hp["d_model"], hp["d_kv"], hp["num_heads"], hp["d_ff"], hp["vocab_size"]
+    ffp, tied, I = hp["feed_forward_proj"], bool(hp["tied"]), hp["num_heads"] * hp["d_kv"]
+    if ffp not in ("gated-gelu", "relu", "gelu"):
+        raise ValueError(f"write_t5: feed_forward_proj {ffp!r}")
+    rng = np.random.default_rng(seed)
+    N = lambda *s, std=1.0: rng.standard_normal(s, dtype=np.float32) * np.float32(std)
+    nodes, inits, anon = [], [], [1000]   # inits: byte pieces; the weights themselves are not copied until they are written
+
+    def init(name, arr):
+        arr = np.ascontiguousarray(arr, np.float32)
+        head = b"".join(_vi(1, d) for d in arr.shape) + _vi(2, 1) + _ld(8, name.encode())
+        raw = memoryview(arr).cast("B")
+        data_tag = _vint((9 << 3) | 2) + _vint(len(raw))
+        inits.extend([_vint((5 << 3) | 2) + _vint(len(head) + len(data_tag) + len(raw)), head, data_tag, raw])
+        return name
+
+    def node(op, name, inputs):
+        nodes.append(_ld(1, _node(op, name, inputs, [name + "_output_0"])))
+        return name + "_output_0"
+
+    def matmul(name, x, w_in_out):
+        anon[0] += 1
+        return node("MatMul", name + "/MatMul", [x, init(f"onnx::MatMul_{anon[0]}", w_in_out)])
+
+    def norm(mod, x):   # T5LayerNorm: x * rsqrt(mean(x^2) + eps), then the weight
+        p = _t5_path(mod)
+        h = node("Mul", p + "/Mul", [x, node("Pow", p + "/Pow", [x])])
+        return node("Mul", p + "/Mul_1", [init(mod + ".weight", 1 + N(D, std=0.1)), h])
+
+    def attention(mod, x, kv, bias):
+        p = _t5_path(mod)
+        q = matmul(p + "/q", x, N(D, I, std=(D * dk) ** -0.5))
+        k = matmul(p + "/k", kv, N(D, I, std=D ** -0.5))
+        v = matmul(p + "/v", kv, N(D, I, std=D ** -0.5))
+        s = node("MatMul", p + "/MatMul", [q, k])
+        if bias:
+            b = node("Gather", p + "/relative_attention_bias/Gather",
+                     [init(mod + ".relative_attention_bias.weight", N(hp["num_buckets"], H, std=0.5)), p + "/bucket"])
+            s = node("Add", p + "/Add", [s, b])
+        a = node("MatMul", p + "/MatMul_1", [node("Softmax", p + "/Softmax", [s]), v])
+        return matmul(p + "/o", a, N(I, D, std=I ** -0.5))
+
+    def ffn(mod, x):
+        p = _t5_path(mod)
+        if ffp == "gated-gelu":   # gelu_new(wi_0 x) * (wi_1 x)
+            a = matmul(p + "/wi_0", x, N(D, FF, std=D ** -0.5))
+            t = node("Tanh", p + "/act/Tanh", [node("Pow", p + "/act/Pow", [a])])
+            b = matmul(p + "/wi_1", x, N(D, FF, std=D ** -0.5))
+            h = node("Mul", p + "/Mul", [node("Mul", p + "/act/Mul_3", [a, t]), b])
+        else:
+            a = matmul(p + "/wi", x, N(D, FF, std=D ** -0.5))
+            h = node("Relu", p + "/act/Relu", [a]) if ffp == "relu" else \
+                node("Mul", p + "/act/Mul_1", [a, node("Erf", p + "/act/Erf", [node("Div", p + "/act/Div", [a])])])
+        return matmul(p + "/wo", h, N(FF, D, std=FF ** -0.5))
+
+    table = N(V, D)
+    shared = init("shared.weight", table)
+    x = node("Gather", "/encoder/embed_tokens/Gather", [shared, "input_ids"])
+    for b in range(hp["num_layers"]):
+        m = f"encoder.block.{b}"
+        x = node("Add", f"/encoder/block.{b}/layer.0/Add",
+                 [x, attention(f"{m}.layer.0.SelfAttention", *[norm(f"{m}.layer.0.layer_norm", x)] * 2, bias=b == 0)])
+        x = node("Add", f"/encoder/block.{b}/layer.1/Add", [x, ffn(f"{m}.layer.1.DenseReluDense", norm(f"{m}.layer.1.layer_norm", x))])
+    enc = norm("encoder.final_layer_norm", x)
+    x = node("Gather", "/decoder/embed_tokens/Gather", [shared, "decoder_input_ids"])
+    for b in range(hp["num_decoder_layers"]):
+        m = f"decoder.block.{b}"
+        x = node("Add", f"/decoder/block.{b}/layer.0/Add",
+                 [x, attention(f"{m}.layer.0.SelfAttention", *[norm(f"{m}.layer.0.layer_norm", x)] * 2, bias=b == 0)])
+        x = node("Add", f"/decoder/block.{b}/layer.1/Add",
+                 [x, attention(f"{m}.layer.1.EncDecAttention", norm(f"{m}.layer.1.layer_norm", x), enc, bias=False)])
+        x = node("Add", f"/decoder/block.{b}/layer.2/Add", [x, ffn(f"{m}.layer.2.DenseReluDense", norm(f"{m}.layer.2.layer_norm", x))])
+    x = norm("decoder.final_layer_norm", x)
+    if tied:   # T5ForConditionalGeneration.forward: sequence_output * d_model^-0.5 when the head shares the embedding
+        nodes.append(_ld(1, _node("Constant", "/Constant", [], ["/Constant_output_0"],
+                                  _ld(5, _ld(1, b"value") + _ld(5, _vi(2, 1) + _ld(9, np.float32(D ** -0.5).tobytes())) + _vi(20, 4)))))
+        x = node("Mul", "/Mul", [x, "/Constant_output_0"])
+    anon[0] += 1
+    w = init(f"onnx::MatMul_{anon[0]}", table.T if tied else N(D, V, std=8 * D ** -0.5))
+    nodes.append(_ld(1, _node("MatMul", "/lm_head/MatMul", [x, w], ["logits"])))
+
+    inputs = ["input_ids", "attention_mask", "decoder_input_ids"]
+    g_head = b"".join(nodes) + _ld(2, b"main_graph")
+    g_tail = b"".join(_ld(11, _ld(1, n.encode())) for n in inputs) + _ld(12, _ld(1, b"logits"))
+    g_len = len(g_head) + sum(len(p) for p in inits) + len(g_tail)
+    os.makedirs(os.path.dirname(os.path.abspath(path)) or ".", exist_ok=True)
+    tmp = f"{path}.tmp{os.getpid()}"   # (tests share a cache directory: never a half-written model under the final name)
+    with open(tmp, "wb") as f:
+        f.write(_vi(1, 8) + _ld(2, b"pytorch") + _ld(3, b"2.10.0") + _vint((7 << 3) | 2) + _vint(g_len) + g_head)
+        for p in inits:
+            f.write(p)
+        f.write(g_tail + _ld(8, _ld(1, b"") + _vi(2, 15)))
+    os.replace(tmp, path)
     return hp
 
 
