@@ -6,7 +6,7 @@
 // Why: these layers are HBM-bound (8-20 FLOP/B, 4-5 TB/s measured).  As two launches of conv_sx_kernel a step moves
 // 20 bytes per element: c1 reads x and writes the intermediate, c2 reads the intermediate AND x (the residual) and
 // writes the result.  Here the intermediate never leaves the CU - it is produced as the fp16 operand planes c2 reads,
-// directly into LDS - and x is read once (the residual is requested next to the x tile, cf. SX_RES_EARLY):
+// directly into LDS - and x is read once (the registers the tile is loaded into are the residual, SX_PAIR_ONE_READ*):
 // ~4 * (1 + halo/256) + 4 bytes per element, 2.1-2.3x less.  The matrix work is the same (+ the 2-10 overlap columns
 // of a 256-column tile), so the matrix pipe is about twice as busy as in the two-launch form.
 //
@@ -16,7 +16,8 @@
 //
 // Structure (one workgroup = 4 waves, all C output channels, 256 columns):
 //   prologue the whole x tile (all channels, 256 + halo columns) global -> registers -> lrelu -> fp16 split -> LDS, one
-//            HBM round trip;
+//            HBM round trip; the 256 columns the waves produce are loaded in the accumulator layout and stay in registers
+//            as the residual, the halo columns pass through transient registers;
 //   phase 1  c1 over columns [t0 - P2, t0 - P2 + 256) from that tile: weights global -> registers one step ahead, B
 //            fragments from LDS, no DMA and no barriers;
 //   hand-over  accumulators * 2^-k1 + bias1 -> lrelu -> two fp16 planes -> LDS array Y[chunk][plane][half][col]
@@ -71,8 +72,9 @@ struct SxPairArgs {
     int xgs = 0;              // XCD grouping of the time tiles (SxArgs::xgs)
 };
 
-// (the 32-channel variant needs ~165 registers and <= 40 KiB of LDS: three workgroups per CU hide more of each
-// other's load / hand-over / store phases than two; the 64-channel one holds 64 accumulators + 64 residual registers)
+// (the 32-channel variant needs 124-133 registers and <= 40 KiB of LDS: three workgroups per CU hide more of each
+// other's load / hand-over / store phases than two; the 64-channel one holds 64 accumulators + 64 residual registers
+// from the prologue to the epilogue: 207-223 registers.  No instantiation uses scratch - see the `pk` pins in the kernel)
 #ifndef SX_PAIR_PROF
 #define SX_PAIR_PROF 0  // diagnostic build: s_memtime stamps at the phase boundaries, summed per launch into SxPairArgs::prof
 #endif
@@ -90,7 +92,7 @@ struct SxPairArgs {
 #define SX_PAIR_DEPTH64 2
 #endif
 #ifndef SX_PAIR_EARLY_ACC
-#define SX_PAIR_EARLY_ACC 0
+#define SX_PAIR_EARLY_ACC 0  // (experiment, 32 channels: the running sum requested in the prologue too; only builds with SX_PAIR_ONE_READ32=0)
 #endif
 #ifndef SX_PAIR_WGS32
 #define SX_PAIR_WGS32 3  // workgroups per CU the 32-channel variant is compiled for (4 = 128 registers: 116-172 bytes of scratch
@@ -102,6 +104,23 @@ struct SxPairArgs {
 #ifndef SX_PAIR_ST_SC1
 #define SX_PAIR_ST_SC1 0
 #endif
+// Prologue in the accumulator layout (default, both variants): every thread loads the 16-byte half cells of x it will add as
+// the residual (the 256 columns the waves produce) straight into `pre`, converts THOSE registers into the LDS operand planes,
+// and keeps them; only the halo columns left and right of the 256 go through transient whole-cell registers.  x crosses the
+// L2 -> CU path once per tile and is never requested again.  0 = the earlier form: the tile staged as whole cells in a
+// thread-to-cell order of its own (96 registers at 64 channels) and the residual requested separately - right behind the tile
+// at 32 channels (SX_PAIR_EARLY32; a second request, no second HBM read), after phase 1 (CHAIN) / phase 2 (PAIR) at 64
+// channels, when the tile's lines had left the L2: 1.96 x the HBM read bytes per launch of the 32-channel variant.
+// Same-box A/B (tools/pair_bench.py --frames 430), bit-identical results: 64 channels k = 3 / 7 / 11 pairs 0.418 / 0.741 /
+// 1.021 -> 0.382 / 0.715 / 0.995 ms, k = 3 / 5 chains 0.194 / 0.286 -> 0.175 / 0.283; 32 channels 0.276 / 0.445 / 0.616 ->
+// 0.233 / 0.424 / 0.588, chains 0.283 / 0.406 / 0.605 -> 0.240 / 0.348 / 0.556 (part of it is the `pk` pins).
+// The =0 forms are this change's A/B lever only (no test builds them); they go with the next change to this prologue.
+#ifndef SX_PAIR_ONE_READ64
+#define SX_PAIR_ONE_READ64 1
+#endif
+#ifndef SX_PAIR_ONE_READ32
+#define SX_PAIR_ONE_READ32 1
+#endif
 // NCH > 1: the multi-receptive-field sum of a ResBlock2 stage, xs = (rb_0(x) + rb_1(x) + ..) / n (models.py:356-363), as ONE
 // launch: the x tile (widest halo of the chains) is loaded and split ONCE and stays in LDS (Y no longer overlays it), the
 // chains run one after the other over the same 256 columns - a chain with a shorter reach reads its operands xoff / yoff
@@ -112,14 +131,17 @@ template <int MW, int NW, int WM, int WN, int EPI, bool CHAIN, int NCH = 1>
 __global__ __launch_bounds__(256, (NW == 2 && !SX_PAIR_EARLY_ACC && NCH == 1) ? SX_PAIR_WGS32 : 2) void conv_sx_pair_kernel(SxPairArgs a) {
     constexpr int BN = NW * WN * 32, NH = NW / 2;
     static_assert(NCH == 1 || (CHAIN && NW == 2 && (EPI & EPI_ACC) == 0), "fused chains: 32 channels, no external running sum");
-    // 32-channel variant: the residual is requested in the prologue, right behind the x tile, and waits in registers
-    // (its lines are in flight at that moment; after phase 1 they have left the L2: PMC showed the re-read going to
-    // the fabric).  The running sum (EPI_ACC) is NOT: with it the variant needs 188 registers, loses the third
-    // workgroup per CU and runs 12-16 % slower (profiles r02_v5 -> r02_v6).
-    constexpr bool EARLY = NW == 2 && SX_PAIR_EARLY32;
+    // The residual is in registers from the prologue on: loaded there as the x tile itself (ONE_READ), or (the earlier form
+    // of the 32-channel variant, SX_PAIR_EARLY32) requested right behind the tile - its lines are in flight at that moment;
+    // after phase 1 they have left the L2: PMC showed the re-read going to the fabric.  The running sum (EPI_ACC) is NOT:
+    // with it the 32-channel variant needs 188 registers, loses the third workgroup per CU and runs 12-16 % slower
+    // (profiles r02_v5 -> r02_v6).
+    constexpr bool ONE_READ = NW == 4 ? SX_PAIR_ONE_READ64 != 0 : SX_PAIR_ONE_READ32 != 0;  // x tile loaded in the accumulator layout
+    constexpr bool EARLY = ONE_READ || (NW == 2 && SX_PAIR_EARLY32);
     constexpr int DEPTH = NW == 2 ? SX_PAIR_DEPTH32 : SX_PAIR_DEPTH64;  // weight look-ahead in steps (run_conv)
     static_assert(DEPTH >= 2 && DEPTH <= 6, "wait_a covers up to five younger sets");
     constexpr bool ACC = (EPI & EPI_ACC) != 0 && SX_PAIR_EARLY_ACC;
+    static_assert(!(ONE_READ && ACC), "the running sum is not pulled into the single-read prologue");
     static_assert(WM * WN == 4 && MW == 1 && BN == 256, "one block row per wave, 256 columns");
     constexpr int NPW = 2, STEPBYTES = WM * MW * NPW * 1024;
     constexpr int MAXCH = WM * 2;  // 16-channel chunks: C = 32 * WM
@@ -222,7 +244,91 @@ __global__ __launch_bounds__(256, (NW == 2 && !SX_PAIR_EARLY_ACC && NCH == 1) ? 
         for (int q = 0; q < 4; q++) bq[q] = __builtin_bit_cast(f32x4, t4[q]);
     };
     constexpr int NXC = 3;
-    {
+    if constexpr (ONE_READ) {
+        // The 256 columns [t1, t1 + 256) = tile cells [pad1, pad1 + 256): wave (wm, wn), block column n, lane (l31, hi) loads
+        // half `hi` of the cell of channel group 4 wm + q at column (wn NW + n) 32 + l31 - the element of x it adds as the
+        // residual - so one wave instruction covers 1 KiB of contiguous memory (32 cells, first halves then second halves).
+        // The HW = LW - 256 halo columns, [0, pad1) and [pad1 + 256, LW), of the C / 8 groups: whole cells, h = it 256 + tid
+        // (HW <= 128 by sx_pair_supported: at most MAXCH cells per thread).  Halo first, then `pre` block column by block
+        // column: loads return in order, so block column n has landed when only the 4 (NW - 1 - n) younger loads are in flight.
+        constexpr int NXH = MAXCH, NG = 2 * MAXCH;
+        const int HW = LW - 256, pad1 = a.pad1;
+        const int nhc = HW * NG, nxh = (nhc + 255) >> 8;
+        u32x4 hst[NXH][2];
+        bool hin[NXH], hok[NXH];
+        uint32_t hlds[NXH];
+        const float *hp[NXH];
+#pragma unroll
+        for (int it = 0; it < NXH; it++) {
+            const int h = it * 256 + tid;
+            hin[it] = h < nhc;
+            const int g = hin[it] ? h / HW : 0;
+            const int c = hin[it] ? h - g * HW : 0;
+            const int col = c < pad1 ? c : c + 256;
+            const int t = t1 - pad1 + col;
+            hok[it] = hin[it] && t >= 0 && t < TV;
+            hp[it] = xrb + (hok[it] ? ((int64_t)g * T + t) * 8 : (int64_t)0);
+            hlds[it] = lds0 + (uint32_t)(g >> 1) * XB + (uint32_t)((g & 1) * LW + col) * 16u;
+        }
+        static_for<NXH>([&](auto I) {
+            constexpr int it = decltype(I)::value;
+            if (it < nxh) {  // (uniform.  Nothing else may be issued between here and the split: the waits below count `pre` only)
+                hst[it][0] = global_read128_v<0>(hp[it]);
+                hst[it][1] = global_read128_v<16>(hp[it]);
+            }
+        });
+        load_pre();
+        const float isl = a.islope;
+        static_for<NW>([&](auto N) {
+            constexpr int n = decltype(N)::value;
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * (NW - 1 - n)) : "memory");
+            __builtin_amdgcn_sched_barrier(0);  // (nothing else ties the consumers to the wait)
+#if SX_PAIR_PROF
+            if constexpr (n == 0) tp[1] = stamp();  // the halo and the first block column have arrived
+#endif
+            if constexpr (n == 0) {
+                static_for<NXH>([&](auto I) {
+                    constexpr int it = decltype(I)::value;
+                    if (it < nxh && hin[it]) {
+                        float v[8];
+#pragma unroll
+                        for (int e = 0; e < 8; e++) {
+                            const float x = hok[it] ? __uint_as_float(hst[it][e >> 2][e & 3]) : 0.f;
+                            v[e] = fmaxf(x, x * isl);
+                        }
+                        unsigned p0[4], p1[4];
+#pragma unroll
+                        for (int e = 0; e < 4; e++) split2h_pair_pk(v[2 * e], v[2 * e + 1], p0[e], p1[e], pk);
+                        ds_write128(hlds[it], u32x4{p0[0], p0[1], p0[2], p0[3]});
+                        ds_write128(hlds[it] + (uint32_t)(2 * LW) * 16u, u32x4{p1[0], p1[1], p1[2], p1[3]});
+                    }
+                });
+            }
+            const int col = (wn * NW + n) * 32 + l31;
+            const int t = t1 + col;
+            const bool ok = t >= 0 && t < TV;  // outside the tensor: zeros in LDS; `pre` keeps what the clamped load returned
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                float v[4];
+#pragma unroll
+                for (int e = 0; e < 4; e++) {
+                    const float x = ok ? pre[n / 2][n % 2][q][e] : 0.f;
+                    v[e] = fmaxf(x, x * isl);
+                }
+                unsigned wa[2], wb[2];
+                split2h_pair_pk(v[0], v[1], wa[0], wa[1], pk);
+                split2h_pair_pk(v[2], v[3], wb[0], wb[1], pk);
+                // channel group g = 4 * wm + q -> chunk g / 2, half g % 2; 4 channels = 8 bytes of the 16-byte cell
+                const int g = 4 * wm + q;
+                const uint32_t cell = lds0 + (uint32_t)(g >> 1) * XB + (uint32_t)((g & 1) * LW + pad1 + col) * 16u + 8u * hi;
+                asm volatile("ds_write_b64 %0, %1" ::"v"(cell), "v"(u32x2{wa[0], wb[0]}) : "memory");
+                asm volatile("ds_write_b64 %0, %1" ::"v"(cell + (uint32_t)(2 * LW) * 16u), "v"(u32x2{wa[1], wb[1]}) : "memory");
+            }
+            // (the range guard is only read at the kernel's end: without this hipcc sinks its max chain there and keeps all 64
+            // activated values alive - in scratch - through both phases)
+            asm volatile("" : "+v"(pk));
+        });
+    } else {
         u32x4 xst[MAXCH][NXC][2];
         const int nxc = (2 * LW + 255) >> 8;
         uint32_t xroff[NXC];
@@ -510,8 +616,9 @@ __global__ __launch_bounds__(256, (NW == 2 && !SX_PAIR_EARLY_ACC && NCH == 1) ? 
     static_assert(NCH == 1 || EARLY, "fused chains keep x in registers from the prologue on");
     // Y: over the x stages (one chain: x is dead after phase 1), or behind them (fused chains: x is every chain's input)
     const uint32_t ylds = NCH > 1 ? lds0 + (uint32_t)a.nchunks * XB : lds0;
-    // (xkeep = x in the accumulator layout, saved at the first hand-over: `pre` is still in flight here - it was requested
-    // by the prologue's asm loads and is only known to have landed once phase 1 has waited for its last weights)
+    // (xkeep = x in the accumulator layout, saved at the first hand-over: without ONE_READ `pre` is still in flight here - it
+    // was requested by the prologue's asm loads and is only known to have landed once phase 1 has waited for its last weights;
+    // with it the prologue's waits have covered `pre` before the split read it)
     f32x4 xkeep[NCH > 1 ? NW / 2 : 1][2][4], tot[NCH > 1 ? NW / 2 : 1][2][4];
 #if SX_PAIR_ALIAS
     // one set of weight registers for both phases (phase 2's first weights are requested when phase 1 has consumed its
@@ -555,9 +662,9 @@ __global__ __launch_bounds__(256, (NW == 2 && !SX_PAIR_EARLY_ACC && NCH == 1) ? 
         run_conv(f1s, cp.wb1, cp.K1, cp.dil1, lds0 + (uint32_t)(hi * LW + wn * (NW * 32) + l31 + (int)cp.xoff) * 16u, XB,
                  (uint32_t)(2 * LW) * 16u);
 
-    // ---- the residual (64-channel variant): the tile's lines were fetched a phase or two ago; CHAIN needs them now
-    // (x1 = c1(..) + x at the hand-over), PAIR only in the epilogue and requests them there, so that they do not occupy
-    // registers during phase 2.
+    // ---- the residual of the 64-channel variant without ONE_READ: the tile's lines were fetched a phase or two ago; CHAIN
+    // needs them now (x1 = c1(..) + x at the hand-over), PAIR only in the epilogue and requests them there - a second read
+    // from beyond the L2.
 #if SX_PAIR_PROF
     tp[4] = stamp();  // phase 1 done
 #endif
@@ -611,6 +718,9 @@ __global__ __launch_bounds__(256, (NW == 2 && !SX_PAIR_EARLY_ACC && NCH == 1) ? 
                 asm volatile("ds_write_b64 %0, %1" ::"v"(cell), "v"(u32x2{wa[0], wb[0]}) : "memory");
                 asm volatile("ds_write_b64 %0, %1" ::"v"(cell + 2u * LW2 * 16u), "v"(u32x2{wa[1], wb[1]}) : "memory");
             }
+            // (as in the prologue: the range guard's max chain stays here.  Sunk to the kernel's end it kept 10-30 activated
+            // values per lane alive through phase 2: 153-165 registers at 32 channels, 52-84 bytes of scratch at 64, before)
+            asm volatile("" : "+v"(pk));
         }
     }
     zero_acc();
@@ -731,7 +841,8 @@ inline bool sx_pair_supported(int C, int cfg, int K1, int dil1, int K2, int dil2
     if (K1 < 3 || K2 < 3 || dil1 < 1 || dil2 < 1) return false;
     if (!((C == 64 && cfg == 1) || (C == 32 && cfg == 2))) return false;  // one row tile holds every channel
     const int LW1 = 256 + (K1 - 1) * dil1;
-    if (2 * LW1 > 768) return false;                                      // x staging: three cells per thread
+    if (2 * LW1 > 768) return false;                                      // halo <= 128 columns (C / 16 halo cells per thread; the
+                                                                          // SX_PAIR_ONE_READ*=0 staging: three cells per thread)
     const int halo2 = (K2 - 1) * dil2;
     static const int keep_min = [] {
         const char *e = std::getenv("VITSMI_PAIR_MIN_KEEP");  // A/B timing only
@@ -831,7 +942,7 @@ inline bool sx_mrf_geom(int C, int n, const int *K1, const int *dil1, const int 
         p2 = a2 > p2 ? a2 : p2;
     }
     const int LW1 = 256 + 2 * p1;
-    if (2 * LW1 > 768) return false;       // x staging: three cells per thread
+    if (2 * LW1 > 768) return false;       // (as sx_pair_supported: halo <= 128 columns)
     if (256 - 2 * p2 < 160) return false;  // (as sx_pair_supported: more than 37 % of a tile recomputed)
     const int LW2 = (256 + p2 + 7) / 8 * 8;
     const size_t lds = (size_t)(C / 16) * 4 * LW1 * 16 + (size_t)(C / 16) * 4 * LW2 * 16 + (size_t)p2 * 16;
