@@ -350,32 +350,13 @@ void conv_event_end(Ctx &c, bool sx, double flops, double bytes, const ConvDesc 
     hipEventRecord(h->conv_events[i].second, c.st);
 }
 
-// Launch one conv through the engine; accounts algorithmic FLOPs/bytes per stage.
-struct ConvExtra {           // rarely used arguments of conv()
-    int wn_split = 0;        // EPI_WN: first skip row
-    uint16_t *out_pl = nullptr;  // fp16 operand planes of the rows [0, pl_rows) of `out` for a following sx conv
-    int pl_rows = 0;
-};
-
-void conv(Ctx &c, const ConvDesc &d, const float *x, int64_t x_bstride, int T, float *out, int64_t out_bstride,
-          int flags, const int *len = nullptr, const float *res = nullptr, int64_t res_bstride = 0,
-          const float *bias_b = nullptr, int bias_b_stride = 0, float slope = 0.1f, float div = 1.f,
-          float oslope = 1.f, float *out2 = nullptr, float oslope2 = 1.f, int x_cstride = 0, int out_cstride = 0,
-          const ConvExtra *ex = nullptr) {
+// What a launch's arguments take from the conv's descriptor, for conv() / conv_sx() and the kernel test hooks alike (A: the
+// arena the descriptor's offsets count from; zeros: its zero page).  Everything else is the caller's.
+ConvArgs conv_args(const ConvDesc &d, const float *A, const float *zeros) {
     ConvArgs a{};
-    a.x = x;
-    a.x_bstride = x_bstride;
-    a.T = T;
-    a.len = len;
-    a.wp = c.P(d.w_off);
-    a.bias = c.P(d.b_off);
-    a.bias_b = bias_b;
-    a.bias_b_stride = bias_b_stride;
-    a.out = out;
-    a.out_bstride = out_bstride;
-    a.res = res;
-    a.res_bstride = res_bstride;
-    a.zeros = c.P(c.m.zeros_off);
+    a.wp = A + d.w_off;
+    a.bias = d.b_off >= 0 ? A + d.b_off : nullptr;
+    a.zeros = zeros;
     a.Cin = d.Cin;
     a.Cout = d.Cout;
     a.K = d.K;
@@ -384,21 +365,82 @@ void conv(Ctx &c, const ConvDesc &d, const float *x, int64_t x_bstride, int T, f
     a.CK = d.CK;
     a.nchunks = d.nchunks;
     a.ups = d.ups;
+    a.div = 1.f;  // (EPI_DIV's operand: neutral until a caller sets one)
+    return a;
+}
+
+// ... of the split-operand engine, for an input of T columns: the batch strides are those of whole tensors in the engine's
+// layouts (conv_sx() below)
+SxArgs sx_args(const ConvDesc &d, const float *A, const float *zeros, int T) {
+    SxArgs a{};
+    const int Cr = d.Cout / d.ups;
+    a.x_bstride = (int64_t)3 * (d.Cin / 8) * T;
+    a.T = T;
+    a.wp = reinterpret_cast<const u32x4 *>(A + d.w_off);
+    a.bias = d.b_off >= 0 ? A + d.b_off : nullptr;
+    a.raw_bstride = (int64_t)Cr * T * d.ups;
+    a.pl_bstride = 3 * a.raw_bstride;
+    a.zeros = zeros;
+    a.Cin = d.Cin;
+    a.Cout = d.Cout;
+    a.Cr = Cr;
+    a.K = d.K;
+    a.dil = d.dil;
+    a.padL = d.padL;
+    a.nchunks = d.nchunks;
+    a.ups = d.ups;
+    a.div = 1.f;
+    a.wscale = d.wscale;
+    a.s16 = d.s16 ? 1 : 0;
+    static const bool zt_off = std::getenv("VITSMI_NO_ZERO_TAP_SKIP") != nullptr;  // A/B timing
+    a.zt_p = zt_off ? -1 : d.zt_p;
+    return a;
+}
+
+// Launch one conv through the engine; accounts algorithmic FLOPs/bytes per stage.
+struct ConvOpt {                      // the optional arguments of conv(), set by name
+    const int *len = nullptr;         // [B] valid lengths (the mask flags, EPI_WN, EPI_COUPLING)
+    const float *res = nullptr;       // EPI_RES operand and its batch stride
+    int64_t res_bstride = 0;
+    const float *bias_b = nullptr;    // per-utterance bias [B][bias_b_stride]
+    int bias_b_stride = 0;
+    float slope = 0.1f;               // PRO_LRELU
+    float div = 1.f;                  // EPI_DIV
+    float oslope = 1.f;               // leaky_relu slope of the value stored in out (1 = none) ...
+    float *out2 = nullptr;            // ... and in the optional second output
+    float oslope2 = 1.f;
+    int x_cstride = 0;                // floats between the channels of x (0 = T)
+    int out_cstride = 0;              // ... of out / out2 / res (0 = T * ups)
+    int wn_split = 0;                 // EPI_WN: first skip row
+    uint16_t *out_pl = nullptr;       // fp16 operand planes of the rows [0, pl_rows) of `out` for a following sx conv
+    int pl_rows = 0;
+};
+
+void conv(Ctx &c, const ConvDesc &d, const float *x, int64_t x_bstride, int T, float *out, int64_t out_bstride,
+          int flags, const ConvOpt &o = {}) {
+    ConvArgs a = conv_args(d, c.A, c.P(c.m.zeros_off));
+    a.x = x;
+    a.x_bstride = x_bstride;
+    a.x_cstride = o.x_cstride;
+    a.T = T;
+    a.len = o.len;
+    a.bias_b = o.bias_b;
+    a.bias_b_stride = o.bias_b_stride;
+    a.out = out;
+    a.out_bstride = out_bstride;
+    a.out_cstride = o.out_cstride;
+    a.out2 = o.out2;
+    a.res = o.res;
+    a.res_bstride = o.res_bstride;
     a.flags = flags;
-    a.slope = slope;
-    a.div = div;
-    a.oslope = oslope;
-    a.out2 = out2;
-    a.oslope2 = oslope2;
-    a.x_cstride = x_cstride;
-    a.out_cstride = out_cstride;
-    vits_handle *h = c.h;
-    if (ex) {
-        a.wn_split = ex->wn_split;
-        a.out_pl = ex->out_pl;
-        a.pl_rows = ex->pl_rows;
-        a.peak = ex->out_pl ? range_slots(h, true) : nullptr;
-    }
+    a.slope = o.slope;
+    a.div = o.div;
+    a.oslope = o.oslope;
+    a.oslope2 = o.oslope2;
+    a.wn_split = o.wn_split;
+    a.out_pl = o.out_pl;
+    a.pl_rows = o.pl_rows;
+    a.peak = o.out_pl ? range_slots(c.h, true) : nullptr;
     const bool ev = conv_event_begin(c);
     c.note(launch_conv(a, d.cfg, c.B, c.st));
     if (ev) conv_event_end(c, false, 2.0 * d.macs_per_t * (double)T * c.B, 4.0 * c.B * ((double)d.Cin * T + (double)d.Cout * T), d, T);
@@ -409,12 +451,21 @@ void conv(Ctx &c, const ConvDesc &d, const float *x, int64_t x_bstride, int T, f
 // batches in the engine's layouts: input planes [B][3][Cin/8][T][8], outputs raw [B][Cr/8][T*u][8] and/or
 // planes [B][3][Cr/8][T*u][8]; `res` has the raw layout of the output.
 // `x` is the plane tensor, or (d.rawin) the fp32 raw tensor, to which the kernel applies leaky_relu(islope).
-struct SxWn {               // SX_WN_RMW arguments of conv_sx()
+struct SxOpt {                        // the optional arguments of conv_sx(), set by name
+    const float *res = nullptr;       // EPI_RES operand: fp32, the layout of out_raw ...
+    const uint16_t *res_pl = nullptr;  // ... or (d.h1, the residual-plane instantiations) the plane tensor that holds
+    float res_slope = 1.f;             //     leaky_relu(residual, res_slope)
+    const float *bias_b = nullptr;    // per-utterance bias [B][bias_b_stride]
+    int bias_b_stride = 0;
+    float div = 1.f;                  // EPI_DIV
+    float oslope = 1.f, oslope2 = 1.f;  // leaky_relu slope of the value stored in out_raw / split into out_pl (1 = none)
+    float islope = 1.f;               // d.rawin: leaky_relu slope applied to x on the way in
+    // SX_WN_RMW (the planar epilogue):
     const int *len = nullptr;
     float *out_raw2 = nullptr;
-    int row_split = 0, pl_rows = 0;
-    bool pl_of2 = false;          // planes of out_raw2's rows instead of out_raw's
-    int64_t planar_bstride = 0;   // batch stride of out_raw / res (0: row_split * T)
+    int row_split = 0, pl_rows = 0;   // first row that goes to out_raw2; planes of the first pl_rows rows only
+    bool pl_of2 = false;              // planes of out_raw2's rows instead of out_raw's
+    int64_t planar_bstride = 0;       // batch stride of out_raw / res (0: row_split * T)
 };
 
 // largest launch (in workgroups of the short-launch kernel) that conv_sx() hands to conv_sx_small_kernel; process-wide,
@@ -425,57 +476,34 @@ std::atomic<long long> &sx_small_max() {
 }
 
 void conv_sx(Ctx &c, const ConvDesc &d, const void *x, int T, float *out_raw, uint16_t *out_pl, int flags,
-             const float *res = nullptr, const float *bias_b = nullptr, int bias_b_stride = 0, float div = 1.f,
-             float oslope = 1.f, float oslope2 = 1.f, float islope = 1.f, const SxWn *wn = nullptr,
-             const uint16_t *res_pl = nullptr, float res_slope = 1.f) {
-    // res_pl (single-plane mode, d.h1): the residual is the plane tensor that holds leaky_relu(residual, res_slope)
-    SxArgs a{};
-    const int Cr = d.Cout / d.ups;
+             const SxOpt &o = {}) {
+    SxArgs a = sx_args(d, c.A, c.P(c.m.zeros_off), T);
     const int64_t Tout = (int64_t)T * d.ups;
     if (d.rawin) a.xr = static_cast<const float *>(x);
     else a.xp = static_cast<const u32x4 *>(x);
-    a.islope = islope;
-    a.x_bstride = (int64_t)3 * (d.Cin / 8) * T;
-    a.T = T;
-    a.wp = reinterpret_cast<const u32x4 *>(c.P(d.w_off));
-    a.bias = c.P(d.b_off);
-    a.bias_b = bias_b;
-    a.bias_b_stride = bias_b_stride;
+    a.islope = o.islope;
+    a.bias_b = o.bias_b;
+    a.bias_b_stride = o.bias_b_stride;
     a.out_raw = out_raw;
-    a.raw_bstride = (flags & SX_GATE) ? (int64_t)(Cr / 2) * Tout : (int64_t)Cr * Tout;  // (gate: planar acts [H][T])
     a.out_pl = out_pl;
-    a.pl_bstride = (flags & SX_GATE) ? (int64_t)3 * (Cr / 2) * Tout : (int64_t)3 * Cr * Tout;  // (gate: planes of the H acts)
-    if (wn) {  // SX_WN_RMW: planes of the first pl_rows rows only
-        a.len = wn->len;
-        a.out_raw2 = wn->out_raw2;
-        a.row_split = wn->row_split;
-        a.pl_rows = wn->pl_rows;
-        a.pl_bstride = (int64_t)3 * wn->pl_rows * Tout;
-        a.pl_of2 = wn->pl_of2 ? 1 : 0;
-        a.planar_bstride = wn->planar_bstride;
+    if (flags & SX_GATE) {  // half the rows: planar acts [H][T] / planes of the H acts
+        a.raw_bstride = (int64_t)(a.Cr / 2) * Tout;
+        a.pl_bstride = 3 * a.raw_bstride;
     }
-    a.res = res;
-    a.res_pl = res_pl;
-    a.res_unslope = 1.f / res_slope;
-    a.zeros = c.P(c.m.zeros_off);
-    a.Cin = d.Cin;
-    a.Cout = d.Cout;
-    a.Cr = Cr;
-    a.K = d.K;
-    a.dil = d.dil;
-    a.padL = d.padL;
-    a.nchunks = d.nchunks;
-    a.ups = d.ups;
+    a.len = o.len;
+    a.out_raw2 = o.out_raw2;
+    a.row_split = o.row_split;
+    a.pl_rows = o.pl_rows;
+    if (flags & SX_WN_RMW) a.pl_bstride = (int64_t)3 * o.pl_rows * Tout;
+    a.pl_of2 = o.pl_of2 ? 1 : 0;
+    a.planar_bstride = o.planar_bstride;
+    a.res = o.res;
+    a.res_pl = o.res_pl;
+    a.res_unslope = 1.f / o.res_slope;
     a.flags = flags;
-    a.div = div;
-    a.oslope = oslope;
-    a.oslope2 = oslope2;
-    a.wscale = d.wscale;
-    a.s16 = d.s16 ? 1 : 0;
-    {
-        static const bool zt_off = std::getenv("VITSMI_NO_ZERO_TAP_SKIP") != nullptr;  // A/B timing
-        a.zt_p = zt_off ? -1 : d.zt_p;
-    }
+    a.div = o.div;
+    a.oslope = o.oslope;
+    a.oslope2 = o.oslope2;
     vits_handle *h = c.h;
     if (h->cur_stage == 3) a.rag = c.rag_at(T);
     // the flow's tensors are masked by y_len (modules.py:447-466: every conv's input is x * mask, every result * mask): a
@@ -607,14 +635,13 @@ hipError_t launch_attention16(hipStream_t st, int B, int T, int n_heads, int dk,
 
 // A token- / frame-domain conv on the split-operand engine with the planar epilogue (SX_WN_RMW): x_pl = fp16 operand planes
 // of the input; out (may be nullptr when out_pl is given) = planar fp32 [B][Cout][T]; out_pl = operand planes of the output
-// for the next conv; flags = EPI_RELU | EPI_MASK | EPI_ACC | EPI_RES (res: planar, the shape of out).
+// for the next conv; flags = EPI_RELU | EPI_MASK | EPI_ACC | EPI_RES; of the options o.len (the masks) and o.res (planar, the
+// shape of out) are the caller's.
 void conv_sx_planar(Ctx &c, const ConvDesc &d, const uint16_t *x_pl, int T, float *out, uint16_t *out_pl, int flags,
-                    const int *len = nullptr, const float *res = nullptr) {
-    SxWn w;
-    w.len = len;
-    w.row_split = d.Cout;
-    w.pl_rows = out_pl ? d.Cout : 0;
-    conv_sx(c, d, x_pl, T, out, out_pl, SX_WN_RMW | flags, res, nullptr, 0, 1.f, 1.f, 1.f, 1.f, &w);
+                    SxOpt o = {}) {
+    o.row_split = d.Cout;
+    o.pl_rows = out_pl ? d.Cout : 0;
+    conv_sx(c, d, x_pl, T, out, out_pl, SX_WN_RMW | flags, o);
 }
 
 // planar fp32 [B][C][T] (masked by len when given) -> fp16 operand planes of the split-operand engine
@@ -623,6 +650,20 @@ void split_planes(Ctx &c, const float *x, uint16_t *pl, int C, int T, const int 
                                                                                 range_slots(c.h, true));
     c.note(hipGetLastError());
     c.h->stats.total_launches++;
+}
+
+// What follows the launch of n dependent convs as ONE kernel (conv_sx_pair, conv_sx_pair16, conv_sx_mrf): the end event, whose
+// record names the conv `rec`, and the counters - every member is accounted as a conv, the launches that did not happen
+// are taken off again.  fl / by: algorithmic FLOPs and layer-granular bytes of the whole launch.
+void fused_launch_end(Ctx &c, bool ev, const ConvDesc *const *members, int n, const ConvDesc &rec, int T, double fl, double by) {
+    vits_stats &st = c.h->stats;
+    if (ev) conv_event_end(c, true, fl, by, rec, T);
+    for (int i = 0; i < n; i++) conv_account(c, *members[i], T);
+    st.conv_launches -= n - 1;
+    st.total_launches -= n - 1;
+    st.sx_flops += fl;
+    st.sx_bytes += by;
+    st.sx_launches++;
 }
 
 // Two dependent convs of a ResBlock as ONE launch (conv_sx_pair.hip.hpp), raw-format stages only (x, out: fp32 raw
@@ -692,14 +733,8 @@ void conv_sx_pair(Ctx &c, const ConvDesc &c1, const ConvDesc &c2, const float *x
     const double wf = c.work_frac();
     const double fl = 2.0 * (c1.macs_per_t + c2.macs_per_t) * (double)T * c.B * wf;
     const double by = 4.0 * c.B * ((double)(c1.Cin + c1.Cout) * T + (double)(c2.Cin + c2.Cout) * T) * wf;
-    if (ev) conv_event_end(c, true, fl, by, c1, T);
-    conv_account(c, c1, T);
-    conv_account(c, c2, T);
-    h->stats.conv_launches--;  // (two convs, one launch)
-    h->stats.total_launches--;
-    h->stats.sx_flops += fl;
-    h->stats.sx_bytes += by;
-    h->stats.sx_launches++;
+    const ConvDesc *const members[] = {&c1, &c2};
+    fused_launch_end(c, ev, members, 2, c1, T, fl, by);
 }
 
 // Two dependent convs of a ResBlock on the 16x16x32 loop (conv_sx_pair16.hip.hpp): f16x3 (fp32 raw tensors; the convs'
@@ -753,14 +788,8 @@ void conv_sx_pair16(Ctx &c, const ConvDesc &c1, const ConvDesc &c2, const uint16
     c.note(launch_conv_sx_pair16(a, C, h1 ? 1 : 2, c.B, c.st, chain));
     const double fl = 2.0 * (c1.macs_per_t + c2.macs_per_t) * (double)T * c.B * c.work_frac();
     const double by = ebytes * c.B * ((double)(c1.Cin + c1.Cout) * T + (double)(c2.Cin + c2.Cout) * T) * c.work_frac();
-    if (ev) conv_event_end(c, true, fl, by, c1, T);
-    conv_account(c, c1, T);
-    conv_account(c, c2, T);
-    h->stats.conv_launches--;  // (two convs, one launch)
-    h->stats.total_launches--;
-    h->stats.sx_flops += fl;
-    h->stats.sx_bytes += by;
-    h->stats.sx_launches++;
+    const ConvDesc *const members[] = {&c1, &c2};
+    fused_launch_end(c, ev, members, 2, c1, T, fl, by);
 }
 
 // The multi-receptive-field sum of a 32-channel ResBlock2 stage, xs = (rb_0(x) + .. + rb_{n-1}(x)) / n with every rb a
@@ -798,8 +827,11 @@ void conv_sx_mrf(Ctx &c, const UpStageDesc &stg, const float *x, int T, float *o
     a.div = (float)n;
     a.nchain = n;
     double macs = 0, bytes = 0;
+    const ConvDesc *members[6];  // (sx_mrf_ok: n <= 3)
     for (int j = 0; j < n; j++) {
         const ConvDesc &c1 = stg.rbs[j].c1[0], &c2 = stg.rbs[j].c1[1];
+        members[2 * j] = &c1;
+        members[2 * j + 1] = &c2;
         auto &ch = a.ch[j];
         ch.wp1 = reinterpret_cast<const u32x4 *>(c.P(c1.w_off));
         ch.wp2 = reinterpret_cast<const u32x4 *>(c.P(c2.w_off));
@@ -821,16 +853,7 @@ void conv_sx_mrf(Ctx &c, const UpStageDesc &stg, const float *x, int T, float *o
     bytes *= c.work_frac();
     const bool ev = conv_event_begin(c);
     c.note(launch_conv_sx_mrf(a, c.B, c.st));
-    if (ev) conv_event_end(c, true, 2.0 * macs * (double)T * c.B, bytes * T * c.B, stg.rbs[n - 1].c1[0], T);
-    for (int j = 0; j < n; j++) {
-        conv_account(c, stg.rbs[j].c1[0], T);
-        conv_account(c, stg.rbs[j].c1[1], T);
-    }
-    h->stats.conv_launches -= 2 * n - 1;  // (2 n convs, one launch)
-    h->stats.total_launches -= 2 * n - 1;
-    h->stats.sx_flops += 2.0 * macs * (double)T * c.B;
-    h->stats.sx_bytes += bytes * T * c.B;
-    h->stats.sx_launches++;
+    fused_launch_end(c, ev, members, 2 * n, stg.rbs[n - 1].c1[0], T, 2.0 * macs * (double)T * c.B, bytes * T * c.B);
 }
 
 // Pinned output buffer of `bytes` bytes: the handle's pool when it is free (grown on demand), else a fresh
@@ -1150,6 +1173,10 @@ int run_tokens(vits_handle *h, const int64_t *d_ids, const int64_t *d_lens, int 
     h->stats.total_launches += 2;
     const int64_t sHT = (int64_t)H * T;
     const float *xin = xe;  // layer input: the embedding for layer 0, x afterwards
+    ConvOpt masked;         // the convs whose flags mask by the token counts
+    masked.len = len;
+    SxOpt masked_sx;
+    masked_sx.len = len;
     // split-operand engine (Model::enc_sx): every conv reads fp16 operand planes and writes planar fp32 (what attention,
     // LayerNorm and the duration predictor read) or planes for the next conv
     uint16_t *x_pl = nullptr, *att_pl = nullptr, *ff_pl = nullptr, *qkv_pl = nullptr;
@@ -1176,11 +1203,13 @@ int run_tokens(vits_handle *h, const int64_t *d_ids, const int64_t *d_lens, int 
             h->stats.total_launches++;
             h->stats.enc_flops += 2.0 * B * m.n_heads * (2.0 * m.dk * T * (double)T);
             if (!apl) split_planes(c, att, att_pl, H, T, nullptr);
-            conv_sx_planar(c, L.o_sx, att_pl, T, x, nullptr, EPI_RES, nullptr, xin);
+            SxOpt ores;
+            ores.res = xin;
+            conv_sx_planar(c, L.o_sx, att_pl, T, x, nullptr, EPI_RES, ores);
             xin = x;
             layernorm(c, x, x, L.ln1_g, L.ln1_b, len, H, T, LN_MASK, x_pl);
-            conv_sx_planar(c, L.ffn1_sx, x_pl, T, nullptr, ff_pl, EPI_RELU | EPI_MASK, len);
-            conv_sx_planar(c, L.ffn2_sx, ff_pl, T, x, nullptr, EPI_MASK | EPI_ACC, len);
+            conv_sx_planar(c, L.ffn1_sx, x_pl, T, nullptr, ff_pl, EPI_RELU | EPI_MASK, masked_sx);
+            conv_sx_planar(c, L.ffn2_sx, ff_pl, T, x, nullptr, EPI_MASK | EPI_ACC, masked_sx);
             layernorm(c, x, x, L.ln2_g, L.ln2_b, len, H, T, LN_MASK, x_pl);
             continue;
         }
@@ -1191,22 +1220,28 @@ int run_tokens(vits_handle *h, const int64_t *d_ids, const int64_t *d_lens, int 
         h->stats.total_launches++;
         h->stats.enc_flops += 2.0 * B * m.n_heads * (2.0 * m.dk * T * (double)T);
         // x = LN(x + conv_o(att))  (attentions.py:66-68)
-        conv(c, L.o, att, sHT, T, x, sHT, EPI_RES, nullptr, xin, sHT);
+        ConvOpt ores;
+        ores.res = xin;
+        ores.res_bstride = sHT;
+        conv(c, L.o, att, sHT, T, x, sHT, EPI_RES, ores);
         xin = x;
         // Padded positions never reach valid ones (keys are masked, every other op is per-position or reads
         // x*mask), so masking the LayerNorm outputs changes no observable value and lets the FFN convs read
         // their input without a ragged mask (16-byte LDS-DMA path).
         layernorm(c, x, x, L.ln1_g, L.ln1_b, len, H, T, LN_MASK);
         // FFN (attentions.py:386-407): conv(x*mask) -> relu -> conv(h*mask) -> *mask ; x = LN(x + y)
-        conv(c, L.ffn1, x, sHT, T, ffh, (int64_t)m.FF * T, EPI_RELU | EPI_MASK, len);
-        conv(c, L.ffn2, ffh, (int64_t)m.FF * T, T, x, sHT, EPI_MASK | EPI_RES, len, x, sHT);
+        conv(c, L.ffn1, x, sHT, T, ffh, (int64_t)m.FF * T, EPI_RELU | EPI_MASK, masked);
+        ConvOpt ffn_res = masked;
+        ffn_res.res = x;
+        ffn_res.res_bstride = sHT;
+        conv(c, L.ffn2, ffh, (int64_t)m.FF * T, T, x, sHT, EPI_MASK | EPI_RES, ffn_res);
         layernorm(c, x, x, L.ln2_g, L.ln2_b, len, H, T, LN_MASK);
     }
     // x = x * mask ; stats = proj(x) * mask (models.py:205-208)
     mask_kernel<<<dim3((T + 255) / 256, H, B), 256, 0, st>>>(x, len, H, T);
     h->stats.total_launches++;
-    if (m.enc_sx) conv_sx_planar(c, m.enc_proj_sx, x_pl, T, stats, nullptr, EPI_MASK, len);
-    else conv(c, m.enc_proj, x, sHT, T, stats, (int64_t)2 * C * T, EPI_MASK, len);
+    if (m.enc_sx) conv_sx_planar(c, m.enc_proj_sx, x_pl, T, stats, nullptr, EPI_MASK, masked_sx);
+    else conv(c, m.enc_proj, x, sHT, T, stats, (int64_t)2 * C * T, EPI_MASK, masked);
     h->d_mp = stats;                       // [B, 2C, T] : m_p = rows [0,C), logs_p = rows [C,2C)
     h->d_logs = stats + (int64_t)C * T;    // batch stride 2*C*T for both
 
@@ -1237,9 +1272,12 @@ int run_tokens(vits_handle *h, const int64_t *d_ids, const int64_t *d_lens, int 
         float *pr = slab_take<float>(s, (size_t)B * pr_rows * T);
         float *z = slab_take<float>(s, (size_t)B * 2 * T);
         // h = pre(x) [+ cond(g)] ; DDSConv ; cond = proj(h)*mask (models.py:65-70)
-        conv(c, m.dp_pre, x, sHT, T, hb, sC, 0, nullptr, nullptr, 0, dp_cond, m.dp_cond_rows);
+        ConvOpt cond_bias;
+        cond_bias.bias_b = dp_cond;
+        cond_bias.bias_b_stride = m.dp_cond_rows;
+        conv(c, m.dp_pre, x, sHT, T, hb, sC, 0, cond_bias);
         if (!ddsconv(c, m.dp_convs, hb, y, y2, len, Cd, T, &m.dp_proj, m.dp_proj16, cond))
-            conv(c, m.dp_proj, hb, sC, T, cond, sC, EPI_MASK, len);
+            conv(c, m.dp_proj, hb, sC, T, cond, sC, EPI_MASK, masked);
         // z = randn * noise_scale_w (models.py:111), per utterance: +0.0 where noise_w is 0
         int64_t nz = (int64_t)B * 2 * T;
         if (!rr.any(B, 2)) {
@@ -1266,7 +1304,7 @@ int run_tokens(vits_handle *h, const int64_t *d_ids, const int64_t *d_lens, int 
                 h->stats.total_launches++;
             }
             if (!ddsconv(c, cf.convs, h2, y, y2, len, Cd, T, &cf.proj, cf.proj16, pr, use_head ? &hd : nullptr))
-                conv(c, cf.proj, h2, sC, T, pr, (int64_t)cf.proj.Cout * T, EPI_MASK, len);
+                conv(c, cf.proj, h2, sC, T, pr, (int64_t)cf.proj.Cout * T, EPI_MASK, masked);
             float sqc = std::sqrt((float)Cd);
             if (cf.nb <= 10)
                 rqs_inverse_kernel<10><<<dim3((T + 63) / 64, B), 64, 0, st>>>(pr, z, len, ch0, ch1, cf.nb, T, sqc);
@@ -1288,11 +1326,11 @@ int run_tokens(vits_handle *h, const int64_t *d_ids, const int64_t *d_lens, int 
         }
         float *h1 = slab_take<float>(s, (size_t)B * Fd * T), *h2 = slab_take<float>(s, (size_t)B * Fd * T);
         const int64_t sF = (int64_t)Fd * T;
-        conv(c, m.dpp_conv1, xi, sHT, T, h1, sF, PRO_MASK | EPI_RELU, len);
+        conv(c, m.dpp_conv1, xi, sHT, T, h1, sF, PRO_MASK | EPI_RELU, masked);
         layernorm(c, h1, h1, m.dpp_n1_g, m.dpp_n1_b, len, Fd, T, 0);
-        conv(c, m.dpp_conv2, h1, sF, T, h2, sF, PRO_MASK | EPI_RELU, len);
+        conv(c, m.dpp_conv2, h1, sF, T, h2, sF, PRO_MASK | EPI_RELU, masked);
         layernorm(c, h2, h2, m.dpp_n2_g, m.dpp_n2_b, len, Fd, T, 0);
-        conv(c, m.dpp_proj, h2, sF, T, h->d_logw, T, PRO_MASK | EPI_MASK, len);
+        conv(c, m.dpp_proj, h2, sF, T, h->d_logw, T, PRO_MASK | EPI_MASK, masked);
     }
     // ---- durations (models.py:702-704)
     if (forced)
@@ -1385,16 +1423,54 @@ void rag_begin(vits_handle *h, Ctx &c, const int *ylen, int B, int F) {
 // the frame counts the tail kernel zeroes behind (nullptr: the reference's padded rendering is kept as it is)
 const int *tail_len(const vits_handle *h, const int *ylen) { return h->tails_reference ? nullptr : ylen; }
 
-// The PLANE-STREAM generator of the two fp16 arithmetics: f16x3 (the default: two fp16 planes per operand, three MFMA
-// products per fp32 product) and f16 (VITSMI_GEN_PRECISION=f16, BASELINE config 4's reduced-precision vocoder: one plane, one
-// product).  Every tensor between two convs exists ONCE, as the operand planes of the consumer's leaky_relu
-// ([planes][C/8][T][8]: 4 / 2 bytes per element): a conv reads them as its B operand straight from LDS (by LDS-DMA), and
-// a residual add recovers x from them by undoing the leaky_relu (x = p >= 0 ? p : p / 0.1; exact up to the planes' own
-// resolution - 22 bits in f16x3).  No fp32 copy of the residual stream is written or read; only the multi-receptive-field
-// sum xs (models.py:356-363; three read-modify-writes per stage) is fp32.  Everything in front of z is unchanged.  Same
-// dataflow as run_generator_sx (which now serves the exact bf16x6 arithmetic only).
-int run_generator_planes(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int z_cstride, const int *ylen, int B,
-                     int F, const float *dec_cond, Slab &s) {
+// ---- the generator (models.py:348-368): three walkers over one dataflow, picked by run_generator() below.  Common to them:
+
+// MRF accumulation (models.py:356-363) by the last step of ResBlock j of nk: xs = rb0(x); xs += rb1(x); ...; x = xs / nk
+int mrf_flags(int j, int nk) { return (j == 0 ? 0 : EPI_ACC) | (j == nk - 1 && nk > 1 ? EPI_DIV : 0); }
+
+// what one step of a ResBlock writes on the split-operand engine: epilogue flags, fp32 raw and plane destination
+struct StepOut {
+    int flags;
+    float *raw;
+    uint16_t *pl;
+};
+
+// conv_post's launch check and accounting
+void conv_post_account(vits_handle *h, Ctx &c, int B, int T) {
+    const Model &m = h->model;
+    c.note(hipGetLastError());
+    h->stats.total_launches++;
+    const double fl = 2.0 * m.post_cin * m.post_k * (double)T * B * c.work_frac(), by = 4.0 * B * ((double)m.post_cin * T + T) * c.work_frac();
+    h->stats.dec_flops += fl;
+    h->stats.dec_bytes += by;
+}
+
+// leaky_relu(0.01), conv_post, tanh (models.py:364-366) from the fp32 raw stage output of the two split-operand walkers
+void conv_post_sx(vits_handle *h, Ctx &c, const float *x, const int *ylen, int B, int T, int F, Slab &s) {
+    const Model &m = h->model;
+    hipStream_t st = h->stream;
+    h->S = T;
+    h->d_out = slab_take<float>(s, (size_t)B * T);
+    const size_t lds = (size_t)m.post_cin * (256 + m.post_k - 1) * sizeof(float);
+    if (m.post_k == 7)
+        post_conv_tanh_blocked_kernel<7><<<dim3((T + 255) / 256, B), 256, lds, st>>>(x, c.P(m.post_w), h->d_out, m.post_cin,
+                                                                                    m.post_k, T, 0.01f, tail_len(h, ylen), T / F);
+    else
+        post_conv_tanh_blocked_kernel<0><<<dim3((T + 255) / 256, B), 256, lds, st>>>(x, c.P(m.post_w), h->d_out, m.post_cin,
+                                                                                    m.post_k, T, 0.01f, tail_len(h, ylen), T / F);
+    conv_post_account(h, c, B, T);
+}
+
+// The PLANE-STREAM generator of the two fp16 arithmetics (Model::gen_planes): f16 (VITSMI_GEN_PRECISION=f16, BASELINE config
+// 4's reduced-precision vocoder: one fp16 plane per operand, one product) and, for A/B runs, f16x3 (VITSMI_F16X3_STREAM=planes:
+// two planes, three MFMA products per fp32 product).  Every tensor between two convs exists ONCE, as the operand planes of the
+// consumer's leaky_relu ([planes][C/8][T][8]: 4 / 2 bytes per element): a conv reads them as its B operand straight from LDS
+// (by LDS-DMA), and a residual add recovers x from them by undoing the leaky_relu (x = p >= 0 ? p : p / 0.1; exact up to the
+// planes' own resolution - 22 bits in f16x3).  No fp32 copy of the residual stream is written or read; only the
+// multi-receptive-field sum xs (models.py:356-363; three read-modify-writes per stage) is fp32.  Everything in front of z is
+// unchanged.  Same dataflow as run_generator_sx.
+void run_generator_planes(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int z_cstride, const int *ylen, int B,
+                          int F, const float *dec_cond, Slab &s) {
     const Model &m = h->model;
     hipStream_t st = h->stream;
     const size_t R = gen_region_floats(m, B, F);
@@ -1402,111 +1478,82 @@ int run_generator_planes(vits_handle *h, Ctx &c, const float *z, int64_t z_bstri
     auto planes = [&]() { return reinterpret_cast<uint16_t *>(slab_take<float>(s, RP)); };
     uint16_t *stage_in[2] = {planes(), planes()}, *y_pl = planes(), *raa[2] = {planes(), planes()}, *tmp_pl = planes();
     float *xs_raw = slab_take<float>(s, R);
-    h->cur_stage = 3;
-    stage_mark(h, 3);
     rag_begin(h, c, ylen, B, F);
     const float S = 0.1f;  // Generator.LRELU_SLOPE / ResBlock LRELU_SLOPE
     const int nst = (int)m.ups.size();
+    SxOpt act;  // every plane tensor is stored as leaky_relu(value, 0.1): what its consumer multiplies
+    act.oslope2 = S;
     // z * y_mask (models.py:349) as conv_pre's operand plane (no activation in front of conv_pre)
     sx_split_planes_kernel<<<dim3((F + 255) / 256, m.C / 8, B), 256, 0, st>>>(z, z_bstride, z_cstride, ylen, tmp_pl, m.C, F,
                                                                               m.gen_h1 ? 2 : 1, range_slots(h, true));
     c.note(hipGetLastError());
     h->stats.total_launches++;
     // xa = leaky_relu(conv_pre(z) [+ cond(g)], 0.1) (models.py:349-354)
-    conv_sx(c, m.conv_pre, tmp_pl, F, nullptr, stage_in[0], 0, nullptr, dec_cond, m.C0, 1.f, 1.f, S);
+    SxOpt pre = act;
+    pre.bias_b = dec_cond;
+    pre.bias_b_stride = m.C0;
+    conv_sx(c, m.conv_pre, tmp_pl, F, nullptr, stage_in[0], 0, pre);
     const uint16_t *xa = stage_in[0];
     int T = F;
     for (int si = 0; si < nst; si++) {
         const auto &stg = m.ups[si];
         rag_margin(c, m.gen_rf_stage[si]);  // (what is left of the receptive field from this stage's input on)
         // y = up(xa), stored as leaky_relu(y, 0.1): the resblocks' first operand and, un-activated, their residual
-        conv_sx(c, stg.up, xa, T, nullptr, y_pl, 0, nullptr, nullptr, 0, 1.f, 1.f, S);
+        conv_sx(c, stg.up, xa, T, nullptr, y_pl, 0, act);
         T *= stg.u;
         uint16_t *xs_pl = stage_in[(si + 1) & 1];
         const int nk = (int)stg.rbs.size();
         const bool last_stage = si == nst - 1;
         for (int j = 0; j < nk; j++) {
             const auto &rbk = stg.rbs[j];
-            const uint16_t *cur = y_pl;
-            const bool final_rb = j == nk - 1;
-            for (int q = 0; q < rbk.n; q++) {
-                const bool last = q == rbk.n - 1;
-                int fl = EPI_RES;
-                float *dst = nullptr;          // fp32 destination: the running sum xs
-                uint16_t *dsta = raa[q & 1];   // plane destination: the block's stream
-                if (last) {
-                    // xs = rb0(x); xs += rb1(x); ...; x = xs / nk.  The stage output feeds the next upsampler as a plane
-                    // (leaky_relu 0.1); the last stage's feeds conv_post as fp32 (its kernel applies leaky_relu 0.01)
-                    fl |= (j == 0 ? 0 : EPI_ACC) | (final_rb && nk > 1 ? EPI_DIV : 0);
-                    dst = xs_raw;
-                    dsta = nullptr;
-                    if (final_rb && !last_stage) {
-                        dsta = xs_pl;
-                        if (nk > 1) fl |= SX_NO_RAW_STORE;
-                        else dst = nullptr;
+            // Step q of this block writes its stream as planes; the last step the running sum xs instead (fp32).  The stage
+            // output x = xs / nk feeds the next upsampler as a plane (leaky_relu 0.1) - with one block per stage there is
+            // no sum to keep and no fp32 destination at all; the last stage's feeds conv_post as fp32 (its kernel applies
+            // leaky_relu 0.01).
+            auto step_out = [&](int q) {
+                StepOut w{EPI_RES, nullptr, raa[q & 1]};
+                if (q == rbk.n - 1) {
+                    w.flags |= mrf_flags(j, nk);
+                    w.raw = xs_raw;
+                    w.pl = nullptr;
+                    if (j == nk - 1 && !last_stage) {
+                        w.pl = xs_pl;
+                        if (nk > 1) w.flags |= SX_NO_RAW_STORE;
+                        else w.raw = nullptr;
                     }
                 }
-                // flags of a fused launch: the multi-receptive-field arithmetic + which of the two destinations it writes
-                auto p16_flags = [&](int f, float *d_raw, uint16_t *d_pl) {
-                    return (f & (EPI_ACC | EPI_DIV)) | (d_raw && !(f & SX_NO_RAW_STORE) ? P16_HAS_RAW : 0) | (d_pl ? P16_HAS_PL : 0);
-                };
+                return w;
+            };
+            // flags of a fused launch: the multi-receptive-field arithmetic + which of the two destinations it writes
+            auto p16_flags = [](const StepOut &w) {
+                return (w.flags & (EPI_ACC | EPI_DIV)) | (w.raw && !(w.flags & SX_NO_RAW_STORE) ? P16_HAS_RAW : 0) | (w.pl ? P16_HAS_PL : 0);
+            };
+            const uint16_t *cur = y_pl;
+            for (int q = 0; q < rbk.n; q++) {
+                StepOut w = step_out(q);
+                SxOpt res = act;  // a step's closing conv: + x, recovered from the planes of leaky_relu(x)
+                res.div = (float)nk;
+                res.res_pl = cur;
+                res.res_slope = S;
                 if (rbk.type1) {  // modules.py:301-314: x = c2(lrelu(c1(lrelu(x)))) + x
                     if (sx_pair16_ok(h, rbk.c1[q], rbk.c2[q]))
-                        conv_sx_pair16(c, rbk.c1[q], rbk.c2[q], cur, T, dst, dsta, p16_flags(fl, dst, dsta), (float)nk, S, false);
+                        conv_sx_pair16(c, rbk.c1[q], rbk.c2[q], cur, T, w.raw, w.pl, p16_flags(w), (float)nk, S, false);
                     else {
-                        conv_sx(c, rbk.c1[q], cur, T, nullptr, tmp_pl, 0, nullptr, nullptr, 0, 1.f, 1.f, S);
-                        conv_sx(c, rbk.c2[q], tmp_pl, T, dst, dsta, fl, nullptr, nullptr, 0, (float)nk, 1.f, S, 1.f, nullptr, cur, S);
+                        conv_sx(c, rbk.c1[q], cur, T, nullptr, tmp_pl, 0, act);
+                        conv_sx(c, rbk.c2[q], tmp_pl, T, w.raw, w.pl, w.flags, res);
                     }
                 } else if (q + 1 < rbk.n && sx_pair16_ok(h, rbk.c1[q], rbk.c1[q + 1])) {
                     // modules.py:355-364, two steps in one launch: x1 = c(lrelu(x)) + x ; x = c'(lrelu(x1)) + x1
-                    q++;
-                    const bool last2 = q == rbk.n - 1;
-                    int fl2 = EPI_RES;
-                    float *dst2 = nullptr;
-                    uint16_t *dsta2 = raa[q & 1];
-                    if (last2) {
-                        fl2 |= (j == 0 ? 0 : EPI_ACC) | (final_rb && nk > 1 ? EPI_DIV : 0);
-                        dst2 = xs_raw;
-                        dsta2 = nullptr;
-                        if (final_rb && !last_stage) {
-                            dsta2 = xs_pl;
-                            if (nk > 1) fl2 |= SX_NO_RAW_STORE;
-                            else dst2 = nullptr;
-                        }
-                    }
-                    conv_sx_pair16(c, rbk.c1[q - 1], rbk.c1[q], cur, T, dst2, dsta2, p16_flags(fl2, dst2, dsta2), (float)nk, S, true);
-                    dsta = dsta2;
+                    w = step_out(++q);
+                    conv_sx_pair16(c, rbk.c1[q - 1], rbk.c1[q], cur, T, w.raw, w.pl, p16_flags(w), (float)nk, S, true);
                 } else  // modules.py:355-364: x = c(lrelu(x)) + x
-                    conv_sx(c, rbk.c1[q], cur, T, dst, dsta, fl, nullptr, nullptr, 0, (float)nk, 1.f, S, 1.f, nullptr, cur, S);
-                cur = dsta;
+                    conv_sx(c, rbk.c1[q], cur, T, w.raw, w.pl, w.flags, res);
+                cur = w.pl;
             }
         }
         xa = xs_pl;
     }
-    // leaky_relu(0.01), conv_post, tanh (models.py:364-366) from the fp32 stage output
-    h->S = T;
-    h->d_out = slab_take<float>(s, (size_t)B * T);
-    {
-        const size_t lds = (size_t)m.post_cin * (256 + m.post_k - 1) * sizeof(float);
-        if (m.post_k == 7)
-            post_conv_tanh_blocked_kernel<7><<<dim3((T + 255) / 256, B), 256, lds, st>>>(xs_raw, c.P(m.post_w), h->d_out,
-                                                                                        m.post_cin, m.post_k, T, 0.01f,
-                                                                                        tail_len(h, ylen), T / F);
-        else
-            post_conv_tanh_blocked_kernel<0><<<dim3((T + 255) / 256, B), 256, lds, st>>>(xs_raw, c.P(m.post_w), h->d_out,
-                                                                                        m.post_cin, m.post_k, T, 0.01f,
-                                                                                        tail_len(h, ylen), T / F);
-    }
-    c.note(hipGetLastError());
-    h->stats.total_launches++;
-    {
-        double fl = 2.0 * m.post_cin * m.post_k * (double)T * B * c.work_frac(), by = 4.0 * B * ((double)m.post_cin * T + T) * c.work_frac();
-        h->stats.dec_flops += fl;
-        h->stats.dec_bytes += by;
-    }
-    c.rag = SxRagged{nullptr, 0, 0};
-    stage_mark(h, 4);
-    return 0;
+    conv_post_sx(h, c, xs_raw, ylen, B, T, F, s);
 }
 
 // f16x3, plane-format stages: residual stream as operand planes only (run_generator_sx); VITSMI_F16X3_RES=raw for the fp32 one
@@ -1517,12 +1564,12 @@ bool res_planes_on() {  // (read per run: tests switch it inside one process)
     return e ? std::string(e) != "raw" : true;
 }
 
-// The generator on the split-operand engine.  Same dataflow as run_generator below; tensors that feed a conv
-// are stored as 16-bit planes (already leaky-ReLU'd by their producer), the residual stream as fp32 raw cells.
-int run_generator_sx(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int z_cstride, const int *ylen, int B,
-                     int F, const float *dec_cond, Slab &s) {
+// The RAW-STREAM generator on the split-operand engine (f16x3, the default, and bf16x6).  Same dataflow as run_generator_f32
+// below; tensors that feed a conv are stored as 16-bit planes (already leaky-ReLU'd by their producer), the residual stream as
+// fp32 raw cells.
+void run_generator_sx(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int z_cstride, const int *ylen, int B,
+                      int F, const float *dec_cond, Slab &s) {
     const Model &m = h->model;
-    if (m.gen_planes) return run_generator_planes(h, c, z, z_bstride, z_cstride, ylen, B, F, dec_cond, s);
     hipStream_t st = h->stream;
     const size_t R = gen_region_floats(m, B, F);
     const size_t RP = R + R / 2 + 64;  // floats holding R elements as three 16-bit plane slots (the fp16 mode uses two)
@@ -1532,14 +1579,15 @@ int run_generator_sx(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, 
     float *xs_raw = slab_take<float>(s, R);
     // the plane regions double as fp32 raw buffers where a stage uses the raw format (RP >= R floats)
     float *tmp_raw = reinterpret_cast<float *>(tmp_pl), *xin_raw = reinterpret_cast<float *>(stage_in[0]);
-    h->cur_stage = 3;
-    stage_mark(h, 3);
     rag_begin(h, c, ylen, B, F);
     const float S = 0.1f;  // Generator.LRELU_SLOPE / ResBlock LRELU_SLOPE
     const int nst = (int)m.ups.size();
     // Tensor formats (model.hpp sx_raw_format): > 64 channels: 16-bit planes that already carry the consumer's
     // leaky_relu (+ fp32 raw where the tensor is also a residual); <= 64 channels: fp32 raw only, the consuming
     // conv applies the leaky_relu and the split while loading (its `islope`).
+    SxOpt lrelu;  // a conv between tensors of either format: both slopes (each is read only where its tensor exists)
+    lrelu.oslope2 = S;
+    lrelu.islope = S;
     // ---- z * y_mask (models.py:349) in conv_pre's input format
     const void *zin;
     if (sx_raw_format(m.C)) {
@@ -1554,13 +1602,16 @@ int run_generator_sx(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, 
     c.note(hipGetLastError());
     h->stats.total_launches++;
     // ---- xa = conv_pre(z) [+ cond(g)]; leaky_relu(0.1) follows (models.py:349-354)
-    bool xa_is_raw = sx_raw_format(m.C0);
+    SxOpt pre;
+    pre.bias_b = dec_cond;
+    pre.bias_b_stride = m.C0;
     const void *xa;
-    if (xa_is_raw) {
-        conv_sx(c, m.conv_pre, zin, F, xin_raw, nullptr, 0, nullptr, dec_cond, m.C0);
+    if (sx_raw_format(m.C0)) {
+        conv_sx(c, m.conv_pre, zin, F, xin_raw, nullptr, 0, pre);
         xa = xin_raw;
     } else {
-        conv_sx(c, m.conv_pre, zin, F, nullptr, stage_in[0], 0, nullptr, dec_cond, m.C0, 1.f, 1.f, S);
+        pre.oslope2 = S;
+        conv_sx(c, m.conv_pre, zin, F, nullptr, stage_in[0], 0, pre);
         xa = stage_in[0];
     }
     int T = F;
@@ -1568,6 +1619,9 @@ int run_generator_sx(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, 
         const auto &stg = m.ups[si];
         rag_margin(c, m.gen_rf_stage[si]);  // (what is left of the receptive field from this stage's input on)
         const bool fr = sx_raw_format(stg.C);  // format of this stage's tensors
+        SxOpt act;  // ... and with it who applies the leaky_relu between two of its convs: the consumer (raw) or the producer
+        if (fr) act.islope = S;
+        else act.oslope2 = S;
         // Plane-format stages (> 64 channels) in f16x3: the residual stream as operand planes ONLY (SX_RES_PL: a residual is
         // recovered from the planes of leaky_relu(x), 22 bits, as in run_generator_planes) - no fp32 copy of y and of the
         // blocks' intermediate x is written or read: 12 instead of 16 bytes per element on the residual convs, which at 128
@@ -1577,7 +1631,7 @@ int run_generator_sx(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, 
         for (const auto &rbk : stg.rbs)
             for (int q = 0; q < rbk.n && rpl; q++) rpl = rbk.c1[q].s16 && rbk.c1[q].f16 && (!rbk.type1 || (rbk.c2[q].s16 && rbk.c2[q].f16));
         // y = up(leaky_relu(xa)): pixel-shuffled dense conv; raw (residual / raw-format input) [+ planes]
-        conv_sx(c, stg.up, xa, T, rpl ? nullptr : y_raw, fr ? nullptr : y_pl, 0, nullptr, nullptr, 0, 1.f, 1.f, S, S);
+        conv_sx(c, stg.up, xa, T, rpl ? nullptr : y_raw, fr ? nullptr : y_pl, 0, lrelu);
         T *= stg.u;
         uint16_t *xs_pl = stage_in[(si + 1) & 1];
         const int nk = (int)stg.rbs.size();
@@ -1585,127 +1639,94 @@ int run_generator_sx(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, 
         if (fr && sx_mrf_ok(h, stg)) {
             // every ResBlock2 of the stage in one launch: x read once, the sum formed in registers, one store
             conv_sx_mrf(c, stg, y_raw, T, xs_raw, S);
-            xa_is_raw = true;
             xa = xs_raw;
             continue;
         }
         for (int j = 0; j < nk; j++) {
             const auto &rbk = stg.rbs[j];
+            // Step q of this block writes its stream raw and (plane format) as planes - as planes only where the residual is
+            // taken from them (rpl); the last step the running sum xs instead.  The stage output x = xs / nk feeds the next
+            // upsampler (leaky_relu 0.1) or conv_post (0.01): planes carry the activation, raw tensors get it from their
+            // consumer.
+            auto step_out = [&](int q) {
+                StepOut w{EPI_RES, rpl ? nullptr : ra[q & 1], fr ? nullptr : raa[q & 1]};
+                if (q == rbk.n - 1) {
+                    w.flags |= mrf_flags(j, nk);
+                    w.raw = xs_raw;
+                    w.pl = nullptr;
+                    if (j == nk - 1 && !last_stage && !fr) {
+                        w.pl = xs_pl;
+                        w.flags |= SX_NO_RAW_STORE;
+                    }
+                }
+                return w;
+            };
             const float *cur = y_raw;          // residual operand
             const uint16_t *cura = y_pl;       // plane format: leaky_relu(cur) as planes
-            // MRF accumulation (models.py:356-363): xs = rb0(x); xs += rb1(x); ... ; x = xs / nk
-            const bool final_rb = j == nk - 1;
             for (int q = 0; q < rbk.n; q++) {
-                const bool last = q == rbk.n - 1;
-                int fl = EPI_RES;
-                float *dst = ra[q & 1];
-                uint16_t *dsta = fr ? nullptr : raa[q & 1];
-                if (last) {
-                    fl |= (j == 0 ? 0 : EPI_ACC) | (final_rb && nk > 1 ? EPI_DIV : 0);
-                    dst = xs_raw;
-                    dsta = nullptr;
-                    // the stage output x = xs / nk feeds the next upsampler (leaky_relu 0.1) or conv_post (0.01):
-                    // planes carry the activation, raw tensors get it from their consumer
-                    if (final_rb && !last_stage && !fr) {
-                        dsta = xs_pl;
-                        fl |= SX_NO_RAW_STORE;
-                    }
-                }
-                const void *in = fr ? static_cast<const void *>(cur) : static_cast<const void *>(cura);
-                if (rpl) {
-                    // (the block's stream exists as planes only: an inner step writes no raw tensor, every step takes its
-                    // residual from the planes of its own input)
-                    if (!last) dst = nullptr;
-                    if (rbk.type1) {
-                        conv_sx(c, rbk.c1[q], in, T, nullptr, tmp_pl, 0, nullptr, nullptr, 0, 1.f, 1.f, S);
-                        conv_sx(c, rbk.c2[q], tmp_pl, T, dst, dsta, fl, nullptr, nullptr, 0, (float)nk, 1.f, S, 1.f, nullptr, cura, S);
-                    } else
-                        conv_sx(c, rbk.c1[q], in, T, dst, dsta, fl, nullptr, nullptr, 0, (float)nk, 1.f, S, 1.f, nullptr, cura, S);
-                    cur = dst;
-                    cura = dsta;
-                    continue;
-                }
-                if (rbk.type1) {  // modules.py:301-314: x = c2(lrelu(c1(lrelu(x)))) + x
-                    if (fr && sx_pair_ok(h, rbk.c1[q], rbk.c2[q])) {
-                        // both convs in one launch: the intermediate stays in LDS, x is read once
-                        conv_sx_pair(c, rbk.c1[q], rbk.c2[q], cur, T, dst, fl, (float)nk, S);
-                    } else if (fr) {
-                        conv_sx(c, rbk.c1[q], in, T, tmp_raw, nullptr, 0, nullptr, nullptr, 0, 1.f, 1.f, 1.f, S);
-                        conv_sx(c, rbk.c2[q], tmp_raw, T, dst, nullptr, fl, cur, nullptr, 0, (float)nk, 1.f, 1.f, S);
-                    } else {
-                        conv_sx(c, rbk.c1[q], in, T, nullptr, tmp_pl, 0, nullptr, nullptr, 0, 1.f, 1.f, S);
-                        conv_sx(c, rbk.c2[q], tmp_pl, T, dst, dsta, fl, cur, nullptr, 0, (float)nk, 1.f, S);
-                    }
-                } else if (fr && q + 1 < rbk.n && sx_pair_ok(h, rbk.c1[q], rbk.c1[q + 1])) {
+                StepOut w = step_out(q);
+                if (rbk.type1 && fr && sx_pair_ok(h, rbk.c1[q], rbk.c2[q])) {
+                    // modules.py:301-314 in one launch: the intermediate stays in LDS, x is read once
+                    conv_sx_pair(c, rbk.c1[q], rbk.c2[q], cur, T, w.raw, w.flags, (float)nk, S);
+                } else if (!rbk.type1 && fr && q + 1 < rbk.n && sx_pair_ok(h, rbk.c1[q], rbk.c1[q + 1])) {
                     // modules.py:355-364, two steps in one launch: x1 = c(lrelu(x)) + x ; x = c'(lrelu(x1)) + x1
-                    q++;
-                    const bool last2 = q == rbk.n - 1;
-                    int fl2 = EPI_RES;
-                    float *dst2 = ra[q & 1];
-                    if (last2) {
-                        fl2 |= (j == 0 ? 0 : EPI_ACC) | (final_rb && nk > 1 ? EPI_DIV : 0);
-                        dst2 = xs_raw;
-                    }
-                    conv_sx_pair(c, rbk.c1[q - 1], rbk.c1[q], cur, T, dst2, fl2, (float)nk, S, /*chain=*/true);
-                    dst = dst2;
-                    dsta = nullptr;
-                } else  // modules.py:355-364: x = c(lrelu(x)) + x
-                    conv_sx(c, rbk.c1[q], in, T, dst, dsta, fl, cur, nullptr, 0, (float)nk, 1.f, S, S);
-                cur = dst;
-                cura = dsta;
+                    w = step_out(++q);
+                    conv_sx_pair(c, rbk.c1[q - 1], rbk.c1[q], cur, T, w.raw, w.flags, (float)nk, S, /*chain=*/true);
+                } else {
+                    const void *in = fr ? static_cast<const void *>(cur) : static_cast<const void *>(cura);
+                    // a step's closing conv: + x, the fp32 tensor or (rpl) recovered from the planes of the step's own input
+                    // (a ResBlock2 step with the fp32 residual is given both slopes, as the upsampler)
+                    SxOpt res = rbk.type1 || rpl ? act : lrelu;
+                    res.div = (float)nk;
+                    if (rpl) {
+                        res.res_pl = cura;
+                        res.res_slope = S;
+                    } else
+                        res.res = cur;
+                    if (rbk.type1) {  // modules.py:301-314: x = c2(lrelu(c1(lrelu(x)))) + x  (tmp_raw and tmp_pl: one buffer)
+                        conv_sx(c, rbk.c1[q], in, T, fr ? tmp_raw : nullptr, fr ? nullptr : tmp_pl, 0, act);
+                        conv_sx(c, rbk.c2[q], tmp_pl, T, w.raw, w.pl, w.flags, res);
+                    } else  // modules.py:355-364: x = c(lrelu(x)) + x
+                        conv_sx(c, rbk.c1[q], in, T, w.raw, w.pl, w.flags, res);
+                }
+                cur = w.raw;
+                cura = w.pl;
             }
         }
         // next stage input: the planes written by the final conv, or the raw x = xs / nk itself
-        xa_is_raw = fr || last_stage;
         xa = (fr || last_stage) ? static_cast<const void *>(xs_raw) : static_cast<const void *>(xs_pl);
     }
-    // leaky_relu(0.01), conv_post, tanh (models.py:364-366) from the raw stage output
-    h->S = T;
-    h->d_out = slab_take<float>(s, (size_t)B * T);
-    {
-        const size_t lds = (size_t)m.post_cin * (256 + m.post_k - 1) * sizeof(float);
-        if (m.post_k == 7)
-            post_conv_tanh_blocked_kernel<7><<<dim3((T + 255) / 256, B), 256, lds, st>>>(xs_raw, c.P(m.post_w), h->d_out,
-                                                                                        m.post_cin, m.post_k, T, 0.01f,
-                                                                                        tail_len(h, ylen), T / F);
-        else
-            post_conv_tanh_blocked_kernel<0><<<dim3((T + 255) / 256, B), 256, lds, st>>>(xs_raw, c.P(m.post_w), h->d_out,
-                                                                                        m.post_cin, m.post_k, T, 0.01f,
-                                                                                        tail_len(h, ylen), T / F);
-    }
-    c.note(hipGetLastError());
-    h->stats.total_launches++;
-    {
-        double fl = 2.0 * m.post_cin * m.post_k * (double)T * B * c.work_frac(), by = 4.0 * B * ((double)m.post_cin * T + T) * c.work_frac();
-        h->stats.dec_flops += fl;
-        h->stats.dec_bytes += by;
-    }
-    c.rag = SxRagged{nullptr, 0, 0};
-    stage_mark(h, 4);
-    (void)xa_is_raw;
-    return 0;
+    conv_post_sx(h, c, xs_raw, ylen, B, T, F, s);
 }
 
-int run_generator(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int z_cstride, const int *ylen, int B,
-                  int F, const float *dec_cond, Slab &s) {
+// The generator on the f32 engine: the only one for shapes the split-operand packing refuses.
+void run_generator_f32(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int z_cstride, const int *ylen, int B,
+                       int F, const float *dec_cond, Slab &s) {
     const Model &m = h->model;
-    if (m.gen_sx) return run_generator_sx(h, c, z, z_bstride, z_cstride, ylen, B, F, dec_cond, s);
     hipStream_t st = h->stream;
     const size_t R = gen_region_floats(m, B, F);
     float *reg[kGenRegions];
     for (int i = 0; i < kGenRegions; i++) reg[i] = slab_take<float>(s, R);
-    h->cur_stage = 3;
-    stage_mark(h, 3);
     // Every leaky_relu of the generator (models.py:354,364; modules.py:303,307,357) is applied by the
     // PRODUCER's epilogue, so no conv carries activation math in its MFMA loop (conv_engine.hip.hpp).
     // A tensor that is needed both raw (residual) and activated (next conv input) is stored twice.
     const float S = 0.1f;  // Generator.LRELU_SLOPE / ResBlock LRELU_SLOPE
     const int nst = (int)m.ups.size();
+    ConvOpt gen;  // (no conv here has a prologue activation)
+    gen.slope = 1.f;
+    ConvOpt mid = gen;  // c1 of a ResBlock1 step: activated for c2
+    mid.oslope = S;
     // xa = leaky_relu(conv_pre(z * y_mask) [+ cond(g)], 0.1)            (models.py:349-354)
     float *xa = reg[0];
     const int Fp = (F + 3) & ~3;  // pitch of conv_pre's output rows: lets ups[0] use the 16-byte DMA path
-    conv(c, m.conv_pre, z, z_bstride, F, xa, (int64_t)m.C0 * Fp, ylen ? PRO_MASK : 0, ylen, nullptr, 0, dec_cond, m.C0,
-         1.f, 1.f, S, nullptr, 1.f, z_cstride, Fp);
+    ConvOpt pre = gen;
+    pre.len = ylen;
+    pre.bias_b = dec_cond;
+    pre.bias_b_stride = m.C0;
+    pre.oslope = S;
+    pre.x_cstride = z_cstride;
+    pre.out_cstride = Fp;
+    conv(c, m.conv_pre, z, z_bstride, F, xa, (int64_t)m.C0 * Fp, ylen ? PRO_MASK : 0, pre);
     int T = F, Cc = m.C0, xs_idx = 0;
     int in_pitch = Fp;
     for (int si = 0; si < nst; si++) {
@@ -1713,8 +1734,11 @@ int run_generator(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int
         // y = up(xa) as a pixel-shuffled dense conv; stored raw (residual) and activated (conv input)
         float *y = reg[2], *ya = reg[3];
         const int To = T * stg.u;
-        conv(c, stg.up, xa, (int64_t)Cc * in_pitch, T, y, (int64_t)stg.C * To, 0, nullptr, nullptr, 0, nullptr, 0, 1.f, 1.f,
-             1.f, ya, S, in_pitch, 0);
+        ConvOpt up = gen;
+        up.out2 = ya;
+        up.oslope2 = S;
+        up.x_cstride = in_pitch;
+        conv(c, stg.up, xa, (int64_t)Cc * in_pitch, T, y, (int64_t)stg.C * To, 0, up);
         in_pitch = To;
         T = To;
         Cc = stg.C;
@@ -1728,45 +1752,49 @@ int run_generator(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int
         for (int j = 0; j < nk; j++) {
             const auto &rbk = stg.rbs[j];
             const float *cur = y, *cura = ya;
-            // MRF accumulation (models.py:356-363): xs = rb0(x); xs += rb1(x); ... ; x = xs / nk
-            const bool final_rb = j == nk - 1;
-            const int last_flags = (j == 0 ? 0 : EPI_ACC) | (final_rb && nk > 1 ? EPI_DIV : 0);
-            const float last_oslope = final_rb ? out_slope : 1.f;
             for (int q = 0; q < rbk.n; q++) {
+                // a step writes the block's stream raw and activated; the last one the running sum xs, which the final
+                // block stores activated for its only consumer
                 const bool last = q == rbk.n - 1;
                 float *dst = last ? xs : ra[q & 1];
-                float *dsta = last ? nullptr : raa[q & 1];
-                const int fl = EPI_RES | (last ? last_flags : 0);
-                const float osl = last ? last_oslope : 1.f;
+                const int fl = EPI_RES | (last ? mrf_flags(j, nk) : 0);
+                ConvOpt res = gen;
+                res.res = cur;
+                res.res_bstride = sCT;
+                res.div = (float)nk;
+                res.oslope = last && j == nk - 1 ? out_slope : 1.f;
+                res.out2 = last ? nullptr : raa[q & 1];
+                res.oslope2 = S;
                 if (rbk.type1) {  // modules.py:301-314: x = c2(lrelu(c1(lrelu(x)))) + x
-                    conv(c, rbk.c1[q], cura, sCT, T, tmp, sCT, 0, nullptr, nullptr, 0, nullptr, 0, 1.f, 1.f, S);
-                    conv(c, rbk.c2[q], tmp, sCT, T, dst, sCT, fl, nullptr, cur, sCT, nullptr, 0, 1.f, (float)nk, osl, dsta,
-                         S);
-                } else {  // modules.py:355-364: x = c(lrelu(x)) + x
-                    conv(c, rbk.c1[q], cura, sCT, T, dst, sCT, fl, nullptr, cur, sCT, nullptr, 0, 1.f, (float)nk, osl, dsta,
-                         S);
-                }
+                    conv(c, rbk.c1[q], cura, sCT, T, tmp, sCT, 0, mid);
+                    conv(c, rbk.c2[q], tmp, sCT, T, dst, sCT, fl, res);
+                } else  // modules.py:355-364: x = c(lrelu(x)) + x
+                    conv(c, rbk.c1[q], cura, sCT, T, dst, sCT, fl, res);
                 cur = dst;
-                cura = dsta;
+                cura = res.out2;
             }
         }
         xa = xs;  // already activated for its only consumer
     }
-    float *x = xa;
-    // x = leaky_relu(x) [slope 0.01]; conv_post; tanh (models.py:364-366)
+    // conv_post; tanh (models.py:364-366): the leaky_relu(0.01) of models.py:364 was applied by the last stage's epilogue
     h->S = T;
     h->d_out = reg[9];
-    size_t lds = ((size_t)m.post_cin * (256 + m.post_k - 1) + (size_t)m.post_cin * m.post_k) * sizeof(float);
-    // (the leaky_relu(0.01) of models.py:364 was applied by the last stage's epilogue)
-    post_conv_tanh_kernel<<<dim3((T + 255) / 256, B), 256, lds, st>>>(x, c.P(m.post_w), h->d_out, m.post_cin, m.post_k,
+    const size_t lds = ((size_t)m.post_cin * (256 + m.post_k - 1) + (size_t)m.post_cin * m.post_k) * sizeof(float);
+    post_conv_tanh_kernel<<<dim3((T + 255) / 256, B), 256, lds, st>>>(xa, c.P(m.post_w), h->d_out, m.post_cin, m.post_k,
                                                                       T, 1.0f, tail_len(h, ylen), T / F);
-    c.note(hipGetLastError());
-    h->stats.total_launches++;
-    {
-        double fl = 2.0 * m.post_cin * m.post_k * (double)T * B * c.work_frac(), by = 4.0 * B * ((double)m.post_cin * T + T) * c.work_frac();
-        h->stats.dec_flops += fl;
-        h->stats.dec_bytes += by;
-    }
+    conv_post_account(h, c, B, T);
+}
+
+// One utterance batch through the generator: which walker a voice takes is decided here, once (Model::gen_sx: the
+// split-operand packing took every conv; Model::gen_planes: its plane-stream form)
+int run_generator(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int z_cstride, const int *ylen, int B,
+                  int F, const float *dec_cond, Slab &s) {
+    const Model &m = h->model;
+    h->cur_stage = 3;
+    stage_mark(h, 3);
+    if (!m.gen_sx) run_generator_f32(h, c, z, z_bstride, z_cstride, ylen, B, F, dec_cond, s);
+    else if (m.gen_planes) run_generator_planes(h, c, z, z_bstride, z_cstride, ylen, B, F, dec_cond, s);
+    else run_generator_sx(h, c, z, z_bstride, z_cstride, ylen, B, F, dec_cond, s);
     c.rag = SxRagged{nullptr, 0, 0};
     stage_mark(h, 4);
     return 0;
@@ -1948,6 +1976,10 @@ int run_frames(vits_handle *h, int B, int T, const RunRows &rr, const int64_t *d
     uint16_t *x0_pl = reinterpret_cast<uint16_t *>(slab_take<float>(s, nCF));
     uint16_t *skip_pl = reinterpret_cast<uint16_t *>(slab_take<float>(s, nHF * 2));
     bool x0_planes_ready = false;
+    ConvOpt masked;  // the convs whose flags mask by the frame counts
+    masked.len = ylen;
+    SxOpt masked_sx;
+    masked_sx.len = ylen;
     for (size_t ci = 0; ci < m.flow.size(); ci++) {
         const auto &cd = m.flow[ci];
         const bool pp = cd.pre_sx.sx && cd.post_sx.sx && half % 32 == 0;
@@ -1967,9 +1999,9 @@ int run_frames(vits_handle *h, int B, int T, const RunRows &rr, const int64_t *d
         // in-layer runs on the split engine, also emits x as that conv's fp16 operand planes - as `pre` does for the
         // first layer - so neither an update nor a split launch is left (they were 2 of the 5 launches of a layer).
         const bool planes0 = cd.n_wn > 0 && cd.wn[0].in.sx && cd.wn[0].in.f16 && Hf % 32 == 0;
-        ConvExtra ex0;
-        ex0.out_pl = planes0 ? hx_pl : nullptr;
-        ex0.pl_rows = Hf;
+        ConvOpt pre = masked;
+        pre.out_pl = planes0 ? hx_pl : nullptr;
+        pre.pl_rows = Hf;
         // h = pre(x0) * mask
         if (pp) {
             if (!x0_planes_ready) {
@@ -1977,14 +2009,18 @@ int run_frames(vits_handle *h, int B, int T, const RunRows &rr, const int64_t *d
                                                                                         range_slots(h, true));
                 h->stats.total_launches++;
             }
-            conv_sx_planar(c, cd.pre_sx, x0_pl, F, hx, planes0 ? hx_pl : nullptr, EPI_MASK, ylen);
+            conv_sx_planar(c, cd.pre_sx, x0_pl, F, hx, planes0 ? hx_pl : nullptr, EPI_MASK, masked_sx);
         } else
-            conv(c, cd.pre, x0, sCF, F, hx, sHF, EPI_MASK, ylen, nullptr, 0, nullptr, 0, 0.1f, 1.f, 1.f, nullptr, 1.f, 0, 0, &ex0);
+            conv(c, cd.pre, x0, sCF, F, hx, sHF, EPI_MASK, pre);
         x0_planes_ready = false;
         for (int i = 0; i < cd.n_wn; i++) {
             const bool last = i == cd.n_wn - 1;
+            const float *gc_i = gc ? gc + (int64_t)i * 2 * Hf : nullptr;  // the layer's rows of the speaker conditioning
             // x_in = in_layer(h) + g_l ; acts = tanh * sigmoid ; rs = res_skip(acts)
             if (cd.wn[i].in.sx) {
+                SxOpt gcond;
+                gcond.bias_b = gc_i;
+                gcond.bias_b_stride = gc_rows;
                 // split-operand engine: planes of hx (from the producing epilogue, or split here), conv to the raw cell
                 // layout, gate reads that layout
                 const bool have_planes = cd.wn[i].in.f16 && Hf % 32 == 0;
@@ -1998,10 +2034,8 @@ int run_frames(vits_handle *h, int B, int T, const RunRows &rr, const int64_t *d
                     // gate in the in-layer's epilogue, acts handed over as fp16 operand planes; the res_skip 1 x 1 conv on
                     // the same engine reads them and folds the update in: x += res * mask (+ the next in-layer's planes),
                     // skip += .. (the first layer stores it)
-                    conv_sx(c, cd.wn[i].in, hx_pl, F, nullptr, acts_pl, SX_GATE, nullptr, gc ? gc + (int64_t)i * 2 * Hf : nullptr,
-                            gc_rows);
-                    SxWn w;
-                    w.len = ylen;
+                    conv_sx(c, cd.wn[i].in, hx_pl, F, nullptr, acts_pl, SX_GATE, gcond);
+                    SxOpt w = masked_sx;
                     w.out_raw2 = skip;
                     w.row_split = last ? 0 : Hf;
                     const bool np = !last && cd.wn[i + 1].in.sx && cd.wn[i + 1].in.f16 && Hf % 32 == 0;
@@ -2013,44 +2047,42 @@ int run_frames(vits_handle *h, int B, int T, const RunRows &rr, const int64_t *d
                         rs_pl = skip_pl;
                     }
                     // (the first layer stores its skip rows: no zero fill of skip, no read of it)
-                    conv_sx(c, cd.wn[i].rs_sx, acts_pl, F, hx, rs_pl,
-                            SX_WN_RMW | EPI_ACC | EPI_MASK | (i == 0 ? SX_PLANAR_STORE2 : 0), nullptr, nullptr, 0, 1.f, 1.f, 1.f, 1.f, &w);
+                    conv_sx(c, cd.wn[i].rs_sx, acts_pl, F, hx, rs_pl, SX_WN_RMW | EPI_ACC | EPI_MASK | (i == 0 ? SX_PLANAR_STORE2 : 0), w);
                     continue;
                 } else if (cd.wn[i].in.gate) {  // tanh * sigmoid in the conv's epilogue: acts directly
-                    conv_sx(c, cd.wn[i].in, hx_pl, F, acts, nullptr, SX_GATE, nullptr, gc ? gc + (int64_t)i * 2 * Hf : nullptr,
-                            gc_rows);
+                    conv_sx(c, cd.wn[i].in, hx_pl, F, acts, nullptr, SX_GATE, gcond);
                     h->stats.total_launches--;  // (no gate launch: undo the increment below)
                 } else {
-                    conv_sx(c, cd.wn[i].in, hx_pl, F, a2, nullptr, 0, nullptr, gc ? gc + (int64_t)i * 2 * Hf : nullptr, gc_rows);
+                    conv_sx(c, cd.wn[i].in, hx_pl, F, a2, nullptr, 0, gcond);
                     wn_gate_blocked_kernel<<<dim3((F + 255) / 256, Hf / 8, B), 256, 0, st>>>(a2, acts, Hf, F);
                 }
             } else {
-                conv(c, cd.wn[i].in, hx, sHF, F, a2, 2 * sHF, 0, nullptr, nullptr, 0,
-                     gc ? gc + (int64_t)i * 2 * Hf : nullptr, gc_rows);
+                ConvOpt gcond;
+                gcond.bias_b = gc_i;
+                gcond.bias_b_stride = gc_rows;
+                conv(c, cd.wn[i].in, hx, sHF, F, a2, 2 * sHF, 0, gcond);
                 wn_gate_kernel<<<dim3((F + 255) / 256, Hf, B), 256, 0, st>>>(a2, acts, Hf, F);
             }
             h->stats.total_launches++;
             // res_skip conv + update: rows [0, Hf) -> hx (residual half), rows [Hf, 2 Hf) -> skip; last layer: skip only
-            ConvExtra ex;
-            ex.wn_split = last ? 0 : Hf;
+            ConvOpt upd = masked;
+            upd.out2 = skip;
+            upd.wn_split = last ? 0 : Hf;
             const bool next_planes = !last && cd.wn[i + 1].in.sx && cd.wn[i + 1].in.f16 && Hf % 32 == 0;
-            ex.out_pl = next_planes ? hx_pl : nullptr;
-            ex.pl_rows = Hf;
-            conv(c, cd.wn[i].rs, acts, sHF, F, hx, sHF, EPI_WN | EPI_MASK | (i == 0 ? EPI_WN_FIRST : 0), ylen, nullptr, 0,
-                 nullptr, 0, 0.1f, 1.f, 1.f, skip, 1.f, 0, 0, &ex);
+            upd.out_pl = next_planes ? hx_pl : nullptr;
+            upd.pl_rows = Hf;
+            conv(c, cd.wn[i].rs, acts, sHF, F, hx, sHF, EPI_WN | EPI_MASK | (i == 0 ? EPI_WN_FIRST : 0), upd);
         }
         // x1 = (x1 - post(skip)*mask) * mask
         if (pp) {
-            SxWn w;
-            w.len = ylen;
+            SxOpt w = masked_sx;
             w.row_split = half;
             w.planar_bstride = sCF;           // (x1's rows live inside z)
             w.pl_rows = pp_next ? half : 0;   // ... and are the next coupling's x0: its operand planes
-            conv_sx(c, cd.post_sx, skip_pl, F, x1, pp_next ? x0_pl : nullptr, SX_WN_RMW | EPI_ACC | EPI_MASK | SX_PLANAR_COUPLING,
-                    nullptr, nullptr, 0, 1.f, 1.f, 1.f, 1.f, &w);
+            conv_sx(c, cd.post_sx, skip_pl, F, x1, pp_next ? x0_pl : nullptr, SX_WN_RMW | EPI_ACC | EPI_MASK | SX_PLANAR_COUPLING, w);
             x0_planes_ready = pp_next;
         } else
-            conv(c, cd.post, skip, sHF, F, x1, sCF, EPI_COUPLING, ylen);
+            conv(c, cd.post, skip, sHF, F, x1, sCF, EPI_COUPLING, masked);
     }
     c.note(hipGetLastError());
 
@@ -2904,20 +2936,14 @@ static int run_test_conv(const ConvDesc &d, const std::vector<float> &arena, con
     TCHECK(hipMemcpy(dA, arena.data(), arena.size() * 4, hipMemcpyHostToDevice));
     TCHECK(hipMemcpy(dx, x, nx * 4, hipMemcpyHostToDevice));
     TCHECK(hipMemset(dout, 0, out_elems * 4));
-    ConvArgs a{};
+    ConvArgs a = conv_args(d, dA, dA);  // (pack_test_* reserve a zero page at offset 0)
     a.x = dx;
     a.x_bstride = (int64_t)d.Cin * T;
     a.T = T;
-    a.wp = dA + d.w_off;
-    a.bias = d.b_off >= 0 ? dA + d.b_off : nullptr;
     a.out = dout;
     a.out_bstride = out_bstride;
-    a.zeros = dA;  // pack_test_* reserve a zero page at offset 0
-    a.Cin = d.Cin; a.Cout = d.Cout; a.K = d.K; a.dil = d.dil; a.padL = d.padL; a.CK = d.CK;
-    a.nchunks = d.nchunks; a.ups = d.ups;
     a.flags = ((flags & 1) ? PRO_LRELU : 0) | ((flags & 2) ? EPI_RELU : 0);
     a.slope = slope;
-    a.div = 1.f;
     TCHECK(launch_conv(a, d.cfg, B, nullptr));
     TCHECK(hipDeviceSynchronize());
     TCHECK(hipMemcpy(out, dout, out_elems * 4, hipMemcpyDeviceToHost));
@@ -2963,16 +2989,12 @@ int vits_bench_conv1d(int device_id, int B, int Cin, int Cout, int T, int K, int
     TCHECK(hipMalloc((void **)&dout, (size_t)B * Cout * T * 4));
     TCHECK(hipMemcpy(dA, arena.data(), arena.size() * 4, hipMemcpyHostToDevice));
     TCHECK(hipMemcpy(dx, x.data(), x.size() * 4, hipMemcpyHostToDevice));
-    ConvArgs a{};
+    ConvArgs a = conv_args(d, dA, dA);
     a.x = dx;
     a.x_bstride = (int64_t)Cin * T;
     a.T = T;
-    a.wp = dA + d.w_off;
     a.out = dout;
     a.out_bstride = (int64_t)Cout * T;
-    a.zeros = dA;
-    a.Cin = d.Cin; a.Cout = d.Cout; a.K = d.K; a.dil = d.dil; a.padL = d.padL; a.CK = d.CK;
-    a.nchunks = d.nchunks; a.ups = 1;
     a.flags = ((dbg & 4) ? 0 : PRO_LRELU) | ((dbg & 1) ? DBG_NO_DMA : 0) | ((dbg & 2) ? DBG_NO_EPI : 0);
     if ((dbg & 8) && Cin == Cout) {  // residual epilogue + pre-activated second output, as the generator runs it
         a.flags |= EPI_RES;
@@ -2981,7 +3003,6 @@ int vits_bench_conv1d(int device_id, int B, int Cin, int Cout, int T, int K, int
         a.oslope2 = 0.1f;
     }
     a.slope = 0.1f;
-    a.div = 1.f;
     hipEvent_t e0, e1;
     hipEventCreate(&e0);
     hipEventCreate(&e1);
@@ -3017,22 +3038,6 @@ int vits_test_conv_transpose1d(int device_id, const float *x, int B, int Cin, in
 
 // ---- the same hooks through the split-operand engine: planar host tensors are converted to the engine's
 // plane / raw layouts on the device, the result is converted back.
-static void fill_sx_args(SxArgs &a, const ConvDesc &d, const float *dA, int T) {
-    const int Cr = d.Cout / d.ups;
-    a.x_bstride = (int64_t)3 * (d.Cin / 8) * T;
-    a.T = T;
-    a.wp = reinterpret_cast<const u32x4 *>(dA + d.w_off);
-    a.bias = d.b_off >= 0 ? dA + d.b_off : nullptr;
-    a.raw_bstride = (int64_t)Cr * T * d.ups;
-    a.pl_bstride = 3 * a.raw_bstride;
-    a.zeros = dA;  // pack_test_* reserve a zero page at offset 0
-    a.Cin = d.Cin; a.Cout = d.Cout; a.Cr = Cr; a.K = d.K; a.dil = d.dil; a.padL = d.padL;
-    a.nchunks = d.nchunks; a.ups = d.ups;
-    a.div = 1.f;
-    a.s16 = d.s16 ? 1 : 0;
-    a.zt_p = std::getenv("VITSMI_NO_ZERO_TAP_SKIP") ? -1 : d.zt_p;
-}
-
 static int run_test_conv_sx(const ConvDesc &d, const std::vector<float> &arena, const float *x, int B, int T, int flags,
                             float slope, float *out) {
     const int Cr = d.Cout / d.ups, To = T * d.ups;
@@ -3060,8 +3065,7 @@ static int run_test_conv_sx(const ConvDesc &d, const std::vector<float> &arena, 
                                                                          d.h1 ? 2 : (d.f16 ? 1 : 0));
     TCHECK(hipMalloc((void **)&dres, nx * 4 + 16));  // x in the raw layout: raw-input operand and residual
     sx_block_kernel<<<dim3((T + 255) / 256, d.Cin / 8, B), 256>>>(dx, (int64_t)d.Cin * T, T, nullptr, dres, d.Cin, T);
-    SxArgs a{};
-    fill_sx_args(a, d, dA, T);
+    SxArgs a = sx_args(d, dA, dA, T);  // (pack_test_* reserve a zero page at offset 0)
     a.xp = reinterpret_cast<const u32x4 *>(dxp);
     a.xr = dres;
     a.islope = (flags & 8) ? slope : 1.f;  // (raw-input convs only)
@@ -3079,9 +3083,7 @@ static int run_test_conv_sx(const ConvDesc &d, const std::vector<float> &arena, 
         a.flags |= EPI_RES;
     }
     const int nprod = d.h1 ? 1 : (d.f16 ? 2 : 6);
-    a.wscale = d.wscale;
     if (flags & 256) {  // the short-launch kernel (conv_sx_small.hip.hpp) with the generator's epilogue
-        a.s16 = d.s16 ? 1 : 0;
         if (!conv_sx_small_ok(a, d.rawin, nprod)) return fail(nullptr, VITS_E_ARG, "arguments not taken by the short-launch kernel");
         TCHECK(launch_conv_sx_small(a, B, d.cfg, nullptr));
     } else
@@ -3164,10 +3166,7 @@ int vits_test_conv1d_sx_planar(int device_id, const float *x, int B, int Cin, in
         }
     }
     sx_split_planes_kernel<<<dim3((T + 255) / 256, Cin / 8, B), 256>>>(dx, (int64_t)Cin * T, T, nullptr, dxp, Cin, T, 1);
-    SxArgs a{};
-    fill_sx_args(a, d, dA, T);
-    a.wscale = d.wscale;
-    a.s16 = 1;
+    SxArgs a = sx_args(d, dA, dA, T);  // (pack_test_* reserve a zero page at offset 0)
     a.xp = reinterpret_cast<const u32x4 *>(dxp);
     a.out_raw = row_split ? d1 : nullptr;
     a.out_raw2 = srows ? d2 : nullptr;
@@ -3234,10 +3233,7 @@ int vits_test_conv1d_sx_gate(int device_id, const float *x, int B, int Cin, int 
     TCHECK(hipMemcpy(dbb, bias_b, (size_t)B * Cout * 4, hipMemcpyHostToDevice));
     TCHECK(hipMemset(dact, 0xff, no * 4));
     sx_split_planes_kernel<<<dim3((T + 255) / 256, Cin / 8, B), 256>>>(dx, (int64_t)Cin * T, T, nullptr, dxp, Cin, T, 1);
-    SxArgs a{};
-    fill_sx_args(a, d, dA, T);
-    a.wscale = d.wscale;
-    a.s16 = 1;
+    SxArgs a = sx_args(d, dA, dA, T);  // (pack_test_* reserve a zero page at offset 0)
     a.xp = reinterpret_cast<const u32x4 *>(dxp);
     a.bias_b = dbb;
     a.bias_b_stride = Cout;
@@ -3484,9 +3480,7 @@ int vits_bench_conv1d_sx(int device_id, int B, int Cin, int Cout, int T, int K, 
     TCHECK(hipMemset(dres, 0, no * 4));
     sx_split_planes_kernel<<<dim3((T + 255) / 256, Cin / 8, B), 256>>>(dx, (int64_t)Cin * T, T, nullptr, dxp, Cin, T,
                                                                        d.h1 ? 2 : (d.f16 ? 1 : 0));
-    SxArgs a{};
-    fill_sx_args(a, d, dA, T);
-    a.wscale = d.wscale;
+    SxArgs a = sx_args(d, dA, dA, T);  // (pack_test_* reserve a zero page at offset 0)
     a.xp = reinterpret_cast<const u32x4 *>(dxp);
     a.out_pl = dop;  // as the generator's inner convs: planes out
     a.oslope2 = 0.1f;
