@@ -20,6 +20,7 @@
 #include "../../include/g2pmi.h"
 #include "../../include/vitsmi.h"
 #include "g2p_model.hpp"
+#include "test_dev.hip.hpp"
 
 using namespace vitsmi;
 
@@ -1483,25 +1484,6 @@ int g2p_test_forced_steps(g2p_handle *h, const int64_t *input_ids, const int *le
 
 // ---- kernel-level test hooks: host buffers in, host buffers out, through linear_launch / step_launch (the engine's choice of
 // kernel), on a stream of their own
-namespace {
-struct DevBufs {
-    std::vector<void *> p;
-    ~DevBufs() {
-        for (void *q : p) hipFree(q);
-    }
-    float *up(const float *host, size_t n, bool &ok) {
-        void *d = nullptr;
-        if (!ok || hipMalloc(&d, (n ? n : 1) * sizeof(float)) != hipSuccess) {
-            ok = false;
-            return nullptr;
-        }
-        p.push_back(d);
-        if (host && hipMemcpy(d, host, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) ok = false;
-        return static_cast<float *>(d);
-    }
-};
-}  // namespace
-
 int g2p_test_linear(int device, int njobs, const float *const *W, const int *out, int in, const float *x, int T, int xp,
                     const float *const *res, int64_t y_rs, int64_t y_cs, int mode, float *const *y) {
     if (njobs < 1 || njobs > 3 || !W || !out || !x || !y || in < 1 || T < 1 || xp < T || (mode != 0 && mode != 1))
@@ -1518,28 +1500,27 @@ int g2p_test_linear(int device, int njobs, const float *const *W, const int *out
     }
     if (hipSetDevice(device) != hipSuccess) return gfail(nullptr, VITS_E_DEVICE, "hipSetDevice(%d) failed", device);
     DevBufs B;
-    bool ok = true;
     G2PLinArgs a{};
     a.njobs = njobs;
     a.in = in;
     a.T = T;
     a.xp = xp;
-    a.x = B.up(x, (size_t)in * xp, ok);
+    a.x = B.up(x, (size_t)in * xp);
     for (int j = 0; j < njobs; j++) {
         G2PLinJob &d = a.job[j];
-        d.W = B.up(W[j], (size_t)out[j] * in, ok);
-        d.y = B.up(y[j], ny[j], ok);  // (what the kernel does not write comes back as it went in)
-        d.res = res && res[j] ? B.up(res[j], ny[j], ok) : nullptr;
+        d.W = B.up(W[j], (size_t)out[j] * in);
+        d.y = B.up(y[j], ny[j]);  // (what the kernel does not write comes back as it went in)
+        d.res = res && res[j] ? B.up(res[j], ny[j]) : nullptr;
         d.out = out[j];
         d.tiles = (out[j] + 15) / 16;
         d.y_rs = y_rs;
         d.y_cs = y_cs;
     }
-    if (!ok) return gfail(nullptr, VITS_E_NOMEM, "g2p_test_linear: device buffers");
+    if (!B.ok()) return gfail(nullptr, VITS_E_NOMEM, "g2p_test_linear: device buffers");
     hipError_t e = linear_launch(nullptr, a, true, mode == 1);
     if (e == hipSuccess) e = hipGetLastError();
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    for (int j = 0; j < njobs && e == hipSuccess; j++) e = hipMemcpy(y[j], a.job[j].y, ny[j] * sizeof(float), hipMemcpyDeviceToHost);
+    for (int j = 0; j < njobs && e == hipSuccess; j++) e = download(y[j], a.job[j].y, ny[j]);
     if (e != hipSuccess) return gfail(nullptr, VITS_E_DEVICE, "g2p_test_linear failed: %s", hipGetErrorString(e));
     return VITS_OK;
 }
@@ -1553,33 +1534,32 @@ int g2p_test_step(int device, int NB, int njobs, const float *const *W, const fl
         if (!W[j] || !y[j] || out[j] < 1 || out[j] > (1 << 20)) return gfail(nullptr, VITS_E_ARG, "bad g2p_test_step job %d", j);
     if (hipSetDevice(device) != hipSuccess) return gfail(nullptr, VITS_E_DEVICE, "hipSetDevice(%d) failed", device);
     DevBufs B;
-    bool ok = true;
     G2PStepArgs a{};
     a.njobs = njobs;
     a.in = in;
     a.act = act;
     a.eps = eps;
     a.post = post;
-    a.x = B.up(x, (size_t)NB * in, ok);
-    a.g = g ? B.up(g, (size_t)in, ok) : nullptr;
+    a.x = B.up(x, (size_t)NB * in);
+    a.g = g ? B.up(g, (size_t)in) : nullptr;
     for (int j = 0; j < njobs; j++) {
         G2PStepJob &d = a.job[j];
         const size_t n = (size_t)NB * out[j];  // y / res: [NB][out]
-        d.W = B.up(W[j], (size_t)out[j] * in, ok);
-        d.W2 = W2 && W2[j] ? B.up(W2[j], (size_t)out[j] * in, ok) : nullptr;
-        d.y = B.up(y[j], n, ok);
-        d.res = res && res[j] ? B.up(res[j], n, ok) : nullptr;
+        d.W = B.up(W[j], (size_t)out[j] * in);
+        d.W2 = W2 && W2[j] ? B.up(W2[j], (size_t)out[j] * in) : nullptr;
+        d.y = B.up(y[j], n);
+        d.res = res && res[j] ? B.up(res[j], n) : nullptr;
         d.ys = 1;
         d.yb = out[j];
         d.out = out[j];
         d.blocks = (out[j] + 3) / 4;
     }
-    if (!ok) return gfail(nullptr, VITS_E_NOMEM, "g2p_test_step: device buffers");
+    if (!B.ok()) return gfail(nullptr, VITS_E_NOMEM, "g2p_test_step: device buffers");
     hipError_t e = step_launch(nullptr, NB, a);
     if (e == hipSuccess) e = hipGetLastError();
     if (e == hipSuccess) e = hipDeviceSynchronize();
     for (int j = 0; j < njobs && e == hipSuccess; j++)
-        e = hipMemcpy(y[j], a.job[j].y, (size_t)NB * out[j] * sizeof(float), hipMemcpyDeviceToHost);
+        e = download(y[j], a.job[j].y, (size_t)NB * out[j]);
     if (e != hipSuccess) return gfail(nullptr, VITS_E_DEVICE, "g2p_test_step failed: %s", hipGetErrorString(e));
     return VITS_OK;
 }

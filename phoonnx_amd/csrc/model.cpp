@@ -507,6 +507,10 @@ struct Packer {
     std::vector<float> &arena;
     const bool dry;
     int64_t size = 0;  // floats laid out so far (== arena.size() unless dry)
+    // what holds for a stretch of a build (read by pick_tiling):
+    int hint = 0;  // size class of the layers being packed: 0 = frame/sample domain (generator), 1 = frame domain (flow),
+                   // 2 = token domain (encoder, durations)
+    int cfg_override = -1, ck_override = -1;  // kernel tuning only (tools/conv_bench.py): this tile / chunk, no choice
     explicit Packer(std::vector<float> &a, bool dry_ = false) : arena(a), dry(dry_), size(int64_t(a.size())) {}
     int64_t alloc(int64_t n) {
         int64_t off = (size + 63) / 64 * 64;  // 256-byte alignment
@@ -548,13 +552,11 @@ size_t stage_capacity(int cfg) {  // conv_engine.hip.hpp conv_stage_floats
     return cfg <= 2 ? 9728 : size_t(cap3);
 }
 
-// hint: 0 = frame/sample domain (generator), 1 = frame domain (flow), 2 = token domain (encoder, durations)
-thread_local int t_cfg_override = -1, t_ck_override = -1;  // kernel tuning only (tools/conv_bench.py)
-
-void pick_tiling(int Cin, int Cout, int K, int dil, int padL, int hint, int &cfg, int &CK) {
-    if (t_cfg_override >= 0) {
-        cfg = t_cfg_override;
-        CK = t_ck_override > 0 ? t_ck_override : 8;
+void pick_tiling(const Packer &P, int Cin, int Cout, int K, int dil, int padL, int &cfg, int &CK) {
+    const int hint = P.hint;
+    if (P.cfg_override >= 0) {
+        cfg = P.cfg_override;
+        CK = P.ck_override > 0 ? P.ck_override : 8;
         if (stage_floats(cfg, K, dil, padL, CK) > stage_capacity(cfg)) throw std::runtime_error("override does not fit LDS");
         return;
     }
@@ -590,28 +592,17 @@ void pick_tiling(int Cin, int Cout, int K, int dil, int padL, int hint, int &cfg
                              ", dilation " + std::to_string(dil) + ")");
 }
 
-thread_local int t_hint = 0;  // size class of the layers being packed (set by Model::build)
-thread_local bool t_sx_f16 = false;  // pack_conv_sx: two scaled fp16 planes instead of three bf16 planes
-thread_local bool t_sx_force16 = false;  // pack_conv_sx: the 16x16x32 layout whatever the channel count (conv_sx_pair16's weights)
-thread_local bool t_sx_h1 = false;   // pack_conv_sx: ONE scaled fp16 plane in the 16x16x32 layout (VITSMI_GEN_PRECISION=f16)
-// the encoder / flow run f16x3 under the default arithmetic AND under the reduced-precision vocoder ("f16": everything in
-// front of z is unchanged); bf16x6 keeps them on their exact engines
-bool precision_is_fp16_family(const char *pe) { return !pe || !*pe || std::string(pe) == "f16x3" || std::string(pe) == "f16"; }
-thread_local int t_sx_min_cfg = 0;   // pack_conv_sx: smallest tile index allowed (1 = no 128-row tiles)
-thread_local bool t_sx_shape32 = false;  // pack_conv_sx: never the 16x16x32 packing (bench / ablation hooks)
-
 // W is addressed through a functor so that permutations / transposed-conv rewrites need no copies:
 // w(co, ci, tap) for co < Cout, ci < Cin, tap < K.
 template <class WF>
 ConvDesc pack_conv(Packer &P, int Cin, int Cout, int K, int dil, int padL, WF w, const float *bias_virtual) {
-    const int hint = t_hint;
     ConvDesc d;
     d.Cin = Cin;
     d.Cout = Cout;
     d.K = K;
     d.dil = dil;
     d.padL = padL;
-    pick_tiling(Cin, Cout, K, dil, padL, hint, d.cfg, d.CK);
+    pick_tiling(P, Cin, Cout, K, dil, padL, d.cfg, d.CK);
     d.nchunks = (Cin + d.CK - 1) / d.CK;
     int bm = tile_m(d.cfg);
     d.mblocks = (Cout + bm - 1) / bm * (bm / 32);
@@ -708,9 +699,10 @@ ConvDesc pack_convT(Packer &P, const Resolver &R, const std::string &name) {
 // ---- split-operand (sx) packing: weights as three bf16 planes (or two scaled fp16 planes) in the A-operand lane order of
 // v_mfma_f32_32x32x16_bf16 (lane l: row l&31, k = 8*(l>>5) .. +7 = eight consecutive input channels).
 int sx_tile_m(int cfg) { return cfg == 0 ? 128 : (cfg == 1 ? 64 : 32); }
-int sx_tile_n(int) { return 256; }
-int sx_pick_cfg(int Cout) {
-    static const int min_cfg = [] {
+constexpr int kSxTileN = 256;
+// min_cfg: smallest tile index the caller allows (SxPack::min_cfg)
+int sx_pick_cfg(int Cout, int min_cfg) {
+    static const int env_min_cfg = [] {
         const char *e = std::getenv("VITSMI_SX_MIN_CFG");  // tuning experiments only: 1 = no 128-row tiles
         return e ? std::atoi(e) : 0;
     }();
@@ -720,12 +712,12 @@ int sx_pick_cfg(int Cout) {
     }();
     int cfg = Cout % 128 == 0 ? 0 : (Cout % 64 == 0 ? 1 : 2);
     if (Cout == cfg1_for && cfg == 0) cfg = 1;
-    const int lo = min_cfg > t_sx_min_cfg ? min_cfg : t_sx_min_cfg;
+    const int lo = min_cfg > env_min_cfg ? min_cfg : env_min_cfg;
     return cfg < lo ? lo : cfg;
 }
 
 template <class WF>
-ConvDesc pack_conv_sx(Packer &P, int Cin, int Cout, int K, int dil, int padL, WF w, const float *bias_virtual) {
+ConvDesc pack_conv_sx(Packer &P, SxPack fmt, int Cin, int Cout, int K, int dil, int padL, WF w, const float *bias_virtual) {
     if (!sx_supported(Cin, Cout, Cout, K, dil)) throw std::runtime_error("conv shape not supported by the sx engine");
     // the 32x32x16 pipeline needs >= 3 taps per chunk: narrower kernels get zero taps appended on the right.  (The
     // 16x16x32 loop waits for everything at each chunk start and takes a 1 x 1 conv as it is: decided below.)
@@ -734,14 +726,14 @@ ConvDesc pack_conv_sx(Packer &P, int Cin, int Cout, int K, int dil, int padL, WF
         const char *e = std::getenv("VITSMI_SX_SHAPE");  // "32": A/B timing against the v_mfma_f32_32x32x16 loop
         return e && std::string(e) == "32";
     }();
-    const bool h1 = t_sx_h1;
+    const bool h1 = fmt.planes == SxPack::F16X1, f16 = fmt.planes == SxPack::F16X2;
     if (h1 && (Cin % 32 || (size_t)4 * (256 + (Kreal - 1) * dil) * 16 > (size_t)10 * 4096))
         throw std::runtime_error("the f16 single-plane arithmetic needs Cin % 32 == 0 and a halo of at most 384 columns");
     // (force16: the 32- / 64-channel convs of a plane-stream generator - the fused pair kernel's weights; their own x stage
     // of up to twelve DMA rounds serves the unfused fallback)
-    const bool want16 = h1 || (t_sx_f16 && t_sx_force16 && sx_raw_format(Cin) && Cin % 32 == 0 &&
+    const bool want16 = h1 || (f16 && fmt.force16 && sx_raw_format(Cin) && Cin % 32 == 0 &&
                                (size_t)8 * (256 + (Kreal - 1) * dil) * 16 <= (size_t)12 * 4096) ||
-                        (t_sx_f16 && !sx_raw_format(Cin) && !shape32_only && !t_sx_shape32 && Cin % 32 == 0 &&
+                        (f16 && !sx_raw_format(Cin) && !shape32_only && !fmt.no_s16 && Cin % 32 == 0 &&
                          (size_t)8 * (256 + (Kreal - 1) * dil) * 16 <= (size_t)10 * 4096);
     if (K < 3 && !want16) K = 3;
     auto wz = [&](int co, int ci, int tap) { return tap < Kreal ? w(co, ci, tap) : 0.f; };
@@ -754,13 +746,13 @@ ConvDesc pack_conv_sx(Packer &P, int Cin, int Cout, int K, int dil, int padL, WF
     d.padL = padL;
     d.CK = 16;
     d.nchunks = Cin / 16;
-    d.rawin = sx_raw_format(Cin) && !h1 && !(t_sx_f16 && t_sx_force16);  // (plane-stream generators: every tensor is a plane tensor)
+    d.rawin = sx_raw_format(Cin) && !h1 && !(f16 && fmt.force16);  // (plane-stream generators: every tensor is a plane tensor)
     d.h1 = h1;
-    d.cfg = sx_pick_cfg(Cout);
+    d.cfg = sx_pick_cfg(Cout, fmt.min_cfg);
     if (d.rawin && d.cfg == 0) d.cfg = 1;  // the raw-input path exists for the 64- and 32-row tiles only
     d.mblocks = Cout / 32;
     const int MB = sx_tile_m(d.cfg) / 32;
-    const int npw = h1 ? 1 : (t_sx_f16 ? 2 : 3);                   // planes per 32-row block
+    const int npw = h1 ? 1 : (f16 ? 2 : 3);                   // planes per 32-row block
     // 16x16x32 main loop (f16x3, plane input, 32-channel chunks): when the x stage of a 32-channel chunk (8 rows of
     // 256 + halo cells) fits ten DMA rounds, i.e. two workgroups per CU
     d.s16 = want16;
@@ -773,7 +765,7 @@ ConvDesc pack_conv_sx(Packer &P, int Cin, int Cout, int K, int dil, int padL, WF
     if (bias_virtual) d.b_off = P.put(bias_virtual, Cout);
     d.macs_per_t = double(Cin) * Cout * Kreal;
     float wmul = 1.f;
-    if (t_sx_f16 || h1) {
+    if (f16 || h1) {
         // per-tensor power of two that lifts the largest weight into [2^14, 2^15): both fp16 planes of every weight
         // within 2^-18 of the largest are then normal numbers; undone exactly on the accumulators
         float wmax = 0.f;
@@ -819,7 +811,7 @@ ConvDesc pack_conv_sx(Packer &P, int Cin, int Cout, int K, int dil, int padL, WF
                     for (int i = 0; i < 8; i++) {
                         uint16_t p[3];
                         const float wv = wz(mb * 32 + (lane & 31), chunk * 16 + 8 * (lane >> 5) + i, tap);
-                        if (t_sx_f16) split2h_host(wv * wmul, p);
+                        if (f16) split2h_host(wv * wmul, p);
                         else split3_host(wv, p);
                         for (int pl = 0; pl < npw; pl++) dst[(base + pl) * 512 + lane * 8 + i] = p[pl];
                     }
@@ -828,7 +820,7 @@ ConvDesc pack_conv_sx(Packer &P, int Cin, int Cout, int K, int dil, int padL, WF
 }
 
 // out_perm (optional): packed row r holds the module's output channel out_perm[r]
-ConvDesc pack_named_sx(Packer &P, const Resolver &R, const std::string &name, int dil, int padL,
+ConvDesc pack_named_sx(Packer &P, const Resolver &R, SxPack fmt, const std::string &name, int dil, int padL,
                        const std::vector<int> *out_perm = nullptr) {
     const TRef &w = R.need(name + ".weight", 3);
     int Cout = int(w.dims[0]), Cin = int(w.dims[1]), K = int(w.dims[2]);
@@ -844,7 +836,7 @@ ConvDesc pack_named_sx(Packer &P, const Resolver &R, const std::string &name, in
         for (int c = 0; c < Cout; c++) bperm[c] = b->p[(*out_perm)[c]];
         bp = bperm.data();
     }
-    return pack_conv_sx(P, Cin, Cout, K, dil, padL, wf, bp);
+    return pack_conv_sx(P, fmt, Cin, Cout, K, dil, padL, wf, bp);
 }
 
 // geometry of ConvTranspose1d [Cin, Cout, K] (stride u, padding p) as a dense conv over taps o_min..o_max
@@ -877,7 +869,7 @@ ConvTGeom convt_geom(const Resolver &R, const std::string &name) {
 // holds 32 consecutive real channels of ONE output phase r, which is what the sx epilogue's cell stores need, and the
 // blocks of a tile are the phases of the same channels, so that a workgroup writes whole runs of an output line
 // (conv_sx_engine.hip.hpp, geom).
-ConvDesc pack_convT_sx(Packer &P, const Resolver &R, const std::string &name) {
+ConvDesc pack_convT_sx(Packer &P, const Resolver &R, SxPack fmt, const std::string &name) {
     const ConvTGeom g = convt_geom(R, name);
     const float *wp = R.req(name + ".weight").p;
     const int Kv = g.o_max - g.o_min + 1;
@@ -906,7 +898,7 @@ ConvDesc pack_convT_sx(Packer &P, const Resolver &R, const std::string &name) {
         }
     }
     if (g.Cout % 32) throw std::runtime_error(name + ": sx transposed conv needs Cout % 32 == 0");
-    ConvDesc d = pack_conv_sx(P, g.Cin, g.Cout * g.u, Kv, 1, -g.o_min, wf, b ? bv.data() : nullptr);
+    ConvDesc d = pack_conv_sx(P, fmt, g.Cin, g.Cout * g.u, Kv, 1, -g.o_min, wf, b ? bv.data() : nullptr);
     d.ups = g.u;
     d.macs_per_t = double(g.Cin) * g.Cout * g.K;
     // K = 2 u, three dense taps starting at -1: phase r reads taps {e, e + 1} with e = (r + p) / u in {0, 1} - the third is zero
@@ -1054,47 +1046,26 @@ void split2h_host(float v, uint16_t p[3]) {
     p[2] = 0;
 }
 
-void set_sx_f16(bool on) { t_sx_f16 = on; }
-void set_sx_h1(bool on) { t_sx_h1 = on; }
-void set_sx_force16(bool on) { t_sx_force16 = on; }
-void set_sx_shape32(bool on) { t_sx_shape32 = on; }
-
-// Arithmetic of the split-operand convs for the opens that follow on this thread: an explicit choice
-// (vits_open_opts) wins over VITSMI_GEN_PRECISION in the environment; nullptr / "" = the default (f16x3).
-thread_local std::string t_precision_override;
-thread_local bool t_precision_set = false;
-void set_gen_precision_override(const char *name) {
-    t_precision_set = name != nullptr;
-    t_precision_override = name ? name : "";
-}
-const char *gen_precision_name() {
-    return t_precision_set ? t_precision_override.c_str() : std::getenv("VITSMI_GEN_PRECISION");
-}
-
 bool sx_supported(int Cin, int Cout_virtual, int Cr, int K, int dil) {
     if (Cin < 16 || Cin % 16 || Cout_virtual % 32 || Cr % 32 || K < 1 || dil < 1) return false;
-    const int cfg = sx_pick_cfg(Cout_virtual);
     // an x stage is at most 12 DMA rounds of 4 KiB (conv_sx_engine.hip.hpp launch_conv_sx)
-    const size_t LW = size_t(sx_tile_n(cfg)) + size_t((K < 3 ? 3 : K) - 1) * dil;
+    const size_t LW = size_t(kSxTileN) + size_t((K < 3 ? 3 : K) - 1) * dil;
     const size_t x_bytes = (6 * LW * 16 + 4095) / 4096 * 4096;
     if (sx_raw_format(Cin) && 2 * LW > 768) return false;  // raw-input staging: three cells per thread
     return x_bytes <= 12 * 4096;
 }
 
-void set_tiling_override(int cfg, int ck) {
-    t_cfg_override = cfg;
-    t_ck_override = ck;
-}
-
 std::string pack_test_conv(const float *w, const float *bias, int Cin, int Cout, int K, int dil, int pad_l, int hint,
-                           ConvDesc *d, std::vector<float> *arena) {
+                           ConvDesc *d, std::vector<float> *arena, const TestPack &o) {
     if (Cin < 1 || Cout < 1 || K < 1 || dil < 1 || pad_l < 0) return "bad conv shape";
-    t_hint = hint;
     Packer P(*arena);
+    P.hint = hint;
+    P.cfg_override = o.cfg;
+    P.ck_override = o.ck;
     P.alloc(256);  // zero page at offset 0
     auto wf = [&](int co, int ci, int tap) { return w[(int64_t(co) * Cin + ci) * K + tap]; };
     try {
-        if (hint == 3) *d = pack_conv_sx(P, Cin, Cout, K, dil, pad_l, wf, bias);
+        if (hint == 3) *d = pack_conv_sx(P, o.sx, Cin, Cout, K, dil, pad_l, wf, bias);
         else *d = pack_conv(P, Cin, Cout, K, dil, pad_l, wf, bias);
     } catch (const std::exception &e) {
         return e.what();
@@ -1103,9 +1074,8 @@ std::string pack_test_conv(const float *w, const float *bias, int Cin, int Cout,
 }
 
 std::string pack_test_convT(const float *w, const float *bias, int Cin, int Cout, int K, int stride, ConvDesc *d,
-                            std::vector<float> *arena, bool sx) {
+                            std::vector<float> *arena, bool sx, const TestPack &o) {
     try {
-        t_hint = 0;
         Resolver R;
         TRef t;
         t.p = w;
@@ -1120,19 +1090,31 @@ std::string pack_test_convT(const float *w, const float *bias, int Cin, int Cout
         R.ints["t.stride"] = stride;
         R.ints["t.pad"] = (K - stride) / 2;
         Packer P(*arena);
+        P.cfg_override = o.cfg;
+        P.ck_override = o.ck;
         P.alloc(256);  // zero page at offset 0
-        *d = sx ? pack_convT_sx(P, R, "t") : pack_convT(P, R, "t");
+        *d = sx ? pack_convT_sx(P, R, o.sx, "t") : pack_convT(P, R, "t");
     } catch (const std::exception &e) {
         return e.what();
     }
     return "";
 }
 
-std::string Model::build(const OnnxModel &om, bool layout_only) {
-    t_sx_f16 = false;
-    t_sx_h1 = false;
-    t_sx_force16 = false;
+std::string Model::build(const OnnxModel &om, bool layout_only, const char *precision_name) {
     try {
+        // default: the split-operand convs on two fp16 planes / three products per fp32 product (fp32-grade error);
+        // bf16x6: three bf16 planes, six exact products; f16: the generator on ONE fp16 plane (see Model::Precision).
+        // An unknown name is refused where the generator's engine is chosen, behind whatever the file itself is refused
+        // for; until there it packs like bf16x6, the arithmetic that asks nothing of a layer.
+        const char *pe = precision_name && *precision_name ? precision_name : std::getenv("VITSMI_GEN_PRECISION");
+        const std::string ps = pe ? pe : "";
+        const bool precision_known = ps.empty() || ps == "f16x3" || ps == "bf16x6" || ps == "f16";
+        precision = (ps.empty() || ps == "f16x3") ? Precision::F16X3 : (ps == "f16" ? Precision::F16 : Precision::BF16X6);
+        // the formats the sections below pack in.  Encoder and flow: two fp16 planes under the default arithmetic AND under
+        // the reduced-precision vocoder ("f16": everything in front of z is unchanged); bf16x6 keeps them exact
+        const bool fp16_family = precision != Precision::BF16X6;
+        SxPack f16x2;
+        f16x2.planes = SxPack::F16X2;
         Resolver R;
         resolve(om, R);
         arena.clear();
@@ -1153,7 +1135,7 @@ std::string Model::build(const OnnxModel &om, bool layout_only) {
                 throw std::runtime_error("language-embedding conditioned voices are not supported (" + kv.first + ")");
 
         // ---------------- text encoder (models.py:168-209, attentions.py)
-        t_hint = 2;
+        P.hint = 2;
         const TRef &embw = R.need("enc_p.emb.weight", 2);
         n_vocab = int(embw.dims[0]);
         H = int(embw.dims[1]);
@@ -1165,9 +1147,7 @@ std::string Model::build(const OnnxModel &om, bool layout_only) {
         bool enc_want_sx = false;
         {
             const char *ge = std::getenv("VITSMI_GEN_ENGINE"), *ee = std::getenv("VITSMI_ENC_ENGINE");
-            const char *pe = gen_precision_name();
-            enc_want_sx = !(ge && std::string(ge) == "f32") && !(ee && std::string(ee) == "f32") &&
-                          precision_is_fp16_family(pe) && H % 32 == 0;
+            enc_want_sx = !(ge && std::string(ge) == "f32") && !(ee && std::string(ee) == "f32") && fp16_family && H % 32 == 0;
         }
         bool enc_all_sx = enc_want_sx;
         auto sx_twin = [&](const ConvDesc &f, const std::function<ConvDesc()> &mk) {
@@ -1176,9 +1156,7 @@ std::string Model::build(const OnnxModel &om, bool layout_only) {
                 enc_all_sx = false;
                 return d;
             }
-            t_sx_f16 = true;
             d = mk();
-            t_sx_f16 = false;
             if (!d.sx || !d.f16 || !d.s16 || d.K != f.K) enc_all_sx = false;
             return d;
         };
@@ -1203,8 +1181,8 @@ std::string Model::build(const OnnxModel &om, bool layout_only) {
             std::memcpy(b3.data() + 2 * H, bv.p, size_t(H) * 4);
             L.qkv = pack_conv(P, H, 3 * H, 1, 1, 0, wf, b3.data());
             L.o = pack_named(P, R, a + ".conv_o", 1, 0);
-            L.qkv_sx = sx_twin(L.qkv, [&] { return pack_conv_sx(P, H, 3 * H, 1, 1, 0, wf, b3.data()); });
-            L.o_sx = sx_twin(L.o, [&] { return pack_named_sx(P, R, a + ".conv_o", 1, 0); });
+            L.qkv_sx = sx_twin(L.qkv, [&] { return pack_conv_sx(P, f16x2, H, 3 * H, 1, 1, 0, wf, b3.data()); });
+            L.o_sx = sx_twin(L.o, [&] { return pack_named_sx(P, R, f16x2, a + ".conv_o", 1, 0); });
             const TRef &rk = R.need(a + ".emb_rel_k", 3);
             if (rk.dims[0] != 1) throw std::runtime_error("per-head relative embeddings are unsupported");
             if (rk.dims[1] % 2 != 1) throw std::runtime_error(a + ".emb_rel_k: expected 2*window+1 rows");
@@ -1229,8 +1207,8 @@ std::string Model::build(const OnnxModel &om, bool layout_only) {
             L.ffn1 = pack_named(P, R, f + ".conv_1", 1, (fk - 1) / 2);  // attentions.py:419-427
             L.ffn2 = pack_named(P, R, f + ".conv_2", 1, (fk - 1) / 2);
             if (L.ffn1.Cin != H || L.ffn2.Cin != FF || L.ffn2.Cout != H) throw std::runtime_error(f + ": unexpected FFN shape");
-            L.ffn1_sx = sx_twin(L.ffn1, [&] { return pack_named_sx(P, R, f + ".conv_1", 1, (fk - 1) / 2); });
-            L.ffn2_sx = sx_twin(L.ffn2, [&] { return pack_named_sx(P, R, f + ".conv_2", 1, (fk - 1) / 2); });
+            L.ffn1_sx = sx_twin(L.ffn1, [&] { return pack_named_sx(P, R, f16x2, f + ".conv_1", 1, (fk - 1) / 2); });
+            L.ffn2_sx = sx_twin(L.ffn2, [&] { return pack_named_sx(P, R, f16x2, f + ".conv_2", 1, (fk - 1) / 2); });
             enc.push_back(L);
         }
         n_layers = int(enc.size());
@@ -1238,7 +1216,7 @@ std::string Model::build(const OnnxModel &om, bool layout_only) {
         enc_proj = pack_named(P, R, "enc_p.proj", 1, 0);
         if (enc_proj.Cin != H || enc_proj.K != 1 || enc_proj.Cout % 2) throw std::runtime_error("enc_p.proj: unexpected shape");
         C = enc_proj.Cout / 2;
-        enc_proj_sx = sx_twin(enc_proj, [&] { return pack_named_sx(P, R, "enc_p.proj", 1, 0); });
+        enc_proj_sx = sx_twin(enc_proj, [&] { return pack_named_sx(P, R, f16x2, "enc_p.proj", 1, 0); });
         enc_sx = enc_all_sx;
 
         // ---------------- speaker embedding (models.py:614-615)
@@ -1302,7 +1280,7 @@ std::string Model::build(const OnnxModel &om, bool layout_only) {
         }
 
         // ---------------- flow (models.py:212-254), Flip folded into channel permutations
-        t_hint = 1;
+        P.hint = 1;
         {
             int nfl = 0;
             while (R.get("flow.flows." + std::to_string(2 * nfl) + ".pre.weight")) nfl++;
@@ -1336,17 +1314,17 @@ std::string Model::build(const OnnxModel &om, bool layout_only) {
                     const bool f32_only = env && std::string(env) == "f32";
                     const int ci = int(w->dims[1]), co = int(w->dims[0]);
                     if (!f32_only && !sx_raw_format(ci) && co % 64 == 0 && ci % 8 == 0 && sx_supported(ci, co, co, k, dil)) {
-                        const char *pe = gen_precision_name();  // (same arithmetic as the generator)
-                        t_sx_f16 = precision_is_fp16_family(pe);
+                        SxPack fmt;
+                        fmt.planes = fp16_family ? SxPack::F16X2 : SxPack::BF16X3;  // (same arithmetic as the generator)
                         // frame-domain tensors are short (F ~ 3 T): 64-row tiles give the grid twice the workgroups
                         // (288 -> 576 at batch 32), measured 3.04 -> 2.87 ms for the flow
-                        t_sx_min_cfg = 1;
+                        fmt.min_cfg = 1;
                         // Gate folded into this conv's epilogue (SX_GATE): rows permuted so that every 64-row tile holds
                         // 32 tanh channels and their 32 sigmoid partners (row r of tile m: channel 32 m + r for r < 32,
                         // H + 32 m + r - 32 above).  VITSMI_FLOW_NO_GATE keeps the separate gate kernel (A/B timing).
                         static const bool no_gate = std::getenv("VITSMI_FLOW_NO_GATE") != nullptr;
                         std::vector<int> perm;
-                        const bool gate = !no_gate && co == 2 * flow_H && flow_H % 32 == 0 && sx_pick_cfg(co) == 1;
+                        const bool gate = !no_gate && co == 2 * flow_H && flow_H % 32 == 0 && sx_pick_cfg(co, fmt.min_cfg) == 1;
                         if (gate) {
                             perm.resize(co);
                             for (int r = 0; r < co; r++) {
@@ -1354,10 +1332,8 @@ std::string Model::build(const OnnxModel &om, bool layout_only) {
                                 perm[r] = rr < 32 ? 32 * m + rr : flow_H + 32 * m + rr - 32;
                             }
                         }
-                        cd.wn[i].in = pack_named_sx(P, R, in, dil, same_pad(k, dil), gate ? &perm : nullptr);
+                        cd.wn[i].in = pack_named_sx(P, R, fmt, in, dil, same_pad(k, dil), gate ? &perm : nullptr);
                         cd.wn[i].in.gate = gate;
-                        t_sx_min_cfg = 0;
-                        t_sx_f16 = false;
                     } else
                         cd.wn[i].in = pack_named(P, R, in, dil, same_pad(k, dil));
                     cd.wn[i].rs = pack_named(P, R, s + ".enc.res_skip_layers." + std::to_string(i), 1, 0);
@@ -1368,9 +1344,7 @@ std::string Model::build(const OnnxModel &om, bool layout_only) {
                         static const bool rs_f32 = std::getenv("VITSMI_FLOW_RS_F32") != nullptr;
                         const auto &inl = cd.wn[i].in;
                         if (!rs_f32 && inl.sx && inl.f16 && inl.gate && inl.s16 && flow_H % 32 == 0) {
-                            t_sx_f16 = true;
-                            ConvDesc r2 = pack_named_sx(P, R, s + ".enc.res_skip_layers." + std::to_string(i), 1, 0);
-                            t_sx_f16 = false;
+                            ConvDesc r2 = pack_named_sx(P, R, f16x2, s + ".enc.res_skip_layers." + std::to_string(i), 1, 0);
                             if (r2.s16 && r2.K == 1) cd.wn[i].rs_sx = r2;
                         }
                     }
@@ -1404,10 +1378,8 @@ std::string Model::build(const OnnxModel &om, bool layout_only) {
                             for (int c = 0; c < half; c++) bperm[c] = bpost->p[rev[c]];
                             bp = bperm.data();
                         }
-                        t_sx_f16 = true;
-                        ConvDesc a = pack_conv_sx(P, half, flow_H, 1, 1, 0, wf_pre, bpre ? bpre->p : nullptr);
-                        ConvDesc b = pack_conv_sx(P, flow_H, half, 1, 1, 0, wf_post, bp);
-                        t_sx_f16 = false;
+                        ConvDesc a = pack_conv_sx(P, f16x2, half, flow_H, 1, 1, 0, wf_pre, bpre ? bpre->p : nullptr);
+                        ConvDesc b = pack_conv_sx(P, f16x2, flow_H, half, 1, 1, 0, wf_post, bp);
                         if (a.s16 && b.s16 && a.K == 1 && b.K == 1) {
                             cd.pre_sx = a;
                             cd.post_sx = b;
@@ -1425,7 +1397,7 @@ std::string Model::build(const OnnxModel &om, bool layout_only) {
         }
 
         // ---------------- generator (models.py:299-368)
-        t_hint = 0;
+        P.hint = 0;
         int nups = 0;
         while (R.get("dec.ups." + std::to_string(nups) + ".weight")) nups++;
         int nrb = 0;
@@ -1459,18 +1431,13 @@ std::string Model::build(const OnnxModel &om, bool layout_only) {
                     ok = conv_ok(c1) && (!t1 || conv_ok(rb + ".convs2." + std::to_string(q)));
                 }
             gen_sx = ok;
-            // default: the generator's convs on two fp16 planes / three products per fp32 product (fp32-grade error);
-            // VITSMI_GEN_PRECISION=bf16x6 (exact products, six bf16 plane products), bf16x3 or bf16 pack bf16 planes
-            const char *pe = gen_precision_name();
-            gen_f16 = gen_sx && (!pe || !*pe || std::string(pe) == "f16x3");
+            if (!precision_known)
+                throw std::runtime_error("unknown generator precision '" + ps + "' (VITSMI_GEN_PRECISION: f16x3, bf16x6, f16)");
+            gen_f16 = gen_sx && precision == Precision::F16X3;
             // "f16": ONE fp16 plane per operand, one product, activations stored as fp16 (BASELINE config 4's reduced-
             // precision vocoder); needs every generator conv on the 16x16x32 loop (pack_conv_sx throws where it cannot)
-            gen_h1 = gen_sx && pe && std::string(pe) == "f16";
-            if (pe && *pe && std::string(pe) != "f16x3" && std::string(pe) != "f16" && std::string(pe) != "bf16x6")
-                throw std::runtime_error(std::string("unknown generator precision '") + pe + "' (VITSMI_GEN_PRECISION: f16x3, bf16x6, f16)");
+            gen_h1 = gen_sx && precision == Precision::F16;
         }
-        t_sx_f16 = gen_f16;
-        t_sx_h1 = gen_h1;
         // Both fp16 arithmetics run the PLANE-STREAM generator (vitsmi.hip run_generator_planes): every tensor between two
         // convs is stored once, as the operand planes of its consumer - also on the 32- / 64-channel stages, whose convs are
         // therefore packed for plane input on the 16x16x32 loop like everyone else (no raw-input kernels)
@@ -1479,9 +1446,11 @@ std::string Model::build(const OnnxModel &om, bool layout_only) {
         // tensors - so f16x3 keeps the raw-stream generator; VITSMI_F16X3_STREAM=planes selects the other for A/B runs)
         const char *se = std::getenv("VITSMI_F16X3_STREAM");
         gen_planes = gen_h1 || (gen_f16 && se && std::string(se) == "planes");
-        t_sx_force16 = gen_f16 && gen_planes;
+        SxPack gfmt;  // the generator's format, conv_pre to the last ResBlock
+        gfmt.planes = gen_h1 ? SxPack::F16X1 : (gen_f16 ? SxPack::F16X2 : SxPack::BF16X3);
+        gfmt.force16 = gen_f16 && gen_planes;
         auto gconv = [&](const std::string &name, int dil, int padL) {
-            return gen_sx ? pack_named_sx(P, R, name, dil, padL) : pack_named(P, R, name, dil, padL);
+            return gen_sx ? pack_named_sx(P, R, gfmt, name, dil, padL) : pack_named(P, R, name, dil, padL);
         };
         {
             const TRef &wpre = R.need("dec.conv_pre.weight", 3);
@@ -1496,7 +1465,7 @@ std::string Model::build(const OnnxModel &om, bool layout_only) {
         hop = 1;
         for (int i = 0; i < nups; i++) {
             UpStageDesc st;
-            st.up = gen_sx ? pack_convT_sx(P, R, "dec.ups." + std::to_string(i)) : pack_convT(P, R, "dec.ups." + std::to_string(i));
+            st.up = gen_sx ? pack_convT_sx(P, R, gfmt, "dec.ups." + std::to_string(i)) : pack_convT(P, R, "dec.ups." + std::to_string(i));
             st.u = st.up.ups;
             st.C = st.up.Cout / st.u;
             if (st.up.Cin != (i == 0 ? C0 : ups.back().C)) throw std::runtime_error("dec.ups: channel chain is broken");
@@ -1527,9 +1496,6 @@ std::string Model::build(const OnnxModel &om, bool layout_only) {
             }
             ups.push_back(st);
         }
-        t_sx_f16 = false;
-        t_sx_h1 = false;
-        t_sx_force16 = false;
         const TRef &pw = R.need("dec.conv_post.weight", 3);
         if (pw.dims[0] != 1) throw std::runtime_error("conv_post must have one output channel");
         if (ups.empty() || pw.dims[1] != ups.back().C) throw std::runtime_error("conv_post: input width differs from the last stage");

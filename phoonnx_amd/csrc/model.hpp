@@ -146,6 +146,12 @@ struct Model {
     std::vector<CouplingDesc> flow;
     int flow_H = 0;
 
+    // ---- arithmetic of the split-operand convs (resolved once by build): two fp16 planes / three products per fp32 product;
+    // three bf16 planes / six exact products; ONE fp16 plane / one product in the generator (reduced-precision vocoder).
+    // The encoder and the flow run F16X3 under F16 too; BF16X6 keeps them on their exact engines.
+    enum class Precision { F16X3, BF16X6, F16 };
+    Precision precision = Precision::F16X3;
+
     // ---- generator
     ConvDesc conv_pre;
     int C0 = 0;
@@ -166,19 +172,34 @@ struct Model {
 
     // Build from a parsed file.  Returns "" or an error message.  layout_only: compute every offset and descriptor
     // but materialise no weight (the packed bytes already live on the device: vits_open_with_arena).
-    std::string build(const OnnxModel &om, bool layout_only = false);
+    // precision: the arithmetic of the split-operand convs by name (f16x3, bf16x6, f16); nullptr or "" = VITSMI_GEN_PRECISION
+    // from the environment, f16x3 where that is unset too.  An unknown name is an error.
+    std::string build(const OnnxModel &om, bool layout_only = false, const char *precision = nullptr);
 
     // reference-definition work per unit: MACs per frame / per token
     double dec_macs_per_frame = 0, flow_macs_per_frame = 0, enc_macs_per_token = 0, dp_macs_per_token = 0;
     double dec_elems_per_frame = 0;  // conv input + output elements per frame (layer-granular bytes / 4)
 };
 
-// kernel-level test hooks: pack one conv / transposed conv into a private arena
+// How pack_conv_sx lays out one conv for the split-operand engine: stated by whoever packs it, conv by conv.
+struct SxPack {
+    enum Planes { BF16X3, F16X2, F16X1 };  // three bf16 planes; two scaled fp16 planes; ONE scaled fp16 plane (16x16x32 layout)
+    Planes planes = BF16X3;
+    bool force16 = false;  // F16X2: the 16x16x32 layout also for <= 64 input channels (the fused pair16 kernel's operand)
+    bool no_s16 = false;   // F16X2: never the 16x16x32 packing (bench hooks: ablation flags, A/B of the MFMA shapes)
+    int min_cfg = 0;       // smallest tile index allowed (1 = no 128-row tiles)
+};
+
+// kernel-level test hooks: pack one conv / transposed conv into a private arena.  hint 0-2 = the f32 engine's size class,
+// 3 = the split-operand engine in the format o.sx
+struct TestPack {
+    SxPack sx;
+    int cfg = -1, ck = -1;  // f32 engine: this tile / chunk instead of the automatic choice (kernel tuning only)
+};
 std::string pack_test_conv(const float *w, const float *bias, int Cin, int Cout, int K, int dil, int pad_l, int hint,
-                           ConvDesc *d, std::vector<float> *arena);
-void set_tiling_override(int cfg, int ck);  // -1,-1 = automatic (kernel tuning only)
+                           ConvDesc *d, std::vector<float> *arena, const TestPack &o = {});
 std::string pack_test_convT(const float *w, const float *bias, int Cin, int Cout, int K, int stride, ConvDesc *d,
-                            std::vector<float> *arena, bool sx = false);
+                            std::vector<float> *arena, bool sx = false, const TestPack &o = {});
 
 // fp32 -> bf16 planes of the split-exact engine (host mirror of split3 in conv_sx_engine.hip.hpp)
 uint16_t bf16_rne(float f);
@@ -188,14 +209,6 @@ void split3_host(float v, uint16_t p[3]);
 uint16_t f16_rne(float f);
 float f16_to_f32(uint16_t h);
 void split2h_host(float v, uint16_t p[3]);
-void set_sx_force16(bool on);  // ... the 16x16x32 layout also for <= 64 input channels (the fused pair kernel's operand)
-void set_sx_h1(bool on);   // ... one fp16 plane in the 16x16x32 layout (the NP = 1 mode)
-void set_sx_f16(bool on);  // pack_conv_sx format for the calls that follow on this thread (test hooks)
-void set_sx_shape32(bool on);  // ... never the 16x16x32 (s16) packing (bench hooks: ablation flags, A/B of the MFMA shapes)
-// generator arithmetic for the Model::build calls that follow on this thread: explicit name, or nullptr = take
-// VITSMI_GEN_PRECISION from the environment (default f16x3)
-void set_gen_precision_override(const char *name);
-const char *gen_precision_name();
 // may this conv shape run on the sx engine (channel multiples, LDS budget)?
 bool sx_supported(int Cin, int Cout_virtual, int Cr, int K, int dil);
 // Storage format of a generator tensor with C channels on the sx path: true = fp32 raw only (its consumers

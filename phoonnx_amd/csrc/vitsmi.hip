@@ -25,6 +25,7 @@
 #include "conv_sx_small.hip.hpp"
 #include "kernels.hip.hpp"
 #include "model.hpp"
+#include "test_dev.hip.hpp"
 
 using namespace vitsmi;
 
@@ -2103,8 +2104,9 @@ int run_frames(vits_handle *h, int B, int T, const RunRows &rr, const int64_t *d
 
 // ================================================================================== C ABI
 
+// precision: an explicit arithmetic name (vits_open_opts), or nullptr = VITSMI_GEN_PRECISION / the default
 static int open_common(const char *path, vits_handle **out, bool host_only, int device, void *ext_arena,
-                       size_t ext_bytes, bool layout_only = false) {
+                       size_t ext_bytes, bool layout_only = false, const char *precision = nullptr) {
     if (!out || !path) return fail(nullptr, VITS_E_ARG, "null argument");
     *out = nullptr;
     OnnxModel om;
@@ -2112,7 +2114,7 @@ static int open_common(const char *path, vits_handle **out, bool host_only, int 
     if (!e.empty()) return fail(nullptr, e.rfind("cannot open", 0) == 0 ? VITS_E_IO : VITS_E_FORMAT, "%s", e.c_str());
     vits_handle *h = new vits_handle();
     // a handle that adopts a resident arena only needs the layout (offsets, descriptors): no weight is re-packed
-    e = h->model.build(om, /*layout_only=*/ext_arena != nullptr || layout_only);
+    e = h->model.build(om, /*layout_only=*/ext_arena != nullptr || layout_only, precision);
     if (!e.empty()) {
         delete h;
         return fail(nullptr, VITS_E_FORMAT, "%s: %s", path, e.c_str());
@@ -2133,15 +2135,8 @@ static int open_common(const char *path, vits_handle **out, bool host_only, int 
         //   f16    the reduced-precision vocoder of BASELINE config 4: ONE fp16 plane per operand, one product, fp32
         //          accumulation, generator activations stored as fp16 (everything in front of z unchanged)
         // gen_nprod: 2 = f16x3, 1 = f16 (Model::build packed the weights for either), 6 = the six bf16 plane products.
-        const char *pe = gen_precision_name();
-        const std::string ps = pe ? pe : "";
-        if (ps.empty() || ps == "f16x3") h->gen_nprod = 2;
-        else if (ps == "bf16x6") h->gen_nprod = 6;
-        else if (ps == "f16") h->gen_nprod = 1;
-        else {
-            delete h;
-            return fail(nullptr, VITS_E_ARG, "VITSMI_GEN_PRECISION must be f16x3, bf16x6 or f16 (got '%s')", pe);
-        }
+        const Model::Precision pr = h->model.precision;  // (resolved by Model::build, which refuses an unknown name)
+        h->gen_nprod = pr == Model::Precision::F16X3 ? 2 : (pr == Model::Precision::F16 ? 1 : 6);
         if (!h->model.gen_sx) {
             // (a generator the split-operand engine cannot take - a channel count that is not a multiple of 32 - runs on the f32
             // engine: fine for the two fp32-grade requests, whose results it matches, but NOT a reduced-precision vocoder: an
@@ -2212,11 +2207,8 @@ int vits_open_layout(const char *p, vits_handle **out) { return open_common(p, o
 int vits_open_opts(const char *p, const vits_open_options *o, vits_handle **out) {
     if (!o) return fail(nullptr, VITS_E_ARG, "null options");
     if (o->arena_dev && o->host_only) return fail(nullptr, VITS_E_ARG, "host_only excludes arena_dev");
-    set_gen_precision_override(o->gen_precision && *o->gen_precision ? o->gen_precision : nullptr);
-    const int rc = open_common(p, out, o->host_only != 0, o->host_only ? -1 : o->device_id, o->arena_dev, o->arena_bytes,
-                               o->layout_only != 0);
-    set_gen_precision_override(nullptr);
-    return rc;
+    return open_common(p, out, o->host_only != 0, o->host_only ? -1 : o->device_id, o->arena_dev, o->arena_bytes,
+                       o->layout_only != 0, o->gen_precision);
 }
 
 void vits_close(vits_handle *h) {
@@ -2928,14 +2920,12 @@ static int test_dev(int device_id) {
 
 static int run_test_conv(const ConvDesc &d, const std::vector<float> &arena, const float *x, int B, int T,
                          int flags, float slope, float *out, size_t out_elems, int64_t out_bstride) {
-    float *dA = nullptr, *dx = nullptr, *dout = nullptr;
-    size_t nx = (size_t)B * d.Cin * T;
-    TCHECK(hipMalloc((void **)&dA, arena.size() * 4));
-    TCHECK(hipMalloc((void **)&dx, nx * 4 + 16));
-    TCHECK(hipMalloc((void **)&dout, out_elems * 4 + 16));
-    TCHECK(hipMemcpy(dA, arena.data(), arena.size() * 4, hipMemcpyHostToDevice));
-    TCHECK(hipMemcpy(dx, x, nx * 4, hipMemcpyHostToDevice));
-    TCHECK(hipMemset(dout, 0, out_elems * 4));
+    DevBufs D;
+    const size_t nx = (size_t)B * d.Cin * T;
+    float *dA = D.up(arena.data(), arena.size());
+    float *dx = D.up(x, nx, 16);
+    float *dout = D.fill<float>(out_elems, 0, 16);
+    TCHECK(D.err);
     ConvArgs a = conv_args(d, dA, dA);  // (pack_test_* reserve a zero page at offset 0)
     a.x = dx;
     a.x_bstride = (int64_t)d.Cin * T;
@@ -2946,10 +2936,7 @@ static int run_test_conv(const ConvDesc &d, const std::vector<float> &arena, con
     a.slope = slope;
     TCHECK(launch_conv(a, d.cfg, B, nullptr));
     TCHECK(hipDeviceSynchronize());
-    TCHECK(hipMemcpy(out, dout, out_elems * 4, hipMemcpyDeviceToHost));
-    hipFree(dA);
-    hipFree(dx);
-    hipFree(dout);
+    TCHECK(download(out, dout, out_elems));
     return VITS_OK;
 }
 
@@ -2962,12 +2949,8 @@ int vits_test_conv1d(int device_id, const float *x, int B, int Cin, int T, const
     return run_test_conv(d, arena, x, B, T, flags, slope, out, (size_t)B * Cout * T, (int64_t)Cout * T);
 }
 
-// Micro-benchmark of one conv shape on random data (kernel tuning; tools/conv_bench.py): returns the
-// average launch time in ms over `iters` back-to-back launches (HIP events on the null stream).
-int vits_bench_conv1d(int device_id, int B, int Cin, int Cout, int T, int K, int dil, int hint, int iters,
-                      int cfg_override, int ck_override, float *ms_out) {
-    if (int rc = test_dev(device_id)) return rc;
-    std::vector<float> w((size_t)Cout * Cin * K), x((size_t)B * Cin * T);
+// the bench hooks' random data: one LCG stream, the weights (scaled by 0.05) first, then x
+static void bench_fill(std::vector<float> &w, std::vector<float> &x) {
     uint32_t s = 12345u;
     auto rnd = [&]() {
         s = s * 1664525u + 1013904223u;
@@ -2975,20 +2958,29 @@ int vits_bench_conv1d(int device_id, int B, int Cin, int Cout, int T, int K, int
     };
     for (auto &v : w) v = rnd() * 0.05f;
     for (auto &v : x) v = rnd();
+}
+
+// Micro-benchmark of one conv shape on random data (kernel tuning; tools/conv_bench.py): returns the
+// average launch time in ms over `iters` back-to-back launches (HIP events on the null stream).
+int vits_bench_conv1d(int device_id, int B, int Cin, int Cout, int T, int K, int dil, int hint, int iters,
+                      int cfg_override, int ck_override, float *ms_out) {
+    if (int rc = test_dev(device_id)) return rc;
+    std::vector<float> w((size_t)Cout * Cin * K), x((size_t)B * Cin * T);
+    bench_fill(w, x);
     ConvDesc d;
     std::vector<float> arena;
-    set_tiling_override(cfg_override, ck_override);
     const int dbg = hint >> 8;  // bit0: no DMA after warm-up chunks, bit1: no epilogue, bit2: no lrelu prologue
     hint &= 3;
-    std::string e = pack_test_conv(w.data(), nullptr, Cin, Cout, K, dil, dil * (K - 1) / 2, hint, &d, &arena);
-    set_tiling_override(-1, -1);
+    TestPack o;
+    o.cfg = cfg_override;
+    o.ck = ck_override;
+    std::string e = pack_test_conv(w.data(), nullptr, Cin, Cout, K, dil, dil * (K - 1) / 2, hint, &d, &arena, o);
     if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
-    float *dA = nullptr, *dx = nullptr, *dout = nullptr;
-    TCHECK(hipMalloc((void **)&dA, arena.size() * 4));
-    TCHECK(hipMalloc((void **)&dx, x.size() * 4));
-    TCHECK(hipMalloc((void **)&dout, (size_t)B * Cout * T * 4));
-    TCHECK(hipMemcpy(dA, arena.data(), arena.size() * 4, hipMemcpyHostToDevice));
-    TCHECK(hipMemcpy(dx, x.data(), x.size() * 4, hipMemcpyHostToDevice));
+    DevBufs D;
+    float *dA = D.up(arena.data(), arena.size());
+    float *dx = D.up(x.data(), x.size());
+    float *dout = D.alloc<float>((size_t)B * Cout * T);
+    TCHECK(D.err);
     ConvArgs a = conv_args(d, dA, dA);
     a.x = dx;
     a.x_bstride = (int64_t)Cin * T;
@@ -3003,27 +2995,16 @@ int vits_bench_conv1d(int device_id, int B, int Cin, int Cout, int T, int K, int
         a.oslope2 = 0.1f;
     }
     a.slope = 0.1f;
-    hipEvent_t e0, e1;
-    hipEventCreate(&e0);
-    hipEventCreate(&e1);
-    for (int i = 0; i < 2; i++) TCHECK(launch_conv(a, d.cfg, B, nullptr));
+    auto go = [&] { return launch_conv(a, d.cfg, B, nullptr); };
+    for (int i = 0; i < 2; i++) TCHECK(go());
     TCHECK(hipDeviceSynchronize());
-    hipEventRecord(e0, nullptr);
-    for (int i = 0; i < iters; i++) TCHECK(launch_conv(a, d.cfg, B, nullptr));
-    hipEventRecord(e1, nullptr);
-    TCHECK(hipEventSynchronize(e1));
     float ms = 0.f;
-    hipEventElapsedTime(&ms, e0, e1);
+    TCHECK(time_launches(iters, go, &ms));
     if (ms_out) {
-        ms_out[0] = ms / iters;
+        ms_out[0] = ms;
         ms_out[1] = (float)d.cfg;
         ms_out[2] = (float)d.CK;
     }
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
-    hipFree(dA);
-    hipFree(dx);
-    hipFree(dout);
     return VITS_OK;
 }
 
@@ -3036,34 +3017,39 @@ int vits_test_conv_transpose1d(int device_id, const float *x, int B, int Cin, in
     return run_test_conv(d, arena, x, B, T, 0, 0.f, out, (size_t)B * Cout * T * stride, (int64_t)Cout * T * stride);
 }
 
+// the test hooks' format of a split-operand conv: two fp16 planes unless stated otherwise
+static TestPack sx_test_pack(SxPack::Planes planes = SxPack::F16X2) {
+    TestPack o;
+    o.sx.planes = planes;
+    return o;
+}
+
 // ---- the same hooks through the split-operand engine: planar host tensors are converted to the engine's
 // plane / raw layouts on the device, the result is converted back.
 static int run_test_conv_sx(const ConvDesc &d, const std::vector<float> &arena, const float *x, int B, int T, int flags,
                             float slope, float *out) {
     const int Cr = d.Cout / d.ups, To = T * d.ups;
     const size_t nx = (size_t)B * d.Cin * T, no = (size_t)B * Cr * To;
-    float *dA = nullptr, *dx = nullptr, *dres = nullptr, *draw = nullptr, *dout = nullptr;
-    uint16_t *dxp = nullptr, *dop = nullptr;
-    TCHECK(hipMalloc((void **)&dA, arena.size() * 4));
-    TCHECK(hipMalloc((void **)&dx, nx * 4 + 16));
-    TCHECK(hipMalloc((void **)&dxp, nx * 6 + 16));
-    TCHECK(hipMalloc((void **)&draw, no * 4 + 16));
-    TCHECK(hipMalloc((void **)&dop, no * 6 + 16));
-    TCHECK(hipMalloc((void **)&dout, no * 4 + 16));
-    TCHECK(hipMemcpy(dA, arena.data(), arena.size() * 4, hipMemcpyHostToDevice));
-    TCHECK(hipMemcpy(dx, x, nx * 4, hipMemcpyHostToDevice));
-    TCHECK(hipMemset(draw, 0, no * 4));
-    TCHECK(hipMemset(dop, 0, no * 6));
+    if ((flags & 4) && (d.Cin != d.Cout || d.ups != 1)) return fail(nullptr, VITS_E_ARG, "residual test needs Cin == Cout");
+    std::vector<float> xa;
     if (d.h1 && (flags & 8)) {
         // single-plane mode with an input slope: the plane holds leaky_relu(x, slope) - what the conv consumes - and the
         // residual x is recovered from it (out = conv(lrelu(x)) + x): activate on the host, then store
-        std::vector<float> xa(nx);
+        xa.resize(nx);
         for (size_t i = 0; i < nx; i++) xa[i] = x[i] >= 0.f ? x[i] : x[i] * slope;
-        TCHECK(hipMemcpy(dx, xa.data(), nx * 4, hipMemcpyHostToDevice));
+        x = xa.data();
     }
+    DevBufs D;
+    float *dA = D.up(arena.data(), arena.size());
+    float *dx = D.up(x, nx, 16);
+    uint16_t *dxp = D.alloc<uint16_t>(nx * 3, 16);
+    float *draw = D.fill<float>(no, 0, 16);
+    uint16_t *dop = D.fill<uint16_t>(no * 3, 0, 16);
+    float *dout = D.alloc<float>(no, 16);
+    float *dres = D.alloc<float>(nx, 16);  // x in the raw layout: raw-input operand and residual
+    TCHECK(D.err);
     sx_split_planes_kernel<<<dim3((T + 255) / 256, d.Cin / 8, B), 256>>>(dx, (int64_t)d.Cin * T, T, nullptr, dxp, d.Cin, T,
                                                                          d.h1 ? 2 : (d.f16 ? 1 : 0));
-    TCHECK(hipMalloc((void **)&dres, nx * 4 + 16));  // x in the raw layout: raw-input operand and residual
     sx_block_kernel<<<dim3((T + 255) / 256, d.Cin / 8, B), 256>>>(dx, (int64_t)d.Cin * T, T, nullptr, dres, d.Cin, T);
     SxArgs a = sx_args(d, dA, dA, T);  // (pack_test_* reserve a zero page at offset 0)
     a.xp = reinterpret_cast<const u32x4 *>(dxp);
@@ -3074,7 +3060,6 @@ static int run_test_conv_sx(const ConvDesc &d, const std::vector<float> &arena, 
     a.oslope = 1.f;
     a.oslope2 = (flags & 1) ? slope : 1.f;
     if (flags & 4) {  // residual: res = x (same shape only)
-        if (d.Cin != d.Cout || d.ups != 1) return fail(nullptr, VITS_E_ARG, "residual test needs Cin == Cout");
         if (d.h1) {
             a.res_pl = dxp;  // the residual is the input plane itself, un-activated on the way in
             a.res_unslope = (flags & 8) ? 1.f / slope : 1.f;
@@ -3092,9 +3077,7 @@ static int run_test_conv_sx(const ConvDesc &d, const std::vector<float> &arena, 
                                                                   d.h1 ? 2 : (d.f16 ? 1 : 0));
     TCHECK(hipGetLastError());
     TCHECK(hipDeviceSynchronize());
-    TCHECK(hipMemcpy(out, dout, no * 4, hipMemcpyDeviceToHost));
-    hipFree(dA); hipFree(dx); hipFree(dxp); hipFree(draw); hipFree(dop); hipFree(dout);
-    if (dres) hipFree(dres);
+    TCHECK(download(out, dout, no));
     return VITS_OK;
 }
 
@@ -3106,11 +3089,8 @@ int vits_test_conv1d_sx(int device_id, const float *x, int B, int Cin, int T, co
     const int prec = (flags >> 4) & 3;  // 0: bf16x6, 3: f16x3 (two fp16 planes), 2: f16 (one fp16 plane, one product)
     if (prec == 1) return fail(nullptr, VITS_E_ARG, "precision code 1 (bf16x3) was retired");
     if ((flags & 128) && !(flags & 1)) return fail(nullptr, VITS_E_ARG, "planes-only output is read back from the planes (bit 0)");
-    set_sx_f16(prec == 3);
-    set_sx_h1(prec == 2);
-    std::string e = pack_test_conv(w, bias, Cin, Cout, K, dil, pad_l, 3, &d, &arena);
-    set_sx_f16(false);
-    set_sx_h1(false);
+    const TestPack o = sx_test_pack(prec == 2 ? SxPack::F16X1 : (prec == 3 ? SxPack::F16X2 : SxPack::BF16X3));
+    std::string e = pack_test_conv(w, bias, Cin, Cout, K, dil, pad_l, 3, &d, &arena, o);
     if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
     return run_test_conv_sx(d, arena, x, B, T, flags, slope, out);
 }
@@ -3127,33 +3107,25 @@ int vits_test_conv1d_sx_planar(int device_id, const float *x, int B, int Cin, in
     if (Cin % 32 || Cout % 32 || row_split % 32 || row_split > Cout || pl_rows % 32) return fail(nullptr, VITS_E_ARG, "bad planar test shape");
     ConvDesc d;
     std::vector<float> arena;
-    set_sx_f16(true);
-    std::string e = pack_test_conv(w, bias, Cin, Cout, K, dil, dil * (K - 1) / 2, 3, &d, &arena);
-    set_sx_f16(false);
+    std::string e = pack_test_conv(w, bias, Cin, Cout, K, dil, dil * (K - 1) / 2, 3, &d, &arena, sx_test_pack());
     if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
     if (!d.s16) return fail(nullptr, VITS_E_ARG, "shape not taken by the 16x16x32 loop");
     const int srows = Cout - row_split;
     const size_t nx = (size_t)B * Cin * T, n1 = (size_t)B * (row_split ? row_split : 1) * T, n2 = (size_t)B * (srows ? srows : 1) * T;
-    float *dA = nullptr, *dx = nullptr, *d1 = nullptr, *d2 = nullptr, *dres = nullptr, *dpo = nullptr;
-    uint16_t *dxp = nullptr, *dpl = nullptr;
-    int *dlen = nullptr;
-    TCHECK(hipMalloc((void **)&dA, arena.size() * 4));
-    TCHECK(hipMalloc((void **)&dx, nx * 4 + 16));
-    TCHECK(hipMalloc((void **)&dxp, nx * 6 + 64));
-    TCHECK(hipMalloc((void **)&d1, n1 * 4 + 16));
-    TCHECK(hipMalloc((void **)&d2, n2 * 4 + 16));
-    TCHECK(hipMalloc((void **)&dres, n1 * 4 + 16));
-    TCHECK(hipMalloc((void **)&dpl, (size_t)B * 3 * (pl_rows ? pl_rows : 32) * T * 2 + 64));
-    TCHECK(hipMalloc((void **)&dpo, (size_t)B * (pl_rows ? pl_rows : 32) * T * 4 + 16));
-    TCHECK(hipMalloc((void **)&dlen, (size_t)B * 4));
+    const size_t npl = (size_t)B * (pl_rows ? pl_rows : 32) * T;
     std::vector<int> l32(B);
     for (int b = 0; b < B; b++) l32[b] = lens ? (int)lens[b] : T;
-    TCHECK(hipMemcpy(dlen, l32.data(), (size_t)B * 4, hipMemcpyHostToDevice));
-    TCHECK(hipMemcpy(dA, arena.data(), arena.size() * 4, hipMemcpyHostToDevice));
-    TCHECK(hipMemcpy(dx, x, nx * 4, hipMemcpyHostToDevice));
-    TCHECK(hipMemset(d1, 0, n1 * 4));
-    TCHECK(hipMemset(d2, 0, n2 * 4));
-    TCHECK(hipMemset(dres, 0, n1 * 4));
+    DevBufs D;
+    float *dA = D.up(arena.data(), arena.size());
+    float *dx = D.up(x, nx, 16);
+    uint16_t *dxp = D.alloc<uint16_t>(nx * 3, 64);
+    float *d1 = D.fill<float>(n1, 0, 16);
+    float *d2 = D.fill<float>(n2, 0, 16);
+    float *dres = D.fill<float>(n1, 0, 16);
+    uint16_t *dpl = D.alloc<uint16_t>(npl * 3, 64);
+    float *dpo = D.alloc<float>(npl, 16);
+    int *dlen = D.up(l32.data(), (size_t)B);
+    TCHECK(D.err);
     if (old) {
         // [B][Cout][T] -> the two planar tensors (accumulate / coupling) or the residual (rows of the first tensor)
         for (int b = 0; b < B; b++) {
@@ -3189,13 +3161,10 @@ int vits_test_conv1d_sx_planar(int device_id, const float *x, int B, int Cin, in
     TCHECK(hipGetLastError());
     TCHECK(hipDeviceSynchronize());
     for (int b = 0; b < B; b++) {
-        if (row_split)
-            TCHECK(hipMemcpy(out + (size_t)b * Cout * T, d1 + (size_t)b * row_split * T, (size_t)row_split * T * 4, hipMemcpyDeviceToHost));
-        if (srows)
-            TCHECK(hipMemcpy(out + ((size_t)b * Cout + row_split) * T, d2 + (size_t)b * srows * T, (size_t)srows * T * 4, hipMemcpyDeviceToHost));
+        if (row_split) TCHECK(download(out + (size_t)b * Cout * T, d1 + (size_t)b * row_split * T, (size_t)row_split * T));
+        if (srows) TCHECK(download(out + ((size_t)b * Cout + row_split) * T, d2 + (size_t)b * srows * T, (size_t)srows * T));
     }
-    if (pl_rows && planes_out) TCHECK(hipMemcpy(planes_out, dpo, (size_t)B * pl_rows * T * 4, hipMemcpyDeviceToHost));
-    hipFree(dA); hipFree(dx); hipFree(dxp); hipFree(d1); hipFree(d2); hipFree(dres); hipFree(dpl); hipFree(dpo); hipFree(dlen);
+    if (pl_rows && planes_out) TCHECK(download(planes_out, dpo, (size_t)B * pl_rows * T));
     return VITS_OK;
 }
 
@@ -3213,25 +3182,19 @@ int vits_test_conv1d_sx_gate(int device_id, const float *x, int B, int Cin, int 
     if (Cin % 32 || Cout % 64) return fail(nullptr, VITS_E_ARG, "bad gate test shape");
     ConvDesc d;
     std::vector<float> arena;
-    set_sx_f16(true);
-    std::string e = pack_test_conv(w, bias, Cin, Cout, K, dil, dil * (K - 1) / 2, 3, &d, &arena);
-    set_sx_f16(false);
+    std::string e = pack_test_conv(w, bias, Cin, Cout, K, dil, dil * (K - 1) / 2, 3, &d, &arena, sx_test_pack());
     if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
     if (!d.s16) return fail(nullptr, VITS_E_ARG, "shape not taken by the 16x16x32 loop");
     const int H = Cout / 2;
     const size_t nx = (size_t)B * Cin * T, no = (size_t)B * H * T;
-    float *dA = nullptr, *dx = nullptr, *dact = nullptr, *dbb = nullptr;
-    uint16_t *dxp = nullptr, *dpl = nullptr;
-    TCHECK(hipMalloc((void **)&dA, arena.size() * 4));
-    TCHECK(hipMalloc((void **)&dx, nx * 4 + 16));
-    TCHECK(hipMalloc((void **)&dxp, nx * 6 + 64));
-    TCHECK(hipMalloc((void **)&dact, no * 4 + 16));
-    TCHECK(hipMalloc((void **)&dpl, no * 6 + 64));
-    TCHECK(hipMalloc((void **)&dbb, (size_t)B * Cout * 4));
-    TCHECK(hipMemcpy(dA, arena.data(), arena.size() * 4, hipMemcpyHostToDevice));
-    TCHECK(hipMemcpy(dx, x, nx * 4, hipMemcpyHostToDevice));
-    TCHECK(hipMemcpy(dbb, bias_b, (size_t)B * Cout * 4, hipMemcpyHostToDevice));
-    TCHECK(hipMemset(dact, 0xff, no * 4));
+    DevBufs D;
+    float *dA = D.up(arena.data(), arena.size());
+    float *dx = D.up(x, nx, 16);
+    uint16_t *dxp = D.alloc<uint16_t>(nx * 3, 64);
+    float *dact = D.fill<float>(no, 0xff, 16);
+    uint16_t *dpl = D.alloc<uint16_t>(no * 3, 64);
+    float *dbb = D.up(bias_b, (size_t)B * Cout);
+    TCHECK(D.err);
     sx_split_planes_kernel<<<dim3((T + 255) / 256, Cin / 8, B), 256>>>(dx, (int64_t)Cin * T, T, nullptr, dxp, Cin, T, 1);
     SxArgs a = sx_args(d, dA, dA, T);  // (pack_test_* reserve a zero page at offset 0)
     a.xp = reinterpret_cast<const u32x4 *>(dxp);
@@ -3250,8 +3213,7 @@ int vits_test_conv1d_sx_gate(int device_id, const float *x, int B, int Cin, int 
     if (flags & 2) sx_unblock_kernel<<<dim3((T + 255) / 256, H / 8, B), 256>>>(nullptr, dpl, dact, H, T, 1);
     TCHECK(hipGetLastError());
     TCHECK(hipDeviceSynchronize());
-    TCHECK(hipMemcpy(out, dact, no * 4, hipMemcpyDeviceToHost));
-    hipFree(dA); hipFree(dx); hipFree(dxp); hipFree(dact); hipFree(dpl); hipFree(dbb);
+    TCHECK(download(out, dact, no));
     return VITS_OK;
 }
 
@@ -3262,9 +3224,7 @@ int vits_test_conv_transpose1d_sx(int device_id, const float *x, int B, int Cin,
     std::vector<float> arena;
     const bool f16 = stride < 0;  // (test hook convention: negative stride = the fp16 two-plane mode)
     if (f16) stride = -stride;
-    set_sx_f16(f16);
-    std::string e = pack_test_convT(w, bias, Cin, Cout, K, stride, &d, &arena, true);
-    set_sx_f16(false);
+    std::string e = pack_test_convT(w, bias, Cin, Cout, K, stride, &d, &arena, true, sx_test_pack(f16 ? SxPack::F16X2 : SxPack::BF16X3));
     if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
     return run_test_conv_sx(d, arena, x, B, T, 0, 0.f, out);
 }
@@ -3282,40 +3242,29 @@ int vits_test_conv_pair_sx(int device_id, const float *x, int B, int C, int T, c
     const int kern = (chain >> 1) & 3;
     const bool from_plane = (chain & 8) != 0;
     chain &= 1;
+    const bool h1 = kern == 2;
+    ConvDesc d1, d2;
+    std::vector<float> arena;
+    TestPack o = sx_test_pack(h1 ? SxPack::F16X1 : SxPack::F16X2);
+    o.sx.force16 = kern && !h1;  // (the pair16 kernel takes its 32- / 64-channel weights in the 16x16x32 layout)
+    std::string e = pack_test_conv(w1, b1, C, C, K, dil1, dil1 * (K - 1) / 2, 3, &d1, &arena, o);
+    if (e.empty()) e = pack_test_conv(w2, b2, C, C, K, dil2, dil2 * (K - 1) / 2, 3, &d2, &arena, o);
+    if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
+    const size_t n = (size_t)B * C * T;
+    DevBufs D;
     if (kern) {
-        const bool h1 = kern == 2;
-        ConvDesc d1, d2;
-        std::vector<float> arena;
-        set_sx_f16(!h1);
-        set_sx_force16(!h1);
-        set_sx_h1(h1);
-        std::string e = pack_test_conv(w1, b1, C, C, K, dil1, dil1 * (K - 1) / 2, 3, &d1, &arena);
-        if (e.empty()) e = pack_test_conv(w2, b2, C, C, K, dil2, dil2 * (K - 1) / 2, 3, &d2, &arena);
-        set_sx_f16(false);
-        set_sx_force16(false);
-        set_sx_h1(false);
-        if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
         if (!d1.s16 || !d2.s16 || d1.rawin || !sx_pair16_plan(C, h1 ? 1 : 2, d1.K, d1.dil, d2.K, d2.dil, nullptr))
             return fail(nullptr, VITS_E_ARG, "this conv pair cannot run fused on the 16x16x32 loop (C %d, kernel %d, dilation %d)", C, K, dil1);
-        const size_t n = (size_t)B * C * T;
-        float *dA = nullptr, *dx = nullptr, *dxr = nullptr, *draw = nullptr, *dout = nullptr;
-        uint16_t *dxp = nullptr, *dop = nullptr;
-        TCHECK(hipMalloc((void **)&dA, arena.size() * 4));
-        TCHECK(hipMalloc((void **)&dx, n * 4 + 16));
-        TCHECK(hipMalloc((void **)&dxr, n * 4 + 16));
-        TCHECK(hipMalloc((void **)&dxp, n * 6 + 16));
-        TCHECK(hipMalloc((void **)&dop, n * 6 + 16));
-        TCHECK(hipMalloc((void **)&draw, n * 4 + 16));
-        TCHECK(hipMalloc((void **)&dout, n * 4 + 16));
-        TCHECK(hipMemcpy(dA, arena.data(), arena.size() * 4, hipMemcpyHostToDevice));
-        TCHECK(hipMemset(draw, 0, n * 4));
-        TCHECK(hipMemset(dop, 0, n * 6));
-        {  // the input planes hold leaky_relu(x, slope)
-            std::vector<float> xa(n);
-            for (size_t i = 0; i < n; i++) xa[i] = x[i] >= 0.f ? x[i] : x[i] * slope;
-            TCHECK(hipMemcpy(dx, xa.data(), n * 4, hipMemcpyHostToDevice));
-            sx_split_planes_kernel<<<dim3((T + 255) / 256, C / 8, B), 256>>>(dx, (int64_t)C * T, T, nullptr, dxp, C, T, h1 ? 2 : 1);
-        }
+        std::vector<float> xa(n);  // the input planes hold leaky_relu(x, slope)
+        for (size_t i = 0; i < n; i++) xa[i] = x[i] >= 0.f ? x[i] : x[i] * slope;
+        float *dA = D.up(arena.data(), arena.size());
+        float *dx = D.up(xa.data(), n, 16);
+        uint16_t *dxp = D.alloc<uint16_t>(n * 3, 16);
+        uint16_t *dop = D.fill<uint16_t>(n * 3, 0, 16);
+        float *draw = D.fill<float>(n, 0, 16);
+        float *dout = D.alloc<float>(n, 16);
+        TCHECK(D.err);
+        sx_split_planes_kernel<<<dim3((T + 255) / 256, C / 8, B), 256>>>(dx, (int64_t)C * T, T, nullptr, dxp, C, T, h1 ? 2 : 1);
         SxPair16Args a{};
         a.xpl = dxp;
         a.x_bstride = (int64_t)3 * C * T;
@@ -3336,19 +3285,19 @@ int vits_test_conv_pair_sx(int device_id, const float *x, int B, int C, int T, c
         a.K2 = d2.K; a.dil2 = d2.dil; a.pad2 = d2.padL;
         a.flags = from_plane ? P16_HAS_PL : P16_HAS_RAW;
         a.div = 1.f;
-        TCHECK(launch_conv_sx_pair16(a, C, h1 ? 1 : 2, B, nullptr, chain != 0));
+        auto go = [&] { return launch_conv_sx_pair16(a, C, h1 ? 1 : 2, B, nullptr, chain != 0); };
+        TCHECK(go());
         TCHECK(hipDeviceSynchronize());
 #if P16_PROF
         {
-            unsigned long long *dprof = nullptr;
             const size_t nwg = 1 << 17;  // (>= the launch's workgroups)
-            TCHECK(hipMalloc((void **)&dprof, nwg * 64));
-            TCHECK(hipMemset(dprof, 0, nwg * 64));
+            unsigned long long *dprof = D.fill<unsigned long long>(nwg * 8);
+            TCHECK(D.err);
             a.prof = dprof;
-            TCHECK(launch_conv_sx_pair16(a, C, h1 ? 1 : 2, B, nullptr, chain != 0));
+            TCHECK(go());
             TCHECK(hipDeviceSynchronize());
             std::vector<unsigned long long> hp(nwg * 8);
-            TCHECK(hipMemcpy(hp.data(), dprof, nwg * 64, hipMemcpyDeviceToHost));
+            TCHECK(download(hp.data(), dprof, nwg * 8));
             // (a row per workgroup: phase sums over its tiles, [7] = tiles - one in the one-shot form, many in the persistent one)
             double sum[7] = {0, 0, 0, 0, 0, 0, 0};
             unsigned long long n = 0, wgs = 0;
@@ -3361,49 +3310,23 @@ int vits_test_conv_pair_sx(int device_id, const float *x, int B, int C, int T, c
             fprintf(stderr, "p16prof C %d npl %d K %d wgs %llu tiles %llu | x wait %.0f  barrier %.0f  phase1 %.0f  hand-over %.0f  phase2 %.0f  epilogue %.0f  drain %.0f (cycles per TILE)\n",
                     C, h1 ? 1 : 2, K, wgs, n, sum[0] / n, sum[1] / n, sum[2] / n, sum[3] / n, sum[4] / n, sum[5] / n, sum[6] / n);
             a.prof = nullptr;
-            hipFree(dprof);
         }
 #endif
-        if (ms_out) {
-            hipEvent_t e0, e1;
-            hipEventCreate(&e0);
-            hipEventCreate(&e1);
-            hipEventRecord(e0, nullptr);
-            for (int i = 0; i < 10; i++) TCHECK(launch_conv_sx_pair16(a, C, h1 ? 1 : 2, B, nullptr, chain != 0));
-            hipEventRecord(e1, nullptr);
-            TCHECK(hipEventSynchronize(e1));
-            float ms = 0.f;
-            hipEventElapsedTime(&ms, e0, e1);
-            *ms_out = ms / 10;
-            hipEventDestroy(e0);
-            hipEventDestroy(e1);
-        }
+        if (ms_out) TCHECK(time_launches(10, go, ms_out));
         sx_unblock_kernel<<<dim3((T + 255) / 256, C / 8, B), 256>>>(draw, from_plane ? dop : nullptr, dout, C, T, h1 ? 2 : 1);
         TCHECK(hipGetLastError());
         TCHECK(hipDeviceSynchronize());
-        TCHECK(hipMemcpy(out, dout, n * 4, hipMemcpyDeviceToHost));
-        hipFree(dA); hipFree(dx); hipFree(dxr); hipFree(dxp); hipFree(dop); hipFree(draw); hipFree(dout);
+        TCHECK(download(out, dout, n));
         return VITS_OK;
     }
-    ConvDesc d1, d2;
-    std::vector<float> arena;
-    set_sx_f16(true);
-    std::string e = pack_test_conv(w1, b1, C, C, K, dil1, dil1 * (K - 1) / 2, 3, &d1, &arena);
-    if (e.empty()) e = pack_test_conv(w2, b2, C, C, K, dil2, dil2 * (K - 1) / 2, 3, &d2, &arena);
-    set_sx_f16(false);
-    if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
     if (!d1.rawin || !d2.rawin || d1.cfg != d2.cfg || !sx_pair_supported(C, d1.cfg, d1.K, d1.dil, d2.K, d2.dil))
         return fail(nullptr, VITS_E_ARG, "this conv pair cannot run fused (C %d, kernel %d, dilation %d)", C, K, dil1);
-    const size_t n = (size_t)B * C * T;
-    float *dA = nullptr, *dx = nullptr, *dxr = nullptr, *draw = nullptr, *dout = nullptr;
-    TCHECK(hipMalloc((void **)&dA, arena.size() * 4));
-    TCHECK(hipMalloc((void **)&dx, n * 4 + 16));
-    TCHECK(hipMalloc((void **)&dxr, n * 4 + 16));
-    TCHECK(hipMalloc((void **)&draw, n * 4 + 16));
-    TCHECK(hipMalloc((void **)&dout, n * 4 + 16));
-    TCHECK(hipMemcpy(dA, arena.data(), arena.size() * 4, hipMemcpyHostToDevice));
-    TCHECK(hipMemcpy(dx, x, n * 4, hipMemcpyHostToDevice));
-    TCHECK(hipMemset(draw, 0, n * 4));
+    float *dA = D.up(arena.data(), arena.size());
+    float *dx = D.up(x, n, 16);
+    float *dxr = D.alloc<float>(n, 16);
+    float *draw = D.fill<float>(n, 0, 16);
+    float *dout = D.alloc<float>(n, 16);
+    TCHECK(D.err);
     sx_block_kernel<<<dim3((T + 255) / 256, C / 8, B), 256>>>(dx, (int64_t)C * T, T, nullptr, dxr, C, T);
     SxPairArgs a{};
     a.xr = dxr;
@@ -3421,27 +3344,14 @@ int vits_test_conv_pair_sx(int device_id, const float *x, int B, int C, int T, c
     a.K1 = d1.K; a.dil1 = d1.dil; a.pad1 = d1.padL;
     a.K2 = d2.K; a.dil2 = d2.dil; a.pad2 = d2.padL;
     a.div = 1.f;
-    TCHECK(launch_conv_sx_pair(a, d1.cfg, B, nullptr, chain != 0));
+    auto go = [&] { return launch_conv_sx_pair(a, d1.cfg, B, nullptr, chain != 0); };
+    TCHECK(go());
     TCHECK(hipDeviceSynchronize());
-    if (ms_out) {
-        hipEvent_t e0, e1;
-        hipEventCreate(&e0);
-        hipEventCreate(&e1);
-        hipEventRecord(e0, nullptr);
-        for (int i = 0; i < 10; i++) TCHECK(launch_conv_sx_pair(a, d1.cfg, B, nullptr, chain != 0));
-        hipEventRecord(e1, nullptr);
-        TCHECK(hipEventSynchronize(e1));
-        float ms = 0.f;
-        hipEventElapsedTime(&ms, e0, e1);
-        *ms_out = ms / 10;
-        hipEventDestroy(e0);
-        hipEventDestroy(e1);
-    }
+    if (ms_out) TCHECK(time_launches(10, go, ms_out));
     sx_unblock_kernel<<<dim3((T + 255) / 256, C / 8, B), 256>>>(draw, nullptr, dout, C, T, 1);
     TCHECK(hipGetLastError());
     TCHECK(hipDeviceSynchronize());
-    TCHECK(hipMemcpy(out, dout, n * 4, hipMemcpyDeviceToHost));
-    hipFree(dA); hipFree(dx); hipFree(dxr); hipFree(draw); hipFree(dout);
+    TCHECK(download(out, dout, n));
     return VITS_OK;
 }
 
@@ -3449,35 +3359,25 @@ int vits_bench_conv1d_sx(int device_id, int B, int Cin, int Cout, int T, int K, 
                          float *ms_out) {
     if (int rc = test_dev(device_id)) return rc;
     std::vector<float> w((size_t)Cout * Cin * K), x((size_t)B * Cin * T);
-    uint32_t s = 12345u;
-    auto rnd = [&]() {
-        s = s * 1664525u + 1013904223u;
-        return ((s >> 8) * (1.0f / 8388608.0f)) - 1.0f;
-    };
-    for (auto &v : w) v = rnd() * 0.05f;
-    for (auto &v : x) v = rnd();
+    bench_fill(w, x);
     ConvDesc d;
     std::vector<float> arena;
-    set_sx_f16((dbg & 128) != 0);
-    set_sx_h1((dbg & 64) != 0);  // one fp16 plane, one product (VITSMI_GEN_PRECISION=f16)
-    set_sx_shape32((dbg & (1 | 2 | 16 | 256)) != 0);  // ablation / cycle-breakdown builds exist for the 32x32x16 loop only
-    std::string e = pack_test_conv(w.data(), nullptr, Cin, Cout, K, dil, dil * (K - 1) / 2, 3, &d, &arena);
-    set_sx_f16(false);
-    set_sx_h1(false);
-    set_sx_shape32(false);
+    // bit 6: one fp16 plane, one product (VITSMI_GEN_PRECISION=f16); bit 7: two fp16 planes
+    TestPack o = sx_test_pack((dbg & 64) ? SxPack::F16X1 : ((dbg & 128) ? SxPack::F16X2 : SxPack::BF16X3));
+    o.sx.no_s16 = (dbg & (1 | 2 | 16 | 256)) != 0;  // ablation / cycle-breakdown builds exist for the 32x32x16 loop only
+    std::string e = pack_test_conv(w.data(), nullptr, Cin, Cout, K, dil, dil * (K - 1) / 2, 3, &d, &arena, o);
     if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
-    float *dA = nullptr, *dx = nullptr, *draw = nullptr, *dres = nullptr;
-    uint16_t *dxp = nullptr, *dop = nullptr;
     const size_t nx = x.size(), no = (size_t)B * Cout * T;
-    TCHECK(hipMalloc((void **)&dA, arena.size() * 4));
-    TCHECK(hipMalloc((void **)&dx, nx * 4));
-    TCHECK(hipMalloc((void **)&dxp, nx * 6));
-    TCHECK(hipMalloc((void **)&draw, no * 4));
-    TCHECK(hipMalloc((void **)&dres, no * 4));
-    TCHECK(hipMalloc((void **)&dop, no * 6));
-    TCHECK(hipMemcpy(dA, arena.data(), arena.size() * 4, hipMemcpyHostToDevice));
-    TCHECK(hipMemcpy(dx, x.data(), nx * 4, hipMemcpyHostToDevice));
-    TCHECK(hipMemset(dres, 0, no * 4));
+    DevBufs D;
+    float *dA = D.up(arena.data(), arena.size());
+    float *dx = D.up(x.data(), nx);
+    uint16_t *dxp = D.alloc<uint16_t>(nx * 3);
+    float *draw = D.alloc<float>(no);
+    float *dres = D.fill<float>(no);
+    uint16_t *dop = D.alloc<uint16_t>(no * 3);
+    // per-step cycle breakdown (128x128 tile only), returned in ms_out[3..8]
+    unsigned long long *dprof = (dbg & 16) ? D.fill<unsigned long long>(8) : nullptr;
+    TCHECK(D.err);
     sx_split_planes_kernel<<<dim3((T + 255) / 256, Cin / 8, B), 256>>>(dx, (int64_t)Cin * T, T, nullptr, dxp, Cin, T,
                                                                        d.h1 ? 2 : (d.f16 ? 1 : 0));
     SxArgs a = sx_args(d, dA, dA, T);  // (pack_test_* reserve a zero page at offset 0)
@@ -3501,39 +3401,24 @@ int vits_bench_conv1d_sx(int device_id, int B, int Cin, int Cout, int T, int K, 
         a.out_pl = nullptr;
         a.out_raw = draw;
     }
-    unsigned long long *dprof = nullptr;
-    if (dbg & 16) {  // per-step cycle breakdown (128x128 tile only), returned in ms_out[3..8]
-        TCHECK(hipMalloc((void **)&dprof, 64));
-        TCHECK(hipMemset(dprof, 0, 64));
-        a.prof = dprof;
-    }
-    hipEvent_t e0, e1;
-    hipEventCreate(&e0);
-    hipEventCreate(&e1);
-    for (int i = 0; i < 2; i++) TCHECK(launch_conv_sx(a, d.cfg, B, nullptr, d.rawin, d.h1 ? 1 : (d.f16 ? 2 : 6)));
+    a.prof = dprof;
+    auto go = [&] { return launch_conv_sx(a, d.cfg, B, nullptr, d.rawin, d.h1 ? 1 : (d.f16 ? 2 : 6)); };
+    for (int i = 0; i < 2; i++) TCHECK(go());
     TCHECK(hipDeviceSynchronize());
     if (dprof) TCHECK(hipMemset(dprof, 0, 64));
-    hipEventRecord(e0, nullptr);
-    for (int i = 0; i < iters; i++) TCHECK(launch_conv_sx(a, d.cfg, B, nullptr, d.rawin, d.h1 ? 1 : (d.f16 ? 2 : 6)));
-    hipEventRecord(e1, nullptr);
-    TCHECK(hipEventSynchronize(e1));
     float ms = 0.f;
-    hipEventElapsedTime(&ms, e0, e1);
+    TCHECK(time_launches(iters, go, &ms));
     if (ms_out) {
-        ms_out[0] = ms / iters;
+        ms_out[0] = ms;
         ms_out[1] = (float)d.cfg;
         ms_out[2] = 0.f;
         if (dprof) {
             unsigned long long hp[8];
-            TCHECK(hipMemcpy(hp, dprof, sizeof hp, hipMemcpyDeviceToHost));
+            TCHECK(download(hp, dprof, 8));
             for (int i = 0; i < 5; i++) ms_out[3 + i] = hp[5] ? (float)((double)hp[i] / (double)hp[5]) : 0.f;  // per step
             ms_out[2] = hp[7] ? (float)((double)hp[6] / (double)hp[7] * 0.1) : 0.f;  // shader clock, GHz
         }
     }
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
-    if (dprof) hipFree(dprof);
-    hipFree(dA); hipFree(dx); hipFree(dxp); hipFree(draw); hipFree(dres); hipFree(dop);
     return VITS_OK;
 }
 
@@ -3542,25 +3427,20 @@ int vits_test_attention(int device_id, const float *qkv, int B, int C, int T, in
     if (int rc = test_dev(device_id)) return rc;
     if (window > 4 || C % n_heads) return fail(nullptr, VITS_E_ARG, "bad attention test arguments");
     int dk = C / n_heads;
-    float *dq = nullptr, *dout = nullptr, *drk = nullptr, *drv = nullptr;
-    int *dlen = nullptr;
     size_t nq = (size_t)B * 3 * C * T, no = (size_t)B * C * T, nr = (size_t)(2 * window + 1) * dk;
     std::vector<int> l32(B);
     for (int b = 0; b < B; b++) l32[b] = (int)lens[b];
-    TCHECK(hipMalloc((void **)&dq, nq * 4));
-    TCHECK(hipMalloc((void **)&dout, no * 4));
-    TCHECK(hipMalloc((void **)&drk, nr * 4));
-    TCHECK(hipMalloc((void **)&drv, nr * 4));
-    TCHECK(hipMalloc((void **)&dlen, B * 4));
-    TCHECK(hipMemcpy(dq, qkv, nq * 4, hipMemcpyHostToDevice));
-    TCHECK(hipMemcpy(drk, rel_k, nr * 4, hipMemcpyHostToDevice));
-    TCHECK(hipMemcpy(drv, rel_v, nr * 4, hipMemcpyHostToDevice));
-    TCHECK(hipMemcpy(dlen, l32.data(), B * 4, hipMemcpyHostToDevice));
+    DevBufs D;
+    float *dq = D.up(qkv, nq);
+    float *dout = D.alloc<float>(no);
+    float *drk = D.up(rel_k, nr);
+    float *drv = D.up(rel_v, nr);
+    int *dlen = D.up(l32.data(), (size_t)B);
+    TCHECK(D.err);
     launch_attention(nullptr, B, T, n_heads, dk, window, dq, dout, drk, drv, dlen, C);
     TCHECK(hipGetLastError());
     TCHECK(hipDeviceSynchronize());
-    TCHECK(hipMemcpy(out, dout, no * 4, hipMemcpyDeviceToHost));
-    hipFree(dq); hipFree(dout); hipFree(drk); hipFree(drv); hipFree(dlen);
+    TCHECK(download(out, dout, no));
     return VITS_OK;
 }
 
@@ -3574,59 +3454,37 @@ int vits_test_attention16(int device_id, const float *qkv, int B, int C, int T, 
     if (window > 4 || C % n_heads || C % 8) return fail(nullptr, VITS_E_ARG, "bad attention test arguments");
     int dk = C / n_heads;
     if (kernel == 1 && !(dk % 32 == 0 && dk <= 96)) return fail(nullptr, VITS_E_ARG, "attention16 needs a head width of 32, 64 or 96");
-    float *dq = nullptr, *dout = nullptr, *drk = nullptr, *drv = nullptr;
-    uint16_t *dqp = nullptr, *dop = nullptr;
-    unsigned *dpk = nullptr;
-    int *dlen = nullptr;
     size_t nq = (size_t)B * 3 * C * T, no = (size_t)B * C * T, nr = (size_t)(2 * window + 1) * dk;
     std::vector<int> l32(B);
     for (int b = 0; b < B; b++) l32[b] = (int)lens[b];
-    TCHECK(hipMalloc((void **)&dq, nq * 4));
-    TCHECK(hipMalloc((void **)&dqp, nq * 3 * 2));
-    TCHECK(hipMalloc((void **)&dop, no * 3 * 2));
-    TCHECK(hipMalloc((void **)&dpk, kSxPeakSlots * kSxPeakStride * 4));
-    TCHECK(hipMalloc((void **)&dout, no * 4));
-    TCHECK(hipMalloc((void **)&drk, nr * 4));
-    TCHECK(hipMalloc((void **)&drv, nr * 4));
-    TCHECK(hipMalloc((void **)&dlen, B * 4));
-    TCHECK(hipMemset(dpk, 0, kSxPeakSlots * kSxPeakStride * 4));
-    TCHECK(hipMemset(dop, 0xff, no * 3 * 2));
-    TCHECK(hipMemset(dout, 0xff, no * 4));
-    TCHECK(hipMemcpy(dq, qkv, nq * 4, hipMemcpyHostToDevice));
-    TCHECK(hipMemcpy(drk, rel_k, nr * 4, hipMemcpyHostToDevice));
-    TCHECK(hipMemcpy(drv, rel_v, nr * 4, hipMemcpyHostToDevice));
-    TCHECK(hipMemcpy(dlen, l32.data(), B * 4, hipMemcpyHostToDevice));
-    sx_split_planes_kernel<<<dim3((T + 255) / 256, 3 * C / 8, B), 256>>>(dq, (int64_t)3 * C * T, T, nullptr, dqp, 3 * C, T, 1, dpk);
+    DevBufs D;
+    float *dq = D.up(qkv, nq);
+    uint16_t *dqp = D.alloc<uint16_t>(nq * 3);
+    uint16_t *dop = D.fill<uint16_t>(no * 3, 0xff);
+    unsigned *dpk = D.fill<unsigned>((size_t)kSxPeakSlots * kSxPeakStride);
+    float *dout = D.fill<float>(no, 0xff);
+    float *drk = D.up(rel_k, nr);
+    float *drv = D.up(rel_v, nr);
+    int *dlen = D.up(l32.data(), (size_t)B);
     unsigned long long *dprof = nullptr;
     const int prof_wgs = ((n_heads * B + 7) / 8) * 8 * ((T + 63) / 64);
 #if ATT16_PROF
-    TCHECK(hipMalloc((void **)&dprof, (size_t)prof_wgs * 4 * 8));
-    TCHECK(hipMemset(dprof, 0, (size_t)prof_wgs * 4 * 8));
+    dprof = D.fill<unsigned long long>((size_t)prof_wgs * 4);
 #endif
+    TCHECK(D.err);
+    sx_split_planes_kernel<<<dim3((T + 255) / 256, 3 * C / 8, B), 256>>>(dq, (int64_t)3 * C * T, T, nullptr, dqp, 3 * C, T, 1, dpk);
     auto go = [&] {
         if (kernel == 1) (void)launch_attention16(nullptr, B, T, n_heads, dk, window, dqp, dout, dop, drk, drv, dlen, C, dpk, dprof);
         else launch_attention(nullptr, B, T, n_heads, dk, window, dq, dout, drk, drv, dlen, C, dk % 8 == 0 ? dop : nullptr, dpk);
+        return hipSuccess;
     };
     go();
     TCHECK(hipGetLastError());
     TCHECK(hipDeviceSynchronize());
-    if (reps > 0 && ms_out) {
-        hipEvent_t e0, e1;
-        hipEventCreate(&e0);
-        hipEventCreate(&e1);
-        hipEventRecord(e0, nullptr);
-        for (int r = 0; r < reps; r++) go();
-        hipEventRecord(e1, nullptr);
-        TCHECK(hipEventSynchronize(e1));
-        float ms = 0.f;
-        hipEventElapsedTime(&ms, e0, e1);
-        ms_out[0] = ms / reps;
-        hipEventDestroy(e0);
-        hipEventDestroy(e1);
-    }
+    if (reps > 0 && ms_out) TCHECK(time_launches(reps, go, ms_out));
     if (dprof && kernel == 1) {  // ATT16_PROF builds: where a workgroup's time goes (shader-clock cycles, means over the launch)
         std::vector<unsigned long long> hp((size_t)prof_wgs * 4);
-        TCHECK(hipMemcpy(hp.data(), dprof, hp.size() * 8, hipMemcpyDeviceToHost));
+        TCHECK(download(hp.data(), dprof, hp.size()));
         double d[3] = {0, 0, 0};
         unsigned long long t0 = ~0ull, t1 = 0;
         int n = 0;
@@ -3639,11 +3497,9 @@ int vits_test_attention16(int device_id, const float *qkv, int B, int C, int T, 
         }
         if (n) std::fprintf(stderr, "att16 stamps B=%d T=%d: %d workgroups; cycles prologue %.0f loop %.0f epilogue %.0f; first start -> last end %llu\n",
                             B, T, n, d[0] / n, d[1] / n, d[2] / n, t1 - t0);
-        hipFree(dprof);
     }
-    TCHECK(hipMemcpy(out, dout, no * 4, hipMemcpyDeviceToHost));
-    if (out_planes) TCHECK(hipMemcpy(out_planes, dop, no * 3 * 2, hipMemcpyDeviceToHost));
-    hipFree(dq); hipFree(dqp); hipFree(dop); hipFree(dpk); hipFree(dout); hipFree(drk); hipFree(drv); hipFree(dlen);
+    TCHECK(download(out, dout, no));
+    if (out_planes) TCHECK(download(out_planes, dop, no * 3));
     return VITS_OK;
 }
 

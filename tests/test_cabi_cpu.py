@@ -654,6 +654,43 @@ def test_f16_request_on_a_voice_whose_generator_cannot_run_it_is_refused_with_th
     s.close()
 
 
+def test_a_failed_open_leaves_nothing_behind_for_the_next_one(tmp_path):
+    """What a conv is packed into depends on the file and the options of THIS open, not on what ran before it on the thread:
+    a full-size voice packs to the same bytes before and after opens that fail - one of them inside the flow's WN in-layer
+    (a bias whose dims were damaged), where the packing format used to be thread state that an exception left set (64-row
+    tiles for every later conv on the thread)."""
+    import hashlib
+    from phoonnx_amd.synth import write_voice
+    good = str(tmp_path / "medium.onnx")
+    write_voice(good, "medium", seed=1234)
+
+    def digest():
+        s = MiSession(good, host_only=True)
+        d = hashlib.sha256(np.asarray(s.arena_host()).tobytes()).hexdigest()
+        s.close()
+        return d
+
+    first = digest()
+    buf = bytearray(open(good, "rb").read())
+    name = b"flow.flows.2.enc.in_layers.1.bias"
+    i = buf.find(b"\x10\x01\x42" + bytes([len(name)]) + name)   # dims (08 80 03 = 384), data_type, name
+    assert i > 3 and bytes(buf[i - 3:i]) == b"\x08\x80\x03"
+    buf[i - 1] = 0x02                                            # 384 -> 256 values announced
+    bad = str(tmp_path / "bad_bias.onnx")
+    open(bad, "wb").write(buf)
+    with pytest.raises(SessionError, match="in_layers.1.bias"):
+        MiSession(bad, host_only=True)
+    assert digest() == first
+    cut = str(tmp_path / "cut.onnx")
+    open(cut, "wb").write(bytes(buf[:len(buf) // 2]))
+    with pytest.raises(SessionError):
+        MiSession(cut, host_only=True)
+    assert digest() == first
+    with pytest.raises(SessionError, match="precision"):
+        MiSession(good, host_only=True, gen_precision="fp8")
+    assert digest() == first
+
+
 def test_sgpr_vmem_hazard_check_on_hand_written_isa():
     """phoonnx_amd.build.sgpr_vmem_hazards (DESIGN 5.1g hazard 5): an inline-asm memory instruction whose scalar base was
     written by v_readlane / v_readfirstlane fewer than five wait states earlier is a finding (the compiler inserts the wait
