@@ -40,6 +40,7 @@
 
 #include <cstdio>
 
+#include "conv_geom.hpp"
 #include "sx_split.hip.hpp"
 
 namespace vitsmi {
@@ -576,30 +577,7 @@ __global__ __launch_bounds__(256, (MW * NW >= 4) ? 3 : 4) void conv_engine_kerne
     if (a.peak) sx_publish_peak(a.peak, (int)(blockIdx.x + blockIdx.y + blockIdx.z), pk);  // (uniform; every thread arrives)
 }
 
-// tile configs: index -> (BM, BN)
-//   0: 32x512   1: 64x256   2: 128x128   3: 64x64   4: 32x128   5: 32x64, the four waves split the reduction (KS = 4)
-inline int conv_tile_m(int cfg) { return cfg == 2 ? 128 : ((cfg == 1 || cfg == 3) ? 64 : 32); }
-inline int conv_tile_n(int cfg) {
-    switch (cfg) {
-        case 0: return 512;
-        case 1: return 256;
-        case 2: return 128;
-        case 3: return 64;
-        case 5: return 64;
-        default: return 128;
-    }
-}
-
-// largest pipeline stage (floats) a layer may use: 38 KiB (two workgroups per CU)
-inline int conv_stage_floats(int cfg) {
-    static const int cap3 = [] {
-        const char *e = std::getenv("VITSMI_STAGE_CAP_SMALL");  // tuning experiments only (model.cpp stage_capacity)
-        return e ? std::atoi(e) : 4864;
-    }();
-    if (cfg == 5) return 6144;
-    return cfg <= 2 ? 9728 : cap3;
-}
-
+// (tile configs, stage arithmetic and the stage capacity: conv_geom.hpp)
 template <int MW, int NW, int WM, int WN, int VEC, int ACT, int KS = 1>
 inline hipError_t launch_conv_k(const ConvArgs &a, dim3 grid, size_t lds, hipStream_t stream) {
     static std::atomic<uint64_t> attr_done{0};  // allow > 64 KiB of dynamic LDS, once per (instantiation, device)
@@ -617,39 +595,30 @@ inline hipError_t launch_conv_t(const ConvArgs &a, dim3 grid, bool vec4, bool ac
     return act ? launch_conv_k<MW, NW, WM, WN, 1, 1, KS>(a, grid, lds, stream) : launch_conv_k<MW, NW, WM, WN, 1, 0, KS>(a, grid, lds, stream);
 }
 
-// Launch on `stream`; LW / padLa / xs_floats / magic are filled in here.
+// Launch on `stream`; LW / padLa / xs_floats / stage_floats (conv_geom.hpp conv_stage) and magic are filled in here.
 hipError_t launch_conv(ConvArgs a, int cfg, int B, hipStream_t stream);
 #ifdef VITSMI_IMPL_CONV_F32  // (tu_conv_f32.hip: the f32 engine's instantiations are one translation unit)
 hipError_t launch_conv(ConvArgs a, int cfg, int B, hipStream_t stream) {
     const int BN = conv_tile_n(cfg), BM = conv_tile_m(cfg);
-    const int halo = (a.K - 1) * a.dil;
     // 16-byte DMA needs 16-byte aligned rows: T % 4 == 0, aligned base/batch stride, no ragged input mask
     if (a.x_cstride == 0) a.x_cstride = a.T;
     if (a.out_cstride == 0) a.out_cstride = a.T * a.ups;
     // (rows may be padded with zeros up to a pitch that is a multiple of 4: x_cstride)
     const bool vec4 = (a.x_cstride % 4 == 0) && (a.x_bstride % 4 == 0) && ((reinterpret_cast<uintptr_t>(a.x) & 15) == 0) &&
                       !(a.flags & PRO_MASK);
-    if (vec4) {
-        a.padLa = (a.padL + 3) & ~3;
-        const int padRa = (halo - a.padL + 3) & ~3;
-        a.LW = BN + a.padLa + padRa;
-        a.xs_floats = (a.CK * a.LW + 1023) / 1024 * 1024;
-    } else {
-        a.padLa = a.padL;
-        a.LW = BN + halo;
-        a.xs_floats = (a.CK * a.LW + 255) / 256 * 256;
-    }
+    const ConvStage g = conv_stage(cfg, a.K, a.dil, a.padL, a.CK, vec4);
+    a.padLa = g.padLa;
+    a.LW = g.LW;
+    a.xs_floats = g.xs_floats;
+    a.stage_floats = g.stage_floats;
     a.magic = (unsigned)((0x100000000ull + a.LW - 1) / a.LW);
     if (a.oslope == 0.f) a.oslope = 1.f;
     if (a.oslope2 == 0.f) a.oslope2 = 1.f;
     const bool act = (a.flags & PRO_LRELU) && a.slope != 1.f;
     dim3 grid((a.T + BN - 1) / BN, (a.Cout + BM - 1) / BM, B);
     if (grid.x == 0 || grid.y == 0 || B == 0) return hipSuccess;
-    const size_t stage = (size_t)a.xs_floats + (size_t)(BM / 32) * (a.K * a.CK / 8) * 256;
-    if (stage > (size_t)conv_stage_floats(cfg)) return hipErrorInvalidValue;  // pick_tiling guarantees this never fires
-    a.stage_floats = (int)((stage + 63) / 64 * 64);
-    size_t lds = 2 * (size_t)a.stage_floats * sizeof(float);
-    if (cfg == 5 && lds < (size_t)4 * 2 * 16 * 64 * 4) lds = (size_t)4 * 2 * 16 * 64 * 4;  // the four partial 32 x 64 tiles
+    if (!g.fits) return hipErrorInvalidValue;  // never fires: pack_conv (model.cpp) refuses a conv whose stage does not fit
+    const size_t lds = g.lds;
     if ((int64_t)a.Cout * (a.ups == 1 ? a.out_cstride : a.T) >= (int64_t)1 << 31) return hipErrorInvalidValue;  // 32-bit element offsets per utterance
     if ((int64_t)a.CK * a.x_cstride + a.T >= (int64_t)1 << 31) return hipErrorInvalidValue;  // ... and inside a chunk of the input
     switch (cfg) {

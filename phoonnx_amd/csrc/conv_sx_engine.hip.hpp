@@ -52,6 +52,7 @@
 #include <utility>
 
 #include "conv_engine.hip.hpp"
+#include "conv_geom.hpp"
 
 #ifndef SX_CFG0_WIDE
 #define SX_CFG0_WIDE 0  // 128 x 256 tile as four 32-row waves x 256 columns (half the weight bytes per workgroup)
@@ -450,7 +451,7 @@ __global__ __launch_bounds__(256, (MW * NW > 8) ? 1 : ((SH == 16 && MW * NW == 2
     };
     // ---- RAWIN: x tile through registers.  A thread owns cells i = it*256 + tid of the [2 channel groups][LW]
     // tile (8 fp32 = two 16-byte loads each); rows past the tile and out-of-range columns read the zero page.
-    constexpr int NXC = 3;  // cells per thread: 2 * LW <= 768 (launch_conv_sx)
+    constexpr int NXC = 3;  // cells per thread: 2 * LW <= kSxRawStageCells (conv_geom.hpp)
     u32x4 xst[NXC][2];
     const float *xrb = RAWIN ? a.xr + (int64_t)b * a.Cin * T : nullptr;
     const int nxc = (2 * LW + 255) >> 8;
@@ -1347,12 +1348,7 @@ __global__ __launch_bounds__(256, (MW * NW > 8) ? 1 : ((SH == 16 && MW * NW == 2
     }
 }
 
-// sx tile configs: index -> (BM, BN, waves WM x WN, blocks per wave MW x NW):
-//   0: 128x256 (2x2 waves of 64x128)   1: 64x256 (2x2 waves of 32x128)   2: 32x256 (1x4 waves of 32x64)
-// All are 256 columns wide: the weights of a step then serve 4 (2) block columns per register load.
-// 3: 64x128 (2x2 waves of 32x64), run-time choice for short grids of 64-row layers (same packed weights as 1)
-inline int sx_tile_m(int cfg) { return cfg == 0 ? 128 : ((cfg == 1 || cfg == 3) ? 64 : 32); }
-inline int sx_tile_n(int cfg) { return cfg == 3 ? 128 : 256; }
+// (sx tile configs, the x stage's geometry and its limits: conv_geom.hpp)
 
 template <int MW, int NW, int WM, int WN, int EPI = -1, bool PROF = false, bool RAWIN = false, int NP = 6, int SH = 32>
 inline hipError_t launch_conv_sx_k(const SxArgs &a, dim3 grid, size_t lds, hipStream_t stream) {
@@ -1439,41 +1435,26 @@ hipError_t launch_conv_sx_f16_s16p(const SxArgs &a, int cfg, int epi, dim3 grid,
 #ifdef VITSMI_IMPL_SX
 hipError_t launch_conv_sx(SxArgs a, int cfg, int B, hipStream_t stream, bool rawin, int nprod, int pack_cfg) {
     const int BM = sx_tile_m(cfg), BN = sx_tile_n(cfg);
-    a.wshift = 0;
-    if (pack_cfg >= 0 && pack_cfg != cfg) {
-        const int PM = sx_tile_m(pack_cfg);
-        if (PM < BM || PM % BM || rawin) return hipErrorInvalidValue;
-        while ((BM << a.wshift) < PM) a.wshift++;
-    }
-    a.LW = BN + (a.K - 1) * a.dil;
-    a.RS = a.LW;
-    // an x stage is padded to whole DMA rounds (256 cells = 4 KiB), so that every wave issues the same count
-    // (rows = 2 channel-group halves x the planes the mode reads: 3 bf16 planes, 2 in the fp16 / bf16x3 modes, 1 in bf16)
-    int xrows = nprod == 6 ? 6 : 4;
     const bool s16 = a.s16 != 0;
-    if (cfg == 3 && !s16) return hipErrorInvalidValue;  // (64 x 128 tiles exist for the 16x16x32 loop only)
-    if (s16) {
-        // weights packed for the 16x16x32 main loop: chunks of 32 channels (4 channel groups x 2 planes = 8 rows per stage)
-        if ((nprod != 2 && nprod != 1) || rawin || a.prof || (a.flags & (DBG_NO_DMA | DBG_NO_EPI)) || a.Cin % 32) return hipErrorInvalidValue;
-        xrows = nprod == 1 ? 4 : 8;
-        // rows 16 cells apart modulo 16: the ds_read_b128 of a B fragment (lanes 16 apart = the next channel group) is then
-        // free of bank conflicts; where that does not fit two workgroups per CU the rows stay packed (mild conflicts)
-        // (two workgroups per CU = 80 KiB each, all of it dynamic: the 16x16x32 kernels have no static LDS)
-        const int rs16 = (a.LW + 15) / 16 * 16;
-        if (((size_t)xrows * rs16 * 16 + 4095) / 4096 * 4096 + (size_t)xrows * rs16 * 16 <= (size_t)80 * 1024) a.RS = rs16;
-    } else if (nprod == 1)
-        return hipErrorInvalidValue;  // (the single-plane mode exists on the 16x16x32 loop only)
+    a.wshift = 0;
+    if (!sx_tile_reads(pack_cfg >= 0 ? pack_cfg : cfg, cfg, s16)) return hipErrorInvalidValue;
+    if (pack_cfg >= 0 && pack_cfg != cfg) {
+        if (rawin) return hipErrorInvalidValue;
+        while ((BM << a.wshift) < sx_tile_m(pack_cfg)) a.wshift++;
+    }
+    // weights packed for the 16x16x32 main loop: the plane-input fp16 modes only
+    if (s16 && ((nprod != 2 && nprod != 1) || rawin || a.prof || (a.flags & (DBG_NO_DMA | DBG_NO_EPI)) || a.Cin % 32)) return hipErrorInvalidValue;
+    // the x stage and its refusals (pack_conv_sx and sx_supported() of model.cpp ask the same function)
+    const SxStage g = sx_stage(BN, a.K, a.dil, nprod == 6 ? 3 : (nprod == 1 ? 1 : 2), s16);
+    if (!g.fits) return hipErrorInvalidValue;
+    a.LW = g.LW;
+    a.RS = g.RS;
     a.magic = (unsigned)((0x100000000ull + a.RS - 1) / a.RS);
-    a.x_bytes = (unsigned)(((size_t)xrows * a.RS * 16 + 4095) / 4096 * 4096);
-    if (s16 && (a.x_bytes > 12 * 4096 || ((long long)(2 * (a.Cin / 8) + 2) * a.T) * 16 >= (1ll << 32))) return hipErrorInvalidValue;
-    // two x stages; the weights never touch LDS.  (16x16x32: the second stage ends with its last row - the DMA rounds are
-    // whole 4 KiB but lanes past the last row are masked off - which keeps the 50-cell halo of a k = 11, dilation 5 conv
-    // inside 80 KiB)
-    const size_t lds = s16 ? (size_t)a.x_bytes + (size_t)xrows * a.RS * 16 : 2 * (size_t)a.x_bytes;
+    a.x_bytes = g.x_bytes;
+    const size_t lds = g.lds;
     a.lds_bytes = (unsigned)lds;
-    // (pack_conv_sx pads narrower kernels to 3 taps; model.cpp sx_supported() mirrors the size limits)
-    if (lds > (size_t)kSxMaxDynLds || a.x_bytes > 12 * 4096 || (a.K < 3 && !s16)) return hipErrorInvalidValue;
-    if (rawin && (cfg == 0 || 2 * a.LW > 768 || !a.xr || (long long)a.T * 64 + 64 >= (1ll << 32))) return hipErrorInvalidValue;
+    if (s16 && ((long long)(2 * (a.Cin / 8) + 2) * a.T) * 16 >= (1ll << 32)) return hipErrorInvalidValue;
+    if (rawin && (cfg == 0 || !g.raw_ok || !a.xr || (long long)a.T * 64 + 64 >= (1ll << 32))) return hipErrorInvalidValue;
     if (a.oslope == 0.f) a.oslope = 1.f;
     if (a.oslope2 == 0.f) a.oslope2 = 1.f;
     if (a.islope == 0.f) a.islope = 1.f;

@@ -30,6 +30,7 @@
 //            of the 256 - 2 P2 interior columns (P2 = c2's one-sided reach; columns nearer the tile edge saw garbage).
 #pragma once
 #include <cstdlib>
+#include "conv_geom.hpp"
 #include "conv_sx_engine.hip.hpp"
 
 namespace vitsmi {
@@ -841,7 +842,7 @@ inline bool sx_pair_supported(int C, int cfg, int K1, int dil1, int K2, int dil2
     if (K1 < 3 || K2 < 3 || dil1 < 1 || dil2 < 1) return false;
     if (!((C == 64 && cfg == 1) || (C == 32 && cfg == 2))) return false;  // one row tile holds every channel
     const int LW1 = 256 + (K1 - 1) * dil1;
-    if (2 * LW1 > 768) return false;                                      // halo <= 128 columns (C / 16 halo cells per thread; the
+    if (2 * LW1 > kSxRawStageCells) return false;                         // halo <= 128 columns (C / 16 halo cells per thread; the
                                                                           // SX_PAIR_ONE_READ*=0 staging: three cells per thread)
     const int halo2 = (K2 - 1) * dil2;
     static const int keep_min = [] {
@@ -858,7 +859,7 @@ inline bool sx_pair_supported(int C, int cfg, int K1, int dil1, int K2, int dil2
     if (C == 64 && 256 - halo2 < keep64) return false;
     const size_t lds_y = (size_t)(C / 16) * 4 * (size_t)((256 + halo2 / 2 + 7) / 8 * 8) * 16 + (size_t)(halo2 / 2) * 16;
     const size_t lds_x = (size_t)(C / 16) * 4 * LW1 * 16;                 // the whole x tile is resident
-    return (lds_y > lds_x ? lds_y : lds_x) <= 80 * 1024 - 256;            // two workgroups per CU
+    return (lds_y > lds_x ? lds_y : lds_x) <= kLdsTwoPerCu;
 }
 
 // flags: EPI_ACC (out += ...), EPI_DIV (then / div).  chain = false: out = c2(lrelu(c1(lrelu(x)))) + x;
@@ -890,7 +891,7 @@ hipError_t launch_conv_sx_pair(SxPairArgs a, int cfg, int B, hipStream_t stream,
     // Y overlays the x stages (every chunk has its own)
     const size_t lds_x = (size_t)a.nchunks * a.x_bytes, lds_y = (size_t)a.nchunks * a.y_chunk_bytes + (size_t)a.pad2 * 16;
     size_t lds = lds_x > lds_y ? lds_x : lds_y;
-    if (lds > 80 * 1024 - 256 || !sx_pair_supported(a.C, cfg, a.K1, a.dil1, a.K2, a.dil2)) return hipErrorInvalidValue;
+    if (lds > kLdsTwoPerCu || !sx_pair_supported(a.C, cfg, a.K1, a.dil1, a.K2, a.dil2)) return hipErrorInvalidValue;
     if (cfg != 1 && SX_PAIR_SHARED_A) {  // 32 channels: the shared weight ring behind the tile (3 groups x 2 steps x 2 KiB)
         a.a_ring = (unsigned)((lds + 1023) / 1024 * 1024);
         lds = a.a_ring + 3 * 4096;
@@ -942,11 +943,11 @@ inline bool sx_mrf_geom(int C, int n, const int *K1, const int *dil1, const int 
         p2 = a2 > p2 ? a2 : p2;
     }
     const int LW1 = 256 + 2 * p1;
-    if (2 * LW1 > 768) return false;       // (as sx_pair_supported: halo <= 128 columns)
+    if (2 * LW1 > kSxRawStageCells) return false;  // (as sx_pair_supported: halo <= 128 columns)
     if (256 - 2 * p2 < 160) return false;  // (as sx_pair_supported: more than 37 % of a tile recomputed)
     const int LW2 = (256 + p2 + 7) / 8 * 8;
     const size_t lds = (size_t)(C / 16) * 4 * LW1 * 16 + (size_t)(C / 16) * 4 * LW2 * 16 + (size_t)p2 * 16;
-    if (lds > 80 * 1024 - 256) return false;  // two workgroups per CU
+    if (lds > kLdsTwoPerCu) return false;
     if (g) *g = SxMrfGeom{p1, p2, LW1, LW2, lds};
     return true;
 }

@@ -25,6 +25,7 @@
 // so results differ from the two-launch form in the last bits (not bit-identical; tests: against float64 / the oracle at the
 // tolerances of the engine).
 #pragma once
+#include "conv_geom.hpp"
 #include "conv_sx_engine.hip.hpp"
 
 namespace vitsmi {
@@ -718,7 +719,7 @@ bool sx_pair16_persist_ok(int C, int npl, int BN, int K1, int dil1, int K2, int 
         return e && e[0] == '1';
     }();
     SxPair16Geom g;
-    return on && sx_pair16_geom(C, npl, BN, false, K1, dil1, K2, dil2, &g) && g.lds <= (size_t)80 * 1024 - 256;
+    return on && sx_pair16_geom(C, npl, BN, false, K1, dil1, K2, dil2, &g) && g.lds <= (size_t)kLdsTwoPerCu;
 }
 int sx_pair16_plan(int C, int npl, int K1, int dil1, int K2, int dil2, bool *ovl) {
     static const int force = [] {
@@ -742,7 +743,7 @@ int sx_pair16_plan(int C, int npl, int K1, int dil1, int K2, int dil2, bool *ovl
     }
     for (int i = 0; i < 2; i++) {
         SxPair16Geom g;
-        if (sx_pair16_geom(C, npl, pref[i], o, K1, dil1, K2, dil2, &g) && g.lds <= (size_t)80 * 1024 - 256) return pref[i];
+        if (sx_pair16_geom(C, npl, pref[i], o, K1, dil1, K2, dil2, &g) && g.lds <= (size_t)kLdsTwoPerCu) return pref[i];
     }
     return 0;
 }

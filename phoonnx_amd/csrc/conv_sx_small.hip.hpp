@@ -16,6 +16,7 @@
 // pair, per-utterance conditioning bias) and the generator's (raw cells and / or planes, residual, running sum; ups == 1).  Same argument block (SxArgs) and semantics as conv_sx_kernel; conv_sx() in
 // vitsmi.hip picks this kernel when the launch would be at most a few workgroups per CU.
 #pragma once
+#include "conv_geom.hpp"
 #include "conv_sx_engine.hip.hpp"
 
 namespace vitsmi {

@@ -7,6 +7,7 @@
 // ("/flow/flows.6/enc/in_layers.0/Conv"), which is what we key on.
 #include "model.hpp"
 #include "g2p_model.hpp"
+#include "conv_geom.hpp"
 
 #include <functional>
 #include <cctype>
@@ -526,45 +527,22 @@ struct Packer {
     int64_t put(const TRef &r) { return put(r.p, r.numel()); }
 };
 
-// ---- tile / chunk selection (mirrors conv_engine.hip.hpp; kept here so model.cpp stays HIP-free)
-// cfg: 0: 32x512, 1: 64x256, 2: 128x128 (long sequences), 3: 64x64, 4: 32x128 (short sequences), 5: 32x64 with the
-// reduction split over the workgroup's four waves (token domain)
-int tile_m(int cfg) { return cfg == 2 ? 128 : ((cfg == 1 || cfg == 3) ? 64 : 32); }
-int tile_n(int cfg) {
-    static const int n[6] = {512, 256, 128, 64, 128, 64};
-    return n[cfg];
-}
-// floats of ONE pipeline stage (x tile + A slab) in the 16-byte-DMA layout (the larger one)
-size_t stage_floats(int cfg, int K, int dil, int padL, int CK) {
-    const int BN = tile_n(cfg), BM = tile_m(cfg), halo = (K - 1) * dil;
-    const int padLa = (padL + 3) & ~3, padRa = (halo - padL + 3) & ~3;
-    const size_t LW = size_t(BN + padLa + padRa);
-    const size_t xs = (size_t(CK) * LW + 1023) / 1024 * 1024;
-    const size_t as = size_t(BM / 32) * size_t(K * CK / 8) * 256;
-    return xs + as;
-}
-size_t stage_capacity(int cfg) {  // conv_engine.hip.hpp conv_stage_floats
-    static const long cap3 = [] {
-        const char *e = std::getenv("VITSMI_STAGE_CAP_SMALL");  // tuning experiments only
-        return e ? std::atol(e) : 4864l;
-    }();
-    if (cfg == 5) return 6144;  // (its workgroups hold >= 32 KiB for the partial tiles anyway: room for 32-channel chunks)
-    return cfg <= 2 ? 9728 : size_t(cap3);
-}
-
+// ---- tile / chunk selection (tiles, stage arithmetic and capacity: conv_geom.hpp, which launch_conv reads too: a (tile,
+// chunk) chosen here is one its stage check accepts).  A stage is sized in the 16-byte-DMA layout, never the smaller of the
+// two a launch may use.
 void pick_tiling(const Packer &P, int Cin, int Cout, int K, int dil, int padL, int &cfg, int &CK) {
     const int hint = P.hint;
     if (P.cfg_override >= 0) {
         cfg = P.cfg_override;
         CK = P.ck_override > 0 ? P.ck_override : 8;
-        if (stage_floats(cfg, K, dil, padL, CK) > stage_capacity(cfg)) throw std::runtime_error("override does not fit LDS");
+        if (!conv_stage(cfg, K, dil, padL, CK, true).fits) throw std::runtime_error("override does not fit LDS");
         return;
     }
     std::vector<int> cands;
     static const bool no_splitk = std::getenv("VITSMI_NO_SPLITK") != nullptr;  // A/B timing only
     // token domain: deep reductions into few rows (the encoder's 768 -> 192, k = 3 FFN conv: 2304 products per output)
     // split the reduction over the workgroup's waves (cfg 5); wide, shallow layers keep a block per wave (measured at
-    // batch 32: 127 -> 98 us for the former, 94 -> 104 us for the 192 -> 768 conv)
+    // batch 32: 127 -> 98 us for the former, 94 -> 104 us for the conv from 192 to 768 channels)
     if (hint == 2) cands = {Cout <= 32 ? 4 : ((!no_splitk && Cin * K >= 1024) ? 5 : 3)};
     else if (hint == 1 && Cout % 128 != 0) cands = {Cout <= 32 ? 4 : 3};
     // long-sequence tiles, also the fallback when a wide kernel does not fit a small tile's LDS stage
@@ -581,8 +559,8 @@ void pick_tiling(const Packer &P, int Cin, int Cout, int K, int dil, int padL, i
         for (int c : cands)
             for (int ck : {32, 16, 8}) {
                 if (ck > cin8 && ck != 8) continue;
-                const size_t lim = (cap && c <= 2) ? cap : stage_capacity(c);
-                if (stage_floats(c, K, dil, padL, ck) <= lim) {
+                const size_t lim = (cap && c <= 2) ? cap : conv_stage_capacity(c);
+                if (conv_stage(c, K, dil, padL, ck, true).floats <= lim) {
                     cfg = c;
                     CK = ck;
                     return;
@@ -604,7 +582,7 @@ ConvDesc pack_conv(Packer &P, int Cin, int Cout, int K, int dil, int padL, WF w,
     d.padL = padL;
     pick_tiling(P, Cin, Cout, K, dil, padL, d.cfg, d.CK);
     d.nchunks = (Cin + d.CK - 1) / d.CK;
-    int bm = tile_m(d.cfg);
+    int bm = conv_tile_m(d.cfg);
     d.mblocks = (Cout + bm - 1) / bm * (bm / 32);
     int64_t per_block = int64_t(d.nchunks * K * d.CK / 8) * 64 * 4;  // float4 groups x lanes x 4
     d.w_off = P.alloc(per_block * d.mblocks);
@@ -698,8 +676,6 @@ ConvDesc pack_convT(Packer &P, const Resolver &R, const std::string &name) {
 
 // ---- split-operand (sx) packing: weights as three bf16 planes (or two scaled fp16 planes) in the A-operand lane order of
 // v_mfma_f32_32x32x16_bf16 (lane l: row l&31, k = 8*(l>>5) .. +7 = eight consecutive input channels).
-int sx_tile_m(int cfg) { return cfg == 0 ? 128 : (cfg == 1 ? 64 : 32); }
-constexpr int kSxTileN = 256;
 // min_cfg: smallest tile index the caller allows (SxPack::min_cfg)
 int sx_pick_cfg(int Cout, int min_cfg) {
     static const int env_min_cfg = [] {
@@ -727,14 +703,16 @@ ConvDesc pack_conv_sx(Packer &P, SxPack fmt, int Cin, int Cout, int K, int dil, 
         return e && std::string(e) == "32";
     }();
     const bool h1 = fmt.planes == SxPack::F16X1, f16 = fmt.planes == SxPack::F16X2;
-    if (h1 && (Cin % 32 || (size_t)4 * (256 + (Kreal - 1) * dil) * 16 > (size_t)10 * 4096))
+    const int npw = h1 ? 1 : (f16 ? 2 : 3);  // planes per 32-row block
+    // the x stage the 16x16x32 loop would use for the unpadded kernel (fp16 modes), on the widest tile
+    const SxStage g16 = sx_stage(sx_tile_n(0), Kreal, dil, h1 ? 1 : 2, true);
+    const bool two_per_cu = g16.packed_bytes() <= size_t(kSx16StageMax);  // (unrounded: stricter than the launcher's limit)
+    if (h1 && (Cin % 32 || !two_per_cu))
         throw std::runtime_error("the f16 single-plane arithmetic needs Cin % 32 == 0 and a halo of at most 384 columns");
     // (force16: the 32- / 64-channel convs of a plane-stream generator - the fused pair kernel's weights; their own x stage
     // of up to twelve DMA rounds serves the unfused fallback)
-    const bool want16 = h1 || (f16 && fmt.force16 && sx_raw_format(Cin) && Cin % 32 == 0 &&
-                               (size_t)8 * (256 + (Kreal - 1) * dil) * 16 <= (size_t)12 * 4096) ||
-                        (f16 && !sx_raw_format(Cin) && !shape32_only && !fmt.no_s16 && Cin % 32 == 0 &&
-                         (size_t)8 * (256 + (Kreal - 1) * dil) * 16 <= (size_t)10 * 4096);
+    const bool want16 = h1 || (f16 && fmt.force16 && sx_raw_format(Cin) && Cin % 32 == 0 && g16.fits) ||
+                        (f16 && !sx_raw_format(Cin) && !shape32_only && !fmt.no_s16 && Cin % 32 == 0 && two_per_cu);
     if (K < 3 && !want16) K = 3;
     auto wz = [&](int co, int ci, int tap) { return tap < Kreal ? w(co, ci, tap) : 0.f; };
     ConvDesc d;
@@ -752,13 +730,20 @@ ConvDesc pack_conv_sx(Packer &P, SxPack fmt, int Cin, int Cout, int K, int dil, 
     if (d.rawin && d.cfg == 0) d.cfg = 1;  // the raw-input path exists for the 64- and 32-row tiles only
     d.mblocks = Cout / 32;
     const int MB = sx_tile_m(d.cfg) / 32;
-    const int npw = h1 ? 1 : (f16 ? 2 : 3);                   // planes per 32-row block
     // 16x16x32 main loop (f16x3, plane input, 32-channel chunks): when the x stage of a 32-channel chunk (8 rows of
     // 256 + halo cells) fits ten DMA rounds, i.e. two workgroups per CU
     d.s16 = want16;
     if (d.s16) {
         d.CK = 32;
         d.nchunks = Cin / 32;
+    }
+    // packed implies launchable: the stage of the packed tile and of every tile conv_sx() may run this packing on instead
+    for (int run = 0; run < 4; run++) {
+        if (!sx_tile_reads(d.cfg, run, d.s16) || (d.rawin && run != d.cfg)) continue;
+        const SxStage g = sx_stage(sx_tile_n(run), K, dil, npw, d.s16);
+        if (!g.fits || (d.rawin && !g.raw_ok))
+            throw std::runtime_error("conv " + std::to_string(Cin) + " -> " + std::to_string(Cout) + ", kernel " + std::to_string(K) + ", dilation " +
+                                     std::to_string(dil) + ": the x stage does not fit sx tile " + std::to_string(run));
     }
     const int64_t kib = int64_t(d.mblocks) * (Cin / 16) * K * npw;  // 1 KiB = one (block, plane) fragment set of k = 16
     d.w_off = P.alloc(kib * 256);
@@ -1048,11 +1033,9 @@ void split2h_host(float v, uint16_t p[3]) {
 
 bool sx_supported(int Cin, int Cout_virtual, int Cr, int K, int dil) {
     if (Cin < 16 || Cin % 16 || Cout_virtual % 32 || Cr % 32 || K < 1 || dil < 1) return false;
-    // an x stage is at most 12 DMA rounds of 4 KiB (conv_sx_engine.hip.hpp launch_conv_sx)
-    const size_t LW = size_t(kSxTileN) + size_t((K < 3 ? 3 : K) - 1) * dil;
-    const size_t x_bytes = (6 * LW * 16 + 4095) / 4096 * 4096;
-    if (sx_raw_format(Cin) && 2 * LW > 768) return false;  // raw-input staging: three cells per thread
-    return x_bytes <= 12 * 4096;
+    // the largest x stage any format takes: three planes on the 32x32x16 loop (narrower kernels are padded to 3 taps)
+    const SxStage g = sx_stage(sx_tile_n(0), K < 3 ? 3 : K, dil, 3, false);
+    return g.fits && (!sx_raw_format(Cin) || g.raw_ok);
 }
 
 std::string pack_test_conv(const float *w, const float *bias, int Cin, int Cout, int K, int dil, int pad_l, int hint,

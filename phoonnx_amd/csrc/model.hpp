@@ -24,10 +24,10 @@ struct ConvDesc {
     int CK = 8, nchunks = 0;
     int mblocks = 0;      // packed 32-row blocks (padded to the tile config)
     int ups = 1;          // pixel-shuffle factor (transposed conv), real Cout = Cout/ups
-    int cfg = 0;          // tile: 0: 32x512, 1: 64x256, 2: 128x128, 3: 64x64, 4: 32x128
+    int cfg = 0;          // tile config: conv_geom.hpp conv_tile_m / conv_tile_n
     // sx = packed for the split-operand engine (conv_sx_engine.hip.hpp) instead: weights as three bf16
     // planes [m-tile][chunk of 16 ci][tap][32-row block][plane][lane][8]; cfg then indexes the sx tiles
-    // (0: 128x256, 1: 64x256, 2: 32x256) and a transposed conv's virtual rows are r-major (r*Cr + co).
+    // (conv_geom.hpp sx_tile_m / sx_tile_n) and a transposed conv's virtual rows are r-major (r*Cr + co).
     bool sx = false;
     // sx only: the input tensor is in the fp32 raw layout and is split into planes inside the kernel (tensors of
     // <= 64 channels, see sx_raw_format); such convs use the 64- or 32-row tiles

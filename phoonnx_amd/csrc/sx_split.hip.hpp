@@ -7,6 +7,8 @@
 
 #include <atomic>
 
+#include "conv_geom.hpp"
+
 namespace vitsmi {
 
 typedef float sxf32x2 __attribute__((ext_vector_type(2)));
@@ -73,8 +75,6 @@ __device__ __forceinline__ void unact4h(u32x2 w, float unslope, float (&o)[4]) {
 // already holds as much (nearly always, after the first workgroups of a launch).  A first version with one atomic
 // per WAVE on 64 adjacent words made the 10 us split kernel take 200 us: atomics on one cache line serialise in the L2.
 constexpr int kSxPeakStride = 32;  // uints between slots: one 128-byte line each
-// (sx_publish_peak's four floats are static LDS: the dynamic part a kernel may ask for is the CU's 160 KiB less that)
-constexpr int kSxMaxDynLds = 160 * 1024 - 256;
 // hipFuncAttributeMaxDynamicSharedMemorySize belongs to the (function, device) pair: a process that opens handles on several
 // GPUs must set it once per device, and the engine's launchers run on PipelinedSession's worker threads.  `done` is the
 // instantiation's own bit mask of devices (device id modulo 64; a collision only repeats the idempotent call).

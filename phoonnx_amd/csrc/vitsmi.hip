@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/vitsmi.h"
+#include "conv_geom.hpp"
 #include "conv_sx_engine.hip.hpp"
 #include "conv_sx_pair.hip.hpp"
 #include "conv_sx_pair16.hip.hpp"
