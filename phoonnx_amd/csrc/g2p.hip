@@ -20,6 +20,7 @@
 #include "../../include/g2pmi.h"
 #include "../../include/vitsmi.h"
 #include "g2p_model.hpp"
+#include "g2p_workspace.hpp"
 #include "test_dev.hip.hpp"
 
 using namespace vitsmi;
@@ -811,17 +812,9 @@ struct Run {
     hipStream_t st;
     const float *A;
     hipError_t err = hipSuccess;
-    char *ws;
-    size_t used = 0;
     const float *P(int64_t off) const { return A + off; }
     void note(hipError_t e) {
         if (err == hipSuccess && e != hipSuccess) err = e;
-    }
-    template <class Tp>
-    Tp *take(size_t n) {
-        size_t off = (used + 255) & ~size_t(255);
-        used = off + n * sizeof(Tp);
-        return reinterpret_cast<Tp *>(ws + off);
     }
 };
 
@@ -986,6 +979,17 @@ int ws_reserve(g2p_handle *h, size_t bytes) {
     return 0;
 }
 
+// Reserve what `walk` (g2p_workspace.hpp) measures dry, then run it over the workspace.  The check behind the real walk
+// cannot fire while both are one call; it turns a later mistake into an error here, before any launch.
+template <class Walk>
+int ws_carve(g2p_handle *h, Walk &&walk) {
+    if (int rc = ws_reserve(h, carved_bytes(walk))) return rc;
+    Carver cv(h->ws, h->ws_cap);
+    walk(cv);
+    if (!cv.fits()) return gfail(h, VITS_E_NOMEM, "g2p workspace: its walk carved %zu bytes of the %zu reserved", cv.used, cv.cap);
+    return 0;
+}
+
 // encoder over nseq sequences of S ids each (device, zero-padded; true lengths in d_lens, or nullptr = all S)
 // -> enc_out [d_model][nseq * S]; a padded column attends like the others and is never attended to
 void run_encoder(Run &r, const int64_t *d_ids, int S, int nseq, const int *d_lens, float *x, float *hn, float *q, float *k,
@@ -1133,20 +1137,12 @@ int g2p_run(g2p_handle *h, const int64_t *input_ids, int S, const int64_t *mask,
         if (n1 == 0) return gfail(h, VITS_E_ARG, "attention_mask masks every input position");
         S = n1;
     }
-    const int L = S > T ? S : T;
-    const size_t per = (size_t)(m.d_model > m.inner ? m.d_model : m.inner) * L * 4 + 512;
-    const size_t need = 8 * per + 2 * ((size_t)m.d_ff * L * 4 + 512) + (size_t)m.vocab * T * 8 + (size_t)(S + T) * 8 + 4096 +
-                        2 * ((size_t)m.inner * S * 4 + 512);
-    if (int rc = ws_reserve(h, need)) return rc;
+    G2PRunBufs w;
+    if (int rc = ws_carve(h, [&](Carver &cv) { w = carve_g2p_run(cv, m, S, T); })) return rc;
     Run r{h, h->stream, h->arena_dev};
-    r.ws = h->ws;
-    int64_t *d_in = r.take<int64_t>(S), *d_dec = r.take<int64_t>(T);
-    const size_t nA = (size_t)(m.d_model > m.inner ? m.d_model : m.inner) * L;
-    float *xe = r.take<float>(nA), *xd = r.take<float>(nA), *hn = r.take<float>(nA), *q = r.take<float>(nA);
-    float *k = r.take<float>(nA), *v = r.take<float>(nA), *att = r.take<float>(nA);
-    float *fa = r.take<float>((size_t)m.d_ff * L), *fb = r.take<float>((size_t)m.d_ff * L);
-    float *kc = r.take<float>((size_t)m.inner * S), *vc = r.take<float>((size_t)m.inner * S);
-    float *lg = r.take<float>((size_t)m.vocab * T), *lgt = r.take<float>((size_t)m.vocab * T);
+    int64_t *d_in = w.in, *d_dec = w.dec;
+    float *xe = w.xe, *xd = w.xd, *hn = w.hn, *q = w.q, *k = w.k, *v = w.v, *att = w.att, *fa = w.fa, *fb = w.fb;
+    float *kc = w.kc, *vc = w.vc, *lg = w.lg, *lgt = w.lgt;
     hipStream_t st = h->stream;
     r.note(hipMemcpyAsync(d_in, input_ids, (size_t)S * 8, hipMemcpyHostToDevice, st));
     r.note(hipMemcpyAsync(d_dec, dec_ids, (size_t)T * 8, hipMemcpyHostToDevice, st));
@@ -1215,44 +1211,29 @@ static int generate_impl(g2p_handle *h, const int64_t *input_ids, const int *len
     const bool wide = NB > 4;
     const int TM = max_length + 1;  // decoder positions: the start token + every generated one
     const int T = S * NB;
-    const size_t nA = (size_t)(m.d_model > m.inner ? m.d_model : m.inner) * T;
     const int nd = (int)m.dec.size();
-    const size_t need = 8 * (nA * 4 + 512) + 2 * ((size_t)m.d_ff * T * 4 + 512) +
-                        (size_t)nd * 2 * ((size_t)NB * m.inner * TM * 4 + 512) + (size_t)nd * 2 * ((size_t)m.inner * T * 4 + 512) +
-                        (size_t)(T + (size_t)NB * TM) * 8 + (size_t)NB * (m.vocab + 2 * m.d_model + 2 * m.inner + 2 * m.d_ff + 64) * 4 +
-                        (size_t)(3 + 8 * nd) * sizeof(G2PPhase) + (1 << 18) +
-                        (forced ? (size_t)NB * TM * 8 + (size_t)max_length * NB * m.vocab * 4 + 1024 : 0);
-    if (int rc = ws_reserve(h, need)) return rc;
-    Run r{h, h->stream, h->arena_dev};
-    r.ws = h->ws;
-    hipStream_t st = h->stream;
-    int64_t *d_in = r.take<int64_t>(T), *d_gen = r.take<int64_t>((size_t)NB * TM);
-    int *d_lens = r.take<int>(NB);
-    float *xe = r.take<float>(nA), *hn = r.take<float>(nA), *q = r.take<float>(nA), *k = r.take<float>(nA);
-    float *v = r.take<float>(nA), *att = r.take<float>(nA);
-    float *fa = r.take<float>((size_t)m.d_ff * T), *fb = r.take<float>((size_t)m.d_ff * T);
-    std::vector<float *> ks(nd), vs(nd), kc(nd), vc(nd);
-    for (int l = 0; l < nd; l++) {
-        ks[l] = r.take<float>((size_t)NB * m.inner * TM);  // self-attention cache [NB][inner][TM]
-        vs[l] = r.take<float>((size_t)NB * m.inner * TM);
-        kc[l] = r.take<float>((size_t)m.inner * T);        // cross-attention keys / values of the encoder output [inner][NB * S]
-        vc[l] = r.take<float>((size_t)m.inner * T);
-    }
-    float *x1 = r.take<float>((size_t)NB * m.d_model), *q1 = r.take<float>((size_t)NB * m.inner);
-    float *a1 = r.take<float>((size_t)NB * m.inner), *f1 = r.take<float>((size_t)NB * m.d_ff), *lg = r.take<float>((size_t)NB * m.vocab);
-    float *h1 = r.take<float>((size_t)NB * m.d_model), *f2 = r.take<float>((size_t)NB * m.d_ff);  // (wide step only)
-    // forced steps: the argmax lands in a scratch copy of the id table (the given inputs stay), every step's logits are kept
-    int64_t *d_arg = forced ? r.take<int64_t>((size_t)NB * TM) : d_gen;
-    float *d_steplog = forced ? r.take<float>((size_t)max_length * NB * m.vocab) : nullptr;
     // The narrow step as one persistent launch (see g2p_decode_step_kernel), opt-in: VITSMI_G2P_PERSIST=1.
+    const bool persist = !wide && g2p_persist_on();
+    G2PGenerateBufs<G2PPhase> w;
+    if (int rc = ws_carve(h, [&](Carver &cv) { w = carve_g2p_generate<G2PPhase>(cv, m, S, NB, TM, forced != nullptr, persist); })) return rc;
+    Run r{h, h->stream, h->arena_dev};
+    hipStream_t st = h->stream;
+    int64_t *d_in = w.in, *d_gen = w.gen;
+    int *d_lens = w.lens;
+    float *xe = w.xe, *hn = w.hn, *q = w.q, *k = w.k, *v = w.v, *att = w.att, *fa = w.fa, *fb = w.fb;
+    const std::vector<float *> &ks = w.ks, &vs = w.vs, &kc = w.kc, &vc = w.vc;
+    float *x1 = w.x1, *q1 = w.q1, *a1 = w.a1, *f1 = w.f1, *lg = w.lg;
+    float *h1 = w.h1, *f2 = w.f2;  // (wide step only)
+    // forced steps: the argmax lands in a scratch copy of the id table (the given inputs stay), every step's logits are kept
+    int64_t *d_arg = w.arg;
+    float *d_steplog = w.steplog;
     const float post = m.scale_out ? 1.0f / std::sqrt((float)m.d_model) : 1.0f;
     const int D = m.d_model, I = m.inner;
     const int64_t cache_bs = (int64_t)I * TM;
-    const bool persist = !wide && g2p_persist_on();
     const int nph = 3 + 8 * nd;
-    G2PPhase *d_ph = persist ? r.take<G2PPhase>(nph) : nullptr;
-    const size_t nbar = 32 * (1 + 4096 / 4);  // top counter + give-up flag, then a line per group
-    unsigned *d_bar = persist ? r.take<unsigned>(nbar) : nullptr;
+    G2PPhase *d_ph = w.ph;
+    const size_t nbar = kG2PBarrierWords;
+    unsigned *d_bar = w.bar;
     int persist_gs = 32;
     if (const char *e = std::getenv("VITSMI_G2P_PERSIST_GROUP")) persist_gs = std::atoi(e) >= 4 ? std::atoi(e) : persist_gs;
     int64_t *gave_up_host = h->tok_host + (size_t)G2P_MAX_BATCH * G2PModel::kMaxPos, *gave_up_dev = h->tok_dev + (size_t)G2P_MAX_BATCH * G2PModel::kMaxPos;

@@ -27,6 +27,7 @@
 #include "kernels.hip.hpp"
 #include "model.hpp"
 #include "test_dev.hip.hpp"
+#include "workspace.hpp"
 
 using namespace vitsmi;
 
@@ -34,9 +35,11 @@ namespace {
 
 thread_local std::string g_open_error;
 
+// One device allocation, carved anew by every run: its size comes from a dry walk of the run's plan (workspace.hpp), its
+// buffers from the same walk over a Carver on [base, base + cap).
 struct Slab {
     char *base = nullptr;
-    size_t cap = 0, used = 0;
+    size_t cap = 0;
 };
 
 // Pinned host buffer handed out by vits_run()/vits_run_vocoder() and returned by vits_free_output():
@@ -253,14 +256,17 @@ int slab_reserve(vits_handle *h, Slab &s, size_t bytes, bool slack = true) {
     return 0;
 }
 
-template <class Tp>
-Tp *slab_take(Slab &s, size_t n) {
-    size_t off = (s.used + 255) & ~size_t(255);
-    s.used = off + n * sizeof(Tp);
-    return reinterpret_cast<Tp *>(s.base + off);
+// Reserve what `walk` measures dry, then run it over the slab.  The check behind the real walk cannot fire while both are
+// one function of the same arguments; it is there so that a later mistake is an error here, before any launch, and not a
+// kernel writing past the allocation.
+template <class Walk>
+int slab_carve(vits_handle *h, Slab &s, const char *name, Walk &&walk) {
+    if (int rc = slab_reserve(h, s, carved_bytes(walk))) return rc;
+    Carver cv(s.base, s.cap);
+    walk(cv);
+    if (!cv.fits()) return fail(h, VITS_E_NOMEM, "%s workspace: its walk carved %zu bytes of the %zu reserved", name, cv.used, cv.cap);
+    return 0;
 }
-
-inline size_t al(size_t nfloats) { return ((nfloats * 4 + 255) & ~size_t(255)) + 256; }
 
 struct Ctx {
     vits_handle *h;
@@ -590,12 +596,7 @@ void launch_attention(hipStream_t st, int B, int T, int n_heads, int dk, int win
 #undef VITSMI_ATT
 }
 
-// ... on the 16-bit matrix pipe as f16x3 products (attention16.hip.hpp): head widths of 32 / 64 / 96, q | k | v given as
-// operand planes too (the q|k|v conv's planar epilogue writes them).  VITSMI_ATT16=0 keeps the fp32-MFMA kernel (A/B timing).
-bool attention16_ok(int dk, int window) {
-    static const bool off = [] { const char *e = std::getenv("VITSMI_ATT16"); return e && e[0] == '0'; }();
-    return !off && dk % 32 == 0 && dk <= 96 && window <= 4;
-}
+// ... on the 16-bit matrix pipe as f16x3 products (attention16.hip.hpp) where attention16_ok (workspace.hpp)
 template <int DKS, int NS, int QT>
 hipError_t launch_attention16_t(hipStream_t st, const Att16Args &a) {
     constexpr int lds = NS * 4 * (DKS * 2) * 1024 + 9 * DKS * 32 * 4 + 16 + 64 * QT * kAtt16RelPitch * 4;
@@ -1063,30 +1064,6 @@ void stage_mark(vits_handle *h, int idx) {
     if (h->timing) hipEventRecord(h->ev[idx], h->stream);
 }
 
-// bytes of the token-domain slab for B utterances of T tokens (run_tokens' plan)
-size_t tokens_ws_bytes(const Model &m, int B, int T) {
-    const int H = m.H, C = m.C;
-    const size_t nHT = (size_t)B * H * T;
-    const int Cdp = m.use_sdp ? m.dp_pre.Cout : m.dpp_F;
-    size_t need = 0;
-    need += al(nHT) * 4;                                   // x, attn out, embedding, spare
-    need += al((size_t)B * 3 * H * T);                     // qkv
-    need += al((size_t)B * m.FF * T);                      // ffn hidden
-    if (m.enc_sx) need += 2 * al(nHT * 3 / 2 + 64) + al((size_t)B * m.FF * T * 3 / 2 + 64);  // operand planes: x, attn out, ffn hidden
-    if (m.enc_sx && attention16_ok(m.dk, m.window)) need += al(nHT * 9 / 2 + 64);  // operand planes: q | k | v
-    need += al((size_t)B * 2 * C * T) + 2 * al((size_t)B * C * T);  // stats, m_p, logs_p
-    need += al((size_t)B * Cdp * T) * 5;                   // dp buffers
-    int pr_rows = 32;  // spline parameters per position: 3 * bins - 1 (29 for the reference's 10 bins, up to 47)
-    if (m.use_sdp)
-        for (const auto &cfd : m.cf) pr_rows = cfd.proj.Cout > pr_rows ? cfd.proj.Cout : pr_rows;
-    need += al((size_t)B * pr_rows * T) + al((size_t)B * 2 * T) * 2 + al((size_t)B * T) * 4;
-    need += al((size_t)B * (m.gin + m.dp_cond_rows + m.C0 + 16)) + (1 << 16);
-    for (auto &cd : m.flow) need += al((size_t)B * 2 * m.flow_H * cd.n_wn);
-    need += al((size_t)B * 3) + al((size_t)B * 2);         // per-utterance settings and seeds (RunRows)
-    need += al((size_t)B * T * 2);                         // forced durations (int64) or per-token rates (vits_controls)
-    return need;
-}
-
 // The synthesis settings of a run: the call's one [3] vector (noise_scale, length_scale, noise_w) for every utterance, or
 // (vits_run_*_rows) a host [B][3] row per utterance and optionally a host [B] of per-utterance noise seeds.  run_tokens
 // copies the rows and seeds into the token slab; kernels read them there (d_rows / d_seeds), or take the call's scalars
@@ -1115,51 +1092,34 @@ int run_tokens(vits_handle *h, const int64_t *d_ids, const int64_t *d_lens, int 
                const int64_t *d_sid, const float *d_noise_dp, uint64_t seed) {
     const Model &m = h->model;
     const int H = m.H, C = m.C;
-    // workspace plan (floats)
-    const size_t nHT = (size_t)B * H * T;
-    const int Cdp = m.use_sdp ? m.dp_pre.Cout : m.dpp_F;
-    const size_t need = tokens_ws_bytes(m, B, T);
-    int pr_rows = 32;  // spline parameters per position: 3 * bins - 1 (29 for the reference's 10 bins, up to 47)
-    if (m.use_sdp)
-        for (const auto &cfd : m.cf) pr_rows = cfd.proj.Cout > pr_rows ? cfd.proj.Cout : pr_rows;
-    if (int rc = slab_reserve(h, h->tok, need)) return rc;
-    Slab &s = h->tok;
-    s.used = 0;
+    TokenBufs w;
+    if (int rc = slab_carve(h, h->tok, "token", [&](Carver &cv) { w = carve_tokens(cv, m, B, T); })) return rc;
     Ctx c{h, m, h->stream, h->arena_dev, B};
     hipStream_t st = h->stream;
 
-    h->d_len = slab_take<int>(s, B);
-    h->d_ylen64 = slab_take<int64_t>(s, B);
-    h->d_cum = slab_take<int>(s, (size_t)B * T);
-    float *x = slab_take<float>(s, nHT), *att = slab_take<float>(s, nHT);
-    // the embedded ids keep their own buffer (tap "emb": the integer gather, checked bit for bit); layer 0 reads it
-    // and writes `x`, so nothing is copied
-    float *xe = slab_take<float>(s, nHT);
+    h->d_len = w.len;
+    h->d_ylen64 = w.ylen64;
+    h->d_cum = w.cum;
+    float *x = w.x, *att = w.att, *xe = w.xe, *qkv = w.qkv, *ffh = w.ffh, *stats = w.stats;
     h->d_emb = xe;
-    float *qkv = slab_take<float>(s, (size_t)B * 3 * H * T);
-    float *ffh = slab_take<float>(s, (size_t)B * m.FF * T);
-    float *stats = slab_take<float>(s, (size_t)B * 2 * C * T);
     h->d_x = x;
-    h->d_logw = slab_take<float>(s, (size_t)B * T);
-    h->d_wceil = slab_take<float>(s, (size_t)B * T + B);  // [w_ceil | y_len]: one block, read back with one copy
+    h->d_logw = w.logw;
+    h->d_wceil = w.wceil;
     h->d_ylen = reinterpret_cast<int *>(h->d_wceil + (size_t)B * T);
 
     if (rr.rows) {
-        float *d_rows = slab_take<float>(s, (size_t)B * 3);
-        HIPCHECK(h, hipMemcpyAsync(d_rows, rr.scales, sizeof(float) * 3 * B, hipMemcpyHostToDevice, st));
-        rr.d_rows = d_rows;
+        HIPCHECK(h, hipMemcpyAsync(w.rows, rr.scales, sizeof(float) * 3 * B, hipMemcpyHostToDevice, st));
+        rr.d_rows = w.rows;
     }
     if (rr.seeds) {
-        uint64_t *d_seeds = slab_take<uint64_t>(s, B);
-        HIPCHECK(h, hipMemcpyAsync(d_seeds, rr.seeds, sizeof(uint64_t) * B, hipMemcpyHostToDevice, st));
-        rr.d_seeds = d_seeds;
+        HIPCHECK(h, hipMemcpyAsync(w.seeds, rr.seeds, sizeof(uint64_t) * B, hipMemcpyHostToDevice, st));
+        rr.d_seeds = w.seeds;
     }
     if (rr.durations) {
-        int64_t *d = slab_take<int64_t>(s, (size_t)B * T);
-        HIPCHECK(h, hipMemcpyAsync(d, rr.durations, sizeof(int64_t) * B * T, hipMemcpyHostToDevice, st));
-        rr.d_durations = d;
+        HIPCHECK(h, hipMemcpyAsync(w.ctl, rr.durations, sizeof(int64_t) * B * T, hipMemcpyHostToDevice, st));
+        rr.d_durations = w.ctl;
     } else if (rr.token_rate) {
-        float *d = slab_take<float>(s, (size_t)B * T);
+        float *d = reinterpret_cast<float *>(w.ctl);
         HIPCHECK(h, hipMemcpyAsync(d, rr.token_rate, sizeof(float) * B * T, hipMemcpyHostToDevice, st));
         rr.d_token_rate = d;
     }
@@ -1181,14 +1141,8 @@ int run_tokens(vits_handle *h, const int64_t *d_ids, const int64_t *d_lens, int 
     masked_sx.len = len;
     // split-operand engine (Model::enc_sx): every conv reads fp16 operand planes and writes planar fp32 (what attention,
     // LayerNorm and the duration predictor read) or planes for the next conv
-    uint16_t *x_pl = nullptr, *att_pl = nullptr, *ff_pl = nullptr, *qkv_pl = nullptr;
-    if (m.enc_sx) {
-        x_pl = reinterpret_cast<uint16_t *>(slab_take<float>(s, nHT * 3 / 2 + 64));
-        att_pl = reinterpret_cast<uint16_t *>(slab_take<float>(s, nHT * 3 / 2 + 64));
-        ff_pl = reinterpret_cast<uint16_t *>(slab_take<float>(s, (size_t)B * m.FF * T * 3 / 2 + 64));
-        if (attention16_ok(m.dk, m.window)) qkv_pl = reinterpret_cast<uint16_t *>(slab_take<float>(s, nHT * 9 / 2 + 64));
-        split_planes(c, xe, x_pl, H, T, len);
-    }
+    uint16_t *x_pl = w.x_pl, *att_pl = w.att_pl, *ff_pl = w.ff_pl, *qkv_pl = w.qkv_pl;
+    if (m.enc_sx) split_planes(c, xe, x_pl, H, T, len);
     for (auto &L : m.enc) {
         if (m.enc_sx) {
             const bool a16 = attention16_ok(m.dk, m.window);
@@ -1251,7 +1205,7 @@ int run_tokens(vits_handle *h, const int64_t *d_ids, const int64_t *d_lens, int 
     float *dp_cond = nullptr;
     if (m.gin && !d_sid) return fail(h, VITS_E_ARG, "Missing speaker id");
     if (m.gin && !forced) {
-        dp_cond = slab_take<float>(s, (size_t)B * m.dp_cond_rows);
+        dp_cond = w.dp_cond;
         cond_matvec_kernel<<<dim3((m.dp_cond_rows + 63) / 64, B), 64, 0, st>>>(
             c.P(m.emb_g), d_sid, m.n_speakers, c.P(m.dp_cond_w), c.P(m.dp_cond_b), dp_cond, m.dp_cond_rows, m.gin);
         h->stats.total_launches++;
@@ -1268,11 +1222,7 @@ int run_tokens(vits_handle *h, const int64_t *d_ids, const int64_t *d_lens, int 
     } else if (m.use_sdp) {
         const int Cd = m.dp_pre.Cout;
         const int64_t sC = (int64_t)Cd * T;
-        float *hb = slab_take<float>(s, (size_t)B * Cd * T), *y = slab_take<float>(s, (size_t)B * Cd * T);
-        float *y2 = slab_take<float>(s, (size_t)B * Cd * T), *cond = slab_take<float>(s, (size_t)B * Cd * T);
-        float *h2 = slab_take<float>(s, (size_t)B * Cd * T);
-        float *pr = slab_take<float>(s, (size_t)B * pr_rows * T);
-        float *z = slab_take<float>(s, (size_t)B * 2 * T);
+        float *hb = w.hb, *y = w.y, *y2 = w.y2, *cond = w.cond, *h2 = w.h2, *pr = w.pr, *z = w.z;
         // h = pre(x) [+ cond(g)] ; DDSConv ; cond = proj(h)*mask (models.py:65-70)
         ConvOpt cond_bias;
         cond_bias.bias_b = dp_cond;
@@ -1322,11 +1272,11 @@ int run_tokens(vits_handle *h, const int64_t *d_ids, const int64_t *d_lens, int 
         const int Fd = m.dpp_F;
         float *xi = x;
         if (dp_cond) {  // x = x + cond(g) (models.py:153-155)
-            xi = slab_take<float>(s, nHT);
+            xi = w.xi;
             add_bias_b_kernel<<<dim3((T + 255) / 256, H, B), 256, 0, st>>>(x, xi, dp_cond, m.dp_cond_rows, H, T);
             h->stats.total_launches++;
         }
-        float *h1 = slab_take<float>(s, (size_t)B * Fd * T), *h2 = slab_take<float>(s, (size_t)B * Fd * T);
+        float *h1 = w.h1, *h2 = w.h2;
         const int64_t sF = (int64_t)Fd * T;
         conv(c, m.dpp_conv1, xi, sHT, T, h1, sF, PRO_MASK | EPI_RELU, masked);
         layernorm(c, h1, h1, m.dpp_n1_g, m.dpp_n1_b, len, Fd, T, 0);
@@ -1376,26 +1326,6 @@ int run_tokens(vits_handle *h, const int64_t *d_ids, const int64_t *d_lens, int 
     for (int b = 0; b < B; b++) F = h->h_ylen[b] > F ? h->h_ylen[b] : F;
     h->F = F;
     return 0;
-}
-
-// frame-domain layout: flow buffers + generator ping-pong regions
-size_t gen_region_floats(const Model &m, int B, int F) {
-    size_t mx = (size_t)B * (m.C0 > m.C ? m.C0 : m.C) * ((F + 3) & ~3);
-    int64_t t = F;
-    for (auto &st : m.ups) {
-        t *= st.u;
-        size_t n = (size_t)B * st.C * t;
-        mx = n > mx ? n : mx;
-    }
-    return mx;
-}
-
-constexpr int kGenRegions = 10;     // f32 engine: ten fp32 regions
-constexpr int kGenRegionsSx = 15;   // sx engine: 4 raw + 6 plane tensors (1.5 regions each) + the waveform, rounded up
-
-// bytes of generator workspace (the largest tensor decides the region size)
-size_t gen_ws_bytes(const Model &m, int B, int F) {
-    return (size_t)(m.gen_sx ? kGenRegionsSx : kGenRegions) * al(gen_region_floats(m, B, F));
 }
 
 // Ragged rendering of a padded batch (vits_handle::tails_reference == false): from here on every generator launch ends
@@ -1448,11 +1378,11 @@ void conv_post_account(vits_handle *h, Ctx &c, int B, int T) {
 }
 
 // leaky_relu(0.01), conv_post, tanh (models.py:364-366) from the fp32 raw stage output of the two split-operand walkers
-void conv_post_sx(vits_handle *h, Ctx &c, const float *x, const int *ylen, int B, int T, int F, Slab &s) {
+void conv_post_sx(vits_handle *h, Ctx &c, const float *x, const int *ylen, int B, int T, int F, float *out) {
     const Model &m = h->model;
     hipStream_t st = h->stream;
     h->S = T;
-    h->d_out = slab_take<float>(s, (size_t)B * T);
+    h->d_out = out;
     const size_t lds = (size_t)m.post_cin * (256 + m.post_k - 1) * sizeof(float);
     if (m.post_k == 7)
         post_conv_tanh_blocked_kernel<7><<<dim3((T + 255) / 256, B), 256, lds, st>>>(x, c.P(m.post_w), h->d_out, m.post_cin,
@@ -1472,14 +1402,12 @@ void conv_post_sx(vits_handle *h, Ctx &c, const float *x, const int *ylen, int B
 // multi-receptive-field sum xs (models.py:356-363; three read-modify-writes per stage) is fp32.  Everything in front of z is
 // unchanged.  Same dataflow as run_generator_sx.
 void run_generator_planes(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int z_cstride, const int *ylen, int B,
-                          int F, const float *dec_cond, Slab &s) {
+                          int F, const float *dec_cond, const GenBufs &gb) {
     const Model &m = h->model;
     hipStream_t st = h->stream;
-    const size_t R = gen_region_floats(m, B, F);
-    const size_t RP = R + R / 2 + 64;  // (plane tensors keep the three-slot batch stride of the other modes)
-    auto planes = [&]() { return reinterpret_cast<uint16_t *>(slab_take<float>(s, RP)); };
-    uint16_t *stage_in[2] = {planes(), planes()}, *y_pl = planes(), *raa[2] = {planes(), planes()}, *tmp_pl = planes();
-    float *xs_raw = slab_take<float>(s, R);
+    // (plane tensors keep the three-slot batch stride of the other modes)
+    uint16_t *const *stage_in = gb.stage_in, *y_pl = gb.y_pl, *const *raa = gb.raa, *tmp_pl = gb.tmp_pl;
+    float *xs_raw = gb.xs_raw;
     rag_begin(h, c, ylen, B, F);
     const float S = 0.1f;  // Generator.LRELU_SLOPE / ResBlock LRELU_SLOPE
     const int nst = (int)m.ups.size();
@@ -1555,7 +1483,7 @@ void run_generator_planes(vits_handle *h, Ctx &c, const float *z, int64_t z_bstr
         }
         xa = xs_pl;
     }
-    conv_post_sx(h, c, xs_raw, ylen, B, T, F, s);
+    conv_post_sx(h, c, xs_raw, ylen, B, T, F, gb.out);
 }
 
 // f16x3, plane-format stages: residual stream as operand planes only (run_generator_sx); VITSMI_F16X3_RES=raw for the fp32 one
@@ -1570,16 +1498,12 @@ bool res_planes_on() {  // (read per run: tests switch it inside one process)
 // below; tensors that feed a conv are stored as 16-bit planes (already leaky-ReLU'd by their producer), the residual stream as
 // fp32 raw cells.
 void run_generator_sx(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int z_cstride, const int *ylen, int B,
-                      int F, const float *dec_cond, Slab &s) {
+                      int F, const float *dec_cond, const GenBufs &gb) {
     const Model &m = h->model;
     hipStream_t st = h->stream;
-    const size_t R = gen_region_floats(m, B, F);
-    const size_t RP = R + R / 2 + 64;  // floats holding R elements as three 16-bit plane slots (the fp16 mode uses two)
-    auto planes = [&]() { return reinterpret_cast<uint16_t *>(slab_take<float>(s, RP)); };
-    uint16_t *stage_in[2] = {planes(), planes()}, *y_pl = planes(), *raa[2] = {planes(), planes()}, *tmp_pl = planes();
-    float *y_raw = slab_take<float>(s, R), *ra[2] = {slab_take<float>(s, R), slab_take<float>(s, R)};
-    float *xs_raw = slab_take<float>(s, R);
-    // the plane regions double as fp32 raw buffers where a stage uses the raw format (RP >= R floats)
+    uint16_t *const *stage_in = gb.stage_in, *y_pl = gb.y_pl, *const *raa = gb.raa, *tmp_pl = gb.tmp_pl;
+    float *y_raw = gb.y_raw, *const *ra = gb.ra, *xs_raw = gb.xs_raw;
+    // the plane regions double as fp32 raw buffers where a stage uses the raw format (plane_floats(R) >= R floats)
     float *tmp_raw = reinterpret_cast<float *>(tmp_pl), *xin_raw = reinterpret_cast<float *>(stage_in[0]);
     rag_begin(h, c, ylen, B, F);
     const float S = 0.1f;  // Generator.LRELU_SLOPE / ResBlock LRELU_SLOPE
@@ -1698,17 +1622,15 @@ void run_generator_sx(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride,
         // next stage input: the planes written by the final conv, or the raw x = xs / nk itself
         xa = (fr || last_stage) ? static_cast<const void *>(xs_raw) : static_cast<const void *>(xs_pl);
     }
-    conv_post_sx(h, c, xs_raw, ylen, B, T, F, s);
+    conv_post_sx(h, c, xs_raw, ylen, B, T, F, gb.out);
 }
 
 // The generator on the f32 engine: the only one for shapes the split-operand packing refuses.
 void run_generator_f32(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int z_cstride, const int *ylen, int B,
-                       int F, const float *dec_cond, Slab &s) {
+                       int F, const float *dec_cond, const GenBufs &gb) {
     const Model &m = h->model;
     hipStream_t st = h->stream;
-    const size_t R = gen_region_floats(m, B, F);
-    float *reg[kGenRegions];
-    for (int i = 0; i < kGenRegions; i++) reg[i] = slab_take<float>(s, R);
+    float *const *reg = gb.reg;
     // Every leaky_relu of the generator (models.py:354,364; modules.py:303,307,357) is applied by the
     // PRODUCER's epilogue, so no conv carries activation math in its MFMA loop (conv_engine.hip.hpp).
     // A tensor that is needed both raw (residual) and activated (next conv input) is stored twice.
@@ -1780,7 +1702,7 @@ void run_generator_f32(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride
     }
     // conv_post; tanh (models.py:364-366): the leaky_relu(0.01) of models.py:364 was applied by the last stage's epilogue
     h->S = T;
-    h->d_out = reg[9];
+    h->d_out = gb.out;  // (reg[9])
     const size_t lds = ((size_t)m.post_cin * (256 + m.post_k - 1) + (size_t)m.post_cin * m.post_k) * sizeof(float);
     post_conv_tanh_kernel<<<dim3((T + 255) / 256, B), 256, lds, st>>>(xa, c.P(m.post_w), h->d_out, m.post_cin, m.post_k,
                                                                       T, 1.0f, tail_len(h, ylen), T / F);
@@ -1790,13 +1712,13 @@ void run_generator_f32(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride
 // One utterance batch through the generator: which walker a voice takes is decided here, once (Model::gen_sx: the
 // split-operand packing took every conv; Model::gen_planes: its plane-stream form)
 int run_generator(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int z_cstride, const int *ylen, int B,
-                  int F, const float *dec_cond, Slab &s) {
+                  int F, const float *dec_cond, const GenBufs &gb) {
     const Model &m = h->model;
     h->cur_stage = 3;
     stage_mark(h, 3);
-    if (!m.gen_sx) run_generator_f32(h, c, z, z_bstride, z_cstride, ylen, B, F, dec_cond, s);
-    else if (m.gen_planes) run_generator_planes(h, c, z, z_bstride, z_cstride, ylen, B, F, dec_cond, s);
-    else run_generator_sx(h, c, z, z_bstride, z_cstride, ylen, B, F, dec_cond, s);
+    if (!m.gen_sx) run_generator_f32(h, c, z, z_bstride, z_cstride, ylen, B, F, dec_cond, gb);
+    else if (m.gen_planes) run_generator_planes(h, c, z, z_bstride, z_cstride, ylen, B, F, dec_cond, gb);
+    else run_generator_sx(h, c, z, z_bstride, z_cstride, ylen, B, F, dec_cond, gb);
     c.rag = SxRagged{nullptr, 0, 0};
     stage_mark(h, 4);
     return 0;
@@ -1816,28 +1738,28 @@ __global__ void chunk_len_kernel(const int *ylen, int *out, int B, int lo, int n
 // order wherever a column sits in a tile).  Finished chunks go to the host through two pinned buffers; the callback
 // for chunk i runs while chunk i + 1 renders.
 int render_chunks(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int z_cstride, const int *ylen, int B, int F,
-                  const float *dec_cond, Slab &s, const ChunkSink &sink) {
+                  const float *dec_cond, const FrameBufs &fb, int Fgen, const ChunkSink &sink) {
     const Model &m = h->model;
     hipStream_t st = h->stream;
     const int ov = m.gen_rf_frames, hop = m.hop;
     const int chunk = sink.chunk_frames;
-    const size_t need = (size_t)B * chunk * hop * sizeof(float);
-    if (need > h->ring_cap) {
+    const size_t ring_bytes = (size_t)B * chunk * hop * sizeof(float);
+    if (ring_bytes > h->ring_cap) {
         for (auto &r : h->ring) {
             if (r) hipHostFree(r);
             r = nullptr;
         }
         h->ring_cap = 0;
         for (auto &r : h->ring)
-            if (hipHostMalloc((void **)&r, need) != hipSuccess) return fail(h, VITS_E_NOMEM, "pinned chunk buffer (%zu bytes)", need);
-        h->ring_cap = need;
+            if (hipHostMalloc((void **)&r, ring_bytes) != hipSuccess) return fail(h, VITS_E_NOMEM, "pinned chunk buffer (%zu bytes)", ring_bytes);
+        h->ring_cap = ring_bytes;
     }
     for (auto &e : h->ring_ev)
         if (!e) hipEventCreateWithFlags(&e, hipEventDisableTiming);
     // per-chunk valid lengths, ALWAYS passed: a chunk is a window into rows whose neighbours are real data, and only a
     // length mask makes the conv engines bound their reads by the chunk instead of by the row pitch
-    int *yl = slab_take<int>(s, B);
-    const size_t mark = s.used;
+    int *yl = fb.gen.yl;
+    Carver cv(h->frm.base, h->frm.cap);
     const int *const whole_len = c.h_len;  // host copy of ylen (or nullptr)
     const int64_t total = (int64_t)F * hop;
     int64_t pend_first = 0, pend_n = 0;
@@ -1852,14 +1774,15 @@ int render_chunks(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int
     for (int f0 = 0; f0 < F && !stop; f0 += chunk, k ^= 1) {
         const int f1 = f0 + chunk < F ? f0 + chunk : F;
         const int lo = f0 - ov > 0 ? f0 - ov : 0, hi = f1 + ov < F ? f1 + ov : F, n = hi - lo;
-        s.used = mark;  // the previous chunk's workspace (its copy-out precedes this chunk on the stream)
+        cv.rewind(fb.gen_at);  // the previous chunk's workspace (its copy-out precedes this chunk on the stream)
+        const GenBufs gb = carve_generator(cv, m, B, Fgen);
         chunk_len_kernel<<<(B + 63) / 64, 64, 0, st>>>(ylen, yl, B, lo, n);
         // (host mirror of chunk_len_kernel for the ragged accounting; without frame counts every frame is valid)
         std::vector<int> hyl((size_t)B, n);
         if (ylen && whole_len)
             for (int b = 0; b < B; b++) hyl[b] = whole_len[b] - lo < 0 ? 0 : (whole_len[b] - lo > n ? n : whole_len[b] - lo);
         c.h_len = ylen && !whole_len ? nullptr : hyl.data();
-        const int rc_gen = run_generator(h, c, z + lo, z_bstride, z_cstride, yl, B, n, dec_cond, s);
+        const int rc_gen = run_generator(h, c, z + lo, z_bstride, z_cstride, yl, B, n, dec_cond, gb);
         c.h_len = whole_len;
         if (rc_gen) return rc_gen;
         if (c.err != hipSuccess) return fail(h, VITS_E_DEVICE, "kernel launch failed: %s", hipGetErrorString(c.err));
@@ -1880,17 +1803,6 @@ int render_chunks(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int
     return 0;
 }
 
-// bytes of the frame-domain slab (flow + generator) for B utterances of F frames (a multiple of 4), the generator rendering
-// Fgen frames at a time (run_frames' plan)
-size_t frames_ws_bytes(const Model &m, int B, int F, int Fgen) {
-    const size_t nCF = (size_t)B * m.C * F, nHF = (size_t)B * m.flow_H * F;
-    size_t need = al(nCF) * 3 + al(nHF) * 3 + al(nHF * 2) * 2 + al(nHF * 2) + gen_ws_bytes(m, B, Fgen) + (1 << 16);
-    for (auto &cd : m.flow) need += al((size_t)B * 2 * m.flow_H * cd.n_wn);
-    need += al((size_t)B * m.C0);
-    need += al(nCF) + al(nHF * 2);  // operand planes of a coupling's x0 and of its skip sum (pre / post on the split-operand engine)
-    return need;
-}
-
 int run_frames(vits_handle *h, int B, int T, const RunRows &rr, const int64_t *d_sid, const float *d_noise_z,
                int64_t noise_z_stride, uint64_t seed, const ChunkSink *sink = nullptr) {
     const Model &m = h->model;
@@ -1903,17 +1815,16 @@ int run_frames(vits_handle *h, int B, int T, const RunRows &rr, const int64_t *d
     // its row pitch.
     const int F = (Freal + 3) & ~3;
     h->Fpitch = F;
-    const size_t nCF = (size_t)B * C * F, nHF = (size_t)B * Hf * F;
-    // frames the generator renders at a time: everything, or one chunk with its context
-    const int Fgen = sink && sink->chunk_frames + 2 * m.gen_rf_frames < F ? sink->chunk_frames + 2 * m.gen_rf_frames : F;
-    if (int rc = slab_reserve(h, h->frm, frames_ws_bytes(m, B, F, Fgen))) return rc;
-    Slab &s = h->frm;
-    s.used = 0;
+    const size_t nCF = (size_t)B * C * F;
+    const int Fgen = gen_frames(m, F, sink ? sink->chunk_frames : 0);
+    FrameBufs fb;
+    if (int rc = slab_carve(h, h->frm, "frame", [&](Carver &cv) { fb = carve_frames(cv, m, B, F, Fgen, /*flow=*/true); })) return rc;
+    const FlowBufs &w = fb.flow;
     Ctx c{h, m, h->stream, h->arena_dev, B};
     if ((int)h->h_ylen.size() == B) c.h_len = h->h_ylen.data();
     hipStream_t st = h->stream;
     const int *len = h->d_len, *ylen = h->d_ylen;
-    float *zp = slab_take<float>(s, nCF), *z = slab_take<float>(s, nCF);
+    float *zp = w.zp, *z = w.z;
     h->d_zp = zp;
     h->d_z = z;
     h->cur_stage = 2;
@@ -1944,7 +1855,7 @@ int run_frames(vits_handle *h, int B, int T, const RunRows &rr, const int64_t *d
             nz = d_noise_z;
             nzs = noise_z_stride;
         } else if (!rr.d_seeds) {
-            float *g = slab_take<float>(s, nCF);
+            float *g = w.g;
             fill_normal_kernel<<<(unsigned)((nCF / 4 + 256) / 256), 256, 0, st>>>(g, (int64_t)nCF, seed, 2);
             h->stats.total_launches++;
             nz = g;
@@ -1967,16 +1878,14 @@ int run_frames(vits_handle *h, int B, int T, const RunRows &rr, const int64_t *d
         HIPCHECK(h, hipMemcpyAsync(z, zp, nCF * 4, hipMemcpyDeviceToDevice, st));
 
     // ---- inverse coupling flow (models.py:247-254, modules.py:447-466); Flips folded at pack time
-    float *hx = slab_take<float>(s, nHF), *skip = slab_take<float>(s, nHF), *acts = slab_take<float>(s, nHF);
-    float *a2 = slab_take<float>(s, nHF * 2), *rs = slab_take<float>(s, nHF * 2);
-    uint16_t *hx_pl = reinterpret_cast<uint16_t *>(slab_take<float>(s, nHF * 2));  // planes of hx (sx in-layers)
+    float *hx = w.hx, *skip = w.skip, *acts = w.acts, *a2 = w.a2;
+    uint16_t *hx_pl = w.hx_pl;  // planes of hx (sx in-layers)
     const int half = C / 2;
     const int64_t sCF = (int64_t)C * F, sHF = (int64_t)Hf * F;
     uint16_t *acts_pl = reinterpret_cast<uint16_t *>(a2);  // (a2 is unused where the gate writes operand planes)
     // pre / post on the split-operand engine (CouplingDesc::pre_sx): planes of x0 (written by the previous coupling's post:
     // its x1 is this one's x0; split here for the first) and of the skip sum (written by the last res_skip conv)
-    uint16_t *x0_pl = reinterpret_cast<uint16_t *>(slab_take<float>(s, nCF));
-    uint16_t *skip_pl = reinterpret_cast<uint16_t *>(slab_take<float>(s, nHF * 2));
+    uint16_t *x0_pl = w.x0_pl, *skip_pl = w.skip_pl;
     bool x0_planes_ready = false;
     ConvOpt masked;  // the convs whose flags mask by the frame counts
     masked.len = ylen;
@@ -1989,7 +1898,7 @@ int run_frames(vits_handle *h, int B, int T, const RunRows &rr, const int64_t *d
         float *gc = nullptr;
         const int gc_rows = 2 * Hf * cd.n_wn;
         if (m.gin) {
-            gc = slab_take<float>(s, (size_t)B * gc_rows);
+            gc = w.gc[ci];
             cond_matvec_kernel<<<dim3((gc_rows + 63) / 64, B), 64, 0, st>>>(c.P(m.emb_g), d_sid, m.n_speakers, c.P(cd.cond_w),
                                                                            c.P(cd.cond_b), gc, gc_rows, m.gin);
             h->stats.total_launches++;
@@ -2090,13 +1999,13 @@ int run_frames(vits_handle *h, int B, int T, const RunRows &rr, const int64_t *d
 
     float *dec_cond = nullptr;
     if (m.gin) {
-        dec_cond = slab_take<float>(s, (size_t)B * m.C0);
+        dec_cond = w.dec_cond;
         cond_matvec_kernel<<<dim3((m.C0 + 63) / 64, B), 64, 0, st>>>(c.P(m.emb_g), d_sid, m.n_speakers, c.P(m.dec_cond_w),
                                                                     c.P(m.dec_cond_b), dec_cond, m.C0, m.gin);
         h->stats.total_launches++;
     }
-    if (sink) return render_chunks(h, c, z, sCF, F, ylen, B, Freal, dec_cond, s, *sink);
-    if (int rc = run_generator(h, c, z, sCF, F, ylen, B, Freal, dec_cond, s)) return rc;
+    if (sink) return render_chunks(h, c, z, sCF, F, ylen, B, Freal, dec_cond, fb, Fgen, *sink);
+    if (int rc = run_generator(h, c, z, sCF, F, ylen, B, Freal, dec_cond, fb.gen)) return rc;
     if (c.err != hipSuccess) return fail(h, VITS_E_DEVICE, "kernel launch failed: %s", hipGetErrorString(c.err));
     return 0;
 }
@@ -2322,19 +2231,17 @@ int vits_reserve(vits_handle *h, int B, int T, int F) {
     std::lock_guard<std::mutex> lk(h->mu);
     const Model &m = h->model;
     if (B <= 0 || T < 0 || F < 0) return fail(h, VITS_E_ARG, "vits_reserve: B=%d T=%d F=%d", B, T, F);
+    const int Fp = (F + 3) & ~3;  // (the flow runs on whole groups of 4 frames)
     if (T > 0) {
-        if (int rc = slab_reserve(h, h->tok, tokens_ws_bytes(m, B, T), false)) return rc;
-        // the staging slab: ids | lens | sid, and injected noises where a caller passes them (vits_noise)
-        // ... or, between runs, vits_last_pcm16's int16 waveform and per-utterance peaks (the larger of the two uses)
-        const size_t io_in = (size_t)B * T * 8 + (size_t)B * 16 + (size_t)B * 2 * T * 4 + (size_t)B * m.C * (size_t)((F + 3) & ~3) * 4 + 4096;
-        const size_t io_pcm = (((size_t)B * F * m.hop * 2 + 255) & ~size_t(255)) + (size_t)B * 4 + 256;
-        const size_t io = io_in > io_pcm ? io_in : io_pcm;
-        if (int rc = slab_reserve(h, h->io, io, false)) return rc;
+        if (int rc = slab_reserve(h, h->tok, carved_bytes([&](Carver &cv) { carve_tokens(cv, m, B, T); }), false)) return rc;
+        // the staging slab: the inputs of a call, injected noises included (vits_noise) ... or, between runs,
+        // vits_last_pcm16's int16 waveform and per-utterance peaks (the larger of the two uses)
+        const size_t io_in = carved_bytes([&](Carver &cv) { carve_inputs(cv, m, B, T, T, Fp); });
+        const size_t io_pcm = carved_bytes([&](Carver &cv) { carve_pcm16(cv, B, F * m.hop); });
+        if (int rc = slab_reserve(h, h->io, io_in > io_pcm ? io_in : io_pcm, false)) return rc;
     }
-    if (F > 0) {
-        const int Fp = (F + 3) & ~3;
-        if (int rc = slab_reserve(h, h->frm, frames_ws_bytes(m, B, Fp, Fp), false)) return rc;
-    }
+    if (F > 0)
+        if (int rc = slab_reserve(h, h->frm, carved_bytes([&](Carver &cv) { carve_frames(cv, m, B, Fp, Fp, /*flow=*/true); }), false)) return rc;
     return VITS_OK;
 }
 
@@ -2499,16 +2406,15 @@ static int stage_inputs(vits_handle *h, const int64_t *ids, const int64_t *lens,
             return fail(h, VITS_E_ARG, "sid[%d]=%lld is out of range [0,%d)", b, (long long)sid[b], m.n_speakers);
     }
     if (m.gin && !sid) return fail(h, VITS_E_ARG, "Missing speaker id");
-    size_t nb = (size_t)B * T * 8 + (size_t)B * 16 + 1024;
-    size_t ndp = noise && noise->noise_dp ? (size_t)B * 2 * T * 4 : 0;
-    size_t nz = noise && noise->noise_z ? (size_t)B * m.C * (size_t)noise->noise_z_stride * 4 : 0;
-    if (int rc0 = slab_reserve(h, h->io, nb + ndp + nz + 1024)) return rc0;
-    char *stage = h->io.base;
-    sg.d_ids = (int64_t *)stage;
-    sg.d_lens = sg.d_ids + (size_t)B * T;
-    int64_t *d_sid = sg.d_lens + B;
-    float *d_ndp = (float *)(stage + ((nb + 255) & ~size_t(255)));
-    float *d_nz = (float *)((char *)d_ndp + ((ndp + 255) & ~size_t(255)));
+    const int64_t Fz = noise && noise->noise_z ? noise->noise_z_stride : 0;
+    const int Tdp = noise && noise->noise_dp ? T : 0;
+    const size_t ndp = (size_t)B * 2 * Tdp * 4, nz = (size_t)B * m.C * Fz * 4;
+    InputBufs in;
+    if (int rc0 = slab_carve(h, h->io, "staging", [&](Carver &cv) { in = carve_inputs(cv, m, B, T, Tdp, Fz); })) return rc0;
+    sg.d_ids = in.ids;
+    sg.d_lens = in.lens;
+    int64_t *d_sid = in.sid;
+    float *d_ndp = in.noise_dp, *d_nz = in.noise_z;
     hipStream_t st = h->stream;
     int rc = VITS_OK;
     auto cp = [&](void *d, const void *s, size_t n) {
@@ -2688,10 +2594,10 @@ int vits_last_pcm16(vits_handle *h, int normalize, float volume, int16_t *out, s
     const size_t n = (size_t)B * S;
     if (!out || out_elems < n) return fail(h, VITS_E_ARG, "pcm16 buffer too small: %zu < %zu", out_elems, n);
     // the staging slab is idle between runs (vits_run has consumed its inputs before it returns)
-    const size_t pcm_bytes = (n * 2 + 255) & ~size_t(255);
-    if (int rc = slab_reserve(h, h->io, pcm_bytes + (size_t)B * 4 + 256)) return rc;
-    int16_t *d_pcm = (int16_t *)h->io.base;
-    unsigned *d_peak = (unsigned *)(h->io.base + pcm_bytes);
+    PcmBufs pb;
+    if (int rc = slab_carve(h, h->io, "staging", [&](Carver &cv) { pb = carve_pcm16(cv, B, S); })) return rc;
+    int16_t *d_pcm = pb.pcm;
+    unsigned *d_peak = pb.peak;
     hipStream_t st = h->stream;
     hipError_t e = hipMemsetAsync(d_peak, 0, (size_t)B * 4, st);
     const int hop = h->model.hop;
@@ -2725,21 +2631,19 @@ static int vocoder_common(vits_handle *h, const float *z, int B, int F, const in
     g_launch_name_on = h->timing == 1;
     h->range_failed = false;
     const size_t nCF = (size_t)B * m.C * F;
-    const int Fgen = sink && sink->chunk_frames + 2 * m.gen_rf_frames < F ? sink->chunk_frames + 2 * m.gen_rf_frames : F;
-    size_t need = al(nCF) + gen_ws_bytes(m, B, Fgen) + al((size_t)B * m.C0) + (1 << 16);
-    if (int rc = slab_reserve(h, h->frm, need)) return rc;
-    Slab &s = h->frm;
-    s.used = 0;
+    const int Fgen = gen_frames(m, F, sink ? sink->chunk_frames : 0);
+    FrameBufs fb;
+    if (int rc = slab_carve(h, h->frm, "frame", [&](Carver &cv) { fb = carve_frames(cv, m, B, F, Fgen, /*flow=*/false); })) return rc;
     hipStream_t st = h->stream;
-    float *dz = slab_take<float>(s, nCF);
+    float *dz = fb.voc.z;
     HIPCHECK(h, hipMemcpyAsync(dz, z, nCF * 4, hipMemcpyHostToDevice, st));
     Ctx c{h, m, st, h->arena_dev, B};
     float *dec_cond = nullptr;
     int64_t *d_sid = nullptr;
     if (m.gin) {
-        d_sid = slab_take<int64_t>(s, B);
+        d_sid = fb.voc.sid;
         HIPCHECK(h, hipMemcpyAsync(d_sid, sid, (size_t)B * 8, hipMemcpyHostToDevice, st));
-        dec_cond = slab_take<float>(s, (size_t)B * m.C0);
+        dec_cond = fb.voc.dec_cond;
         cond_matvec_kernel<<<dim3((m.C0 + 63) / 64, B), 64, 0, st>>>(c.P(m.emb_g), d_sid, m.n_speakers, c.P(m.dec_cond_w),
                                                                     c.P(m.dec_cond_b), dec_cond, m.C0, m.gin);
     }
@@ -2749,8 +2653,8 @@ static int vocoder_common(vits_handle *h, const float *z, int B, int F, const in
     h->h_dur_B = h->h_dur_T = 0;  // (no tokens: vits_last_durations has nothing to report)
     range_begin(h);
     int rc;
-    if (sink) rc = render_chunks(h, c, dz, (int64_t)m.C * F, F, nullptr, B, F, dec_cond, s, *sink);
-    else rc = run_generator(h, c, dz, (int64_t)m.C * F, F, nullptr, B, F, dec_cond, s);
+    if (sink) rc = render_chunks(h, c, dz, (int64_t)m.C * F, F, nullptr, B, F, dec_cond, fb, Fgen, *sink);
+    else rc = run_generator(h, c, dz, (int64_t)m.C * F, F, nullptr, B, F, dec_cond, fb.gen);
     if (rc) return rc;
     if (c.err != hipSuccess) return fail(h, VITS_E_DEVICE, "kernel launch failed: %s", hipGetErrorString(c.err));
     range_end(h);

@@ -1,0 +1,239 @@
+// workspace.hpp — the device workspaces of a VITS run, each stated once as the walk that carves it (slab.hpp).
+// Host-side C++17: model.hpp and the carver only, so the plans can be exercised without a device.
+//
+// A walk takes the model and the sizes of a request - never an option of one call: vits_reserve(B, T, F) sizes the slabs
+// by the same walks and must cover whatever call comes later, so a buffer only some calls use (per-utterance settings,
+// seeds, forced durations, the prior noise, the chunk lengths) is carved for all of them.  Branches follow the model.
+// Every walk's size is non-decreasing in each of its sizes: a reservation for the largest request covers the smaller ones.
+#pragma once
+#include <cstdint>
+#include <cstdlib>
+#include <vector>
+
+#include "model.hpp"
+#include "slab.hpp"
+
+namespace vitsmi {
+
+// attention on the 16-bit matrix pipe as f16x3 products (attention16.hip.hpp): head widths of 32 / 64 / 96, q | k | v given as
+// operand planes too (the q|k|v conv's planar epilogue writes them).  VITSMI_ATT16=0 keeps the fp32-MFMA kernel (A/B timing).
+inline bool attention16_ok(int dk, int window) {
+    static const bool off = [] { const char *e = std::getenv("VITSMI_ATT16"); return e && e[0] == '0'; }();
+    return !off && dk % 32 == 0 && dk <= 96 && window <= 4;
+}
+
+// operand planes are 16-bit cells carved in floats: n fp32 elements as three plane slots + the whole-cell pad
+constexpr size_t kPlanePad = 64;
+inline size_t plane_floats(size_t n) { return n + n / 2 + kPlanePad; }
+inline uint16_t *take_planes(Carver &cv, size_t nfloats) { return reinterpret_cast<uint16_t *>(cv.take<float>(nfloats)); }
+
+// ---- token domain (vits_handle::tok): encoder + duration predictor + durations, B utterances of T tokens
+struct TokenBufs {
+    int *len, *cum;
+    int64_t *ylen64;
+    float *x, *att, *xe, *qkv, *ffh, *stats, *logw;
+    float *wceil;     // [w_ceil B*T | y_len B]: one block, read back with one copy
+    float *rows;      // per-utterance settings [B][3]
+    uint64_t *seeds;  // per-utterance noise seeds [B]
+    int64_t *ctl;     // forced durations (int64 [B][T]) or, in the same buffer, per-token rates (float [B][T])
+    uint16_t *x_pl, *att_pl, *ff_pl, *qkv_pl;  // Model::enc_sx: operand planes of x, attn out, ffn hidden and q | k | v
+    float *dp_cond;                            // Model::gin
+    int pr_rows;  // spline parameters per position: 3 * bins - 1 (29 for the reference's 10 bins, up to 47)
+    float *hb, *y, *y2, *cond, *h2, *pr, *z;   // stochastic duration predictor (h2: also the plain one's)
+    float *xi, *h1;                            // plain duration predictor (xi: x + cond(g), Model::gin)
+};
+
+inline TokenBufs carve_tokens(Carver &cv, const Model &m, int B, int T) {
+    TokenBufs t{};
+    const size_t nBT = (size_t)B * T, nHT = nBT * m.H;
+    t.len = cv.take<int>(B);
+    t.ylen64 = cv.take<int64_t>(B);
+    t.cum = cv.take<int>(nBT);
+    t.x = cv.take<float>(nHT);
+    t.att = cv.take<float>(nHT);
+    t.xe = cv.take<float>(nHT);  // the embedded ids keep their own buffer (tap "emb"); layer 0 reads it and writes x
+    t.qkv = cv.take<float>(3 * nHT);
+    t.ffh = cv.take<float>(nBT * m.FF);
+    t.stats = cv.take<float>(nBT * 2 * m.C);
+    t.logw = cv.take<float>(nBT);
+    t.wceil = cv.take<float>(nBT + B);
+    t.rows = cv.take<float>((size_t)B * 3);
+    t.seeds = cv.take<uint64_t>(B);
+    t.ctl = cv.take<int64_t>(nBT);
+    if (m.enc_sx) {
+        t.x_pl = take_planes(cv, plane_floats(nHT));
+        t.att_pl = take_planes(cv, plane_floats(nHT));
+        t.ff_pl = take_planes(cv, plane_floats(nBT * m.FF));
+        if (attention16_ok(m.dk, m.window)) t.qkv_pl = take_planes(cv, nHT * 9 / 2 + kPlanePad);
+    }
+    if (m.gin) t.dp_cond = cv.take<float>((size_t)B * m.dp_cond_rows);
+    if (m.use_sdp) {
+        const size_t n = nBT * m.dp_pre.Cout;
+        t.pr_rows = 32;
+        for (const auto &cf : m.cf) t.pr_rows = cf.proj.Cout > t.pr_rows ? cf.proj.Cout : t.pr_rows;
+        t.hb = cv.take<float>(n);
+        t.y = cv.take<float>(n);
+        t.y2 = cv.take<float>(n);
+        t.cond = cv.take<float>(n);
+        t.h2 = cv.take<float>(n);
+        t.pr = cv.take<float>(nBT * t.pr_rows);
+        t.z = cv.take<float>(nBT * 2);
+    } else {
+        if (m.gin) t.xi = cv.take<float>(nHT);
+        t.h1 = cv.take<float>(nBT * m.dpp_F);
+        t.h2 = cv.take<float>(nBT * m.dpp_F);
+    }
+    return t;
+}
+
+// ---- frame domain (vits_handle::frm): [flow | vocoder input] then the generator
+
+// the inverse coupling flow over B utterances of F frames (F a multiple of 4)
+struct FlowBufs {
+    float *zp, *z;
+    float *g;  // the prior noise of a run that draws it from the flat stream
+    float *hx, *skip, *acts, *a2;
+    uint16_t *hx_pl, *x0_pl, *skip_pl;  // planes of hx (sx in-layers), of a coupling's x0 and of its skip sum (sx pre / post)
+    std::vector<float *> gc;            // Model::gin: a coupling's speaker conditioning [B][2 * flow_H * n_wn]
+    float *dec_cond;                    // Model::gin: the generator's [B][C0]
+};
+
+inline FlowBufs carve_flow(Carver &cv, const Model &m, int B, int F) {
+    FlowBufs f{};
+    const size_t nCF = (size_t)B * m.C * F, nHF = (size_t)B * m.flow_H * F;
+    f.zp = cv.take<float>(nCF);
+    f.z = cv.take<float>(nCF);
+    f.g = cv.take<float>(nCF);
+    f.hx = cv.take<float>(nHF);
+    f.skip = cv.take<float>(nHF);
+    f.acts = cv.take<float>(nHF);
+    f.a2 = cv.take<float>(nHF * 2);
+    f.hx_pl = take_planes(cv, nHF * 2);
+    f.x0_pl = take_planes(cv, nCF);
+    f.skip_pl = take_planes(cv, nHF * 2);
+    if (m.gin) {
+        for (const auto &cd : m.flow) f.gc.push_back(cv.take<float>((size_t)B * 2 * m.flow_H * cd.n_wn));
+        f.dec_cond = cv.take<float>((size_t)B * m.C0);
+    }
+    return f;
+}
+
+// what a vocoder-only call puts in front of the generator: z [B][C][F] from the host, and the speaker bias
+struct VocoderIn {
+    float *z;
+    int64_t *sid;     // Model::gin
+    float *dec_cond;  // Model::gin
+};
+
+inline VocoderIn carve_vocoder_in(Carver &cv, const Model &m, int B, int F) {
+    VocoderIn v{};
+    v.z = cv.take<float>((size_t)B * m.C * F);
+    if (m.gin) {
+        v.sid = cv.take<int64_t>(B);
+        v.dec_cond = cv.take<float>((size_t)B * m.C0);
+    }
+    return v;
+}
+
+// the generator's region: floats of its largest tensor when it renders F frames
+inline size_t gen_region_floats(const Model &m, int B, int F) {
+    size_t mx = (size_t)B * (m.C0 > m.C ? m.C0 : m.C) * ((F + 3) & ~3);
+    int64_t t = F;
+    for (auto &st : m.ups) {
+        t *= st.u;
+        size_t n = (size_t)B * st.C * t;
+        mx = n > mx ? n : mx;
+    }
+    return mx;
+}
+
+// frames the generator renders at a time when F are asked for: everything, or (chunk_frames > 0) one chunk with its context
+inline int gen_frames(const Model &m, int F, int chunk_frames) {
+    const int n = chunk_frames + 2 * m.gen_rf_frames;
+    return chunk_frames > 0 && n < F ? n : F;
+}
+
+// The three generator walkers' buffers; what a walker does not use stays null.
+struct GenBufs {
+    int *yl;  // the frame counts of the chunk being rendered
+    // split-operand walkers: plane tensors (R elements each as three 16-bit slots; they double as fp32 raw buffers where a
+    // stage uses the raw format), the fp32 multi-receptive-field sum, and (raw-stream walker) the fp32 residual stream
+    uint16_t *stage_in[2], *y_pl, *raa[2], *tmp_pl;
+    float *xs_raw, *y_raw, *ra[2];
+    float *reg[10];  // f32 engine: ten fp32 regions; the waveform is the last
+    float *out;      // the waveform [B][F * hop]
+};
+
+inline GenBufs carve_generator(Carver &cv, const Model &m, int B, int F) {
+    GenBufs g{};
+    const size_t R = gen_region_floats(m, B, F);
+    g.yl = cv.take<int>(B);
+    if (!m.gen_sx) {
+        for (auto &r : g.reg) r = cv.take<float>(R);
+        g.out = g.reg[9];
+        return g;
+    }
+    for (uint16_t **p : {&g.stage_in[0], &g.stage_in[1], &g.y_pl, &g.raa[0], &g.raa[1], &g.tmp_pl}) *p = take_planes(cv, plane_floats(R));
+    if (!m.gen_planes) {
+        g.y_raw = cv.take<float>(R);
+        g.ra[0] = cv.take<float>(R);
+        g.ra[1] = cv.take<float>(R);
+    }
+    g.xs_raw = cv.take<float>(R);
+    g.out = cv.take<float>((size_t)B * F * m.hop);
+    return g;
+}
+
+// The whole frame-domain slab of a request: B utterances, F frames in front of the generator (a multiple of 4 for the
+// flow), the generator rendering Fgen at a time (gen_frames).  `flow`: a synthesis run; false: a vocoder-only call.
+struct FrameBufs {
+    FlowBufs flow;
+    VocoderIn voc;
+    size_t gen_at;  // mark in front of the generator's part: each chunk of a chunked run carves it again
+    GenBufs gen;
+};
+
+inline FrameBufs carve_frames(Carver &cv, const Model &m, int B, int F, int Fgen, bool flow) {
+    FrameBufs f{};
+    if (flow) f.flow = carve_flow(cv, m, B, F);
+    else f.voc = carve_vocoder_in(cv, m, B, F);
+    f.gen_at = cv.mark();
+    f.gen = carve_generator(cv, m, B, Fgen);
+    return f;
+}
+
+// ---- staging slab (vits_handle::io): the host inputs of a call, or - between runs - the 16-bit waveform
+
+// ids | lens | sid contiguous (they arrive in one copy), then the injected noises: noise_dp [B][2][Tdp] and noise_z [B][C][Fz]
+// (Tdp, Fz: the tokens / frames per row of the noise a caller passes - sizes of the request like B and T; 0 without one)
+struct InputBufs {
+    int64_t *ids, *lens, *sid;
+    float *noise_dp, *noise_z;
+};
+
+inline InputBufs carve_inputs(Carver &cv, const Model &m, int B, int T, int Tdp, int64_t Fz) {
+    InputBufs i{};
+    i.ids = cv.take<int64_t>((size_t)B * T + 2 * (size_t)B);
+    if (i.ids) {
+        i.lens = i.ids + (size_t)B * T;
+        i.sid = i.lens + B;
+    }
+    i.noise_dp = cv.take<float>((size_t)B * 2 * Tdp);
+    i.noise_z = cv.take<float>((size_t)B * m.C * Fz);
+    return i;
+}
+
+// vits_last_pcm16: the int16 waveform [B][S] and the per-utterance peaks
+struct PcmBufs {
+    int16_t *pcm;
+    unsigned *peak;
+};
+
+inline PcmBufs carve_pcm16(Carver &cv, int B, int S) {
+    PcmBufs p{};
+    p.pcm = cv.take<int16_t>((size_t)B * S);
+    p.peak = cv.take<unsigned>(B);
+    return p;
+}
+
+}  // namespace vitsmi
