@@ -342,6 +342,55 @@ int vits_set_timing(vits_handle *h, int enable);
  * Applies to the following runs of this handle (whole and chunked). */
 int vits_set_tails(vits_handle *h, int reference);
 
+/* ---- output rate: the waveform delivered at a requested sample rate, resampled on the device -----------------
+ * The reference has no counterpart (phoonnx/voice.py writes config.sample_rate into the WAV header and nothing else); like
+ * vits_last_pcm16 this is an extension, and the definition below is its specification.
+ *
+ * The resampled signal.  Rates fi (in) and fo (out), g = gcd(fi, fo), L = fo / g, M = fi / g.  Constants Z = 16,
+ * beta = 8.555504641634386, rho = 0.85 (the widely used "kaiser_fast" windowed-sinc parameters).
+ *   s = rho * min(1, L / M),  W = Z / s,  K = 2 * ceil(W)
+ *   sinc(u) = sin(pi u) / (pi u);  kaiser(u) = I0(beta * sqrt(1 - u^2)) / I0(beta) for |u| < 1, else 0
+ *   k(d) = s * sinc(s * d) * kaiser(d / W)                                   (the continuous kernel)
+ *   h[p][j] = (float)k(p / L + K / 2 - 1 - j)   for p in [0, L), j in [0, K)  (the table)
+ * The table is computed in double on the host and rounded once to fp32; there is no per-phase renormalisation.
+ * Row b has n_b valid input samples (y_lengths[b] * hop; F * hop for a vocoder-only run) and N_b = ceil(n_b * L / M) output
+ * samples; S_out = max_b N_b.  Output sample n < N_b:
+ *   i = floor(n * M / L),  p = (n * M) mod L  (int64 arithmetic),  m0 = i - K / 2 + 1
+ *   y[b][n] = sum_{j = 0 .. K-1} h[p][j] * x[b][m0 + j]
+ * accumulated in fp32 with fmaf in ascending j, starting from 0.0f, where x[b][m] reads 0 for m < 0 and for m >= n_b -
+ * whatever the tails mode left behind n_b - and y[b][n] = 0.0f exactly for n >= N_b.
+ * i.e. a row's output depends on its own valid samples alone: neither the batch layout nor vits_set_tails enters, and the
+ * whole and the chunked rendering - which share one device function for a sample - agree bit for bit.
+ * (In float64 this design passes a tone at 0.3 of the lower rate at amplitude 1 within 1.5e-4 for 22050 -> 8000 / 16000 /
+ * 48000 Hz, leaves 2.1 - 2.3e-5 of a tone at 0.6 fo above the output Nyquist, has phase sums within 1.8e-5 of 1 and
+ * max_p sum_j |h[p][j]| <= 1.95.)
+ * Limits: both rates in [1, 384000]; L * K <= 2^18 table entries (the common targets need at most 16 640; 22050 -> 22051 is
+ * refused); N_b must fit in int.  A violation is VITS_E_ARG naming the value, before anything is allocated.
+ *
+ * vits_set_output_rate: handle state for the following runs, like vits_set_tails.  out_rate == 0 switches resampling off;
+ * in_rate <= 0 means the file's "sample_rate" metadata (22050 without it).  out_rate == in_rate is "no resampling": the
+ * native path, unchanged.  Host-only and layout-only handles accept it and keep the plan (no table on a device).  With a
+ * rate set:
+ *   vits_run (out), vits_fetch_output and vits_last_pcm16 deliver the resampled waveform: dims = [B,1,1,S_out], row pitch
+ *     rules as before; vits_last_pcm16 takes the peak over the resampled valid samples, then the same fp32 operations;
+ *   vits_run_chunked* / vits_run_vocoder_chunked keep the last K input samples of every row on the device between chunks:
+ *     after each chunk the callback receives exactly the output samples whose K inputs now all exist, after the last one the
+ *     rest (against zeros).  first_sample, n_samples and total_samples (= ceil(F * hop * L / M)) count output-rate samples;
+ *     deliveries are contiguous and in order; a chunk that completes no output sample (chunk_frames * hop shorter than the
+ *     filter's look-ahead) makes no call.  Concatenated they are the whole run's [B, S_out] bit for bit, for every
+ *     chunk_frames >= 1;
+ *   vits_last_y_lengths, vits_last_durations and vits_tap are untouched: frames stay frames;
+ *   vits_run_device* return VITS_E_ARG ("not covered with an output rate set");
+ *   vits_reserve covers the resampled waveform and its 16-bit rendering too.
+ * With the rate off, every path executes exactly what it executed before the rate existed. */
+int vits_set_output_rate(vits_handle *h, int in_rate, int out_rate);
+/* N_b per row of the last run at the CURRENT output rate (y_lengths * hop with the rate off): from host state like
+ * vits_last_y_lengths, valid from the same moment.  Writes min(n, B) values, returns B. */
+int vits_last_sample_counts(vits_handle *h, int64_t *buf, int n);
+/* The plan of a pair of rates - pure host code, no handle, no device: L, M, K (each pointer may be NULL) and, with
+ * table != NULL, h as [L][K] floats (table_elems >= L * K).  table == NULL asks for the sizes. */
+int vits_resample_plan(int in_rate, int out_rate, int64_t *L, int64_t *M, int64_t *K, float *table, size_t table_elems);
+
 /* Size the handle's device workspaces NOW for requests of up to B utterances x T tokens that render up to F frames each
  * (the batch's longest utterance; T = 0 or F = 0 leaves that domain alone).  A run grows a workspace when a request
  * needs more than any before it - hipFree + hipMalloc of tens of GB at batch 32, a device-wide synchronisation that was
@@ -443,6 +492,15 @@ int vits_test_attention(int device_id, const float *qkv, int B, int C, int T, in
 int vits_test_attention16(int device_id, const float *qkv, int B, int C, int T, int n_heads, const float *rel_k,
                           const float *rel_v, int window, const int64_t *lens, float *out, uint16_t *out_planes, int kernel,
                           int reps, float *ms_out);
+
+/* The resampler by value: x [B][S] host, lens [B] the rows' valid samples (what lies behind must not show), y [B][S_out]
+ * with S_out >= max_b ceil(lens[b] * L / M); every column of y is written. */
+int vits_test_resample(int device_id, const float *x, const int64_t *lens, int B, int S, int in_rate, int out_rate, float *y,
+                       int64_t S_out);
+/* ... the same input through the chunked entry, piece_samples input samples at a time (S_out >= ceil(S * L / M)).  Returns
+ * the number of deliveries; ranges (nullable, max_ranges pairs) receives each one's (first_sample, n_samples). */
+int vits_test_resample_pieces(int device_id, const float *x, const int64_t *lens, int B, int S, int in_rate, int out_rate,
+                              int piece_samples, float *y, int64_t S_out, int64_t *ranges, int max_ranges);
 
 #ifdef __cplusplus
 }

@@ -62,6 +62,7 @@ EXPORTS = [
     "vits_bench_conv1d_sx", "vits_test_conv_pair_sx", "vits_fetch_output", "vits_run_async", "vits_host_alloc", "vits_host_free",
     "vits_launch_records", "vits_run_async_rows", "vits_run_device_rows", "vits_run_chunked_rows",
     "vits_run_async_ctl", "vits_run_chunked_ctl", "vits_last_durations",
+    "vits_set_output_rate", "vits_last_sample_counts", "vits_resample_plan", "vits_test_resample", "vits_test_resample_pieces",
 ]
 
 
@@ -127,6 +128,11 @@ def load():
     lib.vits_run_chunked_ctl.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.POINTER(VitsNoise), C.POINTER(VitsControls),
                                          C.c_int, CHUNK_FN, vp]
     lib.vits_last_durations.argtypes = [vp, i64p, C.c_size_t]
+    lib.vits_set_output_rate.argtypes = [vp, C.c_int, C.c_int]
+    lib.vits_last_sample_counts.argtypes = [vp, i64p, C.c_int]
+    lib.vits_resample_plan.argtypes = [C.c_int, C.c_int, i64p, i64p, i64p, vp, C.c_size_t]
+    lib.vits_test_resample.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int64]
+    lib.vits_test_resample_pieces.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int64, vp, C.c_int]
     lib.vits_free_output.argtypes = [vp, C.POINTER(VitsOutput)]
     lib.vits_free_output.restype = None
     lib.vits_sync.argtypes = [vp]

@@ -26,6 +26,7 @@
 #include "conv_sx_small.hip.hpp"
 #include "kernels.hip.hpp"
 #include "model.hpp"
+#include "resample.hip.hpp"
 #include "test_dev.hip.hpp"
 #include "workspace.hpp"
 
@@ -115,6 +116,14 @@ struct vits_handle {
     char *ring[2] = {nullptr, nullptr};
     size_t ring_cap = 0;
     hipEvent_t ring_ev[2] = {nullptr, nullptr};
+    // Output rate (vits_set_output_rate): the plan and, on a device handle, its table.  rs.plan.on() == false: every path is
+    // the native one.  A run with a rate leaves its resampled waveform in the staging slab: d_out / S then describe THAT
+    // buffer, out_resampled says so, d_nout holds the rows' output sample counts (vits_last_pcm16's valid lengths) and
+    // rs_run_K the K its walk was carved with.
+    ResampleDev rs;
+    bool out_resampled = false;
+    int *d_nout = nullptr;
+    int rs_run_K = 0;
 };
 
 // chunked rendering (vits_run_chunked / vits_run_vocoder_chunked): where the audio goes
@@ -228,7 +237,12 @@ void forget_results_in(vits_handle *h, const Slab &s) {
         h->d_ylen64 = nullptr;
         h->h_dur_B = h->h_dur_T = 0;
     } else if (&s == &h->frm) {
-        h->d_zp = h->d_z = h->d_out = nullptr;
+        h->d_zp = h->d_z = nullptr;
+        if (!h->out_resampled) h->d_out = nullptr;
+    } else if (&s == &h->io && h->out_resampled) {  // (with an output rate set the waveform lives in the staging slab)
+        h->d_out = nullptr;
+        h->d_nout = nullptr;
+        h->out_resampled = false;
     }
 }
 
@@ -1732,6 +1746,50 @@ __global__ void chunk_len_kernel(const int *ylen, int *out, int B, int lo, int n
     }
 }
 
+// ---- output rate (vits_set_output_rate): the rendered waveform resampled on the device (resample.hip.hpp)
+
+// The staging slab carved for the resampled result of B rows of S_in input samples.  The run's inputs lived there: every
+// kernel that read them precedes the resampler on the stream (and a growing slab waits for the stream first).
+int resample_carve(vits_handle *h, int B, int64_t S_in, ResampleBufs &rb, int &S_out) {
+    const ResamplePlan &p = h->rs.plan;
+    const int64_t so = p.count(S_in);
+    if (so > INT_MAX)
+        return fail(h, VITS_E_ARG, "%lld samples at %d Hz are %lld samples at %d Hz: more than a row admits (%d)", (long long)S_in,
+                    p.fi, (long long)so, p.fo, INT_MAX);
+    S_out = (int)so;
+    return slab_carve(h, h->io, "staging", [&](Carver &cv) { rb = carve_resample(cv, B, S_out, (int)p.K); });
+}
+
+// The whole waveform a run has just rendered (h->d_out, rows of h->S samples, ylen[b] * hop of them valid; no frame counts:
+// all) -> [B][S_out] at the output rate.  d_out / S describe the resampled buffer afterwards.
+int resample_run(vits_handle *h, const int *ylen, int B) {
+    const ResamplePlan &p = h->rs.plan;
+    const int S = h->S;
+    ResampleBufs rb;
+    int S_out = 0;
+    if (int rc = resample_carve(h, B, S, rb, S_out)) return rc;
+    hipStream_t st = h->stream;
+    resample_counts_kernel<<<(B + 63) / 64, 64, 0, st>>>(ylen, h->model.hop, S, p.L, p.M, rb.n_in, rb.n_out, B);
+    ResampleArgs a = resample_args(h->rs);
+    a.x = h->d_out;
+    a.x_pitch = S;
+    a.x_n = S;
+    a.n_in = rb.n_in;
+    a.n_out = rb.n_out;
+    a.y = rb.out;
+    a.y_pitch = S_out;
+    a.n_hi = S_out;
+    const hipError_t e = launch_resample(a, B, /*piece=*/false, st);
+    if (e != hipSuccess) return fail(h, VITS_E_DEVICE, "resampler launch failed: %s", hipGetErrorString(e));
+    h->stats.total_launches += 2;
+    h->d_out = rb.out;
+    h->S = S_out;
+    h->d_nout = rb.n_out;
+    h->rs_run_K = (int)p.K;
+    h->out_resampled = true;
+    return 0;
+}
+
 // Frames [0, F) of z rendered in chunks of sink->chunk_frames: each chunk is rendered together with gen_rf_frames of
 // context on either side (clipped at the utterance ends, where the generator really sees zero padding) and only its
 // interior is kept, so every sample equals the one an unchunked run produces (the convolutions accumulate in the same
@@ -1743,7 +1801,23 @@ int render_chunks(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int
     hipStream_t st = h->stream;
     const int ov = m.gen_rf_frames, hop = m.hop;
     const int chunk = sink.chunk_frames;
-    const size_t ring_bytes = (size_t)B * chunk * hop * sizeof(float);
+    // With an output rate set the chunks' interiors go through the resampler's piece entry, which keeps the last K input
+    // samples of every row on the device (the carry): after each chunk exactly the output samples whose K inputs now all
+    // exist are delivered, after the last one the rest (against zeros) - the batch path's [B][S_out], bit for bit.
+    const bool rs = h->rs.plan.on();
+    const ResamplePlan &rp = h->rs.plan;
+    ResampleBufs rb{};
+    int S_out = 0, rs_gen = 0, emitted = 0;
+    int64_t emit_cap = 0;
+    if (rs) {
+        if (int rc = resample_carve(h, B, (int64_t)F * hop, rb, S_out)) return rc;
+        emit_cap = rp.count((int64_t)(chunk < F ? chunk : F) * hop + rp.K / 2) + 2;  // output samples one chunk can complete
+        emit_cap = emit_cap < S_out ? emit_cap : S_out;
+        resample_counts_kernel<<<(B + 63) / 64, 64, 0, st>>>(ylen, hop, F * hop, rp.L, rp.M, rb.n_in, rb.n_out, B);
+        HIPCHECK(h, hipMemsetAsync(rb.carry[0], 0, (size_t)B * rp.K * sizeof(float), st));
+        h->stats.total_launches++;
+    }
+    const size_t ring_bytes = rs ? (size_t)B * emit_cap * sizeof(float) : (size_t)B * chunk * hop * sizeof(float);
     if (ring_bytes > h->ring_cap) {
         for (auto &r : h->ring) {
             if (r) hipHostFree(r);
@@ -1761,7 +1835,7 @@ int render_chunks(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int
     int *yl = fb.gen.yl;
     Carver cv(h->frm.base, h->frm.cap);
     const int *const whole_len = c.h_len;  // host copy of ylen (or nullptr)
-    const int64_t total = (int64_t)F * hop;
+    const int64_t total = rs ? (int64_t)S_out : (int64_t)F * hop;
     int64_t pend_first = 0, pend_n = 0;
     int pend = -1, k = 0, stop = 0;
     auto deliver = [&]() -> int {  // hand the pending chunk to the caller
@@ -1787,6 +1861,45 @@ int render_chunks(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int
         if (rc_gen) return rc_gen;
         if (c.err != hipSuccess) return fail(h, VITS_E_DEVICE, "kernel launch failed: %s", hipGetErrorString(c.err));
         const int64_t ns = (int64_t)(f1 - f0) * hop;
+        if (rs) {
+            // interior of this chunk = input samples [f0 * hop, f1 * hop) of every row, behind the carry
+            const int64_t done = rp.complete((int64_t)f1 * hop);
+            const int n_hi = f1 == F ? S_out : (int)(done < S_out ? done : S_out), ne = n_hi - emitted;
+            ResampleArgs a = resample_args(h->rs);
+            a.x = h->d_out + (int64_t)(f0 - lo) * hop;
+            a.x_pitch = h->S;
+            a.x_first = (int)((int64_t)f0 * hop);
+            a.x_n = (int)ns;
+            a.carry = rb.carry[rs_gen];
+            a.n_in = rb.n_in;
+            a.n_out = rb.n_out;
+            a.y = rb.out;  // [B][ne]: what this chunk completes (the previous chunk's copy-out precedes it on the stream)
+            a.y_pitch = ne;
+            a.y_first = emitted;
+            a.n_lo = emitted;
+            a.n_hi = n_hi;
+            hipError_t e = launch_resample(a, B, /*piece=*/true, st);
+            if (e == hipSuccess && f1 < F) {
+                resample_carry_kernel<<<dim3((unsigned)((rp.K + 255) / 256), B), 256, 0, st>>>(rb.carry[rs_gen], a.x, a.x_pitch, a.x_n,
+                                                                                            a.K, rb.carry[rs_gen ^ 1]);
+                e = hipGetLastError();
+                rs_gen ^= 1;
+            }
+            if (e != hipSuccess) return fail(h, VITS_E_DEVICE, "resampler launch failed: %s", hipGetErrorString(e));
+            h->stats.total_launches += 2;
+            if (ne <= 0) {  // (a chunk shorter than the filter's look-ahead completes nothing: no call)
+                k ^= 1;
+                continue;
+            }
+            HIPCHECK(h, hipMemcpyAsync(h->ring[k], rb.out, (size_t)B * ne * 4, hipMemcpyDeviceToHost, st));
+            HIPCHECK(h, hipEventRecord(h->ring_ev[k], st));
+            if (int rc = deliver()) return rc;
+            pend = k;
+            pend_first = emitted;
+            pend_n = ne;
+            emitted = n_hi;
+            continue;
+        }
         // interior of this chunk: samples [(f0 - lo) * hop, (f1 - lo) * hop) of every row -> ring[k] as [B, ns]
         HIPCHECK(h, hipMemcpy2DAsync(h->ring[k], (size_t)ns * 4, h->d_out + (int64_t)(f0 - lo) * hop, (size_t)h->S * 4,
                                      (size_t)ns * 4, B, hipMemcpyDeviceToHost, st));
@@ -2132,6 +2245,7 @@ void vits_close(vits_handle *h) {
         if (h->tok.base) hipFree(h->tok.base);
         if (h->frm.base) hipFree(h->frm.base);
         if (h->io.base) hipFree(h->io.base);
+        if (h->rs.table) hipFree(h->rs.table);
         if (h->pin.base) hipHostFree(h->pin.base);
         if (h->d_range) hipFree(h->d_range);
         if (h->h_range) hipHostFree(h->h_range);
@@ -2219,6 +2333,71 @@ int vits_set_tails(vits_handle *h, int reference) {
     return VITS_OK;
 }
 
+int vits_set_output_rate(vits_handle *h, int in_rate, int out_rate) {
+    if (!h) return VITS_E_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (out_rate < 0) return fail(h, VITS_E_ARG, "output rate %d is negative", out_rate);
+    ResampleDev nw;  // (off)
+    if (out_rate != 0) {
+        int fi = in_rate;
+        if (fi <= 0) {
+            auto it = h->model.meta.find("sample_rate");
+            fi = it != h->model.meta.end() ? std::atoi(it->second.c_str()) : 22050;
+        }
+        ResamplePlan p;
+        const std::string e = resample_plan(fi, out_rate, p);
+        if (!e.empty()) return fail(h, VITS_E_ARG, "%s", e.c_str());
+        if (fi != out_rate) nw.plan = p;  // (equal rates: no resampling, the native path)
+    }
+    if (nw.plan.on() && !h->host_only) {
+        nw.Kp = resample_pitch(nw.plan);
+        std::vector<float> t((size_t)nw.plan.L * nw.Kp);
+        resample_table(nw.plan, t.data(), nw.Kp);
+        if (hipSetDevice(h->device) != hipSuccess) return fail(h, VITS_E_DEVICE, "hipSetDevice(%d) failed", h->device);
+        if (hipMalloc((void **)&nw.table, t.size() * sizeof(float)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(h, VITS_E_NOMEM, "cannot place the %zu-byte resampling table on device %d", t.size() * sizeof(float), h->device);
+        }
+        if (hipMemcpy(nw.table, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+            hipFree(nw.table);
+            return fail(h, VITS_E_DEVICE, "cannot copy the resampling table to device %d", h->device);
+        }
+    }
+    if (h->rs.table) {  // (a run that reads the old table may still be in flight)
+        hipSetDevice(h->device);
+        hipStreamSynchronize(h->stream);
+        hipFree(h->rs.table);
+    }
+    h->rs = nw;
+    return VITS_OK;
+}
+
+int vits_last_sample_counts(vits_handle *h, int64_t *buf, int n) {
+    if (!h) return VITS_E_ARG;
+    const int B = (int)h->h_ylen.size();
+    const int64_t hop = h->model.hop;
+    for (int b = 0; b < B && b < n && buf; b++) {
+        const int64_t s = (int64_t)h->h_ylen[b] * hop;
+        buf[b] = h->rs.plan.on() ? h->rs.plan.count(s) : s;
+    }
+    return B;
+}
+
+int vits_resample_plan(int in_rate, int out_rate, int64_t *L, int64_t *M, int64_t *K, float *table, size_t table_elems) {
+    ResamplePlan p;
+    const std::string e = resample_plan(in_rate, out_rate, p);
+    if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
+    if (L) *L = p.L;
+    if (M) *M = p.M;
+    if (K) *K = p.K;
+    if (table) {
+        if (table_elems < (size_t)(p.L * p.K))
+            return fail(nullptr, VITS_E_ARG, "table buffer too small: %zu < %lld", table_elems, (long long)(p.L * p.K));
+        resample_table(p, table, p.K);
+    }
+    return VITS_OK;
+}
+
 static int check_dev(vits_handle *h) {
     if (!h) return VITS_E_ARG;
     if (h->host_only) return fail(h, VITS_E_DEVICE, "handle was opened host-only");
@@ -2238,7 +2417,14 @@ int vits_reserve(vits_handle *h, int B, int T, int F) {
         // vits_last_pcm16's int16 waveform and per-utterance peaks (the larger of the two uses)
         const size_t io_in = carved_bytes([&](Carver &cv) { carve_inputs(cv, m, B, T, T, Fp); });
         const size_t io_pcm = carved_bytes([&](Carver &cv) { carve_pcm16(cv, B, F * m.hop); });
-        if (int rc = slab_reserve(h, h->io, io_in > io_pcm ? io_in : io_pcm, false)) return rc;
+        size_t io = io_in > io_pcm ? io_in : io_pcm;
+        if (h->rs.plan.on()) {  // ... or the resampled waveform with its own 16-bit rendering
+            const int64_t so = h->rs.plan.count((int64_t)F * m.hop);
+            if (so > INT_MAX) return fail(h, VITS_E_ARG, "vits_reserve: F=%d frames are %lld samples at %d Hz", F, (long long)so, h->rs.plan.fo);
+            const size_t io_rs = carved_bytes([&](Carver &cv) { carve_resample(cv, B, (int)so, (int)h->rs.plan.K); });
+            io = io_rs > io ? io_rs : io;
+        }
+        if (int rc = slab_reserve(h, h->io, io, false)) return rc;
     }
     if (F > 0)
         if (int rc = slab_reserve(h, h->frm, carved_bytes([&](Carver &cv) { carve_frames(cv, m, B, Fp, Fp, /*flow=*/true); }), false)) return rc;
@@ -2317,6 +2503,7 @@ static int run_device_locked(vits_handle *h, const int64_t *ids, const int64_t *
     h->B = B;
     h->T = T;
     h->range_failed = false;
+    h->out_resampled = false;
     uint64_t seed = noise ? noise->seed : 0;
     seed = seed * 0x9E3779B97F4A7C15ull + (++h->run_counter);
     // (run_tokens' one synchronisation also completes the previous run on this handle: its range verdict, if nobody
@@ -2326,6 +2513,8 @@ static int run_device_locked(vits_handle *h, const int64_t *ids, const int64_t *
     if (int rc = run_frames(h, B, T, rr, sid, noise ? noise->noise_z : nullptr, noise ? noise->noise_z_stride : 0,
                             seed, sink))
         return rc;
+    if (h->rs.plan.on() && !sink)
+        if (int rc = resample_run(h, h->d_ylen, B)) return rc;
     ylen_to_i64<<<(B + 63) / 64, 64, 0, h->stream>>>(h->d_ylen, h->d_ylen64, B);
     range_end(h);
     if (out) {
@@ -2344,6 +2533,7 @@ int vits_run_device(vits_handle *h, const int64_t *ids, const int64_t *lens, int
     if (int rc = check_dev(h)) return rc;
     std::lock_guard<std::mutex> lk(h->mu);
     if (!out) return fail(h, VITS_E_ARG, "null argument");
+    if (h->rs.plan.on()) return fail(h, VITS_E_ARG, "vits_run_device is not covered with an output rate set");
     return run_device_locked(h, ids, lens, B, T, one_row(scales), sid, noise, out);
 }
 
@@ -2352,6 +2542,7 @@ int vits_run_device_rows(vits_handle *h, const int64_t *ids, const int64_t *lens
     if (int rc = check_dev(h)) return rc;
     std::lock_guard<std::mutex> lk(h->mu);
     if (!out) return fail(h, VITS_E_ARG, "null argument");
+    if (h->rs.plan.on()) return fail(h, VITS_E_ARG, "vits_run_device_rows is not covered with an output rate set");
     RunRows rr;
     if (int rc = host_rows(h, scales, B, seeds, rr)) return rc;
     return run_device_locked(h, ids, lens, B, T, rr, sid, noise, out);
@@ -2411,6 +2602,7 @@ static int stage_inputs(vits_handle *h, const int64_t *ids, const int64_t *lens,
     const size_t ndp = (size_t)B * 2 * Tdp * 4, nz = (size_t)B * m.C * Fz * 4;
     InputBufs in;
     if (int rc0 = slab_carve(h, h->io, "staging", [&](Carver &cv) { in = carve_inputs(cv, m, B, T, Tdp, Fz); })) return rc0;
+    if (h->out_resampled) forget_results_in(h, h->io);  // (a resampled waveform lived where these inputs go)
     sg.d_ids = in.ids;
     sg.d_lens = in.lens;
     int64_t *d_sid = in.sid;
@@ -2595,17 +2787,25 @@ int vits_last_pcm16(vits_handle *h, int normalize, float volume, int16_t *out, s
     if (!out || out_elems < n) return fail(h, VITS_E_ARG, "pcm16 buffer too small: %zu < %zu", out_elems, n);
     // the staging slab is idle between runs (vits_run has consumed its inputs before it returns)
     PcmBufs pb;
-    if (int rc = slab_carve(h, h->io, "staging", [&](Carver &cv) { pb = carve_pcm16(cv, B, S); })) return rc;
+    const bool rs = h->out_resampled;  // the waveform is the resampled one: its walk carved these buffers behind it
+    if (rs) {
+        const int K = h->rs_run_K;
+        if (int rc = slab_carve(h, h->io, "staging", [&](Carver &cv) { pb = carve_resample(cv, B, S, K).pcm; })) return rc;
+        if (!h->d_out) return fail(h, VITS_E_ARG, "no completed run to post-process");
+    } else if (int rc = slab_carve(h, h->io, "staging", [&](Carver &cv) { pb = carve_pcm16(cv, B, S); }))
+        return rc;
     int16_t *d_pcm = pb.pcm;
     unsigned *d_peak = pb.peak;
     hipStream_t st = h->stream;
     hipError_t e = hipMemsetAsync(d_peak, 0, (size_t)B * 4, st);
-    const int hop = h->model.hop;
+    // (valid samples of a row: y_len[b] * hop, or - resampled - its output sample count)
+    const int hop = rs ? 1 : h->model.hop;
+    const int *vlen = rs ? h->d_nout : h->d_ylen;
     if (e == hipSuccess) {
         int gx = (S + 255) / 256;
         gx = gx > 256 ? 256 : gx;
-        peak_abs_kernel<<<dim3(gx, B), 256, 0, st>>>(h->d_out, h->d_ylen, hop, S, d_peak);
-        pcm16_kernel<<<dim3((S + 255) / 256, B), 256, 0, st>>>(h->d_out, h->d_ylen, hop, S, d_peak, normalize, volume, d_pcm);
+        peak_abs_kernel<<<dim3(gx, B), 256, 0, st>>>(h->d_out, vlen, hop, S, d_peak);
+        pcm16_kernel<<<dim3((S + 255) / 256, B), 256, 0, st>>>(h->d_out, vlen, hop, S, d_peak, normalize, volume, d_pcm);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(out, d_pcm, n * 2, hipMemcpyDeviceToHost, st);
@@ -2649,6 +2849,7 @@ static int vocoder_common(vits_handle *h, const float *z, int B, int F, const in
     }
     h->B = B;
     h->F = F;
+    h->out_resampled = false;
     h->d_ylen = nullptr;  // (no frame counts: vits_last_pcm16 does not apply to a vocoder-only run)
     h->h_dur_B = h->h_dur_T = 0;  // (no tokens: vits_last_durations has nothing to report)
     range_begin(h);
@@ -2657,6 +2858,8 @@ static int vocoder_common(vits_handle *h, const float *z, int B, int F, const in
     else rc = run_generator(h, c, dz, (int64_t)m.C * F, F, nullptr, B, F, dec_cond, fb.gen);
     if (rc) return rc;
     if (c.err != hipSuccess) return fail(h, VITS_E_DEVICE, "kernel launch failed: %s", hipGetErrorString(c.err));
+    if (h->rs.plan.on() && !sink)
+        if (int rc2 = resample_run(h, nullptr, B)) return rc2;
     range_end(h);
     if (sink) {
         HIPCHECK(h, hipStreamSynchronize(st));
@@ -3406,6 +3609,119 @@ int vits_test_attention16(int device_id, const float *qkv, int B, int C, int T, 
     TCHECK(download(out, dout, no));
     if (out_planes) TCHECK(download(out_planes, dop, no * 3));
     return VITS_OK;
+}
+
+// The resampler by value: what both hooks share - the plan's table on the device, the rows' valid input samples
+// (lens, clipped to [0, S]) and output sample counts.
+namespace {
+struct ResampleTest {
+    ResampleDev dev;
+    std::vector<int> n_in, n_out;
+    int *d_n_in = nullptr, *d_n_out = nullptr;
+    int64_t n_max = 0;
+};
+int resample_test_setup(DevBufs &D, const int64_t *lens, int B, int S, int in_rate, int out_rate, ResampleTest &t) {
+    if (!lens || B <= 0 || S <= 0) return fail(nullptr, VITS_E_ARG, "bad resampler test arguments");
+    const std::string e = resample_plan(in_rate, out_rate, t.dev.plan);
+    if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
+    const ResamplePlan &p = t.dev.plan;
+    if (p.count(S) > INT_MAX) return fail(nullptr, VITS_E_ARG, "%d samples are %lld at %d Hz", S, (long long)p.count(S), out_rate);
+    t.dev.Kp = resample_pitch(p);
+    std::vector<float> tab((size_t)p.L * t.dev.Kp);
+    resample_table(p, tab.data(), t.dev.Kp);
+    t.dev.table = D.up(tab.data(), tab.size());
+    for (int b = 0; b < B; b++) {
+        const int64_t n = lens[b] < 0 ? 0 : (lens[b] > S ? S : lens[b]);
+        t.n_in.push_back((int)n);
+        t.n_out.push_back((int)p.count(n));
+        t.n_max = p.count(n) > t.n_max ? p.count(n) : t.n_max;
+    }
+    t.d_n_in = D.up(t.n_in.data(), (size_t)B);
+    t.d_n_out = D.up(t.n_out.data(), (size_t)B);
+    return VITS_OK;
+}
+}  // namespace
+
+int vits_test_resample(int device_id, const float *x, const int64_t *lens, int B, int S, int in_rate, int out_rate, float *y,
+                       int64_t S_out) {
+    if (int rc = test_dev(device_id)) return rc;
+    if (!x || !y) return fail(nullptr, VITS_E_ARG, "bad resampler test arguments");
+    DevBufs D;
+    ResampleTest t;
+    if (int rc = resample_test_setup(D, lens, B, S, in_rate, out_rate, t)) return rc;
+    if (S_out < t.n_max || S_out < 1 || S_out > INT_MAX)
+        return fail(nullptr, VITS_E_ARG, "S_out = %lld, the longest row has %lld output samples", (long long)S_out, (long long)t.n_max);
+    float *dx = D.up(x, (size_t)B * S);
+    float *dy = D.fill<float>((size_t)B * S_out, 0xff);
+    TCHECK(D.err);
+    ResampleArgs a = resample_args(t.dev);
+    a.x = dx;
+    a.x_pitch = S;
+    a.x_n = S;
+    a.n_in = t.d_n_in;
+    a.n_out = t.d_n_out;
+    a.y = dy;
+    a.y_pitch = S_out;
+    a.n_hi = (int)S_out;
+    TCHECK(launch_resample(a, B, /*piece=*/false, nullptr));
+    TCHECK(hipDeviceSynchronize());
+    TCHECK(download(y, dy, (size_t)B * S_out));
+    return VITS_OK;
+}
+
+int vits_test_resample_pieces(int device_id, const float *x, const int64_t *lens, int B, int S, int in_rate, int out_rate,
+                              int piece_samples, float *y, int64_t S_out, int64_t *ranges, int max_ranges) {
+    if (int rc = test_dev(device_id)) return rc;
+    if (!x || !y || piece_samples < 1) return fail(nullptr, VITS_E_ARG, "bad resampler test arguments");
+    DevBufs D;
+    ResampleTest t;
+    if (int rc = resample_test_setup(D, lens, B, S, in_rate, out_rate, t)) return rc;
+    const ResamplePlan &p = t.dev.plan;
+    const int total = (int)p.count(S), K = (int)p.K;
+    if (S_out < total) return fail(nullptr, VITS_E_ARG, "S_out = %lld, %d input samples give %d", (long long)S_out, S, total);
+    float *dx = D.up(x, (size_t)B * S);
+    float *dy = D.fill<float>((size_t)B * total, 0xff);  // one piece's output [B][ne]
+    float *carry[2] = {D.fill<float>((size_t)B * K), D.fill<float>((size_t)B * K)};
+    TCHECK(D.err);
+    std::vector<float> piece((size_t)B * total);
+    std::memset(y, 0, (size_t)B * S_out * sizeof(float));
+    int emitted = 0, gen = 0, calls = 0;
+    for (int f0 = 0; f0 < S; f0 += piece_samples) {
+        const int f1 = S - f0 > piece_samples ? f0 + piece_samples : S;
+        const int64_t done = p.complete(f1);
+        const int n_hi = f1 == S ? total : (int)(done < total ? done : total), ne = n_hi - emitted;
+        ResampleArgs a = resample_args(t.dev);
+        a.x = dx + f0;
+        a.x_pitch = S;
+        a.x_first = f0;
+        a.x_n = f1 - f0;
+        a.carry = carry[gen];
+        a.n_in = t.d_n_in;
+        a.n_out = t.d_n_out;
+        a.y = dy;
+        a.y_pitch = ne;
+        a.y_first = emitted;
+        a.n_lo = emitted;
+        a.n_hi = n_hi;
+        TCHECK(launch_resample(a, B, /*piece=*/true, nullptr));
+        if (f1 < S) {
+            resample_carry_kernel<<<dim3((unsigned)((K + 255) / 256), B), 256>>>(carry[gen], a.x, a.x_pitch, a.x_n, K, carry[gen ^ 1]);
+            TCHECK(hipGetLastError());
+            gen ^= 1;
+        }
+        if (ne <= 0) continue;
+        TCHECK(hipDeviceSynchronize());
+        TCHECK(download(piece.data(), dy, (size_t)B * ne));
+        for (int b = 0; b < B; b++) std::memcpy(y + (size_t)b * S_out + emitted, piece.data() + (size_t)b * ne, (size_t)ne * sizeof(float));
+        if (ranges && calls < max_ranges) {
+            ranges[2 * calls] = emitted;
+            ranges[2 * calls + 1] = ne;
+        }
+        calls++;
+        emitted = n_hi;
+    }
+    TCHECK(hipDeviceSynchronize());
+    return calls;
 }
 
 }  // extern "C"

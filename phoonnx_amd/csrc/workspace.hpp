@@ -236,4 +236,26 @@ inline PcmBufs carve_pcm16(Carver &cv, int B, int S) {
     return p;
 }
 
+// With an output rate set (vits_set_output_rate), the staging slab holds the run's RESULT once its inputs are consumed:
+// the resampled fp32 waveform [B][S_out] (a chunked run: the output samples of one chunk, never more than S_out per
+// row), the rows' valid input and output sample counts, the two generations of the chunked path's carry [B][K] (the
+// last K input samples of every row; one is read while the other is written), and behind them vits_last_pcm16's buffers
+// for that waveform - one walk, so that converting it never moves what it converts.
+struct ResampleBufs {
+    float *out;
+    int *n_in, *n_out;
+    float *carry[2];
+    PcmBufs pcm;
+};
+
+inline ResampleBufs carve_resample(Carver &cv, int B, int S_out, int K) {
+    ResampleBufs r{};
+    r.out = cv.take<float>((size_t)B * S_out);
+    r.n_in = cv.take<int>(B);
+    r.n_out = cv.take<int>(B);
+    for (auto &c : r.carry) c = cv.take<float>((size_t)B * K);
+    r.pcm = carve_pcm16(cv, B, S_out);
+    return r;
+}
+
 }  // namespace vitsmi

@@ -218,6 +218,29 @@ def _controls(rows, seeds, durations, token_rate):
     return c
 
 
+def resample_plan(in_rate: int, out_rate: int, table: bool = False):
+    """The output-rate resampler's plan for a pair of rates (vitsmi.h, "output rate"; pure host code): (L, M, K), or with
+    table=True (L, M, K, h float32 [L, K]).  Raises SessionError for a pair the engine refuses."""
+    lib = _ffi.load()
+    L, M, K = C.c_int64(), C.c_int64(), C.c_int64()
+    rc = lib.vits_resample_plan(int(in_rate), int(out_rate), C.byref(L), C.byref(M), C.byref(K), None, 0)
+    if rc != 0:
+        raise SessionError(f"vits_resample_plan({in_rate}, {out_rate}) failed [{rc}]: {_ffi.last_error(None)}")
+    if not table:
+        return L.value, M.value, K.value
+    h = np.empty((L.value, K.value), np.float32)
+    rc = lib.vits_resample_plan(int(in_rate), int(out_rate), None, None, None, _ffi.ptr(h), h.size)
+    if rc != 0:
+        raise SessionError(f"vits_resample_plan({in_rate}, {out_rate}) failed [{rc}]: {_ffi.last_error(None)}")
+    return L.value, M.value, K.value, h
+
+
+def output_sample_counts(n_samples, in_rate: int, out_rate: int) -> np.ndarray:
+    """ceil(n * L / M): the output samples of rows of n valid input samples (what last_sample_counts() reports per row)."""
+    L, M, _ = resample_plan(in_rate, out_rate)
+    return -(-np.asarray(n_samples, np.int64) * L // M)
+
+
 def _rows(scales, B):
     """[3] -> [B, 3] (the row twins of the C ABI take one row per utterance)"""
     return np.ascontiguousarray(np.broadcast_to(scales, (B, 3)) if scales.ndim == 1 else scales, np.float32)
@@ -237,7 +260,7 @@ class MiSession:
     def __init__(self, path_or_bytes, sess_options=None, providers=None, provider_options=None, device_id: int = 0,
                  arena_device_ptr: Optional[int] = None, arena_bytes: int = 0, host_only: bool = False,
                  gen_precision: Optional[str] = None, range_fallback: bool = True, layout_only: bool = False,
-                 pinned_results: bool = True, tails: Optional[str] = None, **kwargs):
+                 pinned_results: bool = True, tails: Optional[str] = None, output_rate: Optional[int] = None, **kwargs):
         """tails: what a padded batch (B > 1, unequal frame counts) holds behind each utterance's end - None (VITSMI_TAILS or
         the default "zero"), "zero" (those samples are not rendered at all and read 0.0; every valid sample is bit-identical to
         the padded rendering), "reference" (the exported graph's own padded rendering: its generator is not masked,
@@ -247,6 +270,8 @@ class MiSession:
         "f16x3", "bf16x6" (exact products), "f16" (the reduced-precision vocoder of BASELINE config 4: fp16 storage, one
         fp16 product per fp32 product, fp32 accumulation).  range_fallback: on a RangeError of an fp16 arithmetic, reopen
         with "bf16x6" and repeat the call (never silently clamped audio).
+        output_rate: None (the voice's own rate) or the sample rate in Hz every result is delivered at, resampled on the device
+        (set_output_rate; vitsmi.h, "output rate").
         pinned_results: run() / synthesize_batch() return arrays that VIEW page-locked host memory (the DMA engine's
         target; recycled when the array is garbage-collected).  An application that keeps many results alive thereby pins
         that much host RAM: pass False to get ordinary pageable arrays (one extra host copy per call).
@@ -271,6 +296,10 @@ class MiSession:
         if tails not in (None, "zero", "reference"):
             raise SessionError(f"tails must be None, 'zero' or 'reference' (got {tails!r})")
         self.tails = tails
+        if output_rate is not None and (not isinstance(output_rate, (int, np.integer)) or output_rate <= 0):
+            raise SessionError(f"output_rate must be None or a positive integer (got {output_rate!r})")
+        self.output_rate = None if output_rate is None else int(output_rate)
+        self.input_rate = None   # (None: the file's sample_rate metadata)
         self._seed = 0
         self.range_fallbacks = 0  # times this session reopened itself with bf16x6 after a RangeError (stats())
         self._open(gen_precision)
@@ -292,6 +321,12 @@ class MiSession:
         self.gen_precision = gen_precision
         if self.tails is not None:
             self._lib.vits_set_tails(self._h, 1 if self.tails == "reference" else 0)
+        if self.output_rate is not None:
+            rc = self._lib.vits_set_output_rate(self._h, self.input_rate or 0, self.output_rate)
+            if rc != 0:
+                msg = self._err()
+                self.close()
+                raise SessionError(f"vits_set_output_rate({self.input_rate}, {self.output_rate}) failed [{rc}]: {msg}")
         n = self._lib.vits_num_inputs(self._h)
         self._input_names = [self._lib.vits_input_name(self._h, i).decode() for i in range(n)]
 
@@ -415,6 +450,8 @@ class MiSession:
     def synthesize_batch(self, ids, lens, scales, sid=None, noise_dp=None, noise_z=None, taps=(), seeds=None,
                          durations=None, token_rate=None, return_durations=False):
         """One batched run.  Returns {"output": [B,1,1,S] float32, "y_lengths": int64 [B], taps...}.
+        With an output rate set (set_output_rate) "output" is the resampled waveform [B,1,1,S_out] and "sample_lengths"
+        (int64 [B]) holds each row's valid samples at that rate; "y_lengths" stay frames.
         noise_dp [B,2,T] / noise_z [B,inter,>=F] inject the graph's noise for parity runs.
         scales: float32 [3] for every utterance, or [B, 3] - utterance b's own [noise_scale, length_scale, noise_w];
         seeds: None (the session's stream, set_seed) or B integers - utterance b's own noise stream, which does not
@@ -454,7 +491,8 @@ class MiSession:
                 self._begin(ids, lens, scales, sid, noise, seeds, durations, token_rate)
                 ylen = self.last_y_lengths()
                 dur = self.last_durations() if return_durations else None
-                S = int(ylen.max()) * self.hparam("hop")
+                counts = self.last_sample_counts() if self.resampling else None
+                S = int(ylen.max()) * self.hparam("hop") if counts is None else int(counts.max())
                 audio = _POOL.array((B, 1, 1, S)) if self.pinned_results else np.empty((B, 1, 1, S), np.float32)
                 self._fetch(audio, 0, B)
             except RangeError as exc:
@@ -462,6 +500,8 @@ class MiSession:
                 return self.synthesize_batch(ids, lens, scales, sid, noise_dp, noise_z, taps, seeds=seeds,
                                              durations=durations, token_rate=token_rate, return_durations=return_durations)
             res = {"output": audio, "y_lengths": ylen}
+            if counts is not None:
+                res["sample_lengths"] = counts
             if return_durations:
                 res["durations"] = dur
             for t in taps:
@@ -670,6 +710,39 @@ class MiSession:
             self.tails = tails
             self._lib.vits_set_tails(self._h, 1 if tails == "reference" else 0)
 
+    def set_output_rate(self, rate: Optional[int], input_rate: Optional[int] = None):
+        """Deliver the following runs' audio at `rate` Hz, resampled on the device (vitsmi.h, "output rate"): batch results,
+        device PCM and stream chunks alike.  None switches it off; `input_rate` None means the file's sample_rate metadata
+        (22050 without it).  A rate equal to the input rate is the native path, bit for bit.  Kept across a bf16x6 fallback."""
+        if rate is not None and (not isinstance(rate, (int, np.integer)) or rate <= 0):
+            raise SessionError(f"output rate must be None or a positive integer (got {rate!r})")
+        if input_rate is not None and (not isinstance(input_rate, (int, np.integer)) or input_rate <= 0):
+            raise SessionError(f"input rate must be None or a positive integer (got {input_rate!r})")
+        with self._locked():
+            rc = self._lib.vits_set_output_rate(self._h, int(input_rate or 0), int(rate or 0))
+            if rc != 0:
+                self._raise("vits_set_output_rate", rc)
+            self.output_rate = None if rate is None else int(rate)
+            self.input_rate = None if input_rate is None else int(input_rate)
+
+    @property
+    def resampling(self) -> bool:
+        """An output rate is set and differs from the input rate: results are resampled."""
+        if self.output_rate is None:
+            return False
+        fi = self.input_rate or int(self.meta("sample_rate") or 22050)
+        return fi != self.output_rate
+
+    def last_sample_counts(self) -> np.ndarray:
+        """int64 [B]: the valid samples of each row of the last run at the current output rate (y_lengths * hop with the
+        rate off).  From host state like last_y_lengths(): no wait, and a stream's consumer may call it."""
+        with self._locked(read_only=True):
+            n = self._lib.vits_last_sample_counts(self._h, None, 0)
+            buf = np.zeros(max(n, 0), np.int64)
+            if n > 0:
+                self._lib.vits_last_sample_counts(self._h, buf.ctypes.data_as(C.POINTER(C.c_int64)), n)
+            return buf
+
     def reserve(self, batch: int, tokens: int = 0, frames: int = 0):
         """Size the device workspaces now for requests of up to `batch` utterances x `tokens` ids rendering up to `frames`
         frames each (vits_reserve): a serving process calls this once at start-up with the largest request it admits, so that
@@ -782,7 +855,8 @@ class MiSession:
     def synthesize_batch_pcm16(self, ids, lens, scales, sid=None, normalize: bool = True, volume: float = 1.0):
         """One batched run whose result leaves the GPU as 16-bit PCM only: peak-normalise / volume / clip / int16
         happen on the device (bit-identical to TTSVoice._postprocess + AudioChunk), the fp32 waveform is never
-        copied to the host.  Returns (pcm int16 [B, S], y_lengths int64 [B])."""
+        copied to the host.  Returns (pcm int16 [B, S], y_lengths int64 [B]); with an output rate set (set_output_rate)
+        (pcm int16 [B, S_out] of the resampled waveform, sample_lengths int64 [B])."""
         ids = np.ascontiguousarray(ids, np.int64)
         lens = np.ascontiguousarray(lens, np.int64)
         scales = np.ascontiguousarray(scales, np.float32)
@@ -798,6 +872,9 @@ class MiSession:
                                     C.byref(noise), None)
             if rc != 0:
                 raise SessionError(f"vits_run failed [{rc}]: {self._err()}")
+            if self.resampling:
+                counts = self.last_sample_counts()
+                return self.last_pcm16(normalize, volume, shape=(B, int(counts.max()))), counts
             ylen = self.last_y_lengths()
             S = int(ylen.max()) * self.hparam("hop")
             return self.last_pcm16(normalize, volume, shape=(B, S)), ylen
@@ -820,6 +897,9 @@ class PipelinedSession:
     def __init__(self, first: MiSession, parts: int = 2):
         if parts < 1:
             raise SessionError("parts must be >= 1")
+        if getattr(first, "output_rate", None) is not None:
+            raise SessionError("PipelinedSession runs the device-pointer entries, which do not resample: the session has an "
+                               f"output rate set ({first.output_rate} Hz); call set_output_rate(None) first")
         self.parts = [first]
         # `first` owns the weight arena the other handles borrow: it must never close and reopen itself under them
         # (MiSession's own fallback would free the arena while the borrowers run on it).  The fallback happens HERE,
@@ -1302,3 +1382,41 @@ def test_attention(qkv, n_heads, rel_k, rel_v, lens, device_id=0):
     if rc != 0:
         raise SessionError(_ffi.last_error(None))
     return out
+
+
+def _resample_test_args(x, lens, in_rate, out_rate):
+    x = np.ascontiguousarray(x, np.float32)
+    lens = np.ascontiguousarray(lens, np.int64)
+    if x.ndim != 2 or lens.shape != (x.shape[0],):
+        raise SessionError(f"x must be [B, S] and lens [B], got {x.shape} / {lens.shape}")
+    L, M, _ = resample_plan(in_rate, out_rate)
+    return x, lens, L, M
+
+
+def test_resample(x, lens, in_rate, out_rate, device_id=0):
+    """The output-rate resampler by value (vits_test_resample): x float32 [B, S], lens [B] valid samples per row ->
+    (y float32 [B, S_out], counts int64 [B]) with counts = ceil(lens * L / M) and S_out = max(1, counts.max())."""
+    x, lens, L, M = _resample_test_args(x, lens, in_rate, out_rate)
+    B, S = x.shape
+    counts = -(-np.clip(lens, 0, S) * L // M)
+    y = np.full((B, max(1, int(counts.max()))), np.nan, np.float32)
+    rc = _ffi.load().vits_test_resample(device_id, _ffi.ptr(x), _ffi.ptr(lens), B, S, int(in_rate), int(out_rate), _ffi.ptr(y),
+                                        y.shape[1])
+    if rc != 0:
+        raise SessionError(f"vits_test_resample failed [{rc}]: {_ffi.last_error(None)}")
+    return y, counts
+
+
+def test_resample_pieces(x, lens, in_rate, out_rate, piece_samples, device_id=0):
+    """The same input through the chunked entry, `piece_samples` input samples at a time (vits_test_resample_pieces):
+    (y float32 [B, ceil(S * L / M)], [(first_sample, n_samples) of every delivery])."""
+    x, lens, L, M = _resample_test_args(x, lens, in_rate, out_rate)
+    B, S = x.shape
+    y = np.full((B, -(-S * L // M)), np.nan, np.float32)
+    max_ranges = -(-S // int(piece_samples)) + 1
+    ranges = np.zeros((max_ranges, 2), np.int64)
+    n = _ffi.load().vits_test_resample_pieces(device_id, _ffi.ptr(x), _ffi.ptr(lens), B, S, int(in_rate), int(out_rate),
+                                              int(piece_samples), _ffi.ptr(y), y.shape[1], _ffi.ptr(ranges), max_ranges)
+    if n < 0:
+        raise SessionError(f"vits_test_resample_pieces failed [{n}]: {_ffi.last_error(None)}")
+    return y, [(int(a), int(b)) for a, b in ranges[:n]]

@@ -149,6 +149,11 @@ class ShardedSynthesizer:
         self.world = dist.get_world_size() if dist else 1
         self.open_stats = {}
         if session is not None:
+            if getattr(session, "output_rate", None) is not None:
+                from .session import SessionError
+                raise SessionError("ShardedSynthesizer trims and gathers by frames and runs the device-pointer entries, which do "
+                                   f"not resample: the session has an output rate set ({session.output_rate} Hz); call "
+                                   "set_output_rate(None) first")
             self.session, self._arena = session, None
         else:
             self.session, self._arena = open_sharded(path, device_id, dist, force_broadcast=force_broadcast,

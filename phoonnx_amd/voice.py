@@ -120,12 +120,15 @@ class PhonemeAlignment:
 
 
 def build_alignments(groups: Sequence[Tuple[str, Sequence[int]]], durations: Sequence[int], hop: int,
-                     total_frames: Optional[int] = None) -> List[PhonemeAlignment]:
+                     total_frames: Optional[int] = None, ratio: Optional[Tuple[int, int]] = None) -> List[PhonemeAlignment]:
     """(token, [ids]) groups (phonemes_to_id_groups) + the frames each id occupies (`durations`, one per id in group order;
     longer, e.g. a padded batch row, is fine) + the samples per frame -> one PhonemeAlignment per group: cumulative
     starts, num_samples = the group's frames * hop, so that they sum to sum(durations) * hop; a token of zero frames gets
     0 samples.  total_frames: the utterance's frame count where it is known - the engine renders max(1, sum) frames, so
-    an utterance whose durations are all 0 still has one frame of audio, which then goes to the last entry."""
+    an utterance whose durations are all 0 still has one frame of audio, which then goes to the last entry.
+    ratio: (L, M) of an output rate (out / in, reduced; MiSession.set_output_rate) - the chunk's audio then has
+    N = ceil(samples * L / M) samples and a boundary at input sample e lies at output sample min(N, ceil(e * L / M)), so
+    that num_samples still sum to the chunk's length and a token of zero frames still gets 0 samples."""
     out: List[PhonemeAlignment] = []
     pos = frames = 0
     for token, ids in groups:
@@ -136,6 +139,12 @@ def build_alignments(groups: Sequence[Tuple[str, Sequence[int]]], durations: Seq
         frames += n
     if out and total_frames is not None and total_frames > frames:
         out[-1].num_samples += (int(total_frames) - frames) * hop
+    if ratio is not None:
+        L, M = (int(v) for v in ratio)
+        n_total = -(-sum(a.num_samples for a in out) * L // M)
+        for a in out:
+            lo, hi = (min(n_total, -(-e * L // M)) for e in (a.start_sample, a.start_sample + a.num_samples))
+            a.start_sample, a.num_samples = lo, hi - lo
     return out
 
 
@@ -171,8 +180,15 @@ class TTSVoice:
     phonetic_spellings: Optional[Any] = None
     phonemizer: Optional[Any] = None
     dedupe_sentences: bool = False  # False = reference behaviour (every sentence list is doubled)
+    # extension: deliver audio at this rate instead of config.sample_rate, resampled on the device by the session
+    output_sample_rate: Optional[int] = None
 
     def __post_init__(self):
+        if self.output_sample_rate is not None:
+            if not hasattr(self.session, "set_output_rate"):
+                raise ValueError("output_sample_rate needs a session that resamples on the device (MiSession.set_output_rate); "
+                                 f"{type(self.session).__name__} has none")
+            self.session.set_output_rate(int(self.output_sample_rate), int(self.config.sample_rate))
         if self.phonemizer is None:
             self.phonemizer = get_phonemizer(self.config.phoneme_type, self.config.alphabet,
                                              self.config.phonemizer_model)
@@ -182,17 +198,25 @@ class TTSVoice:
     def load(model_path: Union[str, Path], config_path: Optional[Union[str, Path]] = None,
              phonemes_txt: Optional[str] = None, phoneme_map: Optional[str] = None, lang_code: Optional[str] = None,
              phoneme_type_str: Optional[str] = None, use_cuda: bool = False, device_id: int = 0,
-             phonemizer: Optional[Any] = None, strict: bool = True) -> "TTSVoice":
+             phonemizer: Optional[Any] = None, strict: bool = True, output_sample_rate: Optional[int] = None,
+             session: Optional[Any] = None) -> "TTSVoice":
         """Load a voice: `<model>.onnx` + `<model>.onnx.json` (voice.py:125-172).  `use_cuda` is
         accepted for signature compatibility; the engine always runs on the MI355X `device_id`.
-        strict (extension): raise ValueError when JSON, .onnx metadata and graph disagree (check_consistency)."""
+        strict (extension): raise ValueError when JSON, .onnx metadata and graph disagree (check_consistency).
+        output_sample_rate (extension): deliver every chunk, WAV header included, at this rate: the session resamples on the
+        device from config.sample_rate (MiSession.set_output_rate); ValueError with a session that cannot.
+        session (extension): an already opened session to use instead of opening `model_path`."""
         import os
         from .session import MiSession
         if config_path is None:
             config_path = f"{model_path}.json"
             LOG.debug("Guessing voice config path: %s", config_path)
-        session = MiSession(str(model_path), sess_options=None, providers=["MI355XExecutionProvider"],
-                            device_id=device_id)
+        if output_sample_rate is not None and session is not None and not hasattr(session, "set_output_rate"):
+            raise ValueError("output_sample_rate needs a session that resamples on the device (MiSession.set_output_rate); "
+                             f"{type(session).__name__} has none")
+        if session is None:
+            session = MiSession(str(model_path), sess_options=None, providers=["MI355XExecutionProvider"],
+                                device_id=device_id)
         if os.path.exists(config_path):
             with open(config_path, "r", encoding="utf-8") as fh:
                 config_dict = json.load(fh)
@@ -200,7 +224,7 @@ class TTSVoice:
             # extension: no JSON next to the model -> rebuild the config from the
             # metadata_props export_onnx.py:335-350 wrote into the .onnx itself
             config_dict = config_from_metadata(session.get_modelmeta().custom_metadata_map)
-        if strict:
+        if strict and hasattr(session, "hparam"):
             try:
                 check_consistency(config_dict, session.get_modelmeta().custom_metadata_map,
                                   session.hparam("n_speakers"), session.hparam("n_vocab"))
@@ -209,7 +233,26 @@ class TTSVoice:
                 raise
         config = VoiceConfig.from_dict(config_dict, phonemes_txt=phonemes_txt, lang_code=lang_code,
                                        phoneme_type_str=phoneme_type_str)
-        return TTSVoice(session=session, config=config, phonemizer=phonemizer)
+        return TTSVoice(session=session, config=config, phonemizer=phonemizer, output_sample_rate=output_sample_rate)
+
+    @property
+    def sample_rate(self) -> int:
+        """The rate of the audio this voice hands out: output_sample_rate, or the voice's own."""
+        return int(self.output_sample_rate) if self.output_sample_rate is not None else self.config.sample_rate
+
+    def _ratio(self) -> Optional[Tuple[int, int]]:
+        """(L, M) = output rate / voice rate, reduced; None when the audio is not resampled."""
+        import math
+        fi, fo = int(self.config.sample_rate), self.sample_rate
+        if fi == fo:
+            return None
+        g = math.gcd(fi, fo)
+        return fo // g, fi // g
+
+    @staticmethod
+    def _valid_samples(out, hop) -> np.ndarray:
+        """Valid samples per row of a synthesize_batch result: "sample_lengths" (an output rate is set), else frames * hop."""
+        return np.asarray(out["sample_lengths"] if "sample_lengths" in out else np.asarray(out["y_lengths"]) * hop, np.int64)
 
     # ------------------------------------------------------------------ text -> phonemes -> ids
     def phonemize(self, text: str) -> List[List[str]]:
@@ -284,7 +327,7 @@ class TTSVoice:
         else:
             audios = (self.phoneme_ids_to_audio(ids, syn_config) for ids in all_ids)
         for audio in audios:
-            yield AudioChunk(sample_rate=self.config.sample_rate, sample_width=2, sample_channels=1,
+            yield AudioChunk(sample_rate=self.sample_rate, sample_width=2, sample_channels=1,
                              audio_float_array=self._postprocess(audio, syn_config))
 
     def _synthesize_aligned(self, text: str, syn_config: SynthesisConfig, batch_sentences: bool) -> Iterable[AudioChunk]:
@@ -298,10 +341,13 @@ class TTSVoice:
             # (a batch of one is what session.run issues, voice.py:374; the durations come back with the same call)
             rows = ((a[0], d[0]) for a, d in (self.phoneme_ids_batch_to_audio([ids], syn_config, return_durations=True)
                                               for ids in all_ids))
+        ratio = self._ratio()
         for groups, (audio, dur) in zip(all_groups, rows):
-            yield AudioChunk(sample_rate=self.config.sample_rate, sample_width=2, sample_channels=1,
+            # (the engine renders max(1, sum of durations) frames; natively that is the chunk's length in frames)
+            frames = len(audio) // hop if ratio is None else max(1, int(np.sum(dur)))
+            yield AudioChunk(sample_rate=self.sample_rate, sample_width=2, sample_channels=1,
                              audio_float_array=self._postprocess(audio, syn_config),
-                             phoneme_alignments=build_alignments(groups, dur, hop, total_frames=len(audio) // hop))
+                             phoneme_alignments=build_alignments(groups, dur, hop, total_frames=frames, ratio=ratio))
 
     def _sentence_phonemes(self, text: str, syn_config: SynthesisConfig) -> List[List[str]]:
         """synthesize()'s front end up to the phonemes: phonetic spellings, diacritics, phonemize."""
@@ -375,14 +421,15 @@ class TTSVoice:
             else:
                 row_seeds = np.asarray([sentence_seed(seeds[r], k) for r, k, _ in run], np.uint64)
                 out = self.session.synthesize_batch(ids, lens, scales, sid, seeds=row_seeds, **more)
+            valid = self._valid_samples(out, hop)
             for b, (r, k, _) in enumerate(run):
-                audio[r, k] = out["output"][b, 0, 0, :int(out["y_lengths"][b]) * hop].copy()
+                audio[r, k] = out["output"][b, 0, 0, :int(valid[b])].copy()
                 if want_dur:
                     aligned[r, k] = build_alignments(groups[r, k], out["durations"][b], hop,
-                                                     total_frames=int(out["y_lengths"][b]))
+                                                     total_frames=int(out["y_lengths"][b]), ratio=self._ratio())
         result = [[] for _ in requests]
         for r, k, _ in rows:  # (rows are in request, then sentence order)
-            result[r].append(AudioChunk(sample_rate=self.config.sample_rate, sample_width=2, sample_channels=1,
+            result[r].append(AudioChunk(sample_rate=self.sample_rate, sample_width=2, sample_channels=1,
                                         audio_float_array=self._postprocess(audio[r, k], cfgs[r]),
                                         phoneme_alignments=aligned.get((r, k))))
         return result
@@ -395,7 +442,7 @@ class TTSVoice:
         if device_pcm16 and hasattr(self.session, "synthesize_batch_pcm16"):
             return self._synthesize_wav_device_pcm16(text, wav_file, syn_config or SynthesisConfig(), set_wav_format)
         sentence_silence = 0.0  # seconds of silence after each sentence (fixed in the reference)
-        silence = bytes(int(self.config.sample_rate * sentence_silence * 2))
+        silence = bytes(int(self.sample_rate * sentence_silence * 2))
         first = True
         for chunk in self.synthesize(text, syn_config=syn_config, batch_sentences=batch_sentences):
             if first:
@@ -421,7 +468,7 @@ class TTSVoice:
         all_ids = [self.phonemes_to_ids(p) for p in self.phonemize(text) if p]
         all_ids = [ids for ids in all_ids if ids]
         if set_wav_format:
-            wav_file.setframerate(self.config.sample_rate)
+            wav_file.setframerate(self.sample_rate)
             wav_file.setsampwidth(2)
             wav_file.setnchannels(1)
         if not all_ids:
@@ -431,7 +478,8 @@ class TTSVoice:
         sid = np.full((len(all_ids),), syn_config.speaker_id or 0, np.int64) if "sid" in expected else None
         pcm, ylen = self.session.synthesize_batch_pcm16(ids, lens, self._scales(syn_config), sid,
                                                         normalize=syn_config.normalize_audio, volume=syn_config.volume)
-        hop = self.session.hparam("hop")
+        # (with an output rate set the second value already counts samples at that rate: MiSession.synthesize_batch_pcm16)
+        hop = 1 if self._ratio() is not None else self.session.hparam("hop")
         for b in range(len(all_ids)):
             wav_file.writeframes(pcm[b, :int(ylen[b]) * hop].tobytes())
 
@@ -488,7 +536,8 @@ class TTSVoice:
             more["return_durations"] = True
         out = self.session.synthesize_batch(ids, lens, self._scales(syn_config), sid, **more)
         hop = self.session.hparam("hop")
-        audios = [out["output"][b, 0, 0, :int(out["y_lengths"][b]) * hop].copy() for b in range(len(batch_ids))]
+        valid = self._valid_samples(out, hop)
+        audios = [out["output"][b, 0, 0, :int(valid[b])].copy() for b in range(len(batch_ids))]
         if return_durations:
             return audios, [out["durations"][b, :len(i)].copy() for b, i in enumerate(batch_ids)]
         return audios
