@@ -502,6 +502,31 @@ int vits_test_resample(int device_id, const float *x, const int64_t *lens, int B
 int vits_test_resample_pieces(int device_id, const float *x, const int64_t *lens, int B, int S, int in_rate, int out_rate,
                               int piece_samples, float *y, int64_t S_out, int64_t *ranges, int max_ranges);
 
+/* The kernels that turn tokens into frames and frames into samples, by value.  Every hook checks its sizes and extents on the
+ * host (VITS_E_ARG) and launches the pipeline's kernel with the pipeline's grid.
+ * Durations: logw [B][T] (the free form: w_ceil = ceil(exp(logw) * mask * length_scale [* token_rate]), length_scale the
+ * utterance's column 1 of rows [B][3] when rows is given) or dur int64 [B][T] (the forced form), exactly one of them;
+ * lens [B] within [0, T].  Out: w_ceil [B][T], cum int32 [B][T] (inclusive running sum), y_len int32 [B] (max(sum, 1)). */
+int vits_test_durations(int device_id, const float *logw, const int64_t *dur, const int64_t *lens, int B, int T, float length_scale,
+                        const float *rows, const float *token_rate, float *w_ceil, int32_t *cum, int32_t *y_len);
+/* Length regulator and prior sample: m_logs [B][2C][T] (m_p in the first C channels, logs_p in the second), cum / y_len as
+ * vits_test_durations leaves them (y_len[b] <= F), noise (nullable) [B][C][noise_stride] of which the first noise_frames
+ * <= noise_stride frames are read (zeros behind), else seeds (nullable) uint64 [B]: stream 2 of each utterance; noise_scale
+ * or column 0 of rows [B][3].  Out: z_p [B][C][F]. */
+int vits_test_expand_prior(int device_id, const float *m_logs, int B, int C, int T, const int32_t *cum, const int64_t *lens,
+                           const int32_t *y_len, int F, const float *noise, int64_t noise_stride, int noise_frames,
+                           float noise_scale, const float *rows, const uint64_t *seeds, float *z_p);
+/* The flat noise stream (out [n]) and the per-utterance one (out [B][channels][T] = stream `stream` of seeds[b] times
+ * rows[b][col], +0.0 where that is 0). */
+int vits_test_fill_normal(int device_id, int64_t n, uint64_t seed, uint64_t stream_id, float *out);
+int vits_test_fill_normal_rows(int device_id, int B, int channels, int T, const uint64_t *seeds, uint32_t stream, const float *rows,
+                               int col, float *out);
+/* The vocoder's tail, out [B][T] = tanh(conv_post(leaky_relu(x, slope))) with w [C][K], zeros at and behind vlen[b] * hop
+ * (vlen nullable).  kernel 0: x planar [B][C][T]; 1: x in the raw layout [B][C/8][T][8], the 7-tap instantiation when K == 7;
+ * 2: the same layout, always the generic instantiation.  C % 8 == 0 for 1 and 2; the staged tile must fit 64 KiB of LDS. */
+int vits_test_post_conv(int device_id, const float *x, int B, int C, int T, const float *w, int K, float slope, const int64_t *vlen,
+                        int hop, int kernel, float *out);
+
 #ifdef __cplusplus
 }
 #endif

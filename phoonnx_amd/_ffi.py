@@ -63,6 +63,7 @@ EXPORTS = [
     "vits_launch_records", "vits_run_async_rows", "vits_run_device_rows", "vits_run_chunked_rows",
     "vits_run_async_ctl", "vits_run_chunked_ctl", "vits_last_durations",
     "vits_set_output_rate", "vits_last_sample_counts", "vits_resample_plan", "vits_test_resample", "vits_test_resample_pieces",
+    "vits_test_durations", "vits_test_expand_prior", "vits_test_fill_normal", "vits_test_fill_normal_rows", "vits_test_post_conv",
 ]
 
 
@@ -133,6 +134,12 @@ def load():
     lib.vits_resample_plan.argtypes = [C.c_int, C.c_int, i64p, i64p, i64p, vp, C.c_size_t]
     lib.vits_test_resample.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int64]
     lib.vits_test_resample_pieces.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int64, vp, C.c_int]
+    lib.vits_test_durations.argtypes = [C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp, vp]
+    lib.vits_test_expand_prior.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int64, C.c_int,
+                                           C.c_float, vp, vp, vp]
+    lib.vits_test_fill_normal.argtypes = [C.c_int, C.c_int64, C.c_uint64, C.c_uint64, vp]
+    lib.vits_test_fill_normal_rows.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_uint32, vp, C.c_int, vp]
+    lib.vits_test_post_conv.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_float, vp, C.c_int, C.c_int, vp]
     lib.vits_free_output.argtypes = [vp, C.POINTER(VitsOutput)]
     lib.vits_free_output.restype = None
     lib.vits_sync.argtypes = [vp]

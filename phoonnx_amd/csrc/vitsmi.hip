@@ -650,6 +650,54 @@ hipError_t launch_attention16(hipStream_t st, int B, int T, int n_heads, int dk,
     return ns == 3 ? launch_attention16_t<3, 3, 1>(st, a) : launch_attention16_t<3, 2, 1>(st, a);
 }
 
+// The token-to-frame and frame-to-sample kernels (kernels.hip.hpp), one launch each.  The pipeline and the kernel-level test
+// hooks (vits_test_durations ...) both launch through these, so each kernel's grid is stated once.
+void launch_durations(hipStream_t st, int B, int T, const float *logw, const int *len, float length_scale, const float *rows,
+                      const float *token_rate, float *w_ceil, int *cum, int *y_len) {
+    duration_kernel<<<B, 256, 0, st>>>(logw, len, length_scale, rows, token_rate, w_ceil, cum, y_len, T);
+}
+
+void launch_forced_durations(hipStream_t st, int B, int T, const int64_t *dur, const int *len, float *w_ceil, int *cum, int *y_len) {
+    forced_duration_kernel<<<B, 256, 0, st>>>(dur, len, w_ceil, cum, y_len, T);
+}
+
+// out [B][channels][T] = the utterances' own stream `stream` times column `col` of rows
+void launch_fill_normal_rows(hipStream_t st, int B, int channels, int T, float *out, const uint64_t *seeds, uint32_t stream,
+                             const float *rows, int col) {
+    fill_normal_rows_kernel<<<dim3((unsigned)(((T + 3) / 4 + 63) / 64), channels, B), 64, 0, st>>>(out, T, seeds, stream, rows, col);
+}
+
+void launch_fill_normal(hipStream_t st, float *out, int64_t n, uint64_t seed, uint64_t stream_id) {
+    fill_normal_kernel<<<(unsigned)((n / 4 + 256) / 256), 256, 0, st>>>(out, n, seed, stream_id);
+}
+
+void launch_expand_prior(hipStream_t st, int B, int C, int T, int F, const float *m_p, const float *logs_p, int64_t bstride,
+                         const int *cum, const int *len, const int *y_len, const float *noise, int64_t noise_stride,
+                         float noise_scale, const float *rows, const uint64_t *seeds, float *z_p, int Fnoise) {
+    expand_prior_strided_kernel<<<dim3((F + 255) / 256, (C + 3) / 4, B), 64, 0, st>>>(m_p, logs_p, bstride, cum, len, y_len, noise,
+                                                                                     noise_stride, noise_scale, rows, seeds, z_p, C,
+                                                                                     T, F, Fnoise);
+}
+
+// the vocoder's tail on the planar layout (the f32 generator) ...
+size_t post_conv_lds(int C, int K) { return ((size_t)C * (256 + K - 1) + (size_t)C * K) * sizeof(float); }
+void launch_post_conv(hipStream_t st, int B, int C, int K, int T, const float *x, const float *w, float *out, float slope,
+                      const int *vlen, int hop) {
+    const size_t lds = post_conv_lds(C, K);
+    post_conv_tanh_kernel<<<dim3((T + 255) / 256, B), 256, lds, st>>>(x, w, out, C, K, T, slope, vlen, hop);
+}
+
+// ... and on the fp32 raw layout [C/8][T][8] of the split-operand walkers (generic: the runtime tap count even for K = 7)
+size_t post_conv_blocked_lds(int C, int K) { return (size_t)C * (256 + K - 1) * sizeof(float); }
+void launch_post_conv_blocked(hipStream_t st, int B, int C, int K, int T, const float *x, const float *w, float *out, float slope,
+                              const int *vlen, int hop, bool generic = false) {
+    const size_t lds = post_conv_blocked_lds(C, K);
+    if (K == 7 && !generic)
+        post_conv_tanh_blocked_kernel<7><<<dim3((T + 255) / 256, B), 256, lds, st>>>(x, w, out, C, K, T, slope, vlen, hop);
+    else
+        post_conv_tanh_blocked_kernel<0><<<dim3((T + 255) / 256, B), 256, lds, st>>>(x, w, out, C, K, T, slope, vlen, hop);
+}
+
 // A token- / frame-domain conv on the split-operand engine with the planar epilogue (SX_WN_RMW): x_pl = fp16 operand planes
 // of the input; out (may be nullptr when out_pl is given) = planar fp32 [B][Cout][T]; out_pl = operand planes of the output
 // for the next conv; flags = EPI_RELU | EPI_MASK | EPI_ACC | EPI_RES; of the options o.len (the masks) and o.res (planar, the
@@ -1251,10 +1299,9 @@ int run_tokens(vits_handle *h, const int64_t *d_ids, const int64_t *d_lens, int 
         } else if (d_noise_dp) {
             scale_kernel<<<(unsigned)((nz + 255) / 256), 256, 0, st>>>(d_noise_dp, z, noise_w, rr.d_rows, 2, 2 * T, nz);
         } else if (rr.d_seeds) {
-            fill_normal_rows_kernel<<<dim3((unsigned)(((T + 3) / 4 + 63) / 64), 2, B), 64, 0, st>>>(z, T, rr.d_seeds, 1u,
-                                                                                                rr.d_rows, 2);
+            launch_fill_normal_rows(st, B, 2, T, z, rr.d_seeds, 1u, rr.d_rows, 2);
         } else {
-            fill_normal_kernel<<<(unsigned)((nz / 4 + 256) / 256), 256, 0, st>>>(z, nz, seed, 1);
+            launch_fill_normal(st, z, nz, seed, 1);
             scale_kernel<<<(unsigned)((nz + 255) / 256), 256, 0, st>>>(z, z, noise_w, rr.d_rows, 2, 2 * T, nz);
         }
         h->stats.total_launches += 2;
@@ -1300,10 +1347,9 @@ int run_tokens(vits_handle *h, const int64_t *d_ids, const int64_t *d_lens, int 
     }
     // ---- durations (models.py:702-704)
     if (forced)
-        forced_duration_kernel<<<B, 256, 0, st>>>(rr.d_durations, len, h->d_wceil, h->d_cum, h->d_ylen, T);
+        launch_forced_durations(st, B, T, rr.d_durations, len, h->d_wceil, h->d_cum, h->d_ylen);
     else
-        duration_kernel<<<B, 256, 0, st>>>(h->d_logw, len, rr.at(0, 1), rr.d_rows, rr.d_token_rate, h->d_wceil, h->d_cum,
-                                           h->d_ylen, T);
+        launch_durations(st, B, T, h->d_logw, len, rr.at(0, 1), rr.d_rows, rr.d_token_rate, h->d_wceil, h->d_cum, h->d_ylen);
     h->stats.total_launches++;
     c.note(hipGetLastError());
     if (c.err != hipSuccess) return fail(h, VITS_E_DEVICE, "kernel launch failed: %s", hipGetErrorString(c.err));
@@ -1397,13 +1443,7 @@ void conv_post_sx(vits_handle *h, Ctx &c, const float *x, const int *ylen, int B
     hipStream_t st = h->stream;
     h->S = T;
     h->d_out = out;
-    const size_t lds = (size_t)m.post_cin * (256 + m.post_k - 1) * sizeof(float);
-    if (m.post_k == 7)
-        post_conv_tanh_blocked_kernel<7><<<dim3((T + 255) / 256, B), 256, lds, st>>>(x, c.P(m.post_w), h->d_out, m.post_cin,
-                                                                                    m.post_k, T, 0.01f, tail_len(h, ylen), T / F);
-    else
-        post_conv_tanh_blocked_kernel<0><<<dim3((T + 255) / 256, B), 256, lds, st>>>(x, c.P(m.post_w), h->d_out, m.post_cin,
-                                                                                    m.post_k, T, 0.01f, tail_len(h, ylen), T / F);
+    launch_post_conv_blocked(st, B, m.post_cin, m.post_k, T, x, c.P(m.post_w), h->d_out, 0.01f, tail_len(h, ylen), T / F);
     conv_post_account(h, c, B, T);
 }
 
@@ -1717,9 +1757,7 @@ void run_generator_f32(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride
     // conv_post; tanh (models.py:364-366): the leaky_relu(0.01) of models.py:364 was applied by the last stage's epilogue
     h->S = T;
     h->d_out = gb.out;  // (reg[9])
-    const size_t lds = ((size_t)m.post_cin * (256 + m.post_k - 1) + (size_t)m.post_cin * m.post_k) * sizeof(float);
-    post_conv_tanh_kernel<<<dim3((T + 255) / 256, B), 256, lds, st>>>(xa, c.P(m.post_w), h->d_out, m.post_cin, m.post_k,
-                                                                      T, 1.0f, tail_len(h, ylen), T / F);
+    launch_post_conv(st, B, m.post_cin, m.post_k, T, xa, c.P(m.post_w), h->d_out, 1.0f, tail_len(h, ylen), T / F);
     conv_post_account(h, c, B, T);
 }
 
@@ -1969,17 +2007,15 @@ int run_frames(vits_handle *h, int B, int T, const RunRows &rr, const int64_t *d
             nzs = noise_z_stride;
         } else if (!rr.d_seeds) {
             float *g = w.g;
-            fill_normal_kernel<<<(unsigned)((nCF / 4 + 256) / 256), 256, 0, st>>>(g, (int64_t)nCF, seed, 2);
+            launch_fill_normal(st, g, (int64_t)nCF, seed, 2);
             h->stats.total_launches++;
             nz = g;
         }
     }
     // m_p / logs_p are the two halves of the proj output: channel stride T, batch stride 2*C*T
     // (with per-utterance seeds and no injected noise, the kernel draws each utterance's prior noise itself)
-    expand_prior_strided_kernel<<<dim3((F + 255) / 256, (C + 3) / 4, B), 64, 0, st>>>(h->d_mp, h->d_logs, (int64_t)2 * C * T, h->d_cum,
-                                                                        len, ylen, nz, nzs, noise_scale, rr.d_rows,
-                                                                        nz ? nullptr : rr.d_seeds, zp, C, T, F,
-                                                                        nz == d_noise_z ? Freal : F);
+    launch_expand_prior(st, B, C, T, F, h->d_mp, h->d_logs, (int64_t)2 * C * T, h->d_cum, len, ylen, nz, nzs, noise_scale,
+                        rr.d_rows, nz ? nullptr : rr.d_seeds, zp, nz == d_noise_z ? Freal : F);
     h->stats.total_launches++;
     if (c.flow_len) {
         // z = z_p * y_mask: the ragged flow leaves the frames behind an utterance's end alone, where the reference's couplings
@@ -3722,6 +3758,157 @@ int vits_test_resample_pieces(int device_id, const float *x, const int64_t *lens
     }
     TCHECK(hipDeviceSynchronize());
     return calls;
+}
+
+// The token-to-frame and frame-to-sample kernels by value.  Each hook checks on the host whatever a kernel could read or
+// write out of bounds with, then launches through the pipeline's own launch_* function.
+namespace {
+// lens [B] within [0, T], as int for the kernels
+int glue_test_lens(const int64_t *lens, int B, int T, std::vector<int> &l32) {
+    if (!lens || B <= 0 || B > 65535 || T <= 0) return fail(nullptr, VITS_E_ARG, "bad sizes (B=%d, T=%d) or null lens", B, T);
+    l32.resize(B);
+    for (int b = 0; b < B; b++) {
+        if (lens[b] < 0 || lens[b] > T) return fail(nullptr, VITS_E_ARG, "lens[%d]=%lld outside [0,%d]", b, (long long)lens[b], T);
+        l32[b] = (int)lens[b];
+    }
+    return VITS_OK;
+}
+}  // namespace
+
+int vits_test_durations(int device_id, const float *logw, const int64_t *dur, const int64_t *lens, int B, int T, float length_scale,
+                        const float *rows, const float *token_rate, float *w_ceil, int32_t *cum, int32_t *y_len) {
+    if (int rc = test_dev(device_id)) return rc;
+    std::vector<int> l32;
+    if (int rc = glue_test_lens(lens, B, T, l32)) return rc;
+    if (!w_ceil || !cum || !y_len || (logw != nullptr) == (dur != nullptr))
+        return fail(nullptr, VITS_E_ARG, "one of logw and dur, and three outputs, are needed");
+    if (dur && token_rate) return fail(nullptr, VITS_E_ARG, "forced durations leave nothing to scale");
+    if (dur)
+        for (int b = 0; b < B; b++) {
+            int64_t sum = 0;
+            for (int t = 0; t < l32[b]; t++) {
+                const int64_t d = dur[(size_t)b * T + t];
+                if (d < 0 || d > VITS_MAX_FORCED_FRAMES || (sum += d) > VITS_MAX_FORCED_FRAMES)
+                    return fail(nullptr, VITS_E_ARG, "dur[%d,%d]=%lld is negative or passes %d frames in its row", b, t, (long long)d,
+                                VITS_MAX_FORCED_FRAMES);
+            }
+        }
+    const size_t nBT = (size_t)B * T;
+    DevBufs D;
+    int *dlen = D.up(l32.data(), (size_t)B);
+    const float *drows = rows ? D.up(rows, (size_t)B * 3) : nullptr;
+    float *dw = D.fill<float>(nBT, 0xff);
+    int *dcum = D.fill<int>(nBT, 0xff), *dyl = D.fill<int>((size_t)B, 0xff);
+    if (dur) {
+        const int64_t *dd = D.up(dur, nBT);
+        TCHECK(D.err);
+        launch_forced_durations(nullptr, B, T, dd, dlen, dw, dcum, dyl);
+    } else {
+        const float *dl = D.up(logw, nBT);
+        const float *dr = token_rate ? D.up(token_rate, nBT) : nullptr;
+        TCHECK(D.err);
+        launch_durations(nullptr, B, T, dl, dlen, length_scale, drows, dr, dw, dcum, dyl);
+    }
+    TCHECK(hipGetLastError());
+    TCHECK(hipDeviceSynchronize());
+    TCHECK(download(w_ceil, dw, nBT));
+    TCHECK(download(cum, dcum, nBT));
+    TCHECK(download(y_len, dyl, (size_t)B));
+    return VITS_OK;
+}
+
+int vits_test_expand_prior(int device_id, const float *m_logs, int B, int C, int T, const int32_t *cum, const int64_t *lens,
+                           const int32_t *y_len, int F, const float *noise, int64_t noise_stride, int noise_frames,
+                           float noise_scale, const float *rows, const uint64_t *seeds, float *z_p) {
+    if (int rc = test_dev(device_id)) return rc;
+    std::vector<int> l32;
+    if (int rc = glue_test_lens(lens, B, T, l32)) return rc;
+    if (!m_logs || !cum || !y_len || !z_p || C <= 0 || (C + 3) / 4 > 65535 || F <= 0)
+        return fail(nullptr, VITS_E_ARG, "bad length-regulator test arguments (C=%d, F=%d)", C, F);
+    if (noise && (noise_frames < 0 || noise_stride < noise_frames))
+        return fail(nullptr, VITS_E_ARG, "noise_frames = %d, the noise rows hold %lld", noise_frames, (long long)noise_stride);
+    for (int b = 0; b < B; b++) {
+        const int32_t *cb = cum + (size_t)b * T;
+        for (int t = 0; t < T; t++)
+            if (cb[t] < (t ? cb[t - 1] : 0)) return fail(nullptr, VITS_E_ARG, "cum[%d,%d]=%d: not a running sum of frame counts", b, t, cb[t]);
+        if (y_len[b] != (cb[T - 1] < 1 ? 1 : cb[T - 1]) || y_len[b] > F)
+            return fail(nullptr, VITS_E_ARG, "y_len[%d]=%d with cum ending at %d and F=%d", b, y_len[b], cb[T - 1], F);
+    }
+    const size_t nBT = (size_t)B * T, nz = (size_t)B * C * F;
+    DevBufs D;
+    const float *dm = D.up(m_logs, nBT * 2 * C);
+    const int *dcum = D.up(cum, nBT), *dlen = D.up(l32.data(), (size_t)B), *dyl = D.up(y_len, (size_t)B);
+    const float *dn = noise ? D.up(noise, (size_t)B * C * noise_stride) : nullptr;
+    const float *drows = rows ? D.up(rows, (size_t)B * 3) : nullptr;
+    const uint64_t *dseeds = !noise && seeds ? D.up(seeds, (size_t)B) : nullptr;
+    float *dz = D.fill<float>(nz, 0xff);
+    TCHECK(D.err);
+    launch_expand_prior(nullptr, B, C, T, F, dm, dm + (size_t)C * T, (int64_t)2 * C * T, dcum, dlen, dyl, dn, noise_stride, noise_scale,
+                        drows, dseeds, dz, noise ? noise_frames : F);
+    TCHECK(hipGetLastError());
+    TCHECK(hipDeviceSynchronize());
+    TCHECK(download(z_p, dz, nz));
+    return VITS_OK;
+}
+
+int vits_test_fill_normal(int device_id, int64_t n, uint64_t seed, uint64_t stream_id, float *out) {
+    if (int rc = test_dev(device_id)) return rc;
+    if (!out || n < 0 || n > ((int64_t)1 << 28)) return fail(nullptr, VITS_E_ARG, "n = %lld outside [0, 2^28] or null output", (long long)n);
+    DevBufs D;
+    float *d = D.fill<float>((size_t)n, 0xff);
+    TCHECK(D.err);
+    launch_fill_normal(nullptr, d, n, seed, stream_id);
+    TCHECK(hipGetLastError());
+    TCHECK(hipDeviceSynchronize());
+    TCHECK(download(out, d, (size_t)n));
+    return VITS_OK;
+}
+
+int vits_test_fill_normal_rows(int device_id, int B, int channels, int T, const uint64_t *seeds, uint32_t stream, const float *rows,
+                               int col, float *out) {
+    if (int rc = test_dev(device_id)) return rc;
+    if (!seeds || !rows || !out || B <= 0 || B > 65535 || channels <= 0 || channels > 65535 || T <= 0 || col < 0 || col > 2)
+        return fail(nullptr, VITS_E_ARG, "bad row-noise test arguments (B=%d, channels=%d, T=%d, col=%d)", B, channels, T, col);
+    const size_t n = (size_t)B * channels * T;
+    DevBufs D;
+    const uint64_t *ds = D.up(seeds, (size_t)B);
+    const float *dr = D.up(rows, (size_t)B * 3);
+    float *d = D.fill<float>(n, 0xff);
+    TCHECK(D.err);
+    launch_fill_normal_rows(nullptr, B, channels, T, d, ds, stream, dr, col);
+    TCHECK(hipGetLastError());
+    TCHECK(hipDeviceSynchronize());
+    TCHECK(download(out, d, n));
+    return VITS_OK;
+}
+
+int vits_test_post_conv(int device_id, const float *x, int B, int C, int T, const float *w, int K, float slope, const int64_t *vlen,
+                        int hop, int kernel, float *out) {
+    if (int rc = test_dev(device_id)) return rc;
+    if (!x || !w || !out || B <= 0 || B > 65535 || C <= 0 || T <= 0 || K <= 0 || K > 4096 || hop < 1 || kernel < 0 || kernel > 2)
+        return fail(nullptr, VITS_E_ARG, "bad vocoder-tail test arguments (B=%d, C=%d, T=%d, K=%d, hop=%d, kernel=%d)", B, C, T, K, hop, kernel);
+    if (kernel != 0 && C % 8) return fail(nullptr, VITS_E_ARG, "the blocked layout holds 8 channels per cell: C=%d", C);
+    const size_t lds = kernel == 0 ? post_conv_lds(C, K) : post_conv_blocked_lds(C, K);
+    if (lds > 64 * 1024) return fail(nullptr, VITS_E_ARG, "C=%d, K=%d need %zu bytes of LDS: more than 64 KiB", C, K, lds);
+    std::vector<int> v32;
+    if (vlen)
+        for (int b = 0; b < B; b++) {
+            if (vlen[b] < 0 || vlen[b] > INT_MAX) return fail(nullptr, VITS_E_ARG, "vlen[%d]=%lld is not a frame count", b, (long long)vlen[b]);
+            v32.push_back((int)vlen[b]);
+        }
+    const size_t nx = (size_t)B * C * T, no = (size_t)B * T;
+    DevBufs D;
+    const float *dx = D.up(x, nx);
+    const float *dw = D.up(w, (size_t)C * K);
+    const int *dv = vlen ? D.up(v32.data(), (size_t)B) : nullptr;
+    float *dout = D.fill<float>(no, 0xff);
+    TCHECK(D.err);
+    if (kernel == 0) launch_post_conv(nullptr, B, C, K, T, dx, dw, dout, slope, dv, hop);
+    else launch_post_conv_blocked(nullptr, B, C, K, T, dx, dw, dout, slope, dv, hop, kernel == 2);
+    TCHECK(hipGetLastError());
+    TCHECK(hipDeviceSynchronize());
+    TCHECK(download(out, dout, no));
+    return VITS_OK;
 }
 
 }  // extern "C"

@@ -1420,3 +1420,132 @@ def test_resample_pieces(x, lens, in_rate, out_rate, piece_samples, device_id=0)
     if n < 0:
         raise SessionError(f"vits_test_resample_pieces failed [{n}]: {_ffi.last_error(None)}")
     return y, [(int(a), int(b)) for a, b in ranges[:n]]
+
+
+# ---- the token-to-frame and frame-to-sample kernels by value (include/vitsmi.h: vits_test_durations ...) ----------------
+
+def _glue_check(rc, name):
+    if rc != 0:
+        raise SessionError(f"{name} failed [{rc}]: {_ffi.last_error(None)}")
+
+
+def _rows3(rows, B):
+    if rows is None:
+        return None
+    rows = np.ascontiguousarray(rows, np.float32)
+    if rows.shape != (B, 3):
+        raise SessionError(f"rows must be [B, 3] = [{B}, 3], got {rows.shape}")
+    return rows
+
+
+def test_durations(logw=None, dur=None, lens=None, length_scale=1.0, rows=None, token_rate=None, device_id=0):
+    """duration_kernel (logw float32 [B, T]) or forced_duration_kernel (dur int64 [B, T]) -> (w_ceil float32 [B, T],
+    cum int32 [B, T], y_len int32 [B]); rows [B, 3] (column 1: length_scale per utterance), token_rate [B, T]."""
+    if (logw is None) == (dur is None):
+        raise SessionError("one of logw and dur is needed")
+    src = np.ascontiguousarray(logw, np.float32) if dur is None else np.ascontiguousarray(dur, np.int64)
+    lens = np.ascontiguousarray(lens, np.int64)
+    if src.ndim != 2 or lens.shape != (src.shape[0],):
+        raise SessionError(f"logw / dur must be [B, T] and lens [B], got {src.shape} / {lens.shape}")
+    B, T = src.shape
+    rows = _rows3(rows, B)
+    if token_rate is not None:
+        token_rate = np.ascontiguousarray(token_rate, np.float32)
+        if token_rate.shape != (B, T):
+            raise SessionError(f"token_rate must be [B, T], got {token_rate.shape}")
+    w_ceil = np.full((B, T), np.nan, np.float32)
+    cum, y_len = np.full((B, T), -1, np.int32), np.full(B, -1, np.int32)
+    rc = _ffi.load().vits_test_durations(device_id, _ffi.ptr(src) if dur is None else None, None if dur is None else _ffi.ptr(src),
+                                         _ffi.ptr(lens), B, T, float(length_scale), _ffi.ptr(rows), _ffi.ptr(token_rate),
+                                         _ffi.ptr(w_ceil), _ffi.ptr(cum), _ffi.ptr(y_len))
+    _glue_check(rc, "vits_test_durations")
+    return w_ceil, cum, y_len
+
+
+def test_expand_prior(m_logs, cum, lens, y_len, F, noise=None, noise_scale=0.667, rows=None, seeds=None, noise_frames=None,
+                      device_id=0):
+    """expand_prior_strided_kernel: m_logs float32 [B, 2C, T] (m_p | logs_p), cum int32 [B, T], lens [B], y_len [B] -> z_p
+    [B, C, F].  noise [B, C, Fn] (Fn < F reads as 0 behind Fn; noise_frames: how many of the Fn the kernel may read, Fn when
+    None), else seeds uint64 [B]; rows [B, 3] (column 0: noise_scale per utterance)."""
+    m_logs = np.ascontiguousarray(m_logs, np.float32)
+    if m_logs.ndim != 3 or m_logs.shape[1] % 2:
+        raise SessionError(f"m_logs must be [B, 2C, T], got {m_logs.shape}")
+    B, C2, T = m_logs.shape
+    Cc = C2 // 2
+    cum = np.ascontiguousarray(cum, np.int32)
+    lens = np.ascontiguousarray(lens, np.int64)
+    y_len = np.ascontiguousarray(y_len, np.int32)
+    if cum.shape != (B, T) or lens.shape != (B,) or y_len.shape != (B,):
+        raise SessionError(f"cum must be [B, T], lens and y_len [B], got {cum.shape} / {lens.shape} / {y_len.shape}")
+    rows = _rows3(rows, B)
+    stride = 0
+    if noise is not None:
+        noise = np.ascontiguousarray(noise, np.float32)
+        if noise.ndim != 3 or noise.shape[:2] != (B, Cc):
+            raise SessionError(f"noise must be [B, C, Fn] = [{B}, {Cc}, Fn], got {noise.shape}")
+        stride = noise.shape[2]
+    if seeds is not None:
+        seeds = np.ascontiguousarray(seeds, np.uint64)
+        if seeds.shape != (B,):
+            raise SessionError(f"seeds must be [B], got {seeds.shape}")
+    F = int(F)
+    z_p = np.full((B, Cc, max(F, 0)), np.nan, np.float32)
+    rc = _ffi.load().vits_test_expand_prior(device_id, _ffi.ptr(m_logs), B, Cc, T, _ffi.ptr(cum), _ffi.ptr(lens), _ffi.ptr(y_len), F,
+                                            _ffi.ptr(noise), stride, int(stride if noise_frames is None else noise_frames),
+                                            float(noise_scale), _ffi.ptr(rows), _ffi.ptr(seeds), _ffi.ptr(z_p))
+    _glue_check(rc, "vits_test_expand_prior")
+    return z_p
+
+
+def test_fill_normal(n, seed, stream_id, device_id=0):
+    """fill_normal_kernel: the flat stream `stream_id` of `seed`, float32 [n]"""
+    n = int(n)
+    out = np.full(max(n, 0), np.nan, np.float32)
+    rc = _ffi.load().vits_test_fill_normal(device_id, n, int(seed), int(stream_id), _ffi.ptr(out))
+    _glue_check(rc, "vits_test_fill_normal")
+    return out
+
+
+def test_fill_normal_rows(T, channels, seeds, stream, rows, col, device_id=0):
+    """fill_normal_rows_kernel: float32 [B, channels, T], utterance b's stream `stream` of seeds[b] times rows[b, col]"""
+    seeds = np.ascontiguousarray(seeds, np.uint64)
+    if seeds.ndim != 1:
+        raise SessionError(f"seeds must be [B], got {seeds.shape}")
+    B = seeds.shape[0]
+    rows = _rows3(rows, B)
+    T, channels = int(T), int(channels)
+    out = np.full((B, max(channels, 0), max(T, 0)), np.nan, np.float32)
+    rc = _ffi.load().vits_test_fill_normal_rows(device_id, B, channels, T, _ffi.ptr(seeds), int(stream), _ffi.ptr(rows), int(col),
+                                                _ffi.ptr(out))
+    _glue_check(rc, "vits_test_fill_normal_rows")
+    return out
+
+
+_POST_CONV_KERNELS = {"planar": 0, "blocked": 1, "blocked_generic": 2}
+
+
+def test_post_conv(x, w, slope, vlen=None, hop=1, kernel="planar", device_id=0):
+    """The vocoder's tail: x float32 [B, C, T], w [C, K] -> out [B, T] = tanh(conv_post(leaky_relu(x, slope))), zeros at and
+    behind vlen[b] * hop.  kernel: "planar" (post_conv_tanh_kernel), "blocked" (post_conv_tanh_blocked_kernel, <7> when
+    K == 7, else <0>) or "blocked_generic" (always <0>); for the blocked ones x is laid out as [C/8][T][8] here."""
+    if kernel not in _POST_CONV_KERNELS:
+        raise SessionError(f"unknown kernel {kernel!r}")
+    x = np.ascontiguousarray(x, np.float32)
+    w = np.ascontiguousarray(w, np.float32)
+    if x.ndim != 3 or w.ndim != 2 or w.shape[0] != x.shape[1]:
+        raise SessionError(f"x must be [B, C, T] and w [C, K], got {x.shape} / {w.shape}")
+    B, Cc, T = x.shape
+    K = w.shape[1]
+    if kernel != "planar":
+        if Cc % 8:
+            raise SessionError(f"the blocked layout holds 8 channels per cell: C={Cc}")
+        x = np.ascontiguousarray(x.reshape(B, Cc // 8, 8, T).transpose(0, 1, 3, 2))
+    if vlen is not None:
+        vlen = np.ascontiguousarray(vlen, np.int64)
+        if vlen.shape != (B,):
+            raise SessionError(f"vlen must be [B], got {vlen.shape}")
+    out = np.full((B, T), np.nan, np.float32)
+    rc = _ffi.load().vits_test_post_conv(device_id, _ffi.ptr(x), B, Cc, T, _ffi.ptr(w), K, float(slope), _ffi.ptr(vlen), int(hop),
+                                         _POST_CONV_KERNELS[kernel], _ffi.ptr(out))
+    _glue_check(rc, "vits_test_post_conv")
+    return out

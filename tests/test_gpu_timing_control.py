@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import ALL_PRESETS, GOLDEN, case_get, golden_cases, zero_tails
+from glue_ref import regulate_ref as _regulate   # (the NumPy length regulator + prior sample)
 
 pytestmark = pytest.mark.gpu
 
@@ -246,23 +247,6 @@ def test_token_rate(preset):
 
 
 # ------------------------------------------------------------------ 4b. dropped tokens (0 frames) in the length regulator
-
-def _regulate(m_p, logs_p, dur, noise, noise_scale, ylen):
-    """NumPy length regulator + prior sample (commons.py:116-129, models.py:711-718) over the run's own m_p / logs_p:
-    z_p[b, c, f] = m_p[b, c, i(f)] + noise[b, c, f] * exp(logs_p[b, c, i(f)]) * noise_scale, i(f) = the token frame f belongs
-    to under `dur`; an utterance without any frame has the one masked frame the graph gives it (m = 0, logs = 0)."""
-    B, C, T = m_p.shape
-    out = np.zeros((B, C, int(ylen.max())), np.float32)
-    ns = np.float32(noise_scale)
-    for b in range(B):
-        idx = np.repeat(np.arange(T), dur[b])
-        n = len(idx)
-        if n:
-            out[b, :, :n] = m_p[b][:, idx] + noise[b, :, :n] * np.exp(logs_p[b][:, idx]) * ns
-        else:
-            out[b, :, 0] = noise[b, :, 0] * ns
-    return out
-
 
 @pytest.mark.parametrize("preset", ["tiny_rb1", "tiny_dp", "sx_rb2_ms"])
 def test_dropped_tokens_render_what_the_length_regulator_gives(preset):

@@ -8,6 +8,7 @@ import pytest
 
 from bench import voice_cache
 from conftest import ALL_PRESETS, GOLDEN, case_get
+from philox_ref import row_noise
 
 pytestmark = pytest.mark.gpu
 
@@ -36,37 +37,7 @@ def _interior(out, b, ylen, hop, rf):
     return out[b, 0, 0, :n]
 
 
-# ------------------------------------------------------------------ NumPy restatement of the documented stream (vitsmi.h)
-
-M32 = np.uint64(0xFFFFFFFF)
-
-
-def philox4x32_10(c0, c1, c2, c3, key):
-    c = [np.asarray(x, np.uint64) & M32 for x in (c0, c1, c2, c3)]
-    k0, k1 = np.uint64(key & 0xFFFFFFFF), np.uint64(key >> 32)
-    for _ in range(10):
-        p0 = np.uint64(0xD2511F53) * c[0]
-        p1 = np.uint64(0xCD9E8D57) * c[2]
-        c = [(p1 >> np.uint64(32)) ^ c[1] ^ k0, p1 & M32, (p0 >> np.uint64(32)) ^ c[3] ^ k1, p0 & M32]
-        k0 = (k0 + np.uint64(0x9E3779B9)) & M32
-        k1 = (k1 + np.uint64(0xBB67AE85)) & M32
-    return c
-
-
-def row_noise(seed, stream, channels, n):
-    """[channels, n]: element (ch, pos) = v[pos & 3] of Philox4x32-10(counter (pos >> 2, ch, stream, 0), key seed) + Box-Muller"""
-    p4 = np.arange((n + 3) // 4, dtype=np.uint64)[None, :]
-    ch = np.arange(channels, dtype=np.uint64)[:, None]
-    r = philox4x32_10(np.broadcast_to(p4, (channels, p4.shape[1])), np.broadcast_to(ch, (channels, p4.shape[1])),
-                      np.uint64(stream), np.uint64(0), int(seed))
-    k = np.float32(2.3283064365386963e-10)
-    u = [(x.astype(np.float32) + np.float32(0.5)) * k for x in r]
-    u0 = np.minimum(np.maximum(u[0], np.float32(1e-12)), np.float32(1.0))
-    u2 = np.minimum(np.maximum(u[2], np.float32(1e-12)), np.float32(1.0))
-    ra, rb = np.sqrt(np.float32(-2.0) * np.log(u0)), np.sqrt(np.float32(-2.0) * np.log(u2))
-    tp = np.float32(6.283185307179586)
-    v = np.stack([ra * np.cos(tp * u[1]), ra * np.sin(tp * u[1]), rb * np.cos(tp * u[3]), rb * np.sin(tp * u[3])], -1)
-    return v.reshape(channels, -1)[:, :n].astype(np.float32)
+# (the NumPy restatement of the documented stream, vitsmi.h: tests/philox_ref.py)
 
 
 def _mixed_rows(B, base):
