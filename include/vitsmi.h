@@ -391,13 +391,69 @@ int vits_last_sample_counts(vits_handle *h, int64_t *buf, int n);
  * table != NULL, h as [L][K] floats (table_elems >= L * K).  table == NULL asks for the sizes. */
 int vits_resample_plan(int in_rate, int out_rate, int64_t *L, int64_t *M, int64_t *K, float *table, size_t table_elems);
 
+/* ---- delivery: the last run's audio packed per request on the device - PCM16, G.711, F32, pauses -------------------
+ * The reference post-processes and frames every sentence on the host (phoonnx/voice.py:271-282 peak-normalise / volume /
+ * clip, :88-91 int16, :307-326 the pause in front of a sentence); this does it for a whole batch in one operation: read the
+ * valid samples of the rows of the last run, apply each row's own post-processing, encode, and lay the results out back to
+ * back as the byte streams the callers will send.  The definition below is its specification.
+ *
+ * Input: the last completed run of the handle, through any entry that leaves a whole waveform - vits_run* with or without
+ * `out`, vits_run_async*, vits_run_device* after vits_sync, vits_run_vocoder - natively or at an output rate.  Its rows are
+ * x[b][0 .. n_b), n_b = what vits_last_sample_counts reports: y_lengths[b] * hop, or the count at the rate the run was
+ * resampled to; every row of a vocoder-only run has F * hop samples, or their resampled count.  Whatever lies behind n_b
+ * never shows.
+ *
+ * Plan: G segments, n_streams = J output streams, an encoding (w bytes per element: 2, 1, 1, 4).
+ * Layout: stream j holds, for its segments in the order given, lead_samples elements of silence and then n_row elements;
+ * N_j = sum (lead + n_row), 0 for a stream without segments.  Streams lie back to back in dst: off_0 = 0,
+ * off_{j+1} = off_j + w * N_j, total = off_J.  Silence is the encoding of sample value 0: 00 00 (PCM16), 0xFF (u-law),
+ * 0xD5 (A-law), +0.0f (F32).
+ * One sample, in fp32, in exactly this order (the operations of vits_last_pcm16):
+ *   peak_row = max |x[b][i]| over i < n_b  (0 for n_b = 0)
+ *   peak     = peak_row (normalize 1) | max of peak_row over the stream's segments with normalize 2 (normalize 2)
+ *   v = x[b][i];  if normalize: v = peak < 1e-8f ? 0.0f : v / peak;  if volume != 1.0f: v = v * volume;  v = min(max(v,-1),1)
+ *   F32:   v
+ *   PCM16: q = (int16) trunc(min(max(v * 32767.0f, -32767.0f), 32767.0f)), little endian
+ *   ULAW:  s = q >> 2 (arithmetic); neg = s < 0; m = (neg ? -s : s) + 33; seg = clamp(floor(log2 m) - 5, 0, 8);
+ *          u = seg == 8 ? 0x7F : (seg << 4) | ((m >> (seg + 1)) & 15);  byte = u ^ (neg ? 0x7F : 0xFF)
+ *   ALAW:  s = q >> 3; neg = s < 0; m = neg ? -s - 1 : s; seg = clamp(floor(log2 max(m,1)) - 4, 0, 7);
+ *          a = (seg << 4) | ((seg < 2 ? m >> 1 : m >> seg) & 15);   byte = a ^ (neg ? 0x55 : 0xD5)
+ * (the two G.711 forms equal CPython's audioop.lin2ulaw / lin2alaw, width 2, on all 65 536 int16 values).
+ * So: one row per stream, PCM16, is row b of vits_last_pcm16 cut to n_b, bit for bit; a row's bytes depend on that row alone
+ * (with normalize 2: on the stream's other rows too); batch layout, tails mode and position in dst do not enter.
+ * The device writes only the audio, packed; silence is filled in on the host and never crosses the bus, and the audio
+ * arrives with one copy per maximal run of segments without silence between them (no leads: one copy for the batch).
+ * Validation happens on the host before anything is enqueued or allocated; VITS_E_ARG, the message naming the segment
+ * index and the value: row outside [0, B); a row named twice (naming the second segment); stream outside [0, n_streams);
+ * n_streams outside [1, B]; n_segs outside [0, B]; lead_samples outside [0, INT_MAX]; normalize outside 0..2; a non-finite
+ * volume; an unknown encoding; dst_bytes < total (the message states the bytes needed); no completed run or a chunked run
+ * ("no completed run").  A rejected call leaves the last run deliverable. */
+enum { VITS_ENC_PCM16 = 0, VITS_ENC_ULAW = 1, VITS_ENC_ALAW = 2, VITS_ENC_F32 = 3 };   /* w = 2, 1, 1, 4 bytes */
+typedef struct {
+    int32_t row;           /* source row of the last run; each row in at most one segment */
+    int32_t stream;        /* [0, n_streams): a stream is its segments concatenated in the order given */
+    int64_t lead_samples;  /* samples of silence in front of this segment, at the delivered rate; [0, INT_MAX] */
+    int32_t normalize;     /* 0 none; 1 peak of this row (voice.py:271-277); 2 peak of the stream */
+    float   volume;        /* finite */
+} vits_segment;
+/* pure host code, no handle, no device (like vits_resample_plan): counts [B] -> stream_samples [n_streams], stream_offsets
+ * [n_streams + 1] (each nullable), *total_bytes */
+int vits_delivery_plan(const int64_t *counts, int B, const vits_segment *segs, int n_segs, int n_streams, int encoding,
+                       int64_t *stream_samples, int64_t *stream_offsets, int64_t *total_bytes);
+/* the last run, delivered into caller-owned host memory (pageable, or vits_host_alloc); waits for the run; VITS_E_RANGE as
+ * vits_last_pcm16; may be called again with another plan or encoding; vits_fetch_output / vits_last_pcm16 / vits_tap still
+ * work afterwards.  dst == NULL asks for the layout only (stream_samples, stream_offsets; stream_offsets[n_streams] is the
+ * total): the plan is validated against the last run, nothing is enqueued and nothing waited for. */
+int vits_deliver(vits_handle *h, const vits_segment *segs, int n_segs, int n_streams, int encoding, void *dst, size_t dst_bytes,
+                 int64_t *stream_samples, int64_t *stream_offsets);
+
 /* Size the handle's device workspaces NOW for requests of up to B utterances x T tokens that render up to F frames each
  * (the batch's longest utterance; T = 0 or F = 0 leaves that domain alone).  A run grows a workspace when a request
  * needs more than any before it - hipFree + hipMalloc of tens of GB at batch 32, a device-wide synchronisation that was
  * measured at 0.3 ms to 5 s - so a serving process calls this once at start-up with the largest request it admits (the
  * frame count of a batch depends on the durations the model predicts, i.e. on the noise as well: leave headroom), and no
- * request up to that size allocates device memory afterwards (vits_last_pcm16's int16 staging of such a request
- * included).  onnxruntime has no counterpart (its arena grows the same way, voice.py:167-171 passes default
+ * request up to that size allocates device memory afterwards (vits_last_pcm16's int16 staging and vits_deliver's packed
+ * buffer of such a request included).  onnxruntime has no counterpart (its arena grows the same way, voice.py:167-171 passes default
  * SessionOptions); nothing in the reference needs to call it.
  * INVALIDATES THE LAST RUN'S RESULTS when a workspace actually grows: the device waveform, frame counts and taps of the
  * last run live in those workspaces, so after a growing vits_reserve (or any run that grows one) vits_fetch_output /
@@ -526,6 +582,11 @@ int vits_test_fill_normal_rows(int device_id, int B, int channels, int T, const 
  * 2: the same layout, always the generic instantiation.  C % 8 == 0 for 1 and 2; the staged tile must fit 64 KiB of LDS. */
 int vits_test_post_conv(int device_id, const float *x, int B, int C, int T, const float *w, int K, float slope, const int64_t *vlen,
                         int hop, int kernel, float *out);
+
+/* The delivery by value: x [B][S] host, counts [B] the rows' valid samples (within [0, S]; what lies behind must not show);
+ * launches the pipeline's kernels with the pipeline's grids.  Everything else as vits_deliver. */
+int vits_test_deliver(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_segment *segs, int n_segs,
+                      int n_streams, int encoding, void *dst, size_t dst_bytes, int64_t *stream_samples, int64_t *stream_offsets);
 
 #ifdef __cplusplus
 }

@@ -5,6 +5,8 @@ import os
 
 import numpy as np
 
+from . import audio_encoding
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 
@@ -44,6 +46,15 @@ class VitsControls(C.Structure):
     _fields_ = [("scales_rows", C.c_void_p), ("seeds", C.c_void_p), ("durations", C.c_void_p), ("token_rate", C.c_void_p)]
 
 
+class VitsSegment(C.Structure):
+    _fields_ = [("row", C.c_int32), ("stream", C.c_int32), ("lead_samples", C.c_int64), ("normalize", C.c_int32),
+                ("volume", C.c_float)]
+
+
+# name -> (VITS_ENC_* code, element type): audio_encoding lists the names in the order of the header's enum
+ENCODINGS = {name: (code, audio_encoding.DTYPES[name]) for code, name in enumerate(audio_encoding.ENCODINGS)}
+
+
 # int fn(void *user, const float *samples, int B, int64 first_sample, int64 n_samples, int64 total_samples)
 CHUNK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_int64, C.c_int64, C.c_int64)
 
@@ -64,6 +75,7 @@ EXPORTS = [
     "vits_run_async_ctl", "vits_run_chunked_ctl", "vits_last_durations",
     "vits_set_output_rate", "vits_last_sample_counts", "vits_resample_plan", "vits_test_resample", "vits_test_resample_pieces",
     "vits_test_durations", "vits_test_expand_prior", "vits_test_fill_normal", "vits_test_fill_normal_rows", "vits_test_post_conv",
+    "vits_delivery_plan", "vits_deliver", "vits_test_deliver",
 ]
 
 
@@ -140,6 +152,9 @@ def load():
     lib.vits_test_fill_normal.argtypes = [C.c_int, C.c_int64, C.c_uint64, C.c_uint64, vp]
     lib.vits_test_fill_normal_rows.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_uint32, vp, C.c_int, vp]
     lib.vits_test_post_conv.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_float, vp, C.c_int, C.c_int, vp]
+    lib.vits_delivery_plan.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, i64p]
+    lib.vits_deliver.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vp, vp]
+    lib.vits_test_deliver.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vp, vp]
     lib.vits_free_output.argtypes = [vp, C.POINTER(VitsOutput)]
     lib.vits_free_output.restype = None
     lib.vits_sync.argtypes = [vp]

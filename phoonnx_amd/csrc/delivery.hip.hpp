@@ -1,0 +1,142 @@
+// delivery.hip.hpp — the kernels of a delivery (include/vitsmi.h, "delivery"; the plan: delivery.hpp).
+//
+// Two launches.  delivery_peak_kernel (skipped when no segment normalises) folds max |x| of every normalising segment's row
+// into its peak slot - the row's own, or its stream's - with atomicMax on the float bits, which is order-independent.
+// delivery_pack_kernel runs over the PACKED elements (the rows' valid samples only, in dst order), not over B x S_max: a
+// workgroup owns 256 cells of 16 output bytes, finds the segment of its first element by binary search in the segment table
+// and walks forward from there.  Every lane loads element base + i * 256 + lane of the tile (coalesced fp32), encodes it and
+// parks it in LDS; after the barrier each lane stores its 16-byte cell.  The packed buffer starts 256-byte aligned and
+// holds whole cells, so every store is a full 16-byte one wherever the segment boundaries fall inside a cell.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "delivery.hpp"
+
+namespace vitsmi {
+
+constexpr int kDeliveryThreads = 256;
+
+template <int ENC> struct DeliveryElem { using type = int16_t; };
+template <> struct DeliveryElem<VITS_ENC_ULAW> { using type = uint8_t; };
+template <> struct DeliveryElem<VITS_ENC_ALAW> { using type = uint8_t; };
+template <> struct DeliveryElem<VITS_ENC_F32> { using type = float; };
+
+// the fp32 post-processing of one sample: the operations of pcm16_kernel in their order
+__device__ inline float delivery_value(float v, bool norm, float peak, float volume) {
+    if (norm) v = peak < 1e-8f ? 0.f : v / peak;
+    if (volume != 1.0f) v = v * volume;
+    return fminf(fmaxf(v, -1.0f), 1.0f);
+}
+
+__device__ inline int delivery_q16(float v) { return (int)(int16_t)fminf(fmaxf(v * 32767.0f, -32767.0f), 32767.0f); }
+
+__device__ inline unsigned delivery_ulaw(int q) {
+    const int s = q >> 2;
+    const bool neg = s < 0;
+    const int m = (neg ? -s : s) + 33;  // >= 33
+    int seg = (31 - __clz(m)) - 5;
+    seg = seg > 8 ? 8 : seg;
+    const unsigned u = seg == 8 ? 0x7Fu : (unsigned)((seg << 4) | ((m >> (seg + 1)) & 15));
+    return (u ^ (neg ? 0x7Fu : 0xFFu)) & 0xFFu;
+}
+
+__device__ inline unsigned delivery_alaw(int q) {
+    const int s = q >> 3;
+    const bool neg = s < 0;
+    const int m = neg ? -s - 1 : s;
+    int seg = (31 - __clz(m > 1 ? m : 1)) - 4;
+    seg = seg < 0 ? 0 : (seg > 7 ? 7 : seg);
+    const unsigned a = (unsigned)((seg << 4) | ((seg < 2 ? m >> 1 : m >> seg) & 15));
+    return (a ^ (neg ? 0x55u : 0xD5u)) & 0xFFu;
+}
+
+template <int ENC>
+__device__ inline typename DeliveryElem<ENC>::type delivery_encode(float v) {
+    if constexpr (ENC == VITS_ENC_F32) return v;
+    else if constexpr (ENC == VITS_ENC_PCM16) return (int16_t)delivery_q16(v);
+    else if constexpr (ENC == VITS_ENC_ULAW) return (uint8_t)delivery_ulaw(delivery_q16(v));
+    else return (uint8_t)delivery_alaw(delivery_q16(v));
+}
+
+// grid (gx, G): segment blockIdx.y's row, folded into its slot
+__global__ __launch_bounds__(kDeliveryThreads) void delivery_peak_kernel(const float *x, const DeliverySeg *segs, unsigned *peak_bits) {
+    const DeliverySeg s = segs[blockIdx.y];
+    if (s.peak < 0) return;
+    float m = 0.f;
+    for (int i = blockIdx.x * kDeliveryThreads + threadIdx.x; i < s.n; i += gridDim.x * kDeliveryThreads)
+        m = fmaxf(m, fabsf(x[s.src + i]));
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    if ((threadIdx.x & 63) == 0 && s.n > 0) atomicMax(&peak_bits[s.peak], __float_as_uint(m));  // non-negative floats order as uints
+}
+
+// grid ceil(P / (256 * E)), E = 16 / sizeof(element): packed elements [0, P) -> cells of 16 bytes; the last cell is
+// written whole (zeros behind P: the packed buffer holds whole cells)
+template <int ENC>
+__global__ __launch_bounds__(kDeliveryThreads) void delivery_pack_kernel(const float *x, const DeliverySeg *segs, int G,
+                                                                         const unsigned *peak_bits, int64_t P, uint4 *packed) {
+    using T = typename DeliveryElem<ENC>::type;
+    constexpr int E = 16 / (int)sizeof(T);
+    __shared__ uint4 tile[kDeliveryThreads];
+    T *lt = reinterpret_cast<T *>(tile);
+    const int64_t base = (int64_t)blockIdx.x * (kDeliveryThreads * E);
+    // the last segment that starts at or in front of the tile (segs[0].start == 0; empty segments share a start with their
+    // successor and are passed over)
+    int lo = 0, hi = G;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (segs[mid].start <= base) lo = mid;
+        else hi = mid;
+    }
+    int g = lo, loaded = lo;
+    DeliverySeg s = segs[g];
+    int64_t next = g + 1 < G ? segs[g + 1].start : P;
+    // (unrolled by four: the passes' loads do not depend on one another, so the compiler may issue them together instead of
+    // waiting out one latency per pass; the kernel's own time has not been profiled)
+#pragma unroll 4
+    for (int i = 0; i < E; i++) {
+        const int64_t e = base + (int64_t)i * kDeliveryThreads + threadIdx.x;
+        T o = T(0);
+        if (e < P) {
+            while (e >= next) {  // (e < P: ends at the segment that holds e)
+                g++;
+                next = g + 1 < G ? segs[g + 1].start : P;
+            }
+            if (loaded != g) {
+                s = segs[g];
+                loaded = g;
+            }
+            const float peak = s.peak >= 0 ? __uint_as_float(peak_bits[s.peak]) : 1.f;
+            o = delivery_encode<ENC>(delivery_value(x[s.src + (e - s.start)], s.peak >= 0, peak, s.volume));
+        }
+        lt[i * kDeliveryThreads + threadIdx.x] = o;
+    }
+    __syncthreads();
+    const int64_t cell = base / E + threadIdx.x;
+    if (cell * E < P) packed[cell] = tile[threadIdx.x];
+}
+
+// both launches on `st`; peak_bits [2B] must read 0 (the caller's memset in front).  P > 0.
+inline hipError_t launch_delivery(const float *x, const DeliveryPlan &p, const DeliverySeg *d_segs, unsigned *d_peak, void *d_packed,
+                                  hipStream_t st) {
+    const int G = (int)p.segs.size();
+    if (p.any_norm) {
+        int gx = (p.max_n + kDeliveryThreads - 1) / kDeliveryThreads;
+        gx = gx > 256 ? 256 : (gx < 1 ? 1 : gx);
+        delivery_peak_kernel<<<dim3(gx, G), kDeliveryThreads, 0, st>>>(x, d_segs, d_peak);
+    }
+    const int64_t P = p.packed_elems;
+    const int64_t per = (int64_t)kDeliveryThreads * (16 / p.width);
+    const dim3 grid((unsigned)((P + per - 1) / per));
+    uint4 *out = static_cast<uint4 *>(d_packed);
+    switch (p.encoding) {
+        case VITS_ENC_PCM16: delivery_pack_kernel<VITS_ENC_PCM16><<<grid, kDeliveryThreads, 0, st>>>(x, d_segs, G, d_peak, P, out); break;
+        case VITS_ENC_ULAW: delivery_pack_kernel<VITS_ENC_ULAW><<<grid, kDeliveryThreads, 0, st>>>(x, d_segs, G, d_peak, P, out); break;
+        case VITS_ENC_ALAW: delivery_pack_kernel<VITS_ENC_ALAW><<<grid, kDeliveryThreads, 0, st>>>(x, d_segs, G, d_peak, P, out); break;
+        default: delivery_pack_kernel<VITS_ENC_F32><<<grid, kDeliveryThreads, 0, st>>>(x, d_segs, G, d_peak, P, out); break;
+    }
+    return hipGetLastError();
+}
+
+}  // namespace vitsmi

@@ -1,0 +1,171 @@
+// delivery.hpp — the plan of a delivery (include/vitsmi.h, "delivery"): which rows of the last run go where in the caller's
+// byte streams, validated and laid out on the host.  Host-side C++17, no HIP types: like the resampler's plan it is a pure
+// function of its arguments, answered without a handle or a device.
+//
+// The device never sees silence.  It writes ONE packed buffer: the encoded audio of the segments in `dst` order, back to
+// back, element p of the packed buffer at byte w * p.  The plan therefore carries three things: the segment table the
+// kernels read (DeliverySeg, in dst order, with each segment's first packed element), the copies that move maximal
+// silence-free runs of the packed buffer to their place in dst, and the silence regions the host fills itself.
+#pragma once
+#include <climits>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/vitsmi.h"
+
+namespace vitsmi {
+
+// bytes per element of an encoding; 0: unknown
+inline int delivery_width(int encoding) {
+    switch (encoding) {
+        case VITS_ENC_PCM16: return 2;
+        case VITS_ENC_ULAW:
+        case VITS_ENC_ALAW: return 1;
+        case VITS_ENC_F32: return 4;
+    }
+    return 0;
+}
+
+// one segment as the kernels read it (32 bytes; the table is in dst order, `start` ascending)
+struct DeliverySeg {
+    int64_t start;  // first packed element of this segment (prefix sum of n)
+    int64_t src;    // element offset of the row's first sample in the waveform: row * pitch
+    int32_t n;      // valid samples of the row
+    int32_t peak;   // peak slot to normalise by (row: [0, B); stream: B + stream), or -1
+    float volume;
+    int32_t pad;
+};
+
+struct DeliveryCopy {
+    int64_t packed_off, dst_off, bytes;
+};
+struct DeliveryFill {
+    int64_t dst_off, elems;
+};
+
+struct DeliveryPlan {
+    int encoding = 0, width = 0;
+    std::vector<int64_t> stream_samples, stream_offsets;  // [J], [J + 1]
+    std::vector<DeliverySeg> segs;
+    std::vector<DeliveryCopy> copies;
+    std::vector<DeliveryFill> fills;
+    int64_t packed_elems = 0, total_bytes = 0;
+    int max_n = 0;          // the longest segment (the peak launch's grid)
+    bool any_norm = false;  // some segment normalises: the peak launch is needed
+};
+
+// "" or what is wrong with the plan, naming the segment and the value.  counts [B]: the rows' valid samples; pitch: samples
+// between two rows of the waveform.
+inline std::string delivery_plan(const int64_t *counts, int B, int64_t pitch, const vits_segment *segs, int n_segs, int n_streams,
+                                 int encoding, DeliveryPlan &p) {
+    char buf[200];
+    const int w = delivery_width(encoding);
+    if (!w) {
+        std::snprintf(buf, sizeof buf, "unknown encoding %d (0 PCM16, 1 u-law, 2 A-law, 3 F32)", encoding);
+        return buf;
+    }
+    if (B < 1 || !counts) return "delivery: no rows";
+    if (n_streams < 1 || n_streams > B) {
+        std::snprintf(buf, sizeof buf, "n_streams = %d outside [1, %d]", n_streams, B);
+        return buf;
+    }
+    if (n_segs < 0 || n_segs > B || (n_segs > 0 && !segs)) {
+        std::snprintf(buf, sizeof buf, "n_segs = %d outside [0, %d]", n_segs, B);
+        return buf;
+    }
+    std::vector<int> seen(B, -1), per_stream(n_streams + 1, 0);
+    for (int g = 0; g < n_segs; g++) {
+        const vits_segment &s = segs[g];
+        if (s.row < 0 || s.row >= B) {
+            std::snprintf(buf, sizeof buf, "segment %d: row %d outside [0, %d)", g, s.row, B);
+            return buf;
+        }
+        if (seen[s.row] >= 0) {
+            std::snprintf(buf, sizeof buf, "segment %d: row %d is already in segment %d", g, s.row, seen[s.row]);
+            return buf;
+        }
+        seen[s.row] = g;
+        if (s.stream < 0 || s.stream >= n_streams) {
+            std::snprintf(buf, sizeof buf, "segment %d: stream %d outside [0, %d)", g, s.stream, n_streams);
+            return buf;
+        }
+        if (s.lead_samples < 0 || s.lead_samples > INT_MAX) {
+            std::snprintf(buf, sizeof buf, "segment %d: lead_samples %lld outside [0, %d]", g, (long long)s.lead_samples, INT_MAX);
+            return buf;
+        }
+        if (s.normalize < 0 || s.normalize > 2) {
+            std::snprintf(buf, sizeof buf, "segment %d: normalize %d outside 0..2", g, s.normalize);
+            return buf;
+        }
+        if (!std::isfinite(s.volume)) {
+            std::snprintf(buf, sizeof buf, "segment %d: volume %g is not finite", g, (double)s.volume);
+            return buf;
+        }
+        if (counts[s.row] < 0 || counts[s.row] > INT_MAX) {
+            std::snprintf(buf, sizeof buf, "segment %d: row %d has %lld samples, outside [0, %d]", g, s.row, (long long)counts[s.row], INT_MAX);
+            return buf;
+        }
+        per_stream[s.stream + 1]++;
+    }
+    // dst order: stream by stream, a stream's segments in the order given (a counting sort)
+    for (int j = 0; j < n_streams; j++) per_stream[j + 1] += per_stream[j];
+    std::vector<int> order(n_segs);
+    {
+        std::vector<int> at(per_stream.begin(), per_stream.end() - 1);
+        for (int g = 0; g < n_segs; g++) order[at[segs[g].stream]++] = g;
+    }
+    p = DeliveryPlan{};
+    p.encoding = encoding;
+    p.width = w;
+    p.stream_samples.assign(n_streams, 0);
+    p.stream_offsets.assign(n_streams + 1, 0);
+    p.segs.reserve(n_segs);
+    int64_t packed = 0, dst = 0;  // elements
+    int k = 0;
+    for (int j = 0; j < n_streams; j++) {
+        p.stream_offsets[j] = dst * w;
+        for (; k < per_stream[j + 1]; k++) {
+            const vits_segment &s = segs[order[k]];
+            const int64_t n = counts[s.row];
+            if (s.lead_samples > 0) {
+                p.fills.push_back({dst * w, s.lead_samples});
+                dst += s.lead_samples;
+            }
+            if (n > 0) {
+                // a copy runs on while no silence lies in front of the segment
+                if (!p.copies.empty() && s.lead_samples == 0 && p.copies.back().dst_off + p.copies.back().bytes == dst * w)
+                    p.copies.back().bytes += n * w;
+                else
+                    p.copies.push_back({packed * w, dst * w, n * w});
+            }
+            DeliverySeg d{};
+            d.start = packed;
+            d.src = (int64_t)s.row * pitch;
+            d.n = (int32_t)n;
+            d.peak = s.normalize == 1 ? s.row : (s.normalize == 2 ? B + s.stream : -1);
+            d.volume = s.volume;
+            p.segs.push_back(d);
+            p.any_norm = p.any_norm || s.normalize != 0;
+            p.max_n = d.n > p.max_n ? d.n : p.max_n;
+            packed += n;
+            dst += n;
+            p.stream_samples[j] += s.lead_samples + n;
+        }
+    }
+    p.stream_offsets[n_streams] = dst * w;
+    p.packed_elems = packed;
+    p.total_bytes = dst * w;
+    return "";
+}
+
+// the silence regions of dst: the encoding of sample value 0
+inline void delivery_silence(const DeliveryPlan &p, void *dst) {
+    const int byte = p.encoding == VITS_ENC_ULAW ? 0xFF : (p.encoding == VITS_ENC_ALAW ? 0xD5 : 0);
+    for (const DeliveryFill &f : p.fills) std::memset(static_cast<char *>(dst) + f.dst_off, byte, (size_t)(f.elems * p.width));
+}
+
+}  // namespace vitsmi

@@ -24,6 +24,7 @@
 #include "conv_sx_pair16.hip.hpp"
 #include "attention16.hip.hpp"
 #include "conv_sx_small.hip.hpp"
+#include "delivery.hip.hpp"
 #include "kernels.hip.hpp"
 #include "model.hpp"
 #include "resample.hip.hpp"
@@ -124,6 +125,8 @@ struct vits_handle {
     bool out_resampled = false;
     int *d_nout = nullptr;
     int rs_run_K = 0;
+    int64_t rs_run_L = 1, rs_run_M = 1;  // ... and the ratio its sample counts follow (vits_deliver's valid lengths)
+    bool last_vocoder = false;           // the last run was vocoder-only: every row has F frames, h_ylen is not its
 };
 
 // chunked rendering (vits_run_chunked / vits_run_vocoder_chunked): where the audio goes
@@ -1824,6 +1827,8 @@ int resample_run(vits_handle *h, const int *ylen, int B) {
     h->S = S_out;
     h->d_nout = rb.n_out;
     h->rs_run_K = (int)p.K;
+    h->rs_run_L = p.L;
+    h->rs_run_M = p.M;
     h->out_resampled = true;
     return 0;
 }
@@ -2453,8 +2458,10 @@ int vits_reserve(vits_handle *h, int B, int T, int F) {
         // vits_last_pcm16's int16 waveform and per-utterance peaks (the larger of the two uses)
         const size_t io_in = carved_bytes([&](Carver &cv) { carve_inputs(cv, m, B, T, T, Fp); });
         const size_t io_pcm = carved_bytes([&](Carver &cv) { carve_pcm16(cv, B, F * m.hop); });
+        const size_t io_dlv = carved_bytes([&](Carver &cv) { carve_delivery(cv, B, F * m.hop); });  // ... or vits_deliver's
         size_t io = io_in > io_pcm ? io_in : io_pcm;
-        if (h->rs.plan.on()) {  // ... or the resampled waveform with its own 16-bit rendering
+        io = io_dlv > io ? io_dlv : io;
+        if (h->rs.plan.on()) {  // ... or the resampled waveform with its own 16-bit rendering and delivery buffers
             const int64_t so = h->rs.plan.count((int64_t)F * m.hop);
             if (so > INT_MAX) return fail(h, VITS_E_ARG, "vits_reserve: F=%d frames are %lld samples at %d Hz", F, (long long)so, h->rs.plan.fo);
             const size_t io_rs = carved_bytes([&](Carver &cv) { carve_resample(cv, B, (int)so, (int)h->rs.plan.K); });
@@ -2540,6 +2547,7 @@ static int run_device_locked(vits_handle *h, const int64_t *ids, const int64_t *
     h->T = T;
     h->range_failed = false;
     h->out_resampled = false;
+    h->last_vocoder = false;
     uint64_t seed = noise ? noise->seed : 0;
     seed = seed * 0x9E3779B97F4A7C15ull + (++h->run_counter);
     // (run_tokens' one synchronisation also completes the previous run on this handle: its range verdict, if nobody
@@ -2852,6 +2860,84 @@ int vits_last_pcm16(vits_handle *h, int normalize, float volume, int16_t *out, s
     return VITS_OK;
 }
 
+// ---- delivery (vitsmi.h, "delivery"): the plan on the host (delivery.hpp), two launches (delivery.hip.hpp), one copy per
+// silence-free run of segments, the silence filled in here while the copies run
+
+int vits_delivery_plan(const int64_t *counts, int B, const vits_segment *segs, int n_segs, int n_streams, int encoding,
+                       int64_t *stream_samples, int64_t *stream_offsets, int64_t *total_bytes) {
+    DeliveryPlan p;
+    const std::string e = delivery_plan(counts, B, 0, segs, n_segs, n_streams, encoding, p);
+    if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
+    for (int j = 0; j < n_streams && stream_samples; j++) stream_samples[j] = p.stream_samples[j];
+    for (int j = 0; j <= n_streams && stream_offsets; j++) stream_offsets[j] = p.stream_offsets[j];
+    if (total_bytes) *total_bytes = p.total_bytes;
+    return VITS_OK;
+}
+
+// Everything a delivery puts on the stream: segment table up, peaks cleared, the launches, the copies into dst; then the
+// silence, on the host.  The caller synchronises.  db: carve_delivery's buffers for a waveform of at least the plan's rows.
+static hipError_t delivery_enqueue(const float *d_x, const DeliveryPlan &p, const DeliveryBufs &db, int B, hipStream_t st, void *dst) {
+    hipError_t e = hipSuccess;
+    if (p.packed_elems > 0) {
+        e = hipMemcpyAsync(db.segs, p.segs.data(), p.segs.size() * sizeof(DeliverySeg), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && p.any_norm) e = hipMemsetAsync(db.peak, 0, 2 * (size_t)B * sizeof(unsigned), st);
+        if (e == hipSuccess) e = launch_delivery(d_x, p, db.segs, db.peak, db.packed, st);
+        for (size_t i = 0; i < p.copies.size() && e == hipSuccess; i++)
+            e = hipMemcpyAsync(static_cast<char *>(dst) + p.copies[i].dst_off, db.packed + p.copies[i].packed_off,
+                               (size_t)p.copies[i].bytes, hipMemcpyDeviceToHost, st);
+    }
+    delivery_silence(p, dst);
+    return e;
+}
+
+static void delivery_report(const DeliveryPlan &p, int64_t *stream_samples, int64_t *stream_offsets) {
+    for (size_t j = 0; j < p.stream_samples.size() && stream_samples; j++) stream_samples[j] = p.stream_samples[j];
+    for (size_t j = 0; j < p.stream_offsets.size() && stream_offsets; j++) stream_offsets[j] = p.stream_offsets[j];
+}
+
+int vits_deliver(vits_handle *h, const vits_segment *segs, int n_segs, int n_streams, int encoding, void *dst, size_t dst_bytes,
+                 int64_t *stream_samples, int64_t *stream_offsets) {
+    if (int rc = check_dev(h)) return rc;
+    std::lock_guard<std::mutex> lk(h->mu);
+    const int B = h->B, S = h->S;
+    if (!h->d_out || B <= 0 || S <= 0 || (!h->last_vocoder && (int)h->h_ylen.size() != B))
+        return fail(h, VITS_E_ARG, "no completed run to deliver");
+    // the rows' valid samples: frames * hop, or their count at the rate the run was resampled to
+    const bool rs = h->out_resampled;
+    std::vector<int64_t> counts(B);
+    for (int b = 0; b < B; b++) {
+        const int64_t n = (int64_t)(h->last_vocoder ? h->F : h->h_ylen[b]) * h->model.hop;
+        counts[b] = rs ? (n * h->rs_run_L + h->rs_run_M - 1) / h->rs_run_M : n;
+        if (counts[b] > S) return fail(h, VITS_E_ARG, "no completed run to deliver (row %d: %lld samples of %d)", b, (long long)counts[b], S);
+    }
+    DeliveryPlan p;
+    const std::string e = delivery_plan(counts.data(), B, S, segs, n_segs, n_streams, encoding, p);
+    if (!e.empty()) return fail(h, VITS_E_ARG, "%s", e.c_str());
+    if (!dst) {  // the layout only: nothing is enqueued, nothing waited for
+        delivery_report(p, stream_samples, stream_offsets);
+        return VITS_OK;
+    }
+    if (dst_bytes < (size_t)p.total_bytes)
+        return fail(h, VITS_E_ARG, "delivery buffer too small: %zu bytes, %lld needed", dst_bytes, (long long)p.total_bytes);
+    // the staging slab is idle between runs; a resampled waveform lives in it, and its walk carved these buffers behind it
+    DeliveryBufs db{};
+    if (rs) {
+        const int K = h->rs_run_K;
+        if (int rc = slab_carve(h, h->io, "staging", [&](Carver &cv) { db = carve_resample(cv, B, S, K).dlv; })) return rc;
+        if (!h->d_out) return fail(h, VITS_E_ARG, "no completed run to deliver");
+    } else if (int rc = slab_carve(h, h->io, "staging", [&](Carver &cv) { db = carve_delivery(cv, B, S); }))
+        return rc;
+    hipStream_t st = h->stream;
+    hipError_t err = delivery_enqueue(h->d_out, p, db, B, st, dst);
+    if (err == hipSuccess) err = hipStreamSynchronize(st);
+    else hipStreamSynchronize(st);
+    if (err != hipSuccess) return fail(h, VITS_E_DEVICE, "delivery failed: %s", hipGetErrorString(err));
+    if (int rc = range_check(h)) return rc;  // (after vits_run_async this is the first synchronisation of that run)
+    if (h->range_failed) return fail(h, VITS_E_RANGE, "the last run left the range of the fp16 operand planes (see vits_get_stats)");
+    delivery_report(p, stream_samples, stream_offsets);
+    return VITS_OK;
+}
+
 // vocoder-only entry points: z (host, [B, inter, F], already masked) -> device, speaker bias; then either the whole
 // waveform or chunks
 static int vocoder_common(vits_handle *h, const float *z, int B, int F, const int64_t *sid, vits_output *out,
@@ -2886,6 +2972,7 @@ static int vocoder_common(vits_handle *h, const float *z, int B, int F, const in
     h->B = B;
     h->F = F;
     h->out_resampled = false;
+    h->last_vocoder = true;
     h->d_ylen = nullptr;  // (no frame counts: vits_last_pcm16 does not apply to a vocoder-only run)
     h->h_dur_B = h->h_dur_T = 0;  // (no tokens: vits_last_durations has nothing to report)
     range_begin(h);
@@ -3702,6 +3789,37 @@ int vits_test_resample(int device_id, const float *x, const int64_t *lens, int B
     TCHECK(launch_resample(a, B, /*piece=*/false, nullptr));
     TCHECK(hipDeviceSynchronize());
     TCHECK(download(y, dy, (size_t)B * S_out));
+    return VITS_OK;
+}
+
+int vits_test_deliver(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_segment *segs, int n_segs,
+                      int n_streams, int encoding, void *dst, size_t dst_bytes, int64_t *stream_samples, int64_t *stream_offsets) {
+    if (!x || !counts || B <= 0 || S <= 0 || (int64_t)B * S > (int64_t)1 << 40) return fail(nullptr, VITS_E_ARG, "bad delivery test arguments");
+    for (int b = 0; b < B; b++)
+        if (counts[b] < 0 || counts[b] > S) return fail(nullptr, VITS_E_ARG, "counts[%d] = %lld outside [0, %d]", b, (long long)counts[b], S);
+    DeliveryPlan p;
+    const std::string e = delivery_plan(counts, B, S, segs, n_segs, n_streams, encoding, p);
+    if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
+    if (!dst) {  // the layout only: nothing is enqueued, nothing waited for
+        delivery_report(p, stream_samples, stream_offsets);
+        return VITS_OK;
+    }
+    if (dst_bytes < (size_t)p.total_bytes)
+        return fail(nullptr, VITS_E_ARG, "delivery buffer too small: %zu bytes, %lld needed", dst_bytes, (long long)p.total_bytes);
+    if (int rc = test_dev(device_id)) return rc;
+    DevBufs D;
+    float *dx = D.up(x, (size_t)B * S);
+    DeliveryBufs db{};
+    db.packed = D.alloc<unsigned char>((size_t)B * S * 4 + 16);
+    db.segs = D.alloc<DeliverySeg>((size_t)B);
+    db.peak = D.alloc<unsigned>(2 * (size_t)B);
+    TCHECK(D.err);
+    // (wait whatever the enqueue answered: the plan's segment table is the pageable source of a copy that may be in flight)
+    const hipError_t enq = delivery_enqueue(dx, p, db, B, nullptr, dst);
+    const hipError_t done = hipDeviceSynchronize();
+    TCHECK(enq);
+    TCHECK(done);
+    delivery_report(p, stream_samples, stream_offsets);
     return VITS_OK;
 }
 

@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "delivery.hpp"
 #include "model.hpp"
 #include "slab.hpp"
 
@@ -236,16 +237,34 @@ inline PcmBufs carve_pcm16(Carver &cv, int B, int S) {
     return p;
 }
 
+// vits_deliver: the packed, encoded audio of the segments (whole 16-byte cells), the segment table and the peak slots (one
+// per row, one per stream).  Every row is in at most one segment, so the request bounds all three: at most 4 * B * S bytes
+// of audio (F32), B segments, 2 * B slots - whatever plan and encoding a call brings.
+struct DeliveryBufs {
+    unsigned char *packed;
+    DeliverySeg *segs;
+    unsigned *peak;
+};
+
+inline DeliveryBufs carve_delivery(Carver &cv, int B, int S) {
+    DeliveryBufs d{};
+    d.packed = cv.take<unsigned char>((size_t)B * S * 4 + 16);
+    d.segs = cv.take<DeliverySeg>(B);
+    d.peak = cv.take<unsigned>(2 * (size_t)B);
+    return d;
+}
+
 // With an output rate set (vits_set_output_rate), the staging slab holds the run's RESULT once its inputs are consumed:
 // the resampled fp32 waveform [B][S_out] (a chunked run: the output samples of one chunk, never more than S_out per
 // row), the rows' valid input and output sample counts, the two generations of the chunked path's carry [B][K] (the
 // last K input samples of every row; one is read while the other is written), and behind them vits_last_pcm16's buffers
-// for that waveform - one walk, so that converting it never moves what it converts.
+// and then vits_deliver's for that waveform - one walk, so that converting or delivering it never moves it.
 struct ResampleBufs {
     float *out;
     int *n_in, *n_out;
     float *carry[2];
     PcmBufs pcm;
+    DeliveryBufs dlv;
 };
 
 inline ResampleBufs carve_resample(Carver &cv, int B, int S_out, int K) {
@@ -255,6 +274,7 @@ inline ResampleBufs carve_resample(Carver &cv, int B, int S_out, int K) {
     r.n_out = cv.take<int>(B);
     for (auto &c : r.carry) c = cv.take<float>((size_t)B * K);
     r.pcm = carve_pcm16(cv, B, S_out);
+    r.dlv = carve_delivery(cv, B, S_out);
     return r;
 }
 

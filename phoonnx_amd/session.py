@@ -241,6 +241,61 @@ def output_sample_counts(n_samples, in_rate: int, out_rate: int) -> np.ndarray:
     return -(-np.asarray(n_samples, np.int64) * L // M)
 
 
+@dataclass
+class Segment:
+    """One segment of a delivery plan (vitsmi.h, vits_segment): row `row` of the last run goes into stream `stream`, behind
+    `lead_samples` samples of silence; normalize: 0 none, 1 by the row's own peak, 2 by the peak of the stream."""
+    row: int
+    stream: int = 0
+    lead_samples: int = 0
+    normalize: int = 1
+    volume: float = 1.0
+
+
+def _encoding(encoding):
+    try:
+        return _ffi.ENCODINGS[encoding]
+    except (KeyError, TypeError):
+        raise SessionError(f"unknown encoding {encoding!r}: one of {sorted(_ffi.ENCODINGS)}") from None
+
+
+def _segments(segments):
+    """Segment objects -> (ctypes array of vits_segment, its length)"""
+    segments = list(segments)
+    arr = (_ffi.VitsSegment * max(len(segments), 1))()
+    for i, g in enumerate(segments):
+        try:
+            arr[i] = _ffi.VitsSegment(int(g.row), int(g.stream), int(g.lead_samples), int(g.normalize), float(g.volume))
+        except (AttributeError, TypeError, ValueError, OverflowError) as e:
+            raise SessionError(f"segment {i}: {e}") from None
+    return arr, len(segments)
+
+
+def _n_streams(segments, n_streams):
+    if n_streams is not None:
+        return int(n_streams)
+    return max([int(g.stream) for g in segments], default=0) + 1
+
+
+def delivery_plan(counts, segments, n_streams=None, encoding="pcm16"):
+    """The layout of a delivery (vits_delivery_plan: pure host code, no session, no device): counts int64 [B] - the rows' valid
+    samples - and a plan -> {"stream_samples": int64 [J], "stream_offsets": int64 [J + 1] (bytes), "total_bytes": int}.
+    A plan the engine would refuse raises SessionError with its message."""
+    counts = np.ascontiguousarray(counts, np.int64)
+    if counts.ndim != 1:
+        raise SessionError(f"counts must be int64 [B], got {counts.shape}")
+    segments = list(segments)
+    code, _ = _encoding(encoding)
+    J = _n_streams(segments, n_streams)
+    arr, n = _segments(segments)
+    samples, offsets, total = np.zeros(max(J, 0), np.int64), np.zeros(max(J, 0) + 1, np.int64), C.c_int64()
+    rc = _ffi.load().vits_delivery_plan(_ffi.ptr(counts), counts.shape[0], arr, n, J, code, _ffi.ptr(samples), _ffi.ptr(offsets),
+                                        C.byref(total))
+    if rc != 0:
+        raise SessionError(f"vits_delivery_plan failed [{rc}]: {_ffi.last_error(None)}")
+    return {"stream_samples": samples, "stream_offsets": offsets, "total_bytes": int(total.value)}
+
+
 def _rows(scales, B):
     """[3] -> [B, 3] (the row twins of the C ABI take one row per utterance)"""
     return np.ascontiguousarray(np.broadcast_to(scales, (B, 3)) if scales.ndim == 1 else scales, np.float32)
@@ -460,6 +515,34 @@ class MiSession:
         (with a free run's durations and seeds: that run's audio bit for bit); token_rate: None or floats [B, T] - a
         multiplier on each token's predicted duration (0 drops the token).  One or the other (vitsmi.h, vits_controls).
         return_durations: adds "durations", int64 [B, T] - the frames each token occupies (last_durations())."""
+        ids, lens, scales, sid, noise_dp, noise_z, noise, seeds, durations, token_rate = self._run_arguments(
+            ids, lens, scales, sid, noise_dp, noise_z, seeds, durations, token_rate)
+        B = ids.shape[0]
+        with self._locked():  # enqueue -> frame counts -> copy-out -> taps all use this handle's one workspace
+            try:
+                self._begin(ids, lens, scales, sid, noise, seeds, durations, token_rate)
+                ylen = self.last_y_lengths()
+                dur = self.last_durations() if return_durations else None
+                counts = self.last_sample_counts() if self.resampling else None
+                S = int(ylen.max()) * self.hparam("hop") if counts is None else int(counts.max())
+                audio = _POOL.array((B, 1, 1, S)) if self.pinned_results else np.empty((B, 1, 1, S), np.float32)
+                self._fetch(audio, 0, B)
+            except RangeError as exc:
+                self._fall_back_to_bf16x6(exc)
+                return self.synthesize_batch(ids, lens, scales, sid, noise_dp, noise_z, taps, seeds=seeds,
+                                             durations=durations, token_rate=token_rate, return_durations=return_durations)
+            res = {"output": audio, "y_lengths": ylen}
+            if counts is not None:
+                res["sample_lengths"] = counts
+            if return_durations:
+                res["durations"] = dur
+            for t in taps:
+                res[t] = self.tap(t)
+            return res
+
+    def _run_arguments(self, ids, lens, scales, sid, noise_dp, noise_z, seeds, durations, token_rate):
+        """The arguments of one batched run, validated and made contiguous (synthesize_batch, synthesize_delivered); the
+        noise arrays are returned too: the VitsNoise struct only points into them."""
         ids = np.ascontiguousarray(ids)
         lens = np.ascontiguousarray(lens)
         if ids.dtype != np.int64 or lens.dtype != np.int64:
@@ -486,27 +569,7 @@ class MiSession:
                 raise SessionError(f"noise_z must be [B,inter,F], got {noise_z.shape}")
             noise.noise_z = noise_z.ctypes.data
             noise.noise_z_stride = noise_z.shape[2]
-        with self._locked():  # enqueue -> frame counts -> copy-out -> taps all use this handle's one workspace
-            try:
-                self._begin(ids, lens, scales, sid, noise, seeds, durations, token_rate)
-                ylen = self.last_y_lengths()
-                dur = self.last_durations() if return_durations else None
-                counts = self.last_sample_counts() if self.resampling else None
-                S = int(ylen.max()) * self.hparam("hop") if counts is None else int(counts.max())
-                audio = _POOL.array((B, 1, 1, S)) if self.pinned_results else np.empty((B, 1, 1, S), np.float32)
-                self._fetch(audio, 0, B)
-            except RangeError as exc:
-                self._fall_back_to_bf16x6(exc)
-                return self.synthesize_batch(ids, lens, scales, sid, noise_dp, noise_z, taps, seeds=seeds,
-                                             durations=durations, token_rate=token_rate, return_durations=return_durations)
-            res = {"output": audio, "y_lengths": ylen}
-            if counts is not None:
-                res["sample_lengths"] = counts
-            if return_durations:
-                res["durations"] = dur
-            for t in taps:
-                res[t] = self.tap(t)
-            return res
+        return ids, lens, scales, sid, noise_dp, noise_z, noise, seeds, durations, token_rate
 
     def _begin(self, ids, lens, scales, sid, noise, seeds=None, durations=None, token_rate=None):
         """vits_run_async: validated host arrays in, the whole path enqueued; frame counts and durations are known on
@@ -878,6 +941,69 @@ class MiSession:
             ylen = self.last_y_lengths()
             S = int(ylen.max()) * self.hparam("hop")
             return self.last_pcm16(normalize, volume, shape=(B, S)), ylen
+
+    def deliver(self, segments, n_streams=None, encoding="pcm16"):
+        """The last run's audio, post-processed, encoded and laid out per request on the device (vitsmi.h, "delivery"):
+        segments - Segment objects, each row of the run in at most one; encoding "pcm16" / "ulaw" / "alaw" / "f32".  Returns
+        one NumPy array per stream (int16 / uint8 / float32), all views into ONE buffer in stream order - page-locked memory
+        from the pool when pinned_results.  The fp32 waveform stays on the device; tap / last_pcm16 / a fetch of the same run
+        still work afterwards, and so does another deliver() with another plan."""
+        segments = list(segments)
+        code, dtype = _encoding(encoding)
+        J = _n_streams(segments, n_streams)
+        arr, n = _segments(segments)
+        samples, offsets = np.zeros(max(J, 0), np.int64), np.zeros(max(J, 0) + 1, np.int64)
+        with self._locked():
+            # (dst = NULL: the layout only - no device work, no wait)
+            rc = self._lib.vits_deliver(self._h, arr, n, J, code, None, 0, _ffi.ptr(samples), _ffi.ptr(offsets))
+            if rc != 0:
+                self._raise("vits_deliver", rc)
+            total = int(offsets[-1])
+            buf = _POOL.array((total,), np.uint8) if self.pinned_results and total else np.empty(total, np.uint8)
+            rc = self._lib.vits_deliver(self._h, arr, n, J, code, _ffi.ptr(buf), total, _ffi.ptr(samples), _ffi.ptr(offsets))
+            if rc != 0:
+                self._raise("vits_deliver", rc)
+        return [buf[int(offsets[j]):int(offsets[j + 1])].view(dtype) for j in range(J)]
+
+    def synthesize_delivered(self, ids, lens, scales, sid=None, *, segments=None, n_streams=None, encoding="pcm16",
+                             normalize=True, volume=1.0, seeds=None, durations=None, token_rate=None, noise_dp=None,
+                             noise_z=None, return_durations=False):
+        """One batched run and its delivery under one hold of the session lock: what leaves the GPU is the encoded audio
+        of the plan and nothing else - the fp32 waveform is never copied to the host.  segments=None: one stream per row,
+        with `normalize` / `volume` as scalars or [B] arrays (row b's own).  Everything in front of the delivery is
+        synthesize_batch's (scales [3] or [B, 3], seeds, durations, token_rate, injected noise, the bf16x6 fallback).
+        Returns {"streams": [array per stream], "stream_samples": int64 [J], "y_lengths": int64 [B], "sample_lengths":
+        int64 [B] (each row's valid samples at the delivered rate)[, "durations"]}."""
+        ids, lens, scales, sid, noise_dp, noise_z, noise, seeds, durations, token_rate = self._run_arguments(
+            ids, lens, scales, sid, noise_dp, noise_z, seeds, durations, token_rate)
+        B = ids.shape[0]
+        if segments is None:
+            try:
+                nz = np.broadcast_to(np.asarray(normalize, bool), (B,))
+                vol = np.broadcast_to(np.asarray(volume, np.float32), (B,))
+            except ValueError:
+                raise SessionError(f"normalize / volume must be scalars or [{B}] arrays") from None
+            segments = [Segment(b, b, 0, 1 if nz[b] else 0, float(vol[b])) for b in range(B)]
+            n_streams = B
+        segments = list(segments)
+        _encoding(encoding)
+        with self._locked():
+            try:
+                self._begin(ids, lens, scales, sid, noise, seeds, durations, token_rate)
+                ylen = self.last_y_lengths()
+                dur = self.last_durations() if return_durations else None
+                counts = self.last_sample_counts()
+                streams = self.deliver(segments, n_streams, encoding)
+            except RangeError as exc:
+                self._fall_back_to_bf16x6(exc)
+                return self.synthesize_delivered(ids, lens, scales, sid, segments=segments, n_streams=n_streams,
+                                                 encoding=encoding, seeds=seeds, durations=durations, token_rate=token_rate,
+                                                 noise_dp=noise_dp, noise_z=noise_z, return_durations=return_durations)
+        res = {"streams": streams, "stream_samples": np.array([a.size for a in streams], np.int64), "y_lengths": ylen,
+               "sample_lengths": counts}
+        if return_durations:
+            res["durations"] = dur
+        return res
 
     def sync(self):
         with self._locked():
@@ -1423,6 +1549,27 @@ def test_resample_pieces(x, lens, in_rate, out_rate, piece_samples, device_id=0)
 
 
 # ---- the token-to-frame and frame-to-sample kernels by value (include/vitsmi.h: vits_test_durations ...) ----------------
+
+def test_deliver(x, counts, segments, n_streams=None, encoding="pcm16", device_id=0, dst=None):
+    """vits_test_deliver: x [B, S] float32 and the rows' valid samples through the delivery kernels -> one array per stream,
+    views into `dst` (uint8; default: a buffer of exactly the plan's size, sized by delivery_plan).  A refusal raises
+    SessionError and leaves a `dst` passed in untouched."""
+    x = np.ascontiguousarray(x, np.float32)
+    counts = np.ascontiguousarray(counts, np.int64)
+    B, S = x.shape
+    segments = list(segments)
+    code, dtype = _encoding(encoding)
+    J = _n_streams(segments, n_streams)
+    if dst is None:
+        dst = np.empty(delivery_plan(counts, segments, J, encoding)["total_bytes"], np.uint8)
+    arr, n = _segments(segments)
+    samples, offsets = np.zeros(max(J, 0), np.int64), np.zeros(max(J, 0) + 1, np.int64)
+    rc = _ffi.load().vits_test_deliver(device_id, _ffi.ptr(x), _ffi.ptr(counts), B, S, arr, n, J, code, _ffi.ptr(dst), dst.nbytes,
+                                       _ffi.ptr(samples), _ffi.ptr(offsets))
+    if rc != 0:
+        raise SessionError(f"vits_test_deliver failed [{rc}]: {_ffi.last_error(None)}")
+    return [dst[int(offsets[j]):int(offsets[j + 1])].view(dtype) for j in range(J)]
+
 
 def _glue_check(rc, name):
     if rc != 0:

@@ -13,7 +13,10 @@ Extensions: `synthesize(..., batch_sentences=True)` render
 sentences of a text in ONE batched engine call; `synthesize_requests()` renders the sentences
 of many requests, each with its own SynthesisConfig (and optionally its own noise seed), in
 shared batches; `synthesize(..., alignments=True)` / `synthesize_requests(..., alignments=True)` attach per-phoneme
-timing (`AudioChunk.phoneme_alignments`) from the durations the engine reports (MiSession.last_durations).
+timing (`AudioChunk.phoneme_alignments`) from the durations the engine reports (MiSession.last_durations);
+`synthesize_encoded()` / `synthesize_requests_encoded()` return a text's or a request's audio as one encoded stream (16-bit
+PCM, G.711 mu-law / A-law, float32) with a pause in front of every sentence - post-processed, encoded and packed on the
+device by sessions that deliver (MiSession.synthesize_delivered), by audio_encoding on the host otherwise.
 """
 import json
 import logging
@@ -433,6 +436,173 @@ class TTSVoice:
                                         audio_float_array=self._postprocess(audio[r, k], cfgs[r]),
                                         phoneme_alignments=aligned.get((r, k))))
         return result
+
+    # ------------------------------------------------------------------ encoded delivery (extension)
+    def _lead_samples(self, sentence_silence: float) -> int:
+        """Samples of silence in front of every sentence: the reference's framing (voice.py:307-326 writes
+        int(sample_rate * sentence_silence * 2) bytes of 16-bit silence) wherever that byte count is even."""
+        if not sentence_silence >= 0.0:
+            raise ValueError(f"sentence_silence must be >= 0 (got {sentence_silence})")
+        return int(self.sample_rate * sentence_silence * 2) // 2
+
+    @staticmethod
+    def _scaled(audio: np.ndarray, peak, volume: float) -> np.ndarray:
+        """_postprocess with the peak given (None: no normalisation): the same float32 operations in the same order."""
+        if peak is not None:
+            audio = np.zeros_like(audio) if peak < 1e-8 else audio / peak
+        if volume != 1.0:
+            audio = audio * volume
+        return np.clip(audio, -1.0, 1.0).astype(np.float32)
+
+    def synthesize_encoded(self, text: str, syn_config: Optional[SynthesisConfig] = None, encoding: str = "pcm16",
+                           sentence_silence: float = 0.0, normalize_scope: str = "sentence",
+                           alignments: bool = False):
+        """Extension: the whole text as ONE stream of encoded audio ("pcm16", "ulaw", "alaw", "f32"; audio_encoding).  All
+        sentences render in one batch; with a session that delivers (MiSession.synthesize_delivered) post-processing,
+        encoding and the packing happen on the device and only the encoded audio crosses the bus; any other session
+        gets the same bytes from the host encoder.  In front of every sentence, the first included, lie
+        int(sample_rate * sentence_silence * 2) // 2 samples of silence.  normalize_scope: "sentence" - each sentence by its
+        own peak (what synthesize() does), "text" - all by the largest peak of the text, so that their relative levels
+        survive.  alignments=True fills phoneme_alignments (per sentence; start_sample counted from the stream's start).
+        Returns an audio_encoding.EncodedAudio."""
+        from . import audio_encoding as ae
+        from .sharding import pad_batch
+        cfg = syn_config if syn_config is not None else SynthesisConfig()
+        ae._check(encoding)
+        if normalize_scope not in ("sentence", "text"):
+            raise ValueError(f"normalize_scope must be 'sentence' or 'text' (got {normalize_scope!r})")
+        lead = self._lead_samples(sentence_silence)
+        want_dur = alignments and hasattr(self.session, "last_durations") and hasattr(self.session, "synthesize_batch")
+        groups = self._sentence_groups(text, cfg) if want_dur else None
+        all_ids = [[i for _, ids in g for i in ids] for g in groups] if want_dur else self._sentence_ids(text, cfg)
+        if not all_ids:
+            return ae.EncodedAudio(ae.silence(0, encoding), encoding, self.sample_rate, [], [], [] if want_dur else None)
+        durs = frames = None
+        if hasattr(self.session, "synthesize_delivered"):
+            from .session import Segment
+            ids, lens = pad_batch(all_ids)
+            expected = [i.name for i in self.session.get_inputs()]
+            if "sid" in expected:  # (checked before anything runs, as synthesize_requests_encoded does)
+                n_spk = int(self.session.hparam("n_speakers")) if hasattr(self.session, "hparam") else self.config.num_speakers
+                if not 0 <= (cfg.speaker_id or 0) < max(n_spk, 1):
+                    raise ValueError(f"speaker_id {cfg.speaker_id or 0} is out of range [0, {max(n_spk, 1)})")
+            sid = np.full((len(all_ids),), cfg.speaker_id or 0, np.int64) if "sid" in expected else None
+            norm = 0 if not cfg.normalize_audio else (2 if normalize_scope == "text" else 1)
+            segs = [Segment(b, 0, lead, norm, float(cfg.volume)) for b in range(len(all_ids))]
+            out = self.session.synthesize_delivered(ids, lens, self._scales(cfg), sid, segments=segs, n_streams=1,
+                                                    encoding=encoding, return_durations=want_dur)
+            data = out["streams"][0]
+            counts = [int(n) for n in out["sample_lengths"]]
+            if want_dur:
+                durs, frames = out["durations"], [int(f) for f in out["y_lengths"]]
+        else:
+            if hasattr(self.session, "synthesize_batch"):
+                res = self.phoneme_ids_batch_to_audio(all_ids, cfg, return_durations=want_dur)
+                audios, durs = res if want_dur else (res, None)
+            else:
+                audios = [self.phoneme_ids_to_audio(ids, cfg) for ids in all_ids]
+            peaks = [np.max(np.abs(a)) if len(a) else np.float32(0) for a in audios]
+            if not cfg.normalize_audio:
+                peaks = [None] * len(audios)
+            elif normalize_scope == "text":
+                peaks = [max(peaks)] * len(audios)
+            pieces = []
+            for a, pk in zip(audios, peaks):
+                pieces += [ae.silence(lead, encoding), ae.encode(self._scaled(a, pk, cfg.volume), encoding)]
+            data = np.concatenate(pieces)
+            counts = [len(a) for a in audios]
+        starts, pos = [], 0
+        for n in counts:
+            starts.append(pos + lead)
+            pos += lead + n
+        aligned = None
+        if want_dur:
+            hop, ratio = self.session.hparam("hop"), self._ratio()
+            aligned = []
+            for b, g in enumerate(groups):
+                total = frames[b] if frames is not None else max(1, int(np.sum(durs[b])))
+                al = build_alignments(g, durs[b], hop, total_frames=total, ratio=ratio)
+                for a in al:
+                    a.start_sample += starts[b]
+                aligned.append(al)
+        return ae.EncodedAudio(data, encoding, self.sample_rate, starts, counts, aligned)
+
+    def synthesize_requests_encoded(self, requests: Sequence[Tuple[str, Optional[SynthesisConfig]]],
+                                    seeds: Optional[Sequence[int]] = None, max_batch: int = 32, encoding: str = "pcm16",
+                                    sentence_silence: float = 0.0, alignments: bool = False):
+        """Extension: synthesize_requests with every request's audio returned as one stream of encoded audio
+        (audio_encoding.EncodedAudio; the pause of synthesize_encoded in front of each sentence).  The batching is
+        synthesize_requests': sentences sorted by length, max_batch at a time, each with its request's settings and seed.
+        With a session that delivers, every sentence leaves the device as its own encoded stream, post-processed with its
+        request's normalize_audio / volume; a request's pieces are joined with their silence on the host, because its
+        sentences may render in different runs (for the same reason each sentence is normalised by its own peak).  Any other
+        session: the host encoder over synthesize_requests' chunks - the same bytes."""
+        from . import audio_encoding as ae
+        ae._check(encoding)
+        lead = self._lead_samples(sentence_silence)
+
+        def join(pieces, aligns):
+            starts, pos = [], 0
+            for p in pieces:
+                starts.append(pos + lead)
+                pos += lead + len(p)
+            parts = [q for p in pieces for q in (ae.silence(lead, encoding), p)]
+            data = np.concatenate(parts) if parts else ae.silence(0, encoding)
+            if aligns is not None:
+                for st, al in zip(starts, aligns):
+                    for a in al or []:
+                        a.start_sample += st
+            return ae.EncodedAudio(data, encoding, self.sample_rate, starts, [len(p) for p in pieces], aligns)
+
+        if not hasattr(self.session, "synthesize_delivered"):
+            chunks = self.synthesize_requests(requests, seeds=seeds, max_batch=max_batch, alignments=alignments)
+            return [join([ae.encode(c.audio_float_array, encoding) for c in cs],
+                         [c.phoneme_alignments for c in cs] if alignments and all(c.phoneme_alignments is not None for c in cs)
+                         else None) for cs in chunks]
+        if max_batch < 1:
+            raise ValueError(f"max_batch must be >= 1 (got {max_batch})")
+        if seeds is not None and len(seeds) != len(requests):
+            raise ValueError(f"seeds must hold one seed per request ({len(requests)}), got {len(seeds)}")
+        cfgs = [cfg if cfg is not None else SynthesisConfig() for _, cfg in requests]
+        expected = [i.name for i in self.session.get_inputs()]
+        if "sid" in expected:  # every request's speaker is checked before anything runs
+            n_spk = int(self.session.hparam("n_speakers"))
+            for r, cfg in enumerate(cfgs):
+                spk = cfg.speaker_id or 0
+                if not 0 <= spk < max(n_spk, 1):
+                    raise ValueError(f"request {r}: speaker_id {spk} is out of range [0, {max(n_spk, 1)})")
+        from .session import Segment
+        from .sharding import pad_batch
+        want_dur = alignments and hasattr(self.session, "last_durations")
+        rows, groups = [], {}
+        for r, ((text, _), cfg) in enumerate(zip(requests, cfgs)):
+            if want_dur:
+                for k, g in enumerate(self._sentence_groups(text, cfg)):
+                    groups[r, k] = g
+                    rows.append((r, k, [i for _, ids in g for i in ids]))
+            else:
+                rows.extend((r, k, ids) for k, ids in enumerate(self._sentence_ids(text, cfg)))
+        piece, aligned = {}, {}
+        hop = self.session.hparam("hop")
+        order = sorted(range(len(rows)), key=lambda i: len(rows[i][2]))  # (stable: equal lengths keep request order)
+        for c0 in range(0, len(order), max_batch):
+            run = [rows[i] for i in order[c0:c0 + max_batch]]
+            ids, lens = pad_batch([ids for _, _, ids in run])
+            scales = np.stack([self._scales(cfgs[r]) for r, _, _ in run])
+            sid = np.asarray([cfgs[r].speaker_id or 0 for r, _, _ in run], np.int64) if "sid" in expected else None
+            row_seeds = None if seeds is None else np.asarray([sentence_seed(seeds[r], k) for r, k, _ in run], np.uint64)
+            segs = [Segment(b, b, 0, 1 if cfgs[r].normalize_audio else 0, float(cfgs[r].volume)) for b, (r, _, _) in enumerate(run)]
+            out = self.session.synthesize_delivered(ids, lens, scales, sid, segments=segs, n_streams=len(run), encoding=encoding,
+                                                    seeds=row_seeds, return_durations=want_dur)
+            for b, (r, k, _) in enumerate(run):
+                piece[r, k] = out["streams"][b]
+                if want_dur:
+                    aligned[r, k] = build_alignments(groups[r, k], out["durations"][b], hop,
+                                                     total_frames=int(out["y_lengths"][b]), ratio=self._ratio())
+        per_request = [[] for _ in requests]
+        for r, k, _ in rows:  # (rows are in request, then sentence order)
+            per_request[r].append((r, k))
+        return [join([piece[key] for key in keys], [aligned[key] for key in keys] if want_dur else None) for keys in per_request]
 
     def synthesize_wav(self, text: str, wav_file: wave.Wave_write, syn_config: Optional[SynthesisConfig] = None,
                        set_wav_format: bool = True, batch_sentences: bool = False, device_pcm16: bool = False) -> None:
