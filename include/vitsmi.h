@@ -447,13 +447,57 @@ int vits_delivery_plan(const int64_t *counts, int B, const vits_segment *segs, i
 int vits_deliver(vits_handle *h, const vits_segment *segs, int n_segs, int n_streams, int encoding, void *dst, size_t dst_bytes,
                  int64_t *stream_samples, int64_t *stream_offsets);
 
+/* ---- encoded streaming: a chunked run's chunks post-processed, encoded and masked on the device --------------------------
+ * vits_run_chunked* hands every chunk over as fp32 [B][n]; vits_deliver refuses a chunked run.  The two entries below are the
+ * chunked runs with the delivery's post-processing and encoders applied per chunk, by one more launch per chunk
+ * (csrc/stream_pack.hip.hpp); like the delivery they are an extension, and the text below is their specification.
+ *
+ * What stays the chunked run's.  Apart from `fmt` and the callback type, vits_run_chunked_enc is vits_run_chunked_ctl and
+ * vits_run_vocoder_chunked_enc is vits_run_vocoder_chunked: the same chunks in the same order with the same first_sample /
+ * n_samples / total_samples; at an output rate the counts are output-rate samples, through the resampler's carry, and a chunk
+ * that completes no output sample makes no call; a non-zero return stops the run; VITS_E_RANGE is reported at the end;
+ * vits_last_y_lengths, vits_last_durations and vits_last_sample_counts work as after a chunked run, and vits_deliver still
+ * answers "no completed run".
+ *
+ * Row lengths.  Row b has n_b valid samples - what vits_last_sample_counts reports; F * hop, or its count at the output rate,
+ * for every row of a vocoder-only run - and valid[b] = clamp(n_b - first_sample, 0, n_samples).
+ * Layout of a chunk.  `bytes` is [B][row_pitch_bytes], row_pitch_bytes = round_up(w * n_samples, 16) (w as in the delivery: 2,
+ * 1, 1, 4).  Row b holds valid[b] encoded elements and behind them, up to the pitch, the encoding of sample value 0: 00 00,
+ * 0xFF, 0xD5 or +0.0f.  A row that has ended is all silence: what the generator rendered behind a row's end never shows, in
+ * either tails mode.  `bytes`, `valid` and `peak` are valid during the call.
+ * One sample, in fp32, in exactly this order:
+ *   v = x[b][i];  if ref_peak: v = ref_peak[b] < 1e-8f ? 0.0f : v / ref_peak[b] (the correctly rounded division);
+ *   if volume[b] != 1.0f: v = v * volume[b];  v = min(max(v, -1), 1);  then the encoders of the delivery section, unchanged
+ * i.e. vits_deliver's sample with peak := ref_peak[b] (a stream cannot know its own peak).
+ * Running peak.  peak[b] = max |x[b][i]| over the row's valid samples i < first_sample + valid[b], taken before any gain with
+ * fmaxf semantics, 0 for an empty row; non-decreasing from chunk to chunk, and after the last chunk the peak vits_deliver's
+ * normalize 1 would use.  With fixed seeds, or for a voice calibrated once, a caller feeds a reported peak back as ref_peak:
+ * the stream is then the normalised delivery, bit for bit.
+ * Validation happens on the host before anything is enqueued or allocated and before the chunked run's own checks; VITS_E_ARG
+ * naming the row and the value: fmt == NULL; an unknown encoding; a non-finite volume[b]; a non-finite or negative
+ * ref_peak[b].  fn == NULL is allowed, as in vits_run_chunked.  A rejected call makes no callback and leaves the previous
+ * run's results readable and deliverable.
+ * vits_reserve(B, T, F) covers the device chunk buffer for every chunk_frames <= F. */
+typedef struct {
+    int32_t encoding;        /* VITS_ENC_* */
+    const float *ref_peak;   /* host [B] or NULL: row b is normalised by THIS peak (a stream cannot know its own) */
+    const float *volume;     /* host [B] or NULL (= 1.0f) */
+} vits_stream_format;
+typedef int (*vits_enc_chunk_fn)(void *user, const void *bytes, int B, int64_t row_pitch_bytes, int64_t first_sample,
+                                 int64_t n_samples, const int32_t *valid, const float *peak, int64_t total_samples);
+int vits_run_chunked_enc(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
+                         const vits_noise *noise, const vits_controls *ctl, const vits_stream_format *fmt,
+                         int chunk_frames, vits_enc_chunk_fn fn, void *user);
+int vits_run_vocoder_chunked_enc(vits_handle *h, const float *z, int B, int F, const int64_t *sid,
+                                 const vits_stream_format *fmt, int chunk_frames, vits_enc_chunk_fn fn, void *user);
+
 /* Size the handle's device workspaces NOW for requests of up to B utterances x T tokens that render up to F frames each
  * (the batch's longest utterance; T = 0 or F = 0 leaves that domain alone).  A run grows a workspace when a request
  * needs more than any before it - hipFree + hipMalloc of tens of GB at batch 32, a device-wide synchronisation that was
  * measured at 0.3 ms to 5 s - so a serving process calls this once at start-up with the largest request it admits (the
  * frame count of a batch depends on the durations the model predicts, i.e. on the noise as well: leave headroom), and no
- * request up to that size allocates device memory afterwards (vits_last_pcm16's int16 staging and vits_deliver's packed
- * buffer of such a request included).  onnxruntime has no counterpart (its arena grows the same way, voice.py:167-171 passes default
+ * request up to that size allocates device memory afterwards (vits_last_pcm16's int16 staging, vits_deliver's packed
+ * buffer and an encoded stream's chunk buffer of such a request included).  onnxruntime has no counterpart (its arena grows the same way, voice.py:167-171 passes default
  * SessionOptions); nothing in the reference needs to call it.
  * INVALIDATES THE LAST RUN'S RESULTS when a workspace actually grows: the device waveform, frame counts and taps of the
  * last run live in those workspaces, so after a growing vits_reserve (or any run that grows one) vits_fetch_output /
@@ -587,6 +631,15 @@ int vits_test_post_conv(int device_id, const float *x, int B, int C, int T, cons
  * launches the pipeline's kernels with the pipeline's grids.  Everything else as vits_deliver. */
 int vits_test_deliver(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_segment *segs, int n_segs,
                       int n_streams, int encoding, void *dst, size_t dst_bytes, int64_t *stream_samples, int64_t *stream_offsets);
+
+/* The encoded stream's kernel by value: x [B][S] host, counts [B] the rows' valid samples (within [0, S]; what lies behind
+ * must not show).  Columns [0, S) are cut into pieces of piece_samples samples (the last one shorter); each piece goes through
+ * the pipeline's kernel with the pipeline's grid.  The pieces' [B][pitch] blocks land back to back in bytes (bytes_cap >= their
+ * sum); pitches [piece], valid [piece][B] and peaks [piece][B] are per piece (max_pieces of each).  Returns the number of
+ * pieces. */
+int vits_test_stream_pack(int device_id, const float *x, const int64_t *counts, int B, int S, int piece_samples,
+                          const vits_stream_format *fmt, void *bytes, size_t bytes_cap, int64_t *pitches, int32_t *valid,
+                          float *peaks, int max_pieces);
 
 #ifdef __cplusplus
 }

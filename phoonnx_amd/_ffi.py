@@ -51,12 +51,21 @@ class VitsSegment(C.Structure):
                 ("volume", C.c_float)]
 
 
+class VitsStreamFormat(C.Structure):
+    _fields_ = [("encoding", C.c_int32), ("ref_peak", C.c_void_p), ("volume", C.c_void_p)]
+
+
 # name -> (VITS_ENC_* code, element type): audio_encoding lists the names in the order of the header's enum
 ENCODINGS = {name: (code, audio_encoding.DTYPES[name]) for code, name in enumerate(audio_encoding.ENCODINGS)}
 
 
 # int fn(void *user, const float *samples, int B, int64 first_sample, int64 n_samples, int64 total_samples)
 CHUNK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_int64, C.c_int64, C.c_int64)
+
+# int fn(void *user, const void *bytes, int B, int64 row_pitch_bytes, int64 first_sample, int64 n_samples,
+#        const int32 *valid, const float *peak, int64 total_samples)
+ENC_CHUNK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int32),
+                           C.POINTER(C.c_float), C.c_int64)
 
 VITS_E_RANGE = -6
 
@@ -76,6 +85,7 @@ EXPORTS = [
     "vits_set_output_rate", "vits_last_sample_counts", "vits_resample_plan", "vits_test_resample", "vits_test_resample_pieces",
     "vits_test_durations", "vits_test_expand_prior", "vits_test_fill_normal", "vits_test_fill_normal_rows", "vits_test_post_conv",
     "vits_delivery_plan", "vits_deliver", "vits_test_deliver",
+    "vits_run_chunked_enc", "vits_run_vocoder_chunked_enc", "vits_test_stream_pack",
 ]
 
 
@@ -140,6 +150,12 @@ def load():
     lib.vits_run_async_ctl.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.POINTER(VitsNoise), C.POINTER(VitsControls)]
     lib.vits_run_chunked_ctl.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.POINTER(VitsNoise), C.POINTER(VitsControls),
                                          C.c_int, CHUNK_FN, vp]
+    # (encoded twins: the vits_stream_format struct in front of chunk_frames, the encoded callback type)
+    lib.vits_run_chunked_enc.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.POINTER(VitsNoise), C.POINTER(VitsControls),
+                                         C.POINTER(VitsStreamFormat), C.c_int, ENC_CHUNK_FN, vp]
+    lib.vits_run_vocoder_chunked_enc.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.POINTER(VitsStreamFormat), C.c_int, ENC_CHUNK_FN, vp]
+    lib.vits_test_stream_pack.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(VitsStreamFormat), vp, C.c_size_t,
+                                          vp, vp, vp, C.c_int]
     lib.vits_last_durations.argtypes = [vp, i64p, C.c_size_t]
     lib.vits_set_output_rate.argtypes = [vp, C.c_int, C.c_int]
     lib.vits_last_sample_counts.argtypes = [vp, i64p, C.c_int]

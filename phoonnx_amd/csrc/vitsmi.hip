@@ -28,6 +28,7 @@
 #include "kernels.hip.hpp"
 #include "model.hpp"
 #include "resample.hip.hpp"
+#include "stream_pack.hip.hpp"
 #include "test_dev.hip.hpp"
 #include "workspace.hpp"
 
@@ -134,6 +135,9 @@ struct ChunkSink {
     int chunk_frames;
     vits_chunk_fn fn;
     void *user;
+    // the encoded form (vits_run_chunked_enc): fmt != nullptr, validated; the chunks go to efn, not to fn
+    const vits_stream_format *fmt = nullptr;
+    vits_enc_chunk_fn efn = nullptr;
 };
 
 constexpr int kMaxRangeLaunches = 512;
@@ -1791,14 +1795,26 @@ __global__ void chunk_len_kernel(const int *ylen, int *out, int B, int lo, int n
 
 // The staging slab carved for the resampled result of B rows of S_in input samples.  The run's inputs lived there: every
 // kernel that read them precedes the resampler on the stream (and a growing slab waits for the stream first).
-int resample_carve(vits_handle *h, int B, int64_t S_in, ResampleBufs &rb, int &S_out) {
+// (sp: an encoded stream's buffers behind them in the same walk, for chunks of at most min(sp_n_max, S_out) samples)
+int resample_carve(vits_handle *h, int B, int64_t S_in, ResampleBufs &rb, int &S_out, StreamPackBufs *sp = nullptr, int64_t sp_n_max = 0) {
     const ResamplePlan &p = h->rs.plan;
     const int64_t so = p.count(S_in);
     if (so > INT_MAX)
         return fail(h, VITS_E_ARG, "%lld samples at %d Hz are %lld samples at %d Hz: more than a row admits (%d)", (long long)S_in,
                     p.fi, (long long)so, p.fo, INT_MAX);
     S_out = (int)so;
+    if (sp)
+        return slab_carve(h, h->io, "staging", [&](Carver &cv) {
+            rb = carve_resample(cv, B, S_out, (int)p.K);
+            *sp = carve_stream_pack(cv, B, sp_n_max < so ? sp_n_max : so);
+        });
     return slab_carve(h, h->io, "staging", [&](Carver &cv) { rb = carve_resample(cv, B, S_out, (int)p.K); });
+}
+
+// output samples one chunk of `chunk` frames (of F) can complete at the output rate, at most S_out
+int64_t resample_emit_cap(const ResamplePlan &rp, int chunk, int F, int hop, int64_t S_out) {
+    const int64_t cap = rp.count((int64_t)(chunk < F ? chunk : F) * hop + rp.K / 2) + 2;
+    return cap < S_out ? cap : S_out;
 }
 
 // The whole waveform a run has just rendered (h->d_out, rows of h->S samples, ylen[b] * hop of them valid; no frame counts:
@@ -1852,15 +1868,30 @@ int render_chunks(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int
     ResampleBufs rb{};
     int S_out = 0, rs_gen = 0, emitted = 0;
     int64_t emit_cap = 0;
-    if (rs) {
+    // The encoded form of the sink: every chunk goes through stream_pack_kernel into the chunk buffer and reaches the ring as
+    // [B][pitch] bytes with the B running peaks behind them, in one copy.  enc == false executes what it always executed.
+    const bool enc = sink.fmt != nullptr;
+    const int enc_w = !enc ? 4 : (sink.fmt->encoding == VITS_ENC_PCM16 ? 2 : (sink.fmt->encoding == VITS_ENC_F32 ? 4 : 1));
+    StreamPackBufs sp{};
+    if (rs && enc) {
+        // (the chunk bound needs S_out, which the carve computes: state it from the same count)
+        const int64_t so = rp.count((int64_t)F * hop);
+        if (int rc = resample_carve(h, B, (int64_t)F * hop, rb, S_out, &sp, resample_emit_cap(rp, chunk, F, hop, so))) return rc;
+    } else if (rs) {
         if (int rc = resample_carve(h, B, (int64_t)F * hop, rb, S_out)) return rc;
-        emit_cap = rp.count((int64_t)(chunk < F ? chunk : F) * hop + rp.K / 2) + 2;  // output samples one chunk can complete
-        emit_cap = emit_cap < S_out ? emit_cap : S_out;
+    } else if (enc) {
+        if (int rc = slab_carve(h, h->io, "staging", [&](Carver &cv) { sp = carve_stream_pack(cv, B, (int64_t)(chunk < F ? chunk : F) * hop); }))
+            return rc;
+    }
+    if (rs) {
+        emit_cap = resample_emit_cap(rp, chunk, F, hop, S_out);  // output samples one chunk can complete
         resample_counts_kernel<<<(B + 63) / 64, 64, 0, st>>>(ylen, hop, F * hop, rp.L, rp.M, rb.n_in, rb.n_out, B);
         HIPCHECK(h, hipMemsetAsync(rb.carry[0], 0, (size_t)B * rp.K * sizeof(float), st));
         h->stats.total_launches++;
     }
-    const size_t ring_bytes = rs ? (size_t)B * emit_cap * sizeof(float) : (size_t)B * chunk * hop * sizeof(float);
+    const int64_t n_max = rs ? emit_cap : (int64_t)(chunk < F ? chunk : F) * hop;  // samples per row of the largest chunk
+    const size_t ring_bytes = enc ? (size_t)B * StreamPackBufs::pitch(enc_w, n_max) + StreamPackBufs::peak_floats(B) * sizeof(float)
+                              : rs ? (size_t)B * emit_cap * sizeof(float) : (size_t)B * chunk * hop * sizeof(float);
     if (ring_bytes > h->ring_cap) {
         for (auto &r : h->ring) {
             if (r) hipHostFree(r);
@@ -1881,10 +1912,53 @@ int render_chunks(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int
     const int64_t total = rs ? (int64_t)S_out : (int64_t)F * hop;
     int64_t pend_first = 0, pend_n = 0;
     int pend = -1, k = 0, stop = 0;
+    // encoded form: the rows' valid samples (host: the callback's valid[]; device: the kernel's), the per-run upload
+    // [zeros of the running peaks | {ref_peak, volume} per row] in one copy, and the launch + copy of one chunk
+    std::vector<int64_t> row_n;
+    std::vector<int32_t> valid;
+    StreamPackRows sp_rows{nullptr, 1, 0};
+    std::vector<float> up;  // (pageable source of an asynchronous copy: lives until the chunks behind it have been waited for)
+    if (enc) {
+        row_n.resize((size_t)B);
+        valid.resize((size_t)B);
+        for (int b = 0; b < B; b++) {
+            const int64_t nb = (int64_t)(ylen ? h->h_ylen[b] : F) * hop;
+            row_n[b] = rs ? rp.count(nb) : nb;
+        }
+        sp_rows = rs ? StreamPackRows{rb.n_out, 1, S_out} : StreamPackRows{ylen, hop, F * hop};
+        const size_t Bp = StreamPackBufs::peak_floats(B);
+        up.assign(Bp + 2 * (size_t)B, 0.f);
+        for (int b = 0; b < B; b++) {
+            up[Bp + 2 * b] = sink.fmt->ref_peak ? sink.fmt->ref_peak[b] : 1.0f;
+            up[Bp + 2 * b + 1] = sink.fmt->volume ? sink.fmt->volume[b] : 1.0f;
+        }
+        HIPCHECK(h, hipMemcpyAsync(sp.peak_run, up.data(), up.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    }
+    // x: the chunk's [B][n] at row pitch x_pitch, its first column sample `first` of the rows
+    auto pack_chunk = [&](const float *x, int64_t x_pitch, int64_t first, int64_t n, int slot) -> int {
+        const size_t pitch = StreamPackBufs::pitch(enc_w, n);
+        unsigned char *d = sp.at(B, pitch);
+        const hipError_t e = launch_stream_pack(sink.fmt->encoding, x, x_pitch, sp_rows, B, (int)first, (int)n, sp.fmt,
+                                                sink.fmt->ref_peak != nullptr, d, sp.peak_run, st);
+        if (e != hipSuccess) return fail(h, VITS_E_DEVICE, "stream pack launch failed: %s", hipGetErrorString(e));
+        h->stats.total_launches++;
+        HIPCHECK(h, hipMemcpyAsync(h->ring[slot], d, (size_t)B * pitch + (size_t)B * sizeof(float), hipMemcpyDeviceToHost, st));
+        return 0;
+    };
     auto deliver = [&]() -> int {  // hand the pending chunk to the caller
         if (pend < 0) return 0;
         if (hipEventSynchronize(h->ring_ev[pend]) != hipSuccess) return fail(h, VITS_E_DEVICE, "chunk copy failed");
-        stop = sink.fn ? sink.fn(sink.user, reinterpret_cast<const float *>(h->ring[pend]), B, pend_first, pend_n, total) : 0;
+        if (enc) {
+            const int64_t pitch = (int64_t)StreamPackBufs::pitch(enc_w, pend_n);
+            for (int b = 0; b < B; b++) {
+                const int64_t v = row_n[b] - pend_first;
+                valid[b] = (int32_t)(v < 0 ? 0 : (v > pend_n ? pend_n : v));
+            }
+            stop = sink.efn ? sink.efn(sink.user, h->ring[pend], B, pitch, pend_first, pend_n, valid.data(),
+                                       reinterpret_cast<const float *>(h->ring[pend] + (size_t)B * pitch), total)
+                            : 0;
+        } else
+            stop = sink.fn ? sink.fn(sink.user, reinterpret_cast<const float *>(h->ring[pend]), B, pend_first, pend_n, total) : 0;
         pend = -1;
         return 0;
     };
@@ -1934,7 +2008,10 @@ int render_chunks(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int
                 k ^= 1;
                 continue;
             }
-            HIPCHECK(h, hipMemcpyAsync(h->ring[k], rb.out, (size_t)B * ne * 4, hipMemcpyDeviceToHost, st));
+            if (enc) {
+                if (int rc = pack_chunk(rb.out, ne, emitted, ne, k)) return rc;
+            } else
+                HIPCHECK(h, hipMemcpyAsync(h->ring[k], rb.out, (size_t)B * ne * 4, hipMemcpyDeviceToHost, st));
             HIPCHECK(h, hipEventRecord(h->ring_ev[k], st));
             if (int rc = deliver()) return rc;
             pend = k;
@@ -1944,8 +2021,11 @@ int render_chunks(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int
             continue;
         }
         // interior of this chunk: samples [(f0 - lo) * hop, (f1 - lo) * hop) of every row -> ring[k] as [B, ns]
-        HIPCHECK(h, hipMemcpy2DAsync(h->ring[k], (size_t)ns * 4, h->d_out + (int64_t)(f0 - lo) * hop, (size_t)h->S * 4,
-                                     (size_t)ns * 4, B, hipMemcpyDeviceToHost, st));
+        if (enc) {
+            if (int rc = pack_chunk(h->d_out + (int64_t)(f0 - lo) * hop, h->S, (int64_t)f0 * hop, ns, k)) return rc;
+        } else
+            HIPCHECK(h, hipMemcpy2DAsync(h->ring[k], (size_t)ns * 4, h->d_out + (int64_t)(f0 - lo) * hop, (size_t)h->S * 4,
+                                         (size_t)ns * 4, B, hipMemcpyDeviceToHost, st));
         HIPCHECK(h, hipEventRecord(h->ring_ev[k], st));
         if (int rc = deliver()) return rc;  // (the previous chunk, while this one renders)
         pend = k;
@@ -2459,12 +2539,19 @@ int vits_reserve(vits_handle *h, int B, int T, int F) {
         const size_t io_in = carved_bytes([&](Carver &cv) { carve_inputs(cv, m, B, T, T, Fp); });
         const size_t io_pcm = carved_bytes([&](Carver &cv) { carve_pcm16(cv, B, F * m.hop); });
         const size_t io_dlv = carved_bytes([&](Carver &cv) { carve_delivery(cv, B, F * m.hop); });  // ... or vits_deliver's
+        // ... or an encoded stream's chunk buffer: every chunk_frames <= F, i.e. chunks of up to F * hop samples
+        const size_t io_sp = carved_bytes([&](Carver &cv) { carve_stream_pack(cv, B, (int64_t)F * m.hop); });
         size_t io = io_in > io_pcm ? io_in : io_pcm;
         io = io_dlv > io ? io_dlv : io;
+        io = io_sp > io ? io_sp : io;
         if (h->rs.plan.on()) {  // ... or the resampled waveform with its own 16-bit rendering and delivery buffers
             const int64_t so = h->rs.plan.count((int64_t)F * m.hop);
             if (so > INT_MAX) return fail(h, VITS_E_ARG, "vits_reserve: F=%d frames are %lld samples at %d Hz", F, (long long)so, h->rs.plan.fo);
-            const size_t io_rs = carved_bytes([&](Carver &cv) { carve_resample(cv, B, (int)so, (int)h->rs.plan.K); });
+            // (with the encoded stream's buffers behind them: chunks of up to `so` samples)
+            const size_t io_rs = carved_bytes([&](Carver &cv) {
+                carve_resample(cv, B, (int)so, (int)h->rs.plan.K);
+                carve_stream_pack(cv, B, so);
+            });
             io = io_rs > io ? io_rs : io;
         }
         if (int rc = slab_reserve(h, h->io, io, false)) return rc;
@@ -2762,12 +2849,11 @@ int vits_run(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int
     return rc;
 }
 
-static int run_chunked_locked(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const RunRows &rr,
-                              const int64_t *sid, const vits_noise *noise, int chunk_frames, vits_chunk_fn fn, void *user) {
-    if (!rr.scales || chunk_frames < 1) return fail(h, VITS_E_ARG, "bad chunked-run arguments");
+static int run_chunked_sink(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const RunRows &rr,
+                            const int64_t *sid, const vits_noise *noise, const ChunkSink &sink) {
+    if (!rr.scales || sink.chunk_frames < 1) return fail(h, VITS_E_ARG, "bad chunked-run arguments");
     Staged sg;
     int rc = stage_inputs(h, ids, lens, B, T, sid, noise, sg);
-    const ChunkSink sink{chunk_frames, fn, user};
     if (rc == VITS_OK)
         rc = run_device_locked(h, sg.d_ids, sg.d_lens, B, T, rr, sg.d_sid, sg.has_noise ? &sg.dn : nullptr, nullptr, &sink);
     if (hipStreamSynchronize(h->stream) != hipSuccess && rc == VITS_OK)
@@ -2775,6 +2861,38 @@ static int run_chunked_locked(vits_handle *h, const int64_t *ids, const int64_t 
     // (chunks are handed out as they finish; a range violation is therefore reported after the fact)
     if (rc == VITS_OK) rc = range_check(h);
     return rc;
+}
+
+static int run_chunked_locked(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const RunRows &rr,
+                              const int64_t *sid, const vits_noise *noise, int chunk_frames, vits_chunk_fn fn, void *user) {
+    return run_chunked_sink(h, ids, lens, B, T, rr, sid, noise, ChunkSink{chunk_frames, fn, user});
+}
+
+// vits_stream_format, checked on the host before anything else looks at the call (vitsmi.h, "encoded streaming")
+static int host_stream_format(vits_handle *h, const vits_stream_format *fmt, int B) {
+    if (!fmt) return fail(h, VITS_E_ARG, "null stream format");
+    if (fmt->encoding < VITS_ENC_PCM16 || fmt->encoding > VITS_ENC_F32) return fail(h, VITS_E_ARG, "unknown encoding %d", (int)fmt->encoding);
+    for (int b = 0; b < B; b++) {
+        if (fmt->volume && !std::isfinite(fmt->volume[b])) return fail(h, VITS_E_ARG, "volume[%d] = %g is not finite", b, (double)fmt->volume[b]);
+        if (fmt->ref_peak && !(std::isfinite(fmt->ref_peak[b]) && fmt->ref_peak[b] >= 0.f))
+            return fail(h, VITS_E_ARG, "ref_peak[%d] = %g is not a finite value >= 0", b, (double)fmt->ref_peak[b]);
+    }
+    return VITS_OK;
+}
+
+int vits_run_chunked_enc(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
+                         const vits_noise *noise, const vits_controls *ctl, const vits_stream_format *fmt, int chunk_frames,
+                         vits_enc_chunk_fn fn, void *user) {
+    if (!h) return VITS_E_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (int rc = host_stream_format(h, fmt, B)) return rc;  // (pure host code: a host-only handle answers it too)
+    if (int rc = check_dev(h)) return rc;
+    RunRows rr;
+    if (int rc = host_controls(h, ctl, lens, B, T, rr)) return rc;
+    ChunkSink sink{chunk_frames, nullptr, user};
+    sink.fmt = fmt;
+    sink.efn = fn;
+    return run_chunked_sink(h, ids, lens, B, T, rr, sid, noise, sink);
 }
 
 int vits_run_chunked(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const float scales[3],
@@ -3023,6 +3141,19 @@ int vits_run_vocoder_chunked(vits_handle *h, const float *z, int B, int F, const
     std::lock_guard<std::mutex> lk(h->mu);
     if (chunk_frames < 1) return fail(h, VITS_E_ARG, "bad vocoder arguments");
     const ChunkSink sink{chunk_frames, fn, user};
+    return vocoder_common(h, z, B, F, sid, nullptr, &sink);
+}
+
+int vits_run_vocoder_chunked_enc(vits_handle *h, const float *z, int B, int F, const int64_t *sid, const vits_stream_format *fmt,
+                                 int chunk_frames, vits_enc_chunk_fn fn, void *user) {
+    if (!h) return VITS_E_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (int rc = host_stream_format(h, fmt, B)) return rc;
+    if (int rc = check_dev(h)) return rc;
+    if (chunk_frames < 1) return fail(h, VITS_E_ARG, "bad vocoder arguments");
+    ChunkSink sink{chunk_frames, nullptr, user};
+    sink.fmt = fmt;
+    sink.efn = fn;
     return vocoder_common(h, z, B, F, sid, nullptr, &sink);
 }
 
@@ -3821,6 +3952,67 @@ int vits_test_deliver(int device_id, const float *x, const int64_t *counts, int 
     TCHECK(done);
     delivery_report(p, stream_samples, stream_offsets);
     return VITS_OK;
+}
+
+int vits_test_stream_pack(int device_id, const float *x, const int64_t *counts, int B, int S, int piece_samples,
+                          const vits_stream_format *fmt, void *bytes, size_t bytes_cap, int64_t *pitches, int32_t *valid, float *peaks,
+                          int max_pieces) {
+    if (!x || !counts || !bytes || !pitches || !valid || !peaks || B <= 0 || B > 65535 || S <= 0 || piece_samples < 1 ||
+        (int64_t)B * S > (int64_t)1 << 40)
+        return fail(nullptr, VITS_E_ARG, "bad stream pack test arguments");
+    for (int b = 0; b < B; b++)
+        if (counts[b] < 0 || counts[b] > S) return fail(nullptr, VITS_E_ARG, "counts[%d] = %lld outside [0, %d]", b, (long long)counts[b], S);
+    if (int rc = host_stream_format(nullptr, fmt, B)) return rc;
+    const int w = fmt->encoding == VITS_ENC_PCM16 ? 2 : (fmt->encoding == VITS_ENC_F32 ? 4 : 1);
+    const int64_t pieces = ((int64_t)S + piece_samples - 1) / piece_samples;
+    size_t need = 0;
+    for (int64_t f0 = 0; f0 < S; f0 += piece_samples)
+        need += (size_t)B * StreamPackBufs::pitch(w, S - f0 > piece_samples ? piece_samples : S - f0);
+    if (pieces > max_pieces || need > bytes_cap)
+        return fail(nullptr, VITS_E_ARG, "%lld pieces of %zu bytes: room for %d pieces and %zu bytes", (long long)pieces, need, max_pieces, bytes_cap);
+    if (int rc = test_dev(device_id)) return rc;
+    DevBufs D;
+    float *dx = D.up(x, (size_t)B * S);
+    std::vector<int> c32((size_t)B);
+    for (int b = 0; b < B; b++) c32[b] = (int)counts[b];
+    int *dcount = D.up(c32.data(), (size_t)B);
+    // the pipeline's buffer, by the pipeline's walk
+    const int64_t n_max = piece_samples < S ? piece_samples : S;
+    const size_t total = carved_bytes([&](Carver &cv) { carve_stream_pack(cv, B, n_max); });
+    unsigned char *slab = D.alloc<unsigned char>(total);
+    TCHECK(D.err);
+    Carver cv(slab, total);
+    const StreamPackBufs sp = carve_stream_pack(cv, B, n_max);
+    if (!cv.fits()) return fail(nullptr, VITS_E_NOMEM, "stream pack walk carved %zu of %zu bytes", cv.used, cv.cap);
+    const size_t Bp = StreamPackBufs::peak_floats(B);
+    std::vector<float> up(Bp + 2 * (size_t)B, 0.f);
+    for (int b = 0; b < B; b++) {
+        up[Bp + 2 * b] = fmt->ref_peak ? fmt->ref_peak[b] : 1.0f;
+        up[Bp + 2 * b + 1] = fmt->volume ? fmt->volume[b] : 1.0f;
+    }
+    TCHECK(hipMemcpy(sp.peak_run, up.data(), up.size() * sizeof(float), hipMemcpyHostToDevice));
+    const StreamPackRows rows{dcount, 1, S};
+    unsigned char *dst = static_cast<unsigned char *>(bytes);
+    std::vector<unsigned char> landing;
+    int k = 0;
+    for (int64_t f0 = 0; f0 < S; f0 += piece_samples, k++) {
+        const int64_t n = S - f0 > piece_samples ? piece_samples : S - f0;
+        const size_t pitch = StreamPackBufs::pitch(w, n);
+        unsigned char *d = sp.at(B, pitch);
+        TCHECK(launch_stream_pack(fmt->encoding, dx + f0, S, rows, B, (int)f0, (int)n, sp.fmt, fmt->ref_peak != nullptr, d, sp.peak_run, nullptr));
+        TCHECK(hipDeviceSynchronize());
+        landing.resize((size_t)B * pitch + (size_t)B * sizeof(float));
+        TCHECK(hipMemcpy(landing.data(), d, landing.size(), hipMemcpyDeviceToHost));  // bytes and peaks in one copy, as the pipeline
+        std::memcpy(dst, landing.data(), (size_t)B * pitch);
+        std::memcpy(peaks + (size_t)k * B, landing.data() + (size_t)B * pitch, (size_t)B * sizeof(float));
+        dst += (size_t)B * pitch;
+        pitches[k] = (int64_t)pitch;
+        for (int b = 0; b < B; b++) {
+            const int64_t v = counts[b] - f0;
+            valid[(size_t)k * B + b] = (int32_t)(v < 0 ? 0 : (v > n ? n : v));
+        }
+    }
+    return k;
 }
 
 int vits_test_resample_pieces(int device_id, const float *x, const int64_t *lens, int B, int S, int in_rate, int out_rate,

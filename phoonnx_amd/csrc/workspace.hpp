@@ -278,4 +278,32 @@ inline ResampleBufs carve_resample(Carver &cv, int B, int S_out, int K) {
     return r;
 }
 
+// An encoded stream (vits_run_chunked_enc): one device buffer [chunk bytes | running peaks | format table].  `cap` bytes hold
+// the largest chunk in the widest encoding - B rows of n_max samples as F32 at a 16-byte row pitch - whatever encoding and
+// chunk_frames a call brings; the running peaks [B] (padded to whole 16-byte cells) sit right behind at a 16-byte-aligned
+// offset and never move, and a chunk's [B][pitch] bytes END at them (at()), so one copy of B * pitch + 4 * B bytes carries a
+// chunk and its peaks.  Behind the peaks: {ref_peak, volume} per row, uploaded with the peaks' zeros in one copy per run.
+// In a resampled run it is carved behind carve_resample's buffers in the same walk of the staging slab (the chunk it
+// packs lives there); in a native run from the slab's base, like vits_deliver's buffers: the run's inputs are consumed.
+struct StreamPackBufs {
+    unsigned char *buf;
+    size_t cap;
+    unsigned *peak_run;
+    float *fmt;
+    static size_t pitch(int width, int64_t n) { return (size_t)(((int64_t)width * n + 15) & ~(int64_t)15); }
+    static size_t peak_floats(int B) { return ((size_t)B + 3) & ~size_t(3); }
+    unsigned char *at(int B, size_t row_pitch) const { return buf + cap - (size_t)B * row_pitch; }  // row_pitch <= pitch(4, n_max)
+};
+
+inline StreamPackBufs carve_stream_pack(Carver &cv, int B, int64_t n_max) {
+    StreamPackBufs s{};
+    s.cap = (size_t)B * StreamPackBufs::pitch(4, n_max);
+    s.buf = cv.take<unsigned char>(s.cap + (StreamPackBufs::peak_floats(B) + 2 * (size_t)B) * sizeof(float));
+    if (s.buf) {
+        s.peak_run = reinterpret_cast<unsigned *>(s.buf + s.cap);
+        s.fmt = reinterpret_cast<float *>(s.peak_run) + StreamPackBufs::peak_floats(B);
+    }
+    return s;
+}
+
 }  // namespace vitsmi

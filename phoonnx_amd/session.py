@@ -296,6 +296,48 @@ def delivery_plan(counts, segments, n_streams=None, encoding="pcm16"):
     return {"stream_samples": samples, "stream_offsets": offsets, "total_bytes": int(total.value)}
 
 
+@dataclass
+class EncodedChunk:
+    """One chunk of an encoded stream (vitsmi.h, "encoded streaming"): `data` [B, n] in the encoding's dtype - row b holds
+    valid[b] encoded samples and silence behind them - covering samples [first_sample, first_sample + n) of the rows;
+    peak[b]: the running max |x| of row b's valid samples so far (before any gain)."""
+    first_sample: int
+    data: np.ndarray
+    valid: np.ndarray
+    peak: np.ndarray
+    total_samples: int
+
+
+def _stream_format(encoding, ref_peak, volume, B):
+    """The vits_stream_format struct of an encoded stream: `ref_peak` / `volume` None, a scalar (every row) or [B] floats.
+    Like _controls the struct holds the arrays it points into (`_keep`).  Returns (struct, dtype); raises SessionError naming
+    the argument, the row and the value before anything reaches the handle (the engine checks the same once more)."""
+    code, dtype = _encoding(encoding)
+    fmt = _ffi.VitsStreamFormat()
+    fmt.encoding = code
+    keep = []
+    for name, val in (("ref_peak", ref_peak), ("volume", volume)):
+        if val is None:
+            keep.append(None)
+            continue
+        try:
+            arr = np.asarray(val, np.float32)
+        except (TypeError, ValueError):
+            raise SessionError(f"Unexpected input: '{name}' must be a float or floats of shape [batch_size]") from None
+        if arr.shape not in ((), (B,)):
+            raise SessionError(f"Invalid shape for '{name}': {arr.shape}, expected a scalar or [batch_size] = {(B,)}")
+        arr = np.ascontiguousarray(np.broadcast_to(arr, (B,)), np.float32)
+        ok = np.isfinite(arr) if name == "volume" else np.isfinite(arr) & (arr >= 0)
+        bad = np.flatnonzero(~ok)
+        if bad.size:
+            what = "is not finite" if name == "volume" else "is not a finite value >= 0"
+            raise SessionError(f"{name}[{int(bad[0])}]={float(arr[bad[0]])} {what}")
+        keep.append(arr)
+        setattr(fmt, name, arr.ctypes.data)
+    fmt._keep = tuple(keep)
+    return fmt, dtype
+
+
 def _rows(scales, B):
     """[3] -> [B, 3] (the row twins of the C ABI take one row per utterance)"""
     return np.ascontiguousarray(np.broadcast_to(scales, (B, 3)) if scales.ndim == 1 else scales, np.float32)
@@ -625,9 +667,11 @@ class MiSession:
                 self._lib.vits_free_output(self._h, C.byref(out))
 
     # ------------------------------------------------------------------ chunked (streaming) rendering, SURVEY §8 f1
-    def _stream(self, start):
-        """Run `start(callback)` (a blocking C call) on a worker thread and yield (first_sample, samples [B, n]) as the
-        engine hands chunks over: the consumer works on chunk i while chunk i + 1 renders."""
+    def _stream(self, start, wrap=None):
+        """Run `start(callback)` (a blocking C call) on a worker thread and yield (first_sample, samples [B, n], total) as
+        the engine hands chunks over: the consumer works on chunk i while chunk i + 1 renders.  `wrap` (callback type,
+        function of the callback's arguments behind `user` -> the item to yield) replaces the fp32 chunk callback by
+        another one; stop flag, bounded queue and lock ownership are the same for both."""
         import queue
         import threading
         if getattr(self, "_stream_owner", None) == threading.get_ident():
@@ -644,11 +688,16 @@ class MiSession:
                 except queue.Full:
                     pass
 
-        @_ffi.CHUNK_FN
-        def on_chunk(user, samples, B, first, n, total):
+        def fp32_chunk(samples, B, first, n, total):
+            return int(first), np.ctypeslib.as_array(samples, shape=(B * n,)).reshape(B, n).copy(), int(total)
+
+        fn_type, item_of = wrap if wrap is not None else (_ffi.CHUNK_FN, fp32_chunk)
+
+        @fn_type
+        def on_chunk(user, *args):
             if stop.is_set():
                 return 1  # the consumer is gone: end the run (vits_chunk_fn's "stop" return)
-            put((int(first), np.ctypeslib.as_array(samples, shape=(B * n,)).reshape(B, n).copy(), int(total)))
+            put(item_of(*args))
             return 1 if stop.is_set() else 0
 
         def work():
@@ -678,7 +727,7 @@ class MiSession:
                     break
                 if isinstance(item, BaseException):
                     raise item
-                if len(item) == 2:
+                if isinstance(item, tuple) and len(item) == 2:
                     cls = RangeError if item[0] == _ffi.VITS_E_RANGE else SessionError
                     raise cls(f"chunked run failed [{item[0]}]: {item[1]}")
                 yield item
@@ -730,6 +779,63 @@ class MiSession:
         return self._stream(lambda cb: self._lib.vits_run_chunked_rows(
             self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(rows), _ffi.ptr(sid), C.byref(noise), _ffi.ptr(seeds),
             int(chunk_frames), cb, None))
+
+    @staticmethod
+    def _encoded_items(dtype):
+        """_stream's `wrap` of an encoded run: the callback type and the EncodedChunk of one call - `data` is a copy cut from
+        the pitched rows (the engine's buffer is only valid during the call)."""
+        width = np.dtype(dtype).itemsize
+
+        def item(data, B, pitch, first, n, valid, peak, total):
+            raw = np.ctypeslib.as_array(C.cast(data, C.POINTER(C.c_uint8)), shape=(B * pitch,)).reshape(B, pitch)
+            rows = np.array(raw[:, :n * width]).view(dtype).reshape(B, n)   # (np.array: a copy also where the pitch is n * width)
+            return EncodedChunk(int(first), rows, np.ctypeslib.as_array(valid, shape=(B,)).copy(),
+                                np.ctypeslib.as_array(peak, shape=(B,)).copy(), int(total))
+
+        return _ffi.ENC_CHUNK_FN, item
+
+    def synthesize_stream_encoded(self, ids, lens, scales, sid=None, chunk_frames: int = 64, encoding="pcm16", ref_peak=None,
+                                  volume=None, noise_dp=None, noise_z=None, seeds=None, durations=None, token_rate=None):
+        """synthesize_stream with every chunk post-processed, encoded and masked to each row's own length on the device
+        (vitsmi.h, "encoded streaming"): yields EncodedChunk.  encoding "pcm16" / "ulaw" / "alaw" / "f32"; `volume` and
+        `ref_peak` None, a scalar or [B]: row b is scaled by volume[b] and - with ref_peak - normalised by ref_peak[b] (a
+        stream cannot know its own peak: feed back the final `peak` of an earlier stream with the same seeds, or a
+        calibrated one).  The same chunk ranges as synthesize_stream, at the session's output rate; each row's valid
+        elements, joined, are what deliver() gives for that row (normalize 0, or 1 with ref_peak = its peak)."""
+        ids = np.ascontiguousarray(ids, np.int64)
+        lens = np.ascontiguousarray(lens, np.int64)
+        B, T = ids.shape
+        fmt, dtype = _stream_format(encoding, ref_peak, volume, B)
+        scales, seeds = _settings(np.ascontiguousarray(scales, np.float32), B, seeds)
+        durations, token_rate = _timing(durations, token_rate, lens, B, T)
+        sid = None if sid is None else np.ascontiguousarray(sid, np.int64)
+        noise = _ffi.VitsNoise()
+        noise.seed = self._seed
+        # (as synthesize_stream: every host array the C call reads on the worker thread belongs to the closure)
+        keep = noise._keep = []
+        if noise_dp is not None:
+            keep.append(np.ascontiguousarray(noise_dp, np.float32))
+            noise.noise_dp = keep[-1].ctypes.data
+        if noise_z is not None:
+            keep.append(np.ascontiguousarray(noise_z, np.float32))
+            noise.noise_z = keep[-1].ctypes.data
+            noise.noise_z_stride = keep[-1].shape[2]
+        ctl = _controls(_rows(scales, B), seeds, durations, token_rate)
+        return self._stream(lambda cb: self._lib.vits_run_chunked_enc(
+            self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(sid), C.byref(noise), C.byref(ctl), C.byref(fmt),
+            int(chunk_frames), cb, None), self._encoded_items(dtype))
+
+    def vocoder_stream_encoded(self, z, sid=None, chunk_frames: int = 64, encoding="pcm16", ref_peak=None, volume=None):
+        """Vocoder only, chunked and encoded: yields EncodedChunk (every row has F * hop samples, or their count at the
+        output rate)."""
+        z = np.ascontiguousarray(z, np.float32)
+        B, Cc, F = z.shape
+        fmt, dtype = _stream_format(encoding, ref_peak, volume, B)
+        if Cc != self.hparam("inter"):
+            raise SessionError(f"z must have {self.hparam('inter')} channels")
+        sid = None if sid is None else np.ascontiguousarray(sid, np.int64)
+        return self._stream(lambda cb: self._lib.vits_run_vocoder_chunked_enc(
+            self._h, _ffi.ptr(z), B, F, _ffi.ptr(sid), C.byref(fmt), int(chunk_frames), cb, None), self._encoded_items(dtype))
 
     def vocoder_stream(self, z, sid=None, chunk_frames: int = 64):
         """Vocoder only, chunked: yields (first_sample, float32 [B, n], total_samples)."""
@@ -1546,6 +1652,35 @@ def test_resample_pieces(x, lens, in_rate, out_rate, piece_samples, device_id=0)
     if n < 0:
         raise SessionError(f"vits_test_resample_pieces failed [{n}]: {_ffi.last_error(None)}")
     return y, [(int(a), int(b)) for a, b in ranges[:n]]
+
+
+def test_stream_pack(x, counts, piece_samples, encoding="pcm16", ref_peak=None, volume=None, device_id=0):
+    """vits_test_stream_pack: x [B, S] float32 and the rows' valid samples through the encoded stream's kernel, `piece_samples`
+    columns at a time -> one EncodedChunk per piece, with `data` the whole pitched block as uint8 [B, pitch] (pad bytes
+    included: they are part of what the kernel writes)."""
+    x = np.ascontiguousarray(x, np.float32)
+    counts = np.ascontiguousarray(counts, np.int64)
+    B, S = x.shape
+    fmt, dtype = _stream_format(encoding, ref_peak, volume, B)
+    w, piece = np.dtype(dtype).itemsize, int(piece_samples)
+    if piece < 1:
+        raise SessionError(f"piece_samples = {piece} is not positive")
+    sizes = [min(piece, S - f0) for f0 in range(0, S, piece)]
+    pitch = [-(-w * n // 16) * 16 for n in sizes]
+    out = np.full(B * sum(pitch), 0xA5, np.uint8)
+    pitches = np.zeros(len(sizes), np.int64)
+    valid = np.full((len(sizes), B), -1, np.int32)
+    peaks = np.full((len(sizes), B), np.nan, np.float32)
+    n = _ffi.load().vits_test_stream_pack(device_id, _ffi.ptr(x), _ffi.ptr(counts), B, S, piece, C.byref(fmt), _ffi.ptr(out),
+                                          out.nbytes, _ffi.ptr(pitches), _ffi.ptr(valid), _ffi.ptr(peaks), len(sizes))
+    if n < 0:
+        raise SessionError(f"vits_test_stream_pack failed [{n}]: {_ffi.last_error(None)}")
+    chunks, off = [], 0
+    for k in range(n):
+        p = int(pitches[k])
+        chunks.append(EncodedChunk(k * piece, out[off:off + B * p].reshape(B, p), valid[k], peaks[k], S))
+        off += B * p
+    return chunks
 
 
 # ---- the token-to-frame and frame-to-sample kernels by value (include/vitsmi.h: vits_test_durations ...) ----------------

@@ -527,6 +527,96 @@ class TTSVoice:
                 aligned.append(al)
         return ae.EncodedAudio(data, encoding, self.sample_rate, starts, counts, aligned)
 
+    def stream_encoded(self, text: str, syn_config: Optional[SynthesisConfig] = None, encoding: str = "pcm16",
+                       chunk_frames: int = 64, sentence_silence: float = 0.0, ref_peak=None):
+        """Extension: synthesize_encoded's ONE stream as a generator of `bytes`, handed out while the audio still renders.
+        All sentences render as one chunked batch (MiSession.synthesize_stream_encoded: post-processing, encoding and the
+        masking to each sentence's own length happen on the device, per chunk).  Sentence 0's chunks are yielded as they
+        arrive, behind its pause; the later sentences' bytes are kept on the host and yielded - each behind its pause - once
+        their predecessor is complete.  Joined, the pieces are synthesize_encoded(...).data.tobytes() for the same audio.
+        A stream cannot know its own peak: syn_config.normalize_audio needs `ref_peak` (a float, or one per sentence - the
+        peak each sentence is normalised by, e.g. the final EncodedChunk.peak of an earlier stream with the same seeds) and
+        raises ValueError without one; with normalize_audio off, ref_peak is not used.  volume is the config's.  A session
+        without synthesize_stream_encoded gets the same bytes from the host encoder: over synthesize_stream's chunks where
+        that exists, else over the whole rendering."""
+        from . import audio_encoding as ae
+        cfg = syn_config if syn_config is not None else SynthesisConfig()
+        ae._check(encoding)
+        lead = self._lead_samples(sentence_silence)
+        if cfg.normalize_audio and ref_peak is None:
+            raise ValueError("a stream cannot know its own peak: pass ref_peak (the peak to normalise by), or switch "
+                             "normalize_audio off")
+        if int(chunk_frames) < 1:
+            raise ValueError(f"chunk_frames must be >= 1 (got {chunk_frames})")
+        return self._stream_encoded(text, cfg, encoding, int(chunk_frames), lead, ref_peak)
+
+    def _stream_encoded(self, text, cfg, encoding, chunk_frames, lead, ref_peak):
+        from . import audio_encoding as ae
+        from .sharding import pad_batch
+        all_ids = self._sentence_ids(text, cfg)
+        B = len(all_ids)
+        if not B:
+            return
+        peaks = None
+        if cfg.normalize_audio:
+            peaks = np.asarray(ref_peak, np.float32)
+            if peaks.shape not in ((), (B,)):
+                raise ValueError(f"ref_peak must be a float or one per sentence ({B}), got shape {peaks.shape}")
+            peaks = np.ascontiguousarray(np.broadcast_to(peaks, (B,)))
+        volume = float(cfg.volume)
+        pause = ae.silence(lead, encoding).tobytes()
+        session = self.session
+
+        def host_bytes(b, audio):
+            return ae.encode(self._scaled(audio, None if peaks is None else peaks[b], volume), encoding).tobytes()
+
+        streams = hasattr(session, "synthesize_stream_encoded") or hasattr(session, "synthesize_stream")
+        if not streams:  # the whole rendering, sentence by sentence through the host encoder
+            if hasattr(session, "synthesize_batch"):
+                audios = self.phoneme_ids_batch_to_audio(all_ids, cfg)
+            else:
+                audios = (self.phoneme_ids_to_audio(ids, cfg) for ids in all_ids)
+            for b, a in enumerate(audios):
+                yield pause + host_bytes(b, np.atleast_1d(a))
+            return
+        ids, lens = pad_batch(all_ids)
+        expected = [i.name for i in session.get_inputs()]
+        if "sid" in expected:  # (checked before anything runs, as synthesize_encoded does)
+            n_spk = int(session.hparam("n_speakers")) if hasattr(session, "hparam") else self.config.num_speakers
+            if not 0 <= (cfg.speaker_id or 0) < max(n_spk, 1):
+                raise ValueError(f"speaker_id {cfg.speaker_id or 0} is out of range [0, {max(n_spk, 1)})")
+        sid = np.full((B,), cfg.speaker_id or 0, np.int64) if "sid" in expected else None
+        if hasattr(session, "synthesize_stream_encoded"):
+            chunks = ((c.first_sample, c.data.shape[1], c.total_samples, c.valid, [c.data[b, :int(c.valid[b])].tobytes() for b in range(B)])
+                      for c in session.synthesize_stream_encoded(ids, lens, self._scales(cfg), sid, chunk_frames=chunk_frames,
+                                                                 encoding=encoding, ref_peak=peaks, volume=volume))
+        else:
+            def host_chunks():
+                counts = None
+                for first, x, total in session.synthesize_stream(ids, lens, self._scales(cfg), sid, chunk_frames=chunk_frames):
+                    if counts is None:  # (known from the first chunk on)
+                        counts = (np.asarray(session.last_sample_counts(), np.int64) if hasattr(session, "last_sample_counts")
+                                  else np.asarray(session.last_y_lengths(), np.int64) * session.hparam("hop"))
+                    n = x.shape[1]
+                    valid = np.clip(counts - first, 0, n)
+                    yield first, n, total, valid, [host_bytes(b, x[b, :int(valid[b])]) for b in range(B)]
+            chunks = host_chunks()
+        cur, kept = 0, [[] for _ in range(B)]
+        if pause:
+            yield pause
+        for first, n, total, valid, rows in chunks:
+            if rows[cur]:
+                yield rows[cur]
+            for b in range(cur + 1, B):
+                kept[b].append(rows[b])
+            # a sentence is complete once a chunk holds less of it than the chunk is long, or the stream ends
+            while cur + 1 < B and (int(valid[cur]) < n or first + n >= total):
+                cur += 1
+                yield pause + b"".join(kept[cur])
+                kept[cur] = []
+        for b in range(cur + 1, B):  # (a stream that ended early: what was kept still goes out in order)
+            yield pause + b"".join(kept[b])
+
     def synthesize_requests_encoded(self, requests: Sequence[Tuple[str, Optional[SynthesisConfig]]],
                                     seeds: Optional[Sequence[int]] = None, max_batch: int = 32, encoding: str = "pcm16",
                                     sentence_silence: float = 0.0, alignments: bool = False):
