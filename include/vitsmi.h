@@ -447,6 +447,58 @@ int vits_delivery_plan(const int64_t *counts, int B, const vits_segment *segs, i
 int vits_deliver(vits_handle *h, const vits_segment *segs, int n_segs, int n_streams, int encoding, void *dst, size_t dst_bytes,
                  int64_t *stream_samples, int64_t *stream_offsets);
 
+/* ---- trimmed delivery: the delivery with the near-silence at either end of a row cut off on the device, and trailing silence ----
+ * A VITS voice renders a stretch of near-silence in front of and behind every sentence.  The entries below are vits_deliver
+ * with that stretch found by a scan on the device and left out of what is encoded, packed and copied, and with silence
+ * behind a segment as well as in front of it.  One vits_trim runs parallel to each vits_segment; the text below is the
+ * specification.
+ *
+ * For a segment on row b with n = n_b valid samples (as in the delivery) and trim t:
+ *   peak_all = max |x[b][i]| over i < n, fmaxf semantics; 0 for n = 0
+ *   thr      = t.threshold (mode 1) | t.threshold * peak_all, one fp32 product (mode 2)
+ *   sample i < n is ACTIVE iff fabsf(x[b][i]) > thr - strictly: a sample equal to the threshold is not active.  Whatever
+ *   lies behind n never enters.
+ *   mode 0:            a = 0, c = n
+ *   no active sample:  a = 0, c = 0
+ *   otherwise, f the first and l the last active index:  a = max(0, f - keep_lead), e = min(n, l + 1 + keep_tail),
+ *                      c = e - a  (all in int64)
+ * The segment contributes lead_samples of silence, the encoded samples x[b][a .. a + c), and tail_samples of silence
+ * (silence bytes as in the delivery).  peak_row of the delivery's sample formula is taken over the kept range [a, a + c);
+ * normalize 2 takes the max of those kept-range peaks over the stream's normalize-2 segments.  The sample formula and the
+ * encoders are unchanged.  N_j = sum (lead + c + tail).
+ * So: with trims == NULL, or with every trim at mode 0 and tail_samples 0, the bytes, stream_samples and stream_offsets
+ * are vits_deliver's, bit for bit; a row's bytes depend on that row alone (with normalize 2: on the stream's other rows
+ * too); tails mode, batch layout and output rate enter only through x and n_b.
+ * Device side (csrc/delivery.hip.hpp): delivery_peak_kernel over the untrimmed rows for peak_all (only when a segment uses
+ * mode 2), delivery_trim_scan_kernel (min / max of the active indices: order-independent, hence repeatable), one small copy
+ * of the bounds to the host, vits_trim_range per segment and the plan there, then the delivery's two kernels over the kept
+ * ranges.
+ * Validation happens on the host before anything is enqueued or allocated; VITS_E_ARG, the message naming the segment
+ * index and the value: mode outside 0..2; a threshold that is not finite or negative; a negative keep_lead or keep_tail;
+ * tail_samples outside [0, INT_MAX]; everything vits_deliver refuses.  A rejected call leaves the last run deliverable.
+ * Not covered: the encoded stream (its chunks share one first_sample timeline, and a stream cannot know where its audio
+ * ends), fades, loudness (RMS) levelling. */
+typedef struct {
+    int32_t mode;          /* 0 off; 1 absolute: thr = threshold; 2 relative: thr = threshold * peak_all (one fp32 product) */
+    float   threshold;     /* finite, >= 0 */
+    int32_t keep_lead;     /* samples kept in front of the first active sample, >= 0 */
+    int32_t keep_tail;     /* samples kept behind the last active sample, >= 0 */
+    int64_t tail_samples;  /* silence behind the segment at the delivered rate, [0, INT_MAX] */
+} vits_trim;
+/* pure host code: the rule above.  n in [0, INT_MAX]; first_active > last_active means "none active", otherwise
+ * 0 <= first_active <= last_active < n. */
+int vits_trim_range(int64_t n, int64_t first_active, int64_t last_active, const vits_trim *t, int64_t *a, int64_t *c);
+/* pure host code: vits_delivery_plan over kept counts (kept[b]: row b's c), with the tails of trims (nullable) */
+int vits_delivery_plan_trimmed(const int64_t *kept, int B, const vits_segment *segs, const vits_trim *trims, int n_segs,
+                               int n_streams, int encoding, int64_t *stream_samples, int64_t *stream_offsets, int64_t *total_bytes);
+/* vits_deliver with trims [n_segs] (or NULL: none).  Input run, waiting, VITS_E_RANGE and repeatability as vits_deliver.
+ * kept_first / kept_count [n_segs] (each nullable) receive every segment's a and c.  The layout depends on the data, so
+ * dst == NULL too waits for the run and runs the scan: it reports the layout and the kept ranges, packs nothing and
+ * writes to no dst.  dst_bytes < total: VITS_E_ARG, the message states the bytes needed, dst is untouched. */
+int vits_deliver_trimmed(vits_handle *h, const vits_segment *segs, const vits_trim *trims, int n_segs, int n_streams, int encoding,
+                         void *dst, size_t dst_bytes, int64_t *stream_samples, int64_t *stream_offsets, int64_t *kept_first,
+                         int64_t *kept_count);
+
 /* ---- encoded streaming: a chunked run's chunks post-processed, encoded and masked on the device --------------------------
  * vits_run_chunked* hands every chunk over as fp32 [B][n]; vits_deliver refuses a chunked run.  The two entries below are the
  * chunked runs with the delivery's post-processing and encoders applied per chunk, by one more launch per chunk
@@ -631,6 +683,12 @@ int vits_test_post_conv(int device_id, const float *x, int B, int C, int T, cons
  * launches the pipeline's kernels with the pipeline's grids.  Everything else as vits_deliver. */
 int vits_test_deliver(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_segment *segs, int n_segs,
                       int n_streams, int encoding, void *dst, size_t dst_bytes, int64_t *stream_samples, int64_t *stream_offsets);
+
+/* The trimmed delivery by value: x, counts as vits_test_deliver; launches the pipeline's kernels with the pipeline's grids.
+ * Everything else as vits_deliver_trimmed. */
+int vits_test_deliver_trimmed(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_segment *segs,
+                              const vits_trim *trims, int n_segs, int n_streams, int encoding, void *dst, size_t dst_bytes,
+                              int64_t *stream_samples, int64_t *stream_offsets, int64_t *kept_first, int64_t *kept_count);
 
 /* The encoded stream's kernel by value: x [B][S] host, counts [B] the rows' valid samples (within [0, S]; what lies behind
  * must not show).  Columns [0, S) are cut into pieces of piece_samples samples (the last one shorter); each piece goes through

@@ -51,6 +51,11 @@ class VitsSegment(C.Structure):
                 ("volume", C.c_float)]
 
 
+class VitsTrim(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("threshold", C.c_float), ("keep_lead", C.c_int32), ("keep_tail", C.c_int32),
+                ("tail_samples", C.c_int64)]
+
+
 class VitsStreamFormat(C.Structure):
     _fields_ = [("encoding", C.c_int32), ("ref_peak", C.c_void_p), ("volume", C.c_void_p)]
 
@@ -85,6 +90,7 @@ EXPORTS = [
     "vits_set_output_rate", "vits_last_sample_counts", "vits_resample_plan", "vits_test_resample", "vits_test_resample_pieces",
     "vits_test_durations", "vits_test_expand_prior", "vits_test_fill_normal", "vits_test_fill_normal_rows", "vits_test_post_conv",
     "vits_delivery_plan", "vits_deliver", "vits_test_deliver",
+    "vits_trim_range", "vits_delivery_plan_trimmed", "vits_deliver_trimmed", "vits_test_deliver_trimmed",
     "vits_run_chunked_enc", "vits_run_vocoder_chunked_enc", "vits_test_stream_pack",
 ]
 
@@ -171,6 +177,11 @@ def load():
     lib.vits_delivery_plan.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, i64p]
     lib.vits_deliver.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vp, vp]
     lib.vits_test_deliver.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vp, vp]
+    lib.vits_trim_range.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.POINTER(VitsTrim), i64p, i64p]
+    lib.vits_delivery_plan_trimmed.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, i64p]
+    lib.vits_deliver_trimmed.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vp, vp, vp, vp]
+    lib.vits_test_deliver_trimmed.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_size_t,
+                                              vp, vp, vp, vp]
     lib.vits_free_output.argtypes = [vp, C.POINTER(VitsOutput)]
     lib.vits_free_output.restype = None
     lib.vits_sync.argtypes = [vp]

@@ -5,6 +5,9 @@ they travel in.
 for a session that can deliver (MiSession.deliver), computed here for one that cannot (the onnxruntime duck type, pipelined
 and sharded sessions).  Both take the post-processed float32 samples in [-1, 1] (TTSVoice._postprocess) and give the same
 bytes.  The two G.711 forms equal CPython's audioop.lin2ulaw / lin2alaw (width 2) on every int16 value.
+
+`trim_range` and `join_trimmed` are the same for the trimmed delivery (include/vitsmi.h, "trimmed delivery"): the kept range
+of a row, and one stream of rows cut to their kept ranges with silence in front of and behind each.
 """
 import io
 import struct
@@ -76,6 +79,55 @@ def silence(n: int, encoding: str = "pcm16") -> np.ndarray:
     """n elements of silence: the encoding of sample value 0"""
     _check(encoding)
     return np.full(int(n), SILENCE[encoding], DTYPES[encoding])
+
+
+def trim_range(x, n, trim):
+    """The kept range (a, c) of a row: x[:n] are its valid samples, `trim` anything with the fields of vits_trim - mode (0 off,
+    1 absolute, 2 relative to the row's peak), threshold, keep_lead, keep_tail - or None (off).  A sample is active iff
+    |x| > thr, strictly; no active sample: (0, 0)."""
+    n = int(n)
+    if trim is None or int(trim.mode) == 0:
+        return 0, n
+    if int(trim.mode) not in (1, 2):
+        raise ValueError(f"trim mode {trim.mode} outside 0..2")
+    mag = np.abs(np.asarray(x, np.float32)[:n])
+    thr = np.float32(trim.threshold)
+    if int(trim.mode) == 2:
+        thr = np.float32(thr * (np.max(mag) if n else np.float32(0)))     # one float32 product
+    active = np.flatnonzero(mag > thr)
+    if active.size == 0:
+        return 0, 0
+    a = max(0, int(active[0]) - int(trim.keep_lead))
+    e = min(n, int(active[-1]) + 1 + int(trim.keep_tail))
+    return a, e - a
+
+
+def scaled(audio: np.ndarray, peak, volume: float) -> np.ndarray:
+    """The delivery's sample formula in float32: peak None - no normalisation; peak < 1e-8 - zeros."""
+    audio = np.asarray(audio, np.float32)
+    if peak is not None:
+        audio = np.zeros_like(audio) if np.float32(peak) < np.float32(1e-8) else audio / np.float32(peak)
+    if np.float32(volume) != np.float32(1.0):
+        audio = audio * np.float32(volume)
+    return np.clip(audio, np.float32(-1.0), np.float32(1.0)).astype(np.float32)
+
+
+def join_trimmed(rows, encoding="pcm16", lead=0, tail=0, trim=None, normalize=1, volume=1.0):
+    """ONE stream of a trimmed delivery on the host: every row (its valid float32 samples) cut to trim_range, then `lead`
+    elements of silence, the row's kept samples post-processed and encoded, `tail` elements of silence.  normalize: 0 none,
+    1 by the peak of the row's kept range, 2 by the largest of those peaks.  Returns (data, [(a, c) per row])."""
+    _check(encoding)
+    kept = [trim_range(r, len(r), trim) for r in rows]
+    cut = [np.asarray(r, np.float32)[a:a + c] for r, (a, c) in zip(rows, kept)]
+    peaks = [np.max(np.abs(v)) if len(v) else np.float32(0) for v in cut]
+    if normalize == 0:
+        peaks = [None] * len(cut)
+    elif normalize == 2:
+        peaks = [max(peaks)] * len(cut) if cut else []
+    pieces = []
+    for v, pk in zip(cut, peaks):
+        pieces += [silence(lead, encoding), encode(scaled(v, pk, volume), encoding), silence(tail, encoding)]
+    return (np.concatenate(pieces) if pieces else silence(0, encoding)), kept
 
 
 @dataclass

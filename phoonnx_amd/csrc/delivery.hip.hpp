@@ -7,9 +7,14 @@
 // and walks forward from there.  Every lane loads element base + i * 256 + lane of the tile (coalesced fp32), encodes it and
 // parks it in LDS; after the barrier each lane stores its 16-byte cell.  The packed buffer starts 256-byte aligned and
 // holds whole cells, so every store is a full 16-byte one wherever the segment boundaries fall inside a cell.
+//
+// A trimmed delivery (vitsmi.h, "trimmed delivery") puts delivery_trim_scan_kernel in front: the first and the last sample
+// of every row above the segment's threshold, folded with atomicMin / atomicMax - order-independent like the peaks.  The host
+// turns the bounds into kept ranges; the two kernels above then run over those, unchanged (a segment is src and n).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <cstdint>
 
 #include "delivery.hpp"
@@ -69,6 +74,49 @@ __global__ __launch_bounds__(kDeliveryThreads) void delivery_peak_kernel(const f
         m = fmaxf(m, fabsf(x[s.src + i]));
     for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
     if ((threadIdx.x & 63) == 0 && s.n > 0) atomicMax(&peak_bits[s.peak], __float_as_uint(m));  // non-negative floats order as uints
+}
+
+// grid (gx, G) over a SCAN table: segment blockIdx.y's row [src, src + n) as in the plan, with `pad` = the trim's mode,
+// `volume` = its threshold and `peak` = the slot of peak_all that holds the row's max |x| (mode 2), or -1.  bounds [G][2]
+// must read {INT_MAX, -1}: they receive the smallest and the largest i < n with |x[i]| > thr (strictly; a NaN is not active).
+__global__ __launch_bounds__(kDeliveryThreads) void delivery_trim_scan_kernel(const float *x, const DeliverySeg *segs, const unsigned *peak_all,
+                                                                              int *bounds) {
+    const DeliverySeg s = segs[blockIdx.y];
+    if (s.pad == 0) return;
+    float thr = s.volume;
+    if (s.peak >= 0) thr = thr * __uint_as_float(peak_all[s.peak]);
+    int lo = INT_MAX, hi = -1;
+    // (an int64 index: i + the grid's stride may pass INT_MAX for n close to it)
+    for (int64_t i = (int64_t)blockIdx.x * kDeliveryThreads + threadIdx.x; i < s.n; i += (int64_t)gridDim.x * kDeliveryThreads)
+        if (fabsf(x[s.src + i]) > thr) {
+            lo = (int)i < lo ? (int)i : lo;
+            hi = (int)i;  // (a lane's indices ascend)
+        }
+    for (int o = 32; o > 0; o >>= 1) {
+        const int l2 = __shfl_xor(lo, o), h2 = __shfl_xor(hi, o);
+        lo = l2 < lo ? l2 : lo;
+        hi = h2 > hi ? h2 : hi;
+    }
+    if ((threadIdx.x & 63) == 0 && hi >= 0) {
+        atomicMin(&bounds[2 * blockIdx.y], lo);
+        atomicMax(&bounds[2 * blockIdx.y + 1], hi);
+    }
+}
+
+// the scan of a trimmed delivery on `st`: d_scan [G] the scan table, bounds [G][2] preset, peak_all [G] zero when any_rel
+// (some segment's threshold is relative: the peak launch over the untrimmed rows goes in front).  G > 0.
+// Grid: a lane walks about kTrimSpan samples, at most 64 workgroups a row.  Every wave ends in atomics on its row's slots,
+// and those serialise; the fewer waves, the fewer of them.  Measured in DESIGN.md 5.10 (kernel trace, 32 rows of 215 040
+// samples): delivery_peak_kernel 0.299 ms under launch_delivery's grid (a sample per lane, up to 256 workgroups a row),
+// 0.032 ms under this one; this scan 0.045 ms.
+constexpr int kTrimSpan = 32;
+inline hipError_t launch_trim_scan(const float *x, const DeliverySeg *d_scan, int G, int max_n, bool any_rel, unsigned *d_peak_all, int *d_bounds,
+                                   hipStream_t st) {
+    int gx = (max_n + kDeliveryThreads * kTrimSpan - 1) / (kDeliveryThreads * kTrimSpan);
+    gx = gx > 64 ? 64 : (gx < 1 ? 1 : gx);
+    if (any_rel) delivery_peak_kernel<<<dim3(gx, G), kDeliveryThreads, 0, st>>>(x, d_scan, d_peak_all);
+    delivery_trim_scan_kernel<<<dim3(gx, G), kDeliveryThreads, 0, st>>>(x, d_scan, d_peak_all, d_bounds);
+    return hipGetLastError();
 }
 
 // grid ceil(P / (256 * E)), E = 16 / sizeof(element): packed elements [0, P) -> cells of 16 bytes; the last cell is

@@ -6,6 +6,9 @@
 // back, element p of the packed buffer at byte w * p.  The plan therefore carries three things: the segment table the
 // kernels read (DeliverySeg, in dst order, with each segment's first packed element), the copies that move maximal
 // silence-free runs of the packed buffer to their place in dst, and the silence regions the host fills itself.
+//
+// A trimmed delivery (vitsmi.h, "trimmed delivery") is the same plan over a sub-range of every row: `counts` are then the
+// kept counts, `first` the kept ranges' first samples, and the trims bring the silence behind each segment.
 #pragma once
 #include <climits>
 #include <cmath>
@@ -33,8 +36,8 @@ inline int delivery_width(int encoding) {
 // one segment as the kernels read it (32 bytes; the table is in dst order, `start` ascending)
 struct DeliverySeg {
     int64_t start;  // first packed element of this segment (prefix sum of n)
-    int64_t src;    // element offset of the row's first sample in the waveform: row * pitch
-    int32_t n;      // valid samples of the row
+    int64_t src;    // element offset of the segment's first sample in the waveform: row * pitch (+ the kept range's start)
+    int32_t n;      // valid (trimmed: kept) samples of the row
     int32_t peak;   // peak slot to normalise by (row: [0, B); stream: B + stream), or -1
     float volume;
     int32_t pad;
@@ -51,6 +54,7 @@ struct DeliveryPlan {
     int encoding = 0, width = 0;
     std::vector<int64_t> stream_samples, stream_offsets;  // [J], [J + 1]
     std::vector<DeliverySeg> segs;
+    std::vector<int> order;  // segs[k] is the caller's segment order[k]
     std::vector<DeliveryCopy> copies;
     std::vector<DeliveryFill> fills;
     int64_t packed_elems = 0, total_bytes = 0;
@@ -58,10 +62,39 @@ struct DeliveryPlan {
     bool any_norm = false;  // some segment normalises: the peak launch is needed
 };
 
+// "" or what is wrong with one trim, naming the value (the caller names the segment)
+inline std::string trim_fault(const vits_trim &t) {
+    char buf[160];
+    buf[0] = 0;
+    if (t.mode < 0 || t.mode > 2) std::snprintf(buf, sizeof buf, "trim mode %d outside 0..2", t.mode);
+    else if (!std::isfinite(t.threshold) || t.threshold < 0) std::snprintf(buf, sizeof buf, "trim threshold %g is not finite and >= 0", (double)t.threshold);
+    else if (t.keep_lead < 0) std::snprintf(buf, sizeof buf, "keep_lead %d is negative", t.keep_lead);
+    else if (t.keep_tail < 0) std::snprintf(buf, sizeof buf, "keep_tail %d is negative", t.keep_tail);
+    else if (t.tail_samples < 0 || t.tail_samples > INT_MAX)
+        std::snprintf(buf, sizeof buf, "tail_samples %lld outside [0, %d]", (long long)t.tail_samples, INT_MAX);
+    return buf;
+}
+
+// the kept range [a, a + c) of a row of n valid samples whose first / last active samples are f / l (f > l: none active)
+inline void trim_range(int64_t n, int64_t f, int64_t l, const vits_trim &t, int64_t &a, int64_t &c) {
+    a = 0;
+    c = n;
+    if (t.mode == 0) return;
+    if (f > l) {
+        c = 0;
+        return;
+    }
+    a = f - t.keep_lead > 0 ? f - t.keep_lead : 0;
+    const int64_t e = l + 1 + t.keep_tail < n ? l + 1 + t.keep_tail : n;
+    c = e - a;
+}
+
 // "" or what is wrong with the plan, naming the segment and the value.  counts [B]: the rows' valid samples; pitch: samples
-// between two rows of the waveform.
+// between two rows of the waveform.  trims [n_segs] (nullable): each is validated and its tail_samples of silence follow its
+// segment; first [B] (nullable): the segment of row r starts at sample first[r] of the row - counts[r] is then what is kept
+// of it.  Without the two this is the untrimmed plan exactly.
 inline std::string delivery_plan(const int64_t *counts, int B, int64_t pitch, const vits_segment *segs, int n_segs, int n_streams,
-                                 int encoding, DeliveryPlan &p) {
+                                 int encoding, DeliveryPlan &p, const vits_trim *trims = nullptr, const int64_t *first = nullptr) {
     char buf[200];
     const int w = delivery_width(encoding);
     if (!w) {
@@ -109,6 +142,17 @@ inline std::string delivery_plan(const int64_t *counts, int B, int64_t pitch, co
             std::snprintf(buf, sizeof buf, "segment %d: row %d has %lld samples, outside [0, %d]", g, s.row, (long long)counts[s.row], INT_MAX);
             return buf;
         }
+        if (trims) {
+            const std::string e = trim_fault(trims[g]);
+            if (!e.empty()) {
+                std::snprintf(buf, sizeof buf, "segment %d: %s", g, e.c_str());
+                return buf;
+            }
+        }
+        if (first && (first[s.row] < 0 || first[s.row] > INT_MAX - counts[s.row])) {
+            std::snprintf(buf, sizeof buf, "segment %d: row %d is kept from sample %lld on", g, s.row, (long long)first[s.row]);
+            return buf;
+        }
         per_stream[s.stream + 1]++;
     }
     // dst order: stream by stream, a stream's segments in the order given (a counting sort)
@@ -124,6 +168,7 @@ inline std::string delivery_plan(const int64_t *counts, int B, int64_t pitch, co
     p.stream_samples.assign(n_streams, 0);
     p.stream_offsets.assign(n_streams + 1, 0);
     p.segs.reserve(n_segs);
+    p.order = order;
     int64_t packed = 0, dst = 0;  // elements
     int k = 0;
     for (int j = 0; j < n_streams; j++) {
@@ -131,12 +176,14 @@ inline std::string delivery_plan(const int64_t *counts, int B, int64_t pitch, co
         for (; k < per_stream[j + 1]; k++) {
             const vits_segment &s = segs[order[k]];
             const int64_t n = counts[s.row];
+            const int64_t tail = trims ? trims[order[k]].tail_samples : 0;
             if (s.lead_samples > 0) {
                 p.fills.push_back({dst * w, s.lead_samples});
                 dst += s.lead_samples;
             }
             if (n > 0) {
-                // a copy runs on while no silence lies in front of the segment
+                // a copy runs on while no silence lies in front of the segment: no lead of its own, and (a tail has moved
+                // dst on) no tail behind the copy's last segment
                 if (!p.copies.empty() && s.lead_samples == 0 && p.copies.back().dst_off + p.copies.back().bytes == dst * w)
                     p.copies.back().bytes += n * w;
                 else
@@ -144,7 +191,7 @@ inline std::string delivery_plan(const int64_t *counts, int B, int64_t pitch, co
             }
             DeliverySeg d{};
             d.start = packed;
-            d.src = (int64_t)s.row * pitch;
+            d.src = (int64_t)s.row * pitch + (first ? first[s.row] : 0);
             d.n = (int32_t)n;
             d.peak = s.normalize == 1 ? s.row : (s.normalize == 2 ? B + s.stream : -1);
             d.volume = s.volume;
@@ -153,7 +200,11 @@ inline std::string delivery_plan(const int64_t *counts, int B, int64_t pitch, co
             p.max_n = d.n > p.max_n ? d.n : p.max_n;
             packed += n;
             dst += n;
-            p.stream_samples[j] += s.lead_samples + n;
+            if (tail > 0) {
+                p.fills.push_back({dst * w, tail});
+                dst += tail;
+            }
+            p.stream_samples[j] += s.lead_samples + n + tail;
         }
     }
     p.stream_offsets[n_streams] = dst * w;

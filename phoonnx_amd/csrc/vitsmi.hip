@@ -2538,7 +2538,11 @@ int vits_reserve(vits_handle *h, int B, int T, int F) {
         // vits_last_pcm16's int16 waveform and per-utterance peaks (the larger of the two uses)
         const size_t io_in = carved_bytes([&](Carver &cv) { carve_inputs(cv, m, B, T, T, Fp); });
         const size_t io_pcm = carved_bytes([&](Carver &cv) { carve_pcm16(cv, B, F * m.hop); });
-        const size_t io_dlv = carved_bytes([&](Carver &cv) { carve_delivery(cv, B, F * m.hop); });  // ... or vits_deliver's
+        // ... or vits_deliver's, with vits_deliver_trimmed's slots behind them
+        const size_t io_dlv = carved_bytes([&](Carver &cv) {
+            carve_delivery(cv, B, F * m.hop);
+            carve_trim(cv, B);
+        });
         // ... or an encoded stream's chunk buffer: every chunk_frames <= F, i.e. chunks of up to F * hop samples
         const size_t io_sp = carved_bytes([&](Carver &cv) { carve_stream_pack(cv, B, (int64_t)F * m.hop); });
         size_t io = io_in > io_pcm ? io_in : io_pcm;
@@ -2553,6 +2557,12 @@ int vits_reserve(vits_handle *h, int B, int T, int F) {
                 carve_stream_pack(cv, B, so);
             });
             io = io_rs > io ? io_rs : io;
+            // (a trimmed delivery's slots lie behind the resampled result too: in the place of an encoded stream's buffers)
+            const size_t io_rt = carved_bytes([&](Carver &cv) {
+                carve_resample(cv, B, (int)so, (int)h->rs.plan.K);
+                carve_trim(cv, B);
+            });
+            io = io_rt > io ? io_rt : io;
         }
         if (int rc = slab_reserve(h, h->io, io, false)) return rc;
     }
@@ -2992,6 +3002,28 @@ int vits_delivery_plan(const int64_t *counts, int B, const vits_segment *segs, i
     return VITS_OK;
 }
 
+int vits_trim_range(int64_t n, int64_t first_active, int64_t last_active, const vits_trim *t, int64_t *a, int64_t *c) {
+    if (!t || !a || !c) return fail(nullptr, VITS_E_ARG, "null argument");
+    const std::string e = trim_fault(*t);
+    if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
+    if (n < 0 || n > INT_MAX) return fail(nullptr, VITS_E_ARG, "n = %lld outside [0, %d]", (long long)n, INT_MAX);
+    if (first_active <= last_active && (first_active < 0 || last_active >= n))
+        return fail(nullptr, VITS_E_ARG, "active samples [%lld, %lld] outside [0, %lld)", (long long)first_active, (long long)last_active, (long long)n);
+    trim_range(n, first_active, last_active, *t, *a, *c);
+    return VITS_OK;
+}
+
+int vits_delivery_plan_trimmed(const int64_t *kept, int B, const vits_segment *segs, const vits_trim *trims, int n_segs, int n_streams,
+                               int encoding, int64_t *stream_samples, int64_t *stream_offsets, int64_t *total_bytes) {
+    DeliveryPlan p;
+    const std::string e = delivery_plan(kept, B, 0, segs, n_segs, n_streams, encoding, p, trims);
+    if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
+    for (int j = 0; j < n_streams && stream_samples; j++) stream_samples[j] = p.stream_samples[j];
+    for (int j = 0; j <= n_streams && stream_offsets; j++) stream_offsets[j] = p.stream_offsets[j];
+    if (total_bytes) *total_bytes = p.total_bytes;
+    return VITS_OK;
+}
+
 // Everything a delivery puts on the stream: segment table up, peaks cleared, the launches, the copies into dst; then the
 // silence, on the host.  The caller synchronises.  db: carve_delivery's buffers for a waveform of at least the plan's rows.
 static hipError_t delivery_enqueue(const float *d_x, const DeliveryPlan &p, const DeliveryBufs &db, int B, hipStream_t st, void *dst) {
@@ -3013,6 +3045,19 @@ static void delivery_report(const DeliveryPlan &p, int64_t *stream_samples, int6
     for (size_t j = 0; j < p.stream_offsets.size() && stream_offsets; j++) stream_offsets[j] = p.stream_offsets[j];
 }
 
+// the valid samples of the rows of a run that can be delivered: frames * hop, or their count at the rate the run was
+// resampled to
+static int delivery_counts(vits_handle *h, std::vector<int64_t> &counts) {
+    const int B = h->B, S = h->S;
+    counts.resize(B);
+    for (int b = 0; b < B; b++) {
+        const int64_t n = (int64_t)(h->last_vocoder ? h->F : h->h_ylen[b]) * h->model.hop;
+        counts[b] = h->out_resampled ? (n * h->rs_run_L + h->rs_run_M - 1) / h->rs_run_M : n;
+        if (counts[b] > S) return fail(h, VITS_E_ARG, "no completed run to deliver (row %d: %lld samples of %d)", b, (long long)counts[b], S);
+    }
+    return 0;
+}
+
 int vits_deliver(vits_handle *h, const vits_segment *segs, int n_segs, int n_streams, int encoding, void *dst, size_t dst_bytes,
                  int64_t *stream_samples, int64_t *stream_offsets) {
     if (int rc = check_dev(h)) return rc;
@@ -3020,14 +3065,9 @@ int vits_deliver(vits_handle *h, const vits_segment *segs, int n_segs, int n_str
     const int B = h->B, S = h->S;
     if (!h->d_out || B <= 0 || S <= 0 || (!h->last_vocoder && (int)h->h_ylen.size() != B))
         return fail(h, VITS_E_ARG, "no completed run to deliver");
-    // the rows' valid samples: frames * hop, or their count at the rate the run was resampled to
     const bool rs = h->out_resampled;
-    std::vector<int64_t> counts(B);
-    for (int b = 0; b < B; b++) {
-        const int64_t n = (int64_t)(h->last_vocoder ? h->F : h->h_ylen[b]) * h->model.hop;
-        counts[b] = rs ? (n * h->rs_run_L + h->rs_run_M - 1) / h->rs_run_M : n;
-        if (counts[b] > S) return fail(h, VITS_E_ARG, "no completed run to deliver (row %d: %lld samples of %d)", b, (long long)counts[b], S);
-    }
+    std::vector<int64_t> counts;
+    if (int rc = delivery_counts(h, counts)) return rc;
     DeliveryPlan p;
     const std::string e = delivery_plan(counts.data(), B, S, segs, n_segs, n_streams, encoding, p);
     if (!e.empty()) return fail(h, VITS_E_ARG, "%s", e.c_str());
@@ -3053,6 +3093,112 @@ int vits_deliver(vits_handle *h, const vits_segment *segs, int n_segs, int n_str
     if (int rc = range_check(h)) return rc;  // (after vits_run_async this is the first synchronisation of that run)
     if (h->range_failed) return fail(h, VITS_E_RANGE, "the last run left the range of the fp16 operand planes (see vits_get_stats)");
     delivery_report(p, stream_samples, stream_offsets);
+    return VITS_OK;
+}
+
+// ---- trimmed delivery (vitsmi.h, "trimmed delivery"): the scan in front of the delivery, the kept ranges and the plan
+// over them on the host in between
+
+// The scan of the plan p0 (over the whole rows) and the wait for it: first / kept [B] receive every row's kept range (rows
+// outside the plan, and segments whose trim is off: the whole row).  Waits whatever happened: the tables are the pageable
+// sources of copies that may be in flight.
+static hipError_t trim_scan(const float *d_x, const DeliveryPlan &p0, const vits_segment *segs, const vits_trim *trims, const int64_t *counts,
+                            int B, const DeliveryBufs &db, const TrimBufs &tb, hipStream_t st, std::vector<int64_t> &first,
+                            std::vector<int64_t> &kept) {
+    first.assign(B, 0);
+    kept.assign(counts, counts + B);
+    const int G = (int)p0.segs.size();
+    std::vector<DeliverySeg> scan(p0.segs);
+    std::vector<int32_t> bounds(2 * (size_t)G);
+    bool any = false, any_rel = false;
+    for (int k = 0; k < G && trims; k++) {
+        const vits_trim &t = trims[p0.order[k]];
+        scan[k].peak = t.mode == 2 ? k : -1;
+        scan[k].volume = t.threshold;
+        scan[k].pad = t.mode;
+        bounds[2 * k] = INT_MAX;
+        bounds[2 * k + 1] = -1;
+        any = any || t.mode != 0;
+        any_rel = any_rel || t.mode == 2;
+    }
+    hipError_t e = hipSuccess;
+    if (any && p0.max_n > 0) {  // (rows without samples keep their presets: none active)
+        e = hipMemcpyAsync(db.segs, scan.data(), (size_t)G * sizeof(DeliverySeg), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(tb.bounds, bounds.data(), bounds.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && any_rel) e = hipMemsetAsync(tb.peak_all, 0, (size_t)G * sizeof(unsigned), st);
+        if (e == hipSuccess) e = launch_trim_scan(d_x, db.segs, G, p0.max_n, any_rel, tb.peak_all, tb.bounds, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(bounds.data(), tb.bounds, bounds.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    }
+    const hipError_t done = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = done;
+    if (e != hipSuccess || !any) return e;
+    for (int k = 0; k < G; k++) {
+        const int g = p0.order[k], row = segs[g].row;
+        trim_range(counts[row], bounds[2 * k], bounds[2 * k + 1], trims[g], first[row], kept[row]);
+    }
+    return hipSuccess;
+}
+
+static void trim_report(const vits_segment *segs, int n_segs, const std::vector<int64_t> &first, const std::vector<int64_t> &kept,
+                        int64_t *kept_first, int64_t *kept_count) {
+    for (int g = 0; g < n_segs; g++) {
+        if (kept_first) kept_first[g] = first[segs[g].row];
+        if (kept_count) kept_count[g] = kept[segs[g].row];
+    }
+}
+
+int vits_deliver_trimmed(vits_handle *h, const vits_segment *segs, const vits_trim *trims, int n_segs, int n_streams, int encoding,
+                         void *dst, size_t dst_bytes, int64_t *stream_samples, int64_t *stream_offsets, int64_t *kept_first,
+                         int64_t *kept_count) {
+    if (int rc = check_dev(h)) return rc;
+    std::lock_guard<std::mutex> lk(h->mu);
+    const int B = h->B, S = h->S;
+    if (!h->d_out || B <= 0 || S <= 0 || (!h->last_vocoder && (int)h->h_ylen.size() != B))
+        return fail(h, VITS_E_ARG, "no completed run to deliver");
+    const bool rs = h->out_resampled;
+    std::vector<int64_t> counts;
+    if (int rc = delivery_counts(h, counts)) return rc;
+    DeliveryPlan p0;  // over the whole rows: the validation, and the table the scan reads
+    std::string e = delivery_plan(counts.data(), B, S, segs, n_segs, n_streams, encoding, p0, trims);
+    if (!e.empty()) return fail(h, VITS_E_ARG, "%s", e.c_str());
+    DeliveryBufs db{};
+    TrimBufs tb{};
+    if (rs) {
+        // (the run's own walk ends with carve_resample, or with an encoded stream's buffers behind it; the trim slots behind
+        // carve_resample are at most 12 B + 512 bytes more than the former.  Growing the slab here would drop the waveform that
+        // lives in it - the check below - and does not happen: slab_reserve allocates 1 MiB above every request, and
+        // vits_reserve counts this walk.)
+        const int K = h->rs_run_K;
+        if (int rc = slab_carve(h, h->io, "staging", [&](Carver &cv) {
+                db = carve_resample(cv, B, S, K).dlv;
+                tb = carve_trim(cv, B);
+            }))
+            return rc;
+        if (!h->d_out) return fail(h, VITS_E_ARG, "no completed run to deliver");
+    } else if (int rc = slab_carve(h, h->io, "staging", [&](Carver &cv) {
+                   db = carve_delivery(cv, B, S);
+                   tb = carve_trim(cv, B);
+               }))
+        return rc;
+    hipStream_t st = h->stream;
+    std::vector<int64_t> first, kept;
+    hipError_t err = trim_scan(h->d_out, p0, segs, trims, counts.data(), B, db, tb, st, first, kept);
+    if (err != hipSuccess) return fail(h, VITS_E_DEVICE, "trim scan failed: %s", hipGetErrorString(err));
+    if (int rc = range_check(h)) return rc;  // (after vits_run_async this is the first synchronisation of that run)
+    if (h->range_failed) return fail(h, VITS_E_RANGE, "the last run left the range of the fp16 operand planes (see vits_get_stats)");
+    DeliveryPlan p;
+    e = delivery_plan(kept.data(), B, S, segs, n_segs, n_streams, encoding, p, trims, first.data());
+    if (!e.empty()) return fail(h, VITS_E_ARG, "%s", e.c_str());
+    if (dst && dst_bytes < (size_t)p.total_bytes)
+        return fail(h, VITS_E_ARG, "delivery buffer too small: %zu bytes, %lld needed", dst_bytes, (long long)p.total_bytes);
+    if (dst) {
+        err = delivery_enqueue(h->d_out, p, db, B, st, dst);
+        if (err == hipSuccess) err = hipStreamSynchronize(st);
+        else hipStreamSynchronize(st);
+        if (err != hipSuccess) return fail(h, VITS_E_DEVICE, "delivery failed: %s", hipGetErrorString(err));
+    }
+    delivery_report(p, stream_samples, stream_offsets);
+    trim_report(segs, n_segs, first, kept, kept_first, kept_count);
     return VITS_OK;
 }
 
@@ -3951,6 +4097,44 @@ int vits_test_deliver(int device_id, const float *x, const int64_t *counts, int 
     TCHECK(enq);
     TCHECK(done);
     delivery_report(p, stream_samples, stream_offsets);
+    return VITS_OK;
+}
+
+int vits_test_deliver_trimmed(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_segment *segs,
+                              const vits_trim *trims, int n_segs, int n_streams, int encoding, void *dst, size_t dst_bytes,
+                              int64_t *stream_samples, int64_t *stream_offsets, int64_t *kept_first, int64_t *kept_count) {
+    if (!x || !counts || B <= 0 || S <= 0 || (int64_t)B * S > (int64_t)1 << 40) return fail(nullptr, VITS_E_ARG, "bad delivery test arguments");
+    for (int b = 0; b < B; b++)
+        if (counts[b] < 0 || counts[b] > S) return fail(nullptr, VITS_E_ARG, "counts[%d] = %lld outside [0, %d]", b, (long long)counts[b], S);
+    DeliveryPlan p0;
+    std::string e = delivery_plan(counts, B, S, segs, n_segs, n_streams, encoding, p0, trims);
+    if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
+    if (int rc = test_dev(device_id)) return rc;
+    DevBufs D;
+    float *dx = D.up(x, (size_t)B * S);
+    DeliveryBufs db{};
+    db.packed = D.alloc<unsigned char>((size_t)B * S * 4 + 16);
+    db.segs = D.alloc<DeliverySeg>((size_t)B);
+    db.peak = D.alloc<unsigned>(2 * (size_t)B);
+    TrimBufs tb{};
+    tb.bounds = D.alloc<int32_t>(2 * (size_t)B);
+    tb.peak_all = D.alloc<unsigned>((size_t)B);
+    TCHECK(D.err);
+    std::vector<int64_t> first, kept;
+    TCHECK(trim_scan(dx, p0, segs, trims, counts, B, db, tb, nullptr, first, kept));
+    DeliveryPlan p;
+    e = delivery_plan(kept.data(), B, S, segs, n_segs, n_streams, encoding, p, trims, first.data());
+    if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
+    if (dst && dst_bytes < (size_t)p.total_bytes)
+        return fail(nullptr, VITS_E_ARG, "delivery buffer too small: %zu bytes, %lld needed", dst_bytes, (long long)p.total_bytes);
+    if (dst) {
+        const hipError_t enq = delivery_enqueue(dx, p, db, B, nullptr, dst);
+        const hipError_t done = hipDeviceSynchronize();
+        TCHECK(enq);
+        TCHECK(done);
+    }
+    delivery_report(p, stream_samples, stream_offsets);
+    trim_report(segs, n_segs, first, kept, kept_first, kept_count);
     return VITS_OK;
 }
 

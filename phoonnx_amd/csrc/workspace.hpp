@@ -254,6 +254,21 @@ inline DeliveryBufs carve_delivery(Carver &cv, int B, int S) {
     return d;
 }
 
+// vits_deliver_trimmed on top of the delivery's buffers (a walk of its own, behind them): the scan's bounds - {first, last}
+// active index per segment, preset to {INT_MAX, -1} - and the untrimmed rows' peaks the relative thresholds read.  At most
+// B segments.
+struct TrimBufs {
+    int32_t *bounds;
+    unsigned *peak_all;
+};
+
+inline TrimBufs carve_trim(Carver &cv, int B) {
+    TrimBufs t{};
+    t.bounds = cv.take<int32_t>(2 * (size_t)B);
+    t.peak_all = cv.take<unsigned>(B);
+    return t;
+}
+
 // With an output rate set (vits_set_output_rate), the staging slab holds the run's RESULT once its inputs are consumed:
 // the resampled fp32 waveform [B][S_out] (a chunked run: the output samples of one chunk, never more than S_out per
 // row), the rows' valid input and output sample counts, the two generations of the chunked path's carry [B][K] (the

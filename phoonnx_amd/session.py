@@ -252,6 +252,18 @@ class Segment:
     volume: float = 1.0
 
 
+@dataclass
+class Trim:
+    """The trim of one segment (vitsmi.h, vits_trim): mode 0 off, 1 - a sample is active above `threshold`, 2 - above
+    `threshold` times the row's peak; the segment keeps its first to its last active sample and keep_lead / keep_tail samples
+    around them, and is followed by tail_samples samples of silence."""
+    mode: int = 0
+    threshold: float = 0.0
+    keep_lead: int = 0
+    keep_tail: int = 0
+    tail_samples: int = 0
+
+
 def _encoding(encoding):
     try:
         return _ffi.ENCODINGS[encoding]
@@ -271,17 +283,35 @@ def _segments(segments):
     return arr, len(segments)
 
 
+def _trims(trims, n):
+    """None, one Trim or one per segment -> ctypes array of n vits_trim (None: no trims)"""
+    if trims is None:
+        return None
+    trims = [trims] * n if isinstance(trims, Trim) else list(trims)
+    if len(trims) != n:
+        raise SessionError(f"trims must be one Trim or one per segment ({n}), got {len(trims)}")
+    arr = (_ffi.VitsTrim * max(n, 1))()
+    for i, t in enumerate(trims):
+        try:
+            arr[i] = _ffi.VitsTrim(int(t.mode), float(t.threshold), int(t.keep_lead), int(t.keep_tail), int(t.tail_samples))
+        except (AttributeError, TypeError, ValueError, OverflowError) as e:
+            raise SessionError(f"segment {i}: trim: {e}") from None
+    return arr
+
+
 def _n_streams(segments, n_streams):
     if n_streams is not None:
         return int(n_streams)
     return max([int(g.stream) for g in segments], default=0) + 1
 
 
-def delivery_plan(counts, segments, n_streams=None, encoding="pcm16"):
+def delivery_plan(counts, segments, n_streams=None, encoding="pcm16", trims=None, kept=None):
     """The layout of a delivery (vits_delivery_plan: pure host code, no session, no device): counts int64 [B] - the rows' valid
     samples - and a plan -> {"stream_samples": int64 [J], "stream_offsets": int64 [J + 1] (bytes), "total_bytes": int}.
-    A plan the engine would refuse raises SessionError with its message."""
-    counts = np.ascontiguousarray(counts, np.int64)
+    A plan the engine would refuse raises SessionError with its message.  trims (one Trim or one per segment) and kept
+    (int64 [B]: what a trimmed delivery keeps of each row, in the place of counts) give the layout of a trimmed delivery
+    (vits_delivery_plan_trimmed)."""
+    counts = np.ascontiguousarray(counts if kept is None else kept, np.int64)
     if counts.ndim != 1:
         raise SessionError(f"counts must be int64 [B], got {counts.shape}")
     segments = list(segments)
@@ -289,6 +319,12 @@ def delivery_plan(counts, segments, n_streams=None, encoding="pcm16"):
     J = _n_streams(segments, n_streams)
     arr, n = _segments(segments)
     samples, offsets, total = np.zeros(max(J, 0), np.int64), np.zeros(max(J, 0) + 1, np.int64), C.c_int64()
+    if trims is not None or kept is not None:
+        rc = _ffi.load().vits_delivery_plan_trimmed(_ffi.ptr(counts), counts.shape[0], arr, _trims(trims, n), n, J, code,
+                                                    _ffi.ptr(samples), _ffi.ptr(offsets), C.byref(total))
+        if rc != 0:
+            raise SessionError(f"vits_delivery_plan_trimmed failed [{rc}]: {_ffi.last_error(None)}")
+        return {"stream_samples": samples, "stream_offsets": offsets, "total_bytes": int(total.value)}
     rc = _ffi.load().vits_delivery_plan(_ffi.ptr(counts), counts.shape[0], arr, n, J, code, _ffi.ptr(samples), _ffi.ptr(offsets),
                                         C.byref(total))
     if rc != 0:
@@ -1048,17 +1084,39 @@ class MiSession:
             S = int(ylen.max()) * self.hparam("hop")
             return self.last_pcm16(normalize, volume, shape=(B, S)), ylen
 
-    def deliver(self, segments, n_streams=None, encoding="pcm16"):
+    def deliver(self, segments, n_streams=None, encoding="pcm16", trims=None, return_kept=False):
         """The last run's audio, post-processed, encoded and laid out per request on the device (vitsmi.h, "delivery"):
         segments - Segment objects, each row of the run in at most one; encoding "pcm16" / "ulaw" / "alaw" / "f32".  Returns
         one NumPy array per stream (int16 / uint8 / float32), all views into ONE buffer in stream order - page-locked memory
         from the pool when pinned_results.  The fp32 waveform stays on the device; tap / last_pcm16 / a fetch of the same run
-        still work afterwards, and so does another deliver() with another plan."""
+        still work afterwards, and so does another deliver() with another plan.
+        trims - one Trim or one per segment (vitsmi.h, "trimmed delivery"): every row is cut to its kept range on the device
+        and followed by its tail of silence.  return_kept=True: (streams, kept_first int64 [G], kept_count int64 [G]).
+        The layout of a trimmed delivery depends on the data, so its ONE buffer is sized before the scan, by the untrimmed
+        layout plus the tails (one call and one scan instead of two): the views returned keep a buffer alive that is larger
+        than what was delivered by what was trimmed - copy them if that matters."""
         segments = list(segments)
         code, dtype = _encoding(encoding)
         J = _n_streams(segments, n_streams)
         arr, n = _segments(segments)
         samples, offsets = np.zeros(max(J, 0), np.int64), np.zeros(max(J, 0) + 1, np.int64)
+        if trims is not None or return_kept:
+            tarr = _trims(trims, n)
+            first, count = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
+            width = np.dtype(dtype).itemsize
+            with self._locked():
+                # the untrimmed layout (no device work, no wait) and the tails bound the bytes: ONE trimmed call, one scan
+                rc = self._lib.vits_deliver(self._h, arr, n, J, code, None, 0, _ffi.ptr(samples), _ffi.ptr(offsets))
+                if rc != 0:
+                    self._raise("vits_deliver", rc)
+                cap = int(offsets[-1]) + width * sum(max(int(tarr[i].tail_samples), 0) for i in range(n if tarr else 0))
+                buf = _POOL.array((cap,), np.uint8) if self.pinned_results and cap else np.empty(cap, np.uint8)
+                rc = self._lib.vits_deliver_trimmed(self._h, arr, tarr, n, J, code, _ffi.ptr(buf), cap, _ffi.ptr(samples),
+                                                    _ffi.ptr(offsets), _ffi.ptr(first), _ffi.ptr(count))
+                if rc != 0:
+                    self._raise("vits_deliver_trimmed", rc)
+            streams = [buf[int(offsets[j]):int(offsets[j + 1])].view(dtype) for j in range(J)]
+            return (streams, first[:n], count[:n]) if return_kept else streams
         with self._locked():
             # (dst = NULL: the layout only - no device work, no wait)
             rc = self._lib.vits_deliver(self._h, arr, n, J, code, None, 0, _ffi.ptr(samples), _ffi.ptr(offsets))
@@ -1071,15 +1129,33 @@ class MiSession:
                 self._raise("vits_deliver", rc)
         return [buf[int(offsets[j]):int(offsets[j + 1])].view(dtype) for j in range(J)]
 
+    def deliver_layout(self, segments, n_streams=None, encoding="pcm16", trims=None):
+        """What deliver(..., trims=) would return, without the bytes (vits_deliver_trimmed with dst = NULL: waits for the run
+        and runs the scan, packs and copies nothing): {"stream_samples", "stream_offsets", "kept_first", "kept_count"}."""
+        segments = list(segments)
+        code, _ = _encoding(encoding)
+        J = _n_streams(segments, n_streams)
+        arr, n = _segments(segments)
+        samples, offsets = np.zeros(max(J, 0), np.int64), np.zeros(max(J, 0) + 1, np.int64)
+        first, count = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
+        with self._locked():
+            rc = self._lib.vits_deliver_trimmed(self._h, arr, _trims(trims, n), n, J, code, None, 0, _ffi.ptr(samples),
+                                                _ffi.ptr(offsets), _ffi.ptr(first), _ffi.ptr(count))
+            if rc != 0:
+                self._raise("vits_deliver_trimmed", rc)
+        return {"stream_samples": samples, "stream_offsets": offsets, "kept_first": first[:n], "kept_count": count[:n]}
+
     def synthesize_delivered(self, ids, lens, scales, sid=None, *, segments=None, n_streams=None, encoding="pcm16",
                              normalize=True, volume=1.0, seeds=None, durations=None, token_rate=None, noise_dp=None,
-                             noise_z=None, return_durations=False):
+                             noise_z=None, return_durations=False, trim=None):
         """One batched run and its delivery under one hold of the session lock: what leaves the GPU is the encoded audio
         of the plan and nothing else - the fp32 waveform is never copied to the host.  segments=None: one stream per row,
         with `normalize` / `volume` as scalars or [B] arrays (row b's own).  Everything in front of the delivery is
         synthesize_batch's (scales [3] or [B, 3], seeds, durations, token_rate, injected noise, the bf16x6 fallback).
+        trim - one Trim or one per segment: deliver(..., trims=trim).
         Returns {"streams": [array per stream], "stream_samples": int64 [J], "y_lengths": int64 [B], "sample_lengths":
-        int64 [B] (each row's valid samples at the delivered rate)[, "durations"]}."""
+        int64 [B] (each row's valid samples at the delivered rate), "kept_first" / "kept_count": int64 [G] (what each
+        segment delivers of its row: all of it without a trim)[, "durations"]}."""
         ids, lens, scales, sid, noise_dp, noise_z, noise, seeds, durations, token_rate = self._run_arguments(
             ids, lens, scales, sid, noise_dp, noise_z, seeds, durations, token_rate)
         B = ids.shape[0]
@@ -1099,14 +1175,20 @@ class MiSession:
                 ylen = self.last_y_lengths()
                 dur = self.last_durations() if return_durations else None
                 counts = self.last_sample_counts()
-                streams = self.deliver(segments, n_streams, encoding)
+                if trim is None:
+                    streams = self.deliver(segments, n_streams, encoding)
+                    kept_first = np.zeros(len(segments), np.int64)
+                    kept_count = np.array([counts[int(g.row)] for g in segments], np.int64)
+                else:
+                    streams, kept_first, kept_count = self.deliver(segments, n_streams, encoding, trims=trim, return_kept=True)
             except RangeError as exc:
                 self._fall_back_to_bf16x6(exc)
                 return self.synthesize_delivered(ids, lens, scales, sid, segments=segments, n_streams=n_streams,
                                                  encoding=encoding, seeds=seeds, durations=durations, token_rate=token_rate,
-                                                 noise_dp=noise_dp, noise_z=noise_z, return_durations=return_durations)
+                                                 noise_dp=noise_dp, noise_z=noise_z, return_durations=return_durations,
+                                                 trim=trim)
         res = {"streams": streams, "stream_samples": np.array([a.size for a in streams], np.int64), "y_lengths": ylen,
-               "sample_lengths": counts}
+               "sample_lengths": counts, "kept_first": kept_first, "kept_count": kept_count}
         if return_durations:
             res["durations"] = dur
         return res
@@ -1704,6 +1786,32 @@ def test_deliver(x, counts, segments, n_streams=None, encoding="pcm16", device_i
     if rc != 0:
         raise SessionError(f"vits_test_deliver failed [{rc}]: {_ffi.last_error(None)}")
     return [dst[int(offsets[j]):int(offsets[j + 1])].view(dtype) for j in range(J)]
+
+
+def test_deliver_trimmed(x, counts, segments, trims=None, n_streams=None, encoding="pcm16", device_id=0, dst=None, layout_only=False):
+    """vits_test_deliver_trimmed: test_deliver with trims (one Trim, one per segment, or None) -> {"streams": one array per
+    stream, views into `dst` (uint8; default: a buffer of the untrimmed plan's size with the tails), "stream_samples",
+    "stream_offsets", "kept_first", "kept_count"}.  layout_only: dst = NULL - the scan runs, nothing is packed ("streams" is
+    None).  A refusal raises SessionError and leaves a `dst` passed in untouched."""
+    x = np.ascontiguousarray(x, np.float32)
+    counts = np.ascontiguousarray(counts, np.int64)
+    B, S = x.shape
+    segments = list(segments)
+    code, dtype = _encoding(encoding)
+    J = _n_streams(segments, n_streams)
+    arr, n = _segments(segments)
+    tarr = _trims(trims, n)
+    if dst is None and not layout_only:
+        dst = np.empty(delivery_plan(counts, segments, J, encoding, trims=trims)["total_bytes"], np.uint8)
+    samples, offsets = np.zeros(max(J, 0), np.int64), np.zeros(max(J, 0) + 1, np.int64)
+    first, count = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
+    rc = _ffi.load().vits_test_deliver_trimmed(device_id, _ffi.ptr(x), _ffi.ptr(counts), B, S, arr, tarr, n, J, code,
+                                               None if layout_only else _ffi.ptr(dst), 0 if layout_only else dst.nbytes,
+                                               _ffi.ptr(samples), _ffi.ptr(offsets), _ffi.ptr(first), _ffi.ptr(count))
+    if rc != 0:
+        raise SessionError(f"vits_test_deliver_trimmed failed [{rc}]: {_ffi.last_error(None)}")
+    streams = None if layout_only else [dst[int(offsets[j]):int(offsets[j + 1])].view(dtype) for j in range(J)]
+    return {"streams": streams, "stream_samples": samples, "stream_offsets": offsets, "kept_first": first[:n], "kept_count": count[:n]}
 
 
 def _glue_check(rc, name):

@@ -18,6 +18,7 @@ timing (`AudioChunk.phoneme_alignments`) from the durations the engine reports (
 PCM, G.711 mu-law / A-law, float32) with a pause in front of every sentence - post-processed, encoded and packed on the
 device by sessions that deliver (MiSession.synthesize_delivered), by audio_encoding on the host otherwise.
 """
+import dataclasses
 import json
 import logging
 import re
@@ -375,7 +376,7 @@ class TTSVoice:
 
     def synthesize_requests(self, requests: Sequence[Tuple[str, Optional[SynthesisConfig]]],
                             seeds: Optional[Sequence[int]] = None, max_batch: int = 32,
-                            alignments: bool = False) -> List[List[AudioChunk]]:
+                            alignments: bool = False, postprocess: bool = True) -> List[List[AudioChunk]]:
         """Extension: many independent requests (text, SynthesisConfig or None) rendered together.  Every sentence of
         every request becomes one row of a batch with its request's own speaker, length / noise scales and (with `seeds`,
         one integer per request) its own noise seed - sentence k of request r: sentence_seed(seeds[r], k); rows are sorted
@@ -383,7 +384,10 @@ class TTSVoice:
         AudioChunk per sentence, post-processed with that request's normalize_audio / volume.  With seeds, a request's
         durations do not depend on which other requests share its batches (vitsmi.h, vits_run_async_rows).  A session
         without synthesize_batch (the onnxruntime duck type) renders the requests one by one through synthesize().
-        alignments=True fills every chunk's phoneme_alignments as synthesize(text, cfg, alignments=True) does."""
+        alignments=True fills every chunk's phoneme_alignments as synthesize(text, cfg, alignments=True) does.
+        postprocess=False (what synthesize_requests_encoded's trimmed fallback asks for: the cut comes before the peak) returns
+        the rows as rendered - no normalisation, volume or clipping; everything else, alignments included, as with True (a
+        session without synthesize_batch reports no durations either way, so its chunks carry no alignments)."""
         if max_batch < 1:
             raise ValueError(f"max_batch must be >= 1 (got {max_batch})")
         if seeds is not None and len(seeds) != len(requests):
@@ -397,6 +401,10 @@ class TTSVoice:
                 if not 0 <= spk < max(n_spk, 1):
                     raise ValueError(f"request {r}: speaker_id {spk} is out of range [0, {max(n_spk, 1)})")
         if not hasattr(self.session, "synthesize_batch"):
+            if not postprocess:
+                return [[AudioChunk(sample_rate=self.sample_rate, sample_width=2, sample_channels=1,
+                                    audio_float_array=np.atleast_1d(self.phoneme_ids_to_audio(ids, cfg)))
+                         for ids in self._sentence_ids(text, cfg)] for (text, _), cfg in zip(requests, cfgs)]
             return [list(self.synthesize(text, cfg, alignments=alignments)) for (text, _), cfg in zip(requests, cfgs)]
         from .sharding import pad_batch
         want_dur = alignments and hasattr(self.session, "last_durations")
@@ -433,7 +441,7 @@ class TTSVoice:
         result = [[] for _ in requests]
         for r, k, _ in rows:  # (rows are in request, then sentence order)
             result[r].append(AudioChunk(sample_rate=self.sample_rate, sample_width=2, sample_channels=1,
-                                        audio_float_array=self._postprocess(audio[r, k], cfgs[r]),
+                                        audio_float_array=self._postprocess(audio[r, k], cfgs[r]) if postprocess else audio[r, k],
                                         phoneme_alignments=aligned.get((r, k))))
         return result
 
@@ -448,15 +456,44 @@ class TTSVoice:
     @staticmethod
     def _scaled(audio: np.ndarray, peak, volume: float) -> np.ndarray:
         """_postprocess with the peak given (None: no normalisation): the same float32 operations in the same order."""
-        if peak is not None:
-            audio = np.zeros_like(audio) if peak < 1e-8 else audio / peak
-        if volume != 1.0:
-            audio = audio * volume
-        return np.clip(audio, -1.0, 1.0).astype(np.float32)
+        from . import audio_encoding as ae
+        return ae.scaled(audio, peak, volume)
+
+    def _trim(self, trim_silence, trailing_silence: float):
+        """trim_silence / trailing_silence of the encoded entries -> a session.Trim in samples at the delivered rate, or None
+        when both are left at their defaults.  A float is a threshold relative to the sentence's peak; a Trim is taken with
+        keep_lead / keep_tail in SECONDS, converted like the pause (_lead_samples); trailing_silence, in seconds, is added to
+        its tail_samples."""
+        from .session import Trim
+        if not trailing_silence >= 0.0:
+            raise ValueError(f"trailing_silence must be >= 0 (got {trailing_silence})")
+        tail = self._lead_samples(trailing_silence)
+        if trim_silence is None:
+            return Trim(0, 0.0, 0, 0, tail) if tail else None
+        if isinstance(trim_silence, Trim):
+            t = trim_silence
+            if not (t.keep_lead >= 0 and t.keep_tail >= 0):
+                raise ValueError(f"trim_silence: keep_lead / keep_tail must be >= 0 seconds (got {t.keep_lead}, {t.keep_tail})")
+            return Trim(int(t.mode), float(t.threshold), self._lead_samples(t.keep_lead), self._lead_samples(t.keep_tail),
+                        int(t.tail_samples) + tail)
+        thr = float(trim_silence)
+        if not (thr >= 0.0 and np.isfinite(thr)):
+            raise ValueError(f"trim_silence must be a finite threshold >= 0 (got {trim_silence})")
+        return Trim(2, thr, 0, 0, tail)
+
+    @staticmethod
+    def _cut_alignments(al, a: int, c: int):
+        """A sentence's alignments after its audio was cut to [a, a + c): every phoneme's [start, start + num) shifted by -a
+        and clamped to [0, c] - num_samples still sum to c, a phoneme that was trimmed away keeps 0 samples."""
+        for p in al:
+            lo = min(max(p.start_sample - a, 0), c)
+            hi = min(max(p.start_sample + p.num_samples - a, 0), c)
+            p.start_sample, p.num_samples = lo, hi - lo
+        return al
 
     def synthesize_encoded(self, text: str, syn_config: Optional[SynthesisConfig] = None, encoding: str = "pcm16",
                            sentence_silence: float = 0.0, normalize_scope: str = "sentence",
-                           alignments: bool = False):
+                           alignments: bool = False, trim_silence=None, trailing_silence: float = 0.0):
         """Extension: the whole text as ONE stream of encoded audio ("pcm16", "ulaw", "alaw", "f32"; audio_encoding).  All
         sentences render in one batch; with a session that delivers (MiSession.synthesize_delivered) post-processing,
         encoding and the packing happen on the device and only the encoded audio crosses the bus; any other session
@@ -464,6 +501,12 @@ class TTSVoice:
         int(sample_rate * sentence_silence * 2) // 2 samples of silence.  normalize_scope: "sentence" - each sentence by its
         own peak (what synthesize() does), "text" - all by the largest peak of the text, so that their relative levels
         survive.  alignments=True fills phoneme_alignments (per sentence; start_sample counted from the stream's start).
+        trim_silence (None; a float: the threshold as a fraction of the sentence's peak; or a session.Trim with keep_lead /
+        keep_tail in seconds) cuts every sentence to its first .. last sample above the threshold - on the device with a
+        session that delivers (vitsmi.h, "trimmed delivery"), by audio_encoding.join_trimmed otherwise: the same bytes -
+        and trailing_silence seconds of silence follow every sentence.  Peaks are then those of what is kept,
+        sentence_samples the kept lengths, and the alignments are cut to the kept ranges (they still sum to
+        sentence_samples; a phoneme that was trimmed away has num_samples == 0).
         Returns an audio_encoding.EncodedAudio."""
         from . import audio_encoding as ae
         from .sharding import pad_batch
@@ -472,6 +515,9 @@ class TTSVoice:
         if normalize_scope not in ("sentence", "text"):
             raise ValueError(f"normalize_scope must be 'sentence' or 'text' (got {normalize_scope!r})")
         lead = self._lead_samples(sentence_silence)
+        trim = self._trim(trim_silence, trailing_silence)
+        tail = trim.tail_samples if trim is not None else 0
+        kept = None
         want_dur = alignments and hasattr(self.session, "last_durations") and hasattr(self.session, "synthesize_batch")
         groups = self._sentence_groups(text, cfg) if want_dur else None
         all_ids = [[i for _, ids in g for i in ids] for g in groups] if want_dur else self._sentence_ids(text, cfg)
@@ -489,10 +535,13 @@ class TTSVoice:
             sid = np.full((len(all_ids),), cfg.speaker_id or 0, np.int64) if "sid" in expected else None
             norm = 0 if not cfg.normalize_audio else (2 if normalize_scope == "text" else 1)
             segs = [Segment(b, 0, lead, norm, float(cfg.volume)) for b in range(len(all_ids))]
+            more = {} if trim is None else {"trim": trim}
             out = self.session.synthesize_delivered(ids, lens, self._scales(cfg), sid, segments=segs, n_streams=1,
-                                                    encoding=encoding, return_durations=want_dur)
+                                                    encoding=encoding, return_durations=want_dur, **more)
             data = out["streams"][0]
             counts = [int(n) for n in out["sample_lengths"]]
+            if trim is not None:
+                kept = [(int(a), int(c)) for a, c in zip(out["kept_first"], out["kept_count"])]
             if want_dur:
                 durs, frames = out["durations"], [int(f) for f in out["y_lengths"]]
         else:
@@ -501,20 +550,16 @@ class TTSVoice:
                 audios, durs = res if want_dur else (res, None)
             else:
                 audios = [self.phoneme_ids_to_audio(ids, cfg) for ids in all_ids]
-            peaks = [np.max(np.abs(a)) if len(a) else np.float32(0) for a in audios]
-            if not cfg.normalize_audio:
-                peaks = [None] * len(audios)
-            elif normalize_scope == "text":
-                peaks = [max(peaks)] * len(audios)
-            pieces = []
-            for a, pk in zip(audios, peaks):
-                pieces += [ae.silence(lead, encoding), ae.encode(self._scaled(a, pk, cfg.volume), encoding)]
-            data = np.concatenate(pieces)
             counts = [len(a) for a in audios]
+            norm = 0 if not cfg.normalize_audio else (2 if normalize_scope == "text" else 1)
+            data, cut = ae.join_trimmed([np.atleast_1d(a) for a in audios], encoding, lead, tail, trim, norm, cfg.volume)
+            kept = cut if trim is not None else None
+        if kept is not None:
+            counts = [c for _, c in kept]
         starts, pos = [], 0
         for n in counts:
             starts.append(pos + lead)
-            pos += lead + n
+            pos += lead + n + tail
         aligned = None
         if want_dur:
             hop, ratio = self.session.hparam("hop"), self._ratio()
@@ -522,6 +567,8 @@ class TTSVoice:
             for b, g in enumerate(groups):
                 total = frames[b] if frames is not None else max(1, int(np.sum(durs[b])))
                 al = build_alignments(g, durs[b], hop, total_frames=total, ratio=ratio)
+                if kept is not None:
+                    self._cut_alignments(al, *kept[b])
                 for a in al:
                     a.start_sample += starts[b]
                 aligned.append(al)
@@ -619,36 +666,57 @@ class TTSVoice:
 
     def synthesize_requests_encoded(self, requests: Sequence[Tuple[str, Optional[SynthesisConfig]]],
                                     seeds: Optional[Sequence[int]] = None, max_batch: int = 32, encoding: str = "pcm16",
-                                    sentence_silence: float = 0.0, alignments: bool = False):
+                                    sentence_silence: float = 0.0, alignments: bool = False, trim_silence=None,
+                                    trailing_silence: float = 0.0):
         """Extension: synthesize_requests with every request's audio returned as one stream of encoded audio
         (audio_encoding.EncodedAudio; the pause of synthesize_encoded in front of each sentence).  The batching is
         synthesize_requests': sentences sorted by length, max_batch at a time, each with its request's settings and seed.
         With a session that delivers, every sentence leaves the device as its own encoded stream, post-processed with its
         request's normalize_audio / volume; a request's pieces are joined with their silence on the host, because its
         sentences may render in different runs (for the same reason each sentence is normalised by its own peak).  Any other
-        session: the host encoder over synthesize_requests' chunks - the same bytes."""
+        session: the host encoder over synthesize_requests' chunks - the same bytes.  trim_silence / trailing_silence as in
+        synthesize_encoded: every sentence cut to its kept range (normalised by the peak of what is kept) and followed by
+        its trailing silence."""
         from . import audio_encoding as ae
         ae._check(encoding)
         lead = self._lead_samples(sentence_silence)
+        trim = self._trim(trim_silence, trailing_silence)
+        tail = trim.tail_samples if trim is not None else 0
 
-        def join(pieces, aligns):
+        def join(pieces, aligns, kept=None):
             starts, pos = [], 0
             for p in pieces:
                 starts.append(pos + lead)
-                pos += lead + len(p)
-            parts = [q for p in pieces for q in (ae.silence(lead, encoding), p)]
+                pos += lead + len(p) + tail
+            parts = [q for p in pieces for q in ((ae.silence(lead, encoding), p, ae.silence(tail, encoding)) if tail else
+                                                 (ae.silence(lead, encoding), p))]
             data = np.concatenate(parts) if parts else ae.silence(0, encoding)
             if aligns is not None:
-                for st, al in zip(starts, aligns):
+                for k, (st, al) in enumerate(zip(starts, aligns)):
+                    if kept is not None:
+                        self._cut_alignments(al or [], *kept[k])
                     for a in al or []:
                         a.start_sample += st
             return ae.EncodedAudio(data, encoding, self.sample_rate, starts, [len(p) for p in pieces], aligns)
 
         if not hasattr(self.session, "synthesize_delivered"):
-            chunks = self.synthesize_requests(requests, seeds=seeds, max_batch=max_batch, alignments=alignments)
-            return [join([ae.encode(c.audio_float_array, encoding) for c in cs],
-                         [c.phoneme_alignments for c in cs] if alignments and all(c.phoneme_alignments is not None for c in cs)
-                         else None) for cs in chunks]
+            want_al = lambda cs: alignments and all(c.phoneme_alignments is not None for c in cs)
+            if trim is None:
+                chunks = self.synthesize_requests(requests, seeds=seeds, max_batch=max_batch, alignments=alignments)
+                return [join([ae.encode(c.audio_float_array, encoding) for c in cs],
+                             [c.phoneme_alignments for c in cs] if want_al(cs) else None) for cs in chunks]
+            # the rows as rendered, each cut, then post-processed by the peak of what is kept
+            chunks = self.synthesize_requests(requests, seeds=seeds, max_batch=max_batch, alignments=alignments, postprocess=False)
+            result = []
+            for (_, cfg), cs in zip(requests, chunks):
+                cfg = cfg if cfg is not None else SynthesisConfig()
+                pieces, kept = [], []
+                for c in cs:
+                    data, k = ae.join_trimmed([c.audio_float_array], encoding, 0, 0, trim, 1 if cfg.normalize_audio else 0, cfg.volume)
+                    pieces.append(data)
+                    kept += k
+                result.append(join(pieces, [c.phoneme_alignments for c in cs] if want_al(cs) else None, kept))
+            return result
         if max_batch < 1:
             raise ValueError(f"max_batch must be >= 1 (got {max_batch})")
         if seeds is not None and len(seeds) != len(requests):
@@ -672,7 +740,7 @@ class TTSVoice:
                     rows.append((r, k, [i for _, ids in g for i in ids]))
             else:
                 rows.extend((r, k, ids) for k, ids in enumerate(self._sentence_ids(text, cfg)))
-        piece, aligned = {}, {}
+        piece, aligned, kept_of = {}, {}, {}
         hop = self.session.hparam("hop")
         order = sorted(range(len(rows)), key=lambda i: len(rows[i][2]))  # (stable: equal lengths keep request order)
         for c0 in range(0, len(order), max_batch):
@@ -682,17 +750,22 @@ class TTSVoice:
             sid = np.asarray([cfgs[r].speaker_id or 0 for r, _, _ in run], np.int64) if "sid" in expected else None
             row_seeds = None if seeds is None else np.asarray([sentence_seed(seeds[r], k) for r, k, _ in run], np.uint64)
             segs = [Segment(b, b, 0, 1 if cfgs[r].normalize_audio else 0, float(cfgs[r].volume)) for b, (r, _, _) in enumerate(run)]
+            # (the tail is joined on the host like the pause: the device delivers each sentence's kept range alone)
+            more = {} if trim is None else {"trim": dataclasses.replace(trim, tail_samples=0)}
             out = self.session.synthesize_delivered(ids, lens, scales, sid, segments=segs, n_streams=len(run), encoding=encoding,
-                                                    seeds=row_seeds, return_durations=want_dur)
+                                                    seeds=row_seeds, return_durations=want_dur, **more)
             for b, (r, k, _) in enumerate(run):
                 piece[r, k] = out["streams"][b]
+                if trim is not None:
+                    kept_of[r, k] = (int(out["kept_first"][b]), int(out["kept_count"][b]))
                 if want_dur:
                     aligned[r, k] = build_alignments(groups[r, k], out["durations"][b], hop,
                                                      total_frames=int(out["y_lengths"][b]), ratio=self._ratio())
         per_request = [[] for _ in requests]
         for r, k, _ in rows:  # (rows are in request, then sentence order)
             per_request[r].append((r, k))
-        return [join([piece[key] for key in keys], [aligned[key] for key in keys] if want_dur else None) for keys in per_request]
+        return [join([piece[key] for key in keys], [aligned[key] for key in keys] if want_dur else None,
+                     [kept_of[key] for key in keys] if trim is not None else None) for keys in per_request]
 
     def synthesize_wav(self, text: str, wav_file: wave.Wave_write, syn_config: Optional[SynthesisConfig] = None,
                        set_wav_format: bool = True, batch_sentences: bool = False, device_pcm16: bool = False) -> None:
