@@ -679,6 +679,47 @@ int vits_test_fill_normal_rows(int device_id, int B, int channels, int T, const 
 int vits_test_post_conv(int device_id, const float *x, int B, int C, int T, const float *w, int K, float slope, const int64_t *vlen,
                         int hop, int kernel, float *out);
 
+/* The text-side kernels of the encoder and the stochastic duration predictor, by value: LayerNorm, the DDSConv layers,
+ * ConvFlow.pre, the inverse spline and the ElementwiseAffine.  The hooks launch through the pipeline's own launch functions;
+ * the form is an ARGUMENT (the VITSMI_* switches are read once per process and select nothing here).  Every `out` holds a
+ * guard row of T elements behind the tensor (T cells of 8 for planes): outputs are pre-filled with 0xff bytes, so an element
+ * never written and a write past the end both show.  Argument combinations the pipeline never forms are VITS_E_ARG.
+ * LayerNorm over channels of x [B][C][T]: flags = 1 GELU | 2 ACCUM (out += ...) | 4 MASK (lens) | 8 RELU_IN; form 0 = 16 time
+ * steps per workgroup, 1 = 32 (both C <= 256), 2 = one lane per column (any C); out_init (nullable) = the initial content of
+ * out; in_place: x is the initial content of out and the kernel reads it there.  dw_w [C][K] (nullable) with dw_b, K, dil: the
+ * depthwise conv of x * mask in front of LN + GELU (flags = 1, out of place, form 1 for C <= 256 and 2 above).  planes
+ * (nullable, tile forms, C % 8 == 0): the result's fp16 operand planes [B][3][C/8][T][8] (the third plane is not written).
+ * out: B * C * T + T floats; planes: B * 3 * C * T + 8 T halves. */
+int vits_test_layernorm(int device_id, const float *x, const float *out_init, int B, int C, int T, const float *gamma,
+                        const float *beta, const int64_t *lens, int flags, int form, int in_place, const float *dw_w,
+                        const float *dw_b, int K, int dil, float *out, uint16_t *planes);
+/* A stack of n_layers <= 4 fused DDSConv layers (k = 3) on x [B][C][T]: form 16 = dds_layer16_kernel (C in 64, 128, 192, 256),
+ * 32 = dds_layer_kernel (32, 64, 96, 128, 192, 256).  mask_out 1: the stack as the pipeline runs it (buffer ping-pong, mask
+ * behind the last layer), the result read where the pipeline reads it; 0: ONE layer launched with its mask off.
+ * Head (form 16, n_layers >= 2; head_cond nullable): the stack's input is head_w[c] * z[b][head_ch][t] + head_b[c] +
+ * head_cond[b][c][t] with z [B][2][T]; x is then not read.  Tail (form 16; tail_w [tail_rows][C] nullable, tail_b nullable,
+ * tail_rows <= C): out = (tail_w . result + tail_b) * mask, [B][tail_rows][T].  out: B * (C or tail_rows) * T + T floats. */
+typedef struct vits_test_dds_layer {
+    const float *dw_w, *dw_b;   /* depthwise [C][3], [C] */
+    const float *ln1_g, *ln1_b; /* [C] */
+    const float *pw_w, *pw_b;   /* 1 x 1 conv [C][C], [C] */
+    const float *ln2_g, *ln2_b; /* [C] */
+    int32_t dil;
+} vits_test_dds_layer;
+int vits_test_dds(int device_id, int form, const float *x, int B, int C, int T, const int64_t *lens, int n_layers,
+                  const vits_test_dds_layer *layers, int mask_out, const float *head_cond, const float *head_z, int head_ch,
+                  const float *head_w, const float *head_b, const float *tail_w, const float *tail_b, int tail_rows, float *out);
+/* ConvFlow.pre + conditioning: out[b][c][t] = w[c] * z[b][ch][t] + bias[c] + cond[b][c][t]; z [B][2][T].  out: B * C * T + T. */
+int vits_test_cf_pre(int device_id, const float *z, int ch, const float *w, const float *bias, const float *cond, int B, int C, int T,
+                     float *out);
+/* The inverse rational-quadratic spline with linear tails (tail bound 5) on z [B][2][T]: channel ch0 passes through, channel
+ * ch0 ^ 1 is transformed with pr [B][3 nb - 1][T] (widths, heights: divided by sqrt_c; derivatives), both masked by lens.
+ * nb <= 10 runs rqs_inverse_kernel<10>, up to 16 <16>.  out: B * 2 * T + T. */
+int vits_test_rqs_inverse(int device_id, const float *pr, const float *z, int B, int T, const int64_t *lens, int ch0, int nb,
+                          float sqrt_c, float *out);
+/* ElementwiseAffine reverse on channel ch of z [B][2][T]: out[b][t] = (z - m0) * exp(-logs0) * mask.  out: B * T + T. */
+int vits_test_ea_logw(int device_id, const float *z, int ch, float m0, float logs0, const int64_t *lens, int B, int T, float *out);
+
 /* The delivery by value: x [B][S] host, counts [B] the rows' valid samples (within [0, S]; what lies behind must not show);
  * launches the pipeline's kernels with the pipeline's grids.  Everything else as vits_deliver. */
 int vits_test_deliver(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_segment *segs, int n_segs,

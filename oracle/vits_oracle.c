@@ -548,7 +548,8 @@ static float rqs_inverse(float x, const float *uw, const float *uh, const float 
     float a = (x - ich) * (dd + dp1 - 2.0f * delta) + ih * (delta - dd);
     float b = ih * dd - (x - ich) * (dd + dp1 - 2.0f * delta);
     float c = -delta * (x - ich);
-    float disc = b * b - 4.0f * a * c;
+    /* (fp32 cancels disc to a negative value where delta >> d, at the far end of a steep bin: clamped, as the kernel's) */
+    float disc = fmaxf(b * b - 4.0f * a * c, 0.f);
     float root = (2.0f * c) / (-b - sqrtf(disc));
     return root * ibw + icw;
 }

@@ -56,6 +56,11 @@ class VitsTrim(C.Structure):
                 ("tail_samples", C.c_int64)]
 
 
+class VitsTestDdsLayer(C.Structure):
+    _fields_ = [("dw_w", C.c_void_p), ("dw_b", C.c_void_p), ("ln1_g", C.c_void_p), ("ln1_b", C.c_void_p), ("pw_w", C.c_void_p),
+                ("pw_b", C.c_void_p), ("ln2_g", C.c_void_p), ("ln2_b", C.c_void_p), ("dil", C.c_int32)]
+
+
 class VitsStreamFormat(C.Structure):
     _fields_ = [("encoding", C.c_int32), ("ref_peak", C.c_void_p), ("volume", C.c_void_p)]
 
@@ -92,6 +97,7 @@ EXPORTS = [
     "vits_delivery_plan", "vits_deliver", "vits_test_deliver",
     "vits_trim_range", "vits_delivery_plan_trimmed", "vits_deliver_trimmed", "vits_test_deliver_trimmed",
     "vits_run_chunked_enc", "vits_run_vocoder_chunked_enc", "vits_test_stream_pack",
+    "vits_test_layernorm", "vits_test_dds", "vits_test_cf_pre", "vits_test_rqs_inverse", "vits_test_ea_logw",
 ]
 
 
@@ -174,6 +180,13 @@ def load():
     lib.vits_test_fill_normal.argtypes = [C.c_int, C.c_int64, C.c_uint64, C.c_uint64, vp]
     lib.vits_test_fill_normal_rows.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_uint32, vp, C.c_int, vp]
     lib.vits_test_post_conv.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_float, vp, C.c_int, C.c_int, vp]
+    lib.vits_test_layernorm.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp,
+                                        C.c_int, C.c_int, vp, vp]
+    lib.vits_test_dds.argtypes = [C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.POINTER(VitsTestDdsLayer), C.c_int,
+                                  vp, vp, C.c_int, vp, vp, vp, vp, C.c_int, vp]
+    lib.vits_test_cf_pre.argtypes = [C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]
+    lib.vits_test_rqs_inverse.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_float, vp]
+    lib.vits_test_ea_logw.argtypes = [C.c_int, vp, C.c_int, C.c_float, C.c_float, vp, C.c_int, C.c_int, vp]
     lib.vits_delivery_plan.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, i64p]
     lib.vits_deliver.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vp, vp]
     lib.vits_test_deliver.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vp, vp]

@@ -892,7 +892,10 @@ __global__ void rqs_inverse_kernel(const float *pr, float *z, const int *len, in
         float a = (x - ich) * (dd + dp1 - 2.0f * delta) + ih * (delta - dd);
         float bq = ih * dd - (x - ich) * (dd + dp1 - 2.0f * delta);
         float c = -delta * (x - ich);
-        float disc = bq * bq - 4.0f * a * c;
+        // (exact arithmetic has disc >= (h d)^2 > 0; in fp32 it cancels to a NEGATIVE value where delta >> d, at the far end
+        // of a steep bin - disc / bq^2 = (d / (2 delta - d))^2 < 2^-24 - and sqrtf made the utterance's logw NaN: clamped,
+        // the root is 2 delta / (2 delta - d) = 1 to rounding, the knot itself)
+        float disc = fmaxf(bq * bq - 4.0f * a * c, 0.f);
         float root = (2.0f * c) / (-bq - sqrtf(disc));
         y = root * ibw + icw;
     }

@@ -901,6 +901,16 @@ ConvDesc pack_convT_sx(Packer &P, const Resolver &R, SxPack fmt, const std::stri
 
 int same_pad(int K, int dil) { return (K * dil - dil) / 2; }  // commons.py:17-18, modules.py:102,163
 
+// w [Cout][Cin] -> the A-operand layout of dds_layer16_kernel: lane (row & 15, k & 3) reads its row's weights of
+// k = 4 step + (k & 3), four consecutive steps per float4: dst[((row tile * 4 + k & 3) * 16 + row & 15) * (Cin / 4) + step].
+// Rows behind Cout (a last tile padded to 16) are the caller's to zero.
+void fill_pw16(float *dst, const float *w, int Cout, int Cin) {
+    const int NS = Cin / 4;
+    for (int o = 0; o < Cout; o++)
+        for (int i = 0; i < Cin; i++)
+            dst[(int64_t((o / 16) * 4 + (i & 3)) * 16 + (o & 15)) * NS + (i >> 2)] = w[int64_t(o) * Cin + i];
+}
+
 DDSDesc pack_dds(Packer &P, const Resolver &R, const std::string &pfx) {
     DDSDesc d;
     for (int l = 0; l < 4; l++) {
@@ -927,14 +937,9 @@ DDSDesc pack_dds(Packer &P, const Resolver &R, const std::string &pfx) {
             // the 16-column kernel's A fragments: lane (row & 15, k & 3) reads its row's weights of k = 4 step + (k & 3), four
             // consecutive steps per float4: Wp[((row tile * 4 + k & 3) * 16 + row & 15) * (C / 4) + step]
             const TRef &w1 = R.need(pfx + ".convs_1x1." + std::to_string(l) + ".weight", 3);
-            const int C = int(Cd), NS = C / 4;
+            const int C = int(Cd);
             L.pw16 = P.alloc(int64_t(C) * C);
-            if (!P.dry) {
-                float *dst = P.arena.data() + L.pw16;
-                for (int o = 0; o < C; o++)
-                    for (int i = 0; i < C; i++)
-                        dst[(int64_t((o / 16) * 4 + (i & 3)) * 16 + (o & 15)) * NS + (i >> 2)] = w1.p[int64_t(o) * C + i];
-            }
+            if (!P.dry) fill_pw16(P.arena.data() + L.pw16, w1.p, C, C);
         }
     }
     if (!d.n_layers) throw std::runtime_error("no DDSConv layers under " + pfx);
@@ -946,14 +951,12 @@ DDSDesc pack_dds(Packer &P, const Resolver &R, const std::string &pfx) {
 int64_t pack_pw16(Packer &P, const Resolver &R, const std::string &name, int Cin) {
     const TRef *w = R.get(name + ".weight");
     if (!w || w->dims.size() != 3 || w->dims[2] != 1 || w->dims[1] != Cin || Cin % 16 || R.geti(name + ".group", 1) != 1) return -1;
-    const int Cout = int(w->dims[0]), Cp = (Cout + 15) / 16 * 16, NS = Cin / 4;
+    const int Cout = int(w->dims[0]), Cp = (Cout + 15) / 16 * 16;
     const int64_t off = P.alloc(int64_t(Cp) * Cin);
     if (!P.dry) {
         float *dst = P.arena.data() + off;
         for (int64_t i = 0; i < int64_t(Cp) * Cin; i++) dst[i] = 0.f;
-        for (int o = 0; o < Cout; o++)
-            for (int i = 0; i < Cin; i++)
-                dst[(int64_t((o / 16) * 4 + (i & 3)) * 16 + (o & 15)) * NS + (i >> 2)] = w->p[int64_t(o) * Cin + i];
+        fill_pw16(dst, w->p, Cout, Cin);
     }
     return off;
 }
@@ -1052,6 +1055,25 @@ std::string pack_test_conv(const float *w, const float *bias, int Cin, int Cout,
         else *d = pack_conv(P, Cin, Cout, K, dil, pad_l, wf, bias);
     } catch (const std::exception &e) {
         return e.what();
+    }
+    return "";
+}
+
+std::string pack_test_dds(int C, int n_layers, const float *const *pw_w, const float *const *pw_b, const float *tail_w,
+                          int tail_rows, TestDds *d, std::vector<float> *arena) {
+    if (C < 16 || C % 16 || n_layers < 1 || n_layers > 4 || (tail_w && tail_rows < 1)) return "bad DDSConv test shape";
+    for (int l = 0; l < n_layers; l++) {
+        // (the token domain's tiling, as Model packs the duration predictor's stacks)
+        const std::string e = pack_test_conv(pw_w[l], pw_b[l], C, C, 1, 1, 0, /*hint=*/2, &d->pw[l], arena);
+        if (!e.empty()) return e;
+        Packer P(*arena);
+        d->pw16[l] = P.alloc(int64_t(C) * C);
+        fill_pw16(arena->data() + d->pw16[l], pw_w[l], C, C);
+    }
+    if (tail_w) {
+        Packer P(*arena);
+        d->tail16 = P.alloc(int64_t((tail_rows + 15) / 16 * 16) * C);  // (alloc zero-fills: the padding rows)
+        fill_pw16(arena->data() + d->tail16, tail_w, tail_rows, C);
     }
     return "";
 }

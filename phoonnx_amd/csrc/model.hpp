@@ -200,6 +200,16 @@ std::string pack_test_conv(const float *w, const float *bias, int Cin, int Cout,
                            ConvDesc *d, std::vector<float> *arena, const TestPack &o = {});
 std::string pack_test_convT(const float *w, const float *bias, int Cin, int Cout, int K, int stride, ConvDesc *d,
                             std::vector<float> *arena, bool sx = false, const TestPack &o = {});
+// The 1 x 1 convs of a DDSConv stack of n_layers <= 4 layers (pw_w[l] [C][C], pw_b[l] [C]) in both kernels' layouts - pw:
+// pack_test_conv in the token domain's tiling (dds_layer_kernel), pw16: dds_layer16_kernel's A operand - and optionally the
+// conv behind the stack (tail_w [tail_rows][C]) as that kernel's fused tail.  C % 16 == 0.
+struct TestDds {
+    ConvDesc pw[4];
+    int64_t pw16[4] = {-1, -1, -1, -1};
+    int64_t tail16 = -1;
+};
+std::string pack_test_dds(int C, int n_layers, const float *const *pw_w, const float *const *pw_b, const float *tail_w,
+                          int tail_rows, TestDds *d, std::vector<float> *arena);
 
 // fp32 -> bf16 planes of the split-exact engine (host mirror of split3 in conv_sx_engine.hip.hpp)
 uint16_t bf16_rne(float f);

@@ -954,28 +954,189 @@ void pinned_put(vits_handle *h, void *q) {
     else hipHostFree(q);
 }
 
+// The text-side kernels of the encoder and the stochastic duration predictor (kernels.hip.hpp): LayerNorm, the DDSConv layers,
+// ConvFlow.pre, the spline and the ElementwiseAffine.  As with the token-to-frame kernels above, the pipeline and the kernel-level
+// test hooks (vits_test_layernorm ...) launch through these, so each instantiation's choice and grid are stated once.
+// LayerNorm over channels.  form: 16 or 32 time steps per workgroup of ln_tile_kernel (C <= 256), or one lane per column
+// (layernorm_c_kernel, any C).  planes (tile forms with C % 8 == 0 only): the result once more as fp16 operand planes, `peak` =
+// the range-guard slots of that conversion.
+enum LnForm : int { LN_FORM_TILE16 = 0, LN_FORM_TILE32 = 1, LN_FORM_COLUMN = 2 };
+void launch_layernorm(hipStream_t st, int form, int B, int C, int T, const float *in, float *out, const float *gamma,
+                      const float *beta, const int *len, int flags, uint16_t *planes, unsigned *peak) {
+    if (form == LN_FORM_TILE16 && planes)
+        ln_tile_kernel<0, true, 16><<<dim3((T + 15) / 16, B), 256, 0, st>>>(in, out, gamma, beta, len, C, T, flags, nullptr, nullptr, 1, 1,
+                                                                              planes, peak);
+    else if (form == LN_FORM_TILE32 && planes)
+        ln_tile_kernel<0, true><<<dim3((T + 31) / 32, B), 256, 0, st>>>(in, out, gamma, beta, len, C, T, flags, nullptr, nullptr, 1, 1,
+                                                                          planes, peak);
+    else if (form == LN_FORM_TILE16)
+        ln_tile_kernel<0, false, 16><<<dim3((T + 15) / 16, B), 256, 0, st>>>(in, out, gamma, beta, len, C, T, flags, nullptr, nullptr, 1, 1);
+    else if (form == LN_FORM_TILE32)
+        ln_tile_kernel<0><<<dim3((T + 31) / 32, B), 256, 0, st>>>(in, out, gamma, beta, len, C, T, flags, nullptr, nullptr, 1, 1);
+    else
+        layernorm_c_kernel<<<dim3((T + 63) / 64, B), 64, 0, st>>>(in, out, gamma, beta, len, C, T, flags);
+}
+
+// out = GELU(LN(depthwise conv of in * mask)) (modules.py:121-123): the first third of an unfused DDSConv layer
+void launch_dw_ln(hipStream_t st, int B, int C, int T, int K, int dil, const float *in, float *out, const float *dw_w,
+                  const float *dw_b, const float *gamma, const float *beta, const int *len) {
+    if (C <= 256 && K == 3)
+        ln_tile_kernel<3><<<dim3((T + 31) / 32, B), 256, 0, st>>>(in, out, gamma, beta, len, C, T, LN_GELU, dw_w, dw_b, K, dil);
+    else if (C <= 256)
+        ln_tile_kernel<1><<<dim3((T + 31) / 32, B), 256, 0, st>>>(in, out, gamma, beta, len, C, T, LN_GELU, dw_w, dw_b, K, dil);
+    else
+        dds_dw_ln_gelu_kernel<<<dim3((T + 63) / 64, B), 64, 0, st>>>(in, out, dw_w, dw_b, gamma, beta, len, C, T, K, dil);
+}
+
+// one fused DDSConv layer, nblk = C / 32: 16 columns per workgroup (nblk 2, 4, 6, 8) ...
+void launch_dds_layer16(hipStream_t st, int B, int nblk, const DdsLayer16Args &q) {
+    const dim3 dg16((q.T + 15) / 16, B);
+    switch (nblk) {
+        case 2: dds_layer16_kernel<2><<<dg16, 256, 0, st>>>(q); break;
+        case 4: dds_layer16_kernel<4><<<dg16, 256, 0, st>>>(q); break;
+        case 6: dds_layer16_kernel<6><<<dg16, 256, 0, st>>>(q); break;
+        default: dds_layer16_kernel<8><<<dg16, 256, 0, st>>>(q); break;
+    }
+}
+
+// ... or 32 (nblk 1, 2, 3, 4, 6, 8)
+void launch_dds_layer32(hipStream_t st, int B, int nblk, const DdsLayerArgs &a) {
+    const dim3 dg((a.T + 31) / 32, B);
+    switch (nblk) {  // (channel count at compile time: straight-line channel loops)
+        case 1: dds_layer_kernel<1><<<dg, 256, 0, st>>>(a); break;
+        case 2: dds_layer_kernel<2><<<dg, 256, 0, st>>>(a); break;
+        case 3: dds_layer_kernel<3><<<dg, 256, 0, st>>>(a); break;
+        case 4: dds_layer_kernel<4><<<dg, 256, 0, st>>>(a); break;
+        case 6: dds_layer_kernel<6><<<dg, 256, 0, st>>>(a); break;
+        default: dds_layer_kernel<8><<<dg, 256, 0, st>>>(a); break;
+    }
+}
+
+void launch_cf_pre(hipStream_t st, int B, int C, int T, const float *z, int ch, const float *w, const float *bias, const float *cond,
+                   float *h) {
+    cf_pre_kernel<<<dim3((T + 255) / 256, C, B), 256, 0, st>>>(z, ch, w, bias, cond, h, C, T);
+}
+
+void launch_rqs_inverse(hipStream_t st, int B, int T, int nb, const float *pr, float *z, const int *len, int ch0, int ch1,
+                        float sqrt_c) {
+    if (nb <= 10) rqs_inverse_kernel<10><<<dim3((T + 63) / 64, B), 64, 0, st>>>(pr, z, len, ch0, ch1, nb, T, sqrt_c);
+    else rqs_inverse_kernel<16><<<dim3((T + 63) / 64, B), 64, 0, st>>>(pr, z, len, ch0, ch1, nb, T, sqrt_c);
+}
+
+void launch_ea_logw(hipStream_t st, int B, int T, const float *z, int ch, float m0, float logs0, const int *len, float *logw) {
+    ea_logw_kernel<<<dim3((T + 63) / 64, B), 64, 0, st>>>(z, ch, m0, logs0, len, logw, T);
+}
+
 // planes (optional): the result once more as fp16 operand planes of the split-operand engine (see split_planes)
 void layernorm(Ctx &c, const float *in, float *out, int64_t g, int64_t b, const int *len, int C, int T, int flags,
                uint16_t *planes = nullptr) {
     // (16 time steps per workgroup: VITSMI_LN_TS=32 keeps the 32-step form, A/B timing)
     static const bool ts32 = [] { const char *e = std::getenv("VITSMI_LN_TS"); return e && std::atoi(e) == 32; }();
-    if (C <= 256 && planes && C % 8 == 0 && !ts32)
-        ln_tile_kernel<0, true, 16><<<dim3((T + 15) / 16, c.B), 256, 0, c.st>>>(in, out, c.P(g), c.P(b), len, C, T, flags, nullptr,
-                                                                                nullptr, 1, 1, planes, range_slots(c.h, true));
-    else if (C <= 256 && planes && C % 8 == 0)
-        ln_tile_kernel<0, true><<<dim3((T + 31) / 32, c.B), 256, 0, c.st>>>(in, out, c.P(g), c.P(b), len, C, T, flags, nullptr,
-                                                                            nullptr, 1, 1, planes, range_slots(c.h, true));
-    else if (C <= 256 && !ts32)
-        ln_tile_kernel<0, false, 16><<<dim3((T + 15) / 16, c.B), 256, 0, c.st>>>(in, out, c.P(g), c.P(b), len, C, T, flags, nullptr,
-                                                                                 nullptr, 1, 1);
-    else if (C <= 256)
-        ln_tile_kernel<0><<<dim3((T + 31) / 32, c.B), 256, 0, c.st>>>(in, out, c.P(g), c.P(b), len, C, T, flags, nullptr,
-                                                                      nullptr, 1, 1);
-    else
-        layernorm_c_kernel<<<dim3((T + 63) / 64, c.B), 64, 0, c.st>>>(in, out, c.P(g), c.P(b), len, C, T, flags);
+    const int form = C > 256 ? LN_FORM_COLUMN : (ts32 ? LN_FORM_TILE32 : LN_FORM_TILE16);
+    const bool fused_planes = planes && C <= 256 && C % 8 == 0;
+    launch_layernorm(c.st, form, c.B, C, T, in, out, c.P(g), c.P(b), len, flags, fused_planes ? planes : nullptr,
+                     fused_planes ? range_slots(c.h, true) : nullptr);
     c.note(hipGetLastError());
     c.h->stats.total_launches++;
-    if (planes && !(C <= 256 && C % 8 == 0)) split_planes(c, out, planes, C, T, nullptr);
+    if (planes && !fused_planes) split_planes(c, out, planes, C, T, nullptr);
+}
+
+// A stack of fused DDSConv layers over raw device pointers.  One launch per layer, ping-ponging between the three buffers
+// hbuf, y, y2 ([B][C][T] each) so that the result of the last layer lands in hbuf: each layer must write a buffer other than
+// the one it reads.  layer16: dds_layer16_kernel (C / 32 in {2, 4, 6, 8}), else dds_layer_kernel (1, 2, 3, 4, 6, 8).
+// head, tail (layer16 only, optional): see ddsconv().  With a tail hbuf does NOT receive the stack's result.
+struct DdsLayerPtrs {
+    const float *dw_w, *dw_b, *ln1_g, *ln1_b, *ln2_g, *ln2_b;
+    const float *pw_bias;  // [C]
+    const float *pw16;     // layer16: the 1 x 1 weights in dds_layer16_kernel's A-operand layout
+    const float *pw;       // layer32: ... packed for the conv engine (pack_conv), with that packing's geometry
+    int CK, nchunks, MB;
+    int dil;
+};
+struct DdsHead {
+    const float *in, *z, *w, *b;  // conditioning tensor [B][C][T], z channel row of utterance 0 (rows 2 T apart), pre weights
+};
+struct DdsTail {
+    const float *w16, *b;  // [ceil(rows / 16) * 16][C] in the pw16 layout, bias [rows] or nullptr
+    float *out;            // [B][rows][T]
+    int rows;
+};
+// 32-row blocks per m-tile of a conv-engine packing (DdsLayerPtrs::MB)
+int dds_pw_blocks(const ConvDesc &pw) { return (pw.cfg == 2 ? 128 : ((pw.cfg == 1 || pw.cfg == 3) ? 64 : 32)) / 32; }
+hipError_t launch_dds_stack(hipStream_t st, bool layer16, int B, int C, int T, int n_layers, const DdsLayerPtrs *layers, float *hbuf,
+                            float *y, float *y2, const int *len, const DdsHead *head, const DdsTail *tail) {
+    const int nblk = C / 32;
+    float *bufs[3] = {hbuf, y, y2};
+    int cur = 0;
+    hipError_t err = hipSuccess;
+    auto note = [&](hipError_t e) {
+        if (err == hipSuccess) err = e;
+    };
+    for (int l = 0; l < n_layers; l++) {
+        const DdsLayerPtrs &L = layers[l];
+        const int left = n_layers - 1 - l;            // layers after this one
+        int nxt = left == 0 ? 0 : (cur == 1 ? 2 : 1); // last layer writes hbuf ...
+        if (nxt == cur) {                             // ... unless it would read it too (n_layers == 1): detour
+            nxt = 1;
+        }
+        if (layer16) {
+            DdsLayer16Args q{};
+            q.in = bufs[cur];
+            q.out = bufs[nxt];
+            if (l == 0 && head) {
+                q.in = head->in;
+                q.head_z = head->z;
+                q.head_w = head->w;
+                q.head_b = head->b;
+                q.head_zstride = (int64_t)2 * T;
+            }
+            q.len = len;
+            q.dw_w = L.dw_w;
+            q.dw_b = L.dw_b;
+            q.ln1_g = L.ln1_g;
+            q.ln1_b = L.ln1_b;
+            q.ln2_g = L.ln2_g;
+            q.ln2_b = L.ln2_b;
+            q.pw16 = L.pw16;
+            q.pw_bias = L.pw_bias;
+            q.T = T;
+            q.dil = L.dil;
+            q.mask_out = left == 0;
+            if (left == 0 && tail) {
+                q.tail_w16 = tail->w16;
+                q.tail_b = tail->b;
+                q.tail_out = tail->out;
+                q.tail_rows = tail->rows;
+                q.tail_mask = 1;
+            }
+            launch_dds_layer16(st, B, nblk, q);
+        } else {
+            DdsLayerArgs a{};
+            a.in = bufs[cur];
+            a.out = bufs[nxt];
+            a.len = len;
+            a.dw_w = L.dw_w;
+            a.dw_b = L.dw_b;
+            a.ln1_g = L.ln1_g;
+            a.ln1_b = L.ln1_b;
+            a.ln2_g = L.ln2_g;
+            a.ln2_b = L.ln2_b;
+            a.pw = L.pw;
+            a.pw_bias = L.pw_bias;
+            a.C = C;
+            a.T = T;
+            a.dil = L.dil;
+            a.mask_out = left == 0;
+            a.CK = L.CK;
+            a.nchunks = L.nchunks;
+            a.MB = L.MB;
+            launch_dds_layer32(st, B, nblk, a);
+        }
+        note(hipGetLastError());
+        cur = nxt;
+    }
+    if (cur != 0 && !(layer16 && tail)) note(hipMemcpyAsync(hbuf, bufs[cur], (size_t)B * C * T * 4, hipMemcpyDeviceToDevice, st));
+    return err;
 }
 
 // DDSConv (modules.py:117-129) in place on h [B,C,T]; y,y2 are scratch of the same size.
@@ -983,11 +1144,10 @@ void layernorm(Ctx &c, const float *in, float *out, int64_t g, int64_t b, const 
 // stack's result inside the last layer's launch, written to tail_out [B][tail->Cout][T]; hbuf does then NOT receive the stack's
 // result.  Returns whether the tail was taken (false: the caller runs the conv itself).
 // head (optional, ConvFlow stacks): the stack's input is head->w[c] * z + head->b[c] + head->in (ConvFlow.pre + conditioning),
-// formed by the first layer while it loads; hbuf is then never read.  *head_done tells whether that happened (false: the caller
-// must have filled hbuf, e.g. by cf_pre_kernel).
-struct DdsHead {
-    const float *in, *z, *w, *b;  // conditioning tensor [B][C][T], z channel row of utterance 0 (rows 2 T apart), pre weights
-};
+// formed by the first layer while it loads; hbuf is then never read.  The caller asks dds16_head_ok() whether that form is
+// taken; where it is not, it fills hbuf itself (launch_cf_pre) and passes no head.
+// The form by width: C <= 256 with C / 32 in {2, 4, 6, 8} runs dds_layer16_kernel (VITSMI_DDS16=0: the 32-column kernel, A/B
+// timing), 32 and 96 channels dds_layer_kernel, every other width (160 and 224 among them) the three launches per layer below.
 bool dds16_head_ok(const DDSDesc &d, int C) {
     static const bool off = [] { const char *e = std::getenv("VITSMI_DDS16"); return e && e[0] == '0'; }();
     static const bool head_off = [] { const char *e = std::getenv("VITSMI_DDS_HEAD"); return e && e[0] == '0'; }();  // A/B timing only
@@ -1000,126 +1160,39 @@ bool ddsconv(Ctx &c, const DDSDesc &d, float *hbuf, float *y, float *y2, const i
              const ConvDesc *tail = nullptr, int64_t tail16 = -1, float *tail_out = nullptr, const DdsHead *head = nullptr) {
     static const bool unfused = std::getenv("VITSMI_DDS_UNFUSED") != nullptr;  // A/B timing only
     static const bool tail_off = [] { const char *e = std::getenv("VITSMI_DDS_TAIL"); return e && e[0] == '0'; }();  // A/B timing only
-    bool tail_done = false;
+    static const bool dds16_off = [] { const char *e = std::getenv("VITSMI_DDS16"); return e && e[0] == '0'; }();
     const int nblk = C / 32;
     if (!unfused && C <= 256 && C % 32 == 0 && nblk != 5 && nblk != 7 && d.K == 3 && d.n_layers > 0) {
-        // one launch per layer (dds_layer_kernel), ping-ponging between the three buffers so that the result of the
-        // last layer lands in hbuf: each layer must write a buffer other than the one it reads
-        float *bufs[3] = {hbuf, y, y2};
-        int cur = 0;
+        bool layer16 = !dds16_off && (nblk == 2 || nblk == 4 || nblk == 6 || nblk == 8);
+        DdsLayerPtrs layers[4];
         for (int l = 0; l < d.n_layers; l++) {
             const auto &L = d.l[l];
-            const int left = d.n_layers - 1 - l;          // layers after this one
-            int nxt = left == 0 ? 0 : (cur == 1 ? 2 : 1); // last layer writes hbuf ...
-            if (nxt == cur) {                             // ... unless it would read it too (n_layers == 1): detour
-                nxt = 1;
-            }
-            // 16 columns per workgroup on v_mfma_f32_16x16x4_f32 (kernels.hip.hpp dds_layer16_kernel; VITSMI_DDS16=0: the
-            // 32-column kernel, A/B timing)
-            static const bool dds16_off = [] { const char *e = std::getenv("VITSMI_DDS16"); return e && e[0] == '0'; }();
-            if (!dds16_off && L.pw16 >= 0 && (nblk == 2 || nblk == 4 || nblk == 6 || nblk == 8)) {
-                DdsLayer16Args q{};
-                q.in = bufs[cur];
-                q.out = bufs[nxt];
-                if (l == 0 && head) {  // (dds16_head_ok: the caller checked that this path is taken)
-                    q.in = head->in;
-                    q.head_z = head->z;
-                    q.head_w = head->w;
-                    q.head_b = head->b;
-                    q.head_zstride = (int64_t)2 * T;
-                }
-                q.len = len;
-                q.dw_w = c.P(L.dw_w);
-                q.dw_b = c.P(L.dw_b);
-                q.ln1_g = c.P(L.ln1_g);
-                q.ln1_b = c.P(L.ln1_b);
-                q.ln2_g = c.P(L.ln2_g);
-                q.ln2_b = c.P(L.ln2_b);
-                q.pw16 = c.P(L.pw16);
-                q.pw_bias = L.pw.b_off >= 0 ? c.P(L.pw.b_off) : c.P(c.m.zeros_off);
-                q.T = T;
-                q.dil = L.dil;
-                q.mask_out = l == d.n_layers - 1;
-                if (left == 0 && tail && tail16 >= 0 && tail_out && !tail_off && tail->Cin == C && tail->K == 1 && tail->Cout <= C) {
-                    q.tail_w16 = c.P(tail16);
-                    q.tail_b = tail->b_off >= 0 ? c.P(tail->b_off) : nullptr;
-                    q.tail_out = tail_out;
-                    q.tail_rows = tail->Cout;
-                    q.tail_mask = 1;
-                    tail_done = true;
-                    const double tfl = 2.0 * tail->macs_per_t * (double)T * c.B;  // (accounted as conv() would)
-                    c.h->stats.conv_flops += tfl;
-                    (c.h->cur_stage == 1 ? c.h->stats.dp_flops : c.h->stats.enc_flops) += tfl;
-                }
-                const dim3 dg16((T + 15) / 16, c.B);
-                switch (nblk) {
-                    case 2: dds_layer16_kernel<2><<<dg16, 256, 0, c.st>>>(q); break;
-                    case 4: dds_layer16_kernel<4><<<dg16, 256, 0, c.st>>>(q); break;
-                    case 6: dds_layer16_kernel<6><<<dg16, 256, 0, c.st>>>(q); break;
-                    default: dds_layer16_kernel<8><<<dg16, 256, 0, c.st>>>(q); break;
-                }
-                c.note(hipGetLastError());
-                c.h->stats.total_launches++;
-                {
-                    const double fl = 2.0 * L.pw.macs_per_t * (double)T * c.B;
-                    c.h->stats.conv_flops += fl;
-                    (c.h->cur_stage == 1 ? c.h->stats.dp_flops : c.h->stats.enc_flops) += fl;
-                }
-                cur = nxt;
-                continue;
-            }
-            DdsLayerArgs a{};
-            a.in = bufs[cur];
-            a.out = bufs[nxt];
-            a.len = len;
-            a.dw_w = c.P(L.dw_w);
-            a.dw_b = c.P(L.dw_b);
-            a.ln1_g = c.P(L.ln1_g);
-            a.ln1_b = c.P(L.ln1_b);
-            a.ln2_g = c.P(L.ln2_g);
-            a.ln2_b = c.P(L.ln2_b);
-            a.pw = c.P(L.pw.w_off);
-            a.pw_bias = L.pw.b_off >= 0 ? c.P(L.pw.b_off) : c.P(c.m.zeros_off);
-            a.C = C;
-            a.T = T;
-            a.dil = L.dil;
-            a.mask_out = l == d.n_layers - 1;
-            a.CK = L.pw.CK;
-            a.nchunks = L.pw.nchunks;
-            a.MB = (L.pw.cfg == 2 ? 128 : ((L.pw.cfg == 1 || L.pw.cfg == 3) ? 64 : 32)) / 32;
-            const dim3 dg((T + 31) / 32, c.B);
-            switch (nblk) {  // (channel count at compile time: straight-line channel loops)
-                case 1: dds_layer_kernel<1><<<dg, 256, 0, c.st>>>(a); break;
-                case 2: dds_layer_kernel<2><<<dg, 256, 0, c.st>>>(a); break;
-                case 3: dds_layer_kernel<3><<<dg, 256, 0, c.st>>>(a); break;
-                case 4: dds_layer_kernel<4><<<dg, 256, 0, c.st>>>(a); break;
-                case 6: dds_layer_kernel<6><<<dg, 256, 0, c.st>>>(a); break;
-                default: dds_layer_kernel<8><<<dg, 256, 0, c.st>>>(a); break;
-            }
-            c.note(hipGetLastError());
-            c.h->stats.total_launches++;
-            {   // the 1x1 conv's algorithmic work, as conv() would account it
-                const double fl = 2.0 * L.pw.macs_per_t * (double)T * c.B;
-                c.h->stats.conv_flops += fl;
-                (c.h->cur_stage == 1 ? c.h->stats.dp_flops : c.h->stats.enc_flops) += fl;
-            }
-            cur = nxt;
+            layer16 = layer16 && L.pw16 >= 0;
+            layers[l] = {c.P(L.dw_w), c.P(L.dw_b), c.P(L.ln1_g), c.P(L.ln1_b), c.P(L.ln2_g), c.P(L.ln2_b),
+                         L.pw.b_off >= 0 ? c.P(L.pw.b_off) : c.P(c.m.zeros_off), L.pw16 >= 0 ? c.P(L.pw16) : nullptr,
+                         c.P(L.pw.w_off), L.pw.CK, L.pw.nchunks, dds_pw_blocks(L.pw), L.dil};
+            // the 1x1 conv's algorithmic work, as conv() would account it
+            const double fl = 2.0 * L.pw.macs_per_t * (double)T * c.B;
+            c.h->stats.conv_flops += fl;
+            (c.h->cur_stage == 1 ? c.h->stats.dp_flops : c.h->stats.enc_flops) += fl;
         }
-        if (cur != 0 && !tail_done) c.note(hipMemcpyAsync(hbuf, bufs[cur], (size_t)c.B * C * T * 4, hipMemcpyDeviceToDevice, c.st));
+        DdsTail tl{};
+        const bool tail_done = layer16 && tail && tail16 >= 0 && tail_out && !tail_off && tail->Cin == C && tail->K == 1 && tail->Cout <= C;
+        if (tail_done) {
+            tl = {c.P(tail16), tail->b_off >= 0 ? c.P(tail->b_off) : nullptr, tail_out, tail->Cout};
+            const double tfl = 2.0 * tail->macs_per_t * (double)T * c.B;  // (accounted as conv() would)
+            c.h->stats.conv_flops += tfl;
+            (c.h->cur_stage == 1 ? c.h->stats.dp_flops : c.h->stats.enc_flops) += tfl;
+        }
+        // (head: dds16_head_ok - the caller checked that the 16-column path is taken)
+        c.note(launch_dds_stack(c.st, layer16, c.B, C, T, d.n_layers, layers, hbuf, y, y2, len, layer16 ? head : nullptr,
+                                tail_done ? &tl : nullptr));
+        c.h->stats.total_launches += d.n_layers;
         return tail_done;
     }
     for (int l = 0; l < d.n_layers; l++) {
         const auto &L = d.l[l];
-        if (C <= 256 && d.K == 3)
-            ln_tile_kernel<3><<<dim3((T + 31) / 32, c.B), 256, 0, c.st>>>(hbuf, y, c.P(L.ln1_g), c.P(L.ln1_b), len, C, T,
-                                                                          LN_GELU, c.P(L.dw_w), c.P(L.dw_b), d.K, L.dil);
-        else if (C <= 256)
-            ln_tile_kernel<1><<<dim3((T + 31) / 32, c.B), 256, 0, c.st>>>(hbuf, y, c.P(L.ln1_g), c.P(L.ln1_b), len, C, T,
-                                                                          LN_GELU, c.P(L.dw_w), c.P(L.dw_b), d.K, L.dil);
-        else
-            dds_dw_ln_gelu_kernel<<<dim3((T + 63) / 64, c.B), 64, 0, c.st>>>(hbuf, y, c.P(L.dw_w), c.P(L.dw_b),
-                                                                             c.P(L.ln1_g), c.P(L.ln1_b), len, C, T, d.K,
-                                                                             L.dil);
+        launch_dw_ln(c.st, c.B, C, T, d.K, L.dil, hbuf, y, c.P(L.dw_w), c.P(L.dw_b), c.P(L.ln1_g), c.P(L.ln1_b), len);
         c.note(hipGetLastError());
         c.h->stats.total_launches++;
         conv(c, L.pw, y, (int64_t)C * T, T, y2, (int64_t)C * T, 0);
@@ -1320,21 +1393,18 @@ int run_tokens(vits_handle *h, const int64_t *d_ids, const int64_t *d_lens, int 
             DdsHead hd{cond, z + (int64_t)ch0 * T, c.P(cf.pre_w), c.P(cf.pre_b)};
             const bool use_head = dds16_head_ok(cf.convs, Cd);
             if (!use_head) {
-                cf_pre_kernel<<<dim3((T + 255) / 256, Cd, B), 256, 0, st>>>(z, ch0, c.P(cf.pre_w), c.P(cf.pre_b), cond, h2, Cd, T);
+                launch_cf_pre(st, B, Cd, T, z, ch0, c.P(cf.pre_w), c.P(cf.pre_b), cond, h2);
                 h->stats.total_launches++;
             }
             if (!ddsconv(c, cf.convs, h2, y, y2, len, Cd, T, &cf.proj, cf.proj16, pr, use_head ? &hd : nullptr))
                 conv(c, cf.proj, h2, sC, T, pr, (int64_t)cf.proj.Cout * T, EPI_MASK, masked);
             float sqc = std::sqrt((float)Cd);
-            if (cf.nb <= 10)
-                rqs_inverse_kernel<10><<<dim3((T + 63) / 64, B), 64, 0, st>>>(pr, z, len, ch0, ch1, cf.nb, T, sqc);
-            else
-                rqs_inverse_kernel<16><<<dim3((T + 63) / 64, B), 64, 0, st>>>(pr, z, len, ch0, ch1, cf.nb, T, sqc);
+            launch_rqs_inverse(st, B, T, cf.nb, pr, z, len, ch0, ch1, sqc);
             c.note(hipGetLastError());
             h->stats.total_launches++;
         }
         swapped ^= 1;
-        ea_logw_kernel<<<dim3((T + 63) / 64, B), 64, 0, st>>>(z, swapped, m.ea_m0, m.ea_logs0, len, h->d_logw, T);
+        launch_ea_logw(st, B, T, z, swapped, m.ea_m0, m.ea_logs0, len, h->d_logw);
         h->stats.total_launches++;
     } else {
         const int Fd = m.dpp_F;
@@ -4402,6 +4472,200 @@ int vits_test_post_conv(int device_id, const float *x, int B, int C, int T, cons
     TCHECK(hipGetLastError());
     TCHECK(hipDeviceSynchronize());
     TCHECK(download(out, dout, no));
+    return VITS_OK;
+}
+
+// The text-side kernels of the encoder and the stochastic duration predictor by value (launch_layernorm ... launch_ea_logw
+// above).  Every output is pre-filled with 0xff bytes (NaN as fp32 and as fp16) and downloaded together with a guard row of T
+// elements (T cells of 8 for planes) behind it, so the caller sees an element never written and a write past the tensor's end.
+namespace {
+int sdp_test_sizes(const char *what, int B, int C, int T) {
+    if (B <= 0 || B > 65535 || C <= 0 || C > 65535 || T <= 0 || (int64_t)B * C * T > ((int64_t)1 << 28))
+        return fail(nullptr, VITS_E_ARG, "%s: bad sizes (B=%d, C=%d, T=%d)", what, B, C, T);
+    return VITS_OK;
+}
+// `n` elements of `host` in front of a 0xff guard of `guard` elements
+float *up_guarded(DevBufs &D, const float *host, size_t n, size_t guard) {
+    float *d = D.fill<float>(n + guard, 0xff);
+    if (d && host && n && D.ok()) D.err = hipMemcpy(d, host, n * sizeof(float), hipMemcpyHostToDevice);
+    return d;
+}
+}  // namespace
+
+int vits_test_layernorm(int device_id, const float *x, const float *out_init, int B, int C, int T, const float *gamma,
+                        const float *beta, const int64_t *lens, int flags, int form, int in_place, const float *dw_w,
+                        const float *dw_b, int K, int dil, float *out, uint16_t *planes) {
+    if (int rc = test_dev(device_id)) return rc;
+    if (int rc = sdp_test_sizes("layernorm", B, C, T)) return rc;
+    if (!x || !gamma || !beta || !out || flags < 0 || flags > 15 || form < LN_FORM_TILE16 || form > LN_FORM_COLUMN)
+        return fail(nullptr, VITS_E_ARG, "layernorm: null tensor, flags=%d or form=%d", flags, form);
+    std::vector<int> l32;
+    if (lens)
+        if (int rc = glue_test_lens(lens, B, T, l32)) return rc;
+    if (!lens && ((flags & LN_MASK) || dw_w)) return fail(nullptr, VITS_E_ARG, "layernorm: LN_MASK and the depthwise conv need lens");
+    if (form != LN_FORM_COLUMN && C > 256) return fail(nullptr, VITS_E_ARG, "layernorm: the tile forms hold C <= 256 (C=%d)", C);
+    if (in_place && out_init) return fail(nullptr, VITS_E_ARG, "layernorm: in place, x is the initial content of out");
+    if (dw_w) {  // (the pipeline forms depthwise + LN + GELU out of place, by width, without planes: launch_dw_ln)
+        if (!dw_b || K < 1 || K > 15 || dil < 1 || dil > 65536 || in_place || planes || flags != LN_GELU || form == LN_FORM_TILE16 ||
+            (form == LN_FORM_COLUMN) != (C > 256))
+            return fail(nullptr, VITS_E_ARG, "layernorm: depthwise (K=%d, dil=%d) runs out of place, without planes, with LN_GELU alone, "
+                                             "on tile32 (C <= 256) or column (C > 256)", K, dil);
+    }
+    if (planes && (form == LN_FORM_COLUMN || C % 8)) return fail(nullptr, VITS_E_ARG, "layernorm: planes need a tile form and C %% 8 == 0 (C=%d)", C);
+    const size_t n = (size_t)B * C * T;
+    DevBufs D;
+    const int *dlen = lens ? D.up(l32.data(), (size_t)B) : nullptr;
+    const float *dg = D.up(gamma, (size_t)C), *db = D.up(beta, (size_t)C);
+    float *dout = up_guarded(D, in_place ? x : out_init, n, (size_t)T);
+    const float *dx = in_place ? dout : D.up(x, n);
+    uint16_t *dpl = planes ? D.fill<uint16_t>(n * 3 + (size_t)T * 8, 0xff) : nullptr;
+    unsigned *dpk = planes ? D.fill<unsigned>((size_t)kSxPeakSlots * kSxPeakStride) : nullptr;
+    const float *dww = dw_w ? D.up(dw_w, (size_t)C * K) : nullptr, *dwb = dw_w ? D.up(dw_b, (size_t)C) : nullptr;
+    TCHECK(D.err);
+    if (dw_w) launch_dw_ln(nullptr, B, C, T, K, dil, dx, dout, dww, dwb, dg, db, dlen);
+    else launch_layernorm(nullptr, form, B, C, T, dx, dout, dg, db, dlen, flags, dpl, dpk);
+    TCHECK(hipGetLastError());
+    TCHECK(hipDeviceSynchronize());
+    TCHECK(download(out, dout, n + T));
+    if (planes) TCHECK(download(planes, dpl, n * 3 + (size_t)T * 8));
+    return VITS_OK;
+}
+
+int vits_test_dds(int device_id, int form, const float *x, int B, int C, int T, const int64_t *lens, int n_layers,
+                  const vits_test_dds_layer *layers, int mask_out, const float *head_cond, const float *head_z, int head_ch,
+                  const float *head_w, const float *head_b, const float *tail_w, const float *tail_b, int tail_rows, float *out) {
+    if (int rc = test_dev(device_id)) return rc;
+    if (int rc = sdp_test_sizes("dds", B, C, T)) return rc;
+    std::vector<int> l32;
+    if (int rc = glue_test_lens(lens, B, T, l32)) return rc;
+    const int nblk = C / 32;
+    const bool layer16 = form == 16, head = head_cond != nullptr, tail = tail_w != nullptr;
+    if ((form != 16 && form != 32) || C % 32 || C > 256 || nblk == 5 || nblk == 7 || (layer16 && (nblk & 1)))
+        return fail(nullptr, VITS_E_ARG, "dds: form %d has no instantiation for C=%d", form, C);
+    if (!layers || !out || n_layers < 1 || n_layers > 4 || (!head && !x))
+        return fail(nullptr, VITS_E_ARG, "dds: null tensor or n_layers=%d outside [1, 4]", n_layers);
+    if (!mask_out && (n_layers != 1 || head || tail))
+        return fail(nullptr, VITS_E_ARG, "dds: mask_out = 0 is a single layer without head or tail (the stack masks behind its last layer)");
+    if ((head || tail) && !layer16) return fail(nullptr, VITS_E_ARG, "dds: head and tail belong to the 16-column form");
+    if (head && (!head_z || !head_w || !head_b || (head_ch != 0 && head_ch != 1) || n_layers < 2))
+        return fail(nullptr, VITS_E_ARG, "dds: the head needs z, pre_w, pre_b, a channel 0 / 1 and a stack of >= 2 layers");
+    if (tail && (tail_rows < 1 || tail_rows > C)) return fail(nullptr, VITS_E_ARG, "dds: tail rows %d outside [1, C=%d]", tail_rows, C);
+    const float *pw_w[4], *pw_b[4];
+    for (int l = 0; l < n_layers; l++) {
+        const vits_test_dds_layer &L = layers[l];
+        if (!L.dw_w || !L.dw_b || !L.ln1_g || !L.ln1_b || !L.pw_w || !L.pw_b || !L.ln2_g || !L.ln2_b || L.dil < 1 || L.dil > 65536)
+            return fail(nullptr, VITS_E_ARG, "dds: layer %d has a null tensor or dil=%d", l, L.dil);
+        pw_w[l] = L.pw_w;
+        pw_b[l] = L.pw_b;
+    }
+    TestDds td;
+    std::vector<float> arena;
+    const std::string e = pack_test_dds(C, n_layers, pw_w, pw_b, tail_w, tail_rows, &td, &arena);
+    if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
+    const size_t n = (size_t)B * C * T, nc = (size_t)C;
+    DevBufs D;
+    const float *dA = D.up(arena.data(), arena.size());
+    const int *dlen = D.up(l32.data(), (size_t)B);
+    float *hbuf = up_guarded(D, head ? nullptr : x, n, (size_t)T);  // (with a head the stack never reads hbuf)
+    float *y = D.fill<float>(n, 0xff), *y2 = D.fill<float>(n, 0xff);
+    DdsLayerPtrs lp[4];
+    for (int l = 0; l < n_layers; l++) {
+        const vits_test_dds_layer &L = layers[l];
+        const ConvDesc &pw = td.pw[l];
+        lp[l] = {D.up(L.dw_w, nc * 3), D.up(L.dw_b, nc), D.up(L.ln1_g, nc), D.up(L.ln1_b, nc), D.up(L.ln2_g, nc), D.up(L.ln2_b, nc),
+                 D.up(L.pw_b, nc), dA ? dA + td.pw16[l] : nullptr, dA ? dA + pw.w_off : nullptr, pw.CK, pw.nchunks, dds_pw_blocks(pw),
+                 L.dil};
+    }
+    DdsHead hd{};
+    if (head) hd = {D.up(head_cond, n), nullptr, D.up(head_w, nc), D.up(head_b, nc)};
+    const float *dz = head ? D.up(head_z, (size_t)B * 2 * T) : nullptr;
+    if (head && dz) hd.z = dz + (size_t)head_ch * T;
+    DdsTail tl{};
+    const size_t nt = (size_t)B * (tail ? tail_rows : 0) * T;
+    if (tail) tl = {dA ? dA + td.tail16 : nullptr, tail_b ? D.up(tail_b, (size_t)tail_rows) : nullptr, D.fill<float>(nt + T, 0xff), tail_rows};
+    TCHECK(D.err);
+    if (mask_out) {
+        TCHECK(launch_dds_stack(nullptr, layer16, B, C, T, n_layers, lp, hbuf, y, y2, dlen, head ? &hd : nullptr, tail ? &tl : nullptr));
+    } else {  // one layer, launched directly: x -> y, then into the guarded buffer
+        const DdsLayerPtrs &L = lp[0];
+        if (layer16) {
+            DdsLayer16Args q{};
+            q.in = hbuf; q.out = y; q.len = dlen;
+            q.dw_w = L.dw_w; q.dw_b = L.dw_b; q.ln1_g = L.ln1_g; q.ln1_b = L.ln1_b; q.ln2_g = L.ln2_g; q.ln2_b = L.ln2_b;
+            q.pw16 = L.pw16; q.pw_bias = L.pw_bias; q.T = T; q.dil = L.dil; q.mask_out = 0;
+            launch_dds_layer16(nullptr, B, nblk, q);
+        } else {
+            DdsLayerArgs a{};
+            a.in = hbuf; a.out = y; a.len = dlen;
+            a.dw_w = L.dw_w; a.dw_b = L.dw_b; a.ln1_g = L.ln1_g; a.ln1_b = L.ln1_b; a.ln2_g = L.ln2_g; a.ln2_b = L.ln2_b;
+            a.pw = L.pw; a.pw_bias = L.pw_bias; a.C = C; a.T = T; a.dil = L.dil; a.mask_out = 0;
+            a.CK = L.CK; a.nchunks = L.nchunks; a.MB = L.MB;
+            launch_dds_layer32(nullptr, B, nblk, a);
+        }
+        TCHECK(hipGetLastError());
+        TCHECK(hipMemcpyAsync(hbuf, y, n * sizeof(float), hipMemcpyDeviceToDevice, nullptr));
+    }
+    TCHECK(hipGetLastError());
+    TCHECK(hipDeviceSynchronize());
+    if (tail) TCHECK(download(out, tl.out, nt + T));
+    else TCHECK(download(out, hbuf, n + T));
+    return VITS_OK;
+}
+
+int vits_test_cf_pre(int device_id, const float *z, int ch, const float *w, const float *bias, const float *cond, int B, int C, int T,
+                     float *out) {
+    if (int rc = test_dev(device_id)) return rc;
+    if (int rc = sdp_test_sizes("cf_pre", B, C, T)) return rc;
+    if (!z || !w || !bias || !cond || !out || (ch != 0 && ch != 1)) return fail(nullptr, VITS_E_ARG, "cf_pre: null tensor or channel %d", ch);
+    const size_t n = (size_t)B * C * T;
+    DevBufs D;
+    const float *dz = D.up(z, (size_t)B * 2 * T), *dw = D.up(w, (size_t)C), *db = D.up(bias, (size_t)C), *dc = D.up(cond, n);
+    float *dout = D.fill<float>(n + T, 0xff);
+    TCHECK(D.err);
+    launch_cf_pre(nullptr, B, C, T, dz, ch, dw, db, dc, dout);
+    TCHECK(hipGetLastError());
+    TCHECK(hipDeviceSynchronize());
+    TCHECK(download(out, dout, n + T));
+    return VITS_OK;
+}
+
+int vits_test_rqs_inverse(int device_id, const float *pr, const float *z, int B, int T, const int64_t *lens, int ch0, int nb,
+                          float sqrt_c, float *out) {
+    if (int rc = test_dev(device_id)) return rc;
+    if (int rc = sdp_test_sizes("rqs_inverse", B, 2, T)) return rc;
+    std::vector<int> l32;
+    if (int rc = glue_test_lens(lens, B, T, l32)) return rc;
+    if (!pr || !z || !out || (ch0 != 0 && ch0 != 1) || nb < 1 || nb > 16 || !(sqrt_c > 0.f))
+        return fail(nullptr, VITS_E_ARG, "rqs_inverse: null tensor, channel %d, %d bins outside [1, 16] or divisor %g", ch0, nb, (double)sqrt_c);
+    const size_t n = (size_t)B * 2 * T;
+    DevBufs D;
+    const float *dp = D.up(pr, (size_t)B * (3 * nb - 1) * T);
+    const int *dlen = D.up(l32.data(), (size_t)B);
+    float *dz = up_guarded(D, z, n, (size_t)T);
+    TCHECK(D.err);
+    launch_rqs_inverse(nullptr, B, T, nb, dp, dz, dlen, ch0, ch0 ^ 1, sqrt_c);
+    TCHECK(hipGetLastError());
+    TCHECK(hipDeviceSynchronize());
+    TCHECK(download(out, dz, n + T));
+    return VITS_OK;
+}
+
+int vits_test_ea_logw(int device_id, const float *z, int ch, float m0, float logs0, const int64_t *lens, int B, int T, float *out) {
+    if (int rc = test_dev(device_id)) return rc;
+    if (int rc = sdp_test_sizes("ea_logw", B, 2, T)) return rc;
+    std::vector<int> l32;
+    if (int rc = glue_test_lens(lens, B, T, l32)) return rc;
+    if (!z || !out || (ch != 0 && ch != 1)) return fail(nullptr, VITS_E_ARG, "ea_logw: null tensor or channel %d", ch);
+    const size_t n = (size_t)B * T;
+    DevBufs D;
+    const float *dz = D.up(z, n * 2);
+    const int *dlen = D.up(l32.data(), (size_t)B);
+    float *dout = D.fill<float>(n + T, 0xff);
+    TCHECK(D.err);
+    launch_ea_logw(nullptr, B, T, dz, ch, m0, logs0, dlen, dout);
+    TCHECK(hipGetLastError());
+    TCHECK(hipDeviceSynchronize());
+    TCHECK(download(out, dout, n + T));
     return VITS_OK;
 }
 

@@ -1939,3 +1939,152 @@ def test_post_conv(x, w, slope, vlen=None, hop=1, kernel="planar", device_id=0):
                                          _POST_CONV_KERNELS[kernel], _ffi.ptr(out))
     _glue_check(rc, "vits_test_post_conv")
     return out
+
+
+# ---- the text-side kernels of the encoder and the stochastic duration predictor, by value.  Every wrapper returns the
+# tensor AND the guard row behind it as the device left it (0xff bytes, NaN, where nothing wrote).
+
+LN_GELU, LN_ACCUM, LN_MASK, LN_RELU_IN = 1, 2, 4, 8
+_LN_FORMS = {"tile16": 0, "tile32": 1, "column": 2}
+
+
+def _f32(a, shape, name):
+    a = np.ascontiguousarray(a, np.float32)
+    if a.shape != tuple(shape):
+        raise SessionError(f"{name} must be {list(shape)}, got {list(a.shape)}")
+    return a
+
+
+def _lens_or_none(lens, B):
+    if lens is None:
+        return None
+    lens = np.ascontiguousarray(lens, np.int64)
+    if lens.shape != (B,):
+        raise SessionError(f"lens must be [B] = [{B}], got {lens.shape}")
+    return lens
+
+
+def _guarded(n, T):
+    return np.zeros(n + T, np.float32)
+
+
+def test_layernorm(x, gamma, beta, lens=None, flags=0, form="tile16", out_init=None, in_place=False, dw_w=None, dw_b=None,
+                   dil=1, planes=False, device_id=0):
+    """LayerNorm over channels of x float32 [B, C, T] through launch_layernorm (form: "tile16", "tile32", "column"), or -
+    dw_w [C, K], dw_b [C] - depthwise conv + LN + GELU through launch_dw_ln.  flags: LN_GELU | LN_ACCUM | LN_MASK | LN_RELU_IN;
+    out_init: the initial content of out (LN_ACCUM), in_place: x is.  Returns (out [B, C, T], guard [T]) and, with planes=True,
+    also (planes uint16 [B, 3, C/8, T, 8], plane guard [T, 8])."""
+    if form not in _LN_FORMS:
+        raise SessionError(f"unknown form {form!r}")
+    x = np.ascontiguousarray(x, np.float32)
+    if x.ndim != 3:
+        raise SessionError(f"x must be [B, C, T], got {x.shape}")
+    B, Cc, T = x.shape
+    gamma, beta = _f32(gamma, (Cc,), "gamma"), _f32(beta, (Cc,), "beta")
+    lens = _lens_or_none(lens, B)
+    if out_init is not None:
+        out_init = _f32(out_init, x.shape, "out_init")
+    K = 1
+    if dw_w is not None:
+        dw_w = np.ascontiguousarray(dw_w, np.float32)
+        if dw_w.ndim != 2 or dw_w.shape[0] != Cc:
+            raise SessionError(f"dw_w must be [C, K], got {dw_w.shape}")
+        K = dw_w.shape[1]
+        dw_b = _f32(dw_b, (Cc,), "dw_b")
+    n = B * Cc * T
+    out = _guarded(n, T)
+    pl = np.zeros(n * 3 + T * 8, np.uint16) if planes else None
+    rc = _ffi.load().vits_test_layernorm(device_id, _ffi.ptr(x), _ffi.ptr(out_init), B, Cc, T, _ffi.ptr(gamma), _ffi.ptr(beta),
+                                         _ffi.ptr(lens), int(flags), _LN_FORMS[form], int(bool(in_place)), _ffi.ptr(dw_w),
+                                         _ffi.ptr(dw_b), int(K), int(dil), _ffi.ptr(out), _ffi.ptr(pl))
+    _glue_check(rc, "vits_test_layernorm")
+    res = (out[:n].reshape(B, Cc, T), out[n:])
+    if planes:
+        res += (pl[:n * 3].reshape(B, 3, Cc // 8, T, 8), pl[n * 3:].reshape(T, 8))
+    return res
+
+
+def test_dds(x, lens, layers, form=16, mask_out=True, head=None, tail=None, device_id=0):
+    """A stack of fused DDSConv layers on x float32 [B, C, T]: form 16 (dds_layer16_kernel) or 32 (dds_layer_kernel); layers =
+    a list of dicts with dw_w [C, 3], dw_b, ln1_g, ln1_b, pw_w [C, C], pw_b, ln2_g, ln2_b, dil.  mask_out=False: one layer with
+    its mask off.  head = dict(cond [B, C, T], z [B, 2, T], ch, pre_w [C], pre_b [C]) (form 16; x may be None), tail =
+    dict(w [R, C], b [R] or None) (form 16).  Returns (the stack's result [B, C, T] - or tail_out [B, R, T] - and guard [T])."""
+    lens = np.ascontiguousarray(lens, np.int64)
+    src = head["cond"] if x is None and head is not None else x
+    src = np.ascontiguousarray(src, np.float32)
+    if src.ndim != 3 or lens.shape != (src.shape[0],):
+        raise SessionError(f"x must be [B, C, T] and lens [B], got {src.shape} / {lens.shape}")
+    B, Cc, T = src.shape
+    x = None if x is None else src
+    keep = []
+    arr = (_ffi.VitsTestDdsLayer * len(layers))()
+    for i, L in enumerate(layers):
+        for name, shape in (("dw_w", (Cc, 3)), ("dw_b", (Cc,)), ("ln1_g", (Cc,)), ("ln1_b", (Cc,)), ("pw_w", (Cc, Cc)),
+                            ("pw_b", (Cc,)), ("ln2_g", (Cc,)), ("ln2_b", (Cc,))):
+            a = _f32(L[name], shape, f"layers[{i}].{name}")
+            keep.append(a)
+            setattr(arr[i], name, a.ctypes.data)
+        arr[i].dil = int(L["dil"])
+    hc = hz = hw = hb = tw = tb = None
+    hch, R = 0, 0
+    if head is not None:
+        hc, hz = _f32(head["cond"], (B, Cc, T), "head.cond"), _f32(head["z"], (B, 2, T), "head.z")
+        hw, hb = _f32(head["pre_w"], (Cc,), "head.pre_w"), _f32(head["pre_b"], (Cc,), "head.pre_b")
+        hch = int(head["ch"])
+    if tail is not None:
+        tw = np.ascontiguousarray(tail["w"], np.float32)
+        if tw.ndim != 2 or tw.shape[1] != Cc:
+            raise SessionError(f"tail.w must be [R, C], got {tw.shape}")
+        R = tw.shape[0]
+        tb = None if tail.get("b") is None else _f32(tail["b"], (R,), "tail.b")
+    rows = R if tail is not None else Cc
+    out = _guarded(B * rows * T, T)
+    rc = _ffi.load().vits_test_dds(device_id, int(form), _ffi.ptr(x), B, Cc, T, _ffi.ptr(lens), len(layers), arr, int(bool(mask_out)),
+                                   _ffi.ptr(hc), _ffi.ptr(hz), hch, _ffi.ptr(hw), _ffi.ptr(hb), _ffi.ptr(tw), _ffi.ptr(tb), R,
+                                   _ffi.ptr(out))
+    _glue_check(rc, "vits_test_dds")
+    del keep
+    return out[:B * rows * T].reshape(B, rows, T), out[B * rows * T:]
+
+
+def test_cf_pre(z, ch, w, bias, cond, device_id=0):
+    """cf_pre_kernel: out = w[c] * z[b, ch, t] + bias[c] + cond[b, c, t]; z [B, 2, T], cond [B, C, T] -> (out, guard [T])"""
+    cond = np.ascontiguousarray(cond, np.float32)
+    if cond.ndim != 3:
+        raise SessionError(f"cond must be [B, C, T], got {cond.shape}")
+    B, Cc, T = cond.shape
+    z, w, bias = _f32(z, (B, 2, T), "z"), _f32(w, (Cc,), "w"), _f32(bias, (Cc,), "bias")
+    out = _guarded(B * Cc * T, T)
+    rc = _ffi.load().vits_test_cf_pre(device_id, _ffi.ptr(z), int(ch), _ffi.ptr(w), _ffi.ptr(bias), _ffi.ptr(cond), B, Cc, T, _ffi.ptr(out))
+    _glue_check(rc, "vits_test_cf_pre")
+    return out[:B * Cc * T].reshape(B, Cc, T), out[B * Cc * T:]
+
+
+def test_rqs_inverse(pr, z, lens, ch0, nb, sqrt_c, device_id=0):
+    """rqs_inverse_kernel (<10> for nb <= 10, else <16>): z float32 [B, 2, T] with channel ch0 passing through and channel
+    ch0 ^ 1 transformed by the spline of pr [B, 3 nb - 1, T] -> (z [B, 2, T], guard [T])"""
+    z = np.ascontiguousarray(z, np.float32)
+    if z.ndim != 3 or z.shape[1] != 2:
+        raise SessionError(f"z must be [B, 2, T], got {z.shape}")
+    B, _, T = z.shape
+    nb = int(nb)
+    pr = _f32(pr, (B, 3 * nb - 1, T), "pr")
+    lens = _lens_or_none(lens, B)
+    out = _guarded(B * 2 * T, T)
+    rc = _ffi.load().vits_test_rqs_inverse(device_id, _ffi.ptr(pr), _ffi.ptr(z), B, T, _ffi.ptr(lens), int(ch0), nb, float(sqrt_c),
+                                           _ffi.ptr(out))
+    _glue_check(rc, "vits_test_rqs_inverse")
+    return out[:B * 2 * T].reshape(B, 2, T), out[B * 2 * T:]
+
+
+def test_ea_logw(z, ch, m0, logs0, lens, device_id=0):
+    """ea_logw_kernel: logw = (z[b, ch, t] - m0) * exp(-logs0) * mask -> (logw [B, T], guard [T])"""
+    z = np.ascontiguousarray(z, np.float32)
+    if z.ndim != 3 or z.shape[1] != 2:
+        raise SessionError(f"z must be [B, 2, T], got {z.shape}")
+    B, _, T = z.shape
+    lens = _lens_or_none(lens, B)
+    out = _guarded(B * T, T)
+    rc = _ffi.load().vits_test_ea_logw(device_id, _ffi.ptr(z), int(ch), float(m0), float(logs0), _ffi.ptr(lens), B, T, _ffi.ptr(out))
+    _glue_check(rc, "vits_test_ea_logw")
+    return out[:B * T].reshape(B, T), out[B * T:]
