@@ -477,7 +477,7 @@ int vits_deliver(vits_handle *h, const vits_segment *segs, int n_segs, int n_str
  * index and the value: mode outside 0..2; a threshold that is not finite or negative; a negative keep_lead or keep_tail;
  * tail_samples outside [0, INT_MAX]; everything vits_deliver refuses.  A rejected call leaves the last run deliverable.
  * Not covered: the encoded stream (its chunks share one first_sample timeline, and a stream cannot know where its audio
- * ends), fades, loudness (RMS) levelling. */
+ * ends), fades.  Loudness levelling: the next section. */
 typedef struct {
     int32_t mode;          /* 0 off; 1 absolute: thr = threshold; 2 relative: thr = threshold * peak_all (one fp32 product) */
     float   threshold;     /* finite, >= 0 */
@@ -498,6 +498,79 @@ int vits_delivery_plan_trimmed(const int64_t *kept, int B, const vits_segment *s
 int vits_deliver_trimmed(vits_handle *h, const vits_segment *segs, const vits_trim *trims, int n_segs, int n_streams, int encoding,
                          void *dst, size_t dst_bytes, int64_t *stream_samples, int64_t *stream_offsets, int64_t *kept_first,
                          int64_t *kept_count);
+
+/* ---- levelled delivery: the trimmed delivery with every segment (or stream) brought to a loudness target on the device ------
+ * Peak normalisation makes every sentence equally tall, not equally loud.  The entries below are vits_deliver_trimmed with the
+ * integrated loudness of ITU-R BS.1770-4 / EBU R 128 measured on the device over each segment's kept range, turned into ONE gain
+ * per segment on the host and applied by the pack launch.  One vits_level runs parallel to each vits_segment; the text below
+ * is the specification (tests/loudness_ref.py states it a second time, in float64).
+ *
+ * For a segment on row b with kept range x[b][a .. a + c) (the trimmed delivery's; a = 0, c = n_b without trims) at the
+ * delivered sample rate fs:
+ *   K-weighting: two biquads in series, each at rest in front of sample a; coefficients in double on the host, the standard's
+ *   analogue prototypes through the bilinear transform (at 48 kHz: the table of BS.1770-4):
+ *     shelf      f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196;
+ *                K = tan(pi f0 / fs), Vh = 10^(G/20), Vb = Vh^0.4996667741545416, a0 = 1 + K/Q + K^2;
+ *                b = [(Vh + Vb K/Q + K^2)/a0, 2 (K^2 - Vh)/a0, (Vh - Vb K/Q + K^2)/a0], a = [1, 2 (K^2 - 1)/a0, (1 - K/Q + K^2)/a0]
+ *     high-pass  f0 = 38.13547087602444, Q = 0.5003270373238773; K = tan(pi f0 / fs), a0 = 1 + K/Q + K^2;
+ *                b = [1, -2, 1], a = [1, 2 (K^2 - 1)/a0, (1 - K/Q + K^2)/a0]
+ *   sub-blocks:  hop = (fs + 5) / 10 samples (integer division); sub-block k is the filtered samples [k hop, (k + 1) hop) of
+ *                the kept range, e_k the sum of their squares - an fp32 value from the device; only whole sub-blocks count:
+ *                n_sub = c / hop
+ *   blocks and gates (host, double): z_j = (e_j + e_{j+1} + e_{j+2} + e_{j+3}) / (4 hop), j = 0 .. n_sub - 4 (400 ms, 75 %
+ *                overlap); l_j = -0.691 + 10 log10 z_j; absolute gate l_j > -70; Gamma = -0.691 + 10 log10(mean z over the
+ *                absolute-gated blocks) - 10; L = -0.691 + 10 log10(mean z over the blocks with l_j > -70 and l_j > Gamma);
+ *                no block, or none that passes: L = -inf
+ *   scope:       mode 1 - the segment's own blocks; mode 2 - the blocks of all mode-2 segments of the stream pooled into one
+ *                gating computation.  In both the filters restart per row and no block straddles two rows.
+ *   gain:        peak = the sample peak of the kept range (mode 2: the max over the stream's mode-2 segments; the quantity
+ *                the delivery's normalisation uses - a SAMPLE peak, not a true peak).  L = -inf: g = 1.  Otherwise, in
+ *                double: g = 10^((target_lufs - L) / 20); g = min(g, 10^(max_gain_db / 20)); if peak_ceiling > 0 and
+ *                peak > 0: g = min(g, peak_ceiling / peak); then rounded once to fp32.
+ *   sample:      a levelled segment: v = x[b][i] * g (one fp32 product), then if (volume != 1.0f) v = v * volume, then the
+ *                clip; the encoders are unchanged.  Unlevelled segments keep the delivery's formula.
+ * So: with levels == NULL, or with every level at mode 0, bytes and layout are vits_deliver_trimmed's, bit for bit.  The
+ * layout never depends on the levels.
+ * Device side (csrc/loudness.hip.hpp): the kept range is cut into chunks of Lc samples counted from a; every chunk runs the
+ * recurrence from rest, the true states are carried through a row's chunks with the 4x4 transition over Lc samples (built in
+ * double on the host), every chunk runs again from its true state and sums y^2 per sub-block.  No floating-point atomics, a
+ * fixed order of every sum: e_k is bit-identical from call to call and depends on the row's kept samples alone.  Nothing is
+ * launched for segments at mode 0.  delivery_peak_kernel supplies the peaks; one small copy brings energies and peaks to the
+ * host, which gates, computes the gains and then enqueues the delivery's launches.
+ * Validation happens on the host before anything is enqueued or allocated; VITS_E_ARG, the message naming the segment index
+ * and the value: mode outside 0..2; a target that is not finite or outside [-70, 0]; max_gain_db not finite or outside
+ * [0, 120]; peak_ceiling not finite, negative or above 1 (0: none); a levelled segment whose normalize is not 0; mode-2
+ * segments of one stream that disagree in target, max_gain_db or ceiling; with a levelled segment, sample_rate outside
+ * [8000, 192000], or differing from the output rate when the handle has one set; everything vits_deliver_trimmed refuses.
+ * A rejected call leaves the last run deliverable.
+ * Not covered: the encoded stream (it cannot know its integrated loudness in advance; feed a gain in as its volume), true
+ * peak, momentary / short-term loudness and loudness range, fades. */
+typedef struct {
+    int32_t mode;          /* 0 off, 1 row, 2 stream */
+    float   target_lufs;   /* finite, [-70, 0] */
+    float   max_gain_db;   /* finite, [0, 120] */
+    float   peak_ceiling;  /* sample-peak ceiling of the levelled segment, (0, 1]; 0: none */
+} vits_level;
+/* pure host code: the K-weighting of a rate in [8000, 192000] - coef: shelf {b0, b1, b2, a1, a2}, high-pass {b0, b1, b2, a1,
+ * a2} - and its hop (each nullable) */
+int vits_loudness_filter(int sample_rate, double *coef, int32_t *hop);
+/* pure host code: the gates.  e: the sub-block energies of n_rows rows back to back, row r has n_sub[r] >= 0 of them; the
+ * rows' blocks are pooled into one gating computation.  L (may be -inf) and the counts of blocks, of blocks that pass the
+ * absolute gate, and of blocks that pass both (each nullable). */
+int vits_loudness_gate(const float *e, const int32_t *n_sub, int n_rows, int32_t hop, double *L, int32_t *n_blocks, int32_t *n_abs,
+                       int32_t *n_rel);
+/* pure host code: the gain rule above */
+int vits_level_gain(double L, float peak, const vits_level *level, float *gain);
+/* pure host code: vits_delivery_plan_trimmed with the levels' validation (levels nullable).  The layout is the trimmed one. */
+int vits_delivery_plan_leveled(const int64_t *kept, int B, const vits_segment *segs, const vits_trim *trims, const vits_level *levels,
+                               int n_segs, int n_streams, int encoding, int sample_rate, int64_t *stream_samples,
+                               int64_t *stream_offsets, int64_t *total_bytes);
+/* vits_deliver_trimmed with levels [n_segs] (or NULL: none) at the delivered rate sample_rate.  loudness [n_segs] (nullable)
+ * receives every levelled segment's L (mode 2: its stream's; -inf possible), NaN for a segment at mode 0; gain [n_segs]
+ * (nullable) every segment's g (mode 0: 1).  dst == NULL measures and reports, packs nothing and writes to no dst. */
+int vits_deliver_leveled(vits_handle *h, const vits_segment *segs, const vits_trim *trims, const vits_level *levels, int n_segs,
+                         int n_streams, int encoding, int sample_rate, void *dst, size_t dst_bytes, int64_t *stream_samples,
+                         int64_t *stream_offsets, int64_t *kept_first, int64_t *kept_count, double *loudness, float *gain);
 
 /* ---- encoded streaming: a chunked run's chunks post-processed, encoded and masked on the device --------------------------
  * vits_run_chunked* hands every chunk over as fp32 [B][n]; vits_deliver refuses a chunked run.  The two entries below are the
@@ -730,6 +803,18 @@ int vits_test_deliver(int device_id, const float *x, const int64_t *counts, int 
 int vits_test_deliver_trimmed(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_segment *segs,
                               const vits_trim *trims, int n_segs, int n_streams, int encoding, void *dst, size_t dst_bytes,
                               int64_t *stream_samples, int64_t *stream_offsets, int64_t *kept_first, int64_t *kept_count);
+
+/* The loudness kernels by value: x [B][S] host, row b's kept range x[b][firsts[b] .. firsts[b] + counts[b]) (within the row;
+ * what lies outside must not show), all rows in one set of launches with the pipeline's grids.  n_sub [B] receives every
+ * row's whole sub-blocks, e their energies back to back (e_cap >= their sum, else VITS_E_ARG), *chunk the compiled Lc. */
+int vits_test_loudness_blocks(int device_id, const float *x, const int64_t *counts, const int64_t *firsts, int B, int S,
+                              int sample_rate, float *e, size_t e_cap, int32_t *n_sub, int32_t *chunk);
+
+/* The levelled delivery by value: as vits_test_deliver_trimmed; everything else as vits_deliver_leveled. */
+int vits_test_deliver_leveled(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_segment *segs,
+                              const vits_trim *trims, const vits_level *levels, int n_segs, int n_streams, int encoding,
+                              int sample_rate, void *dst, size_t dst_bytes, int64_t *stream_samples, int64_t *stream_offsets,
+                              int64_t *kept_first, int64_t *kept_count, double *loudness, float *gain);
 
 /* The encoded stream's kernel by value: x [B][S] host, counts [B] the rows' valid samples (within [0, S]; what lies behind
  * must not show).  Columns [0, S) are cut into pieces of piece_samples samples (the last one shorter); each piece goes through

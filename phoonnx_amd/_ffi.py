@@ -61,6 +61,10 @@ class VitsTestDdsLayer(C.Structure):
                 ("pw_b", C.c_void_p), ("ln2_g", C.c_void_p), ("ln2_b", C.c_void_p), ("dil", C.c_int32)]
 
 
+class VitsLevel(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("target_lufs", C.c_float), ("max_gain_db", C.c_float), ("peak_ceiling", C.c_float)]
+
+
 class VitsStreamFormat(C.Structure):
     _fields_ = [("encoding", C.c_int32), ("ref_peak", C.c_void_p), ("volume", C.c_void_p)]
 
@@ -96,6 +100,8 @@ EXPORTS = [
     "vits_test_durations", "vits_test_expand_prior", "vits_test_fill_normal", "vits_test_fill_normal_rows", "vits_test_post_conv",
     "vits_delivery_plan", "vits_deliver", "vits_test_deliver",
     "vits_trim_range", "vits_delivery_plan_trimmed", "vits_deliver_trimmed", "vits_test_deliver_trimmed",
+    "vits_loudness_filter", "vits_loudness_gate", "vits_level_gain", "vits_delivery_plan_leveled", "vits_deliver_leveled",
+    "vits_test_loudness_blocks", "vits_test_deliver_leveled",
     "vits_run_chunked_enc", "vits_run_vocoder_chunked_enc", "vits_test_stream_pack",
     "vits_test_layernorm", "vits_test_dds", "vits_test_cf_pre", "vits_test_rqs_inverse", "vits_test_ea_logw",
 ]
@@ -195,6 +201,14 @@ def load():
     lib.vits_deliver_trimmed.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vp, vp, vp, vp]
     lib.vits_test_deliver_trimmed.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_size_t,
                                               vp, vp, vp, vp]
+    lib.vits_loudness_filter.argtypes = [C.c_int, vp, vp]
+    lib.vits_loudness_gate.argtypes = [vp, vp, C.c_int, C.c_int32, vp, vp, vp, vp]
+    lib.vits_level_gain.argtypes = [C.c_double, C.c_float, C.POINTER(VitsLevel), C.POINTER(C.c_float)]
+    lib.vits_delivery_plan_leveled.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, i64p]
+    lib.vits_deliver_leveled.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vp, vp, vp, vp, vp, vp]
+    lib.vits_test_loudness_blocks.argtypes = [C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vp, vp]
+    lib.vits_test_deliver_leveled.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp,
+                                              C.c_size_t, vp, vp, vp, vp, vp, vp]
     lib.vits_free_output.argtypes = [vp, C.POINTER(VitsOutput)]
     lib.vits_free_output.restype = None
     lib.vits_sync.argtypes = [vp]

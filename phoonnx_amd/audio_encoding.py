@@ -8,8 +8,13 @@ bytes.  The two G.711 forms equal CPython's audioop.lin2ulaw / lin2alaw (width 2
 
 `trim_range` and `join_trimmed` are the same for the trimmed delivery (include/vitsmi.h, "trimmed delivery"): the kept range
 of a row, and one stream of rows cut to their kept ranges with silence in front of and behind each.
+
+`loudness`, `level_gain` and `join_leveled` are the same for the levelled delivery (include/vitsmi.h, "levelled delivery"), in
+float64: the integrated loudness of ITU-R BS.1770-4 of a row, the gain that brings it to a target, and one stream of rows
+levelled, encoded and joined.
 """
 import io
+import math
 import struct
 import wave
 from dataclasses import dataclass
@@ -130,6 +135,116 @@ def join_trimmed(rows, encoding="pcm16", lead=0, tail=0, trim=None, normalize=1,
     return (np.concatenate(pieces) if pieces else silence(0, encoding)), kept
 
 
+def k_weighting(rate):
+    """The K-weighting of BS.1770 at `rate` Hz: ((b, a) of the shelf, (b, a) of the high-pass), the standard's analogue
+    prototypes through the bilinear transform (at 48 kHz: its table)."""
+    G, Q, f0 = 3.999843853973347, 0.7071752369554196, 1681.974450955533
+    K = math.tan(math.pi * f0 / rate)
+    Vh = 10.0 ** (G / 20.0)
+    Vb = Vh ** 0.4996667741545416
+    a0 = 1.0 + K / Q + K * K
+    shelf = ([(Vh + Vb * K / Q + K * K) / a0, 2.0 * (K * K - Vh) / a0, (Vh - Vb * K / Q + K * K) / a0],
+             [1.0, 2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0])
+    Q, f0 = 0.5003270373238773, 38.13547087602444
+    K = math.tan(math.pi * f0 / rate)
+    a0 = 1.0 + K / Q + K * K
+    return shelf, ([1.0, -2.0, 1.0], [1.0, 2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0])
+
+
+def _biquad(b, a, x):
+    """one biquad from rest over a list of floats (transposed direct form II, float64)"""
+    b0, b1, b2 = b
+    _, a1, a2 = a
+    z1 = z2 = 0.0
+    y = [0.0] * len(x)
+    for n, v in enumerate(x):
+        w = b0 * v + z1
+        z1 = b1 * v - a1 * w + z2
+        z2 = b2 * v - a2 * w
+        y[n] = w
+    return y
+
+
+def sub_block_energies(x, rate) -> np.ndarray:
+    """The K-weighted energies of the whole 100 ms sub-blocks of x (float64 [len(x) // hop]), hop = (rate + 5) // 10."""
+    hop = (int(rate) + 5) // 10
+    n_sub = len(x) // hop
+    if n_sub == 0:
+        return np.zeros(0, np.float64)
+    shelf, hp = k_weighting(rate)
+    y = np.array(_biquad(*hp, _biquad(*shelf, np.asarray(x, np.float64)[:n_sub * hop].tolist())), np.float64)
+    return (y * y).reshape(n_sub, hop).sum(axis=1)
+
+
+def gated_loudness(rows_e, rate) -> float:
+    """The gates of BS.1770-4 over the sub-block energies of one or several rows, pooled: 400 ms blocks at 75 % overlap within
+    each row, the absolute gate at -70 LUFS, the relative gate 10 LU below the absolute-gated mean.  -inf: no block passes."""
+    hop = (int(rate) + 5) // 10
+    z = [np.zeros(0)]
+    for e in rows_e:
+        e = np.asarray(e, np.float64)
+        if e.size >= 4:
+            z.append((e[:-3] + e[1:-2] + e[2:-1] + e[3:]) / (4.0 * hop))
+    z = np.concatenate(z)
+    with np.errstate(divide="ignore"):
+        l = -0.691 + 10.0 * np.log10(z)
+    keep = l > -70.0
+    if not keep.any():
+        return -math.inf
+    both = keep & (l > -0.691 + 10.0 * math.log10(z[keep].mean()) - 10.0)
+    return -0.691 + 10.0 * math.log10(z[both].mean()) if both.any() else -math.inf
+
+
+def loudness(x, rate) -> float:
+    """The integrated loudness of x at `rate` Hz in LUFS (ITU-R BS.1770-4, mono); -inf for less than 400 ms or silence."""
+    return gated_loudness([sub_block_energies(x, rate)], rate)
+
+
+def level_gain(loudness, peak, target_lufs, max_gain_db=30.0, peak_ceiling=0.0) -> np.float32:
+    """The gain that brings audio of integrated loudness `loudness` to target_lufs: at most max_gain_db, and with
+    peak_ceiling > 0 no more than what keeps the sample peak `peak` at or below it; 1 for a loudness of -inf."""
+    if loudness == -math.inf:
+        return np.float32(1.0)
+    g = min(10.0 ** ((float(np.float32(target_lufs)) - loudness) / 20.0), 10.0 ** (float(np.float32(max_gain_db)) / 20.0))
+    if peak_ceiling > 0 and peak > 0:
+        g = min(g, float(np.float32(peak_ceiling)) / float(peak))
+    return np.float32(g)
+
+
+def leveled(audio: np.ndarray, gain, volume: float) -> np.ndarray:
+    """The levelled delivery's sample formula in float32: one product with the gain, the volume's, the clip."""
+    return scaled(np.asarray(audio, np.float32) * np.float32(gain), None, volume)
+
+
+def level_rows(rows, rate, level):
+    """The loudness and the gain of every row (its float32 samples, already cut to what is kept) under `level`: anything with
+    the fields of vits_level - mode (1: every row by itself, 2: the rows pooled into one gating computation, one gain by the
+    largest peak), target_lufs, max_gain_db, peak_ceiling.  Returns (loudness per row, gain per row)."""
+    if int(level.mode) not in (1, 2):
+        raise ValueError(f"level mode {level.mode} outside 1..2")
+    peaks = [np.max(np.abs(v)) if len(v) else np.float32(0) for v in rows]
+    energies = [sub_block_energies(v, rate) for v in rows]
+    if int(level.mode) == 1:
+        loud = [gated_loudness([e], rate) for e in energies]
+    else:
+        loud = [gated_loudness(energies, rate)] * len(rows)
+        peaks = [max(peaks)] * len(rows) if rows else []
+    return loud, [level_gain(L, pk, level.target_lufs, level.max_gain_db, level.peak_ceiling) for L, pk in zip(loud, peaks)]
+
+
+def join_leveled(rows, rate, level, encoding="pcm16", lead=0, tail=0, trim=None, volume=1.0):
+    """ONE stream of a levelled delivery on the host: join_trimmed with every row's kept range brought to a loudness target
+    (level_rows) instead of peak-normalised.  Returns (data, [(a, c) per row], loudness per row, gain per row)."""
+    _check(encoding)
+    kept = [trim_range(r, len(r), trim) for r in rows]
+    cut = [np.asarray(r, np.float32)[a:a + c] for r, (a, c) in zip(rows, kept)]
+    loud, gains = level_rows(cut, rate, level)
+    pieces = []
+    for v, g in zip(cut, gains):
+        pieces += [silence(lead, encoding), encode(leveled(v, g, volume), encoding), silence(tail, encoding)]
+    return (np.concatenate(pieces) if pieces else silence(0, encoding)), kept, loud, gains
+
+
 @dataclass
 class EncodedAudio:
     """One stream of encoded audio: `data` holds the elements (int16 / uint8 / float32, one per sample), sentence k's audio
@@ -142,6 +257,10 @@ class EncodedAudio:
     # synthesize_encoded(..., alignments=True): per sentence, its PhonemeAlignment list with start_sample counted from the
     # beginning of `data`
     phoneme_alignments: Optional[List[List[Any]]] = None
+    # synthesize_encoded(..., loudness=): per sentence, the integrated loudness measured in front of the gain (LUFS; with
+    # loudness_scope="text" the text's, repeated; -inf below 400 ms) and the gain applied
+    loudness: Optional[List[float]] = None
+    gain: Optional[List[float]] = None
 
     def tobytes(self) -> bytes:
         return np.ascontiguousarray(self.data).tobytes()

@@ -11,6 +11,9 @@
 // A trimmed delivery (vitsmi.h, "trimmed delivery") puts delivery_trim_scan_kernel in front: the first and the last sample
 // of every row above the segment's threshold, folded with atomicMin / atomicMax - order-independent like the peaks.  The host
 // turns the bounds into kept ranges; the two kernels above then run over those, unchanged (a segment is src and n).
+//
+// A levelled delivery (vitsmi.h, "levelled delivery") measures in front of the pack (loudness.hip.hpp, and the peak kernel
+// under the scan's grid); the pack kernel multiplies a levelled segment's samples by the gain in its record.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -110,12 +113,22 @@ __global__ __launch_bounds__(kDeliveryThreads) void delivery_trim_scan_kernel(co
 // samples): delivery_peak_kernel 0.299 ms under launch_delivery's grid (a sample per lane, up to 256 workgroups a row),
 // 0.032 ms under this one; this scan 0.045 ms.
 constexpr int kTrimSpan = 32;
+inline int trim_scan_gx(int max_n) {
+    const int gx = (max_n + kDeliveryThreads * kTrimSpan - 1) / (kDeliveryThreads * kTrimSpan);
+    return gx > 64 ? 64 : (gx < 1 ? 1 : gx);
+}
 inline hipError_t launch_trim_scan(const float *x, const DeliverySeg *d_scan, int G, int max_n, bool any_rel, unsigned *d_peak_all, int *d_bounds,
                                    hipStream_t st) {
-    int gx = (max_n + kDeliveryThreads * kTrimSpan - 1) / (kDeliveryThreads * kTrimSpan);
-    gx = gx > 64 ? 64 : (gx < 1 ? 1 : gx);
+    const int gx = trim_scan_gx(max_n);
     if (any_rel) delivery_peak_kernel<<<dim3(gx, G), kDeliveryThreads, 0, st>>>(x, d_scan, d_peak_all);
     delivery_trim_scan_kernel<<<dim3(gx, G), kDeliveryThreads, 0, st>>>(x, d_scan, d_peak_all, d_bounds);
+    return hipGetLastError();
+}
+
+// the sample peaks of a levelled delivery on `st`: d_table [G] the plan's table with `peak` = the slot of every levelled
+// segment (-1: not measured), d_peak zeroed.  The scan's grid: the measurement above.
+inline hipError_t launch_level_peaks(const float *x, const DeliverySeg *d_table, int G, int max_n, unsigned *d_peak, hipStream_t st) {
+    delivery_peak_kernel<<<dim3(trim_scan_gx(max_n), G), kDeliveryThreads, 0, st>>>(x, d_table, d_peak);
     return hipGetLastError();
 }
 
@@ -156,7 +169,9 @@ __global__ __launch_bounds__(kDeliveryThreads) void delivery_pack_kernel(const f
                 loaded = g;
             }
             const float peak = s.peak >= 0 ? __uint_as_float(peak_bits[s.peak]) : 1.f;
-            o = delivery_encode<ENC>(delivery_value(x[s.src + (e - s.start)], s.peak >= 0, peak, s.volume));
+            float v = x[s.src + (e - s.start)];
+            if (s.peak == kDeliveryLevelled) v = v * __int_as_float(s.pad);  // (one fp32 product, in front of the volume's)
+            o = delivery_encode<ENC>(delivery_value(v, s.peak >= 0, peak, s.volume));
         }
         lt[i * kDeliveryThreads + threadIdx.x] = o;
     }

@@ -9,6 +9,9 @@
 //
 // A trimmed delivery (vitsmi.h, "trimmed delivery") is the same plan over a sub-range of every row: `counts` are then the
 // kept counts, `first` the kept ranges' first samples, and the trims bring the silence behind each segment.
+//
+// A levelled delivery (vitsmi.h, "levelled delivery") changes nothing in the layout: once the gains are known, level_apply
+// marks the levelled segments of a finished plan and puts each one's gain into its record.
 #pragma once
 #include <climits>
 #include <cmath>
@@ -38,10 +41,11 @@ struct DeliverySeg {
     int64_t start;  // first packed element of this segment (prefix sum of n)
     int64_t src;    // element offset of the segment's first sample in the waveform: row * pitch (+ the kept range's start)
     int32_t n;      // valid (trimmed: kept) samples of the row
-    int32_t peak;   // peak slot to normalise by (row: [0, B); stream: B + stream), or -1
+    int32_t peak;   // peak slot to normalise by (row: [0, B); stream: B + stream), -1, or kDeliveryLevelled
     float volume;
-    int32_t pad;
+    int32_t pad;    // a levelled segment: the bits of its gain (the trim scan's table: the trim's mode)
 };
+constexpr int32_t kDeliveryLevelled = -2;  // `peak` of a levelled segment: v = x * gain, no normalisation
 
 struct DeliveryCopy {
     int64_t packed_off, dst_off, bytes;
@@ -73,6 +77,65 @@ inline std::string trim_fault(const vits_trim &t) {
     else if (t.tail_samples < 0 || t.tail_samples > INT_MAX)
         std::snprintf(buf, sizeof buf, "tail_samples %lld outside [0, %d]", (long long)t.tail_samples, INT_MAX);
     return buf;
+}
+
+// the rates a levelled delivery admits (the smallest one bounds the sub-blocks of a row: workspace.hpp, carve_level)
+constexpr int kLevelMinRate = 8000, kLevelMaxRate = 192000;
+
+// "" or what is wrong with one level, naming the value (the caller names the segment)
+inline std::string level_fault(const vits_level &l) {
+    char buf[160];
+    buf[0] = 0;
+    if (l.mode < 0 || l.mode > 2) std::snprintf(buf, sizeof buf, "level mode %d outside 0..2", l.mode);
+    else if (!std::isfinite(l.target_lufs) || l.target_lufs < -70.f || l.target_lufs > 0.f)
+        std::snprintf(buf, sizeof buf, "target_lufs %g is not finite and within [-70, 0]", (double)l.target_lufs);
+    else if (!std::isfinite(l.max_gain_db) || l.max_gain_db < 0.f || l.max_gain_db > 120.f)
+        std::snprintf(buf, sizeof buf, "max_gain_db %g is not finite and within [0, 120]", (double)l.max_gain_db);
+    else if (!std::isfinite(l.peak_ceiling) || l.peak_ceiling < 0.f || l.peak_ceiling > 1.f)
+        std::snprintf(buf, sizeof buf, "peak_ceiling %g is not finite and within [0, 1]", (double)l.peak_ceiling);
+    return buf;
+}
+
+// "" or what is wrong with the levels of a plan that delivery_plan has accepted: each level by itself, a levelled segment
+// that also normalises, the mode-2 segments of a stream that disagree, the rate.  levels == nullptr: "".
+inline std::string level_plan_fault(const vits_segment *segs, const vits_level *levels, int n_segs, int n_streams, int sample_rate) {
+    if (!levels) return "";
+    char buf[240];
+    bool any = false;
+    std::vector<int> lead(n_streams, -1);  // a stream's first mode-2 segment
+    for (int g = 0; g < n_segs; g++) {
+        const vits_level &l = levels[g];
+        const std::string e = level_fault(l);
+        if (!e.empty()) {
+            std::snprintf(buf, sizeof buf, "segment %d: %s", g, e.c_str());
+            return buf;
+        }
+        if (l.mode == 0) continue;
+        any = true;
+        if (segs[g].normalize != 0) {
+            std::snprintf(buf, sizeof buf, "segment %d: normalize %d with level mode %d: a levelled segment is not normalised", g,
+                          segs[g].normalize, l.mode);
+            return buf;
+        }
+        if (l.mode != 2) continue;
+        const int f = lead[segs[g].stream];
+        if (f < 0) {
+            lead[segs[g].stream] = g;
+            continue;
+        }
+        const vits_level &o = levels[f];
+        if (l.target_lufs != o.target_lufs || l.max_gain_db != o.max_gain_db || l.peak_ceiling != o.peak_ceiling) {
+            std::snprintf(buf, sizeof buf, "segment %d: stream level (%g LUFS, %g dB, ceiling %g) differs from segment %d's (%g, %g, %g)", g,
+                          (double)l.target_lufs, (double)l.max_gain_db, (double)l.peak_ceiling, f, (double)o.target_lufs,
+                          (double)o.max_gain_db, (double)o.peak_ceiling);
+            return buf;
+        }
+    }
+    if (any && (sample_rate < kLevelMinRate || sample_rate > kLevelMaxRate)) {
+        std::snprintf(buf, sizeof buf, "sample_rate %d outside [%d, %d]", sample_rate, kLevelMinRate, kLevelMaxRate);
+        return buf;
+    }
+    return "";
 }
 
 // the kept range [a, a + c) of a row of n valid samples whose first / last active samples are f / l (f > l: none active)
@@ -211,6 +274,16 @@ inline std::string delivery_plan(const int64_t *counts, int B, int64_t pitch, co
     p.packed_elems = packed;
     p.total_bytes = dst * w;
     return "";
+}
+
+// a finished plan with the gains of its levelled segments: gain [n_segs] in the caller's order
+inline void level_apply(DeliveryPlan &p, const vits_level *levels, const float *gain) {
+    for (size_t k = 0; k < p.segs.size() && levels; k++) {
+        const int g = p.order[k];
+        if (levels[g].mode == 0) continue;
+        p.segs[k].peak = kDeliveryLevelled;
+        std::memcpy(&p.segs[k].pad, &gain[g], sizeof(float));
+    }
 }
 
 // the silence regions of dst: the encoding of sample value 0

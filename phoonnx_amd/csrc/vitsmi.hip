@@ -26,6 +26,7 @@
 #include "conv_sx_small.hip.hpp"
 #include "delivery.hip.hpp"
 #include "kernels.hip.hpp"
+#include "loudness.hip.hpp"
 #include "model.hpp"
 #include "resample.hip.hpp"
 #include "stream_pack.hip.hpp"
@@ -2608,10 +2609,11 @@ int vits_reserve(vits_handle *h, int B, int T, int F) {
         // vits_last_pcm16's int16 waveform and per-utterance peaks (the larger of the two uses)
         const size_t io_in = carved_bytes([&](Carver &cv) { carve_inputs(cv, m, B, T, T, Fp); });
         const size_t io_pcm = carved_bytes([&](Carver &cv) { carve_pcm16(cv, B, F * m.hop); });
-        // ... or vits_deliver's, with vits_deliver_trimmed's slots behind them
+        // ... or vits_deliver's, with vits_deliver_trimmed's slots and vits_deliver_leveled's buffers behind them
         const size_t io_dlv = carved_bytes([&](Carver &cv) {
             carve_delivery(cv, B, F * m.hop);
             carve_trim(cv, B);
+            carve_level(cv, B, F * m.hop);
         });
         // ... or an encoded stream's chunk buffer: every chunk_frames <= F, i.e. chunks of up to F * hop samples
         const size_t io_sp = carved_bytes([&](Carver &cv) { carve_stream_pack(cv, B, (int64_t)F * m.hop); });
@@ -2627,10 +2629,12 @@ int vits_reserve(vits_handle *h, int B, int T, int F) {
                 carve_stream_pack(cv, B, so);
             });
             io = io_rs > io ? io_rs : io;
-            // (a trimmed delivery's slots lie behind the resampled result too: in the place of an encoded stream's buffers)
+            // (a trimmed delivery's slots and a levelled one's buffers lie behind the resampled result too: in the place of
+            // an encoded stream's buffers)
             const size_t io_rt = carved_bytes([&](Carver &cv) {
                 carve_resample(cv, B, (int)so, (int)h->rs.plan.K);
                 carve_trim(cv, B);
+                carve_level(cv, B, (int)so);
             });
             io = io_rt > io ? io_rt : io;
         }
@@ -3094,6 +3098,54 @@ int vits_delivery_plan_trimmed(const int64_t *kept, int B, const vits_segment *s
     return VITS_OK;
 }
 
+int vits_loudness_filter(int sample_rate, double *coef, int32_t *hop) {
+    if (sample_rate < kLevelMinRate || sample_rate > kLevelMaxRate)
+        return fail(nullptr, VITS_E_ARG, "sample_rate %d outside [%d, %d]", sample_rate, kLevelMinRate, kLevelMaxRate);
+    if (coef) loudness_filter(sample_rate, coef);
+    if (hop) *hop = loudness_hop(sample_rate);
+    return VITS_OK;
+}
+
+int vits_loudness_gate(const float *e, const int32_t *n_sub, int n_rows, int32_t hop, double *L, int32_t *n_blocks, int32_t *n_abs,
+                       int32_t *n_rel) {
+    if (n_rows < 0 || (n_rows > 0 && !n_sub) || hop < 1) return fail(nullptr, VITS_E_ARG, "loudness gate: n_rows = %d, hop = %d", n_rows, hop);
+    size_t total = 0;
+    for (int r = 0; r < n_rows; r++) {
+        if (n_sub[r] < 0) return fail(nullptr, VITS_E_ARG, "loudness gate: n_sub[%d] = %d is negative", r, n_sub[r]);
+        total += (size_t)n_sub[r];
+    }
+    if (total > 0 && !e) return fail(nullptr, VITS_E_ARG, "null argument");
+    const LoudGate g = loudness_gate(e, n_sub, n_rows, hop);
+    if (L) *L = g.L;
+    if (n_blocks) *n_blocks = g.blocks;
+    if (n_abs) *n_abs = g.abs_pass;
+    if (n_rel) *n_rel = g.rel_pass;
+    return VITS_OK;
+}
+
+int vits_level_gain(double L, float peak, const vits_level *level, float *gain) {
+    if (!level || !gain) return fail(nullptr, VITS_E_ARG, "null argument");
+    const std::string e = level_fault(*level);
+    if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
+    if (std::isnan(L) || L == std::numeric_limits<double>::infinity() || !(peak >= 0.f))
+        return fail(nullptr, VITS_E_ARG, "loudness %g / peak %g: a loudness is a number or -inf, a peak is >= 0", L, (double)peak);
+    *gain = level_gain(L, peak, *level);
+    return VITS_OK;
+}
+
+int vits_delivery_plan_leveled(const int64_t *kept, int B, const vits_segment *segs, const vits_trim *trims, const vits_level *levels,
+                               int n_segs, int n_streams, int encoding, int sample_rate, int64_t *stream_samples,
+                               int64_t *stream_offsets, int64_t *total_bytes) {
+    DeliveryPlan p;
+    std::string e = delivery_plan(kept, B, 0, segs, n_segs, n_streams, encoding, p, trims);
+    if (e.empty()) e = level_plan_fault(segs, levels, n_segs, n_streams, sample_rate);
+    if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
+    for (int j = 0; j < n_streams && stream_samples; j++) stream_samples[j] = p.stream_samples[j];
+    for (int j = 0; j <= n_streams && stream_offsets; j++) stream_offsets[j] = p.stream_offsets[j];
+    if (total_bytes) *total_bytes = p.total_bytes;
+    return VITS_OK;
+}
+
 // Everything a delivery puts on the stream: segment table up, peaks cleared, the launches, the copies into dst; then the
 // silence, on the host.  The caller synchronises.  db: carve_delivery's buffers for a waveform of at least the plan's rows.
 static hipError_t delivery_enqueue(const float *d_x, const DeliveryPlan &p, const DeliveryBufs &db, int B, hipStream_t st, void *dst) {
@@ -3217,9 +3269,109 @@ static void trim_report(const vits_segment *segs, int n_segs, const std::vector<
     }
 }
 
-int vits_deliver_trimmed(vits_handle *h, const vits_segment *segs, const vits_trim *trims, int n_segs, int n_streams, int encoding,
-                         void *dst, size_t dst_bytes, int64_t *stream_samples, int64_t *stream_offsets, int64_t *kept_first,
-                         int64_t *kept_count) {
+// ---- levelled delivery (vitsmi.h, "levelled delivery"): the measurement between the kept ranges and the delivery
+
+static bool any_level(const vits_level *levels, int n_segs) {
+    for (int g = 0; g < n_segs && levels; g++)
+        if (levels[g].mode != 0) return true;
+    return false;
+}
+
+// The loudness and peak launches over the plan p (over the kept ranges), the copy of energies and peaks, the wait, then
+// gates and gains on the host: loud / gain [n_segs] in the caller's order (mode 0: NaN / 1).  Waits whatever happened: the
+// tables are the pageable sources of copies that may be in flight.
+static hipError_t level_measure(const float *d_x, const DeliveryPlan &p, const vits_segment *segs, const vits_level *levels, int n_segs,
+                                int n_streams, int sample_rate, const DeliveryBufs &db, const LevelBufs &lb, hipStream_t st,
+                                std::vector<double> &loud, std::vector<float> &gain) {
+    loud.assign(n_segs, std::numeric_limits<double>::quiet_NaN());
+    gain.assign(n_segs, 1.0f);
+    if (!any_level(levels, n_segs)) return hipSuccess;
+    const LoudCoef k = loudness_coef(sample_rate);
+    const int G = (int)p.segs.size();
+    std::vector<DeliverySeg> table(p.segs);  // the peak launch's: slot k for a levelled segment
+    std::vector<LoudSeg> ls;                 // the loudness launches': the levelled segments only
+    std::vector<int> ls_k;                   // ... and which of the plan's each one is
+    std::vector<int32_t> n_sub(G, 0);
+    int64_t chunks = 0, subs = 0;
+    int max_n = 0;
+    for (int kk = 0; kk < G; kk++) {
+        table[kk].peak = -1;
+        if (levels[p.order[kk]].mode == 0) continue;
+        table[kk].peak = kk;
+        n_sub[kk] = p.segs[kk].n / k.hop;
+        LoudSeg s{};
+        s.src = p.segs[kk].src;
+        s.chunk0 = chunks;
+        s.sub0 = subs;
+        s.n = n_sub[kk] * k.hop;
+        chunks += ((int64_t)s.n + kLoudChunk - 1) / kLoudChunk;
+        subs += n_sub[kk];
+        max_n = s.n > max_n ? s.n : max_n;
+        ls.push_back(s);
+        ls_k.push_back(kk);
+    }
+    if ((size_t)chunks > lb.n_chunks || (size_t)subs > lb.n_subs || (size_t)G > lb.n_peaks) return hipErrorInvalidValue;  // (cannot happen: carve_level)
+    std::vector<unsigned> result(lb.n_peaks + (size_t)subs, 0u);
+    hipError_t e = hipSuccess;
+    if (p.max_n > 0) {  // (segments without samples: peak 0, no sub-blocks)
+        e = hipMemcpyAsync(db.segs, table.data(), (size_t)G * sizeof(DeliverySeg), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemsetAsync(lb.result, 0, lb.n_peaks * sizeof(unsigned), st);
+        if (e == hipSuccess) e = launch_level_peaks(d_x, db.segs, G, p.max_n, lb.result, st);
+        if (e == hipSuccess && max_n > 0) {
+            e = hipMemcpyAsync(lb.segs, ls.data(), ls.size() * sizeof(LoudSeg), hipMemcpyHostToDevice, st);
+            if (e == hipSuccess) e = launch_loudness(d_x, lb.segs, (int)ls.size(), max_n, k, lb.fin, lb.init, lb.part, lb.e(), st);
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(result.data(), lb.result, result.size() * sizeof(unsigned), hipMemcpyDeviceToHost, st);
+    }
+    const hipError_t done = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = done;
+    if (e != hipSuccess) return e;
+    const float *peaks = reinterpret_cast<const float *>(result.data());
+    const float *en = peaks + lb.n_peaks;
+    // mode 1: a segment by itself
+    for (size_t i = 0; i < ls.size(); i++) {
+        const int kk = ls_k[i], g = p.order[kk];
+        if (levels[g].mode != 1) continue;
+        loud[g] = loudness_gate(en + ls[i].sub0, &n_sub[kk], 1, k.hop).L;
+        gain[g] = level_gain(loud[g], peaks[kk], levels[g]);
+    }
+    // mode 2: the stream's mode-2 segments pooled (the plan's order within a stream is the caller's)
+    for (int j = 0; j < n_streams; j++) {
+        std::vector<float> pool;
+        std::vector<int32_t> pool_n;
+        float peak = 0.f;
+        int lead = -1;
+        for (size_t i = 0; i < ls.size(); i++) {
+            const int kk = ls_k[i], g = p.order[kk];
+            if (levels[g].mode != 2 || segs[g].stream != j) continue;
+            lead = lead < 0 ? g : lead;
+            pool.insert(pool.end(), en + ls[i].sub0, en + ls[i].sub0 + n_sub[kk]);
+            pool_n.push_back(n_sub[kk]);
+            peak = fmaxf(peak, peaks[kk]);
+        }
+        if (lead < 0) continue;
+        const double L = loudness_gate(pool.data(), pool_n.data(), (int)pool_n.size(), k.hop).L;
+        const float gn = level_gain(L, peak, levels[lead]);
+        for (int g = 0; g < n_segs; g++)
+            if (levels[g].mode == 2 && segs[g].stream == j) {
+                loud[g] = L;
+                gain[g] = gn;
+            }
+    }
+    return hipSuccess;
+}
+
+static void level_report(int n_segs, const std::vector<double> &loud, const std::vector<float> &gn, double *loudness, float *gain) {
+    for (int g = 0; g < n_segs; g++) {
+        if (loudness) loudness[g] = loud[g];
+        if (gain) gain[g] = gn[g];
+    }
+}
+
+// vits_deliver_trimmed and vits_deliver_leveled: levels == nullptr is the former exactly
+static int deliver_kept(vits_handle *h, const vits_segment *segs, const vits_trim *trims, const vits_level *levels, int n_segs, int n_streams,
+                        int encoding, int sample_rate, void *dst, size_t dst_bytes, int64_t *stream_samples, int64_t *stream_offsets,
+                        int64_t *kept_first, int64_t *kept_count, double *loudness, float *gain) {
     if (int rc = check_dev(h)) return rc;
     std::lock_guard<std::mutex> lk(h->mu);
     const int B = h->B, S = h->S;
@@ -3230,24 +3382,36 @@ int vits_deliver_trimmed(vits_handle *h, const vits_segment *segs, const vits_tr
     if (int rc = delivery_counts(h, counts)) return rc;
     DeliveryPlan p0;  // over the whole rows: the validation, and the table the scan reads
     std::string e = delivery_plan(counts.data(), B, S, segs, n_segs, n_streams, encoding, p0, trims);
+    if (e.empty()) e = level_plan_fault(segs, levels, n_segs, n_streams, sample_rate);
     if (!e.empty()) return fail(h, VITS_E_ARG, "%s", e.c_str());
+    const bool lev = any_level(levels, n_segs);
+    if (lev && h->rs.plan.on() && sample_rate != h->rs.plan.fo)
+        return fail(h, VITS_E_ARG, "sample_rate %d differs from the output rate %d", sample_rate, (int)h->rs.plan.fo);
     DeliveryBufs db{};
     TrimBufs tb{};
+    LevelBufs lb{};
     if (rs) {
         // (the run's own walk ends with carve_resample, or with an encoded stream's buffers behind it; the trim slots behind
         // carve_resample are at most 12 B + 512 bytes more than the former.  Growing the slab here would drop the waveform that
         // lives in it - the check below - and does not happen: slab_reserve allocates 1 MiB above every request, and
-        // vits_reserve counts this walk.)
+        // vits_reserve counts this walk.  A levelled delivery's buffers - some 0.05 bytes a sample - fit into the quarter a
+        // growing slab adds to every request; where a slab does not hold them the call is refused and the run stays
+        // deliverable.)
         const int K = h->rs_run_K;
-        if (int rc = slab_carve(h, h->io, "staging", [&](Carver &cv) {
-                db = carve_resample(cv, B, S, K).dlv;
-                tb = carve_trim(cv, B);
-            }))
-            return rc;
+        auto walk = [&](Carver &cv) {
+            db = carve_resample(cv, B, S, K).dlv;
+            tb = carve_trim(cv, B);
+            if (lev) lb = carve_level(cv, B, S);
+        };
+        if (lev && carved_bytes(walk) > h->io.cap)
+            return fail(h, VITS_E_NOMEM, "a levelled delivery of this run needs %zu bytes of staging, %zu are there: vits_reserve covers it",
+                        carved_bytes(walk), h->io.cap);
+        if (int rc = slab_carve(h, h->io, "staging", walk)) return rc;
         if (!h->d_out) return fail(h, VITS_E_ARG, "no completed run to deliver");
     } else if (int rc = slab_carve(h, h->io, "staging", [&](Carver &cv) {
                    db = carve_delivery(cv, B, S);
                    tb = carve_trim(cv, B);
+                   if (lev) lb = carve_level(cv, B, S);
                }))
         return rc;
     hipStream_t st = h->stream;
@@ -3261,6 +3425,11 @@ int vits_deliver_trimmed(vits_handle *h, const vits_segment *segs, const vits_tr
     if (!e.empty()) return fail(h, VITS_E_ARG, "%s", e.c_str());
     if (dst && dst_bytes < (size_t)p.total_bytes)
         return fail(h, VITS_E_ARG, "delivery buffer too small: %zu bytes, %lld needed", dst_bytes, (long long)p.total_bytes);
+    std::vector<double> loud;
+    std::vector<float> gn;
+    err = level_measure(h->d_out, p, segs, levels, n_segs, n_streams, sample_rate, db, lb, st, loud, gn);
+    if (err != hipSuccess) return fail(h, VITS_E_DEVICE, "loudness measurement failed: %s", hipGetErrorString(err));
+    level_apply(p, levels, gn.data());
     if (dst) {
         err = delivery_enqueue(h->d_out, p, db, B, st, dst);
         if (err == hipSuccess) err = hipStreamSynchronize(st);
@@ -3269,7 +3438,22 @@ int vits_deliver_trimmed(vits_handle *h, const vits_segment *segs, const vits_tr
     }
     delivery_report(p, stream_samples, stream_offsets);
     trim_report(segs, n_segs, first, kept, kept_first, kept_count);
+    level_report(n_segs, loud, gn, loudness, gain);
     return VITS_OK;
+}
+
+int vits_deliver_trimmed(vits_handle *h, const vits_segment *segs, const vits_trim *trims, int n_segs, int n_streams, int encoding,
+                         void *dst, size_t dst_bytes, int64_t *stream_samples, int64_t *stream_offsets, int64_t *kept_first,
+                         int64_t *kept_count) {
+    return deliver_kept(h, segs, trims, nullptr, n_segs, n_streams, encoding, 0, dst, dst_bytes, stream_samples, stream_offsets, kept_first,
+                        kept_count, nullptr, nullptr);
+}
+
+int vits_deliver_leveled(vits_handle *h, const vits_segment *segs, const vits_trim *trims, const vits_level *levels, int n_segs,
+                         int n_streams, int encoding, int sample_rate, void *dst, size_t dst_bytes, int64_t *stream_samples,
+                         int64_t *stream_offsets, int64_t *kept_first, int64_t *kept_count, double *loudness, float *gain) {
+    return deliver_kept(h, segs, trims, levels, n_segs, n_streams, encoding, sample_rate, dst, dst_bytes, stream_samples, stream_offsets,
+                        kept_first, kept_count, loudness, gain);
 }
 
 // vocoder-only entry points: z (host, [B, inter, F], already masked) -> device, speaker bias; then either the whole
@@ -4170,14 +4354,30 @@ int vits_test_deliver(int device_id, const float *x, const int64_t *counts, int 
     return VITS_OK;
 }
 
-int vits_test_deliver_trimmed(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_segment *segs,
-                              const vits_trim *trims, int n_segs, int n_streams, int encoding, void *dst, size_t dst_bytes,
-                              int64_t *stream_samples, int64_t *stream_offsets, int64_t *kept_first, int64_t *kept_count) {
+// a test hook's LevelBufs: carve_level's buffers as allocations of their own
+static LevelBufs test_level_bufs(DevBufs &D, int B, int S) {
+    LevelBufs lb{};
+    lb.n_peaks = (size_t)B;
+    lb.n_chunks = (size_t)B * ((size_t)S / kLoudChunk + 1);
+    lb.n_subs = (size_t)B * ((size_t)S / kLoudMinHop);
+    lb.segs = D.alloc<LoudSeg>((size_t)B);
+    lb.fin = D.alloc<LoudState>(lb.n_chunks);
+    lb.init = D.alloc<LoudState>(lb.n_chunks);
+    lb.part = D.alloc<float>(lb.n_chunks * kLoudParts);
+    lb.result = D.alloc<unsigned>(lb.n_peaks + lb.n_subs);
+    return lb;
+}
+
+static int test_deliver_kept(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_segment *segs,
+                             const vits_trim *trims, const vits_level *levels, int n_segs, int n_streams, int encoding, int sample_rate,
+                             void *dst, size_t dst_bytes, int64_t *stream_samples, int64_t *stream_offsets, int64_t *kept_first,
+                             int64_t *kept_count, double *loudness, float *gain) {
     if (!x || !counts || B <= 0 || S <= 0 || (int64_t)B * S > (int64_t)1 << 40) return fail(nullptr, VITS_E_ARG, "bad delivery test arguments");
     for (int b = 0; b < B; b++)
         if (counts[b] < 0 || counts[b] > S) return fail(nullptr, VITS_E_ARG, "counts[%d] = %lld outside [0, %d]", b, (long long)counts[b], S);
     DeliveryPlan p0;
     std::string e = delivery_plan(counts, B, S, segs, n_segs, n_streams, encoding, p0, trims);
+    if (e.empty()) e = level_plan_fault(segs, levels, n_segs, n_streams, sample_rate);
     if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
     if (int rc = test_dev(device_id)) return rc;
     DevBufs D;
@@ -4189,6 +4389,8 @@ int vits_test_deliver_trimmed(int device_id, const float *x, const int64_t *coun
     TrimBufs tb{};
     tb.bounds = D.alloc<int32_t>(2 * (size_t)B);
     tb.peak_all = D.alloc<unsigned>((size_t)B);
+    LevelBufs lb{};
+    if (any_level(levels, n_segs)) lb = test_level_bufs(D, B, S);
     TCHECK(D.err);
     std::vector<int64_t> first, kept;
     TCHECK(trim_scan(dx, p0, segs, trims, counts, B, db, tb, nullptr, first, kept));
@@ -4197,6 +4399,10 @@ int vits_test_deliver_trimmed(int device_id, const float *x, const int64_t *coun
     if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
     if (dst && dst_bytes < (size_t)p.total_bytes)
         return fail(nullptr, VITS_E_ARG, "delivery buffer too small: %zu bytes, %lld needed", dst_bytes, (long long)p.total_bytes);
+    std::vector<double> loud;
+    std::vector<float> gn;
+    TCHECK(level_measure(dx, p, segs, levels, n_segs, n_streams, sample_rate, db, lb, nullptr, loud, gn));
+    level_apply(p, levels, gn.data());
     if (dst) {
         const hipError_t enq = delivery_enqueue(dx, p, db, B, nullptr, dst);
         const hipError_t done = hipDeviceSynchronize();
@@ -4205,6 +4411,59 @@ int vits_test_deliver_trimmed(int device_id, const float *x, const int64_t *coun
     }
     delivery_report(p, stream_samples, stream_offsets);
     trim_report(segs, n_segs, first, kept, kept_first, kept_count);
+    level_report(n_segs, loud, gn, loudness, gain);
+    return VITS_OK;
+}
+
+int vits_test_deliver_trimmed(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_segment *segs,
+                              const vits_trim *trims, int n_segs, int n_streams, int encoding, void *dst, size_t dst_bytes,
+                              int64_t *stream_samples, int64_t *stream_offsets, int64_t *kept_first, int64_t *kept_count) {
+    return test_deliver_kept(device_id, x, counts, B, S, segs, trims, nullptr, n_segs, n_streams, encoding, 0, dst, dst_bytes, stream_samples,
+                             stream_offsets, kept_first, kept_count, nullptr, nullptr);
+}
+
+int vits_test_deliver_leveled(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_segment *segs,
+                              const vits_trim *trims, const vits_level *levels, int n_segs, int n_streams, int encoding,
+                              int sample_rate, void *dst, size_t dst_bytes, int64_t *stream_samples, int64_t *stream_offsets,
+                              int64_t *kept_first, int64_t *kept_count, double *loudness, float *gain) {
+    return test_deliver_kept(device_id, x, counts, B, S, segs, trims, levels, n_segs, n_streams, encoding, sample_rate, dst, dst_bytes,
+                             stream_samples, stream_offsets, kept_first, kept_count, loudness, gain);
+}
+
+int vits_test_loudness_blocks(int device_id, const float *x, const int64_t *counts, const int64_t *firsts, int B, int S,
+                              int sample_rate, float *e, size_t e_cap, int32_t *n_sub, int32_t *chunk) {
+    if (chunk) *chunk = kLoudChunk;
+    if (!x || !counts || !firsts || !n_sub || B <= 0 || S <= 0 || (int64_t)B * S > (int64_t)1 << 40)
+        return fail(nullptr, VITS_E_ARG, "bad loudness test arguments");
+    if (sample_rate < kLevelMinRate || sample_rate > kLevelMaxRate)
+        return fail(nullptr, VITS_E_ARG, "sample_rate %d outside [%d, %d]", sample_rate, kLevelMinRate, kLevelMaxRate);
+    const LoudCoef k = loudness_coef(sample_rate);
+    std::vector<LoudSeg> ls(B);
+    int64_t chunks = 0, subs = 0;
+    int max_n = 0;
+    for (int b = 0; b < B; b++) {
+        if (firsts[b] < 0 || counts[b] < 0 || firsts[b] + counts[b] > S)
+            return fail(nullptr, VITS_E_ARG, "row %d: kept range [%lld, +%lld) outside [0, %d]", b, (long long)firsts[b], (long long)counts[b], S);
+        n_sub[b] = (int32_t)(counts[b] / k.hop);
+        ls[b] = LoudSeg{(int64_t)b * S + firsts[b], chunks, subs, n_sub[b] * k.hop, 0};
+        chunks += ((int64_t)ls[b].n + kLoudChunk - 1) / kLoudChunk;
+        subs += n_sub[b];
+        max_n = ls[b].n > max_n ? ls[b].n : max_n;
+    }
+    if ((size_t)subs > e_cap || (subs > 0 && !e)) return fail(nullptr, VITS_E_ARG, "energy buffer too small: %zu < %lld", e_cap, (long long)subs);
+    if (int rc = test_dev(device_id)) return rc;
+    DevBufs D;
+    float *dx = D.up(x, (size_t)B * S);
+    LevelBufs lb = test_level_bufs(D, B, S);
+    TCHECK(D.err);
+    if (max_n > 0) {
+        TCHECK(hipMemcpy(lb.segs, ls.data(), ls.size() * sizeof(LoudSeg), hipMemcpyHostToDevice));
+        const hipError_t enq = launch_loudness(dx, lb.segs, B, max_n, k, lb.fin, lb.init, lb.part, lb.e(), nullptr);
+        const hipError_t done = hipDeviceSynchronize();
+        TCHECK(enq);
+        TCHECK(done);
+        TCHECK(download(e, lb.e(), (size_t)subs));
+    }
     return VITS_OK;
 }
 

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "delivery.hpp"
+#include "loudness.hpp"
 #include "model.hpp"
 #include "slab.hpp"
 
@@ -267,6 +268,33 @@ inline TrimBufs carve_trim(Carver &cv, int B) {
     t.bounds = cv.take<int32_t>(2 * (size_t)B);
     t.peak_all = cv.take<unsigned>(B);
     return t;
+}
+
+// vits_deliver_leveled on top of both (a walk of its own, behind carve_trim's): the table of the levelled segments, the
+// states behind and in front of every chunk, the chunks' partial sums, and ONE result buffer the host fetches in one copy -
+// the segments' sample peaks [B] and behind them the sub-block energies.  Sized by the request: every row is in at most one
+// segment, a row of n <= S samples has at most S / kLoudChunk + 1 chunks and, at the smallest admitted rate's hop, at most
+// S / kLoudMinHop sub-blocks.
+struct LevelBufs {
+    LoudSeg *segs;
+    LoudState *fin, *init;
+    float *part;
+    unsigned *result;  // [B] peaks (float bits), then the energies (float)
+    float *e() const { return reinterpret_cast<float *>(result) + n_peaks; }
+    size_t n_peaks, n_chunks, n_subs;
+};
+
+inline LevelBufs carve_level(Carver &cv, int B, int S) {
+    LevelBufs l{};
+    l.n_peaks = (size_t)B;
+    l.n_chunks = (size_t)B * ((size_t)S / kLoudChunk + 1);
+    l.n_subs = (size_t)B * ((size_t)S / kLoudMinHop);
+    l.segs = cv.take<LoudSeg>(B);
+    l.fin = cv.take<LoudState>(l.n_chunks);
+    l.init = cv.take<LoudState>(l.n_chunks);
+    l.part = cv.take<float>(l.n_chunks * kLoudParts);
+    l.result = cv.take<unsigned>(l.n_peaks + l.n_subs);
+    return l;
 }
 
 // With an output rate set (vits_set_output_rate), the staging slab holds the run's RESULT once its inputs are consumed:

@@ -264,6 +264,17 @@ class Trim:
     tail_samples: int = 0
 
 
+@dataclass
+class Level:
+    """The level of one segment (vitsmi.h, vits_level): mode 0 off, 1 - the segment is brought to `target_lufs` (integrated
+    loudness, ITU-R BS.1770-4) by itself, 2 - together with the stream's other mode-2 segments, by one gain; the gain is at
+    most max_gain_db, and with peak_ceiling > 0 the levelled SAMPLE peak stays at or below it."""
+    mode: int = 0
+    target_lufs: float = -23.0
+    max_gain_db: float = 30.0
+    peak_ceiling: float = 0.0
+
+
 def _encoding(encoding):
     try:
         return _ffi.ENCODINGS[encoding]
@@ -299,6 +310,22 @@ def _trims(trims, n):
     return arr
 
 
+def _levels(levels, n):
+    """None, one Level or one per segment -> ctypes array of n vits_level (None: no levels)"""
+    if levels is None:
+        return None
+    levels = [levels] * n if isinstance(levels, Level) else list(levels)
+    if len(levels) != n:
+        raise SessionError(f"levels must be one Level or one per segment ({n}), got {len(levels)}")
+    arr = (_ffi.VitsLevel * max(n, 1))()
+    for i, l in enumerate(levels):
+        try:
+            arr[i] = _ffi.VitsLevel(int(l.mode), float(l.target_lufs), float(l.max_gain_db), float(l.peak_ceiling))
+        except (AttributeError, TypeError, ValueError, OverflowError) as e:
+            raise SessionError(f"segment {i}: level: {e}") from None
+    return arr
+
+
 def _n_streams(segments, n_streams):
     if n_streams is not None:
         return int(n_streams)
@@ -330,6 +357,61 @@ def delivery_plan(counts, segments, n_streams=None, encoding="pcm16", trims=None
     if rc != 0:
         raise SessionError(f"vits_delivery_plan failed [{rc}]: {_ffi.last_error(None)}")
     return {"stream_samples": samples, "stream_offsets": offsets, "total_bytes": int(total.value)}
+
+
+def level_plan(counts, segments, levels, sample_rate, n_streams=None, encoding="pcm16", trims=None, out=None):
+    """delivery_plan(..., kept=counts) with the levels' validation (vits_delivery_plan_leveled: pure host code).  The layout
+    never depends on the levels.  out: (stream_samples, stream_offsets) arrays to fill; a refusal raises SessionError and
+    leaves them untouched."""
+    counts = np.ascontiguousarray(counts, np.int64)
+    if counts.ndim != 1:
+        raise SessionError(f"counts must be int64 [B], got {counts.shape}")
+    segments = list(segments)
+    code, _ = _encoding(encoding)
+    J = _n_streams(segments, n_streams)
+    arr, n = _segments(segments)
+    samples, offsets = out if out is not None else (np.zeros(max(J, 0), np.int64), np.zeros(max(J, 0) + 1, np.int64))
+    total = C.c_int64()
+    rc = _ffi.load().vits_delivery_plan_leveled(_ffi.ptr(counts), counts.shape[0], arr, _trims(trims, n), _levels(levels, n), n, J,
+                                                code, int(sample_rate), _ffi.ptr(samples), _ffi.ptr(offsets), C.byref(total))
+    if rc != 0:
+        raise SessionError(f"vits_delivery_plan_leveled failed [{rc}]: {_ffi.last_error(None)}")
+    return {"stream_samples": samples, "stream_offsets": offsets, "total_bytes": int(total.value)}
+
+
+def loudness_filter(sample_rate):
+    """The K-weighting of a rate (vits_loudness_filter: pure host code) -> (coef float64 [10]: shelf b0 b1 b2 a1 a2, high-pass
+    b0 b1 b2 a1 a2; hop)"""
+    coef, hop = np.zeros(10, np.float64), C.c_int32()
+    rc = _ffi.load().vits_loudness_filter(int(sample_rate), _ffi.ptr(coef), C.byref(hop))
+    if rc != 0:
+        raise SessionError(f"vits_loudness_filter failed [{rc}]: {_ffi.last_error(None)}")
+    return coef, hop.value
+
+
+def loudness_gate(rows_e, hop):
+    """The gates of BS.1770-4 over the sub-block energies of one or several rows, pooled (vits_loudness_gate: pure host code)
+    -> (L, blocks, blocks past the absolute gate, blocks past both)"""
+    rows_e = [np.ascontiguousarray(e, np.float32).ravel() for e in rows_e]
+    n_sub = np.array([e.size for e in rows_e], np.int32)
+    e = np.concatenate(rows_e) if rows_e else np.zeros(0, np.float32)
+    L, nb, na, nr = C.c_double(), C.c_int32(), C.c_int32(), C.c_int32()
+    rc = _ffi.load().vits_loudness_gate(_ffi.ptr(e), _ffi.ptr(n_sub), len(rows_e), int(hop), C.byref(L), C.byref(nb), C.byref(na),
+                                        C.byref(nr))
+    if rc != 0:
+        raise SessionError(f"vits_loudness_gate failed [{rc}]: {_ffi.last_error(None)}")
+    return L.value, nb.value, na.value, nr.value
+
+
+def level_gain(loudness, peak, level):
+    """The gain of a segment of integrated loudness `loudness` (LUFS, -inf allowed) and sample peak `peak` under `level`
+    (vits_level_gain: pure host code) -> float32"""
+    g = C.c_float()
+    lv = _levels(level, 1)
+    rc = _ffi.load().vits_level_gain(float(loudness), float(peak), lv, C.byref(g))
+    if rc != 0:
+        raise SessionError(f"vits_level_gain failed [{rc}]: {_ffi.last_error(None)}")
+    return np.float32(g.value)
 
 
 @dataclass
@@ -1084,7 +1166,13 @@ class MiSession:
             S = int(ylen.max()) * self.hparam("hop")
             return self.last_pcm16(normalize, volume, shape=(B, S)), ylen
 
-    def deliver(self, segments, n_streams=None, encoding="pcm16", trims=None, return_kept=False):
+    @property
+    def delivered_rate(self) -> int:
+        """The sample rate results are delivered at: the output rate, or the voice's own."""
+        return int(self.output_rate or self.input_rate or self.meta("sample_rate") or 22050)
+
+    def deliver(self, segments, n_streams=None, encoding="pcm16", trims=None, return_kept=False, levels=None, sample_rate=None,
+                return_levels=False):
         """The last run's audio, post-processed, encoded and laid out per request on the device (vitsmi.h, "delivery"):
         segments - Segment objects, each row of the run in at most one; encoding "pcm16" / "ulaw" / "alaw" / "f32".  Returns
         one NumPy array per stream (int16 / uint8 / float32), all views into ONE buffer in stream order - page-locked memory
@@ -1094,12 +1182,36 @@ class MiSession:
         and followed by its tail of silence.  return_kept=True: (streams, kept_first int64 [G], kept_count int64 [G]).
         The layout of a trimmed delivery depends on the data, so its ONE buffer is sized before the scan, by the untrimmed
         layout plus the tails (one call and one scan instead of two): the views returned keep a buffer alive that is larger
-        than what was delivered by what was trimmed - copy them if that matters."""
+        than what was delivered by what was trimmed - copy them if that matters.
+        levels - one Level or one per segment (vitsmi.h, "levelled delivery"): the integrated loudness of every levelled
+        segment's kept range is measured on the device and the segment delivered at its target; sample_rate - the rate the
+        audio is at (default: delivered_rate; refused where it differs from a set output rate).  return_levels=True appends
+        (loudness float64 [G] - NaN for an unlevelled segment, -inf below 400 ms or the gates -, gain float32 [G])."""
         segments = list(segments)
         code, dtype = _encoding(encoding)
         J = _n_streams(segments, n_streams)
         arr, n = _segments(segments)
         samples, offsets = np.zeros(max(J, 0), np.int64), np.zeros(max(J, 0) + 1, np.int64)
+        if levels is not None or return_levels:
+            tarr, larr = _trims(trims, n), _levels(levels, n)
+            rate = self.delivered_rate if sample_rate is None else int(sample_rate)
+            first, count = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
+            loud, gain = np.full(max(n, 1), np.nan, np.float64), np.ones(max(n, 1), np.float32)
+            width = np.dtype(dtype).itemsize
+            with self._locked():
+                rc = self._lib.vits_deliver(self._h, arr, n, J, code, None, 0, _ffi.ptr(samples), _ffi.ptr(offsets))
+                if rc != 0:
+                    self._raise("vits_deliver", rc)
+                cap = int(offsets[-1]) + width * sum(max(int(tarr[i].tail_samples), 0) for i in range(n if tarr else 0))
+                buf = _POOL.array((cap,), np.uint8) if self.pinned_results and cap else np.empty(cap, np.uint8)
+                rc = self._lib.vits_deliver_leveled(self._h, arr, tarr, larr, n, J, code, rate, _ffi.ptr(buf), cap, _ffi.ptr(samples),
+                                                    _ffi.ptr(offsets), _ffi.ptr(first), _ffi.ptr(count), _ffi.ptr(loud),
+                                                    _ffi.ptr(gain))
+                if rc != 0:
+                    self._raise("vits_deliver_leveled", rc)
+            streams = [buf[int(offsets[j]):int(offsets[j + 1])].view(dtype) for j in range(J)]
+            res = (streams,) + ((first[:n], count[:n]) if return_kept else ()) + ((loud[:n], gain[:n]) if return_levels else ())
+            return res if len(res) > 1 else streams
         if trims is not None or return_kept:
             tarr = _trims(trims, n)
             first, count = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
@@ -1147,12 +1259,13 @@ class MiSession:
 
     def synthesize_delivered(self, ids, lens, scales, sid=None, *, segments=None, n_streams=None, encoding="pcm16",
                              normalize=True, volume=1.0, seeds=None, durations=None, token_rate=None, noise_dp=None,
-                             noise_z=None, return_durations=False, trim=None):
+                             noise_z=None, return_durations=False, trim=None, levels=None):
         """One batched run and its delivery under one hold of the session lock: what leaves the GPU is the encoded audio
         of the plan and nothing else - the fp32 waveform is never copied to the host.  segments=None: one stream per row,
         with `normalize` / `volume` as scalars or [B] arrays (row b's own).  Everything in front of the delivery is
         synthesize_batch's (scales [3] or [B, 3], seeds, durations, token_rate, injected noise, the bf16x6 fallback).
-        trim - one Trim or one per segment: deliver(..., trims=trim).
+        trim - one Trim or one per segment: deliver(..., trims=trim).  levels - one Level or one per segment:
+        deliver(..., levels=levels); the result then holds "loudness" (float64 [G]) and "gain" (float32 [G]) too.
         Returns {"streams": [array per stream], "stream_samples": int64 [J], "y_lengths": int64 [B], "sample_lengths":
         int64 [B] (each row's valid samples at the delivered rate), "kept_first" / "kept_count": int64 [G] (what each
         segment delivers of its row: all of it without a trim)[, "durations"]}."""
@@ -1175,7 +1288,11 @@ class MiSession:
                 ylen = self.last_y_lengths()
                 dur = self.last_durations() if return_durations else None
                 counts = self.last_sample_counts()
-                if trim is None:
+                loud = gain = None
+                if levels is not None:
+                    streams, kept_first, kept_count, loud, gain = self.deliver(segments, n_streams, encoding, trims=trim,
+                                                                               return_kept=True, levels=levels, return_levels=True)
+                elif trim is None:
                     streams = self.deliver(segments, n_streams, encoding)
                     kept_first = np.zeros(len(segments), np.int64)
                     kept_count = np.array([counts[int(g.row)] for g in segments], np.int64)
@@ -1186,9 +1303,11 @@ class MiSession:
                 return self.synthesize_delivered(ids, lens, scales, sid, segments=segments, n_streams=n_streams,
                                                  encoding=encoding, seeds=seeds, durations=durations, token_rate=token_rate,
                                                  noise_dp=noise_dp, noise_z=noise_z, return_durations=return_durations,
-                                                 trim=trim)
+                                                 trim=trim, levels=levels)
         res = {"streams": streams, "stream_samples": np.array([a.size for a in streams], np.int64), "y_lengths": ylen,
                "sample_lengths": counts, "kept_first": kept_first, "kept_count": kept_count}
+        if levels is not None:
+            res["loudness"], res["gain"] = loud, gain
         if return_durations:
             res["durations"] = dur
         return res
@@ -1812,6 +1931,58 @@ def test_deliver_trimmed(x, counts, segments, trims=None, n_streams=None, encodi
         raise SessionError(f"vits_test_deliver_trimmed failed [{rc}]: {_ffi.last_error(None)}")
     streams = None if layout_only else [dst[int(offsets[j]):int(offsets[j + 1])].view(dtype) for j in range(J)]
     return {"streams": streams, "stream_samples": samples, "stream_offsets": offsets, "kept_first": first[:n], "kept_count": count[:n]}
+
+
+def test_deliver_leveled(x, counts, segments, levels, sample_rate, trims=None, n_streams=None, encoding="pcm16", device_id=0,
+                         layout_only=False):
+    """vits_test_deliver_leveled: test_deliver_trimmed with levels (one Level, one per segment, or None) at sample_rate; the
+    result holds "loudness" (float64 [G]) and "gain" (float32 [G]) too."""
+    x = np.ascontiguousarray(x, np.float32)
+    counts = np.ascontiguousarray(counts, np.int64)
+    B, S = x.shape
+    segments = list(segments)
+    code, dtype = _encoding(encoding)
+    J = _n_streams(segments, n_streams)
+    arr, n = _segments(segments)
+    tarr, larr = _trims(trims, n), _levels(levels, n)
+    dst = None if layout_only else np.empty(delivery_plan(counts, segments, J, encoding, trims=trims)["total_bytes"], np.uint8)
+    samples, offsets = np.zeros(max(J, 0), np.int64), np.zeros(max(J, 0) + 1, np.int64)
+    first, count = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
+    loud, gain = np.full(max(n, 1), np.nan, np.float64), np.ones(max(n, 1), np.float32)
+    rc = _ffi.load().vits_test_deliver_leveled(device_id, _ffi.ptr(x), _ffi.ptr(counts), B, S, arr, tarr, larr, n, J, code,
+                                               int(sample_rate), None if layout_only else _ffi.ptr(dst),
+                                               0 if layout_only else dst.nbytes, _ffi.ptr(samples), _ffi.ptr(offsets),
+                                               _ffi.ptr(first), _ffi.ptr(count), _ffi.ptr(loud), _ffi.ptr(gain))
+    if rc != 0:
+        raise SessionError(f"vits_test_deliver_leveled failed [{rc}]: {_ffi.last_error(None)}")
+    streams = None if layout_only else [dst[int(offsets[j]):int(offsets[j + 1])].view(dtype) for j in range(J)]
+    return {"streams": streams, "stream_samples": samples, "stream_offsets": offsets, "kept_first": first[:n], "kept_count": count[:n],
+            "loudness": loud[:n], "gain": gain[:n]}
+
+
+def test_loudness_blocks(x, counts, sample_rate, firsts=None, device_id=0):
+    """vits_test_loudness_blocks: x [B, S] float32, row b's kept range x[b, firsts[b] : firsts[b] + counts[b]] through the
+    loudness kernels in one set of launches -> (one float32 array of sub-block energies per row, the compiled chunk Lc)"""
+    x = np.ascontiguousarray(x, np.float32)
+    counts = np.ascontiguousarray(counts, np.int64)
+    B, S = x.shape
+    firsts = np.zeros(B, np.int64) if firsts is None else np.ascontiguousarray(firsts, np.int64)
+    hop = (int(sample_rate) + 5) // 10
+    e = np.full(int(np.sum(np.maximum(counts, 0) // max(hop, 1))) + 1, np.nan, np.float32)
+    n_sub, chunk = np.zeros(B, np.int32), C.c_int32()
+    rc = _ffi.load().vits_test_loudness_blocks(device_id, _ffi.ptr(x), _ffi.ptr(counts), _ffi.ptr(firsts), B, S, int(sample_rate),
+                                               _ffi.ptr(e), e.size, _ffi.ptr(n_sub), C.byref(chunk))
+    if rc != 0:
+        raise SessionError(f"vits_test_loudness_blocks failed [{rc}]: {_ffi.last_error(None)}")
+    ends = np.cumsum(n_sub)
+    return [e[int(b - n):int(b)].copy() for b, n in zip(ends, n_sub)], chunk.value
+
+
+def loudness_chunk():
+    """the compiled Lc of the loudness kernels (no device needed: the hook reports it before it looks at its arguments)"""
+    chunk = C.c_int32()
+    _ffi.load().vits_test_loudness_blocks(0, None, None, None, 0, 0, 0, None, 0, None, C.byref(chunk))
+    return chunk.value
 
 
 def _glue_check(rc, name):

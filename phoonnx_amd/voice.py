@@ -482,6 +482,26 @@ class TTSVoice:
         return Trim(2, thr, 0, 0, tail)
 
     @staticmethod
+    def _level(loudness, loudness_scope: str, peak_ceiling: float, max_gain_db: float, configs):
+        """loudness / loudness_scope / peak_ceiling / max_gain_db of the encoded entries -> a session.Level, or None when
+        loudness is None.  Levelling replaces peak normalisation: a config with normalize_audio=True is refused."""
+        from .session import Level
+        if loudness_scope not in ("sentence", "text"):
+            raise ValueError(f"loudness_scope must be 'sentence' or 'text' (got {loudness_scope!r})")
+        if loudness is None:
+            return None
+        target = float(loudness)
+        if not (np.isfinite(target) and -70.0 <= target <= 0.0):
+            raise ValueError(f"loudness must be a target in LUFS within [-70, 0] (got {loudness})")
+        if not (np.isfinite(max_gain_db) and 0.0 <= max_gain_db <= 120.0):
+            raise ValueError(f"max_gain_db must be within [0, 120] (got {max_gain_db})")
+        if not (np.isfinite(peak_ceiling) and 0.0 <= peak_ceiling <= 1.0):
+            raise ValueError(f"peak_ceiling must be within [0, 1], 0 for none (got {peak_ceiling})")
+        if any(c.normalize_audio for c in configs):
+            raise ValueError("loudness levelling replaces peak normalisation: pass a SynthesisConfig with normalize_audio=False")
+        return Level(1 if loudness_scope == "sentence" else 2, target, float(max_gain_db), float(peak_ceiling))
+
+    @staticmethod
     def _cut_alignments(al, a: int, c: int):
         """A sentence's alignments after its audio was cut to [a, a + c): every phoneme's [start, start + num) shifted by -a
         and clamped to [0, c] - num_samples still sum to c, a phoneme that was trimmed away keeps 0 samples."""
@@ -493,7 +513,8 @@ class TTSVoice:
 
     def synthesize_encoded(self, text: str, syn_config: Optional[SynthesisConfig] = None, encoding: str = "pcm16",
                            sentence_silence: float = 0.0, normalize_scope: str = "sentence",
-                           alignments: bool = False, trim_silence=None, trailing_silence: float = 0.0):
+                           alignments: bool = False, trim_silence=None, trailing_silence: float = 0.0, loudness=None,
+                           loudness_scope: str = "sentence", peak_ceiling: float = 0.0, max_gain_db: float = 30.0):
         """Extension: the whole text as ONE stream of encoded audio ("pcm16", "ulaw", "alaw", "f32"; audio_encoding).  All
         sentences render in one batch; with a session that delivers (MiSession.synthesize_delivered) post-processing,
         encoding and the packing happen on the device and only the encoded audio crosses the bus; any other session
@@ -507,6 +528,13 @@ class TTSVoice:
         and trailing_silence seconds of silence follow every sentence.  Peaks are then those of what is kept,
         sentence_samples the kept lengths, and the alignments are cut to the kept ranges (they still sum to
         sentence_samples; a phoneme that was trimmed away has num_samples == 0).
+        loudness (None, or a target in LUFS) brings what is kept of every sentence (loudness_scope "sentence") or of the text
+        as a whole ("text": one gain, relative levels survive) to that integrated loudness (ITU-R BS.1770-4; vitsmi.h,
+        "levelled delivery") instead of peak-normalising it - the config must say normalize_audio=False.  The gain is at most
+        max_gain_db; peak_ceiling > 0 keeps the levelled sample peak (not the true peak) at or below it.  A sentence shorter
+        than 400 ms has no integrated loudness and keeps gain 1.  Measured on the device with a session that delivers, by
+        audio_encoding.join_leveled otherwise (float64: the gains agree to meter accuracy, not bit for bit).  The result's
+        `loudness` and `gain` hold what was measured and applied per sentence.
         Returns an audio_encoding.EncodedAudio."""
         from . import audio_encoding as ae
         from .sharding import pad_batch
@@ -516,8 +544,9 @@ class TTSVoice:
             raise ValueError(f"normalize_scope must be 'sentence' or 'text' (got {normalize_scope!r})")
         lead = self._lead_samples(sentence_silence)
         trim = self._trim(trim_silence, trailing_silence)
+        level = self._level(loudness, loudness_scope, peak_ceiling, max_gain_db, [cfg])
         tail = trim.tail_samples if trim is not None else 0
-        kept = None
+        kept = loud = gains = None
         want_dur = alignments and hasattr(self.session, "last_durations") and hasattr(self.session, "synthesize_batch")
         groups = self._sentence_groups(text, cfg) if want_dur else None
         all_ids = [[i for _, ids in g for i in ids] for g in groups] if want_dur else self._sentence_ids(text, cfg)
@@ -536,12 +565,16 @@ class TTSVoice:
             norm = 0 if not cfg.normalize_audio else (2 if normalize_scope == "text" else 1)
             segs = [Segment(b, 0, lead, norm, float(cfg.volume)) for b in range(len(all_ids))]
             more = {} if trim is None else {"trim": trim}
+            if level is not None:
+                more["levels"] = level
             out = self.session.synthesize_delivered(ids, lens, self._scales(cfg), sid, segments=segs, n_streams=1,
                                                     encoding=encoding, return_durations=want_dur, **more)
             data = out["streams"][0]
             counts = [int(n) for n in out["sample_lengths"]]
             if trim is not None:
                 kept = [(int(a), int(c)) for a, c in zip(out["kept_first"], out["kept_count"])]
+            if level is not None:
+                loud, gains = [float(v) for v in out["loudness"]], [float(v) for v in out["gain"]]
             if want_dur:
                 durs, frames = out["durations"], [int(f) for f in out["y_lengths"]]
         else:
@@ -552,7 +585,12 @@ class TTSVoice:
                 audios = [self.phoneme_ids_to_audio(ids, cfg) for ids in all_ids]
             counts = [len(a) for a in audios]
             norm = 0 if not cfg.normalize_audio else (2 if normalize_scope == "text" else 1)
-            data, cut = ae.join_trimmed([np.atleast_1d(a) for a in audios], encoding, lead, tail, trim, norm, cfg.volume)
+            if level is not None:
+                data, cut, loud, gains = ae.join_leveled([np.atleast_1d(a) for a in audios], self.sample_rate, level, encoding, lead,
+                                                         tail, trim, cfg.volume)
+                gains = [float(g) for g in gains]
+            else:
+                data, cut = ae.join_trimmed([np.atleast_1d(a) for a in audios], encoding, lead, tail, trim, norm, cfg.volume)
             kept = cut if trim is not None else None
         if kept is not None:
             counts = [c for _, c in kept]
@@ -572,7 +610,7 @@ class TTSVoice:
                 for a in al:
                     a.start_sample += starts[b]
                 aligned.append(al)
-        return ae.EncodedAudio(data, encoding, self.sample_rate, starts, counts, aligned)
+        return ae.EncodedAudio(data, encoding, self.sample_rate, starts, counts, aligned, loud, gains)
 
     def stream_encoded(self, text: str, syn_config: Optional[SynthesisConfig] = None, encoding: str = "pcm16",
                        chunk_frames: int = 64, sentence_silence: float = 0.0, ref_peak=None):
@@ -667,7 +705,8 @@ class TTSVoice:
     def synthesize_requests_encoded(self, requests: Sequence[Tuple[str, Optional[SynthesisConfig]]],
                                     seeds: Optional[Sequence[int]] = None, max_batch: int = 32, encoding: str = "pcm16",
                                     sentence_silence: float = 0.0, alignments: bool = False, trim_silence=None,
-                                    trailing_silence: float = 0.0):
+                                    trailing_silence: float = 0.0, loudness=None, loudness_scope: str = "sentence",
+                                    peak_ceiling: float = 0.0, max_gain_db: float = 30.0):
         """Extension: synthesize_requests with every request's audio returned as one stream of encoded audio
         (audio_encoding.EncodedAudio; the pause of synthesize_encoded in front of each sentence).  The batching is
         synthesize_requests': sentences sorted by length, max_batch at a time, each with its request's settings and seed.
@@ -676,14 +715,20 @@ class TTSVoice:
         sentences may render in different runs (for the same reason each sentence is normalised by its own peak).  Any other
         session: the host encoder over synthesize_requests' chunks - the same bytes.  trim_silence / trailing_silence as in
         synthesize_encoded: every sentence cut to its kept range (normalised by the peak of what is kept) and followed by
-        its trailing silence."""
+        its trailing silence.  loudness / loudness_scope / peak_ceiling / max_gain_db as in synthesize_encoded, per request
+        ("text": the request's sentences pooled); every request's config must say normalize_audio=False.  With scope
+        "sentence" a session that delivers measures and levels on the device.  With scope "text" a request's sentences may
+        render in different runs, so the device delivers them cut but unlevelled as float32 and the host levels them
+        (audio_encoding.level_rows)."""
         from . import audio_encoding as ae
         ae._check(encoding)
         lead = self._lead_samples(sentence_silence)
         trim = self._trim(trim_silence, trailing_silence)
+        level = self._level(loudness, loudness_scope, peak_ceiling, max_gain_db,
+                            [cfg if cfg is not None else SynthesisConfig() for _, cfg in requests])
         tail = trim.tail_samples if trim is not None else 0
 
-        def join(pieces, aligns, kept=None):
+        def join(pieces, aligns, kept=None, loud=None, gains=None):
             starts, pos = [], 0
             for p in pieces:
                 starts.append(pos + lead)
@@ -697,10 +742,27 @@ class TTSVoice:
                         self._cut_alignments(al or [], *kept[k])
                     for a in al or []:
                         a.start_sample += st
-            return ae.EncodedAudio(data, encoding, self.sample_rate, starts, [len(p) for p in pieces], aligns)
+            return ae.EncodedAudio(data, encoding, self.sample_rate, starts, [len(p) for p in pieces], aligns,
+                                   None if loud is None else [float(v) for v in loud], None if gains is None else [float(g) for g in gains])
+
+        def level_on_host(rows, volume):
+            """a request's kept rows (float32, unlevelled) -> (encoded pieces, loudness, gains)"""
+            loud, gains = ae.level_rows(rows, self.sample_rate, level)
+            return [ae.encode(ae.leveled(v, g, volume), encoding) for v, g in zip(rows, gains)], loud, gains
 
         if not hasattr(self.session, "synthesize_delivered"):
             want_al = lambda cs: alignments and all(c.phoneme_alignments is not None for c in cs)
+            if level is not None:
+                chunks = self.synthesize_requests(requests, seeds=seeds, max_batch=max_batch, alignments=alignments, postprocess=False)
+                result = []
+                for (_, cfg), cs in zip(requests, chunks):
+                    cfg = cfg if cfg is not None else SynthesisConfig()
+                    kept = [ae.trim_range(c.audio_float_array, len(c.audio_float_array), trim) for c in cs]
+                    rows = [np.asarray(c.audio_float_array, np.float32)[a:a + n] for c, (a, n) in zip(cs, kept)]
+                    pieces, loud, gains = level_on_host(rows, cfg.volume)
+                    result.append(join(pieces, [c.phoneme_alignments for c in cs] if want_al(cs) else None,
+                                       kept if trim is not None else None, loud, gains))
+                return result
             if trim is None:
                 chunks = self.synthesize_requests(requests, seeds=seeds, max_batch=max_batch, alignments=alignments)
                 return [join([ae.encode(c.audio_float_array, encoding) for c in cs],
@@ -740,7 +802,7 @@ class TTSVoice:
                     rows.append((r, k, [i for _, ids in g for i in ids]))
             else:
                 rows.extend((r, k, ids) for k, ids in enumerate(self._sentence_ids(text, cfg)))
-        piece, aligned, kept_of = {}, {}, {}
+        piece, aligned, kept_of, level_of = {}, {}, {}, {}
         hop = self.session.hparam("hop")
         order = sorted(range(len(rows)), key=lambda i: len(rows[i][2]))  # (stable: equal lengths keep request order)
         for c0 in range(0, len(order), max_batch):
@@ -749,13 +811,20 @@ class TTSVoice:
             scales = np.stack([self._scales(cfgs[r]) for r, _, _ in run])
             sid = np.asarray([cfgs[r].speaker_id or 0 for r, _, _ in run], np.int64) if "sid" in expected else None
             row_seeds = None if seeds is None else np.asarray([sentence_seed(seeds[r], k) for r, k, _ in run], np.uint64)
-            segs = [Segment(b, b, 0, 1 if cfgs[r].normalize_audio else 0, float(cfgs[r].volume)) for b, (r, _, _) in enumerate(run)]
+            host_level = level is not None and level.mode == 2
+            segs = [Segment(b, b, 0, 1 if cfgs[r].normalize_audio else 0, 1.0 if host_level else float(cfgs[r].volume))
+                    for b, (r, _, _) in enumerate(run)]
             # (the tail is joined on the host like the pause: the device delivers each sentence's kept range alone)
             more = {} if trim is None else {"trim": dataclasses.replace(trim, tail_samples=0)}
-            out = self.session.synthesize_delivered(ids, lens, scales, sid, segments=segs, n_streams=len(run), encoding=encoding,
-                                                    seeds=row_seeds, return_durations=want_dur, **more)
+            if level is not None and not host_level:
+                more["levels"] = level
+            out = self.session.synthesize_delivered(ids, lens, scales, sid, segments=segs, n_streams=len(run),
+                                                    encoding="f32" if host_level else encoding, seeds=row_seeds,
+                                                    return_durations=want_dur, **more)
             for b, (r, k, _) in enumerate(run):
                 piece[r, k] = out["streams"][b]
+                if level is not None and not host_level:
+                    level_of[r, k] = (float(out["loudness"][b]), float(out["gain"][b]))
                 if trim is not None:
                     kept_of[r, k] = (int(out["kept_first"][b]), int(out["kept_count"][b]))
                 if want_dur:
@@ -764,8 +833,16 @@ class TTSVoice:
         per_request = [[] for _ in requests]
         for r, k, _ in rows:  # (rows are in request, then sentence order)
             per_request[r].append((r, k))
-        return [join([piece[key] for key in keys], [aligned[key] for key in keys] if want_dur else None,
-                     [kept_of[key] for key in keys] if trim is not None else None) for keys in per_request]
+        result = []
+        for r, keys in enumerate(per_request):
+            pieces, loud, gains = [piece[key] for key in keys], None, None
+            if level is not None and level.mode == 2:
+                pieces, loud, gains = level_on_host(pieces, cfgs[r].volume)
+            elif level is not None:
+                loud, gains = [level_of[key][0] for key in keys], [level_of[key][1] for key in keys]
+            result.append(join(pieces, [aligned[key] for key in keys] if want_dur else None,
+                               [kept_of[key] for key in keys] if trim is not None else None, loud, gains))
+        return result
 
     def synthesize_wav(self, text: str, wav_file: wave.Wave_write, syn_config: Optional[SynthesisConfig] = None,
                        set_wav_format: bool = True, batch_sentences: bool = False, device_pcm16: bool = False) -> None:
