@@ -477,7 +477,7 @@ int vits_deliver(vits_handle *h, const vits_segment *segs, int n_segs, int n_str
  * index and the value: mode outside 0..2; a threshold that is not finite or negative; a negative keep_lead or keep_tail;
  * tail_samples outside [0, INT_MAX]; everything vits_deliver refuses.  A rejected call leaves the last run deliverable.
  * Not covered: the encoded stream (its chunks share one first_sample timeline, and a stream cannot know where its audio
- * ends), fades.  Loudness levelling: the next section. */
+ * ends).  Loudness levelling: the next section; fades: the section "shaped delivery" behind it. */
 typedef struct {
     int32_t mode;          /* 0 off; 1 absolute: thr = threshold; 2 relative: thr = threshold * peak_all (one fp32 product) */
     float   threshold;     /* finite, >= 0 */
@@ -544,7 +544,7 @@ int vits_deliver_trimmed(vits_handle *h, const vits_segment *segs, const vits_tr
  * [8000, 192000], or differing from the output rate when the handle has one set; everything vits_deliver_trimmed refuses.
  * A rejected call leaves the last run deliverable.
  * Not covered: the encoded stream (it cannot know its integrated loudness in advance; feed a gain in as its volume), true
- * peak, momentary / short-term loudness and loudness range, fades. */
+ * peak, momentary / short-term loudness and loudness range.  Fades: the next section, "shaped delivery". */
 typedef struct {
     int32_t mode;          /* 0 off, 1 row, 2 stream */
     float   target_lufs;   /* finite, [-70, 0] */
@@ -571,6 +571,77 @@ int vits_delivery_plan_leveled(const int64_t *kept, int B, const vits_segment *s
 int vits_deliver_leveled(vits_handle *h, const vits_segment *segs, const vits_trim *trims, const vits_level *levels, int n_segs,
                          int n_streams, int encoding, int sample_rate, void *dst, size_t dst_bytes, int64_t *stream_samples,
                          int64_t *stream_offsets, int64_t *kept_first, int64_t *kept_count, double *loudness, float *gain);
+
+/* ---- shaped delivery: the levelled delivery with a time-varying volume - fades and per-token gain - applied on the device ------
+ * A trimmed segment starts and ends at whatever value the waveform has keep_lead / keep_tail samples away from the threshold
+ * crossing: next to the digital silence of a lead, tail or pause that is a step, and through G.711 a click.  And volume can
+ * be steered per sentence only (vits_segment.volume), not per word.  Both are one operation, a time-varying `volume`: the
+ * entries below are vits_deliver_leveled with a multiplier per sample, computed by the pack launch.  One vits_shape runs
+ * parallel to each vits_segment, and all breakpoints of a call live in one array; the text below is the specification
+ * (tests/shape_ref.py states it a second time, in NumPy float32), and it is made so that every byte can be checked exactly.
+ *
+ * vits_env_point.pos is a sample index of the ROW at the delivered rate, counted from the row's start and not from the kept
+ * range; it lies in [0, INT_MAX].  vits_env_point.gain is 0, or lies in [2^-20, 64].  fade_in is the number of samples of the
+ * kept range that ramp up from 0, fade_out the number that ramp down to 0.
+ *
+ * For a segment on row b with kept range x[b][a .. a + c) (the trimmed delivery's; a = 0, c = n_b without trims) and points
+ * (p_k, g_k), k < m, p strictly ascending:
+ *   slopes (host, fp32):  s_k = (g_{k+1} - g_k) / (float)(p_{k+1} - p_k): one fp32 subtraction, one int-to-float conversion,
+ *                one correctly rounded fp32 division
+ *   envelope at row sample i:  m == 0: e = 1.0f;  i <= p_0: e = g_0;  i >= p_{m-1}: e = g_{m-1};  otherwise, with k the
+ *                largest index such that p_k <= i:  e = g_k + s_k * (float)(i - p_k) - the product rounded to fp32, then the
+ *                sum rounded to fp32; NOT a fused multiply-add
+ *   fades, j = i - a in [0, c):
+ *                w_in  = 1.0f if fade_in == 0 or j >= fade_in, else curve((float)j / (float)fade_in)
+ *                w_out = 1.0f if fade_out == 0 or c - 1 - j >= fade_out, else curve((float)(c - 1 - j) / (float)fade_out)
+ *                curve 0 (linear): curve(t) = t;  curve 1 (smooth): curve(t) = (t * t) * (3.0f - 2.0f * t), each of its four
+ *                operations rounded to fp32 separately
+ *                So the first and the last kept sample of a faded segment are exactly 0, and fades that overlap
+ *                (fade_in + fade_out > c) simply multiply.
+ *   multiplier:  mul = (e * w_in) * w_out: two rounded fp32 products
+ *   sample:      the existing formula (delivery; levelled delivery) unchanged up to and including
+ *                `if (volume != 1.0f) v = v * volume`; then v = v * mul; then the clip and the encoders, unchanged.
+ * What the measurements see: the peaks of normalize 1 / 2, the trim scan and the loudness measurement all see the UNSHAPED
+ * audio.  A shape is a time-varying volume: like volume, it can drive a sample into the clip.
+ * So, because x * 1.0f == x: with shapes == NULL, or with every shape without fades and points, bytes and layout are
+ * vits_deliver_leveled's, bit for bit.  The layout never depends on the shapes.
+ * Device side (csrc/shape.hip.hpp): delivery_pack_shaped_kernel in the place of delivery_pack_kernel, only when some shape
+ * has a fade or a point - every other delivery launches what it launched before.  It reads the envelope as one 16-byte
+ * record per interval (position, gain, slope, the next interval's start; slope 0 in front of p_0 and from p_{m-1} on, so
+ * that g + s * d is the value above in every case).  Every product, sum, difference and
+ * quotient above is one rounded instruction: they are written in functions compiled with floating-point contraction off
+ * (csrc/shape.hpp; the same functions run the host rule).  HIP's __fmul_rn / __fadd_rn / __fsub_rn / __fdiv_rn are plain
+ * operators to the compiler and do not prevent a contraction to FMA.  The NumPy reference uses plain np.float32 operations.
+ * Validation happens on the host before anything is enqueued or allocated; VITS_E_ARG, the message naming the segment index
+ * and the value: a negative fade; a curve outside 0..1; a negative n_points; first_point < 0 or first_point + n_points beyond
+ * the call's point count; more than 1 << 20 points in a call; a pos outside [0, INT_MAX]; positions of one segment that do
+ * not ascend strictly (naming the point); a gain that is not finite, is negative, lies in (0, 2^-20) or is above 64;
+ * everything vits_deliver_leveled refuses.  A rejected call leaves the last run deliverable and writes nothing to dst.
+ * Not covered: the encoded stream (a fade-out cannot know where the stream ends); crossfades that overlap two segments; a
+ * limiter; PipelinedSession / ShardedSynthesizer on the device path (they take the host fallback, audio_encoding.join_trimmed
+ * / join_leveled with shapes=, which gives the same bytes). */
+typedef struct {
+    int32_t pos;           /* row sample index at the delivered rate, [0, INT_MAX] */
+    float   gain;          /* 0, or [2^-20, 64] */
+} vits_env_point;
+typedef struct {
+    int32_t fade_in;       /* [0, INT_MAX] */
+    int32_t fade_out;      /* [0, INT_MAX] */
+    int32_t curve;         /* 0 linear, 1 smooth */
+    int32_t n_points;      /* >= 0 */
+    int64_t first_point;   /* index of this segment's first point in the call's point array */
+} vits_shape;
+/* pure host code: the validation above of shapes [n_segs] (nullable: nothing to refuse) over the call's n_points points */
+int vits_shape_check(const vits_shape *shapes, int n_segs, const vits_env_point *points, int64_t n_points);
+/* pure host code: the multiplier of row sample i of a segment with kept range [a, a + c), a <= i < a + c <= INT_MAX; `points`
+ * is the call's array (shape->first_point indexes it) */
+int vits_shape_gain(const vits_shape *shape, const vits_env_point *points, int64_t a, int64_t c, int64_t i, float *mul);
+/* vits_deliver_leveled with shapes [n_segs] (or NULL: none) over points [n_points].  Input run, waiting, VITS_E_RANGE,
+ * dst == NULL and repeatability as vits_deliver_leveled; trims, levels and shapes are each nullable. */
+int vits_deliver_shaped(vits_handle *h, const vits_segment *segs, const vits_trim *trims, const vits_level *levels,
+                        const vits_shape *shapes, const vits_env_point *points, int64_t n_points, int n_segs, int n_streams,
+                        int encoding, int sample_rate, void *dst, size_t dst_bytes, int64_t *stream_samples, int64_t *stream_offsets,
+                        int64_t *kept_first, int64_t *kept_count, double *loudness, float *gain);
 
 /* ---- encoded streaming: a chunked run's chunks post-processed, encoded and masked on the device --------------------------
  * vits_run_chunked* hands every chunk over as fp32 [B][n]; vits_deliver refuses a chunked run.  The two entries below are the
@@ -815,6 +886,13 @@ int vits_test_deliver_leveled(int device_id, const float *x, const int64_t *coun
                               const vits_trim *trims, const vits_level *levels, int n_segs, int n_streams, int encoding,
                               int sample_rate, void *dst, size_t dst_bytes, int64_t *stream_samples, int64_t *stream_offsets,
                               int64_t *kept_first, int64_t *kept_count, double *loudness, float *gain);
+
+/* The shaped delivery by value: as vits_test_deliver_leveled; everything else as vits_deliver_shaped. */
+int vits_test_deliver_shaped(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_segment *segs,
+                             const vits_trim *trims, const vits_level *levels, const vits_shape *shapes, const vits_env_point *points,
+                             int64_t n_points, int n_segs, int n_streams, int encoding, int sample_rate, void *dst, size_t dst_bytes,
+                             int64_t *stream_samples, int64_t *stream_offsets, int64_t *kept_first, int64_t *kept_count,
+                             double *loudness, float *gain);
 
 /* The encoded stream's kernel by value: x [B][S] host, counts [B] the rows' valid samples (within [0, S]; what lies behind
  * must not show).  Columns [0, S) are cut into pieces of piece_samples samples (the last one shorter); each piece goes through

@@ -65,6 +65,15 @@ class VitsLevel(C.Structure):
     _fields_ = [("mode", C.c_int32), ("target_lufs", C.c_float), ("max_gain_db", C.c_float), ("peak_ceiling", C.c_float)]
 
 
+class VitsEnvPoint(C.Structure):
+    _fields_ = [("pos", C.c_int32), ("gain", C.c_float)]
+
+
+class VitsShape(C.Structure):
+    _fields_ = [("fade_in", C.c_int32), ("fade_out", C.c_int32), ("curve", C.c_int32), ("n_points", C.c_int32),
+                ("first_point", C.c_int64)]
+
+
 class VitsStreamFormat(C.Structure):
     _fields_ = [("encoding", C.c_int32), ("ref_peak", C.c_void_p), ("volume", C.c_void_p)]
 
@@ -102,6 +111,7 @@ EXPORTS = [
     "vits_trim_range", "vits_delivery_plan_trimmed", "vits_deliver_trimmed", "vits_test_deliver_trimmed",
     "vits_loudness_filter", "vits_loudness_gate", "vits_level_gain", "vits_delivery_plan_leveled", "vits_deliver_leveled",
     "vits_test_loudness_blocks", "vits_test_deliver_leveled",
+    "vits_shape_check", "vits_shape_gain", "vits_deliver_shaped", "vits_test_deliver_shaped",
     "vits_run_chunked_enc", "vits_run_vocoder_chunked_enc", "vits_test_stream_pack",
     "vits_test_layernorm", "vits_test_dds", "vits_test_cf_pre", "vits_test_rqs_inverse", "vits_test_ea_logw",
 ]
@@ -209,6 +219,12 @@ def load():
     lib.vits_test_loudness_blocks.argtypes = [C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vp, vp]
     lib.vits_test_deliver_leveled.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp,
                                               C.c_size_t, vp, vp, vp, vp, vp, vp]
+    lib.vits_shape_check.argtypes = [vp, C.c_int, vp, C.c_int64]
+    lib.vits_shape_gain.argtypes = [C.POINTER(VitsShape), vp, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_float)]
+    lib.vits_deliver_shaped.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vp, vp, vp,
+                                        vp, vp, vp]
+    lib.vits_test_deliver_shaped.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int64, C.c_int, C.c_int, C.c_int,
+                                             C.c_int, vp, C.c_size_t, vp, vp, vp, vp, vp, vp]
     lib.vits_free_output.argtypes = [vp, C.POINTER(VitsOutput)]
     lib.vits_free_output.restype = None
     lib.vits_sync.argtypes = [vp]

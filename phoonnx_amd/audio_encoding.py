@@ -12,6 +12,10 @@ of a row, and one stream of rows cut to their kept ranges with silence in front 
 `loudness`, `level_gain` and `join_leveled` are the same for the levelled delivery (include/vitsmi.h, "levelled delivery"), in
 float64: the integrated loudness of ITU-R BS.1770-4 of a row, the gain that brings it to a target, and one stream of rows
 levelled, encoded and joined.
+
+`shape_multiplier` and the `shapes=` argument of the two joins are the same for the shaped delivery (include/vitsmi.h, "shaped
+delivery"): fades and a breakpoint envelope as one float32 multiplier per kept sample, operation by operation as the device
+computes it - the same bytes.
 """
 import io
 import math
@@ -107,20 +111,86 @@ def trim_range(x, n, trim):
     return a, e - a
 
 
-def scaled(audio: np.ndarray, peak, volume: float) -> np.ndarray:
-    """The delivery's sample formula in float32: peak None - no normalisation; peak < 1e-8 - zeros."""
+def scaled(audio: np.ndarray, peak, volume: float, mul=None) -> np.ndarray:
+    """The delivery's sample formula in float32: peak None - no normalisation; peak < 1e-8 - zeros.  mul (float32, one per
+    sample, or None): the shaped delivery's multiplier, one more product in front of the clip."""
     audio = np.asarray(audio, np.float32)
     if peak is not None:
         audio = np.zeros_like(audio) if np.float32(peak) < np.float32(1e-8) else audio / np.float32(peak)
     if np.float32(volume) != np.float32(1.0):
         audio = audio * np.float32(volume)
+    if mul is not None:
+        audio = audio * np.asarray(mul, np.float32)
     return np.clip(audio, np.float32(-1.0), np.float32(1.0)).astype(np.float32)
 
 
-def join_trimmed(rows, encoding="pcm16", lead=0, tail=0, trim=None, normalize=1, volume=1.0):
+_CURVES = {"linear": 0, "smooth": 1, 0: 0, 1: 1}
+
+
+def _curve(t: np.ndarray, curve: int) -> np.ndarray:
+    if curve == 0:
+        return t
+    return (t * t) * (np.float32(3.0) - np.float32(2.0) * t)       # four float32 operations, each rounded
+
+
+def shape_multiplier(a, c, shape) -> np.ndarray:
+    """The multiplier of every sample of the kept range [a, a + c) of a row under `shape` - anything with the fields of
+    session.Shape: fade_in, fade_out (samples of the kept range), curve ("linear" / "smooth", or 0 / 1), points ((pos, gain),
+    pos a sample index of the ROW, strictly ascending) - or None (ones).  float32 [c], every operation a float32 one, in the
+    order of include/vitsmi.h, "shaped delivery"."""
+    a, c = int(a), int(c)
+    if shape is None:
+        return np.ones(c, np.float32)
+    if shape.curve not in _CURVES:
+        raise ValueError(f"curve {shape.curve!r}: 'linear' or 'smooth'")
+    curve = _CURVES[shape.curve]
+    fade_in, fade_out = int(shape.fade_in), int(shape.fade_out)
+    if fade_in < 0 or fade_out < 0:
+        raise ValueError(f"fades must be >= 0 samples (got {fade_in}, {fade_out})")
+    j = np.arange(c, dtype=np.int64)
+    i = a + j
+    e = np.ones(c, np.float32)
+    pts = list(shape.points)
+    if pts:
+        p = np.array([int(q[0]) for q in pts], np.int64)
+        g = np.array([q[1] for q in pts], np.float32)
+        if (p < 0).any() or (np.diff(p) <= 0).any():
+            raise ValueError("points: positions must be >= 0 and ascend strictly")
+        e = np.where(i <= p[0], g[0], g[-1]).astype(np.float32)
+        if len(p) > 1:
+            s = (g[1:] - g[:-1]) / (p[1:] - p[:-1]).astype(np.float32)
+            k = np.clip(np.searchsorted(p, i, side="right") - 1, 0, len(p) - 2)
+            inner = (i > p[0]) & (i < p[-1])
+            e[inner] = (g[k] + s[k] * (i - p[k]).astype(np.float32))[inner]
+    w_in, w_out = np.ones(c, np.float32), np.ones(c, np.float32)
+    if fade_in:
+        m = j < fade_in
+        w_in[m] = _curve(j[m].astype(np.float32) / np.float32(fade_in), curve)
+    if fade_out:
+        r = c - 1 - j
+        m = r < fade_out
+        w_out[m] = _curve(r[m].astype(np.float32) / np.float32(fade_out), curve)
+    return ((e * w_in) * w_out).astype(np.float32)
+
+
+def _row_shapes(shapes, n):
+    """None, one shape or one per row -> a list of n (None: no shape)"""
+    if shapes is None:
+        return [None] * n
+    if hasattr(shapes, "fade_in"):
+        return [shapes] * n
+    shapes = list(shapes)
+    if len(shapes) != n:
+        raise ValueError(f"shapes must be one shape or one per row ({n}), got {len(shapes)}")
+    return shapes
+
+
+def join_trimmed(rows, encoding="pcm16", lead=0, tail=0, trim=None, normalize=1, volume=1.0, shapes=None):
     """ONE stream of a trimmed delivery on the host: every row (its valid float32 samples) cut to trim_range, then `lead`
     elements of silence, the row's kept samples post-processed and encoded, `tail` elements of silence.  normalize: 0 none,
-    1 by the peak of the row's kept range, 2 by the largest of those peaks.  Returns (data, [(a, c) per row])."""
+    1 by the peak of the row's kept range, 2 by the largest of those peaks.  shapes (None, one shape or one per row): each
+    row's kept samples times shape_multiplier in front of the clip; the peaks are those of the unshaped audio.
+    Returns (data, [(a, c) per row])."""
     _check(encoding)
     kept = [trim_range(r, len(r), trim) for r in rows]
     cut = [np.asarray(r, np.float32)[a:a + c] for r, (a, c) in zip(rows, kept)]
@@ -130,8 +200,13 @@ def join_trimmed(rows, encoding="pcm16", lead=0, tail=0, trim=None, normalize=1,
     elif normalize == 2:
         peaks = [max(peaks)] * len(cut) if cut else []
     pieces = []
-    for v, pk in zip(cut, peaks):
-        pieces += [silence(lead, encoding), encode(scaled(v, pk, volume), encoding), silence(tail, encoding)]
+    if shapes is None:
+        for v, pk in zip(cut, peaks):
+            pieces += [silence(lead, encoding), encode(scaled(v, pk, volume), encoding), silence(tail, encoding)]
+        return (np.concatenate(pieces) if pieces else silence(0, encoding)), kept
+    for v, pk, (a, c), sh in zip(cut, peaks, kept, _row_shapes(shapes, len(cut))):
+        mul = None if sh is None else shape_multiplier(a, c, sh)
+        pieces += [silence(lead, encoding), encode(scaled(v, pk, volume, mul), encoding), silence(tail, encoding)]
     return (np.concatenate(pieces) if pieces else silence(0, encoding)), kept
 
 
@@ -211,9 +286,9 @@ def level_gain(loudness, peak, target_lufs, max_gain_db=30.0, peak_ceiling=0.0) 
     return np.float32(g)
 
 
-def leveled(audio: np.ndarray, gain, volume: float) -> np.ndarray:
-    """The levelled delivery's sample formula in float32: one product with the gain, the volume's, the clip."""
-    return scaled(np.asarray(audio, np.float32) * np.float32(gain), None, volume)
+def leveled(audio: np.ndarray, gain, volume: float, mul=None) -> np.ndarray:
+    """The levelled delivery's sample formula in float32: one product with the gain, the volume's, (a shape's,) the clip."""
+    return scaled(np.asarray(audio, np.float32) * np.float32(gain), None, volume, mul)
 
 
 def level_rows(rows, rate, level):
@@ -232,16 +307,22 @@ def level_rows(rows, rate, level):
     return loud, [level_gain(L, pk, level.target_lufs, level.max_gain_db, level.peak_ceiling) for L, pk in zip(loud, peaks)]
 
 
-def join_leveled(rows, rate, level, encoding="pcm16", lead=0, tail=0, trim=None, volume=1.0):
+def join_leveled(rows, rate, level, encoding="pcm16", lead=0, tail=0, trim=None, volume=1.0, shapes=None):
     """ONE stream of a levelled delivery on the host: join_trimmed with every row's kept range brought to a loudness target
-    (level_rows) instead of peak-normalised.  Returns (data, [(a, c) per row], loudness per row, gain per row)."""
+    (level_rows) instead of peak-normalised.  shapes as in join_trimmed: the loudness is that of the unshaped audio.
+    Returns (data, [(a, c) per row], loudness per row, gain per row)."""
     _check(encoding)
     kept = [trim_range(r, len(r), trim) for r in rows]
     cut = [np.asarray(r, np.float32)[a:a + c] for r, (a, c) in zip(rows, kept)]
     loud, gains = level_rows(cut, rate, level)
     pieces = []
-    for v, g in zip(cut, gains):
-        pieces += [silence(lead, encoding), encode(leveled(v, g, volume), encoding), silence(tail, encoding)]
+    if shapes is None:
+        for v, g in zip(cut, gains):
+            pieces += [silence(lead, encoding), encode(leveled(v, g, volume), encoding), silence(tail, encoding)]
+        return (np.concatenate(pieces) if pieces else silence(0, encoding)), kept, loud, gains
+    for v, g, (a, c), sh in zip(cut, gains, kept, _row_shapes(shapes, len(cut))):
+        mul = None if sh is None else shape_multiplier(a, c, sh)
+        pieces += [silence(lead, encoding), encode(leveled(v, g, volume, mul), encoding), silence(tail, encoding)]
     return (np.concatenate(pieces) if pieces else silence(0, encoding)), kept, loud, gains
 
 

@@ -25,6 +25,7 @@
 #include "attention16.hip.hpp"
 #include "conv_sx_small.hip.hpp"
 #include "delivery.hip.hpp"
+#include "shape.hip.hpp"
 #include "kernels.hip.hpp"
 #include "loudness.hip.hpp"
 #include "model.hpp"
@@ -2609,11 +2610,14 @@ int vits_reserve(vits_handle *h, int B, int T, int F) {
         // vits_last_pcm16's int16 waveform and per-utterance peaks (the larger of the two uses)
         const size_t io_in = carved_bytes([&](Carver &cv) { carve_inputs(cv, m, B, T, T, Fp); });
         const size_t io_pcm = carved_bytes([&](Carver &cv) { carve_pcm16(cv, B, F * m.hop); });
-        // ... or vits_deliver's, with vits_deliver_trimmed's slots and vits_deliver_leveled's buffers behind them
+        // ... or vits_deliver's, with vits_deliver_trimmed's slots, vits_deliver_leveled's buffers and vits_deliver_shaped's
+        // tables behind them (two breakpoints per token: what a per-token gain needs at most)
+        const int64_t shape_pts = std::min<int64_t>((int64_t)2 * B * T, kShapeMaxPoints) + B;  // (knots: a segment's points + 1)
         const size_t io_dlv = carved_bytes([&](Carver &cv) {
             carve_delivery(cv, B, F * m.hop);
             carve_trim(cv, B);
             carve_level(cv, B, F * m.hop);
+            carve_shape(cv, B, shape_pts);
         });
         // ... or an encoded stream's chunk buffer: every chunk_frames <= F, i.e. chunks of up to F * hop samples
         const size_t io_sp = carved_bytes([&](Carver &cv) { carve_stream_pack(cv, B, (int64_t)F * m.hop); });
@@ -2635,6 +2639,7 @@ int vits_reserve(vits_handle *h, int B, int T, int F) {
                 carve_resample(cv, B, (int)so, (int)h->rs.plan.K);
                 carve_trim(cv, B);
                 carve_level(cv, B, (int)so);
+                carve_shape(cv, B, shape_pts);
             });
             io = io_rt > io ? io_rt : io;
         }
@@ -3146,14 +3151,66 @@ int vits_delivery_plan_leveled(const int64_t *kept, int B, const vits_segment *s
     return VITS_OK;
 }
 
+int vits_shape_check(const vits_shape *shapes, int n_segs, const vits_env_point *points, int64_t n_points) {
+    if (n_segs < 0) return fail(nullptr, VITS_E_ARG, "n_segs = %d is negative", n_segs);
+    const std::string e = shape_fault(shapes, n_segs, points, n_points);
+    if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
+    return VITS_OK;
+}
+
+int vits_shape_gain(const vits_shape *shape, const vits_env_point *points, int64_t a, int64_t c, int64_t i, float *mul) {
+    if (!shape || !mul) return fail(nullptr, VITS_E_ARG, "null argument");
+    if (shape->first_point < 0 || shape->n_points < 0 || shape->first_point > kShapeMaxPoints - shape->n_points)
+        return fail(nullptr, VITS_E_ARG, "points [%lld, +%d) outside [0, %lld]", (long long)shape->first_point, shape->n_points,
+                    (long long)kShapeMaxPoints);
+    const std::string e = shape_fault(shape, 1, points, shape->first_point + shape->n_points);
+    if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
+    if (a < 0 || c < 0 || a > INT_MAX - c || i < a || i >= a + c)
+        return fail(nullptr, VITS_E_ARG, "sample %lld outside the kept range [%lld, +%lld) of a row of at most %d samples", (long long)i,
+                    (long long)a, (long long)c, INT_MAX);
+    std::vector<float> slopes;
+    shape_slopes(points, shape->first_point + shape->n_points, slopes);
+    const ShapeSeg t{(int32_t)a, (int32_t)c, shape->fade_in, shape->fade_out, shape->curve, shape->n_points, shape->first_point};
+    *mul = shape_gain(t, points, slopes.data(), (int32_t)i);
+    return VITS_OK;
+}
+
+// what a shaped delivery adds to the enqueue: the records of the plan's segments and their knots (host), and carve_shape's
+// buffers they go to.  The vectors are the pageable sources of copies: they outlive the caller's wait.
+struct ShapeJob {
+    std::vector<ShapeSeg> table;
+    std::vector<ShapeKnot> knots;
+    ShapeBufs sb{};
+};
+
+// the job of a finished plan p (over the kept ranges first / kept [B]); shapes have passed shape_fault
+static void shape_job(const DeliveryPlan &p, const vits_segment *segs, const vits_shape *shapes, const vits_env_point *points,
+                      const std::vector<int64_t> &first, const std::vector<int64_t> &kept, ShapeJob &job) {
+    std::vector<int64_t> a(p.order.size()), c(p.order.size());
+    for (size_t k = 0; k < p.order.size(); k++) {
+        const int row = segs[p.order[k]].row;
+        a[k] = first[row];
+        c[k] = kept[row];
+    }
+    shape_table(shapes, p.order, a.data(), c.data(), job.table);
+    shape_knots(job.table, points, job.knots);
+}
+
 // Everything a delivery puts on the stream: segment table up, peaks cleared, the launches, the copies into dst; then the
 // silence, on the host.  The caller synchronises.  db: carve_delivery's buffers for a waveform of at least the plan's rows.
-static hipError_t delivery_enqueue(const float *d_x, const DeliveryPlan &p, const DeliveryBufs &db, int B, hipStream_t st, void *dst) {
+// job: a shaped delivery's tables (nullptr: none - launch_delivery, as ever).
+static hipError_t delivery_enqueue(const float *d_x, const DeliveryPlan &p, const DeliveryBufs &db, int B, hipStream_t st, void *dst,
+                                   const ShapeJob *job = nullptr) {
     hipError_t e = hipSuccess;
     if (p.packed_elems > 0) {
         e = hipMemcpyAsync(db.segs, p.segs.data(), p.segs.size() * sizeof(DeliverySeg), hipMemcpyHostToDevice, st);
         if (e == hipSuccess && p.any_norm) e = hipMemsetAsync(db.peak, 0, 2 * (size_t)B * sizeof(unsigned), st);
-        if (e == hipSuccess) e = launch_delivery(d_x, p, db.segs, db.peak, db.packed, st);
+        if (job) {
+            if (e == hipSuccess) e = hipMemcpyAsync(job->sb.segs, job->table.data(), job->table.size() * sizeof(ShapeSeg), hipMemcpyHostToDevice, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(job->sb.knots, job->knots.data(), job->knots.size() * sizeof(ShapeKnot), hipMemcpyHostToDevice, st);
+            if (e == hipSuccess) e = launch_delivery_shaped(d_x, p, db.segs, db.peak, db.packed, job->sb.segs, job->sb.knots, st);
+        } else if (e == hipSuccess)
+            e = launch_delivery(d_x, p, db.segs, db.peak, db.packed, st);
         for (size_t i = 0; i < p.copies.size() && e == hipSuccess; i++)
             e = hipMemcpyAsync(static_cast<char *>(dst) + p.copies[i].dst_off, db.packed + p.copies[i].packed_off,
                                (size_t)p.copies[i].bytes, hipMemcpyDeviceToHost, st);
@@ -3368,10 +3425,12 @@ static void level_report(int n_segs, const std::vector<double> &loud, const std:
     }
 }
 
-// vits_deliver_trimmed and vits_deliver_leveled: levels == nullptr is the former exactly
+// vits_deliver_trimmed, vits_deliver_leveled and vits_deliver_shaped: levels == nullptr is the first exactly, shapes == nullptr
+// (or shapes without fades and points) the second
 static int deliver_kept(vits_handle *h, const vits_segment *segs, const vits_trim *trims, const vits_level *levels, int n_segs, int n_streams,
                         int encoding, int sample_rate, void *dst, size_t dst_bytes, int64_t *stream_samples, int64_t *stream_offsets,
-                        int64_t *kept_first, int64_t *kept_count, double *loudness, float *gain) {
+                        int64_t *kept_first, int64_t *kept_count, double *loudness, float *gain, const vits_shape *shapes = nullptr,
+                        const vits_env_point *points = nullptr, int64_t n_points = 0) {
     if (int rc = check_dev(h)) return rc;
     std::lock_guard<std::mutex> lk(h->mu);
     const int B = h->B, S = h->S;
@@ -3383,8 +3442,12 @@ static int deliver_kept(vits_handle *h, const vits_segment *segs, const vits_tri
     DeliveryPlan p0;  // over the whole rows: the validation, and the table the scan reads
     std::string e = delivery_plan(counts.data(), B, S, segs, n_segs, n_streams, encoding, p0, trims);
     if (e.empty()) e = level_plan_fault(segs, levels, n_segs, n_streams, sample_rate);
+    if (e.empty()) e = shape_fault(shapes, n_segs, points, n_points);
     if (!e.empty()) return fail(h, VITS_E_ARG, "%s", e.c_str());
     const bool lev = any_level(levels, n_segs);
+    const bool shaped = any_shape(shapes, n_segs);
+    const int64_t n_knots = shape_knot_count(shapes, n_segs);
+    ShapeJob job;
     if (lev && h->rs.plan.on() && sample_rate != h->rs.plan.fo)
         return fail(h, VITS_E_ARG, "sample_rate %d differs from the output rate %d", sample_rate, (int)h->rs.plan.fo);
     DeliveryBufs db{};
@@ -3402,9 +3465,10 @@ static int deliver_kept(vits_handle *h, const vits_segment *segs, const vits_tri
             db = carve_resample(cv, B, S, K).dlv;
             tb = carve_trim(cv, B);
             if (lev) lb = carve_level(cv, B, S);
+            if (shaped) job.sb = carve_shape(cv, B, n_knots);
         };
-        if (lev && carved_bytes(walk) > h->io.cap)
-            return fail(h, VITS_E_NOMEM, "a levelled delivery of this run needs %zu bytes of staging, %zu are there: vits_reserve covers it",
+        if ((lev || shaped) && carved_bytes(walk) > h->io.cap)
+            return fail(h, VITS_E_NOMEM, "a levelled or shaped delivery of this run needs %zu bytes of staging, %zu are there: vits_reserve covers it",
                         carved_bytes(walk), h->io.cap);
         if (int rc = slab_carve(h, h->io, "staging", walk)) return rc;
         if (!h->d_out) return fail(h, VITS_E_ARG, "no completed run to deliver");
@@ -3412,6 +3476,7 @@ static int deliver_kept(vits_handle *h, const vits_segment *segs, const vits_tri
                    db = carve_delivery(cv, B, S);
                    tb = carve_trim(cv, B);
                    if (lev) lb = carve_level(cv, B, S);
+                   if (shaped) job.sb = carve_shape(cv, B, n_knots);
                }))
         return rc;
     hipStream_t st = h->stream;
@@ -3431,7 +3496,8 @@ static int deliver_kept(vits_handle *h, const vits_segment *segs, const vits_tri
     if (err != hipSuccess) return fail(h, VITS_E_DEVICE, "loudness measurement failed: %s", hipGetErrorString(err));
     level_apply(p, levels, gn.data());
     if (dst) {
-        err = delivery_enqueue(h->d_out, p, db, B, st, dst);
+        if (shaped) shape_job(p, segs, shapes, points, first, kept, job);
+        err = delivery_enqueue(h->d_out, p, db, B, st, dst, shaped ? &job : nullptr);
         if (err == hipSuccess) err = hipStreamSynchronize(st);
         else hipStreamSynchronize(st);
         if (err != hipSuccess) return fail(h, VITS_E_DEVICE, "delivery failed: %s", hipGetErrorString(err));
@@ -3454,6 +3520,14 @@ int vits_deliver_leveled(vits_handle *h, const vits_segment *segs, const vits_tr
                          int64_t *stream_offsets, int64_t *kept_first, int64_t *kept_count, double *loudness, float *gain) {
     return deliver_kept(h, segs, trims, levels, n_segs, n_streams, encoding, sample_rate, dst, dst_bytes, stream_samples, stream_offsets,
                         kept_first, kept_count, loudness, gain);
+}
+
+int vits_deliver_shaped(vits_handle *h, const vits_segment *segs, const vits_trim *trims, const vits_level *levels,
+                        const vits_shape *shapes, const vits_env_point *points, int64_t n_points, int n_segs, int n_streams,
+                        int encoding, int sample_rate, void *dst, size_t dst_bytes, int64_t *stream_samples, int64_t *stream_offsets,
+                        int64_t *kept_first, int64_t *kept_count, double *loudness, float *gain) {
+    return deliver_kept(h, segs, trims, levels, n_segs, n_streams, encoding, sample_rate, dst, dst_bytes, stream_samples, stream_offsets,
+                        kept_first, kept_count, loudness, gain, shapes, points, n_points);
 }
 
 // vocoder-only entry points: z (host, [B, inter, F], already masked) -> device, speaker bias; then either the whole
@@ -4371,14 +4445,17 @@ static LevelBufs test_level_bufs(DevBufs &D, int B, int S) {
 static int test_deliver_kept(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_segment *segs,
                              const vits_trim *trims, const vits_level *levels, int n_segs, int n_streams, int encoding, int sample_rate,
                              void *dst, size_t dst_bytes, int64_t *stream_samples, int64_t *stream_offsets, int64_t *kept_first,
-                             int64_t *kept_count, double *loudness, float *gain) {
+                             int64_t *kept_count, double *loudness, float *gain, const vits_shape *shapes = nullptr,
+                             const vits_env_point *points = nullptr, int64_t n_points = 0) {
     if (!x || !counts || B <= 0 || S <= 0 || (int64_t)B * S > (int64_t)1 << 40) return fail(nullptr, VITS_E_ARG, "bad delivery test arguments");
     for (int b = 0; b < B; b++)
         if (counts[b] < 0 || counts[b] > S) return fail(nullptr, VITS_E_ARG, "counts[%d] = %lld outside [0, %d]", b, (long long)counts[b], S);
     DeliveryPlan p0;
     std::string e = delivery_plan(counts, B, S, segs, n_segs, n_streams, encoding, p0, trims);
     if (e.empty()) e = level_plan_fault(segs, levels, n_segs, n_streams, sample_rate);
+    if (e.empty()) e = shape_fault(shapes, n_segs, points, n_points);
     if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
+    const bool shaped = any_shape(shapes, n_segs);
     if (int rc = test_dev(device_id)) return rc;
     DevBufs D;
     float *dx = D.up(x, (size_t)B * S);
@@ -4391,6 +4468,11 @@ static int test_deliver_kept(int device_id, const float *x, const int64_t *count
     tb.peak_all = D.alloc<unsigned>((size_t)B);
     LevelBufs lb{};
     if (any_level(levels, n_segs)) lb = test_level_bufs(D, B, S);
+    ShapeJob job;
+    if (shaped) {
+        job.sb.segs = D.alloc<ShapeSeg>((size_t)B);
+        job.sb.knots = D.alloc<ShapeKnot>((size_t)shape_knot_count(shapes, n_segs));
+    }
     TCHECK(D.err);
     std::vector<int64_t> first, kept;
     TCHECK(trim_scan(dx, p0, segs, trims, counts, B, db, tb, nullptr, first, kept));
@@ -4404,7 +4486,8 @@ static int test_deliver_kept(int device_id, const float *x, const int64_t *count
     TCHECK(level_measure(dx, p, segs, levels, n_segs, n_streams, sample_rate, db, lb, nullptr, loud, gn));
     level_apply(p, levels, gn.data());
     if (dst) {
-        const hipError_t enq = delivery_enqueue(dx, p, db, B, nullptr, dst);
+        if (shaped) shape_job(p, segs, shapes, points, first, kept, job);
+        const hipError_t enq = delivery_enqueue(dx, p, db, B, nullptr, dst, shaped ? &job : nullptr);
         const hipError_t done = hipDeviceSynchronize();
         TCHECK(enq);
         TCHECK(done);
@@ -4428,6 +4511,15 @@ int vits_test_deliver_leveled(int device_id, const float *x, const int64_t *coun
                               int64_t *kept_first, int64_t *kept_count, double *loudness, float *gain) {
     return test_deliver_kept(device_id, x, counts, B, S, segs, trims, levels, n_segs, n_streams, encoding, sample_rate, dst, dst_bytes,
                              stream_samples, stream_offsets, kept_first, kept_count, loudness, gain);
+}
+
+int vits_test_deliver_shaped(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_segment *segs,
+                             const vits_trim *trims, const vits_level *levels, const vits_shape *shapes, const vits_env_point *points,
+                             int64_t n_points, int n_segs, int n_streams, int encoding, int sample_rate, void *dst, size_t dst_bytes,
+                             int64_t *stream_samples, int64_t *stream_offsets, int64_t *kept_first, int64_t *kept_count,
+                             double *loudness, float *gain) {
+    return test_deliver_kept(device_id, x, counts, B, S, segs, trims, levels, n_segs, n_streams, encoding, sample_rate, dst, dst_bytes,
+                             stream_samples, stream_offsets, kept_first, kept_count, loudness, gain, shapes, points, n_points);
 }
 
 int vits_test_loudness_blocks(int device_id, const float *x, const int64_t *counts, const int64_t *firsts, int B, int S,

@@ -13,6 +13,7 @@
 #include "delivery.hpp"
 #include "loudness.hpp"
 #include "model.hpp"
+#include "shape.hpp"
 #include "slab.hpp"
 
 namespace vitsmi {
@@ -295,6 +296,21 @@ inline LevelBufs carve_level(Carver &cv, int B, int S) {
     l.part = cv.take<float>(l.n_chunks * kLoudParts);
     l.result = cv.take<unsigned>(l.n_peaks + l.n_subs);
     return l;
+}
+
+// vits_deliver_shaped on top of the three (a walk of its own, behind carve_level's - or behind carve_trim's where nothing is
+// levelled): the shape records parallel to the segment table, and the segments' knots (shape.hpp: a segment's points and
+// one more).  At most B segments; n_knots is the call's, shape_knot_count.
+struct ShapeBufs {
+    ShapeSeg *segs;
+    ShapeKnot *knots;
+};
+
+inline ShapeBufs carve_shape(Carver &cv, int B, int64_t n_knots) {
+    ShapeBufs s{};
+    s.segs = cv.take<ShapeSeg>(B);
+    s.knots = cv.take<ShapeKnot>((size_t)n_knots);
+    return s;
 }
 
 // With an output rate set (vits_set_output_rate), the staging slab holds the run's RESULT once its inputs are consumed:

@@ -9,7 +9,9 @@ and forwards them over the C ABI (include/vitsmi.h) to the gfx950 engine.  There
 fallback: without libvitsmi.so + an MI355X this raises.
 """
 import ctypes as C
+import dataclasses
 import time
+from collections import namedtuple
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence
 
@@ -275,6 +277,20 @@ class Level:
     peak_ceiling: float = 0.0
 
 
+@dataclass
+class Shape:
+    """The shape of one segment (vitsmi.h, vits_shape): fade_in / fade_out - the samples of the kept range that ramp up from 0
+    and down to 0; curve "linear" or "smooth"; points - (pos, gain) breakpoints of a piecewise-linear volume over the ROW's
+    samples at the delivered rate (pos counted from the row's start, strictly ascending; gain 0 or within [2^-20, 64])."""
+    fade_in: int = 0
+    fade_out: int = 0
+    curve: str = "linear"
+    points: Sequence = ()
+
+
+_CURVES = {"linear": 0, "smooth": 1}
+
+
 def _encoding(encoding):
     try:
         return _ffi.ENCODINGS[encoding]
@@ -324,6 +340,147 @@ def _levels(levels, n):
         except (AttributeError, TypeError, ValueError, OverflowError) as e:
             raise SessionError(f"segment {i}: level: {e}") from None
     return arr
+
+
+# shapes as the C structs hold them, for the tests of the validation: shapes - (fade_in, fade_out, curve, n_points, first_point)
+# per segment; points - (pos, gain) pairs; n_points - the count the call states (None: len(points))
+RawShapes = namedtuple("RawShapes", "shapes points n_points", defaults=(None,))
+
+
+def _points(flat):
+    """(pos, gain) pairs -> a C array of vits_env_point (at least one element)"""
+    arr = np.zeros(max(len(flat), 1), np.dtype([("pos", "<i4"), ("gain", "<f4")]))
+    if flat:
+        pos = np.array([p for p, _ in flat], np.int64)
+        if ((pos < -2 ** 31) | (pos >= 2 ** 31)).any():
+            k = int(np.flatnonzero((pos < -2 ** 31) | (pos >= 2 ** 31))[0])
+            raise SessionError(f"point {k}: pos {int(pos[k])} outside [0, {2 ** 31 - 1}]")
+        arr["pos"], arr["gain"] = pos, np.array([g for _, g in flat], np.float32)
+    return arr
+
+
+def _shapes(shapes, n):
+    """None, one Shape or one per segment -> (ctypes array of n vits_shape, the points of all of them back to back as a
+    structured array of vits_env_point, their count); (None, None, 0) for None"""
+    if shapes is None:
+        return None, None, 0
+    if isinstance(shapes, RawShapes):
+        arr = (_ffi.VitsShape * max(len(shapes.shapes), 1))(*[_ffi.VitsShape(*(int(v) for v in r)) for r in shapes.shapes])
+        flat = [(int(p), float(g)) for p, g in shapes.points]
+        return arr, _ffi.ptr(_points(flat)), len(flat) if shapes.n_points is None else int(shapes.n_points)
+    shapes = [shapes] * n if isinstance(shapes, Shape) else list(shapes)
+    if len(shapes) != n:
+        raise SessionError(f"shapes must be one Shape or one per segment ({n}), got {len(shapes)}")
+    arr = (_ffi.VitsShape * max(n, 1))()
+    flat = []
+    for i, sh in enumerate(shapes):
+        try:
+            curve = _CURVES[sh.curve] if isinstance(sh.curve, str) else int(sh.curve)
+            pts = [(int(pos), float(gain)) for pos, gain in sh.points]
+            arr[i] = _ffi.VitsShape(int(sh.fade_in), int(sh.fade_out), curve, len(pts), len(flat))
+            flat += pts
+        except KeyError:
+            raise SessionError(f"segment {i}: shape: curve {sh.curve!r}: one of {sorted(_CURVES)}") from None
+        except (AttributeError, TypeError, ValueError, OverflowError) as e:
+            raise SessionError(f"segment {i}: shape: {e}") from None
+    return arr, _ffi.ptr(_points(flat)), len(flat)
+
+
+def shape_check(shapes, n=None):
+    """The validation of a shaped delivery's shapes (vits_shape_check: pure host code); a refusal raises SessionError."""
+    if n is None:
+        n = 1 if isinstance(shapes, Shape) else len(shapes.shapes if isinstance(shapes, RawShapes) else list(shapes))
+    arr, points, n_points = _shapes(shapes, n)
+    rc = _ffi.load().vits_shape_check(arr, n, points, n_points)
+    if rc != 0:
+        raise SessionError(f"vits_shape_check failed [{rc}]: {_ffi.last_error(None)}")
+
+
+def shape_gain(shape, a, c, i):
+    """The multiplier of row sample i of a segment with kept range [a, a + c) under `shape` (vits_shape_gain: pure host code)
+    -> float32"""
+    arr, points, _ = _shapes(shape, 1)
+    mul = C.c_float()
+    rc = _ffi.load().vits_shape_gain(arr, points, int(a), int(c), int(i), C.byref(mul))
+    if rc != 0:
+        raise SessionError(f"vits_shape_gain failed [{rc}]: {_ffi.last_error(None)}")
+    return np.float32(mul.value)
+
+
+def token_envelope(bounds, gains, ramp):
+    """A per-token volume as breakpoints: bounds - int [T + 1], the tokens' boundaries in row samples at the delivered rate
+    (build_alignments' rule: min(N, ceil(e * L / M))); gains - float32 [T], one linear gain per token; ramp - the samples a
+    change of gain takes, centred on the boundary -> [(pos, gain)].
+    Tokens of zero samples are skipped.  Every boundary s between consecutive non-empty tokens u, v with g_u != g_v gets
+    h = min(ramp // 2, len_u // 2, len_v // 2) and the points (s - h, g_u), (s + h, g_v) - for h == 0: (s - 1, g_u), (s, g_v);
+    a point whose pos equals the previous point's is dropped (it then has the same gain).  All gains equal to g != 1: the
+    single point (0, g); all equal to 1: no points."""
+    bounds = np.asarray(bounds, np.int64).ravel()
+    gains = np.asarray(gains, np.float32).ravel()
+    if bounds.size != gains.size + 1:
+        raise SessionError(f"token_envelope: {gains.size} gains need {gains.size + 1} boundaries, got {bounds.size}")
+    if (np.diff(bounds) < 0).any() or (bounds.size and bounds[0] < 0):
+        raise SessionError("token_envelope: boundaries must be >= 0 and must not descend")
+    ramp = int(ramp)
+    if ramp < 0:
+        raise SessionError(f"token_envelope: ramp {ramp} is negative")
+    live = [t for t in range(gains.size) if bounds[t + 1] > bounds[t]]
+    if not live:
+        return []
+    if all(gains[t] == gains[live[0]] for t in live):
+        g = float(gains[live[0]])
+        return [] if g == 1.0 else [(0, g)]
+    points = []
+    for u, v in zip(live[:-1], live[1:]):
+        if gains[u] == gains[v]:
+            continue
+        s = int(bounds[v])
+        h = min(ramp // 2, int(bounds[u + 1] - bounds[u]) // 2, int(bounds[v + 1] - bounds[v]) // 2)
+        pair = ((s - h, gains[u]), (s + h, gains[v])) if h > 0 else ((s - 1, gains[u]), (s, gains[v]))
+        for pos, g in pair:
+            if not points or pos != points[-1][0]:
+                points.append((pos, float(g)))
+    return points
+
+
+def token_bounds(durations, n_tokens, hop, count, ratio=None) -> np.ndarray:
+    """The boundaries of one row's tokens in samples at the delivered rate: durations - the frames per token (a padded row is
+    fine), n_tokens - the row's own tokens, count - the row's valid samples N, ratio - (L, M) of an output rate or None ->
+    int64 [len(durations) + 1], by build_alignments' rule: the boundary at input sample e lies at min(N, ceil(e * L / M)),
+    and at N behind the row's last token (the engine renders at least one frame)."""
+    L, M = (int(v) for v in ratio) if ratio is not None else (1, 1)
+    e = np.concatenate([[0], np.cumsum(np.asarray(durations, np.int64))]) * int(hop)
+    bounds = np.minimum(int(count), -(-e * L // M))
+    bounds[int(n_tokens):] = int(count)
+    return bounds
+
+
+def token_gain_shapes(segments, shapes, gains, bounds, ramp):
+    """The shapes of a delivery with every segment's points set from the token gains of its row: gains float32 [B][T],
+    bounds one token_bounds per row, ramp in samples.  A segment that already has points is refused."""
+    out = []
+    for i, (g, sh) in enumerate(zip(segments, shapes)):
+        if len(sh.points):
+            raise SessionError(f"segment {i}: token_gain_db and explicit points on the same segment")
+        bd = bounds[int(g.row)]          # (a row's own tokens, or the padded row's: what lies behind them has no samples)
+        out.append(dataclasses.replace(sh, points=token_envelope(bd, gains[int(g.row)][:len(bd) - 1], ramp)))
+    return out
+
+
+def token_gains(token_gain_db, B, T):
+    """token_gain_db [B][T] in dB -> float32 [B, T] linear gains (float32(10 ** (dB / 20)); -inf: 0)"""
+    try:
+        db = np.asarray(token_gain_db, np.float64)
+    except (TypeError, ValueError):
+        raise SessionError(f"token_gain_db must be [{B}][{T}] numbers") from None
+    if db.shape != (B, T):
+        raise SessionError(f"token_gain_db must be [{B}][{T}], got {db.shape}")
+    ok = (db == -np.inf) | (np.isfinite(db) & (db >= -120.0) & (db <= 36.0))
+    if not ok.all():
+        b, t = (int(v) for v in np.argwhere(~ok)[0])
+        raise SessionError(f"token_gain_db[{b}][{t}] = {db[b, t]}: -inf, or within [-120, 36] dB")
+    with np.errstate(over="ignore"):
+        return np.where(db == -np.inf, 0.0, 10.0 ** (db / 20.0)).astype(np.float32)
 
 
 def _n_streams(segments, n_streams):
@@ -1172,7 +1329,7 @@ class MiSession:
         return int(self.output_rate or self.input_rate or self.meta("sample_rate") or 22050)
 
     def deliver(self, segments, n_streams=None, encoding="pcm16", trims=None, return_kept=False, levels=None, sample_rate=None,
-                return_levels=False):
+                return_levels=False, shapes=None):
         """The last run's audio, post-processed, encoded and laid out per request on the device (vitsmi.h, "delivery"):
         segments - Segment objects, each row of the run in at most one; encoding "pcm16" / "ulaw" / "alaw" / "f32".  Returns
         one NumPy array per stream (int16 / uint8 / float32), all views into ONE buffer in stream order - page-locked memory
@@ -1186,14 +1343,18 @@ class MiSession:
         levels - one Level or one per segment (vitsmi.h, "levelled delivery"): the integrated loudness of every levelled
         segment's kept range is measured on the device and the segment delivered at its target; sample_rate - the rate the
         audio is at (default: delivered_rate; refused where it differs from a set output rate).  return_levels=True appends
-        (loudness float64 [G] - NaN for an unlevelled segment, -inf below 400 ms or the gates -, gain float32 [G])."""
+        (loudness float64 [G] - NaN for an unlevelled segment, -inf below 400 ms or the gates -, gain float32 [G]).
+        shapes - one Shape or one per segment (vitsmi.h, "shaped delivery"): fades at either end of what is kept of a segment
+        and a piecewise-linear volume over its row, applied by the pack launch; peaks, trim scan and loudness see the
+        unshaped audio, and the layout does not depend on the shapes."""
         segments = list(segments)
         code, dtype = _encoding(encoding)
         J = _n_streams(segments, n_streams)
         arr, n = _segments(segments)
         samples, offsets = np.zeros(max(J, 0), np.int64), np.zeros(max(J, 0) + 1, np.int64)
-        if levels is not None or return_levels:
+        if levels is not None or return_levels or shapes is not None:
             tarr, larr = _trims(trims, n), _levels(levels, n)
+            sarr, parr, n_points = _shapes(shapes, n)
             rate = self.delivered_rate if sample_rate is None else int(sample_rate)
             first, count = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
             loud, gain = np.full(max(n, 1), np.nan, np.float64), np.ones(max(n, 1), np.float32)
@@ -1204,11 +1365,18 @@ class MiSession:
                     self._raise("vits_deliver", rc)
                 cap = int(offsets[-1]) + width * sum(max(int(tarr[i].tail_samples), 0) for i in range(n if tarr else 0))
                 buf = _POOL.array((cap,), np.uint8) if self.pinned_results and cap else np.empty(cap, np.uint8)
-                rc = self._lib.vits_deliver_leveled(self._h, arr, tarr, larr, n, J, code, rate, _ffi.ptr(buf), cap, _ffi.ptr(samples),
-                                                    _ffi.ptr(offsets), _ffi.ptr(first), _ffi.ptr(count), _ffi.ptr(loud),
-                                                    _ffi.ptr(gain))
-                if rc != 0:
-                    self._raise("vits_deliver_leveled", rc)
+                if shapes is not None:
+                    rc = self._lib.vits_deliver_shaped(self._h, arr, tarr, larr, sarr, parr, n_points, n, J, code, rate, _ffi.ptr(buf),
+                                                       cap, _ffi.ptr(samples), _ffi.ptr(offsets), _ffi.ptr(first), _ffi.ptr(count),
+                                                       _ffi.ptr(loud), _ffi.ptr(gain))
+                    if rc != 0:
+                        self._raise("vits_deliver_shaped", rc)
+                else:
+                    rc = self._lib.vits_deliver_leveled(self._h, arr, tarr, larr, n, J, code, rate, _ffi.ptr(buf), cap, _ffi.ptr(samples),
+                                                        _ffi.ptr(offsets), _ffi.ptr(first), _ffi.ptr(count), _ffi.ptr(loud),
+                                                        _ffi.ptr(gain))
+                    if rc != 0:
+                        self._raise("vits_deliver_leveled", rc)
             streams = [buf[int(offsets[j]):int(offsets[j + 1])].view(dtype) for j in range(J)]
             res = (streams,) + ((first[:n], count[:n]) if return_kept else ()) + ((loud[:n], gain[:n]) if return_levels else ())
             return res if len(res) > 1 else streams
@@ -1259,13 +1427,20 @@ class MiSession:
 
     def synthesize_delivered(self, ids, lens, scales, sid=None, *, segments=None, n_streams=None, encoding="pcm16",
                              normalize=True, volume=1.0, seeds=None, durations=None, token_rate=None, noise_dp=None,
-                             noise_z=None, return_durations=False, trim=None, levels=None):
+                             noise_z=None, return_durations=False, trim=None, levels=None, shapes=None, token_gain_db=None,
+                             gain_ramp=0.01):
         """One batched run and its delivery under one hold of the session lock: what leaves the GPU is the encoded audio
         of the plan and nothing else - the fp32 waveform is never copied to the host.  segments=None: one stream per row,
         with `normalize` / `volume` as scalars or [B] arrays (row b's own).  Everything in front of the delivery is
         synthesize_batch's (scales [3] or [B, 3], seeds, durations, token_rate, injected noise, the bf16x6 fallback).
         trim - one Trim or one per segment: deliver(..., trims=trim).  levels - one Level or one per segment:
         deliver(..., levels=levels); the result then holds "loudness" (float64 [G]) and "gain" (float32 [G]) too.
+        shapes - one Shape or one per segment: deliver(..., shapes=shapes).  token_gain_db - [B][T], a volume in dB per token of
+        every row (-inf: silent; else within [-120, 36]): between the run and the delivery it becomes breakpoints of the
+        segment on that row - token_envelope over the tokens' boundaries at the delivered rate (last_durations(), the hop, the
+        output-rate ratio) with gains float32(10 ** (dB / 20)) and a ramp of int(delivered_rate * gain_ramp) samples around
+        every change.  No second run, no waveform on the host.  A segment with explicit points AND token gains is refused.
+        With either, the result holds "shapes": the Shape every segment was delivered with.
         Returns {"streams": [array per stream], "stream_samples": int64 [J], "y_lengths": int64 [B], "sample_lengths":
         int64 [B] (each row's valid samples at the delivered rate), "kept_first" / "kept_count": int64 [G] (what each
         segment delivers of its row: all of it without a trim)[, "durations"]}."""
@@ -1282,14 +1457,35 @@ class MiSession:
             n_streams = B
         segments = list(segments)
         _encoding(encoding)
+        used = None
+        if shapes is not None or token_gain_db is not None:
+            used = [Shape()] * len(segments) if shapes is None else ([shapes] * len(segments) if isinstance(shapes, Shape) else list(shapes))
+            if len(used) != len(segments):
+                raise SessionError(f"shapes must be one Shape or one per segment ({len(segments)}), got {len(used)}")
+        tgains = None
+        if token_gain_db is not None:
+            tgains = token_gains(token_gain_db, B, ids.shape[1])
+            if not (np.isfinite(gain_ramp) and gain_ramp >= 0):
+                raise SessionError(f"gain_ramp must be >= 0 seconds (got {gain_ramp})")
+            for i, sh in enumerate(used):
+                if len(sh.points):
+                    raise SessionError(f"segment {i}: token_gain_db and explicit points on the same segment")
         with self._locked():
             try:
                 self._begin(ids, lens, scales, sid, noise, seeds, durations, token_rate)
                 ylen = self.last_y_lengths()
-                dur = self.last_durations() if return_durations else None
+                dur = self.last_durations() if return_durations or tgains is not None else None
                 counts = self.last_sample_counts()
                 loud = gain = None
-                if levels is not None:
+                if tgains is not None:
+                    used = self._token_shapes(segments, used, tgains, dur, lens, counts, gain_ramp)
+                if used is not None:
+                    res = self.deliver(segments, n_streams, encoding, trims=trim, return_kept=True, levels=levels,
+                                       return_levels=levels is not None, shapes=used)
+                    streams, kept_first, kept_count = res[:3]
+                    if levels is not None:
+                        loud, gain = res[3:]
+                elif levels is not None:
                     streams, kept_first, kept_count, loud, gain = self.deliver(segments, n_streams, encoding, trims=trim,
                                                                                return_kept=True, levels=levels, return_levels=True)
                 elif trim is None:
@@ -1303,14 +1499,26 @@ class MiSession:
                 return self.synthesize_delivered(ids, lens, scales, sid, segments=segments, n_streams=n_streams,
                                                  encoding=encoding, seeds=seeds, durations=durations, token_rate=token_rate,
                                                  noise_dp=noise_dp, noise_z=noise_z, return_durations=return_durations,
-                                                 trim=trim, levels=levels)
+                                                 trim=trim, levels=levels, shapes=shapes, token_gain_db=token_gain_db,
+                                                 gain_ramp=gain_ramp)
         res = {"streams": streams, "stream_samples": np.array([a.size for a in streams], np.int64), "y_lengths": ylen,
                "sample_lengths": counts, "kept_first": kept_first, "kept_count": kept_count}
         if levels is not None:
             res["loudness"], res["gain"] = loud, gain
+        if used is not None:
+            res["shapes"] = used
         if return_durations:
             res["durations"] = dur
         return res
+
+    def _token_shapes(self, segments, shapes, gains, durations, lens, counts, gain_ramp):
+        """the shapes of a delivery of the last run with every segment's points set from its row's token gains"""
+        ratio = None
+        if self.resampling:
+            ratio = resample_plan(self.input_rate or int(self.meta("sample_rate") or 22050), self.output_rate)[:2]
+        hop = self.hparam("hop")
+        bounds = [token_bounds(durations[b], lens[b], hop, counts[b], ratio) for b in range(len(lens))]
+        return token_gain_shapes(segments, shapes, gains, bounds, int(self.delivered_rate * float(gain_ramp)))
 
     def sync(self):
         with self._locked():
@@ -1955,6 +2163,35 @@ def test_deliver_leveled(x, counts, segments, levels, sample_rate, trims=None, n
                                                _ffi.ptr(first), _ffi.ptr(count), _ffi.ptr(loud), _ffi.ptr(gain))
     if rc != 0:
         raise SessionError(f"vits_test_deliver_leveled failed [{rc}]: {_ffi.last_error(None)}")
+    streams = None if layout_only else [dst[int(offsets[j]):int(offsets[j + 1])].view(dtype) for j in range(J)]
+    return {"streams": streams, "stream_samples": samples, "stream_offsets": offsets, "kept_first": first[:n], "kept_count": count[:n],
+            "loudness": loud[:n], "gain": gain[:n]}
+
+
+def test_deliver_shaped(x, counts, segments, shapes, trims=None, levels=None, sample_rate=22050, n_streams=None, encoding="pcm16",
+                        device_id=0, dst=None, layout_only=False):
+    """vits_test_deliver_shaped: test_deliver_leveled with shapes (one Shape, one per segment, or None); `dst` as in
+    test_deliver_trimmed: a refusal raises SessionError and leaves a `dst` passed in untouched."""
+    x = np.ascontiguousarray(x, np.float32)
+    counts = np.ascontiguousarray(counts, np.int64)
+    B, S = x.shape
+    segments = list(segments)
+    code, dtype = _encoding(encoding)
+    J = _n_streams(segments, n_streams)
+    arr, n = _segments(segments)
+    tarr, larr = _trims(trims, n), _levels(levels, n)
+    sarr, parr, n_points = _shapes(shapes, n)
+    if dst is None and not layout_only:
+        dst = np.empty(delivery_plan(counts, segments, J, encoding, trims=trims)["total_bytes"], np.uint8)
+    samples, offsets = np.zeros(max(J, 0), np.int64), np.zeros(max(J, 0) + 1, np.int64)
+    first, count = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
+    loud, gain = np.full(max(n, 1), np.nan, np.float64), np.ones(max(n, 1), np.float32)
+    rc = _ffi.load().vits_test_deliver_shaped(device_id, _ffi.ptr(x), _ffi.ptr(counts), B, S, arr, tarr, larr, sarr, parr, n_points, n, J,
+                                              code, int(sample_rate), None if layout_only else _ffi.ptr(dst),
+                                              0 if layout_only else dst.nbytes, _ffi.ptr(samples), _ffi.ptr(offsets),
+                                              _ffi.ptr(first), _ffi.ptr(count), _ffi.ptr(loud), _ffi.ptr(gain))
+    if rc != 0:
+        raise SessionError(f"vits_test_deliver_shaped failed [{rc}]: {_ffi.last_error(None)}")
     streams = None if layout_only else [dst[int(offsets[j]):int(offsets[j + 1])].view(dtype) for j in range(J)]
     return {"streams": streams, "stream_samples": samples, "stream_offsets": offsets, "kept_first": first[:n], "kept_count": count[:n],
             "loudness": loud[:n], "gain": gain[:n]}

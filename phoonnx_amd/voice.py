@@ -37,6 +37,7 @@ LOG = logging.getLogger(__name__)
 
 _PHONEME_BLOCK = re.compile(r"(\[\[.*?\]\])")
 _MAX_WAV_VALUE = 32767.0
+_GAIN_RAMP = 0.01   # seconds a change of per-phoneme volume takes (synthesize_encoded, phoneme_gain_db)
 _MASK64 = (1 << 64) - 1
 _GOLDEN64 = 0x9E3779B97F4A7C15
 
@@ -376,7 +377,8 @@ class TTSVoice:
 
     def synthesize_requests(self, requests: Sequence[Tuple[str, Optional[SynthesisConfig]]],
                             seeds: Optional[Sequence[int]] = None, max_batch: int = 32,
-                            alignments: bool = False, postprocess: bool = True) -> List[List[AudioChunk]]:
+                            alignments: bool = False, postprocess: bool = True,
+                            _durations: Optional[dict] = None) -> List[List[AudioChunk]]:
         """Extension: many independent requests (text, SynthesisConfig or None) rendered together.  Every sentence of
         every request becomes one row of a batch with its request's own speaker, length / noise scales and (with `seeds`,
         one integer per request) its own noise seed - sentence k of request r: sentence_seed(seeds[r], k); rows are sorted
@@ -387,7 +389,9 @@ class TTSVoice:
         alignments=True fills every chunk's phoneme_alignments as synthesize(text, cfg, alignments=True) does.
         postprocess=False (what synthesize_requests_encoded's trimmed fallback asks for: the cut comes before the peak) returns
         the rows as rendered - no normalisation, volume or clipping; everything else, alignments included, as with True (a
-        session without synthesize_batch reports no durations either way, so its chunks carry no alignments)."""
+        session without synthesize_batch reports no durations either way, so its chunks carry no alignments).
+        _durations (internal: synthesize_requests_encoded's shaped fallback): a dict that receives the frames per phoneme id
+        of sentence k of request r under (r, k); needs a session with synthesize_batch."""
         if max_batch < 1:
             raise ValueError(f"max_batch must be >= 1 (got {max_batch})")
         if seeds is not None and len(seeds) != len(requests):
@@ -401,6 +405,8 @@ class TTSVoice:
                 if not 0 <= spk < max(n_spk, 1):
                     raise ValueError(f"request {r}: speaker_id {spk} is out of range [0, {max(n_spk, 1)})")
         if not hasattr(self.session, "synthesize_batch"):
+            if _durations is not None:
+                raise ValueError("phoneme_gain_db needs a session that reports durations (synthesize_batch)")
             if not postprocess:
                 return [[AudioChunk(sample_rate=self.sample_rate, sample_width=2, sample_channels=1,
                                     audio_float_array=np.atleast_1d(self.phoneme_ids_to_audio(ids, cfg)))
@@ -419,7 +425,7 @@ class TTSVoice:
                 rows.extend((r, k, ids) for k, ids in enumerate(self._sentence_ids(text, cfg)))
         audio = {}
         aligned = {}
-        more = {"return_durations": True} if want_dur else {}
+        more = {"return_durations": True} if want_dur or _durations is not None else {}
         hop = self.session.hparam("hop")
         order = sorted(range(len(rows)), key=lambda i: len(rows[i][2]))  # (stable: equal lengths keep request order)
         for c0 in range(0, len(order), max_batch):
@@ -433,8 +439,10 @@ class TTSVoice:
                 row_seeds = np.asarray([sentence_seed(seeds[r], k) for r, k, _ in run], np.uint64)
                 out = self.session.synthesize_batch(ids, lens, scales, sid, seeds=row_seeds, **more)
             valid = self._valid_samples(out, hop)
-            for b, (r, k, _) in enumerate(run):
+            for b, (r, k, ids_b) in enumerate(run):
                 audio[r, k] = out["output"][b, 0, 0, :int(valid[b])].copy()
+                if _durations is not None:
+                    _durations[r, k] = np.asarray(out["durations"][b, :len(ids_b)], np.int64).copy()
                 if want_dur:
                     aligned[r, k] = build_alignments(groups[r, k], out["durations"][b], hop,
                                                      total_frames=int(out["y_lengths"][b]), ratio=self._ratio())
@@ -501,6 +509,49 @@ class TTSVoice:
             raise ValueError("loudness levelling replaces peak normalisation: pass a SynthesisConfig with normalize_audio=False")
         return Level(1 if loudness_scope == "sentence" else 2, target, float(max_gain_db), float(peak_ceiling))
 
+    def _shape(self, fade_in: float, fade_out: float, fade_curve: str):
+        """fade_in / fade_out (seconds) and fade_curve of the encoded entries -> a session.Shape in samples at the delivered
+        rate (int(sample_rate * seconds)), or None when neither fades."""
+        from .session import Shape
+        for name, v in (("fade_in", fade_in), ("fade_out", fade_out)):
+            if not (v >= 0.0 and np.isfinite(v)):
+                raise ValueError(f"{name} must be a finite number of seconds >= 0 (got {v})")
+        if fade_curve not in ("linear", "smooth"):
+            raise ValueError(f"fade_curve must be 'linear' or 'smooth' (got {fade_curve!r})")
+        fi, fo = int(self.sample_rate * fade_in), int(self.sample_rate * fade_out)
+        return Shape(fi, fo, fade_curve) if fi or fo else None
+
+    @staticmethod
+    def _group_db(phoneme_gain_db, k: int, groups) -> List[float]:
+        """phoneme_gain_db(k, [the tokens of sentence k's groups]) -> one dB value per phoneme id: all ids of a group, its
+        blanks included, take the group's value"""
+        vals = list(phoneme_gain_db(k, [token for token, _ in groups]))
+        if len(vals) != len(groups):
+            raise ValueError(f"phoneme_gain_db returned {len(vals)} values for the {len(groups)} groups of sentence {k}")
+        return [float(v) for v, (_, ids) in zip(vals, groups) for _ in ids]
+
+    @staticmethod
+    def _padded_db(token_db) -> np.ndarray:
+        """per-row dB lists -> [B, T], 0 dB behind each row's end (tokens of no frames: they never show)"""
+        db = np.zeros((len(token_db), max(len(q) for q in token_db)), np.float64)
+        for b, q in enumerate(token_db):
+            db[b, :len(q)] = q
+        return db
+
+    def _row_shapes(self, shape, token_db, durs, counts):
+        """The host fallback's shapes, one per row: `shape` (or none), with the points of each row's token gains - what
+        MiSession.synthesize_delivered(token_gain_db=) computes between run and delivery, from the same durations."""
+        from .session import Segment, Shape, token_bounds, token_gain_shapes, token_gains
+        n = len(counts)
+        shapes = [shape if shape is not None else Shape()] * n
+        if token_db is None:
+            return shapes
+        db = self._padded_db(token_db)
+        hop, ratio = self.session.hparam("hop"), self._ratio()
+        bounds = [token_bounds(durs[b], len(token_db[b]), hop, counts[b], ratio) for b in range(n)]
+        return token_gain_shapes([Segment(b) for b in range(n)], shapes, token_gains(db, *db.shape), bounds,
+                                 int(self.sample_rate * _GAIN_RAMP))
+
     @staticmethod
     def _cut_alignments(al, a: int, c: int):
         """A sentence's alignments after its audio was cut to [a, a + c): every phoneme's [start, start + num) shifted by -a
@@ -514,7 +565,8 @@ class TTSVoice:
     def synthesize_encoded(self, text: str, syn_config: Optional[SynthesisConfig] = None, encoding: str = "pcm16",
                            sentence_silence: float = 0.0, normalize_scope: str = "sentence",
                            alignments: bool = False, trim_silence=None, trailing_silence: float = 0.0, loudness=None,
-                           loudness_scope: str = "sentence", peak_ceiling: float = 0.0, max_gain_db: float = 30.0):
+                           loudness_scope: str = "sentence", peak_ceiling: float = 0.0, max_gain_db: float = 30.0,
+                           fade_in: float = 0.0, fade_out: float = 0.0, fade_curve: str = "linear", phoneme_gain_db=None):
         """Extension: the whole text as ONE stream of encoded audio ("pcm16", "ulaw", "alaw", "f32"; audio_encoding).  All
         sentences render in one batch; with a session that delivers (MiSession.synthesize_delivered) post-processing,
         encoding and the packing happen on the device and only the encoded audio crosses the bus; any other session
@@ -535,6 +587,13 @@ class TTSVoice:
         than 400 ms has no integrated loudness and keeps gain 1.  Measured on the device with a session that delivers, by
         audio_encoding.join_leveled otherwise (float64: the gains agree to meter accuracy, not bit for bit).  The result's
         `loudness` and `gain` hold what was measured and applied per sentence.
+        fade_in / fade_out (seconds; int(sample_rate * seconds) samples) ramp what is kept of every sentence up from and down
+        to exactly 0, along fade_curve "linear" or "smooth" - no step next to the silence of a pause.  phoneme_gain_db - a
+        callable (sentence_index, [the tokens of the sentence's groups, as phonemes_to_id_groups gives them]) -> one volume
+        in dB per group (-inf: silent; else within [-120, 36]): every phoneme is delivered at its own volume, with a ramp of
+        10 ms around each change.  Both are a time-varying volume in front of the clip (vitsmi.h, "shaped delivery"): on the
+        device with a session that delivers, by audio_encoding's shapes= otherwise - the same bytes; peaks, trimming and
+        loudness see the unshaped audio.  phoneme_gain_db needs a session that reports durations.
         Returns an audio_encoding.EncodedAudio."""
         from . import audio_encoding as ae
         from .sharding import pad_batch
@@ -545,13 +604,17 @@ class TTSVoice:
         lead = self._lead_samples(sentence_silence)
         trim = self._trim(trim_silence, trailing_silence)
         level = self._level(loudness, loudness_scope, peak_ceiling, max_gain_db, [cfg])
+        shape = self._shape(fade_in, fade_out, fade_curve)
         tail = trim.tail_samples if trim is not None else 0
         kept = loud = gains = None
         want_dur = alignments and hasattr(self.session, "last_durations") and hasattr(self.session, "synthesize_batch")
-        groups = self._sentence_groups(text, cfg) if want_dur else None
-        all_ids = [[i for _, ids in g for i in ids] for g in groups] if want_dur else self._sentence_ids(text, cfg)
+        if phoneme_gain_db is not None and not (hasattr(self.session, "synthesize_delivered") or hasattr(self.session, "synthesize_batch")):
+            raise ValueError("phoneme_gain_db needs a session that reports durations (synthesize_batch)")
+        groups = self._sentence_groups(text, cfg) if want_dur or phoneme_gain_db is not None else None
+        all_ids = [[i for _, ids in g for i in ids] for g in groups] if groups is not None else self._sentence_ids(text, cfg)
         if not all_ids:
             return ae.EncodedAudio(ae.silence(0, encoding), encoding, self.sample_rate, [], [], [] if want_dur else None)
+        token_db = None if phoneme_gain_db is None else [self._group_db(phoneme_gain_db, k, g) for k, g in enumerate(groups)]
         durs = frames = None
         if hasattr(self.session, "synthesize_delivered"):
             from .session import Segment
@@ -567,6 +630,10 @@ class TTSVoice:
             more = {} if trim is None else {"trim": trim}
             if level is not None:
                 more["levels"] = level
+            if shape is not None:
+                more["shapes"] = shape
+            if token_db is not None:
+                more["token_gain_db"], more["gain_ramp"] = self._padded_db(token_db), _GAIN_RAMP
             out = self.session.synthesize_delivered(ids, lens, self._scales(cfg), sid, segments=segs, n_streams=1,
                                                     encoding=encoding, return_durations=want_dur, **more)
             data = out["streams"][0]
@@ -578,19 +645,22 @@ class TTSVoice:
             if want_dur:
                 durs, frames = out["durations"], [int(f) for f in out["y_lengths"]]
         else:
+            need_dur = want_dur or token_db is not None
             if hasattr(self.session, "synthesize_batch"):
-                res = self.phoneme_ids_batch_to_audio(all_ids, cfg, return_durations=want_dur)
-                audios, durs = res if want_dur else (res, None)
+                res = self.phoneme_ids_batch_to_audio(all_ids, cfg, return_durations=need_dur)
+                audios, durs = res if need_dur else (res, None)
             else:
                 audios = [self.phoneme_ids_to_audio(ids, cfg) for ids in all_ids]
-            counts = [len(a) for a in audios]
+            counts = [len(np.atleast_1d(a)) for a in audios]
             norm = 0 if not cfg.normalize_audio else (2 if normalize_scope == "text" else 1)
+            # (without fades and gains: exactly the calls made before there were any)
+            more = {} if shape is None and token_db is None else {"shapes": self._row_shapes(shape, token_db, durs, counts)}
             if level is not None:
                 data, cut, loud, gains = ae.join_leveled([np.atleast_1d(a) for a in audios], self.sample_rate, level, encoding, lead,
-                                                         tail, trim, cfg.volume)
+                                                         tail, trim, cfg.volume, **more)
                 gains = [float(g) for g in gains]
             else:
-                data, cut = ae.join_trimmed([np.atleast_1d(a) for a in audios], encoding, lead, tail, trim, norm, cfg.volume)
+                data, cut = ae.join_trimmed([np.atleast_1d(a) for a in audios], encoding, lead, tail, trim, norm, cfg.volume, **more)
             kept = cut if trim is not None else None
         if kept is not None:
             counts = [c for _, c in kept]
@@ -706,7 +776,8 @@ class TTSVoice:
                                     seeds: Optional[Sequence[int]] = None, max_batch: int = 32, encoding: str = "pcm16",
                                     sentence_silence: float = 0.0, alignments: bool = False, trim_silence=None,
                                     trailing_silence: float = 0.0, loudness=None, loudness_scope: str = "sentence",
-                                    peak_ceiling: float = 0.0, max_gain_db: float = 30.0):
+                                    peak_ceiling: float = 0.0, max_gain_db: float = 30.0, fade_in: float = 0.0,
+                                    fade_out: float = 0.0, fade_curve: str = "linear", phoneme_gain_db=None):
         """Extension: synthesize_requests with every request's audio returned as one stream of encoded audio
         (audio_encoding.EncodedAudio; the pause of synthesize_encoded in front of each sentence).  The batching is
         synthesize_requests': sentences sorted by length, max_batch at a time, each with its request's settings and seed.
@@ -719,11 +790,15 @@ class TTSVoice:
         ("text": the request's sentences pooled); every request's config must say normalize_audio=False.  With scope
         "sentence" a session that delivers measures and levels on the device.  With scope "text" a request's sentences may
         render in different runs, so the device delivers them cut but unlevelled as float32 and the host levels them
-        (audio_encoding.level_rows)."""
+        (audio_encoding.level_rows).  fade_in / fade_out / fade_curve / phoneme_gain_db as in synthesize_encoded, for every
+        sentence of every request (phoneme_gain_db's sentence_index counts within its request); with loudness scope "text"
+        the host that levels applies them too (audio_encoding.shape_multiplier)."""
         from . import audio_encoding as ae
         ae._check(encoding)
         lead = self._lead_samples(sentence_silence)
         trim = self._trim(trim_silence, trailing_silence)
+        shape = self._shape(fade_in, fade_out, fade_curve)
+        shaped = shape is not None or phoneme_gain_db is not None
         level = self._level(loudness, loudness_scope, peak_ceiling, max_gain_db,
                             [cfg if cfg is not None else SynthesisConfig() for _, cfg in requests])
         tail = trim.tail_samples if trim is not None else 0
@@ -745,23 +820,61 @@ class TTSVoice:
             return ae.EncodedAudio(data, encoding, self.sample_rate, starts, [len(p) for p in pieces], aligns,
                                    None if loud is None else [float(v) for v in loud], None if gains is None else [float(g) for g in gains])
 
-        def level_on_host(rows, volume):
-            """a request's kept rows (float32, unlevelled) -> (encoded pieces, loudness, gains)"""
+        def level_on_host(rows, volume, muls=None):
+            """a request's kept rows (float32, unlevelled) -> (encoded pieces, loudness, gains); muls: their shapes' multipliers"""
             loud, gains = ae.level_rows(rows, self.sample_rate, level)
-            return [ae.encode(ae.leveled(v, g, volume), encoding) for v, g in zip(rows, gains)], loud, gains
+            muls = muls if muls is not None else [None] * len(rows)
+            return [ae.encode(ae.leveled(v, g, volume, m), encoding) for v, g, m in zip(rows, gains, muls)], loud, gains
+
+        def request_db(r, text, cfg):
+            """the dB per phoneme id of every sentence of request r, or None"""
+            if phoneme_gain_db is None:
+                return None
+            return [self._group_db(phoneme_gain_db, k, g) for k, g in enumerate(self._sentence_groups(text, cfg))]
 
         if not hasattr(self.session, "synthesize_delivered"):
             want_al = lambda cs: alignments and all(c.phoneme_alignments is not None for c in cs)
+            durs = {} if phoneme_gain_db is not None else None
+            more = {} if durs is None else {"_durations": durs}
+
+            def host_shapes(r, text, cfg, cs):
+                """request r's shapes, one per sentence (None: nothing shapes)"""
+                if not shaped:
+                    return None
+                db = request_db(r, text, cfg)
+                return self._row_shapes(shape, db, None if db is None else [durs[r, k] for k in range(len(cs))],
+                                        [len(c.audio_float_array) for c in cs])
+
             if level is not None:
-                chunks = self.synthesize_requests(requests, seeds=seeds, max_batch=max_batch, alignments=alignments, postprocess=False)
+                chunks = self.synthesize_requests(requests, seeds=seeds, max_batch=max_batch, alignments=alignments, postprocess=False,
+                                                  **more)
                 result = []
-                for (_, cfg), cs in zip(requests, chunks):
+                for r, ((text, cfg), cs) in enumerate(zip(requests, chunks)):
                     cfg = cfg if cfg is not None else SynthesisConfig()
                     kept = [ae.trim_range(c.audio_float_array, len(c.audio_float_array), trim) for c in cs]
                     rows = [np.asarray(c.audio_float_array, np.float32)[a:a + n] for c, (a, n) in zip(cs, kept)]
-                    pieces, loud, gains = level_on_host(rows, cfg.volume)
+                    shapes = host_shapes(r, text, cfg, cs)
+                    muls = None if shapes is None else [ae.shape_multiplier(a, n, sh) for (a, n), sh in zip(kept, shapes)]
+                    pieces, loud, gains = level_on_host(rows, cfg.volume, muls)
                     result.append(join(pieces, [c.phoneme_alignments for c in cs] if want_al(cs) else None,
                                        kept if trim is not None else None, loud, gains))
+                return result
+            if shaped:
+                # the rows as rendered, each cut (or whole), shaped in front of the clip
+                chunks = self.synthesize_requests(requests, seeds=seeds, max_batch=max_batch, alignments=alignments, postprocess=False,
+                                                  **more)
+                result = []
+                for r, ((text, cfg), cs) in enumerate(zip(requests, chunks)):
+                    cfg = cfg if cfg is not None else SynthesisConfig()
+                    shapes = host_shapes(r, text, cfg, cs)
+                    pieces, kept = [], []
+                    for c, sh in zip(cs, shapes):
+                        data, k = ae.join_trimmed([c.audio_float_array], encoding, 0, 0, trim, 1 if cfg.normalize_audio else 0,
+                                                  cfg.volume, shapes=[sh])
+                        pieces.append(data)
+                        kept += k
+                    result.append(join(pieces, [c.phoneme_alignments for c in cs] if want_al(cs) else None,
+                                       kept if trim is not None else None))
                 return result
             if trim is None:
                 chunks = self.synthesize_requests(requests, seeds=seeds, max_batch=max_batch, alignments=alignments)
@@ -794,15 +907,17 @@ class TTSVoice:
         from .session import Segment
         from .sharding import pad_batch
         want_dur = alignments and hasattr(self.session, "last_durations")
-        rows, groups = [], {}
+        rows, groups, db_of = [], {}, {}
         for r, ((text, _), cfg) in enumerate(zip(requests, cfgs)):
-            if want_dur:
+            if want_dur or phoneme_gain_db is not None:
                 for k, g in enumerate(self._sentence_groups(text, cfg)):
                     groups[r, k] = g
                     rows.append((r, k, [i for _, ids in g for i in ids]))
+                    if phoneme_gain_db is not None:
+                        db_of[r, k] = self._group_db(phoneme_gain_db, k, g)
             else:
                 rows.extend((r, k, ids) for k, ids in enumerate(self._sentence_ids(text, cfg)))
-        piece, aligned, kept_of, level_of = {}, {}, {}, {}
+        piece, aligned, kept_of, level_of, mul_of = {}, {}, {}, {}, {}
         hop = self.session.hparam("hop")
         order = sorted(range(len(rows)), key=lambda i: len(rows[i][2]))  # (stable: equal lengths keep request order)
         for c0 in range(0, len(order), max_batch):
@@ -818,9 +933,24 @@ class TTSVoice:
             more = {} if trim is None else {"trim": dataclasses.replace(trim, tail_samples=0)}
             if level is not None and not host_level:
                 more["levels"] = level
+            # (scope "text": the host levels the float32 rows and shapes them there - the shape comes behind the gain)
+            if shaped and not host_level:
+                if shape is not None:
+                    more["shapes"] = shape
+                if phoneme_gain_db is not None:
+                    more["token_gain_db"], more["gain_ramp"] = self._padded_db([db_of[r, k] for r, k, _ in run]), _GAIN_RAMP
+            need_dur = want_dur or (host_level and phoneme_gain_db is not None)
             out = self.session.synthesize_delivered(ids, lens, scales, sid, segments=segs, n_streams=len(run),
                                                     encoding="f32" if host_level else encoding, seeds=row_seeds,
-                                                    return_durations=want_dur, **more)
+                                                    return_durations=need_dur, **more)
+            if shaped and host_level:
+                counts = [int(n) for n in out["sample_lengths"]]
+                run_shapes = self._row_shapes(shape, None if phoneme_gain_db is None else [db_of[r, k] for r, k, _ in run],
+                                              None if phoneme_gain_db is None else [out["durations"][b, :len(i)] for b, (_, _, i) in enumerate(run)],
+                                              counts)
+                for b, (r, k, _) in enumerate(run):
+                    a, c = (int(out["kept_first"][b]), int(out["kept_count"][b]))
+                    mul_of[r, k] = ae.shape_multiplier(a, c, run_shapes[b])
             for b, (r, k, _) in enumerate(run):
                 piece[r, k] = out["streams"][b]
                 if level is not None and not host_level:
@@ -837,7 +967,7 @@ class TTSVoice:
         for r, keys in enumerate(per_request):
             pieces, loud, gains = [piece[key] for key in keys], None, None
             if level is not None and level.mode == 2:
-                pieces, loud, gains = level_on_host(pieces, cfgs[r].volume)
+                pieces, loud, gains = level_on_host(pieces, cfgs[r].volume, [mul_of[key] for key in keys] if shaped else None)
             elif level is not None:
                 loud, gains = [level_of[key][0] for key in keys], [level_of[key][1] for key in keys]
             result.append(join(pieces, [aligned[key] for key in keys] if want_dur else None,
