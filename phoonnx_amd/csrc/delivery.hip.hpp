@@ -180,18 +180,24 @@ __global__ __launch_bounds__(kDeliveryThreads) void delivery_pack_kernel(const f
     if (cell * E < P) packed[cell] = tile[threadIdx.x];
 }
 
+// what every delivery launches in front of its pack: the peak launch on `st` where a segment normalises (a sample per lane, up
+// to 256 workgroups a row) -> the pack launch's grid, plain or shaped (shape.hip.hpp)
+inline dim3 launch_delivery_peaks(const float *x, const DeliveryPlan &p, const DeliverySeg *d_segs, unsigned *d_peak, hipStream_t st) {
+    if (p.any_norm) {
+        int gx = (p.max_n + kDeliveryThreads - 1) / kDeliveryThreads;
+        gx = gx > 256 ? 256 : (gx < 1 ? 1 : gx);
+        delivery_peak_kernel<<<dim3(gx, (unsigned)p.segs.size()), kDeliveryThreads, 0, st>>>(x, d_segs, d_peak);
+    }
+    const int64_t per = (int64_t)kDeliveryThreads * (16 / p.width);
+    return dim3((unsigned)((p.packed_elems + per - 1) / per));
+}
+
 // both launches on `st`; peak_bits [2B] must read 0 (the caller's memset in front).  P > 0.
 inline hipError_t launch_delivery(const float *x, const DeliveryPlan &p, const DeliverySeg *d_segs, unsigned *d_peak, void *d_packed,
                                   hipStream_t st) {
     const int G = (int)p.segs.size();
-    if (p.any_norm) {
-        int gx = (p.max_n + kDeliveryThreads - 1) / kDeliveryThreads;
-        gx = gx > 256 ? 256 : (gx < 1 ? 1 : gx);
-        delivery_peak_kernel<<<dim3(gx, G), kDeliveryThreads, 0, st>>>(x, d_segs, d_peak);
-    }
     const int64_t P = p.packed_elems;
-    const int64_t per = (int64_t)kDeliveryThreads * (16 / p.width);
-    const dim3 grid((unsigned)((P + per - 1) / per));
+    const dim3 grid = launch_delivery_peaks(x, p, d_segs, d_peak, st);
     uint4 *out = static_cast<uint4 *>(d_packed);
     switch (p.encoding) {
         case VITS_ENC_PCM16: delivery_pack_kernel<VITS_ENC_PCM16><<<grid, kDeliveryThreads, 0, st>>>(x, d_segs, G, d_peak, P, out); break;

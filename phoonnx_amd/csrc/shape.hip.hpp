@@ -91,14 +91,8 @@ __global__ __launch_bounds__(kDeliveryThreads) void delivery_pack_shaped_kernel(
 inline hipError_t launch_delivery_shaped(const float *x, const DeliveryPlan &p, const DeliverySeg *d_segs, unsigned *d_peak, void *d_packed,
                                          const ShapeSeg *d_shapes, const ShapeKnot *d_knots, hipStream_t st) {
     const int G = (int)p.segs.size();
-    if (p.any_norm) {  // (launch_delivery's grid)
-        int gx = (p.max_n + kDeliveryThreads - 1) / kDeliveryThreads;
-        gx = gx > 256 ? 256 : (gx < 1 ? 1 : gx);
-        delivery_peak_kernel<<<dim3(gx, G), kDeliveryThreads, 0, st>>>(x, d_segs, d_peak);
-    }
     const int64_t P = p.packed_elems;
-    const int64_t per = (int64_t)kDeliveryThreads * (16 / p.width);
-    const dim3 grid((unsigned)((P + per - 1) / per));
+    const dim3 grid = launch_delivery_peaks(x, p, d_segs, d_peak, st);
     uint4 *out = static_cast<uint4 *>(d_packed);
 #define VITSMI_SHAPED(ENC) \
     delivery_pack_shaped_kernel<ENC><<<grid, kDeliveryThreads, 0, st>>>(x, d_segs, G, d_peak, P, out, d_shapes, d_knots)

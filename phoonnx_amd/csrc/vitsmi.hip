@@ -25,6 +25,7 @@
 #include "attention16.hip.hpp"
 #include "conv_sx_small.hip.hpp"
 #include "delivery.hip.hpp"
+#include "delivery_run.hip.hpp"
 #include "shape.hip.hpp"
 #include "kernels.hip.hpp"
 #include "loudness.hip.hpp"
@@ -2613,12 +2614,8 @@ int vits_reserve(vits_handle *h, int B, int T, int F) {
         // ... or vits_deliver's, with vits_deliver_trimmed's slots, vits_deliver_leveled's buffers and vits_deliver_shaped's
         // tables behind them (two breakpoints per token: what a per-token gain needs at most)
         const int64_t shape_pts = std::min<int64_t>((int64_t)2 * B * T, kShapeMaxPoints) + B;  // (knots: a segment's points + 1)
-        const size_t io_dlv = carved_bytes([&](Carver &cv) {
-            carve_delivery(cv, B, F * m.hop);
-            carve_trim(cv, B);
-            carve_level(cv, B, F * m.hop);
-            carve_shape(cv, B, shape_pts);
-        });
+        const DeliveryNeeds all{/*scan=*/true, /*levelled=*/true, /*shaped=*/true, shape_pts};
+        const size_t io_dlv = carved_bytes([&](Carver &cv) { carve_delivery_call(cv, B, F * m.hop, all); });
         // ... or an encoded stream's chunk buffer: every chunk_frames <= F, i.e. chunks of up to F * hop samples
         const size_t io_sp = carved_bytes([&](Carver &cv) { carve_stream_pack(cv, B, (int64_t)F * m.hop); });
         size_t io = io_in > io_pcm ? io_in : io_pcm;
@@ -2636,10 +2633,8 @@ int vits_reserve(vits_handle *h, int B, int T, int F) {
             // (a trimmed delivery's slots and a levelled one's buffers lie behind the resampled result too: in the place of
             // an encoded stream's buffers)
             const size_t io_rt = carved_bytes([&](Carver &cv) {
-                carve_resample(cv, B, (int)so, (int)h->rs.plan.K);
-                carve_trim(cv, B);
-                carve_level(cv, B, (int)so);
-                carve_shape(cv, B, shape_pts);
+                const DeliveryBufs front = carve_resample(cv, B, (int)so, (int)h->rs.plan.K).dlv;
+                carve_delivery_call(cv, B, (int)so, all, &front);
             });
             io = io_rt > io ? io_rt : io;
         }
@@ -3070,15 +3065,24 @@ int vits_last_pcm16(vits_handle *h, int normalize, float volume, int16_t *out, s
 // ---- delivery (vitsmi.h, "delivery"): the plan on the host (delivery.hpp), two launches (delivery.hip.hpp), one copy per
 // silence-free run of segments, the silence filled in here while the copies run
 
-int vits_delivery_plan(const int64_t *counts, int B, const vits_segment *segs, int n_segs, int n_streams, int encoding,
-                       int64_t *stream_samples, int64_t *stream_offsets, int64_t *total_bytes) {
+// the layout of a plan over counts [B] (the rows' valid samples, or what is kept of them), with the trims' and the levels'
+// validation where they are given: the three plan exports
+static int plan_layout(const int64_t *counts, int B, const vits_segment *segs, const vits_trim *trims, const vits_level *levels, int n_segs,
+                       int n_streams, int encoding, int sample_rate, int64_t *stream_samples, int64_t *stream_offsets,
+                       int64_t *total_bytes) {
     DeliveryPlan p;
-    const std::string e = delivery_plan(counts, B, 0, segs, n_segs, n_streams, encoding, p);
+    std::string e = delivery_plan(counts, B, 0, segs, n_segs, n_streams, encoding, p, trims);
+    if (e.empty()) e = level_plan_fault(segs, levels, n_segs, n_streams, sample_rate);
     if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
     for (int j = 0; j < n_streams && stream_samples; j++) stream_samples[j] = p.stream_samples[j];
     for (int j = 0; j <= n_streams && stream_offsets; j++) stream_offsets[j] = p.stream_offsets[j];
     if (total_bytes) *total_bytes = p.total_bytes;
     return VITS_OK;
+}
+
+int vits_delivery_plan(const int64_t *counts, int B, const vits_segment *segs, int n_segs, int n_streams, int encoding,
+                       int64_t *stream_samples, int64_t *stream_offsets, int64_t *total_bytes) {
+    return plan_layout(counts, B, segs, nullptr, nullptr, n_segs, n_streams, encoding, 0, stream_samples, stream_offsets, total_bytes);
 }
 
 int vits_trim_range(int64_t n, int64_t first_active, int64_t last_active, const vits_trim *t, int64_t *a, int64_t *c) {
@@ -3094,13 +3098,7 @@ int vits_trim_range(int64_t n, int64_t first_active, int64_t last_active, const 
 
 int vits_delivery_plan_trimmed(const int64_t *kept, int B, const vits_segment *segs, const vits_trim *trims, int n_segs, int n_streams,
                                int encoding, int64_t *stream_samples, int64_t *stream_offsets, int64_t *total_bytes) {
-    DeliveryPlan p;
-    const std::string e = delivery_plan(kept, B, 0, segs, n_segs, n_streams, encoding, p, trims);
-    if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
-    for (int j = 0; j < n_streams && stream_samples; j++) stream_samples[j] = p.stream_samples[j];
-    for (int j = 0; j <= n_streams && stream_offsets; j++) stream_offsets[j] = p.stream_offsets[j];
-    if (total_bytes) *total_bytes = p.total_bytes;
-    return VITS_OK;
+    return plan_layout(kept, B, segs, trims, nullptr, n_segs, n_streams, encoding, 0, stream_samples, stream_offsets, total_bytes);
 }
 
 int vits_loudness_filter(int sample_rate, double *coef, int32_t *hop) {
@@ -3141,14 +3139,7 @@ int vits_level_gain(double L, float peak, const vits_level *level, float *gain) 
 int vits_delivery_plan_leveled(const int64_t *kept, int B, const vits_segment *segs, const vits_trim *trims, const vits_level *levels,
                                int n_segs, int n_streams, int encoding, int sample_rate, int64_t *stream_samples,
                                int64_t *stream_offsets, int64_t *total_bytes) {
-    DeliveryPlan p;
-    std::string e = delivery_plan(kept, B, 0, segs, n_segs, n_streams, encoding, p, trims);
-    if (e.empty()) e = level_plan_fault(segs, levels, n_segs, n_streams, sample_rate);
-    if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
-    for (int j = 0; j < n_streams && stream_samples; j++) stream_samples[j] = p.stream_samples[j];
-    for (int j = 0; j <= n_streams && stream_offsets; j++) stream_offsets[j] = p.stream_offsets[j];
-    if (total_bytes) *total_bytes = p.total_bytes;
-    return VITS_OK;
+    return plan_layout(kept, B, segs, trims, levels, n_segs, n_streams, encoding, sample_rate, stream_samples, stream_offsets, total_bytes);
 }
 
 int vits_shape_check(const vits_shape *shapes, int n_segs, const vits_env_point *points, int64_t n_points) {
@@ -3175,55 +3166,6 @@ int vits_shape_gain(const vits_shape *shape, const vits_env_point *points, int64
     return VITS_OK;
 }
 
-// what a shaped delivery adds to the enqueue: the records of the plan's segments and their knots (host), and carve_shape's
-// buffers they go to.  The vectors are the pageable sources of copies: they outlive the caller's wait.
-struct ShapeJob {
-    std::vector<ShapeSeg> table;
-    std::vector<ShapeKnot> knots;
-    ShapeBufs sb{};
-};
-
-// the job of a finished plan p (over the kept ranges first / kept [B]); shapes have passed shape_fault
-static void shape_job(const DeliveryPlan &p, const vits_segment *segs, const vits_shape *shapes, const vits_env_point *points,
-                      const std::vector<int64_t> &first, const std::vector<int64_t> &kept, ShapeJob &job) {
-    std::vector<int64_t> a(p.order.size()), c(p.order.size());
-    for (size_t k = 0; k < p.order.size(); k++) {
-        const int row = segs[p.order[k]].row;
-        a[k] = first[row];
-        c[k] = kept[row];
-    }
-    shape_table(shapes, p.order, a.data(), c.data(), job.table);
-    shape_knots(job.table, points, job.knots);
-}
-
-// Everything a delivery puts on the stream: segment table up, peaks cleared, the launches, the copies into dst; then the
-// silence, on the host.  The caller synchronises.  db: carve_delivery's buffers for a waveform of at least the plan's rows.
-// job: a shaped delivery's tables (nullptr: none - launch_delivery, as ever).
-static hipError_t delivery_enqueue(const float *d_x, const DeliveryPlan &p, const DeliveryBufs &db, int B, hipStream_t st, void *dst,
-                                   const ShapeJob *job = nullptr) {
-    hipError_t e = hipSuccess;
-    if (p.packed_elems > 0) {
-        e = hipMemcpyAsync(db.segs, p.segs.data(), p.segs.size() * sizeof(DeliverySeg), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && p.any_norm) e = hipMemsetAsync(db.peak, 0, 2 * (size_t)B * sizeof(unsigned), st);
-        if (job) {
-            if (e == hipSuccess) e = hipMemcpyAsync(job->sb.segs, job->table.data(), job->table.size() * sizeof(ShapeSeg), hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) e = hipMemcpyAsync(job->sb.knots, job->knots.data(), job->knots.size() * sizeof(ShapeKnot), hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) e = launch_delivery_shaped(d_x, p, db.segs, db.peak, db.packed, job->sb.segs, job->sb.knots, st);
-        } else if (e == hipSuccess)
-            e = launch_delivery(d_x, p, db.segs, db.peak, db.packed, st);
-        for (size_t i = 0; i < p.copies.size() && e == hipSuccess; i++)
-            e = hipMemcpyAsync(static_cast<char *>(dst) + p.copies[i].dst_off, db.packed + p.copies[i].packed_off,
-                               (size_t)p.copies[i].bytes, hipMemcpyDeviceToHost, st);
-    }
-    delivery_silence(p, dst);
-    return e;
-}
-
-static void delivery_report(const DeliveryPlan &p, int64_t *stream_samples, int64_t *stream_offsets) {
-    for (size_t j = 0; j < p.stream_samples.size() && stream_samples; j++) stream_samples[j] = p.stream_samples[j];
-    for (size_t j = 0; j < p.stream_offsets.size() && stream_offsets; j++) stream_offsets[j] = p.stream_offsets[j];
-}
-
 // the valid samples of the rows of a run that can be delivered: frames * hop, or their count at the rate the run was
 // resampled to
 static int delivery_counts(vits_handle *h, std::vector<int64_t> &counts) {
@@ -3237,297 +3179,81 @@ static int delivery_counts(vits_handle *h, std::vector<int64_t> &counts) {
     return 0;
 }
 
-int vits_deliver(vits_handle *h, const vits_segment *segs, int n_segs, int n_streams, int encoding, void *dst, size_t dst_bytes,
-                 int64_t *stream_samples, int64_t *stream_offsets) {
+// The handle's side of every delivery (the sequence: delivery_run.hip.hpp): the last run's waveform and its rows' valid
+// samples, the call's buffers from the staging slab, the range check behind the call's first wait.
+static int deliver_last_run(vits_handle *h, const DeliveryRequest &rq, const DeliveryOutputs &out) {
     if (int rc = check_dev(h)) return rc;
     std::lock_guard<std::mutex> lk(h->mu);
     const int B = h->B, S = h->S;
     if (!h->d_out || B <= 0 || S <= 0 || (!h->last_vocoder && (int)h->h_ylen.size() != B))
         return fail(h, VITS_E_ARG, "no completed run to deliver");
-    const bool rs = h->out_resampled;
     std::vector<int64_t> counts;
     if (int rc = delivery_counts(h, counts)) return rc;
-    DeliveryPlan p;
-    const std::string e = delivery_plan(counts.data(), B, S, segs, n_segs, n_streams, encoding, p);
-    if (!e.empty()) return fail(h, VITS_E_ARG, "%s", e.c_str());
-    if (!dst) {  // the layout only: nothing is enqueued, nothing waited for
-        delivery_report(p, stream_samples, stream_offsets);
-        return VITS_OK;
-    }
-    if (dst_bytes < (size_t)p.total_bytes)
-        return fail(h, VITS_E_ARG, "delivery buffer too small: %zu bytes, %lld needed", dst_bytes, (long long)p.total_bytes);
-    // the staging slab is idle between runs; a resampled waveform lives in it, and its walk carved these buffers behind it
-    DeliveryBufs db{};
-    if (rs) {
-        const int K = h->rs_run_K;
-        if (int rc = slab_carve(h, h->io, "staging", [&](Carver &cv) { db = carve_resample(cv, B, S, K).dlv; })) return rc;
-        if (!h->d_out) return fail(h, VITS_E_ARG, "no completed run to deliver");
-    } else if (int rc = slab_carve(h, h->io, "staging", [&](Carver &cv) { db = carve_delivery(cv, B, S); }))
-        return rc;
-    hipStream_t st = h->stream;
-    hipError_t err = delivery_enqueue(h->d_out, p, db, B, st, dst);
-    if (err == hipSuccess) err = hipStreamSynchronize(st);
-    else hipStreamSynchronize(st);
-    if (err != hipSuccess) return fail(h, VITS_E_DEVICE, "delivery failed: %s", hipGetErrorString(err));
-    if (int rc = range_check(h)) return rc;  // (after vits_run_async this is the first synchronisation of that run)
-    if (h->range_failed) return fail(h, VITS_E_RANGE, "the last run left the range of the fp16 operand planes (see vits_get_stats)");
-    delivery_report(p, stream_samples, stream_offsets);
-    return VITS_OK;
+    auto bufs = [&](const DeliveryNeeds &need, const float *&d_x, DeliveryCallBufs &cb) -> DeliveryStatus {
+        if (need.levelled && h->rs.plan.on() && rq.sample_rate != h->rs.plan.fo)
+            return delivery_refusal(VITS_E_ARG, "sample_rate %d differs from the output rate %d", rq.sample_rate, (int)h->rs.plan.fo);
+        // the staging slab is idle between runs; a resampled waveform lives in it, and its walk carved these buffers behind it
+        if (h->out_resampled) {
+            // (the run's own walk ends with carve_resample, or with an encoded stream's buffers behind it; the trim slots behind
+            // carve_resample are at most 12 B + 512 bytes more than the former.  Growing the slab here would drop the waveform that
+            // lives in it - the check below - and does not happen: slab_reserve allocates 1 MiB above every request, and
+            // vits_reserve counts this walk.  A levelled delivery's buffers - some 0.05 bytes a sample - fit into the quarter a
+            // growing slab adds to every request; where a slab does not hold them the call is refused and the run stays
+            // deliverable.)
+            const int K = h->rs_run_K;
+            auto walk = [&](Carver &cv) {
+                const DeliveryBufs front = carve_resample(cv, B, S, K).dlv;
+                cb = carve_delivery_call(cv, B, S, need, &front);
+            };
+            if ((need.levelled || need.shaped) && carved_bytes(walk) > h->io.cap)
+                return delivery_refusal(VITS_E_NOMEM,
+                                        "a levelled or shaped delivery of this run needs %zu bytes of staging, %zu are there: vits_reserve covers it",
+                                        carved_bytes(walk), h->io.cap);
+            if (int rc = slab_carve(h, h->io, "staging", walk)) return {rc, h->err};
+            if (!h->d_out) return delivery_refusal(VITS_E_ARG, "no completed run to deliver");
+        } else if (int rc = slab_carve(h, h->io, "staging", [&](Carver &cv) { cb = carve_delivery_call(cv, B, S, need); }))
+            return {rc, h->err};
+        d_x = h->d_out;
+        return {};
+    };
+    auto waited = [&]() -> DeliveryStatus {  // (after vits_run_async this is the first synchronisation of that run)
+        if (int rc = range_check(h)) return {rc, h->err};
+        if (h->range_failed)
+            return delivery_refusal(VITS_E_RANGE, "the last run left the range of the fp16 operand planes (see vits_get_stats)");
+        return {};
+    };
+    const DeliveryStatus s = delivery_run(counts.data(), B, S, h->stream, rq, out, bufs, waited);
+    return s.code ? fail(h, s.code, "%s", s.msg.c_str()) : VITS_OK;
 }
 
-// ---- trimmed delivery (vitsmi.h, "trimmed delivery"): the scan in front of the delivery, the kept ranges and the plan
-// over them on the host in between
-
-// The scan of the plan p0 (over the whole rows) and the wait for it: first / kept [B] receive every row's kept range (rows
-// outside the plan, and segments whose trim is off: the whole row).  Waits whatever happened: the tables are the pageable
-// sources of copies that may be in flight.
-static hipError_t trim_scan(const float *d_x, const DeliveryPlan &p0, const vits_segment *segs, const vits_trim *trims, const int64_t *counts,
-                            int B, const DeliveryBufs &db, const TrimBufs &tb, hipStream_t st, std::vector<int64_t> &first,
-                            std::vector<int64_t> &kept) {
-    first.assign(B, 0);
-    kept.assign(counts, counts + B);
-    const int G = (int)p0.segs.size();
-    std::vector<DeliverySeg> scan(p0.segs);
-    std::vector<int32_t> bounds(2 * (size_t)G);
-    bool any = false, any_rel = false;
-    for (int k = 0; k < G && trims; k++) {
-        const vits_trim &t = trims[p0.order[k]];
-        scan[k].peak = t.mode == 2 ? k : -1;
-        scan[k].volume = t.threshold;
-        scan[k].pad = t.mode;
-        bounds[2 * k] = INT_MAX;
-        bounds[2 * k + 1] = -1;
-        any = any || t.mode != 0;
-        any_rel = any_rel || t.mode == 2;
-    }
-    hipError_t e = hipSuccess;
-    if (any && p0.max_n > 0) {  // (rows without samples keep their presets: none active)
-        e = hipMemcpyAsync(db.segs, scan.data(), (size_t)G * sizeof(DeliverySeg), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(tb.bounds, bounds.data(), bounds.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && any_rel) e = hipMemsetAsync(tb.peak_all, 0, (size_t)G * sizeof(unsigned), st);
-        if (e == hipSuccess) e = launch_trim_scan(d_x, db.segs, G, p0.max_n, any_rel, tb.peak_all, tb.bounds, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(bounds.data(), tb.bounds, bounds.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-    }
-    const hipError_t done = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = done;
-    if (e != hipSuccess || !any) return e;
-    for (int k = 0; k < G; k++) {
-        const int g = p0.order[k], row = segs[g].row;
-        trim_range(counts[row], bounds[2 * k], bounds[2 * k + 1], trims[g], first[row], kept[row]);
-    }
-    return hipSuccess;
-}
-
-static void trim_report(const vits_segment *segs, int n_segs, const std::vector<int64_t> &first, const std::vector<int64_t> &kept,
-                        int64_t *kept_first, int64_t *kept_count) {
-    for (int g = 0; g < n_segs; g++) {
-        if (kept_first) kept_first[g] = first[segs[g].row];
-        if (kept_count) kept_count[g] = kept[segs[g].row];
-    }
-}
-
-// ---- levelled delivery (vitsmi.h, "levelled delivery"): the measurement between the kept ranges and the delivery
-
-static bool any_level(const vits_level *levels, int n_segs) {
-    for (int g = 0; g < n_segs && levels; g++)
-        if (levels[g].mode != 0) return true;
-    return false;
-}
-
-// The loudness and peak launches over the plan p (over the kept ranges), the copy of energies and peaks, the wait, then
-// gates and gains on the host: loud / gain [n_segs] in the caller's order (mode 0: NaN / 1).  Waits whatever happened: the
-// tables are the pageable sources of copies that may be in flight.
-static hipError_t level_measure(const float *d_x, const DeliveryPlan &p, const vits_segment *segs, const vits_level *levels, int n_segs,
-                                int n_streams, int sample_rate, const DeliveryBufs &db, const LevelBufs &lb, hipStream_t st,
-                                std::vector<double> &loud, std::vector<float> &gain) {
-    loud.assign(n_segs, std::numeric_limits<double>::quiet_NaN());
-    gain.assign(n_segs, 1.0f);
-    if (!any_level(levels, n_segs)) return hipSuccess;
-    const LoudCoef k = loudness_coef(sample_rate);
-    const int G = (int)p.segs.size();
-    std::vector<DeliverySeg> table(p.segs);  // the peak launch's: slot k for a levelled segment
-    std::vector<LoudSeg> ls;                 // the loudness launches': the levelled segments only
-    std::vector<int> ls_k;                   // ... and which of the plan's each one is
-    std::vector<int32_t> n_sub(G, 0);
-    int64_t chunks = 0, subs = 0;
-    int max_n = 0;
-    for (int kk = 0; kk < G; kk++) {
-        table[kk].peak = -1;
-        if (levels[p.order[kk]].mode == 0) continue;
-        table[kk].peak = kk;
-        n_sub[kk] = p.segs[kk].n / k.hop;
-        LoudSeg s{};
-        s.src = p.segs[kk].src;
-        s.chunk0 = chunks;
-        s.sub0 = subs;
-        s.n = n_sub[kk] * k.hop;
-        chunks += ((int64_t)s.n + kLoudChunk - 1) / kLoudChunk;
-        subs += n_sub[kk];
-        max_n = s.n > max_n ? s.n : max_n;
-        ls.push_back(s);
-        ls_k.push_back(kk);
-    }
-    if ((size_t)chunks > lb.n_chunks || (size_t)subs > lb.n_subs || (size_t)G > lb.n_peaks) return hipErrorInvalidValue;  // (cannot happen: carve_level)
-    std::vector<unsigned> result(lb.n_peaks + (size_t)subs, 0u);
-    hipError_t e = hipSuccess;
-    if (p.max_n > 0) {  // (segments without samples: peak 0, no sub-blocks)
-        e = hipMemcpyAsync(db.segs, table.data(), (size_t)G * sizeof(DeliverySeg), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemsetAsync(lb.result, 0, lb.n_peaks * sizeof(unsigned), st);
-        if (e == hipSuccess) e = launch_level_peaks(d_x, db.segs, G, p.max_n, lb.result, st);
-        if (e == hipSuccess && max_n > 0) {
-            e = hipMemcpyAsync(lb.segs, ls.data(), ls.size() * sizeof(LoudSeg), hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) e = launch_loudness(d_x, lb.segs, (int)ls.size(), max_n, k, lb.fin, lb.init, lb.part, lb.e(), st);
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(result.data(), lb.result, result.size() * sizeof(unsigned), hipMemcpyDeviceToHost, st);
-    }
-    const hipError_t done = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = done;
-    if (e != hipSuccess) return e;
-    const float *peaks = reinterpret_cast<const float *>(result.data());
-    const float *en = peaks + lb.n_peaks;
-    // mode 1: a segment by itself
-    for (size_t i = 0; i < ls.size(); i++) {
-        const int kk = ls_k[i], g = p.order[kk];
-        if (levels[g].mode != 1) continue;
-        loud[g] = loudness_gate(en + ls[i].sub0, &n_sub[kk], 1, k.hop).L;
-        gain[g] = level_gain(loud[g], peaks[kk], levels[g]);
-    }
-    // mode 2: the stream's mode-2 segments pooled (the plan's order within a stream is the caller's)
-    for (int j = 0; j < n_streams; j++) {
-        std::vector<float> pool;
-        std::vector<int32_t> pool_n;
-        float peak = 0.f;
-        int lead = -1;
-        for (size_t i = 0; i < ls.size(); i++) {
-            const int kk = ls_k[i], g = p.order[kk];
-            if (levels[g].mode != 2 || segs[g].stream != j) continue;
-            lead = lead < 0 ? g : lead;
-            pool.insert(pool.end(), en + ls[i].sub0, en + ls[i].sub0 + n_sub[kk]);
-            pool_n.push_back(n_sub[kk]);
-            peak = fmaxf(peak, peaks[kk]);
-        }
-        if (lead < 0) continue;
-        const double L = loudness_gate(pool.data(), pool_n.data(), (int)pool_n.size(), k.hop).L;
-        const float gn = level_gain(L, peak, levels[lead]);
-        for (int g = 0; g < n_segs; g++)
-            if (levels[g].mode == 2 && segs[g].stream == j) {
-                loud[g] = L;
-                gain[g] = gn;
-            }
-    }
-    return hipSuccess;
-}
-
-static void level_report(int n_segs, const std::vector<double> &loud, const std::vector<float> &gn, double *loudness, float *gain) {
-    for (int g = 0; g < n_segs; g++) {
-        if (loudness) loudness[g] = loud[g];
-        if (gain) gain[g] = gn[g];
-    }
+int vits_deliver(vits_handle *h, const vits_segment *segs, int n_segs, int n_streams, int encoding, void *dst, size_t dst_bytes,
+                 int64_t *stream_samples, int64_t *stream_offsets) {
+    return deliver_last_run(h, {segs, nullptr, nullptr, nullptr, nullptr, 0, n_segs, n_streams, encoding, 0, dst, dst_bytes, /*kept=*/false},
+                            {stream_samples, stream_offsets, nullptr, nullptr, nullptr, nullptr});
 }
 
 // vits_deliver_trimmed, vits_deliver_leveled and vits_deliver_shaped: levels == nullptr is the first exactly, shapes == nullptr
 // (or shapes without fades and points) the second
-static int deliver_kept(vits_handle *h, const vits_segment *segs, const vits_trim *trims, const vits_level *levels, int n_segs, int n_streams,
-                        int encoding, int sample_rate, void *dst, size_t dst_bytes, int64_t *stream_samples, int64_t *stream_offsets,
-                        int64_t *kept_first, int64_t *kept_count, double *loudness, float *gain, const vits_shape *shapes = nullptr,
-                        const vits_env_point *points = nullptr, int64_t n_points = 0) {
-    if (int rc = check_dev(h)) return rc;
-    std::lock_guard<std::mutex> lk(h->mu);
-    const int B = h->B, S = h->S;
-    if (!h->d_out || B <= 0 || S <= 0 || (!h->last_vocoder && (int)h->h_ylen.size() != B))
-        return fail(h, VITS_E_ARG, "no completed run to deliver");
-    const bool rs = h->out_resampled;
-    std::vector<int64_t> counts;
-    if (int rc = delivery_counts(h, counts)) return rc;
-    DeliveryPlan p0;  // over the whole rows: the validation, and the table the scan reads
-    std::string e = delivery_plan(counts.data(), B, S, segs, n_segs, n_streams, encoding, p0, trims);
-    if (e.empty()) e = level_plan_fault(segs, levels, n_segs, n_streams, sample_rate);
-    if (e.empty()) e = shape_fault(shapes, n_segs, points, n_points);
-    if (!e.empty()) return fail(h, VITS_E_ARG, "%s", e.c_str());
-    const bool lev = any_level(levels, n_segs);
-    const bool shaped = any_shape(shapes, n_segs);
-    const int64_t n_knots = shape_knot_count(shapes, n_segs);
-    ShapeJob job;
-    if (lev && h->rs.plan.on() && sample_rate != h->rs.plan.fo)
-        return fail(h, VITS_E_ARG, "sample_rate %d differs from the output rate %d", sample_rate, (int)h->rs.plan.fo);
-    DeliveryBufs db{};
-    TrimBufs tb{};
-    LevelBufs lb{};
-    if (rs) {
-        // (the run's own walk ends with carve_resample, or with an encoded stream's buffers behind it; the trim slots behind
-        // carve_resample are at most 12 B + 512 bytes more than the former.  Growing the slab here would drop the waveform that
-        // lives in it - the check below - and does not happen: slab_reserve allocates 1 MiB above every request, and
-        // vits_reserve counts this walk.  A levelled delivery's buffers - some 0.05 bytes a sample - fit into the quarter a
-        // growing slab adds to every request; where a slab does not hold them the call is refused and the run stays
-        // deliverable.)
-        const int K = h->rs_run_K;
-        auto walk = [&](Carver &cv) {
-            db = carve_resample(cv, B, S, K).dlv;
-            tb = carve_trim(cv, B);
-            if (lev) lb = carve_level(cv, B, S);
-            if (shaped) job.sb = carve_shape(cv, B, n_knots);
-        };
-        if ((lev || shaped) && carved_bytes(walk) > h->io.cap)
-            return fail(h, VITS_E_NOMEM, "a levelled or shaped delivery of this run needs %zu bytes of staging, %zu are there: vits_reserve covers it",
-                        carved_bytes(walk), h->io.cap);
-        if (int rc = slab_carve(h, h->io, "staging", walk)) return rc;
-        if (!h->d_out) return fail(h, VITS_E_ARG, "no completed run to deliver");
-    } else if (int rc = slab_carve(h, h->io, "staging", [&](Carver &cv) {
-                   db = carve_delivery(cv, B, S);
-                   tb = carve_trim(cv, B);
-                   if (lev) lb = carve_level(cv, B, S);
-                   if (shaped) job.sb = carve_shape(cv, B, n_knots);
-               }))
-        return rc;
-    hipStream_t st = h->stream;
-    std::vector<int64_t> first, kept;
-    hipError_t err = trim_scan(h->d_out, p0, segs, trims, counts.data(), B, db, tb, st, first, kept);
-    if (err != hipSuccess) return fail(h, VITS_E_DEVICE, "trim scan failed: %s", hipGetErrorString(err));
-    if (int rc = range_check(h)) return rc;  // (after vits_run_async this is the first synchronisation of that run)
-    if (h->range_failed) return fail(h, VITS_E_RANGE, "the last run left the range of the fp16 operand planes (see vits_get_stats)");
-    DeliveryPlan p;
-    e = delivery_plan(kept.data(), B, S, segs, n_segs, n_streams, encoding, p, trims, first.data());
-    if (!e.empty()) return fail(h, VITS_E_ARG, "%s", e.c_str());
-    if (dst && dst_bytes < (size_t)p.total_bytes)
-        return fail(h, VITS_E_ARG, "delivery buffer too small: %zu bytes, %lld needed", dst_bytes, (long long)p.total_bytes);
-    std::vector<double> loud;
-    std::vector<float> gn;
-    err = level_measure(h->d_out, p, segs, levels, n_segs, n_streams, sample_rate, db, lb, st, loud, gn);
-    if (err != hipSuccess) return fail(h, VITS_E_DEVICE, "loudness measurement failed: %s", hipGetErrorString(err));
-    level_apply(p, levels, gn.data());
-    if (dst) {
-        if (shaped) shape_job(p, segs, shapes, points, first, kept, job);
-        err = delivery_enqueue(h->d_out, p, db, B, st, dst, shaped ? &job : nullptr);
-        if (err == hipSuccess) err = hipStreamSynchronize(st);
-        else hipStreamSynchronize(st);
-        if (err != hipSuccess) return fail(h, VITS_E_DEVICE, "delivery failed: %s", hipGetErrorString(err));
-    }
-    delivery_report(p, stream_samples, stream_offsets);
-    trim_report(segs, n_segs, first, kept, kept_first, kept_count);
-    level_report(n_segs, loud, gn, loudness, gain);
-    return VITS_OK;
-}
-
 int vits_deliver_trimmed(vits_handle *h, const vits_segment *segs, const vits_trim *trims, int n_segs, int n_streams, int encoding,
                          void *dst, size_t dst_bytes, int64_t *stream_samples, int64_t *stream_offsets, int64_t *kept_first,
                          int64_t *kept_count) {
-    return deliver_kept(h, segs, trims, nullptr, n_segs, n_streams, encoding, 0, dst, dst_bytes, stream_samples, stream_offsets, kept_first,
-                        kept_count, nullptr, nullptr);
+    return deliver_last_run(h, {segs, trims, nullptr, nullptr, nullptr, 0, n_segs, n_streams, encoding, 0, dst, dst_bytes, /*kept=*/true},
+                            {stream_samples, stream_offsets, kept_first, kept_count, nullptr, nullptr});
 }
 
 int vits_deliver_leveled(vits_handle *h, const vits_segment *segs, const vits_trim *trims, const vits_level *levels, int n_segs,
                          int n_streams, int encoding, int sample_rate, void *dst, size_t dst_bytes, int64_t *stream_samples,
                          int64_t *stream_offsets, int64_t *kept_first, int64_t *kept_count, double *loudness, float *gain) {
-    return deliver_kept(h, segs, trims, levels, n_segs, n_streams, encoding, sample_rate, dst, dst_bytes, stream_samples, stream_offsets,
-                        kept_first, kept_count, loudness, gain);
+    return deliver_last_run(h, {segs, trims, levels, nullptr, nullptr, 0, n_segs, n_streams, encoding, sample_rate, dst, dst_bytes, /*kept=*/true},
+                            {stream_samples, stream_offsets, kept_first, kept_count, loudness, gain});
 }
 
 int vits_deliver_shaped(vits_handle *h, const vits_segment *segs, const vits_trim *trims, const vits_level *levels,
                         const vits_shape *shapes, const vits_env_point *points, int64_t n_points, int n_segs, int n_streams,
                         int encoding, int sample_rate, void *dst, size_t dst_bytes, int64_t *stream_samples, int64_t *stream_offsets,
                         int64_t *kept_first, int64_t *kept_count, double *loudness, float *gain) {
-    return deliver_kept(h, segs, trims, levels, n_segs, n_streams, encoding, sample_rate, dst, dst_bytes, stream_samples, stream_offsets,
-                        kept_first, kept_count, loudness, gain, shapes, points, n_points);
+    return deliver_last_run(h, {segs, trims, levels, shapes, points, n_points, n_segs, n_streams, encoding, sample_rate, dst, dst_bytes, /*kept=*/true},
+                            {stream_samples, stream_offsets, kept_first, kept_count, loudness, gain});
 }
 
 // vocoder-only entry points: z (host, [B, inter, F], already masked) -> device, speaker bias; then either the whole
@@ -4397,120 +4123,50 @@ int vits_test_resample(int device_id, const float *x, const int64_t *lens, int B
     return VITS_OK;
 }
 
+// A hook's side of every delivery (the sequence: delivery_run.hip.hpp, the handle's own): x uploaded, the call's buffers in one
+// allocation carved by the handle's walk, nothing behind the first wait.
+static int test_deliver_run(int device_id, const float *x, const int64_t *counts, int B, int S, const DeliveryRequest &rq,
+                            const DeliveryOutputs &out) {
+    if (!x || !counts || B <= 0 || S <= 0 || (int64_t)B * S > (int64_t)1 << 40) return fail(nullptr, VITS_E_ARG, "bad delivery test arguments");
+    for (int b = 0; b < B; b++)
+        if (counts[b] < 0 || counts[b] > S) return fail(nullptr, VITS_E_ARG, "counts[%d] = %lld outside [0, %d]", b, (long long)counts[b], S);
+    DevBufs D;
+    auto bufs = [&](const DeliveryNeeds &need, const float *&d_x, DeliveryCallBufs &cb) -> DeliveryStatus {
+        if (int rc = test_dev(device_id)) return {rc, g_open_error};
+        d_x = D.up(x, (size_t)B * S);
+        const size_t total = carved_bytes([&](Carver &cv) { carve_delivery_call(cv, B, S, need); });
+        Carver cv(D.alloc<unsigned char>(total), total);
+        if (!D.ok()) return delivery_refusal(VITS_E_DEVICE, "delivery test buffers: %s", hipGetErrorString(D.err));
+        cb = carve_delivery_call(cv, B, S, need);
+        if (!cv.fits()) return delivery_refusal(VITS_E_NOMEM, "delivery walk carved %zu of %zu bytes", cv.used, cv.cap);
+        return {};
+    };
+    const DeliveryStatus s = delivery_run(counts, B, S, nullptr, rq, out, bufs, [] { return DeliveryStatus{}; });
+    return s.code ? fail(nullptr, s.code, "%s", s.msg.c_str()) : VITS_OK;
+}
+
 int vits_test_deliver(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_segment *segs, int n_segs,
                       int n_streams, int encoding, void *dst, size_t dst_bytes, int64_t *stream_samples, int64_t *stream_offsets) {
-    if (!x || !counts || B <= 0 || S <= 0 || (int64_t)B * S > (int64_t)1 << 40) return fail(nullptr, VITS_E_ARG, "bad delivery test arguments");
-    for (int b = 0; b < B; b++)
-        if (counts[b] < 0 || counts[b] > S) return fail(nullptr, VITS_E_ARG, "counts[%d] = %lld outside [0, %d]", b, (long long)counts[b], S);
-    DeliveryPlan p;
-    const std::string e = delivery_plan(counts, B, S, segs, n_segs, n_streams, encoding, p);
-    if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
-    if (!dst) {  // the layout only: nothing is enqueued, nothing waited for
-        delivery_report(p, stream_samples, stream_offsets);
-        return VITS_OK;
-    }
-    if (dst_bytes < (size_t)p.total_bytes)
-        return fail(nullptr, VITS_E_ARG, "delivery buffer too small: %zu bytes, %lld needed", dst_bytes, (long long)p.total_bytes);
-    if (int rc = test_dev(device_id)) return rc;
-    DevBufs D;
-    float *dx = D.up(x, (size_t)B * S);
-    DeliveryBufs db{};
-    db.packed = D.alloc<unsigned char>((size_t)B * S * 4 + 16);
-    db.segs = D.alloc<DeliverySeg>((size_t)B);
-    db.peak = D.alloc<unsigned>(2 * (size_t)B);
-    TCHECK(D.err);
-    // (wait whatever the enqueue answered: the plan's segment table is the pageable source of a copy that may be in flight)
-    const hipError_t enq = delivery_enqueue(dx, p, db, B, nullptr, dst);
-    const hipError_t done = hipDeviceSynchronize();
-    TCHECK(enq);
-    TCHECK(done);
-    delivery_report(p, stream_samples, stream_offsets);
-    return VITS_OK;
-}
-
-// a test hook's LevelBufs: carve_level's buffers as allocations of their own
-static LevelBufs test_level_bufs(DevBufs &D, int B, int S) {
-    LevelBufs lb{};
-    lb.n_peaks = (size_t)B;
-    lb.n_chunks = (size_t)B * ((size_t)S / kLoudChunk + 1);
-    lb.n_subs = (size_t)B * ((size_t)S / kLoudMinHop);
-    lb.segs = D.alloc<LoudSeg>((size_t)B);
-    lb.fin = D.alloc<LoudState>(lb.n_chunks);
-    lb.init = D.alloc<LoudState>(lb.n_chunks);
-    lb.part = D.alloc<float>(lb.n_chunks * kLoudParts);
-    lb.result = D.alloc<unsigned>(lb.n_peaks + lb.n_subs);
-    return lb;
-}
-
-static int test_deliver_kept(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_segment *segs,
-                             const vits_trim *trims, const vits_level *levels, int n_segs, int n_streams, int encoding, int sample_rate,
-                             void *dst, size_t dst_bytes, int64_t *stream_samples, int64_t *stream_offsets, int64_t *kept_first,
-                             int64_t *kept_count, double *loudness, float *gain, const vits_shape *shapes = nullptr,
-                             const vits_env_point *points = nullptr, int64_t n_points = 0) {
-    if (!x || !counts || B <= 0 || S <= 0 || (int64_t)B * S > (int64_t)1 << 40) return fail(nullptr, VITS_E_ARG, "bad delivery test arguments");
-    for (int b = 0; b < B; b++)
-        if (counts[b] < 0 || counts[b] > S) return fail(nullptr, VITS_E_ARG, "counts[%d] = %lld outside [0, %d]", b, (long long)counts[b], S);
-    DeliveryPlan p0;
-    std::string e = delivery_plan(counts, B, S, segs, n_segs, n_streams, encoding, p0, trims);
-    if (e.empty()) e = level_plan_fault(segs, levels, n_segs, n_streams, sample_rate);
-    if (e.empty()) e = shape_fault(shapes, n_segs, points, n_points);
-    if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
-    const bool shaped = any_shape(shapes, n_segs);
-    if (int rc = test_dev(device_id)) return rc;
-    DevBufs D;
-    float *dx = D.up(x, (size_t)B * S);
-    DeliveryBufs db{};
-    db.packed = D.alloc<unsigned char>((size_t)B * S * 4 + 16);
-    db.segs = D.alloc<DeliverySeg>((size_t)B);
-    db.peak = D.alloc<unsigned>(2 * (size_t)B);
-    TrimBufs tb{};
-    tb.bounds = D.alloc<int32_t>(2 * (size_t)B);
-    tb.peak_all = D.alloc<unsigned>((size_t)B);
-    LevelBufs lb{};
-    if (any_level(levels, n_segs)) lb = test_level_bufs(D, B, S);
-    ShapeJob job;
-    if (shaped) {
-        job.sb.segs = D.alloc<ShapeSeg>((size_t)B);
-        job.sb.knots = D.alloc<ShapeKnot>((size_t)shape_knot_count(shapes, n_segs));
-    }
-    TCHECK(D.err);
-    std::vector<int64_t> first, kept;
-    TCHECK(trim_scan(dx, p0, segs, trims, counts, B, db, tb, nullptr, first, kept));
-    DeliveryPlan p;
-    e = delivery_plan(kept.data(), B, S, segs, n_segs, n_streams, encoding, p, trims, first.data());
-    if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
-    if (dst && dst_bytes < (size_t)p.total_bytes)
-        return fail(nullptr, VITS_E_ARG, "delivery buffer too small: %zu bytes, %lld needed", dst_bytes, (long long)p.total_bytes);
-    std::vector<double> loud;
-    std::vector<float> gn;
-    TCHECK(level_measure(dx, p, segs, levels, n_segs, n_streams, sample_rate, db, lb, nullptr, loud, gn));
-    level_apply(p, levels, gn.data());
-    if (dst) {
-        if (shaped) shape_job(p, segs, shapes, points, first, kept, job);
-        const hipError_t enq = delivery_enqueue(dx, p, db, B, nullptr, dst, shaped ? &job : nullptr);
-        const hipError_t done = hipDeviceSynchronize();
-        TCHECK(enq);
-        TCHECK(done);
-    }
-    delivery_report(p, stream_samples, stream_offsets);
-    trim_report(segs, n_segs, first, kept, kept_first, kept_count);
-    level_report(n_segs, loud, gn, loudness, gain);
-    return VITS_OK;
+    return test_deliver_run(device_id, x, counts, B, S,
+                            {segs, nullptr, nullptr, nullptr, nullptr, 0, n_segs, n_streams, encoding, 0, dst, dst_bytes, /*kept=*/false},
+                            {stream_samples, stream_offsets, nullptr, nullptr, nullptr, nullptr});
 }
 
 int vits_test_deliver_trimmed(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_segment *segs,
                               const vits_trim *trims, int n_segs, int n_streams, int encoding, void *dst, size_t dst_bytes,
                               int64_t *stream_samples, int64_t *stream_offsets, int64_t *kept_first, int64_t *kept_count) {
-    return test_deliver_kept(device_id, x, counts, B, S, segs, trims, nullptr, n_segs, n_streams, encoding, 0, dst, dst_bytes, stream_samples,
-                             stream_offsets, kept_first, kept_count, nullptr, nullptr);
+    return test_deliver_run(device_id, x, counts, B, S,
+                            {segs, trims, nullptr, nullptr, nullptr, 0, n_segs, n_streams, encoding, 0, dst, dst_bytes, /*kept=*/true},
+                            {stream_samples, stream_offsets, kept_first, kept_count, nullptr, nullptr});
 }
 
 int vits_test_deliver_leveled(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_segment *segs,
                               const vits_trim *trims, const vits_level *levels, int n_segs, int n_streams, int encoding,
                               int sample_rate, void *dst, size_t dst_bytes, int64_t *stream_samples, int64_t *stream_offsets,
                               int64_t *kept_first, int64_t *kept_count, double *loudness, float *gain) {
-    return test_deliver_kept(device_id, x, counts, B, S, segs, trims, levels, n_segs, n_streams, encoding, sample_rate, dst, dst_bytes,
-                             stream_samples, stream_offsets, kept_first, kept_count, loudness, gain);
+    return test_deliver_run(device_id, x, counts, B, S,
+                            {segs, trims, levels, nullptr, nullptr, 0, n_segs, n_streams, encoding, sample_rate, dst, dst_bytes, /*kept=*/true},
+                            {stream_samples, stream_offsets, kept_first, kept_count, loudness, gain});
 }
 
 int vits_test_deliver_shaped(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_segment *segs,
@@ -4518,8 +4174,9 @@ int vits_test_deliver_shaped(int device_id, const float *x, const int64_t *count
                              int64_t n_points, int n_segs, int n_streams, int encoding, int sample_rate, void *dst, size_t dst_bytes,
                              int64_t *stream_samples, int64_t *stream_offsets, int64_t *kept_first, int64_t *kept_count,
                              double *loudness, float *gain) {
-    return test_deliver_kept(device_id, x, counts, B, S, segs, trims, levels, n_segs, n_streams, encoding, sample_rate, dst, dst_bytes,
-                             stream_samples, stream_offsets, kept_first, kept_count, loudness, gain, shapes, points, n_points);
+    return test_deliver_run(device_id, x, counts, B, S,
+                            {segs, trims, levels, shapes, points, n_points, n_segs, n_streams, encoding, sample_rate, dst, dst_bytes, /*kept=*/true},
+                            {stream_samples, stream_offsets, kept_first, kept_count, loudness, gain});
 }
 
 int vits_test_loudness_blocks(int device_id, const float *x, const int64_t *counts, const int64_t *firsts, int B, int S,
@@ -4546,8 +4203,11 @@ int vits_test_loudness_blocks(int device_id, const float *x, const int64_t *coun
     if (int rc = test_dev(device_id)) return rc;
     DevBufs D;
     float *dx = D.up(x, (size_t)B * S);
-    LevelBufs lb = test_level_bufs(D, B, S);
+    // the pipeline's buffers, by the pipeline's walk
+    const size_t total = carved_bytes([&](Carver &cv) { carve_level(cv, B, S); });
+    Carver cv(D.alloc<unsigned char>(total), total);
     TCHECK(D.err);
+    const LevelBufs lb = carve_level(cv, B, S);
     if (max_n > 0) {
         TCHECK(hipMemcpy(lb.segs, ls.data(), ls.size() * sizeof(LoudSeg), hipMemcpyHostToDevice));
         const hipError_t enq = launch_loudness(dx, lb.segs, B, max_n, k, lb.fin, lb.init, lb.part, lb.e(), nullptr);

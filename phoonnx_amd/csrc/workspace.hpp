@@ -337,6 +337,32 @@ inline ResampleBufs carve_resample(Carver &cv, int B, int S_out, int K) {
     return r;
 }
 
+// The buffers of ONE delivery call, whichever entry it came through, and the one walk that carves them: the delivery's own
+// (carved here, or - `front` - those a carve_resample in the same walk has just carved behind the resampled waveform), then
+// what the call's stages need, in this order: the trim slots of a call that scans (every one but vits_deliver), the level
+// buffers where a segment is levelled, the shape tables where one is shaped.  vits_reserve walks it with everything on.
+struct DeliveryNeeds {
+    bool scan, levelled, shaped;
+    int64_t n_knots;  // shape_knot_count
+};
+
+struct DeliveryCallBufs {
+    DeliveryBufs dlv;
+    TrimBufs trim;
+    LevelBufs level;
+    ShapeBufs shape;
+};
+
+inline DeliveryCallBufs carve_delivery_call(Carver &cv, int B, int S, const DeliveryNeeds &need, const DeliveryBufs *front = nullptr) {
+    DeliveryCallBufs c{};
+    c.dlv = front ? *front : carve_delivery(cv, B, S);
+    if (!need.scan) return c;
+    c.trim = carve_trim(cv, B);
+    if (need.levelled) c.level = carve_level(cv, B, S);
+    if (need.shaped) c.shape = carve_shape(cv, B, need.n_knots);
+    return c;
+}
+
 // An encoded stream (vits_run_chunked_enc): one device buffer [chunk bytes | running peaks | format table].  `cap` bytes hold
 // the largest chunk in the widest encoding - B rows of n_max samples as F32 at a 16-byte row pitch - whatever encoding and
 // chunk_frames a call brings; the running peaks [B] (padded to whole 16-byte cells) sit right behind at a 16-byte-aligned

@@ -489,37 +489,10 @@ def _n_streams(segments, n_streams):
     return max([int(g.stream) for g in segments], default=0) + 1
 
 
-def delivery_plan(counts, segments, n_streams=None, encoding="pcm16", trims=None, kept=None):
-    """The layout of a delivery (vits_delivery_plan: pure host code, no session, no device): counts int64 [B] - the rows' valid
-    samples - and a plan -> {"stream_samples": int64 [J], "stream_offsets": int64 [J + 1] (bytes), "total_bytes": int}.
-    A plan the engine would refuse raises SessionError with its message.  trims (one Trim or one per segment) and kept
-    (int64 [B]: what a trimmed delivery keeps of each row, in the place of counts) give the layout of a trimmed delivery
-    (vits_delivery_plan_trimmed)."""
-    counts = np.ascontiguousarray(counts if kept is None else kept, np.int64)
-    if counts.ndim != 1:
-        raise SessionError(f"counts must be int64 [B], got {counts.shape}")
-    segments = list(segments)
-    code, _ = _encoding(encoding)
-    J = _n_streams(segments, n_streams)
-    arr, n = _segments(segments)
-    samples, offsets, total = np.zeros(max(J, 0), np.int64), np.zeros(max(J, 0) + 1, np.int64), C.c_int64()
-    if trims is not None or kept is not None:
-        rc = _ffi.load().vits_delivery_plan_trimmed(_ffi.ptr(counts), counts.shape[0], arr, _trims(trims, n), n, J, code,
-                                                    _ffi.ptr(samples), _ffi.ptr(offsets), C.byref(total))
-        if rc != 0:
-            raise SessionError(f"vits_delivery_plan_trimmed failed [{rc}]: {_ffi.last_error(None)}")
-        return {"stream_samples": samples, "stream_offsets": offsets, "total_bytes": int(total.value)}
-    rc = _ffi.load().vits_delivery_plan(_ffi.ptr(counts), counts.shape[0], arr, n, J, code, _ffi.ptr(samples), _ffi.ptr(offsets),
-                                        C.byref(total))
-    if rc != 0:
-        raise SessionError(f"vits_delivery_plan failed [{rc}]: {_ffi.last_error(None)}")
-    return {"stream_samples": samples, "stream_offsets": offsets, "total_bytes": int(total.value)}
-
-
-def level_plan(counts, segments, levels, sample_rate, n_streams=None, encoding="pcm16", trims=None, out=None):
-    """delivery_plan(..., kept=counts) with the levels' validation (vits_delivery_plan_leveled: pure host code).  The layout
-    never depends on the levels.  out: (stream_samples, stream_offsets) arrays to fill; a refusal raises SessionError and
-    leaves them untouched."""
+def _plan_call(name, counts, segments, n_streams, encoding, arrays=(), rate=(), out=None):
+    """One of the vits_delivery_plan* entries over counts int64 [B]: arrays - (marshaller, value) of what the entry takes
+    between the segments and their count (trims, levels), rate - () or (sample_rate,), out - (stream_samples, stream_offsets)
+    arrays to fill."""
     counts = np.ascontiguousarray(counts, np.int64)
     if counts.ndim != 1:
         raise SessionError(f"counts must be int64 [B], got {counts.shape}")
@@ -529,11 +502,31 @@ def level_plan(counts, segments, levels, sample_rate, n_streams=None, encoding="
     arr, n = _segments(segments)
     samples, offsets = out if out is not None else (np.zeros(max(J, 0), np.int64), np.zeros(max(J, 0) + 1, np.int64))
     total = C.c_int64()
-    rc = _ffi.load().vits_delivery_plan_leveled(_ffi.ptr(counts), counts.shape[0], arr, _trims(trims, n), _levels(levels, n), n, J,
-                                                code, int(sample_rate), _ffi.ptr(samples), _ffi.ptr(offsets), C.byref(total))
+    rc = getattr(_ffi.load(), name)(_ffi.ptr(counts), counts.shape[0], arr, *[f(v, n) for f, v in arrays], n, J, code, *rate,
+                                    _ffi.ptr(samples), _ffi.ptr(offsets), C.byref(total))
     if rc != 0:
-        raise SessionError(f"vits_delivery_plan_leveled failed [{rc}]: {_ffi.last_error(None)}")
+        raise SessionError(f"{name} failed [{rc}]: {_ffi.last_error(None)}")
     return {"stream_samples": samples, "stream_offsets": offsets, "total_bytes": int(total.value)}
+
+
+def delivery_plan(counts, segments, n_streams=None, encoding="pcm16", trims=None, kept=None):
+    """The layout of a delivery (vits_delivery_plan: pure host code, no session, no device): counts int64 [B] - the rows' valid
+    samples - and a plan -> {"stream_samples": int64 [J], "stream_offsets": int64 [J + 1] (bytes), "total_bytes": int}.
+    A plan the engine would refuse raises SessionError with its message.  trims (one Trim or one per segment) and kept
+    (int64 [B]: what a trimmed delivery keeps of each row, in the place of counts) give the layout of a trimmed delivery
+    (vits_delivery_plan_trimmed)."""
+    if trims is not None or kept is not None:
+        return _plan_call("vits_delivery_plan_trimmed", counts if kept is None else kept, segments, n_streams, encoding,
+                          arrays=((_trims, trims),))
+    return _plan_call("vits_delivery_plan", counts, segments, n_streams, encoding)
+
+
+def level_plan(counts, segments, levels, sample_rate, n_streams=None, encoding="pcm16", trims=None, out=None):
+    """delivery_plan(..., kept=counts) with the levels' validation (vits_delivery_plan_leveled: pure host code).  The layout
+    never depends on the levels.  out: (stream_samples, stream_offsets) arrays to fill; a refusal raises SessionError and
+    leaves them untouched."""
+    return _plan_call("vits_delivery_plan_leveled", counts, segments, n_streams, encoding, arrays=((_trims, trims), (_levels, levels)),
+                      rate=(int(sample_rate),), out=out)
 
 
 def loudness_filter(sample_rate):
@@ -1352,62 +1345,40 @@ class MiSession:
         J = _n_streams(segments, n_streams)
         arr, n = _segments(segments)
         samples, offsets = np.zeros(max(J, 0), np.int64), np.zeros(max(J, 0) + 1, np.int64)
-        if levels is not None or return_levels or shapes is not None:
+        plain = trims is None and levels is None and shapes is None and not return_kept and not return_levels
+        tarr = larr = sarr = parr = first = count = loud = gain = None  # (a plain delivery has none of them and pays for none)
+        n_points = rate = tails = 0
+        if not plain:
             tarr, larr = _trims(trims, n), _levels(levels, n)
             sarr, parr, n_points = _shapes(shapes, n)
-            rate = self.delivered_rate if sample_rate is None else int(sample_rate)
-            first, count = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
-            loud, gain = np.full(max(n, 1), np.nan, np.float64), np.ones(max(n, 1), np.float32)
-            width = np.dtype(dtype).itemsize
-            with self._locked():
-                rc = self._lib.vits_deliver(self._h, arr, n, J, code, None, 0, _ffi.ptr(samples), _ffi.ptr(offsets))
-                if rc != 0:
-                    self._raise("vits_deliver", rc)
-                cap = int(offsets[-1]) + width * sum(max(int(tarr[i].tail_samples), 0) for i in range(n if tarr else 0))
-                buf = _POOL.array((cap,), np.uint8) if self.pinned_results and cap else np.empty(cap, np.uint8)
-                if shapes is not None:
-                    rc = self._lib.vits_deliver_shaped(self._h, arr, tarr, larr, sarr, parr, n_points, n, J, code, rate, _ffi.ptr(buf),
-                                                       cap, _ffi.ptr(samples), _ffi.ptr(offsets), _ffi.ptr(first), _ffi.ptr(count),
-                                                       _ffi.ptr(loud), _ffi.ptr(gain))
-                    if rc != 0:
-                        self._raise("vits_deliver_shaped", rc)
-                else:
-                    rc = self._lib.vits_deliver_leveled(self._h, arr, tarr, larr, n, J, code, rate, _ffi.ptr(buf), cap, _ffi.ptr(samples),
-                                                        _ffi.ptr(offsets), _ffi.ptr(first), _ffi.ptr(count), _ffi.ptr(loud),
-                                                        _ffi.ptr(gain))
-                    if rc != 0:
-                        self._raise("vits_deliver_leveled", rc)
-            streams = [buf[int(offsets[j]):int(offsets[j + 1])].view(dtype) for j in range(J)]
-            res = (streams,) + ((first[:n], count[:n]) if return_kept else ()) + ((loud[:n], gain[:n]) if return_levels else ())
-            return res if len(res) > 1 else streams
-        if trims is not None or return_kept:
-            tarr = _trims(trims, n)
-            first, count = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
-            width = np.dtype(dtype).itemsize
-            with self._locked():
-                # the untrimmed layout (no device work, no wait) and the tails bound the bytes: ONE trimmed call, one scan
-                rc = self._lib.vits_deliver(self._h, arr, n, J, code, None, 0, _ffi.ptr(samples), _ffi.ptr(offsets))
-                if rc != 0:
-                    self._raise("vits_deliver", rc)
-                cap = int(offsets[-1]) + width * sum(max(int(tarr[i].tail_samples), 0) for i in range(n if tarr else 0))
-                buf = _POOL.array((cap,), np.uint8) if self.pinned_results and cap else np.empty(cap, np.uint8)
-                rc = self._lib.vits_deliver_trimmed(self._h, arr, tarr, n, J, code, _ffi.ptr(buf), cap, _ffi.ptr(samples),
-                                                    _ffi.ptr(offsets), _ffi.ptr(first), _ffi.ptr(count))
-                if rc != 0:
-                    self._raise("vits_deliver_trimmed", rc)
-            streams = [buf[int(offsets[j]):int(offsets[j + 1])].view(dtype) for j in range(J)]
-            return (streams, first[:n], count[:n]) if return_kept else streams
+            if levels is not None:  # (only a levelled delivery looks at the rate: 0 elsewhere, which nothing refuses)
+                rate = self.delivered_rate if sample_rate is None else int(sample_rate)
+            # (what the caller does not want back is not reported: NULL, the engine's own "none")
+            if return_kept:
+                first, count = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
+            if return_levels:
+                loud, gain = np.full(max(n, 1), np.nan, np.float64), np.ones(max(n, 1), np.float32)
+            if tarr:
+                tails = np.dtype(dtype).itemsize * sum(max(int(tarr[i].tail_samples), 0) for i in range(n))
         with self._locked():
-            # (dst = NULL: the layout only - no device work, no wait)
+            # the untrimmed layout (dst = NULL: no device work, no wait) and the tails bound the bytes: ONE delivery, one scan
             rc = self._lib.vits_deliver(self._h, arr, n, J, code, None, 0, _ffi.ptr(samples), _ffi.ptr(offsets))
             if rc != 0:
                 self._raise("vits_deliver", rc)
-            total = int(offsets[-1])
-            buf = _POOL.array((total,), np.uint8) if self.pinned_results and total else np.empty(total, np.uint8)
-            rc = self._lib.vits_deliver(self._h, arr, n, J, code, _ffi.ptr(buf), total, _ffi.ptr(samples), _ffi.ptr(offsets))
+            cap = int(offsets[-1]) + tails
+            buf = _POOL.array((cap,), np.uint8) if self.pinned_results and cap else np.empty(cap, np.uint8)
+            if plain:
+                rc = self._lib.vits_deliver(self._h, arr, n, J, code, _ffi.ptr(buf), cap, _ffi.ptr(samples), _ffi.ptr(offsets))
+            else:  # (vits_deliver_trimmed and vits_deliver_leveled are this entry with NULLs)
+                rc = self._lib.vits_deliver_shaped(self._h, arr, tarr, larr, sarr, parr, n_points, n, J, code, rate, _ffi.ptr(buf), cap,
+                                                   _ffi.ptr(samples), _ffi.ptr(offsets), _ffi.ptr(first), _ffi.ptr(count),
+                                                   _ffi.ptr(loud), _ffi.ptr(gain))
             if rc != 0:
-                self._raise("vits_deliver", rc)
-        return [buf[int(offsets[j]):int(offsets[j + 1])].view(dtype) for j in range(J)]
+                self._raise("vits_deliver" if plain else "vits_deliver_shaped", rc)
+        streams = [buf[int(offsets[j]):int(offsets[j + 1])].view(dtype) for j in range(J)]
+        if not (return_kept or return_levels):
+            return streams
+        return (streams,) + ((first[:n], count[:n]) if return_kept else ()) + ((loud[:n], gain[:n]) if return_levels else ())
 
     def deliver_layout(self, segments, n_streams=None, encoding="pcm16", trims=None):
         """What deliver(..., trims=) would return, without the bytes (vits_deliver_trimmed with dst = NULL: waits for the run
@@ -1479,21 +1450,14 @@ class MiSession:
                 loud = gain = None
                 if tgains is not None:
                     used = self._token_shapes(segments, used, tgains, dur, lens, counts, gain_ramp)
-                if used is not None:
-                    res = self.deliver(segments, n_streams, encoding, trims=trim, return_kept=True, levels=levels,
-                                       return_levels=levels is not None, shapes=used)
-                    streams, kept_first, kept_count = res[:3]
-                    if levels is not None:
-                        loud, gain = res[3:]
-                elif levels is not None:
-                    streams, kept_first, kept_count, loud, gain = self.deliver(segments, n_streams, encoding, trims=trim,
-                                                                               return_kept=True, levels=levels, return_levels=True)
-                elif trim is None:
+                if used is None and levels is None and trim is None:
                     streams = self.deliver(segments, n_streams, encoding)
                     kept_first = np.zeros(len(segments), np.int64)
                     kept_count = np.array([counts[int(g.row)] for g in segments], np.int64)
                 else:
-                    streams, kept_first, kept_count = self.deliver(segments, n_streams, encoding, trims=trim, return_kept=True)
+                    streams, kept_first, kept_count, *lv = self.deliver(segments, n_streams, encoding, trims=trim, return_kept=True,
+                                                                        levels=levels, return_levels=levels is not None, shapes=used)
+                    loud, gain = lv or (None, None)
             except RangeError as exc:
                 self._fall_back_to_bf16x6(exc)
                 return self.synthesize_delivered(ids, lens, scales, sid, segments=segments, n_streams=n_streams,
@@ -2094,84 +2058,11 @@ def test_stream_pack(x, counts, piece_samples, encoding="pcm16", ref_peak=None, 
 
 # ---- the token-to-frame and frame-to-sample kernels by value (include/vitsmi.h: vits_test_durations ...) ----------------
 
-def test_deliver(x, counts, segments, n_streams=None, encoding="pcm16", device_id=0, dst=None):
-    """vits_test_deliver: x [B, S] float32 and the rows' valid samples through the delivery kernels -> one array per stream,
-    views into `dst` (uint8; default: a buffer of exactly the plan's size, sized by delivery_plan).  A refusal raises
-    SessionError and leaves a `dst` passed in untouched."""
-    x = np.ascontiguousarray(x, np.float32)
-    counts = np.ascontiguousarray(counts, np.int64)
-    B, S = x.shape
-    segments = list(segments)
-    code, dtype = _encoding(encoding)
-    J = _n_streams(segments, n_streams)
-    if dst is None:
-        dst = np.empty(delivery_plan(counts, segments, J, encoding)["total_bytes"], np.uint8)
-    arr, n = _segments(segments)
-    samples, offsets = np.zeros(max(J, 0), np.int64), np.zeros(max(J, 0) + 1, np.int64)
-    rc = _ffi.load().vits_test_deliver(device_id, _ffi.ptr(x), _ffi.ptr(counts), B, S, arr, n, J, code, _ffi.ptr(dst), dst.nbytes,
-                                       _ffi.ptr(samples), _ffi.ptr(offsets))
-    if rc != 0:
-        raise SessionError(f"vits_test_deliver failed [{rc}]: {_ffi.last_error(None)}")
-    return [dst[int(offsets[j]):int(offsets[j + 1])].view(dtype) for j in range(J)]
-
-
-def test_deliver_trimmed(x, counts, segments, trims=None, n_streams=None, encoding="pcm16", device_id=0, dst=None, layout_only=False):
-    """vits_test_deliver_trimmed: test_deliver with trims (one Trim, one per segment, or None) -> {"streams": one array per
-    stream, views into `dst` (uint8; default: a buffer of the untrimmed plan's size with the tails), "stream_samples",
-    "stream_offsets", "kept_first", "kept_count"}.  layout_only: dst = NULL - the scan runs, nothing is packed ("streams" is
-    None).  A refusal raises SessionError and leaves a `dst` passed in untouched."""
-    x = np.ascontiguousarray(x, np.float32)
-    counts = np.ascontiguousarray(counts, np.int64)
-    B, S = x.shape
-    segments = list(segments)
-    code, dtype = _encoding(encoding)
-    J = _n_streams(segments, n_streams)
-    arr, n = _segments(segments)
-    tarr = _trims(trims, n)
-    if dst is None and not layout_only:
-        dst = np.empty(delivery_plan(counts, segments, J, encoding, trims=trims)["total_bytes"], np.uint8)
-    samples, offsets = np.zeros(max(J, 0), np.int64), np.zeros(max(J, 0) + 1, np.int64)
-    first, count = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
-    rc = _ffi.load().vits_test_deliver_trimmed(device_id, _ffi.ptr(x), _ffi.ptr(counts), B, S, arr, tarr, n, J, code,
-                                               None if layout_only else _ffi.ptr(dst), 0 if layout_only else dst.nbytes,
-                                               _ffi.ptr(samples), _ffi.ptr(offsets), _ffi.ptr(first), _ffi.ptr(count))
-    if rc != 0:
-        raise SessionError(f"vits_test_deliver_trimmed failed [{rc}]: {_ffi.last_error(None)}")
-    streams = None if layout_only else [dst[int(offsets[j]):int(offsets[j + 1])].view(dtype) for j in range(J)]
-    return {"streams": streams, "stream_samples": samples, "stream_offsets": offsets, "kept_first": first[:n], "kept_count": count[:n]}
-
-
-def test_deliver_leveled(x, counts, segments, levels, sample_rate, trims=None, n_streams=None, encoding="pcm16", device_id=0,
-                         layout_only=False):
-    """vits_test_deliver_leveled: test_deliver_trimmed with levels (one Level, one per segment, or None) at sample_rate; the
-    result holds "loudness" (float64 [G]) and "gain" (float32 [G]) too."""
-    x = np.ascontiguousarray(x, np.float32)
-    counts = np.ascontiguousarray(counts, np.int64)
-    B, S = x.shape
-    segments = list(segments)
-    code, dtype = _encoding(encoding)
-    J = _n_streams(segments, n_streams)
-    arr, n = _segments(segments)
-    tarr, larr = _trims(trims, n), _levels(levels, n)
-    dst = None if layout_only else np.empty(delivery_plan(counts, segments, J, encoding, trims=trims)["total_bytes"], np.uint8)
-    samples, offsets = np.zeros(max(J, 0), np.int64), np.zeros(max(J, 0) + 1, np.int64)
-    first, count = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
-    loud, gain = np.full(max(n, 1), np.nan, np.float64), np.ones(max(n, 1), np.float32)
-    rc = _ffi.load().vits_test_deliver_leveled(device_id, _ffi.ptr(x), _ffi.ptr(counts), B, S, arr, tarr, larr, n, J, code,
-                                               int(sample_rate), None if layout_only else _ffi.ptr(dst),
-                                               0 if layout_only else dst.nbytes, _ffi.ptr(samples), _ffi.ptr(offsets),
-                                               _ffi.ptr(first), _ffi.ptr(count), _ffi.ptr(loud), _ffi.ptr(gain))
-    if rc != 0:
-        raise SessionError(f"vits_test_deliver_leveled failed [{rc}]: {_ffi.last_error(None)}")
-    streams = None if layout_only else [dst[int(offsets[j]):int(offsets[j + 1])].view(dtype) for j in range(J)]
-    return {"streams": streams, "stream_samples": samples, "stream_offsets": offsets, "kept_first": first[:n], "kept_count": count[:n],
-            "loudness": loud[:n], "gain": gain[:n]}
-
-
-def test_deliver_shaped(x, counts, segments, shapes, trims=None, levels=None, sample_rate=22050, n_streams=None, encoding="pcm16",
-                        device_id=0, dst=None, layout_only=False):
-    """vits_test_deliver_shaped: test_deliver_leveled with shapes (one Shape, one per segment, or None); `dst` as in
-    test_deliver_trimmed: a refusal raises SessionError and leaves a `dst` passed in untouched."""
+def _test_deliver(stage, x, counts, segments, n_streams, encoding, device_id, dst=None, layout_only=False, trims=None, levels=None,
+                  sample_rate=0, shapes=None):
+    """What the four test_deliver* helpers share.  stage 0 .. 3: vits_test_deliver, _trimmed, _leveled, _shaped - each entry takes
+    what the one before it takes and its own arrays.  -> the dict of test_deliver_leveled."""
+    name = ("vits_test_deliver", "vits_test_deliver_trimmed", "vits_test_deliver_leveled", "vits_test_deliver_shaped")[stage]
     x = np.ascontiguousarray(x, np.float32)
     counts = np.ascontiguousarray(counts, np.int64)
     B, S = x.shape
@@ -2186,15 +2077,45 @@ def test_deliver_shaped(x, counts, segments, shapes, trims=None, levels=None, sa
     samples, offsets = np.zeros(max(J, 0), np.int64), np.zeros(max(J, 0) + 1, np.int64)
     first, count = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
     loud, gain = np.full(max(n, 1), np.nan, np.float64), np.ones(max(n, 1), np.float32)
-    rc = _ffi.load().vits_test_deliver_shaped(device_id, _ffi.ptr(x), _ffi.ptr(counts), B, S, arr, tarr, larr, sarr, parr, n_points, n, J,
-                                              code, int(sample_rate), None if layout_only else _ffi.ptr(dst),
-                                              0 if layout_only else dst.nbytes, _ffi.ptr(samples), _ffi.ptr(offsets),
-                                              _ffi.ptr(first), _ffi.ptr(count), _ffi.ptr(loud), _ffi.ptr(gain))
+    args = [arr, tarr, larr, sarr, parr, n_points][:(1, 2, 3, 6)[stage]] + [n, J, code] + [int(sample_rate)] * (stage >= 2)
+    args += [None if layout_only else _ffi.ptr(dst), 0 if layout_only else dst.nbytes, _ffi.ptr(samples), _ffi.ptr(offsets)]
+    args += [_ffi.ptr(first), _ffi.ptr(count), _ffi.ptr(loud), _ffi.ptr(gain)][:(0, 2, 4, 4)[stage]]
+    rc = getattr(_ffi.load(), name)(device_id, _ffi.ptr(x), _ffi.ptr(counts), B, S, *args)
     if rc != 0:
-        raise SessionError(f"vits_test_deliver_shaped failed [{rc}]: {_ffi.last_error(None)}")
+        raise SessionError(f"{name} failed [{rc}]: {_ffi.last_error(None)}")
     streams = None if layout_only else [dst[int(offsets[j]):int(offsets[j + 1])].view(dtype) for j in range(J)]
     return {"streams": streams, "stream_samples": samples, "stream_offsets": offsets, "kept_first": first[:n], "kept_count": count[:n],
             "loudness": loud[:n], "gain": gain[:n]}
+
+
+def test_deliver(x, counts, segments, n_streams=None, encoding="pcm16", device_id=0, dst=None):
+    """vits_test_deliver: x [B, S] float32 and the rows' valid samples through the delivery kernels -> one array per stream,
+    views into `dst` (uint8; default: a buffer of exactly the plan's size, sized by delivery_plan).  A refusal raises
+    SessionError and leaves a `dst` passed in untouched."""
+    return _test_deliver(0, x, counts, segments, n_streams, encoding, device_id, dst)["streams"]
+
+
+def test_deliver_trimmed(x, counts, segments, trims=None, n_streams=None, encoding="pcm16", device_id=0, dst=None, layout_only=False):
+    """vits_test_deliver_trimmed: test_deliver with trims (one Trim, one per segment, or None) -> {"streams": one array per
+    stream, views into `dst` (uint8; default: a buffer of the untrimmed plan's size with the tails), "stream_samples",
+    "stream_offsets", "kept_first", "kept_count"}.  layout_only: dst = NULL - the scan runs, nothing is packed ("streams" is
+    None).  A refusal raises SessionError and leaves a `dst` passed in untouched."""
+    r = _test_deliver(1, x, counts, segments, n_streams, encoding, device_id, dst, layout_only, trims)
+    return {k: v for k, v in r.items() if k not in ("loudness", "gain")}
+
+
+def test_deliver_leveled(x, counts, segments, levels, sample_rate, trims=None, n_streams=None, encoding="pcm16", device_id=0,
+                         layout_only=False):
+    """vits_test_deliver_leveled: test_deliver_trimmed with levels (one Level, one per segment, or None) at sample_rate; the
+    result holds "loudness" (float64 [G]) and "gain" (float32 [G]) too."""
+    return _test_deliver(2, x, counts, segments, n_streams, encoding, device_id, None, layout_only, trims, levels, sample_rate)
+
+
+def test_deliver_shaped(x, counts, segments, shapes, trims=None, levels=None, sample_rate=22050, n_streams=None, encoding="pcm16",
+                        device_id=0, dst=None, layout_only=False):
+    """vits_test_deliver_shaped: test_deliver_leveled with shapes (one Shape, one per segment, or None); `dst` as in
+    test_deliver_trimmed: a refusal raises SessionError and leaves a `dst` passed in untouched."""
+    return _test_deliver(3, x, counts, segments, n_streams, encoding, device_id, dst, layout_only, trims, levels, sample_rate, shapes)
 
 
 def test_loudness_blocks(x, counts, sample_rate, firsts=None, device_id=0):

@@ -1,11 +1,13 @@
 // Driver of test_loudness_cpu.py: loudness.hpp + workspace.hpp + slab.hpp under the host compiler, no HIP.  Walks the levelled
-// delivery's buffers dry, over a slab of exactly that size and over one a byte short, and checks the chunk-to-chunk
+// delivery's buffers dry, over a slab of exactly that size and over one a byte short (and holds the one walk of a delivery
+// call against the hand-stated sequence: delivery_walk_check.hpp), and checks the chunk-to-chunk
 // transition of the filter's state against the recurrence itself.  One JSON object per line.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 
+#include "delivery_walk_check.hpp"
 #include "workspace.hpp"
 
 using namespace vitsmi;
@@ -35,7 +37,8 @@ int main() {
                             reinterpret_cast<const char *>(lb.e()) == reinterpret_cast<const char *>(lb.result) + 4 * lb.n_peaks;
         printf("{\"walk\": 1, \"B\": %d, \"S\": %d, \"Lc\": %d, \"delivery\": %zu, \"level\": %zu, \"fits\": %d, \"short_fits\": %d, "
                "\"chunks\": %zu, \"subs\": %zu, \"peaks\": %zu}\n",
-               B, S, kLoudChunk, dlv, all - dlv, (int)(real.fits() && inside), (int)tight.fits(), lb.n_chunks, lb.n_subs, lb.n_peaks);
+               B, S, kLoudChunk, dlv, all - dlv, (int)(real.fits() && inside && delivery_call_walk_agrees(B, S)), (int)tight.fits(),
+               lb.n_chunks, lb.n_subs, lb.n_peaks);
     }
     // the transition: kLoudChunk samples from a state z0 = (the same samples from rest) + M z0
     double c[10], m[16];

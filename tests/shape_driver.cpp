@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "delivery_walk_check.hpp"
 #include "workspace.hpp"
 
 using namespace vitsmi;
@@ -108,7 +109,8 @@ int main(int argc, char **argv) {
         const bool ok = !s0.segs && !s0.knots && real.fits() && real.used == dry.used && sizeof(ShapeKnot) == 16 &&
                         (char *)s.segs >= (char *)l.result + 4 * (l.n_peaks + l.n_subs) &&
                         (char *)s.knots >= (char *)s.segs + sizeof(ShapeSeg) * (size_t)B && (uintptr_t)s.knots % 16 == 0 &&
-                        (char *)s.knots + 16 * (size_t)n_points <= base + real.used;
+                        (char *)s.knots + 16 * (size_t)n_points <= base + real.used &&
+                        delivery_call_walk_agrees(B, 4097);  // (and the one walk of a delivery call carves the same)
         printf("{\"walk\":%d,\"ok\":%d,\"level\":%zu,\"with_shape\":%zu,\"points\":%lld,\"record\":%zu}\n", B, (int)ok, level, dry.used,
                (long long)n_points, sizeof(ShapeSeg));
     }

@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 
+#include "delivery_walk_check.hpp"
 #include "workspace.hpp"
 
 using namespace vitsmi;
@@ -100,7 +101,8 @@ int main() {
         const TrimBufs t = carve_trim(real, B);
         const bool ok = !t0.bounds && !t0.peak_all && real.fits() && real.used == dry.used &&
                         (char *)t.bounds >= (char *)d.peak + 8 * (size_t)B && (char *)t.peak_all >= (char *)t.bounds + 8 * (size_t)B &&
-                        (char *)t.peak_all + 4 * (size_t)B <= base + real.used;
+                        (char *)t.peak_all + 4 * (size_t)B <= base + real.used &&
+                        delivery_call_walk_agrees(B, 4097);  // (and the one walk of a delivery call carves the same)
         printf("{\"walk\":%d,\"ok\":%d,\"delivery\":%zu,\"with_trim\":%zu}\n", B, (int)ok, dlv, dry.used);
     }
     return 0;
