@@ -617,9 +617,9 @@ int vits_deliver_leveled(vits_handle *h, const vits_segment *segs, const vits_tr
  * the call's point count; more than 1 << 20 points in a call; a pos outside [0, INT_MAX]; positions of one segment that do
  * not ascend strictly (naming the point); a gain that is not finite, is negative, lies in (0, 2^-20) or is above 64;
  * everything vits_deliver_leveled refuses.  A rejected call leaves the last run deliverable and writes nothing to dst.
- * Not covered: the encoded stream (a fade-out cannot know where the stream ends); crossfades that overlap two segments; a
- * limiter; PipelinedSession / ShardedSynthesizer on the device path (they take the host fallback, audio_encoding.join_trimmed
- * / join_leveled with shapes=, which gives the same bytes). */
+ * Not covered: the encoded stream (a fade-out cannot know where the stream ends); crossfades that overlap two segments;
+ * PipelinedSession / ShardedSynthesizer on the device path (they take the host fallback, audio_encoding.join_trimmed
+ * / join_leveled with shapes=, which gives the same bytes).  A limiter: the next section, "limited delivery". */
 typedef struct {
     int32_t pos;           /* row sample index at the delivered rate, [0, INT_MAX] */
     float   gain;          /* 0, or [2^-20, 64] */
@@ -642,6 +642,73 @@ int vits_deliver_shaped(vits_handle *h, const vits_segment *segs, const vits_tri
                         const vits_shape *shapes, const vits_env_point *points, int64_t n_points, int n_segs, int n_streams,
                         int encoding, int sample_rate, void *dst, size_t dst_bytes, int64_t *stream_samples, int64_t *stream_offsets,
                         int64_t *kept_first, int64_t *kept_count, double *loudness, float *gain);
+
+/* ---- limited delivery: the shaped delivery with a look-ahead peak limiter as the last stage in front of the clip -------------
+ * A quiet voice levelled to a loudness target gets a gain that pushes its peaks past full scale, and so does a per-token
+ * boost.  vits_level.peak_ceiling answers by capping the gain - the target is then missed -, the clip by flattening the peaks.
+ * The entries below are vits_deliver_shaped with a gain per sample that ducks under the peaks instead.  One vits_limit runs
+ * parallel to each vits_segment; the text below is the specification (tests/limit_ref.py states it a second time, in NumPy),
+ * and it is made so that every byte can be checked exactly whatever parallel algorithm computes it: the gain is integer
+ * arithmetic up to one final division - no recursive smoother, no floating-point sum whose order matters.
+ *
+ * A limited segment (mode 1) has kept range [a, a + c) (the trimmed delivery's) and look-ahead L = lookahead.  u[j], j in
+ * [0, c), is the value of the existing sample formula up to and including `v = v * mul`: the levelled gain or the
+ * normalisation, the volume, the shape's multiplier - everything in front of the clip.
+ *   q[j] (int32): the gain this sample would need on its own, in units of 2^-16.  fabsf(u[j]) <= ceiling: q[j] = 65536.
+ *                Otherwise q[j] = (int32) floorf((ceiling / fabsf(u[j])) * 65536.0f): the quotient one correctly rounded fp32
+ *                division, its product with 2^16 exact.  (A NaN is not above the ceiling: 65536.)  q[k] = 65536 for every k
+ *                outside [0, c): a segment never sees its neighbours, nor the rest of its row.
+ *   M[j] = min(q[j], .., q[j + L]), j in [-L, c): the look-ahead.
+ *   S[j] = M[j - L] + .. + M[j]: the smoothing, a box of L + 1.  An integer, at most 1025 * 65536: it fits int32.
+ *   g[j] = (float) S[j] / (float) ((L + 1) * 65536): one int-to-float conversion (round to nearest even) and one correctly
+ *                rounded fp32 division.
+ *   sample:      v = u[j] * g[j] (one rounded product), then v = fminf(fmaxf(v, -ceiling), ceiling); then the clip and the
+ *                encoders, unchanged.
+ * What follows from it:
+ *   - every window that enters S[j] contains j, so in exact arithmetic g[j] <= ceiling / |u[j]| and the clamp only absorbs
+ *     rounding: no delivered sample of a limited segment exceeds `ceiling` in magnitude;
+ *   - where no sample of the segment exceeds the ceiling, S = (L + 1) * 65536 and g = 1.0f: every byte is vits_deliver_shaped's;
+ *   - with limits == NULL, or every mode 0, bytes and layout are vits_deliver_shaped's, bit for bit, and exactly the launches
+ *     of that entry are made;
+ *   - the layout never depends on the limits;
+ *   - peaks, the trim scan and the loudness measurement see the UNLIMITED audio, as they see the unshaped one;
+ *   - a faded segment still starts and ends at exactly 0;
+ *   - the gain begins to fall L samples ahead of a peak and has recovered L samples behind it: the window is symmetric,
+ *     2 L + 1 wide.
+ * Device side (csrc/limit.hip.hpp): two launches beside the existing ones, only when some segment has mode 1, behind the peak
+ * launch.  limit_gain_kernel writes g of every packed element into an fp32 buffer (1.0f in a segment that is not limited): a
+ * workgroup stages q of a piece of a segment with a halo of L on either side in LDS - recomputing u of the halo, never
+ * reading x outside the kept range -, forms M by doubling minima and S from prefix sums, all int32, then divides.
+ * delivery_pack_limited_kernel is the shaped pack's body with the product and the clamp above in front of the clip.  The
+ * quotients and products of the rule are the contraction-off functions of csrc/shape.hpp, on the host and on the device.
+ * Validation happens on the host before anything is enqueued or allocated; VITS_E_ARG, the message naming the segment index
+ * and the value: a mode outside 0..1; reserved != 0; of a limited segment: a ceiling that is not finite, is <= 0 or is > 1, a
+ * lookahead outside [1, VITS_LIMIT_MAX_LOOKAHEAD], a |volume| above 1024 (which keeps u finite); everything
+ * vits_deliver_shaped refuses.  (An all-zero vits_limit is "off".)  A rejected call leaves the last run deliverable and writes
+ * nothing to dst.
+ * Not covered: the encoded stream (a look-ahead there needs a carry across chunks and adds latency: a later change); a
+ * true-peak ceiling (the ceiling holds for the samples, not for the waveform between them); separate attack and release
+ * times.  PipelinedSession / ShardedSynthesizer take the host fallback (audio_encoding, limits=: the same bytes). */
+#define VITS_LIMIT_MAX_LOOKAHEAD 1024
+typedef struct {
+    int32_t mode;          /* 0 off, 1 on */
+    float   ceiling;       /* (0, 1]: no delivered sample of the segment exceeds it in magnitude */
+    int32_t lookahead;     /* L: samples at the delivered rate, [1, VITS_LIMIT_MAX_LOOKAHEAD] */
+    int32_t reserved;      /* 0 */
+} vits_limit;              /* 16 bytes */
+/* pure host code: the validation above of limits [n_segs] (nullable: nothing to refuse) over segs [n_segs] (nullable: the
+ * volumes are then not looked at) */
+int vits_limit_check(const vits_limit *limits, const vits_segment *segs, int n_segs);
+/* pure host code: the rule above for one segment - u [c] the unlimited values of its kept range, g [c] receives the gains;
+ * written for clarity, not for speed (c * L steps).  Mode 0: every g is 1. */
+int vits_limit_gains(const float *u, int64_t c, const vits_limit *limit, float *g);
+/* vits_deliver_shaped with limits [n_segs] (or NULL: none) behind n_points.  Input run, waiting, VITS_E_RANGE, dst == NULL and
+ * repeatability as vits_deliver_shaped; trims, levels, shapes and limits are each nullable.  The gain buffer is one float per
+ * delivered sample of staging: vits_reserve covers it. */
+int vits_deliver_limited(vits_handle *h, const vits_segment *segs, const vits_trim *trims, const vits_level *levels,
+                         const vits_shape *shapes, const vits_env_point *points, int64_t n_points, const vits_limit *limits, int n_segs,
+                         int n_streams, int encoding, int sample_rate, void *dst, size_t dst_bytes, int64_t *stream_samples,
+                         int64_t *stream_offsets, int64_t *kept_first, int64_t *kept_count, double *loudness, float *gain);
 
 /* ---- encoded streaming: a chunked run's chunks post-processed, encoded and masked on the device --------------------------
  * vits_run_chunked* hands every chunk over as fp32 [B][n]; vits_deliver refuses a chunked run.  The two entries below are the
@@ -893,6 +960,13 @@ int vits_test_deliver_shaped(int device_id, const float *x, const int64_t *count
                              int64_t n_points, int n_segs, int n_streams, int encoding, int sample_rate, void *dst, size_t dst_bytes,
                              int64_t *stream_samples, int64_t *stream_offsets, int64_t *kept_first, int64_t *kept_count,
                              double *loudness, float *gain);
+
+/* The limited delivery by value: as vits_test_deliver_shaped; everything else as vits_deliver_limited. */
+int vits_test_deliver_limited(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_segment *segs,
+                              const vits_trim *trims, const vits_level *levels, const vits_shape *shapes, const vits_env_point *points,
+                              int64_t n_points, const vits_limit *limits, int n_segs, int n_streams, int encoding, int sample_rate,
+                              void *dst, size_t dst_bytes, int64_t *stream_samples, int64_t *stream_offsets, int64_t *kept_first,
+                              int64_t *kept_count, double *loudness, float *gain);
 
 /* The encoded stream's kernel by value: x [B][S] host, counts [B] the rows' valid samples (within [0, S]; what lies behind
  * must not show).  Columns [0, S) are cut into pieces of piece_samples samples (the last one shorter); each piece goes through

@@ -74,6 +74,10 @@ class VitsShape(C.Structure):
                 ("first_point", C.c_int64)]
 
 
+class VitsLimit(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("ceiling", C.c_float), ("lookahead", C.c_int32), ("reserved", C.c_int32)]
+
+
 class VitsStreamFormat(C.Structure):
     _fields_ = [("encoding", C.c_int32), ("ref_peak", C.c_void_p), ("volume", C.c_void_p)]
 
@@ -112,6 +116,7 @@ EXPORTS = [
     "vits_loudness_filter", "vits_loudness_gate", "vits_level_gain", "vits_delivery_plan_leveled", "vits_deliver_leveled",
     "vits_test_loudness_blocks", "vits_test_deliver_leveled",
     "vits_shape_check", "vits_shape_gain", "vits_deliver_shaped", "vits_test_deliver_shaped",
+    "vits_limit_check", "vits_limit_gains", "vits_deliver_limited", "vits_test_deliver_limited",
     "vits_run_chunked_enc", "vits_run_vocoder_chunked_enc", "vits_test_stream_pack",
     "vits_test_layernorm", "vits_test_dds", "vits_test_cf_pre", "vits_test_rqs_inverse", "vits_test_ea_logw",
 ]
@@ -225,6 +230,12 @@ def load():
                                         vp, vp, vp]
     lib.vits_test_deliver_shaped.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int64, C.c_int, C.c_int, C.c_int,
                                              C.c_int, vp, C.c_size_t, vp, vp, vp, vp, vp, vp]
+    lib.vits_limit_check.argtypes = [vp, vp, C.c_int]
+    lib.vits_limit_gains.argtypes = [vp, C.c_int64, C.POINTER(VitsLimit), vp]
+    lib.vits_deliver_limited.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int64, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vp,
+                                         vp, vp, vp, vp, vp]
+    lib.vits_test_deliver_limited.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int64, vp, C.c_int, C.c_int,
+                                              C.c_int, C.c_int, vp, C.c_size_t, vp, vp, vp, vp, vp, vp]
     lib.vits_free_output.argtypes = [vp, C.POINTER(VitsOutput)]
     lib.vits_free_output.restype = None
     lib.vits_sync.argtypes = [vp]

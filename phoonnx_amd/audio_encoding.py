@@ -16,6 +16,10 @@ levelled, encoded and joined.
 `shape_multiplier` and the `shapes=` argument of the two joins are the same for the shaped delivery (include/vitsmi.h, "shaped
 delivery"): fades and a breakpoint envelope as one float32 multiplier per kept sample, operation by operation as the device
 computes it - the same bytes.
+
+`limit_gains` and the `limits=` argument of the two joins are the same for the limited delivery (include/vitsmi.h, "limited
+delivery"): the look-ahead peak limiter's gain per kept sample - integers up to one float32 division - and its product and
+clamp in front of the clip: the same bytes.
 """
 import io
 import math
@@ -111,9 +115,50 @@ def trim_range(x, n, trim):
     return a, e - a
 
 
-def scaled(audio: np.ndarray, peak, volume: float, mul=None) -> np.ndarray:
+LIMIT_MAX_LOOKAHEAD = 1024
+
+
+def limit_gains(u, ceiling, lookahead) -> np.ndarray:
+    """The limiter's gain of every sample of one segment whose unlimited values are u (float32 [c]): the rule of
+    include/vitsmi.h, "limited delivery" - q = floor(ceiling / |u| * 2^16) where |u| > ceiling, 2^16 elsewhere and outside the
+    segment; M = the minimum of q over the next lookahead samples; S = the sum of M over the last lookahead + 1;
+    g = float32(S) / float32((lookahead + 1) * 2^16).  Integers up to the division.  float32 [c]."""
+    u = np.asarray(u, np.float32).ravel()
+    c, L, ceil = u.size, int(lookahead), np.float32(ceiling)
+    if not (np.isfinite(ceil) and 0 < ceil <= 1):
+        raise ValueError(f"limit ceiling {ceiling} is not finite and within (0, 1]")
+    if not 1 <= L <= LIMIT_MAX_LOOKAHEAD:
+        raise ValueError(f"lookahead {lookahead} outside [1, {LIMIT_MAX_LOOKAHEAD}]")
+    mag = np.abs(u)
+    over = mag > ceil
+    q = np.full(c + 2 * L, 65536, np.int64)          # q[j] at index j + L, j in [-L, c + L)
+    with np.errstate(over="ignore"):
+        q[L:L + c][over] = np.floor((ceil / mag[over]) * np.float32(65536.0)).astype(np.int64)
+    # minima over L + 1 by doubling: m[t] = min q[t : t + span]
+    m, span = q, 1
+    while 2 * span <= L + 1:
+        m = np.minimum(m[:-span], m[span:])
+        span *= 2
+    M = np.minimum(m[:c + L], m[L + 1 - span:L + 1 - span + c + L])      # M[j] at index j + L, j in [-L, c)
+    E = np.concatenate([[0], np.cumsum(M)])
+    S = E[L + 1:L + 1 + c] - E[:c]
+    return S.astype(np.float32) / np.float32((L + 1) * 65536)
+
+
+def limited(v: np.ndarray, limit) -> np.ndarray:
+    """v (float32, the samples of one segment in front of the clip) under `limit` - anything with the fields ceiling and
+    lookahead, or None (v itself): one float32 product with limit_gains, then the clamp to +-ceiling."""
+    if limit is None:
+        return v
+    v = np.asarray(v, np.float32)
+    ceil = np.float32(limit.ceiling)
+    return np.minimum(np.maximum(v * limit_gains(v, ceil, limit.lookahead), -ceil), ceil).astype(np.float32)
+
+
+def scaled(audio: np.ndarray, peak, volume: float, mul=None, limit=None) -> np.ndarray:
     """The delivery's sample formula in float32: peak None - no normalisation; peak < 1e-8 - zeros.  mul (float32, one per
-    sample, or None): the shaped delivery's multiplier, one more product in front of the clip."""
+    sample, or None): the shaped delivery's multiplier, one more product in front of the clip.  limit (or None): the limited
+    delivery's limiter over these samples - one segment's - behind it."""
     audio = np.asarray(audio, np.float32)
     if peak is not None:
         audio = np.zeros_like(audio) if np.float32(peak) < np.float32(1e-8) else audio / np.float32(peak)
@@ -121,6 +166,7 @@ def scaled(audio: np.ndarray, peak, volume: float, mul=None) -> np.ndarray:
         audio = audio * np.float32(volume)
     if mul is not None:
         audio = audio * np.asarray(mul, np.float32)
+    audio = limited(audio, limit)
     return np.clip(audio, np.float32(-1.0), np.float32(1.0)).astype(np.float32)
 
 
@@ -185,11 +231,24 @@ def _row_shapes(shapes, n):
     return shapes
 
 
-def join_trimmed(rows, encoding="pcm16", lead=0, tail=0, trim=None, normalize=1, volume=1.0, shapes=None):
+def _row_limits(limits, n):
+    """None, one limit or one per row (None in the list: off) -> a list of n"""
+    if limits is None:
+        return [None] * n
+    if hasattr(limits, "ceiling"):
+        return [limits] * n
+    limits = list(limits)
+    if len(limits) != n:
+        raise ValueError(f"limits must be one limit or one per row ({n}), got {len(limits)}")
+    return limits
+
+
+def join_trimmed(rows, encoding="pcm16", lead=0, tail=0, trim=None, normalize=1, volume=1.0, shapes=None, limits=None):
     """ONE stream of a trimmed delivery on the host: every row (its valid float32 samples) cut to trim_range, then `lead`
     elements of silence, the row's kept samples post-processed and encoded, `tail` elements of silence.  normalize: 0 none,
     1 by the peak of the row's kept range, 2 by the largest of those peaks.  shapes (None, one shape or one per row): each
-    row's kept samples times shape_multiplier in front of the clip; the peaks are those of the unshaped audio.
+    row's kept samples times shape_multiplier in front of the clip; the peaks are those of the unshaped audio.  limits (None,
+    one limit or one per row, None for a row without): each row's limiter (limit_gains) behind that, over its kept samples.
     Returns (data, [(a, c) per row])."""
     _check(encoding)
     kept = [trim_range(r, len(r), trim) for r in rows]
@@ -200,13 +259,13 @@ def join_trimmed(rows, encoding="pcm16", lead=0, tail=0, trim=None, normalize=1,
     elif normalize == 2:
         peaks = [max(peaks)] * len(cut) if cut else []
     pieces = []
-    if shapes is None:
+    if shapes is None and limits is None:
         for v, pk in zip(cut, peaks):
             pieces += [silence(lead, encoding), encode(scaled(v, pk, volume), encoding), silence(tail, encoding)]
         return (np.concatenate(pieces) if pieces else silence(0, encoding)), kept
-    for v, pk, (a, c), sh in zip(cut, peaks, kept, _row_shapes(shapes, len(cut))):
+    for v, pk, (a, c), sh, lm in zip(cut, peaks, kept, _row_shapes(shapes, len(cut)), _row_limits(limits, len(cut))):
         mul = None if sh is None else shape_multiplier(a, c, sh)
-        pieces += [silence(lead, encoding), encode(scaled(v, pk, volume, mul), encoding), silence(tail, encoding)]
+        pieces += [silence(lead, encoding), encode(scaled(v, pk, volume, mul, lm), encoding), silence(tail, encoding)]
     return (np.concatenate(pieces) if pieces else silence(0, encoding)), kept
 
 
@@ -286,9 +345,10 @@ def level_gain(loudness, peak, target_lufs, max_gain_db=30.0, peak_ceiling=0.0) 
     return np.float32(g)
 
 
-def leveled(audio: np.ndarray, gain, volume: float, mul=None) -> np.ndarray:
-    """The levelled delivery's sample formula in float32: one product with the gain, the volume's, (a shape's,) the clip."""
-    return scaled(np.asarray(audio, np.float32) * np.float32(gain), None, volume, mul)
+def leveled(audio: np.ndarray, gain, volume: float, mul=None, limit=None) -> np.ndarray:
+    """The levelled delivery's sample formula in float32: one product with the gain, the volume's, (a shape's, a limiter's,)
+    the clip."""
+    return scaled(np.asarray(audio, np.float32) * np.float32(gain), None, volume, mul, limit)
 
 
 def level_rows(rows, rate, level):
@@ -307,22 +367,23 @@ def level_rows(rows, rate, level):
     return loud, [level_gain(L, pk, level.target_lufs, level.max_gain_db, level.peak_ceiling) for L, pk in zip(loud, peaks)]
 
 
-def join_leveled(rows, rate, level, encoding="pcm16", lead=0, tail=0, trim=None, volume=1.0, shapes=None):
+def join_leveled(rows, rate, level, encoding="pcm16", lead=0, tail=0, trim=None, volume=1.0, shapes=None, limits=None):
     """ONE stream of a levelled delivery on the host: join_trimmed with every row's kept range brought to a loudness target
-    (level_rows) instead of peak-normalised.  shapes as in join_trimmed: the loudness is that of the unshaped audio.
+    (level_rows) instead of peak-normalised.  shapes and limits as in join_trimmed: the loudness is that of the unshaped,
+    unlimited audio.
     Returns (data, [(a, c) per row], loudness per row, gain per row)."""
     _check(encoding)
     kept = [trim_range(r, len(r), trim) for r in rows]
     cut = [np.asarray(r, np.float32)[a:a + c] for r, (a, c) in zip(rows, kept)]
     loud, gains = level_rows(cut, rate, level)
     pieces = []
-    if shapes is None:
+    if shapes is None and limits is None:
         for v, g in zip(cut, gains):
             pieces += [silence(lead, encoding), encode(leveled(v, g, volume), encoding), silence(tail, encoding)]
         return (np.concatenate(pieces) if pieces else silence(0, encoding)), kept, loud, gains
-    for v, g, (a, c), sh in zip(cut, gains, kept, _row_shapes(shapes, len(cut))):
+    for v, g, (a, c), sh, lm in zip(cut, gains, kept, _row_shapes(shapes, len(cut)), _row_limits(limits, len(cut))):
         mul = None if sh is None else shape_multiplier(a, c, sh)
-        pieces += [silence(lead, encoding), encode(leveled(v, g, volume, mul), encoding), silence(tail, encoding)]
+        pieces += [silence(lead, encoding), encode(leveled(v, g, volume, mul, lm), encoding), silence(tail, encoding)]
     return (np.concatenate(pieces) if pieces else silence(0, encoding)), kept, loud, gains
 
 

@@ -1,6 +1,6 @@
 // delivery_run.hip.hpp — a delivery from start to finish over a waveform on the device (include/vitsmi.h, "delivery" to
 // "shaped delivery"): the stages - the scan, the measurement, the enqueue, the reports - and delivery_run, the ONE sequence
-// behind vits_deliver, vits_deliver_trimmed / _leveled / _shaped and the four vits_test_deliver* hooks (vitsmi.hip).
+// behind vits_deliver, vits_deliver_trimmed / _leveled / _shaped / _limited and the vits_test_deliver* hooks (vitsmi.hip).
 //
 // Nothing here knows a handle.  Where the handle and a hook differ they hand it in: how the call's buffers (workspace.hpp,
 // carve_delivery_call) are obtained, and what follows the call's first wait.  Refusals come back as a code and a message
@@ -19,6 +19,7 @@
 
 #include "../../include/vitsmi.h"
 #include "delivery.hip.hpp"
+#include "limit.hip.hpp"
 #include "loudness.hip.hpp"
 #include "shape.hip.hpp"
 #include "workspace.hpp"
@@ -33,10 +34,13 @@ struct ShapeJob {
     ShapeBufs sb{};
 };
 
-// the job of a finished plan p (over the kept ranges first / kept [B]); shapes have passed shape_fault
+// the job of a finished plan p (over the kept ranges first / kept [B]); shapes have passed shape_fault (nullptr: a limited
+// call without shapes - every segment gets the shape without fades and points)
 inline void shape_job(const DeliveryPlan &p, const vits_segment *segs, const vits_shape *shapes, const vits_env_point *points,
                       const std::vector<int64_t> &first, const std::vector<int64_t> &kept, ShapeJob &job) {
     std::vector<int64_t> a(p.order.size()), c(p.order.size());
+    const std::vector<vits_shape> none(shapes ? 0 : p.order.size(), vits_shape{});
+    if (!shapes) shapes = none.data();
     for (size_t k = 0; k < p.order.size(); k++) {
         const int row = segs[p.order[k]].row;
         a[k] = first[row];
@@ -46,11 +50,18 @@ inline void shape_job(const DeliveryPlan &p, const vits_segment *segs, const vit
     shape_knots(job.table, points, job.knots);
 }
 
+// what a limited delivery adds on top of a ShapeJob: the records of the plan's segments (host) and carve_limit's buffers
+struct LimitJob {
+    std::vector<LimitSeg> table;
+    LimitBufs lb{};
+};
+
 // Everything a delivery puts on the stream: segment table up, peaks cleared, the launches, the copies into dst; then the
 // silence, on the host.  The caller synchronises.  db: carve_delivery's buffers for a waveform of at least the plan's rows.
-// job: a shaped delivery's tables (nullptr: none - launch_delivery, as ever).
+// job: a shaped delivery's tables (nullptr: none - launch_delivery, as ever).  lim: a limited delivery's (nullptr: none;
+// with one, `job` is there too - launch_delivery_limited in the place of launch_delivery_shaped).
 inline hipError_t delivery_enqueue(const float *d_x, const DeliveryPlan &p, const DeliveryBufs &db, int B, hipStream_t st, void *dst,
-                                   const ShapeJob *job = nullptr) {
+                                   const ShapeJob *job = nullptr, const LimitJob *lim = nullptr) {
     hipError_t e = hipSuccess;
     if (p.packed_elems > 0) {
         e = hipMemcpyAsync(db.segs, p.segs.data(), p.segs.size() * sizeof(DeliverySeg), hipMemcpyHostToDevice, st);
@@ -58,7 +69,12 @@ inline hipError_t delivery_enqueue(const float *d_x, const DeliveryPlan &p, cons
         if (job) {
             if (e == hipSuccess) e = hipMemcpyAsync(job->sb.segs, job->table.data(), job->table.size() * sizeof(ShapeSeg), hipMemcpyHostToDevice, st);
             if (e == hipSuccess) e = hipMemcpyAsync(job->sb.knots, job->knots.data(), job->knots.size() * sizeof(ShapeKnot), hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) e = launch_delivery_shaped(d_x, p, db.segs, db.peak, db.packed, job->sb.segs, job->sb.knots, st);
+            if (lim) {
+                if (e == hipSuccess) e = hipMemcpyAsync(lim->lb.segs, lim->table.data(), lim->table.size() * sizeof(LimitSeg), hipMemcpyHostToDevice, st);
+                if (e == hipSuccess)
+                    e = launch_delivery_limited(d_x, p, db.segs, db.peak, db.packed, job->sb.segs, job->sb.knots, lim->lb.segs, lim->lb.gain, st);
+            } else if (e == hipSuccess)
+                e = launch_delivery_shaped(d_x, p, db.segs, db.peak, db.packed, job->sb.segs, job->sb.knots, st);
         } else if (e == hipSuccess)
             e = launch_delivery(d_x, p, db.segs, db.peak, db.packed, st);
         for (size_t i = 0; i < p.copies.size() && e == hipSuccess; i++)
@@ -253,6 +269,7 @@ struct DeliveryRequest {
     void *dst;
     size_t dst_bytes;
     bool kept;  // the scan and the measurement in front of the delivery: every entry but vits_deliver and vits_test_deliver
+    const vits_limit *limits = nullptr;  // (nullable; behind the rest: the entries without limits state none)
 };
 
 // ... and where it wants the answers (each nullable)
@@ -278,9 +295,12 @@ DeliveryStatus delivery_run(const int64_t *counts, int B, int S, hipStream_t st,
     std::string e = delivery_plan(counts, B, S, rq.segs, rq.n_segs, rq.n_streams, rq.encoding, p0, rq.trims);
     if (e.empty()) e = level_plan_fault(rq.segs, rq.levels, rq.n_segs, rq.n_streams, rq.sample_rate);
     if (e.empty()) e = shape_fault(rq.shapes, rq.n_segs, rq.points, rq.n_points);
+    if (e.empty()) e = limit_fault(rq.limits, rq.segs, rq.n_segs);
     if (!e.empty()) return {VITS_E_ARG, e};
-    const bool shaped = any_shape(rq.shapes, rq.n_segs);
-    const DeliveryNeeds need{rq.kept, any_level(rq.levels, rq.n_segs), shaped, shape_knot_count(rq.shapes, rq.n_segs)};
+    const bool limited = rq.kept && any_limit(rq.limits, rq.n_segs);
+    const bool shaped = limited || any_shape(rq.shapes, rq.n_segs);  // (the limiter's kernels read every segment's shape record)
+    const DeliveryNeeds need{rq.kept, any_level(rq.levels, rq.n_segs), shaped,
+                             rq.shapes ? shape_knot_count(rq.shapes, rq.n_segs) : (limited ? (int64_t)rq.n_segs : 0), limited};
     if (!rq.kept) {
         if (!rq.dst) {  // the layout only: nothing is enqueued, nothing waited for
             delivery_report(p0, out.stream_samples, out.stream_offsets);
@@ -310,11 +330,14 @@ DeliveryStatus delivery_run(const int64_t *counts, int B, int S, hipStream_t st,
     }
     const DeliveryPlan &p = rq.kept ? pk : p0;
     ShapeJob job;
+    LimitJob lim;
     if (rq.dst) {
         job.sb = cb.shape;
+        lim.lb = cb.limit;
         if (shaped) shape_job(p, rq.segs, rq.shapes, rq.points, first, kept, job);
+        if (limited) limit_table(rq.limits, p.order, lim.table);
         // (wait whatever the enqueue answered: the plan's tables are the pageable sources of copies that may be in flight)
-        hipError_t err = delivery_enqueue(d_x, p, cb.dlv, B, st, rq.dst, shaped ? &job : nullptr);
+        hipError_t err = delivery_enqueue(d_x, p, cb.dlv, B, st, rq.dst, shaped ? &job : nullptr, limited ? &lim : nullptr);
         const hipError_t done = hipStreamSynchronize(st);
         if (err == hipSuccess) err = done;
         if (err != hipSuccess) return delivery_refusal(VITS_E_DEVICE, "delivery failed: %s", hipGetErrorString(err));

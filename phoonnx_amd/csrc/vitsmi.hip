@@ -2614,7 +2614,8 @@ int vits_reserve(vits_handle *h, int B, int T, int F) {
         // ... or vits_deliver's, with vits_deliver_trimmed's slots, vits_deliver_leveled's buffers and vits_deliver_shaped's
         // tables behind them (two breakpoints per token: what a per-token gain needs at most)
         const int64_t shape_pts = std::min<int64_t>((int64_t)2 * B * T, kShapeMaxPoints) + B;  // (knots: a segment's points + 1)
-        const DeliveryNeeds all{/*scan=*/true, /*levelled=*/true, /*shaped=*/true, shape_pts};
+        // ... and vits_deliver_limited's gain buffer last
+        const DeliveryNeeds all{/*scan=*/true, /*levelled=*/true, /*shaped=*/true, shape_pts, /*limited=*/true};
         const size_t io_dlv = carved_bytes([&](Carver &cv) { carve_delivery_call(cv, B, F * m.hop, all); });
         // ... or an encoded stream's chunk buffer: every chunk_frames <= F, i.e. chunks of up to F * hop samples
         const size_t io_sp = carved_bytes([&](Carver &cv) { carve_stream_pack(cv, B, (int64_t)F * m.hop); });
@@ -3207,7 +3208,7 @@ static int deliver_last_run(vits_handle *h, const DeliveryRequest &rq, const Del
             };
             if ((need.levelled || need.shaped) && carved_bytes(walk) > h->io.cap)
                 return delivery_refusal(VITS_E_NOMEM,
-                                        "a levelled or shaped delivery of this run needs %zu bytes of staging, %zu are there: vits_reserve covers it",
+                                        "a levelled, shaped or limited delivery of this run needs %zu bytes of staging, %zu are there: vits_reserve covers it",
                                         carved_bytes(walk), h->io.cap);
             if (int rc = slab_carve(h, h->io, "staging", walk)) return {rc, h->err};
             if (!h->d_out) return delivery_refusal(VITS_E_ARG, "no completed run to deliver");
@@ -3253,6 +3254,31 @@ int vits_deliver_shaped(vits_handle *h, const vits_segment *segs, const vits_tri
                         int encoding, int sample_rate, void *dst, size_t dst_bytes, int64_t *stream_samples, int64_t *stream_offsets,
                         int64_t *kept_first, int64_t *kept_count, double *loudness, float *gain) {
     return deliver_last_run(h, {segs, trims, levels, shapes, points, n_points, n_segs, n_streams, encoding, sample_rate, dst, dst_bytes, /*kept=*/true},
+                            {stream_samples, stream_offsets, kept_first, kept_count, loudness, gain});
+}
+
+// vits_deliver_limited: limits == nullptr (or every mode 0) is vits_deliver_shaped exactly
+int vits_limit_check(const vits_limit *limits, const vits_segment *segs, int n_segs) {
+    if (n_segs < 0) return fail(nullptr, VITS_E_ARG, "n_segs = %d is negative", n_segs);
+    const std::string e = limit_fault(limits, segs, n_segs);
+    if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
+    return VITS_OK;
+}
+
+int vits_limit_gains(const float *u, int64_t c, const vits_limit *limit, float *g) {
+    if (!limit || c < 0 || c > INT_MAX || (c > 0 && (!u || !g))) return fail(nullptr, VITS_E_ARG, "bad limiter arguments (c = %lld)", (long long)c);
+    const std::string e = limit_fault(limit, nullptr, 1);
+    if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
+    if (limit->mode == 0) std::fill(g, g + c, 1.0f);
+    else limit_gains(u, c, limit->ceiling, limit->lookahead, g);
+    return VITS_OK;
+}
+
+int vits_deliver_limited(vits_handle *h, const vits_segment *segs, const vits_trim *trims, const vits_level *levels,
+                         const vits_shape *shapes, const vits_env_point *points, int64_t n_points, const vits_limit *limits, int n_segs,
+                         int n_streams, int encoding, int sample_rate, void *dst, size_t dst_bytes, int64_t *stream_samples,
+                         int64_t *stream_offsets, int64_t *kept_first, int64_t *kept_count, double *loudness, float *gain) {
+    return deliver_last_run(h, {segs, trims, levels, shapes, points, n_points, n_segs, n_streams, encoding, sample_rate, dst, dst_bytes, /*kept=*/true, limits},
                             {stream_samples, stream_offsets, kept_first, kept_count, loudness, gain});
 }
 
@@ -4176,6 +4202,16 @@ int vits_test_deliver_shaped(int device_id, const float *x, const int64_t *count
                              double *loudness, float *gain) {
     return test_deliver_run(device_id, x, counts, B, S,
                             {segs, trims, levels, shapes, points, n_points, n_segs, n_streams, encoding, sample_rate, dst, dst_bytes, /*kept=*/true},
+                            {stream_samples, stream_offsets, kept_first, kept_count, loudness, gain});
+}
+
+int vits_test_deliver_limited(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_segment *segs,
+                              const vits_trim *trims, const vits_level *levels, const vits_shape *shapes, const vits_env_point *points,
+                              int64_t n_points, const vits_limit *limits, int n_segs, int n_streams, int encoding, int sample_rate,
+                              void *dst, size_t dst_bytes, int64_t *stream_samples, int64_t *stream_offsets, int64_t *kept_first,
+                              int64_t *kept_count, double *loudness, float *gain) {
+    return test_deliver_run(device_id, x, counts, B, S,
+                            {segs, trims, levels, shapes, points, n_points, n_segs, n_streams, encoding, sample_rate, dst, dst_bytes, /*kept=*/true, limits},
                             {stream_samples, stream_offsets, kept_first, kept_count, loudness, gain});
 }
 

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "delivery.hpp"
+#include "limit.hpp"
 #include "loudness.hpp"
 #include "model.hpp"
 #include "shape.hpp"
@@ -313,6 +314,20 @@ inline ShapeBufs carve_shape(Carver &cv, int B, int64_t n_knots) {
     return s;
 }
 
+// vits_deliver_limited on top of the four (a walk of its own, carved last): the limit records parallel to the segment table,
+// and the gain of every packed element - fp32 [B * S], since every row is in at most one segment.
+struct LimitBufs {
+    LimitSeg *segs;
+    float *gain;
+};
+
+inline LimitBufs carve_limit(Carver &cv, int B, int S) {
+    LimitBufs l{};
+    l.segs = cv.take<LimitSeg>(B);
+    l.gain = cv.take<float>((size_t)B * S);
+    return l;
+}
+
 // With an output rate set (vits_set_output_rate), the staging slab holds the run's RESULT once its inputs are consumed:
 // the resampled fp32 waveform [B][S_out] (a chunked run: the output samples of one chunk, never more than S_out per
 // row), the rows' valid input and output sample counts, the two generations of the chunked path's carry [B][K] (the
@@ -340,10 +355,13 @@ inline ResampleBufs carve_resample(Carver &cv, int B, int S_out, int K) {
 // The buffers of ONE delivery call, whichever entry it came through, and the one walk that carves them: the delivery's own
 // (carved here, or - `front` - those a carve_resample in the same walk has just carved behind the resampled waveform), then
 // what the call's stages need, in this order: the trim slots of a call that scans (every one but vits_deliver), the level
-// buffers where a segment is levelled, the shape tables where one is shaped.  vits_reserve walks it with everything on.
+// buffers where a segment is levelled, the shape tables where one is shaped - or limited: the limiter reads every segment's
+// shape record, a one-knot envelope of gain 1 where it has none -, the limiter's buffers last.  vits_reserve walks it with
+// everything on.
 struct DeliveryNeeds {
     bool scan, levelled, shaped;
-    int64_t n_knots;  // shape_knot_count
+    int64_t n_knots;       // shape_knot_count; a limited call without shapes: one per segment
+    bool limited = false;  // (implies shaped)
 };
 
 struct DeliveryCallBufs {
@@ -351,6 +369,7 @@ struct DeliveryCallBufs {
     TrimBufs trim;
     LevelBufs level;
     ShapeBufs shape;
+    LimitBufs limit;
 };
 
 inline DeliveryCallBufs carve_delivery_call(Carver &cv, int B, int S, const DeliveryNeeds &need, const DeliveryBufs *front = nullptr) {
@@ -360,6 +379,7 @@ inline DeliveryCallBufs carve_delivery_call(Carver &cv, int B, int S, const Deli
     c.trim = carve_trim(cv, B);
     if (need.levelled) c.level = carve_level(cv, B, S);
     if (need.shaped) c.shape = carve_shape(cv, B, need.n_knots);
+    if (need.limited) c.limit = carve_limit(cv, B, S);
     return c;
 }
 

@@ -288,6 +288,15 @@ class Shape:
     points: Sequence = ()
 
 
+@dataclass
+class Limit:
+    """The look-ahead peak limiter of one segment (vitsmi.h, vits_limit): no delivered sample of the segment exceeds `ceiling`
+    ((0, 1]) in magnitude; the gain begins to fall `lookahead` samples (at the delivered rate, [1, 1024]) ahead of a peak and
+    has recovered as many behind it.  In a list of limits, None stands for a segment that is not limited."""
+    ceiling: float = 1.0
+    lookahead: int = 110
+
+
 _CURVES = {"linear": 0, "smooth": 1}
 
 
@@ -384,6 +393,58 @@ def _shapes(shapes, n):
         except (AttributeError, TypeError, ValueError, OverflowError) as e:
             raise SessionError(f"segment {i}: shape: {e}") from None
     return arr, _ffi.ptr(_points(flat)), len(flat)
+
+
+# limits as the C structs hold them, for the tests of the validation: (mode, ceiling, lookahead, reserved) per segment
+RawLimits = namedtuple("RawLimits", "limits")
+
+
+def _limits(limits, n):
+    """None, one Limit or one per segment (None in the list: that segment is off) -> ctypes array of n vits_limit (None: no
+    limits)"""
+    if limits is None:
+        return None
+    if isinstance(limits, RawLimits):
+        return (_ffi.VitsLimit * max(len(limits.limits), 1))(*[_ffi.VitsLimit(int(m), float(c), int(l), int(r)) for m, c, l, r in limits.limits])
+    limits = [limits] * n if isinstance(limits, Limit) else list(limits)
+    if len(limits) != n:
+        raise SessionError(f"limits must be one Limit or one per segment ({n}), got {len(limits)}")
+    arr = (_ffi.VitsLimit * max(n, 1))()
+    for i, l in enumerate(limits):
+        try:
+            arr[i] = _ffi.VitsLimit(0, 1.0, 1, 0) if l is None else _ffi.VitsLimit(1, float(l.ceiling), int(l.lookahead), 0)
+        except (AttributeError, TypeError, ValueError, OverflowError) as e:
+            raise SessionError(f"segment {i}: limit: {e}") from None
+    return arr
+
+
+def limit_check(limits, segments=None, n=None):
+    """The validation of a limited delivery's limits (vits_limit_check: pure host code) over `segments` (None: the volumes are
+    not looked at); a refusal raises SessionError."""
+    if n is None:
+        n = 1 if isinstance(limits, Limit) else len(limits.limits if isinstance(limits, RawLimits) else list(limits))
+    sarr = None
+    if segments is not None:
+        sarr, ns = _segments(segments)
+        if ns != n:
+            raise SessionError(f"limit_check: {n} limits over {ns} segments")
+    rc = _ffi.load().vits_limit_check(_limits(limits, n), sarr, n)
+    if rc != 0:
+        raise SessionError(f"vits_limit_check failed [{rc}]: {_ffi.last_error(None)}")
+
+
+def limit_gains(u, limit):
+    """The gains of one segment whose unlimited values are u (float32 [c]) under `limit` (a Limit, or None: off) -> float32
+    [c] (vits_limit_gains: pure host code, the rule written for clarity: c * lookahead steps)."""
+    u = np.ascontiguousarray(u, np.float32)
+    if u.ndim != 1:
+        raise SessionError(f"u must be float32 [c], got {u.shape}")
+    g = np.empty(u.shape, np.float32)
+    arr = _limits(limit if isinstance(limit, RawLimits) else [limit], 1)
+    rc = _ffi.load().vits_limit_gains(_ffi.ptr(u), u.size, arr, _ffi.ptr(g))
+    if rc != 0:
+        raise SessionError(f"vits_limit_gains failed [{rc}]: {_ffi.last_error(None)}")
+    return g
 
 
 def shape_check(shapes, n=None):
@@ -1322,7 +1383,7 @@ class MiSession:
         return int(self.output_rate or self.input_rate or self.meta("sample_rate") or 22050)
 
     def deliver(self, segments, n_streams=None, encoding="pcm16", trims=None, return_kept=False, levels=None, sample_rate=None,
-                return_levels=False, shapes=None):
+                return_levels=False, shapes=None, limits=None):
         """The last run's audio, post-processed, encoded and laid out per request on the device (vitsmi.h, "delivery"):
         segments - Segment objects, each row of the run in at most one; encoding "pcm16" / "ulaw" / "alaw" / "f32".  Returns
         one NumPy array per stream (int16 / uint8 / float32), all views into ONE buffer in stream order - page-locked memory
@@ -1339,14 +1400,18 @@ class MiSession:
         (loudness float64 [G] - NaN for an unlevelled segment, -inf below 400 ms or the gates -, gain float32 [G]).
         shapes - one Shape or one per segment (vitsmi.h, "shaped delivery"): fades at either end of what is kept of a segment
         and a piecewise-linear volume over its row, applied by the pack launch; peaks, trim scan and loudness see the
-        unshaped audio, and the layout does not depend on the shapes."""
+        unshaped audio, and the layout does not depend on the shapes.
+        limits - one Limit or one per segment, None for a segment without one (vitsmi.h, "limited delivery"): a look-ahead
+        peak limiter as the last stage in front of the clip; peaks, trim scan and loudness see the unlimited audio, and the
+        layout does not depend on the limits."""
         segments = list(segments)
         code, dtype = _encoding(encoding)
         J = _n_streams(segments, n_streams)
         arr, n = _segments(segments)
         samples, offsets = np.zeros(max(J, 0), np.int64), np.zeros(max(J, 0) + 1, np.int64)
-        plain = trims is None and levels is None and shapes is None and not return_kept and not return_levels
+        plain = trims is None and levels is None and shapes is None and limits is None and not return_kept and not return_levels
         tarr = larr = sarr = parr = first = count = loud = gain = None  # (a plain delivery has none of them and pays for none)
+        marr = _limits(limits, n)
         n_points = rate = tails = 0
         if not plain:
             tarr, larr = _trims(trims, n), _levels(levels, n)
@@ -1369,12 +1434,16 @@ class MiSession:
             buf = _POOL.array((cap,), np.uint8) if self.pinned_results and cap else np.empty(cap, np.uint8)
             if plain:
                 rc = self._lib.vits_deliver(self._h, arr, n, J, code, _ffi.ptr(buf), cap, _ffi.ptr(samples), _ffi.ptr(offsets))
-            else:  # (vits_deliver_trimmed and vits_deliver_leveled are this entry with NULLs)
+            elif marr is None:  # (vits_deliver_trimmed and vits_deliver_leveled are this entry with NULLs)
                 rc = self._lib.vits_deliver_shaped(self._h, arr, tarr, larr, sarr, parr, n_points, n, J, code, rate, _ffi.ptr(buf), cap,
                                                    _ffi.ptr(samples), _ffi.ptr(offsets), _ffi.ptr(first), _ffi.ptr(count),
                                                    _ffi.ptr(loud), _ffi.ptr(gain))
+            else:
+                rc = self._lib.vits_deliver_limited(self._h, arr, tarr, larr, sarr, parr, n_points, marr, n, J, code, rate, _ffi.ptr(buf),
+                                                    cap, _ffi.ptr(samples), _ffi.ptr(offsets), _ffi.ptr(first), _ffi.ptr(count),
+                                                    _ffi.ptr(loud), _ffi.ptr(gain))
             if rc != 0:
-                self._raise("vits_deliver" if plain else "vits_deliver_shaped", rc)
+                self._raise("vits_deliver" if plain else ("vits_deliver_shaped" if marr is None else "vits_deliver_limited"), rc)
         streams = [buf[int(offsets[j]):int(offsets[j + 1])].view(dtype) for j in range(J)]
         if not (return_kept or return_levels):
             return streams
@@ -1399,7 +1468,7 @@ class MiSession:
     def synthesize_delivered(self, ids, lens, scales, sid=None, *, segments=None, n_streams=None, encoding="pcm16",
                              normalize=True, volume=1.0, seeds=None, durations=None, token_rate=None, noise_dp=None,
                              noise_z=None, return_durations=False, trim=None, levels=None, shapes=None, token_gain_db=None,
-                             gain_ramp=0.01):
+                             gain_ramp=0.01, limits=None):
         """One batched run and its delivery under one hold of the session lock: what leaves the GPU is the encoded audio
         of the plan and nothing else - the fp32 waveform is never copied to the host.  segments=None: one stream per row,
         with `normalize` / `volume` as scalars or [B] arrays (row b's own).  Everything in front of the delivery is
@@ -1412,6 +1481,7 @@ class MiSession:
         output-rate ratio) with gains float32(10 ** (dB / 20)) and a ramp of int(delivered_rate * gain_ramp) samples around
         every change.  No second run, no waveform on the host.  A segment with explicit points AND token gains is refused.
         With either, the result holds "shapes": the Shape every segment was delivered with.
+        limits - one Limit or one per segment (None in the list: off): deliver(..., limits=limits).
         Returns {"streams": [array per stream], "stream_samples": int64 [J], "y_lengths": int64 [B], "sample_lengths":
         int64 [B] (each row's valid samples at the delivered rate), "kept_first" / "kept_count": int64 [G] (what each
         segment delivers of its row: all of it without a trim)[, "durations"]}."""
@@ -1450,13 +1520,14 @@ class MiSession:
                 loud = gain = None
                 if tgains is not None:
                     used = self._token_shapes(segments, used, tgains, dur, lens, counts, gain_ramp)
-                if used is None and levels is None and trim is None:
+                if used is None and levels is None and trim is None and limits is None:
                     streams = self.deliver(segments, n_streams, encoding)
                     kept_first = np.zeros(len(segments), np.int64)
                     kept_count = np.array([counts[int(g.row)] for g in segments], np.int64)
                 else:
                     streams, kept_first, kept_count, *lv = self.deliver(segments, n_streams, encoding, trims=trim, return_kept=True,
-                                                                        levels=levels, return_levels=levels is not None, shapes=used)
+                                                                        levels=levels, return_levels=levels is not None, shapes=used,
+                                                                        limits=limits)
                     loud, gain = lv or (None, None)
             except RangeError as exc:
                 self._fall_back_to_bf16x6(exc)
@@ -1464,7 +1535,7 @@ class MiSession:
                                                  encoding=encoding, seeds=seeds, durations=durations, token_rate=token_rate,
                                                  noise_dp=noise_dp, noise_z=noise_z, return_durations=return_durations,
                                                  trim=trim, levels=levels, shapes=shapes, token_gain_db=token_gain_db,
-                                                 gain_ramp=gain_ramp)
+                                                 gain_ramp=gain_ramp, limits=limits)
         res = {"streams": streams, "stream_samples": np.array([a.size for a in streams], np.int64), "y_lengths": ylen,
                "sample_lengths": counts, "kept_first": kept_first, "kept_count": kept_count}
         if levels is not None:
@@ -2059,10 +2130,11 @@ def test_stream_pack(x, counts, piece_samples, encoding="pcm16", ref_peak=None, 
 # ---- the token-to-frame and frame-to-sample kernels by value (include/vitsmi.h: vits_test_durations ...) ----------------
 
 def _test_deliver(stage, x, counts, segments, n_streams, encoding, device_id, dst=None, layout_only=False, trims=None, levels=None,
-                  sample_rate=0, shapes=None):
-    """What the four test_deliver* helpers share.  stage 0 .. 3: vits_test_deliver, _trimmed, _leveled, _shaped - each entry takes
-    what the one before it takes and its own arrays.  -> the dict of test_deliver_leveled."""
-    name = ("vits_test_deliver", "vits_test_deliver_trimmed", "vits_test_deliver_leveled", "vits_test_deliver_shaped")[stage]
+                  sample_rate=0, shapes=None, limits=None):
+    """What the test_deliver* helpers share.  stage 0 .. 4: vits_test_deliver, _trimmed, _leveled, _shaped, _limited - each entry
+    takes what the one before it takes and its own arrays.  -> the dict of test_deliver_leveled."""
+    name = ("vits_test_deliver", "vits_test_deliver_trimmed", "vits_test_deliver_leveled", "vits_test_deliver_shaped",
+            "vits_test_deliver_limited")[stage]
     x = np.ascontiguousarray(x, np.float32)
     counts = np.ascontiguousarray(counts, np.int64)
     B, S = x.shape
@@ -2077,9 +2149,9 @@ def _test_deliver(stage, x, counts, segments, n_streams, encoding, device_id, ds
     samples, offsets = np.zeros(max(J, 0), np.int64), np.zeros(max(J, 0) + 1, np.int64)
     first, count = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
     loud, gain = np.full(max(n, 1), np.nan, np.float64), np.ones(max(n, 1), np.float32)
-    args = [arr, tarr, larr, sarr, parr, n_points][:(1, 2, 3, 6)[stage]] + [n, J, code] + [int(sample_rate)] * (stage >= 2)
+    args = [arr, tarr, larr, sarr, parr, n_points, _limits(limits, n)][:(1, 2, 3, 6, 7)[stage]] + [n, J, code] + [int(sample_rate)] * (stage >= 2)
     args += [None if layout_only else _ffi.ptr(dst), 0 if layout_only else dst.nbytes, _ffi.ptr(samples), _ffi.ptr(offsets)]
-    args += [_ffi.ptr(first), _ffi.ptr(count), _ffi.ptr(loud), _ffi.ptr(gain)][:(0, 2, 4, 4)[stage]]
+    args += [_ffi.ptr(first), _ffi.ptr(count), _ffi.ptr(loud), _ffi.ptr(gain)][:(0, 2, 4, 4, 4)[stage]]
     rc = getattr(_ffi.load(), name)(device_id, _ffi.ptr(x), _ffi.ptr(counts), B, S, *args)
     if rc != 0:
         raise SessionError(f"{name} failed [{rc}]: {_ffi.last_error(None)}")
@@ -2116,6 +2188,14 @@ def test_deliver_shaped(x, counts, segments, shapes, trims=None, levels=None, sa
     """vits_test_deliver_shaped: test_deliver_leveled with shapes (one Shape, one per segment, or None); `dst` as in
     test_deliver_trimmed: a refusal raises SessionError and leaves a `dst` passed in untouched."""
     return _test_deliver(3, x, counts, segments, n_streams, encoding, device_id, dst, layout_only, trims, levels, sample_rate, shapes)
+
+
+def test_deliver_limited(x, counts, segments, limits, shapes=None, trims=None, levels=None, sample_rate=22050, n_streams=None,
+                         encoding="pcm16", device_id=0, dst=None, layout_only=False):
+    """vits_test_deliver_limited: test_deliver_shaped with limits (one Limit, one per segment - None in the list: off -, or
+    None); `dst` as in test_deliver_trimmed: a refusal raises SessionError and leaves a `dst` passed in untouched."""
+    return _test_deliver(4, x, counts, segments, n_streams, encoding, device_id, dst, layout_only, trims, levels, sample_rate, shapes,
+                         limits)
 
 
 def test_loudness_blocks(x, counts, sample_rate, firsts=None, device_id=0):

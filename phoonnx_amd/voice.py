@@ -521,6 +521,21 @@ class TTSVoice:
         fi, fo = int(self.sample_rate * fade_in), int(self.sample_rate * fade_out)
         return Shape(fi, fo, fade_curve) if fi or fo else None
 
+    def _limit(self, limit_ceiling: float, limit_lookahead: float):
+        """limit_ceiling / limit_lookahead (seconds) of the encoded entries -> a session.Limit with the look-ahead in samples
+        at the delivered rate (round(limit_lookahead * sample_rate)), or None when limit_ceiling is 0."""
+        from .session import Limit
+        if not (np.isfinite(limit_ceiling) and 0.0 <= limit_ceiling <= 1.0):
+            raise ValueError(f"limit_ceiling must be within (0, 1], 0 for no limiter (got {limit_ceiling})")
+        if limit_ceiling == 0.0:
+            return None
+        if not (np.isfinite(limit_lookahead) and limit_lookahead >= 0.0):
+            raise ValueError(f"limit_lookahead must be a finite number of seconds >= 0 (got {limit_lookahead})")
+        L = int(round(limit_lookahead * self.sample_rate))
+        if not 1 <= L <= 1024:
+            raise ValueError(f"limit_lookahead {limit_lookahead} s is {L} samples at {self.sample_rate} Hz: outside [1, 1024]")
+        return Limit(float(limit_ceiling), L)
+
     @staticmethod
     def _group_db(phoneme_gain_db, k: int, groups) -> List[float]:
         """phoneme_gain_db(k, [the tokens of sentence k's groups]) -> one dB value per phoneme id: all ids of a group, its
@@ -566,7 +581,8 @@ class TTSVoice:
                            sentence_silence: float = 0.0, normalize_scope: str = "sentence",
                            alignments: bool = False, trim_silence=None, trailing_silence: float = 0.0, loudness=None,
                            loudness_scope: str = "sentence", peak_ceiling: float = 0.0, max_gain_db: float = 30.0,
-                           fade_in: float = 0.0, fade_out: float = 0.0, fade_curve: str = "linear", phoneme_gain_db=None):
+                           fade_in: float = 0.0, fade_out: float = 0.0, fade_curve: str = "linear", phoneme_gain_db=None,
+                           limit_ceiling: float = 0.0, limit_lookahead: float = 0.005):
         """Extension: the whole text as ONE stream of encoded audio ("pcm16", "ulaw", "alaw", "f32"; audio_encoding).  All
         sentences render in one batch; with a session that delivers (MiSession.synthesize_delivered) post-processing,
         encoding and the packing happen on the device and only the encoded audio crosses the bus; any other session
@@ -594,6 +610,11 @@ class TTSVoice:
         10 ms around each change.  Both are a time-varying volume in front of the clip (vitsmi.h, "shaped delivery"): on the
         device with a session that delivers, by audio_encoding's shapes= otherwise - the same bytes; peaks, trimming and
         loudness see the unshaped audio.  phoneme_gain_db needs a session that reports durations.
+        limit_ceiling (0: off; else within (0, 1]) puts a look-ahead peak limiter behind all of that, in front of the clip
+        (vitsmi.h, "limited delivery"): no sample of a sentence exceeds the ceiling, and the gain ducks under a peak from
+        limit_lookahead seconds ahead of it to as long behind it (round(limit_lookahead * sample_rate) samples, within
+        [1, 1024]) - a loudness target or a boost can then be reached without flattening the peaks.  On the device with a
+        session that delivers, by audio_encoding's limits= otherwise: the same bytes.
         Returns an audio_encoding.EncodedAudio."""
         from . import audio_encoding as ae
         from .sharding import pad_batch
@@ -605,6 +626,7 @@ class TTSVoice:
         trim = self._trim(trim_silence, trailing_silence)
         level = self._level(loudness, loudness_scope, peak_ceiling, max_gain_db, [cfg])
         shape = self._shape(fade_in, fade_out, fade_curve)
+        limit = self._limit(limit_ceiling, limit_lookahead)
         tail = trim.tail_samples if trim is not None else 0
         kept = loud = gains = None
         want_dur = alignments and hasattr(self.session, "last_durations") and hasattr(self.session, "synthesize_batch")
@@ -634,6 +656,8 @@ class TTSVoice:
                 more["shapes"] = shape
             if token_db is not None:
                 more["token_gain_db"], more["gain_ramp"] = self._padded_db(token_db), _GAIN_RAMP
+            if limit is not None:  # (passed down only when asked for: sessions from before the limiter do not know the keyword)
+                more["limits"] = limit
             out = self.session.synthesize_delivered(ids, lens, self._scales(cfg), sid, segments=segs, n_streams=1,
                                                     encoding=encoding, return_durations=want_dur, **more)
             data = out["streams"][0]
@@ -655,6 +679,8 @@ class TTSVoice:
             norm = 0 if not cfg.normalize_audio else (2 if normalize_scope == "text" else 1)
             # (without fades and gains: exactly the calls made before there were any)
             more = {} if shape is None and token_db is None else {"shapes": self._row_shapes(shape, token_db, durs, counts)}
+            if limit is not None:
+                more["limits"] = limit
             if level is not None:
                 data, cut, loud, gains = ae.join_leveled([np.atleast_1d(a) for a in audios], self.sample_rate, level, encoding, lead,
                                                          tail, trim, cfg.volume, **more)
@@ -777,7 +803,8 @@ class TTSVoice:
                                     sentence_silence: float = 0.0, alignments: bool = False, trim_silence=None,
                                     trailing_silence: float = 0.0, loudness=None, loudness_scope: str = "sentence",
                                     peak_ceiling: float = 0.0, max_gain_db: float = 30.0, fade_in: float = 0.0,
-                                    fade_out: float = 0.0, fade_curve: str = "linear", phoneme_gain_db=None):
+                                    fade_out: float = 0.0, fade_curve: str = "linear", phoneme_gain_db=None,
+                                    limit_ceiling: float = 0.0, limit_lookahead: float = 0.005):
         """Extension: synthesize_requests with every request's audio returned as one stream of encoded audio
         (audio_encoding.EncodedAudio; the pause of synthesize_encoded in front of each sentence).  The batching is
         synthesize_requests': sentences sorted by length, max_batch at a time, each with its request's settings and seed.
@@ -792,13 +819,15 @@ class TTSVoice:
         render in different runs, so the device delivers them cut but unlevelled as float32 and the host levels them
         (audio_encoding.level_rows).  fade_in / fade_out / fade_curve / phoneme_gain_db as in synthesize_encoded, for every
         sentence of every request (phoneme_gain_db's sentence_index counts within its request); with loudness scope "text"
-        the host that levels applies them too (audio_encoding.shape_multiplier)."""
+        the host that levels applies them too (audio_encoding.shape_multiplier).  limit_ceiling / limit_lookahead as in
+        synthesize_encoded, for every sentence of every request (where the host levels, it limits too)."""
         from . import audio_encoding as ae
         ae._check(encoding)
         lead = self._lead_samples(sentence_silence)
         trim = self._trim(trim_silence, trailing_silence)
         shape = self._shape(fade_in, fade_out, fade_curve)
         shaped = shape is not None or phoneme_gain_db is not None
+        limit = self._limit(limit_ceiling, limit_lookahead)
         level = self._level(loudness, loudness_scope, peak_ceiling, max_gain_db,
                             [cfg if cfg is not None else SynthesisConfig() for _, cfg in requests])
         tail = trim.tail_samples if trim is not None else 0
@@ -824,7 +853,7 @@ class TTSVoice:
             """a request's kept rows (float32, unlevelled) -> (encoded pieces, loudness, gains); muls: their shapes' multipliers"""
             loud, gains = ae.level_rows(rows, self.sample_rate, level)
             muls = muls if muls is not None else [None] * len(rows)
-            return [ae.encode(ae.leveled(v, g, volume, m), encoding) for v, g, m in zip(rows, gains, muls)], loud, gains
+            return [ae.encode(ae.leveled(v, g, volume, m, limit), encoding) for v, g, m in zip(rows, gains, muls)], loud, gains
 
         def request_db(r, text, cfg):
             """the dB per phoneme id of every sentence of request r, or None"""
@@ -859,18 +888,18 @@ class TTSVoice:
                     result.append(join(pieces, [c.phoneme_alignments for c in cs] if want_al(cs) else None,
                                        kept if trim is not None else None, loud, gains))
                 return result
-            if shaped:
-                # the rows as rendered, each cut (or whole), shaped in front of the clip
+            if shaped or limit is not None:
+                # the rows as rendered, each cut (or whole), shaped and limited in front of the clip
                 chunks = self.synthesize_requests(requests, seeds=seeds, max_batch=max_batch, alignments=alignments, postprocess=False,
                                                   **more)
                 result = []
                 for r, ((text, cfg), cs) in enumerate(zip(requests, chunks)):
                     cfg = cfg if cfg is not None else SynthesisConfig()
-                    shapes = host_shapes(r, text, cfg, cs)
+                    shapes = host_shapes(r, text, cfg, cs) or [None] * len(cs)
                     pieces, kept = [], []
                     for c, sh in zip(cs, shapes):
                         data, k = ae.join_trimmed([c.audio_float_array], encoding, 0, 0, trim, 1 if cfg.normalize_audio else 0,
-                                                  cfg.volume, shapes=[sh])
+                                                  cfg.volume, shapes=None if sh is None else [sh], limits=limit)
                         pieces.append(data)
                         kept += k
                     result.append(join(pieces, [c.phoneme_alignments for c in cs] if want_al(cs) else None,
@@ -939,6 +968,8 @@ class TTSVoice:
                     more["shapes"] = shape
                 if phoneme_gain_db is not None:
                     more["token_gain_db"], more["gain_ramp"] = self._padded_db([db_of[r, k] for r, k, _ in run]), _GAIN_RAMP
+            if limit is not None and not host_level:  # (scope "text": the host that levels limits too)
+                more["limits"] = limit
             need_dur = want_dur or (host_level and phoneme_gain_db is not None)
             out = self.session.synthesize_delivered(ids, lens, scales, sid, segments=segs, n_streams=len(run),
                                                     encoding="f32" if host_level else encoding, seeds=row_seeds,
