@@ -617,7 +617,7 @@ int vits_deliver_leveled(vits_handle *h, const vits_segment *segs, const vits_tr
  * the call's point count; more than 1 << 20 points in a call; a pos outside [0, INT_MAX]; positions of one segment that do
  * not ascend strictly (naming the point); a gain that is not finite, is negative, lies in (0, 2^-20) or is above 64;
  * everything vits_deliver_leveled refuses.  A rejected call leaves the last run deliverable and writes nothing to dst.
- * Not covered: the encoded stream (a fade-out cannot know where the stream ends); crossfades that overlap two segments;
+ * Not covered: crossfades that overlap two segments (the encoded stream: "shaped streaming" below);
  * PipelinedSession / ShardedSynthesizer on the device path (they take the host fallback, audio_encoding.join_trimmed
  * / join_leveled with shapes=, which gives the same bytes).  A limiter: the next section, "limited delivery". */
 typedef struct {
@@ -686,7 +686,7 @@ int vits_deliver_shaped(vits_handle *h, const vits_segment *segs, const vits_tri
  * lookahead outside [1, VITS_LIMIT_MAX_LOOKAHEAD], a |volume| above 1024 (which keeps u finite); everything
  * vits_deliver_shaped refuses.  (An all-zero vits_limit is "off".)  A rejected call leaves the last run deliverable and writes
  * nothing to dst.
- * Not covered: the encoded stream (a look-ahead there needs a carry across chunks and adds latency: a later change); a
+ * Not covered (the encoded stream: "shaped streaming" below, with a carry across chunks): a
  * true-peak ceiling (the ceiling holds for the samples, not for the waveform between them); separate attack and release
  * times.  PipelinedSession / ShardedSynthesizer take the host fallback (audio_encoding, limits=: the same bytes). */
 #define VITS_LIMIT_MAX_LOOKAHEAD 1024
@@ -754,13 +754,83 @@ int vits_run_chunked_enc(vits_handle *h, const int64_t *ids, const int64_t *lens
 int vits_run_vocoder_chunked_enc(vits_handle *h, const float *z, int B, int F, const int64_t *sid,
                                  const vits_stream_format *fmt, int chunk_frames, vits_enc_chunk_fn fn, void *user);
 
+/* ---- shaped streaming: the encoded stream with fades, a per-token volume and the look-ahead limiter ------------------------
+ * The encoded stream above is what a serving process uses when latency matters, and it lacked what the batch delivery has
+ * since "shaped delivery" and "limited delivery": a streamed sentence met the silence of its pause with a step, could not
+ * take a per-token volume, and clipped where the delivery ducks.  The two entries below are the two _enc entries with a
+ * shaping.  Trimming and levelling stay out: a stream cannot know its onset threshold or its integrated loudness in advance.
+ *
+ * The rule.  One sample of row b follows the rule of the limited delivery for a segment that keeps the whole row: the kept
+ * range is [0, n_b) (a stream does know where it ends: the frame counts are on the host before the first chunk is rendered);
+ * peak := ref_peak[b]; there is no level gain.  So fade_out counts back from the row's own end n_b, and the valid elements of
+ * a row, joined over the chunks, are the bytes the limited delivery gives for that row - bit for bit, in all four encodings,
+ * whatever chunk_frames is.  That equality is the specification; tests/stream_shape_ref.py composes it in NumPy.
+ *
+ * The shaping.  shapes: one vits_shape per row, or NULL.  points / n_points: the call's breakpoints, row samples at the
+ * delivered rate, as in the shaped delivery.  lookahead: one L for the call - 0: no limiter; otherwise within
+ * [1, VITS_LIMIT_MAX_LOOKAHEAD].  ceiling: host [B] or NULL - 0: this row is not limited; otherwise within (0, 1].  One L
+ * per call keeps a chunk rectangular: a row that is not limited gets g = 1 and the same delay.
+ * The plan callback (optional) is called once, on the calling thread, after the durations are on the host and before the
+ * first chunk is rendered: durations [B][T] are the frames per token and sample_counts [B] the rows' n_b at the delivered
+ * rate (a vocoder run has no tokens: T = 0, durations = NULL).  It may replace shapes, points, n_points and ceiling of
+ * `inout` (a copy of the call's shaping; what it points to must live until the run returns) - that is how breakpoints land
+ * on the token boundaries of a free-running utterance.  lookahead may not change.  A non-zero return ends the run with
+ * VITS_E_ARG.  What it writes is validated like up-front shaping; a refusal there ends the run with VITS_E_ARG and no chunk
+ * callback - but the run has begun: the PREVIOUS run's results are then gone, unlike after an up-front refusal.
+ *
+ * The timeline with lookahead = L > 0.  A rendered piece covers [first, first + n) and delivers
+ * [max(first - L, 0), first + n - L); the last piece delivers through total_samples; a piece that completes nothing makes no
+ * call (the resampler's rule).  So the first chunk arrives when it arrives today, L samples shorter, and the last one is L
+ * samples longer: the latency is L samples of audio, not time.  total_samples does not change.  valid[b] is the clamp of
+ * n_b against the delivered range.  peak[b] is the running peak over what has been RENDERED so far: it runs up to L samples
+ * ahead of what has been delivered, is still non-decreasing and still final after the last chunk.  With L = 0 the timeline
+ * is the encoded stream's.
+ *
+ * With shaping == NULL, or with no fades, no points, no plan and lookahead == 0, the entries make exactly the launches and
+ * bytes of the _enc entries (which forward here with NULL).
+ * Device side (csrc/stream_shape.hip.hpp): with L = 0 stream_pack_shaped_kernel, the stream's kernel with the shaped
+ * delivery's multiplier in front of the clip; with L > 0 stream_pack_limited_kernel, ONE launch per chunk - a workgroup
+ * stages q of a tile of the delivered range with a halo of L on either side, runs the limited delivery's minima and prefix
+ * sums in LDS, applies, clamps, encodes and stores whole 16-byte cells - and a small kernel that keeps the last 2 L raw
+ * samples of every row for the next chunk (the carry, [B][2 L] floats in two generations).
+ * Validation happens on the host before anything is enqueued or allocated; VITS_E_ARG, the message naming the row and the
+ * value: everything the shape check refuses (rows in the place of segments); a lookahead outside [0, 1024]; a ceiling that
+ * is not finite or lies outside {0} and (0, 1]; a |volume[b]| above 1024 on a limited row; everything the _enc entries
+ * refuse.  vits_reserve covers the stream's buffers for L = 1024 and two breakpoints per token.
+ * Not covered: trimming and loudness in a stream; a look-ahead that differs per row; crossfades between sentences; a
+ * true-peak ceiling.  PipelinedSession / ShardedSynthesizer take the host fallback (audio_encoding: the same chunks). */
+struct vits_stream_shaping;
+typedef int (*vits_stream_plan_fn)(void *user, int B, int T, const int64_t *durations, const int64_t *sample_counts,
+                                   struct vits_stream_shaping *inout);
+typedef struct vits_stream_shaping {
+    const vits_shape *shapes;        /* [B] or NULL; fade_out counts back from the row's own end */
+    const vits_env_point *points;    /* the call's breakpoints */
+    int64_t n_points;
+    const float *ceiling;            /* host [B] or NULL; 0: the row is not limited, else (0, 1] */
+    int32_t lookahead;               /* L for the call: 0 no limiter, else [1, VITS_LIMIT_MAX_LOOKAHEAD] */
+    int32_t reserved;                /* padding, stated: not read */
+    vits_stream_plan_fn plan;        /* or NULL */
+    void *plan_user;
+} vits_stream_shaping;               /* 56 bytes */
+/* pure host code: the validation above of a shaping (nullable: nothing to refuse) over B rows; fmt (nullable) gives the
+ * volumes of the limited rows */
+int vits_stream_shaping_check(const vits_stream_shaping *shaping, const vits_stream_format *fmt, int B);
+/* pure host code: the timeline above - what the rendered piece [first, first + n) of rows of `total` samples delivers */
+int vits_stream_emit_range(int64_t first, int64_t n, int is_last, int64_t total, int lookahead, int64_t *e_first, int64_t *e_n);
+int vits_run_chunked_enc_shaped(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
+                                const vits_noise *noise, const vits_controls *ctl, const vits_stream_format *fmt,
+                                const vits_stream_shaping *shaping, int chunk_frames, vits_enc_chunk_fn fn, void *user);
+int vits_run_vocoder_chunked_enc_shaped(vits_handle *h, const float *z, int B, int F, const int64_t *sid,
+                                        const vits_stream_format *fmt, const vits_stream_shaping *shaping, int chunk_frames,
+                                        vits_enc_chunk_fn fn, void *user);
+
 /* Size the handle's device workspaces NOW for requests of up to B utterances x T tokens that render up to F frames each
  * (the batch's longest utterance; T = 0 or F = 0 leaves that domain alone).  A run grows a workspace when a request
  * needs more than any before it - hipFree + hipMalloc of tens of GB at batch 32, a device-wide synchronisation that was
  * measured at 0.3 ms to 5 s - so a serving process calls this once at start-up with the largest request it admits (the
  * frame count of a batch depends on the durations the model predicts, i.e. on the noise as well: leave headroom), and no
  * request up to that size allocates device memory afterwards (vits_last_pcm16's int16 staging, vits_deliver's packed
- * buffer and an encoded stream's chunk buffer of such a request included).  onnxruntime has no counterpart (its arena grows the same way, voice.py:167-171 passes default
+ * buffer and an encoded stream's chunk buffer of such a request included, shaped or not).  onnxruntime has no counterpart (its arena grows the same way, voice.py:167-171 passes default
  * SessionOptions); nothing in the reference needs to call it.
  * INVALIDATES THE LAST RUN'S RESULTS when a workspace actually grows: the device waveform, frame counts and taps of the
  * last run live in those workspaces, so after a growing vits_reserve (or any run that grows one) vits_fetch_output /
@@ -976,6 +1046,14 @@ int vits_test_deliver_limited(int device_id, const float *x, const int64_t *coun
 int vits_test_stream_pack(int device_id, const float *x, const int64_t *counts, int B, int S, int piece_samples,
                           const vits_stream_format *fmt, void *bytes, size_t bytes_cap, int64_t *pitches, int32_t *valid,
                           float *peaks, int max_pieces);
+
+/* vits_test_stream_pack with a shaping (nullable; its plan is not called).  Every piece goes through the pipeline's kernels -
+ * the shaped one, or the limited one and the carry - and delivers the range of vits_stream_emit_range: firsts [piece] and
+ * ns [piece] receive it.  A piece that delivers nothing has n 0 and pitch 0, lands no bytes and leaves its valid and peaks
+ * untouched.  Returns the number of pieces. */
+int vits_test_stream_pack_shaped(int device_id, const float *x, const int64_t *counts, int B, int S, int piece_samples,
+                                 const vits_stream_format *fmt, const vits_stream_shaping *shaping, void *bytes, size_t bytes_cap,
+                                 int64_t *pitches, int32_t *valid, float *peaks, int64_t *firsts, int64_t *ns, int max_pieces);
 
 #ifdef __cplusplus
 }

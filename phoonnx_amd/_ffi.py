@@ -82,6 +82,17 @@ class VitsStreamFormat(C.Structure):
     _fields_ = [("encoding", C.c_int32), ("ref_peak", C.c_void_p), ("volume", C.c_void_p)]
 
 
+class VitsStreamShaping(C.Structure):
+    pass
+
+
+# int fn(void *user, int B, int T, const int64 *durations, const int64 *sample_counts, vits_stream_shaping *inout)
+STREAM_PLAN_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(VitsStreamShaping))
+
+VitsStreamShaping._fields_ = [("shapes", C.c_void_p), ("points", C.c_void_p), ("n_points", C.c_int64), ("ceiling", C.c_void_p),
+                              ("lookahead", C.c_int32), ("reserved", C.c_int32), ("plan", STREAM_PLAN_FN), ("plan_user", C.c_void_p)]
+
+
 # name -> (VITS_ENC_* code, element type): audio_encoding lists the names in the order of the header's enum
 ENCODINGS = {name: (code, audio_encoding.DTYPES[name]) for code, name in enumerate(audio_encoding.ENCODINGS)}
 
@@ -118,6 +129,8 @@ EXPORTS = [
     "vits_shape_check", "vits_shape_gain", "vits_deliver_shaped", "vits_test_deliver_shaped",
     "vits_limit_check", "vits_limit_gains", "vits_deliver_limited", "vits_test_deliver_limited",
     "vits_run_chunked_enc", "vits_run_vocoder_chunked_enc", "vits_test_stream_pack",
+    "vits_stream_shaping_check", "vits_stream_emit_range", "vits_run_chunked_enc_shaped", "vits_run_vocoder_chunked_enc_shaped",
+    "vits_test_stream_pack_shaped",
     "vits_test_layernorm", "vits_test_dds", "vits_test_cf_pre", "vits_test_rqs_inverse", "vits_test_ea_logw",
 ]
 
@@ -187,6 +200,14 @@ def load():
     lib.vits_run_chunked_enc.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.POINTER(VitsNoise), C.POINTER(VitsControls),
                                          C.POINTER(VitsStreamFormat), C.c_int, ENC_CHUNK_FN, vp]
     lib.vits_run_vocoder_chunked_enc.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.POINTER(VitsStreamFormat), C.c_int, ENC_CHUNK_FN, vp]
+    lib.vits_stream_shaping_check.argtypes = [C.POINTER(VitsStreamShaping), C.POINTER(VitsStreamFormat), C.c_int]
+    lib.vits_stream_emit_range.argtypes = [C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int, i64p, i64p]
+    lib.vits_run_chunked_enc_shaped.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.POINTER(VitsNoise), C.POINTER(VitsControls),
+                                                C.POINTER(VitsStreamFormat), C.POINTER(VitsStreamShaping), C.c_int, ENC_CHUNK_FN, vp]
+    lib.vits_run_vocoder_chunked_enc_shaped.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.POINTER(VitsStreamFormat),
+                                                        C.POINTER(VitsStreamShaping), C.c_int, ENC_CHUNK_FN, vp]
+    lib.vits_test_stream_pack_shaped.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(VitsStreamFormat),
+                                                 C.POINTER(VitsStreamShaping), vp, C.c_size_t, vp, vp, vp, vp, vp, C.c_int]
     lib.vits_test_stream_pack.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(VitsStreamFormat), vp, C.c_size_t,
                                           vp, vp, vp, C.c_int]
     lib.vits_last_durations.argtypes = [vp, i64p, C.c_size_t]

@@ -20,6 +20,10 @@ computes it - the same bytes.
 `limit_gains` and the `limits=` argument of the two joins are the same for the limited delivery (include/vitsmi.h, "limited
 delivery"): the look-ahead peak limiter's gain per kept sample - integers up to one float32 division - and its product and
 clamp in front of the clip: the same bytes.
+
+`emit_range` and `stream_shaped` are the same for the shaped, limited encoded stream (include/vitsmi.h, "shaped streaming"):
+the chunks of an fp32 stream shaped, limited across the chunk boundaries and encoded, on the engine's delayed timeline - the
+same chunks.
 """
 import io
 import math
@@ -155,10 +159,9 @@ def limited(v: np.ndarray, limit) -> np.ndarray:
     return np.minimum(np.maximum(v * limit_gains(v, ceil, limit.lookahead), -ceil), ceil).astype(np.float32)
 
 
-def scaled(audio: np.ndarray, peak, volume: float, mul=None, limit=None) -> np.ndarray:
-    """The delivery's sample formula in float32: peak None - no normalisation; peak < 1e-8 - zeros.  mul (float32, one per
-    sample, or None): the shaped delivery's multiplier, one more product in front of the clip.  limit (or None): the limited
-    delivery's limiter over these samples - one segment's - behind it."""
+def unlimited(audio: np.ndarray, peak, volume: float, mul=None) -> np.ndarray:
+    """The front of the delivery's sample formula in float32, up to the shaped delivery's product: peak None - no
+    normalisation; peak < 1e-8 - zeros; mul (float32, one per sample, or None) the multiplier."""
     audio = np.asarray(audio, np.float32)
     if peak is not None:
         audio = np.zeros_like(audio) if np.float32(peak) < np.float32(1e-8) else audio / np.float32(peak)
@@ -166,7 +169,14 @@ def scaled(audio: np.ndarray, peak, volume: float, mul=None, limit=None) -> np.n
         audio = audio * np.float32(volume)
     if mul is not None:
         audio = audio * np.asarray(mul, np.float32)
-    audio = limited(audio, limit)
+    return audio
+
+
+def scaled(audio: np.ndarray, peak, volume: float, mul=None, limit=None) -> np.ndarray:
+    """The delivery's sample formula in float32: peak None - no normalisation; peak < 1e-8 - zeros.  mul (float32, one per
+    sample, or None): the shaped delivery's multiplier, one more product in front of the clip.  limit (or None): the limited
+    delivery's limiter over these samples - one segment's - behind it."""
+    audio = limited(unlimited(audio, peak, volume, mul), limit)
     return np.clip(audio, np.float32(-1.0), np.float32(1.0)).astype(np.float32)
 
 
@@ -267,6 +277,64 @@ def join_trimmed(rows, encoding="pcm16", lead=0, tail=0, trim=None, normalize=1,
         mul = None if sh is None else shape_multiplier(a, c, sh)
         pieces += [silence(lead, encoding), encode(scaled(v, pk, volume, mul, lm), encoding), silence(tail, encoding)]
     return (np.concatenate(pieces) if pieces else silence(0, encoding)), kept
+
+
+def emit_range(first, n, is_last, total, lookahead):
+    """The timeline of a shaped stream (include/vitsmi.h, "shaped streaming"): the rendered piece [first, first + n) of rows of
+    `total` samples delivers (e_first, e_n) - everything whose look-ahead has been rendered, the last piece the rest."""
+    first, n, total, L = int(first), int(n), int(total), int(lookahead)
+    e_first = max(first - L, 0)
+    end = min(total if is_last else first + n - L, total)
+    return e_first, max(end - e_first, 0)
+
+
+def stream_shaped(chunks, counts, encoding="pcm16", ref_peak=None, volume=None, shapes=None, limits=None):
+    """The shaped, limited encoded stream on the host: `chunks` yields (first_sample, float32 [B, n], total_samples) - an fp32
+    stream, MiSession.synthesize_stream's -, counts (int [B], or a callable asked once, at the first chunk) are the rows'
+    valid samples.  ref_peak / volume: None or one per row; shapes: None, one shape or one per row, over the whole row (a
+    fade-out ends at the row's own end) - or a callable of the counts that gives them, asked with them; limits: None, one limit or one per row (None: that row is not limited), with ONE
+    lookahead L.  Yields (first_sample, data [B, n] in the encoding's dtype, valid int32 [B], peak float32 [B],
+    total_samples) - the chunks, timeline included, of the engine's shaped stream: a piece is delivered L samples late, the
+    last one L longer, one that completes nothing not at all; `peak` is the running max |x| over what has been rendered."""
+    _check(encoding)
+    state = None
+    for first, x, total in chunks:
+        x = np.asarray(x, np.float32)
+        B, n = x.shape
+        first, total = int(first), int(total)
+        if state is None:
+            cnt = np.asarray(counts() if callable(counts) else counts, np.int64)
+            shp, lim = _row_shapes(shapes(cnt) if callable(shapes) else shapes, B), _row_limits(limits, B)
+            ahead = sorted({int(l.lookahead) for l in lim if l is not None})
+            if len(ahead) > 1:
+                raise ValueError(f"limits: one lookahead per stream, got {ahead}")
+            L = ahead[0] if ahead else 0
+            muls = [None if shp[b] is None else shape_multiplier(0, cnt[b], shp[b]) for b in range(B)]
+            pk = [None] * B if ref_peak is None else list(np.broadcast_to(np.asarray(ref_peak, np.float32), (B,)))
+            vol = np.broadcast_to(np.asarray(1.0 if volume is None else volume, np.float32), (B,))
+            state = np.zeros((B, 2 * L), np.float32), np.zeros(B, np.float32)     # the carry, the running peaks
+        carry, peak = state
+        joined = np.concatenate([carry, x], axis=1)                  # samples [first - 2 L, first + n) of the rows
+        base = first - 2 * L
+        for b in range(B):
+            seen = x[b, :int(np.clip(cnt[b] - first, 0, n))]
+            if seen.size:
+                peak[b] = max(peak[b], np.max(np.abs(seen)))
+        state = joined[:, joined.shape[1] - 2 * L:], peak
+        ef, en = emit_range(first, n, first + n >= total, total, L)
+        if en == 0:
+            continue
+        data = np.full((B, en), SILENCE[encoding], DTYPES[encoding])
+        valid = np.clip(cnt - ef, 0, en).astype(np.int32)
+        for b in range(B):
+            if not valid[b]:
+                continue
+            # g of [ef, ef + valid) needs q of L samples on either side: u over [lo, hi), inside the row
+            lo, hi = max(ef - L, 0), int(min(ef + en + L, cnt[b]))
+            u = unlimited(joined[b, lo - base:hi - base], pk[b], vol[b], None if muls[b] is None else muls[b][lo:hi])
+            v = limited(u, lim[b])[ef - lo:ef - lo + int(valid[b])]
+            data[b, :int(valid[b])] = encode(np.clip(v, np.float32(-1.0), np.float32(1.0)).astype(np.float32), encoding)
+        yield ef, data, valid, peak.copy(), total
 
 
 def k_weighting(rate):

@@ -61,6 +61,59 @@ __device__ inline float limit_value(const float *x, const DeliverySeg &s, const 
     return shape_mul(v, mul);
 }
 
+// The parallel form of the rule, stated once for every kernel that stages q (limit_gain_kernel here, the limited stream pack
+// of stream_shape.hip.hpp): buf[0][t], t < n + 2 L, holds q of a piece of n samples with its halos, visible to the whole
+// workgroup (a barrier lies behind the staging).  Returns E, the exclusive prefix sums of M[0 .. n + L], in one of the two
+// buffers: S of the piece's sample i is E[i + L + 1] - E[i].  Every lane of the workgroup calls it with the same arguments;
+// its loops run trip counts that depend on n and L alone, and it ends behind a barrier.
+__device__ inline const int32_t *limit_window_sums(int32_t (*buf)[kLimitStage], int32_t *wave_sum, int32_t n, int32_t L) {
+    const int lane = threadIdx.x;
+    const int32_t W = L + 1, nq = n + 2 * L, nm = n + L;
+    int cur = 0, span = 1;  // buf[cur][t] = min q over [t, t + span)
+    while (2 * span <= W) {
+        for (int t = lane; t < nq; t += kDeliveryThreads) {
+            const int32_t a = buf[cur][t];
+            const int32_t b = t + span < nq ? buf[cur][t + span] : kLimitUnity;
+            buf[cur ^ 1][t] = b < a ? b : a;
+        }
+        __syncthreads();
+        cur ^= 1;
+        span *= 2;
+    }
+    // M[t] = min over [t, t + W) from two spans; M[nm] = 0 closes the prefix sums (t + W - span + span - 1 = t + L < nq)
+    int32_t *const M = buf[cur ^ 1];
+    for (int t = lane; t <= nm; t += kDeliveryThreads) {
+        int32_t m = 0;
+        if (t < nm) {
+            const int32_t a = buf[cur][t], b = buf[cur][t + W - span];
+            m = b < a ? b : a;
+        }
+        M[t] = m;
+    }
+    __syncthreads();
+    // exclusive prefix sums of M[0 .. nm] in place: lane owns [lane * K, lane * K + K)
+    const int K = (nm + 1 + kDeliveryThreads - 1) / kDeliveryThreads;
+    const int t0 = lane * K, t1 = t0 + K < nm + 1 ? t0 + K : nm + 1;
+    int32_t mine = 0;
+    for (int t = t0; t < t1; t++) mine += M[t];
+    int32_t incl = mine;
+    for (int o = 1; o < 64; o <<= 1) {
+        const int32_t up = __shfl_up(incl, o);
+        if ((lane & 63) >= o) incl += up;
+    }
+    if ((lane & 63) == 63) wave_sum[lane >> 6] = incl;
+    __syncthreads();
+    int32_t run = incl - mine;
+    for (int wv = 0; wv < (lane >> 6); wv++) run += wave_sum[wv];
+    for (int t = t0; t < t1; t++) {
+        const int32_t m = M[t];
+        M[t] = run;
+        run += m;
+    }
+    __syncthreads();
+    return M;
+}
+
 // grid ceil(P / kLimitTile): gain [P] receives g of every packed element (1.0f in a segment that is not limited)
 __global__ __launch_bounds__(kDeliveryThreads) void limit_gain_kernel(const float *x, const DeliverySeg *segs, int G, const unsigned *peak_bits,
                                                                       int64_t P, const ShapeSeg *shapes, const ShapeKnot *knots,
@@ -89,8 +142,8 @@ __global__ __launch_bounds__(kDeliveryThreads) void limit_gain_kernel(const floa
             for (int t = lane; t < n; t += kDeliveryThreads) gain[p0 + t] = 1.0f;
             continue;
         }
-        const int32_t L = lm.L, W = L + 1;
-        const int32_t nq = n + 2 * L, nm = n + L;  // staged q: j = j0 - L + t, t < nq; M: j = j0 - L + t, t < nm
+        const int32_t L = lm.L;
+        const int32_t nq = n + 2 * L;  // staged q: j = j0 - L + t, t < nq
         const ShapeSeg sh = shapes[g];
         LimitKnotWalk walk;
         bool ducks = false;  // some staged sample of this lane is above the ceiling
@@ -106,48 +159,7 @@ __global__ __launch_bounds__(kDeliveryThreads) void limit_gain_kernel(const floa
             for (int t = lane; t < n; t += kDeliveryThreads) gain[p0 + t] = 1.0f;
             continue;
         }
-        int cur = 0, span = 1;  // buf[cur][t] = min q over [t, t + span)
-        while (2 * span <= W) {
-            for (int t = lane; t < nq; t += kDeliveryThreads) {
-                const int32_t a = buf[cur][t];
-                const int32_t b = t + span < nq ? buf[cur][t + span] : kLimitUnity;
-                buf[cur ^ 1][t] = b < a ? b : a;
-            }
-            __syncthreads();
-            cur ^= 1;
-            span *= 2;
-        }
-        // M[t] = min over [t, t + W) from two spans; M[nm] = 0 closes the prefix sums (t + W - span + span - 1 = t + L < nq)
-        int32_t *const M = buf[cur ^ 1];
-        for (int t = lane; t <= nm; t += kDeliveryThreads) {
-            int32_t m = 0;
-            if (t < nm) {
-                const int32_t a = buf[cur][t], b = buf[cur][t + W - span];
-                m = b < a ? b : a;
-            }
-            M[t] = m;
-        }
-        __syncthreads();
-        // exclusive prefix sums of M[0 .. nm] in place: lane owns [lane * K, lane * K + K)
-        const int K = (nm + 1 + kDeliveryThreads - 1) / kDeliveryThreads;
-        const int t0 = lane * K, t1 = t0 + K < nm + 1 ? t0 + K : nm + 1;
-        int32_t mine = 0;
-        for (int t = t0; t < t1; t++) mine += M[t];
-        int32_t incl = mine;
-        for (int o = 1; o < 64; o <<= 1) {
-            const int32_t up = __shfl_up(incl, o);
-            if ((lane & 63) >= o) incl += up;
-        }
-        if ((lane & 63) == 63) wave_sum[lane >> 6] = incl;
-        __syncthreads();
-        int32_t run = incl - mine;
-        for (int wv = 0; wv < (lane >> 6); wv++) run += wave_sum[wv];
-        for (int t = t0; t < t1; t++) {
-            const int32_t m = M[t];
-            M[t] = run;
-            run += m;
-        }
-        __syncthreads();
+        const int32_t *const M = limit_window_sums(buf, wave_sum, n, L);
         // kept sample j0 + i: M indices [i, i + L]
         for (int i = lane; i < n; i += kDeliveryThreads) gain[p0 + i] = limit_g(M[i + L + 1] - M[i], L);
         __syncthreads();  // (the next piece stages into the same buffers)

@@ -32,6 +32,7 @@
 #include "model.hpp"
 #include "resample.hip.hpp"
 #include "stream_pack.hip.hpp"
+#include "stream_shape.hip.hpp"
 #include "test_dev.hip.hpp"
 #include "workspace.hpp"
 
@@ -141,6 +142,8 @@ struct ChunkSink {
     // the encoded form (vits_run_chunked_enc): fmt != nullptr, validated; the chunks go to efn, not to fn
     const vits_stream_format *fmt = nullptr;
     vits_enc_chunk_fn efn = nullptr;
+    // ... shaped (vits_run_chunked_enc_shaped): validated, nullable
+    const vits_stream_shaping *shaping = nullptr;
 };
 
 constexpr int kMaxRangeLaunches = 512;
@@ -1869,7 +1872,10 @@ __global__ void chunk_len_kernel(const int *ylen, int *out, int B, int lo, int n
 // The staging slab carved for the resampled result of B rows of S_in input samples.  The run's inputs lived there: every
 // kernel that read them precedes the resampler on the stream (and a growing slab waits for the stream first).
 // (sp: an encoded stream's buffers behind them in the same walk, for chunks of at most min(sp_n_max, S_out) samples)
-int resample_carve(vits_handle *h, int B, int64_t S_in, ResampleBufs &rb, int &S_out, StreamPackBufs *sp = nullptr, int64_t sp_n_max = 0) {
+// (ss: a shaped stream's buffers behind those, for a look-ahead of ss_L and ss_knots knots; sp_n_max then counts the L samples the
+// last chunk delivers beyond what it renders)
+int resample_carve(vits_handle *h, int B, int64_t S_in, ResampleBufs &rb, int &S_out, StreamPackBufs *sp = nullptr, int64_t sp_n_max = 0,
+                   StreamShapeBufs *ss = nullptr, int ss_L = 0, int64_t ss_knots = 0) {
     const ResamplePlan &p = h->rs.plan;
     const int64_t so = p.count(S_in);
     if (so > INT_MAX)
@@ -1880,6 +1886,7 @@ int resample_carve(vits_handle *h, int B, int64_t S_in, ResampleBufs &rb, int &S
         return slab_carve(h, h->io, "staging", [&](Carver &cv) {
             rb = carve_resample(cv, B, S_out, (int)p.K);
             *sp = carve_stream_pack(cv, B, sp_n_max < so ? sp_n_max : so);
+            if (ss) *ss = carve_stream_shape(cv, B, ss_L, ss_knots);
         });
     return slab_carve(h, h->io, "staging", [&](Carver &cv) { rb = carve_resample(cv, B, S_out, (int)p.K); });
 }
@@ -1946,14 +1953,56 @@ int render_chunks(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int
     const bool enc = sink.fmt != nullptr;
     const int enc_w = !enc ? 4 : (sink.fmt->encoding == VITS_ENC_PCM16 ? 2 : (sink.fmt->encoding == VITS_ENC_F32 ? 4 : 1));
     StreamPackBufs sp{};
+    // encoded form: the rows' valid samples (host: the callback's valid[]; device: the kernel's)
+    std::vector<int64_t> row_n;
+    if (enc) {
+        row_n.resize((size_t)B);
+        for (int b = 0; b < B; b++) {
+            const int64_t nb = (int64_t)(ylen ? h->h_ylen[b] : F) * hop;
+            row_n[b] = rs ? rp.count(nb) : nb;
+        }
+    }
+    // The shaped form of the encoded sink (vitsmi.h, "shaped streaming"): the plan callback first - the durations and the
+    // rows' sample counts are on the host, nothing of this run's audio exists yet -, then what it wrote through the checks of
+    // up-front shaping.  Without fades, points and look-ahead everything below is the unshaped stream's.
+    vits_stream_shaping shp{};
+    bool shaped = false;
+    if (enc && stream_shaped(sink.shaping, B)) {
+        shp = *sink.shaping;
+        if (shp.plan) {
+            // (the run has begun: whatever the callback answers, the previous run's waveform no longer belongs to the frame
+            // counts and durations on the host - a refusal below leaves "no completed run")
+            h->d_out = nullptr;
+            const bool tokens = ylen != nullptr && h->h_dur_B == B && h->h_dur_T > 0;
+            const int T = tokens ? h->h_dur_T : 0;
+            std::vector<int64_t> dur((size_t)B * T);
+            for (size_t i = 0; i < dur.size(); i++) dur[i] = (int64_t)h->h_dur[i];
+            if (shp.plan(shp.plan_user, B, T, tokens ? dur.data() : nullptr, row_n.data(), &shp) != 0)
+                return fail(h, VITS_E_ARG, "the stream's plan callback refused the run");
+            if (shp.lookahead != sink.shaping->lookahead)
+                return fail(h, VITS_E_ARG, "the stream's plan callback changed lookahead from %d to %d", sink.shaping->lookahead, shp.lookahead);
+            const std::string e = stream_shape_fault(&shp, sink.fmt->volume, B);
+            if (!e.empty()) return fail(h, VITS_E_ARG, "plan callback: %s", e.c_str());
+        }
+        shaped = shp.lookahead > 0 || any_shape(shp.shapes, B);
+    }
+    const int sL = shaped ? shp.lookahead : 0;  // the last chunk delivers sL samples more than it renders
+    const int64_t s_knots = shaped ? stream_knot_count(&shp, B) : 0;
+    StreamShapeBufs ssb{};
     if (rs && enc) {
         // (the chunk bound needs S_out, which the carve computes: state it from the same count)
         const int64_t so = rp.count((int64_t)F * hop);
-        if (int rc = resample_carve(h, B, (int64_t)F * hop, rb, S_out, &sp, resample_emit_cap(rp, chunk, F, hop, so))) return rc;
+        if (int rc = resample_carve(h, B, (int64_t)F * hop, rb, S_out, &sp, resample_emit_cap(rp, chunk, F, hop, so) + sL,
+                                    shaped ? &ssb : nullptr, sL, s_knots))
+            return rc;
     } else if (rs) {
         if (int rc = resample_carve(h, B, (int64_t)F * hop, rb, S_out)) return rc;
     } else if (enc) {
-        if (int rc = slab_carve(h, h->io, "staging", [&](Carver &cv) { sp = carve_stream_pack(cv, B, (int64_t)(chunk < F ? chunk : F) * hop); }))
+        const int64_t all = (int64_t)F * hop, most = (int64_t)(chunk < F ? chunk : F) * hop + sL;
+        if (int rc = slab_carve(h, h->io, "staging", [&](Carver &cv) {
+                sp = carve_stream_pack(cv, B, most < all ? most : all);
+                if (shaped) ssb = carve_stream_shape(cv, B, sL, s_knots);
+            }))
             return rc;
     }
     if (rs) {
@@ -1962,7 +2011,9 @@ int render_chunks(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int
         HIPCHECK(h, hipMemsetAsync(rb.carry[0], 0, (size_t)B * rp.K * sizeof(float), st));
         h->stats.total_launches++;
     }
-    const int64_t n_max = rs ? emit_cap : (int64_t)(chunk < F ? chunk : F) * hop;  // samples per row of the largest chunk
+    // samples per row of the largest chunk: what a piece renders, and the look-ahead the last one delivers on top - never
+    // more than the row
+    const int64_t n_max = std::min<int64_t>((rs ? emit_cap : (int64_t)(chunk < F ? chunk : F) * hop) + sL, rs ? (int64_t)S_out : (int64_t)F * hop);
     const size_t ring_bytes = enc ? (size_t)B * StreamPackBufs::pitch(enc_w, n_max) + StreamPackBufs::peak_floats(B) * sizeof(float)
                               : rs ? (size_t)B * emit_cap * sizeof(float) : (size_t)B * chunk * hop * sizeof(float);
     if (ring_bytes > h->ring_cap) {
@@ -1985,19 +2036,14 @@ int render_chunks(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int
     const int64_t total = rs ? (int64_t)S_out : (int64_t)F * hop;
     int64_t pend_first = 0, pend_n = 0;
     int pend = -1, k = 0, stop = 0;
-    // encoded form: the rows' valid samples (host: the callback's valid[]; device: the kernel's), the per-run upload
-    // [zeros of the running peaks | {ref_peak, volume} per row] in one copy, and the launch + copy of one chunk
-    std::vector<int64_t> row_n;
+    // encoded form: the per-run upload [zeros of the running peaks | {ref_peak, volume} per row] in one copy, and the launch +
+    // copy of one chunk
     std::vector<int32_t> valid;
+    StreamShapeRun srun;
     StreamPackRows sp_rows{nullptr, 1, 0};
     std::vector<float> up;  // (pageable source of an asynchronous copy: lives until the chunks behind it have been waited for)
     if (enc) {
-        row_n.resize((size_t)B);
         valid.resize((size_t)B);
-        for (int b = 0; b < B; b++) {
-            const int64_t nb = (int64_t)(ylen ? h->h_ylen[b] : F) * hop;
-            row_n[b] = rs ? rp.count(nb) : nb;
-        }
         sp_rows = rs ? StreamPackRows{rb.n_out, 1, S_out} : StreamPackRows{ylen, hop, F * hop};
         const size_t Bp = StreamPackBufs::peak_floats(B);
         up.assign(Bp + 2 * (size_t)B, 0.f);
@@ -2006,15 +2052,29 @@ int render_chunks(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int
             up[Bp + 2 * b + 1] = sink.fmt->volume ? sink.fmt->volume[b] : 1.0f;
         }
         HIPCHECK(h, hipMemcpyAsync(sp.peak_run, up.data(), up.size() * sizeof(float), hipMemcpyHostToDevice, st));
+        if (shaped) HIPCHECK(h, stream_shape_begin(srun, &shp, B, ssb, st));
     }
-    // x: the chunk's [B][n] at row pitch x_pitch, its first column sample `first` of the rows
-    auto pack_chunk = [&](const float *x, int64_t x_pitch, int64_t first, int64_t n, int slot) -> int {
-        const size_t pitch = StreamPackBufs::pitch(enc_w, n);
-        unsigned char *d = sp.at(B, pitch);
-        const hipError_t e = launch_stream_pack(sink.fmt->encoding, x, x_pitch, sp_rows, B, (int)first, (int)n, sp.fmt,
-                                                sink.fmt->ref_peak != nullptr, d, sp.peak_run, st);
-        if (e != hipSuccess) return fail(h, VITS_E_DEVICE, "stream pack launch failed: %s", hipGetErrorString(e));
-        h->stats.total_launches++;
+    // x: the chunk's [B][n] at row pitch x_pitch, its first column sample `first` of the rows.  [ef, ef + en): what it
+    // delivers - itself, or in a shaped stream with a look-ahead the range L samples behind it; en == 0: nothing, no copy
+    auto pack_chunk = [&](const float *x, int64_t x_pitch, int64_t first, int64_t n, int slot, int64_t &ef, int64_t &en) -> int {
+        unsigned char *d = nullptr;
+        if (shaped) {
+            int launches = 0;
+            const hipError_t e = stream_shape_chunk(srun, sink.fmt->encoding, enc_w, x, x_pitch, sp_rows, B, first, n, total, sp,
+                                                    sink.fmt->ref_peak != nullptr, st, ef, en, d, launches);
+            if (e != hipSuccess) return fail(h, VITS_E_DEVICE, "shaped stream pack launch failed: %s", hipGetErrorString(e));
+            h->stats.total_launches += launches;
+            if (en <= 0) return 0;
+        } else {
+            ef = first;
+            en = n;
+            d = sp.at(B, StreamPackBufs::pitch(enc_w, n));
+            const hipError_t e = launch_stream_pack(sink.fmt->encoding, x, x_pitch, sp_rows, B, (int)first, (int)n, sp.fmt,
+                                                    sink.fmt->ref_peak != nullptr, d, sp.peak_run, st);
+            if (e != hipSuccess) return fail(h, VITS_E_DEVICE, "stream pack launch failed: %s", hipGetErrorString(e));
+            h->stats.total_launches++;
+        }
+        const size_t pitch = StreamPackBufs::pitch(enc_w, en);
         HIPCHECK(h, hipMemcpyAsync(h->ring[slot], d, (size_t)B * pitch + (size_t)B * sizeof(float), hipMemcpyDeviceToHost, st));
         return 0;
     };
@@ -2081,29 +2141,39 @@ int render_chunks(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int
                 k ^= 1;
                 continue;
             }
+            int64_t ef = emitted, en = ne;
+            emitted = n_hi;
             if (enc) {
-                if (int rc = pack_chunk(rb.out, ne, emitted, ne, k)) return rc;
+                if (int rc = pack_chunk(rb.out, ne, ef, ne, k, ef, en)) return rc;
+                if (en <= 0) {  // (a shaped stream: the piece lies inside the look-ahead)
+                    k ^= 1;
+                    continue;
+                }
             } else
                 HIPCHECK(h, hipMemcpyAsync(h->ring[k], rb.out, (size_t)B * ne * 4, hipMemcpyDeviceToHost, st));
             HIPCHECK(h, hipEventRecord(h->ring_ev[k], st));
             if (int rc = deliver()) return rc;
             pend = k;
-            pend_first = emitted;
-            pend_n = ne;
-            emitted = n_hi;
+            pend_first = ef;
+            pend_n = en;
             continue;
         }
         // interior of this chunk: samples [(f0 - lo) * hop, (f1 - lo) * hop) of every row -> ring[k] as [B, ns]
+        int64_t ef = (int64_t)f0 * hop, en = ns;
         if (enc) {
-            if (int rc = pack_chunk(h->d_out + (int64_t)(f0 - lo) * hop, h->S, (int64_t)f0 * hop, ns, k)) return rc;
+            if (int rc = pack_chunk(h->d_out + (int64_t)(f0 - lo) * hop, h->S, (int64_t)f0 * hop, ns, k, ef, en)) return rc;
+            if (en <= 0) {  // (a shaped stream: the piece lies inside the look-ahead)
+                k ^= 1;
+                continue;
+            }
         } else
             HIPCHECK(h, hipMemcpy2DAsync(h->ring[k], (size_t)ns * 4, h->d_out + (int64_t)(f0 - lo) * hop, (size_t)h->S * 4,
                                          (size_t)ns * 4, B, hipMemcpyDeviceToHost, st));
         HIPCHECK(h, hipEventRecord(h->ring_ev[k], st));
         if (int rc = deliver()) return rc;  // (the previous chunk, while this one renders)
         pend = k;
-        pend_first = (int64_t)f0 * hop;
-        pend_n = ns;
+        pend_first = ef;
+        pend_n = en;
     }
     if (!stop)
         if (int rc = deliver()) return rc;
@@ -2618,7 +2688,12 @@ int vits_reserve(vits_handle *h, int B, int T, int F) {
         const DeliveryNeeds all{/*scan=*/true, /*levelled=*/true, /*shaped=*/true, shape_pts, /*limited=*/true};
         const size_t io_dlv = carved_bytes([&](Carver &cv) { carve_delivery_call(cv, B, F * m.hop, all); });
         // ... or an encoded stream's chunk buffer: every chunk_frames <= F, i.e. chunks of up to F * hop samples
-        const size_t io_sp = carved_bytes([&](Carver &cv) { carve_stream_pack(cv, B, (int64_t)F * m.hop); });
+        // (shaped: the rows' records and knots and the limiter's carries for the longest look-ahead behind it; a chunk never
+        // exceeds the row, so the L samples the last chunk delivers beyond what it renders are inside F * hop)
+        const size_t io_sp = carved_bytes([&](Carver &cv) {
+            carve_stream_pack(cv, B, (int64_t)F * m.hop);
+            carve_stream_shape(cv, B, VITS_LIMIT_MAX_LOOKAHEAD, shape_pts);
+        });
         size_t io = io_in > io_pcm ? io_in : io_pcm;
         io = io_dlv > io ? io_dlv : io;
         io = io_sp > io ? io_sp : io;
@@ -2629,6 +2704,7 @@ int vits_reserve(vits_handle *h, int B, int T, int F) {
             const size_t io_rs = carved_bytes([&](Carver &cv) {
                 carve_resample(cv, B, (int)so, (int)h->rs.plan.K);
                 carve_stream_pack(cv, B, so);
+                carve_stream_shape(cv, B, VITS_LIMIT_MAX_LOOKAHEAD, shape_pts);
             });
             io = io_rs > io ? io_rs : io;
             // (a trimmed delivery's slots and a levelled one's buffers lie behind the resampled result too: in the place of
@@ -2965,19 +3041,47 @@ static int host_stream_format(vits_handle *h, const vits_stream_format *fmt, int
     return VITS_OK;
 }
 
-int vits_run_chunked_enc(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
-                         const vits_noise *noise, const vits_controls *ctl, const vits_stream_format *fmt, int chunk_frames,
-                         vits_enc_chunk_fn fn, void *user) {
+// vits_stream_shaping, checked on the host behind the format (vitsmi.h, "shaped streaming")
+static int host_stream_shaping(vits_handle *h, const vits_stream_shaping *shaping, const vits_stream_format *fmt, int B) {
+    const std::string e = stream_shape_fault(shaping, fmt ? fmt->volume : nullptr, B);
+    if (!e.empty()) return fail(h, VITS_E_ARG, "%s", e.c_str());
+    return VITS_OK;
+}
+
+int vits_stream_shaping_check(const vits_stream_shaping *shaping, const vits_stream_format *fmt, int B) {
+    if (B < 0) return fail(nullptr, VITS_E_ARG, "B = %d is negative", B);
+    return host_stream_shaping(nullptr, shaping, fmt, B);
+}
+
+int vits_stream_emit_range(int64_t first, int64_t n, int is_last, int64_t total, int lookahead, int64_t *e_first, int64_t *e_n) {
+    if (!e_first || !e_n || first < 0 || n < 0 || total < 0 || first + n > total || lookahead < 0 || lookahead > VITS_LIMIT_MAX_LOOKAHEAD)
+        return fail(nullptr, VITS_E_ARG, "bad emit range arguments: piece [%lld, +%lld) of %lld, lookahead %d", (long long)first, (long long)n,
+                    (long long)total, lookahead);
+    stream_emit_range(first, n, is_last != 0, total, lookahead, *e_first, *e_n);
+    return VITS_OK;
+}
+
+int vits_run_chunked_enc_shaped(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
+                                const vits_noise *noise, const vits_controls *ctl, const vits_stream_format *fmt,
+                                const vits_stream_shaping *shaping, int chunk_frames, vits_enc_chunk_fn fn, void *user) {
     if (!h) return VITS_E_ARG;
     std::lock_guard<std::mutex> lk(h->mu);
     if (int rc = host_stream_format(h, fmt, B)) return rc;  // (pure host code: a host-only handle answers it too)
+    if (int rc = host_stream_shaping(h, shaping, fmt, B)) return rc;
     if (int rc = check_dev(h)) return rc;
     RunRows rr;
     if (int rc = host_controls(h, ctl, lens, B, T, rr)) return rc;
     ChunkSink sink{chunk_frames, nullptr, user};
     sink.fmt = fmt;
     sink.efn = fn;
+    sink.shaping = shaping;
     return run_chunked_sink(h, ids, lens, B, T, rr, sid, noise, sink);
+}
+
+int vits_run_chunked_enc(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
+                         const vits_noise *noise, const vits_controls *ctl, const vits_stream_format *fmt, int chunk_frames,
+                         vits_enc_chunk_fn fn, void *user) {
+    return vits_run_chunked_enc_shaped(h, ids, lens, B, T, sid, noise, ctl, fmt, nullptr, chunk_frames, fn, user);
 }
 
 int vits_run_chunked(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const float scales[3],
@@ -3370,17 +3474,24 @@ int vits_run_vocoder_chunked(vits_handle *h, const float *z, int B, int F, const
     return vocoder_common(h, z, B, F, sid, nullptr, &sink);
 }
 
-int vits_run_vocoder_chunked_enc(vits_handle *h, const float *z, int B, int F, const int64_t *sid, const vits_stream_format *fmt,
-                                 int chunk_frames, vits_enc_chunk_fn fn, void *user) {
+int vits_run_vocoder_chunked_enc_shaped(vits_handle *h, const float *z, int B, int F, const int64_t *sid, const vits_stream_format *fmt,
+                                        const vits_stream_shaping *shaping, int chunk_frames, vits_enc_chunk_fn fn, void *user) {
     if (!h) return VITS_E_ARG;
     std::lock_guard<std::mutex> lk(h->mu);
     if (int rc = host_stream_format(h, fmt, B)) return rc;
+    if (int rc = host_stream_shaping(h, shaping, fmt, B)) return rc;
     if (int rc = check_dev(h)) return rc;
     if (chunk_frames < 1) return fail(h, VITS_E_ARG, "bad vocoder arguments");
     ChunkSink sink{chunk_frames, nullptr, user};
     sink.fmt = fmt;
     sink.efn = fn;
+    sink.shaping = shaping;
     return vocoder_common(h, z, B, F, sid, nullptr, &sink);
+}
+
+int vits_run_vocoder_chunked_enc(vits_handle *h, const float *z, int B, int F, const int64_t *sid, const vits_stream_format *fmt,
+                                 int chunk_frames, vits_enc_chunk_fn fn, void *user) {
+    return vits_run_vocoder_chunked_enc_shaped(h, z, B, F, sid, fmt, nullptr, chunk_frames, fn, user);
 }
 
 int vits_tap(vits_handle *h, const char *name, float *buf, size_t buf_elems, int64_t dims[VITS_MAX_DIMS]) {
@@ -4311,6 +4422,93 @@ int vits_test_stream_pack(int device_id, const float *x, const int64_t *counts, 
         for (int b = 0; b < B; b++) {
             const int64_t v = counts[b] - f0;
             valid[(size_t)k * B + b] = (int32_t)(v < 0 ? 0 : (v > n ? n : v));
+        }
+    }
+    return k;
+}
+
+int vits_test_stream_pack_shaped(int device_id, const float *x, const int64_t *counts, int B, int S, int piece_samples,
+                                 const vits_stream_format *fmt, const vits_stream_shaping *shaping, void *bytes, size_t bytes_cap,
+                                 int64_t *pitches, int32_t *valid, float *peaks, int64_t *firsts, int64_t *ns, int max_pieces) {
+    if (!x || !counts || !bytes || !pitches || !valid || !peaks || !firsts || !ns || B <= 0 || B > 65535 || S <= 0 || piece_samples < 1 ||
+        (int64_t)B * S > (int64_t)1 << 40)
+        return fail(nullptr, VITS_E_ARG, "bad stream pack test arguments");
+    for (int b = 0; b < B; b++)
+        if (counts[b] < 0 || counts[b] > S) return fail(nullptr, VITS_E_ARG, "counts[%d] = %lld outside [0, %d]", b, (long long)counts[b], S);
+    if (int rc = host_stream_format(nullptr, fmt, B)) return rc;
+    if (int rc = host_stream_shaping(nullptr, shaping, fmt, B)) return rc;
+    const vits_stream_shaping none{};
+    const vits_stream_shaping &shp = shaping ? *shaping : none;  // (the hook always runs the shaped kernels: that is its subject)
+    const int L = shp.lookahead;
+    const int w = fmt->encoding == VITS_ENC_PCM16 ? 2 : (fmt->encoding == VITS_ENC_F32 ? 4 : 1);
+    const int64_t pieces = ((int64_t)S + piece_samples - 1) / piece_samples;
+    size_t need = 0;
+    int64_t n_max = 1;
+    for (int64_t f0 = 0; f0 < S; f0 += piece_samples) {
+        int64_t ef, en;
+        stream_emit_range(f0, S - f0 > piece_samples ? piece_samples : S - f0, f0 + piece_samples >= S, S, L, ef, en);
+        if (en > 0) need += (size_t)B * StreamPackBufs::pitch(w, en);
+        n_max = en > n_max ? en : n_max;
+    }
+    if (pieces > max_pieces || need > bytes_cap)
+        return fail(nullptr, VITS_E_ARG, "%lld pieces of %zu bytes: room for %d pieces and %zu bytes", (long long)pieces, need, max_pieces, bytes_cap);
+    if (int rc = test_dev(device_id)) return rc;
+    DevBufs D;
+    float *dx = D.up(x, (size_t)B * S);
+    std::vector<int> c32((size_t)B);
+    for (int b = 0; b < B; b++) c32[b] = (int)counts[b];
+    int *dcount = D.up(c32.data(), (size_t)B);
+    // the pipeline's buffers, by the pipeline's walk
+    const int64_t knots = stream_knot_count(&shp, B);
+    StreamPackBufs sp{};
+    StreamShapeBufs ssb{};
+    auto walk = [&](Carver &cv) {
+        sp = carve_stream_pack(cv, B, n_max);
+        ssb = carve_stream_shape(cv, B, L, knots);
+    };
+    const size_t total = carved_bytes(walk);
+    unsigned char *slab = D.alloc<unsigned char>(total);
+    TCHECK(D.err);
+    Carver cv(slab, total);
+    walk(cv);
+    if (!cv.fits()) return fail(nullptr, VITS_E_NOMEM, "stream shape walk carved %zu of %zu bytes", cv.used, cv.cap);
+    const size_t Bp = StreamPackBufs::peak_floats(B);
+    std::vector<float> up(Bp + 2 * (size_t)B, 0.f);
+    for (int b = 0; b < B; b++) {
+        up[Bp + 2 * b] = fmt->ref_peak ? fmt->ref_peak[b] : 1.0f;
+        up[Bp + 2 * b + 1] = fmt->volume ? fmt->volume[b] : 1.0f;
+    }
+    TCHECK(hipMemcpy(sp.peak_run, up.data(), up.size() * sizeof(float), hipMemcpyHostToDevice));
+    StreamShapeRun srun;
+    TCHECK(stream_shape_begin(srun, &shp, B, ssb, nullptr));
+    const StreamPackRows rows{dcount, 1, S};
+    unsigned char *dst = static_cast<unsigned char *>(bytes);
+    std::vector<unsigned char> landing;
+    int k = 0;
+    for (int64_t f0 = 0; f0 < S; f0 += piece_samples, k++) {
+        const int64_t n = S - f0 > piece_samples ? piece_samples : S - f0;
+        int64_t ef = 0, en = 0;
+        unsigned char *d = nullptr;
+        int launches = 0;
+        const hipError_t enq = stream_shape_chunk(srun, fmt->encoding, w, dx + f0, S, rows, B, f0, n, S, sp, fmt->ref_peak != nullptr, nullptr, ef,
+                                                  en, d, launches);
+        const hipError_t done = hipDeviceSynchronize();
+        TCHECK(enq);
+        TCHECK(done);
+        firsts[k] = ef;
+        ns[k] = en;
+        pitches[k] = 0;
+        if (en <= 0) continue;
+        const size_t pitch = StreamPackBufs::pitch(w, en);
+        landing.resize((size_t)B * pitch + (size_t)B * sizeof(float));
+        TCHECK(hipMemcpy(landing.data(), d, landing.size(), hipMemcpyDeviceToHost));  // bytes and peaks in one copy, as the pipeline
+        std::memcpy(dst, landing.data(), (size_t)B * pitch);
+        std::memcpy(peaks + (size_t)k * B, landing.data() + (size_t)B * pitch, (size_t)B * sizeof(float));
+        dst += (size_t)B * pitch;
+        pitches[k] = (int64_t)pitch;
+        for (int b = 0; b < B; b++) {
+            const int64_t v = counts[b] - ef;
+            valid[(size_t)k * B + b] = (int32_t)(v < 0 ? 0 : (v > en ? en : v));
         }
     }
     return k;

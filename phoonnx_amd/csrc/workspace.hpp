@@ -16,6 +16,7 @@
 #include "model.hpp"
 #include "shape.hpp"
 #include "slab.hpp"
+#include "stream_shape.hpp"
 
 namespace vitsmi {
 
@@ -408,6 +409,24 @@ inline StreamPackBufs carve_stream_pack(Carver &cv, int B, int64_t n_max) {
         s.peak_run = reinterpret_cast<unsigned *>(s.buf + s.cap);
         s.fmt = reinterpret_cast<float *>(s.peak_run) + StreamPackBufs::peak_floats(B);
     }
+    return s;
+}
+
+// A shaped, limited encoded stream (vits_run_chunked_enc_shaped) carves this behind carve_stream_pack in the same walk: the
+// rows' records and the knots of their envelopes, and the two generations of the limiter's carry - the last 2 L raw samples
+// of every row, one read while the other is written.  The chunk buffer's L extra samples per row - the last chunk delivers L
+// more than it renders - are carve_stream_pack's: the caller hands it n_max + L.
+struct StreamShapeBufs {
+    StreamShapeRow *rows;
+    ShapeKnot *knots;
+    float *carry[2];
+};
+
+inline StreamShapeBufs carve_stream_shape(Carver &cv, int B, int L, int64_t n_knots) {
+    StreamShapeBufs s{};
+    s.rows = cv.take<StreamShapeRow>(B);
+    s.knots = cv.take<ShapeKnot>((size_t)n_knots);
+    for (auto &c : s.carry) c = cv.take<float>((size_t)B * 2 * L);
     return s;
 }
 

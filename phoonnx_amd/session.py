@@ -667,6 +667,82 @@ def _stream_format(encoding, ref_peak, volume, B):
     return fmt, dtype
 
 
+def _stream_limit(limit, B):
+    """The limiter of a shaped stream: None, one Limit (every row) or one per row (None in the list: that row is not limited)
+    -> (lookahead, ceilings float32 [B] or None).  One look-ahead per call keeps a chunk rectangular: limits that differ in
+    it are refused."""
+    if limit is None:
+        return 0, None
+    rows = [limit] * B if isinstance(limit, Limit) else list(limit)
+    if len(rows) != B:
+        raise SessionError(f"limit must be one Limit or one per row ({B}), got {len(rows)}")
+    try:
+        ahead = sorted({int(l.lookahead) for l in rows if l is not None})
+        ceilings = np.array([0.0 if l is None else float(l.ceiling) for l in rows], np.float32)
+    except (AttributeError, TypeError, ValueError, OverflowError) as e:
+        raise SessionError(f"limit: {e}") from None
+    if len(ahead) > 1:
+        raise SessionError(f"limit: one lookahead per stream, got {ahead}")
+    if not ahead:
+        return 0, None
+    for b, l in enumerate(rows):
+        if l is not None and not ceilings[b] > 0:
+            raise SessionError(f"row {b}: limit ceiling {float(l.ceiling)} is not finite and within (0, 1]")
+    return ahead[0], ceilings
+
+
+def _stream_shaping(shapes, limit, B):
+    """The vits_stream_shaping struct of a shaped stream (vitsmi.h, "shaped streaming"), or None when neither is asked for:
+    shapes - None, one Shape or one per row (or RawShapes); limit - as _stream_limit.  Like _stream_format the struct holds
+    what it points into (`_keep`)."""
+    if shapes is None and limit is None:
+        return None
+    shp = _ffi.VitsStreamShaping()
+    keep = []
+    if shapes is not None:
+        arr, points, n_points = _shapes(shapes, B)
+        keep += [arr, points]
+        shp.shapes, shp.points, shp.n_points = C.addressof(arr), points, n_points
+    if isinstance(limit, RawStreamLimit):
+        ceilings = None if limit.ceiling is None else np.ascontiguousarray(limit.ceiling, np.float32)
+        shp.lookahead = int(limit.lookahead)
+    else:
+        shp.lookahead, ceilings = _stream_limit(limit, B)
+    if ceilings is not None:
+        keep.append(ceilings)
+        shp.ceiling = ceilings.ctypes.data
+    shp._keep = keep
+    return shp
+
+
+# a stream's limiter as the C struct holds it, for the tests of the validation: lookahead, and ceiling [B] or None
+RawStreamLimit = namedtuple("RawStreamLimit", "lookahead ceiling")
+
+
+def stream_shaping_check(shapes=None, limit=None, B=1, volume=None):
+    """The validation of a shaped stream's shaping (vits_stream_shaping_check: pure host code) over B rows of `volume` (None:
+    the volumes are not looked at); a refusal raises SessionError."""
+    shp = _stream_shaping(shapes, limit, B)
+    fmt = None
+    if volume is not None:
+        fmt = _ffi.VitsStreamFormat()
+        vol = np.ascontiguousarray(np.broadcast_to(np.asarray(volume, np.float32), (B,)), np.float32)
+        fmt.volume = vol.ctypes.data
+    rc = _ffi.load().vits_stream_shaping_check(None if shp is None else C.byref(shp), None if fmt is None else C.byref(fmt), int(B))
+    if rc != 0:
+        raise SessionError(f"vits_stream_shaping_check failed [{rc}]: {_ffi.last_error(None)}")
+
+
+def stream_emit_range(first, n, is_last, total, lookahead):
+    """What the rendered piece [first, first + n) of rows of `total` samples delivers under a look-ahead (vits_stream_emit_range:
+    pure host code) -> (first, n) of the delivered range; n == 0: the piece completes nothing."""
+    ef, en = C.c_int64(), C.c_int64()
+    rc = _ffi.load().vits_stream_emit_range(int(first), int(n), int(bool(is_last)), int(total), int(lookahead), C.byref(ef), C.byref(en))
+    if rc != 0:
+        raise SessionError(f"vits_stream_emit_range failed [{rc}]: {_ffi.last_error(None)}")
+    return ef.value, en.value
+
+
 def _rows(scales, B):
     """[3] -> [B, 3] (the row twins of the C ABI take one row per utterance)"""
     return np.ascontiguousarray(np.broadcast_to(scales, (B, 3)) if scales.ndim == 1 else scales, np.float32)
@@ -1124,17 +1200,27 @@ class MiSession:
         return _ffi.ENC_CHUNK_FN, item
 
     def synthesize_stream_encoded(self, ids, lens, scales, sid=None, chunk_frames: int = 64, encoding="pcm16", ref_peak=None,
-                                  volume=None, noise_dp=None, noise_z=None, seeds=None, durations=None, token_rate=None):
+                                  volume=None, noise_dp=None, noise_z=None, seeds=None, durations=None, token_rate=None,
+                                  shapes=None, token_gain_db=None, gain_ramp=0.01, limit=None):
         """synthesize_stream with every chunk post-processed, encoded and masked to each row's own length on the device
         (vitsmi.h, "encoded streaming"): yields EncodedChunk.  encoding "pcm16" / "ulaw" / "alaw" / "f32"; `volume` and
         `ref_peak` None, a scalar or [B]: row b is scaled by volume[b] and - with ref_peak - normalised by ref_peak[b] (a
         stream cannot know its own peak: feed back the final `peak` of an earlier stream with the same seeds, or a
         calibrated one).  The same chunk ranges as synthesize_stream, at the session's output rate; each row's valid
-        elements, joined, are what deliver() gives for that row (normalize 0, or 1 with ref_peak = its peak)."""
+        elements, joined, are what deliver() gives for that row (normalize 0, or 1 with ref_peak = its peak).
+        shapes (one Shape or one per row), token_gain_db ([B][T] dB, with gain_ramp seconds around every change) and limit
+        (one Limit, or one per row with None for a row that is not limited; one lookahead for all) are those of
+        synthesize_delivered(shapes=, token_gain_db=, gain_ramp=, limits=) for segments that keep their whole rows (vitsmi.h,
+        "shaped streaming"): each row's valid elements, joined, are what that delivery gives - a fade-out ends at the row's
+        own end, and with a look-ahead of L samples every chunk is delivered L samples late (the first chunk is L shorter,
+        the last L longer; EncodedChunk.peak then runs up to L samples ahead of the audio).  token_gain_db places its
+        breakpoints on the token boundaries of THIS run - free or forced durations - inside the engine's plan callback,
+        before the first chunk is rendered."""
         ids = np.ascontiguousarray(ids, np.int64)
         lens = np.ascontiguousarray(lens, np.int64)
         B, T = ids.shape
         fmt, dtype = _stream_format(encoding, ref_peak, volume, B)
+        shaping = self._stream_plan(shapes, token_gain_db, gain_ramp, limit, lens, B, T)
         scales, seeds = _settings(np.ascontiguousarray(scales, np.float32), B, seeds)
         durations, token_rate = _timing(durations, token_rate, lens, B, T)
         sid = None if sid is None else np.ascontiguousarray(sid, np.int64)
@@ -1150,21 +1236,81 @@ class MiSession:
             noise.noise_z = keep[-1].ctypes.data
             noise.noise_z_stride = keep[-1].shape[2]
         ctl = _controls(_rows(scales, B), seeds, durations, token_rate)
-        return self._stream(lambda cb: self._lib.vits_run_chunked_enc(
+        if shaping is None:  # (nothing asked for: the call made before there was any shaping)
+            return self._stream(lambda cb: self._lib.vits_run_chunked_enc(
+                self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(sid), C.byref(noise), C.byref(ctl), C.byref(fmt),
+                int(chunk_frames), cb, None), self._encoded_items(dtype))
+        self._shaping_check(shaping, fmt, B)
+        return self._stream(lambda cb: self._lib.vits_run_chunked_enc_shaped(
             self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(sid), C.byref(noise), C.byref(ctl), C.byref(fmt),
-            int(chunk_frames), cb, None), self._encoded_items(dtype))
+            C.byref(shaping), int(chunk_frames), cb, None), self._encoded_items(dtype))
 
-    def vocoder_stream_encoded(self, z, sid=None, chunk_frames: int = 64, encoding="pcm16", ref_peak=None, volume=None):
+    def _shaping_check(self, shaping, fmt, B):
+        """a shaping the engine would refuse up front raises here, by the call itself: nothing was started"""
+        if self._lib.vits_stream_shaping_check(C.byref(shaping), C.byref(fmt), B) != 0:
+            raise SessionError(f"shaped stream refused: {_ffi.last_error(None)}")
+
+    def _stream_plan(self, shapes, token_gain_db, gain_ramp, limit, lens, B, T):
+        """_stream_shaping with the plan callback of a per-token volume: the callback builds every row's envelope from the
+        run's own durations and sample counts (token_bounds / token_envelope: what synthesize_delivered(token_gain_db=)
+        computes between its run and its delivery) and hands the engine the shapes that carry them."""
+        if token_gain_db is None:
+            return _stream_shaping(shapes, limit, B)
+        tgains = token_gains(token_gain_db, B, T)
+        if not (np.isfinite(gain_ramp) and gain_ramp >= 0):
+            raise SessionError(f"gain_ramp must be >= 0 seconds (got {gain_ramp})")
+        base = [Shape()] * B if shapes is None else ([shapes] * B if isinstance(shapes, Shape) else list(shapes))
+        if len(base) != B:
+            raise SessionError(f"shapes must be one Shape or one per row ({B}), got {len(base)}")
+        for i, sh in enumerate(base):
+            if len(sh.points):
+                raise SessionError(f"row {i}: token_gain_db and explicit points on the same row")
+        shaping = _stream_shaping(base, limit, B)
+        hop = self.hparam("hop")
+        ratio = None
+        if self.resampling:
+            ratio = resample_plan(self.input_rate or int(self.meta("sample_rate") or 22050), self.output_rate)[:2]
+        ramp = int(self.delivered_rate * float(gain_ramp))
+        keep = shaping._keep
+
+        @_ffi.STREAM_PLAN_FN
+        def plan(user, Bc, Tc, dur, counts, inout):
+            try:
+                d = np.ctypeslib.as_array(dur, shape=(Bc * Tc,)).reshape(Bc, Tc)
+                n = np.ctypeslib.as_array(counts, shape=(Bc,))
+                bounds = [token_bounds(d[b], lens[b], hop, n[b], ratio) for b in range(Bc)]
+                used = token_gain_shapes([Segment(b) for b in range(Bc)], base, tgains, bounds, ramp)
+                arr, points, n_points = _shapes(used, Bc)
+                keep.extend([arr, points])
+                shaping.used_shapes = used
+                inout.contents.shapes, inout.contents.points, inout.contents.n_points = C.addressof(arr), points.value, n_points
+                return 0
+            except Exception as e:  # noqa: BLE001 - a Python error must not cross the C frames: the run is refused instead
+                shaping.plan_error = e
+                return 1
+
+        shaping.plan = plan
+        keep.append(plan)
+        return shaping
+
+    def vocoder_stream_encoded(self, z, sid=None, chunk_frames: int = 64, encoding="pcm16", ref_peak=None, volume=None, shapes=None,
+                               limit=None):
         """Vocoder only, chunked and encoded: yields EncodedChunk (every row has F * hop samples, or their count at the
-        output rate)."""
+        output rate).  shapes / limit as synthesize_stream_encoded."""
         z = np.ascontiguousarray(z, np.float32)
         B, Cc, F = z.shape
         fmt, dtype = _stream_format(encoding, ref_peak, volume, B)
+        shaping = _stream_shaping(shapes, limit, B)
         if Cc != self.hparam("inter"):
             raise SessionError(f"z must have {self.hparam('inter')} channels")
         sid = None if sid is None else np.ascontiguousarray(sid, np.int64)
-        return self._stream(lambda cb: self._lib.vits_run_vocoder_chunked_enc(
-            self._h, _ffi.ptr(z), B, F, _ffi.ptr(sid), C.byref(fmt), int(chunk_frames), cb, None), self._encoded_items(dtype))
+        if shaping is None:
+            return self._stream(lambda cb: self._lib.vits_run_vocoder_chunked_enc(
+                self._h, _ffi.ptr(z), B, F, _ffi.ptr(sid), C.byref(fmt), int(chunk_frames), cb, None), self._encoded_items(dtype))
+        self._shaping_check(shaping, fmt, B)
+        return self._stream(lambda cb: self._lib.vits_run_vocoder_chunked_enc_shaped(
+            self._h, _ffi.ptr(z), B, F, _ffi.ptr(sid), C.byref(fmt), C.byref(shaping), int(chunk_frames), cb, None),
+            self._encoded_items(dtype))
 
     def vocoder_stream(self, z, sid=None, chunk_frames: int = 64):
         """Vocoder only, chunked: yields (first_sample, float32 [B, n], total_samples)."""
@@ -2125,6 +2271,40 @@ def test_stream_pack(x, counts, piece_samples, encoding="pcm16", ref_peak=None, 
         chunks.append(EncodedChunk(k * piece, out[off:off + B * p].reshape(B, p), valid[k], peaks[k], S))
         off += B * p
     return chunks
+
+
+def test_stream_pack_shaped(x, counts, piece_samples, encoding="pcm16", ref_peak=None, volume=None, shapes=None, limit=None,
+                            device_id=0):
+    """vits_test_stream_pack_shaped: test_stream_pack through the shaped stream's kernels (shapes / limit as
+    MiSession.synthesize_stream_encoded, or RawShapes / RawStreamLimit) -> (one EncodedChunk per piece that delivered
+    something - first_sample and `data` [B, pitch] of the DELIVERED range -, [(first, n) delivered by every piece])."""
+    x = np.ascontiguousarray(x, np.float32)
+    counts = np.ascontiguousarray(counts, np.int64)
+    B, S = x.shape
+    fmt, dtype = _stream_format(encoding, ref_peak, volume, B)
+    shaping = _stream_shaping(shapes, limit, B)
+    w, piece = np.dtype(dtype).itemsize, int(piece_samples)
+    if piece < 1:
+        raise SessionError(f"piece_samples = {piece} is not positive")
+    n_pieces = -(-S // piece)
+    out = np.full(B * (-(-w * S // 16) * 16 + 16 * n_pieces), 0xA5, np.uint8)
+    pitches = np.zeros(n_pieces, np.int64)
+    firsts, ns = np.full(n_pieces, -1, np.int64), np.full(n_pieces, -1, np.int64)
+    valid = np.full((n_pieces, B), -1, np.int32)
+    peaks = np.full((n_pieces, B), np.nan, np.float32)
+    n = _ffi.load().vits_test_stream_pack_shaped(device_id, _ffi.ptr(x), _ffi.ptr(counts), B, S, piece, C.byref(fmt),
+                                                 None if shaping is None else C.byref(shaping), _ffi.ptr(out), out.nbytes,
+                                                 _ffi.ptr(pitches), _ffi.ptr(valid), _ffi.ptr(peaks), _ffi.ptr(firsts), _ffi.ptr(ns),
+                                                 n_pieces)
+    if n < 0:
+        raise SessionError(f"vits_test_stream_pack_shaped failed [{n}]: {_ffi.last_error(None)}")
+    chunks, off = [], 0
+    for k in range(n):
+        p = int(pitches[k])
+        if ns[k] > 0:
+            chunks.append(EncodedChunk(int(firsts[k]), out[off:off + B * p].reshape(B, p), valid[k], peaks[k], S))
+        off += B * p
+    return chunks, [(int(f), int(c)) for f, c in zip(firsts[:n], ns[:n])]
 
 
 # ---- the token-to-frame and frame-to-sample kernels by value (include/vitsmi.h: vits_test_durations ...) ----------------

@@ -709,7 +709,9 @@ class TTSVoice:
         return ae.EncodedAudio(data, encoding, self.sample_rate, starts, counts, aligned, loud, gains)
 
     def stream_encoded(self, text: str, syn_config: Optional[SynthesisConfig] = None, encoding: str = "pcm16",
-                       chunk_frames: int = 64, sentence_silence: float = 0.0, ref_peak=None):
+                       chunk_frames: int = 64, sentence_silence: float = 0.0, ref_peak=None, fade_in: float = 0.0,
+                       fade_out: float = 0.0, fade_curve: str = "linear", phoneme_gain_db=None, limit_ceiling: float = 0.0,
+                       limit_lookahead: float = 0.005):
         """Extension: synthesize_encoded's ONE stream as a generator of `bytes`, handed out while the audio still renders.
         All sentences render as one chunked batch (MiSession.synthesize_stream_encoded: post-processing, encoding and the
         masking to each sentence's own length happen on the device, per chunk).  Sentence 0's chunks are yielded as they
@@ -719,25 +721,41 @@ class TTSVoice:
         peak each sentence is normalised by, e.g. the final EncodedChunk.peak of an earlier stream with the same seeds) and
         raises ValueError without one; with normalize_audio off, ref_peak is not used.  volume is the config's.  A session
         without synthesize_stream_encoded gets the same bytes from the host encoder: over synthesize_stream's chunks where
-        that exists, else over the whole rendering."""
+        that exists, else over the whole rendering.
+        fade_in / fade_out / fade_curve, phoneme_gain_db and limit_ceiling / limit_lookahead have the meanings and refusals of
+        synthesize_encoded, for every sentence (vitsmi.h, "shaped streaming"): a streamed sentence meets the silence of its
+        pause at exactly 0, takes a volume per phoneme and ducks under its peaks instead of clipping - joined, still
+        synthesize_encoded's bytes.  With a limiter every chunk arrives limit_lookahead of audio later.  They are passed
+        down only when asked for; a session that streams fp32 only takes audio_encoding.stream_shaped."""
         from . import audio_encoding as ae
         cfg = syn_config if syn_config is not None else SynthesisConfig()
         ae._check(encoding)
         lead = self._lead_samples(sentence_silence)
+        shape = self._shape(fade_in, fade_out, fade_curve)
+        limit = self._limit(limit_ceiling, limit_lookahead)
+        if phoneme_gain_db is not None and not hasattr(self.session, "synthesize_batch"):
+            raise ValueError("phoneme_gain_db needs a session that reports durations (synthesize_batch)")
         if cfg.normalize_audio and ref_peak is None:
             raise ValueError("a stream cannot know its own peak: pass ref_peak (the peak to normalise by), or switch "
                              "normalize_audio off")
         if int(chunk_frames) < 1:
             raise ValueError(f"chunk_frames must be >= 1 (got {chunk_frames})")
-        return self._stream_encoded(text, cfg, encoding, int(chunk_frames), lead, ref_peak)
+        return self._stream_encoded(text, cfg, encoding, int(chunk_frames), lead, ref_peak, shape, phoneme_gain_db, limit)
 
-    def _stream_encoded(self, text, cfg, encoding, chunk_frames, lead, ref_peak):
+    def _stream_encoded(self, text, cfg, encoding, chunk_frames, lead, ref_peak, shape=None, phoneme_gain_db=None, limit=None):
         from . import audio_encoding as ae
         from .sharding import pad_batch
-        all_ids = self._sentence_ids(text, cfg)
+        token_db = None
+        if phoneme_gain_db is not None:
+            groups = self._sentence_groups(text, cfg)
+            all_ids = [[i for _, ids in g for i in ids] for g in groups]
+            token_db = [self._group_db(phoneme_gain_db, k, g) for k, g in enumerate(groups)]
+        else:
+            all_ids = self._sentence_ids(text, cfg)
         B = len(all_ids)
         if not B:
             return
+        shaped = shape is not None or token_db is not None or limit is not None
         peaks = None
         if cfg.normalize_audio:
             peaks = np.asarray(ref_peak, np.float32)
@@ -753,12 +771,21 @@ class TTSVoice:
 
         streams = hasattr(session, "synthesize_stream_encoded") or hasattr(session, "synthesize_stream")
         if not streams:  # the whole rendering, sentence by sentence through the host encoder
+            durs = None
             if hasattr(session, "synthesize_batch"):
-                audios = self.phoneme_ids_batch_to_audio(all_ids, cfg)
+                res = self.phoneme_ids_batch_to_audio(all_ids, cfg, return_durations=token_db is not None)
+                audios, durs = res if token_db is not None else (res, None)
             else:
                 audios = (self.phoneme_ids_to_audio(ids, cfg) for ids in all_ids)
+            if not shaped:
+                for b, a in enumerate(audios):
+                    yield pause + host_bytes(b, np.atleast_1d(a))
+                return
+            audios = [np.atleast_1d(a) for a in audios]
+            shapes = self._row_shapes(shape, token_db, durs, [len(a) for a in audios])
             for b, a in enumerate(audios):
-                yield pause + host_bytes(b, np.atleast_1d(a))
+                mul = ae.shape_multiplier(0, len(a), shapes[b])
+                yield pause + ae.encode(ae.scaled(a, None if peaks is None else peaks[b], volume, mul, limit), encoding).tobytes()
             return
         ids, lens = pad_batch(all_ids)
         expected = [i.name for i in session.get_inputs()]
@@ -768,9 +795,33 @@ class TTSVoice:
                 raise ValueError(f"speaker_id {cfg.speaker_id or 0} is out of range [0, {max(n_spk, 1)})")
         sid = np.full((B,), cfg.speaker_id or 0, np.int64) if "sid" in expected else None
         if hasattr(session, "synthesize_stream_encoded"):
+            more = {}   # (passed down only when asked for: sessions from before the shaped stream do not know the keywords)
+            if shape is not None:
+                more["shapes"] = shape
+            if token_db is not None:
+                more["token_gain_db"], more["gain_ramp"] = self._padded_db(token_db), _GAIN_RAMP
+            if limit is not None:
+                more["limit"] = limit
             chunks = ((c.first_sample, c.data.shape[1], c.total_samples, c.valid, [c.data[b, :int(c.valid[b])].tobytes() for b in range(B)])
                       for c in session.synthesize_stream_encoded(ids, lens, self._scales(cfg), sid, chunk_frames=chunk_frames,
-                                                                 encoding=encoding, ref_peak=peaks, volume=volume))
+                                                                 encoding=encoding, ref_peak=peaks, volume=volume, **more))
+        elif shaped:
+            if token_db is not None and not hasattr(session, "last_durations"):
+                raise ValueError("phoneme_gain_db needs a session that reports durations (last_durations)")
+
+            def sample_counts():
+                return (np.asarray(session.last_sample_counts(), np.int64) if hasattr(session, "last_sample_counts")
+                        else np.asarray(session.last_y_lengths(), np.int64) * session.hparam("hop"))
+
+            def row_shapes(counts):  # (counts and durations are known from the first chunk on: stream_shaped asks there)
+                durs = None if token_db is None else np.asarray(session.last_durations())
+                return self._row_shapes(shape, token_db, durs, [int(c) for c in counts])
+
+            def shaped_chunks():
+                fp32 = session.synthesize_stream(ids, lens, self._scales(cfg), sid, chunk_frames=chunk_frames)
+                for first, data, valid, _, total in ae.stream_shaped(fp32, sample_counts, encoding, peaks, volume, row_shapes, limit):
+                    yield first, data.shape[1], total, valid, [data[b, :int(valid[b])].tobytes() for b in range(B)]
+            chunks = shaped_chunks()
         else:
             def host_chunks():
                 counts = None
