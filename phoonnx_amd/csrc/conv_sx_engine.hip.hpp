@@ -95,7 +95,7 @@ enum : int { SX_NO_RAW_STORE = 256 };  // out_raw is only the EPI_ACC operand, n
 // batch to the longest one's length).  Utterance b's tensors END at min(T, (len[b] + add) * mul) columns: a workgroup whose
 // tile starts behind that end exits at once, columns behind it are zero padding for the loads and are not stored.  `add` is
 // the generator's receptive field in frames (Model::gen_rf_frames), so every VALID sample (frame < len[b]) still sees exactly
-// the values the padded rendering computes - the chunked renderer (vitsmi.hip render_chunks) relies on the same argument.
+// the values the padded rendering computes - the chunked renderer (vitsmi.hip, the render step of render_chunks) relies on the same argument.
 // len == nullptr: every utterance spans T (the padded rendering).
 struct SxRagged {
     const int *len;       // valid frames per utterance (device), or nullptr

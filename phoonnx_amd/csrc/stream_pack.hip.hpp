@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "delivery.hip.hpp"
 
@@ -69,20 +70,28 @@ __global__ __launch_bounds__(kDeliveryThreads) void stream_pack_kernel(const flo
 // row pitch of a chunk of n samples at w bytes per element
 inline int64_t stream_pack_pitch(int width, int64_t n) { return (width * n + 15) & ~(int64_t)15; }
 
+// f(std::integral_constant<int, ENC>) for a (validated) encoding: the kernels' template argument
+template <class F>
+inline void stream_for_encoding(int encoding, F &&f) {
+    switch (encoding) {
+        case VITS_ENC_PCM16: return f(std::integral_constant<int, VITS_ENC_PCM16>{});
+        case VITS_ENC_ULAW: return f(std::integral_constant<int, VITS_ENC_ULAW>{});
+        case VITS_ENC_ALAW: return f(std::integral_constant<int, VITS_ENC_ALAW>{});
+        default: return f(std::integral_constant<int, VITS_ENC_F32>{});
+    }
+}
+
 // one chunk on `st`: bytes [B][pitch] (16-byte aligned), pitch = stream_pack_pitch(width of encoding, n); n >= 1
 inline hipError_t launch_stream_pack(int encoding, const float *x, int64_t x_pitch, const StreamPackRows &rows, int B, int first, int n,
                                      const float *fmt, bool norm, void *bytes, unsigned *peak_run, hipStream_t st) {
-    const int width = encoding == VITS_ENC_PCM16 ? 2 : (encoding == VITS_ENC_F32 ? 4 : 1);
+    const int width = delivery_width(encoding);
     const int cells = (int)(stream_pack_pitch(width, n) / 16);
     const dim3 grid((unsigned)((cells + kDeliveryThreads - 1) / kDeliveryThreads), (unsigned)B);
     uint4 *out = static_cast<uint4 *>(bytes);
     const int nm = norm ? 1 : 0;
-    switch (encoding) {
-        case VITS_ENC_PCM16: stream_pack_kernel<VITS_ENC_PCM16><<<grid, kDeliveryThreads, 0, st>>>(x, x_pitch, rows, first, n, fmt, nm, out, cells, peak_run); break;
-        case VITS_ENC_ULAW: stream_pack_kernel<VITS_ENC_ULAW><<<grid, kDeliveryThreads, 0, st>>>(x, x_pitch, rows, first, n, fmt, nm, out, cells, peak_run); break;
-        case VITS_ENC_ALAW: stream_pack_kernel<VITS_ENC_ALAW><<<grid, kDeliveryThreads, 0, st>>>(x, x_pitch, rows, first, n, fmt, nm, out, cells, peak_run); break;
-        default: stream_pack_kernel<VITS_ENC_F32><<<grid, kDeliveryThreads, 0, st>>>(x, x_pitch, rows, first, n, fmt, nm, out, cells, peak_run); break;
-    }
+    stream_for_encoding(encoding, [&](auto enc) {
+        stream_pack_kernel<decltype(enc)::value><<<grid, kDeliveryThreads, 0, st>>>(x, x_pitch, rows, first, n, fmt, nm, out, cells, peak_run);
+    });
     return hipGetLastError();
 }
 

@@ -1,0 +1,120 @@
+// stream_run.hip.hpp — the stages a piece of a chunked run goes through behind the generator: the resampler's piece entry with its
+// carry (include/vitsmi.h, "Output rate") and the encoded sink's pack, plain ("encoded streaming") or shaped and limited ("shaped
+// streaming", stream_shape.hip.hpp).  The pipeline (vitsmi.hip, render_chunks) and the hooks vits_test_resample_pieces /
+// vits_test_stream_pack / _shaped run THESE functions.  Nothing here knows a handle.  The buffers are carve_stream's (workspace.hpp);
+// errors come back as hipError_t, launch counts by reference.  All is enqueued on the caller's stream; the caller copies out and waits.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <vector>
+
+#include "resample.hip.hpp"
+#include "stream_shape.hip.hpp"
+#include "workspace.hpp"
+
+namespace vitsmi {
+
+// ---- resampled pieces: the batch path's [B][S_out], bit for bit, whatever the pieces
+struct ResampleRun {
+    ResamplePlan plan;
+    ResampleArgs a{};  // what every piece shares: the table, the rows' counts, the output buffer
+    float *carry[2] = {nullptr, nullptr};
+    int S_out = 0;
+    int gen = 0;      // the carry generation in front of the next piece
+    int emitted = 0;  // output samples delivered so far
+};
+
+// the rows' counts (ylen[b] * hop, without frame counts n_all; at most n_all) and a zero carry in front of the first piece
+inline hipError_t resample_run_begin(ResampleRun &r, const ResampleDev &dev, const ResampleBufs &rb, const int *ylen, int hop, int n_all,
+                                     int S_out, int B, hipStream_t st) {
+    r = ResampleRun{dev.plan, resample_args(dev), {rb.carry[0], rb.carry[1]}, S_out};
+    r.a.n_in = rb.n_in;
+    r.a.n_out = rb.n_out;
+    r.a.y = rb.out;
+    resample_counts_kernel<<<(B + 63) / 64, 64, 0, st>>>(ylen, hop, n_all, dev.plan.L, dev.plan.M, rb.n_in, rb.n_out, B);
+    return hipMemsetAsync(rb.carry[0], 0, (size_t)B * dev.plan.K * sizeof(float), st);
+}
+
+// The piece x [B][n], input samples [first, first + n) of every row: "carry | piece" in, the output samples whose K inputs now all
+// exist - the last piece: the rest - out to rb.out as [B][e_n], they are [e_first, e_first + e_n); behind every piece but the last the
+// carry's other generation.  e_n == 0: it completes nothing.  (launches: two per piece, as a run's statistics have always counted.)
+inline hipError_t resample_run_piece(ResampleRun &r, const float *x, int64_t x_pitch, int64_t first, int64_t n, bool is_last, int B,
+                                     hipStream_t st, int64_t &e_first, int64_t &e_n, int &launches) {
+    const int n_hi = (int)resample_emit_end(r.plan, first + n, is_last, r.S_out), ne = n_hi - r.emitted;
+    ResampleArgs a = r.a;
+    a.x = x;
+    a.x_pitch = x_pitch;
+    a.x_first = (int)first;
+    a.x_n = (int)n;
+    a.carry = r.carry[r.gen];
+    a.y_pitch = ne;  // (the previous piece's copy-out precedes this one on the stream)
+    a.y_first = r.emitted;
+    a.n_lo = r.emitted;
+    a.n_hi = n_hi;
+    hipError_t e = launch_resample(a, B, /*piece=*/true, st);
+    if (e == hipSuccess && !is_last) {
+        resample_carry_kernel<<<dim3((unsigned)((a.K + 255) / 256), B), 256, 0, st>>>(a.carry, x, x_pitch, a.x_n, a.K, r.carry[r.gen ^ 1]);
+        e = hipGetLastError();
+        r.gen ^= 1;
+    }
+    launches = 2;
+    e_first = r.emitted;
+    e_n = ne > 0 ? ne : 0;
+    if (ne > 0) r.emitted = n_hi;
+    return e;
+}
+
+// ---- packed pieces: the encoded sink.  A piece reaches sp's chunk buffer as [B][pitch] bytes that end at the running peaks.
+struct StreamPackRun {
+    int encoding = 0, width = 0;
+    bool norm = false, shaped = false;
+    StreamPackBufs sp{};
+    StreamPackRows rows{nullptr, 1, 0};
+    int64_t total = 0;
+    StreamShapeRun shape;
+    std::vector<float> up;  // (pageable source of an asynchronous copy: lives until the pieces behind it have been waited for)
+};
+
+// The per-run upload [zeros of the running peaks | {ref_peak, volume} per row] in one copy and, with a `shaping` (nullptr: the
+// plain kernel), its records and knots.  fmt and shaping are validated; rows / total: the rows' valid samples and their length.
+inline hipError_t stream_pack_begin(StreamPackRun &r, const vits_stream_format *fmt, const vits_stream_shaping *shaping, int B,
+                                    const StreamPackBufs &sp, const StreamShapeBufs &ss, const StreamPackRows &rows, int64_t total,
+                                    hipStream_t st) {
+    r.encoding = fmt->encoding;
+    r.width = delivery_width(fmt->encoding);
+    r.norm = fmt->ref_peak != nullptr;
+    r.shaped = shaping != nullptr;
+    r.sp = sp;
+    r.rows = rows;
+    r.total = total;
+    const size_t Bp = StreamPackBufs::peak_floats(B);
+    r.up.assign(Bp + 2 * (size_t)B, 0.f);
+    for (int b = 0; b < B; b++) {
+        r.up[Bp + 2 * b] = fmt->ref_peak ? fmt->ref_peak[b] : 1.0f;
+        r.up[Bp + 2 * b + 1] = fmt->volume ? fmt->volume[b] : 1.0f;
+    }
+    hipError_t e = hipMemcpyAsync(sp.peak_run, r.up.data(), r.up.size() * sizeof(float), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && r.shaped) e = stream_shape_begin(r.shape, shaping, B, ss, st);
+    return e;
+}
+
+// The piece x [B][n] at `first`: what it delivers - itself or, shaped with a look-ahead, the range that far behind it - as [B][pitch]
+// bytes at d with the running peaks behind, for one copy.  e_n == 0: it lies inside the look-ahead, nothing was delivered, d is not set.
+inline hipError_t stream_pack_piece(StreamPackRun &r, const float *x, int64_t x_pitch, int64_t first, int64_t n, int B, hipStream_t st,
+                                    unsigned char *&d, int64_t &e_first, int64_t &e_n, size_t &pitch, int &launches) {
+    pitch = StreamPackBufs::pitch(r.width, n);
+    if (r.shaped) {
+        const hipError_t e = stream_shape_chunk(r.shape, r.encoding, r.width, x, x_pitch, r.rows, B, first, n, r.total, r.sp, r.norm, st, e_first,
+                                                e_n, d, launches);
+        pitch = StreamPackBufs::pitch(r.width, e_n);
+        return e;
+    }
+    e_first = first;
+    e_n = n;
+    d = r.sp.at(B, pitch);
+    launches = 1;
+    return launch_stream_pack(r.encoding, x, x_pitch, r.rows, B, (int)first, (int)n, r.sp.fmt, r.norm, d, r.sp.peak_run, st);
+}
+
+}  // namespace vitsmi

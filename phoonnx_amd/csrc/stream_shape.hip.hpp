@@ -196,20 +196,15 @@ __global__ void stream_carry_kernel(const float *old, const float *x, int64_t x_
 inline hipError_t launch_stream_pack_shaped(int encoding, const float *x, int64_t x_pitch, const StreamPackRows &rows, int B, int first, int n,
                                             const float *fmt, bool norm, void *bytes, unsigned *peak_run, const StreamShapeRow *srows,
                                             const ShapeKnot *knots, hipStream_t st) {
-    const int width = encoding == VITS_ENC_PCM16 ? 2 : (encoding == VITS_ENC_F32 ? 4 : 1);
+    const int width = delivery_width(encoding);
     const int cells = (int)(stream_pack_pitch(width, n) / 16);
     const dim3 grid((unsigned)((cells + kDeliveryThreads - 1) / kDeliveryThreads), (unsigned)B);
     uint4 *out = static_cast<uint4 *>(bytes);
     const int nm = norm ? 1 : 0;
-#define VITSMI_STREAM_SHAPED(ENC) \
-    stream_pack_shaped_kernel<ENC><<<grid, kDeliveryThreads, 0, st>>>(x, x_pitch, rows, first, n, fmt, nm, out, cells, peak_run, srows, knots)
-    switch (encoding) {
-        case VITS_ENC_PCM16: VITSMI_STREAM_SHAPED(VITS_ENC_PCM16); break;
-        case VITS_ENC_ULAW: VITSMI_STREAM_SHAPED(VITS_ENC_ULAW); break;
-        case VITS_ENC_ALAW: VITSMI_STREAM_SHAPED(VITS_ENC_ALAW); break;
-        default: VITSMI_STREAM_SHAPED(VITS_ENC_F32); break;
-    }
-#undef VITSMI_STREAM_SHAPED
+    stream_for_encoding(encoding, [&](auto enc) {
+        stream_pack_shaped_kernel<decltype(enc)::value><<<grid, kDeliveryThreads, 0, st>>>(x, x_pitch, rows, first, n, fmt, nm, out, cells, peak_run,
+                                                                                           srows, knots);
+    });
     return hipGetLastError();
 }
 
@@ -217,20 +212,14 @@ inline hipError_t launch_stream_pack_shaped(int encoding, const float *x, int64_
 inline hipError_t launch_stream_pack_limited(int encoding, const StreamLimitArgs &a, const StreamPackRows &rows, int B, const float *fmt, bool norm,
                                              void *bytes, unsigned *peak_run, const StreamShapeRow *srows, const ShapeKnot *knots,
                                              hipStream_t st) {
-    const int width = encoding == VITS_ENC_PCM16 ? 2 : (encoding == VITS_ENC_F32 ? 4 : 1);
+    const int width = delivery_width(encoding);
     const int cells = (int)(stream_pack_pitch(width, a.en) / 16);
     const dim3 grid((unsigned)((a.en + kStreamTile - 1) / kStreamTile), (unsigned)B);
     uint4 *out = static_cast<uint4 *>(bytes);
     const int nm = norm ? 1 : 0;
-#define VITSMI_STREAM_LIMITED(ENC) \
-    stream_pack_limited_kernel<ENC><<<grid, kDeliveryThreads, 0, st>>>(a, rows, fmt, nm, out, cells, peak_run, srows, knots)
-    switch (encoding) {
-        case VITS_ENC_PCM16: VITSMI_STREAM_LIMITED(VITS_ENC_PCM16); break;
-        case VITS_ENC_ULAW: VITSMI_STREAM_LIMITED(VITS_ENC_ULAW); break;
-        case VITS_ENC_ALAW: VITSMI_STREAM_LIMITED(VITS_ENC_ALAW); break;
-        default: VITSMI_STREAM_LIMITED(VITS_ENC_F32); break;
-    }
-#undef VITSMI_STREAM_LIMITED
+    stream_for_encoding(encoding, [&](auto enc) {
+        stream_pack_limited_kernel<decltype(enc)::value><<<grid, kDeliveryThreads, 0, st>>>(a, rows, fmt, nm, out, cells, peak_run, srows, knots);
+    });
     return hipGetLastError();
 }
 
@@ -240,7 +229,8 @@ inline hipError_t launch_stream_carry(const float *old, const float *x, int64_t 
     return hipGetLastError();
 }
 
-// ---- a shaped stream from its first chunk to its last: what the pipeline (vitsmi.hip, render_chunks) and the test hook share
+// ---- a shaped stream from its first chunk to its last: the shaped form of the pack stage (stream_run.hip.hpp,
+// stream_pack_begin / stream_pack_piece), which the pipeline and the test hooks run
 
 // the state of one run.  The vectors are the pageable sources of copies: they outlive the run's waits.
 struct StreamShapeRun {

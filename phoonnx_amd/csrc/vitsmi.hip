@@ -32,6 +32,7 @@
 #include "model.hpp"
 #include "resample.hip.hpp"
 #include "stream_pack.hip.hpp"
+#include "stream_run.hip.hpp"
 #include "stream_shape.hip.hpp"
 #include "test_dev.hip.hpp"
 #include "workspace.hpp"
@@ -1869,32 +1870,21 @@ __global__ void chunk_len_kernel(const int *ylen, int *out, int B, int lo, int n
 
 // ---- output rate (vits_set_output_rate): the rendered waveform resampled on the device (resample.hip.hpp)
 
-// The staging slab carved for the resampled result of B rows of S_in input samples.  The run's inputs lived there: every
-// kernel that read them precedes the resampler on the stream (and a growing slab waits for the stream first).
-// (sp: an encoded stream's buffers behind them in the same walk, for chunks of at most min(sp_n_max, S_out) samples)
-// (ss: a shaped stream's buffers behind those, for a look-ahead of ss_L and ss_knots knots; sp_n_max then counts the L samples the
-// last chunk delivers beyond what it renders)
-int resample_carve(vits_handle *h, int B, int64_t S_in, ResampleBufs &rb, int &S_out, StreamPackBufs *sp = nullptr, int64_t sp_n_max = 0,
-                   StreamShapeBufs *ss = nullptr, int ss_L = 0, int64_t ss_knots = 0) {
+// the output samples of a row of S_in input samples, refused where a row does not admit them
+int resample_count(vits_handle *h, int64_t S_in, int &S_out) {
     const ResamplePlan &p = h->rs.plan;
     const int64_t so = p.count(S_in);
-    if (so > INT_MAX)
-        return fail(h, VITS_E_ARG, "%lld samples at %d Hz are %lld samples at %d Hz: more than a row admits (%d)", (long long)S_in,
-                    p.fi, (long long)so, p.fo, INT_MAX);
     S_out = (int)so;
-    if (sp)
-        return slab_carve(h, h->io, "staging", [&](Carver &cv) {
-            rb = carve_resample(cv, B, S_out, (int)p.K);
-            *sp = carve_stream_pack(cv, B, sp_n_max < so ? sp_n_max : so);
-            if (ss) *ss = carve_stream_shape(cv, B, ss_L, ss_knots);
-        });
-    return slab_carve(h, h->io, "staging", [&](Carver &cv) { rb = carve_resample(cv, B, S_out, (int)p.K); });
+    if (so <= INT_MAX) return 0;
+    return fail(h, VITS_E_ARG, "%lld samples at %d Hz are %lld samples at %d Hz: more than a row admits (%d)", (long long)S_in, p.fi,
+                (long long)so, p.fo, INT_MAX);
 }
 
-// output samples one chunk of `chunk` frames (of F) can complete at the output rate, at most S_out
-int64_t resample_emit_cap(const ResamplePlan &rp, int chunk, int F, int hop, int64_t S_out) {
-    const int64_t cap = rp.count((int64_t)(chunk < F ? chunk : F) * hop + rp.K / 2) + 2;
-    return cap < S_out ? cap : S_out;
+// The staging slab carved for the resampled result of B rows of S_in input samples.  The run's inputs lived there: every
+// kernel that read them precedes the resampler on the stream (and a growing slab waits for the stream first).
+int resample_carve(vits_handle *h, int B, int64_t S_in, ResampleBufs &rb, int &S_out) {
+    if (int rc = resample_count(h, S_in, S_out)) return rc;
+    return slab_carve(h, h->io, "staging", [&](Carver &cv) { rb = carve_resample(cv, B, S_out, (int)h->rs.plan.K); });
 }
 
 // The whole waveform a run has just rendered (h->d_out, rows of h->S samples, ylen[b] * hop of them valid; no frame counts:
@@ -1929,30 +1919,49 @@ int resample_run(vits_handle *h, const int *ylen, int B) {
     return 0;
 }
 
+// The two pinned buffers (vits_handle::ring) finished pieces reach the host through.  A piece is copied into slot(); queue()
+// records the slot's event, hands the piece queued before it to the caller - whose callback so runs while this one renders -
+// and moves on to the other slot.  A piece that delivers nothing is never queued and the ring does not move: the pending slot,
+// which the callback may still be reading, is never the next one written.
+template <class Call>
+struct ChunkRing {
+    vits_handle *h;
+    Call call;                          // the caller's callback over (slot, first, n): its answer
+    int next = 0, pend = -1, stop = 0;  // stop: the last answer
+    int64_t pend_first = 0, pend_n = 0;
+    char *slot() const { return h->ring[next]; }
+    int deliver() {  // hand the pending piece to the caller
+        if (pend < 0) return 0;
+        if (hipEventSynchronize(h->ring_ev[pend]) != hipSuccess) return fail(h, VITS_E_DEVICE, "chunk copy failed");
+        stop = call(h->ring[pend], pend_first, pend_n);
+        pend = -1;
+        return 0;
+    }
+    int queue(int64_t first, int64_t n) {  // samples [first, first + n) of the rows have been enqueued into slot()
+        HIPCHECK(h, hipEventRecord(h->ring_ev[next], h->stream));
+        if (int rc = deliver()) return rc;  // (the previous piece, while this one renders)
+        pend = next;
+        pend_first = first;
+        pend_n = n;
+        next ^= 1;
+        return 0;
+    }
+};
+
 // Frames [0, F) of z rendered in chunks of sink->chunk_frames: each chunk is rendered together with gen_rf_frames of
 // context on either side (clipped at the utterance ends, where the generator really sees zero padding) and only its
 // interior is kept, so every sample equals the one an unchunked run produces (the convolutions accumulate in the same
-// order wherever a column sits in a tile).  Finished chunks go to the host through two pinned buffers; the callback
-// for chunk i runs while chunk i + 1 renders.
+// order wherever a column sits in a tile).  The interior then goes through the stages of stream_run.hip.hpp (resample, pack)
+// and what is left to deliver reaches the host through the ring; the callback for chunk i runs while chunk i + 1 renders.
 int render_chunks(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int z_cstride, const int *ylen, int B, int F,
                   const float *dec_cond, const FrameBufs &fb, int Fgen, const ChunkSink &sink) {
     const Model &m = h->model;
     hipStream_t st = h->stream;
     const int ov = m.gen_rf_frames, hop = m.hop;
     const int chunk = sink.chunk_frames;
-    // With an output rate set the chunks' interiors go through the resampler's piece entry, which keeps the last K input
-    // samples of every row on the device (the carry): after each chunk exactly the output samples whose K inputs now all
-    // exist are delivered, after the last one the rest (against zeros) - the batch path's [B][S_out], bit for bit.
-    const bool rs = h->rs.plan.on();
     const ResamplePlan &rp = h->rs.plan;
-    ResampleBufs rb{};
-    int S_out = 0, rs_gen = 0, emitted = 0;
-    int64_t emit_cap = 0;
-    // The encoded form of the sink: every chunk goes through stream_pack_kernel into the chunk buffer and reaches the ring as
-    // [B][pitch] bytes with the B running peaks behind them, in one copy.  enc == false executes what it always executed.
-    const bool enc = sink.fmt != nullptr;
-    const int enc_w = !enc ? 4 : (sink.fmt->encoding == VITS_ENC_PCM16 ? 2 : (sink.fmt->encoding == VITS_ENC_F32 ? 4 : 1));
-    StreamPackBufs sp{};
+    const bool rs = rp.on();             // an output rate: the batch path's [B][S_out], bit for bit
+    const bool enc = sink.fmt != nullptr;  // the encoded form of the sink; false executes what it always executed
     // encoded form: the rows' valid samples (host: the callback's valid[]; device: the kernel's)
     std::vector<int64_t> row_n;
     if (enc) {
@@ -1986,36 +1995,23 @@ int render_chunks(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int
         }
         shaped = shp.lookahead > 0 || any_shape(shp.shapes, B);
     }
+    // the sizes of the run's pieces, the one walk of the staging slab, the ring
     const int sL = shaped ? shp.lookahead : 0;  // the last chunk delivers sL samples more than it renders
-    const int64_t s_knots = shaped ? stream_knot_count(&shp, B) : 0;
-    StreamShapeBufs ssb{};
-    if (rs && enc) {
-        // (the chunk bound needs S_out, which the carve computes: state it from the same count)
-        const int64_t so = rp.count((int64_t)F * hop);
-        if (int rc = resample_carve(h, B, (int64_t)F * hop, rb, S_out, &sp, resample_emit_cap(rp, chunk, F, hop, so) + sL,
-                                    shaped ? &ssb : nullptr, sL, s_knots))
-            return rc;
-    } else if (rs) {
-        if (int rc = resample_carve(h, B, (int64_t)F * hop, rb, S_out)) return rc;
-    } else if (enc) {
-        const int64_t all = (int64_t)F * hop, most = (int64_t)(chunk < F ? chunk : F) * hop + sL;
-        if (int rc = slab_carve(h, h->io, "staging", [&](Carver &cv) {
-                sp = carve_stream_pack(cv, B, most < all ? most : all);
-                if (shaped) ssb = carve_stream_shape(cv, B, sL, s_knots);
-            }))
-            return rc;
-    }
+    int S_out = 0;
+    if (rs)
+        if (int rc = resample_count(h, (int64_t)F * hop, S_out)) return rc;
+    const int64_t total = rs ? (int64_t)S_out : (int64_t)F * hop, n_max = stream_n_max(rp, chunk, F, hop, sL, total);
+    StreamBufs sb{};
+    if (int rc = slab_carve(h, h->io, "staging", [&](Carver &cv) {
+            sb = carve_stream(cv, B, total, n_max, rs ? (int)rp.K : 0, enc, shaped, sL, shaped ? stream_knot_count(&shp, B) : 0);
+        }))
+        return rc;
+    ResampleRun rrun;
     if (rs) {
-        emit_cap = resample_emit_cap(rp, chunk, F, hop, S_out);  // output samples one chunk can complete
-        resample_counts_kernel<<<(B + 63) / 64, 64, 0, st>>>(ylen, hop, F * hop, rp.L, rp.M, rb.n_in, rb.n_out, B);
-        HIPCHECK(h, hipMemsetAsync(rb.carry[0], 0, (size_t)B * rp.K * sizeof(float), st));
+        HIPCHECK(h, resample_run_begin(rrun, h->rs, sb.rs, ylen, hop, F * hop, S_out, B, st));
         h->stats.total_launches++;
     }
-    // samples per row of the largest chunk: what a piece renders, and the look-ahead the last one delivers on top - never
-    // more than the row
-    const int64_t n_max = std::min<int64_t>((rs ? emit_cap : (int64_t)(chunk < F ? chunk : F) * hop) + sL, rs ? (int64_t)S_out : (int64_t)F * hop);
-    const size_t ring_bytes = enc ? (size_t)B * StreamPackBufs::pitch(enc_w, n_max) + StreamPackBufs::peak_floats(B) * sizeof(float)
-                              : rs ? (size_t)B * emit_cap * sizeof(float) : (size_t)B * chunk * hop * sizeof(float);
+    const size_t ring_bytes = stream_ring_bytes(B, n_max, enc ? delivery_width(sink.fmt->encoding) : 0);
     if (ring_bytes > h->ring_cap) {
         for (auto &r : h->ring) {
             if (r) hipHostFree(r);
@@ -2028,74 +2024,25 @@ int render_chunks(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int
     }
     for (auto &e : h->ring_ev)
         if (!e) hipEventCreateWithFlags(&e, hipEventDisableTiming);
+    StreamPackRun prun;
+    if (enc)
+        HIPCHECK(h, stream_pack_begin(prun, sink.fmt, shaped ? &shp : nullptr, B, sb.sp, sb.ss,
+                                      rs ? StreamPackRows{sb.rs.n_out, 1, S_out} : StreamPackRows{ylen, hop, F * hop}, total, st));
+    std::vector<int32_t> valid((size_t)(enc ? B : 0));
+    auto call = [&](const char *buf, int64_t first, int64_t n) -> int {  // the caller's callback over a finished piece
+        if (!enc) return sink.fn ? sink.fn(sink.user, reinterpret_cast<const float *>(buf), B, first, n, total) : 0;
+        const int64_t pitch = (int64_t)StreamPackBufs::pitch(prun.width, n);
+        for (int b = 0; b < B; b++) valid[b] = (int32_t)std::clamp<int64_t>(row_n[b] - first, 0, n);
+        const float *peaks = reinterpret_cast<const float *>(buf + (size_t)B * pitch);
+        return sink.efn ? sink.efn(sink.user, buf, B, pitch, first, n, valid.data(), peaks, total) : 0;
+    };
+    ChunkRing<decltype(call)> ring{h, call};
     // per-chunk valid lengths, ALWAYS passed: a chunk is a window into rows whose neighbours are real data, and only a
     // length mask makes the conv engines bound their reads by the chunk instead of by the row pitch
     int *yl = fb.gen.yl;
     Carver cv(h->frm.base, h->frm.cap);
     const int *const whole_len = c.h_len;  // host copy of ylen (or nullptr)
-    const int64_t total = rs ? (int64_t)S_out : (int64_t)F * hop;
-    int64_t pend_first = 0, pend_n = 0;
-    int pend = -1, k = 0, stop = 0;
-    // encoded form: the per-run upload [zeros of the running peaks | {ref_peak, volume} per row] in one copy, and the launch +
-    // copy of one chunk
-    std::vector<int32_t> valid;
-    StreamShapeRun srun;
-    StreamPackRows sp_rows{nullptr, 1, 0};
-    std::vector<float> up;  // (pageable source of an asynchronous copy: lives until the chunks behind it have been waited for)
-    if (enc) {
-        valid.resize((size_t)B);
-        sp_rows = rs ? StreamPackRows{rb.n_out, 1, S_out} : StreamPackRows{ylen, hop, F * hop};
-        const size_t Bp = StreamPackBufs::peak_floats(B);
-        up.assign(Bp + 2 * (size_t)B, 0.f);
-        for (int b = 0; b < B; b++) {
-            up[Bp + 2 * b] = sink.fmt->ref_peak ? sink.fmt->ref_peak[b] : 1.0f;
-            up[Bp + 2 * b + 1] = sink.fmt->volume ? sink.fmt->volume[b] : 1.0f;
-        }
-        HIPCHECK(h, hipMemcpyAsync(sp.peak_run, up.data(), up.size() * sizeof(float), hipMemcpyHostToDevice, st));
-        if (shaped) HIPCHECK(h, stream_shape_begin(srun, &shp, B, ssb, st));
-    }
-    // x: the chunk's [B][n] at row pitch x_pitch, its first column sample `first` of the rows.  [ef, ef + en): what it
-    // delivers - itself, or in a shaped stream with a look-ahead the range L samples behind it; en == 0: nothing, no copy
-    auto pack_chunk = [&](const float *x, int64_t x_pitch, int64_t first, int64_t n, int slot, int64_t &ef, int64_t &en) -> int {
-        unsigned char *d = nullptr;
-        if (shaped) {
-            int launches = 0;
-            const hipError_t e = stream_shape_chunk(srun, sink.fmt->encoding, enc_w, x, x_pitch, sp_rows, B, first, n, total, sp,
-                                                    sink.fmt->ref_peak != nullptr, st, ef, en, d, launches);
-            if (e != hipSuccess) return fail(h, VITS_E_DEVICE, "shaped stream pack launch failed: %s", hipGetErrorString(e));
-            h->stats.total_launches += launches;
-            if (en <= 0) return 0;
-        } else {
-            ef = first;
-            en = n;
-            d = sp.at(B, StreamPackBufs::pitch(enc_w, n));
-            const hipError_t e = launch_stream_pack(sink.fmt->encoding, x, x_pitch, sp_rows, B, (int)first, (int)n, sp.fmt,
-                                                    sink.fmt->ref_peak != nullptr, d, sp.peak_run, st);
-            if (e != hipSuccess) return fail(h, VITS_E_DEVICE, "stream pack launch failed: %s", hipGetErrorString(e));
-            h->stats.total_launches++;
-        }
-        const size_t pitch = StreamPackBufs::pitch(enc_w, en);
-        HIPCHECK(h, hipMemcpyAsync(h->ring[slot], d, (size_t)B * pitch + (size_t)B * sizeof(float), hipMemcpyDeviceToHost, st));
-        return 0;
-    };
-    auto deliver = [&]() -> int {  // hand the pending chunk to the caller
-        if (pend < 0) return 0;
-        if (hipEventSynchronize(h->ring_ev[pend]) != hipSuccess) return fail(h, VITS_E_DEVICE, "chunk copy failed");
-        if (enc) {
-            const int64_t pitch = (int64_t)StreamPackBufs::pitch(enc_w, pend_n);
-            for (int b = 0; b < B; b++) {
-                const int64_t v = row_n[b] - pend_first;
-                valid[b] = (int32_t)(v < 0 ? 0 : (v > pend_n ? pend_n : v));
-            }
-            stop = sink.efn ? sink.efn(sink.user, h->ring[pend], B, pitch, pend_first, pend_n, valid.data(),
-                                       reinterpret_cast<const float *>(h->ring[pend] + (size_t)B * pitch), total)
-                            : 0;
-        } else
-            stop = sink.fn ? sink.fn(sink.user, reinterpret_cast<const float *>(h->ring[pend]), B, pend_first, pend_n, total) : 0;
-        pend = -1;
-        return 0;
-    };
-    for (int f0 = 0; f0 < F && !stop; f0 += chunk, k ^= 1) {
+    for (int f0 = 0; f0 < F && !ring.stop; f0 += chunk) {
         const int f1 = f0 + chunk < F ? f0 + chunk : F;
         const int lo = f0 - ov > 0 ? f0 - ov : 0, hi = f1 + ov < F ? f1 + ov : F, n = hi - lo;
         cv.rewind(fb.gen_at);  // the previous chunk's workspace (its copy-out precedes this chunk on the stream)
@@ -2110,73 +2057,36 @@ int render_chunks(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int
         c.h_len = whole_len;
         if (rc_gen) return rc_gen;
         if (c.err != hipSuccess) return fail(h, VITS_E_DEVICE, "kernel launch failed: %s", hipGetErrorString(c.err));
-        const int64_t ns = (int64_t)(f1 - f0) * hop;
+        // the piece: the chunk's interior, samples [first, first + pn) of every row at x - what each stage leaves of it
+        const float *x = h->d_out + (int64_t)(f0 - lo) * hop;
+        int64_t x_pitch = h->S, first = (int64_t)f0 * hop, pn = (int64_t)(f1 - f0) * hop;
+        int launches = 0;
         if (rs) {
-            // interior of this chunk = input samples [f0 * hop, f1 * hop) of every row, behind the carry
-            const int64_t done = rp.complete((int64_t)f1 * hop);
-            const int n_hi = f1 == F ? S_out : (int)(done < S_out ? done : S_out), ne = n_hi - emitted;
-            ResampleArgs a = resample_args(h->rs);
-            a.x = h->d_out + (int64_t)(f0 - lo) * hop;
-            a.x_pitch = h->S;
-            a.x_first = (int)((int64_t)f0 * hop);
-            a.x_n = (int)ns;
-            a.carry = rb.carry[rs_gen];
-            a.n_in = rb.n_in;
-            a.n_out = rb.n_out;
-            a.y = rb.out;  // [B][ne]: what this chunk completes (the previous chunk's copy-out precedes it on the stream)
-            a.y_pitch = ne;
-            a.y_first = emitted;
-            a.n_lo = emitted;
-            a.n_hi = n_hi;
-            hipError_t e = launch_resample(a, B, /*piece=*/true, st);
-            if (e == hipSuccess && f1 < F) {
-                resample_carry_kernel<<<dim3((unsigned)((rp.K + 255) / 256), B), 256, 0, st>>>(rb.carry[rs_gen], a.x, a.x_pitch, a.x_n,
-                                                                                            a.K, rb.carry[rs_gen ^ 1]);
-                e = hipGetLastError();
-                rs_gen ^= 1;
-            }
+            const hipError_t e = resample_run_piece(rrun, x, x_pitch, first, pn, f1 == F, B, st, first, pn, launches);
             if (e != hipSuccess) return fail(h, VITS_E_DEVICE, "resampler launch failed: %s", hipGetErrorString(e));
-            h->stats.total_launches += 2;
-            if (ne <= 0) {  // (a chunk shorter than the filter's look-ahead completes nothing: no call)
-                k ^= 1;
-                continue;
-            }
-            int64_t ef = emitted, en = ne;
-            emitted = n_hi;
-            if (enc) {
-                if (int rc = pack_chunk(rb.out, ne, ef, ne, k, ef, en)) return rc;
-                if (en <= 0) {  // (a shaped stream: the piece lies inside the look-ahead)
-                    k ^= 1;
-                    continue;
-                }
-            } else
-                HIPCHECK(h, hipMemcpyAsync(h->ring[k], rb.out, (size_t)B * ne * 4, hipMemcpyDeviceToHost, st));
-            HIPCHECK(h, hipEventRecord(h->ring_ev[k], st));
-            if (int rc = deliver()) return rc;
-            pend = k;
-            pend_first = ef;
-            pend_n = en;
-            continue;
+            h->stats.total_launches += launches;
+            x = sb.rs.out;  // [B][pn]
+            x_pitch = pn;
         }
-        // interior of this chunk: samples [(f0 - lo) * hop, (f1 - lo) * hop) of every row -> ring[k] as [B, ns]
-        int64_t ef = (int64_t)f0 * hop, en = ns;
-        if (enc) {
-            if (int rc = pack_chunk(h->d_out + (int64_t)(f0 - lo) * hop, h->S, (int64_t)f0 * hop, ns, k, ef, en)) return rc;
-            if (en <= 0) {  // (a shaped stream: the piece lies inside the look-ahead)
-                k ^= 1;
-                continue;
-            }
-        } else
-            HIPCHECK(h, hipMemcpy2DAsync(h->ring[k], (size_t)ns * 4, h->d_out + (int64_t)(f0 - lo) * hop, (size_t)h->S * 4,
-                                         (size_t)ns * 4, B, hipMemcpyDeviceToHost, st));
-        HIPCHECK(h, hipEventRecord(h->ring_ev[k], st));
-        if (int rc = deliver()) return rc;  // (the previous chunk, while this one renders)
-        pend = k;
-        pend_first = ef;
-        pend_n = en;
+        unsigned char *d = nullptr;
+        size_t pitch = 0;
+        if (enc && pn > 0) {
+            const hipError_t e = stream_pack_piece(prun, x, x_pitch, first, pn, B, st, d, first, pn, pitch, launches);
+            if (e != hipSuccess) return fail(h, VITS_E_DEVICE, "%sstream pack launch failed: %s", shaped ? "shaped " : "", hipGetErrorString(e));
+            h->stats.total_launches += launches;
+        }
+        // (a chunk shorter than the filter's or the limiter's look-ahead completes nothing: no copy, no call, the same slot next)
+        if (pn <= 0) continue;
+        if (enc)  // bytes and peaks in one copy
+            HIPCHECK(h, hipMemcpyAsync(ring.slot(), d, (size_t)B * pitch + (size_t)B * sizeof(float), hipMemcpyDeviceToHost, st));
+        else if (rs)
+            HIPCHECK(h, hipMemcpyAsync(ring.slot(), x, (size_t)B * pn * 4, hipMemcpyDeviceToHost, st));
+        else  // straight out of the rendered rows
+            HIPCHECK(h, hipMemcpy2DAsync(ring.slot(), (size_t)pn * 4, x, (size_t)x_pitch * 4, (size_t)pn * 4, B, hipMemcpyDeviceToHost, st));
+        if (int rc = ring.queue(first, pn)) return rc;
     }
-    if (!stop)
-        if (int rc = deliver()) return rc;
+    if (!ring.stop)
+        if (int rc = ring.deliver()) return rc;
     h->S = (int)total;
     h->d_out = nullptr;  // (no whole waveform exists on the device after a chunked run)
     return 0;
@@ -2687,25 +2597,19 @@ int vits_reserve(vits_handle *h, int B, int T, int F) {
         // ... and vits_deliver_limited's gain buffer last
         const DeliveryNeeds all{/*scan=*/true, /*levelled=*/true, /*shaped=*/true, shape_pts, /*limited=*/true};
         const size_t io_dlv = carved_bytes([&](Carver &cv) { carve_delivery_call(cv, B, F * m.hop, all); });
-        // ... or an encoded stream's chunk buffer: every chunk_frames <= F, i.e. chunks of up to F * hop samples
-        // (shaped: the rows' records and knots and the limiter's carries for the longest look-ahead behind it; a chunk never
-        // exceeds the row, so the L samples the last chunk delivers beyond what it renders are inside F * hop)
-        const size_t io_sp = carved_bytes([&](Carver &cv) {
-            carve_stream_pack(cv, B, (int64_t)F * m.hop);
-            carve_stream_shape(cv, B, VITS_LIMIT_MAX_LOOKAHEAD, shape_pts);
-        });
+        // ... or a stream's (carve_stream): every chunk_frames <= F, i.e. chunks of up to the row's samples - the look-ahead the
+        // last chunk delivers beyond what it renders included -, shaped for the longest look-ahead; at an output rate K > 0
+        const auto stream_bytes = [&](int64_t row, int K) {
+            return carved_bytes([&](Carver &cv) { carve_stream(cv, B, row, row, K, true, true, VITS_LIMIT_MAX_LOOKAHEAD, shape_pts); });
+        };
+        const size_t io_sp = stream_bytes((int64_t)F * m.hop, 0);
         size_t io = io_in > io_pcm ? io_in : io_pcm;
         io = io_dlv > io ? io_dlv : io;
         io = io_sp > io ? io_sp : io;
         if (h->rs.plan.on()) {  // ... or the resampled waveform with its own 16-bit rendering and delivery buffers
             const int64_t so = h->rs.plan.count((int64_t)F * m.hop);
             if (so > INT_MAX) return fail(h, VITS_E_ARG, "vits_reserve: F=%d frames are %lld samples at %d Hz", F, (long long)so, h->rs.plan.fo);
-            // (with the encoded stream's buffers behind them: chunks of up to `so` samples)
-            const size_t io_rs = carved_bytes([&](Carver &cv) {
-                carve_resample(cv, B, (int)so, (int)h->rs.plan.K);
-                carve_stream_pack(cv, B, so);
-                carve_stream_shape(cv, B, VITS_LIMIT_MAX_LOOKAHEAD, shape_pts);
-            });
+            const size_t io_rs = stream_bytes(so, (int)h->rs.plan.K);
             io = io_rs > io ? io_rs : io;
             // (a trimmed delivery's slots and a levelled one's buffers lie behind the resampled result too: in the place of
             // an encoded stream's buffers)
@@ -4366,89 +4270,31 @@ int vits_test_loudness_blocks(int device_id, const float *x, const int64_t *coun
     return VITS_OK;
 }
 
-int vits_test_stream_pack(int device_id, const float *x, const int64_t *counts, int B, int S, int piece_samples,
-                          const vits_stream_format *fmt, void *bytes, size_t bytes_cap, int64_t *pitches, int32_t *valid, float *peaks,
-                          int max_pieces) {
+// The encoded stream's pieces by value: what both hooks are.  x [B][S] in pieces of piece_samples through the pipeline's pack
+// stage (stream_run.hip.hpp) over the pipeline's walk - `shaped`: through the shaped stream's kernels, with `shaping`
+// (nullable) - and every piece's bytes and peaks out in one copy, as the pipeline.  firsts / ns: nullable.
+namespace {
+int stream_pack_test(int device_id, const float *x, const int64_t *counts, int B, int S, int piece_samples, const vits_stream_format *fmt,
+                     bool shaped, const vits_stream_shaping *shaping, void *bytes, size_t bytes_cap, int64_t *pitches, int32_t *valid,
+                     float *peaks, int64_t *firsts, int64_t *ns, int max_pieces) {
     if (!x || !counts || !bytes || !pitches || !valid || !peaks || B <= 0 || B > 65535 || S <= 0 || piece_samples < 1 ||
         (int64_t)B * S > (int64_t)1 << 40)
         return fail(nullptr, VITS_E_ARG, "bad stream pack test arguments");
     for (int b = 0; b < B; b++)
         if (counts[b] < 0 || counts[b] > S) return fail(nullptr, VITS_E_ARG, "counts[%d] = %lld outside [0, %d]", b, (long long)counts[b], S);
     if (int rc = host_stream_format(nullptr, fmt, B)) return rc;
-    const int w = fmt->encoding == VITS_ENC_PCM16 ? 2 : (fmt->encoding == VITS_ENC_F32 ? 4 : 1);
-    const int64_t pieces = ((int64_t)S + piece_samples - 1) / piece_samples;
-    size_t need = 0;
-    for (int64_t f0 = 0; f0 < S; f0 += piece_samples)
-        need += (size_t)B * StreamPackBufs::pitch(w, S - f0 > piece_samples ? piece_samples : S - f0);
-    if (pieces > max_pieces || need > bytes_cap)
-        return fail(nullptr, VITS_E_ARG, "%lld pieces of %zu bytes: room for %d pieces and %zu bytes", (long long)pieces, need, max_pieces, bytes_cap);
-    if (int rc = test_dev(device_id)) return rc;
-    DevBufs D;
-    float *dx = D.up(x, (size_t)B * S);
-    std::vector<int> c32((size_t)B);
-    for (int b = 0; b < B; b++) c32[b] = (int)counts[b];
-    int *dcount = D.up(c32.data(), (size_t)B);
-    // the pipeline's buffer, by the pipeline's walk
-    const int64_t n_max = piece_samples < S ? piece_samples : S;
-    const size_t total = carved_bytes([&](Carver &cv) { carve_stream_pack(cv, B, n_max); });
-    unsigned char *slab = D.alloc<unsigned char>(total);
-    TCHECK(D.err);
-    Carver cv(slab, total);
-    const StreamPackBufs sp = carve_stream_pack(cv, B, n_max);
-    if (!cv.fits()) return fail(nullptr, VITS_E_NOMEM, "stream pack walk carved %zu of %zu bytes", cv.used, cv.cap);
-    const size_t Bp = StreamPackBufs::peak_floats(B);
-    std::vector<float> up(Bp + 2 * (size_t)B, 0.f);
-    for (int b = 0; b < B; b++) {
-        up[Bp + 2 * b] = fmt->ref_peak ? fmt->ref_peak[b] : 1.0f;
-        up[Bp + 2 * b + 1] = fmt->volume ? fmt->volume[b] : 1.0f;
-    }
-    TCHECK(hipMemcpy(sp.peak_run, up.data(), up.size() * sizeof(float), hipMemcpyHostToDevice));
-    const StreamPackRows rows{dcount, 1, S};
-    unsigned char *dst = static_cast<unsigned char *>(bytes);
-    std::vector<unsigned char> landing;
-    int k = 0;
-    for (int64_t f0 = 0; f0 < S; f0 += piece_samples, k++) {
-        const int64_t n = S - f0 > piece_samples ? piece_samples : S - f0;
-        const size_t pitch = StreamPackBufs::pitch(w, n);
-        unsigned char *d = sp.at(B, pitch);
-        TCHECK(launch_stream_pack(fmt->encoding, dx + f0, S, rows, B, (int)f0, (int)n, sp.fmt, fmt->ref_peak != nullptr, d, sp.peak_run, nullptr));
-        TCHECK(hipDeviceSynchronize());
-        landing.resize((size_t)B * pitch + (size_t)B * sizeof(float));
-        TCHECK(hipMemcpy(landing.data(), d, landing.size(), hipMemcpyDeviceToHost));  // bytes and peaks in one copy, as the pipeline
-        std::memcpy(dst, landing.data(), (size_t)B * pitch);
-        std::memcpy(peaks + (size_t)k * B, landing.data() + (size_t)B * pitch, (size_t)B * sizeof(float));
-        dst += (size_t)B * pitch;
-        pitches[k] = (int64_t)pitch;
-        for (int b = 0; b < B; b++) {
-            const int64_t v = counts[b] - f0;
-            valid[(size_t)k * B + b] = (int32_t)(v < 0 ? 0 : (v > n ? n : v));
-        }
-    }
-    return k;
-}
-
-int vits_test_stream_pack_shaped(int device_id, const float *x, const int64_t *counts, int B, int S, int piece_samples,
-                                 const vits_stream_format *fmt, const vits_stream_shaping *shaping, void *bytes, size_t bytes_cap,
-                                 int64_t *pitches, int32_t *valid, float *peaks, int64_t *firsts, int64_t *ns, int max_pieces) {
-    if (!x || !counts || !bytes || !pitches || !valid || !peaks || !firsts || !ns || B <= 0 || B > 65535 || S <= 0 || piece_samples < 1 ||
-        (int64_t)B * S > (int64_t)1 << 40)
-        return fail(nullptr, VITS_E_ARG, "bad stream pack test arguments");
-    for (int b = 0; b < B; b++)
-        if (counts[b] < 0 || counts[b] > S) return fail(nullptr, VITS_E_ARG, "counts[%d] = %lld outside [0, %d]", b, (long long)counts[b], S);
-    if (int rc = host_stream_format(nullptr, fmt, B)) return rc;
-    if (int rc = host_stream_shaping(nullptr, shaping, fmt, B)) return rc;
+    if (shaped)
+        if (int rc = host_stream_shaping(nullptr, shaping, fmt, B)) return rc;
     const vits_stream_shaping none{};
-    const vits_stream_shaping &shp = shaping ? *shaping : none;  // (the hook always runs the shaped kernels: that is its subject)
-    const int L = shp.lookahead;
-    const int w = fmt->encoding == VITS_ENC_PCM16 ? 2 : (fmt->encoding == VITS_ENC_F32 ? 4 : 1);
+    const vits_stream_shaping *shp = !shaped ? nullptr : (shaping ? shaping : &none);  // (the shaped hook always runs the shaped kernels)
+    const int L = shp ? shp->lookahead : 0;
+    const int w = delivery_width(fmt->encoding);
     const int64_t pieces = ((int64_t)S + piece_samples - 1) / piece_samples;
     size_t need = 0;
-    int64_t n_max = 1;
     for (int64_t f0 = 0; f0 < S; f0 += piece_samples) {
         int64_t ef, en;
         stream_emit_range(f0, S - f0 > piece_samples ? piece_samples : S - f0, f0 + piece_samples >= S, S, L, ef, en);
         if (en > 0) need += (size_t)B * StreamPackBufs::pitch(w, en);
-        n_max = en > n_max ? en : n_max;
     }
     if (pieces > max_pieces || need > bytes_cap)
         return fail(nullptr, VITS_E_ARG, "%lld pieces of %zu bytes: room for %d pieces and %zu bytes", (long long)pieces, need, max_pieces, bytes_cap);
@@ -4459,59 +4305,57 @@ int vits_test_stream_pack_shaped(int device_id, const float *x, const int64_t *c
     for (int b = 0; b < B; b++) c32[b] = (int)counts[b];
     int *dcount = D.up(c32.data(), (size_t)B);
     // the pipeline's buffers, by the pipeline's walk
-    const int64_t knots = stream_knot_count(&shp, B);
-    StreamPackBufs sp{};
-    StreamShapeBufs ssb{};
-    auto walk = [&](Carver &cv) {
-        sp = carve_stream_pack(cv, B, n_max);
-        ssb = carve_stream_shape(cv, B, L, knots);
-    };
+    const int64_t n_max = stream_n_max(ResamplePlan{}, piece_samples, S, 1, L, S);  // (piece_samples "frames" of one sample)
+    const auto walk = [&](Carver &cv) { return carve_stream(cv, B, S, n_max, 0, /*enc=*/true, shaped, L, shaped ? stream_knot_count(shp, B) : 0); };
     const size_t total = carved_bytes(walk);
-    unsigned char *slab = D.alloc<unsigned char>(total);
+    Carver cv(D.alloc<unsigned char>(total), total);
     TCHECK(D.err);
-    Carver cv(slab, total);
-    walk(cv);
-    if (!cv.fits()) return fail(nullptr, VITS_E_NOMEM, "stream shape walk carved %zu of %zu bytes", cv.used, cv.cap);
-    const size_t Bp = StreamPackBufs::peak_floats(B);
-    std::vector<float> up(Bp + 2 * (size_t)B, 0.f);
-    for (int b = 0; b < B; b++) {
-        up[Bp + 2 * b] = fmt->ref_peak ? fmt->ref_peak[b] : 1.0f;
-        up[Bp + 2 * b + 1] = fmt->volume ? fmt->volume[b] : 1.0f;
-    }
-    TCHECK(hipMemcpy(sp.peak_run, up.data(), up.size() * sizeof(float), hipMemcpyHostToDevice));
-    StreamShapeRun srun;
-    TCHECK(stream_shape_begin(srun, &shp, B, ssb, nullptr));
-    const StreamPackRows rows{dcount, 1, S};
+    const StreamBufs sb = walk(cv);
+    if (!cv.fits()) return fail(nullptr, VITS_E_NOMEM, "stream walk carved %zu of %zu bytes", cv.used, cv.cap);
+    StreamPackRun run;
+    TCHECK(stream_pack_begin(run, fmt, shp, B, sb.sp, sb.ss, StreamPackRows{dcount, 1, S}, S, nullptr));
     unsigned char *dst = static_cast<unsigned char *>(bytes);
     std::vector<unsigned char> landing;
     int k = 0;
     for (int64_t f0 = 0; f0 < S; f0 += piece_samples, k++) {
-        const int64_t n = S - f0 > piece_samples ? piece_samples : S - f0;
         int64_t ef = 0, en = 0;
         unsigned char *d = nullptr;
+        size_t pitch = 0;
         int launches = 0;
-        const hipError_t enq = stream_shape_chunk(srun, fmt->encoding, w, dx + f0, S, rows, B, f0, n, S, sp, fmt->ref_peak != nullptr, nullptr, ef,
-                                                  en, d, launches);
+        const int64_t n = S - f0 > piece_samples ? piece_samples : S - f0;
+        const hipError_t enq = stream_pack_piece(run, dx + f0, S, f0, n, B, nullptr, d, ef, en, pitch, launches);
         const hipError_t done = hipDeviceSynchronize();
         TCHECK(enq);
         TCHECK(done);
-        firsts[k] = ef;
-        ns[k] = en;
+        if (firsts) firsts[k] = ef;
+        if (ns) ns[k] = en;
         pitches[k] = 0;
         if (en <= 0) continue;
-        const size_t pitch = StreamPackBufs::pitch(w, en);
         landing.resize((size_t)B * pitch + (size_t)B * sizeof(float));
         TCHECK(hipMemcpy(landing.data(), d, landing.size(), hipMemcpyDeviceToHost));  // bytes and peaks in one copy, as the pipeline
         std::memcpy(dst, landing.data(), (size_t)B * pitch);
         std::memcpy(peaks + (size_t)k * B, landing.data() + (size_t)B * pitch, (size_t)B * sizeof(float));
         dst += (size_t)B * pitch;
         pitches[k] = (int64_t)pitch;
-        for (int b = 0; b < B; b++) {
-            const int64_t v = counts[b] - ef;
-            valid[(size_t)k * B + b] = (int32_t)(v < 0 ? 0 : (v > en ? en : v));
-        }
+        for (int b = 0; b < B; b++) valid[(size_t)k * B + b] = (int32_t)std::clamp<int64_t>(counts[b] - ef, 0, en);
     }
     return k;
+}
+}  // namespace
+
+int vits_test_stream_pack(int device_id, const float *x, const int64_t *counts, int B, int S, int piece_samples,
+                          const vits_stream_format *fmt, void *bytes, size_t bytes_cap, int64_t *pitches, int32_t *valid, float *peaks,
+                          int max_pieces) {
+    return stream_pack_test(device_id, x, counts, B, S, piece_samples, fmt, /*shaped=*/false, nullptr, bytes, bytes_cap, pitches, valid, peaks,
+                            nullptr, nullptr, max_pieces);
+}
+
+int vits_test_stream_pack_shaped(int device_id, const float *x, const int64_t *counts, int B, int S, int piece_samples,
+                                 const vits_stream_format *fmt, const vits_stream_shaping *shaping, void *bytes, size_t bytes_cap,
+                                 int64_t *pitches, int32_t *valid, float *peaks, int64_t *firsts, int64_t *ns, int max_pieces) {
+    if (!firsts || !ns) return fail(nullptr, VITS_E_ARG, "bad stream pack test arguments");
+    return stream_pack_test(device_id, x, counts, B, S, piece_samples, fmt, /*shaped=*/true, shaping, bytes, bytes_cap, pitches, valid, peaks,
+                            firsts, ns, max_pieces);
 }
 
 int vits_test_resample_pieces(int device_id, const float *x, const int64_t *lens, int B, int S, int in_rate, int out_rate,
@@ -4522,48 +4366,35 @@ int vits_test_resample_pieces(int device_id, const float *x, const int64_t *lens
     ResampleTest t;
     if (int rc = resample_test_setup(D, lens, B, S, in_rate, out_rate, t)) return rc;
     const ResamplePlan &p = t.dev.plan;
-    const int total = (int)p.count(S), K = (int)p.K;
+    const int total = (int)p.count(S);
     if (S_out < total) return fail(nullptr, VITS_E_ARG, "S_out = %lld, %d input samples give %d", (long long)S_out, S, total);
     float *dx = D.up(x, (size_t)B * S);
-    float *dy = D.fill<float>((size_t)B * total, 0xff);  // one piece's output [B][ne]
-    float *carry[2] = {D.fill<float>((size_t)B * K), D.fill<float>((size_t)B * K)};
+    // the pipeline's buffers, by the pipeline's walk (poisoned); the rows' counts by its kernel, from the clipped lens
+    const auto walk = [&](Carver &cv) { return carve_stream(cv, B, total, total, (int)p.K, /*enc=*/false, false, 0, 0); };
+    const size_t bytes = carved_bytes(walk);
+    Carver cv(D.fill<unsigned char>(bytes, 0xff), bytes);
     TCHECK(D.err);
+    const StreamBufs sb = walk(cv);
+    if (!cv.fits()) return fail(nullptr, VITS_E_NOMEM, "stream walk carved %zu of %zu bytes", cv.used, cv.cap);
+    ResampleRun run;
+    TCHECK(resample_run_begin(run, t.dev, sb.rs, t.d_n_in, 1, S, total, B, nullptr));
     std::vector<float> piece((size_t)B * total);
     std::memset(y, 0, (size_t)B * S_out * sizeof(float));
-    int emitted = 0, gen = 0, calls = 0;
-    for (int f0 = 0; f0 < S; f0 += piece_samples) {
-        const int f1 = S - f0 > piece_samples ? f0 + piece_samples : S;
-        const int64_t done = p.complete(f1);
-        const int n_hi = f1 == S ? total : (int)(done < total ? done : total), ne = n_hi - emitted;
-        ResampleArgs a = resample_args(t.dev);
-        a.x = dx + f0;
-        a.x_pitch = S;
-        a.x_first = f0;
-        a.x_n = f1 - f0;
-        a.carry = carry[gen];
-        a.n_in = t.d_n_in;
-        a.n_out = t.d_n_out;
-        a.y = dy;
-        a.y_pitch = ne;
-        a.y_first = emitted;
-        a.n_lo = emitted;
-        a.n_hi = n_hi;
-        TCHECK(launch_resample(a, B, /*piece=*/true, nullptr));
-        if (f1 < S) {
-            resample_carry_kernel<<<dim3((unsigned)((K + 255) / 256), B), 256>>>(carry[gen], a.x, a.x_pitch, a.x_n, K, carry[gen ^ 1]);
-            TCHECK(hipGetLastError());
-            gen ^= 1;
-        }
-        if (ne <= 0) continue;
+    int calls = 0;
+    for (int64_t f0 = 0; f0 < S; f0 += piece_samples) {
+        const int64_t n = S - f0 > piece_samples ? piece_samples : S - f0;
+        int64_t ef = 0, en = 0;
+        int launches = 0;
+        TCHECK(resample_run_piece(run, dx + f0, S, f0, n, f0 + n == S, B, nullptr, ef, en, launches));
+        if (en <= 0) continue;  // (a piece shorter than the filter's look-ahead completes nothing)
         TCHECK(hipDeviceSynchronize());
-        TCHECK(download(piece.data(), dy, (size_t)B * ne));
-        for (int b = 0; b < B; b++) std::memcpy(y + (size_t)b * S_out + emitted, piece.data() + (size_t)b * ne, (size_t)ne * sizeof(float));
+        TCHECK(download(piece.data(), sb.rs.out, (size_t)B * en));
+        for (int b = 0; b < B; b++) std::memcpy(y + (size_t)b * S_out + ef, piece.data() + (size_t)b * en, (size_t)en * sizeof(float));
         if (ranges && calls < max_ranges) {
-            ranges[2 * calls] = emitted;
-            ranges[2 * calls + 1] = ne;
+            ranges[2 * calls] = ef;
+            ranges[2 * calls + 1] = en;
         }
         calls++;
-        emitted = n_hi;
     }
     TCHECK(hipDeviceSynchronize());
     return calls;

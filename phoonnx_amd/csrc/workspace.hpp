@@ -14,6 +14,7 @@
 #include "limit.hpp"
 #include "loudness.hpp"
 #include "model.hpp"
+#include "resample.hpp"
 #include "shape.hpp"
 #include "slab.hpp"
 #include "stream_shape.hpp"
@@ -389,8 +390,7 @@ inline DeliveryCallBufs carve_delivery_call(Carver &cv, int B, int S, const Deli
 // chunk_frames a call brings; the running peaks [B] (padded to whole 16-byte cells) sit right behind at a 16-byte-aligned
 // offset and never move, and a chunk's [B][pitch] bytes END at them (at()), so one copy of B * pitch + 4 * B bytes carries a
 // chunk and its peaks.  Behind the peaks: {ref_peak, volume} per row, uploaded with the peaks' zeros in one copy per run.
-// In a resampled run it is carved behind carve_resample's buffers in the same walk of the staging slab (the chunk it
-// packs lives there); in a native run from the slab's base, like vits_deliver's buffers: the run's inputs are consumed.
+// Carved by carve_stream (below) and nowhere else.
 struct StreamPackBufs {
     unsigned char *buf;
     size_t cap;
@@ -412,8 +412,8 @@ inline StreamPackBufs carve_stream_pack(Carver &cv, int B, int64_t n_max) {
     return s;
 }
 
-// A shaped, limited encoded stream (vits_run_chunked_enc_shaped) carves this behind carve_stream_pack in the same walk: the
-// rows' records and the knots of their envelopes, and the two generations of the limiter's carry - the last 2 L raw samples
+// A shaped, limited encoded stream (vits_run_chunked_enc_shaped) has this behind carve_stream_pack in the same walk (carve_stream):
+// the rows' records and the knots of their envelopes, and the two generations of the limiter's carry - the last 2 L raw samples
 // of every row, one read while the other is written.  The chunk buffer's L extra samples per row - the last chunk delivers L
 // more than it renders - are carve_stream_pack's: the caller hands it n_max + L.
 struct StreamShapeBufs {
@@ -427,6 +427,51 @@ inline StreamShapeBufs carve_stream_shape(Carver &cv, int B, int L, int64_t n_kn
     s.rows = cv.take<StreamShapeRow>(B);
     s.knots = cv.take<ShapeKnot>((size_t)n_knots);
     for (auto &c : s.carry) c = cv.take<float>((size_t)B * 2 * L);
+    return s;
+}
+
+// ---- a streamed run (vitsmi.hip, render_chunks; its stages: stream_run.hip.hpp): the sizes of its pieces - host arithmetic, so
+// that a CPU program can walk every schedule - and the ONE walk of the staging slab.  A chunk renders input samples [f0 * hop, f1 * hop);
+// at an output rate it completes the outputs whose K inputs all exist; a look-ahead of L delivers what lies L behind that (stream_emit_range).
+
+// output samples one chunk of `chunk` frames (of F) can complete at the output rate, at most S_out
+inline int64_t resample_emit_cap(const ResamplePlan &rp, int chunk, int F, int hop, int64_t S_out) {
+    const int64_t cap = rp.count((int64_t)(chunk < F ? chunk : F) * hop + rp.K / 2) + 2;
+    return cap < S_out ? cap : S_out;
+}
+
+// the output samples complete once the input in front of position `end` exists (the last piece: all S_out)
+inline int64_t resample_emit_end(const ResamplePlan &rp, int64_t end, bool is_last, int64_t S_out) {
+    const int64_t done = rp.complete(end);
+    return is_last || done > S_out ? S_out : done;
+}
+
+// samples per row of the largest piece a run delivers: what a chunk renders (at a rate: completes) + the look-ahead L, at most the row
+inline int64_t stream_n_max(const ResamplePlan &rp, int chunk, int F, int hop, int L, int64_t total) {
+    const int64_t piece = rp.on() ? resample_emit_cap(rp, chunk, F, hop, total) : (int64_t)(chunk < F ? chunk : F) * hop;
+    return piece + L < total ? piece + L : total;
+}
+
+// bytes of one pinned ring slot: B rows of the largest piece as fp32 (width 0: a float sink) or encoded, the running peaks behind
+inline size_t stream_ring_bytes(int B, int64_t n_max, int width) {
+    if (!width) return (size_t)B * n_max * sizeof(float);
+    return (size_t)B * StreamPackBufs::pitch(width, n_max) + StreamPackBufs::peak_floats(B) * sizeof(float);
+}
+
+// What a streamed run takes from the staging slab (from its base: the run's inputs are consumed), in this order: at an output
+// rate (K > 0: the resampler's) carve_resample's buffers for rows of `row` output samples - the chunk the stream packs lives
+// there -, an encoded sink's chunk buffer for pieces of n_max samples, a shaped one's tables and carries.  The rest stays zero.
+struct StreamBufs {
+    ResampleBufs rs;
+    StreamPackBufs sp;
+    StreamShapeBufs ss;
+};
+
+inline StreamBufs carve_stream(Carver &cv, int B, int64_t row, int64_t n_max, int K, bool enc, bool shaped, int L, int64_t n_knots) {
+    StreamBufs s{};
+    if (K > 0) s.rs = carve_resample(cv, B, (int)row, K);
+    if (enc) s.sp = carve_stream_pack(cv, B, n_max);
+    if (enc && shaped) s.ss = carve_stream_shape(cv, B, L, n_knots);
     return s;
 }
 

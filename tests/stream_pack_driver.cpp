@@ -1,6 +1,6 @@
 // Driver of test_stream_pack_cpu.py: workspace.hpp + slab.hpp under the host compiler, no HIP.  Walks the encoded stream's
-// workspace (carve_stream_pack) - alone (a native run carves it from the staging slab's base) and behind carve_resample's
-// buffers in one walk (a run at an output rate) - over a grid of request sizes: once dry, once over a fake base (never
+// workspace (carve_stream, the one walk of a streamed run) - alone (a native run carves it from the staging slab's base) and
+// behind carve_resample's buffers (a run at an output rate) - over a grid of request sizes: once dry, once over a fake base (never
 // dereferenced), once with one byte too little; and places a chunk of every encoding and of several lengths up to n_max to see
 // that its bytes start inside the buffer, 16-byte aligned, and end exactly at the running peaks.  One line per (B, n_max, K):
 //   <B> <n_max> <K> A <stream pack bytes> <resample + stream pack bytes>     every check held
@@ -62,7 +62,7 @@ void stream_extents(std::vector<Ext> &e, const StreamPackBufs &s, int B, size_t 
 
 std::vector<Ext> alone(Carver &cv, int B, size_t n_max, std::string *placed) {
     std::vector<Ext> e;
-    const StreamPackBufs s = carve_stream_pack(cv, B, (int64_t)n_max);
+    const StreamPackBufs s = carve_stream(cv, B, (int64_t)n_max, (int64_t)n_max, /*K=*/0, /*enc=*/true, /*shaped=*/false, 0, 0).sp;
     stream_extents(e, s, B, n_max);
     if (cv.base && placed) {
         // a chunk of n samples at w bytes: [B][pitch] bytes that end at the peaks
@@ -82,13 +82,14 @@ std::vector<Ext> alone(Carver &cv, int B, size_t n_max, std::string *placed) {
 }
 
 std::vector<Ext> resampled(Carver &cv, int B, size_t S, int K, size_t n_max) {
-    const ResampleBufs r = carve_resample(cv, B, (int)S, K);
+    const StreamBufs sb = carve_stream(cv, B, (int64_t)S, (int64_t)n_max, K, /*enc=*/true, /*shaped=*/false, 0, 0);
+    const ResampleBufs &r = sb.rs;
     std::vector<Ext> e = {{"out", r.out, (size_t)B * S * 4}, {"n_in", r.n_in, (size_t)B * 4}, {"n_out", r.n_out, (size_t)B * 4},
                           {"carry0", r.carry[0], (size_t)B * K * 4}, {"carry1", r.carry[1], (size_t)B * K * 4},
                           {"pcm", r.pcm.pcm, (size_t)B * S * 2}, {"pcm peak", r.pcm.peak, (size_t)B * 4},
                           {"packed", r.dlv.packed, round16((size_t)B * S * 4)}, {"segs", r.dlv.segs, (size_t)B * 32},
                           {"peak", r.dlv.peak, (size_t)B * 2 * 4}};
-    const StreamPackBufs s = carve_stream_pack(cv, B, (int64_t)n_max);
+    const StreamPackBufs &s = sb.sp;
     stream_extents(e, s, B, n_max);
     if (cv.base && (const char *)s.buf < (const char *)r.dlv.peak) e.push_back({"stream pack (behind the resampler's buffers)", nullptr, 0});
     return e;

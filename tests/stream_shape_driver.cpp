@@ -1,12 +1,16 @@
 // Driver of test_stream_shape_cpu.py: workspace.hpp + stream_shape.hpp under the host compiler, no HIP.  Walks the shaped
-// stream's workspace - carve_stream_pack for the chunk of n_max + L samples, carve_stream_shape behind it in the same walk;
-// alone (a native run) and behind carve_resample's buffers (a run at an output rate) - over a grid of request sizes: once
-// dry, once over a fake base (never dereferenced), once with one byte too little.  Then the plan's host code on real memory:
-// the rows' records and knots of a shaping (stream_shape_table), and the timeline over pieces of several sizes.  Lines:
+// stream's workspace - carve_stream, the one walk of a streamed run: the chunk buffer for n_max + L samples, the shaped
+// stream's tables behind it; alone (a native run) and behind carve_resample's buffers (a run at an output rate) - over a grid
+// of request sizes: once dry, once over a fake base (never dereferenced), once with one byte too little.  Then the plan's host
+// code on real memory: the rows' records and knots of a shaping (stream_shape_table), and the timeline over pieces of several
+// sizes.  Last the size arithmetic of a streamed run (stream_n_max, stream_ring_bytes) along the pipeline's own piece
+// schedule: chunks of frames, through the resampler's completion rule, through the look-ahead.  Lines:
 //   walk <B> <n_max> <L> <knots> A <alone bytes> <behind the resampler bytes>     every check held
 //   walk <B> <n_max> <L> <knots> V <what>                                         a check failed
 //   table <rows> <knots> <first knot of every row ...>
 //   emit <L> <piece> <total> <first n ...>                                        the delivered range of every piece
+//   sched <hop> <chunk> <F> <out rate, 0: none> <L> <total> <n_max> <ring bytes: fp32 (L = 0; else 0), 1, 2, 4 bytes wide>
+//         <first n ...>                                 B = kSchedB rows at 22050 Hz: what every chunk delivers, n = 0 included
 // The extents below are what the kernels need of each buffer, written here independently of the walk.
 #include <algorithm>
 #include <cstdio>
@@ -57,9 +61,9 @@ size_t round16(size_t v) { return (v + 15) / 16 * 16; }
 
 // the chunk of n_max + L samples (F32) in whole cells per row, the peaks, the format table; a 32-byte record per row, a
 // 16-byte knot each, two carries of 2 L floats per row
-void shaped_extents(std::vector<Ext> &e, Carver &cv, int B, size_t n_max, int L, size_t knots) {
-    const StreamPackBufs s = carve_stream_pack(cv, B, (int64_t)(n_max + L));
-    const StreamShapeBufs ss = carve_stream_shape(cv, B, L, (int64_t)knots);
+void shaped_extents(std::vector<Ext> &e, const Carver &cv, const StreamBufs &sb, int B, size_t n_max, int L, size_t knots) {
+    const StreamPackBufs &s = sb.sp;
+    const StreamShapeBufs &ss = sb.ss;
     e.push_back({"chunk", s.buf, (size_t)B * round16(4 * (n_max + L))});
     e.push_back({"peak_run", s.peak_run, round16((size_t)B * 4)});
     e.push_back({"fmt", s.fmt, (size_t)B * 2 * 4});
@@ -74,19 +78,51 @@ void shaped_extents(std::vector<Ext> &e, Carver &cv, int B, size_t n_max, int L,
 
 std::vector<Ext> alone(Carver &cv, int B, size_t n_max, int L, size_t knots) {
     std::vector<Ext> e;
-    shaped_extents(e, cv, B, n_max, L, knots);
+    const StreamBufs sb = carve_stream(cv, B, (int64_t)(n_max + L), (int64_t)(n_max + L), /*K=*/0, /*enc=*/true, /*shaped=*/true, L, (int64_t)knots);
+    shaped_extents(e, cv, sb, B, n_max, L, knots);
     return e;
 }
 
 std::vector<Ext> resampled(Carver &cv, int B, size_t S, int K, size_t n_max, int L, size_t knots) {
-    const ResampleBufs r = carve_resample(cv, B, (int)S, K);
+    const StreamBufs sb = carve_stream(cv, B, (int64_t)S, (int64_t)(n_max + L), K, /*enc=*/true, /*shaped=*/true, L, (int64_t)knots);
+    const ResampleBufs &r = sb.rs;
     std::vector<Ext> e = {{"out", r.out, (size_t)B * S * 4}, {"n_in", r.n_in, (size_t)B * 4}, {"n_out", r.n_out, (size_t)B * 4},
                           {"carry0 (resampler)", r.carry[0], (size_t)B * K * 4}, {"carry1 (resampler)", r.carry[1], (size_t)B * K * 4},
                           {"pcm", r.pcm.pcm, (size_t)B * S * 2}, {"pcm peak", r.pcm.peak, (size_t)B * 4},
                           {"packed", r.dlv.packed, round16((size_t)B * S * 4)}, {"segs", r.dlv.segs, (size_t)B * 32},
                           {"peak", r.dlv.peak, (size_t)B * 2 * 4}};
-    shaped_extents(e, cv, B, n_max, L, knots);
+    shaped_extents(e, cv, sb, B, n_max, L, knots);
     return e;
+}
+
+constexpr int kSchedB = 3;
+
+// one streamed run of F frames in chunks of `chunk`, as render_chunks walks it: every chunk's input samples through
+// resample_emit_end (an output rate) and stream_emit_range (the look-ahead; an empty completion is not handed on)
+void schedule(int hop, int chunk, int F, int fo, int L) {
+    ResamplePlan rp;
+    if (fo && !resample_plan(22050, fo, rp).empty()) {
+        printf("sched %d %d %d %d %d bad plan\n", hop, chunk, F, fo, L);
+        return;
+    }
+    const int64_t total = rp.on() ? rp.count((int64_t)F * hop) : (int64_t)F * hop, n_max = stream_n_max(rp, chunk, F, hop, L, total);
+    printf("sched %d %d %d %d %d %lld %lld %zu %zu %zu %zu", hop, chunk, F, fo, L, (long long)total, (long long)n_max,
+           L ? (size_t)0 : stream_ring_bytes(kSchedB, n_max, 0), stream_ring_bytes(kSchedB, n_max, 1), stream_ring_bytes(kSchedB, n_max, 2),
+           stream_ring_bytes(kSchedB, n_max, 4));
+    int64_t emitted = 0;
+    for (int f0 = 0; f0 < F; f0 += chunk) {
+        const int f1 = f0 + chunk < F ? f0 + chunk : F;
+        int64_t first = (int64_t)f0 * hop, n = (int64_t)(f1 - f0) * hop;
+        if (rp.on()) {
+            const int64_t hi = resample_emit_end(rp, first + n, f1 == F, total);
+            first = emitted;
+            n = hi > emitted ? hi - emitted : 0;
+            emitted += n;
+        }
+        if (n > 0) stream_emit_range(first, n, first + n >= total, total, L, first, n);
+        printf(" %lld %lld", (long long)first, (long long)n);
+    }
+    printf("\n");
 }
 
 }  // namespace
@@ -138,5 +174,10 @@ int main() {
                 }
                 printf("\n");
             }
+    for (int hop : {1, 64, 256})
+        for (int chunk : {1, 2, 7, 64})
+            for (int F : {1, 5, 64, 65})
+                for (int fo : {0, 8000, 16000, 44100, 48000})
+                    for (int L : {0, 1, 64, 1024}) schedule(hop, chunk, F, fo, L);
     return 0;
 }

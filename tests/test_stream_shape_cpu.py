@@ -1,7 +1,7 @@
 """Shaped streaming (include/vitsmi.h, "shaped streaming") without a GPU: the NumPy reference against the limited delivery's,
 the timeline, every refusal (Python's checks, the engine's own through the C ABI, no callback made), the exported symbols, the
-workspace walk and the plan's host code in a stand-alone driver (plain and under the sanitizers), the NumPy fallback, and the
-voice layer on stand-in sessions.
+workspace walk, the plan's host code and the sizes of a streamed run along its schedule in a stand-alone driver (plain and under
+the sanitizers), the NumPy fallback, and the voice layer on stand-in sessions.
 
 Reference: tests/stream_shape_ref.py over limit_ref / shape_ref / delivery_ref.  Everything is compared exactly."""
 import ctypes as C
@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import limit_ref as lref
+import resample_ref as rref
 import shape_ref as sref
 import stream_pack_ref as pref
 import stream_shape_ref as ref
@@ -299,6 +300,59 @@ def test_the_driver_states_the_timeline(driver):
         L, piece, total = int(L), int(piece), int(total)
         got = list(zip(map(int, vals[0::2]), map(int, vals[1::2])))
         assert got == ref.timeline(pref.pieces(total, piece), total, L), (L, piece, total)
+
+
+def _completed(P, fi, fo, total):
+    """output samples whose K inputs all lie in front of input position P, by the definition: sample j reads the inputs up to
+    floor(j * M / L) + K / 2"""
+    L, M, K = rref.plan(fi, fo)[:3]
+    last_input = np.arange(total, dtype=np.int64) * M // L + K // 2
+    return int(np.searchsorted(last_input, P - 1, side="right"))
+
+
+def test_the_sizes_of_a_streamed_run_hold_along_its_schedule(driver):
+    """stream_n_max / stream_ring_bytes (workspace.hpp) against the schedule restated here: chunks of frames are pieces of input
+    samples, an output rate completes what the definition says, a look-ahead delivers the timeline of what was completed.
+    Every delivered range is what this says, none exceeds n_max, and a chunk of n_max samples fits a ring slot."""
+    B, FI = 3, 22050
+    scheds = [ln.split() for ln in driver if ln.startswith("sched ")]
+    assert len(scheds) == 3 * 4 * 4 * 5 * 4 and all("bad" not in s for s in scheds)
+    seen, empty_completions = set(), 0
+    for _, hop, chunk, F, fo, L, total, n_max, ring_f, ring1, ring2, ring4, *vals in scheds:
+        hop, chunk, F, fo, L, total, n_max = (int(v) for v in (hop, chunk, F, fo, L, total, n_max))
+        seen.add((hop, chunk, F, fo, L))
+        got = list(zip(map(int, vals[0::2]), map(int, vals[1::2])))
+        rendered = pref.pieces(F * hop, chunk * hop)
+        assert len(got) == len(rendered) == -(-F // chunk)
+        if fo:
+            assert total == int(rref.count(F * hop, FI, fo))
+            done, completed = 0, []
+            for f, n in rendered:
+                upto = total if f + n == F * hop else _completed(f + n, FI, fo, total)
+                completed.append((done, upto - done))
+                done = upto
+            empty_completions += sum(1 for _, n in completed if n == 0)
+        else:
+            assert total == F * hop
+            completed = rendered
+        live = [p for p in completed if p[1]]
+        want = iter(ref.timeline(live, total, L))
+        assert got == [next(want) if n else (f, 0) for f, n in completed], (hop, chunk, F, fo, L)
+        # what is delivered tiles [0, total), piece by piece
+        pos = 0
+        for first, n in got:
+            assert n == 0 or first == pos, (hop, chunk, F, fo, L)
+            assert 0 <= n <= n_max, (hop, chunk, F, fo, L, n, n_max)
+            pos += n
+        assert pos == total and n_max <= total
+        # a slot of the ring holds the largest chunk with the rows' peaks behind it; a float sink's (no look-ahead) its rows
+        for w, ring in ((1, ring1), (2, ring2), (4, ring4)):
+            assert B * (-(-w * n_max // 16) * 16) + 4 * B <= int(ring), (hop, chunk, F, fo, L, w)
+        if L == 0:
+            assert B * 4 * max(n for _, n in got) <= int(ring_f)
+    assert len(seen) == len(scheds)
+    # (hop 1 and hop 64 in chunks of one frame are shorter than every filter's half length: the grid holds such chunks)
+    assert empty_completions > 0
 
 
 def test_the_driver_runs_clean_under_the_sanitizers(tmp_path, driver):
