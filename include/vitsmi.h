@@ -758,7 +758,8 @@ int vits_run_vocoder_chunked_enc(vits_handle *h, const float *z, int B, int F, c
  * The encoded stream above is what a serving process uses when latency matters, and it lacked what the batch delivery has
  * since "shaped delivery" and "limited delivery": a streamed sentence met the silence of its pause with a step, could not
  * take a per-token volume, and clipped where the delivery ducks.  The two entries below are the two _enc entries with a
- * shaping.  Trimming and levelling stay out: a stream cannot know its onset threshold or its integrated loudness in advance.
+ * shaping.  Levelling stays out: a stream cannot know its integrated loudness in advance.  So does a trim against the row's own
+ * peak; the leading trim against an absolute threshold, or one relative to ref_peak[b], is "trimmed streaming" below.
  *
  * The rule.  One sample of row b follows the rule of the limited delivery for a segment that keeps the whole row: the kept
  * range is [0, n_b) (a stream does know where it ends: the frame counts are on the host before the first chunk is rendered);
@@ -797,7 +798,7 @@ int vits_run_vocoder_chunked_enc(vits_handle *h, const float *z, int B, int F, c
  * value: everything the shape check refuses (rows in the place of segments); a lookahead outside [0, 1024]; a ceiling that
  * is not finite or lies outside {0} and (0, 1]; a |volume[b]| above 1024 on a limited row; everything the _enc entries
  * refuse.  vits_reserve covers the stream's buffers for L = 1024 and two breakpoints per token.
- * Not covered: trimming and loudness in a stream; a look-ahead that differs per row; crossfades between sentences; a
+ * Not covered: trailing trim and loudness in a stream; a look-ahead that differs per row; crossfades between sentences; a
  * true-peak ceiling.  PipelinedSession / ShardedSynthesizer take the host fallback (audio_encoding: the same chunks). */
 struct vits_stream_shaping;
 typedef int (*vits_stream_plan_fn)(void *user, int B, int T, const int64_t *durations, const int64_t *sample_counts,
@@ -823,6 +824,75 @@ int vits_run_chunked_enc_shaped(vits_handle *h, const int64_t *ids, const int64_
 int vits_run_vocoder_chunked_enc_shaped(vits_handle *h, const float *z, int B, int F, const int64_t *sid,
                                         const vits_stream_format *fmt, const vits_stream_shaping *shaping, int chunk_frames,
                                         vits_enc_chunk_fn fn, void *user);
+
+/* ---- trimmed streaming: the leading silence of a streamed row cut off on the device ----------------------------------------
+ * A VITS voice renders near-silence in front of every sentence.  The delivery cuts it off ("trimmed delivery"); a caller of
+ * the shaped stream who cuts it off on the host plays a fade-in that started inside what was cut away, and a limiter window
+ * that saw it.  The two entries below are the two _shaped entries with one vits_stream_onset per row: the LEADING half of the
+ * trim.  The trailing half stays out: a stream learns where its audio ends only at the end, and holding back an unbounded
+ * run of quiet samples is a different design - a row keeps everything from its start to n_b.
+ *
+ * The rule.  onsets: one per row, or NULL - no row is trimmed.  mode 0: the row is not trimmed.  mode 1: thr = threshold.
+ * mode 2: thr = threshold * ref_peak[b], one fp32 product - it needs fmt->ref_peak, and is the trimmed delivery's mode 2 with
+ * peak_all := ref_peak[b].  (A threshold relative to the row's own peak is what a stream cannot know; these two it can.)
+ * A valid sample i < n_b is ACTIVE iff fabsf(x[b][i]) > thr: strict, as in the trimmed delivery, and on the raw sample, before
+ * any gain.  f_b is the first active index of the row.  Positions are samples at the delivered rate: the scan sees what the
+ * pack stage sees, behind the resampler.
+ * Let piece k be the rendered piece in which f_b lies and D_k the first sample that piece delivers - e_first of
+ * vits_stream_emit_range for it, whether or not the piece completes anything.  The kept range of row b is [a_b, n_b) with
+ *     a_b = max(f_b - keep_lead, D_k)
+ * i.e. a stream keeps as much of keep_lead as it has not yet handed over.  f_b >= first_k >= D_k >= 0, so 0 <= a_b <= f_b.
+ *   - a_b = max(0, f_b - keep_lead), the delivery's a, whenever f_b lies in the first piece: D_0 = 0.
+ *   - the same whenever keep_lead <= lookahead, whatever chunk_frames is: D_k = max(first_k - L, 0) <= max(f_b - L, 0)
+ *     <= max(f_b - keep_lead, 0).
+ * A trimmed row with no active sample keeps nothing: the delivery's c = 0.
+ * One sample of row b follows the limited delivery's rule for a segment with kept range [a_b, n_b): the fades count
+ * j = i - a_b against c = n_b - a_b; breakpoints stay row positions; q = 65536 outside the kept range ("a segment never sees
+ * ... the rest of its row"); everything in front of a_b is the encoding of 0.
+ * What does not change: the timeline, first_sample, n_samples, valid[b], total_samples.  A chunk stays rectangular.
+ * The callback gains skip[b]: the number of leading elements of row b in THIS chunk that lie in front of a_b,
+ * skip[b] = clamp(a_b - first_sample, 0, valid[b]) - valid[b] while the onset is unknown.  The caller sends
+ * row[skip[b] .. valid[b]).  Joined over the chunks those elements are the bytes vits_deliver_limited gives for that row under
+ * the trim {mode 1, thr, keep_lead = f_b - a_b, keep_tail >= n_b} - bit for bit, in all four encodings.  That equality is the
+ * specification; tests/stream_trim_ref.py composes it in NumPy.  The skips of a row sum to a_b, or to n_b for a row with no
+ * onset.
+ * peak[b] stays the running peak over ALL valid rendered samples, dropped ones included.  After the last chunk it is still
+ * the peak normalize 1 would use over the kept range: every dropped sample is at or below thr, and the kept range holds a
+ * sample above it.
+ * onsets == NULL or every mode 0: exactly the launches and bytes of the _shaped entries, with skip all 0.  The plan callback
+ * of the shaping cannot change onsets.
+ * Device side (csrc/stream_trim.hip.hpp): stream_onset_kernel, one launch per rendered piece in front of the pack launch, one
+ * workgroup per row - an integer minimum, no atomics, so two runs agree - writes a_b once into start [B] (int32, INT32_MAX:
+ * unknown).  The pack kernels read it; a stream with onsets but neither fades, points nor limiter takes the shaped kernel.
+ * start travels to the host with the running peaks behind each chunk's bytes, in the same copy; once the host has read that
+ * every trimmed row's start is known or the row has ended, the scan is not launched again.
+ * Validation on the host before anything is enqueued (the previous run stays readable); VITS_E_ARG naming the row and the
+ * value: a mode outside 0..2; a threshold that is not finite or is negative; a negative keep_lead; reserved != 0; mode 2
+ * without ref_peak; everything the _shaped entries refuse.  vits_reserve covers the starts and the scan's records.
+ * Not covered: the trailing trim and tail_samples; onsets that differ in anything but the three fields; a compacted chunk. */
+typedef struct vits_stream_onset {
+    int32_t mode;                    /* 0 off, 1 absolute threshold, 2 threshold relative to ref_peak[b] */
+    float threshold;
+    int32_t keep_lead;               /* samples at the delivered rate kept in front of the onset, where not yet delivered */
+    int32_t reserved;                /* must be 0 */
+} vits_stream_onset;                 /* 16 bytes */
+/* vits_enc_chunk_fn with skip [B] behind valid */
+typedef int (*vits_enc_chunk_trim_fn)(void *user, const void *bytes, int B, int64_t row_pitch_bytes, int64_t first_sample,
+                                      int64_t n_samples, const int32_t *valid, const int32_t *skip, const float *peak,
+                                      int64_t total_samples);
+/* pure host code: the validation above of onsets (nullable: nothing to refuse) over B rows; fmt (nullable) says whether
+ * there is a ref_peak */
+int vits_stream_onset_check(const vits_stream_onset *onsets, const vits_stream_format *fmt, int B);
+/* pure host code: the rule above - a = max(f - keep_lead, delivered_before) for an onset at f in a piece that delivers from
+ * delivered_before <= f on */
+int vits_stream_onset_start(int64_t f, int64_t keep_lead, int64_t delivered_before, int64_t *a);
+int vits_run_chunked_enc_trimmed(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
+                                 const vits_noise *noise, const vits_controls *ctl, const vits_stream_format *fmt,
+                                 const vits_stream_shaping *shaping, const vits_stream_onset *onsets, int chunk_frames,
+                                 vits_enc_chunk_trim_fn fn, void *user);
+int vits_run_vocoder_chunked_enc_trimmed(vits_handle *h, const float *z, int B, int F, const int64_t *sid,
+                                         const vits_stream_format *fmt, const vits_stream_shaping *shaping,
+                                         const vits_stream_onset *onsets, int chunk_frames, vits_enc_chunk_trim_fn fn, void *user);
 
 /* Size the handle's device workspaces NOW for requests of up to B utterances x T tokens that render up to F frames each
  * (the batch's longest utterance; T = 0 or F = 0 leaves that domain alone).  A run grows a workspace when a request
@@ -1054,6 +1124,14 @@ int vits_test_stream_pack(int device_id, const float *x, const int64_t *counts, 
 int vits_test_stream_pack_shaped(int device_id, const float *x, const int64_t *counts, int B, int S, int piece_samples,
                                  const vits_stream_format *fmt, const vits_stream_shaping *shaping, void *bytes, size_t bytes_cap,
                                  int64_t *pitches, int32_t *valid, float *peaks, int64_t *firsts, int64_t *ns, int max_pieces);
+
+/* vits_test_stream_pack_shaped with onsets (nullable): every piece goes through the scan and the pipeline's kernels.
+ * skip [piece][B] as valid; start [B] receives the rows' final a_b (INT32_MAX where a trimmed row has no onset, 0 for a row
+ * that is not trimmed).  Returns the number of pieces. */
+int vits_test_stream_pack_trimmed(int device_id, const float *x, const int64_t *counts, int B, int S, int piece_samples,
+                                  const vits_stream_format *fmt, const vits_stream_shaping *shaping, const vits_stream_onset *onsets,
+                                  void *bytes, size_t bytes_cap, int64_t *pitches, int32_t *valid, int32_t *skip, float *peaks,
+                                  int64_t *firsts, int64_t *ns, int32_t *start, int max_pieces);
 
 #ifdef __cplusplus
 }

@@ -93,6 +93,10 @@ VitsStreamShaping._fields_ = [("shapes", C.c_void_p), ("points", C.c_void_p), ("
                               ("lookahead", C.c_int32), ("reserved", C.c_int32), ("plan", STREAM_PLAN_FN), ("plan_user", C.c_void_p)]
 
 
+class VitsStreamOnset(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("threshold", C.c_float), ("keep_lead", C.c_int32), ("reserved", C.c_int32)]
+
+
 # name -> (VITS_ENC_* code, element type): audio_encoding lists the names in the order of the header's enum
 ENCODINGS = {name: (code, audio_encoding.DTYPES[name]) for code, name in enumerate(audio_encoding.ENCODINGS)}
 
@@ -104,6 +108,10 @@ CHUNK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_i
 #        const int32 *valid, const float *peak, int64 total_samples)
 ENC_CHUNK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int32),
                            C.POINTER(C.c_float), C.c_int64)
+
+# ENC_CHUNK_FN with `const int32 *skip` behind valid
+ENC_CHUNK_TRIM_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int32),
+                                C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int64)
 
 VITS_E_RANGE = -6
 
@@ -131,6 +139,8 @@ EXPORTS = [
     "vits_run_chunked_enc", "vits_run_vocoder_chunked_enc", "vits_test_stream_pack",
     "vits_stream_shaping_check", "vits_stream_emit_range", "vits_run_chunked_enc_shaped", "vits_run_vocoder_chunked_enc_shaped",
     "vits_test_stream_pack_shaped",
+    "vits_stream_onset_check", "vits_stream_onset_start", "vits_run_chunked_enc_trimmed", "vits_run_vocoder_chunked_enc_trimmed",
+    "vits_test_stream_pack_trimmed",
     "vits_test_layernorm", "vits_test_dds", "vits_test_cf_pre", "vits_test_rqs_inverse", "vits_test_ea_logw",
 ]
 
@@ -208,6 +218,17 @@ def load():
                                                         C.POINTER(VitsStreamShaping), C.c_int, ENC_CHUNK_FN, vp]
     lib.vits_test_stream_pack_shaped.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(VitsStreamFormat),
                                                  C.POINTER(VitsStreamShaping), vp, C.c_size_t, vp, vp, vp, vp, vp, C.c_int]
+    lib.vits_stream_onset_check.argtypes = [C.POINTER(VitsStreamOnset), C.POINTER(VitsStreamFormat), C.c_int]
+    lib.vits_stream_onset_start.argtypes = [C.c_int64, C.c_int64, C.c_int64, i64p]
+    lib.vits_run_chunked_enc_trimmed.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.POINTER(VitsNoise), C.POINTER(VitsControls),
+                                                 C.POINTER(VitsStreamFormat), C.POINTER(VitsStreamShaping), C.POINTER(VitsStreamOnset),
+                                                 C.c_int, ENC_CHUNK_TRIM_FN, vp]
+    lib.vits_run_vocoder_chunked_enc_trimmed.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.POINTER(VitsStreamFormat),
+                                                         C.POINTER(VitsStreamShaping), C.POINTER(VitsStreamOnset), C.c_int,
+                                                         ENC_CHUNK_TRIM_FN, vp]
+    lib.vits_test_stream_pack_trimmed.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(VitsStreamFormat),
+                                                  C.POINTER(VitsStreamShaping), C.POINTER(VitsStreamOnset), vp, C.c_size_t, vp, vp, vp, vp,
+                                                  vp, vp, vp, C.c_int]
     lib.vits_test_stream_pack.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(VitsStreamFormat), vp, C.c_size_t,
                                           vp, vp, vp, C.c_int]
     lib.vits_last_durations.argtypes = [vp, i64p, C.c_size_t]

@@ -288,14 +288,47 @@ def emit_range(first, n, is_last, total, lookahead):
     return e_first, max(end - e_first, 0)
 
 
-def stream_shaped(chunks, counts, encoding="pcm16", ref_peak=None, volume=None, shapes=None, limits=None):
+def _row_onsets(onsets, n):
+    """None, one onset or one per row (None in the list: off) -> a list of n"""
+    if onsets is None:
+        return [None] * n
+    if hasattr(onsets, "keep_lead"):
+        return [onsets] * n
+    onsets = list(onsets)
+    if len(onsets) != n:
+        raise ValueError(f"onsets must be one onset or one per row ({n}), got {len(onsets)}")
+    return onsets
+
+
+def onset_threshold(onset, ref_peak):
+    """thr of a trimmed row (include/vitsmi.h, "trimmed streaming"): mode 1 - the threshold; mode 2 - one float32 product with
+    the row's ref_peak."""
+    mode, thr = int(onset.mode), np.float32(onset.threshold)
+    if mode not in (0, 1, 2):
+        raise ValueError(f"onset mode {mode} outside 0..2")
+    if not np.isfinite(thr) or thr < 0 or int(onset.keep_lead) < 0:
+        raise ValueError(f"onset threshold {float(thr)} / keep_lead {int(onset.keep_lead)}: finite and >= 0")
+    if mode == 2:
+        if ref_peak is None:
+            raise ValueError("onset mode 2 needs ref_peak")
+        return np.float32(thr * np.float32(ref_peak))
+    return thr
+
+
+NO_START = 2 ** 31 - 1      # start of a trimmed row whose onset has not been found
+
+
+def stream_shaped(chunks, counts, encoding="pcm16", ref_peak=None, volume=None, shapes=None, limits=None, onsets=None):
     """The shaped, limited encoded stream on the host: `chunks` yields (first_sample, float32 [B, n], total_samples) - an fp32
     stream, MiSession.synthesize_stream's -, counts (int [B], or a callable asked once, at the first chunk) are the rows'
     valid samples.  ref_peak / volume: None or one per row; shapes: None, one shape or one per row, over the whole row (a
     fade-out ends at the row's own end) - or a callable of the counts that gives them, asked with them; limits: None, one limit or one per row (None: that row is not limited), with ONE
     lookahead L.  Yields (first_sample, data [B, n] in the encoding's dtype, valid int32 [B], peak float32 [B],
     total_samples) - the chunks, timeline included, of the engine's shaped stream: a piece is delivered L samples late, the
-    last one L longer, one that completes nothing not at all; `peak` is the running max |x| over what has been rendered."""
+    last one L longer, one that completes nothing not at all; `peak` is the running max |x| over what has been rendered.
+    onsets (None, one onset - anything with mode, threshold, keep_lead - or one per row, None for a row that is not trimmed):
+    the leading trim of "trimmed streaming" on the same timeline - a row is kept from a_b = max(f_b - keep_lead, D_k) on, its
+    fades count from there, everything in front is silence; the items then carry a sixth element, skip int32 [B]."""
     _check(encoding)
     state = None
     for first, x, total in chunks:
@@ -313,6 +346,9 @@ def stream_shaped(chunks, counts, encoding="pcm16", ref_peak=None, volume=None, 
             pk = [None] * B if ref_peak is None else list(np.broadcast_to(np.asarray(ref_peak, np.float32), (B,)))
             vol = np.broadcast_to(np.asarray(1.0 if volume is None else volume, np.float32), (B,))
             state = np.zeros((B, 2 * L), np.float32), np.zeros(B, np.float32)     # the carry, the running peaks
+            ons = _row_onsets(onsets, B)
+            thr = [None if o is None or int(o.mode) == 0 else onset_threshold(o, pk[b]) for b, o in enumerate(ons)]
+            start = [0 if t is None else NO_START for t in thr]
         carry, peak = state
         joined = np.concatenate([carry, x], axis=1)                  # samples [first - 2 L, first + n) of the rows
         base = first - 2 * L
@@ -322,19 +358,32 @@ def stream_shaped(chunks, counts, encoding="pcm16", ref_peak=None, volume=None, 
                 peak[b] = max(peak[b], np.max(np.abs(seen)))
         state = joined[:, joined.shape[1] - 2 * L:], peak
         ef, en = emit_range(first, n, first + n >= total, total, L)
+        for b in range(B):      # the scan: every rendered piece, whether or not it completes anything
+            if start[b] != NO_START:
+                continue
+            hit = np.flatnonzero(np.abs(x[b, :int(np.clip(cnt[b] - first, 0, n))]) > thr[b])
+            if hit.size:
+                start[b] = max(first + int(hit[0]) - int(ons[b].keep_lead), ef)
+                if shp[b] is not None:
+                    muls[b] = shape_multiplier(start[b], cnt[b] - start[b], shp[b])
         if en == 0:
             continue
         data = np.full((B, en), SILENCE[encoding], DTYPES[encoding])
         valid = np.clip(cnt - ef, 0, en).astype(np.int32)
+        skip = np.clip(np.asarray(start, np.int64) - ef, 0, valid).astype(np.int32)
         for b in range(B):
-            if not valid[b]:
+            if skip[b] >= valid[b]:
                 continue
-            # g of [ef, ef + valid) needs q of L samples on either side: u over [lo, hi), inside the row
-            lo, hi = max(ef - L, 0), int(min(ef + en + L, cnt[b]))
-            u = unlimited(joined[b, lo - base:hi - base], pk[b], vol[b], None if muls[b] is None else muls[b][lo:hi])
-            v = limited(u, lim[b])[ef - lo:ef - lo + int(valid[b])]
-            data[b, :int(valid[b])] = encode(np.clip(v, np.float32(-1.0), np.float32(1.0)).astype(np.float32), encoding)
-        yield ef, data, valid, peak.copy(), total
+            # g of [ef, ef + valid) needs q of L samples on either side: u over [lo, hi), inside the kept range
+            a, d0 = start[b], ef + int(skip[b])
+            lo, hi = max(ef - L, a), int(min(ef + en + L, cnt[b]))
+            u = unlimited(joined[b, lo - base:hi - base], pk[b], vol[b], None if muls[b] is None else muls[b][lo - a:hi - a])
+            v = limited(u, lim[b])[d0 - lo:ef - lo + int(valid[b])]
+            data[b, int(skip[b]):int(valid[b])] = encode(np.clip(v, np.float32(-1.0), np.float32(1.0)).astype(np.float32), encoding)
+        if onsets is None:
+            yield ef, data, valid, peak.copy(), total
+        else:
+            yield ef, data, valid, peak.copy(), total, skip
 
 
 def k_weighting(rate):

@@ -1,16 +1,18 @@
 // stream_run.hip.hpp — the stages a piece of a chunked run goes through behind the generator: the resampler's piece entry with its
 // carry (include/vitsmi.h, "Output rate") and the encoded sink's pack, plain ("encoded streaming") or shaped and limited ("shaped
-// streaming", stream_shape.hip.hpp).  The pipeline (vitsmi.hip, render_chunks) and the hooks vits_test_resample_pieces /
+// streaming", stream_shape.hip.hpp), with the scan of a trimmed stream in front ("trimmed streaming", stream_trim.hip.hpp).  The pipeline (vitsmi.hip, render_chunks) and the hooks vits_test_resample_pieces /
 // vits_test_stream_pack / _shaped run THESE functions.  Nothing here knows a handle.  The buffers are carve_stream's (workspace.hpp);
 // errors come back as hipError_t, launch counts by reference.  All is enqueued on the caller's stream; the caller copies out and waits.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstring>
 #include <vector>
 
 #include "resample.hip.hpp"
 #include "stream_shape.hip.hpp"
+#include "stream_trim.hip.hpp"
 #include "workspace.hpp"
 
 namespace vitsmi {
@@ -74,29 +76,63 @@ struct StreamPackRun {
     int64_t total = 0;
     StreamShapeRun shape;
     std::vector<float> up;  // (pageable source of an asynchronous copy: lives until the pieces behind it have been waited for)
+    // a trimmed stream: the scan's records, and whether the next piece is still scanned - until the host has read back that
+    // every trimmed row's start is known or the row has ended (stream_pack_seen)
+    bool trimmed = false, scan = false;
+    std::vector<StreamOnsetRow> onsets;
+    std::vector<int64_t> row_n;  // the rows' valid samples, where the caller has them on the host (else: empty)
+    // bytes one copy takes behind a chunk's B * pitch: the running peaks - and a trimmed stream's starts behind them
+    size_t tail_bytes(int B) const { return trimmed ? (StreamPackBufs::peak_floats(B) + (size_t)B) * sizeof(float) : (size_t)B * sizeof(float); }
 };
 
 // The per-run upload [zeros of the running peaks | {ref_peak, volume} per row] in one copy and, with a `shaping` (nullptr: the
 // plain kernel), its records and knots.  fmt and shaping are validated; rows / total: the rows' valid samples and their length.
+// onsets (nullable, validated; every mode 0: as nullptr): a trimmed stream - it takes the shaped kernels whatever the shaping,
+// sp and ss are carved `trimmed`, and the upload is [peaks | starts: 0, or kStreamNoStart for a trimmed row | table].
+// row_n (nullable): the rows' valid samples on the host, for stream_pack_seen.
 inline hipError_t stream_pack_begin(StreamPackRun &r, const vits_stream_format *fmt, const vits_stream_shaping *shaping, int B,
                                     const StreamPackBufs &sp, const StreamShapeBufs &ss, const StreamPackRows &rows, int64_t total,
-                                    hipStream_t st) {
+                                    hipStream_t st, const vits_stream_onset *onsets = nullptr, const int64_t *row_n = nullptr) {
+    static const vits_stream_shaping none{};
     r.encoding = fmt->encoding;
     r.width = delivery_width(fmt->encoding);
     r.norm = fmt->ref_peak != nullptr;
-    r.shaped = shaping != nullptr;
+    r.trimmed = r.scan = stream_trimmed(onsets, B);
+    r.shaped = shaping != nullptr || r.trimmed;
     r.sp = sp;
     r.rows = rows;
     r.total = total;
-    const size_t Bp = StreamPackBufs::peak_floats(B);
-    r.up.assign(Bp + 2 * (size_t)B, 0.f);
+    r.row_n.clear();
+    if (row_n) r.row_n.assign(row_n, row_n + B);
+    const size_t Bp = StreamPackBufs::peak_floats(B), Bs = r.trimmed ? Bp : 0;
+    r.up.assign(Bp + Bs + 2 * (size_t)B, 0.f);
+    if (r.trimmed) {
+        stream_onset_table(onsets, fmt->ref_peak, B, r.onsets);
+        for (int b = 0; b < B; b++) {
+            const int32_t s0 = r.onsets[b].on ? kStreamNoStart : 0;
+            std::memcpy(&r.up[Bp + b], &s0, sizeof s0);
+        }
+    }
     for (int b = 0; b < B; b++) {
-        r.up[Bp + 2 * b] = fmt->ref_peak ? fmt->ref_peak[b] : 1.0f;
-        r.up[Bp + 2 * b + 1] = fmt->volume ? fmt->volume[b] : 1.0f;
+        r.up[Bp + Bs + 2 * b] = fmt->ref_peak ? fmt->ref_peak[b] : 1.0f;
+        r.up[Bp + Bs + 2 * b + 1] = fmt->volume ? fmt->volume[b] : 1.0f;
     }
     hipError_t e = hipMemcpyAsync(sp.peak_run, r.up.data(), r.up.size() * sizeof(float), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && r.shaped) e = stream_shape_begin(r.shape, shaping, B, ss, st);
+    if (e == hipSuccess && r.trimmed)
+        e = hipMemcpyAsync(ss.onsets, r.onsets.data(), r.onsets.size() * sizeof(StreamOnsetRow), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && r.shaped) e = stream_shape_begin(r.shape, shaping ? shaping : &none, B, ss, st);
     return e;
+}
+
+// What the host has read back behind a chunk that delivered through `delivered_end`: start [B].  Once every trimmed row's start
+// is known, or the row has ended in front of delivered_end (what is delivered has been scanned), no later piece is scanned.
+inline void stream_pack_seen(StreamPackRun &r, const int32_t *start, int64_t delivered_end, int B) {
+    if (!r.scan) return;
+    for (int b = 0; b < B; b++) {
+        const int64_t nb = r.row_n.empty() ? r.total : r.row_n[b];
+        if (r.onsets[b].on && start[b] == kStreamNoStart && nb > delivered_end) return;
+    }
+    r.scan = false;
 }
 
 // The piece x [B][n] at `first`: what it delivers - itself or, shaped with a look-ahead, the range that far behind it - as [B][pitch]
@@ -105,9 +141,17 @@ inline hipError_t stream_pack_piece(StreamPackRun &r, const float *x, int64_t x_
                                     unsigned char *&d, int64_t &e_first, int64_t &e_n, size_t &pitch, int &launches) {
     pitch = StreamPackBufs::pitch(r.width, n);
     if (r.shaped) {
+        if (r.scan) {  // in front of the pack launch; D: what stream_shape_chunk is about to compute
+            int64_t D = 0, dn = 0;
+            stream_emit_range(first, n, first + n >= r.total, r.total, r.shape.L, D, dn);
+            const hipError_t es = launch_stream_onset(x, x_pitch, r.rows, B, (int)first, (int)n, (int)D, r.shape.ss.onsets, r.sp.start, st);
+            if (es != hipSuccess) return es;
+        }
+        const bool scanned = r.scan;
         const hipError_t e = stream_shape_chunk(r.shape, r.encoding, r.width, x, x_pitch, r.rows, B, first, n, r.total, r.sp, r.norm, st, e_first,
                                                 e_n, d, launches);
         pitch = StreamPackBufs::pitch(r.width, e_n);
+        launches += scanned ? 1 : 0;
         return e;
     }
     e_first = first;

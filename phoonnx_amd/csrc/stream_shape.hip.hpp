@@ -27,6 +27,11 @@
 // Every loop that holds a barrier runs a trip count that depends on the tile and L alone.  LDS is static: limit_gain_kernel's
 // two buffers (32 KiB), u of a tile (8 KiB), the encoded tile (8 KiB).
 //
+// A trimmed stream (include/vitsmi.h, "trimmed streaming"; the scan: stream_trim.hip.hpp) runs the TRIM instantiations of both
+// kernels: the kept range is [start[b], n_b) instead of [0, n_b) - the fades count from start[b], the knots stay row
+// positions, what lies in front is outside the limiter's windows and is delivered as silence.  The instantiations without
+// TRIM are the kernels as they were, and are what every stream without onsets launches.
+//
 // stream_carry_kernel writes the other generation of the carry behind a piece: the last K = 2 L samples of
 // "old carry | piece", right also where the piece is shorter than the carry (resample_carry_kernel's form).
 #pragma once
@@ -44,16 +49,18 @@ namespace vitsmi {
 
 constexpr int kStreamTile = kLimitTile;  // delivered elements of a workgroup of the limited stream pack: the staged range is limit_gain_kernel's
 
-// u of sample j of a row of c samples whose raw value is v: limit_value's operations, with peak := ref (norm) and no level gain
+// u of row sample j whose raw value is v, kept sample jf of a kept range of c samples (an untrimmed row: jf = j, c = n_b; a
+// trimmed one: jf = j - a_b, c = n_b - a_b): limit_value's operations, with peak := ref (norm) and no level gain.  The knots
+// walk by row position, the fades count within the kept range.
 __device__ inline float stream_shape_value(float v, bool norm, float ref, float volume, const StreamShapeRow &r, const ShapeKnot *knots,
-                                           int32_t j, int32_t c, LimitKnotWalk &w) {
+                                           int32_t j, int32_t jf, int32_t c, LimitKnotWalk &w) {
     if (!w.located) {
         w.kp = shape_knot_locate(knots + r.first, r.n_points, j);
         w.kn = knots[r.first + w.kp];
         w.located = true;
     }
     while (j >= w.kn.next) w.kn = knots[r.first + ++w.kp];  // (the last knot's next is INT_MAX: kp stays <= n_points)
-    const float mul = shape_combine(shape_knot_env(w.kn, j), shape_w_in(j, r.fade_in, r.curve), shape_w_out(j, c, r.fade_out, r.curve));
+    const float mul = shape_combine(shape_knot_env(w.kn, j), shape_w_in(jf, r.fade_in, r.curve), shape_w_out(jf, c, r.fade_out, r.curve));
     if (norm) v = ref < 1e-8f ? 0.f : v / ref;
     if (volume != 1.0f) v = v * volume;
     return shape_mul(v, mul);
@@ -66,12 +73,15 @@ __device__ inline int stream_row_count(const StreamPackRows &rows, int b) {
     return nb < 0 ? 0 : (int)nb;
 }
 
-// stream_pack_kernel's arguments and the rows' records and knots
-template <int ENC>
+// stream_pack_kernel's arguments and the rows' records and knots.  TRIM (a trimmed stream, "trimmed streaming"): the kept range
+// of row b is [start[b], n_b) - kStreamNoStart while the onset is unknown: nothing of the row is kept yet - and every element
+// in front of it is silence; the running peak still folds every valid sample.  Without TRIM `start` is not read.
+template <int ENC, bool TRIM>
 __global__ __launch_bounds__(kDeliveryThreads) void stream_pack_shaped_kernel(const float *x, int64_t x_pitch, StreamPackRows rows, int first,
                                                                               int n, const float *fmt, int norm, uint4 *bytes,
                                                                               int cells_per_row, unsigned *peak_run,
-                                                                              const StreamShapeRow *srows, const ShapeKnot *knots) {
+                                                                              const StreamShapeRow *srows, const ShapeKnot *knots,
+                                                                              const int32_t *start) {
     using T = typename DeliveryElem<ENC>::type;
     constexpr int E = 16 / (int)sizeof(T);
     __shared__ uint4 tile[kDeliveryThreads];
@@ -83,6 +93,7 @@ __global__ __launch_bounds__(kDeliveryThreads) void stream_pack_shaped_kernel(co
     const float ref = fmt[2 * b], volume = fmt[2 * b + 1];
     const float *xr = x + (int64_t)b * x_pitch;
     const StreamShapeRow sr = srows[b];
+    const int ab = TRIM ? start[b] : 0;
     LimitKnotWalk walk;
     const T silence = delivery_encode<ENC>(delivery_value(0.0f, false, 1.0f, 1.0f));
     const int base = blockIdx.x * (kDeliveryThreads * E);
@@ -93,8 +104,10 @@ __global__ __launch_bounds__(kDeliveryThreads) void stream_pack_shaped_kernel(co
         if (e < valid) {
             const float v = xr[e];
             m = fmaxf(m, fabsf(v));
-            const float u = stream_shape_value(v, norm != 0, ref, volume, sr, knots, first + e, nb, walk);
-            o = delivery_encode<ENC>(fminf(fmaxf(u, -1.0f), 1.0f));
+            if (!TRIM || first + e >= ab) {
+                const float u = stream_shape_value(v, norm != 0, ref, volume, sr, knots, first + e, first + e - ab, nb - ab, walk);
+                o = delivery_encode<ENC>(fminf(fmaxf(u, -1.0f), 1.0f));
+            }
         }
         lt[i * kDeliveryThreads + threadIdx.x] = o;
     }
@@ -116,10 +129,13 @@ struct StreamLimitArgs {
     const float *carry;
 };
 
-template <int ENC>
+// TRIM: as in stream_pack_shaped_kernel - a staged sample in front of start[b] is outside the kept range (q = 65536, the
+// delivery's "a segment never sees the rest of its row") and a delivered one is silence
+template <int ENC, bool TRIM>
 __global__ __launch_bounds__(kDeliveryThreads) void stream_pack_limited_kernel(StreamLimitArgs a, StreamPackRows rows, const float *fmt, int norm,
                                                                                uint4 *bytes, int cells_per_row, unsigned *peak_run,
-                                                                               const StreamShapeRow *srows, const ShapeKnot *knots) {
+                                                                               const StreamShapeRow *srows, const ShapeKnot *knots,
+                                                                               const int32_t *start) {
     using T = typename DeliveryElem<ENC>::type;
     constexpr int E = 16 / (int)sizeof(T);
     constexpr int kCells = kStreamTile / E;  // 16-byte cells of a tile
@@ -136,6 +152,7 @@ __global__ __launch_bounds__(kDeliveryThreads) void stream_pack_limited_kernel(S
     const float *cr = a.carry + (int64_t)b * 2 * a.L;
     const StreamShapeRow sr = srows[b];
     const bool limited = sr.ceiling > 0.f;
+    const int ab = TRIM ? start[b] : 0;
     const int L = a.L;
     // the tile: delivered elements [d0, d0 + nt) of the row (everything here but `lane` is uniform over the workgroup)
     const int off = blockIdx.x * kStreamTile;
@@ -153,8 +170,10 @@ __global__ __launch_bounds__(kDeliveryThreads) void stream_pack_limited_kernel(S
         if (j >= 0 && j < nb && r >= -2 * L && r < a.n) {
             const float v = r < 0 ? cr[2 * L + r] : xr[r];
             if (j >= a.fold_from) m = fmaxf(m, fabsf(v));
-            u = stream_shape_value(v, norm != 0, ref, volume, sr, knots, j, nb, walk);
-            if (limited) q = limit_q(u, sr.ceiling);
+            if (!TRIM || j >= ab) {
+                u = stream_shape_value(v, norm != 0, ref, volume, sr, knots, j, j - ab, nb - ab, walk);
+                if (limited) q = limit_q(u, sr.ceiling);
+            }
         }
         buf[0][t] = q;
         if (t >= L && t < L + nt) us[t - L] = u;
@@ -168,7 +187,7 @@ __global__ __launch_bounds__(kDeliveryThreads) void stream_pack_limited_kernel(S
     const T silence = delivery_encode<ENC>(delivery_value(0.0f, false, 1.0f, 1.0f));
     for (int i = lane; i < kStreamTile; i += kDeliveryThreads) {
         T o = silence;
-        if (i < nt && d0 + i < nb) {
+        if (i < nt && d0 + i < nb && (!TRIM || d0 + i >= ab)) {
             float v = us[i];
             if (limited) v = limit_apply(v, pass ? limit_g(M[i + L + 1] - M[i], L) : 1.0f, sr.ceiling);
             o = delivery_encode<ENC>(fminf(fmaxf(v, -1.0f), 1.0f));
@@ -195,15 +214,19 @@ __global__ void stream_carry_kernel(const float *old, const float *x, int64_t x_
 // one chunk on `st`, L = 0: launch_stream_pack with the rows' records and knots
 inline hipError_t launch_stream_pack_shaped(int encoding, const float *x, int64_t x_pitch, const StreamPackRows &rows, int B, int first, int n,
                                             const float *fmt, bool norm, void *bytes, unsigned *peak_run, const StreamShapeRow *srows,
-                                            const ShapeKnot *knots, hipStream_t st) {
+                                            const ShapeKnot *knots, const int32_t *start, hipStream_t st) {
     const int width = delivery_width(encoding);
     const int cells = (int)(stream_pack_pitch(width, n) / 16);
     const dim3 grid((unsigned)((cells + kDeliveryThreads - 1) / kDeliveryThreads), (unsigned)B);
     uint4 *out = static_cast<uint4 *>(bytes);
     const int nm = norm ? 1 : 0;
     stream_for_encoding(encoding, [&](auto enc) {
-        stream_pack_shaped_kernel<decltype(enc)::value><<<grid, kDeliveryThreads, 0, st>>>(x, x_pitch, rows, first, n, fmt, nm, out, cells, peak_run,
-                                                                                           srows, knots);
+        if (start)
+            stream_pack_shaped_kernel<decltype(enc)::value, true><<<grid, kDeliveryThreads, 0, st>>>(x, x_pitch, rows, first, n, fmt, nm, out, cells,
+                                                                                                     peak_run, srows, knots, start);
+        else
+            stream_pack_shaped_kernel<decltype(enc)::value, false><<<grid, kDeliveryThreads, 0, st>>>(x, x_pitch, rows, first, n, fmt, nm, out, cells,
+                                                                                                      peak_run, srows, knots, nullptr);
     });
     return hipGetLastError();
 }
@@ -211,14 +234,19 @@ inline hipError_t launch_stream_pack_shaped(int encoding, const float *x, int64_
 // one chunk on `st`, L > 0: bytes [B][pitch] of the delivered range, pitch = stream_pack_pitch(width, a.en); a.en >= 1
 inline hipError_t launch_stream_pack_limited(int encoding, const StreamLimitArgs &a, const StreamPackRows &rows, int B, const float *fmt, bool norm,
                                              void *bytes, unsigned *peak_run, const StreamShapeRow *srows, const ShapeKnot *knots,
-                                             hipStream_t st) {
+                                             const int32_t *start, hipStream_t st) {
     const int width = delivery_width(encoding);
     const int cells = (int)(stream_pack_pitch(width, a.en) / 16);
     const dim3 grid((unsigned)((a.en + kStreamTile - 1) / kStreamTile), (unsigned)B);
     uint4 *out = static_cast<uint4 *>(bytes);
     const int nm = norm ? 1 : 0;
     stream_for_encoding(encoding, [&](auto enc) {
-        stream_pack_limited_kernel<decltype(enc)::value><<<grid, kDeliveryThreads, 0, st>>>(a, rows, fmt, nm, out, cells, peak_run, srows, knots);
+        if (start)
+            stream_pack_limited_kernel<decltype(enc)::value, true><<<grid, kDeliveryThreads, 0, st>>>(a, rows, fmt, nm, out, cells, peak_run, srows,
+                                                                                                      knots, start);
+        else
+            stream_pack_limited_kernel<decltype(enc)::value, false><<<grid, kDeliveryThreads, 0, st>>>(a, rows, fmt, nm, out, cells, peak_run, srows,
+                                                                                                       knots, nullptr);
     });
     return hipGetLastError();
 }
@@ -270,10 +298,10 @@ inline hipError_t stream_shape_chunk(StreamShapeRun &r, int encoding, int width,
         d = sp.at(B, StreamPackBufs::pitch(width, e_n));
         if (r.L == 0)
             e = launch_stream_pack_shaped(encoding, x, x_pitch, rows, B, (int)first, (int)n, sp.fmt, norm, d, sp.peak_run, r.ss.rows,
-                                          r.ss.knots, st);
+                                          r.ss.knots, sp.start, st);
         else {
             const StreamLimitArgs a{x, x_pitch, (int)first, (int)n, (int)e_first, (int)e_n, (int)r.fold_from, r.L, r.ss.carry[r.gen]};
-            e = launch_stream_pack_limited(encoding, a, rows, B, sp.fmt, norm, d, sp.peak_run, r.ss.rows, r.ss.knots, st);
+            e = launch_stream_pack_limited(encoding, a, rows, B, sp.fmt, norm, d, sp.peak_run, r.ss.rows, r.ss.knots, sp.start, st);
             r.fold_from = first + n;
         }
         launches++;

@@ -87,4 +87,58 @@ inline int64_t stream_knot_count(const vits_stream_shaping *s, int B) {
     return s && s->shapes ? shape_knot_count(s->shapes, B) : (int64_t)B;
 }
 
+// ---- the leading trim of a stream (include/vitsmi.h, "trimmed streaming"): the onsets' validation, the start rule, and what
+// the scan (stream_trim.hip.hpp) reads
+
+constexpr int32_t kStreamNoStart = INT32_MAX;  // start[b] of a trimmed row whose onset has not been found
+
+// one row as the scan reads it (16 bytes): thr is the resolved threshold - mode 2's one fp32 product is made on the host
+struct StreamOnsetRow {
+    int32_t on;  // 0: the row is not trimmed (its start is 0 from the beginning)
+    float thr;
+    int32_t keep_lead;
+    int32_t pad;
+};
+
+inline bool stream_trimmed(const vits_stream_onset *o, int B) {
+    for (int b = 0; o && b < B; b++)
+        if (o[b].mode != 0) return true;
+    return false;
+}
+
+// "" or what is wrong with the onsets of a call, naming the row and the value.  nullptr: "".
+inline std::string stream_onset_fault(const vits_stream_onset *o, const float *ref_peak, int B) {
+    char buf[200];
+    for (int b = 0; o && b < B; b++) {
+        buf[0] = 0;
+        if (o[b].mode < 0 || o[b].mode > 2)
+            std::snprintf(buf, sizeof buf, "row %d: onset mode %d outside 0..2", b, (int)o[b].mode);
+        else if (!(std::isfinite(o[b].threshold) && o[b].threshold >= 0.f))
+            std::snprintf(buf, sizeof buf, "row %d: onset threshold %g is not a finite value >= 0", b, (double)o[b].threshold);
+        else if (o[b].keep_lead < 0)
+            std::snprintf(buf, sizeof buf, "row %d: onset keep_lead %d is negative", b, (int)o[b].keep_lead);
+        else if (o[b].reserved != 0)
+            std::snprintf(buf, sizeof buf, "row %d: onset reserved %d is not 0", b, (int)o[b].reserved);
+        else if (o[b].mode == 2 && !ref_peak)
+            std::snprintf(buf, sizeof buf, "row %d: onset mode 2 needs ref_peak", b);
+        if (buf[0]) return buf;
+    }
+    return "";
+}
+
+// a_b of a row whose first active sample f lies in a piece that delivers from `delivered_before` on (its e_first)
+inline int64_t stream_onset_start(int64_t f, int64_t keep_lead, int64_t delivered_before) {
+    const int64_t a = f - keep_lead;
+    return a > delivered_before ? a : delivered_before;
+}
+
+// the scan's records of a call's B rows; the onsets have passed stream_onset_fault
+inline void stream_onset_table(const vits_stream_onset *o, const float *ref_peak, int B, std::vector<StreamOnsetRow> &rows) {
+    rows.resize((size_t)B);
+    for (int b = 0; b < B; b++) {
+        const float thr = o[b].mode == 2 ? o[b].threshold * ref_peak[b] : o[b].threshold;
+        rows[b] = StreamOnsetRow{o[b].mode != 0, thr, o[b].keep_lead, 0};
+    }
+}
+
 }  // namespace vitsmi

@@ -145,6 +145,9 @@ struct ChunkSink {
     vits_enc_chunk_fn efn = nullptr;
     // ... shaped (vits_run_chunked_enc_shaped): validated, nullable
     const vits_stream_shaping *shaping = nullptr;
+    // ... trimmed (vits_run_chunked_enc_trimmed): validated, nullable; its chunks go to tfn, with the rows' skips
+    const vits_stream_onset *onsets = nullptr;
+    vits_enc_chunk_trim_fn tfn = nullptr;
 };
 
 constexpr int kMaxRangeLaunches = 512;
@@ -1995,6 +1998,10 @@ int render_chunks(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int
         }
         shaped = shp.lookahead > 0 || any_shape(shp.shapes, B);
     }
+    // The trimmed form (vitsmi.h, "trimmed streaming"): the onsets are the call's - the plan callback has no say in them - and a
+    // trimmed stream takes the shaped kernels, with an empty shaping where there is none.
+    const bool trimmed = enc && stream_trimmed(sink.onsets, B);
+    shaped = shaped || trimmed;
     // the sizes of the run's pieces, the one walk of the staging slab, the ring
     const int sL = shaped ? shp.lookahead : 0;  // the last chunk delivers sL samples more than it renders
     int S_out = 0;
@@ -2003,7 +2010,7 @@ int render_chunks(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int
     const int64_t total = rs ? (int64_t)S_out : (int64_t)F * hop, n_max = stream_n_max(rp, chunk, F, hop, sL, total);
     StreamBufs sb{};
     if (int rc = slab_carve(h, h->io, "staging", [&](Carver &cv) {
-            sb = carve_stream(cv, B, total, n_max, rs ? (int)rp.K : 0, enc, shaped, sL, shaped ? stream_knot_count(&shp, B) : 0);
+            sb = carve_stream(cv, B, total, n_max, rs ? (int)rp.K : 0, enc, shaped, sL, shaped ? stream_knot_count(&shp, B) : 0, trimmed);
         }))
         return rc;
     ResampleRun rrun;
@@ -2011,7 +2018,7 @@ int render_chunks(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int
         HIPCHECK(h, resample_run_begin(rrun, h->rs, sb.rs, ylen, hop, F * hop, S_out, B, st));
         h->stats.total_launches++;
     }
-    const size_t ring_bytes = stream_ring_bytes(B, n_max, enc ? delivery_width(sink.fmt->encoding) : 0);
+    const size_t ring_bytes = stream_ring_bytes(B, n_max, enc ? delivery_width(sink.fmt->encoding) : 0, trimmed);
     if (ring_bytes > h->ring_cap) {
         for (auto &r : h->ring) {
             if (r) hipHostFree(r);
@@ -2027,13 +2034,20 @@ int render_chunks(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int
     StreamPackRun prun;
     if (enc)
         HIPCHECK(h, stream_pack_begin(prun, sink.fmt, shaped ? &shp : nullptr, B, sb.sp, sb.ss,
-                                      rs ? StreamPackRows{sb.rs.n_out, 1, S_out} : StreamPackRows{ylen, hop, F * hop}, total, st));
-    std::vector<int32_t> valid((size_t)(enc ? B : 0));
+                                      rs ? StreamPackRows{sb.rs.n_out, 1, S_out} : StreamPackRows{ylen, hop, F * hop}, total, st,
+                                      trimmed ? sink.onsets : nullptr, row_n.data()));
+    std::vector<int32_t> valid((size_t)(enc ? B : 0)), skip((size_t)(enc ? B : 0), 0);
     auto call = [&](const char *buf, int64_t first, int64_t n) -> int {  // the caller's callback over a finished piece
         if (!enc) return sink.fn ? sink.fn(sink.user, reinterpret_cast<const float *>(buf), B, first, n, total) : 0;
         const int64_t pitch = (int64_t)StreamPackBufs::pitch(prun.width, n);
         for (int b = 0; b < B; b++) valid[b] = (int32_t)std::clamp<int64_t>(row_n[b] - first, 0, n);
         const float *peaks = reinterpret_cast<const float *>(buf + (size_t)B * pitch);
+        if (trimmed) {  // the rows' starts came with the peaks: the skips, and whether the next piece is still scanned
+            const int32_t *start = reinterpret_cast<const int32_t *>(peaks + StreamPackBufs::peak_floats(B));
+            for (int b = 0; b < B; b++) skip[b] = (int32_t)std::clamp<int64_t>((int64_t)start[b] - first, 0, valid[b]);
+            stream_pack_seen(prun, start, first + n, B);
+        }
+        if (sink.tfn) return sink.tfn(sink.user, buf, B, pitch, first, n, valid.data(), skip.data(), peaks, total);
         return sink.efn ? sink.efn(sink.user, buf, B, pitch, first, n, valid.data(), peaks, total) : 0;
     };
     ChunkRing<decltype(call)> ring{h, call};
@@ -2077,8 +2091,8 @@ int render_chunks(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int
         }
         // (a chunk shorter than the filter's or the limiter's look-ahead completes nothing: no copy, no call, the same slot next)
         if (pn <= 0) continue;
-        if (enc)  // bytes and peaks in one copy
-            HIPCHECK(h, hipMemcpyAsync(ring.slot(), d, (size_t)B * pitch + (size_t)B * sizeof(float), hipMemcpyDeviceToHost, st));
+        if (enc)  // bytes and peaks - a trimmed stream: and starts - in one copy
+            HIPCHECK(h, hipMemcpyAsync(ring.slot(), d, (size_t)B * pitch + prun.tail_bytes(B), hipMemcpyDeviceToHost, st));
         else if (rs)
             HIPCHECK(h, hipMemcpyAsync(ring.slot(), x, (size_t)B * pn * 4, hipMemcpyDeviceToHost, st));
         else  // straight out of the rendered rows
@@ -2598,9 +2612,9 @@ int vits_reserve(vits_handle *h, int B, int T, int F) {
         const DeliveryNeeds all{/*scan=*/true, /*levelled=*/true, /*shaped=*/true, shape_pts, /*limited=*/true};
         const size_t io_dlv = carved_bytes([&](Carver &cv) { carve_delivery_call(cv, B, F * m.hop, all); });
         // ... or a stream's (carve_stream): every chunk_frames <= F, i.e. chunks of up to the row's samples - the look-ahead the
-        // last chunk delivers beyond what it renders included -, shaped for the longest look-ahead; at an output rate K > 0
+        // last chunk delivers beyond what it renders included -, shaped for the longest look-ahead and trimmed; at an output rate K > 0
         const auto stream_bytes = [&](int64_t row, int K) {
-            return carved_bytes([&](Carver &cv) { carve_stream(cv, B, row, row, K, true, true, VITS_LIMIT_MAX_LOOKAHEAD, shape_pts); });
+            return carved_bytes([&](Carver &cv) { carve_stream(cv, B, row, row, K, true, true, VITS_LIMIT_MAX_LOOKAHEAD, shape_pts, /*trimmed=*/true); });
         };
         const size_t io_sp = stream_bytes((int64_t)F * m.hop, 0);
         size_t io = io_in > io_pcm ? io_in : io_pcm;
@@ -2965,13 +2979,35 @@ int vits_stream_emit_range(int64_t first, int64_t n, int is_last, int64_t total,
     return VITS_OK;
 }
 
-int vits_run_chunked_enc_shaped(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
-                                const vits_noise *noise, const vits_controls *ctl, const vits_stream_format *fmt,
-                                const vits_stream_shaping *shaping, int chunk_frames, vits_enc_chunk_fn fn, void *user) {
+// vits_stream_onset, checked on the host behind the shaping (vitsmi.h, "trimmed streaming")
+static int host_stream_onsets(vits_handle *h, const vits_stream_onset *onsets, const vits_stream_format *fmt, int B) {
+    const std::string e = stream_onset_fault(onsets, fmt ? fmt->ref_peak : nullptr, B);
+    if (!e.empty()) return fail(h, VITS_E_ARG, "%s", e.c_str());
+    return VITS_OK;
+}
+
+int vits_stream_onset_check(const vits_stream_onset *onsets, const vits_stream_format *fmt, int B) {
+    if (B < 0) return fail(nullptr, VITS_E_ARG, "B = %d is negative", B);
+    return host_stream_onsets(nullptr, onsets, fmt, B);
+}
+
+int vits_stream_onset_start(int64_t f, int64_t keep_lead, int64_t delivered_before, int64_t *a) {
+    if (!a || f < 0 || keep_lead < 0 || delivered_before < 0 || delivered_before > f)
+        return fail(nullptr, VITS_E_ARG, "bad onset start arguments: f %lld, keep_lead %lld, delivered_before %lld", (long long)f,
+                    (long long)keep_lead, (long long)delivered_before);
+    *a = stream_onset_start(f, keep_lead, delivered_before);
+    return VITS_OK;
+}
+
+// the three encoded entries of the whole path: fn without, tfn with the rows' skips
+static int run_chunked_enc(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid, const vits_noise *noise,
+                           const vits_controls *ctl, const vits_stream_format *fmt, const vits_stream_shaping *shaping,
+                           const vits_stream_onset *onsets, int chunk_frames, vits_enc_chunk_fn fn, vits_enc_chunk_trim_fn tfn, void *user) {
     if (!h) return VITS_E_ARG;
     std::lock_guard<std::mutex> lk(h->mu);
     if (int rc = host_stream_format(h, fmt, B)) return rc;  // (pure host code: a host-only handle answers it too)
     if (int rc = host_stream_shaping(h, shaping, fmt, B)) return rc;
+    if (int rc = host_stream_onsets(h, onsets, fmt, B)) return rc;
     if (int rc = check_dev(h)) return rc;
     RunRows rr;
     if (int rc = host_controls(h, ctl, lens, B, T, rr)) return rc;
@@ -2979,7 +3015,22 @@ int vits_run_chunked_enc_shaped(vits_handle *h, const int64_t *ids, const int64_
     sink.fmt = fmt;
     sink.efn = fn;
     sink.shaping = shaping;
+    sink.onsets = onsets;
+    sink.tfn = tfn;
     return run_chunked_sink(h, ids, lens, B, T, rr, sid, noise, sink);
+}
+
+int vits_run_chunked_enc_trimmed(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
+                                 const vits_noise *noise, const vits_controls *ctl, const vits_stream_format *fmt,
+                                 const vits_stream_shaping *shaping, const vits_stream_onset *onsets, int chunk_frames,
+                                 vits_enc_chunk_trim_fn fn, void *user) {
+    return run_chunked_enc(h, ids, lens, B, T, sid, noise, ctl, fmt, shaping, onsets, chunk_frames, nullptr, fn, user);
+}
+
+int vits_run_chunked_enc_shaped(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
+                                const vits_noise *noise, const vits_controls *ctl, const vits_stream_format *fmt,
+                                const vits_stream_shaping *shaping, int chunk_frames, vits_enc_chunk_fn fn, void *user) {
+    return run_chunked_enc(h, ids, lens, B, T, sid, noise, ctl, fmt, shaping, nullptr, chunk_frames, fn, nullptr, user);
 }
 
 int vits_run_chunked_enc(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
@@ -3378,19 +3429,34 @@ int vits_run_vocoder_chunked(vits_handle *h, const float *z, int B, int F, const
     return vocoder_common(h, z, B, F, sid, nullptr, &sink);
 }
 
-int vits_run_vocoder_chunked_enc_shaped(vits_handle *h, const float *z, int B, int F, const int64_t *sid, const vits_stream_format *fmt,
-                                        const vits_stream_shaping *shaping, int chunk_frames, vits_enc_chunk_fn fn, void *user) {
+static int run_vocoder_chunked_enc(vits_handle *h, const float *z, int B, int F, const int64_t *sid, const vits_stream_format *fmt,
+                                   const vits_stream_shaping *shaping, const vits_stream_onset *onsets, int chunk_frames, vits_enc_chunk_fn fn,
+                                   vits_enc_chunk_trim_fn tfn, void *user) {
     if (!h) return VITS_E_ARG;
     std::lock_guard<std::mutex> lk(h->mu);
     if (int rc = host_stream_format(h, fmt, B)) return rc;
     if (int rc = host_stream_shaping(h, shaping, fmt, B)) return rc;
+    if (int rc = host_stream_onsets(h, onsets, fmt, B)) return rc;
     if (int rc = check_dev(h)) return rc;
     if (chunk_frames < 1) return fail(h, VITS_E_ARG, "bad vocoder arguments");
     ChunkSink sink{chunk_frames, nullptr, user};
     sink.fmt = fmt;
     sink.efn = fn;
     sink.shaping = shaping;
+    sink.onsets = onsets;
+    sink.tfn = tfn;
     return vocoder_common(h, z, B, F, sid, nullptr, &sink);
+}
+
+int vits_run_vocoder_chunked_enc_trimmed(vits_handle *h, const float *z, int B, int F, const int64_t *sid, const vits_stream_format *fmt,
+                                         const vits_stream_shaping *shaping, const vits_stream_onset *onsets, int chunk_frames,
+                                         vits_enc_chunk_trim_fn fn, void *user) {
+    return run_vocoder_chunked_enc(h, z, B, F, sid, fmt, shaping, onsets, chunk_frames, nullptr, fn, user);
+}
+
+int vits_run_vocoder_chunked_enc_shaped(vits_handle *h, const float *z, int B, int F, const int64_t *sid, const vits_stream_format *fmt,
+                                        const vits_stream_shaping *shaping, int chunk_frames, vits_enc_chunk_fn fn, void *user) {
+    return run_vocoder_chunked_enc(h, z, B, F, sid, fmt, shaping, nullptr, chunk_frames, fn, nullptr, user);
 }
 
 int vits_run_vocoder_chunked_enc(vits_handle *h, const float *z, int B, int F, const int64_t *sid, const vits_stream_format *fmt,
@@ -4276,7 +4342,8 @@ int vits_test_loudness_blocks(int device_id, const float *x, const int64_t *coun
 namespace {
 int stream_pack_test(int device_id, const float *x, const int64_t *counts, int B, int S, int piece_samples, const vits_stream_format *fmt,
                      bool shaped, const vits_stream_shaping *shaping, void *bytes, size_t bytes_cap, int64_t *pitches, int32_t *valid,
-                     float *peaks, int64_t *firsts, int64_t *ns, int max_pieces) {
+                     float *peaks, int64_t *firsts, int64_t *ns, int max_pieces, const vits_stream_onset *onsets = nullptr,
+                     int32_t *skip = nullptr, int32_t *start_out = nullptr) {
     if (!x || !counts || !bytes || !pitches || !valid || !peaks || B <= 0 || B > 65535 || S <= 0 || piece_samples < 1 ||
         (int64_t)B * S > (int64_t)1 << 40)
         return fail(nullptr, VITS_E_ARG, "bad stream pack test arguments");
@@ -4285,6 +4352,8 @@ int stream_pack_test(int device_id, const float *x, const int64_t *counts, int B
     if (int rc = host_stream_format(nullptr, fmt, B)) return rc;
     if (shaped)
         if (int rc = host_stream_shaping(nullptr, shaping, fmt, B)) return rc;
+    if (int rc = host_stream_onsets(nullptr, onsets, fmt, B)) return rc;
+    const bool trimmed = stream_trimmed(onsets, B);
     const vits_stream_shaping none{};
     const vits_stream_shaping *shp = !shaped ? nullptr : (shaping ? shaping : &none);  // (the shaped hook always runs the shaped kernels)
     const int L = shp ? shp->lookahead : 0;
@@ -4306,16 +4375,19 @@ int stream_pack_test(int device_id, const float *x, const int64_t *counts, int B
     int *dcount = D.up(c32.data(), (size_t)B);
     // the pipeline's buffers, by the pipeline's walk
     const int64_t n_max = stream_n_max(ResamplePlan{}, piece_samples, S, 1, L, S);  // (piece_samples "frames" of one sample)
-    const auto walk = [&](Carver &cv) { return carve_stream(cv, B, S, n_max, 0, /*enc=*/true, shaped, L, shaped ? stream_knot_count(shp, B) : 0); };
+    const auto walk = [&](Carver &cv) {
+        return carve_stream(cv, B, S, n_max, 0, /*enc=*/true, shaped, L, shaped ? stream_knot_count(shp, B) : 0, trimmed);
+    };
     const size_t total = carved_bytes(walk);
     Carver cv(D.alloc<unsigned char>(total), total);
     TCHECK(D.err);
     const StreamBufs sb = walk(cv);
     if (!cv.fits()) return fail(nullptr, VITS_E_NOMEM, "stream walk carved %zu of %zu bytes", cv.used, cv.cap);
     StreamPackRun run;
-    TCHECK(stream_pack_begin(run, fmt, shp, B, sb.sp, sb.ss, StreamPackRows{dcount, 1, S}, S, nullptr));
+    TCHECK(stream_pack_begin(run, fmt, shp, B, sb.sp, sb.ss, StreamPackRows{dcount, 1, S}, S, nullptr, trimmed ? onsets : nullptr, counts));
     unsigned char *dst = static_cast<unsigned char *>(bytes);
     std::vector<unsigned char> landing;
+    std::vector<int32_t> start((size_t)B, 0);
     int k = 0;
     for (int64_t f0 = 0; f0 < S; f0 += piece_samples, k++) {
         int64_t ef = 0, en = 0;
@@ -4331,14 +4403,21 @@ int stream_pack_test(int device_id, const float *x, const int64_t *counts, int B
         if (ns) ns[k] = en;
         pitches[k] = 0;
         if (en <= 0) continue;
-        landing.resize((size_t)B * pitch + (size_t)B * sizeof(float));
-        TCHECK(hipMemcpy(landing.data(), d, landing.size(), hipMemcpyDeviceToHost));  // bytes and peaks in one copy, as the pipeline
+        landing.resize((size_t)B * pitch + run.tail_bytes(B));
+        TCHECK(hipMemcpy(landing.data(), d, landing.size(), hipMemcpyDeviceToHost));  // bytes, peaks (and starts) in one copy, as the pipeline
         std::memcpy(dst, landing.data(), (size_t)B * pitch);
         std::memcpy(peaks + (size_t)k * B, landing.data() + (size_t)B * pitch, (size_t)B * sizeof(float));
         dst += (size_t)B * pitch;
         pitches[k] = (int64_t)pitch;
         for (int b = 0; b < B; b++) valid[(size_t)k * B + b] = (int32_t)std::clamp<int64_t>(counts[b] - ef, 0, en);
+        if (trimmed) {
+            std::memcpy(start.data(), landing.data() + (size_t)B * pitch + StreamPackBufs::peak_floats(B) * sizeof(float), (size_t)B * sizeof(int32_t));
+            stream_pack_seen(run, start.data(), ef + en, B);
+        }
+        for (int b = 0; b < B && skip; b++)
+            skip[(size_t)k * B + b] = (int32_t)std::clamp<int64_t>((int64_t)start[b] - ef, 0, valid[(size_t)k * B + b]);
     }
+    for (int b = 0; b < B && start_out; b++) start_out[b] = start[b];
     return k;
 }
 }  // namespace
@@ -4356,6 +4435,15 @@ int vits_test_stream_pack_shaped(int device_id, const float *x, const int64_t *c
     if (!firsts || !ns) return fail(nullptr, VITS_E_ARG, "bad stream pack test arguments");
     return stream_pack_test(device_id, x, counts, B, S, piece_samples, fmt, /*shaped=*/true, shaping, bytes, bytes_cap, pitches, valid, peaks,
                             firsts, ns, max_pieces);
+}
+
+int vits_test_stream_pack_trimmed(int device_id, const float *x, const int64_t *counts, int B, int S, int piece_samples,
+                                  const vits_stream_format *fmt, const vits_stream_shaping *shaping, const vits_stream_onset *onsets, void *bytes,
+                                  size_t bytes_cap, int64_t *pitches, int32_t *valid, int32_t *skip, float *peaks, int64_t *firsts, int64_t *ns,
+                                  int32_t *start, int max_pieces) {
+    if (!firsts || !ns || !skip || !start) return fail(nullptr, VITS_E_ARG, "bad stream pack test arguments");
+    return stream_pack_test(device_id, x, counts, B, S, piece_samples, fmt, /*shaped=*/true, shaping, bytes, bytes_cap, pitches, valid, peaks,
+                            firsts, ns, max_pieces, onsets, skip, start);
 }
 
 int vits_test_resample_pieces(int device_id, const float *x, const int64_t *lens, int B, int S, int in_rate, int out_rate,

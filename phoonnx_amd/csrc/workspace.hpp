@@ -390,24 +390,29 @@ inline DeliveryCallBufs carve_delivery_call(Carver &cv, int B, int S, const Deli
 // chunk_frames a call brings; the running peaks [B] (padded to whole 16-byte cells) sit right behind at a 16-byte-aligned
 // offset and never move, and a chunk's [B][pitch] bytes END at them (at()), so one copy of B * pitch + 4 * B bytes carries a
 // chunk and its peaks.  Behind the peaks: {ref_peak, volume} per row, uploaded with the peaks' zeros in one copy per run.
+// A trimmed stream (vits_run_chunked_enc_trimmed) has the rows' starts [B] (int32, padded like the peaks) between the peaks and
+// the format table: the one copy then carries bytes, peaks and starts, B * pitch + 4 * (peak_floats(B) + B) bytes.
 // Carved by carve_stream (below) and nowhere else.
 struct StreamPackBufs {
     unsigned char *buf;
     size_t cap;
     unsigned *peak_run;
     float *fmt;
+    int32_t *start = nullptr;  // a trimmed stream's; right behind the peaks
     static size_t pitch(int width, int64_t n) { return (size_t)(((int64_t)width * n + 15) & ~(int64_t)15); }
     static size_t peak_floats(int B) { return ((size_t)B + 3) & ~size_t(3); }
     unsigned char *at(int B, size_t row_pitch) const { return buf + cap - (size_t)B * row_pitch; }  // row_pitch <= pitch(4, n_max)
 };
 
-inline StreamPackBufs carve_stream_pack(Carver &cv, int B, int64_t n_max) {
+inline StreamPackBufs carve_stream_pack(Carver &cv, int B, int64_t n_max, bool trimmed = false) {
     StreamPackBufs s{};
     s.cap = (size_t)B * StreamPackBufs::pitch(4, n_max);
-    s.buf = cv.take<unsigned char>(s.cap + (StreamPackBufs::peak_floats(B) + 2 * (size_t)B) * sizeof(float));
+    const size_t starts = trimmed ? StreamPackBufs::peak_floats(B) : 0;
+    s.buf = cv.take<unsigned char>(s.cap + (StreamPackBufs::peak_floats(B) + starts + 2 * (size_t)B) * sizeof(float));
     if (s.buf) {
         s.peak_run = reinterpret_cast<unsigned *>(s.buf + s.cap);
-        s.fmt = reinterpret_cast<float *>(s.peak_run) + StreamPackBufs::peak_floats(B);
+        if (trimmed) s.start = reinterpret_cast<int32_t *>(s.peak_run + StreamPackBufs::peak_floats(B));
+        s.fmt = reinterpret_cast<float *>(s.peak_run) + StreamPackBufs::peak_floats(B) + starts;
     }
     return s;
 }
@@ -420,13 +425,15 @@ struct StreamShapeBufs {
     StreamShapeRow *rows;
     ShapeKnot *knots;
     float *carry[2];
+    StreamOnsetRow *onsets = nullptr;  // a trimmed stream's: what the scan reads (stream_trim.hip.hpp), carved last
 };
 
-inline StreamShapeBufs carve_stream_shape(Carver &cv, int B, int L, int64_t n_knots) {
+inline StreamShapeBufs carve_stream_shape(Carver &cv, int B, int L, int64_t n_knots, bool trimmed = false) {
     StreamShapeBufs s{};
     s.rows = cv.take<StreamShapeRow>(B);
     s.knots = cv.take<ShapeKnot>((size_t)n_knots);
     for (auto &c : s.carry) c = cv.take<float>((size_t)B * 2 * L);
+    if (trimmed) s.onsets = cv.take<StreamOnsetRow>(B);
     return s;
 }
 
@@ -452,26 +459,29 @@ inline int64_t stream_n_max(const ResamplePlan &rp, int chunk, int F, int hop, i
     return piece + L < total ? piece + L : total;
 }
 
-// bytes of one pinned ring slot: B rows of the largest piece as fp32 (width 0: a float sink) or encoded, the running peaks behind
-inline size_t stream_ring_bytes(int B, int64_t n_max, int width) {
+// bytes of one pinned ring slot: B rows of the largest piece as fp32 (width 0: a float sink) or encoded, the running peaks behind -
+// and behind them a trimmed stream's starts
+inline size_t stream_ring_bytes(int B, int64_t n_max, int width, bool trimmed = false) {
     if (!width) return (size_t)B * n_max * sizeof(float);
-    return (size_t)B * StreamPackBufs::pitch(width, n_max) + StreamPackBufs::peak_floats(B) * sizeof(float);
+    return (size_t)B * StreamPackBufs::pitch(width, n_max) + StreamPackBufs::peak_floats(B) * (trimmed ? 2 : 1) * sizeof(float);
 }
 
 // What a streamed run takes from the staging slab (from its base: the run's inputs are consumed), in this order: at an output
 // rate (K > 0: the resampler's) carve_resample's buffers for rows of `row` output samples - the chunk the stream packs lives
 // there -, an encoded sink's chunk buffer for pieces of n_max samples, a shaped one's tables and carries.  The rest stays zero.
+// trimmed (implies shaped: a trimmed stream runs the shaped kernels): the rows' starts and the scan's records on top.
 struct StreamBufs {
     ResampleBufs rs;
     StreamPackBufs sp;
     StreamShapeBufs ss;
 };
 
-inline StreamBufs carve_stream(Carver &cv, int B, int64_t row, int64_t n_max, int K, bool enc, bool shaped, int L, int64_t n_knots) {
+inline StreamBufs carve_stream(Carver &cv, int B, int64_t row, int64_t n_max, int K, bool enc, bool shaped, int L, int64_t n_knots,
+                               bool trimmed = false) {
     StreamBufs s{};
     if (K > 0) s.rs = carve_resample(cv, B, (int)row, K);
-    if (enc) s.sp = carve_stream_pack(cv, B, n_max);
-    if (enc && shaped) s.ss = carve_stream_shape(cv, B, L, n_knots);
+    if (enc) s.sp = carve_stream_pack(cv, B, n_max, trimmed);
+    if (enc && shaped) s.ss = carve_stream_shape(cv, B, L, n_knots, trimmed);
     return s;
 }
 

@@ -297,6 +297,16 @@ class Limit:
     lookahead: int = 110
 
 
+@dataclass
+class Onset:
+    """The leading trim of one row of an encoded stream (vitsmi.h, vits_stream_onset): mode 0 off, 1 - a sample is active
+    above `threshold`, 2 - above `threshold` times the row's ref_peak; the row is kept from its first active sample on, with
+    up to keep_lead samples (at the delivered rate) in front of it - as many of them as the stream has not handed over yet."""
+    mode: int = 0
+    threshold: float = 0.0
+    keep_lead: int = 0
+
+
 _CURVES = {"linear": 0, "smooth": 1}
 
 
@@ -635,6 +645,9 @@ class EncodedChunk:
     valid: np.ndarray
     peak: np.ndarray
     total_samples: int
+    # a trimmed stream (vitsmi.h, "trimmed streaming"): skip[b] leading elements of row b lie in front of the row's kept range -
+    # the caller sends data[b, skip[b]:valid[b]]; None: the stream is not trimmed (nothing to skip)
+    skip: Optional[np.ndarray] = None
 
 
 def _stream_format(encoding, ref_peak, volume, B):
@@ -717,6 +730,52 @@ def _stream_shaping(shapes, limit, B):
 
 # a stream's limiter as the C struct holds it, for the tests of the validation: lookahead, and ceiling [B] or None
 RawStreamLimit = namedtuple("RawStreamLimit", "lookahead ceiling")
+
+# a row's onset as the C struct holds it, for the tests of the validation
+RawOnset = namedtuple("RawOnset", "mode threshold keep_lead reserved")
+
+
+def _stream_onsets(onsets, B):
+    """The vits_stream_onset array of a trimmed stream (vitsmi.h, "trimmed streaming"), or None: onsets - None, one Onset
+    (every row) or one per row (None in the list: that row is not trimmed; RawOnset: the struct's four fields as they are)."""
+    if onsets is None:
+        return None
+    rows = [onsets] * B if isinstance(onsets, (Onset, RawOnset)) else list(onsets)
+    if len(rows) != B:
+        raise SessionError(f"onsets must be one Onset or one per row ({B}), got {len(rows)}")
+    arr = (_ffi.VitsStreamOnset * B)()
+    for b, o in enumerate(rows):
+        if o is None:
+            continue
+        try:
+            arr[b].mode, arr[b].threshold, arr[b].keep_lead = int(o.mode), float(o.threshold), int(o.keep_lead)
+            arr[b].reserved = int(getattr(o, "reserved", 0))
+        except (AttributeError, TypeError, ValueError, OverflowError) as e:
+            raise SessionError(f"row {b}: onset: {e}") from None
+    return arr
+
+
+def stream_onset_check(onsets, B=1, ref_peak=None):
+    """The validation of a trimmed stream's onsets (vits_stream_onset_check: pure host code) over B rows, with or without a
+    ref_peak; a refusal raises SessionError."""
+    arr = _stream_onsets(onsets, B)
+    fmt = _ffi.VitsStreamFormat()
+    peak = None if ref_peak is None else np.ascontiguousarray(np.broadcast_to(np.asarray(ref_peak, np.float32), (B,)), np.float32)
+    if peak is not None:
+        fmt.ref_peak = peak.ctypes.data
+    rc = _ffi.load().vits_stream_onset_check(arr, C.byref(fmt), int(B))
+    if rc != 0:
+        raise SessionError(f"vits_stream_onset_check failed [{rc}]: {_ffi.last_error(None)}")
+
+
+def stream_onset_start(f, keep_lead, delivered_before):
+    """a_b of a row whose first active sample f lies in a piece that delivers from `delivered_before` on
+    (vits_stream_onset_start: pure host code)."""
+    a = C.c_int64()
+    rc = _ffi.load().vits_stream_onset_start(int(f), int(keep_lead), int(delivered_before), C.byref(a))
+    if rc != 0:
+        raise SessionError(f"vits_stream_onset_start failed [{rc}]: {_ffi.last_error(None)}")
+    return a.value
 
 
 def stream_shaping_check(shapes=None, limit=None, B=1, volume=None):
@@ -1199,9 +1258,26 @@ class MiSession:
 
         return _ffi.ENC_CHUNK_FN, item
 
+    @staticmethod
+    def _trimmed_items(dtype):
+        """_encoded_items for a trimmed run: the callback with the rows' skips"""
+        _, plain = MiSession._encoded_items(dtype)
+
+        def item(data, B, pitch, first, n, valid, skip, peak, total):
+            chunk = plain(data, B, pitch, first, n, valid, peak, total)
+            chunk.skip = np.ctypeslib.as_array(skip, shape=(B,)).copy()
+            return chunk
+
+        return _ffi.ENC_CHUNK_TRIM_FN, item
+
+    def _onsets_check(self, onsets, fmt, B):
+        """onsets the engine would refuse up front raise here, by the call itself: nothing was started"""
+        if self._lib.vits_stream_onset_check(onsets, C.byref(fmt), B) != 0:
+            raise SessionError(f"trimmed stream refused: {_ffi.last_error(None)}")
+
     def synthesize_stream_encoded(self, ids, lens, scales, sid=None, chunk_frames: int = 64, encoding="pcm16", ref_peak=None,
                                   volume=None, noise_dp=None, noise_z=None, seeds=None, durations=None, token_rate=None,
-                                  shapes=None, token_gain_db=None, gain_ramp=0.01, limit=None):
+                                  shapes=None, token_gain_db=None, gain_ramp=0.01, limit=None, onsets=None):
         """synthesize_stream with every chunk post-processed, encoded and masked to each row's own length on the device
         (vitsmi.h, "encoded streaming"): yields EncodedChunk.  encoding "pcm16" / "ulaw" / "alaw" / "f32"; `volume` and
         `ref_peak` None, a scalar or [B]: row b is scaled by volume[b] and - with ref_peak - normalised by ref_peak[b] (a
@@ -1215,7 +1291,11 @@ class MiSession:
         own end, and with a look-ahead of L samples every chunk is delivered L samples late (the first chunk is L shorter,
         the last L longer; EncodedChunk.peak then runs up to L samples ahead of the audio).  token_gain_db places its
         breakpoints on the token boundaries of THIS run - free or forced durations - inside the engine's plan callback,
-        before the first chunk is rendered."""
+        before the first chunk is rendered.
+        onsets (one Onset or one per row, None for a row that is not trimmed) cuts the leading silence of every row on the
+        device (vitsmi.h, "trimmed streaming"): EncodedChunk.skip[b] elements of row b lie in front of its kept range; fades
+        and limiter count from there, and data[b, skip[b]:valid[b]], joined, is what the delivery gives under the equivalent
+        Trim.  The chunk ranges do not change."""
         ids = np.ascontiguousarray(ids, np.int64)
         lens = np.ascontiguousarray(lens, np.int64)
         B, T = ids.shape
@@ -1236,6 +1316,14 @@ class MiSession:
             noise.noise_z = keep[-1].ctypes.data
             noise.noise_z_stride = keep[-1].shape[2]
         ctl = _controls(_rows(scales, B), seeds, durations, token_rate)
+        trim = _stream_onsets(onsets, B)
+        if trim is not None:  # (passed down only when asked for)
+            if shaping is not None:
+                self._shaping_check(shaping, fmt, B)
+            self._onsets_check(trim, fmt, B)
+            return self._stream(lambda cb: self._lib.vits_run_chunked_enc_trimmed(
+                self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(sid), C.byref(noise), C.byref(ctl), C.byref(fmt),
+                None if shaping is None else C.byref(shaping), trim, int(chunk_frames), cb, None), self._trimmed_items(dtype))
         if shaping is None:  # (nothing asked for: the call made before there was any shaping)
             return self._stream(lambda cb: self._lib.vits_run_chunked_enc(
                 self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(sid), C.byref(noise), C.byref(ctl), C.byref(fmt),
@@ -1294,9 +1382,9 @@ class MiSession:
         return shaping
 
     def vocoder_stream_encoded(self, z, sid=None, chunk_frames: int = 64, encoding="pcm16", ref_peak=None, volume=None, shapes=None,
-                               limit=None):
+                               limit=None, onsets=None):
         """Vocoder only, chunked and encoded: yields EncodedChunk (every row has F * hop samples, or their count at the
-        output rate).  shapes / limit as synthesize_stream_encoded."""
+        output rate).  shapes / limit / onsets as synthesize_stream_encoded."""
         z = np.ascontiguousarray(z, np.float32)
         B, Cc, F = z.shape
         fmt, dtype = _stream_format(encoding, ref_peak, volume, B)
@@ -1304,6 +1392,14 @@ class MiSession:
         if Cc != self.hparam("inter"):
             raise SessionError(f"z must have {self.hparam('inter')} channels")
         sid = None if sid is None else np.ascontiguousarray(sid, np.int64)
+        trim = _stream_onsets(onsets, B)
+        if trim is not None:
+            if shaping is not None:
+                self._shaping_check(shaping, fmt, B)
+            self._onsets_check(trim, fmt, B)
+            return self._stream(lambda cb: self._lib.vits_run_vocoder_chunked_enc_trimmed(
+                self._h, _ffi.ptr(z), B, F, _ffi.ptr(sid), C.byref(fmt), None if shaping is None else C.byref(shaping), trim,
+                int(chunk_frames), cb, None), self._trimmed_items(dtype))
         if shaping is None:
             return self._stream(lambda cb: self._lib.vits_run_vocoder_chunked_enc(
                 self._h, _ffi.ptr(z), B, F, _ffi.ptr(sid), C.byref(fmt), int(chunk_frames), cb, None), self._encoded_items(dtype))
@@ -2305,6 +2401,42 @@ def test_stream_pack_shaped(x, counts, piece_samples, encoding="pcm16", ref_peak
             chunks.append(EncodedChunk(int(firsts[k]), out[off:off + B * p].reshape(B, p), valid[k], peaks[k], S))
         off += B * p
     return chunks, [(int(f), int(c)) for f, c in zip(firsts[:n], ns[:n])]
+
+
+def test_stream_pack_trimmed(x, counts, piece_samples, encoding="pcm16", ref_peak=None, volume=None, shapes=None, limit=None,
+                             onsets=None, device_id=0):
+    """vits_test_stream_pack_trimmed: test_stream_pack_shaped with onsets (as MiSession.synthesize_stream_encoded, or
+    RawOnset) -> (chunks - each with its `skip` -, [(first, n) delivered by every piece], start int32 [B]: the rows' final
+    a_b, INT32_MAX where a trimmed row has no onset)."""
+    x = np.ascontiguousarray(x, np.float32)
+    counts = np.ascontiguousarray(counts, np.int64)
+    B, S = x.shape
+    fmt, dtype = _stream_format(encoding, ref_peak, volume, B)
+    shaping = _stream_shaping(shapes, limit, B)
+    trim = _stream_onsets(onsets, B)
+    w, piece = np.dtype(dtype).itemsize, int(piece_samples)
+    if piece < 1:
+        raise SessionError(f"piece_samples = {piece} is not positive")
+    n_pieces = -(-S // piece)
+    out = np.full(B * (-(-w * S // 16) * 16 + 16 * n_pieces), 0xA5, np.uint8)
+    pitches = np.zeros(n_pieces, np.int64)
+    firsts, ns = np.full(n_pieces, -1, np.int64), np.full(n_pieces, -1, np.int64)
+    valid, skip = np.full((n_pieces, B), -1, np.int32), np.full((n_pieces, B), -1, np.int32)
+    peaks = np.full((n_pieces, B), np.nan, np.float32)
+    start = np.full(B, -1, np.int32)
+    n = _ffi.load().vits_test_stream_pack_trimmed(device_id, _ffi.ptr(x), _ffi.ptr(counts), B, S, piece, C.byref(fmt),
+                                                  None if shaping is None else C.byref(shaping), trim, _ffi.ptr(out), out.nbytes,
+                                                  _ffi.ptr(pitches), _ffi.ptr(valid), _ffi.ptr(skip), _ffi.ptr(peaks), _ffi.ptr(firsts),
+                                                  _ffi.ptr(ns), _ffi.ptr(start), n_pieces)
+    if n < 0:
+        raise SessionError(f"vits_test_stream_pack_trimmed failed [{n}]: {_ffi.last_error(None)}")
+    chunks, off = [], 0
+    for k in range(n):
+        p = int(pitches[k])
+        if ns[k] > 0:
+            chunks.append(EncodedChunk(int(firsts[k]), out[off:off + B * p].reshape(B, p), valid[k], peaks[k], S, skip[k]))
+        off += B * p
+    return chunks, [(int(f), int(c)) for f, c in zip(firsts[:n], ns[:n])], start
 
 
 # ---- the token-to-frame and frame-to-sample kernels by value (include/vitsmi.h: vits_test_durations ...) ----------------

@@ -711,7 +711,7 @@ class TTSVoice:
     def stream_encoded(self, text: str, syn_config: Optional[SynthesisConfig] = None, encoding: str = "pcm16",
                        chunk_frames: int = 64, sentence_silence: float = 0.0, ref_peak=None, fade_in: float = 0.0,
                        fade_out: float = 0.0, fade_curve: str = "linear", phoneme_gain_db=None, limit_ceiling: float = 0.0,
-                       limit_lookahead: float = 0.005):
+                       limit_lookahead: float = 0.005, trim_silence=None):
         """Extension: synthesize_encoded's ONE stream as a generator of `bytes`, handed out while the audio still renders.
         All sentences render as one chunked batch (MiSession.synthesize_stream_encoded: post-processing, encoding and the
         masking to each sentence's own length happen on the device, per chunk).  Sentence 0's chunks are yielded as they
@@ -726,13 +726,20 @@ class TTSVoice:
         synthesize_encoded, for every sentence (vitsmi.h, "shaped streaming"): a streamed sentence meets the silence of its
         pause at exactly 0, takes a volume per phoneme and ducks under its peaks instead of clipping - joined, still
         synthesize_encoded's bytes.  With a limiter every chunk arrives limit_lookahead of audio later.  They are passed
-        down only when asked for; a session that streams fp32 only takes audio_encoding.stream_shaped."""
+        down only when asked for; a session that streams fp32 only takes audio_encoding.stream_shaped.
+        trim_silence (None; a float: the threshold as a fraction of the sentence's ref_peak - it needs normalize_audio and
+        ref_peak; or a session.Onset with keep_lead in seconds) cuts the LEADING silence of every sentence on the device
+        (vitsmi.h, "trimmed streaming"): every sentence is yielded from its onset on, behind its pause, and its fade-in and
+        limiter start there.  A stream keeps as much of keep_lead as it has not handed over yet: with keep_lead <=
+        limit_lookahead, or an onset within the first chunk, the bytes are synthesize_encoded's under the same leading trim.
+        The trailing silence stays: a stream learns where its audio ends only at the end."""
         from . import audio_encoding as ae
         cfg = syn_config if syn_config is not None else SynthesisConfig()
         ae._check(encoding)
         lead = self._lead_samples(sentence_silence)
         shape = self._shape(fade_in, fade_out, fade_curve)
         limit = self._limit(limit_ceiling, limit_lookahead)
+        onset = self._onset(trim_silence, cfg, ref_peak)
         if phoneme_gain_db is not None and not hasattr(self.session, "synthesize_batch"):
             raise ValueError("phoneme_gain_db needs a session that reports durations (synthesize_batch)")
         if cfg.normalize_audio and ref_peak is None:
@@ -740,9 +747,31 @@ class TTSVoice:
                              "normalize_audio off")
         if int(chunk_frames) < 1:
             raise ValueError(f"chunk_frames must be >= 1 (got {chunk_frames})")
-        return self._stream_encoded(text, cfg, encoding, int(chunk_frames), lead, ref_peak, shape, phoneme_gain_db, limit)
+        return self._stream_encoded(text, cfg, encoding, int(chunk_frames), lead, ref_peak, shape, phoneme_gain_db, limit, onset)
 
-    def _stream_encoded(self, text, cfg, encoding, chunk_frames, lead, ref_peak, shape=None, phoneme_gain_db=None, limit=None):
+    def _onset(self, trim_silence, cfg, ref_peak):
+        """trim_silence of stream_encoded -> a session.Onset in samples at the delivered rate, or None.  A float is a threshold
+        relative to the sentence's ref_peak (mode 2); an Onset is taken with keep_lead in SECONDS, converted like the pause."""
+        from .session import Onset
+        if trim_silence is None:
+            return None
+        if isinstance(trim_silence, Onset):
+            o = trim_silence
+            if not o.keep_lead >= 0:
+                raise ValueError(f"trim_silence: keep_lead must be >= 0 seconds (got {o.keep_lead})")
+            o = Onset(int(o.mode), float(o.threshold), self._lead_samples(o.keep_lead))
+        else:
+            thr = float(trim_silence)
+            o = Onset(2, thr, 0)
+        if not (o.threshold >= 0.0 and np.isfinite(o.threshold)):
+            raise ValueError(f"trim_silence must be a finite threshold >= 0 (got {o.threshold})")
+        if o.mode == 2 and (not cfg.normalize_audio or ref_peak is None):
+            raise ValueError("trim_silence relative to the peak needs normalize_audio and ref_peak (a stream cannot know its own "
+                             "peak): pass them, or an absolute threshold as Onset(1, threshold)")
+        return o if o.mode else None
+
+    def _stream_encoded(self, text, cfg, encoding, chunk_frames, lead, ref_peak, shape=None, phoneme_gain_db=None, limit=None,
+                        onset=None):
         from . import audio_encoding as ae
         from .sharding import pad_batch
         token_db = None
@@ -755,7 +784,7 @@ class TTSVoice:
         B = len(all_ids)
         if not B:
             return
-        shaped = shape is not None or token_db is not None or limit is not None
+        shaped = shape is not None or token_db is not None or limit is not None or onset is not None
         peaks = None
         if cfg.normalize_audio:
             peaks = np.asarray(ref_peak, np.float32)
@@ -784,8 +813,12 @@ class TTSVoice:
             audios = [np.atleast_1d(a) for a in audios]
             shapes = self._row_shapes(shape, token_db, durs, [len(a) for a in audios])
             for b, a in enumerate(audios):
-                mul = ae.shape_multiplier(0, len(a), shapes[b])
-                yield pause + ae.encode(ae.scaled(a, None if peaks is None else peaks[b], volume, mul, limit), encoding).tobytes()
+                a0 = 0
+                if onset is not None:  # (one piece: a = max(0, f - keep_lead); no onset: nothing is kept)
+                    hit = np.flatnonzero(np.abs(a) > ae.onset_threshold(onset, None if peaks is None else peaks[b]))
+                    a0 = max(int(hit[0]) - onset.keep_lead, 0) if hit.size else len(a)
+                mul = ae.shape_multiplier(a0, len(a) - a0, shapes[b])
+                yield pause + ae.encode(ae.scaled(a[a0:], None if peaks is None else peaks[b], volume, mul, limit), encoding).tobytes()
             return
         ids, lens = pad_batch(all_ids)
         expected = [i.name for i in session.get_inputs()]
@@ -802,7 +835,15 @@ class TTSVoice:
                 more["token_gain_db"], more["gain_ramp"] = self._padded_db(token_db), _GAIN_RAMP
             if limit is not None:
                 more["limit"] = limit
-            chunks = ((c.first_sample, c.data.shape[1], c.total_samples, c.valid, [c.data[b, :int(c.valid[b])].tobytes() for b in range(B)])
+            if onset is not None:
+                more["onsets"] = onset
+
+            def skipped(c, b):  # (a stream that is not trimmed has nothing to skip)
+                skip = getattr(c, "skip", None)
+                return 0 if skip is None else int(skip[b])
+
+            chunks = ((c.first_sample, c.data.shape[1], c.total_samples, c.valid,
+                       [c.data[b, skipped(c, b):int(c.valid[b])].tobytes() for b in range(B)])
                       for c in session.synthesize_stream_encoded(ids, lens, self._scales(cfg), sid, chunk_frames=chunk_frames,
                                                                  encoding=encoding, ref_peak=peaks, volume=volume, **more))
         elif shaped:
@@ -819,8 +860,10 @@ class TTSVoice:
 
             def shaped_chunks():
                 fp32 = session.synthesize_stream(ids, lens, self._scales(cfg), sid, chunk_frames=chunk_frames)
-                for first, data, valid, _, total in ae.stream_shaped(fp32, sample_counts, encoding, peaks, volume, row_shapes, limit):
-                    yield first, data.shape[1], total, valid, [data[b, :int(valid[b])].tobytes() for b in range(B)]
+                for first, data, valid, _, total, *skip in ae.stream_shaped(fp32, sample_counts, encoding, peaks, volume, row_shapes, limit,
+                                                                            onset):
+                    lo = skip[0] if skip else np.zeros(B, np.int32)
+                    yield first, data.shape[1], total, valid, [data[b, int(lo[b]):int(valid[b])].tobytes() for b in range(B)]
             chunks = shaped_chunks()
         else:
             def host_chunks():

@@ -8,7 +8,11 @@ time until the first chunk is in host memory and (b) the whole stream, for the c
   plain        synthesize_stream_encoded as it was: stream_pack_kernel;
   fades        ... with fades of 5 and 10 ms on every row: stream_pack_shaped_kernel;
   limit110     ... with a limiter of 110 samples (5 ms) at a ceiling of 0.5: stream_pack_limited_kernel and the carry;
-  limit1024    ... with the longest look-ahead.
+  limit1024    ... with the longest look-ahead;
+  trim         ... without fades or limiter, every row trimmed at an absolute threshold of 0.01 with keep_lead 110 (vitsmi.h,
+               "trimmed streaming"): stream_onset_kernel until every onset is found, stream_pack_shaped_kernel;
+  trim_never   ... at a threshold nothing reaches: the scan runs in front of every chunk - its worst case;
+  limit110_trim  limit110 with the trim of `trim`.
 --root DIR measures the package of another tree (e.g. a checkout of the parent commit, built) with the same script: columns
 that tree does not have are left out.  --only COLUMN --passes N runs N untimed passes of one column and nothing else (the
 run a kernel trace is taken of).  Prints one JSON line."""
@@ -21,7 +25,7 @@ import time
 import numpy as np
 
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COLUMNS = ("plain", "fades", "limit110", "limit1024")
+COLUMNS = ("plain", "fades", "limit110", "limit1024", "trim", "trim_never", "limit110_trim")
 
 
 def timed(fn, warmup, iters):
@@ -63,6 +67,9 @@ def main():
         fades = session.Shape(int(rate * 0.005), int(rate * 0.010), "linear")
         columns.update({"fades": {"shapes": fades}, "limit110": {"shapes": fades, "limit": session.Limit(0.5, 110)},
                         "limit1024": {"shapes": fades, "limit": session.Limit(0.5, 1024)}})
+    if hasattr(session, "Onset"):
+        columns.update({"trim": {"onsets": session.Onset(1, 0.01, 110)}, "trim_never": {"onsets": session.Onset(1, 1e30, 110)},
+                        "limit110_trim": {"shapes": fades, "limit": session.Limit(0.5, 110), "onsets": session.Onset(1, 0.01, 110)}})
     rng = np.random.default_rng(2024)
     requests = {"b1": np.full(1, T, np.int64), "b32_mixed": np.linspace(32, T, 32).astype(np.int64)}
     out = {"tool": "stream_shape_bench", "root": root, "preset": a.preset, "chunk_frames": cf, "warmup": a.warmup, "iters": a.iters,
