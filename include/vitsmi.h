@@ -391,6 +391,46 @@ int vits_last_sample_counts(vits_handle *h, int64_t *buf, int n);
  * table != NULL, h as [L][K] floats (table_elems >= L * K).  table == NULL asks for the sizes. */
 int vits_resample_plan(int in_rate, int out_rate, int64_t *L, int64_t *M, int64_t *K, float *table, size_t table_elems);
 
+/* ---- output rate per row: each utterance of a batch delivered at its own sample rate ---------------------------
+ * A server that batches callers sees telephony at 8 kHz, ASR at 16 kHz and browsers at 48 kHz in one run.  The text below
+ * is the specification; it extends the one above and changes nothing of it.
+ *
+ * The run has B rows, its input rate is fi, row b has its own rate fo_b.
+ * Native rows: fo_b == 0 or fo_b == fi.  N_b = n_b and y[b][n] = x[b][n] bit for bit for n < n_b.
+ * Resampled rows: every other row, by the definition above unchanged with (L_b, M_b, K_b, h_b) =
+ *   vits_resample_plan(fi, fo_b): N_b = ceil(n_b * L_b / M_b); a sample is K_b fmaf in ascending j from 0.0f; the input reads
+ *   0 outside [0, n_b).
+ * Buffer: S_out = max_b N_b (at least 1); y[b][n] = 0.0f exactly for N_b <= n < S_out.
+ * Consequence: row b of a mixed-rate run is row b of the same run under vits_set_output_rate(fi, fo_b), bit for bit - one
+ * device function renders a sample, whichever entry launched it; a run whose rows all name one rate is that run; a run whose
+ * rows are all native launches nothing and is the native path.
+ * Limits: each rate within the limits above; at most VITS_MAX_ROW_RATES distinct resampling rates in a run.  A violation is
+ * VITS_E_ARG naming the row and the value, before anything is allocated; a refused call leaves the previous setting in place.
+ *
+ * vits_set_output_rates: handle state like vits_set_output_rate, which it replaces (and which, called afterwards, replaces
+ * it).  in_rate as there.  n_rows == 0 or out_rates == NULL clears the row rates (and nothing else).  Host-only and
+ * layout-only handles validate and keep the plans.  A device handle keeps one table per distinct (fi, fo) - taken over
+ * from the setting it replaces where the pair is the same, freed otherwise and at close.  With row rates set:
+ *   a run of B != n_rows rows is VITS_E_ARG naming both numbers, before anything is staged or enqueued: the previous run
+ *     stays readable;
+ *   vits_run*, vits_run_async*, vits_run_vocoder, vits_fetch_output, vits_last_pcm16 and every vits_deliver* work as they
+ *     stand, on [B][S_out] and the rows' N_b (vits_last_sample_counts);
+ *   every chunked entry - vits_run_chunked*, vits_run_vocoder_chunked*, the encoded, shaped and trimmed forms included - and
+ *     vits_run_device* return VITS_E_ARG ("not covered with per-row output rates"): the chunk callbacks describe ONE
+ *     rectangular timeline (first_sample, n_samples, total_samples for all rows), and rows at different rates do not have one;
+ *   every sample-valued field of a delivery is at its row's own rate: leads, trims, fade lengths, envelope points, look-ahead;
+ *   a levelled, shaped or limited delivery's sample_rate must equal the rate of the row of every levelled segment
+ *     (VITS_E_ARG naming the segment and both rates): deliver once per rate - or per rate and encoding -, naming that
+ *     group's rows;
+ *   vits_reserve covers the longest row any of the set plans makes.
+ * vits_last_sample_counts reports, after a run with row rates, N_b at the rates of THAT run.
+ * With no row rates set, every path executes exactly what it executed before they existed. */
+#define VITS_MAX_ROW_RATES 8
+int vits_set_output_rates(vits_handle *h, int in_rate, const int32_t *out_rates, int n_rows);
+/* the rate each row of the last run was delivered at (the voice's own for a native row): host state like
+ * vits_last_sample_counts.  Writes min(n, B) values, returns B. */
+int vits_last_sample_rates(vits_handle *h, int32_t *buf, int n);
+
 /* ---- delivery: the last run's audio packed per request on the device - PCM16, G.711, F32, pauses -------------------
  * The reference post-processes and frames every sentence on the host (phoonnx/voice.py:271-282 peak-normalise / volume /
  * clip, :88-91 int16, :307-326 the pause in front of a sentence); this does it for a whole batch in one operation: read the
@@ -1004,6 +1044,10 @@ int vits_test_resample(int device_id, const float *x, const int64_t *lens, int B
  * the number of deliveries; ranges (nullable, max_ranges pairs) receives each one's (first_sample, n_samples). */
 int vits_test_resample_pieces(int device_id, const float *x, const int64_t *lens, int B, int S, int in_rate, int out_rate,
                               int piece_samples, float *y, int64_t S_out, int64_t *ranges, int max_ranges);
+/* ... and the rows entry ("output rate per row"): out_rates [B], one launch; n_out [B] receives N_b, y is [B][S_out] with
+ * S_out = max_b N_b (y_elems >= B * S_out), every column written. */
+int vits_test_resample_rows(int device_id, const float *x, const int64_t *lens, int B, int S, int in_rate,
+                            const int32_t *out_rates, float *y, size_t y_elems, int64_t *n_out);
 
 /* The kernels that turn tokens into frames and frames into samples, by value.  Every hook checks its sizes and extents on the
  * host (VITS_E_ARG) and launches the pipeline's kernel with the pipeline's grid.

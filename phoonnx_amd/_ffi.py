@@ -129,6 +129,7 @@ EXPORTS = [
     "vits_launch_records", "vits_run_async_rows", "vits_run_device_rows", "vits_run_chunked_rows",
     "vits_run_async_ctl", "vits_run_chunked_ctl", "vits_last_durations",
     "vits_set_output_rate", "vits_last_sample_counts", "vits_resample_plan", "vits_test_resample", "vits_test_resample_pieces",
+    "vits_set_output_rates", "vits_last_sample_rates", "vits_test_resample_rows",
     "vits_test_durations", "vits_test_expand_prior", "vits_test_fill_normal", "vits_test_fill_normal_rows", "vits_test_post_conv",
     "vits_delivery_plan", "vits_deliver", "vits_test_deliver",
     "vits_trim_range", "vits_delivery_plan_trimmed", "vits_deliver_trimmed", "vits_test_deliver_trimmed",
@@ -237,6 +238,9 @@ def load():
     lib.vits_resample_plan.argtypes = [C.c_int, C.c_int, i64p, i64p, i64p, vp, C.c_size_t]
     lib.vits_test_resample.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int64]
     lib.vits_test_resample_pieces.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int64, vp, C.c_int]
+    lib.vits_set_output_rates.argtypes = [vp, C.c_int, vp, C.c_int]
+    lib.vits_last_sample_rates.argtypes = [vp, vp, C.c_int]
+    lib.vits_test_resample_rows.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_size_t, vp]
     lib.vits_test_durations.argtypes = [C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp, vp]
     lib.vits_test_expand_prior.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int64, C.c_int,
                                            C.c_float, vp, vp, vp]

@@ -8,9 +8,9 @@
 // lane streams its own row h[p][0..K) with 16-byte loads (rows are padded to whole 16 bytes) through L1 / L2, where the
 // table - 65 KB for the largest common pair, 1 MiB at the admitted limit - stays resident ("Output rate").
 //
-// Two entries, one function for a sample (resample_sample): resample_kernel reads a whole row, resample_piece_kernel
+// Three entries, one function for a sample (resample_sample): resample_kernel reads a whole row, resample_piece_kernel
 // reads "carry | new piece" - the last K input samples of every row kept between the chunks of a chunked run, then the
-// chunk.  Both accumulate in fp32 with fmaf in ascending j from 0.0f, so a sample has the same bits whichever entry,
+// chunk -, resample_rows_kernel reads a whole row at the row's OWN plan (a rate per row).  All accumulate in fp32 with fmaf in ascending j from 0.0f, so a sample has the same bits whichever entry,
 // tile or input path (LDS, or straight from memory where the span does not fit) rendered it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -116,6 +116,68 @@ __global__ void resample_counts_kernel(const int *ylen, int hop, int n_all, int6
     n_out[b] = (int)((n * L + M - 1) / M);
 }
 
+// ---- a rate per row (include/vitsmi.h, "Output rate per row"): every row of one launch has a plan record of its own
+//
+// resample_rows_kernel is resample_kernel with the plan looked up by row: the workgroup reads its row's record, fills the
+// ResampleArgs a single-rate launch would have been given and runs resample_tile - so row b of a mixed launch is row b of
+// a launch at its rate alone, bit for bit, by construction.  A native row (no table) is a masked copy; a tile wholly behind
+// its row's end writes zeros and stages nothing.  Everything in front of resample_tile's __syncthreads is uniform over the
+// workgroup: it depends on blockIdx and on values indexed by it alone.
+struct ResampleRowPlan {
+    const float *table;  // nullptr: a native row, y = x
+    int Kp, K;
+    int64_t L, M;        // (a native row: 1, 1)
+    int span;            // LDS floats a tile of kResampleBlock samples stages; 0: read through L1 / L2
+};
+
+struct ResampleRowsArgs {
+    const ResampleRowPlan *plans;  // [B], on the device
+    const float *x;                // input samples [0, x_n) of row b at x + b * x_pitch
+    int64_t x_pitch;
+    int x_n;
+    const int *n_in, *n_out;       // [B], as in ResampleArgs
+    float *y;                      // [B][y_pitch]
+    int64_t y_pitch;
+    int n_hi;                      // S_out: the launch renders output samples [0, n_hi) of every row
+};
+
+__global__ void __launch_bounds__(kResampleBlock) resample_rows_kernel(ResampleRowsArgs r) {
+    const int b = blockIdx.y;
+    const ResampleRowPlan p = r.plans[b];
+    const int64_t n0 = (int64_t)blockIdx.x * blockDim.x, n = n0 + threadIdx.x;
+    const int64_t N = r.n_out[b];
+    if (n0 >= N || !p.table) {  // behind the row's end: zeros; a native row: its valid samples, zeros behind them
+        if (n < r.n_hi) r.y[(int64_t)b * r.y_pitch + n] = n < N ? r.x[(int64_t)b * r.x_pitch + n] : 0.f;
+        return;
+    }
+    ResampleArgs a{};
+    a.table = p.table;
+    a.Kp = p.Kp;
+    a.K = p.K;
+    a.L = p.L;
+    a.M = p.M;
+    a.x = r.x;
+    a.x_pitch = r.x_pitch;
+    a.x_n = r.x_n;
+    a.n_in = r.n_in;
+    a.n_out = r.n_out;
+    a.y = r.y;
+    a.y_pitch = r.y_pitch;
+    a.n_hi = r.n_hi;
+    a.span = p.span;
+    resample_tile<false>(a);
+}
+
+// resample_counts_kernel with every row's own L and M (a native row: n_out = n_in)
+__global__ void resample_rows_counts_kernel(const int *ylen, int hop, int n_all, const ResampleRowPlan *plans, int *n_in, int *n_out, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    int64_t n = ylen ? (int64_t)ylen[b] * hop : n_all;
+    n = n < 0 ? 0 : (n > n_all ? n_all : n);
+    n_in[b] = (int)n;
+    n_out[b] = (int)((n * plans[b].L + plans[b].M - 1) / plans[b].M);
+}
+
 // the carry behind a piece of x_n samples: the last K samples of "old carry | piece" (unmasked: readers mask by position)
 __global__ void resample_carry_kernel(const float *old, const float *x, int64_t x_pitch, int x_n, int K, float *nw) {
     const int b = blockIdx.y, q = blockIdx.x * blockDim.x + threadIdx.x;
@@ -148,6 +210,29 @@ inline hipError_t launch_resample(ResampleArgs a, int B, bool piece, hipStream_t
     const dim3 grid((unsigned)(((int64_t)a.n_hi - a.n_lo + block - 1) / block), (unsigned)B);
     if (piece) resample_piece_kernel<<<grid, block, (size_t)span * sizeof(float), st>>>(a);
     else resample_kernel<<<grid, block, (size_t)span * sizeof(float), st>>>(a);
+    return hipGetLastError();
+}
+
+// The record of a row at plan d (nullptr: a native row).  The block size is uniform over a rows launch, so a plan whose
+// kResampleBlock-sample span exceeds what a workgroup may stage is read unstaged: it does not shrink the block.
+inline ResampleRowPlan resample_row_plan(const ResampleDev *d) {
+    ResampleRowPlan r{nullptr, 0, 0, 1, 1, 0};
+    if (!d) return r;
+    r.table = d->table;
+    r.Kp = d->Kp;
+    r.K = (int)d->plan.K;
+    r.L = d->plan.L;
+    r.M = d->plan.M;
+    const int64_t span = (int64_t)(kResampleBlock - 1) * r.M / r.L + 2 + r.K;
+    r.span = span > kResampleLdsFloats ? 0 : (int)span;
+    return r;
+}
+
+// launch the rows entry over output samples [0, r.n_hi) of B rows; lds_floats: the largest span among the rows' records
+inline hipError_t launch_resample_rows(const ResampleRowsArgs &r, int B, int lds_floats, hipStream_t st) {
+    if (B <= 0 || r.n_hi <= 0) return hipSuccess;
+    const dim3 grid((unsigned)(((int64_t)r.n_hi + kResampleBlock - 1) / kResampleBlock), (unsigned)B);
+    resample_rows_kernel<<<grid, kResampleBlock, (size_t)lds_floats * sizeof(float), st>>>(r);
     return hipGetLastError();
 }
 

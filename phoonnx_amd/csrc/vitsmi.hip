@@ -132,7 +132,23 @@ struct vits_handle {
     int *d_nout = nullptr;
     int rs_run_K = 0;
     int64_t rs_run_L = 1, rs_run_M = 1;  // ... and the ratio its sample counts follow (vits_deliver's valid lengths)
-    bool last_vocoder = false;           // the last run was vocoder-only: every row has F frames, h_ylen is not its
+    // A rate per row (vits_set_output_rates): the rows' rates as given, the distinct plans among them - at most
+    // VITS_MAX_ROW_RATES, each with its table on a device handle - and on the device one plan record per row.  rows.on()
+    // excludes rs.plan.on().  A run under it whose rows are not all native goes through the same buffers as one at a handle
+    // rate (out_resampled, d_nout, rs_run_K: the largest K); run_rates / run_L / run_M describe the rows of that run, and of
+    // an all-native one, and are empty after every other run.
+    struct RowRates {
+        int fi = 0;
+        std::vector<int32_t> fo;         // [n_rows]; 0 or fi: native
+        std::vector<int> plan_of;        // [n_rows] index into plans; -1: native
+        std::vector<ResampleDev> plans;  // keyed by (fi, fo)
+        ResampleRowPlan *d_recs = nullptr;
+        int lds = 0;                     // the largest staged span among the plans
+        bool on() const { return !fo.empty(); }
+    } rows;
+    std::vector<int32_t> run_rates;
+    std::vector<int64_t> run_L, run_M;
+    bool last_vocoder = false;          // the last run was vocoder-only: every row has F frames, h_ylen is not its
 };
 
 // chunked rendering (vits_run_chunked / vits_run_vocoder_chunked): where the audio goes
@@ -261,6 +277,24 @@ void forget_results_in(vits_handle *h, const Slab &s) {
         h->d_nout = nullptr;
         h->out_resampled = false;
     }
+}
+
+// a run that begins is not (yet) one with a rate per row
+void forget_row_run(vits_handle *h) {
+    h->run_rates.clear();
+    h->run_L.clear();
+    h->run_M.clear();
+}
+
+// With a rate per row set (vits_set_output_rates), what an entry must meet before anything is staged or enqueued - the
+// previous run stays readable: the chunked entries and the device-pointer entries (`uncovered`: the entry's name) are not
+// covered, and a run has exactly the rows that were named.
+int row_rates_admit(vits_handle *h, int B, const char *uncovered) {
+    if (!h->rows.on()) return 0;
+    if (uncovered) return fail(h, VITS_E_ARG, "%s is not covered with per-row output rates", uncovered);
+    if (B != (int)h->rows.fo.size())
+        return fail(h, VITS_E_ARG, "a run of B = %d rows, vits_set_output_rates named %d rows", B, (int)h->rows.fo.size());
+    return 0;
 }
 
 int slab_reserve(vits_handle *h, Slab &s, size_t bytes, bool slack = true) {
@@ -1922,6 +1956,61 @@ int resample_run(vits_handle *h, const int *ylen, int B) {
     return 0;
 }
 
+// The same with a rate per row (vits_set_output_rates; B == the rows named, checked before the run began): [B][S_out],
+// S_out = max_b N_b, through resample_rows_kernel.  The rows' counts are known on the host (h_ylen; no frame counts: all), so
+// S_out is exact.  A run whose rows are all native launches nothing and leaves the native waveform where it is.
+int resample_rows_run(vits_handle *h, const int *ylen, int B) {
+    const auto &rw = h->rows;
+    const int S = h->S;
+    h->run_rates.assign(B, rw.fi);
+    h->run_L.assign(B, 1);
+    h->run_M.assign(B, 1);
+    int64_t so = 1;
+    int K = 0;
+    for (int b = 0; b < B; b++) {
+        int64_t n = ylen ? (int64_t)h->h_ylen[b] * h->model.hop : S;
+        n = n < 0 ? 0 : (n > S ? S : n);
+        if (rw.plan_of[b] >= 0) {
+            const ResamplePlan &p = rw.plans[rw.plan_of[b]].plan;
+            h->run_rates[b] = p.fo;
+            h->run_L[b] = p.L;
+            h->run_M[b] = p.M;
+            K = p.K > K ? (int)p.K : K;
+            n = p.count(n);
+            if (n > INT_MAX) {
+                forget_row_run(h);
+                return fail(h, VITS_E_ARG, "row %d: its samples are %lld samples at %d Hz: more than a row admits (%d)", b, (long long)n, p.fo, INT_MAX);
+            }
+        }
+        so = n > so ? n : so;
+    }
+    if (K == 0) return 0;  // every row native
+    const int S_out = (int)so;
+    ResampleBufs rb;
+    if (int rc = slab_carve(h, h->io, "staging", [&](Carver &cv) { rb = carve_resample(cv, B, S_out, K); })) return rc;
+    hipStream_t st = h->stream;
+    resample_rows_counts_kernel<<<(B + 63) / 64, 64, 0, st>>>(ylen, h->model.hop, S, rw.d_recs, rb.n_in, rb.n_out, B);
+    ResampleRowsArgs r{};
+    r.plans = rw.d_recs;
+    r.x = h->d_out;
+    r.x_pitch = S;
+    r.x_n = S;
+    r.n_in = rb.n_in;
+    r.n_out = rb.n_out;
+    r.y = rb.out;
+    r.y_pitch = S_out;
+    r.n_hi = S_out;
+    const hipError_t e = launch_resample_rows(r, B, rw.lds, st);
+    if (e != hipSuccess) return fail(h, VITS_E_DEVICE, "resampler launch failed: %s", hipGetErrorString(e));
+    h->stats.total_launches += 2;
+    h->d_out = rb.out;
+    h->S = S_out;
+    h->d_nout = rb.n_out;
+    h->rs_run_K = K;
+    h->out_resampled = true;
+    return 0;
+}
+
 // The two pinned buffers (vits_handle::ring) finished pieces reach the host through.  A piece is copied into slot(); queue()
 // records the slot's event, hands the piece queued before it to the caller - whose callback so runs while this one renders -
 // and moves on to the other slot.  A piece that delivers nothing is never queued and the ring does not move: the pending slot,
@@ -2422,6 +2511,8 @@ int vits_open_opts(const char *p, const vits_open_options *o, vits_handle **out)
                        o->layout_only != 0, o->gen_precision);
 }
 
+static void row_rates_drop(vits_handle *h, const vits_handle::RowRates *keep = nullptr);
+
 void vits_close(vits_handle *h) {
     if (!h) return;
     if (!h->host_only) {
@@ -2434,6 +2525,7 @@ void vits_close(vits_handle *h) {
         if (h->frm.base) hipFree(h->frm.base);
         if (h->io.base) hipFree(h->io.base);
         if (h->rs.table) hipFree(h->rs.table);
+        row_rates_drop(h);
         if (h->pin.base) hipHostFree(h->pin.base);
         if (h->d_range) hipFree(h->d_range);
         if (h->h_range) hipHostFree(h->h_range);
@@ -2521,17 +2613,150 @@ int vits_set_tails(vits_handle *h, int reference) {
     return VITS_OK;
 }
 
+// the rate a handle's voice renders at: in_rate, or (<= 0) the file's "sample_rate" metadata, 22050 without it
+static int native_rate(vits_handle *h, int in_rate) {
+    if (in_rate > 0) return in_rate;
+    auto it = h->model.meta.find("sample_rate");
+    return it != h->model.meta.end() ? std::atoi(it->second.c_str()) : 22050;
+}
+
+// a plan's table on the handle's device, rows padded to whole 16 bytes
+static int resample_table_upload(vits_handle *h, ResampleDev &d) {
+    d.Kp = resample_pitch(d.plan);
+    std::vector<float> t((size_t)d.plan.L * d.Kp);
+    resample_table(d.plan, t.data(), d.Kp);
+    if (hipSetDevice(h->device) != hipSuccess) return fail(h, VITS_E_DEVICE, "hipSetDevice(%d) failed", h->device);
+    if (hipMalloc((void **)&d.table, t.size() * sizeof(float)) != hipSuccess) {
+        (void)hipGetLastError();
+        d.table = nullptr;
+        return fail(h, VITS_E_NOMEM, "cannot place the %zu-byte resampling table on device %d", t.size() * sizeof(float), h->device);
+    }
+    if (hipMemcpy(d.table, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+        hipFree(d.table);
+        d.table = nullptr;
+        return fail(h, VITS_E_DEVICE, "cannot copy the resampling table to device %d", h->device);
+    }
+    return 0;
+}
+
+// Drop the handle's row rates: the tables that `keep` (the setting that replaces them) did not take over, and the records.
+// A run that reads them may still be in flight.
+static void row_rates_drop(vits_handle *h, const vits_handle::RowRates *keep) {
+    auto &old = h->rows;
+    bool synced = false;
+    auto sync = [&] {
+        if (synced) return;
+        hipSetDevice(h->device);
+        hipStreamSynchronize(h->stream);
+        synced = true;
+    };
+    for (auto &d : old.plans) {
+        if (!d.table) continue;
+        bool kept = false;
+        for (size_t i = 0; keep && i < keep->plans.size(); i++) kept = kept || keep->plans[i].table == d.table;
+        if (kept) continue;
+        sync();
+        hipFree(d.table);
+    }
+    if (old.d_recs) {
+        sync();
+        hipFree(old.d_recs);
+    }
+    old = vits_handle::RowRates{};
+}
+
+int vits_set_output_rates(vits_handle *h, int in_rate, const int32_t *out_rates, int n_rows) {
+    if (!h) return VITS_E_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (n_rows < 0) return fail(h, VITS_E_ARG, "n_rows = %d is negative", n_rows);
+    if (!out_rates || n_rows == 0) {  // clear: the row rates alone
+        row_rates_drop(h);
+        return VITS_OK;
+    }
+    vits_handle::RowRates nw;
+    nw.fi = native_rate(h, in_rate);
+    if (nw.fi < 1 || nw.fi > kResampleMaxRate) return fail(h, VITS_E_ARG, "sample rate %d outside [1, %d]", nw.fi, kResampleMaxRate);
+    nw.fo.assign(out_rates, out_rates + n_rows);
+    nw.plan_of.assign(n_rows, -1);
+    // everything is validated before anything is allocated
+    for (int b = 0; b < n_rows; b++) {
+        const int fo = out_rates[b];
+        if (fo < 0) return fail(h, VITS_E_ARG, "row %d: output rate %d is negative", b, fo);
+        if (fo == 0 || fo == nw.fi) continue;  // native
+        int k = 0;
+        while (k < (int)nw.plans.size() && nw.plans[k].plan.fo != fo) k++;
+        if (k == (int)nw.plans.size()) {
+            if (k == VITS_MAX_ROW_RATES)
+                return fail(h, VITS_E_ARG, "row %d: %d Hz is resampling rate number %d of this run; at most %d distinct ones are admitted "
+                                           "(VITS_MAX_ROW_RATES)", b, fo, k + 1, VITS_MAX_ROW_RATES);
+            ResampleDev d;
+            const std::string e = resample_plan(nw.fi, fo, d.plan);
+            if (!e.empty()) return fail(h, VITS_E_ARG, "row %d: %s", b, e.c_str());
+            nw.plans.push_back(d);
+        }
+        nw.plan_of[b] = k;
+    }
+    if (!h->host_only) {
+        // the tables: those of the setting in place are taken over, keyed by (fi, fo)
+        std::vector<char> own(nw.plans.size(), 0);
+        int rc = 0;
+        for (size_t k = 0; k < nw.plans.size() && !rc; k++) {
+            ResampleDev &d = nw.plans[k];
+            for (const ResampleDev &o : h->rows.plans)
+                if (o.table && o.plan.fi == d.plan.fi && o.plan.fo == d.plan.fo) {
+                    d.table = o.table;
+                    d.Kp = o.Kp;
+                }
+            if (d.table) continue;
+            rc = resample_table_upload(h, d);
+            own[k] = rc == 0;
+        }
+        std::vector<ResampleRowPlan> recs((size_t)n_rows);
+        for (int b = 0; b < n_rows && !rc; b++) {
+            recs[b] = resample_row_plan(nw.plan_of[b] >= 0 ? &nw.plans[nw.plan_of[b]] : nullptr);
+            nw.lds = recs[b].span > nw.lds ? recs[b].span : nw.lds;
+        }
+        if (!rc && (hipSetDevice(h->device) != hipSuccess || hipMalloc((void **)&nw.d_recs, recs.size() * sizeof recs[0]) != hipSuccess)) {
+            (void)hipGetLastError();
+            nw.d_recs = nullptr;
+            rc = fail(h, VITS_E_NOMEM, "cannot place %d plan records on device %d", n_rows, h->device);
+        }
+        if (!rc && hipMemcpy(nw.d_recs, recs.data(), recs.size() * sizeof recs[0], hipMemcpyHostToDevice) != hipSuccess)
+            rc = fail(h, VITS_E_DEVICE, "cannot copy the plan records to device %d", h->device);
+        if (rc) {  // refused: the previous setting stays in place
+            for (size_t k = 0; k < nw.plans.size(); k++)
+                if (own[k]) hipFree(nw.plans[k].table);
+            if (nw.d_recs) hipFree(nw.d_recs);
+            return rc;
+        }
+    }
+    if (h->rs.table) {  // it replaces a handle rate (a run that reads the old table may still be in flight)
+        hipSetDevice(h->device);
+        hipStreamSynchronize(h->stream);
+        hipFree(h->rs.table);
+    }
+    h->rs = ResampleDev{};
+    row_rates_drop(h, &nw);
+    h->rows = nw;
+    return VITS_OK;
+}
+
+int vits_last_sample_rates(vits_handle *h, int32_t *buf, int n) {
+    if (!h) return VITS_E_ARG;
+    const int B = h->last_vocoder ? h->B : (int)h->h_ylen.size();
+    const bool rows = (int)h->run_rates.size() == B;
+    const int one = h->rs.plan.on() ? h->rs.plan.fo : native_rate(h, 0);
+    for (int b = 0; b < B && b < n && buf; b++) buf[b] = rows ? h->run_rates[b] : one;
+    return B;
+}
+
 int vits_set_output_rate(vits_handle *h, int in_rate, int out_rate) {
     if (!h) return VITS_E_ARG;
     std::lock_guard<std::mutex> lk(h->mu);
     if (out_rate < 0) return fail(h, VITS_E_ARG, "output rate %d is negative", out_rate);
     ResampleDev nw;  // (off)
     if (out_rate != 0) {
-        int fi = in_rate;
-        if (fi <= 0) {
-            auto it = h->model.meta.find("sample_rate");
-            fi = it != h->model.meta.end() ? std::atoi(it->second.c_str()) : 22050;
-        }
+        const int fi = native_rate(h, in_rate);
         ResamplePlan p;
         const std::string e = resample_plan(fi, out_rate, p);
         if (!e.empty()) return fail(h, VITS_E_ARG, "%s", e.c_str());
@@ -2557,6 +2782,7 @@ int vits_set_output_rate(vits_handle *h, int in_rate, int out_rate) {
         hipFree(h->rs.table);
     }
     h->rs = nw;
+    row_rates_drop(h);  // (a handle rate, or none, replaces a rate per row)
     return VITS_OK;
 }
 
@@ -2564,9 +2790,10 @@ int vits_last_sample_counts(vits_handle *h, int64_t *buf, int n) {
     if (!h) return VITS_E_ARG;
     const int B = (int)h->h_ylen.size();
     const int64_t hop = h->model.hop;
+    const bool rows = !h->last_vocoder && (int)h->run_L.size() == B;  // the last run had a rate per row: at ITS rates
     for (int b = 0; b < B && b < n && buf; b++) {
         const int64_t s = (int64_t)h->h_ylen[b] * hop;
-        buf[b] = h->rs.plan.on() ? h->rs.plan.count(s) : s;
+        buf[b] = rows ? (s * h->run_L[b] + h->run_M[b] - 1) / h->run_M[b] : h->rs.plan.on() ? h->rs.plan.count(s) : s;
     }
     return B;
 }
@@ -2629,6 +2856,21 @@ int vits_reserve(vits_handle *h, int B, int T, int F) {
             // an encoded stream's buffers)
             const size_t io_rt = carved_bytes([&](Carver &cv) {
                 const DeliveryBufs front = carve_resample(cv, B, (int)so, (int)h->rs.plan.K).dlv;
+                carve_delivery_call(cv, B, (int)so, all, &front);
+            });
+            io = io_rt > io ? io_rt : io;
+        }
+        if (!h->rows.plans.empty()) {  // ... or the same at a rate per row: the longest row any plan that is set makes, the largest K
+            int64_t so = (int64_t)F * m.hop;
+            int K = 0;
+            for (const ResampleDev &d : h->rows.plans) {
+                const int64_t c = d.plan.count((int64_t)F * m.hop);
+                if (c > INT_MAX) return fail(h, VITS_E_ARG, "vits_reserve: F=%d frames are %lld samples at %d Hz", F, (long long)c, d.plan.fo);
+                so = c > so ? c : so;
+                K = d.plan.K > K ? (int)d.plan.K : K;
+            }
+            const size_t io_rt = carved_bytes([&](Carver &cv) {
+                const DeliveryBufs front = carve_resample(cv, B, (int)so, K).dlv;
                 carve_delivery_call(cv, B, (int)so, all, &front);
             });
             io = io_rt > io ? io_rt : io;
@@ -2713,6 +2955,7 @@ static int run_device_locked(vits_handle *h, const int64_t *ids, const int64_t *
     h->T = T;
     h->range_failed = false;
     h->out_resampled = false;
+    forget_row_run(h);
     h->last_vocoder = false;
     uint64_t seed = noise ? noise->seed : 0;
     seed = seed * 0x9E3779B97F4A7C15ull + (++h->run_counter);
@@ -2725,6 +2968,8 @@ static int run_device_locked(vits_handle *h, const int64_t *ids, const int64_t *
         return rc;
     if (h->rs.plan.on() && !sink)
         if (int rc = resample_run(h, h->d_ylen, B)) return rc;
+    if (h->rows.on() && !sink)
+        if (int rc = resample_rows_run(h, h->d_ylen, B)) return rc;
     ylen_to_i64<<<(B + 63) / 64, 64, 0, h->stream>>>(h->d_ylen, h->d_ylen64, B);
     range_end(h);
     if (out) {
@@ -2744,6 +2989,7 @@ int vits_run_device(vits_handle *h, const int64_t *ids, const int64_t *lens, int
     std::lock_guard<std::mutex> lk(h->mu);
     if (!out) return fail(h, VITS_E_ARG, "null argument");
     if (h->rs.plan.on()) return fail(h, VITS_E_ARG, "vits_run_device is not covered with an output rate set");
+    if (int rc = row_rates_admit(h, B, "vits_run_device")) return rc;
     return run_device_locked(h, ids, lens, B, T, one_row(scales), sid, noise, out);
 }
 
@@ -2753,6 +2999,7 @@ int vits_run_device_rows(vits_handle *h, const int64_t *ids, const int64_t *lens
     std::lock_guard<std::mutex> lk(h->mu);
     if (!out) return fail(h, VITS_E_ARG, "null argument");
     if (h->rs.plan.on()) return fail(h, VITS_E_ARG, "vits_run_device_rows is not covered with an output rate set");
+    if (int rc = row_rates_admit(h, B, "vits_run_device_rows")) return rc;
     RunRows rr;
     if (int rc = host_rows(h, scales, B, seeds, rr)) return rc;
     return run_device_locked(h, ids, lens, B, T, rr, sid, noise, out);
@@ -2866,6 +3113,7 @@ static int stage_inputs(vits_handle *h, const int64_t *ids, const int64_t *lens,
 static int run_async_locked(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const RunRows &rr,
                             const int64_t *sid, const vits_noise *noise, vits_output *dev) {
     if (!rr.scales) return fail(h, VITS_E_ARG, "null argument");
+    if (int rc = row_rates_admit(h, B, nullptr)) return rc;
     Staged sg;
     int rc = stage_inputs(h, ids, lens, B, T, sid, noise, sg);
     if (rc == VITS_OK) rc = run_device_locked(h, sg.d_ids, sg.d_lens, B, T, rr, sg.d_sid, sg.has_noise ? &sg.dn : nullptr, dev);
@@ -2931,6 +3179,7 @@ int vits_run(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int
 static int run_chunked_sink(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const RunRows &rr,
                             const int64_t *sid, const vits_noise *noise, const ChunkSink &sink) {
     if (!rr.scales || sink.chunk_frames < 1) return fail(h, VITS_E_ARG, "bad chunked-run arguments");
+    if (int rc = row_rates_admit(h, B, "a chunked run")) return rc;
     Staged sg;
     int rc = stage_inputs(h, ids, lens, B, T, sid, noise, sg);
     if (rc == VITS_OK)
@@ -3233,7 +3482,8 @@ static int delivery_counts(vits_handle *h, std::vector<int64_t> &counts) {
     counts.resize(B);
     for (int b = 0; b < B; b++) {
         const int64_t n = (int64_t)(h->last_vocoder ? h->F : h->h_ylen[b]) * h->model.hop;
-        counts[b] = h->out_resampled ? (n * h->rs_run_L + h->rs_run_M - 1) / h->rs_run_M : n;
+        if ((int)h->run_L.size() == B) counts[b] = (n * h->run_L[b] + h->run_M[b] - 1) / h->run_M[b];  // (a rate per row)
+        else counts[b] = h->out_resampled ? (n * h->rs_run_L + h->rs_run_M - 1) / h->rs_run_M : n;
         if (counts[b] > S) return fail(h, VITS_E_ARG, "no completed run to deliver (row %d: %lld samples of %d)", b, (long long)counts[b], S);
     }
     return 0;
@@ -3252,6 +3502,11 @@ static int deliver_last_run(vits_handle *h, const DeliveryRequest &rq, const Del
     auto bufs = [&](const DeliveryNeeds &need, const float *&d_x, DeliveryCallBufs &cb) -> DeliveryStatus {
         if (need.levelled && h->rs.plan.on() && rq.sample_rate != h->rs.plan.fo)
             return delivery_refusal(VITS_E_ARG, "sample_rate %d differs from the output rate %d", rq.sample_rate, (int)h->rs.plan.fo);
+        // (a run with a rate per row: the loudness filter of a call is one rate's, so every levelled segment's row must be at it)
+        for (int g = 0; need.levelled && (int)h->run_rates.size() == B && g < rq.n_segs; g++)
+            if (rq.levels[g].mode != 0 && h->run_rates[rq.segs[g].row] != rq.sample_rate)
+                return delivery_refusal(VITS_E_ARG, "segment %d: sample_rate %d differs from the rate %d its row %d was delivered at", g,
+                                        rq.sample_rate, (int)h->run_rates[rq.segs[g].row], (int)rq.segs[g].row);
         // the staging slab is idle between runs; a resampled waveform lives in it, and its walk carved these buffers behind it
         if (h->out_resampled) {
             // (the run's own walk ends with carve_resample, or with an encoded stream's buffers behind it; the trim slots behind
@@ -3347,6 +3602,7 @@ static int vocoder_common(vits_handle *h, const float *z, int B, int F, const in
                           const ChunkSink *sink) {
     const Model &m = h->model;
     if (!z || (!out && !sink) || B <= 0 || F <= 0) return fail(h, VITS_E_ARG, "bad vocoder arguments");
+    if (int rc = row_rates_admit(h, B, sink ? "a chunked vocoder run" : nullptr)) return rc;
     if (m.gin && !sid) return fail(h, VITS_E_ARG, "Missing speaker id");
     for (int b = 0; sid && m.gin && b < B; b++)
         if (sid[b] < 0 || sid[b] >= m.n_speakers)
@@ -3375,6 +3631,7 @@ static int vocoder_common(vits_handle *h, const float *z, int B, int F, const in
     h->B = B;
     h->F = F;
     h->out_resampled = false;
+    forget_row_run(h);
     h->last_vocoder = true;
     h->d_ylen = nullptr;  // (no frame counts: vits_last_pcm16 does not apply to a vocoder-only run)
     h->h_dur_B = h->h_dur_T = 0;  // (no tokens: vits_last_durations has nothing to report)
@@ -3386,6 +3643,8 @@ static int vocoder_common(vits_handle *h, const float *z, int B, int F, const in
     if (c.err != hipSuccess) return fail(h, VITS_E_DEVICE, "kernel launch failed: %s", hipGetErrorString(c.err));
     if (h->rs.plan.on() && !sink)
         if (int rc2 = resample_run(h, nullptr, B)) return rc2;
+    if (h->rows.on() && !sink)
+        if (int rc2 = resample_rows_run(h, nullptr, B)) return rc2;
     range_end(h);
     if (sink) {
         HIPCHECK(h, hipStreamSynchronize(st));
@@ -4225,6 +4484,71 @@ int vits_test_resample(int device_id, const float *x, const int64_t *lens, int B
     a.y_pitch = S_out;
     a.n_hi = (int)S_out;
     TCHECK(launch_resample(a, B, /*piece=*/false, nullptr));
+    TCHECK(hipDeviceSynchronize());
+    TCHECK(download(y, dy, (size_t)B * S_out));
+    return VITS_OK;
+}
+
+// The rows entry by value: the plans of the distinct rates among out_rates (0 or in_rate: a native row), one record per row,
+// one launch.  y is [B][S_out], S_out = max_b n_out[b].
+int vits_test_resample_rows(int device_id, const float *x, const int64_t *lens, int B, int S, int in_rate, const int32_t *out_rates,
+                            float *y, size_t y_elems, int64_t *n_out) {
+    if (int rc = test_dev(device_id)) return rc;
+    if (!x || !y || !lens || !out_rates || !n_out || B <= 0 || S <= 0) return fail(nullptr, VITS_E_ARG, "bad resampler test arguments");
+    DevBufs D;
+    std::vector<ResampleDev> plans;
+    std::vector<ResampleRowPlan> recs((size_t)B);
+    std::vector<int> n_in(B), no(B);
+    int64_t S_out = 0;
+    int lds = 0;
+    for (int b = 0; b < B; b++) {
+        const int fo = out_rates[b];
+        if (fo < 0) return fail(nullptr, VITS_E_ARG, "row %d: output rate %d is negative", b, fo);
+        const int64_t n = lens[b] < 0 ? 0 : (lens[b] > S ? S : lens[b]);
+        int64_t N = n;
+        if (fo != 0 && fo != in_rate) {
+            size_t k = 0;
+            while (k < plans.size() && plans[k].plan.fo != fo) k++;
+            if (k == plans.size()) {
+                if (k == VITS_MAX_ROW_RATES) return fail(nullptr, VITS_E_ARG, "row %d: more than %d distinct resampling rates", b, VITS_MAX_ROW_RATES);
+                ResampleDev d;
+                const std::string e = resample_plan(in_rate, fo, d.plan);
+                if (!e.empty()) return fail(nullptr, VITS_E_ARG, "row %d: %s", b, e.c_str());
+                d.Kp = resample_pitch(d.plan);
+                std::vector<float> tab((size_t)d.plan.L * d.Kp);
+                resample_table(d.plan, tab.data(), d.Kp);
+                d.table = D.up(tab.data(), tab.size());
+                plans.push_back(d);
+            }
+            recs[b] = resample_row_plan(&plans[k]);
+            N = plans[k].plan.count(n);
+            if (N > INT_MAX) return fail(nullptr, VITS_E_ARG, "row %d: %lld samples at %d Hz", b, (long long)N, fo);
+        } else {
+            recs[b] = resample_row_plan(nullptr);
+        }
+        lds = recs[b].span > lds ? recs[b].span : lds;
+        n_in[b] = (int)n;
+        no[b] = (int)N;
+        n_out[b] = N;
+        S_out = N > S_out ? N : S_out;
+    }
+    if (y_elems < (size_t)B * (size_t)S_out)
+        return fail(nullptr, VITS_E_ARG, "y holds %zu elements, %d rows of %lld need %zu", y_elems, B, (long long)S_out, (size_t)B * (size_t)S_out);
+    if (S_out == 0) return VITS_OK;
+    float *dx = D.up(x, (size_t)B * S);
+    float *dy = D.fill<float>((size_t)B * S_out, 0xff);
+    ResampleRowsArgs r{};
+    r.plans = D.up(recs.data(), recs.size());
+    r.x = dx;
+    r.x_pitch = S;
+    r.x_n = S;
+    r.n_in = D.up(n_in.data(), (size_t)B);
+    r.n_out = D.up(no.data(), (size_t)B);
+    r.y = dy;
+    r.y_pitch = S_out;
+    r.n_hi = (int)S_out;
+    TCHECK(D.err);
+    TCHECK(launch_resample_rows(r, B, lds, nullptr));
     TCHECK(hipDeviceSynchronize());
     TCHECK(download(y, dy, (size_t)B * S_out));
     return VITS_OK;

@@ -334,7 +334,8 @@ inline LimitBufs carve_limit(Carver &cv, int B, int S) {
 // the resampled fp32 waveform [B][S_out] (a chunked run: the output samples of one chunk, never more than S_out per
 // row), the rows' valid input and output sample counts, the two generations of the chunked path's carry [B][K] (the
 // last K input samples of every row; one is read while the other is written), and behind them vits_last_pcm16's buffers
-// and then vits_deliver's for that waveform - one walk, so that converting or delivering it never moves it.
+// and then vits_deliver's for that waveform - one walk, so that converting or delivering it never moves it.  With a rate per
+// row (vits_set_output_rates) it is the same walk: S_out is the longest row's count, K the largest among the rows' plans.
 struct ResampleBufs {
     float *out;
     int *n_in, *n_out;

@@ -8,6 +8,7 @@ It duck-types exactly the three calls the reference makes:
 and forwards them over the C ABI (include/vitsmi.h) to the gfx950 engine.  There is no CPU
 fallback: without libvitsmi.so + an MI355X this raises.
 """
+import contextlib
 import ctypes as C
 import dataclasses
 import time
@@ -237,10 +238,22 @@ def resample_plan(in_rate: int, out_rate: int, table: bool = False):
     return L.value, M.value, K.value, h
 
 
-def output_sample_counts(n_samples, in_rate: int, out_rate: int) -> np.ndarray:
-    """ceil(n * L / M): the output samples of rows of n valid input samples (what last_sample_counts() reports per row)."""
-    L, M, _ = resample_plan(in_rate, out_rate)
-    return -(-np.asarray(n_samples, np.int64) * L // M)
+def output_sample_counts(n_samples, in_rate: int, out_rate) -> np.ndarray:
+    """ceil(n * L / M): the output samples of rows of n valid input samples (what last_sample_counts() reports per row).
+    out_rate: one rate, or one per row of n_samples (vitsmi.h, "output rate per row"; None, 0 or in_rate: a native row)."""
+    n = np.asarray(n_samples, np.int64)
+    if np.ndim(out_rate) == 0 and out_rate is not None:
+        L, M, _ = resample_plan(in_rate, out_rate)
+        return -(-n * L // M)
+    rates = [in_rate] * n.size if out_rate is None else list(out_rate)
+    if n.ndim != 1 or len(rates) != n.shape[0]:
+        raise SessionError(f"output_sample_counts: {len(rates)} rates for rows of shape {n.shape}")
+    out = n.copy()
+    for b, r in enumerate(rates):
+        if r not in (None, 0, in_rate):
+            L, M, _ = resample_plan(in_rate, int(r))
+            out[b] = -(-int(n[b]) * L // M)
+    return out
 
 
 @dataclass
@@ -528,13 +541,15 @@ def token_bounds(durations, n_tokens, hop, count, ratio=None) -> np.ndarray:
 
 def token_gain_shapes(segments, shapes, gains, bounds, ramp):
     """The shapes of a delivery with every segment's points set from the token gains of its row: gains float32 [B][T],
-    bounds one token_bounds per row, ramp in samples.  A segment that already has points is refused."""
+    bounds one token_bounds per row, ramp in samples - one value, or one per row where the rows are at rates of their own.
+    A segment that already has points is refused."""
     out = []
     for i, (g, sh) in enumerate(zip(segments, shapes)):
         if len(sh.points):
             raise SessionError(f"segment {i}: token_gain_db and explicit points on the same segment")
         bd = bounds[int(g.row)]          # (a row's own tokens, or the padded row's: what lies behind them has no samples)
-        out.append(dataclasses.replace(sh, points=token_envelope(bd, gains[int(g.row)][:len(bd) - 1], ramp)))
+        rp = ramp[int(g.row)] if np.ndim(ramp) else ramp
+        out.append(dataclasses.replace(sh, points=token_envelope(bd, gains[int(g.row)][:len(bd) - 1], rp)))
     return out
 
 
@@ -861,6 +876,7 @@ class MiSession:
             raise SessionError(f"output_rate must be None or a positive integer (got {output_rate!r})")
         self.output_rate = None if output_rate is None else int(output_rate)
         self.input_rate = None   # (None: the file's sample_rate metadata)
+        self.output_rates = None  # (set_output_rates: a rate per row, in the place of output_rate)
         self._seed = 0
         self.range_fallbacks = 0  # times this session reopened itself with bf16x6 after a RangeError (stats())
         self._open(gen_precision)
@@ -888,6 +904,13 @@ class MiSession:
                 msg = self._err()
                 self.close()
                 raise SessionError(f"vits_set_output_rate({self.input_rate}, {self.output_rate}) failed [{rc}]: {msg}")
+        if self.output_rates is not None:  # (a reopened session keeps its row rates)
+            arr = np.asarray(self.output_rates, np.int32)
+            rc = self._lib.vits_set_output_rates(self._h, self.input_rate or 0, _ffi.ptr(arr), arr.size)
+            if rc != 0:
+                msg = self._err()
+                self.close()
+                raise SessionError(f"vits_set_output_rates({self.input_rate}, {self.output_rates}) failed [{rc}]: {msg}")
         n = self._lib.vits_num_inputs(self._h)
         self._input_names = [self._lib.vits_input_name(self._h, i).decode() for i in range(n)]
 
@@ -1009,8 +1032,10 @@ class MiSession:
         self._seed = int(seed)
 
     def synthesize_batch(self, ids, lens, scales, sid=None, noise_dp=None, noise_z=None, taps=(), seeds=None,
-                         durations=None, token_rate=None, return_durations=False):
+                         durations=None, token_rate=None, return_durations=False, output_rates=None):
         """One batched run.  Returns {"output": [B,1,1,S] float32, "y_lengths": int64 [B], taps...}.
+        output_rates: None, or a rate per row for this call (set_output_rates; what was set before is put back afterwards);
+        with row rates the result also holds "sample_rates" (int32 [B]).
         With an output rate set (set_output_rate) "output" is the resampled waveform [B,1,1,S_out] and "sample_lengths"
         (int64 [B]) holds each row's valid samples at that rate; "y_lengths" stay frames.
         noise_dp [B,2,T] / noise_z [B,inter,>=F] inject the graph's noise for parity runs.
@@ -1024,12 +1049,13 @@ class MiSession:
         ids, lens, scales, sid, noise_dp, noise_z, noise, seeds, durations, token_rate = self._run_arguments(
             ids, lens, scales, sid, noise_dp, noise_z, seeds, durations, token_rate)
         B = ids.shape[0]
-        with self._locked():  # enqueue -> frame counts -> copy-out -> taps all use this handle's one workspace
+        # enqueue -> frame counts -> copy-out -> taps all use this handle's one workspace
+        with self._locked(), self._rates_for_call(output_rates):
             try:
                 self._begin(ids, lens, scales, sid, noise, seeds, durations, token_rate)
                 ylen = self.last_y_lengths()
                 dur = self.last_durations() if return_durations else None
-                counts = self.last_sample_counts() if self.resampling else None
+                counts = self.last_sample_counts() if self.resampling or self.output_rates is not None else None
                 S = int(ylen.max()) * self.hparam("hop") if counts is None else int(counts.max())
                 audio = _POOL.array((B, 1, 1, S)) if self.pinned_results else np.empty((B, 1, 1, S), np.float32)
                 self._fetch(audio, 0, B)
@@ -1040,6 +1066,8 @@ class MiSession:
             res = {"output": audio, "y_lengths": ylen}
             if counts is not None:
                 res["sample_lengths"] = counts
+            if self.output_rates is not None:
+                res["sample_rates"] = self.last_sample_rates()
             if return_durations:
                 res["durations"] = dur
             for t in taps:
@@ -1464,6 +1492,69 @@ class MiSession:
                 self._raise("vits_set_output_rate", rc)
             self.output_rate = None if rate is None else int(rate)
             self.input_rate = None if input_rate is None else int(input_rate)
+            self.output_rates = None  # (a handle rate, or none, replaces a rate per row)
+
+    def set_output_rates(self, rates, input_rate: Optional[int] = None):
+        """Deliver row b of the following runs at rates[b] Hz (vitsmi.h, "output rate per row"): one entry per row of the
+        run - None, 0 or the input rate for a native row -, at most 8 distinct resampling rates.  Row b of such a run is row b
+        of the same run under set_output_rate(rates[b]), bit for bit.  It replaces set_output_rate's rate (and that call
+        replaces this); None clears it.  The following runs must have exactly len(rates) rows; the chunked entries
+        (stream*, synthesize_chunked) are refused while it is set.  A refused call leaves the previous setting in place."""
+        if input_rate is not None and (not isinstance(input_rate, (int, np.integer)) or input_rate <= 0):
+            raise SessionError(f"input rate must be None or a positive integer (got {input_rate!r})")
+        if rates is None:
+            with self._locked():
+                rc = self._lib.vits_set_output_rates(self._h, 0, None, 0)
+                if rc != 0:
+                    self._raise("vits_set_output_rates", rc)
+                self.output_rates = None
+            return
+        rates = list(rates)
+        for b, r in enumerate(rates):
+            if r is not None and (not isinstance(r, (int, np.integer)) or r < 0):
+                raise SessionError(f"row {b}: output rate must be None or an integer >= 0 (got {r!r})")
+        if not rates:
+            raise SessionError("output rates must be None or one rate per row (got none)")
+        arr = np.asarray([int(r or 0) for r in rates], np.int32)
+        with self._locked():
+            rc = self._lib.vits_set_output_rates(self._h, int(input_rate or 0), _ffi.ptr(arr), arr.size)
+            if rc != 0:
+                self._raise("vits_set_output_rates", rc)
+            self.output_rates = tuple(int(v) for v in arr)
+            self.output_rate = None
+            self.input_rate = None if input_rate is None else int(input_rate)
+
+    def last_sample_rates(self) -> np.ndarray:
+        """int32 [B]: the rate each row of the last run was delivered at (vits_last_sample_rates; host state)."""
+        with self._locked(read_only=True):
+            n = self._lib.vits_last_sample_rates(self._h, None, 0)
+            buf = np.zeros(max(n, 0), np.int32)
+            if n > 0:
+                self._lib.vits_last_sample_rates(self._h, _ffi.ptr(buf), n)
+            return buf
+
+    @contextlib.contextmanager
+    def _rates_for_call(self, output_rates):
+        """output_rates= of one call: set for it, then what was set before is put back (None: nothing happens)"""
+        if output_rates is None:
+            yield
+            return
+        before = (self.output_rate, self.output_rates, self.input_rate)
+        self.set_output_rates(output_rates, self.input_rate)
+        try:
+            yield
+        finally:
+            if before[1] is not None:
+                self.set_output_rates(before[1], before[2])
+            else:
+                self.set_output_rate(before[0], before[2])
+
+    def _row_ratios(self, B):
+        """(L, M) per row of a run under the rates that are set - None for a row that is not resampled"""
+        fi = self.input_rate or int(self.meta("sample_rate") or 22050)
+        if self.output_rates is not None:
+            return [None if r in (0, fi) else resample_plan(fi, r)[:2] for r in self.output_rates]
+        return [resample_plan(fi, self.output_rate)[:2] if self.resampling else None] * B
 
     @property
     def resampling(self) -> bool:
@@ -1660,6 +1751,11 @@ class MiSession:
             sarr, parr, n_points = _shapes(shapes, n)
             if levels is not None:  # (only a levelled delivery looks at the rate: 0 elsewhere, which nothing refuses)
                 rate = self.delivered_rate if sample_rate is None else int(sample_rate)
+                if sample_rate is None and self.output_rates is not None and segments:
+                    # (a rate per row: the rate of the first segment's row - the engine refuses a levelled segment at another)
+                    rates = self.last_sample_rates()
+                    if 0 <= int(segments[0].row) < rates.size:
+                        rate = int(rates[int(segments[0].row)])
             # (what the caller does not want back is not reported: NULL, the engine's own "none")
             if return_kept:
                 first, count = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
@@ -1710,7 +1806,7 @@ class MiSession:
     def synthesize_delivered(self, ids, lens, scales, sid=None, *, segments=None, n_streams=None, encoding="pcm16",
                              normalize=True, volume=1.0, seeds=None, durations=None, token_rate=None, noise_dp=None,
                              noise_z=None, return_durations=False, trim=None, levels=None, shapes=None, token_gain_db=None,
-                             gain_ramp=0.01, limits=None):
+                             gain_ramp=0.01, limits=None, output_rates=None):
         """One batched run and its delivery under one hold of the session lock: what leaves the GPU is the encoded audio
         of the plan and nothing else - the fp32 waveform is never copied to the host.  segments=None: one stream per row,
         with `normalize` / `volume` as scalars or [B] arrays (row b's own).  Everything in front of the delivery is
@@ -1724,6 +1820,11 @@ class MiSession:
         every change.  No second run, no waveform on the host.  A segment with explicit points AND token gains is refused.
         With either, the result holds "shapes": the Shape every segment was delivered with.
         limits - one Limit or one per segment (None in the list: off): deliver(..., limits=limits).
+        output_rates - None, or a rate per row for this call (set_output_rates; what was set before is put back afterwards).
+        With row rates set, by this argument or before, `encoding` may also be one name per segment; the run is then
+        delivered once per (rate, encoding) group of segments - a stream's segments must lie in one group -, every
+        sample-valued field (leads, Trim, Shape, Limit) is at its row's own rate, gain_ramp is converted at each row's rate,
+        and the result holds "sample_rates" (int32 [B]).
         Returns {"streams": [array per stream], "stream_samples": int64 [J], "y_lengths": int64 [B], "sample_lengths":
         int64 [B] (each row's valid samples at the delivered rate), "kept_first" / "kept_count": int64 [G] (what each
         segment delivers of its row: all of it without a trim)[, "durations"]}."""
@@ -1739,7 +1840,16 @@ class MiSession:
             segments = [Segment(b, b, 0, 1 if nz[b] else 0, float(vol[b])) for b in range(B)]
             n_streams = B
         segments = list(segments)
-        _encoding(encoding)
+        if isinstance(encoding, str):
+            _encoding(encoding)
+        else:
+            encoding = list(encoding)
+            if len(encoding) != len(segments):
+                raise SessionError(f"encoding must be one name or one per segment ({len(segments)}), got {len(encoding)}")
+            for e in encoding:
+                _encoding(e)
+            if output_rates is None and self.output_rates is None:
+                raise SessionError("an encoding per segment needs a rate per row (output_rates=, set_output_rates)")
         used = None
         if shapes is not None or token_gain_db is not None:
             used = [Shape()] * len(segments) if shapes is None else ([shapes] * len(segments) if isinstance(shapes, Shape) else list(shapes))
@@ -1753,16 +1863,20 @@ class MiSession:
             for i, sh in enumerate(used):
                 if len(sh.points):
                     raise SessionError(f"segment {i}: token_gain_db and explicit points on the same segment")
-        with self._locked():
+        with self._locked(), self._rates_for_call(output_rates):
             try:
                 self._begin(ids, lens, scales, sid, noise, seeds, durations, token_rate)
                 ylen = self.last_y_lengths()
                 dur = self.last_durations() if return_durations or tgains is not None else None
                 counts = self.last_sample_counts()
+                rates = self.last_sample_rates() if self.output_rates is not None else None
                 loud = gain = None
                 if tgains is not None:
                     used = self._token_shapes(segments, used, tgains, dur, lens, counts, gain_ramp)
-                if used is None and levels is None and trim is None and limits is None:
+                if rates is not None:
+                    streams, kept_first, kept_count, loud, gain = self._deliver_groups(segments, n_streams, encoding, rates, counts,
+                                                                                       trim, levels, used, limits)
+                elif used is None and levels is None and trim is None and limits is None:
                     streams = self.deliver(segments, n_streams, encoding)
                     kept_first = np.zeros(len(segments), np.int64)
                     kept_count = np.array([counts[int(g.row)] for g in segments], np.int64)
@@ -1782,20 +1896,78 @@ class MiSession:
                "sample_lengths": counts, "kept_first": kept_first, "kept_count": kept_count}
         if levels is not None:
             res["loudness"], res["gain"] = loud, gain
+        if rates is not None:
+            res["sample_rates"] = rates
         if used is not None:
             res["shapes"] = used
         if return_durations:
             res["durations"] = dur
         return res
 
+    def _deliver_groups(self, segments, n_streams, encoding, rates, counts, trims, levels, shapes, limits):
+        """The last run - one with a rate per row - delivered once per (rate, encoding) group of segments, in the order the
+        groups first appear: a levelled delivery measures at ONE rate and a delivery has one encoding.  Returns (streams [J],
+        kept_first [G], kept_count [G], loudness [G] or None, gain [G] or None) in the caller's numbering."""
+        G = len(segments)
+        encs = [encoding] * G if isinstance(encoding, str) else list(encoding)
+
+        def per_segment(v, cls, name):
+            if v is None:
+                return None
+            v = [v] * G if isinstance(v, cls) else list(v)
+            if len(v) != G:
+                raise SessionError(f"{name} must be one {cls.__name__} or one per segment ({G}), got {len(v)}")
+            return v
+
+        trims, levels = per_segment(trims, Trim, "trims"), per_segment(levels, Level, "levels")
+        shapes, limits = per_segment(shapes, Shape, "shapes"), per_segment(limits, Limit, "limits")
+        J = _n_streams(segments, n_streams)
+        keys, of_stream = [], {}
+        for i, g in enumerate(segments):
+            if not 0 <= int(g.row) < len(rates):
+                raise SessionError(f"segment {i}: row {int(g.row)} outside [0, {len(rates)})")
+            if not 0 <= int(g.stream) < J:
+                raise SessionError(f"segment {i}: stream {int(g.stream)} outside [0, {J})")
+            keys.append((int(rates[int(g.row)]), encs[i]))
+            if of_stream.setdefault(int(g.stream), keys[i]) != keys[i]:
+                raise SessionError(f"segment {i}: stream {int(g.stream)} would hold audio at {keys[i][0]} Hz as {keys[i][1]} behind "
+                                   f"audio at {of_stream[int(g.stream)][0]} Hz as {of_stream[int(g.stream)][1]}")
+        plain = trims is None and levels is None and shapes is None and limits is None
+        streams = [np.zeros(0, np.uint8)] * J
+        kept_first = np.zeros(G, np.int64)
+        kept_count = np.array([counts[int(g.row)] for g in segments], np.int64)
+        loud = gain = None
+        if levels is not None:
+            loud, gain = np.full(G, np.nan, np.float64), np.ones(G, np.float32)
+        for key in dict.fromkeys(keys):
+            idx = [i for i in range(G) if keys[i] == key]
+            local = {}
+            for i in idx:
+                local.setdefault(int(segments[i].stream), len(local))
+            sub = [dataclasses.replace(segments[i], stream=local[int(segments[i].stream)]) for i in idx]
+            pick = lambda v: None if v is None else [v[i] for i in idx]  # noqa: E731
+            if plain:
+                ss = self.deliver(sub, len(local), key[1])
+            else:
+                ss, kf, kc, *lv = self.deliver(sub, len(local), key[1], trims=pick(trims), return_kept=True, levels=pick(levels),
+                                               sample_rate=key[0], return_levels=levels is not None, shapes=pick(shapes),
+                                               limits=pick(limits))
+                kept_first[idx], kept_count[idx] = kf, kc
+                if lv:
+                    loud[idx], gain[idx] = lv
+            for j, k in local.items():
+                streams[j] = ss[k]
+        return streams, kept_first, kept_count, loud, gain
+
     def _token_shapes(self, segments, shapes, gains, durations, lens, counts, gain_ramp):
         """the shapes of a delivery of the last run with every segment's points set from its row's token gains"""
-        ratio = None
-        if self.resampling:
-            ratio = resample_plan(self.input_rate or int(self.meta("sample_rate") or 22050), self.output_rate)[:2]
         hop = self.hparam("hop")
-        bounds = [token_bounds(durations[b], lens[b], hop, counts[b], ratio) for b in range(len(lens))]
-        return token_gain_shapes(segments, shapes, gains, bounds, int(self.delivered_rate * float(gain_ramp)))
+        ratios = self._row_ratios(len(lens))
+        bounds = [token_bounds(durations[b], lens[b], hop, counts[b], ratios[b]) for b in range(len(lens))]
+        if self.output_rates is None:
+            return token_gain_shapes(segments, shapes, gains, bounds, int(self.delivered_rate * float(gain_ramp)))
+        # (a rate per row: the ramp, given in seconds, at each row's own)
+        return token_gain_shapes(segments, shapes, gains, bounds, [int(int(r) * float(gain_ramp)) for r in self.last_sample_rates()])
 
     def sync(self):
         with self._locked():
@@ -1818,6 +1990,9 @@ class PipelinedSession:
         if getattr(first, "output_rate", None) is not None:
             raise SessionError("PipelinedSession runs the device-pointer entries, which do not resample: the session has an "
                                f"output rate set ({first.output_rate} Hz); call set_output_rate(None) first")
+        if getattr(first, "output_rates", None) is not None:
+            raise SessionError("PipelinedSession runs the device-pointer entries, which do not resample: the session has "
+                               f"per-row output rates set ({list(first.output_rates)}); call set_output_rates(None) first")
         self.parts = [first]
         # `first` owns the weight arena the other handles borrow: it must never close and reopen itself under them
         # (MiSession's own fallback would free the arena while the borrowers run on it).  The fallback happens HERE,
@@ -2323,6 +2498,29 @@ def test_resample(x, lens, in_rate, out_rate, device_id=0):
     if rc != 0:
         raise SessionError(f"vits_test_resample failed [{rc}]: {_ffi.last_error(None)}")
     return y, counts
+
+
+def test_resample_rows(x, lens, in_rate, out_rates, device_id=0):
+    """The rows entry of the resampler by value (vits_test_resample_rows): x float32 [B, S], lens [B], out_rates [B] (None, 0
+    or in_rate: a native row) -> (y float32 [B, S_out], counts int64 [B]) with S_out = counts.max() (at least 1)."""
+    x = np.ascontiguousarray(x, np.float32)
+    lens = np.ascontiguousarray(lens, np.int64)
+    rates = np.asarray([int(r or 0) for r in out_rates], np.int32)
+    if x.ndim != 2 or lens.shape != (x.shape[0],) or rates.shape != lens.shape:
+        raise SessionError(f"x must be [B, S], lens and out_rates [B], got {x.shape} / {lens.shape} / {rates.shape}")
+    B, S = x.shape
+    # (the engine validates the rates and reports the counts: the buffer is sized by a bound that needs no plan)
+    cap = -(-S * max(int(rates.max()), int(in_rate)) // max(int(in_rate), 1)) + 1
+    buf = np.full(B * cap, np.nan, np.float32)
+    counts = np.zeros(B, np.int64)
+    rc = _ffi.load().vits_test_resample_rows(device_id, _ffi.ptr(x), _ffi.ptr(lens), B, S, int(in_rate), _ffi.ptr(rates), _ffi.ptr(buf),
+                                             buf.size, _ffi.ptr(counts))
+    if rc != 0:
+        raise SessionError(f"vits_test_resample_rows failed [{rc}]: {_ffi.last_error(None)}")
+    S_out = int(counts.max())
+    if S_out == 0:  # (nothing was written: one column of zeros, as the single-rate hook gives)
+        return np.zeros((B, 1), np.float32), counts
+    return buf[:B * S_out].reshape(B, S_out).copy(), counts
 
 
 def test_resample_pieces(x, lens, in_rate, out_rate, piece_samples, device_id=0):

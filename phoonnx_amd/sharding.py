@@ -154,6 +154,11 @@ class ShardedSynthesizer:
                 raise SessionError("ShardedSynthesizer trims and gathers by frames and runs the device-pointer entries, which do "
                                    f"not resample: the session has an output rate set ({session.output_rate} Hz); call "
                                    "set_output_rate(None) first")
+            if getattr(session, "output_rates", None) is not None:
+                from .session import SessionError
+                raise SessionError("ShardedSynthesizer trims and gathers by frames and runs the device-pointer entries, which do "
+                                   f"not resample: the session has per-row output rates set ({list(session.output_rates)}); call "
+                                   "set_output_rates(None) first")
             self.session, self._arena = session, None
         else:
             self.session, self._arena = open_sharded(path, device_id, dist, force_broadcast=force_broadcast,

@@ -245,10 +245,11 @@ class TTSVoice:
         """The rate of the audio this voice hands out: output_sample_rate, or the voice's own."""
         return int(self.output_sample_rate) if self.output_sample_rate is not None else self.config.sample_rate
 
-    def _ratio(self) -> Optional[Tuple[int, int]]:
-        """(L, M) = output rate / voice rate, reduced; None when the audio is not resampled."""
+    def _ratio(self, rate: Optional[int] = None) -> Optional[Tuple[int, int]]:
+        """(L, M) = output rate / voice rate, reduced; None when the audio is not resampled.  rate: a request's own output
+        rate where that is not this voice's."""
         import math
-        fi, fo = int(self.config.sample_rate), self.sample_rate
+        fi, fo = int(self.config.sample_rate), self.sample_rate if rate is None else int(rate)
         if fi == fo:
             return None
         g = math.gcd(fi, fo)
@@ -454,12 +455,13 @@ class TTSVoice:
         return result
 
     # ------------------------------------------------------------------ encoded delivery (extension)
-    def _lead_samples(self, sentence_silence: float) -> int:
+    def _lead_samples(self, sentence_silence: float, rate: Optional[int] = None) -> int:
         """Samples of silence in front of every sentence: the reference's framing (voice.py:307-326 writes
-        int(sample_rate * sentence_silence * 2) bytes of 16-bit silence) wherever that byte count is even."""
+        int(sample_rate * sentence_silence * 2) bytes of 16-bit silence) wherever that byte count is even.  rate: the rate the
+        audio is delivered at where that is not this voice's (a request's own: synthesize_requests_encoded)."""
         if not sentence_silence >= 0.0:
             raise ValueError(f"sentence_silence must be >= 0 (got {sentence_silence})")
-        return int(self.sample_rate * sentence_silence * 2) // 2
+        return int((self.sample_rate if rate is None else rate) * sentence_silence * 2) // 2
 
     @staticmethod
     def _scaled(audio: np.ndarray, peak, volume: float) -> np.ndarray:
@@ -467,7 +469,7 @@ class TTSVoice:
         from . import audio_encoding as ae
         return ae.scaled(audio, peak, volume)
 
-    def _trim(self, trim_silence, trailing_silence: float):
+    def _trim(self, trim_silence, trailing_silence: float, rate: Optional[int] = None):
         """trim_silence / trailing_silence of the encoded entries -> a session.Trim in samples at the delivered rate, or None
         when both are left at their defaults.  A float is a threshold relative to the sentence's peak; a Trim is taken with
         keep_lead / keep_tail in SECONDS, converted like the pause (_lead_samples); trailing_silence, in seconds, is added to
@@ -475,14 +477,14 @@ class TTSVoice:
         from .session import Trim
         if not trailing_silence >= 0.0:
             raise ValueError(f"trailing_silence must be >= 0 (got {trailing_silence})")
-        tail = self._lead_samples(trailing_silence)
+        tail = self._lead_samples(trailing_silence, rate)
         if trim_silence is None:
             return Trim(0, 0.0, 0, 0, tail) if tail else None
         if isinstance(trim_silence, Trim):
             t = trim_silence
             if not (t.keep_lead >= 0 and t.keep_tail >= 0):
                 raise ValueError(f"trim_silence: keep_lead / keep_tail must be >= 0 seconds (got {t.keep_lead}, {t.keep_tail})")
-            return Trim(int(t.mode), float(t.threshold), self._lead_samples(t.keep_lead), self._lead_samples(t.keep_tail),
+            return Trim(int(t.mode), float(t.threshold), self._lead_samples(t.keep_lead, rate), self._lead_samples(t.keep_tail, rate),
                         int(t.tail_samples) + tail)
         thr = float(trim_silence)
         if not (thr >= 0.0 and np.isfinite(thr)):
@@ -509,7 +511,7 @@ class TTSVoice:
             raise ValueError("loudness levelling replaces peak normalisation: pass a SynthesisConfig with normalize_audio=False")
         return Level(1 if loudness_scope == "sentence" else 2, target, float(max_gain_db), float(peak_ceiling))
 
-    def _shape(self, fade_in: float, fade_out: float, fade_curve: str):
+    def _shape(self, fade_in: float, fade_out: float, fade_curve: str, rate: Optional[int] = None):
         """fade_in / fade_out (seconds) and fade_curve of the encoded entries -> a session.Shape in samples at the delivered
         rate (int(sample_rate * seconds)), or None when neither fades."""
         from .session import Shape
@@ -518,10 +520,11 @@ class TTSVoice:
                 raise ValueError(f"{name} must be a finite number of seconds >= 0 (got {v})")
         if fade_curve not in ("linear", "smooth"):
             raise ValueError(f"fade_curve must be 'linear' or 'smooth' (got {fade_curve!r})")
-        fi, fo = int(self.sample_rate * fade_in), int(self.sample_rate * fade_out)
+        rate = self.sample_rate if rate is None else rate
+        fi, fo = int(rate * fade_in), int(rate * fade_out)
         return Shape(fi, fo, fade_curve) if fi or fo else None
 
-    def _limit(self, limit_ceiling: float, limit_lookahead: float):
+    def _limit(self, limit_ceiling: float, limit_lookahead: float, rate: Optional[int] = None):
         """limit_ceiling / limit_lookahead (seconds) of the encoded entries -> a session.Limit with the look-ahead in samples
         at the delivered rate (round(limit_lookahead * sample_rate)), or None when limit_ceiling is 0."""
         from .session import Limit
@@ -531,9 +534,10 @@ class TTSVoice:
             return None
         if not (np.isfinite(limit_lookahead) and limit_lookahead >= 0.0):
             raise ValueError(f"limit_lookahead must be a finite number of seconds >= 0 (got {limit_lookahead})")
-        L = int(round(limit_lookahead * self.sample_rate))
+        rate = self.sample_rate if rate is None else rate
+        L = int(round(limit_lookahead * rate))
         if not 1 <= L <= 1024:
-            raise ValueError(f"limit_lookahead {limit_lookahead} s is {L} samples at {self.sample_rate} Hz: outside [1, 1024]")
+            raise ValueError(f"limit_lookahead {limit_lookahead} s is {L} samples at {rate} Hz: outside [1, 1024]")
         return Limit(float(limit_ceiling), L)
 
     @staticmethod
@@ -553,19 +557,24 @@ class TTSVoice:
             db[b, :len(q)] = q
         return db
 
-    def _row_shapes(self, shape, token_db, durs, counts):
+    def _row_shapes(self, shape, token_db, durs, counts, rates=None):
         """The host fallback's shapes, one per row: `shape` (or none), with the points of each row's token gains - what
-        MiSession.synthesize_delivered(token_gain_db=) computes between run and delivery, from the same durations."""
+        MiSession.synthesize_delivered(token_gain_db=) computes between run and delivery, from the same durations.
+        rates: None, or the rate each row is delivered at (`shape` is then one Shape, or none, per row)."""
         from .session import Segment, Shape, token_bounds, token_gain_shapes, token_gains
         n = len(counts)
-        shapes = [shape if shape is not None else Shape()] * n
+        if rates is None:
+            shapes = [shape if shape is not None else Shape()] * n
+        else:
+            shapes = [sh if sh is not None else Shape() for sh in shape]
         if token_db is None:
             return shapes
         db = self._padded_db(token_db)
-        hop, ratio = self.session.hparam("hop"), self._ratio()
-        bounds = [token_bounds(durs[b], len(token_db[b]), hop, counts[b], ratio) for b in range(n)]
-        return token_gain_shapes([Segment(b) for b in range(n)], shapes, token_gains(db, *db.shape), bounds,
-                                 int(self.sample_rate * _GAIN_RAMP))
+        hop = self.session.hparam("hop")
+        ratios = [self._ratio()] * n if rates is None else [self._ratio(r) for r in rates]
+        bounds = [token_bounds(durs[b], len(token_db[b]), hop, counts[b], ratios[b]) for b in range(n)]
+        ramp = int(self.sample_rate * _GAIN_RAMP) if rates is None else [int(int(r) * _GAIN_RAMP) for r in rates]
+        return token_gain_shapes([Segment(b) for b in range(n)], shapes, token_gains(db, *db.shape), bounds, ramp)
 
     @staticmethod
     def _cut_alignments(al, a: int, c: int):
@@ -898,7 +907,9 @@ class TTSVoice:
                                     trailing_silence: float = 0.0, loudness=None, loudness_scope: str = "sentence",
                                     peak_ceiling: float = 0.0, max_gain_db: float = 30.0, fade_in: float = 0.0,
                                     fade_out: float = 0.0, fade_curve: str = "linear", phoneme_gain_db=None,
-                                    limit_ceiling: float = 0.0, limit_lookahead: float = 0.005):
+                                    limit_ceiling: float = 0.0, limit_lookahead: float = 0.005,
+                                    output_sample_rates: Optional[Sequence[Optional[int]]] = None,
+                                    encodings: Optional[Sequence[Optional[str]]] = None):
         """Extension: synthesize_requests with every request's audio returned as one stream of encoded audio
         (audio_encoding.EncodedAudio; the pause of synthesize_encoded in front of each sentence).  The batching is
         synthesize_requests': sentences sorted by length, max_batch at a time, each with its request's settings and seed.
@@ -914,7 +925,15 @@ class TTSVoice:
         (audio_encoding.level_rows).  fade_in / fade_out / fade_curve / phoneme_gain_db as in synthesize_encoded, for every
         sentence of every request (phoneme_gain_db's sentence_index counts within its request); with loudness scope "text"
         the host that levels applies them too (audio_encoding.shape_multiplier).  limit_ceiling / limit_lookahead as in
-        synthesize_encoded, for every sentence of every request (where the host levels, it limits too)."""
+        synthesize_encoded, for every sentence of every request (where the host levels, it limits too).
+        output_sample_rates / encodings: None, or one value per request (None in the list: this voice's rate / `encoding`) -
+        request r's audio at its own rate and in its own encoding, out of the same batched runs: the batching does not look
+        at either, each row of a run is resampled on the device at its request's rate (MiSession.set_output_rates) and each
+        run is delivered once per (rate, encoding) group.  Every seconds-valued argument - sentence_silence,
+        trailing_silence, a Trim's keep_lead / keep_tail, the fades, limit_lookahead - is converted at each request's own rate,
+        alignments count samples at it, and every EncodedAudio carries its request's sample_rate and encoding: request r is
+        what this call returns for it on a voice loaded at that rate with that encoding, bit for bit.  ValueError with a
+        session that has no set_output_rates."""
         from . import audio_encoding as ae
         ae._check(encoding)
         lead = self._lead_samples(sentence_silence)
@@ -924,9 +943,40 @@ class TTSVoice:
         limit = self._limit(limit_ceiling, limit_lookahead)
         level = self._level(loudness, loudness_scope, peak_ceiling, max_gain_db,
                             [cfg if cfg is not None else SynthesisConfig() for _, cfg in requests])
-        tail = trim.tail_samples if trim is not None else 0
+        # what a request's audio is delivered as: (rate, encoding, lead, trim, shape, limit) - this voice's for every request,
+        # or with a rate or an encoding per request the same things at that request's own
+        R = len(requests)
+        mixed = output_sample_rates is not None or encodings is not None
+        as_of = [(self.sample_rate, encoding, lead, trim, shape, limit)] * R
+        if mixed:
+            if not (hasattr(self.session, "set_output_rates") and hasattr(self.session, "synthesize_delivered")):
+                raise ValueError("output_sample_rates / encodings need a session that resamples each row of a run on the device "
+                                 "(MiSession.set_output_rates); this session has no set_output_rates")
+            for name, v in (("output_sample_rates", output_sample_rates), ("encodings", encodings)):
+                if v is not None and len(v) != R:
+                    raise ValueError(f"{name} must hold one value per request ({R}), got {len(v)}")
+            made = {}
+            as_of = []
+            for r in range(R):
+                fo = output_sample_rates[r] if output_sample_rates is not None else None
+                enc = encodings[r] if encodings is not None and encodings[r] is not None else encoding
+                if fo is not None and (not isinstance(fo, (int, np.integer)) or fo <= 0):
+                    raise ValueError(f"request {r}: output_sample_rates must hold None or positive integers (got {fo!r})")
+                fo = self.sample_rate if fo is None else int(fo)
+                ae._check(enc)
+                if fo not in made:
+                    made[fo] = (self._lead_samples(sentence_silence, fo), self._trim(trim_silence, trailing_silence, fo),
+                                self._shape(fade_in, fade_out, fade_curve, fo), self._limit(limit_ceiling, limit_lookahead, fo))
+                as_of.append((fo, enc) + made[fo])
+            shaped = phoneme_gain_db is not None or any(a[4] is not None for a in as_of)
+            # (below, "is there a trim / a shape / a limit" asks whether any request has one)
+            trim = next((a[3] for a in as_of if a[3] is not None), None)
+            shape = next((a[4] for a in as_of if a[4] is not None), None)
+            limit = next((a[5] for a in as_of if a[5] is not None), None)
 
-        def join(pieces, aligns, kept=None, loud=None, gains=None):
+        def join(r, pieces, aligns, kept=None, loud=None, gains=None):
+            rate, encoding, lead, trim = as_of[r][:4]
+            tail = trim.tail_samples if trim is not None else 0
             starts, pos = [], 0
             for p in pieces:
                 starts.append(pos + lead)
@@ -940,12 +990,13 @@ class TTSVoice:
                         self._cut_alignments(al or [], *kept[k])
                     for a in al or []:
                         a.start_sample += st
-            return ae.EncodedAudio(data, encoding, self.sample_rate, starts, [len(p) for p in pieces], aligns,
+            return ae.EncodedAudio(data, encoding, rate, starts, [len(p) for p in pieces], aligns,
                                    None if loud is None else [float(v) for v in loud], None if gains is None else [float(g) for g in gains])
 
-        def level_on_host(rows, volume, muls=None):
-            """a request's kept rows (float32, unlevelled) -> (encoded pieces, loudness, gains); muls: their shapes' multipliers"""
-            loud, gains = ae.level_rows(rows, self.sample_rate, level)
+        def level_on_host(r, rows, volume, muls=None):
+            """request r's kept rows (float32, unlevelled) -> (encoded pieces, loudness, gains); muls: their shapes' multipliers"""
+            rate, encoding, limit = as_of[r][0], as_of[r][1], as_of[r][5]
+            loud, gains = ae.level_rows(rows, rate, level)
             muls = muls if muls is not None else [None] * len(rows)
             return [ae.encode(ae.leveled(v, g, volume, m, limit), encoding) for v, g, m in zip(rows, gains, muls)], loud, gains
 
@@ -978,8 +1029,8 @@ class TTSVoice:
                     rows = [np.asarray(c.audio_float_array, np.float32)[a:a + n] for c, (a, n) in zip(cs, kept)]
                     shapes = host_shapes(r, text, cfg, cs)
                     muls = None if shapes is None else [ae.shape_multiplier(a, n, sh) for (a, n), sh in zip(kept, shapes)]
-                    pieces, loud, gains = level_on_host(rows, cfg.volume, muls)
-                    result.append(join(pieces, [c.phoneme_alignments for c in cs] if want_al(cs) else None,
+                    pieces, loud, gains = level_on_host(r, rows, cfg.volume, muls)
+                    result.append(join(r, pieces, [c.phoneme_alignments for c in cs] if want_al(cs) else None,
                                        kept if trim is not None else None, loud, gains))
                 return result
             if shaped or limit is not None:
@@ -996,24 +1047,24 @@ class TTSVoice:
                                                   cfg.volume, shapes=None if sh is None else [sh], limits=limit)
                         pieces.append(data)
                         kept += k
-                    result.append(join(pieces, [c.phoneme_alignments for c in cs] if want_al(cs) else None,
+                    result.append(join(r, pieces, [c.phoneme_alignments for c in cs] if want_al(cs) else None,
                                        kept if trim is not None else None))
                 return result
             if trim is None:
                 chunks = self.synthesize_requests(requests, seeds=seeds, max_batch=max_batch, alignments=alignments)
-                return [join([ae.encode(c.audio_float_array, encoding) for c in cs],
-                             [c.phoneme_alignments for c in cs] if want_al(cs) else None) for cs in chunks]
+                return [join(r, [ae.encode(c.audio_float_array, encoding) for c in cs],
+                             [c.phoneme_alignments for c in cs] if want_al(cs) else None) for r, cs in enumerate(chunks)]
             # the rows as rendered, each cut, then post-processed by the peak of what is kept
             chunks = self.synthesize_requests(requests, seeds=seeds, max_batch=max_batch, alignments=alignments, postprocess=False)
             result = []
-            for (_, cfg), cs in zip(requests, chunks):
+            for r, ((_, cfg), cs) in enumerate(zip(requests, chunks)):
                 cfg = cfg if cfg is not None else SynthesisConfig()
                 pieces, kept = [], []
                 for c in cs:
                     data, k = ae.join_trimmed([c.audio_float_array], encoding, 0, 0, trim, 1 if cfg.normalize_audio else 0, cfg.volume)
                     pieces.append(data)
                     kept += k
-                result.append(join(pieces, [c.phoneme_alignments for c in cs] if want_al(cs) else None, kept))
+                result.append(join(r, pieces, [c.phoneme_alignments for c in cs] if want_al(cs) else None, kept))
             return result
         if max_batch < 1:
             raise ValueError(f"max_batch must be >= 1 (got {max_batch})")
@@ -1027,7 +1078,7 @@ class TTSVoice:
                 spk = cfg.speaker_id or 0
                 if not 0 <= spk < max(n_spk, 1):
                     raise ValueError(f"request {r}: speaker_id {spk} is out of range [0, {max(n_spk, 1)})")
-        from .session import Segment
+        from .session import Segment, Shape, Trim
         from .sharding import pad_batch
         want_dur = alignments and hasattr(self.session, "last_durations")
         rows, groups, db_of = [], {}, {}
@@ -1065,14 +1116,31 @@ class TTSVoice:
             if limit is not None and not host_level:  # (scope "text": the host that levels limits too)
                 more["limits"] = limit
             need_dur = want_dur or (host_level and phoneme_gain_db is not None)
-            out = self.session.synthesize_delivered(ids, lens, scales, sid, segments=segs, n_streams=len(run),
-                                                    encoding="f32" if host_level else encoding, seeds=row_seeds,
-                                                    return_durations=need_dur, **more)
+            if mixed:
+                # a rate and an encoding per row: the same call with its request's own things in every list (a request whose
+                # trim or shape comes to nothing at its rate: the neutral one)
+                of_row = [as_of[r] for r, _, _ in run]
+                if "trim" in more:
+                    more["trim"] = [dataclasses.replace(a[3], tail_samples=0) if a[3] is not None else Trim(0, 0.0, 0, 0, 0) for a in of_row]
+                if "shapes" in more:
+                    more["shapes"] = [a[4] if a[4] is not None else Shape() for a in of_row]
+                if "limits" in more:
+                    more["limits"] = [a[5] for a in of_row]
+                native = int(self.config.sample_rate)
+                out = self._delivered_at_row_rates([0 if a[0] == native else a[0] for a in of_row], ids, lens, scales, sid,
+                                                   segments=segs, n_streams=len(run),
+                                                   encoding=["f32" if host_level else a[1] for a in of_row], seeds=row_seeds,
+                                                   return_durations=need_dur, **more)
+            else:
+                out = self.session.synthesize_delivered(ids, lens, scales, sid, segments=segs, n_streams=len(run),
+                                                        encoding="f32" if host_level else encoding, seeds=row_seeds,
+                                                        return_durations=need_dur, **more)
             if shaped and host_level:
                 counts = [int(n) for n in out["sample_lengths"]]
-                run_shapes = self._row_shapes(shape, None if phoneme_gain_db is None else [db_of[r, k] for r, k, _ in run],
+                run_shapes = self._row_shapes([as_of[r][4] for r, _, _ in run] if mixed else shape,
+                                              None if phoneme_gain_db is None else [db_of[r, k] for r, k, _ in run],
                                               None if phoneme_gain_db is None else [out["durations"][b, :len(i)] for b, (_, _, i) in enumerate(run)],
-                                              counts)
+                                              counts, [as_of[r][0] for r, _, _ in run] if mixed else None)
                 for b, (r, k, _) in enumerate(run):
                     a, c = (int(out["kept_first"][b]), int(out["kept_count"][b]))
                     mul_of[r, k] = ae.shape_multiplier(a, c, run_shapes[b])
@@ -1084,7 +1152,7 @@ class TTSVoice:
                     kept_of[r, k] = (int(out["kept_first"][b]), int(out["kept_count"][b]))
                 if want_dur:
                     aligned[r, k] = build_alignments(groups[r, k], out["durations"][b], hop,
-                                                     total_frames=int(out["y_lengths"][b]), ratio=self._ratio())
+                                                     total_frames=int(out["y_lengths"][b]), ratio=self._ratio(as_of[r][0]))
         per_request = [[] for _ in requests]
         for r, k, _ in rows:  # (rows are in request, then sentence order)
             per_request[r].append((r, k))
@@ -1092,12 +1160,26 @@ class TTSVoice:
         for r, keys in enumerate(per_request):
             pieces, loud, gains = [piece[key] for key in keys], None, None
             if level is not None and level.mode == 2:
-                pieces, loud, gains = level_on_host(pieces, cfgs[r].volume, [mul_of[key] for key in keys] if shaped else None)
+                pieces, loud, gains = level_on_host(r, pieces, cfgs[r].volume, [mul_of[key] for key in keys] if shaped else None)
             elif level is not None:
                 loud, gains = [level_of[key][0] for key in keys], [level_of[key][1] for key in keys]
-            result.append(join(pieces, [aligned[key] for key in keys] if want_dur else None,
+            result.append(join(r, pieces, [aligned[key] for key in keys] if want_dur else None,
                                [kept_of[key] for key in keys] if trim is not None else None, loud, gains))
         return result
+
+    def _delivered_at_row_rates(self, rates, *args, **kw):
+        """session.synthesize_delivered with row b resampled from the voice's rate to rates[b] (0: not at all); the session's
+        own output rate, or rates, are put back afterwards"""
+        s = self.session
+        before = (s.output_rate, s.output_rates, s.input_rate)
+        s.set_output_rates(rates, int(self.config.sample_rate))
+        try:
+            return s.synthesize_delivered(*args, **kw)
+        finally:
+            if before[1] is not None:
+                s.set_output_rates(before[1], before[2])
+            else:
+                s.set_output_rate(before[0], before[2])
 
     def synthesize_wav(self, text: str, wav_file: wave.Wave_write, syn_config: Optional[SynthesisConfig] = None,
                        set_wav_format: bool = True, batch_sentences: bool = False, device_pcm16: bool = False) -> None:
