@@ -981,6 +981,56 @@ int vits_bench_conv1d(int device_id, int B, int Cin, int Cout, int T, int K, int
 /* out[B,Cout,T*stride] = conv_transpose1d(x, w[Cin,Cout,K], bias, stride, pad=(K-stride)/2). */
 int vits_test_conv_transpose1d(int device_id, const float *x, int B, int Cin, int T, const float *w,
                                const float *bias, int Cout, int K, int stride, float *out);
+/* The f32 conv engine (csrc/conv_engine.hip.hpp) with the whole argument set the pipeline's conv() gives it: prologue and
+ * epilogue flags, per-utterance bias, residual, old contents of the outputs, row pitches, the second output and the fp16
+ * operand planes.  One launch of the engine's own launcher; every pointer is a host pointer.
+ *   value = act(conv(pro(x)) + bias + bias_b[b]), then the flag's rule (the EPI_* enum of conv_engine.hip.hpp).
+ * Refused with VITS_E_ARG, never launched: what the engine cannot form (see the field comments). */
+enum {
+    VITS_CONV_PRO_LRELU = 1, VITS_CONV_PRO_MASK = 2, VITS_CONV_EPI_RELU = 4, VITS_CONV_EPI_MASK = 8, VITS_CONV_EPI_RES = 16,
+    VITS_CONV_EPI_ACC = 32, VITS_CONV_EPI_DIV = 64, VITS_CONV_EPI_COUPLING = 128, VITS_CONV_EPI_WN = 256,
+    VITS_CONV_EPI_WN_FIRST = 512
+};
+typedef struct {
+    int B, Cin, T, Cout;     /* Cout: the module's output channels (a transposed conv: before the pixel shuffle) */
+    int K, dil, pad_l;       /* Conv1d: w [Cout][Cin][K]; pad_l + pad_r == dil * (K - 1) */
+    int stride;              /* 1 = Conv1d; > 1 = ConvTranspose1d, w [Cin][Cout][K], padding (K - stride) / 2 (dil, pad_l unused) */
+    int hint, cfg, ck;       /* tile / chunk: cfg 0..5 and ck > 0 explicitly (refused where the stage does not fit), or
+                              * cfg < 0: by the size class `hint` 0..2 as at pack time */
+    int flags;               /* VITS_CONV_* */
+    float slope, div, oslope, oslope2;  /* PRO_LRELU; EPI_DIV; leaky_relu slope of what out / out2 store (0 or 1 = none) */
+    int wn_split;            /* EPI_WN: first skip row; % 32 == 0, <= Cout */
+    const float *x;          /* [B][Cin][T] dense; the hook lays it out with x_cstride floats per row, zeros behind T */
+    const float *w, *bias;   /* bias [Cout] or NULL */
+    const int64_t *lens;     /* [B] in [0, T], or NULL */
+    const float *bias_b;     /* [B][bias_b_stride] or NULL; bias_b_stride >= Cout */
+    int bias_b_stride;
+    const float *res;        /* EPI_RES: [B][Cout][out pitch] (rows as the conv's own, pitch as out) */
+    int x_cstride;           /* 0 = T, else >= T */
+    int out_cstride;         /* 0 = T * stride; Conv1d: >= T and within the last time tile (the columns behind T are the
+                              * launch's to zero); ConvTranspose1d: T * stride only */
+    int out_rows, out_row0;  /* out / out2 hold out_rows rows per utterance (0 = Cout), the conv's row 0 is row out_row0:
+                              * a window into a wider tensor.  EPI_WN: out_row0 == 0, out_rows >= wn_split and >= Cout - wn_split */
+    const float *old_out, *old_out2;  /* previous contents [B][out_rows][T * stride] dense, or NULL: every element, and
+                                       * always the pitch columns, start as `sentinel` */
+    float sentinel;
+    float *out, *out2;       /* [B][out_rows][out pitch] whole, as the launch left them; out2 NULL = no second output
+                              * (EPI_WN needs one) */
+    int pl_rows;             /* > 0: operand planes of rows [0, pl_rows) of out; % 32 == 0, <= Cout (EPI_WN: <= wn_split),
+                              * stride == 1 */
+    float *planes_out;       /* [B][pl_rows][T] read back from the two fp16 planes (cells nobody wrote read as 1.0591) */
+    char kernel[128];        /* out: the instantiation launched (as in vits_launch_record) */
+    int cfg_used, ck_used;   /* out */
+} vits_test_conv_epi_args;
+int vits_test_conv1d_epi(int device_id, vits_test_conv_epi_args *a);
+/* The flow's gate tanh(a[:H]) * sigmoid(a[H:]) on a [B][2H][T] (planar, host): form 0 = wn_gate_kernel, form 1 =
+ * wn_gate_blocked_kernel, which reads `a` in the raw cell layout [2H/8][T][8] (H % 8 == 0; the hook lays it out).
+ * acts: [B][H][T]. */
+int vits_test_wn_gate(int device_id, const float *a, int B, int H, int T, int form, float *acts);
+/* Speaker conditioning out[b][r] = bias[r] + W[r][:] . emb_g[clamp(sid[b], 0, n_speakers - 1)][:] (cond_matvec_kernel);
+ * emb_g [n_speakers][gin], W [rows][gin], bias [rows] or NULL, out [B][rows]. */
+int vits_test_cond_matvec(int device_id, const float *emb_g, int n_speakers, int gin, const int64_t *sid, int B,
+                          const float *W, const float *bias, int rows, float *out);
 /* The same three hooks through the split-operand engine the generator runs on when all of its channel counts
  * are multiples of 32 (csrc/conv_sx_engine.hip.hpp); needs Cin % 16 == 0 and Cout % 32 == 0.
  * vits_test_conv1d_sx flags: bit0 -> out = leaky_relu(conv, slope) read back from the 16-bit output planes

@@ -37,6 +37,16 @@ class VitsLaunchRecord(C.Structure):
                 ("stage", C.c_int), ("cin", C.c_int), ("cout", C.c_int), ("k", C.c_int), ("dil", C.c_int), ("t", C.c_int)]
 
 
+class VitsTestConvEpiArgs(C.Structure):
+    """vits_test_conv_epi_args of include/vitsmi.h"""
+    _fields_ = [(n, C.c_int) for n in ("B", "Cin", "T", "Cout", "K", "dil", "pad_l", "stride", "hint", "cfg", "ck", "flags")] + \
+               [(n, C.c_float) for n in ("slope", "div", "oslope", "oslope2")] + [("wn_split", C.c_int)] + \
+               [(n, C.c_void_p) for n in ("x", "w", "bias", "lens", "bias_b")] + [("bias_b_stride", C.c_int), ("res", C.c_void_p)] + \
+               [(n, C.c_int) for n in ("x_cstride", "out_cstride", "out_rows", "out_row0")] + \
+               [("old_out", C.c_void_p), ("old_out2", C.c_void_p), ("sentinel", C.c_float), ("out", C.c_void_p), ("out2", C.c_void_p),
+                ("pl_rows", C.c_int), ("planes_out", C.c_void_p), ("kernel", C.c_char * 128), ("cfg_used", C.c_int), ("ck_used", C.c_int)]
+
+
 class VitsOpenOptions(C.Structure):
     _fields_ = [("device_id", C.c_int), ("gen_precision", C.c_char_p), ("arena_dev", C.c_void_p),
                 ("arena_bytes", C.c_size_t), ("host_only", C.c_int), ("layout_only", C.c_int)]
@@ -143,6 +153,7 @@ EXPORTS = [
     "vits_stream_onset_check", "vits_stream_onset_start", "vits_run_chunked_enc_trimmed", "vits_run_vocoder_chunked_enc_trimmed",
     "vits_test_stream_pack_trimmed",
     "vits_test_layernorm", "vits_test_dds", "vits_test_cf_pre", "vits_test_rqs_inverse", "vits_test_ea_logw",
+    "vits_test_conv1d_epi", "vits_test_wn_gate", "vits_test_cond_matvec",
 ]
 
 
@@ -317,6 +328,9 @@ def load():
     lib.vits_test_set_sx_small_max.restype = C.c_longlong
     lib.vits_test_conv1d_sx_gate.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     lib.vits_bench_conv1d_sx.argtypes = [C.c_int] * 9 + [f32p]
+    lib.vits_test_conv1d_epi.argtypes = [C.c_int, C.POINTER(VitsTestConvEpiArgs)]
+    lib.vits_test_wn_gate.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+    lib.vits_test_cond_matvec.argtypes = [C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp]
     lib.vits_test_conv_pair_sx.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int,
                                            C.c_int, C.c_int, C.c_float, vp, f32p]
     lib.g2p_open.argtypes = [C.c_char_p, C.c_int, C.POINTER(vp)]

@@ -3945,6 +3945,156 @@ int vits_test_conv_transpose1d(int device_id, const float *x, int B, int Cin, in
     return run_test_conv(d, arena, x, B, T, 0, 0.f, out, (size_t)B * Cout * T * stride, (int64_t)Cout * T * stride);
 }
 
+// The f32 engine with conv()'s whole argument set (include/vitsmi.h): conv_args() plus the field assignments conv() makes,
+// one launch_conv().  Everything a launch could index out of its buffers with is refused here.
+int vits_test_conv1d_epi(int device_id, vits_test_conv_epi_args *p) {
+    if (int rc = test_dev(device_id)) return rc;
+    if (!p) return fail(nullptr, VITS_E_ARG, "no arguments");
+    const auto bad = [](const char *why) { return fail(nullptr, VITS_E_ARG, "conv epilogue hook: %s", why); };
+    const int B = p->B, Cin = p->Cin, T = p->T, Cr = p->Cout, u = p->stride, flags = p->flags;
+    if (B < 1 || Cin < 1 || T < 1 || Cr < 1 || u < 1 || !p->x || !p->w || !p->out) return bad("bad shape or missing tensor");
+    if (flags & ~1023) return bad("unknown flag");
+    const bool wn = flags & EPI_WN;
+    if ((flags & EPI_WN_FIRST) && !wn) return bad("EPI_WN_FIRST without EPI_WN");
+    if (wn && (flags & (EPI_RES | EPI_ACC | EPI_DIV | EPI_COUPLING))) return bad("EPI_WN excludes the other update rules");
+    if (wn && !p->out2) return bad("EPI_WN needs out2 (the skip rows)");
+    if (wn && (p->wn_split % 32 != 0 || p->wn_split < 0 || p->wn_split > Cr)) return bad("wn_split must be a multiple of 32 within Cout");
+    if ((flags & EPI_RES) && !p->res) return bad("EPI_RES without res");
+    if (p->bias_b && p->bias_b_stride < Cr) return bad("bias_b rows shorter than Cout");
+    if (u > 1 && (wn || p->pl_rows || p->bias_b)) return bad("a transposed conv takes neither EPI_WN nor planes nor bias_b");
+    const int planes_max = wn ? p->wn_split : Cr;
+    if (p->pl_rows < 0 || p->pl_rows % 32 != 0 || p->pl_rows > planes_max) return bad("pl_rows must be a multiple of 32 within the rows stored in out");
+    if (p->pl_rows && !p->planes_out) return bad("planes without planes_out");
+    if (p->lens)
+        for (int b = 0; b < B; b++)
+            if (p->lens[b] < 0 || p->lens[b] > T) return bad("lens outside [0, T]");
+    ConvDesc d;
+    std::vector<float> arena;
+    TestPack o;
+    o.cfg = p->cfg >= 0 ? p->cfg : -1;
+    o.ck = p->ck;
+    if (p->cfg > 5 || (p->cfg >= 0 && p->ck != 8 && p->ck != 16 && p->ck != 32)) return bad("cfg 0..5 with a chunk of 8, 16 or 32 channels");
+    if (u == 1 && (p->K < 1 || p->dil < 1 || p->pad_l < 0 || p->pad_l > (int64_t)p->dil * (p->K - 1))) return bad("pad_l outside the receptive field");
+    {
+        const std::string e = u > 1 ? pack_test_convT(p->w, p->bias, Cin, Cr, p->K, u, &d, &arena, false, o)
+                                    : pack_test_conv(p->w, p->bias, Cin, Cr, p->K, p->dil, p->pad_l, p->hint & 3, &d, &arena, o);
+        if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
+    }
+    const int Tout = T * u;
+    const int xp = p->x_cstride ? p->x_cstride : T, op = p->out_cstride ? p->out_cstride : Tout;
+    const int BN = conv_tile_n(d.cfg);
+    if (xp < T) return bad("x_cstride smaller than T");
+    if (u > 1 && op != Tout) return bad("a transposed conv stores dense rows (out_cstride = T * stride)");
+    if (op < Tout) return bad("out_cstride smaller than T");
+    if (u == 1 && op > (T + BN - 1) / BN * BN) return bad("out_cstride beyond the last time tile: nobody would zero those columns");
+    const int rows = p->out_rows ? p->out_rows : Cr, row0 = p->out_row0;
+    if (row0 < 0 || rows < 1) return bad("bad output window");
+    if (wn ? (row0 != 0 || rows < p->wn_split || rows < Cr - p->wn_split) : row0 + Cr > rows) return bad("the conv's rows leave the output tensor");
+    // host images: x with its pitch (zeros behind T), out / out2 with theirs (sentinel behind T and where nothing is old)
+    std::vector<float> hx((size_t)B * Cin * xp, 0.f);
+    for (size_t r = 0; r < (size_t)B * Cin; r++) std::memcpy(&hx[r * xp], p->x + r * T, (size_t)T * 4);
+    const size_t no = (size_t)B * rows * op;
+    const auto image = [&](const float *old) {
+        std::vector<float> v(no, p->sentinel);
+        if (old)
+            for (size_t r = 0; r < (size_t)B * rows; r++) std::memcpy(&v[r * op], old + r * Tout, (size_t)Tout * 4);
+        return v;
+    };
+    const std::vector<float> ho = image(p->old_out), ho2 = image(p->old_out2);
+    std::vector<int> l32(B);
+    for (int b = 0; b < B; b++) l32[b] = p->lens ? (int)p->lens[b] : T;
+    const size_t npl = (size_t)B * (p->pl_rows ? p->pl_rows : 32) * T;
+    DevBufs D;
+    float *dA = D.up(arena.data(), arena.size());
+    float *dx = D.up(hx.data(), hx.size(), 16);
+    float *dout = D.up(ho.data(), no, 16);
+    float *dout2 = p->out2 ? D.up(ho2.data(), no, 16) : nullptr;
+    float *dres = p->res ? D.up(p->res, (size_t)B * Cr * op, 16) : nullptr;
+    float *dbb = p->bias_b ? D.up(p->bias_b, (size_t)B * p->bias_b_stride) : nullptr;
+    int *dlen = p->lens ? D.up(l32.data(), (size_t)B) : nullptr;
+    uint16_t *dpl = D.fill<uint16_t>(npl * 3, 0x3c, 64);
+    float *dpo = D.alloc<float>(npl, 16);
+    TCHECK(D.err);
+    ConvArgs a = conv_args(d, dA, dA);  // (pack_test_* reserve a zero page at offset 0)
+    a.x = dx;
+    a.x_bstride = (int64_t)Cin * xp;
+    a.x_cstride = p->x_cstride;
+    a.T = T;
+    a.len = dlen;
+    a.bias_b = dbb;
+    a.bias_b_stride = p->bias_b_stride;
+    a.out = dout + (size_t)row0 * op;
+    a.out_bstride = (int64_t)rows * op;
+    a.out_cstride = p->out_cstride;
+    a.out2 = dout2 ? dout2 + (size_t)row0 * op : nullptr;
+    a.res = dres;
+    a.res_bstride = (int64_t)Cr * op;
+    a.flags = flags;
+    a.slope = p->slope;
+    a.div = p->div;
+    a.oslope = p->oslope;
+    a.oslope2 = p->oslope2;
+    a.wn_split = p->wn_split;
+    a.out_pl = p->pl_rows ? dpl : nullptr;
+    a.pl_rows = p->pl_rows;
+    const bool name_was_on = g_launch_name_on;
+    g_launch_name_on = true;
+    g_launch_name[0] = 0;
+    const hipError_t le = launch_conv(a, d.cfg, B, nullptr);
+    g_launch_name_on = name_was_on;
+    TCHECK(le);
+    std::snprintf(p->kernel, sizeof p->kernel, "%s", g_launch_name);
+    p->cfg_used = d.cfg;
+    p->ck_used = d.CK;
+    if (p->pl_rows) sx_unblock_kernel<<<dim3((T + 255) / 256, p->pl_rows / 8, B), 256>>>(nullptr, dpl, dpo, p->pl_rows, T, 1);
+    TCHECK(hipGetLastError());
+    TCHECK(hipDeviceSynchronize());
+    TCHECK(download(p->out, dout, no));
+    if (p->out2) TCHECK(download(p->out2, dout2, no));
+    if (p->pl_rows) TCHECK(download(p->planes_out, dpo, (size_t)B * p->pl_rows * T));
+    return VITS_OK;
+}
+
+int vits_test_wn_gate(int device_id, const float *a, int B, int H, int T, int form, float *acts) {
+    if (int rc = test_dev(device_id)) return rc;
+    if (!a || !acts || B < 1 || H < 1 || T < 1 || (form != 0 && form != 1)) return fail(nullptr, VITS_E_ARG, "bad gate test arguments");
+    if (form == 1 && H % 8) return fail(nullptr, VITS_E_ARG, "the blocked gate reads cells of 8 channels: H %% 8 == 0");
+    const size_t na = (size_t)B * 2 * H * T, no = (size_t)B * H * T;
+    DevBufs D;
+    float *da = D.up(a, na, 16);
+    float *draw = D.alloc<float>(na, 16);
+    float *dacts = D.fill<float>(no, 0xff, 16);
+    TCHECK(D.err);
+    if (form == 1) {
+        sx_block_kernel<<<dim3((T + 255) / 256, 2 * H / 8, B), 256>>>(da, (int64_t)2 * H * T, T, nullptr, draw, 2 * H, T);
+        wn_gate_blocked_kernel<<<dim3((T + 255) / 256, H / 8, B), 256>>>(draw, dacts, H, T);
+    } else
+        wn_gate_kernel<<<dim3((T + 255) / 256, H, B), 256>>>(da, dacts, H, T);
+    TCHECK(hipGetLastError());
+    TCHECK(hipDeviceSynchronize());
+    TCHECK(download(acts, dacts, no));
+    return VITS_OK;
+}
+
+int vits_test_cond_matvec(int device_id, const float *emb_g, int n_speakers, int gin, const int64_t *sid, int B, const float *W,
+                          const float *bias, int rows, float *out) {
+    if (int rc = test_dev(device_id)) return rc;
+    if (!emb_g || !sid || !W || !out || n_speakers < 1 || gin < 1 || B < 1 || rows < 1)
+        return fail(nullptr, VITS_E_ARG, "bad conditioning test arguments");
+    DevBufs D;
+    float *dg = D.up(emb_g, (size_t)n_speakers * gin);
+    int64_t *dsid = D.up(sid, (size_t)B);
+    float *dW = D.up(W, (size_t)rows * gin);
+    float *db = bias ? D.up(bias, (size_t)rows) : nullptr;
+    float *dout = D.fill<float>((size_t)B * rows, 0xff);
+    TCHECK(D.err);
+    cond_matvec_kernel<<<dim3((rows + 63) / 64, B), 64>>>(dg, dsid, n_speakers, dW, db, dout, rows, gin);
+    TCHECK(hipGetLastError());
+    TCHECK(hipDeviceSynchronize());
+    TCHECK(download(out, dout, (size_t)B * rows));
+    return VITS_OK;
+}
+
 // the test hooks' format of a split-operand conv: two fp16 planes unless stated otherwise
 static TestPack sx_test_pack(SxPack::Planes planes = SxPack::F16X2) {
     TestPack o;

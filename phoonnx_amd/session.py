@@ -2352,6 +2352,88 @@ def test_conv1d_sx_planar(x, w, bias=None, dil=1, lens=None, old=None, row_split
     return out, pl
 
 
+# the f32 engine's flags by name (conv_engine.hip.hpp; include/vitsmi.h VITS_CONV_*)
+CONV_FLAGS = {"pro_lrelu": 1, "pro_mask": 2, "relu": 4, "mask": 8, "res": 16, "acc": 32, "div": 64, "coupling": 128, "wn": 256,
+              "wn_first": 512}
+CONV_EPI_SENTINEL = -1234.5678  # what the hook puts where it was given no old contents, and into every pitch column
+
+
+def test_conv1d_epi(x, w, bias=None, flags=(), dil=1, pad_l=None, stride=1, hint=0, cfg=None, ck=None, lens=None, bias_b=None,
+                    res=None, old_out=None, old_out2=None, out2=False, slope=0.1, div=1.0, oslope=1.0, oslope2=1.0, wn_split=0,
+                    x_cstride=0, out_cstride=0, out_rows=0, out_row0=0, pl_rows=0, device_id=0):
+    """The f32 conv engine with the argument set the pipeline's conv() gives it (include/vitsmi.h vits_test_conv1d_epi).
+    flags: names of CONV_FLAGS.  stride > 1: ConvTranspose1d, w [Cin, Cout, K].  cfg / ck: an explicit tile and chunk,
+    else the choice by `hint`.  old_out / old_out2 [B, out_rows, T * stride]: previous contents of the outputs; without
+    them, and in every pitch column, the outputs start as CONV_EPI_SENTINEL.  out2: second output wanted (implied by
+    old_out2).  Returns a dict: out / out2 [B, out_rows, out pitch] whole, planes [B, pl_rows, T] or None, kernel (the
+    instantiation launched), cfg, ck."""
+    lib = _ffi.load()
+    f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+    x, w, bias, bias_b, res, old_out, old_out2 = (f32(a) for a in (x, w, bias, bias_b, res, old_out, old_out2))
+    B, Cin, T = x.shape
+    Cout, K = (w.shape[1] if stride > 1 else w.shape[0]), w.shape[2]
+    ln = None if lens is None else np.ascontiguousarray(lens, np.int64)
+    rows, pitch = out_rows or Cout, out_cstride or T * stride
+    # (the hook reads these by the shapes it derives: whatever disagrees is refused here)
+    for name, arr, shape in (("w", w, (Cin, Cout, K) if stride > 1 else (Cout, Cin, K)), ("bias", bias, (Cout,)),
+                             ("res", res, (B, Cout, pitch)), ("old_out", old_out, (B, rows, T * stride)),
+                             ("old_out2", old_out2, (B, rows, T * stride)), ("lens", ln, (B,))):
+        if arr is not None and arr.shape != shape:
+            raise ValueError(f"{name} has shape {arr.shape}, the launch needs {shape}")
+    if bias_b is not None and (bias_b.ndim != 2 or bias_b.shape[0] != B):
+        raise ValueError(f"bias_b has shape {bias_b.shape}, the launch needs ({B}, stride)")
+    out = np.empty((B, rows, pitch), np.float32)
+    o2 = np.empty((B, rows, pitch), np.float32) if (out2 or old_out2 is not None) else None
+    pl = np.empty((B, pl_rows, T), np.float32) if pl_rows > 0 else None
+    a = _ffi.VitsTestConvEpiArgs()
+    a.B, a.Cin, a.T, a.Cout, a.K, a.dil, a.stride, a.hint = B, Cin, T, Cout, K, dil, stride, hint
+    a.pad_l = dil * (K - 1) // 2 if pad_l is None else pad_l
+    a.cfg, a.ck = (-1 if cfg is None else cfg), (-1 if ck is None else ck)
+    a.flags = sum(CONV_FLAGS[f] for f in flags)
+    a.slope, a.div, a.oslope, a.oslope2, a.wn_split = slope, div, oslope, oslope2, wn_split
+    a.x, a.w, a.bias, a.lens, a.bias_b, a.res = (_ffi.ptr(v) for v in (x, w, bias, ln, bias_b, res))
+    a.bias_b_stride = 0 if bias_b is None else bias_b.shape[1]
+    a.x_cstride, a.out_cstride, a.out_rows, a.out_row0 = x_cstride, out_cstride, out_rows, out_row0
+    a.old_out, a.old_out2, a.sentinel = _ffi.ptr(old_out), _ffi.ptr(old_out2), CONV_EPI_SENTINEL
+    a.out, a.out2, a.pl_rows, a.planes_out = _ffi.ptr(out), _ffi.ptr(o2), pl_rows, _ffi.ptr(pl)
+    rc = lib.vits_test_conv1d_epi(device_id, C.byref(a))
+    if rc != 0:
+        raise SessionError(_ffi.last_error(None))
+    return {"out": out, "out2": o2, "planes": pl, "kernel": a.kernel.decode(), "cfg": a.cfg_used, "ck": a.ck_used}
+
+
+def test_wn_gate(a, blocked=False, device_id=0):
+    """tanh(a[:, :H]) * sigmoid(a[:, H:]) of a [B, 2H, T]: wn_gate_kernel, or (blocked) wn_gate_blocked_kernel on the same
+    values in the raw cell layout.  -> [B, H, T]"""
+    lib = _ffi.load()
+    a = np.ascontiguousarray(a, np.float32)
+    B, C2, T = a.shape
+    if C2 % 2:
+        raise ValueError("a holds the tanh rows and as many sigmoid rows")
+    out = np.empty((B, C2 // 2, T), np.float32)
+    rc = lib.vits_test_wn_gate(device_id, _ffi.ptr(a), B, C2 // 2, T, 1 if blocked else 0, _ffi.ptr(out))
+    if rc != 0:
+        raise SessionError(_ffi.last_error(None))
+    return out
+
+
+def test_cond_matvec(emb_g, sid, W, bias=None, device_id=0):
+    """out[b] = bias + W @ emb_g[clamp(sid[b])] (cond_matvec_kernel); emb_g [n_speakers, gin], W [rows, gin] -> [B, rows]"""
+    lib = _ffi.load()
+    emb_g = np.ascontiguousarray(emb_g, np.float32)
+    W = np.ascontiguousarray(W, np.float32)
+    b = None if bias is None else np.ascontiguousarray(bias, np.float32)
+    sid = np.ascontiguousarray(sid, np.int64)
+    if emb_g.ndim != 2 or W.ndim != 2 or W.shape[1] != emb_g.shape[1] or sid.ndim != 1 or (b is not None and b.shape != W.shape[:1]):
+        raise ValueError("emb_g [n_speakers, gin], W [rows, gin], bias [rows], sid [B]")
+    out = np.empty((len(sid), W.shape[0]), np.float32)
+    rc = lib.vits_test_cond_matvec(device_id, _ffi.ptr(emb_g), emb_g.shape[0], emb_g.shape[1], _ffi.ptr(sid), len(sid),
+                                   _ffi.ptr(W), _ffi.ptr(b), W.shape[0], _ffi.ptr(out))
+    if rc != 0:
+        raise SessionError(_ffi.last_error(None))
+    return out
+
+
 def test_conv1d_sx_gate(x, w, bias, g, dil=1, small=False, planes=False, device_id=0):
     """The flow's WN in-layer with its gate epilogue: acts = tanh(a + g_a) * sigmoid(b + g_b) where (a | b) = conv(x) + bias
     ("same" padding), w [2H, Cin, K], bias [2H], g [B, 2H] in the module's channel order (modules.py:195-203,
