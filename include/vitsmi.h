@@ -1046,6 +1046,53 @@ int vits_test_cond_matvec(int device_id, const float *emb_g, int n_speakers, int
  * bit 16: s_memtime ticks per pipeline step spent in {LDS wait, DMA wait, barrier, DMA issue, loads + MFMA}. */
 int vits_test_conv1d_sx(int device_id, const float *x, int B, int Cin, int T, const float *w, const float *bias,
                         int Cout, int K, int dil, int pad_l, int flags, float slope, float *out);
+/* The split-operand engine (csrc/conv_sx_engine.hip.hpp) with the whole argument set the pipeline's conv_sx() gives a
+ * generator-form launch: arithmetic, packing options, the run tile, epilogue flags, the residual in each of its three
+ * forms, the accumulate operand, per-utterance bias, slopes, per-utterance tensor ends.  One launch of the engine's own
+ * launcher; every pointer is a host pointer, tensors are dense [B][C][T] and the hook converts to and from the engine's
+ * layouts.
+ *   value = conv(leaky_relu(x, islope)) + bias + bias_b[b], + res, + old_out, / div;
+ *   out stores leaky_relu(value, oslope), the planes leaky_relu(value, oslope2); utterance b's tensors end at
+ *   min(T, (lens[b] + rag_add) * rag_mul) columns (0 for lens[b] == 0): nothing behind is read or written.
+ * Both outputs start as `sentinel` (out: as old_out where given), so an element the launch did not write reads back as the
+ * sentinel - through the planes: as the value the planes of the sentinel hold.
+ * Refused with VITS_E_ARG, never launched: whatever launch_conv_sx() would refuse (see the field comments). */
+enum { VITS_SX_EPI_RES = 1, VITS_SX_EPI_ACC = 2, VITS_SX_EPI_DIV = 4, VITS_SX_EPI_NO_RAW_STORE = 8 };
+enum { VITS_SX_BF16X6 = 0, VITS_SX_F16X3 = 1, VITS_SX_F16 = 2 };
+typedef struct {
+    int B, Cin, T, Cout;     /* Cin % 16 == 0, Cout % 32 == 0; Cout: the module's channels (a transposed conv: before the shuffle) */
+    int K, dil, pad_l;       /* Conv1d: w [Cout][Cin][K]; pad_l + pad_r == dil * (K - 1) */
+    int stride;              /* 1 = Conv1d; > 1 = ConvTranspose1d, w [Cin][Cout][K], padding (K - stride) / 2 */
+    int precision;           /* VITS_SX_BF16X6 / F16X3 / F16 (one fp16 plane; Cin % 32 == 0) */
+    int force16, no_s16, min_cfg;  /* SxPack: the 16x16x32 packing also for <= 64 input channels; never that packing;
+                                    * smallest tile index */
+    int run_cfg;             /* -1: the packed tile; else the tile the launch runs on (the packed one is passed as pack_cfg):
+                              * no taller than the packed one, 3 only on the 16x16x32 loop, raw input only on its own */
+    int flags;               /* VITS_SX_EPI_*; NO_RAW_STORE: out is only the accumulate operand */
+    const float *x;          /* [B][Cin][T] */
+    const float *w, *bias;   /* bias [Cout] or NULL */
+    const float *res;        /* EPI_RES: [B][Cout][T * stride] fp32, or (res_planes) uploaded as the operand planes of
+                              * leaky_relu(res, res_slope) and un-activated on the way in (fp16 arithmetics, plane input; the
+                              * single-plane arithmetic has no other form) */
+    int res_is_x;            /* EPI_RES instead: the residual is the raw input's own device tensor (raw-input convs, Cin == Cout) */
+    int res_planes;
+    float res_slope;
+    const float *old_out;    /* [B][Cout][T * stride] previous contents of out (the EPI_ACC operand), or NULL */
+    const float *bias_b;     /* [B][bias_b_stride] or NULL; bias_b_stride >= Cout */
+    int bias_b_stride;
+    float div, oslope, oslope2, islope;  /* EPI_DIV; slopes of what out / the planes store and of the raw-input prologue
+                                          * (0 or 1 = none; islope on raw-input convs only) */
+    const int64_t *lens;     /* [B] in [0, T], or NULL: every utterance spans T */
+    int rag_add, rag_mul;    /* SxRagged::add / mul; rag_mul >= 1 */
+    float sentinel;
+    float *out;              /* [B][Cout][T * stride] as the launch left it, or NULL = no raw tensor */
+    float *planes_out;       /* [B][Cout][T * stride] read back from the output planes, or NULL = no plane output */
+    float *res_seen;         /* nullable, res_planes: leaky_relu(res, res_slope) as the residual planes hold it */
+    char kernel[128];        /* out: the instantiation launched (as in vits_launch_record) */
+    int pack_cfg, run_cfg_used, rawin, s16, ck;  /* out: what pack_conv_sx chose, the tile launched */
+    float peak;              /* out, fp16 arithmetics: the largest of the launch's 64 range-guard slots (SxArgs::peak) */
+} vits_test_conv_sx_epi_args;
+int vits_test_conv1d_sx_epi(int device_id, vits_test_conv_sx_epi_args *a);
 /* The planar epilogue of the split-operand engine (f16x3 arithmetic, 16x16x32 loop; "same" padding), as the flow's
  * res_skip / pre / post convs and the text encoder's convs use it: o = old + act(conv(x) + bias) * mask, rows
  * [0, row_split) into a first planar tensor, the rest into a second.  flags: 1 ReLU, 2 mask (t < lens[b]), 4 residual

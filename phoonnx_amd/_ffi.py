@@ -47,6 +47,19 @@ class VitsTestConvEpiArgs(C.Structure):
                 ("pl_rows", C.c_int), ("planes_out", C.c_void_p), ("kernel", C.c_char * 128), ("cfg_used", C.c_int), ("ck_used", C.c_int)]
 
 
+class VitsTestConvSxEpiArgs(C.Structure):
+    """vits_test_conv_sx_epi_args of include/vitsmi.h"""
+    _fields_ = [(n, C.c_int) for n in ("B", "Cin", "T", "Cout", "K", "dil", "pad_l", "stride", "precision", "force16", "no_s16",
+                                       "min_cfg", "run_cfg", "flags")] + \
+               [(n, C.c_void_p) for n in ("x", "w", "bias", "res")] + \
+               [("res_is_x", C.c_int), ("res_planes", C.c_int), ("res_slope", C.c_float), ("old_out", C.c_void_p),
+                ("bias_b", C.c_void_p), ("bias_b_stride", C.c_int)] + \
+               [(n, C.c_float) for n in ("div", "oslope", "oslope2", "islope")] + \
+               [("lens", C.c_void_p), ("rag_add", C.c_int), ("rag_mul", C.c_int), ("sentinel", C.c_float), ("out", C.c_void_p),
+                ("planes_out", C.c_void_p), ("res_seen", C.c_void_p), ("kernel", C.c_char * 128)] + \
+               [(n, C.c_int) for n in ("pack_cfg", "run_cfg_used", "rawin", "s16", "ck")] + [("peak", C.c_float)]
+
+
 class VitsOpenOptions(C.Structure):
     _fields_ = [("device_id", C.c_int), ("gen_precision", C.c_char_p), ("arena_dev", C.c_void_p),
                 ("arena_bytes", C.c_size_t), ("host_only", C.c_int), ("layout_only", C.c_int)]
@@ -153,7 +166,7 @@ EXPORTS = [
     "vits_stream_onset_check", "vits_stream_onset_start", "vits_run_chunked_enc_trimmed", "vits_run_vocoder_chunked_enc_trimmed",
     "vits_test_stream_pack_trimmed",
     "vits_test_layernorm", "vits_test_dds", "vits_test_cf_pre", "vits_test_rqs_inverse", "vits_test_ea_logw",
-    "vits_test_conv1d_epi", "vits_test_wn_gate", "vits_test_cond_matvec",
+    "vits_test_conv1d_epi", "vits_test_wn_gate", "vits_test_cond_matvec", "vits_test_conv1d_sx_epi",
 ]
 
 
@@ -329,6 +342,7 @@ def load():
     lib.vits_test_conv1d_sx_gate.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     lib.vits_bench_conv1d_sx.argtypes = [C.c_int] * 9 + [f32p]
     lib.vits_test_conv1d_epi.argtypes = [C.c_int, C.POINTER(VitsTestConvEpiArgs)]
+    lib.vits_test_conv1d_sx_epi.argtypes = [C.c_int, C.POINTER(VitsTestConvSxEpiArgs)]
     lib.vits_test_wn_gate.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     lib.vits_test_cond_matvec.argtypes = [C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp]
     lib.vits_test_conv_pair_sx.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int,

@@ -4173,6 +4173,157 @@ int vits_test_conv1d_sx(int device_id, const float *x, int B, int Cin, int T, co
     return run_test_conv_sx(d, arena, x, B, T, flags, slope, out);
 }
 
+// The split-operand engine with conv_sx()'s whole argument set (include/vitsmi.h): sx_args() plus the field assignments
+// conv_sx() makes, one launch_conv_sx() on the run tile asked for.  What launch_conv_sx() would refuse is refused here by
+// name; both outputs start as the sentinel (or the old contents), so what the launch did not write reads back unchanged.
+int vits_test_conv1d_sx_epi(int device_id, vits_test_conv_sx_epi_args *p) {
+    if (int rc = test_dev(device_id)) return rc;
+    if (!p) return fail(nullptr, VITS_E_ARG, "no arguments");
+    const auto bad = [](const char *why) { return fail(nullptr, VITS_E_ARG, "sx conv epilogue hook: %s", why); };
+    const int B = p->B, Cin = p->Cin, T = p->T, Cr = p->Cout, u = p->stride, flags = p->flags;
+    if (B < 1 || Cin < 1 || T < 1 || Cr < 1 || u < 1 || !p->x || !p->w) return bad("bad shape or missing tensor");
+    if (flags & ~(VITS_SX_EPI_RES | VITS_SX_EPI_ACC | VITS_SX_EPI_DIV | VITS_SX_EPI_NO_RAW_STORE)) return bad("unknown flag");
+    if (p->precision < VITS_SX_BF16X6 || p->precision > VITS_SX_F16) return bad("precision: bf16x6, f16x3 or f16");
+    if (Cin % 16 || Cr % 32) return bad("Cin % 16 == 0 and Cout % 32 == 0");
+    if (p->run_cfg < -1 || p->run_cfg > 3 || p->min_cfg < 0 || p->min_cfg > 3) return bad("tile configs are 0..3");
+    if (u == 1 && (p->K < 1 || p->dil < 1 || p->pad_l < 0 || p->pad_l > (int64_t)p->dil * (p->K - 1))) return bad("pad_l outside the receptive field");
+    const bool want_raw = p->out != nullptr, want_pl = p->planes_out != nullptr;
+    const bool f_res = flags & VITS_SX_EPI_RES, f_acc = flags & VITS_SX_EPI_ACC;
+    if (!want_raw && !want_pl) return bad("neither a raw nor a plane output");
+    if (f_acc && !want_raw) return bad("acc without a raw tensor (the accumulate operand is out's previous contents)");
+    if ((flags & VITS_SX_EPI_NO_RAW_STORE) && !want_raw) return bad("no_raw_store without a raw tensor");
+    if (p->old_out && !want_raw) return bad("old_out without a raw tensor");
+    const int res_forms = (p->res ? 1 : 0) + (p->res_is_x ? 1 : 0);
+    if (f_res && res_forms != 1) return bad("res needs exactly one form: a tensor (fp32, or as planes with res_planes) or res_is_x");
+    if (!f_res && (res_forms || p->res_planes)) return bad("a residual operand without the res flag");
+    if (p->res_planes && (!p->res || !(p->res_slope > 0.f))) return bad("res_planes needs the res tensor and res_slope > 0");
+    if (p->bias_b && p->bias_b_stride < Cr) return bad("bias_b rows shorter than Cout");
+    if (p->rag_mul < 1 && p->lens) return bad("rag_mul < 1");
+    if (p->lens)
+        for (int b = 0; b < B; b++)
+            if (p->lens[b] < 0 || p->lens[b] > T) return bad("lens outside [0, T]");
+    ConvDesc d;
+    std::vector<float> arena;
+    TestPack o;
+    o.sx.planes = p->precision == VITS_SX_F16 ? SxPack::F16X1 : (p->precision == VITS_SX_F16X3 ? SxPack::F16X2 : SxPack::BF16X3);
+    o.sx.force16 = p->force16 != 0;
+    o.sx.no_s16 = p->no_s16 != 0;
+    o.sx.min_cfg = p->min_cfg;
+    {
+        const std::string e = u > 1 ? pack_test_convT(p->w, p->bias, Cin, Cr, p->K, u, &d, &arena, true, o)
+                                    : pack_test_conv(p->w, p->bias, Cin, Cr, p->K, p->dil, p->pad_l, 3, &d, &arena, o);
+        if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
+    }
+    // ---- launch_conv_sx()'s refusals, by name
+    const int nprod = d.h1 ? 1 : (d.f16 ? 2 : 6), run = p->run_cfg >= 0 ? p->run_cfg : d.cfg;
+    if (d.rawin && run == 0) return bad("raw input on cfg 0: the raw-input kernels exist for the 64- and 32-row tiles only");
+    if (run == 3 && !d.s16) return bad("run_cfg 3 without s16: the 64 x 128 tile exists on the 16x16x32 loop only");
+    if (sx_tile_m(run) > sx_tile_m(d.cfg)) return bad("a run tile taller than the packed one");
+    if (!sx_tile_reads(d.cfg, run, d.s16) || d.Cout % sx_tile_m(run)) return bad("the run tile cannot read this packing");
+    if (d.rawin && run != d.cfg) return bad("a raw-input conv runs on the tile it was packed for");
+    if (!sx_stage(sx_tile_n(run), d.K, d.dil, nprod == 6 ? 3 : nprod, d.s16).fits) return bad("the x stage does not fit the run tile");
+    if (p->islope != 0.f && p->islope != 1.f && !d.rawin) return bad("islope on a plane-input conv (the raw-input prologue applies it)");
+    if (p->res_is_x && (!d.rawin || Cin != Cr || u != 1)) return bad("res_is_x needs a raw-input conv with Cin == Cout");
+    if (p->res_planes && d.rawin) return bad("res_planes on raw input: a raw-input conv reads its residual as fp32");
+    if (p->res_planes && nprod == 6) return bad("res_planes in bf16x6: only the fp16 arithmetics read a residual from planes");
+    if (f_res && nprod == 1 && !p->res_planes) return bad("the single-plane arithmetic reads its residual from a plane (res_planes)");
+    const int To = T * u, mode = d.h1 ? 2 : (d.f16 ? 1 : 0);
+    const size_t nx = (size_t)B * Cin * T, no = (size_t)B * Cr * To;
+    // host images: the raw output (old contents, else the sentinel), the sentinel whose planes pre-fill the plane output,
+    // the residual as its planes hold it
+    std::vector<float> ho(no, p->sentinel), hs(no, p->sentinel), hr;
+    if (p->old_out) std::memcpy(ho.data(), p->old_out, no * 4);
+    if (p->res_planes) {
+        hr.resize(no);
+        for (size_t i = 0; i < no; i++) hr[i] = p->res[i] >= 0.f ? p->res[i] : p->res[i] * p->res_slope;
+    }
+    std::vector<int> l32(B);
+    for (int b = 0; b < B; b++) l32[b] = p->lens ? (int)p->lens[b] : T;
+    DevBufs D;
+    float *dA = D.up(arena.data(), arena.size());
+    float *dx = D.up(p->x, nx, 16);
+    uint16_t *dxp = d.rawin ? nullptr : D.fill<uint16_t>(nx * 3, 0, 64);
+    float *dxr = d.rawin ? D.alloc<float>(nx, 64) : nullptr;
+    float *dimg = want_raw ? D.up(ho.data(), no, 16) : nullptr;
+    float *draw = want_raw ? D.alloc<float>(no, 64) : nullptr;
+    float *dsen = want_pl ? D.up(hs.data(), no, 16) : nullptr;
+    uint16_t *dop = want_pl ? D.fill<uint16_t>(no * 3, 0, 64) : nullptr;
+    float *dout = D.alloc<float>(no, 16);
+    float *dresin = p->res ? D.up(p->res_planes ? hr.data() : p->res, no, 16) : nullptr;
+    float *dres = (p->res && !p->res_planes) ? D.alloc<float>(no, 64) : nullptr;
+    uint16_t *dresp = p->res_planes ? D.fill<uint16_t>(no * 3, 0, 64) : nullptr;
+    float *dbb = p->bias_b ? D.up(p->bias_b, (size_t)B * p->bias_b_stride) : nullptr;
+    int *dlen = p->lens ? D.up(l32.data(), (size_t)B) : nullptr;
+    unsigned *dpk = mode ? D.fill<unsigned>((size_t)kSxPeakSlots * kSxPeakStride) : nullptr;
+    TCHECK(D.err);
+    const dim3 gin((T + 255) / 256, Cin / 8, B), gout((To + 255) / 256, Cr / 8, B);
+    if (d.rawin) sx_block_kernel<<<gin, 256>>>(dx, (int64_t)Cin * T, T, nullptr, dxr, Cin, T);
+    else sx_split_planes_kernel<<<gin, 256>>>(dx, (int64_t)Cin * T, T, nullptr, dxp, Cin, T, mode);
+    if (want_raw) sx_block_kernel<<<gout, 256>>>(dimg, (int64_t)Cr * To, To, nullptr, draw, Cr, To);
+    if (want_pl) sx_split_planes_kernel<<<gout, 256>>>(dsen, (int64_t)Cr * To, To, nullptr, dop, Cr, To, mode);
+    if (dres) sx_block_kernel<<<gout, 256>>>(dresin, (int64_t)Cr * To, To, nullptr, dres, Cr, To);
+    if (dresp) sx_split_planes_kernel<<<gout, 256>>>(dresin, (int64_t)Cr * To, To, nullptr, dresp, Cr, To, mode);
+    TCHECK(hipGetLastError());
+    SxArgs a = sx_args(d, dA, dA, T);  // (pack_test_* reserve a zero page at offset 0)
+    a.xp = reinterpret_cast<const u32x4 *>(dxp);
+    a.xr = dxr;
+    a.islope = p->islope;
+    a.bias_b = dbb;
+    a.bias_b_stride = p->bias_b_stride;
+    a.out_raw = draw;
+    a.out_pl = dop;
+    a.res = p->res_is_x ? dxr : dres;
+    a.res_pl = dresp;
+    a.res_unslope = p->res_planes ? 1.f / p->res_slope : 1.f;
+    a.flags = (f_res ? EPI_RES : 0) | (f_acc ? EPI_ACC : 0) | ((flags & VITS_SX_EPI_DIV) ? EPI_DIV : 0) |
+              ((flags & VITS_SX_EPI_NO_RAW_STORE) ? SX_NO_RAW_STORE : 0);
+    a.div = p->div == 0.f ? 1.f : p->div;
+    a.oslope = p->oslope;
+    a.oslope2 = p->oslope2;
+    a.rag = SxRagged{dlen, p->rag_add, p->rag_mul};
+    a.peak = dpk;
+    const bool name_was_on = g_launch_name_on;
+    g_launch_name_on = true;
+    g_launch_name[0] = 0;
+    const hipError_t le = launch_conv_sx(a, run, B, nullptr, d.rawin, nprod, d.cfg);
+    g_launch_name_on = name_was_on;
+    if (le != hipSuccess) return fail(nullptr, VITS_E_DEVICE, "sx conv epilogue hook: launch_conv_sx: %s", hipGetErrorString(le));
+    std::snprintf(p->kernel, sizeof p->kernel, "%s", g_launch_name);
+    p->pack_cfg = d.cfg;
+    p->run_cfg_used = run;
+    p->rawin = d.rawin ? 1 : 0;
+    p->s16 = d.s16 ? 1 : 0;
+    p->ck = d.CK;
+    p->peak = 0.f;
+    if (want_raw) {
+        sx_unblock_kernel<<<gout, 256>>>(draw, nullptr, dout, Cr, To, mode);
+        TCHECK(hipGetLastError());
+        TCHECK(hipDeviceSynchronize());
+        TCHECK(download(p->out, dout, no));
+    }
+    if (want_pl) {
+        sx_unblock_kernel<<<gout, 256>>>(nullptr, dop, dout, Cr, To, mode);
+        TCHECK(hipGetLastError());
+        TCHECK(hipDeviceSynchronize());
+        TCHECK(download(p->planes_out, dout, no));
+    }
+    if (dresp && p->res_seen) {
+        sx_unblock_kernel<<<gout, 256>>>(nullptr, dresp, dout, Cr, To, mode);
+        TCHECK(hipGetLastError());
+        TCHECK(hipDeviceSynchronize());
+        TCHECK(download(p->res_seen, dout, no));
+    }
+    TCHECK(hipDeviceSynchronize());
+    if (dpk) {
+        std::vector<unsigned> slots((size_t)kSxPeakSlots * kSxPeakStride);
+        TCHECK(download(slots.data(), dpk, slots.size()));
+        unsigned top = 0;
+        for (int s = 0; s < kSxPeakSlots; s++) top = std::max(top, slots[(size_t)s * kSxPeakStride]);
+        std::memcpy(&p->peak, &top, 4);
+    }
+    return VITS_OK;
+}
+
 int vits_test_conv1d_sx_planar(int device_id, const float *x, int B, int Cin, int T, const float *w, const float *bias,
                                int Cout, int K, int dil, int flags, const int64_t *lens, const float *old, int row_split,
                                int pl_rows, float *out, float *planes_out) {

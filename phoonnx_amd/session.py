@@ -2402,6 +2402,56 @@ def test_conv1d_epi(x, w, bias=None, flags=(), dil=1, pad_l=None, stride=1, hint
     return {"out": out, "out2": o2, "planes": pl, "kernel": a.kernel.decode(), "cfg": a.cfg_used, "ck": a.ck_used}
 
 
+# the split-operand engine's epilogue flags and arithmetics by name (include/vitsmi.h VITS_SX_*)
+SX_EPI_FLAGS = {"res": 1, "acc": 2, "div": 4, "no_raw_store": 8}
+SX_PRECISIONS = {"bf16x6": 0, "f16x3": 1, "f16": 2}
+
+
+def test_conv1d_sx_epi(x, w, bias=None, flags=(), precision="f16x3", dil=1, pad_l=None, stride=1, force16=False, no_s16=False,
+                       min_cfg=0, run_cfg=-1, res=None, res_is_x=False, res_planes=False, res_slope=1.0, old_out=None,
+                       bias_b=None, div=1.0, oslope=1.0, oslope2=1.0, islope=1.0, raw=True, planes=False, lens=None,
+                       rag_add=0, rag_mul=1, sentinel=CONV_EPI_SENTINEL, device_id=0):
+    """The split-operand conv engine with the argument set the pipeline's conv_sx() gives a generator-form launch
+    (include/vitsmi.h vits_test_conv1d_sx_epi).  flags: names of SX_EPI_FLAGS.  stride > 1: ConvTranspose1d, w [Cin, Cout, K].
+    res: fp32 [B, Cout, T * stride], or with res_planes the same tensor uploaded as operand planes of leaky_relu(res,
+    res_slope); res_is_x: the raw input's own device tensor.  raw / planes: which outputs exist; both start as `sentinel`
+    (raw: as old_out where given).  Returns a dict: out, planes [B, Cout, T * stride] or None, res_seen (what the residual
+    planes hold, or None), kernel (the instantiation launched), pack_cfg, run_cfg, rawin, s16, ck, peak."""
+    lib = _ffi.load()
+    f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+    x, w, bias, bias_b, res, old_out = (f32(a) for a in (x, w, bias, bias_b, res, old_out))
+    B, Cin, T = x.shape
+    Cout, K = (w.shape[1] if stride > 1 else w.shape[0]), w.shape[2]
+    To = T * stride
+    ln = None if lens is None else np.ascontiguousarray(lens, np.int64)
+    # (the hook reads these by the shapes it derives: whatever disagrees is refused here)
+    for name, arr, shape in (("w", w, (Cin, Cout, K) if stride > 1 else (Cout, Cin, K)), ("bias", bias, (Cout,)),
+                             ("res", res, (B, Cout, To)), ("old_out", old_out, (B, Cout, To)), ("lens", ln, (B,))):
+        if arr is not None and arr.shape != shape:
+            raise ValueError(f"{name} has shape {arr.shape}, the launch needs {shape}")
+    if bias_b is not None and (bias_b.ndim != 2 or bias_b.shape[0] != B):
+        raise ValueError(f"bias_b has shape {bias_b.shape}, the launch needs ({B}, stride)")
+    out = np.empty((B, Cout, To), np.float32) if raw else None
+    pl = np.empty((B, Cout, To), np.float32) if planes else None
+    seen = np.empty((B, Cout, To), np.float32) if (res_planes and res is not None) else None
+    a = _ffi.VitsTestConvSxEpiArgs()
+    a.B, a.Cin, a.T, a.Cout, a.K, a.dil, a.stride = B, Cin, T, Cout, K, dil, stride
+    a.pad_l = dil * (K - 1) // 2 if pad_l is None else pad_l
+    a.precision, a.force16, a.no_s16, a.min_cfg, a.run_cfg = SX_PRECISIONS[precision], int(force16), int(no_s16), min_cfg, run_cfg
+    a.flags = sum(SX_EPI_FLAGS[f] for f in flags)
+    a.x, a.w, a.bias, a.res, a.old_out, a.bias_b, a.lens = (_ffi.ptr(v) for v in (x, w, bias, res, old_out, bias_b, ln))
+    a.res_is_x, a.res_planes, a.res_slope = int(res_is_x), int(res_planes), res_slope
+    a.bias_b_stride = 0 if bias_b is None else bias_b.shape[1]
+    a.div, a.oslope, a.oslope2, a.islope = div, oslope, oslope2, islope
+    a.rag_add, a.rag_mul, a.sentinel = rag_add, rag_mul, sentinel
+    a.out, a.planes_out, a.res_seen = _ffi.ptr(out), _ffi.ptr(pl), _ffi.ptr(seen)
+    rc = lib.vits_test_conv1d_sx_epi(device_id, C.byref(a))
+    if rc != 0:
+        raise SessionError(_ffi.last_error(None))
+    return {"out": out, "planes": pl, "res_seen": seen, "kernel": a.kernel.decode(), "pack_cfg": a.pack_cfg, "run_cfg": a.run_cfg_used,
+            "rawin": bool(a.rawin), "s16": bool(a.s16), "ck": a.ck, "peak": float(a.peak)}
+
+
 def test_wn_gate(a, blocked=False, device_id=0):
     """tanh(a[:, :H]) * sigmoid(a[:, H:]) of a [B, 2H, T]: wn_gate_kernel, or (blocked) wn_gate_blocked_kernel on the same
     values in the raw cell layout.  -> [B, H, T]"""
