@@ -431,6 +431,83 @@ int vits_set_output_rates(vits_handle *h, int in_rate, const int32_t *out_rates,
  * vits_last_sample_counts.  Writes min(n, B) values, returns B. */
 int vits_last_sample_rates(vits_handle *h, int32_t *buf, int n);
 
+/* ---- intonation: a value in semitones per token, rendered by a time warp on the device -------------------------------
+ * VITS has no F0 input.  The engine raises or lowers a token by the classical RESAMPLING shift: token t is rendered longer
+ * by r_t = 2^(semitones / 12) (the existing token_rate path) and then played back r_t times faster by a windowed-sinc
+ * interpolator of the resampler's design whose speed changes from token to token.  The tempo is what it was, every frequency
+ * of the token is multiplied by r_t - the formants move with the fundamental.  Good for a few semitones; it is not PSOLA
+ * and preserves no formants.  The reference has no counterpart; the definition below is the specification.  ("pitch" in
+ * this code base is a row stride: the control is called semitones, the mechanism the warp.)
+ *
+ * Constants: Z = 16, beta = 8.555504641634386, rho = 0.85 as the resampler's; R = 512; FB = 16, ONE = 1 << FB.  All
+ * position arithmetic is int64: an input position is a Q16 number.
+ * Prototype: g(u) = sinc(u) * kaiser(u / Z) for 0 <= u < Z, else 0; the table G[i] = (float)g(i / R), i = 0 .. Z*R + 1,
+ *   computed in double and rounded once (G[Z*R] = G[Z*R + 1] = 0).
+ * Token t at st = semitones[b][t], finite with |st| <= 12:
+ *   r = 2^(st / 12) in double;  step = llrint(r * ONE);  s = rho * min(1, ONE / step) in double;  c = llrint(s * ONE);
+ *   Kh = ceil(Z * ONE / c) in integers                    (19 half-taps for st <= 0, 38 at +12)
+ * Plan of a row (pure host code; D_t the row's rendered durations in frames, hop): pos = 0 (Q16), n = 0, cum = 0; tokens
+ *   behind lens[b] and tokens with D_t == 0 are skipped; for every other token cum += D_t, P = (cum * hop) << FB,
+ *   k = ceil((P - pos) / step) (0 if P <= pos), the segment {n0 = n, pos0 = pos, step, c, Kh, k} is recorded, n += k,
+ *   pos += k * step.  The overshoot of pos past P is carried into the next token: phase is continuous, nothing is reset.
+ *   N_b = n; token t's OUTPUT SPAN is [n0, n0 + k).  A row without a segment has N_b = n_b and is an identity row.
+ * Output sample n of a segment: pos = pos0 + (n - n0) * step, i0 = pos >> FB, and for m = i0 - Kh + 1 .. i0 + Kh, ascending:
+ *   dq = |(m << FB) - pos|,  v = dq * c,  i = v >> 23,  f = (float)(v & 0x7FFFFF) * 2^-23 (exact),
+ *   w = i < Z*R ? fmaf(f, G[i+1] - G[i], G[i]) : 0,  acc = fmaf(w, x[b][m], acc) from 0.0f,
+ *   where x[b][m] reads 0 outside [0, n_b);  y[b][n] = (float)(c / 65536.0) * acc.
+ *   y[b][n] = 0.0f exactly for n >= N_b; the buffer is [B][S_w], S_w = max(1, max_b N_b).
+ * Identity rows: a row whose tokens all have step == ONE is a masked copy - bit for bit its native row, zeros behind n_b.
+ * (In float64 with the table's linear interpolation this design passes a tone at 0.15 * min(1, 1/r) cycles per sample at r
+ * times its frequency within 1.8e-5 of amplitude 1 for st in {+-1, +-3, +-7, +-12}; the interpolation costs at most
+ * 1.6e-6 against the exact kernel; a tone that lands at 0.6 of the output rate leaves 2.2e-5; max s * sum|w| is 1.95,
+ * below the 1.98 the tests' tolerance counts with.)
+ * Limits: N_b must fit in int; at most T segments per row.  A violation is VITS_E_ARG naming the row and the token; the
+ * semitones are checked before anything is enqueued, and a refused call leaves the previous run readable.
+ *
+ * vits_run_async_warped is vits_run_async_ctl with the intonation on top.
+ *   compensate = 1: token t's duration multiplier becomes token_rate[b][t] * (float)r_t (token_rate 1.0f where
+ *     ctl->token_rate is NULL) - one fp32 product on the host, then the token_rate path unchanged: the run's durations, frame
+ *     counts, z and native waveform are bit for bit those of vits_run_async_ctl with that rate array.  Together with forced
+ *     durations it is VITS_E_ARG: forced durations are the rendered ones.
+ *   compensate = 0: ctl passes through untouched - the pure warp: a raised token is also shorter.
+ *   Not warped: with into == NULL, token_semitones == NULL or every semitone (in front of lens[b]) == 0.0f the call is
+ *     vits_run_async_ctl, bit for bit: no warp is planned or launched.
+ * The warp runs behind the generator: the plans are built from the host copy of the durations (vits_last_durations'), which
+ * exists before the generator is enqueued - no synchronisation is added -, the segment records are uploaded, and one launch
+ * writes [B][S_w] into the staging slab, where the resampled waveform of a run with an output rate lives.  Afterwards
+ *   vits_last_sample_counts (N_b), vits_fetch_output, vits_last_pcm16 and every vits_deliver* work on the warped buffer as
+ *     they stand; vits_last_y_lengths, vits_last_durations and vits_tap stay in frames;
+ *   vits_last_token_spans answers k per token.
+ * Out of scope: a warped run with an output rate or per-row output rates set is VITS_E_ARG ("not covered with an output
+ * rate set") - folding the rate into step is a follow-up; the chunked and the device-pointer entries have no warped form (a
+ * carry for chunks is a follow-up); the speed is constant per token: no glides between tokens; formants are not preserved;
+ * vits_reserve does not count the warped buffer: a warped run grows the staging slab on demand, as any unreserved run does. */
+typedef struct {
+    int64_t n0;          /* first output sample of the segment */
+    int64_t pos0;        /* Q16 input position of that sample */
+    int64_t k;           /* output samples: the token's span is [n0, n0 + k) */
+    int32_t step;        /* Q16 input samples per output sample */
+    int32_t c;           /* Q16 cutoff s */
+    int32_t half_taps;   /* Kh */
+    int32_t pad_;        /* 0 */
+} vits_warp_seg;         /* 40 bytes */
+typedef struct {
+    const float *token_semitones; /* host [B][T]; positions behind lens[b] ignored */
+    int compensate;               /* 1: tempo kept (above); 0: the pure warp */
+} vits_intonation;
+int vits_run_async_warped(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
+                          const vits_noise *noise, const vits_controls *ctl, const vits_intonation *into);
+/* k per token of the last warped run, [B][T] (0 for a dropped token and behind lens[b]): host state, valid as soon as
+ * vits_run_async_warped returns.  Writes min(n_elems, B * T) values and returns B * T; VITS_E_ARG after an unwarped run. */
+int vits_last_token_spans(vits_handle *h, int64_t *buf, size_t n_elems);
+/* The plan - pure host code, no handle, no device.  vits_warp_token: a token's step, cutoff c and half-taps (each pointer may
+ * be NULL); VITS_E_ARG for a value that is not finite or outside [-12, 12].  vits_warp_plan: one row of len tokens (semitones
+ * NULL: all 0); segs == NULL asks for the counts; spans (nullable) [len] receives k per token; *n_out receives N_b.  Returns
+ * the number of segments (<= len), or VITS_E_ARG naming the token. */
+int vits_warp_token(float semitones, int64_t *step, int64_t *cutoff, int32_t *half_taps);
+int vits_warp_plan(const int64_t *durations, const float *semitones, int len, int hop, vits_warp_seg *segs, int64_t *spans,
+                   int64_t *n_out);
+
 /* ---- delivery: the last run's audio packed per request on the device - PCM16, G.711, F32, pauses -------------------
  * The reference post-processes and frames every sentence on the host (phoonnx/voice.py:271-282 peak-normalise / volume /
  * clip, :88-91 int16, :307-326 the pause in front of a sentence); this does it for a whole batch in one operation: read the
@@ -1145,6 +1222,11 @@ int vits_test_resample_pieces(int device_id, const float *x, const int64_t *lens
  * S_out = max_b N_b (y_elems >= B * S_out), every column written. */
 int vits_test_resample_rows(int device_id, const float *x, const int64_t *lens, int B, int S, int in_rate,
                             const int32_t *out_rates, float *y, size_t y_elems, int64_t *n_out);
+/* The time warp by value ("intonation"): x [B][S] host, counts [B] the rows' valid samples (clipped to [0, S]), the rows'
+ * segment records - row b's are segs[seg_first[b] .. seg_first[b + 1]) -, y [B][S_w] with S_w >= max(1, max_b N_b); every
+ * column of y is written.  Records that do not continue their row (n0, pos0) or leave a token's limits are VITS_E_ARG. */
+int vits_test_warp(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_warp_seg *segs,
+                   const int32_t *seg_first /* [B+1] */, float *y, int S_w);
 
 /* The kernels that turn tokens into frames and frames into samples, by value.  Every hook checks its sizes and extents on the
  * host (VITS_E_ARG) and launches the pipeline's kernel with the pipeline's grid.

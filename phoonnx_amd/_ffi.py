@@ -69,6 +69,16 @@ class VitsControls(C.Structure):
     _fields_ = [("scales_rows", C.c_void_p), ("seeds", C.c_void_p), ("durations", C.c_void_p), ("token_rate", C.c_void_p)]
 
 
+class VitsWarpSeg(C.Structure):
+    """vits_warp_seg: one token's segment of a warped row (vitsmi.h, "intonation"); 40 bytes"""
+    _fields_ = [("n0", C.c_int64), ("pos0", C.c_int64), ("k", C.c_int64), ("step", C.c_int32), ("c", C.c_int32),
+                ("half_taps", C.c_int32), ("pad_", C.c_int32)]
+
+
+class VitsIntonation(C.Structure):
+    _fields_ = [("token_semitones", C.c_void_p), ("compensate", C.c_int)]
+
+
 class VitsSegment(C.Structure):
     _fields_ = [("row", C.c_int32), ("stream", C.c_int32), ("lead_samples", C.c_int64), ("normalize", C.c_int32),
                 ("volume", C.c_float)]
@@ -153,6 +163,7 @@ EXPORTS = [
     "vits_run_async_ctl", "vits_run_chunked_ctl", "vits_last_durations",
     "vits_set_output_rate", "vits_last_sample_counts", "vits_resample_plan", "vits_test_resample", "vits_test_resample_pieces",
     "vits_set_output_rates", "vits_last_sample_rates", "vits_test_resample_rows",
+    "vits_run_async_warped", "vits_last_token_spans", "vits_warp_token", "vits_warp_plan", "vits_test_warp",
     "vits_test_durations", "vits_test_expand_prior", "vits_test_fill_normal", "vits_test_fill_normal_rows", "vits_test_post_conv",
     "vits_delivery_plan", "vits_deliver", "vits_test_deliver",
     "vits_trim_range", "vits_delivery_plan_trimmed", "vits_deliver_trimmed", "vits_test_deliver_trimmed",
@@ -265,6 +276,12 @@ def load():
     lib.vits_set_output_rates.argtypes = [vp, C.c_int, vp, C.c_int]
     lib.vits_last_sample_rates.argtypes = [vp, vp, C.c_int]
     lib.vits_test_resample_rows.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_size_t, vp]
+    lib.vits_run_async_warped.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.POINTER(VitsNoise), C.POINTER(VitsControls),
+                                          C.POINTER(VitsIntonation)]
+    lib.vits_last_token_spans.argtypes = [vp, i64p, C.c_size_t]
+    lib.vits_warp_token.argtypes = [C.c_float, i64p, i64p, C.POINTER(C.c_int32)]
+    lib.vits_warp_plan.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, i64p]
+    lib.vits_test_warp.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int]
     lib.vits_test_durations.argtypes = [C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp, vp]
     lib.vits_test_expand_prior.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int64, C.c_int,
                                            C.c_float, vp, vp, vp]

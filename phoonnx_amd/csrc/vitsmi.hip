@@ -35,6 +35,7 @@
 #include "stream_run.hip.hpp"
 #include "stream_shape.hip.hpp"
 #include "test_dev.hip.hpp"
+#include "warp.hip.hpp"
 #include "workspace.hpp"
 
 using namespace vitsmi;
@@ -149,6 +150,15 @@ struct vits_handle {
     std::vector<int32_t> run_rates;
     std::vector<int64_t> run_L, run_M;
     bool last_vocoder = false;          // the last run was vocoder-only: every row has F frames, h_ylen is not its
+    // Intonation (vits_run_async_warped): the prototype table on the device (made by the first warped run), the pinned buffer
+    // a run's plan is uploaded from, and what the last warped run left for the host: its rows' output counts N_b - empty
+    // after every other run - and k per token [B][T].  The warped waveform lives in the staging slab as a resampled one does
+    // (out_resampled, d_nout, rs_run_K = 0).
+    float *warp_G = nullptr;
+    char *warp_pin = nullptr;
+    size_t warp_pin_cap = 0;
+    std::vector<int64_t> warp_counts, warp_spans;
+    int warp_T = 0;
 };
 
 // chunked rendering (vits_run_chunked / vits_run_vocoder_chunked): where the audio goes
@@ -281,6 +291,8 @@ void forget_results_in(vits_handle *h, const Slab &s) {
 
 // a run that begins is not (yet) one with a rate per row
 void forget_row_run(vits_handle *h) {
+    h->warp_counts.clear();  // (nor a warped one)
+    h->warp_spans.clear();
     h->run_rates.clear();
     h->run_L.clear();
     h->run_M.clear();
@@ -1265,6 +1277,9 @@ struct RunRows {
     const uint64_t *d_seeds = nullptr;
     const int64_t *d_durations = nullptr;
     const float *d_token_rate = nullptr;
+    // vits_intonation (validated by vits_run_async_warped): host [B][T] semitones of a run that is warped, and its host lens
+    const float *semitones = nullptr;
+    const int64_t *semitone_lens = nullptr;
     float at(int b, int col) const { return scales[(rows ? (int64_t)b * 3 : 0) + col]; }
     bool any(int B, int col) const {  // some utterance's value is not 0
         for (int b = 0; b < (rows ? B : 1); b++)
@@ -2011,6 +2026,84 @@ int resample_rows_run(vits_handle *h, const int *ylen, int B) {
     return 0;
 }
 
+// ---- intonation (vits_run_async_warped): the rendered waveform warped on the device (warp.hip.hpp)
+
+// The whole waveform a run has just rendered (h->d_out, rows of h->S samples) -> [B][S_w], every token played back at its own
+// speed.  The plans come from the host copy of the durations, which the run's one readback left: no synchronisation.
+// d_out / S describe the warped buffer afterwards, as after resample_run.
+int warp_run(vits_handle *h, const RunRows &rr, int B, int T) {
+    const int S = h->S, hop = h->model.hop;
+    if (h->h_dur_B != B || h->h_dur_T != T) return fail(h, VITS_E_ARG, "no durations to plan the warp from");
+    std::vector<vits_warp_seg> segs;
+    std::vector<int32_t> first((size_t)B + 1, 0);
+    std::vector<int64_t> spans((size_t)B * T, 0), n_in((size_t)B), dur((size_t)T);
+    for (int b = 0; b < B; b++) {
+        const int L = (int)rr.semitone_lens[b];
+        for (int t = 0; t < L; t++) dur[t] = (int64_t)h->h_dur[(size_t)b * T + t];
+        const size_t at = segs.size();
+        segs.resize(at + (size_t)L);
+        int64_t ns = 0, N = 0;
+        const std::string e = warp_plan(dur.data(), rr.semitones + (size_t)b * T, L, hop, segs.data() + at, spans.data() + (size_t)b * T, ns, N);
+        if (!e.empty()) return fail(h, VITS_E_ARG, "row %d, %s", b, e.c_str());
+        segs.resize(at + (size_t)ns);
+        first[(size_t)b + 1] = (int32_t)segs.size();
+        const int64_t n = (int64_t)h->h_ylen[b] * hop;
+        n_in[b] = n < 0 ? 0 : (n > S ? S : n);
+    }
+    std::vector<WarpRow> rows;
+    const int64_t S_w = warp_rows(segs.data(), first.data(), n_in.data(), B, rows);
+    if (S_w > INT_MAX) return fail(h, VITS_E_ARG, "a warped row of %lld samples: more than a row admits (%d)", (long long)S_w, INT_MAX);
+    WarpBufs wb;
+    if (int rc = slab_carve(h, h->io, "staging", [&](Carver &cv) { wb = carve_warp(cv, B, (int)S_w, (int64_t)segs.size()); })) return rc;
+    hipStream_t st = h->stream;
+    if (!h->warp_G) {
+        std::vector<float> G(kWarpTable);
+        warp_table(G.data());
+        HIPCHECK(h, hipMalloc((void **)&h->warp_G, sizeof(float) * kWarpTable));
+        HIPCHECK(h, hipMemcpy(h->warp_G, G.data(), sizeof(float) * kWarpTable, hipMemcpyHostToDevice));
+    }
+    // [segs | rows | n_out] in pinned memory (the copies out of it that the previous run queued completed with this run's readback)
+    const size_t need = wb.plan_bytes + (size_t)B * sizeof(int);
+    if (h->warp_pin_cap < need) {
+        if (h->warp_pin) hipHostFree(h->warp_pin);
+        h->warp_pin = nullptr;
+        h->warp_pin_cap = 0;
+        const size_t cap = need < 65536 ? 65536 : need + need / 4;
+        HIPCHECK(h, hipHostMalloc((void **)&h->warp_pin, cap));
+        h->warp_pin_cap = cap;
+    }
+    const size_t seg_bytes = segs.size() * sizeof(vits_warp_seg);
+    if (seg_bytes) std::memcpy(h->warp_pin, segs.data(), seg_bytes);
+    std::memcpy(h->warp_pin + seg_bytes, rows.data(), (size_t)B * sizeof(WarpRow));
+    int *pin_nout = reinterpret_cast<int *>(h->warp_pin + wb.plan_bytes);
+    for (int b = 0; b < B; b++) pin_nout[b] = rows[(size_t)b].n_out;
+    HIPCHECK(h, hipMemcpyAsync(wb.segs, h->warp_pin, wb.plan_bytes, hipMemcpyHostToDevice, st));
+    HIPCHECK(h, hipMemcpyAsync(wb.front.n_out, pin_nout, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
+    WarpArgs a{};
+    a.segs = wb.segs;
+    a.rows = wb.rows;
+    a.G = h->warp_G;
+    a.x = h->d_out;
+    a.x_pitch = S;
+    a.y = wb.front.out;
+    a.y_pitch = S_w;
+    a.n_hi = (int)S_w;
+    const hipError_t e = launch_warp(a, B, st);
+    if (e != hipSuccess) return fail(h, VITS_E_DEVICE, "warp launch failed: %s", hipGetErrorString(e));
+    h->stats.total_launches += 1;
+    h->d_out = wb.front.out;
+    h->S = (int)S_w;
+    h->d_nout = wb.front.n_out;
+    h->rs_run_K = 0;
+    h->rs_run_L = h->rs_run_M = 1;
+    h->out_resampled = true;
+    h->warp_counts.resize((size_t)B);
+    for (int b = 0; b < B; b++) h->warp_counts[(size_t)b] = rows[(size_t)b].n_out;
+    h->warp_spans = std::move(spans);
+    h->warp_T = T;
+    return 0;
+}
+
 // The two pinned buffers (vits_handle::ring) finished pieces reach the host through.  A piece is copied into slot(); queue()
 // records the slot's event, hands the piece queued before it to the caller - whose callback so runs while this one renders -
 // and moves on to the other slot.  A piece that delivers nothing is never queued and the ring does not move: the pending slot,
@@ -2525,6 +2618,8 @@ void vits_close(vits_handle *h) {
         if (h->frm.base) hipFree(h->frm.base);
         if (h->io.base) hipFree(h->io.base);
         if (h->rs.table) hipFree(h->rs.table);
+        if (h->warp_G) hipFree(h->warp_G);
+        if (h->warp_pin) hipHostFree(h->warp_pin);
         row_rates_drop(h);
         if (h->pin.base) hipHostFree(h->pin.base);
         if (h->d_range) hipFree(h->d_range);
@@ -2791,7 +2886,12 @@ int vits_last_sample_counts(vits_handle *h, int64_t *buf, int n) {
     const int B = (int)h->h_ylen.size();
     const int64_t hop = h->model.hop;
     const bool rows = !h->last_vocoder && (int)h->run_L.size() == B;  // the last run had a rate per row: at ITS rates
+    const bool warped = !h->last_vocoder && (int)h->warp_counts.size() == B && B > 0;  // ... was warped: its plan's counts
     for (int b = 0; b < B && b < n && buf; b++) {
+        if (warped) {
+            buf[b] = h->warp_counts[b];
+            continue;
+        }
         const int64_t s = (int64_t)h->h_ylen[b] * hop;
         buf[b] = rows ? (s * h->run_L[b] + h->run_M[b] - 1) / h->run_M[b] : h->rs.plan.on() ? h->rs.plan.count(s) : s;
     }
@@ -2970,6 +3070,8 @@ static int run_device_locked(vits_handle *h, const int64_t *ids, const int64_t *
         if (int rc = resample_run(h, h->d_ylen, B)) return rc;
     if (h->rows.on() && !sink)
         if (int rc = resample_rows_run(h, h->d_ylen, B)) return rc;
+    if (rr.semitones && !sink)
+        if (int rc = warp_run(h, rr, B, T)) return rc;
     ylen_to_i64<<<(B + 63) / 64, 64, 0, h->stream>>>(h->d_ylen, h->d_ylen64, B);
     range_end(h);
     if (out) {
@@ -3315,6 +3417,84 @@ int vits_run_async_ctl(vits_handle *h, const int64_t *ids, const int64_t *lens, 
     return run_async_locked(h, ids, lens, B, T, rr, sid, noise, &dev);
 }
 
+// vits_run_async_ctl with the intonation on top (vitsmi.h, "intonation").  What is pure host code - the semitones, the
+// contradictions, the rates that are set - is answered before the device is looked at: a host-only handle answers it too.
+int vits_run_async_warped(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
+                          const vits_noise *noise, const vits_controls *ctl, const vits_intonation *into) {
+    if (!h) return VITS_E_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!ctl) return fail(h, VITS_E_ARG, "null argument");
+    const float *sem = into ? into->token_semitones : nullptr;
+    bool warped = false;
+    if (sem) {
+        if (B <= 0 || T <= 0) return fail(h, VITS_E_ARG, "empty batch or sequence (B=%d, T=%d)", B, T);
+        if (!lens) return fail(h, VITS_E_ARG, "null argument");
+        for (int b = 0; b < B; b++) {
+            if (lens[b] < 0 || lens[b] > T) return fail(h, VITS_E_ARG, "input_lengths[%d]=%lld outside [0,%d]", b, (long long)lens[b], T);
+            for (int t = 0; t < (int)lens[b]; t++) {
+                const float v = sem[(int64_t)b * T + t];
+                int64_t step, c;
+                int32_t Kh;
+                if (!warp_token(v, step, c, Kh))
+                    return fail(h, VITS_E_ARG, "token_semitones[%d,%d]=%g is not a finite value within [-12, 12]", b, t, (double)v);
+                warped = warped || v != 0.f;
+            }
+        }
+    }
+    vits_controls c2 = *ctl;
+    std::vector<float> rate;
+    if (warped) {
+        if (into->compensate && ctl->durations)
+            return fail(h, VITS_E_ARG, "compensate and forced durations are contradictory: forced durations are the rendered ones");
+        if (h->rs.plan.on() || h->rows.on()) return fail(h, VITS_E_ARG, "vits_run_async_warped is not covered with an output rate set");
+        if (into->compensate) {  // the duration multiplier of token t: token_rate * (float)r_t, one fp32 product
+            rate.assign((size_t)B * T, 1.0f);
+            for (int b = 0; b < B; b++)
+                for (int t = 0; t < (int)lens[b]; t++) {
+                    const size_t i = (size_t)b * T + t;
+                    rate[i] = (ctl->token_rate ? ctl->token_rate[i] : 1.0f) * (float)std::exp2((double)sem[i] / 12.0);
+                }
+            c2.token_rate = rate.data();
+        }
+    }
+    if (int rc = check_dev(h)) return rc;
+    RunRows rr;
+    if (int rc = host_controls(h, &c2, lens, B, T, rr)) return rc;
+    if (warped) {
+        rr.semitones = sem;
+        rr.semitone_lens = lens;
+    }
+    vits_output dev{};
+    return run_async_locked(h, ids, lens, B, T, rr, sid, noise, &dev);
+}
+
+int vits_last_token_spans(vits_handle *h, int64_t *buf, size_t n_elems) {
+    if (!h) return VITS_E_ARG;
+    const size_t n = h->warp_spans.size();
+    if (n == 0 || h->warp_counts.empty()) return fail(h, VITS_E_ARG, "the last run was not warped: no token spans to report");
+    for (size_t i = 0; i < n && i < n_elems && buf; i++) buf[i] = h->warp_spans[i];
+    return (int)n;
+}
+
+int vits_warp_token(float semitones, int64_t *step, int64_t *cutoff, int32_t *half_taps) {
+    int64_t s, c;
+    int32_t Kh;
+    if (!warp_token(semitones, s, c, Kh)) return fail(nullptr, VITS_E_ARG, "semitones %g is not a finite value within [-12, 12]", (double)semitones);
+    if (step) *step = s;
+    if (cutoff) *cutoff = c;
+    if (half_taps) *half_taps = Kh;
+    return VITS_OK;
+}
+
+int vits_warp_plan(const int64_t *durations, const float *semitones, int len, int hop, vits_warp_seg *segs, int64_t *spans, int64_t *n_out) {
+    if (len < 0 || hop < 1 || (len > 0 && !durations)) return fail(nullptr, VITS_E_ARG, "bad warp plan arguments (len = %d, hop = %d)", len, hop);
+    int64_t ns = 0, N = 0;
+    const std::string e = warp_plan(durations, semitones, len, hop, segs, spans, ns, N);
+    if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
+    if (n_out) *n_out = N;
+    return (int)ns;
+}
+
 int vits_run_chunked_ctl(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
                          const vits_noise *noise, const vits_controls *ctl, int chunk_frames, vits_chunk_fn fn, void *user) {
     if (int rc = check_dev(h)) return rc;
@@ -3482,7 +3662,8 @@ static int delivery_counts(vits_handle *h, std::vector<int64_t> &counts) {
     counts.resize(B);
     for (int b = 0; b < B; b++) {
         const int64_t n = (int64_t)(h->last_vocoder ? h->F : h->h_ylen[b]) * h->model.hop;
-        if ((int)h->run_L.size() == B) counts[b] = (n * h->run_L[b] + h->run_M[b] - 1) / h->run_M[b];  // (a rate per row)
+        if ((int)h->warp_counts.size() == B) counts[b] = h->warp_counts[b];  // (a warped run: its plan's)
+        else if ((int)h->run_L.size() == B) counts[b] = (n * h->run_L[b] + h->run_M[b] - 1) / h->run_M[b];  // (a rate per row)
         else counts[b] = h->out_resampled ? (n * h->rs_run_L + h->rs_run_M - 1) / h->rs_run_M : n;
         if (counts[b] > S) return fail(h, VITS_E_ARG, "no completed run to deliver (row %d: %lld samples of %d)", b, (long long)counts[b], S);
     }
@@ -4787,6 +4968,45 @@ int vits_test_resample(int device_id, const float *x, const int64_t *lens, int B
     TCHECK(launch_resample(a, B, /*piece=*/false, nullptr));
     TCHECK(hipDeviceSynchronize());
     TCHECK(download(y, dy, (size_t)B * S_out));
+    return VITS_OK;
+}
+
+// The time warp by value: the rows' records from the caller's segments, the pipeline's launch.
+int vits_test_warp(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_warp_seg *segs, const int32_t *seg_first,
+                   float *y, int S_w) {
+    if (int rc = test_dev(device_id)) return rc;
+    if (!x || !y || !counts || !seg_first || B <= 0 || S <= 0 || S_w < 1) return fail(nullptr, VITS_E_ARG, "bad warp test arguments");
+    if (seg_first[0] != 0) return fail(nullptr, VITS_E_ARG, "seg_first[0] = %d, not 0", (int)seg_first[0]);
+    std::vector<int64_t> n_in((size_t)B);
+    for (int b = 0; b < B; b++) {
+        const int32_t ns = seg_first[b + 1] - seg_first[b];
+        if (ns < 0 || (ns > 0 && !segs)) return fail(nullptr, VITS_E_ARG, "row %d: seg_first is not ascending", b);
+        const std::string e = warp_segs_fault(segs + seg_first[b], ns);
+        if (!e.empty()) return fail(nullptr, VITS_E_ARG, "row %d: %s", b, e.c_str());
+        n_in[(size_t)b] = counts[b] < 0 ? 0 : (counts[b] > S ? S : counts[b]);
+    }
+    std::vector<WarpRow> rows;
+    const int64_t need = warp_rows(segs, seg_first, n_in.data(), B, rows);
+    if (S_w < need) return fail(nullptr, VITS_E_ARG, "S_w = %d, the longest row has %lld output samples", S_w, (long long)need);
+    std::vector<float> G(kWarpTable);
+    warp_table(G.data());
+    DevBufs D;
+    const size_t n_segs = (size_t)seg_first[B];
+    const vits_warp_seg none{};
+    WarpArgs a{};
+    a.segs = D.up(n_segs ? segs : &none, n_segs ? n_segs : 1);
+    a.rows = D.up(rows.data(), rows.size());
+    a.G = D.up(G.data(), G.size());
+    a.x = D.up(x, (size_t)B * S);
+    a.x_pitch = S;
+    float *dy = D.fill<float>((size_t)B * S_w, 0xff);
+    a.y = dy;
+    a.y_pitch = S_w;
+    a.n_hi = S_w;
+    TCHECK(D.err);
+    TCHECK(launch_warp(a, B, nullptr));
+    TCHECK(hipDeviceSynchronize());
+    TCHECK(download(y, dy, (size_t)B * S_w));
     return VITS_OK;
 }
 

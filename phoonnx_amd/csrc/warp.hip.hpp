@@ -1,0 +1,119 @@
+// warp.hip.hpp — the per-token time warp on the device (include/vitsmi.h, "Intonation"; plan: warp.hpp).
+//
+// One workgroup renders kWarpBlock consecutive output samples of one row.  Input positions never decrease along a row and
+// advance by at most two samples per output, so the tile reads at most 255 * 2 + 2 + 76 input floats: they are staged once
+// in LDS, already masked to the row's valid samples.  The workgroup finds the segments of its first and of its last sample
+// by binary search over the row's n0 - both uniform - and every lane walks forward from the first to its own: a tile may
+// straddle many short segments.  The prototype table G (32 KB) is staged in LDS too: a wave's 64 lanes read 64 different
+// table lines per tap (neighbouring outputs lie some 435 entries apart in G), which LDS serves at full rate and L1 does not
+// - 245 us against 375 us for the launch of a 32-row batch, measured with both placements.
+//
+// One function renders a sample (warp_sample): fp32, fmaf in ascending m from 0.0f, so a sample has the same bits
+// whichever tile or batch rendered it.  Everything in front of the barrier is uniform over the workgroup:
+// it depends on blockIdx and on values indexed by it alone.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "warp.hpp"
+
+namespace vitsmi {
+
+constexpr int kWarpBlock = 256;                                        // output samples (= threads) per workgroup
+constexpr int kWarpSpan = (kWarpBlock - 1) * 2 + 2 + 2 * kWarpMaxHalf;  // the input floats a tile stages at most (588)
+
+struct WarpArgs {
+    const vits_warp_seg *segs;
+    const WarpRow *rows;  // [B]
+    const float *G;       // [kWarpTable]
+    const float *x;       // input samples of row b at x + b * x_pitch
+    int64_t x_pitch;
+    float *y;             // [B][y_pitch]
+    int64_t y_pitch;
+    int n_hi;             // S_w: the launch renders output samples [0, n_hi) of every row
+};
+
+// the last segment whose n0 <= n (segments without an output sample share the n0 of the one behind them)
+__device__ __forceinline__ int warp_find(const vits_warp_seg *sg, int n_segs, int64_t n) {
+    int lo = 0, hi = n_segs - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (sg[mid].n0 <= n) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// THE output sample at input position pos (Q16): taps m = i0 - Kh + 1 .. i0 + Kh, weight G at |m - pos| * c by linear
+// interpolation, x(d) = the input at m = i0 + d
+template <class X>
+__device__ __forceinline__ float warp_sample(const float *G, int64_t pos, int32_t c, int32_t Kh, X x) {
+    const int32_t frac = (int32_t)(pos & (kWarpOne - 1));
+    float acc = 0.f;
+    for (int d = 1 - Kh; d <= Kh; d++) {
+        const int32_t t = d * (int32_t)kWarpOne - frac;  // (m << FB) - pos: within +-38 * 2^16
+        const uint64_t v = (uint64_t)(uint32_t)(t < 0 ? -t : t) * (uint32_t)c;
+        const uint32_t i = (uint32_t)(v >> 23);
+        const float f = (float)(uint32_t)(v & 0x7FFFFFu) * 0x1p-23f;
+        float w = 0.f;
+        if (i < (uint32_t)(kWarpZ * kWarpR)) {
+            const float g0 = G[i], g1 = G[i + 1];
+            w = fmaf(f, g1 - g0, g0);
+        }
+        acc = fmaf(w, x(d), acc);
+    }
+    return ((float)c * 0x1p-16f) * acc;  // (float)(c / 65536.0): c <= 2^16, the scaling is exact
+}
+
+__global__ void __launch_bounds__(kWarpBlock) warp_kernel(WarpArgs a) {
+    __shared__ float xs[kWarpSpan];
+    __shared__ float gs[kWarpTable];
+    const int b = blockIdx.y;
+    const WarpRow r = a.rows[b];
+    const int64_t n0 = (int64_t)blockIdx.x * kWarpBlock, n = n0 + threadIdx.x;
+    const float *xrow = a.x + (int64_t)b * a.x_pitch;
+    float *yrow = a.y + (int64_t)b * a.y_pitch;
+    if (n0 >= r.n_out || r.identity || r.n_segs <= 0) {  // behind the row's end: zeros; an identity row: its valid samples
+        if (n < a.n_hi) yrow[n] = (r.identity && n < r.n_out && n < r.n_in) ? xrow[n] : 0.f;
+        return;
+    }
+    const vits_warp_seg *sg = a.segs + r.seg0;
+    const int64_t n_last = (n0 + kWarpBlock < r.n_out ? n0 + kWarpBlock : (int64_t)r.n_out) - 1;
+    const int j0 = warp_find(sg, r.n_segs, n0), j1 = warp_find(sg, r.n_segs, n_last);
+    const int64_t i_lo = (sg[j0].pos0 + (n0 - sg[j0].n0) * sg[j0].step) >> kWarpFB;
+    const int64_t i_hi = (sg[j1].pos0 + (n_last - sg[j1].n0) * sg[j1].step) >> kWarpFB;
+    const int64_t m_base = i_lo - kWarpMaxHalf + 1;
+    int64_t len = i_hi - i_lo + 2 * kWarpMaxHalf;
+    len = len > kWarpSpan ? kWarpSpan : len;  // (never: positions advance by at most two samples an output)
+    for (int q = threadIdx.x; q < (int)len; q += kWarpBlock) {
+        const int64_t m = m_base + q;
+        xs[q] = m >= 0 && m < r.n_in ? xrow[m] : 0.f;
+    }
+    for (int q = threadIdx.x; q < kWarpTable; q += kWarpBlock) gs[q] = a.G[q];
+    __syncthreads();
+    if (n >= a.n_hi) return;
+    float v = 0.f;
+    if (n < r.n_out) {
+        int j = j0;
+        while (j < j1 && sg[j + 1].n0 <= n) j++;
+        const vits_warp_seg g = sg[j];
+        const int64_t pos = g.pos0 + (n - g.n0) * g.step;
+        const int64_t at = (pos >> kWarpFB) - m_base;  // the tap m = i0 in the staged span
+        if (at - g.half_taps + 1 >= 0 && at + g.half_taps < len) {
+            const float *w = xs + at;
+            v = warp_sample(gs, pos, g.c, g.half_taps, [&](int d) { return w[d]; });
+        }
+    }
+    yrow[n] = v;
+}
+
+// launch over output samples [0, a.n_hi) of B rows
+inline hipError_t launch_warp(const WarpArgs &a, int B, hipStream_t st) {
+    if (B <= 0 || a.n_hi <= 0) return hipSuccess;
+    const dim3 grid((unsigned)(((int64_t)a.n_hi + kWarpBlock - 1) / kWarpBlock), (unsigned)B);
+    warp_kernel<<<grid, kWarpBlock, 0, st>>>(a);
+    return hipGetLastError();
+}
+
+}  // namespace vitsmi

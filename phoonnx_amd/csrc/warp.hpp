@@ -1,0 +1,152 @@
+// warp.hpp — the plan of the per-token time warp (include/vitsmi.h, "Intonation"): a token's step, cutoff and half-taps,
+// a row's segments and output count, and the prototype table G, computed in double on the host and rounded once to fp32.
+// Host-side C++17, no HIP types: the plan is a pure function of the durations and the semitones, answered without a handle
+// or a device.  All position arithmetic is int64 (Q16 input positions).
+#pragma once
+#include <climits>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <string>
+#include <vector>
+
+#include "../../include/vitsmi.h"
+#include "resample.hpp"
+
+namespace vitsmi {
+
+constexpr int kWarpZ = kResampleZ;         // zero crossings on either side, as the resampler
+constexpr int kWarpR = 512;                // table entries per zero crossing
+constexpr int kWarpFB = 16;                // fractional bits of an input position
+constexpr int64_t kWarpOne = int64_t(1) << kWarpFB;
+constexpr int kWarpTable = kWarpZ * kWarpR + 2;  // G[0 .. Z*R + 1]; the last two are 0
+constexpr float kWarpMaxSemitones = 12.f;
+constexpr int64_t kWarpMinStep = kWarpOne / 2, kWarpMaxStep = kWarpOne * 2;  // -12 and +12 semitones
+constexpr int kWarpMaxHalf = 38;           // half-taps at +12 semitones: the most a token has
+
+static_assert(sizeof(vits_warp_seg) == 40, "vits_warp_seg is a 40-byte record");
+
+// a row of a launch: its segment records, its valid input samples, its output samples
+struct WarpRow {
+    int32_t seg0, n_segs;  // records [seg0, seg0 + n_segs) of the launch's segment array
+    int32_t n_in, n_out;
+    int32_t identity;      // a masked copy: no segment, or every step the unit step
+};
+
+// G[i] = (float)g(i / R), g(u) = sinc(u) * kaiser(u / Z) for 0 <= u < Z, else 0
+inline void warp_table(float *G) {
+    const double kPi = 3.14159265358979323846;
+    const double i0b = resample_i0(kResampleBeta);
+    for (int i = 0; i < kWarpTable; i++) {
+        const double u = (double)i / kWarpR;
+        double g = 0.0;
+        if (u < (double)kWarpZ) {
+            const double a = kPi * u, t = u / kWarpZ;
+            g = (a == 0.0 ? 1.0 : std::sin(a) / a) * resample_i0(kResampleBeta * std::sqrt(1.0 - t * t)) / i0b;
+        }
+        G[i] = (float)g;
+    }
+}
+
+// step, cutoff c and half-taps Kh of a token at `semitones`; false: not a finite value within [-12, 12]
+inline bool warp_token(float semitones, int64_t &step, int64_t &c, int32_t &Kh) {
+    if (!std::isfinite(semitones) || std::fabs(semitones) > kWarpMaxSemitones) return false;
+    const double r = std::exp2((double)semitones / 12.0);
+    step = std::llrint(r * (double)kWarpOne);
+    const double q = (double)kWarpOne / (double)step;
+    const double s = kResampleRolloff * (q < 1.0 ? q : 1.0);
+    c = std::llrint(s * (double)kWarpOne);
+    Kh = (int32_t)(((int64_t)kWarpZ * kWarpOne + c - 1) / c);
+    return true;
+}
+
+// The plan of one row: tokens [0, len) with rendered durations D_t (frames) and semitones st_t.  segs == nullptr: counts
+// only.  spans[t] (nullable): k of token t, 0 for a dropped one.  Returns "" or what is wrong, naming the token.
+inline std::string warp_plan(const int64_t *durations, const float *semitones, int len, int hop, vits_warp_seg *segs, int64_t *spans,
+                             int64_t &n_segs, int64_t &n_out) {
+    char buf[200];
+    int64_t pos = 0, n = 0, cum = 0;
+    n_segs = 0;
+    for (int t = 0; t < len; t++) {
+        if (spans) spans[t] = 0;
+        const int64_t D = durations[t];
+        if (D < 0) {
+            std::snprintf(buf, sizeof buf, "token %d: duration %lld is negative", t, (long long)D);
+            return buf;
+        }
+        if (D == 0) continue;
+        int64_t step, c;
+        int32_t Kh;
+        if (!warp_token(semitones ? semitones[t] : 0.f, step, c, Kh)) {
+            std::snprintf(buf, sizeof buf, "token %d: semitones %g is not a finite value within [-12, 12]", t, (double)semitones[t]);
+            return buf;
+        }
+        cum += D;
+        if (cum > (INT64_MAX >> (kWarpFB + 2)) / hop) {
+            std::snprintf(buf, sizeof buf, "token %d: %lld frames of %d samples leave the range of a position", t, (long long)cum, hop);
+            return buf;
+        }
+        const int64_t P = (cum * hop) << kWarpFB;
+        const int64_t k = P <= pos ? 0 : (P - pos + step - 1) / step;
+        if (segs) segs[n_segs] = vits_warp_seg{n, pos, k, (int32_t)step, (int32_t)c, Kh, 0};
+        if (spans) spans[t] = k;
+        n_segs++;
+        n += k;
+        pos += k * step;
+        if (n > INT_MAX) {
+            std::snprintf(buf, sizeof buf, "token %d: the row reaches %lld output samples, more than a row admits (%d)", t, (long long)n, INT_MAX);
+            return buf;
+        }
+    }
+    n_out = n;
+    return "";
+}
+
+// every step of the row is the unit step: a masked copy (a row without a segment too)
+inline bool warp_identity(const vits_warp_seg *segs, int64_t n_segs) {
+    for (int64_t j = 0; j < n_segs; j++)
+        if (segs[j].step != kWarpOne) return false;
+    return true;
+}
+
+// the rows' records of a launch from each row's segments [seg_first[b], seg_first[b + 1]) and valid input samples
+// (a row without a segment: N_b = n_b); returns S_w = max(1, max_b N_b)
+inline int64_t warp_rows(const vits_warp_seg *segs, const int32_t *seg_first, const int64_t *n_in, int B, std::vector<WarpRow> &rows) {
+    rows.resize((size_t)B);
+    int64_t S_w = 1;
+    for (int b = 0; b < B; b++) {
+        const int32_t s0 = seg_first[b], ns = seg_first[b + 1] - s0;
+        const int64_t N = ns > 0 ? segs[s0 + ns - 1].n0 + segs[s0 + ns - 1].k : n_in[b];
+        rows[(size_t)b] = WarpRow{s0, ns, (int32_t)n_in[b], (int32_t)N, warp_identity(segs + s0, ns) ? 1 : 0};
+        S_w = N > S_w ? N : S_w;
+    }
+    return S_w;
+}
+
+// "" or what keeps a row's segment records from being rendered: each within the limits a token has, each starting where the
+// one before it ends - in output samples and in input position -, so that positions never decrease along the row
+inline std::string warp_segs_fault(const vits_warp_seg *segs, int64_t n_segs) {
+    char buf[200];
+    int64_t n = 0, pos = 0;
+    for (int64_t j = 0; j < n_segs; j++) {
+        const vits_warp_seg &g = segs[j];
+        const bool first = j == 0;
+        if (g.step < kWarpMinStep || g.step > kWarpMaxStep || g.c < 1 || g.c > kWarpOne || g.half_taps < 1 || g.half_taps > kWarpMaxHalf ||
+            (int64_t)g.half_taps * g.c < (int64_t)kWarpZ * kWarpOne || g.k < 0 || g.k > INT_MAX || g.n0 != n ||
+            (first ? g.pos0 != 0 : g.pos0 != pos)) {
+            std::snprintf(buf, sizeof buf, "segment %lld {n0 %lld, pos0 %lld, k %lld, step %d, c %d, half_taps %d} does not continue the row at "
+                                           "output %lld, position %lld within the limits of a token",
+                          (long long)j, (long long)g.n0, (long long)g.pos0, (long long)g.k, g.step, g.c, g.half_taps, (long long)n, (long long)pos);
+            return buf;
+        }
+        n += g.k;
+        pos = g.pos0 + g.k * (int64_t)g.step;
+        if (n > INT_MAX) {
+            std::snprintf(buf, sizeof buf, "segment %lld: the row reaches %lld output samples, more than a row admits (%d)", (long long)j, (long long)n, INT_MAX);
+            return buf;
+        }
+    }
+    return "";
+}
+
+}  // namespace vitsmi

@@ -18,6 +18,7 @@
 #include "shape.hpp"
 #include "slab.hpp"
 #include "stream_shape.hpp"
+#include "warp.hpp"
 
 namespace vitsmi {
 
@@ -353,6 +354,31 @@ inline ResampleBufs carve_resample(Carver &cv, int B, int S_out, int K) {
     r.pcm = carve_pcm16(cv, B, S_out);
     r.dlv = carve_delivery(cv, B, S_out);
     return r;
+}
+
+// A warped run (vits_run_async_warped) leaves its result in the staging slab the same way: carve_resample's walk for rows of
+// S_w samples without a carry (K = 0) - so vits_last_pcm16 and vits_deliver*, which carve it again to find their buffers
+// behind the waveform, find them where they are - with the rows' output counts in n_out, and behind it the plan the one
+// launch reads: the segment records and the rows' records, one block, uploaded in one copy.  A delivery's own buffers may
+// reuse the plan block: the launch that read it precedes them on the stream.  Used by warp_run alone; vits_reserve does
+// not count it.
+struct WarpBufs {
+    ResampleBufs front;
+    vits_warp_seg *segs;
+    WarpRow *rows;
+    size_t plan_bytes;  // segs | rows
+};
+
+inline WarpBufs carve_warp(Carver &cv, int B, int S_w, int64_t n_segs) {
+    WarpBufs w{};
+    w.front = carve_resample(cv, B, S_w, 0);
+    w.plan_bytes = (size_t)n_segs * sizeof(vits_warp_seg) + (size_t)B * sizeof(WarpRow);
+    char *p = cv.take<char>(w.plan_bytes);
+    if (p) {
+        w.segs = reinterpret_cast<vits_warp_seg *>(p);
+        w.rows = reinterpret_cast<WarpRow *>(p + (size_t)n_segs * sizeof(vits_warp_seg));
+    }
+    return w;
 }
 
 // The buffers of ONE delivery call, whichever entry it came through, and the one walk that carves them: the delivery's own

@@ -221,6 +221,33 @@ def _controls(rows, seeds, durations, token_rate):
     return c
 
 
+def _semitones(token_semitones, lens, B, T):
+    """token_semitones - None, or floats [B, T] within [-12, 12] in front of lens[b] (vitsmi.h, "intonation") -> float32
+    [B, T], contiguous"""
+    if token_semitones is None:
+        return None
+    st = np.asarray(token_semitones)
+    if st.dtype.kind not in "fiu":
+        raise SessionError(f"Unexpected input data type: 'token_semitones' must be floats, got {st.dtype}")
+    if st.shape != (B, T):
+        raise SessionError(f"Invalid shape for 'token_semitones': {st.shape}, expected [batch_size, phonemes] = {(B, T)}")
+    st = np.ascontiguousarray(st, np.float32)
+    live = np.arange(T)[None, :] < np.asarray(lens)[:, None]
+    bad = live & ~(np.isfinite(st) & (np.abs(st) <= 12))
+    if bad.any():
+        b, t = (int(v) for v in np.argwhere(bad)[0])
+        raise SessionError(f"token_semitones[{b},{t}]={float(st[b, t])} is not a finite value within [-12, 12]")
+    return st
+
+
+def token_span_bounds(spans, count) -> np.ndarray:
+    """token_bounds of a warped row: the boundaries of its tokens in delivered samples from the warp's own spans (k per
+    token, last_token_spans()) -> int64 [len(spans) + 1]; a row's last boundary is its count N."""
+    bounds = np.minimum(int(count), np.concatenate([[0], np.cumsum(np.asarray(spans, np.int64))]))
+    bounds[-1] = int(count)   # (a row whose tokens were all dropped still has its one frame)
+    return bounds
+
+
 def resample_plan(in_rate: int, out_rate: int, table: bool = False):
     """The output-rate resampler's plan for a pair of rates (vitsmi.h, "output rate"; pure host code): (L, M, K), or with
     table=True (L, M, K, h float32 [L, K]).  Raises SessionError for a pair the engine refuses."""
@@ -1032,7 +1059,8 @@ class MiSession:
         self._seed = int(seed)
 
     def synthesize_batch(self, ids, lens, scales, sid=None, noise_dp=None, noise_z=None, taps=(), seeds=None,
-                         durations=None, token_rate=None, return_durations=False, output_rates=None):
+                         durations=None, token_rate=None, return_durations=False, output_rates=None, token_semitones=None,
+                         compensate=True):
         """One batched run.  Returns {"output": [B,1,1,S] float32, "y_lengths": int64 [B], taps...}.
         output_rates: None, or a rate per row for this call (set_output_rates; what was set before is put back afterwards);
         with row rates the result also holds "sample_rates" (int32 [B]).
@@ -1045,24 +1073,32 @@ class MiSession:
         durations: None or integers [B, T] - forced frames per token: the duration predictor is not run, everything else is
         (with a free run's durations and seeds: that run's audio bit for bit); token_rate: None or floats [B, T] - a
         multiplier on each token's predicted duration (0 drops the token).  One or the other (vitsmi.h, vits_controls).
-        return_durations: adds "durations", int64 [B, T] - the frames each token occupies (last_durations())."""
+        return_durations: adds "durations", int64 [B, T] - the frames each token occupies (last_durations()).
+        token_semitones: None or floats [B, T] within [-12, 12] - token t is raised or lowered by that many semitones, by a
+        time warp on the device (vitsmi.h, "intonation": the resampling shift, formants move along); compensate=True keeps
+        the tempo (the token is rendered longer by 2^(st/12) first), False is the pure warp.  The result then holds
+        "sample_lengths" - each row's valid samples behind the warp - and, with return_durations, "token_spans" (int64
+        [B, T]: the output samples of each token; "durations" stay the rendered frames)."""
         ids, lens, scales, sid, noise_dp, noise_z, noise, seeds, durations, token_rate = self._run_arguments(
             ids, lens, scales, sid, noise_dp, noise_z, seeds, durations, token_rate)
         B = ids.shape[0]
+        semitones = _semitones(token_semitones, lens, B, ids.shape[1])
         # enqueue -> frame counts -> copy-out -> taps all use this handle's one workspace
         with self._locked(), self._rates_for_call(output_rates):
             try:
-                self._begin(ids, lens, scales, sid, noise, seeds, durations, token_rate)
+                self._begin(ids, lens, scales, sid, noise, seeds, durations, token_rate, semitones, compensate)
                 ylen = self.last_y_lengths()
                 dur = self.last_durations() if return_durations else None
-                counts = self.last_sample_counts() if self.resampling or self.output_rates is not None else None
+                counts = self.last_sample_counts() if self.resampling or self.output_rates is not None or semitones is not None else None
+                spans = self._token_spans(semitones, lens) if return_durations and semitones is not None else None
                 S = int(ylen.max()) * self.hparam("hop") if counts is None else int(counts.max())
                 audio = _POOL.array((B, 1, 1, S)) if self.pinned_results else np.empty((B, 1, 1, S), np.float32)
                 self._fetch(audio, 0, B)
             except RangeError as exc:
                 self._fall_back_to_bf16x6(exc)
                 return self.synthesize_batch(ids, lens, scales, sid, noise_dp, noise_z, taps, seeds=seeds,
-                                             durations=durations, token_rate=token_rate, return_durations=return_durations)
+                                             durations=durations, token_rate=token_rate, return_durations=return_durations,
+                                             token_semitones=token_semitones, compensate=compensate)
             res = {"output": audio, "y_lengths": ylen}
             if counts is not None:
                 res["sample_lengths"] = counts
@@ -1070,6 +1106,8 @@ class MiSession:
                 res["sample_rates"] = self.last_sample_rates()
             if return_durations:
                 res["durations"] = dur
+            if spans is not None:
+                res["token_spans"] = spans
             for t in taps:
                 res[t] = self.tap(t)
             return res
@@ -1105,11 +1143,18 @@ class MiSession:
             noise.noise_z_stride = noise_z.shape[2]
         return ids, lens, scales, sid, noise_dp, noise_z, noise, seeds, durations, token_rate
 
-    def _begin(self, ids, lens, scales, sid, noise, seeds=None, durations=None, token_rate=None):
+    def _begin(self, ids, lens, scales, sid, noise, seeds=None, durations=None, token_rate=None, semitones=None, compensate=True):
         """vits_run_async: validated host arrays in, the whole path enqueued; frame counts and durations are known on
-        return.  ([B, 3] scales or seeds: vits_run_async_rows; durations or token_rate: vits_run_async_ctl.)"""
+        return.  ([B, 3] scales or seeds: vits_run_async_rows; durations or token_rate: vits_run_async_ctl; semitones:
+        vits_run_async_warped.)"""
         B, T = ids.shape
-        if durations is not None or token_rate is not None:
+        if semitones is not None:
+            rows = _rows(scales, B)
+            ctl = _controls(rows, seeds, durations, token_rate)
+            into = _ffi.VitsIntonation(semitones.ctypes.data, 1 if compensate else 0)
+            rc = self._lib.vits_run_async_warped(self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(sid), C.byref(noise),
+                                                 C.byref(ctl), C.byref(into))
+        elif durations is not None or token_rate is not None:
             rows = _rows(scales, B)
             ctl = _controls(rows, seeds, durations, token_rate)
             rc = self._lib.vits_run_async_ctl(self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(sid), C.byref(noise),
@@ -1671,6 +1716,29 @@ class MiSession:
                 raise SessionError(f"vits_last_durations: the run changed between two calls ({n} != {buf.size})")
             return buf
 
+    def last_token_spans(self) -> np.ndarray:
+        """int64 [B, T]: the output samples each token of the last WARPED run occupies (k of the warp's plan; 0 for a dropped
+        token and behind lens[b]); row sums = last_sample_counts().  Host state like last_durations().  SessionError after a
+        run that was not warped."""
+        with self._locked(read_only=True):
+            n = self._lib.vits_last_token_spans(self._h, None, 0)
+            if n < 0:
+                raise SessionError(f"vits_last_token_spans failed [{n}]: {self._err()}")
+            B = self._lib.vits_last_y_lengths(self._h, None, 0)
+            buf = np.zeros((B, n // B), np.int64)
+            n = self._lib.vits_last_token_spans(self._h, buf.ctypes.data_as(C.POINTER(C.c_int64)), buf.size)
+            if n != buf.size:
+                raise SessionError(f"vits_last_token_spans: the run changed between two calls ({n} != {buf.size})")
+            return buf
+
+    def _token_spans(self, semitones, lens) -> np.ndarray:
+        """the spans of the last run, begun with `semitones`: the warp's, or - every semitone 0, the run was not warped -
+        what the identity plan gives: durations * hop"""
+        live = np.arange(semitones.shape[1])[None, :] < np.asarray(lens)[:, None]
+        if (live & (semitones != 0)).any():
+            return self.last_token_spans()
+        return self.last_durations() * self.hparam("hop")
+
     def last_pcm16(self, normalize: bool = True, volume: float = 1.0, shape=None) -> np.ndarray:
         """int16 PCM of the last run, post-processed on the GPU exactly as TTSVoice.synthesize + AudioChunk do
         (voice.py:271-282, 88-91); [B, S], zeros past each utterance's length."""
@@ -1806,7 +1874,7 @@ class MiSession:
     def synthesize_delivered(self, ids, lens, scales, sid=None, *, segments=None, n_streams=None, encoding="pcm16",
                              normalize=True, volume=1.0, seeds=None, durations=None, token_rate=None, noise_dp=None,
                              noise_z=None, return_durations=False, trim=None, levels=None, shapes=None, token_gain_db=None,
-                             gain_ramp=0.01, limits=None, output_rates=None):
+                             gain_ramp=0.01, limits=None, output_rates=None, token_semitones=None, compensate=True):
         """One batched run and its delivery under one hold of the session lock: what leaves the GPU is the encoded audio
         of the plan and nothing else - the fp32 waveform is never copied to the host.  segments=None: one stream per row,
         with `normalize` / `volume` as scalars or [B] arrays (row b's own).  Everything in front of the delivery is
@@ -1825,12 +1893,15 @@ class MiSession:
         delivered once per (rate, encoding) group of segments - a stream's segments must lie in one group -, every
         sample-valued field (leads, Trim, Shape, Limit) is at its row's own rate, gain_ramp is converted at each row's rate,
         and the result holds "sample_rates" (int32 [B]).
+        token_semitones, compensate - as synthesize_batch: the delivery then works on the warped waveform and its counts; the
+        token gains' breakpoints lie on the warp's own token spans, and with return_durations the result holds "token_spans".
         Returns {"streams": [array per stream], "stream_samples": int64 [J], "y_lengths": int64 [B], "sample_lengths":
         int64 [B] (each row's valid samples at the delivered rate), "kept_first" / "kept_count": int64 [G] (what each
         segment delivers of its row: all of it without a trim)[, "durations"]}."""
         ids, lens, scales, sid, noise_dp, noise_z, noise, seeds, durations, token_rate = self._run_arguments(
             ids, lens, scales, sid, noise_dp, noise_z, seeds, durations, token_rate)
         B = ids.shape[0]
+        semitones = _semitones(token_semitones, lens, B, ids.shape[1])
         if segments is None:
             try:
                 nz = np.broadcast_to(np.asarray(normalize, bool), (B,))
@@ -1865,14 +1936,15 @@ class MiSession:
                     raise SessionError(f"segment {i}: token_gain_db and explicit points on the same segment")
         with self._locked(), self._rates_for_call(output_rates):
             try:
-                self._begin(ids, lens, scales, sid, noise, seeds, durations, token_rate)
+                self._begin(ids, lens, scales, sid, noise, seeds, durations, token_rate, semitones, compensate)
                 ylen = self.last_y_lengths()
                 dur = self.last_durations() if return_durations or tgains is not None else None
                 counts = self.last_sample_counts()
                 rates = self.last_sample_rates() if self.output_rates is not None else None
+                spans = self._token_spans(semitones, lens) if semitones is not None and (return_durations or tgains is not None) else None
                 loud = gain = None
                 if tgains is not None:
-                    used = self._token_shapes(segments, used, tgains, dur, lens, counts, gain_ramp)
+                    used = self._token_shapes(segments, used, tgains, dur, lens, counts, gain_ramp, spans)
                 if rates is not None:
                     streams, kept_first, kept_count, loud, gain = self._deliver_groups(segments, n_streams, encoding, rates, counts,
                                                                                        trim, levels, used, limits)
@@ -1891,7 +1963,8 @@ class MiSession:
                                                  encoding=encoding, seeds=seeds, durations=durations, token_rate=token_rate,
                                                  noise_dp=noise_dp, noise_z=noise_z, return_durations=return_durations,
                                                  trim=trim, levels=levels, shapes=shapes, token_gain_db=token_gain_db,
-                                                 gain_ramp=gain_ramp, limits=limits)
+                                                 gain_ramp=gain_ramp, limits=limits, token_semitones=token_semitones,
+                                                 compensate=compensate)
         res = {"streams": streams, "stream_samples": np.array([a.size for a in streams], np.int64), "y_lengths": ylen,
                "sample_lengths": counts, "kept_first": kept_first, "kept_count": kept_count}
         if levels is not None:
@@ -1902,6 +1975,8 @@ class MiSession:
             res["shapes"] = used
         if return_durations:
             res["durations"] = dur
+            if spans is not None:
+                res["token_spans"] = spans
         return res
 
     def _deliver_groups(self, segments, n_streams, encoding, rates, counts, trims, levels, shapes, limits):
@@ -1959,11 +2034,15 @@ class MiSession:
                 streams[j] = ss[k]
         return streams, kept_first, kept_count, loud, gain
 
-    def _token_shapes(self, segments, shapes, gains, durations, lens, counts, gain_ramp):
-        """the shapes of a delivery of the last run with every segment's points set from its row's token gains"""
+    def _token_shapes(self, segments, shapes, gains, durations, lens, counts, gain_ramp, spans=None):
+        """the shapes of a delivery of the last run with every segment's points set from its row's token gains (spans: the
+        token spans of a run begun with semitones - its boundaries are the warp's)"""
         hop = self.hparam("hop")
         ratios = self._row_ratios(len(lens))
-        bounds = [token_bounds(durations[b], lens[b], hop, counts[b], ratios[b]) for b in range(len(lens))]
+        if spans is not None:
+            bounds = [token_span_bounds(spans[b], counts[b]) for b in range(len(lens))]
+        else:
+            bounds = [token_bounds(durations[b], lens[b], hop, counts[b], ratios[b]) for b in range(len(lens))]
         if self.output_rates is None:
             return token_gain_shapes(segments, shapes, gains, bounds, int(self.delivered_rate * float(gain_ramp)))
         # (a rate per row: the ramp, given in seconds, at each row's own)
@@ -2160,7 +2239,7 @@ class PipelinedSession:
         return np.concatenate([self.parts[i].last_durations() for i in range(n)])
 
     def synthesize_batch(self, ids, lens, scales, sid=None, seeds=None, durations=None, token_rate=None,
-                         return_durations=False, noise_dp=None, noise_z=None):
+                         return_durations=False, noise_dp=None, noise_z=None, token_semitones=None, compensate=True):
         """Host arrays in, host arrays out, like MiSession.synthesize_batch (scales [3] or [B, 3], seeds, durations [B, T],
         token_rate [B, T], injected noise_dp [B, 2, T] / noise_z [B, inter, >= F]: each part gets its own rows of all of
         them; return_durations adds "durations" [B, T], the parts' rows in request order).  One worker thread per sub-batch (the C
@@ -2169,6 +2248,10 @@ class PipelinedSession:
         and lets the DMA engine write its rows straight into that array (vits_fetch_output) - the copy-out of a part
         that finishes early runs under the render of the others, and no byte is copied twice on the host."""
         import threading
+        if token_semitones is not None:
+            # (the parts' warped rows have lengths of their own behind the barrier that sizes the one result: not a pass-through)
+            raise SessionError("Unexpected input: 'token_semitones' / 'compensate' are not covered by PipelinedSession "
+                               "(MiSession.synthesize_batch takes them)")
         ids = np.ascontiguousarray(ids)
         lens = np.ascontiguousarray(lens)
         if ids.dtype != np.int64 or lens.dtype != np.int64 or ids.ndim != 2 or lens.shape != (ids.shape[0],):
@@ -2653,6 +2736,51 @@ def test_resample_rows(x, lens, in_rate, out_rates, device_id=0):
     if S_out == 0:  # (nothing was written: one column of zeros, as the single-rate hook gives)
         return np.zeros((B, 1), np.float32), counts
     return buf[:B * S_out].reshape(B, S_out).copy(), counts
+
+
+def warp_token(semitones):
+    """(step, c, half_taps) of a token at `semitones` (vits_warp_token: pure host code)"""
+    step, c, Kh = C.c_int64(), C.c_int64(), C.c_int32()
+    rc = _ffi.load().vits_warp_token(float(semitones), C.byref(step), C.byref(c), C.byref(Kh))
+    if rc != 0:
+        raise SessionError(f"vits_warp_token failed [{rc}]: {_ffi.last_error(None)}")
+    return step.value, c.value, Kh.value
+
+
+def warp_plan(durations, semitones, hop):
+    """One row's plan (vits_warp_plan: pure host code): durations [T] in frames, semitones [T] or None ->
+    (segments: a ctypes array of _ffi.VitsWarpSeg, spans int64 [T], N)."""
+    D = np.ascontiguousarray(durations, np.int64)
+    st = None if semitones is None else np.ascontiguousarray(semitones, np.float32)
+    if D.ndim != 1 or (st is not None and st.shape != D.shape):
+        raise SessionError(f"durations must be [T] and semitones [T] or None, got {D.shape} / {None if st is None else st.shape}")
+    segs = (_ffi.VitsWarpSeg * max(len(D), 1))()
+    spans = np.zeros(len(D), np.int64)
+    n = C.c_int64()
+    count = _ffi.load().vits_warp_plan(_ffi.ptr(D), _ffi.ptr(st), len(D), int(hop), segs, _ffi.ptr(spans), C.byref(n))
+    if count < 0:
+        raise SessionError(f"vits_warp_plan failed [{count}]: {_ffi.last_error(None)}")
+    return (_ffi.VitsWarpSeg * count)(*segs[:count]), spans, n.value
+
+
+def test_warp(x, counts, row_segs, device_id=0):
+    """The time warp by value (vits_test_warp): x float32 [B, S], counts [B] the rows' valid samples, row_segs - per row a
+    sequence of _ffi.VitsWarpSeg (warp_plan's) -> y float32 [B, S_w], S_w = max(1, max_b N_b); every column is written."""
+    x = np.ascontiguousarray(x, np.float32)
+    counts = np.ascontiguousarray(counts, np.int64)
+    if x.ndim != 2 or counts.shape != (x.shape[0],) or len(row_segs) != x.shape[0]:
+        raise SessionError(f"x must be [B, S], counts [B] and row_segs B sequences, got {x.shape} / {counts.shape} / {len(row_segs)}")
+    B, S = x.shape
+    flat = [g for row in row_segs for g in row]
+    first = np.cumsum([0] + [len(row) for row in row_segs]).astype(np.int32)
+    segs = (_ffi.VitsWarpSeg * max(len(flat), 1))(*flat)
+    n_out = [int(row[-1].n0 + row[-1].k) if len(row) else int(min(max(counts[b], 0), S)) for b, row in enumerate(row_segs)]
+    S_w = max(1, max(n_out))
+    y = np.full((B, S_w), np.nan, np.float32)
+    rc = _ffi.load().vits_test_warp(device_id, _ffi.ptr(x), _ffi.ptr(counts), B, S, segs, _ffi.ptr(first), _ffi.ptr(y), S_w)
+    if rc != 0:
+        raise SessionError(f"vits_test_warp failed [{rc}]: {_ffi.last_error(None)}")
+    return y
 
 
 def test_resample_pieces(x, lens, in_rate, out_rate, piece_samples, device_id=0):

@@ -153,6 +153,23 @@ def build_alignments(groups: Sequence[Tuple[str, Sequence[int]]], durations: Seq
     return out
 
 
+def build_span_alignments(groups: Sequence[Tuple[str, Sequence[int]]], spans: Sequence[int], total: int) -> List[PhonemeAlignment]:
+    """build_alignments for a sentence whose phonemes were raised or lowered (phoneme_pitch): its audio went through the time
+    warp, so a phoneme's samples are the warp's own token spans (MiSession.last_token_spans: output samples per id, in group
+    order; a padded row is fine), not durations * hop.  total: the sentence's valid samples - what the spans sum to; where
+    they do not (every token dropped: the one frame the engine still renders) the rest goes to the last entry."""
+    out: List[PhonemeAlignment] = []
+    pos = at = 0
+    for token, ids in groups:
+        n = int(sum(int(k) for k in spans[pos:pos + len(ids)]))
+        out.append(PhonemeAlignment(phoneme=token, phoneme_ids=[int(i) for i in ids], start_sample=at, num_samples=n))
+        pos += len(ids)
+        at += n
+    if out and int(total) > at:
+        out[-1].num_samples += int(total) - at
+    return out
+
+
 @dataclass
 class AudioChunk:
     """A chunk of raw audio: float samples in [-1, 1] plus their PCM16 rendering."""
@@ -550,6 +567,36 @@ class TTSVoice:
         return [float(v) for v, (_, ids) in zip(vals, groups) for _ in ids]
 
     @staticmethod
+    def _group_semitones(phoneme_pitch, k: int, groups) -> List[float]:
+        """phoneme_pitch -> one value in semitones per phoneme id of sentence k, expanded over the id groups as _group_db
+        expands a volume: a float is the whole sentence's; a callable (sentence_index, [the groups' tokens]) or a sequence
+        indexed by the sentence gives one value per group, which all ids of the group, its blanks included, take"""
+        if callable(phoneme_pitch):
+            vals = list(phoneme_pitch(k, [token for token, _ in groups]))
+        elif isinstance(phoneme_pitch, (int, float, np.integer, np.floating)):
+            vals = [float(phoneme_pitch)] * len(groups)
+        else:
+            vals = list(phoneme_pitch[k])
+        if len(vals) != len(groups):
+            raise ValueError(f"phoneme_pitch gives {len(vals)} values for the {len(groups)} groups of sentence {k}")
+        vals = [float(v) for v in vals]
+        for v in vals:
+            if not (np.isfinite(v) and abs(v) <= 12.0):
+                raise ValueError(f"phoneme_pitch: {v} semitones in sentence {k} is not a finite value within [-12, 12]")
+        return [v for v, (_, ids) in zip(vals, groups) for _ in ids]
+
+    def _pitch_check(self, phoneme_pitch, rates=None) -> None:
+        """phoneme_pitch needs a session whose delivery takes semitones, and audio at the voice's own rate"""
+        import inspect
+        if phoneme_pitch is None:
+            return
+        fn = getattr(self.session, "synthesize_delivered", None)
+        if fn is None or "token_semitones" not in inspect.signature(fn).parameters:
+            raise ValueError("phoneme_pitch needs a session that warps on the device (synthesize_delivered(token_semitones=))")
+        if self._ratio() is not None or any(self._ratio(r) is not None for r in rates or ()):
+            raise ValueError("phoneme_pitch is not covered with an output rate set")
+
+    @staticmethod
     def _padded_db(token_db) -> np.ndarray:
         """per-row dB lists -> [B, T], 0 dB behind each row's end (tokens of no frames: they never show)"""
         db = np.zeros((len(token_db), max(len(q) for q in token_db)), np.float64)
@@ -557,11 +604,12 @@ class TTSVoice:
             db[b, :len(q)] = q
         return db
 
-    def _row_shapes(self, shape, token_db, durs, counts, rates=None):
+    def _row_shapes(self, shape, token_db, durs, counts, rates=None, spans=None):
         """The host fallback's shapes, one per row: `shape` (or none), with the points of each row's token gains - what
         MiSession.synthesize_delivered(token_gain_db=) computes between run and delivery, from the same durations.
-        rates: None, or the rate each row is delivered at (`shape` is then one Shape, or none, per row)."""
-        from .session import Segment, Shape, token_bounds, token_gain_shapes, token_gains
+        rates: None, or the rate each row is delivered at (`shape` is then one Shape, or none, per row).  spans: None, or the
+        token spans of warped rows (phoneme_pitch): the boundaries are then theirs."""
+        from .session import Segment, Shape, token_bounds, token_gain_shapes, token_gains, token_span_bounds
         n = len(counts)
         if rates is None:
             shapes = [shape if shape is not None else Shape()] * n
@@ -572,7 +620,10 @@ class TTSVoice:
         db = self._padded_db(token_db)
         hop = self.session.hparam("hop")
         ratios = [self._ratio()] * n if rates is None else [self._ratio(r) for r in rates]
-        bounds = [token_bounds(durs[b], len(token_db[b]), hop, counts[b], ratios[b]) for b in range(n)]
+        if spans is not None:
+            bounds = [token_span_bounds(spans[b], counts[b]) for b in range(n)]
+        else:
+            bounds = [token_bounds(durs[b], len(token_db[b]), hop, counts[b], ratios[b]) for b in range(n)]
         ramp = int(self.sample_rate * _GAIN_RAMP) if rates is None else [int(int(r) * _GAIN_RAMP) for r in rates]
         return token_gain_shapes([Segment(b) for b in range(n)], shapes, token_gains(db, *db.shape), bounds, ramp)
 
@@ -591,7 +642,7 @@ class TTSVoice:
                            alignments: bool = False, trim_silence=None, trailing_silence: float = 0.0, loudness=None,
                            loudness_scope: str = "sentence", peak_ceiling: float = 0.0, max_gain_db: float = 30.0,
                            fade_in: float = 0.0, fade_out: float = 0.0, fade_curve: str = "linear", phoneme_gain_db=None,
-                           limit_ceiling: float = 0.0, limit_lookahead: float = 0.005):
+                           limit_ceiling: float = 0.0, limit_lookahead: float = 0.005, phoneme_pitch=None):
         """Extension: the whole text as ONE stream of encoded audio ("pcm16", "ulaw", "alaw", "f32"; audio_encoding).  All
         sentences render in one batch; with a session that delivers (MiSession.synthesize_delivered) post-processing,
         encoding and the packing happen on the device and only the encoded audio crosses the bus; any other session
@@ -624,6 +675,12 @@ class TTSVoice:
         limit_lookahead seconds ahead of it to as long behind it (round(limit_lookahead * sample_rate) samples, within
         [1, 1024]) - a loudness target or a boost can then be reached without flattening the peaks.  On the device with a
         session that delivers, by audio_encoding's limits= otherwise: the same bytes.
+        phoneme_pitch - in semitones within [-12, 12]: a float for every sentence, or a value per phoneme as phoneme_gain_db
+        gives a volume (a callable, or one sequence per sentence) - raises or lowers the voice by a time warp on the device
+        (vitsmi.h, "intonation": the resampling shift - formants move along; good for a few semitones).  The tempo is kept.
+        Alignments then come from the warp's token spans, and every sample-valued option - fades, per-phoneme volume, trims,
+        look-ahead - is laid out over the warped audio.  It needs a session that warps (ValueError otherwise) and a voice
+        without an output_sample_rate (ValueError "not covered with an output rate set").
         Returns an audio_encoding.EncodedAudio."""
         from . import audio_encoding as ae
         from .sharding import pad_batch
@@ -641,12 +698,14 @@ class TTSVoice:
         want_dur = alignments and hasattr(self.session, "last_durations") and hasattr(self.session, "synthesize_batch")
         if phoneme_gain_db is not None and not (hasattr(self.session, "synthesize_delivered") or hasattr(self.session, "synthesize_batch")):
             raise ValueError("phoneme_gain_db needs a session that reports durations (synthesize_batch)")
-        groups = self._sentence_groups(text, cfg) if want_dur or phoneme_gain_db is not None else None
+        self._pitch_check(phoneme_pitch)
+        groups = self._sentence_groups(text, cfg) if want_dur or phoneme_gain_db is not None or phoneme_pitch is not None else None
         all_ids = [[i for _, ids in g for i in ids] for g in groups] if groups is not None else self._sentence_ids(text, cfg)
         if not all_ids:
             return ae.EncodedAudio(ae.silence(0, encoding), encoding, self.sample_rate, [], [], [] if want_dur else None)
         token_db = None if phoneme_gain_db is None else [self._group_db(phoneme_gain_db, k, g) for k, g in enumerate(groups)]
-        durs = frames = None
+        token_st = None if phoneme_pitch is None else [self._group_semitones(phoneme_pitch, k, g) for k, g in enumerate(groups)]
+        durs = frames = spans = None
         if hasattr(self.session, "synthesize_delivered"):
             from .session import Segment
             ids, lens = pad_batch(all_ids)
@@ -667,10 +726,14 @@ class TTSVoice:
                 more["token_gain_db"], more["gain_ramp"] = self._padded_db(token_db), _GAIN_RAMP
             if limit is not None:  # (passed down only when asked for: sessions from before the limiter do not know the keyword)
                 more["limits"] = limit
+            if token_st is not None:
+                more["token_semitones"] = self._padded_db(token_st)
             out = self.session.synthesize_delivered(ids, lens, self._scales(cfg), sid, segments=segs, n_streams=1,
                                                     encoding=encoding, return_durations=want_dur, **more)
             data = out["streams"][0]
             counts = [int(n) for n in out["sample_lengths"]]
+            if token_st is not None and want_dur:
+                spans = out["token_spans"]
             if trim is not None:
                 kept = [(int(a), int(c)) for a, c in zip(out["kept_first"], out["kept_count"])]
             if level is not None:
@@ -697,6 +760,7 @@ class TTSVoice:
             else:
                 data, cut = ae.join_trimmed([np.atleast_1d(a) for a in audios], encoding, lead, tail, trim, norm, cfg.volume, **more)
             kept = cut if trim is not None else None
+        valid = counts
         if kept is not None:
             counts = [c for _, c in kept]
         starts, pos = [], 0
@@ -709,7 +773,10 @@ class TTSVoice:
             aligned = []
             for b, g in enumerate(groups):
                 total = frames[b] if frames is not None else max(1, int(np.sum(durs[b])))
-                al = build_alignments(g, durs[b], hop, total_frames=total, ratio=ratio)
+                if spans is not None:  # (a warped sentence: its phonemes lie where the warp put them)
+                    al = build_span_alignments(g, spans[b], valid[b])
+                else:
+                    al = build_alignments(g, durs[b], hop, total_frames=total, ratio=ratio)
                 if kept is not None:
                     self._cut_alignments(al, *kept[b])
                 for a in al:
@@ -720,7 +787,7 @@ class TTSVoice:
     def stream_encoded(self, text: str, syn_config: Optional[SynthesisConfig] = None, encoding: str = "pcm16",
                        chunk_frames: int = 64, sentence_silence: float = 0.0, ref_peak=None, fade_in: float = 0.0,
                        fade_out: float = 0.0, fade_curve: str = "linear", phoneme_gain_db=None, limit_ceiling: float = 0.0,
-                       limit_lookahead: float = 0.005, trim_silence=None):
+                       limit_lookahead: float = 0.005, trim_silence=None, phoneme_pitch=None):
         """Extension: synthesize_encoded's ONE stream as a generator of `bytes`, handed out while the audio still renders.
         All sentences render as one chunked batch (MiSession.synthesize_stream_encoded: post-processing, encoding and the
         masking to each sentence's own length happen on the device, per chunk).  Sentence 0's chunks are yielded as they
@@ -741,8 +808,12 @@ class TTSVoice:
         (vitsmi.h, "trimmed streaming"): every sentence is yielded from its onset on, behind its pause, and its fade-in and
         limiter start there.  A stream keeps as much of keep_lead as it has not handed over yet: with keep_lead <=
         limit_lookahead, or an onset within the first chunk, the bytes are synthesize_encoded's under the same leading trim.
-        The trailing silence stays: a stream learns where its audio ends only at the end."""
+        The trailing silence stays: a stream learns where its audio ends only at the end.
+        phoneme_pitch is refused (ValueError): the chunked entries have no warped form."""
         from . import audio_encoding as ae
+        if phoneme_pitch is not None:
+            raise ValueError("phoneme_pitch is not covered by stream_encoded: the chunked entries have no warped form "
+                             "(synthesize_encoded takes it)")
         cfg = syn_config if syn_config is not None else SynthesisConfig()
         ae._check(encoding)
         lead = self._lead_samples(sentence_silence)
@@ -909,7 +980,7 @@ class TTSVoice:
                                     fade_out: float = 0.0, fade_curve: str = "linear", phoneme_gain_db=None,
                                     limit_ceiling: float = 0.0, limit_lookahead: float = 0.005,
                                     output_sample_rates: Optional[Sequence[Optional[int]]] = None,
-                                    encodings: Optional[Sequence[Optional[str]]] = None):
+                                    encodings: Optional[Sequence[Optional[str]]] = None, phoneme_pitch=None):
         """Extension: synthesize_requests with every request's audio returned as one stream of encoded audio
         (audio_encoding.EncodedAudio; the pause of synthesize_encoded in front of each sentence).  The batching is
         synthesize_requests': sentences sorted by length, max_batch at a time, each with its request's settings and seed.
@@ -933,9 +1004,12 @@ class TTSVoice:
         trailing_silence, a Trim's keep_lead / keep_tail, the fades, limit_lookahead - is converted at each request's own rate,
         alignments count samples at it, and every EncodedAudio carries its request's sample_rate and encoding: request r is
         what this call returns for it on a voice loaded at that rate with that encoding, bit for bit.  ValueError with a
-        session that has no set_output_rates."""
+        session that has no set_output_rates.
+        phoneme_pitch as in synthesize_encoded, for every sentence of every request (a callable's sentence_index counts within
+        its request); ValueError with a session that does not warp, and together with an output rate of the voice or of a request."""
         from . import audio_encoding as ae
         ae._check(encoding)
+        self._pitch_check(phoneme_pitch, [r for r in output_sample_rates or () if r is not None])
         lead = self._lead_samples(sentence_silence)
         trim = self._trim(trim_silence, trailing_silence)
         shape = self._shape(fade_in, fade_out, fade_curve)
@@ -1081,14 +1155,16 @@ class TTSVoice:
         from .session import Segment, Shape, Trim
         from .sharding import pad_batch
         want_dur = alignments and hasattr(self.session, "last_durations")
-        rows, groups, db_of = [], {}, {}
+        rows, groups, db_of, st_of = [], {}, {}, {}
         for r, ((text, _), cfg) in enumerate(zip(requests, cfgs)):
-            if want_dur or phoneme_gain_db is not None:
+            if want_dur or phoneme_gain_db is not None or phoneme_pitch is not None:
                 for k, g in enumerate(self._sentence_groups(text, cfg)):
                     groups[r, k] = g
                     rows.append((r, k, [i for _, ids in g for i in ids]))
                     if phoneme_gain_db is not None:
                         db_of[r, k] = self._group_db(phoneme_gain_db, k, g)
+                    if phoneme_pitch is not None:
+                        st_of[r, k] = self._group_semitones(phoneme_pitch, k, g)
             else:
                 rows.extend((r, k, ids) for k, ids in enumerate(self._sentence_ids(text, cfg)))
         piece, aligned, kept_of, level_of, mul_of = {}, {}, {}, {}, {}
@@ -1116,6 +1192,8 @@ class TTSVoice:
             if limit is not None and not host_level:  # (scope "text": the host that levels limits too)
                 more["limits"] = limit
             need_dur = want_dur or (host_level and phoneme_gain_db is not None)
+            if phoneme_pitch is not None:
+                more["token_semitones"] = self._padded_db([st_of[r, k] for r, k, _ in run])
             if mixed:
                 # a rate and an encoding per row: the same call with its request's own things in every list (a request whose
                 # trim or shape comes to nothing at its rate: the neutral one)
@@ -1140,7 +1218,8 @@ class TTSVoice:
                 run_shapes = self._row_shapes([as_of[r][4] for r, _, _ in run] if mixed else shape,
                                               None if phoneme_gain_db is None else [db_of[r, k] for r, k, _ in run],
                                               None if phoneme_gain_db is None else [out["durations"][b, :len(i)] for b, (_, _, i) in enumerate(run)],
-                                              counts, [as_of[r][0] for r, _, _ in run] if mixed else None)
+                                              counts, [as_of[r][0] for r, _, _ in run] if mixed else None,
+                                              out["token_spans"] if phoneme_pitch is not None and phoneme_gain_db is not None else None)
                 for b, (r, k, _) in enumerate(run):
                     a, c = (int(out["kept_first"][b]), int(out["kept_count"][b]))
                     mul_of[r, k] = ae.shape_multiplier(a, c, run_shapes[b])
@@ -1150,7 +1229,9 @@ class TTSVoice:
                     level_of[r, k] = (float(out["loudness"][b]), float(out["gain"][b]))
                 if trim is not None:
                     kept_of[r, k] = (int(out["kept_first"][b]), int(out["kept_count"][b]))
-                if want_dur:
+                if want_dur and phoneme_pitch is not None:
+                    aligned[r, k] = build_span_alignments(groups[r, k], out["token_spans"][b], int(out["sample_lengths"][b]))
+                elif want_dur:
                     aligned[r, k] = build_alignments(groups[r, k], out["durations"][b], hop,
                                                      total_frames=int(out["y_lengths"][b]), ratio=self._ratio(as_of[r][0]))
         per_request = [[] for _ in requests]
