@@ -480,7 +480,7 @@ int vits_last_sample_rates(vits_handle *h, int32_t *buf, int n);
  *   vits_last_token_spans answers k per token.
  * Out of scope: a warped run with an output rate or per-row output rates set is VITS_E_ARG ("not covered with an output
  * rate set") - folding the rate into step is a follow-up; the chunked and the device-pointer entries have no warped form (a
- * carry for chunks is a follow-up); the speed is constant per token: no glides between tokens; formants are not preserved;
+ * carry for chunks is a follow-up); the speed is constant per token: no glides between tokens here ("pitch contours" below adds them); formants are not preserved;
  * vits_reserve does not count the warped buffer: a warped run grows the staging slab on demand, as any unreserved run does. */
 typedef struct {
     int64_t n0;          /* first output sample of the segment */
@@ -507,6 +507,74 @@ int vits_last_token_spans(vits_handle *h, int64_t *buf, size_t n_elems);
 int vits_warp_token(float semitones, int64_t *step, int64_t *cutoff, int32_t *half_taps);
 int vits_warp_plan(const int64_t *durations, const float *semitones, int len, int hop, vits_warp_seg *segs, int64_t *spans,
                    int64_t *n_out);
+
+/* ---- pitch contours: semitones glide within a token --------------------------------------------------------------------
+ * "Intonation" gives a staircase: the speed is constant per token and jumps at every boundary.  Here token t has a START and
+ * an END value in semitones and the speed moves linearly from one to the other across the token's output samples - the rise
+ * of a question, the fall at a full stop.  Constants, the table G, the sample formula, Q16 positions and int64 arithmetic
+ * are those of "intonation", unchanged; this section is the specification of what differs.
+ *
+ * Token t at st0, st1, each finite with |st| <= 12:  a = llrint(2^(st0 / 12) * ONE), b likewise from st1 (vits_warp_token's
+ *   step).
+ * Plan of a row: pos, n, cum and the skipping of dropped tokens as in "intonation".  For a kept token P = (cum * hop) << FB;
+ *   k = 0 if P <= pos, else L = P - pos and k = ceil(2 L / (a + b)); the record is {n0 = n, pos0 = pos, k, step0 = a,
+ *   step1 = b}.  Sample j of the token (0 <= j < k), all integer, floor division of non-negative numerators,
+ *   sgn = b >= a ? 1 : -1:
+ *     pos_j = pos0 + j * a + sgn * ((|b - a| * j * (j - 1)) / (2 k))
+ *     s_j   = a + sgn * ((|b - a| * j) / k)
+ *   The next token starts at pos = pos_k (the same formula at j = k), n += k.  The token may end up to 0.75 sample short of P
+ *   or under 2 samples past it; that is carried as the overshoot is in "intonation": the next L is measured from where the row
+ *   really is, nothing accumulates.  A token with more than 2^23 output samples is VITS_E_ARG (the products stay in int64);
+ *   N_b fits in int as before.
+ * Cutoff per output sample, from s = s_j in integers:
+ *     c = s <= ONE ? 55706 : (17 * 2^32 + 10 s) / (20 s);   Kh = ceil(Z * ONE / c)
+ *   For all 98 305 steps in [ONE / 2, 2 ONE] this is the c vits_warp_token derives in double, so a token with a == b has
+ *   exactly the step, c, Kh, k and positions of the "intonation" plan.  The sample is that section's formula at pos_j with
+ *   c(s_j), Kh(s_j).
+ * Properties (asserted by the tests on the engine's records): every increment pos_{j+1} - pos_j and every s_j lies in
+ *   [min(a, b), max(a, b)] - positions never decrease and advance by at most two samples per output -; the end of a row is
+ *   within 2 samples of cum * hop; with a == b the records reproduce vits_warp_plan's.
+ * (In float64 a tone at 0.15 / max(1, r_max) cycles per sample through one long token gliding -12 -> +12, +12 -> -12,
+ *   -3 -> +4 or 0 -> +7 comes out as cos(2 pi f0 pos_j / ONE + phase) within 2.1e-5 of amplitude 1; max s * sum|w| over
+ *   every step and 128 phases is 1.987, below the 1.99 the tests' tolerance counts with.)
+ *
+ * vits_run_async_glided is vits_run_async_ctl with the contour on top.
+ *   token_semitones NULL: zeros; token_semitones_end NULL: the start values.
+ *   If every token in front of lens[b] has st0 == st1 the call IS vits_run_async_warped with those values: the same kernel,
+ *     the same launch count, the same bits (all zeros: vits_run_async_ctl).  Otherwise one glide launch takes the place of
+ *     the warp launch; everything after it - vits_last_sample_counts, vits_fetch_output, vits_last_pcm16, every
+ *     vits_deliver*, vits_last_token_spans - works as after a warped run.
+ *   compensate = 1: token t's duration multiplier is token_rate[b][t] * (float)((r0 + r1) * 0.5), r0, r1 the doubles
+ *     2^(st / 12): the arithmetic mean, because k = L / mean step.  With equal ends that is (float)r.  The rest of the
+ *     compensate contract - the refusal with forced durations, compensate = 0 passing ctl through - is "intonation"'s.
+ *   Refusals, all before anything is enqueued, the previous run stays readable: an output rate or per-row rates set ("not
+ *     covered with an output rate set"); a value that is not finite within [-12, 12], naming token_semitones[b,t] or
+ *     token_semitones_end[b,t]; compensate with forced durations; a host-only handle.
+ * Out of scope: glides with an output rate or in chunked runs; curves other than linear in the output index; formant
+ * preservation; contour positions in time (the Python pitch_contour= places its points by phoneme count); vits_reserve does
+ * not count the buffer, as for the warp. */
+typedef struct {
+    int64_t n0;          /* first output sample of the segment */
+    int64_t pos0;        /* Q16 input position of that sample */
+    int64_t k;           /* output samples: the token's span is [n0, n0 + k) */
+    int32_t step0;       /* a: Q16 input samples per output sample at the token's start */
+    int32_t step1;       /* b: ... towards which it moves at the token's end */
+    int32_t pad_[2];     /* 0 */
+} vits_glide_seg;        /* 40 bytes, as vits_warp_seg */
+typedef struct {
+    const float *token_semitones;     /* host [B][T] start values; NULL: zeros */
+    const float *token_semitones_end; /* host [B][T] end values; NULL: = the start values */
+    int compensate;                   /* 1: tempo kept (above); 0: the pure warp */
+} vits_contour;
+int vits_run_async_glided(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
+                          const vits_noise *noise, const vits_controls *ctl, const vits_contour *contour);
+/* The plan - pure host code.  vits_glide_token: a token's two steps and the factor (float)((r0 + r1) / 2) its duration takes
+ * under compensate (each pointer may be NULL).  vits_glide_cutoff: c and Kh of a step within [ONE / 2, 2 ONE].
+ * vits_glide_plan: vits_warp_plan's sibling (st0 NULL: zeros; st1 NULL: = st0). */
+int vits_glide_token(float st0, float st1, int64_t *step0, int64_t *step1, float *rate);
+int vits_glide_cutoff(int64_t step, int64_t *c, int32_t *half_taps);
+int vits_glide_plan(const int64_t *durations, const float *st0, const float *st1, int len, int hop, vits_glide_seg *segs,
+                    int64_t *spans, int64_t *n_out);
 
 /* ---- delivery: the last run's audio packed per request on the device - PCM16, G.711, F32, pauses -------------------
  * The reference post-processes and frames every sentence on the host (phoonnx/voice.py:271-282 peak-normalise / volume /
@@ -1227,6 +1295,9 @@ int vits_test_resample_rows(int device_id, const float *x, const int64_t *lens, 
  * column of y is written.  Records that do not continue their row (n0, pos0) or leave a token's limits are VITS_E_ARG. */
 int vits_test_warp(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_warp_seg *segs,
                    const int32_t *seg_first /* [B+1] */, float *y, int S_w);
+/* ... and the glide ("pitch contours"): the same arguments over vits_glide_seg records, the pipeline's glide launch. */
+int vits_test_glide(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_glide_seg *segs,
+                    const int32_t *seg_first /* [B+1] */, float *y, int S_w);
 
 /* The kernels that turn tokens into frames and frames into samples, by value.  Every hook checks its sizes and extents on the
  * host (VITS_E_ARG) and launches the pipeline's kernel with the pipeline's grid.

@@ -79,6 +79,16 @@ class VitsIntonation(C.Structure):
     _fields_ = [("token_semitones", C.c_void_p), ("compensate", C.c_int)]
 
 
+class VitsGlideSeg(C.Structure):
+    """vits_glide_seg: one token's segment of a row with glides (vitsmi.h, "pitch contours"); 40 bytes"""
+    _fields_ = [("n0", C.c_int64), ("pos0", C.c_int64), ("k", C.c_int64), ("step0", C.c_int32), ("step1", C.c_int32),
+                ("pad_", C.c_int32 * 2)]
+
+
+class VitsContour(C.Structure):
+    _fields_ = [("token_semitones", C.c_void_p), ("token_semitones_end", C.c_void_p), ("compensate", C.c_int)]
+
+
 class VitsSegment(C.Structure):
     _fields_ = [("row", C.c_int32), ("stream", C.c_int32), ("lead_samples", C.c_int64), ("normalize", C.c_int32),
                 ("volume", C.c_float)]
@@ -164,6 +174,7 @@ EXPORTS = [
     "vits_set_output_rate", "vits_last_sample_counts", "vits_resample_plan", "vits_test_resample", "vits_test_resample_pieces",
     "vits_set_output_rates", "vits_last_sample_rates", "vits_test_resample_rows",
     "vits_run_async_warped", "vits_last_token_spans", "vits_warp_token", "vits_warp_plan", "vits_test_warp",
+    "vits_run_async_glided", "vits_glide_token", "vits_glide_cutoff", "vits_glide_plan", "vits_test_glide",
     "vits_test_durations", "vits_test_expand_prior", "vits_test_fill_normal", "vits_test_fill_normal_rows", "vits_test_post_conv",
     "vits_delivery_plan", "vits_deliver", "vits_test_deliver",
     "vits_trim_range", "vits_delivery_plan_trimmed", "vits_deliver_trimmed", "vits_test_deliver_trimmed",
@@ -282,6 +293,12 @@ def load():
     lib.vits_warp_token.argtypes = [C.c_float, i64p, i64p, C.POINTER(C.c_int32)]
     lib.vits_warp_plan.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, i64p]
     lib.vits_test_warp.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int]
+    lib.vits_run_async_glided.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.POINTER(VitsNoise), C.POINTER(VitsControls),
+                                          C.POINTER(VitsContour)]
+    lib.vits_glide_token.argtypes = [C.c_float, C.c_float, i64p, i64p, C.POINTER(C.c_float)]
+    lib.vits_glide_cutoff.argtypes = [C.c_int64, i64p, C.POINTER(C.c_int32)]
+    lib.vits_glide_plan.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, i64p]
+    lib.vits_test_glide.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int]
     lib.vits_test_durations.argtypes = [C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp, vp]
     lib.vits_test_expand_prior.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int64, C.c_int,
                                            C.c_float, vp, vp, vp]

@@ -1278,7 +1278,9 @@ struct RunRows {
     const int64_t *d_durations = nullptr;
     const float *d_token_rate = nullptr;
     // vits_intonation (validated by vits_run_async_warped): host [B][T] semitones of a run that is warped, and its host lens
+    // (vits_contour: semitones_end is set only where some token glides - the run then plans and launches the glide)
     const float *semitones = nullptr;
+    const float *semitones_end = nullptr;
     const int64_t *semitone_lens = nullptr;
     float at(int b, int col) const { return scales[(rows ? (int64_t)b * 3 : 0) + col]; }
     bool any(int B, int col) const {  // some utterance's value is not 0
@@ -2031,10 +2033,13 @@ int resample_rows_run(vits_handle *h, const int *ylen, int B) {
 // The whole waveform a run has just rendered (h->d_out, rows of h->S samples) -> [B][S_w], every token played back at its own
 // speed.  The plans come from the host copy of the durations, which the run's one readback left: no synchronisation.
 // d_out / S describe the warped buffer afterwards, as after resample_run.
-int warp_run(vits_handle *h, const RunRows &rr, int B, int T) {
+// One body serves the warp (Seg = vits_warp_seg) and the glide ("pitch contours", Seg = vits_glide_seg: a record of the same
+// size, so carve_warp carves either plan block): plan_row plans a row into its records, launch is the family's launch.
+template <class Seg, class PlanRow, class Launch>
+int warp_run_as(vits_handle *h, const RunRows &rr, int B, int T, PlanRow plan_row, Launch launch) {
     const int S = h->S, hop = h->model.hop;
     if (h->h_dur_B != B || h->h_dur_T != T) return fail(h, VITS_E_ARG, "no durations to plan the warp from");
-    std::vector<vits_warp_seg> segs;
+    std::vector<Seg> segs;
     std::vector<int32_t> first((size_t)B + 1, 0);
     std::vector<int64_t> spans((size_t)B * T, 0), n_in((size_t)B), dur((size_t)T);
     for (int b = 0; b < B; b++) {
@@ -2043,7 +2048,7 @@ int warp_run(vits_handle *h, const RunRows &rr, int B, int T) {
         const size_t at = segs.size();
         segs.resize(at + (size_t)L);
         int64_t ns = 0, N = 0;
-        const std::string e = warp_plan(dur.data(), rr.semitones + (size_t)b * T, L, hop, segs.data() + at, spans.data() + (size_t)b * T, ns, N);
+        const std::string e = plan_row(b, dur.data(), L, hop, segs.data() + at, spans.data() + (size_t)b * T, ns, N);
         if (!e.empty()) return fail(h, VITS_E_ARG, "row %d, %s", b, e.c_str());
         segs.resize(at + (size_t)ns);
         first[(size_t)b + 1] = (int32_t)segs.size();
@@ -2072,15 +2077,15 @@ int warp_run(vits_handle *h, const RunRows &rr, int B, int T) {
         HIPCHECK(h, hipHostMalloc((void **)&h->warp_pin, cap));
         h->warp_pin_cap = cap;
     }
-    const size_t seg_bytes = segs.size() * sizeof(vits_warp_seg);
+    const size_t seg_bytes = segs.size() * sizeof(Seg);
     if (seg_bytes) std::memcpy(h->warp_pin, segs.data(), seg_bytes);
     std::memcpy(h->warp_pin + seg_bytes, rows.data(), (size_t)B * sizeof(WarpRow));
     int *pin_nout = reinterpret_cast<int *>(h->warp_pin + wb.plan_bytes);
     for (int b = 0; b < B; b++) pin_nout[b] = rows[(size_t)b].n_out;
     HIPCHECK(h, hipMemcpyAsync(wb.segs, h->warp_pin, wb.plan_bytes, hipMemcpyHostToDevice, st));
     HIPCHECK(h, hipMemcpyAsync(wb.front.n_out, pin_nout, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
-    WarpArgs a{};
-    a.segs = wb.segs;
+    WarpArgsT<Seg> a{};
+    a.segs = reinterpret_cast<const Seg *>(wb.segs);
     a.rows = wb.rows;
     a.G = h->warp_G;
     a.x = h->d_out;
@@ -2088,7 +2093,7 @@ int warp_run(vits_handle *h, const RunRows &rr, int B, int T) {
     a.y = wb.front.out;
     a.y_pitch = S_w;
     a.n_hi = (int)S_w;
-    const hipError_t e = launch_warp(a, B, st);
+    const hipError_t e = launch(a, B, st);
     if (e != hipSuccess) return fail(h, VITS_E_DEVICE, "warp launch failed: %s", hipGetErrorString(e));
     h->stats.total_launches += 1;
     h->d_out = wb.front.out;
@@ -2102,6 +2107,23 @@ int warp_run(vits_handle *h, const RunRows &rr, int B, int T) {
     h->warp_spans = std::move(spans);
     h->warp_T = T;
     return 0;
+}
+
+// constant tokens: warp_kernel; some token glides (rr.semitones_end): glide_kernel in its slot
+int warp_run(vits_handle *h, const RunRows &rr, int B, int T) {
+    if (!rr.semitones_end)
+        return warp_run_as<vits_warp_seg>(
+            h, rr, B, T,
+            [&](int b, const int64_t *dur, int L, int hop, vits_warp_seg *segs, int64_t *spans, int64_t &ns, int64_t &N) {
+                return warp_plan(dur, rr.semitones + (size_t)b * T, L, hop, segs, spans, ns, N);
+            },
+            launch_warp);
+    return warp_run_as<vits_glide_seg>(
+        h, rr, B, T,
+        [&](int b, const int64_t *dur, int L, int hop, vits_glide_seg *segs, int64_t *spans, int64_t &ns, int64_t &N) {
+            return glide_plan(dur, rr.semitones + (size_t)b * T, rr.semitones_end + (size_t)b * T, L, hop, segs, spans, ns, N);
+        },
+        launch_glide);
 }
 
 // The two pinned buffers (vits_handle::ring) finished pieces reach the host through.  A piece is copied into slot(); queue()
@@ -3419,40 +3441,49 @@ int vits_run_async_ctl(vits_handle *h, const int64_t *ids, const int64_t *lens, 
 
 // vits_run_async_ctl with the intonation on top (vitsmi.h, "intonation").  What is pure host code - the semitones, the
 // contradictions, the rates that are set - is answered before the device is looked at: a host-only handle answers it too.
-int vits_run_async_warped(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
-                          const vits_noise *noise, const vits_controls *ctl, const vits_intonation *into) {
-    if (!h) return VITS_E_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
+// One body serves both entries: st0 the start values (NULL: zeros), st1 the end values (NULL: every token keeps its speed - the
+// warp's entry); `entry` names the caller in the refusal of an output rate.
+static int run_intoned_locked(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
+                              const vits_noise *noise, const vits_controls *ctl, const float *st0, const float *st1, int compensate,
+                              const char *entry) {
     if (!ctl) return fail(h, VITS_E_ARG, "null argument");
-    const float *sem = into ? into->token_semitones : nullptr;
-    bool warped = false;
-    if (sem) {
+    bool warped = false, glided = false;
+    if (st0 || st1) {
         if (B <= 0 || T <= 0) return fail(h, VITS_E_ARG, "empty batch or sequence (B=%d, T=%d)", B, T);
         if (!lens) return fail(h, VITS_E_ARG, "null argument");
         for (int b = 0; b < B; b++) {
             if (lens[b] < 0 || lens[b] > T) return fail(h, VITS_E_ARG, "input_lengths[%d]=%lld outside [0,%d]", b, (long long)lens[b], T);
             for (int t = 0; t < (int)lens[b]; t++) {
-                const float v = sem[(int64_t)b * T + t];
+                const float v = st0 ? st0[(int64_t)b * T + t] : 0.f, w = st1 ? st1[(int64_t)b * T + t] : v;
                 int64_t step, c;
                 int32_t Kh;
                 if (!warp_token(v, step, c, Kh))
                     return fail(h, VITS_E_ARG, "token_semitones[%d,%d]=%g is not a finite value within [-12, 12]", b, t, (double)v);
-                warped = warped || v != 0.f;
+                if (!warp_token(w, step, c, Kh))
+                    return fail(h, VITS_E_ARG, "token_semitones_end[%d,%d]=%g is not a finite value within [-12, 12]", b, t, (double)w);
+                warped = warped || v != 0.f || w != 0.f;
+                glided = glided || v != w;
             }
         }
     }
     vits_controls c2 = *ctl;
-    std::vector<float> rate;
+    std::vector<float> rate, zeros;
     if (warped) {
-        if (into->compensate && ctl->durations)
+        if (compensate && ctl->durations)
             return fail(h, VITS_E_ARG, "compensate and forced durations are contradictory: forced durations are the rendered ones");
-        if (h->rs.plan.on() || h->rows.on()) return fail(h, VITS_E_ARG, "vits_run_async_warped is not covered with an output rate set");
-        if (into->compensate) {  // the duration multiplier of token t: token_rate * (float)r_t, one fp32 product
+        if (h->rs.plan.on() || h->rows.on()) return fail(h, VITS_E_ARG, "%s is not covered with an output rate set", entry);
+        if (!st0) {
+            zeros.assign((size_t)B * T, 0.f);
+            st0 = zeros.data();
+        }
+        if (compensate) {  // the duration multiplier of token t: token_rate * (float)r_t - r_t the mean of its ends -, one fp32 product
             rate.assign((size_t)B * T, 1.0f);
             for (int b = 0; b < B; b++)
                 for (int t = 0; t < (int)lens[b]; t++) {
                     const size_t i = (size_t)b * T + t;
-                    rate[i] = (ctl->token_rate ? ctl->token_rate[i] : 1.0f) * (float)std::exp2((double)sem[i] / 12.0);
+                    const double r0 = std::exp2((double)st0[i] / 12.0);
+                    const float r = glided ? (float)((r0 + std::exp2((double)st1[i] / 12.0)) * 0.5) : (float)r0;
+                    rate[i] = (ctl->token_rate ? ctl->token_rate[i] : 1.0f) * r;
                 }
             c2.token_rate = rate.data();
         }
@@ -3461,11 +3492,29 @@ int vits_run_async_warped(vits_handle *h, const int64_t *ids, const int64_t *len
     RunRows rr;
     if (int rc = host_controls(h, &c2, lens, B, T, rr)) return rc;
     if (warped) {
-        rr.semitones = sem;
+        rr.semitones = st0;
+        rr.semitones_end = glided ? st1 : nullptr;  // equal ends: the warp itself
         rr.semitone_lens = lens;
     }
     vits_output dev{};
     return run_async_locked(h, ids, lens, B, T, rr, sid, noise, &dev);
+}
+
+int vits_run_async_warped(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
+                          const vits_noise *noise, const vits_controls *ctl, const vits_intonation *into) {
+    if (!h) return VITS_E_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    return run_intoned_locked(h, ids, lens, B, T, sid, noise, ctl, into ? into->token_semitones : nullptr, nullptr,
+                              into ? into->compensate : 0, "vits_run_async_warped");
+}
+
+// ... and with a start and an end value per token (vitsmi.h, "pitch contours"): equal ends everywhere are the call above
+int vits_run_async_glided(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
+                          const vits_noise *noise, const vits_controls *ctl, const vits_contour *contour) {
+    if (!h) return VITS_E_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    return run_intoned_locked(h, ids, lens, B, T, sid, noise, ctl, contour ? contour->token_semitones : nullptr,
+                              contour ? contour->token_semitones_end : nullptr, contour ? contour->compensate : 0, "vits_run_async_glided");
 }
 
 int vits_last_token_spans(vits_handle *h, int64_t *buf, size_t n_elems) {
@@ -3490,6 +3539,38 @@ int vits_warp_plan(const int64_t *durations, const float *semitones, int len, in
     if (len < 0 || hop < 1 || (len > 0 && !durations)) return fail(nullptr, VITS_E_ARG, "bad warp plan arguments (len = %d, hop = %d)", len, hop);
     int64_t ns = 0, N = 0;
     const std::string e = warp_plan(durations, semitones, len, hop, segs, spans, ns, N);
+    if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
+    if (n_out) *n_out = N;
+    return (int)ns;
+}
+
+int vits_glide_token(float st0, float st1, int64_t *step0, int64_t *step1, float *rate) {
+    int64_t a, b;
+    float r;
+    int bad = 0;
+    if (!glide_token(st0, st1, a, b, r, &bad))
+        return fail(nullptr, VITS_E_ARG, "semitones %g is not a finite value within [-12, 12]", (double)(bad ? st1 : st0));
+    if (step0) *step0 = a;
+    if (step1) *step1 = b;
+    if (rate) *rate = r;
+    return VITS_OK;
+}
+
+int vits_glide_cutoff(int64_t step, int64_t *c, int32_t *half_taps) {
+    if (step < kWarpMinStep || step > kWarpMaxStep)
+        return fail(nullptr, VITS_E_ARG, "step %lld outside [%lld, %lld]", (long long)step, (long long)kWarpMinStep, (long long)kWarpMaxStep);
+    int32_t c32, Kh;
+    glide_cutoff(step, c32, Kh);
+    if (c) *c = c32;
+    if (half_taps) *half_taps = Kh;
+    return VITS_OK;
+}
+
+int vits_glide_plan(const int64_t *durations, const float *st0, const float *st1, int len, int hop, vits_glide_seg *segs, int64_t *spans,
+                    int64_t *n_out) {
+    if (len < 0 || hop < 1 || (len > 0 && !durations)) return fail(nullptr, VITS_E_ARG, "bad glide plan arguments (len = %d, hop = %d)", len, hop);
+    int64_t ns = 0, N = 0;
+    const std::string e = glide_plan(durations, st0, st1, len, hop, segs, spans, ns, N);
     if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
     if (n_out) *n_out = N;
     return (int)ns;
@@ -4971,9 +5052,12 @@ int vits_test_resample(int device_id, const float *x, const int64_t *lens, int B
     return VITS_OK;
 }
 
-// The time warp by value: the rows' records from the caller's segments, the pipeline's launch.
-int vits_test_warp(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_warp_seg *segs, const int32_t *seg_first,
-                   float *y, int S_w) {
+// The time warp and the glide by value: the rows' records from the caller's segments, the pipeline's launch.
+extern "C++" {
+namespace {
+template <class Seg, class Fault, class Launch>
+int test_warp_as(int device_id, const float *x, const int64_t *counts, int B, int S, const Seg *segs, const int32_t *seg_first,
+                 float *y, int S_w, Fault fault, Launch launch) {
     if (int rc = test_dev(device_id)) return rc;
     if (!x || !y || !counts || !seg_first || B <= 0 || S <= 0 || S_w < 1) return fail(nullptr, VITS_E_ARG, "bad warp test arguments");
     if (seg_first[0] != 0) return fail(nullptr, VITS_E_ARG, "seg_first[0] = %d, not 0", (int)seg_first[0]);
@@ -4981,7 +5065,7 @@ int vits_test_warp(int device_id, const float *x, const int64_t *counts, int B, 
     for (int b = 0; b < B; b++) {
         const int32_t ns = seg_first[b + 1] - seg_first[b];
         if (ns < 0 || (ns > 0 && !segs)) return fail(nullptr, VITS_E_ARG, "row %d: seg_first is not ascending", b);
-        const std::string e = warp_segs_fault(segs + seg_first[b], ns);
+        const std::string e = fault(segs + seg_first[b], ns);
         if (!e.empty()) return fail(nullptr, VITS_E_ARG, "row %d: %s", b, e.c_str());
         n_in[(size_t)b] = counts[b] < 0 ? 0 : (counts[b] > S ? S : counts[b]);
     }
@@ -4992,8 +5076,8 @@ int vits_test_warp(int device_id, const float *x, const int64_t *counts, int B, 
     warp_table(G.data());
     DevBufs D;
     const size_t n_segs = (size_t)seg_first[B];
-    const vits_warp_seg none{};
-    WarpArgs a{};
+    const Seg none{};
+    WarpArgsT<Seg> a{};
     a.segs = D.up(n_segs ? segs : &none, n_segs ? n_segs : 1);
     a.rows = D.up(rows.data(), rows.size());
     a.G = D.up(G.data(), G.size());
@@ -5004,10 +5088,22 @@ int vits_test_warp(int device_id, const float *x, const int64_t *counts, int B, 
     a.y_pitch = S_w;
     a.n_hi = S_w;
     TCHECK(D.err);
-    TCHECK(launch_warp(a, B, nullptr));
+    TCHECK(launch(a, B, nullptr));
     TCHECK(hipDeviceSynchronize());
     TCHECK(download(y, dy, (size_t)B * S_w));
     return VITS_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int vits_test_warp(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_warp_seg *segs, const int32_t *seg_first,
+                   float *y, int S_w) {
+    return test_warp_as(device_id, x, counts, B, S, segs, seg_first, y, S_w, warp_segs_fault, launch_warp);
+}
+
+int vits_test_glide(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_glide_seg *segs, const int32_t *seg_first,
+                    float *y, int S_w) {
+    return test_warp_as(device_id, x, counts, B, S, segs, seg_first, y, S_w, glide_segs_fault, launch_glide);
 }
 
 // The rows entry by value: the plans of the distinct rates among out_rates (0 or in_rate: a native row), one record per row,

@@ -23,8 +23,9 @@ namespace vitsmi {
 constexpr int kWarpBlock = 256;                                        // output samples (= threads) per workgroup
 constexpr int kWarpSpan = (kWarpBlock - 1) * 2 + 2 + 2 * kWarpMaxHalf;  // the input floats a tile stages at most (588)
 
-struct WarpArgs {
-    const vits_warp_seg *segs;
+template <class Seg>
+struct WarpArgsT {
+    const Seg *segs;
     const WarpRow *rows;  // [B]
     const float *G;       // [kWarpTable]
     const float *x;       // input samples of row b at x + b * x_pitch
@@ -33,9 +34,12 @@ struct WarpArgs {
     int64_t y_pitch;
     int n_hi;             // S_w: the launch renders output samples [0, n_hi) of every row
 };
+using WarpArgs = WarpArgsT<vits_warp_seg>;
+using GlideArgs = WarpArgsT<vits_glide_seg>;  // "pitch contours": the same launch over gliding records
 
 // the last segment whose n0 <= n (segments without an output sample share the n0 of the one behind them)
-__device__ __forceinline__ int warp_find(const vits_warp_seg *sg, int n_segs, int64_t n) {
+template <class Seg>
+__device__ __forceinline__ int warp_find(const Seg *sg, int n_segs, int64_t n) {
     int lo = 0, hi = n_segs - 1;
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
@@ -113,6 +117,70 @@ inline hipError_t launch_warp(const WarpArgs &a, int B, hipStream_t st) {
     if (B <= 0 || a.n_hi <= 0) return hipSuccess;
     const dim3 grid((unsigned)(((int64_t)a.n_hi + kWarpBlock - 1) / kWarpBlock), (unsigned)B);
     warp_kernel<<<grid, kWarpBlock, 0, st>>>(a);
+    return hipGetLastError();
+}
+
+// ---- pitch contours (include/vitsmi.h, "pitch contours"): warp_kernel's sibling for rows with a gliding token.
+//
+// Geometry, staging and the copy branch are warp_kernel's.  What differs is per lane behind the barrier: the position and
+// the speed of a sample come from the closed forms of the definition (glide_pos, glide_step: warp.hpp), the cutoff and the
+// half-taps from the speed (glide_cutoff), then the shared warp_sample.  The divisions are plain unsigned 64-bit divisions
+// by k and by 2k, and one by 20s in the cutoff - the compiler's expansion, three a lane: the numerators reach 2^63, so
+// neither a 32-bit nor a floating-point reciprocal gives the definition's integers for every input, and against the
+// 38..76 taps of a sample the three divisions are a few per cent.  Lanes of one wave now differ in Kh inside a token: the
+// tap loop runs to the wave's longest.  The staging bound holds as it is because every increment of the position lies in
+// [min(a, b), max(a, b)] <= 2 * ONE, across segment boundaries too (a token starts at the pos_k of the one before it).
+__global__ void __launch_bounds__(kWarpBlock) glide_kernel(GlideArgs a) {
+    __shared__ float xs[kWarpSpan];
+    __shared__ float gs[kWarpTable];
+    const int b = blockIdx.y;
+    const WarpRow r = a.rows[b];
+    const int64_t n0 = (int64_t)blockIdx.x * kWarpBlock, n = n0 + threadIdx.x;
+    const float *xrow = a.x + (int64_t)b * a.x_pitch;
+    float *yrow = a.y + (int64_t)b * a.y_pitch;
+    if (n0 >= r.n_out || r.identity || r.n_segs <= 0) {  // behind the row's end: zeros; an identity row: its valid samples
+        if (n < a.n_hi) yrow[n] = (r.identity && n < r.n_out && n < r.n_in) ? xrow[n] : 0.f;
+        return;
+    }
+    const vits_glide_seg *sg = a.segs + r.seg0;
+    const int64_t n_last = (n0 + kWarpBlock < r.n_out ? n0 + kWarpBlock : (int64_t)r.n_out) - 1;
+    const int j0 = warp_find(sg, r.n_segs, n0), j1 = warp_find(sg, r.n_segs, n_last);
+    const int64_t i_lo = glide_pos(sg[j0].pos0, sg[j0].k, sg[j0].step0, sg[j0].step1, n0 - sg[j0].n0) >> kWarpFB;
+    const int64_t i_hi = glide_pos(sg[j1].pos0, sg[j1].k, sg[j1].step0, sg[j1].step1, n_last - sg[j1].n0) >> kWarpFB;
+    const int64_t m_base = i_lo - kWarpMaxHalf + 1;
+    int64_t len = i_hi - i_lo + 2 * kWarpMaxHalf;
+    len = len > kWarpSpan ? kWarpSpan : len;  // (never: positions advance by at most two samples an output)
+    for (int q = threadIdx.x; q < (int)len; q += kWarpBlock) {
+        const int64_t m = m_base + q;
+        xs[q] = m >= 0 && m < r.n_in ? xrow[m] : 0.f;
+    }
+    for (int q = threadIdx.x; q < kWarpTable; q += kWarpBlock) gs[q] = a.G[q];
+    __syncthreads();
+    if (n >= a.n_hi) return;
+    float v = 0.f;
+    if (n < r.n_out) {
+        int j = j0;
+        while (j < j1 && sg[j + 1].n0 <= n) j++;
+        const vits_glide_seg g = sg[j];
+        const int64_t pos = glide_pos(g.pos0, g.k, g.step0, g.step1, n - g.n0);
+        int32_t c, Kh;
+        glide_cutoff(glide_step(g.k, g.step0, g.step1, n - g.n0), c, Kh);
+        const int64_t at = (pos >> kWarpFB) - m_base;  // the tap m = i0 in the staged span
+        // Dead code, kept as the fence it is in warp_kernel: positions never decrease along a row, so i_lo <= pos >> FB <= i_hi,
+        // and Kh <= kWarpMaxHalf because s_j <= max(a, b) <= 2 * ONE; hence 0 <= at - Kh + 1 and at + Kh <= i_hi - i_lo + 75 < len
+        // - len is never clipped, the tile's span being at most 255 increments of at most two samples.
+        if (at - Kh + 1 >= 0 && at + Kh < len) {
+            const float *w = xs + at;
+            v = warp_sample(gs, pos, c, Kh, [&](int d) { return w[d]; });
+        }
+    }
+    yrow[n] = v;
+}
+
+inline hipError_t launch_glide(const GlideArgs &a, int B, hipStream_t st) {
+    if (B <= 0 || a.n_hi <= 0) return hipSuccess;
+    const dim3 grid((unsigned)(((int64_t)a.n_hi + kWarpBlock - 1) / kWarpBlock), (unsigned)B);
+    glide_kernel<<<grid, kWarpBlock, 0, st>>>(a);
     return hipGetLastError();
 }
 

@@ -24,7 +24,16 @@ constexpr float kWarpMaxSemitones = 12.f;
 constexpr int64_t kWarpMinStep = kWarpOne / 2, kWarpMaxStep = kWarpOne * 2;  // -12 and +12 semitones
 constexpr int kWarpMaxHalf = 38;           // half-taps at +12 semitones: the most a token has
 
+constexpr int64_t kGlideMaxSpan = int64_t(1) << 23;  // output samples a gliding token has at most: |b - a| * j * (j - 1) stays in int64
+
 static_assert(sizeof(vits_warp_seg) == 40, "vits_warp_seg is a 40-byte record");
+static_assert(sizeof(vits_glide_seg) == sizeof(vits_warp_seg), "carve_warp carves the plan block of either record");
+
+#if defined(__HIPCC__)
+#define VITSMI_HD __host__ __device__
+#else
+#define VITSMI_HD
+#endif
 
 // a row of a launch: its segment records, its valid input samples, its output samples
 struct WarpRow {
@@ -109,9 +118,108 @@ inline bool warp_identity(const vits_warp_seg *segs, int64_t n_segs) {
     return true;
 }
 
+// ---- pitch contours (include/vitsmi.h, "pitch contours"): the speed moves linearly from step0 to step1 across a token
+
+// THE cutoff of an output sample whose speed is `step` (Q16, within [kWarpMinStep, kWarpMaxStep]), in integers: for every such
+// step the c and Kh warp_token derives in double.  Host plan, hooks and glide_kernel call this one function.
+VITSMI_HD inline void glide_cutoff(int64_t step, int32_t &c, int32_t &Kh) {
+    c = step <= kWarpOne ? 55706 : (int32_t)(((uint64_t(17) << 32) + 10u * (uint64_t)step) / (20u * (uint64_t)step));
+    Kh = (int32_t)(((uint32_t)kWarpZ * (uint32_t)kWarpOne + (uint32_t)c - 1u) / (uint32_t)c);
+}
+
+// Q16 input position of sample j (0 <= j <= k; j == k: where the next token starts) of the record {pos0, k, a, b}:
+// pos0 + j * a + sgn * floor(|b - a| * j * (j - 1) / (2 k)).  The numerator is below 2^17 * 2^23 * 2^23.
+VITSMI_HD inline int64_t glide_pos(int64_t pos0, int64_t k, int32_t a, int32_t b, int64_t j) {
+    const uint64_t d = (uint64_t)(b >= a ? b - a : a - b);
+    if (d == 0 || j < 2) return pos0 + j * a;
+    const int64_t q = (int64_t)(d * (uint64_t)j * (uint64_t)(j - 1) / (2u * (uint64_t)k));
+    return pos0 + j * a + (b >= a ? q : -q);
+}
+
+// the speed of that sample: a + sgn * floor(|b - a| * j / k)
+VITSMI_HD inline int64_t glide_step(int64_t k, int32_t a, int32_t b, int64_t j) {
+    const uint64_t d = (uint64_t)(b >= a ? b - a : a - b);
+    if (d == 0 || j == 0) return a;
+    const int64_t q = (int64_t)(d * (uint64_t)j / (uint64_t)k);
+    return b >= a ? a + q : a - q;
+}
+
+// the two steps of a token and the factor its duration takes under compensate: (float)((r0 + r1) / 2); false: a value is
+// not finite within [-12, 12] (*bad: 0 the start value, 1 the end value)
+inline bool glide_token(float st0, float st1, int64_t &a, int64_t &b, float &rate, int *bad = nullptr) {
+    int64_t c;
+    int32_t Kh;
+    if (!warp_token(st0, a, c, Kh)) {
+        if (bad) *bad = 0;
+        return false;
+    }
+    if (!warp_token(st1, b, c, Kh)) {
+        if (bad) *bad = 1;
+        return false;
+    }
+    rate = (float)((std::exp2((double)st0 / 12.0) + std::exp2((double)st1 / 12.0)) * 0.5);
+    return true;
+}
+
+// warp_plan's sibling: token t glides from st0[t] to st1[t] (st0 == nullptr: zeros; st1 == nullptr: = st0)
+inline std::string glide_plan(const int64_t *durations, const float *st0, const float *st1, int len, int hop, vits_glide_seg *segs,
+                              int64_t *spans, int64_t &n_segs, int64_t &n_out) {
+    char buf[200];
+    int64_t pos = 0, n = 0, cum = 0;
+    n_segs = 0;
+    for (int t = 0; t < len; t++) {
+        if (spans) spans[t] = 0;
+        const int64_t D = durations[t];
+        if (D < 0) {
+            std::snprintf(buf, sizeof buf, "token %d: duration %lld is negative", t, (long long)D);
+            return buf;
+        }
+        if (D == 0) continue;
+        const float v0 = st0 ? st0[t] : 0.f, v1 = st1 ? st1[t] : v0;
+        int64_t a, b;
+        float rate;
+        int bad = 0;
+        if (!glide_token(v0, v1, a, b, rate, &bad)) {
+            std::snprintf(buf, sizeof buf, "token %d: semitones %g is not a finite value within [-12, 12]", t, (double)(bad ? v1 : v0));
+            return buf;
+        }
+        cum += D;
+        if (cum > (INT64_MAX >> (kWarpFB + 2)) / hop) {
+            std::snprintf(buf, sizeof buf, "token %d: %lld frames of %d samples leave the range of a position", t, (long long)cum, hop);
+            return buf;
+        }
+        const int64_t P = (cum * hop) << kWarpFB;
+        const int64_t k = P <= pos ? 0 : (2 * (P - pos) + (a + b) - 1) / (a + b);
+        if (k > kGlideMaxSpan) {
+            std::snprintf(buf, sizeof buf, "token %d: %lld output samples, more than a gliding token admits (%lld)", t, (long long)k,
+                          (long long)kGlideMaxSpan);
+            return buf;
+        }
+        if (segs) segs[n_segs] = vits_glide_seg{n, pos, k, (int32_t)a, (int32_t)b, {0, 0}};
+        if (spans) spans[t] = k;
+        n_segs++;
+        n += k;
+        pos = glide_pos(pos, k, (int32_t)a, (int32_t)b, k);
+        if (n > INT_MAX) {
+            std::snprintf(buf, sizeof buf, "token %d: the row reaches %lld output samples, more than a row admits (%d)", t, (long long)n, INT_MAX);
+            return buf;
+        }
+    }
+    n_out = n;
+    return "";
+}
+
+// every token of the row keeps the unit step: a masked copy (a row without a segment too)
+inline bool warp_identity(const vits_glide_seg *segs, int64_t n_segs) {
+    for (int64_t j = 0; j < n_segs; j++)
+        if (segs[j].step0 != kWarpOne || segs[j].step1 != kWarpOne) return false;
+    return true;
+}
+
 // the rows' records of a launch from each row's segments [seg_first[b], seg_first[b + 1]) and valid input samples
 // (a row without a segment: N_b = n_b); returns S_w = max(1, max_b N_b)
-inline int64_t warp_rows(const vits_warp_seg *segs, const int32_t *seg_first, const int64_t *n_in, int B, std::vector<WarpRow> &rows) {
+template <class Seg>
+inline int64_t warp_rows(const Seg *segs, const int32_t *seg_first, const int64_t *n_in, int B, std::vector<WarpRow> &rows) {
     rows.resize((size_t)B);
     int64_t S_w = 1;
     for (int b = 0; b < B; b++) {
@@ -141,6 +249,30 @@ inline std::string warp_segs_fault(const vits_warp_seg *segs, int64_t n_segs) {
         }
         n += g.k;
         pos = g.pos0 + g.k * (int64_t)g.step;
+        if (n > INT_MAX) {
+            std::snprintf(buf, sizeof buf, "segment %lld: the row reaches %lld output samples, more than a row admits (%d)", (long long)j, (long long)n, INT_MAX);
+            return buf;
+        }
+    }
+    return "";
+}
+
+// warp_segs_fault's sibling: each record within the limits of a gliding token, each starting where the closed form
+// (glide_pos at j = k) ends the one before it
+inline std::string glide_segs_fault(const vits_glide_seg *segs, int64_t n_segs) {
+    char buf[240];
+    int64_t n = 0, pos = 0;
+    for (int64_t j = 0; j < n_segs; j++) {
+        const vits_glide_seg &g = segs[j];
+        if (g.step0 < kWarpMinStep || g.step0 > kWarpMaxStep || g.step1 < kWarpMinStep || g.step1 > kWarpMaxStep || g.k < 0 ||
+            g.k > kGlideMaxSpan || g.n0 != n || g.pos0 != pos) {
+            std::snprintf(buf, sizeof buf, "segment %lld {n0 %lld, pos0 %lld, k %lld, step0 %d, step1 %d} does not continue the row at "
+                                           "output %lld, position %lld within the limits of a token",
+                          (long long)j, (long long)g.n0, (long long)g.pos0, (long long)g.k, g.step0, g.step1, (long long)n, (long long)pos);
+            return buf;
+        }
+        n += g.k;
+        pos = glide_pos(g.pos0, g.k, g.step0, g.step1, g.k);
         if (n > INT_MAX) {
             std::snprintf(buf, sizeof buf, "segment %lld: the row reaches %lld output samples, more than a row admits (%d)", (long long)j, (long long)n, INT_MAX);
             return buf;

@@ -221,23 +221,33 @@ def _controls(rows, seeds, durations, token_rate):
     return c
 
 
-def _semitones(token_semitones, lens, B, T):
+def _semitones(token_semitones, lens, B, T, name="token_semitones"):
     """token_semitones - None, or floats [B, T] within [-12, 12] in front of lens[b] (vitsmi.h, "intonation") -> float32
     [B, T], contiguous"""
     if token_semitones is None:
         return None
     st = np.asarray(token_semitones)
     if st.dtype.kind not in "fiu":
-        raise SessionError(f"Unexpected input data type: 'token_semitones' must be floats, got {st.dtype}")
+        raise SessionError(f"Unexpected input data type: '{name}' must be floats, got {st.dtype}")
     if st.shape != (B, T):
-        raise SessionError(f"Invalid shape for 'token_semitones': {st.shape}, expected [batch_size, phonemes] = {(B, T)}")
+        raise SessionError(f"Invalid shape for '{name}': {st.shape}, expected [batch_size, phonemes] = {(B, T)}")
     st = np.ascontiguousarray(st, np.float32)
     live = np.arange(T)[None, :] < np.asarray(lens)[:, None]
     bad = live & ~(np.isfinite(st) & (np.abs(st) <= 12))
     if bad.any():
         b, t = (int(v) for v in np.argwhere(bad)[0])
-        raise SessionError(f"token_semitones[{b},{t}]={float(st[b, t])} is not a finite value within [-12, 12]")
+        raise SessionError(f"{name}[{b},{t}]={float(st[b, t])} is not a finite value within [-12, 12]")
     return st
+
+
+def _contour(token_semitones, token_semitones_end, lens, B, T):
+    """(start, end) values of a run (vitsmi.h, "pitch contours"): end None - no glide: (_semitones(...), None); else both
+    float32 [B, T], the start values zeros where only the end values are given"""
+    st0 = _semitones(token_semitones, lens, B, T)
+    if token_semitones_end is None:
+        return st0, None
+    st1 = _semitones(token_semitones_end, lens, B, T, "token_semitones_end")
+    return (np.zeros((B, T), np.float32) if st0 is None else st0), st1
 
 
 def token_span_bounds(spans, count) -> np.ndarray:
@@ -1060,7 +1070,7 @@ class MiSession:
 
     def synthesize_batch(self, ids, lens, scales, sid=None, noise_dp=None, noise_z=None, taps=(), seeds=None,
                          durations=None, token_rate=None, return_durations=False, output_rates=None, token_semitones=None,
-                         compensate=True):
+                         compensate=True, token_semitones_end=None):
         """One batched run.  Returns {"output": [B,1,1,S] float32, "y_lengths": int64 [B], taps...}.
         output_rates: None, or a rate per row for this call (set_output_rates; what was set before is put back afterwards);
         with row rates the result also holds "sample_rates" (int32 [B]).
@@ -1078,19 +1088,22 @@ class MiSession:
         time warp on the device (vitsmi.h, "intonation": the resampling shift, formants move along); compensate=True keeps
         the tempo (the token is rendered longer by 2^(st/12) first), False is the pure warp.  The result then holds
         "sample_lengths" - each row's valid samples behind the warp - and, with return_durations, "token_spans" (int64
-        [B, T]: the output samples of each token; "durations" stay the rendered frames)."""
+        [B, T]: the output samples of each token; "durations" stay the rendered frames).
+        token_semitones_end: None or floats [B, T] within [-12, 12] - token t GLIDES from token_semitones[b, t] (zeros where
+        that is None) to this value across its output samples (vitsmi.h, "pitch contours"); compensate=True renders it longer
+        by the mean of 2^(st/12) at its two ends.  Equal ends everywhere are the token_semitones run, bit for bit."""
         ids, lens, scales, sid, noise_dp, noise_z, noise, seeds, durations, token_rate = self._run_arguments(
             ids, lens, scales, sid, noise_dp, noise_z, seeds, durations, token_rate)
         B = ids.shape[0]
-        semitones = _semitones(token_semitones, lens, B, ids.shape[1])
+        semitones, semitones_end = _contour(token_semitones, token_semitones_end, lens, B, ids.shape[1])
         # enqueue -> frame counts -> copy-out -> taps all use this handle's one workspace
         with self._locked(), self._rates_for_call(output_rates):
             try:
-                self._begin(ids, lens, scales, sid, noise, seeds, durations, token_rate, semitones, compensate)
+                self._begin(ids, lens, scales, sid, noise, seeds, durations, token_rate, semitones, compensate, semitones_end)
                 ylen = self.last_y_lengths()
                 dur = self.last_durations() if return_durations else None
                 counts = self.last_sample_counts() if self.resampling or self.output_rates is not None or semitones is not None else None
-                spans = self._token_spans(semitones, lens) if return_durations and semitones is not None else None
+                spans = self._token_spans(semitones, lens, semitones_end) if return_durations and semitones is not None else None
                 S = int(ylen.max()) * self.hparam("hop") if counts is None else int(counts.max())
                 audio = _POOL.array((B, 1, 1, S)) if self.pinned_results else np.empty((B, 1, 1, S), np.float32)
                 self._fetch(audio, 0, B)
@@ -1098,7 +1111,8 @@ class MiSession:
                 self._fall_back_to_bf16x6(exc)
                 return self.synthesize_batch(ids, lens, scales, sid, noise_dp, noise_z, taps, seeds=seeds,
                                              durations=durations, token_rate=token_rate, return_durations=return_durations,
-                                             token_semitones=token_semitones, compensate=compensate)
+                                             token_semitones=token_semitones, compensate=compensate,
+                                             token_semitones_end=token_semitones_end)
             res = {"output": audio, "y_lengths": ylen}
             if counts is not None:
                 res["sample_lengths"] = counts
@@ -1143,12 +1157,19 @@ class MiSession:
             noise.noise_z_stride = noise_z.shape[2]
         return ids, lens, scales, sid, noise_dp, noise_z, noise, seeds, durations, token_rate
 
-    def _begin(self, ids, lens, scales, sid, noise, seeds=None, durations=None, token_rate=None, semitones=None, compensate=True):
+    def _begin(self, ids, lens, scales, sid, noise, seeds=None, durations=None, token_rate=None, semitones=None, compensate=True,
+               semitones_end=None):
         """vits_run_async: validated host arrays in, the whole path enqueued; frame counts and durations are known on
         return.  ([B, 3] scales or seeds: vits_run_async_rows; durations or token_rate: vits_run_async_ctl; semitones:
-        vits_run_async_warped.)"""
+        vits_run_async_warped; semitones_end too: vits_run_async_glided.)"""
         B, T = ids.shape
-        if semitones is not None:
+        if semitones_end is not None:
+            rows = _rows(scales, B)
+            ctl = _controls(rows, seeds, durations, token_rate)
+            contour = _ffi.VitsContour(semitones.ctypes.data, semitones_end.ctypes.data, 1 if compensate else 0)
+            rc = self._lib.vits_run_async_glided(self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(sid), C.byref(noise),
+                                                 C.byref(ctl), C.byref(contour))
+        elif semitones is not None:
             rows = _rows(scales, B)
             ctl = _controls(rows, seeds, durations, token_rate)
             into = _ffi.VitsIntonation(semitones.ctypes.data, 1 if compensate else 0)
@@ -1731,11 +1752,11 @@ class MiSession:
                 raise SessionError(f"vits_last_token_spans: the run changed between two calls ({n} != {buf.size})")
             return buf
 
-    def _token_spans(self, semitones, lens) -> np.ndarray:
-        """the spans of the last run, begun with `semitones`: the warp's, or - every semitone 0, the run was not warped -
-        what the identity plan gives: durations * hop"""
+    def _token_spans(self, semitones, lens, semitones_end=None) -> np.ndarray:
+        """the spans of the last run, begun with `semitones` (and the glides' end values): the warp's, or - every semitone 0,
+        the run was not warped - what the identity plan gives: durations * hop"""
         live = np.arange(semitones.shape[1])[None, :] < np.asarray(lens)[:, None]
-        if (live & (semitones != 0)).any():
+        if (live & ((semitones != 0) if semitones_end is None else ((semitones != 0) | (semitones_end != 0)))).any():
             return self.last_token_spans()
         return self.last_durations() * self.hparam("hop")
 
@@ -1874,7 +1895,8 @@ class MiSession:
     def synthesize_delivered(self, ids, lens, scales, sid=None, *, segments=None, n_streams=None, encoding="pcm16",
                              normalize=True, volume=1.0, seeds=None, durations=None, token_rate=None, noise_dp=None,
                              noise_z=None, return_durations=False, trim=None, levels=None, shapes=None, token_gain_db=None,
-                             gain_ramp=0.01, limits=None, output_rates=None, token_semitones=None, compensate=True):
+                             gain_ramp=0.01, limits=None, output_rates=None, token_semitones=None, compensate=True,
+                             token_semitones_end=None):
         """One batched run and its delivery under one hold of the session lock: what leaves the GPU is the encoded audio
         of the plan and nothing else - the fp32 waveform is never copied to the host.  segments=None: one stream per row,
         with `normalize` / `volume` as scalars or [B] arrays (row b's own).  Everything in front of the delivery is
@@ -1895,13 +1917,14 @@ class MiSession:
         and the result holds "sample_rates" (int32 [B]).
         token_semitones, compensate - as synthesize_batch: the delivery then works on the warped waveform and its counts; the
         token gains' breakpoints lie on the warp's own token spans, and with return_durations the result holds "token_spans".
+        token_semitones_end - as synthesize_batch: the tokens glide ("pitch contours"); everything behind the run is the same.
         Returns {"streams": [array per stream], "stream_samples": int64 [J], "y_lengths": int64 [B], "sample_lengths":
         int64 [B] (each row's valid samples at the delivered rate), "kept_first" / "kept_count": int64 [G] (what each
         segment delivers of its row: all of it without a trim)[, "durations"]}."""
         ids, lens, scales, sid, noise_dp, noise_z, noise, seeds, durations, token_rate = self._run_arguments(
             ids, lens, scales, sid, noise_dp, noise_z, seeds, durations, token_rate)
         B = ids.shape[0]
-        semitones = _semitones(token_semitones, lens, B, ids.shape[1])
+        semitones, semitones_end = _contour(token_semitones, token_semitones_end, lens, B, ids.shape[1])
         if segments is None:
             try:
                 nz = np.broadcast_to(np.asarray(normalize, bool), (B,))
@@ -1936,12 +1959,12 @@ class MiSession:
                     raise SessionError(f"segment {i}: token_gain_db and explicit points on the same segment")
         with self._locked(), self._rates_for_call(output_rates):
             try:
-                self._begin(ids, lens, scales, sid, noise, seeds, durations, token_rate, semitones, compensate)
+                self._begin(ids, lens, scales, sid, noise, seeds, durations, token_rate, semitones, compensate, semitones_end)
                 ylen = self.last_y_lengths()
                 dur = self.last_durations() if return_durations or tgains is not None else None
                 counts = self.last_sample_counts()
                 rates = self.last_sample_rates() if self.output_rates is not None else None
-                spans = self._token_spans(semitones, lens) if semitones is not None and (return_durations or tgains is not None) else None
+                spans = self._token_spans(semitones, lens, semitones_end) if semitones is not None and (return_durations or tgains is not None) else None
                 loud = gain = None
                 if tgains is not None:
                     used = self._token_shapes(segments, used, tgains, dur, lens, counts, gain_ramp, spans)
@@ -1964,7 +1987,7 @@ class MiSession:
                                                  noise_dp=noise_dp, noise_z=noise_z, return_durations=return_durations,
                                                  trim=trim, levels=levels, shapes=shapes, token_gain_db=token_gain_db,
                                                  gain_ramp=gain_ramp, limits=limits, token_semitones=token_semitones,
-                                                 compensate=compensate)
+                                                 compensate=compensate, token_semitones_end=token_semitones_end)
         res = {"streams": streams, "stream_samples": np.array([a.size for a in streams], np.int64), "y_lengths": ylen,
                "sample_lengths": counts, "kept_first": kept_first, "kept_count": kept_count}
         if levels is not None:
@@ -2239,7 +2262,8 @@ class PipelinedSession:
         return np.concatenate([self.parts[i].last_durations() for i in range(n)])
 
     def synthesize_batch(self, ids, lens, scales, sid=None, seeds=None, durations=None, token_rate=None,
-                         return_durations=False, noise_dp=None, noise_z=None, token_semitones=None, compensate=True):
+                         return_durations=False, noise_dp=None, noise_z=None, token_semitones=None, compensate=True,
+                         token_semitones_end=None):
         """Host arrays in, host arrays out, like MiSession.synthesize_batch (scales [3] or [B, 3], seeds, durations [B, T],
         token_rate [B, T], injected noise_dp [B, 2, T] / noise_z [B, inter, >= F]: each part gets its own rows of all of
         them; return_durations adds "durations" [B, T], the parts' rows in request order).  One worker thread per sub-batch (the C
@@ -2252,6 +2276,9 @@ class PipelinedSession:
             # (the parts' warped rows have lengths of their own behind the barrier that sizes the one result: not a pass-through)
             raise SessionError("Unexpected input: 'token_semitones' / 'compensate' are not covered by PipelinedSession "
                                "(MiSession.synthesize_batch takes them)")
+        if token_semitones_end is not None:  # (for the same reason)
+            raise SessionError("Unexpected input: 'token_semitones_end' is not covered by PipelinedSession "
+                               "(MiSession.synthesize_batch takes it)")
         ids = np.ascontiguousarray(ids)
         lens = np.ascontiguousarray(lens)
         if ids.dtype != np.int64 or lens.dtype != np.int64 or ids.ndim != 2 or lens.shape != (ids.shape[0],):
@@ -2780,6 +2807,61 @@ def test_warp(x, counts, row_segs, device_id=0):
     rc = _ffi.load().vits_test_warp(device_id, _ffi.ptr(x), _ffi.ptr(counts), B, S, segs, _ffi.ptr(first), _ffi.ptr(y), S_w)
     if rc != 0:
         raise SessionError(f"vits_test_warp failed [{rc}]: {_ffi.last_error(None)}")
+    return y
+
+
+def glide_token(st0, st1):
+    """(step0, step1, rate) of a token gliding from st0 to st1 semitones (vits_glide_token: pure host code); rate is the
+    float32 factor its duration takes under compensate"""
+    a, b, r = C.c_int64(), C.c_int64(), C.c_float()
+    rc = _ffi.load().vits_glide_token(float(st0), float(st1), C.byref(a), C.byref(b), C.byref(r))
+    if rc != 0:
+        raise SessionError(f"vits_glide_token failed [{rc}]: {_ffi.last_error(None)}")
+    return a.value, b.value, np.float32(r.value)
+
+
+def glide_cutoff(step):
+    """(c, half_taps) of an output sample whose speed is `step` (vits_glide_cutoff: pure host code)"""
+    c, Kh = C.c_int64(), C.c_int32()
+    rc = _ffi.load().vits_glide_cutoff(int(step), C.byref(c), C.byref(Kh))
+    if rc != 0:
+        raise SessionError(f"vits_glide_cutoff failed [{rc}]: {_ffi.last_error(None)}")
+    return c.value, Kh.value
+
+
+def glide_plan(durations, st0, st1, hop):
+    """One row's plan with glides (vits_glide_plan: pure host code): durations [T] in frames, st0 / st1 [T] or None ->
+    (segments: a ctypes array of _ffi.VitsGlideSeg, spans int64 [T], N)."""
+    D = np.ascontiguousarray(durations, np.int64)
+    a = None if st0 is None else np.ascontiguousarray(st0, np.float32)
+    b = None if st1 is None else np.ascontiguousarray(st1, np.float32)
+    if D.ndim != 1 or any(v is not None and v.shape != D.shape for v in (a, b)):
+        raise SessionError(f"durations must be [T] and st0 / st1 [T] or None, got {D.shape}")
+    segs = (_ffi.VitsGlideSeg * max(len(D), 1))()
+    spans = np.zeros(len(D), np.int64)
+    n = C.c_int64()
+    count = _ffi.load().vits_glide_plan(_ffi.ptr(D), _ffi.ptr(a), _ffi.ptr(b), len(D), int(hop), segs, _ffi.ptr(spans), C.byref(n))
+    if count < 0:
+        raise SessionError(f"vits_glide_plan failed [{count}]: {_ffi.last_error(None)}")
+    return (_ffi.VitsGlideSeg * count)(*segs[:count]), spans, n.value
+
+
+def test_glide(x, counts, row_segs, device_id=0):
+    """The glide by value (vits_test_glide): test_warp over rows of _ffi.VitsGlideSeg (glide_plan's)."""
+    x = np.ascontiguousarray(x, np.float32)
+    counts = np.ascontiguousarray(counts, np.int64)
+    if x.ndim != 2 or counts.shape != (x.shape[0],) or len(row_segs) != x.shape[0]:
+        raise SessionError(f"x must be [B, S], counts [B] and row_segs B sequences, got {x.shape} / {counts.shape} / {len(row_segs)}")
+    B, S = x.shape
+    flat = [g for row in row_segs for g in row]
+    first = np.cumsum([0] + [len(row) for row in row_segs]).astype(np.int32)
+    segs = (_ffi.VitsGlideSeg * max(len(flat), 1))(*flat)
+    n_out = [int(row[-1].n0 + row[-1].k) if len(row) else int(min(max(counts[b], 0), S)) for b, row in enumerate(row_segs)]
+    S_w = max(1, max(n_out))
+    y = np.full((B, S_w), np.nan, np.float32)
+    rc = _ffi.load().vits_test_glide(device_id, _ffi.ptr(x), _ffi.ptr(counts), B, S, segs, _ffi.ptr(first), _ffi.ptr(y), S_w)
+    if rc != 0:
+        raise SessionError(f"vits_test_glide failed [{rc}]: {_ffi.last_error(None)}")
     return y
 
 

@@ -585,6 +585,74 @@ class TTSVoice:
                 raise ValueError(f"phoneme_pitch: {v} semitones in sentence {k} is not a finite value within [-12, 12]")
         return [v for v, (_, ids) in zip(vals, groups) for _ in ids]
 
+    @staticmethod
+    def _group_contour(pitch_contour, k: int, groups):
+        """pitch_contour -> (start, end) values in semitones per phoneme id of sentence k.  The contour is a sequence of
+        (position in [0, 1], semitones) points, positions non-decreasing, or a callable (sentence_index, [the groups'
+        tokens]) -> such a sequence.  Positions are fractions of the sentence's PHONEME COUNT: with n groups, boundary i lies
+        at i / n, and its value is interpolated linearly in semitones between the points on either side of it - the first
+        point's value in front of it, the last one's behind it, the later one's where two points share a position.
+        Group i glides from value(i / n) to value((i + 1) / n).  THE id-level rule: a group of m ids splits its glide
+        into m equal parts in semitones - id q starts at v0 + (v1 - v0) * q / m and ends where id q + 1 starts, the last
+        at v1 itself - so the value is continuous across the ids of a group, its blanks included."""
+        pts = pitch_contour(k, [token for token, _ in groups]) if callable(pitch_contour) else pitch_contour
+        try:
+            pts = [(float(p), float(v)) for p, v in pts]
+        except (TypeError, ValueError):
+            raise ValueError(f"pitch_contour of sentence {k} must be a sequence of (position, semitones) points") from None
+        if not pts:
+            raise ValueError(f"pitch_contour of sentence {k} has no point")
+        for i, (p, v) in enumerate(pts):
+            if not (np.isfinite(p) and 0.0 <= p <= 1.0) or (i and p < pts[i - 1][0]):
+                raise ValueError(f"pitch_contour: position {p} in sentence {k} is not within [0, 1] in non-decreasing order")
+            if not (np.isfinite(v) and abs(v) <= 12.0):
+                raise ValueError(f"pitch_contour: {v} semitones in sentence {k} is not a finite value within [-12, 12]")
+
+        def value(x):
+            j = max((i for i, (p, _) in enumerate(pts) if p <= x), default=-1)
+            if j < 0:
+                return pts[0][1]
+            if j == len(pts) - 1:
+                return pts[j][1]
+            (p0, v0), (p1, v1) = pts[j], pts[j + 1]
+            return v0 + (v1 - v0) * (x - p0) / (p1 - p0)
+
+        n = len(groups)
+        st0, st1 = [], []
+        for i, (_, ids) in enumerate(groups):
+            v0, v1 = value(i / n), value((i + 1) / n)
+            m = len(ids)
+            cuts = [v0] + [v0 + (v1 - v0) * q / m for q in range(1, m)] + [v1]
+            st0 += cuts[:m]
+            st1 += cuts[1:m + 1]
+        return st0, st1
+
+    @classmethod
+    def _sentence_semitones(cls, phoneme_pitch, pitch_contour, k: int, groups):
+        """(start values, end values or None) per phoneme id of sentence k: phoneme_pitch alone is _group_semitones' constant
+        tokens; a pitch_contour glides, with phoneme_pitch - if given too - added to both ends"""
+        base = None if phoneme_pitch is None else cls._group_semitones(phoneme_pitch, k, groups)
+        if pitch_contour is None:
+            return base, None
+        st0, st1 = cls._group_contour(pitch_contour, k, groups)
+        if base is not None:
+            st0, st1 = [a + c for a, c in zip(st0, base)], [b + c for b, c in zip(st1, base)]
+            for v in st0 + st1:
+                if not abs(v) <= 12.0:
+                    raise ValueError(f"pitch_contour + phoneme_pitch: {v} semitones in sentence {k} is not within [-12, 12]")
+        return st0, st1
+
+    def _contour_check(self, pitch_contour, rates=None) -> None:
+        """pitch_contour needs a session whose delivery takes end values, and audio at the voice's own rate"""
+        import inspect
+        if pitch_contour is None:
+            return
+        fn = getattr(self.session, "synthesize_delivered", None)
+        if fn is None or "token_semitones_end" not in inspect.signature(fn).parameters:
+            raise ValueError("pitch_contour needs a session that glides on the device (synthesize_delivered(token_semitones_end=))")
+        if self._ratio() is not None or any(self._ratio(r) is not None for r in rates or ()):
+            raise ValueError("pitch_contour is not covered with an output rate set")
+
     def _pitch_check(self, phoneme_pitch, rates=None) -> None:
         """phoneme_pitch needs a session whose delivery takes semitones, and audio at the voice's own rate"""
         import inspect
@@ -642,7 +710,7 @@ class TTSVoice:
                            alignments: bool = False, trim_silence=None, trailing_silence: float = 0.0, loudness=None,
                            loudness_scope: str = "sentence", peak_ceiling: float = 0.0, max_gain_db: float = 30.0,
                            fade_in: float = 0.0, fade_out: float = 0.0, fade_curve: str = "linear", phoneme_gain_db=None,
-                           limit_ceiling: float = 0.0, limit_lookahead: float = 0.005, phoneme_pitch=None):
+                           limit_ceiling: float = 0.0, limit_lookahead: float = 0.005, phoneme_pitch=None, pitch_contour=None):
         """Extension: the whole text as ONE stream of encoded audio ("pcm16", "ulaw", "alaw", "f32"; audio_encoding).  All
         sentences render in one batch; with a session that delivers (MiSession.synthesize_delivered) post-processing,
         encoding and the packing happen on the device and only the encoded audio crosses the bus; any other session
@@ -681,6 +749,14 @@ class TTSVoice:
         Alignments then come from the warp's token spans, and every sample-valued option - fades, per-phoneme volume, trims,
         look-ahead - is laid out over the warped audio.  It needs a session that warps (ValueError otherwise) and a voice
         without an output_sample_rate (ValueError "not covered with an output rate set").
+        pitch_contour - SSML's contour, applied to each sentence: a sequence of (position in [0, 1], semitones within
+        [-12, 12]) points with non-decreasing positions, or a callable (sentence_index, tokens) -> such a sequence.  The pitch
+        GLIDES through the points (vitsmi.h, "pitch contours"): linear in semitones between them, the first and the last
+        value held outside them.  Positions are fractions of the sentence's PHONEME COUNT, not of time - durations do not
+        exist before the run: with n phoneme groups, group i glides from the contour's value at i / n to its value at
+        (i + 1) / n.  phoneme_pitch, if given too, is added to both ends; a sum outside [-12, 12] is a ValueError naming the
+        sentence.  Tempo, alignments and sample-valued options as for phoneme_pitch.  It needs a session that glides
+        (ValueError otherwise) and is refused with an output rate set as phoneme_pitch is.
         Returns an audio_encoding.EncodedAudio."""
         from . import audio_encoding as ae
         from .sharding import pad_batch
@@ -699,12 +775,18 @@ class TTSVoice:
         if phoneme_gain_db is not None and not (hasattr(self.session, "synthesize_delivered") or hasattr(self.session, "synthesize_batch")):
             raise ValueError("phoneme_gain_db needs a session that reports durations (synthesize_batch)")
         self._pitch_check(phoneme_pitch)
-        groups = self._sentence_groups(text, cfg) if want_dur or phoneme_gain_db is not None or phoneme_pitch is not None else None
+        self._contour_check(pitch_contour)
+        pitched = phoneme_pitch is not None or pitch_contour is not None
+        groups = self._sentence_groups(text, cfg) if want_dur or phoneme_gain_db is not None or pitched else None
         all_ids = [[i for _, ids in g for i in ids] for g in groups] if groups is not None else self._sentence_ids(text, cfg)
         if not all_ids:
             return ae.EncodedAudio(ae.silence(0, encoding), encoding, self.sample_rate, [], [], [] if want_dur else None)
         token_db = None if phoneme_gain_db is None else [self._group_db(phoneme_gain_db, k, g) for k, g in enumerate(groups)]
-        token_st = None if phoneme_pitch is None else [self._group_semitones(phoneme_pitch, k, g) for k, g in enumerate(groups)]
+        token_st = token_st_end = None
+        if pitched:
+            pairs = [self._sentence_semitones(phoneme_pitch, pitch_contour, k, g) for k, g in enumerate(groups)]
+            token_st = [a for a, _ in pairs]
+            token_st_end = None if pitch_contour is None else [b for _, b in pairs]
         durs = frames = spans = None
         if hasattr(self.session, "synthesize_delivered"):
             from .session import Segment
@@ -728,6 +810,8 @@ class TTSVoice:
                 more["limits"] = limit
             if token_st is not None:
                 more["token_semitones"] = self._padded_db(token_st)
+            if token_st_end is not None:
+                more["token_semitones_end"] = self._padded_db(token_st_end)
             out = self.session.synthesize_delivered(ids, lens, self._scales(cfg), sid, segments=segs, n_streams=1,
                                                     encoding=encoding, return_durations=want_dur, **more)
             data = out["streams"][0]
@@ -787,7 +871,7 @@ class TTSVoice:
     def stream_encoded(self, text: str, syn_config: Optional[SynthesisConfig] = None, encoding: str = "pcm16",
                        chunk_frames: int = 64, sentence_silence: float = 0.0, ref_peak=None, fade_in: float = 0.0,
                        fade_out: float = 0.0, fade_curve: str = "linear", phoneme_gain_db=None, limit_ceiling: float = 0.0,
-                       limit_lookahead: float = 0.005, trim_silence=None, phoneme_pitch=None):
+                       limit_lookahead: float = 0.005, trim_silence=None, phoneme_pitch=None, pitch_contour=None):
         """Extension: synthesize_encoded's ONE stream as a generator of `bytes`, handed out while the audio still renders.
         All sentences render as one chunked batch (MiSession.synthesize_stream_encoded: post-processing, encoding and the
         masking to each sentence's own length happen on the device, per chunk).  Sentence 0's chunks are yielded as they
@@ -809,8 +893,11 @@ class TTSVoice:
         limiter start there.  A stream keeps as much of keep_lead as it has not handed over yet: with keep_lead <=
         limit_lookahead, or an onset within the first chunk, the bytes are synthesize_encoded's under the same leading trim.
         The trailing silence stays: a stream learns where its audio ends only at the end.
-        phoneme_pitch is refused (ValueError): the chunked entries have no warped form."""
+        phoneme_pitch and pitch_contour are refused (ValueError): the chunked entries have no warped form."""
         from . import audio_encoding as ae
+        if pitch_contour is not None:
+            raise ValueError("pitch_contour is not covered by stream_encoded: the chunked entries have no warped form "
+                             "(synthesize_encoded takes it)")
         if phoneme_pitch is not None:
             raise ValueError("phoneme_pitch is not covered by stream_encoded: the chunked entries have no warped form "
                              "(synthesize_encoded takes it)")
@@ -980,7 +1067,8 @@ class TTSVoice:
                                     fade_out: float = 0.0, fade_curve: str = "linear", phoneme_gain_db=None,
                                     limit_ceiling: float = 0.0, limit_lookahead: float = 0.005,
                                     output_sample_rates: Optional[Sequence[Optional[int]]] = None,
-                                    encodings: Optional[Sequence[Optional[str]]] = None, phoneme_pitch=None):
+                                    encodings: Optional[Sequence[Optional[str]]] = None, phoneme_pitch=None,
+                                    pitch_contour=None):
         """Extension: synthesize_requests with every request's audio returned as one stream of encoded audio
         (audio_encoding.EncodedAudio; the pause of synthesize_encoded in front of each sentence).  The batching is
         synthesize_requests': sentences sorted by length, max_batch at a time, each with its request's settings and seed.
@@ -1006,10 +1094,13 @@ class TTSVoice:
         what this call returns for it on a voice loaded at that rate with that encoding, bit for bit.  ValueError with a
         session that has no set_output_rates.
         phoneme_pitch as in synthesize_encoded, for every sentence of every request (a callable's sentence_index counts within
-        its request); ValueError with a session that does not warp, and together with an output rate of the voice or of a request."""
+        its request); ValueError with a session that does not warp, and together with an output rate of the voice or of a request.
+        pitch_contour as in synthesize_encoded, applied to every sentence of every request, with phoneme_pitch's refusals."""
         from . import audio_encoding as ae
         ae._check(encoding)
         self._pitch_check(phoneme_pitch, [r for r in output_sample_rates or () if r is not None])
+        self._contour_check(pitch_contour, [r for r in output_sample_rates or () if r is not None])
+        pitched = phoneme_pitch is not None or pitch_contour is not None
         lead = self._lead_samples(sentence_silence)
         trim = self._trim(trim_silence, trailing_silence)
         shape = self._shape(fade_in, fade_out, fade_curve)
@@ -1157,14 +1248,14 @@ class TTSVoice:
         want_dur = alignments and hasattr(self.session, "last_durations")
         rows, groups, db_of, st_of = [], {}, {}, {}
         for r, ((text, _), cfg) in enumerate(zip(requests, cfgs)):
-            if want_dur or phoneme_gain_db is not None or phoneme_pitch is not None:
+            if want_dur or phoneme_gain_db is not None or pitched:
                 for k, g in enumerate(self._sentence_groups(text, cfg)):
                     groups[r, k] = g
                     rows.append((r, k, [i for _, ids in g for i in ids]))
                     if phoneme_gain_db is not None:
                         db_of[r, k] = self._group_db(phoneme_gain_db, k, g)
-                    if phoneme_pitch is not None:
-                        st_of[r, k] = self._group_semitones(phoneme_pitch, k, g)
+                    if pitched:
+                        st_of[r, k] = self._sentence_semitones(phoneme_pitch, pitch_contour, k, g)
             else:
                 rows.extend((r, k, ids) for k, ids in enumerate(self._sentence_ids(text, cfg)))
         piece, aligned, kept_of, level_of, mul_of = {}, {}, {}, {}, {}
@@ -1192,8 +1283,10 @@ class TTSVoice:
             if limit is not None and not host_level:  # (scope "text": the host that levels limits too)
                 more["limits"] = limit
             need_dur = want_dur or (host_level and phoneme_gain_db is not None)
-            if phoneme_pitch is not None:
-                more["token_semitones"] = self._padded_db([st_of[r, k] for r, k, _ in run])
+            if pitched:
+                more["token_semitones"] = self._padded_db([st_of[r, k][0] for r, k, _ in run])
+            if pitch_contour is not None:
+                more["token_semitones_end"] = self._padded_db([st_of[r, k][1] for r, k, _ in run])
             if mixed:
                 # a rate and an encoding per row: the same call with its request's own things in every list (a request whose
                 # trim or shape comes to nothing at its rate: the neutral one)
@@ -1219,7 +1312,7 @@ class TTSVoice:
                                               None if phoneme_gain_db is None else [db_of[r, k] for r, k, _ in run],
                                               None if phoneme_gain_db is None else [out["durations"][b, :len(i)] for b, (_, _, i) in enumerate(run)],
                                               counts, [as_of[r][0] for r, _, _ in run] if mixed else None,
-                                              out["token_spans"] if phoneme_pitch is not None and phoneme_gain_db is not None else None)
+                                              out["token_spans"] if pitched and phoneme_gain_db is not None else None)
                 for b, (r, k, _) in enumerate(run):
                     a, c = (int(out["kept_first"][b]), int(out["kept_count"][b]))
                     mul_of[r, k] = ae.shape_multiplier(a, c, run_shapes[b])
@@ -1229,7 +1322,7 @@ class TTSVoice:
                     level_of[r, k] = (float(out["loudness"][b]), float(out["gain"][b]))
                 if trim is not None:
                     kept_of[r, k] = (int(out["kept_first"][b]), int(out["kept_count"][b]))
-                if want_dur and phoneme_pitch is not None:
+                if want_dur and pitched:
                     aligned[r, k] = build_span_alignments(groups[r, k], out["token_spans"][b], int(out["sample_lengths"][b]))
                 elif want_dur:
                     aligned[r, k] = build_alignments(groups[r, k], out["durations"][b], hop,
