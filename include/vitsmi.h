@@ -1262,12 +1262,51 @@ int vits_bench_conv1d_sx(int device_id, int B, int Cin, int Cout, int T, int K, 
                          float *ms_out);
 /* Two dependent convs of a ResBlock in one fused launch on a raw-format stage (csrc/conv_sx_pair.hip.hpp), C in {32, 64},
  * f16x3 arithmetic, c1 = Conv1d(C, C, K, dilation dil1), c2 = Conv1d(C, C, K, dilation dil2), both "same"-padded:
- *   chain == 0 (ResBlock1 step):   out = c2(leaky_relu(c1(leaky_relu(x, slope)), slope)) + x
- *   chain != 0 (two ResBlock2 steps): x1 = c1(leaky_relu(x, slope)) + x ; out = c2(leaky_relu(x1, slope)) + x1
+ *   (chain & 1) == 0 (ResBlock1 step):   out = c2(leaky_relu(c1(leaky_relu(x, slope)), slope)) + x
+ *   (chain & 1) != 0 (two ResBlock2 steps): x1 = c1(leaky_relu(x, slope)) + x ; out = c2(leaky_relu(x1, slope)) + x1
+ * chain bits 1-2 choose the kernel: 0 conv_sx_pair_kernel, 1 conv_sx_pair16_kernel in f16x3, 2 the same in the single-plane
+ * arithmetic; bit 3 (pair16 only): out is read back from the output planes, leaky_relu(result, slope).  The pair16 forms are
+ * vits_test_conv_pair16_epi's launch with `raw` or `planes`, no lens, buffers that start as zeros.
  * ms_out (nullable): average launch time over 10 launches. */
 int vits_test_conv_pair_sx(int device_id, const float *x, int B, int C, int T, const float *w1, const float *b1,
                            const float *w2, const float *b2, int K, int dil1, int dil2, int chain, float slope, float *out,
                            float *ms_out);
+/* The fused ResBlock step (csrc/conv_sx_pair16.hip.hpp, conv_sx_pair16_kernel) with the whole argument set the generator's
+ * conv_sx_pair16() gives it: one launch of the kernel's own launcher, its arguments filled by the function the generator
+ * fills them with.  Every pointer is a host pointer, tensors are dense [B][C][T]; c1 = Conv1d(C, C, K, dilation dil1),
+ * c2 = Conv1d(C, C, K, dilation dil2), both "same"-padded; utterance b's tensors end at end_b = min(T, (lens[b] + rag_add) *
+ * rag_mul) columns (0 for lens[b] == 0; T without lens):
+ *   x is zero at columns >= end_b, whatever the planes hold there
+ *   c1 = conv(leaky_relu(x, slope), w1) + b1;  chain == 0: mid = c1, res = x;  chain != 0: mid = c1 + x, res = mid
+ *   mid is zero at columns >= end_b;  value = conv(leaky_relu(mid, slope), w2) + b2 + res, + old_out (ACC), / div (DIV)
+ *   RAW: out stores value;  PLANES: the planes store leaky_relu(value, slope);  columns >= end_b are not written.
+ * The input is uploaded as the operand planes of leaky_relu(x, slope); where x_tail is given, its values (activated the same
+ * way) replace x at columns >= end_b.  out starts as old_out, else as `sentinel`; the planes start as the sentinel's split;
+ * both carry a guard band of sentinel cells behind the last utterance.
+ * Refused with VITS_E_ARG, never launched: what sx_pair16_plan() refuses, ACC without old_out, lens outside [0, T]; what
+ * launch_conv_sx_pair16() itself refuses (DIV without ACC, ..) comes back as VITS_E_DEVICE. */
+enum { VITS_P16_EPI_ACC = 1, VITS_P16_EPI_DIV = 2, VITS_P16_EPI_RAW = 4, VITS_P16_EPI_PLANES = 8 };
+typedef struct {
+    int B, C, T, K, dil1, dil2, chain;
+    int precision;           /* VITS_SX_F16X3 or VITS_SX_F16 */
+    int flags;               /* VITS_P16_EPI_* */
+    float slope, div, sentinel;
+    const float *x;          /* [B][C][T] */
+    const float *w1, *b1, *w2, *b2;  /* w [C][C][K]; b [C] or NULL */
+    const float *old_out;    /* [B][C][T] previous contents of the raw tensor (the ACC operand), or NULL */
+    const float *x_tail;     /* [B][C][T] or NULL: what the input planes hold at columns >= end_b instead of x */
+    const int64_t *lens;     /* [B] in [0, T], or NULL: every utterance spans T */
+    int rag_add, rag_mul;    /* SxRagged::add / mul; rag_mul >= 1 */
+    float *out;              /* [B][C][T] the raw tensor as the launch left it (nullable) */
+    float *planes_out;       /* [B][C][T] read back from the output planes (nullable) */
+    float *x_seen;           /* [B][C][T] nullable: x as the kernel recovers it from the input planes (leaky_relu undone) */
+    float *ms_out;           /* nullable: average launch time over 10 more launches */
+    char kernel[128];        /* out: the instantiation launched (as in vits_launch_record) */
+    int BN, BNo, ovl;        /* out: tile columns, kept columns per tile, whether Y overlays the x tile */
+    float peak;              /* out: the largest of the launch's 64 range-guard slots (SxPair16Args::peak) */
+    int guard_ok;            /* out: the guard bands behind both outputs, and the planes' unused third, kept their bits */
+} vits_test_conv_pair16_epi_args;
+int vits_test_conv_pair16_epi(int device_id, vits_test_conv_pair16_epi_args *a);
 /* Relative-position multi-head self-attention core (attentions.py:225-272): q,k,v
  * [B,C,T] host, emb_rel_k/v [2w+1, dk], lens int64[B]; out [B,C,T]. */
 int vits_test_attention(int device_id, const float *qkv, int B, int C, int T, int n_heads, const float *rel_k,

@@ -60,6 +60,16 @@ class VitsTestConvSxEpiArgs(C.Structure):
                [(n, C.c_int) for n in ("pack_cfg", "run_cfg_used", "rawin", "s16", "ck")] + [("peak", C.c_float)]
 
 
+class VitsTestConvPair16EpiArgs(C.Structure):
+    """vits_test_conv_pair16_epi_args of include/vitsmi.h"""
+    _fields_ = [(n, C.c_int) for n in ("B", "C", "T", "K", "dil1", "dil2", "chain", "precision", "flags")] + \
+               [(n, C.c_float) for n in ("slope", "div", "sentinel")] + \
+               [(n, C.c_void_p) for n in ("x", "w1", "b1", "w2", "b2", "old_out", "x_tail", "lens")] + \
+               [("rag_add", C.c_int), ("rag_mul", C.c_int)] + \
+               [(n, C.c_void_p) for n in ("out", "planes_out", "x_seen", "ms_out")] + [("kernel", C.c_char * 128)] + \
+               [(n, C.c_int) for n in ("BN", "BNo", "ovl")] + [("peak", C.c_float), ("guard_ok", C.c_int)]
+
+
 class VitsOpenOptions(C.Structure):
     _fields_ = [("device_id", C.c_int), ("gen_precision", C.c_char_p), ("arena_dev", C.c_void_p),
                 ("arena_bytes", C.c_size_t), ("host_only", C.c_int), ("layout_only", C.c_int)]
@@ -189,6 +199,7 @@ EXPORTS = [
     "vits_test_stream_pack_trimmed",
     "vits_test_layernorm", "vits_test_dds", "vits_test_cf_pre", "vits_test_rqs_inverse", "vits_test_ea_logw",
     "vits_test_conv1d_epi", "vits_test_wn_gate", "vits_test_cond_matvec", "vits_test_conv1d_sx_epi",
+    "vits_test_conv_pair16_epi",
 ]
 
 
@@ -377,6 +388,7 @@ def load():
     lib.vits_bench_conv1d_sx.argtypes = [C.c_int] * 9 + [f32p]
     lib.vits_test_conv1d_epi.argtypes = [C.c_int, C.POINTER(VitsTestConvEpiArgs)]
     lib.vits_test_conv1d_sx_epi.argtypes = [C.c_int, C.POINTER(VitsTestConvSxEpiArgs)]
+    lib.vits_test_conv_pair16_epi.argtypes = [C.c_int, C.POINTER(VitsTestConvPair16EpiArgs)]
     lib.vits_test_wn_gate.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     lib.vits_test_cond_matvec.argtypes = [C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp]
     lib.vits_test_conv_pair_sx.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int,

@@ -675,7 +675,12 @@ inline bool sx_pair16_geom(int C, int npl, int BN, bool ovl, int K1, int dil1, i
     return BN - halo2 >= BN / 2 + BN / 8;  // (more than 37 % of a tile recomputed: not worth it)
 }
 
-hipError_t launch_conv_sx_pair16(SxPair16Args a, int C, int npl, int B, hipStream_t stream, bool chain);
+// the tile a launch ran on, as the launcher chose it (for callers that report it: the kernel-level test hook)
+struct SxPair16Tile {
+    int BN, BNo;
+    bool ovl, persist;
+};
+hipError_t launch_conv_sx_pair16(SxPair16Args a, int C, int npl, int B, hipStream_t stream, bool chain, SxPair16Tile *tile = nullptr);
 // which tile a (C, npl, halo) combination runs on: 0 = unsupported, else BN (128 | 256) and whether Y overlays x
 int sx_pair16_plan(int C, int npl, int K1, int dil1, int K2, int dil2, bool *ovl);
 
@@ -748,7 +753,7 @@ int sx_pair16_plan(int C, int npl, int K1, int dil1, int K2, int dil2, bool *ovl
     return 0;
 }
 
-hipError_t launch_conv_sx_pair16(SxPair16Args a, int C, int npl, int B, hipStream_t stream, bool chain) {
+hipError_t launch_conv_sx_pair16(SxPair16Args a, int C, int npl, int B, hipStream_t stream, bool chain, SxPair16Tile *tile) {
     bool ovl = false;
     const int BN = sx_pair16_plan(C, npl, a.K1, a.dil1, a.K2, a.dil2, &ovl);
     // the persistent form where x and Y fit side by side (it cannot overlay: the x buffer is refilled under phase 2)
@@ -757,6 +762,7 @@ hipError_t launch_conv_sx_pair16(SxPair16Args a, int C, int npl, int B, hipStrea
     SxPair16Geom g;
     if (!BN || !sx_pair16_geom(C, npl, BN, ovl, a.K1, a.dil1, a.K2, a.dil2, &g)) return hipErrorInvalidValue;
     if (a.pad1 * 2 != (a.K1 - 1) * a.dil1 || a.pad2 * 2 != (a.K2 - 1) * a.dil2) return hipErrorInvalidValue;  // "same" padding
+    if (tile) *tile = SxPair16Tile{BN, g.BNo, ovl, persist};
     a.LW1 = g.LW1;
     a.RS1 = g.RS1;
     a.RS2 = g.RS2;

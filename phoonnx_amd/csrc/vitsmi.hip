@@ -881,36 +881,48 @@ bool sx_pair16_ok(const vits_handle *h, const ConvDesc &c1, const ConvDesc &c2) 
     return sx_pair16_plan(c1.Cin, h1 ? 1 : 2, c1.K, c1.dil, c2.K, c2.dil, nullptr) != 0;
 }
 
-// x: the operand-plane tensor holding leaky_relu(x, slope) (two fp16 planes: f16x3; one: the single-plane arithmetic).
-// out_raw: fp32 raw destination (flags & P16_HAS_RAW) and / or EPI_ACC operand; out_pl (flags & P16_HAS_PL): operand planes of
-// leaky_relu(result, slope).
-void conv_sx_pair16(Ctx &c, const ConvDesc &c1, const ConvDesc &c2, const uint16_t *x, int T, float *out_raw, uint16_t *out_pl, int flags,
-                    float div, float slope, bool chain) {
+// What a call site decides of a fused launch - the generator below and the kernel-level test hook (vits_test_conv_pair16_epi)
+// fill SxPair16Args here and nowhere else; the tile geometry is launch_conv_sx_pair16()'s.  A: the arena the convs were packed
+// into, zeros: >= 1 KiB of zeros.
+static SxPair16Args sx_pair16_args(const ConvDesc &c1, const ConvDesc &c2, const float *A, const float *zeros, const uint16_t *x, int T,
+                                   float *out_raw, uint16_t *out_pl, int flags, float div, float slope, SxRagged rag, unsigned *peak) {
     SxPair16Args a{};
-    const bool h1 = c1.h1;
     const int C = c1.Cin;
+    const auto P = [A](int64_t off) { return off >= 0 ? A + off : nullptr; };
     a.xpl = x;
     a.x_bstride = (int64_t)3 * C * T;
     a.islope = a.mslope = a.oslope = slope;
     a.T = T;
-    a.wp1 = reinterpret_cast<const u32x4 *>(c.P(c1.w_off));
-    a.wp2 = reinterpret_cast<const u32x4 *>(c.P(c2.w_off));
-    a.bias1 = c.P(c1.b_off);
-    a.bias2 = c.P(c2.b_off);
+    a.wp1 = reinterpret_cast<const u32x4 *>(P(c1.w_off));
+    a.wp2 = reinterpret_cast<const u32x4 *>(P(c2.w_off));
+    a.bias1 = P(c1.b_off);
+    a.bias2 = P(c2.b_off);
     a.wscale1 = c1.wscale;
     a.wscale2 = c2.wscale;
     a.out_raw = out_raw;
     a.raw_bstride = (int64_t)C * T;
     a.out_pl = out_pl;
     a.pl_bstride = (int64_t)3 * C * T;
-    a.zeros = c.P(c.m.zeros_off);
+    a.zeros = zeros;
     a.K1 = c1.K; a.dil1 = c1.dil; a.pad1 = c1.padL;
     a.K2 = c2.K; a.dil2 = c2.dil; a.pad2 = c2.padL;
     a.flags = flags;
     a.div = div;
+    a.rag = rag;
+    a.peak = peak;
+    return a;
+}
+
+// x: the operand-plane tensor holding leaky_relu(x, slope) (two fp16 planes: f16x3; one: the single-plane arithmetic).
+// out_raw: fp32 raw destination (flags & P16_HAS_RAW) and / or EPI_ACC operand; out_pl (flags & P16_HAS_PL): operand planes of
+// leaky_relu(result, slope).
+void conv_sx_pair16(Ctx &c, const ConvDesc &c1, const ConvDesc &c2, const uint16_t *x, int T, float *out_raw, uint16_t *out_pl, int flags,
+                    float div, float slope, bool chain) {
+    const bool h1 = c1.h1;
+    const int C = c1.Cin;
     vits_handle *h = c.h;
-    a.rag = c.rag_at(T);
-    a.peak = range_slots(h, true);
+    const SxPair16Args a = sx_pair16_args(c1, c2, c.A, c.P(c.m.zeros_off), x, T, out_raw, out_pl, flags, div, slope, c.rag_at(T),
+                                          range_slots(h, true));
     const double ebytes = h1 ? 2.0 : 4.0;
     const bool ev = conv_event_begin(c);
     c.note(launch_conv_sx_pair16(a, C, h1 ? 1 : 2, c.B, c.st, chain));
@@ -4720,96 +4732,194 @@ int vits_test_conv_transpose1d_sx(int device_id, const float *x, int B, int Cin,
     return run_test_conv_sx(d, arena, x, B, T, 0, 0.f, out);
 }
 
-// out = c2(lrelu(c1(lrelu(x, slope)), slope)) + x through ONE fused launch (conv_sx_pair.hip.hpp; f16x3 arithmetic).
-// x, out: [B, C, T] host; w1, w2: [C, C, K]; c1 dilated by dil1, c2 dilation 1; flags bit0: also time it (ms_out).
+// The fused ResBlock step as conv_sx_pair16() launches it (include/vitsmi.h): SxPair16Args from sx_pair16_args(), the
+// generator's own filler, one launch_conv_sx_pair16().  The raw tensor starts as old_out or the sentinel, the planes as the
+// sentinel's split, both with a guard band of one 256-column tile row of sentinel cells behind the last utterance: what the
+// launch did not write reads back unchanged.
+int vits_test_conv_pair16_epi(int device_id, vits_test_conv_pair16_epi_args *p) {
+    if (int rc = test_dev(device_id)) return rc;
+    if (!p) return fail(nullptr, VITS_E_ARG, "no arguments");
+    const auto bad = [](const char *why) { return fail(nullptr, VITS_E_ARG, "pair16 epilogue hook: %s", why); };
+    const int B = p->B, C = p->C, T = p->T, K = p->K, flags = p->flags;
+    if (B < 1 || C < 1 || T < 1 || K < 1 || p->dil1 < 1 || p->dil2 < 1 || !p->x || !p->w1 || !p->w2) return bad("bad shape or missing tensor");
+    if (flags & ~(VITS_P16_EPI_ACC | VITS_P16_EPI_DIV | VITS_P16_EPI_RAW | VITS_P16_EPI_PLANES)) return bad("unknown flag");
+    if (p->precision != VITS_SX_F16X3 && p->precision != VITS_SX_F16) return bad("precision: f16x3 or f16");
+    if (C % 32) return bad("C % 32 == 0");
+    if (!(p->slope > 0.f)) return bad("slope > 0 (the residual is recovered by undoing it)");
+    if ((flags & VITS_P16_EPI_ACC) && !p->old_out) return bad("acc without old_out (the accumulate operand is the raw tensor's previous contents)");
+    if (p->lens && p->rag_mul < 1) return bad("rag_mul < 1");
+    if (p->lens)
+        for (int b = 0; b < B; b++)
+            if (p->lens[b] < 0 || p->lens[b] > T) return bad("lens outside [0, T]");
+    const bool h1 = p->precision == VITS_SX_F16, chain = p->chain != 0;
+    const int npl = h1 ? 1 : 2, mode = h1 ? 2 : 1;
+    ConvDesc d1, d2;
+    std::vector<float> arena;
+    TestPack o = sx_test_pack(h1 ? SxPack::F16X1 : SxPack::F16X2);
+    o.sx.force16 = !h1;  // (the pair16 kernel takes its 32- / 64-channel weights in the 16x16x32 layout)
+    std::string e = pack_test_conv(p->w1, p->b1, C, C, K, p->dil1, p->dil1 * (K - 1) / 2, 3, &d1, &arena, o);
+    if (e.empty()) e = pack_test_conv(p->w2, p->b2, C, C, K, p->dil2, p->dil2 * (K - 1) / 2, 3, &d2, &arena, o);
+    if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
+    if (!d1.s16 || !d2.s16 || d1.rawin || d2.rawin || !sx_pair16_plan(C, npl, d1.K, d1.dil, d2.K, d2.dil, nullptr))
+        return fail(nullptr, VITS_E_ARG, "this conv pair cannot run fused on the 16x16x32 loop (C %d, kernel %d, dilations %d, %d)", C, K, p->dil1,
+                    p->dil2);
+    const size_t n = (size_t)B * C * T, CT = (size_t)C * T;
+    const size_t G = 256 * 8;  // guard band behind each output: one tile row of cells
+    const float slope = p->slope, sen = p->sentinel;
+    // where each utterance's tensors end (sx_valid_cols)
+    std::vector<int> l32(B), ends(B);
+    for (int b = 0; b < B; b++) {
+        l32[b] = p->lens ? (int)p->lens[b] : T;
+        const long long v = l32[b] > 0 ? (long long)(l32[b] + p->rag_add) * p->rag_mul : 0;
+        ends[b] = !p->lens ? T : (int)std::min<long long>(std::max<long long>(v, 0), T);
+    }
+    // host images: the input planes' content leaky_relu(x, slope) - x_tail behind each end -, the raw tensor, the sentinel
+    std::vector<float> xa(n), ho(n, sen), hs(n, sen);
+    for (int b = 0; b < B; b++)
+        for (int c = 0; c < C; c++)
+            for (int t = 0; t < T; t++) {
+                const size_t i = ((size_t)b * C + c) * T + t;
+                const float v = (p->x_tail && t >= ends[b]) ? p->x_tail[i] : p->x[i];
+                xa[i] = v >= 0.f ? v : v * slope;
+            }
+    if (p->old_out) std::memcpy(ho.data(), p->old_out, n * 4);
+    const _Float16 sen_h = (_Float16)std::min(std::max(sen, -kF16Max), kF16Max);
+    const std::vector<float> graw(G, sen);
+    const std::vector<uint16_t> gpl(G, __builtin_bit_cast(uint16_t, sen_h));
+    DevBufs D;
+    float *dA = D.up(arena.data(), arena.size());
+    float *dx = D.up(xa.data(), n, 16);
+    uint16_t *dxp = D.fill<uint16_t>(n * 3, 0, 64);
+    float *dimg = D.up(ho.data(), n, 16);
+    float *dsen = D.up(hs.data(), n, 16);
+    float *draw = D.alloc<float>(n + G, 64);
+    uint16_t *dop = D.fill<uint16_t>(n * 3 + G, 0, 64);
+    float *dout = D.alloc<float>(n, 16);
+    int *dlen = p->lens ? D.up(l32.data(), (size_t)B) : nullptr;
+    unsigned *dpk = D.fill<unsigned>((size_t)kSxPeakSlots * kSxPeakStride);
+    TCHECK(D.err);
+    const dim3 grid((T + 255) / 256, C / 8, B);
+    sx_split_planes_kernel<<<grid, 256>>>(dx, (int64_t)CT, T, nullptr, dxp, C, T, mode);
+    sx_block_kernel<<<grid, 256>>>(dimg, (int64_t)CT, T, nullptr, draw, C, T);
+    sx_split_planes_kernel<<<grid, 256>>>(dsen, (int64_t)CT, T, nullptr, dop, C, T, mode);
+    TCHECK(hipGetLastError());
+    TCHECK(hipMemcpy(draw + n, graw.data(), G * 4, hipMemcpyHostToDevice));
+    TCHECK(hipMemcpy(dop + n * 3, gpl.data(), G * 2, hipMemcpyHostToDevice));
+    const int kflags = ((flags & VITS_P16_EPI_ACC) ? EPI_ACC : 0) | ((flags & VITS_P16_EPI_DIV) ? EPI_DIV : 0) |
+                       ((flags & VITS_P16_EPI_RAW) ? P16_HAS_RAW : 0) | ((flags & VITS_P16_EPI_PLANES) ? P16_HAS_PL : 0);
+    const SxRagged rag = dlen ? SxRagged{dlen, p->rag_add, p->rag_mul} : SxRagged{nullptr, 0, 0};
+    SxPair16Args a = sx_pair16_args(d1, d2, dA, dA, dxp, T, draw, dop, kflags, p->div == 0.f ? 1.f : p->div, slope, rag, dpk);  // (pack_test_* reserve a zero page at offset 0)
+    SxPair16Tile tile{};
+    auto go = [&] { return launch_conv_sx_pair16(a, C, npl, B, nullptr, chain, &tile); };
+    const bool name_was_on = g_launch_name_on;
+    g_launch_name_on = true;
+    g_launch_name[0] = 0;
+    const hipError_t le = go();
+    g_launch_name_on = name_was_on;
+    if (le != hipSuccess) return fail(nullptr, VITS_E_DEVICE, "pair16 epilogue hook: launch_conv_sx_pair16: %s", hipGetErrorString(le));
+    TCHECK(hipDeviceSynchronize());
+    std::snprintf(p->kernel, sizeof p->kernel, "%s", g_launch_name);
+    p->BN = tile.BN;  // (the tile as the launcher reports it)
+    p->BNo = tile.BNo;
+    p->ovl = tile.ovl ? 1 : 0;
+    if (p->out) {
+        sx_unblock_kernel<<<grid, 256>>>(draw, nullptr, dout, C, T, mode);
+        TCHECK(hipGetLastError());
+        TCHECK(hipDeviceSynchronize());
+        TCHECK(download(p->out, dout, n));
+    }
+    if (p->planes_out) {
+        sx_unblock_kernel<<<grid, 256>>>(nullptr, dop, dout, C, T, mode);
+        TCHECK(hipGetLastError());
+        TCHECK(hipDeviceSynchronize());
+        TCHECK(download(p->planes_out, dout, n));
+    }
+    if (p->x_seen) {
+        sx_unblock_kernel<<<grid, 256>>>(nullptr, dxp, dout, C, T, mode);
+        TCHECK(hipGetLastError());
+        TCHECK(hipDeviceSynchronize());
+        TCHECK(download(p->x_seen, dout, n));
+        const float un = 1.f / slope;  // (read_x16: v < 0 ? v * un_islope : v)
+        for (size_t i = 0; i < n; i++)
+            if (p->x_seen[i] < 0.f) p->x_seen[i] *= un;
+    }
+    {
+        std::vector<float> gr(G);
+        std::vector<uint16_t> hp(n * 3 + G);
+        TCHECK(download(gr.data(), draw + n, G));
+        TCHECK(download(hp.data(), dop, hp.size()));
+        bool ok = std::memcmp(gr.data(), graw.data(), G * 4) == 0 && std::memcmp(hp.data() + n * 3, gpl.data(), G * 2) == 0;
+        for (int b = 0; b < B && ok; b++)  // the planes the arithmetic does not use
+            for (size_t i = (size_t)npl * CT; i < 3 * CT && ok; i++) ok = hp[(size_t)b * 3 * CT + i] == 0;
+        p->guard_ok = ok ? 1 : 0;
+    }
+    {
+        std::vector<unsigned> slots((size_t)kSxPeakSlots * kSxPeakStride);
+        TCHECK(download(slots.data(), dpk, slots.size()));
+        unsigned top = 0;
+        for (int s = 0; s < kSxPeakSlots; s++) top = std::max(top, slots[(size_t)s * kSxPeakStride]);
+        std::memcpy(&p->peak, &top, 4);
+    }
+#if P16_PROF
+    {
+        const size_t nwg = 1 << 17;  // (>= the launch's workgroups)
+        unsigned long long *dprof = D.fill<unsigned long long>(nwg * 8);
+        TCHECK(D.err);
+        a.prof = dprof;
+        TCHECK(go());
+        TCHECK(hipDeviceSynchronize());
+        std::vector<unsigned long long> hp(nwg * 8);
+        TCHECK(download(hp.data(), dprof, nwg * 8));
+        // (a row per workgroup: phase sums over its tiles, [7] = tiles - one in the one-shot form, many in the persistent one)
+        double sum[7] = {0, 0, 0, 0, 0, 0, 0};
+        unsigned long long nt = 0, wgs = 0;
+        for (size_t w = 0; w < nwg; w++)
+            if (hp[w * 8 + 7]) {
+                wgs++;
+                nt += hp[w * 8 + 7];
+                for (int i = 0; i < 7; i++) sum[i] += (double)hp[w * 8 + i];
+            }
+        fprintf(stderr, "p16prof C %d npl %d K %d wgs %llu tiles %llu | x wait %.0f  barrier %.0f  phase1 %.0f  hand-over %.0f  phase2 %.0f  epilogue %.0f  drain %.0f (cycles per TILE)\n",
+                C, npl, K, wgs, nt, sum[0] / nt, sum[1] / nt, sum[2] / nt, sum[3] / nt, sum[4] / nt, sum[5] / nt, sum[6] / nt);
+        a.prof = nullptr;
+    }
+#endif
+    // (behind the read-back: with ACC every further launch accumulates again)
+    if (p->ms_out) TCHECK(time_launches(10, go, p->ms_out));
+    return VITS_OK;
+}
+
+// Two dependent convs through ONE fused launch (include/vitsmi.h): chain bit 0 = CHAIN (two ResBlock2 steps, else a ResBlock1
+// step), bits 1-2 = kernel: 0 conv_sx_pair_kernel (conv_sx_pair.hip.hpp: 32x32x16 form, f16x3, fp32 raw tensors), 1
+// conv_sx_pair16_kernel in f16x3, 2 the same in the single-plane arithmetic (both: operand planes of leaky_relu(x) in); bit 3
+// (pair16 only): the result is read back from the output PLANES (leaky_relu(out, slope)) instead of the fp32 output.
+// x, out: [B, C, T] host; w1, w2: [C, C, K]; c1 dilated by dil1, c2 by dil2; ms_out (nullable): the launch is also timed.
 int vits_test_conv_pair_sx(int device_id, const float *x, int B, int C, int T, const float *w1, const float *b1,
                            const float *w2, const float *b2, int K, int dil1, int dil2, int chain, float slope, float *out,
                            float *ms_out) {
     if (int rc = test_dev(device_id)) return rc;
-    // chain: bit 0 = CHAIN (two ResBlock2 steps), bits 1-2 = kernel: 0 conv_sx_pair_kernel (32x32x16 form, f16x3, fp32 raw
-    // tensors), 1 conv_sx_pair16_kernel in f16x3, 2 the same in the single-plane arithmetic (both: operand planes of
-    // leaky_relu(x) in); bit 3 (pair16 only): the result is read back from the output PLANES (leaky_relu(out, slope)) instead
-    // of the fp32 output
     const int kern = (chain >> 1) & 3;
     const bool from_plane = (chain & 8) != 0;
     chain &= 1;
-    const bool h1 = kern == 2;
+    if (kern) {  // the pair16 forms: vits_test_conv_pair16_epi's launch with `raw` or `planes`, no lens, zero-filled buffers
+        vits_test_conv_pair16_epi_args e{};
+        e.B = B, e.C = C, e.T = T, e.K = K, e.dil1 = dil1, e.dil2 = dil2, e.chain = chain;
+        e.precision = kern == 2 ? VITS_SX_F16 : VITS_SX_F16X3;
+        e.flags = from_plane ? VITS_P16_EPI_PLANES : VITS_P16_EPI_RAW;
+        e.slope = slope, e.div = 1.f, e.sentinel = 0.f;
+        e.x = x, e.w1 = w1, e.b1 = b1, e.w2 = w2, e.b2 = b2;
+        (from_plane ? e.planes_out : e.out) = out;
+        e.ms_out = ms_out;
+        return vits_test_conv_pair16_epi(device_id, &e);
+    }
     ConvDesc d1, d2;
     std::vector<float> arena;
-    TestPack o = sx_test_pack(h1 ? SxPack::F16X1 : SxPack::F16X2);
-    o.sx.force16 = kern && !h1;  // (the pair16 kernel takes its 32- / 64-channel weights in the 16x16x32 layout)
+    const TestPack o = sx_test_pack(SxPack::F16X2);
     std::string e = pack_test_conv(w1, b1, C, C, K, dil1, dil1 * (K - 1) / 2, 3, &d1, &arena, o);
     if (e.empty()) e = pack_test_conv(w2, b2, C, C, K, dil2, dil2 * (K - 1) / 2, 3, &d2, &arena, o);
     if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
     const size_t n = (size_t)B * C * T;
     DevBufs D;
-    if (kern) {
-        if (!d1.s16 || !d2.s16 || d1.rawin || !sx_pair16_plan(C, h1 ? 1 : 2, d1.K, d1.dil, d2.K, d2.dil, nullptr))
-            return fail(nullptr, VITS_E_ARG, "this conv pair cannot run fused on the 16x16x32 loop (C %d, kernel %d, dilation %d)", C, K, dil1);
-        std::vector<float> xa(n);  // the input planes hold leaky_relu(x, slope)
-        for (size_t i = 0; i < n; i++) xa[i] = x[i] >= 0.f ? x[i] : x[i] * slope;
-        float *dA = D.up(arena.data(), arena.size());
-        float *dx = D.up(xa.data(), n, 16);
-        uint16_t *dxp = D.alloc<uint16_t>(n * 3, 16);
-        uint16_t *dop = D.fill<uint16_t>(n * 3, 0, 16);
-        float *draw = D.fill<float>(n, 0, 16);
-        float *dout = D.alloc<float>(n, 16);
-        TCHECK(D.err);
-        sx_split_planes_kernel<<<dim3((T + 255) / 256, C / 8, B), 256>>>(dx, (int64_t)C * T, T, nullptr, dxp, C, T, h1 ? 2 : 1);
-        SxPair16Args a{};
-        a.xpl = dxp;
-        a.x_bstride = (int64_t)3 * C * T;
-        a.islope = a.mslope = a.oslope = slope;
-        a.T = T;
-        a.wp1 = reinterpret_cast<const u32x4 *>(dA + d1.w_off);
-        a.wp2 = reinterpret_cast<const u32x4 *>(dA + d2.w_off);
-        a.bias1 = d1.b_off >= 0 ? dA + d1.b_off : nullptr;
-        a.bias2 = d2.b_off >= 0 ? dA + d2.b_off : nullptr;
-        a.wscale1 = d1.wscale;
-        a.wscale2 = d2.wscale;
-        a.out_raw = draw;
-        a.raw_bstride = (int64_t)C * T;
-        a.out_pl = dop;
-        a.pl_bstride = (int64_t)3 * C * T;
-        a.zeros = dA;
-        a.K1 = d1.K; a.dil1 = d1.dil; a.pad1 = d1.padL;
-        a.K2 = d2.K; a.dil2 = d2.dil; a.pad2 = d2.padL;
-        a.flags = from_plane ? P16_HAS_PL : P16_HAS_RAW;
-        a.div = 1.f;
-        auto go = [&] { return launch_conv_sx_pair16(a, C, h1 ? 1 : 2, B, nullptr, chain != 0); };
-        TCHECK(go());
-        TCHECK(hipDeviceSynchronize());
-#if P16_PROF
-        {
-            const size_t nwg = 1 << 17;  // (>= the launch's workgroups)
-            unsigned long long *dprof = D.fill<unsigned long long>(nwg * 8);
-            TCHECK(D.err);
-            a.prof = dprof;
-            TCHECK(go());
-            TCHECK(hipDeviceSynchronize());
-            std::vector<unsigned long long> hp(nwg * 8);
-            TCHECK(download(hp.data(), dprof, nwg * 8));
-            // (a row per workgroup: phase sums over its tiles, [7] = tiles - one in the one-shot form, many in the persistent one)
-            double sum[7] = {0, 0, 0, 0, 0, 0, 0};
-            unsigned long long n = 0, wgs = 0;
-            for (size_t w = 0; w < nwg; w++)
-                if (hp[w * 8 + 7]) {
-                    wgs++;
-                    n += hp[w * 8 + 7];
-                    for (int i = 0; i < 7; i++) sum[i] += (double)hp[w * 8 + i];
-                }
-            fprintf(stderr, "p16prof C %d npl %d K %d wgs %llu tiles %llu | x wait %.0f  barrier %.0f  phase1 %.0f  hand-over %.0f  phase2 %.0f  epilogue %.0f  drain %.0f (cycles per TILE)\n",
-                    C, h1 ? 1 : 2, K, wgs, n, sum[0] / n, sum[1] / n, sum[2] / n, sum[3] / n, sum[4] / n, sum[5] / n, sum[6] / n);
-            a.prof = nullptr;
-        }
-#endif
-        if (ms_out) TCHECK(time_launches(10, go, ms_out));
-        sx_unblock_kernel<<<dim3((T + 255) / 256, C / 8, B), 256>>>(draw, from_plane ? dop : nullptr, dout, C, T, h1 ? 2 : 1);
-        TCHECK(hipGetLastError());
-        TCHECK(hipDeviceSynchronize());
-        TCHECK(download(out, dout, n));
-        return VITS_OK;
-    }
     if (!d1.rawin || !d2.rawin || d1.cfg != d2.cfg || !sx_pair_supported(C, d1.cfg, d1.K, d1.dil, d2.K, d2.dil))
         return fail(nullptr, VITS_E_ARG, "this conv pair cannot run fused (C %d, kernel %d, dilation %d)", C, K, dil1);
     float *dA = D.up(arena.data(), arena.size());

@@ -2646,6 +2646,45 @@ def test_conv_pair_sx(x, w1, b1, w2, b2, dil1=1, dil2=1, chain=False, slope=0.1,
     return (out, float(ms.value)) if timed else out
 
 
+# the fused ResBlock step's launch flags by name (include/vitsmi.h VITS_P16_EPI_*)
+P16_EPI_FLAGS = {"acc": 1, "div": 2, "raw": 4, "planes": 8}
+
+
+def test_conv_pair16_epi(x, w1, b1, w2, b2, flags=("raw",), dil1=1, dil2=1, chain=False, slope=0.1, precision="f16x3", div=1.0,
+                         old_out=None, lens=None, rag_add=0, rag_mul=1, x_tail=None, sentinel=CONV_EPI_SENTINEL, device_id=0):
+    """conv_sx_pair16_kernel with the argument set the generator's conv_sx_pair16() gives it (include/vitsmi.h
+    vits_test_conv_pair16_epi): one launch.  flags: names of P16_EPI_FLAGS.  The raw tensor starts as old_out, else as
+    `sentinel`; the planes start as the sentinel's split.  x_tail [B, C, T]: what the input planes hold behind each utterance's
+    end instead of x.  Returns a dict: out (the raw tensor after the launch), planes (read back from the output planes; None
+    without the planes flag), x_seen (x as the kernel recovers it from its input planes), kernel, BN, BNo, ovl, peak, guard_ok."""
+    lib = _ffi.load()
+    f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+    x, w1, b1, w2, b2, old_out, x_tail = (f32(a) for a in (x, w1, b1, w2, b2, old_out, x_tail))
+    B, Cc, T = x.shape
+    K = w1.shape[2]
+    ln = None if lens is None else np.ascontiguousarray(lens, np.int64)
+    # (the hook reads these by the shapes it derives: whatever disagrees is refused here)
+    for name, arr, shape in (("w1", w1, (Cc, Cc, K)), ("w2", w2, (Cc, Cc, K)), ("b1", b1, (Cc,)), ("b2", b2, (Cc,)),
+                             ("old_out", old_out, (B, Cc, T)), ("x_tail", x_tail, (B, Cc, T)), ("lens", ln, (B,))):
+        if arr is not None and arr.shape != shape:
+            raise ValueError(f"{name} has shape {arr.shape}, the launch needs {shape}")
+    out = np.empty((B, Cc, T), np.float32)
+    pl = np.empty((B, Cc, T), np.float32) if "planes" in flags else None
+    seen = np.empty((B, Cc, T), np.float32)
+    a = _ffi.VitsTestConvPair16EpiArgs()
+    a.B, a.C, a.T, a.K, a.dil1, a.dil2, a.chain = B, Cc, T, K, dil1, dil2, int(bool(chain))
+    a.precision, a.flags = SX_PRECISIONS[precision], sum(P16_EPI_FLAGS[f] for f in flags)
+    a.slope, a.div, a.sentinel = slope, div, sentinel
+    a.x, a.w1, a.b1, a.w2, a.b2, a.old_out, a.x_tail, a.lens = (_ffi.ptr(v) for v in (x, w1, b1, w2, b2, old_out, x_tail, ln))
+    a.rag_add, a.rag_mul = rag_add, rag_mul
+    a.out, a.planes_out, a.x_seen = _ffi.ptr(out), _ffi.ptr(pl), _ffi.ptr(seen)
+    rc = lib.vits_test_conv_pair16_epi(device_id, C.byref(a))
+    if rc != 0:
+        raise SessionError(_ffi.last_error(None))
+    return {"out": out, "planes": pl, "x_seen": seen, "kernel": a.kernel.decode(), "BN": a.BN, "BNo": a.BNo, "ovl": bool(a.ovl),
+            "peak": float(a.peak), "guard_ok": bool(a.guard_ok)}
+
+
 def bench_conv1d_sx(B, Cin, Cout, T, K, dil=1, dbg=0, iters=20, device_id=0):
     """Average launch time (ms) of one conv shape on the split-exact engine -> (ms, tile config)."""
     lib = _ffi.load()

@@ -438,25 +438,11 @@ def test_conv_pair16_single_plane_mode(B, C, T, K, d1, d2, chain):
     w2 = (rng.standard_normal((C, C, K)) / np.sqrt(C * K) * 2).astype(np.float32)
     b1 = rng.standard_normal(C).astype(np.float32)
     b2 = rng.standard_normal(C).astype(np.float32)
-    sl = np.float32(0.1)
-    lr = lambda v: np.where(v > 0, v, v * float(sl))
-    h = lambda v: np.asarray(v, np.float32).astype(np.float16).astype(np.float64)
-
-    def conv64(xq, wq, bb, d):
-        p = d * (K - 1) // 2
-        xp = np.pad(xq, ((0, 0), (0, 0), (p, p)))
-        return sum(np.einsum("oc,bct->bot", wq[:, :, k], xp[:, :, k * d:k * d + T]) for k in range(K)) + bb[None, :, None].astype(np.float64)
-
-    xa = h(lr(x).astype(np.float32))                                  # the stored input plane
-    _, w1q = _f16_operands(x, w1)
-    _, w2q = _f16_operands(x, w2)
-    xres = np.where(xa >= 0, xa, xa * float(np.float32(1.0) / sl))      # the residual the kernel recovers
-    c1 = conv64(xa, w1q, b1, d1)
-    if chain:
-        x1 = c1 + xres
-        want = conv64(h(lr(x1)), w2q, b2, d2) + x1
-    else:
-        want = conv64(h(lr(c1)), w2q, b2, d2) + xres
+    from pair_epi_ref import pair_epi_ref
+    lr = lambda v: np.where(v > 0, v, v * float(np.float32(0.1)))
+    # the float64 evaluation of the mode's roundings: fp16 input plane, scaled fp16 weights, fp16 intermediate, the residual
+    # recovered from the stored plane (tests/pair_epi_ref.py, quantized)
+    want = pair_epi_ref(x, w1, b1, w2, b2, dil1=d1, dil2=d2, chain=chain, slope=0.1, quantized=True)["value"]
     got = test_conv_pair_sx(x, w1, b1, w2, b2, dil1=d1, dil2=d2, chain=chain, slope=0.1, kernel="pair16_f16")
     np.testing.assert_allclose(got, want, atol=3e-3, rtol=0)
     assert float(np.sqrt(((got - want) ** 2).mean())) < 1e-4             # ... and nearly everywhere to fp32-accumulation error
