@@ -1316,6 +1316,27 @@ int vits_test_attention(int device_id, const float *qkv, int B, int C, int T, in
 int vits_test_attention16(int device_id, const float *qkv, int B, int C, int T, int n_heads, const float *rel_k,
                           const float *rel_v, int window, const int64_t *lens, float *out, uint16_t *out_planes, int kernel,
                           int reps, float *ms_out);
+/* ... either kernel in the form and the instantiation the caller names.  VITS_E_ARG for a (head width, ns, qt, kh) that has no
+ * compiled instantiation, for a head wider than 128 channels and for a window above 4: nothing falls back to a neighbour. */
+typedef struct {
+    int kernel;              /* 16: attention16 (head width 32 / 64 / 96); 32: the fp32-MFMA kernel (head width <= 128) */
+    const float *qkv;        /* [B][3 C][T] host; may be NULL for kernel 16 when qkv_planes is given */
+    const uint16_t *qkv_planes; /* kernel 16 only, nullable: [B][3][3 C / 8][T][8] operand planes used as they are (otherwise
+                              * qkv is split on the device, as the q|k|v conv's epilogue does) */
+    int B, C, T, n_heads, window;
+    const float *rel_k, *rel_v;  /* [2 window + 1][C / n_heads] */
+    const int64_t *lens;     /* [B] >= 0; a length above T counts as T */
+    int want_out;            /* the launch writes the fp32 output (kernel 32 always does: 0 is refused there) */
+    int want_planes;         /* the launch writes the output's operand planes and the range-guard peak (C % 8 == 0; kernel 32:
+                              * head width % 8 == 0) */
+    int ns, qt;              /* kernel 16: LDS stages / query tiles per wave; 0 = the launcher's own choice */
+    int kh;                  /* kernel 32: key halves (1 / 2); 0 = the launcher's own choice */
+    float *out;              /* [B][C][T], nullable: the device buffer as the launch left it; it starts as 0xff bytes */
+    uint16_t *out_planes;    /* [B][3][C / 8][T][8], nullable: likewise (the third slot is never written) */
+    float peak;              /* out: the largest of the launch's 64 range-guard slots, cleared in front of the launch */
+    char kernel_name[128];   /* out: the instantiation launched (as in vits_launch_record) */
+} vits_test_attention_form_args;
+int vits_test_attention_form(int device_id, vits_test_attention_form_args *a);
 
 /* The resampler by value: x [B][S] host, lens [B] the rows' valid samples (what lies behind must not show), y [B][S_out]
  * with S_out >= max_b ceil(lens[b] * L / M); every column of y is written. */

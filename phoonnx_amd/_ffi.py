@@ -70,6 +70,15 @@ class VitsTestConvPair16EpiArgs(C.Structure):
                [(n, C.c_int) for n in ("BN", "BNo", "ovl")] + [("peak", C.c_float), ("guard_ok", C.c_int)]
 
 
+class VitsTestAttentionFormArgs(C.Structure):
+    """vits_test_attention_form_args of include/vitsmi.h"""
+    _fields_ = [("kernel", C.c_int), ("qkv", C.c_void_p), ("qkv_planes", C.c_void_p)] + \
+               [(n, C.c_int) for n in ("B", "C", "T", "n_heads", "window")] + \
+               [(n, C.c_void_p) for n in ("rel_k", "rel_v", "lens")] + \
+               [(n, C.c_int) for n in ("want_out", "want_planes", "ns", "qt", "kh")] + \
+               [("out", C.c_void_p), ("out_planes", C.c_void_p), ("peak", C.c_float), ("kernel_name", C.c_char * 128)]
+
+
 class VitsOpenOptions(C.Structure):
     _fields_ = [("device_id", C.c_int), ("gen_precision", C.c_char_p), ("arena_dev", C.c_void_p),
                 ("arena_bytes", C.c_size_t), ("host_only", C.c_int), ("layout_only", C.c_int)]
@@ -199,7 +208,7 @@ EXPORTS = [
     "vits_test_stream_pack_trimmed",
     "vits_test_layernorm", "vits_test_dds", "vits_test_cf_pre", "vits_test_rqs_inverse", "vits_test_ea_logw",
     "vits_test_conv1d_epi", "vits_test_wn_gate", "vits_test_cond_matvec", "vits_test_conv1d_sx_epi",
-    "vits_test_conv_pair16_epi",
+    "vits_test_conv_pair16_epi", "vits_test_attention_form",
 ]
 
 
@@ -389,6 +398,7 @@ def load():
     lib.vits_test_conv1d_epi.argtypes = [C.c_int, C.POINTER(VitsTestConvEpiArgs)]
     lib.vits_test_conv1d_sx_epi.argtypes = [C.c_int, C.POINTER(VitsTestConvSxEpiArgs)]
     lib.vits_test_conv_pair16_epi.argtypes = [C.c_int, C.POINTER(VitsTestConvPair16EpiArgs)]
+    lib.vits_test_attention_form.argtypes = [C.c_int, C.POINTER(VitsTestAttentionFormArgs)]
     lib.vits_test_wn_gate.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     lib.vits_test_cond_matvec.argtypes = [C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp]
     lib.vits_test_conv_pair_sx.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int,

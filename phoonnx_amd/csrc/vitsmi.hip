@@ -651,18 +651,26 @@ void conv_sx(Ctx &c, const ConvDesc &d, const void *x, int T, float *out_raw, ui
     h->stats.sx_launches++;
 }
 
+constexpr int kAttMaxHeadWidth = 128;  // attention_relpos_kernel<4, KH>: ceil(dk / 32) <= 4
 // a3: relative-position attention core, one launch (kernels.hip.hpp).  Two key halves per workgroup unless
-// VITSMI_ATT_NOSPLIT is set (A/B timing only).
+// VITSMI_ATT_NOSPLIT is set (A/B timing only); kh = 1 / 2 (the kernel-level test hook) names the key halves itself.
+template <int DKB, int KH>
+void launch_attention_t(hipStream_t st, dim3 grid, const float *qkv, float *att, const float *rel_k, const float *rel_v,
+                        const int *len, int H, int T, int dk, int window, uint16_t *planes, unsigned *peak) {
+    if (g_launch_name_on) snprintf(g_launch_name, sizeof g_launch_name, "attention_relpos_kernel<%d, %d>", DKB, KH);
+    attention_relpos_kernel<DKB, KH><<<grid, 256 * KH, 0, st>>>(qkv, att, rel_k, rel_v, len, H, T, dk, window, planes, peak);
+}
 void launch_attention(hipStream_t st, int B, int T, int n_heads, int dk, int window, const float *qkv, float *att,
                       const float *rel_k, const float *rel_v, const int *len, int H, uint16_t *planes = nullptr,
-                      unsigned *peak = nullptr) {
+                      unsigned *peak = nullptr, int kh = 0) {
     static const bool nosplit = std::getenv("VITSMI_ATT_NOSPLIT") != nullptr;
+    const bool one_half = kh ? kh == 1 : nosplit;
     dim3 ag((T + 127) / 128, n_heads, B);
     const int dkb = (dk + 31) / 32;
-#define VITSMI_ATT(DKB)                                                                                                       \
-    do {                                                                                                                      \
-        if (nosplit) attention_relpos_kernel<DKB, 1><<<ag, 256, 0, st>>>(qkv, att, rel_k, rel_v, len, H, T, dk, window, planes, peak); \
-        else attention_relpos_kernel<DKB, 2><<<ag, 512, 0, st>>>(qkv, att, rel_k, rel_v, len, H, T, dk, window, planes, peak);         \
+#define VITSMI_ATT(DKB)                                                                                             \
+    do {                                                                                                            \
+        if (one_half) launch_attention_t<DKB, 1>(st, ag, qkv, att, rel_k, rel_v, len, H, T, dk, window, planes, peak); \
+        else launch_attention_t<DKB, 2>(st, ag, qkv, att, rel_k, rel_v, len, H, T, dk, window, planes, peak);          \
     } while (0)
     switch (dkb) {
         case 1: VITSMI_ATT(1); break;
@@ -681,13 +689,15 @@ hipError_t launch_attention16_t(hipStream_t st, const Att16Args &a) {
     if (lds > 64 * 1024)
         if (hipError_t e = sx_allow_big_lds(reinterpret_cast<const void *>(&attention_relpos16_kernel<DKS, NS, QT>), done)) return e;
     const int ntile = (a.T + 64 * QT - 1) / (64 * QT), npair = a.nh * a.B;
+    if (g_launch_name_on) snprintf(g_launch_name, sizeof g_launch_name, "attention_relpos16_kernel<%d, %d, %d>", DKS, NS, QT);
     attention_relpos16_kernel<DKS, NS, QT><<<dim3(((npair + 7) / 8) * 8 * ntile), 256, lds, st>>>(a);
     return hipSuccess;
 }
-// stages / query tiles per wave: two stages, 64 queries per workgroup; VITSMI_ATT16_NS / VITSMI_ATT16_QT override (A/B timing)
+// stages / query tiles per wave: two stages, 64 queries per workgroup; VITSMI_ATT16_NS / VITSMI_ATT16_QT override (A/B timing),
+// and ns_arg / qt_arg (the kernel-level test hook; 0 = not given) override those
 hipError_t launch_attention16(hipStream_t st, int B, int T, int n_heads, int dk, int window, const uint16_t *qkv_pl, float *att,
                               uint16_t *att_pl, const float *rel_k, const float *rel_v, const int *len, int H, unsigned *peak,
-                              unsigned long long *prof = nullptr) {
+                              unsigned long long *prof = nullptr, int ns_arg = 0, int qt_arg = 0) {
     static const int env_ns = [] { const char *e = std::getenv("VITSMI_ATT16_NS"); return e ? std::atoi(e) : 0; }();
     static const int env_qt = [] { const char *e = std::getenv("VITSMI_ATT16_QT"); return e ? std::atoi(e) : 0; }();
     Att16Args a{};
@@ -705,7 +715,7 @@ hipError_t launch_attention16(hipStream_t st, int B, int T, int n_heads, int dk,
     a.B = B;
     a.peak = att_pl ? peak : nullptr;
     a.prof = prof;
-    int ns = env_ns ? env_ns : 2, qt = env_qt ? env_qt : 1;  // (measured: 2, 3 and 4 stages time alike)
+    const int ns = ns_arg ? ns_arg : (env_ns ? env_ns : 2), qt = qt_arg ? qt_arg : (env_qt ? env_qt : 1);  // (measured: 2, 3 and 4 stages time alike)
     if (dk == 32) return launch_attention16_t<1, 3, 1>(st, a);
     if (dk == 64) return launch_attention16_t<2, 3, 1>(st, a);
     if (qt == 2) return ns >= 3 ? launch_attention16_t<3, 3, 2>(st, a) : launch_attention16_t<3, 2, 2>(st, a);
@@ -2547,8 +2557,16 @@ static int open_common(const char *path, vits_handle **out, bool host_only, int 
         return fail(nullptr, VITS_E_FORMAT, "%s: %s", path, e.c_str());
     }
     if (h->model.window > 4) {
+        const int window = h->model.window;  // (read before the handle goes: the message once named a freed handle's field)
         delete h;
-        return fail(nullptr, VITS_E_FORMAT, "attention window %d > 4 is unsupported", h->model.window);
+        return fail(nullptr, VITS_E_FORMAT, "attention window %d > 4 is unsupported", window);
+    }
+    // (the widest attention instantiation, DKB = 4, covers 128 channels per head: a wider head would lose channels 128.. from
+    // its scores and leave their output rows unwritten)
+    if (h->model.dk > kAttMaxHeadWidth) {
+        const int dk = h->model.dk;
+        delete h;
+        return fail(nullptr, VITS_E_FORMAT, "attention head width %d > %d is unsupported", dk, kAttMaxHeadWidth);
     }
     h->host_only = host_only;
     {
@@ -5028,6 +5046,7 @@ int vits_test_attention(int device_id, const float *qkv, int B, int C, int T, in
     if (int rc = test_dev(device_id)) return rc;
     if (window > 4 || C % n_heads) return fail(nullptr, VITS_E_ARG, "bad attention test arguments");
     int dk = C / n_heads;
+    if (dk > kAttMaxHeadWidth) return fail(nullptr, VITS_E_ARG, "attention head width %d > %d is unsupported", dk, kAttMaxHeadWidth);
     size_t nq = (size_t)B * 3 * C * T, no = (size_t)B * C * T, nr = (size_t)(2 * window + 1) * dk;
     std::vector<int> l32(B);
     for (int b = 0; b < B; b++) l32[b] = (int)lens[b];
@@ -5055,6 +5074,7 @@ int vits_test_attention16(int device_id, const float *qkv, int B, int C, int T, 
     if (window > 4 || C % n_heads || C % 8) return fail(nullptr, VITS_E_ARG, "bad attention test arguments");
     int dk = C / n_heads;
     if (kernel == 1 && !(dk % 32 == 0 && dk <= 96)) return fail(nullptr, VITS_E_ARG, "attention16 needs a head width of 32, 64 or 96");
+    if (dk > kAttMaxHeadWidth) return fail(nullptr, VITS_E_ARG, "attention head width %d > %d is unsupported", dk, kAttMaxHeadWidth);
     size_t nq = (size_t)B * 3 * C * T, no = (size_t)B * C * T, nr = (size_t)(2 * window + 1) * dk;
     std::vector<int> l32(B);
     for (int b = 0; b < B; b++) l32[b] = (int)lens[b];
@@ -5101,6 +5121,90 @@ int vits_test_attention16(int device_id, const float *qkv, int B, int C, int T, 
     }
     TCHECK(download(out, dout, no));
     if (out_planes) TCHECK(download(out_planes, dop, no * 3));
+    return VITS_OK;
+}
+
+// ... either kernel in the form and instantiation the caller names: which outputs the launch writes (the pipeline's
+// attention16 launch writes planes only), stages / query tiles / key halves, q | k | v planes split here or given.  Both output
+// buffers start as 0xff bytes and come back whole, so what a launch did not write shows.  A (dk, ns, qt, kh) without a
+// compiled instantiation is refused: nothing is rounded to a neighbour.
+int vits_test_attention_form(int device_id, vits_test_attention_form_args *p) {
+    if (int rc = test_dev(device_id)) return rc;
+    if (!p) return fail(nullptr, VITS_E_ARG, "no attention test arguments");
+    const int B = p->B, C = p->C, T = p->T, n_heads = p->n_heads, window = p->window;
+    if (B <= 0 || C <= 0 || T <= 0 || n_heads <= 0 || window < 0 || !p->rel_k || !p->rel_v || !p->lens)
+        return fail(nullptr, VITS_E_ARG, "bad attention test arguments");
+    if (window > 4) return fail(nullptr, VITS_E_ARG, "attention window %d > 4 is unsupported", window);
+    if (C % n_heads) return fail(nullptr, VITS_E_ARG, "%d channels do not divide into %d heads", C, n_heads);
+    const int dk = C / n_heads;
+    if (dk > kAttMaxHeadWidth) return fail(nullptr, VITS_E_ARG, "attention head width %d > %d is unsupported", dk, kAttMaxHeadWidth);
+    const bool k16 = p->kernel == 16;
+    if (!k16 && p->kernel != 32) return fail(nullptr, VITS_E_ARG, "kernel must be 16 (attention16) or 32 (the fp32-MFMA kernel), not %d", p->kernel);
+    if (!p->want_out && !p->want_planes) return fail(nullptr, VITS_E_ARG, "a launch that writes neither output");
+    if ((p->want_out && !p->out) || (p->want_planes && !p->out_planes)) return fail(nullptr, VITS_E_ARG, "a wanted output has no buffer");
+    if (p->want_planes && C % 8) return fail(nullptr, VITS_E_ARG, "output planes need a multiple of 8 channels, not %d", C);
+    if (k16) {
+        if (!(dk == 32 || dk == 64 || dk == 96)) return fail(nullptr, VITS_E_ARG, "attention16 needs a head width of 32, 64 or 96, not %d", dk);
+        if (p->kh) return fail(nullptr, VITS_E_ARG, "attention16 has no key halves (kh = %d)", p->kh);
+        const int ns = p->ns, qt = p->qt;
+        // the compiled instantiations: <1, 3, 1>, <2, 3, 1>, <3, {2, 3, 4}, 1>, <3, {2, 3}, 2>
+        const bool have = dk < 96 ? (ns == 0 || ns == 3) && (qt == 0 || qt == 1)
+                                  : qt == 2 ? (ns == 0 || ns == 2 || ns == 3) : (qt == 0 || qt == 1) && (ns == 0 || (ns >= 2 && ns <= 4));
+        if (!have) return fail(nullptr, VITS_E_ARG, "no attention16 instantiation <%d, %d, %d>", dk / 32, ns, qt);
+        if (!p->qkv && !p->qkv_planes) return fail(nullptr, VITS_E_ARG, "neither q|k|v nor its planes given");
+    } else {
+        if (p->ns || p->qt) return fail(nullptr, VITS_E_ARG, "the fp32 kernel has no stages or query tiles (ns = %d, qt = %d)", p->ns, p->qt);
+        if (p->kh < 0 || p->kh > 2) return fail(nullptr, VITS_E_ARG, "no fp32 attention instantiation with %d key halves", p->kh);
+        if (!p->want_out) return fail(nullptr, VITS_E_ARG, "the fp32 kernel always writes its fp32 output");
+        if (p->want_planes && dk % 8) return fail(nullptr, VITS_E_ARG, "the fp32 kernel's planes need a head width that is a multiple of 8, not %d", dk);
+        if (!p->qkv || p->qkv_planes) return fail(nullptr, VITS_E_ARG, "the fp32 kernel reads q|k|v as fp32");
+    }
+    const size_t nq = (size_t)B * 3 * C * T, no = (size_t)B * C * T, nr = (size_t)(2 * window + 1) * dk;
+    std::vector<int> l32(B);
+    for (int b = 0; b < B; b++) {
+        if (p->lens[b] < 0) return fail(nullptr, VITS_E_ARG, "lens[%d] = %lld", b, (long long)p->lens[b]);
+        l32[b] = (int)std::min<int64_t>(p->lens[b], INT_MAX);
+    }
+    DevBufs D;
+    float *dq = p->qkv && !p->qkv_planes ? D.up(p->qkv, nq) : nullptr;
+    uint16_t *dqp = nullptr;
+    if (k16) dqp = p->qkv_planes ? D.up(p->qkv_planes, nq * 3) : D.alloc<uint16_t>(nq * 3);
+    uint16_t *dop = C % 8 == 0 ? D.fill<uint16_t>(no * 3, 0xff) : nullptr;
+    unsigned *dpk = D.fill<unsigned>((size_t)kSxPeakSlots * kSxPeakStride);
+    float *dout = D.fill<float>(no, 0xff);
+    float *drk = D.up(p->rel_k, nr);
+    float *drv = D.up(p->rel_v, nr);
+    int *dlen = D.up(l32.data(), (size_t)B);
+    TCHECK(D.err);
+    if (k16 && !p->qkv_planes) {
+        sx_split_planes_kernel<<<dim3((T + 255) / 256, 3 * C / 8, B), 256>>>(dq, (int64_t)3 * C * T, T, nullptr, dqp, 3 * C, T, 1, dpk);
+        TCHECK(hipGetLastError());
+        // (the split has left the peak of q | k | v in the slots: the attention launch starts from zeros)
+        TCHECK(hipMemsetAsync(dpk, 0, (size_t)kSxPeakSlots * kSxPeakStride * sizeof(unsigned), nullptr));
+    }
+    const bool name_was_on = g_launch_name_on;
+    g_launch_name_on = true;
+    g_launch_name[0] = 0;
+    hipError_t le = hipSuccess;
+    if (k16)
+        le = launch_attention16(nullptr, B, T, n_heads, dk, window, dqp, p->want_out ? dout : nullptr, p->want_planes ? dop : nullptr,
+                                drk, drv, dlen, C, dpk, nullptr, p->ns, p->qt);
+    else
+        launch_attention(nullptr, B, T, n_heads, dk, window, dq, dout, drk, drv, dlen, C, p->want_planes ? dop : nullptr, dpk, p->kh);
+    g_launch_name_on = name_was_on;
+    TCHECK(le);
+    std::snprintf(p->kernel_name, sizeof p->kernel_name, "%s", g_launch_name);
+    TCHECK(hipGetLastError());
+    TCHECK(hipDeviceSynchronize());
+    if (p->out) TCHECK(download(p->out, dout, no));
+    if (p->out_planes && dop) TCHECK(download(p->out_planes, dop, no * 3));
+    {
+        std::vector<unsigned> slots((size_t)kSxPeakSlots * kSxPeakStride);
+        TCHECK(download(slots.data(), dpk, slots.size()));
+        unsigned top = 0;
+        for (int s = 0; s < kSxPeakSlots; s++) top = std::max(top, slots[(size_t)s * kSxPeakStride]);
+        std::memcpy(&p->peak, &top, 4);
+    }
     return VITS_OK;
 }
 

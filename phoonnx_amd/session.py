@@ -2741,6 +2741,46 @@ def test_attention16(qkv, n_heads, rel_k, rel_v, lens, device_id=0, kernel=1, pl
     return res[0] if len(res) == 1 else res
 
 
+def test_attention_form(qkv, n_heads, rel_k, rel_v, lens, kernel=16, want_out=True, want_planes=True, ns=0, qt=0, kh=0,
+                        qkv_planes=None, device_id=0):
+    """One attention launch in the form and instantiation named (include/vitsmi.h vits_test_attention_form): kernel 16
+    (attention16.hip.hpp) or 32 (the fp32-MFMA kernel); want_out / want_planes: which outputs the launch writes; ns, qt
+    (kernel 16) and kh (kernel 32): the instantiation, 0 = the launcher's choice; qkv_planes (kernel 16): the q|k|v operand
+    planes uint16 [B, 3, 3C/8, T, 8] used as they are instead of the split of qkv.  qkv is fp32 [B, 3C, T].  Returns a dict: out
+    [B, C, T] and planes uint16 [B, 3, C/8, T, 8] - the device buffers as the launch left them, 0xff bytes where it wrote nothing
+    (planes is None when C % 8) -, peak (the range guard's), kernel (the instantiation started)."""
+    lib = _ffi.load()
+    qkv = np.ascontiguousarray(qkv, np.float32)
+    B, C3, T = qkv.shape
+    Cc = C3 // 3
+    rel_k = np.ascontiguousarray(rel_k, np.float32)
+    rel_v = np.ascontiguousarray(rel_v, np.float32)
+    window = (rel_k.shape[0] - 1) // 2
+    lens = np.ascontiguousarray(lens, np.int64)
+    if C3 != 3 * Cc or n_heads <= 0 or Cc % n_heads or lens.shape != (B,):
+        raise ValueError(f"q|k|v {qkv.shape} with {n_heads} heads and lens {lens.shape}")
+    dk = Cc // n_heads
+    if rel_k.shape != (2 * window + 1, dk) or rel_v.shape != rel_k.shape:
+        raise ValueError(f"relative embeddings {rel_k.shape} / {rel_v.shape}, head width {dk}")
+    qp = None
+    if qkv_planes is not None:
+        qp = np.ascontiguousarray(qkv_planes, np.uint16)
+        if C3 % 8 or qp.shape != (B, 3, C3 // 8, T, 8):
+            raise ValueError(f"q|k|v planes {qp.shape}, the launch needs {(B, 3, C3 // 8, T, 8)}")
+    out = np.empty((B, Cc, T), np.float32)
+    opl = np.empty((B, 3, Cc // 8, T, 8), np.uint16) if Cc % 8 == 0 else None
+    a = _ffi.VitsTestAttentionFormArgs()
+    a.kernel, a.qkv, a.qkv_planes = int(kernel), _ffi.ptr(qkv), _ffi.ptr(qp)
+    a.B, a.C, a.T, a.n_heads, a.window = B, Cc, T, n_heads, window
+    a.rel_k, a.rel_v, a.lens = _ffi.ptr(rel_k), _ffi.ptr(rel_v), _ffi.ptr(lens)
+    a.want_out, a.want_planes, a.ns, a.qt, a.kh = int(bool(want_out)), int(bool(want_planes)), int(ns), int(qt), int(kh)
+    a.out, a.out_planes = _ffi.ptr(out), _ffi.ptr(opl)
+    rc = lib.vits_test_attention_form(device_id, C.byref(a))
+    if rc != 0:
+        raise SessionError(_ffi.last_error(None))
+    return {"out": out, "planes": opl, "peak": float(a.peak), "kernel": a.kernel_name.decode()}
+
+
 def test_attention(qkv, n_heads, rel_k, rel_v, lens, device_id=0):
     lib = _ffi.load()
     qkv = np.ascontiguousarray(qkv, np.float32)

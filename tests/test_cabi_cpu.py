@@ -184,6 +184,27 @@ def test_langid_input_is_listed_and_unknown_inputs_are_rejected(tmp_path):
         MiSession(q, host_only=True)
 
 
+def test_attention_shapes_without_a_kernel_are_refused_at_open(tmp_path):
+    """The attention kernels hold nine relative positions (window <= 4) and at most 128 channels per head (DKB = 4): a voice
+    beyond either is refused when it is opened, with the figure in the message - a head of 160 channels would otherwise lose
+    channels 128.. from its scores without an error.  128 channels and window 4 open."""
+    from phoonnx_amd.synth import write_voice
+    cases = [("wide", dict(hidden_channels=160, n_heads=1, n_layers=1), "attention head width 160 > 128"),
+             ("win5", dict(window=5), "attention window 5 > 4"),
+             ("edge", dict(hidden_channels=128, n_heads=1, n_layers=1, window=4), None)]
+    for name, over, refusal in cases:
+        p = str(tmp_path / f"{name}.onnx")
+        write_voice(p, "small", seed=3, **over)
+        for mode in ("host_only", "layout_only"):
+            if refusal is None:
+                s = MiSession(p, **{mode: True})
+                assert s.hparam("window") == 4
+                s.close()
+            else:
+                with pytest.raises(SessionError, match=refusal):
+                    MiSession(p, **{mode: True})
+
+
 def _tensor_spans(buf):
     """(dims byte offsets, name) of every TensorProto whose layout is dims* data_type name raw_data (what the
     exporter and synth.py write): 08 d .. 10 01 42 len name."""

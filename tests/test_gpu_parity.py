@@ -594,12 +594,7 @@ def test_short_launch_kernel_generator_epilogue_matches_the_engine(B, Cin, Cout,
     np.testing.assert_allclose(a, e, atol=3e-6 * scale, rtol=0)
 
 
-def _planes_value(pl):
-    """fp16 operand planes [B, 3, C/8, T, 8] (f16x3 format: h0, h1 * 2^11) -> the fp32 values they stand for [B, C, T]"""
-    h = pl.view(np.float16).astype(np.float64)
-    v = h[:, 0] + h[:, 1] / 2048.0
-    B, CG, T, _ = v.shape
-    return v.transpose(0, 1, 3, 2).reshape(B, CG * 8, T)
+from attention_ref import planes_value as _planes_value  # noqa: E402  (fp16 operand planes -> the values they stand for)
 
 
 ATT16_CASES = [(1, 2, 96, 256, [256]), (2, 2, 96, 70, [33, 70]), (1, 1, 64, 3, [3]), (2, 2, 32, 129, [129, 64]),
