@@ -479,8 +479,8 @@ int vits_last_sample_rates(vits_handle *h, int32_t *buf, int n);
  *     they stand; vits_last_y_lengths, vits_last_durations and vits_tap stay in frames;
  *   vits_last_token_spans answers k per token.
  * Out of scope: a warped run with an output rate or per-row output rates set is VITS_E_ARG ("not covered with an output
- * rate set") - folding the rate into step is a follow-up; the chunked and the device-pointer entries have no warped form (a
- * carry for chunks is a follow-up); the speed is constant per token: no glides between tokens here ("pitch contours" below adds them); formants are not preserved;
+ * rate set") - folding the rate into step is a follow-up; the device-pointer entries and the vocoder-only chunked ones have no warped
+ * form (the chunked entries with tokens: "streamed pitch" below); the speed is constant per token: no glides between tokens here ("pitch contours" below adds them); formants are not preserved;
  * vits_reserve does not count the warped buffer: a warped run grows the staging slab on demand, as any unreserved run does. */
 typedef struct {
     int64_t n0;          /* first output sample of the segment */
@@ -550,7 +550,7 @@ int vits_warp_plan(const int64_t *durations, const float *semitones, int len, in
  *   Refusals, all before anything is enqueued, the previous run stays readable: an output rate or per-row rates set ("not
  *     covered with an output rate set"); a value that is not finite within [-12, 12], naming token_semitones[b,t] or
  *     token_semitones_end[b,t]; compensate with forced durations; a host-only handle.
- * Out of scope: glides with an output rate or in chunked runs; curves other than linear in the output index; formant
+ * Out of scope: glides with an output rate (chunked runs: "streamed pitch" below); curves other than linear in the output index; formant
  * preservation; contour positions in time (the Python pitch_contour= places its points by phoneme count); vits_reserve does
  * not count the buffer, as for the warp. */
 typedef struct {
@@ -1079,6 +1079,58 @@ int vits_run_vocoder_chunked_enc_trimmed(vits_handle *h, const float *z, int B, 
                                          const vits_stream_format *fmt, const vits_stream_shaping *shaping,
                                          const vits_stream_onset *onsets, int chunk_frames, vits_enc_chunk_trim_fn fn, void *user);
 
+/* ---- streamed pitch: "intonation" and "pitch contours" in the chunked runs, warped and glided piece by piece -------------------
+ * A chunked run renders the native waveform rectangularly: behind a piece, input samples [0, X) of every row exist.  Row b has
+ * its plan (vits_warp_seg or vits_glide_seg records, planned as in the two sections above from the durations, which are on the
+ * host before the first chunk), n_b valid input samples and N_b output samples; S_w = max(1, max_b N_b).
+ *
+ * The emit rule (pure host code, int64 as the plans):
+ *   ready_b(X) = the number of n < N_b with (pos_n >> FB) + 38 < X, pos_n by the closed form of the row's family.  Positions
+ *     never decrease along a row, so it is a prefix count, found by bisection over n.  The bound uses the uniform 38 half-taps
+ *     (the most a sample has), not the sample's own Kh: the rule stays monotone for glides, whose Kh changes per sample, and every
+ *     float a tile stages exists when the tile runs.  The price is at most 19 samples of latency on audio that is not raised.
+ *   A row with X >= n_b is complete: its inputs behind n_b read 0, as in the whole run, and it constrains nothing.
+ *   e(X) = min over the rows with X < n_b of ready_b(X); S_w where there is no such row, and on the last piece.
+ *   The piece delivers output samples [emitted, e(X)) of ALL rows - one rectangular output timeline, as every chunk callback
+ *   describes; rows shorter than the range hold 0.0f behind N_b.  A piece that completes nothing makes no call.
+ *   total_samples is S_w.
+ * vits_warp_emit_end / vits_glide_emit_end answer the rule for one row: *ready = N_b where X >= n_in, else ready_b(X).  The
+ *   records are checked as the test hooks check them; n_out must be the N_b they give (without a record: n_in).
+ * Consequence.  At B > 1 the row that needs the most input per output sample - the most raised one - gates the others; when
+ *   it ends, one piece may release a long range.  Such a range is handed over in several calls, in order, of at most
+ *     n_cap = min(S_w, 2 * (min(chunk_frames, F) * hop + 38))
+ *   output samples each (vits_warp_stream_cap): a piece moves every row's bound by chunk_frames * hop inputs, which at the least
+ *   step ONE / 2 completes twice as many outputs, and the 38 of the rule may fall on either side.  The ring, the pack scratch and
+ *   the limiter carry so stay chunk-sized.  With a look-ahead L a call delivers at most n_cap + L.
+ * Device.  The run's native waveform [B][F * hop] is kept in the staging slab (the history: rows at different speeds need
+ *   different amounts of past input, without compensate unboundedly much; 25 MB at batch 32 x 768 frames); every piece's interior
+ *   is appended by one device-to-device copy, and the window [emitted, e) is rendered by the whole run's kernel launched over
+ *   [n_lo, n_hi): the same function renders a sample whichever tile asks for it, so the pieces joined ARE the whole run's
+ *   [B][S_w], bit for bit.  Behind it the stages of "encoded / shaped / trimmed streaming" work on the output timeline unchanged:
+ *   valid[] and the masks count by N_b, the plan callback receives N_b as sample_counts, vits_stream_emit_range takes S_w.
+ *
+ * vits_run_chunked_glided is vits_run_chunked_ctl with the contour on top and delivers fp32 pieces;
+ * vits_run_chunked_enc_glided is vits_run_chunked_enc_trimmed with it (shaping and onsets nullable: skip is all 0 without onsets).
+ *   token_semitones_end == NULL is the warp: one pair of entries covers both sections.  Equal ends launch the warp's kernel,
+ *   otherwise the glide's.  All-zero semitones make the call vits_run_chunked_ctl / vits_run_chunked_enc* exactly: the same chunk
+ *   ranges, bits and total_launches, no history, no plan.  compensate is "intonation"'s / "pitch contours"'.
+ *   Refusals, before anything is enqueued, the previous run stays readable: an output rate or per-row rates set ("not covered
+ *   with an output rate set"); a bad value, naming [b,t]; compensate with forced durations; a host-only handle.
+ *   vits_last_sample_counts (N_b) and vits_last_token_spans answer from the plan callback on, and after the run.
+ * Out of scope: pitch with an output rate, whole or streamed; the vocoder-only chunked entries (no tokens: no warped form);
+ * vits_reserve does not count the history; formant preservation. */
+int vits_warp_emit_end(const vits_warp_seg *segs, int n_segs, int64_t n_in, int64_t n_out, int64_t X, int64_t *ready);
+int vits_glide_emit_end(const vits_glide_seg *segs, int n_segs, int64_t n_in, int64_t n_out, int64_t X, int64_t *ready);
+/* n_cap for pieces of piece_samples input samples (chunk_frames * hop) and rows of S_w output samples; VITS_E_ARG below 1 */
+int64_t vits_warp_stream_cap(int64_t piece_samples, int64_t S_w);
+int vits_run_chunked_glided(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
+                            const vits_noise *noise, const vits_controls *ctl, const vits_contour *contour, int chunk_frames,
+                            vits_chunk_fn fn, void *user);
+int vits_run_chunked_enc_glided(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
+                                const vits_noise *noise, const vits_controls *ctl, const vits_stream_format *fmt,
+                                const vits_stream_shaping *shaping, const vits_stream_onset *onsets, const vits_contour *contour,
+                                int chunk_frames, vits_enc_chunk_trim_fn fn, void *user);
+
 /* Size the handle's device workspaces NOW for requests of up to B utterances x T tokens that render up to F frames each
  * (the batch's longest utterance; T = 0 or F = 0 leaves that domain alone).  A run grows a workspace when a request
  * needs more than any before it - hipFree + hipMalloc of tens of GB at batch 32, a device-wide synchronisation that was
@@ -1358,6 +1410,16 @@ int vits_test_warp(int device_id, const float *x, const int64_t *counts, int B, 
 /* ... and the glide ("pitch contours"): the same arguments over vits_glide_seg records, the pipeline's glide launch. */
 int vits_test_glide(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_glide_seg *segs,
                     const int32_t *seg_first /* [B+1] */, float *y, int S_w);
+/* ... and both cut into pieces ("streamed pitch"): the input arrives in n_pieces pieces that end at piece_bounds[i] (ascending,
+ * the last one S) and goes through the pipeline's stage - history, emit rule, windowed launches - on the pipeline's walk of a
+ * poisoned buffer, with n_cap = vits_warp_stream_cap(longest piece, S_w).  S_w is exactly max(1, max_b N_b).  y [B][S_w]
+ * receives the windows joined; ranges (nullable) [max_ranges][2] {first, n} of every window, in order.  Returns their number. */
+int vits_test_warp_pieces(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_warp_seg *segs,
+                          const int32_t *seg_first /* [B+1] */, const int64_t *piece_bounds, int n_pieces, float *y, int S_w,
+                          int64_t *ranges, int max_ranges);
+int vits_test_glide_pieces(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_glide_seg *segs,
+                           const int32_t *seg_first /* [B+1] */, const int64_t *piece_bounds, int n_pieces, float *y, int S_w,
+                           int64_t *ranges, int max_ranges);
 
 /* The kernels that turn tokens into frames and frames into samples, by value.  Every hook checks its sizes and extents on the
  * host (VITS_E_ARG) and launches the pipeline's kernel with the pipeline's grid.

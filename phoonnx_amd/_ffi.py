@@ -194,6 +194,8 @@ EXPORTS = [
     "vits_set_output_rates", "vits_last_sample_rates", "vits_test_resample_rows",
     "vits_run_async_warped", "vits_last_token_spans", "vits_warp_token", "vits_warp_plan", "vits_test_warp",
     "vits_run_async_glided", "vits_glide_token", "vits_glide_cutoff", "vits_glide_plan", "vits_test_glide",
+    "vits_warp_emit_end", "vits_glide_emit_end", "vits_warp_stream_cap", "vits_run_chunked_glided", "vits_run_chunked_enc_glided",
+    "vits_test_warp_pieces", "vits_test_glide_pieces",
     "vits_test_durations", "vits_test_expand_prior", "vits_test_fill_normal", "vits_test_fill_normal_rows", "vits_test_post_conv",
     "vits_delivery_plan", "vits_deliver", "vits_test_deliver",
     "vits_trim_range", "vits_delivery_plan_trimmed", "vits_deliver_trimmed", "vits_test_deliver_trimmed",
@@ -319,6 +321,17 @@ def load():
     lib.vits_glide_cutoff.argtypes = [C.c_int64, i64p, C.POINTER(C.c_int32)]
     lib.vits_glide_plan.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, i64p]
     lib.vits_test_glide.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int]
+    for name in ("vits_warp_emit_end", "vits_glide_emit_end"):
+        getattr(lib, name).argtypes = [vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, i64p]
+    lib.vits_warp_stream_cap.argtypes = [C.c_int64, C.c_int64]
+    lib.vits_warp_stream_cap.restype = C.c_int64
+    lib.vits_run_chunked_glided.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.POINTER(VitsNoise), C.POINTER(VitsControls),
+                                            C.POINTER(VitsContour), C.c_int, CHUNK_FN, vp]
+    lib.vits_run_chunked_enc_glided.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.POINTER(VitsNoise), C.POINTER(VitsControls),
+                                                C.POINTER(VitsStreamFormat), C.POINTER(VitsStreamShaping), C.POINTER(VitsStreamOnset),
+                                                C.POINTER(VitsContour), C.c_int, ENC_CHUNK_TRIM_FN, vp]
+    for name in ("vits_test_warp_pieces", "vits_test_glide_pieces"):
+        getattr(lib, name).argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, vp, C.c_int]
     lib.vits_test_durations.argtypes = [C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp, vp]
     lib.vits_test_expand_prior.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int64, C.c_int,
                                            C.c_float, vp, vp, vp]

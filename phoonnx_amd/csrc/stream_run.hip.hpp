@@ -1,5 +1,5 @@
-// stream_run.hip.hpp — the stages a piece of a chunked run goes through behind the generator: the resampler's piece entry with its
-// carry (include/vitsmi.h, "Output rate") and the encoded sink's pack, plain ("encoded streaming") or shaped and limited ("shaped
+// stream_run.hip.hpp — the stages a piece of a chunked run goes through behind the generator: the warp's piece entry with its
+// history ("streamed pitch") or the resampler's with its carry (include/vitsmi.h, "Output rate"), and the encoded sink's pack, plain ("encoded streaming") or shaped and limited ("shaped
 // streaming", stream_shape.hip.hpp), with the scan of a trimmed stream in front ("trimmed streaming", stream_trim.hip.hpp).  The pipeline (vitsmi.hip, render_chunks) and the hooks vits_test_resample_pieces /
 // vits_test_stream_pack / _shaped run THESE functions.  Nothing here knows a handle.  The buffers are carve_stream's (workspace.hpp);
 // errors come back as hipError_t, launch counts by reference.  All is enqueued on the caller's stream; the caller copies out and waits.
@@ -13,6 +13,7 @@
 #include "resample.hip.hpp"
 #include "stream_shape.hip.hpp"
 #include "stream_trim.hip.hpp"
+#include "warp.hip.hpp"
 #include "workspace.hpp"
 
 namespace vitsmi {
@@ -65,6 +66,91 @@ inline hipError_t resample_run_piece(ResampleRun &r, const float *x, int64_t x_p
     e_n = ne > 0 ? ne : 0;
     if (ne > 0) r.emitted = n_hi;
     return e;
+}
+
+// ---- warped pieces ("streamed pitch"): the whole run's [B][S_w], bit for bit, whatever the pieces.  The stage in FRONT of the others:
+// it keeps the native waveform (the history), and what a piece completes by the emit rule (warp.hpp) leaves it on the output timeline.
+struct WarpRun {
+    bool glide = false;                 // which family's records the plan holds - and which kernel a window launches
+    std::vector<vits_warp_seg> wsegs;
+    std::vector<vits_glide_seg> gsegs;  // (one of the two is empty)
+    std::vector<int32_t> first;         // [B + 1]
+    std::vector<WarpRow> rows;          // [B]
+    std::vector<int64_t> spans;         // [B][T]: k per token, as vits_last_token_spans reports it
+    int64_t S_w = 0, n_cap = 0;
+    int64_t emitted = 0, e_end = 0;     // output samples delivered so far / complete behind the last piece
+    WarpStreamBufs wb{};
+    const float *G = nullptr;
+    std::vector<char> up;               // (pageable source of the plan's upload where the caller has no pinned block)
+    int64_t n_segs() const { return glide ? (int64_t)gsegs.size() : (int64_t)wsegs.size(); }
+};
+
+// The plan [segs | rows] and the rows' output counts, uploaded once; pin (nullable): plan_bytes + 4 B bytes of pinned memory.
+inline hipError_t warp_run_begin(WarpRun &r, const WarpStreamBufs &wb, const float *G, int64_t n_cap, int B, char *pin, hipStream_t st) {
+    r.wb = wb;
+    r.G = G;
+    r.n_cap = n_cap;
+    r.emitted = r.e_end = 0;
+    const size_t seg_bytes = (size_t)r.n_segs() * sizeof(vits_warp_seg);
+    if (!pin) {
+        r.up.resize(wb.plan_bytes + (size_t)B * sizeof(int));
+        pin = r.up.data();
+    }
+    if (seg_bytes) std::memcpy(pin, r.glide ? (const void *)r.gsegs.data() : (const void *)r.wsegs.data(), seg_bytes);
+    std::memcpy(pin + seg_bytes, r.rows.data(), (size_t)B * sizeof(WarpRow));
+    int *pin_nout = reinterpret_cast<int *>(pin + wb.plan_bytes);
+    for (int b = 0; b < B; b++) pin_nout[b] = r.rows[(size_t)b].n_out;
+    hipError_t e = hipMemcpyAsync(wb.segs, pin, wb.plan_bytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(wb.n_out, pin_nout, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st);
+    return e;
+}
+
+// The piece x [B][n], input samples [first, first + n) of every row, joins the history; what then exists of the output - e(first + n)
+// by the emit rule - is r.e_end.  Nothing is launched: warp_run_window renders [emitted, e_end) in windows of at most n_cap.
+inline hipError_t warp_run_piece(WarpRun &r, const float *x, int64_t x_pitch, int64_t first, int64_t n, bool is_last, int B, hipStream_t st) {
+    hipError_t e = hipSuccess;
+    if (n > 0)
+        e = hipMemcpy2DAsync(r.wb.hist + first, (size_t)r.wb.hist_pitch * 4, x, (size_t)x_pitch * 4, (size_t)n * 4, B, hipMemcpyDeviceToDevice, st);
+    const int64_t end = r.glide ? warp_emit_end(r.gsegs.data(), r.rows, r.S_w, first + n, is_last)
+                                : warp_emit_end(r.wsegs.data(), r.rows, r.S_w, first + n, is_last);
+    r.e_end = end > r.e_end ? end : r.e_end;
+    return e;
+}
+
+// The next window of what the last piece completed: output samples [e_first, e_first + e_n) of every row at y [B][e_n], one launch.
+// e_n == 0: nothing is left of it (a piece that completes nothing: at once).
+inline hipError_t warp_run_window(WarpRun &r, int B, hipStream_t st, const float *&y, int64_t &e_first, int64_t &e_n, int &launches) {
+    const int64_t left = r.e_end - r.emitted;
+    e_first = r.emitted;
+    e_n = left < r.n_cap ? left : r.n_cap;
+    launches = 0;
+    if (e_n <= 0) {
+        e_n = 0;
+        return hipSuccess;
+    }
+    y = r.wb.out;
+    launches = 1;
+    r.emitted += e_n;
+    const auto args = [&](auto &a) {
+        a.rows = r.wb.rows;
+        a.G = r.G;
+        a.x = r.wb.hist;
+        a.x_pitch = r.wb.hist_pitch;
+        a.y = r.wb.out;  // (the previous window's pack or copy-out precedes this one on the stream)
+        a.y_pitch = e_n;
+        a.n_lo = (int)e_first;
+        a.n_hi = (int)(e_first + e_n);
+    };
+    if (r.glide) {
+        GlideArgs a{};
+        a.segs = reinterpret_cast<const vits_glide_seg *>(r.wb.segs);
+        args(a);
+        return launch_glide(a, B, st);
+    }
+    WarpArgs a{};
+    a.segs = r.wb.segs;
+    args(a);
+    return launch_warp(a, B, st);
 }
 
 // ---- packed pieces: the encoded sink.  A piece reaches sp's chunk buffer as [B][pitch] bytes that end at the running peaks.

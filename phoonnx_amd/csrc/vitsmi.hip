@@ -2057,48 +2057,77 @@ int resample_rows_run(vits_handle *h, const int *ylen, int B) {
 // d_out / S describe the warped buffer afterwards, as after resample_run.
 // One body serves the warp (Seg = vits_warp_seg) and the glide ("pitch contours", Seg = vits_glide_seg: a record of the same
 // size, so carve_warp carves either plan block): plan_row plans a row into its records, launch is the family's launch.
-template <class Seg, class PlanRow, class Launch>
-int warp_run_as(vits_handle *h, const RunRows &rr, int B, int T, PlanRow plan_row, Launch launch) {
-    const int S = h->S, hop = h->model.hop;
-    if (h->h_dur_B != B || h->h_dur_T != T) return fail(h, VITS_E_ARG, "no durations to plan the warp from");
-    std::vector<Seg> segs;
-    std::vector<int32_t> first((size_t)B + 1, 0);
-    std::vector<int64_t> spans((size_t)B * T, 0), n_in((size_t)B), dur((size_t)T);
-    for (int b = 0; b < B; b++) {
-        const int L = (int)rr.semitone_lens[b];
-        for (int t = 0; t < L; t++) dur[t] = (int64_t)h->h_dur[(size_t)b * T + t];
-        const size_t at = segs.size();
-        segs.resize(at + (size_t)L);
-        int64_t ns = 0, N = 0;
-        const std::string e = plan_row(b, dur.data(), L, hop, segs.data() + at, spans.data() + (size_t)b * T, ns, N);
-        if (!e.empty()) return fail(h, VITS_E_ARG, "row %d, %s", b, e.c_str());
-        segs.resize(at + (size_t)ns);
-        first[(size_t)b + 1] = (int32_t)segs.size();
-        const int64_t n = (int64_t)h->h_ylen[b] * hop;
-        n_in[b] = n < 0 ? 0 : (n > S ? S : n);
-    }
-    std::vector<WarpRow> rows;
-    const int64_t S_w = warp_rows(segs.data(), first.data(), n_in.data(), B, rows);
-    if (S_w > INT_MAX) return fail(h, VITS_E_ARG, "a warped row of %lld samples: more than a row admits (%d)", (long long)S_w, INT_MAX);
-    WarpBufs wb;
-    if (int rc = slab_carve(h, h->io, "staging", [&](Carver &cv) { wb = carve_warp(cv, B, (int)S_w, (int64_t)segs.size()); })) return rc;
-    hipStream_t st = h->stream;
+// the prototype table on the device (made by the first warped run) and the pinned block a plan is uploaded from
+int warp_device_begin(vits_handle *h, size_t pin_bytes) {
     if (!h->warp_G) {
         std::vector<float> G(kWarpTable);
         warp_table(G.data());
         HIPCHECK(h, hipMalloc((void **)&h->warp_G, sizeof(float) * kWarpTable));
         HIPCHECK(h, hipMemcpy(h->warp_G, G.data(), sizeof(float) * kWarpTable, hipMemcpyHostToDevice));
     }
-    // [segs | rows | n_out] in pinned memory (the copies out of it that the previous run queued completed with this run's readback)
-    const size_t need = wb.plan_bytes + (size_t)B * sizeof(int);
-    if (h->warp_pin_cap < need) {
+    // (the copies out of it that the previous run queued completed with this run's readback)
+    if (h->warp_pin_cap < pin_bytes) {
         if (h->warp_pin) hipHostFree(h->warp_pin);
         h->warp_pin = nullptr;
         h->warp_pin_cap = 0;
-        const size_t cap = need < 65536 ? 65536 : need + need / 4;
+        const size_t cap = pin_bytes < 65536 ? 65536 : pin_bytes + pin_bytes / 4;
         HIPCHECK(h, hipHostMalloc((void **)&h->warp_pin, cap));
         h->warp_pin_cap = cap;
     }
+    return 0;
+}
+
+// The plans of a run's rows from the host copy of the durations, which the run's one readback left: no synchronisation.
+// row_in: the input samples a row has at most.  The whole run (warp_run_as) and the streamed one (render_chunks) plan HERE.
+template <class Seg, class PlanRow>
+int warp_plan_run(vits_handle *h, const RunRows &rr, int B, int T, int64_t row_in, PlanRow plan_row, std::vector<Seg> &segs,
+                  std::vector<int32_t> &first, std::vector<int64_t> &spans, std::vector<WarpRow> &rows, int64_t &S_w) {
+    if (h->h_dur_B != B || h->h_dur_T != T) return fail(h, VITS_E_ARG, "no durations to plan the warp from");
+    std::vector<int64_t> n_in((size_t)B);
+    for (int b = 0; b < B; b++) {
+        const int64_t n = (int64_t)h->h_ylen[b] * h->model.hop;
+        n_in[b] = n < 0 ? 0 : (n > row_in ? row_in : n);
+    }
+    const std::string e = warp_plan_rows(h->h_dur.data(), rr.semitone_lens, n_in.data(), B, T, h->model.hop, plan_row, segs, first, spans, rows, S_w);
+    if (!e.empty()) return fail(h, VITS_E_ARG, "%s", e.c_str());
+    if (S_w > INT_MAX) return fail(h, VITS_E_ARG, "a warped row of %lld samples: more than a row admits (%d)", (long long)S_w, INT_MAX);
+    return 0;
+}
+
+// the two families' plan_row over a run's semitones
+auto warp_plan_row(const RunRows &rr, int T) {
+    return [&rr, T](int b, const int64_t *dur, int L, int hop, vits_warp_seg *segs, int64_t *spans, int64_t &ns, int64_t &N) {
+        return warp_plan(dur, rr.semitones + (size_t)b * T, L, hop, segs, spans, ns, N);
+    };
+}
+auto glide_plan_row(const RunRows &rr, int T) {
+    return [&rr, T](int b, const int64_t *dur, int L, int hop, vits_glide_seg *segs, int64_t *spans, int64_t &ns, int64_t &N) {
+        return glide_plan(dur, rr.semitones + (size_t)b * T, rr.semitones_end + (size_t)b * T, L, hop, segs, spans, ns, N);
+    };
+}
+
+// what a warped run leaves for the host: the rows' output counts and k per token
+void warp_remember(vits_handle *h, const std::vector<WarpRow> &rows, std::vector<int64_t> &&spans, int T) {
+    h->warp_counts.resize(rows.size());
+    for (size_t b = 0; b < rows.size(); b++) h->warp_counts[b] = rows[b].n_out;
+    h->warp_spans = std::move(spans);
+    h->warp_T = T;
+}
+
+template <class Seg, class PlanRow, class Launch>
+int warp_run_as(vits_handle *h, const RunRows &rr, int B, int T, PlanRow plan_row, Launch launch) {
+    const int S = h->S;
+    std::vector<Seg> segs;
+    std::vector<int32_t> first;
+    std::vector<int64_t> spans;
+    std::vector<WarpRow> rows;
+    int64_t S_w = 1;
+    if (int rc = warp_plan_run(h, rr, B, T, S, plan_row, segs, first, spans, rows, S_w)) return rc;
+    WarpBufs wb;
+    if (int rc = slab_carve(h, h->io, "staging", [&](Carver &cv) { wb = carve_warp(cv, B, (int)S_w, (int64_t)segs.size()); })) return rc;
+    hipStream_t st = h->stream;
+    // [segs | rows | n_out] in pinned memory
+    if (int rc = warp_device_begin(h, wb.plan_bytes + (size_t)B * sizeof(int))) return rc;
     const size_t seg_bytes = segs.size() * sizeof(Seg);
     if (seg_bytes) std::memcpy(h->warp_pin, segs.data(), seg_bytes);
     std::memcpy(h->warp_pin + seg_bytes, rows.data(), (size_t)B * sizeof(WarpRow));
@@ -2124,28 +2153,14 @@ int warp_run_as(vits_handle *h, const RunRows &rr, int B, int T, PlanRow plan_ro
     h->rs_run_K = 0;
     h->rs_run_L = h->rs_run_M = 1;
     h->out_resampled = true;
-    h->warp_counts.resize((size_t)B);
-    for (int b = 0; b < B; b++) h->warp_counts[(size_t)b] = rows[(size_t)b].n_out;
-    h->warp_spans = std::move(spans);
-    h->warp_T = T;
+    warp_remember(h, rows, std::move(spans), T);
     return 0;
 }
 
 // constant tokens: warp_kernel; some token glides (rr.semitones_end): glide_kernel in its slot
 int warp_run(vits_handle *h, const RunRows &rr, int B, int T) {
-    if (!rr.semitones_end)
-        return warp_run_as<vits_warp_seg>(
-            h, rr, B, T,
-            [&](int b, const int64_t *dur, int L, int hop, vits_warp_seg *segs, int64_t *spans, int64_t &ns, int64_t &N) {
-                return warp_plan(dur, rr.semitones + (size_t)b * T, L, hop, segs, spans, ns, N);
-            },
-            launch_warp);
-    return warp_run_as<vits_glide_seg>(
-        h, rr, B, T,
-        [&](int b, const int64_t *dur, int L, int hop, vits_glide_seg *segs, int64_t *spans, int64_t &ns, int64_t &N) {
-            return glide_plan(dur, rr.semitones + (size_t)b * T, rr.semitones_end + (size_t)b * T, L, hop, segs, spans, ns, N);
-        },
-        launch_glide);
+    if (!rr.semitones_end) return warp_run_as<vits_warp_seg>(h, rr, B, T, warp_plan_row(rr, T), launch_warp);
+    return warp_run_as<vits_glide_seg>(h, rr, B, T, glide_plan_row(rr, T), launch_glide);
 }
 
 // The two pinned buffers (vits_handle::ring) finished pieces reach the host through.  A piece is copied into slot(); queue()
@@ -2183,7 +2198,7 @@ struct ChunkRing {
 // order wherever a column sits in a tile).  The interior then goes through the stages of stream_run.hip.hpp (resample, pack)
 // and what is left to deliver reaches the host through the ring; the callback for chunk i runs while chunk i + 1 renders.
 int render_chunks(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int z_cstride, const int *ylen, int B, int F,
-                  const float *dec_cond, const FrameBufs &fb, int Fgen, const ChunkSink &sink) {
+                  const float *dec_cond, const FrameBufs &fb, int Fgen, const ChunkSink &sink, const RunRows *pitch = nullptr, int T = 0) {
     const Model &m = h->model;
     hipStream_t st = h->stream;
     const int ov = m.gen_rf_frames, hop = m.hop;
@@ -2191,13 +2206,27 @@ int render_chunks(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int
     const ResamplePlan &rp = h->rs.plan;
     const bool rs = rp.on();             // an output rate: the batch path's [B][S_out], bit for bit
     const bool enc = sink.fmt != nullptr;  // the encoded form of the sink; false executes what it always executed
+    // Streamed pitch (vitsmi.h, "streamed pitch"; the entries refuse it at an output rate): the rows' plans first, from the
+    // durations on the host - the whole run's planning -, so that everything below sees the OUTPUT timeline: S_w, N_b.
+    const bool warp = pitch != nullptr;
+    WarpRun wrun;
+    if (warp) {
+        h->d_out = nullptr;  // (as under a plan callback: the run has begun, the host's counts are this run's from here on)
+        wrun.glide = pitch->semitones_end != nullptr;
+        const int rc = wrun.glide ? warp_plan_run(h, *pitch, B, T, (int64_t)F * hop, glide_plan_row(*pitch, T), wrun.gsegs, wrun.first,
+                                                  wrun.spans, wrun.rows, wrun.S_w)
+                                  : warp_plan_run(h, *pitch, B, T, (int64_t)F * hop, warp_plan_row(*pitch, T), wrun.wsegs, wrun.first,
+                                                  wrun.spans, wrun.rows, wrun.S_w);
+        if (rc) return rc;
+        warp_remember(h, wrun.rows, std::vector<int64_t>(wrun.spans), T);
+    }
     // encoded form: the rows' valid samples (host: the callback's valid[]; device: the kernel's)
     std::vector<int64_t> row_n;
     if (enc) {
         row_n.resize((size_t)B);
         for (int b = 0; b < B; b++) {
             const int64_t nb = (int64_t)(ylen ? h->h_ylen[b] : F) * hop;
-            row_n[b] = rs ? rp.count(nb) : nb;
+            row_n[b] = warp ? (int64_t)wrun.rows[(size_t)b].n_out : rs ? rp.count(nb) : nb;
         }
     }
     // The shaped form of the encoded sink (vitsmi.h, "shaped streaming"): the plan callback first - the durations and the
@@ -2233,12 +2262,20 @@ int render_chunks(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int
     int S_out = 0;
     if (rs)
         if (int rc = resample_count(h, (int64_t)F * hop, S_out)) return rc;
-    const int64_t total = rs ? (int64_t)S_out : (int64_t)F * hop, n_max = stream_n_max(rp, chunk, F, hop, sL, total);
+    const int64_t n_cap = warp ? warp_stream_cap((int64_t)(chunk < F ? chunk : F) * hop, wrun.S_w) : 0;
+    const int64_t total = warp ? wrun.S_w : rs ? (int64_t)S_out : (int64_t)F * hop;
+    const int64_t n_max = warp ? (n_cap + sL < total ? n_cap + sL : total) : stream_n_max(rp, chunk, F, hop, sL, total);
     StreamBufs sb{};
+    WarpStreamBufs wsb{};
     if (int rc = slab_carve(h, h->io, "staging", [&](Carver &cv) {
+            if (warp) wsb = carve_warp_stream(cv, B, (int64_t)F * hop, n_cap, wrun.n_segs());
             sb = carve_stream(cv, B, total, n_max, rs ? (int)rp.K : 0, enc, shaped, sL, shaped ? stream_knot_count(&shp, B) : 0, trimmed);
         }))
         return rc;
+    if (warp) {
+        if (int rc = warp_device_begin(h, wsb.plan_bytes + (size_t)B * sizeof(int))) return rc;
+        HIPCHECK(h, warp_run_begin(wrun, wsb, h->warp_G, n_cap, B, h->warp_pin, st));
+    }
     ResampleRun rrun;
     if (rs) {
         HIPCHECK(h, resample_run_begin(rrun, h->rs, sb.rs, ylen, hop, F * hop, S_out, B, st));
@@ -2260,7 +2297,10 @@ int render_chunks(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int
     StreamPackRun prun;
     if (enc)
         HIPCHECK(h, stream_pack_begin(prun, sink.fmt, shaped ? &shp : nullptr, B, sb.sp, sb.ss,
-                                      rs ? StreamPackRows{sb.rs.n_out, 1, S_out} : StreamPackRows{ylen, hop, F * hop}, total, st,
+                                      warp ? StreamPackRows{wsb.n_out, 1, (int)total}
+                                      : rs ? StreamPackRows{sb.rs.n_out, 1, S_out}
+                                           : StreamPackRows{ylen, hop, F * hop},
+                                      total, st,
                                       trimmed ? sink.onsets : nullptr, row_n.data()));
     std::vector<int32_t> valid((size_t)(enc ? B : 0)), skip((size_t)(enc ? B : 0), 0);
     auto call = [&](const char *buf, int64_t first, int64_t n) -> int {  // the caller's callback over a finished piece
@@ -2277,6 +2317,27 @@ int render_chunks(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int
         return sink.efn ? sink.efn(sink.user, buf, B, pitch, first, n, valid.data(), peaks, total) : 0;
     };
     ChunkRing<decltype(call)> ring{h, call};
+    // What is left of a piece behind the stages in front - x [B][pn] at `first` (dense: its pitch is pn) - through the pack stage
+    // into the ring.
+    auto hand_over = [&](const float *x, int64_t x_pitch, int64_t first, int64_t pn, bool dense) -> int {
+        int launches = 0;
+        unsigned char *d = nullptr;
+        size_t pitch = 0;
+        if (enc && pn > 0) {
+            const hipError_t e = stream_pack_piece(prun, x, x_pitch, first, pn, B, st, d, first, pn, pitch, launches);
+            if (e != hipSuccess) return fail(h, VITS_E_DEVICE, "%sstream pack launch failed: %s", shaped ? "shaped " : "", hipGetErrorString(e));
+            h->stats.total_launches += launches;
+        }
+        // (a chunk shorter than the filter's or the limiter's look-ahead completes nothing: no copy, no call, the same slot next)
+        if (pn <= 0) return 0;
+        if (enc)  // bytes and peaks - a trimmed stream: and starts - in one copy
+            HIPCHECK(h, hipMemcpyAsync(ring.slot(), d, (size_t)B * pitch + prun.tail_bytes(B), hipMemcpyDeviceToHost, st));
+        else if (dense)
+            HIPCHECK(h, hipMemcpyAsync(ring.slot(), x, (size_t)B * pn * 4, hipMemcpyDeviceToHost, st));
+        else  // straight out of the rendered rows
+            HIPCHECK(h, hipMemcpy2DAsync(ring.slot(), (size_t)pn * 4, x, (size_t)x_pitch * 4, (size_t)pn * 4, B, hipMemcpyDeviceToHost, st));
+        return ring.queue(first, pn);
+    };
     // per-chunk valid lengths, ALWAYS passed: a chunk is a window into rows whose neighbours are real data, and only a
     // length mask makes the conv engines bound their reads by the chunk instead of by the row pitch
     int *yl = fb.gen.yl;
@@ -2308,22 +2369,19 @@ int render_chunks(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int
             x = sb.rs.out;  // [B][pn]
             x_pitch = pn;
         }
-        unsigned char *d = nullptr;
-        size_t pitch = 0;
-        if (enc && pn > 0) {
-            const hipError_t e = stream_pack_piece(prun, x, x_pitch, first, pn, B, st, d, first, pn, pitch, launches);
-            if (e != hipSuccess) return fail(h, VITS_E_DEVICE, "%sstream pack launch failed: %s", shaped ? "shaped " : "", hipGetErrorString(e));
-            h->stats.total_launches += launches;
+        if (warp) {  // the history takes the piece; what that completes goes on in windows of at most n_cap output samples
+            const hipError_t ew = warp_run_piece(wrun, x, x_pitch, first, pn, f1 == F, B, st);
+            if (ew != hipSuccess) return fail(h, VITS_E_DEVICE, "warp history copy failed: %s", hipGetErrorString(ew));
+            while (!ring.stop) {
+                const hipError_t e = warp_run_window(wrun, B, st, x, first, pn, launches);
+                if (e != hipSuccess) return fail(h, VITS_E_DEVICE, "warp launch failed: %s", hipGetErrorString(e));
+                if (pn <= 0) break;
+                h->stats.total_launches += launches;
+                if (int rc = hand_over(x, pn, first, pn, /*packed_rows=*/true)) return rc;
+            }
+            continue;
         }
-        // (a chunk shorter than the filter's or the limiter's look-ahead completes nothing: no copy, no call, the same slot next)
-        if (pn <= 0) continue;
-        if (enc)  // bytes and peaks - a trimmed stream: and starts - in one copy
-            HIPCHECK(h, hipMemcpyAsync(ring.slot(), d, (size_t)B * pitch + prun.tail_bytes(B), hipMemcpyDeviceToHost, st));
-        else if (rs)
-            HIPCHECK(h, hipMemcpyAsync(ring.slot(), x, (size_t)B * pn * 4, hipMemcpyDeviceToHost, st));
-        else  // straight out of the rendered rows
-            HIPCHECK(h, hipMemcpy2DAsync(ring.slot(), (size_t)pn * 4, x, (size_t)x_pitch * 4, (size_t)pn * 4, B, hipMemcpyDeviceToHost, st));
-        if (int rc = ring.queue(first, pn)) return rc;
+        if (int rc = hand_over(x, x_pitch, first, pn, rs)) return rc;
     }
     if (!ring.stop)
         if (int rc = ring.deliver()) return rc;
@@ -2531,7 +2589,7 @@ int run_frames(vits_handle *h, int B, int T, const RunRows &rr, const int64_t *d
                                                                     c.P(m.dec_cond_b), dec_cond, m.C0, m.gin);
         h->stats.total_launches++;
     }
-    if (sink) return render_chunks(h, c, z, sCF, F, ylen, B, Freal, dec_cond, fb, Fgen, *sink);
+    if (sink) return render_chunks(h, c, z, sCF, F, ylen, B, Freal, dec_cond, fb, Fgen, *sink, rr.semitones ? &rr : nullptr, T);
     if (int rc = run_generator(h, c, z, sCF, F, ylen, B, Freal, dec_cond, fb.gen)) return rc;
     if (c.err != hipSuccess) return fail(h, VITS_E_DEVICE, "kernel launch failed: %s", hipGetErrorString(c.err));
     return 0;
@@ -3473,9 +3531,22 @@ int vits_run_async_ctl(vits_handle *h, const int64_t *ids, const int64_t *lens, 
 // contradictions, the rates that are set - is answered before the device is looked at: a host-only handle answers it too.
 // One body serves both entries: st0 the start values (NULL: zeros), st1 the end values (NULL: every token keeps its speed - the
 // warp's entry); `entry` names the caller in the refusal of an output rate.
-static int run_intoned_locked(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
-                              const vits_noise *noise, const vits_controls *ctl, const float *st0, const float *st1, int compensate,
-                              const char *entry) {
+// what host_intonation makes of a call: the controls with compensate's duration multiplier folded in, and the values a warped run plans from
+struct Intoned {
+    vits_controls ctl{};
+    std::vector<float> rate, zeros;
+    const float *st0 = nullptr, *st1 = nullptr;  // st1 == nullptr: equal ends everywhere - the warp itself
+    bool warped = false;
+    void apply(RunRows &rr, const int64_t *lens) const {
+        if (!warped) return;
+        rr.semitones = st0;
+        rr.semitones_end = st1;
+        rr.semitone_lens = lens;
+    }
+};
+
+static int host_intonation(vits_handle *h, const vits_controls *ctl, const int64_t *lens, int B, int T, const float *st0, const float *st1,
+                           int compensate, const char *entry, Intoned &in) {
     if (!ctl) return fail(h, VITS_E_ARG, "null argument");
     bool warped = false, glided = false;
     if (st0 || st1) {
@@ -3496,36 +3567,41 @@ static int run_intoned_locked(vits_handle *h, const int64_t *ids, const int64_t 
             }
         }
     }
-    vits_controls c2 = *ctl;
-    std::vector<float> rate, zeros;
-    if (warped) {
-        if (compensate && ctl->durations)
-            return fail(h, VITS_E_ARG, "compensate and forced durations are contradictory: forced durations are the rendered ones");
-        if (h->rs.plan.on() || h->rows.on()) return fail(h, VITS_E_ARG, "%s is not covered with an output rate set", entry);
-        if (!st0) {
-            zeros.assign((size_t)B * T, 0.f);
-            st0 = zeros.data();
-        }
-        if (compensate) {  // the duration multiplier of token t: token_rate * (float)r_t - r_t the mean of its ends -, one fp32 product
-            rate.assign((size_t)B * T, 1.0f);
-            for (int b = 0; b < B; b++)
-                for (int t = 0; t < (int)lens[b]; t++) {
-                    const size_t i = (size_t)b * T + t;
-                    const double r0 = std::exp2((double)st0[i] / 12.0);
-                    const float r = glided ? (float)((r0 + std::exp2((double)st1[i] / 12.0)) * 0.5) : (float)r0;
-                    rate[i] = (ctl->token_rate ? ctl->token_rate[i] : 1.0f) * r;
-                }
-            c2.token_rate = rate.data();
-        }
+    in.ctl = *ctl;
+    in.warped = warped;
+    if (!warped) return VITS_OK;
+    if (compensate && ctl->durations)
+        return fail(h, VITS_E_ARG, "compensate and forced durations are contradictory: forced durations are the rendered ones");
+    if (h->rs.plan.on() || h->rows.on()) return fail(h, VITS_E_ARG, "%s is not covered with an output rate set", entry);
+    if (!st0) {
+        in.zeros.assign((size_t)B * T, 0.f);
+        st0 = in.zeros.data();
     }
+    if (compensate) {  // the duration multiplier of token t: token_rate * (float)r_t - r_t the mean of its ends -, one fp32 product
+        in.rate.assign((size_t)B * T, 1.0f);
+        for (int b = 0; b < B; b++)
+            for (int t = 0; t < (int)lens[b]; t++) {
+                const size_t i = (size_t)b * T + t;
+                const double r0 = std::exp2((double)st0[i] / 12.0);
+                const float r = glided ? (float)((r0 + std::exp2((double)st1[i] / 12.0)) * 0.5) : (float)r0;
+                in.rate[i] = (ctl->token_rate ? ctl->token_rate[i] : 1.0f) * r;
+            }
+        in.ctl.token_rate = in.rate.data();
+    }
+    in.st0 = st0;
+    in.st1 = glided ? st1 : nullptr;  // equal ends: the warp itself
+    return VITS_OK;
+}
+
+static int run_intoned_locked(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
+                              const vits_noise *noise, const vits_controls *ctl, const float *st0, const float *st1, int compensate,
+                              const char *entry) {
+    Intoned in;
+    if (int rc = host_intonation(h, ctl, lens, B, T, st0, st1, compensate, entry, in)) return rc;
     if (int rc = check_dev(h)) return rc;
     RunRows rr;
-    if (int rc = host_controls(h, &c2, lens, B, T, rr)) return rc;
-    if (warped) {
-        rr.semitones = st0;
-        rr.semitones_end = glided ? st1 : nullptr;  // equal ends: the warp itself
-        rr.semitone_lens = lens;
-    }
+    if (int rc = host_controls(h, &in.ctl, lens, B, T, rr)) return rc;
+    in.apply(rr, lens);
     vits_output dev{};
     return run_async_locked(h, ids, lens, B, T, rr, sid, noise, &dev);
 }
@@ -3606,6 +3682,35 @@ int vits_glide_plan(const int64_t *durations, const float *st0, const float *st1
     return (int)ns;
 }
 
+// the emit rule of a row (vitsmi.h, "streamed pitch"), without a handle
+extern "C++" {
+template <class Seg, class Fault>
+static int emit_end_as(const Seg *segs, int n_segs, int64_t n_in, int64_t n_out, int64_t X, int64_t *ready, Fault fault) {
+    if (n_segs < 0 || (n_segs > 0 && !segs) || n_in < 0 || n_out < 0 || X < 0 || !ready)
+        return fail(nullptr, VITS_E_ARG, "bad emit end arguments (n_segs = %d, n_in = %lld, n_out = %lld, X = %lld)", n_segs, (long long)n_in,
+                    (long long)n_out, (long long)X);
+    const std::string e = fault(segs, n_segs);
+    if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
+    const int64_t N = n_segs > 0 ? segs[n_segs - 1].n0 + segs[n_segs - 1].k : n_in;
+    if (n_out != N) return fail(nullptr, VITS_E_ARG, "n_out = %lld, the row's records give %lld", (long long)n_out, (long long)N);
+    *ready = warp_emit_row(segs, n_segs, n_in, n_out, X);
+    return VITS_OK;
+}
+}  // extern "C++"
+
+int vits_warp_emit_end(const vits_warp_seg *segs, int n_segs, int64_t n_in, int64_t n_out, int64_t X, int64_t *ready) {
+    return emit_end_as(segs, n_segs, n_in, n_out, X, ready, warp_segs_fault);
+}
+
+int vits_glide_emit_end(const vits_glide_seg *segs, int n_segs, int64_t n_in, int64_t n_out, int64_t X, int64_t *ready) {
+    return emit_end_as(segs, n_segs, n_in, n_out, X, ready, glide_segs_fault);
+}
+
+int64_t vits_warp_stream_cap(int64_t piece_samples, int64_t S_w) {
+    if (piece_samples < 1 || S_w < 1) return fail(nullptr, VITS_E_ARG, "bad stream cap arguments (%lld, %lld)", (long long)piece_samples, (long long)S_w);
+    return warp_stream_cap(piece_samples, S_w);
+}
+
 int vits_run_chunked_ctl(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
                          const vits_noise *noise, const vits_controls *ctl, int chunk_frames, vits_chunk_fn fn, void *user) {
     if (int rc = check_dev(h)) return rc;
@@ -3613,6 +3718,48 @@ int vits_run_chunked_ctl(vits_handle *h, const int64_t *ids, const int64_t *lens
     RunRows rr;
     if (int rc = host_controls(h, ctl, lens, B, T, rr)) return rc;
     return run_chunked_locked(h, ids, lens, B, T, rr, sid, noise, chunk_frames, fn, user);
+}
+
+// The chunked entries with pitch (vitsmi.h, "streamed pitch"): the checks are the whole run's (host_intonation), before anything is
+// enqueued.  All-zero semitones leave rr without them: the call then is vits_run_chunked_ctl / vits_run_chunked_enc* itself.
+int vits_run_chunked_glided(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid, const vits_noise *noise,
+                            const vits_controls *ctl, const vits_contour *contour, int chunk_frames, vits_chunk_fn fn, void *user) {
+    if (!h) return VITS_E_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    Intoned in;
+    if (int rc = host_intonation(h, ctl, lens, B, T, contour ? contour->token_semitones : nullptr, contour ? contour->token_semitones_end : nullptr,
+                                 contour ? contour->compensate : 0, "vits_run_chunked_glided", in))
+        return rc;
+    if (int rc = check_dev(h)) return rc;
+    RunRows rr;
+    if (int rc = host_controls(h, &in.ctl, lens, B, T, rr)) return rc;
+    in.apply(rr, lens);
+    return run_chunked_locked(h, ids, lens, B, T, rr, sid, noise, chunk_frames, fn, user);
+}
+
+int vits_run_chunked_enc_glided(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
+                                const vits_noise *noise, const vits_controls *ctl, const vits_stream_format *fmt,
+                                const vits_stream_shaping *shaping, const vits_stream_onset *onsets, const vits_contour *contour,
+                                int chunk_frames, vits_enc_chunk_trim_fn fn, void *user) {
+    if (!h) return VITS_E_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (int rc = host_stream_format(h, fmt, B)) return rc;
+    if (int rc = host_stream_shaping(h, shaping, fmt, B)) return rc;
+    if (int rc = host_stream_onsets(h, onsets, fmt, B)) return rc;
+    Intoned in;
+    if (int rc = host_intonation(h, ctl, lens, B, T, contour ? contour->token_semitones : nullptr, contour ? contour->token_semitones_end : nullptr,
+                                 contour ? contour->compensate : 0, "vits_run_chunked_enc_glided", in))
+        return rc;
+    if (int rc = check_dev(h)) return rc;
+    RunRows rr;
+    if (int rc = host_controls(h, &in.ctl, lens, B, T, rr)) return rc;
+    in.apply(rr, lens);
+    ChunkSink sink{chunk_frames, nullptr, user};
+    sink.fmt = fmt;
+    sink.shaping = shaping;
+    sink.onsets = onsets;
+    sink.tfn = fn;
+    return run_chunked_sink(h, ids, lens, B, T, rr, sid, noise, sink);
 }
 
 void vits_free_output(vits_handle *h, vits_output *out) {
@@ -5318,6 +5465,93 @@ int vits_test_warp(int device_id, const float *x, const int64_t *counts, int B, 
 int vits_test_glide(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_glide_seg *segs, const int32_t *seg_first,
                     float *y, int S_w) {
     return test_warp_as(device_id, x, counts, B, S, segs, seg_first, y, S_w, glide_segs_fault, launch_glide);
+}
+
+// Streamed pitch by value: the input cut at piece_bounds (increasing piece ends, the last one S), every piece through the
+// pipeline's stage (warp_run_begin / _piece / _window) on the pipeline's walk; n_cap is warp_stream_cap of the longest piece.
+extern "C++" {
+namespace {
+template <class Seg, class Fault>
+int test_warp_pieces_as(int device_id, const float *x, const int64_t *counts, int B, int S, const Seg *segs, const int32_t *seg_first,
+                        const int64_t *piece_bounds, int n_pieces, float *y, int S_w, int64_t *ranges, int max_ranges, Fault fault,
+                        std::vector<Seg> WarpRun::*mine, bool glide) {
+    if (int rc = test_dev(device_id)) return rc;
+    if (!x || !y || !counts || !seg_first || !piece_bounds || B <= 0 || S <= 0 || S_w < 1 || n_pieces < 1)
+        return fail(nullptr, VITS_E_ARG, "bad warp test arguments");
+    if (seg_first[0] != 0) return fail(nullptr, VITS_E_ARG, "seg_first[0] = %d, not 0", (int)seg_first[0]);
+    int64_t longest = 0;
+    for (int i = 0; i < n_pieces; i++) {
+        const int64_t lo = i ? piece_bounds[i - 1] : 0;
+        if (piece_bounds[i] <= lo || piece_bounds[i] > S) return fail(nullptr, VITS_E_ARG, "piece_bounds[%d] = %lld does not ascend within (0, %d]", i, (long long)piece_bounds[i], S);
+        longest = piece_bounds[i] - lo > longest ? piece_bounds[i] - lo : longest;
+    }
+    if (piece_bounds[n_pieces - 1] != S) return fail(nullptr, VITS_E_ARG, "the last piece ends at %lld, not at S = %d", (long long)piece_bounds[n_pieces - 1], S);
+    std::vector<int64_t> n_in((size_t)B);
+    for (int b = 0; b < B; b++) {
+        const int32_t ns = seg_first[b + 1] - seg_first[b];
+        if (ns < 0 || (ns > 0 && !segs)) return fail(nullptr, VITS_E_ARG, "row %d: seg_first is not ascending", b);
+        const std::string e = fault(segs + seg_first[b], ns);
+        if (!e.empty()) return fail(nullptr, VITS_E_ARG, "row %d: %s", b, e.c_str());
+        n_in[(size_t)b] = counts[b] < 0 ? 0 : (counts[b] > S ? S : counts[b]);
+    }
+    WarpRun run;
+    run.glide = glide;
+    const size_t n_segs = (size_t)seg_first[B];
+    (run.*mine).assign(segs, segs + n_segs);
+    run.first.assign(seg_first, seg_first + B + 1);
+    run.S_w = warp_rows(segs, seg_first, n_in.data(), B, run.rows);
+    if (S_w != run.S_w) return fail(nullptr, VITS_E_ARG, "S_w = %d, the rows give %lld", S_w, (long long)run.S_w);
+    const int64_t n_cap = warp_stream_cap(longest, run.S_w);
+    std::vector<float> G(kWarpTable);
+    warp_table(G.data());
+    DevBufs D;
+    const float *dG = D.up(G.data(), G.size());
+    const float *dx = D.up(x, (size_t)B * S);
+    const auto walk = [&](Carver &cv) { return carve_warp_stream(cv, B, S, n_cap, (int64_t)n_segs); };
+    const size_t bytes = carved_bytes(walk);
+    Carver cv(D.fill<unsigned char>(bytes, 0xff), bytes);  // (poisoned: what a window must not read is NaN)
+    TCHECK(D.err);
+    const WarpStreamBufs wb = walk(cv);
+    if (!cv.fits()) return fail(nullptr, VITS_E_NOMEM, "stream walk carved %zu of %zu bytes", cv.used, cv.cap);
+    TCHECK(warp_run_begin(run, wb, dG, n_cap, B, nullptr, nullptr));
+    std::vector<float> piece((size_t)B * n_cap);
+    std::memset(y, 0, (size_t)B * S_w * sizeof(float));
+    int calls = 0;
+    for (int i = 0; i < n_pieces; i++) {
+        const int64_t f0 = i ? piece_bounds[i - 1] : 0, n = piece_bounds[i] - f0;
+        TCHECK(warp_run_piece(run, dx + f0, S, f0, n, i == n_pieces - 1, B, nullptr));
+        for (;;) {
+            const float *dy = nullptr;
+            int64_t ef = 0, en = 0;
+            int launches = 0;
+            TCHECK(warp_run_window(run, B, nullptr, dy, ef, en, launches));
+            if (en <= 0) break;
+            TCHECK(hipDeviceSynchronize());
+            TCHECK(download(piece.data(), dy, (size_t)B * en));
+            for (int b = 0; b < B; b++) std::memcpy(y + (size_t)b * S_w + ef, piece.data() + (size_t)b * en, (size_t)en * sizeof(float));
+            if (ranges && calls < max_ranges) {
+                ranges[2 * calls] = ef;
+                ranges[2 * calls + 1] = en;
+            }
+            calls++;
+        }
+    }
+    TCHECK(hipDeviceSynchronize());
+    return calls;
+}
+}  // namespace
+}  // extern "C++"
+
+int vits_test_warp_pieces(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_warp_seg *segs, const int32_t *seg_first,
+                          const int64_t *piece_bounds, int n_pieces, float *y, int S_w, int64_t *ranges, int max_ranges) {
+    return test_warp_pieces_as(device_id, x, counts, B, S, segs, seg_first, piece_bounds, n_pieces, y, S_w, ranges, max_ranges, warp_segs_fault,
+                               &WarpRun::wsegs, false);
+}
+
+int vits_test_glide_pieces(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_glide_seg *segs, const int32_t *seg_first,
+                           const int64_t *piece_bounds, int n_pieces, float *y, int S_w, int64_t *ranges, int max_ranges) {
+    return test_warp_pieces_as(device_id, x, counts, B, S, segs, seg_first, piece_bounds, n_pieces, y, S_w, ranges, max_ranges, glide_segs_fault,
+                               &WarpRun::gsegs, true);
 }
 
 // The rows entry by value: the plans of the distinct rates among out_rates (0 or in_rate: a native row), one record per row,

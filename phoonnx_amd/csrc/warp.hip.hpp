@@ -30,9 +30,10 @@ struct WarpArgsT {
     const float *G;       // [kWarpTable]
     const float *x;       // input samples of row b at x + b * x_pitch
     int64_t x_pitch;
-    float *y;             // [B][y_pitch]
+    float *y;             // [B][y_pitch]: row b's output sample n_lo at y + b * y_pitch
     int64_t y_pitch;
-    int n_hi;             // S_w: the launch renders output samples [0, n_hi) of every row
+    int n_hi;             // the launch renders output samples [n_lo, n_hi) of every row; a whole run: [0, S_w)
+    int n_lo;             // a window of a streamed run ("streamed pitch"): tile i covers [n_lo + 256 i, ...), clipped by n_hi
 };
 using WarpArgs = WarpArgsT<vits_warp_seg>;
 using GlideArgs = WarpArgsT<vits_glide_seg>;  // "pitch contours": the same launch over gliding records
@@ -75,15 +76,17 @@ __global__ void __launch_bounds__(kWarpBlock) warp_kernel(WarpArgs a) {
     __shared__ float gs[kWarpTable];
     const int b = blockIdx.y;
     const WarpRow r = a.rows[b];
-    const int64_t n0 = (int64_t)blockIdx.x * kWarpBlock, n = n0 + threadIdx.x;
+    const int64_t n0 = a.n_lo + (int64_t)blockIdx.x * kWarpBlock, n = n0 + threadIdx.x;
     const float *xrow = a.x + (int64_t)b * a.x_pitch;
-    float *yrow = a.y + (int64_t)b * a.y_pitch;
+    float *yrow = a.y + (int64_t)b * a.y_pitch - a.n_lo;  // indexed by n
     if (n0 >= r.n_out || r.identity || r.n_segs <= 0) {  // behind the row's end: zeros; an identity row: its valid samples
         if (n < a.n_hi) yrow[n] = (r.identity && n < r.n_out && n < r.n_in) ? xrow[n] : 0.f;
         return;
     }
     const vits_warp_seg *sg = a.segs + r.seg0;
-    const int64_t n_last = (n0 + kWarpBlock < r.n_out ? n0 + kWarpBlock : (int64_t)r.n_out) - 1;
+    // the tile's last sample: clipped by the row and by the window, so that nothing behind the window's last position is staged
+    const int64_t n_end = n0 + kWarpBlock < a.n_hi ? n0 + kWarpBlock : (int64_t)a.n_hi;
+    const int64_t n_last = (n_end < r.n_out ? n_end : (int64_t)r.n_out) - 1;
     const int j0 = warp_find(sg, r.n_segs, n0), j1 = warp_find(sg, r.n_segs, n_last);
     const int64_t i_lo = (sg[j0].pos0 + (n0 - sg[j0].n0) * sg[j0].step) >> kWarpFB;
     const int64_t i_hi = (sg[j1].pos0 + (n_last - sg[j1].n0) * sg[j1].step) >> kWarpFB;
@@ -112,10 +115,10 @@ __global__ void __launch_bounds__(kWarpBlock) warp_kernel(WarpArgs a) {
     yrow[n] = v;
 }
 
-// launch over output samples [0, a.n_hi) of B rows
+// launch over output samples [a.n_lo, a.n_hi) of B rows
 inline hipError_t launch_warp(const WarpArgs &a, int B, hipStream_t st) {
-    if (B <= 0 || a.n_hi <= 0) return hipSuccess;
-    const dim3 grid((unsigned)(((int64_t)a.n_hi + kWarpBlock - 1) / kWarpBlock), (unsigned)B);
+    if (B <= 0 || a.n_hi <= a.n_lo || a.n_lo < 0) return hipSuccess;
+    const dim3 grid((unsigned)(((int64_t)a.n_hi - a.n_lo + kWarpBlock - 1) / kWarpBlock), (unsigned)B);
     warp_kernel<<<grid, kWarpBlock, 0, st>>>(a);
     return hipGetLastError();
 }
@@ -135,15 +138,17 @@ __global__ void __launch_bounds__(kWarpBlock) glide_kernel(GlideArgs a) {
     __shared__ float gs[kWarpTable];
     const int b = blockIdx.y;
     const WarpRow r = a.rows[b];
-    const int64_t n0 = (int64_t)blockIdx.x * kWarpBlock, n = n0 + threadIdx.x;
+    const int64_t n0 = a.n_lo + (int64_t)blockIdx.x * kWarpBlock, n = n0 + threadIdx.x;
     const float *xrow = a.x + (int64_t)b * a.x_pitch;
-    float *yrow = a.y + (int64_t)b * a.y_pitch;
+    float *yrow = a.y + (int64_t)b * a.y_pitch - a.n_lo;  // indexed by n
     if (n0 >= r.n_out || r.identity || r.n_segs <= 0) {  // behind the row's end: zeros; an identity row: its valid samples
         if (n < a.n_hi) yrow[n] = (r.identity && n < r.n_out && n < r.n_in) ? xrow[n] : 0.f;
         return;
     }
     const vits_glide_seg *sg = a.segs + r.seg0;
-    const int64_t n_last = (n0 + kWarpBlock < r.n_out ? n0 + kWarpBlock : (int64_t)r.n_out) - 1;
+    // the tile's last sample: clipped by the row and by the window, so that nothing behind the window's last position is staged
+    const int64_t n_end = n0 + kWarpBlock < a.n_hi ? n0 + kWarpBlock : (int64_t)a.n_hi;
+    const int64_t n_last = (n_end < r.n_out ? n_end : (int64_t)r.n_out) - 1;
     const int j0 = warp_find(sg, r.n_segs, n0), j1 = warp_find(sg, r.n_segs, n_last);
     const int64_t i_lo = glide_pos(sg[j0].pos0, sg[j0].k, sg[j0].step0, sg[j0].step1, n0 - sg[j0].n0) >> kWarpFB;
     const int64_t i_hi = glide_pos(sg[j1].pos0, sg[j1].k, sg[j1].step0, sg[j1].step1, n_last - sg[j1].n0) >> kWarpFB;
@@ -178,8 +183,8 @@ __global__ void __launch_bounds__(kWarpBlock) glide_kernel(GlideArgs a) {
 }
 
 inline hipError_t launch_glide(const GlideArgs &a, int B, hipStream_t st) {
-    if (B <= 0 || a.n_hi <= 0) return hipSuccess;
-    const dim3 grid((unsigned)(((int64_t)a.n_hi + kWarpBlock - 1) / kWarpBlock), (unsigned)B);
+    if (B <= 0 || a.n_hi <= a.n_lo || a.n_lo < 0) return hipSuccess;
+    const dim3 grid((unsigned)(((int64_t)a.n_hi - a.n_lo + kWarpBlock - 1) / kWarpBlock), (unsigned)B);
     glide_kernel<<<grid, kWarpBlock, 0, st>>>(a);
     return hipGetLastError();
 }

@@ -281,4 +281,88 @@ inline std::string glide_segs_fault(const vits_glide_seg *segs, int64_t n_segs) 
     return "";
 }
 
+// ---- streamed pitch (include/vitsmi.h, "streamed pitch"): which output samples exist once input samples [0, X) do
+
+// Q16 input position of sample j of a record, by the closed form of its family
+VITSMI_HD inline int64_t warp_seg_pos(const vits_warp_seg &g, int64_t j) { return g.pos0 + j * (int64_t)g.step; }
+VITSMI_HD inline int64_t warp_seg_pos(const vits_glide_seg &g, int64_t j) { return glide_pos(g.pos0, g.k, g.step0, g.step1, j); }
+
+// Q16 input position of output sample n (0 <= n < N) of a row; a row without a record is the masked copy: n itself
+template <class Seg>
+inline int64_t warp_row_pos(const Seg *segs, int64_t n_segs, int64_t n) {
+    if (n_segs <= 0) return n << kWarpFB;
+    int64_t lo = 0, hi = n_segs - 1;  // the last record whose n0 <= n, as warp_find on the device
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if (segs[mid].n0 <= n) lo = mid;
+        else hi = mid - 1;
+    }
+    return warp_seg_pos(segs[lo], n - segs[lo].n0);
+}
+
+// ready_b(X): how many n < N have (pos_n >> FB) + kWarpMaxHalf < X - every input a tile stages for them exists.  Positions never
+// decrease along a row, so it is a prefix count: bisection over n.
+template <class Seg>
+inline int64_t warp_ready(const Seg *segs, int64_t n_segs, int64_t N, int64_t X) {
+    int64_t lo = 0, hi = N;  // samples [0, lo) are ready, sample hi (if any) is not
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if ((warp_row_pos(segs, n_segs, mid) >> kWarpFB) + kWarpMaxHalf < X) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// ... and what the row admits: a row whose n_in valid inputs all exist (X >= n_in) is complete - N
+template <class Seg>
+inline int64_t warp_emit_row(const Seg *segs, int64_t n_segs, int64_t n_in, int64_t N, int64_t X) {
+    return X >= n_in ? N : warp_ready(segs, n_segs, N, X);
+}
+
+// e(X) of a launch's rows: the least ready count among the rows still short of input; S_w without one, or on the last piece
+template <class Seg>
+inline int64_t warp_emit_end(const Seg *segs, const std::vector<WarpRow> &rows, int64_t S_w, int64_t X, bool is_last) {
+    int64_t e = S_w;
+    if (is_last) return e;
+    for (const WarpRow &r : rows) {
+        if (X >= r.n_in) continue;
+        const int64_t q = warp_ready(segs + r.seg0, r.n_segs, r.n_out, X);
+        e = q < e ? q : e;
+    }
+    return e;
+}
+
+// n_cap: output samples one delivery of a streamed run holds at most.  A piece of `piece_in` input samples moves every position's
+// bound by that much, which at the least step ONE / 2 completes 2 * piece_in outputs, and the uniform kWarpMaxHalf of the rule may
+// fall on either side of it: 2 * (piece_in + kWarpMaxHalf).  Longer ranges - a slow row's end releasing the others - are cut.
+inline int64_t warp_stream_cap(int64_t piece_in, int64_t S_w) {
+    const int64_t cap = 2 * (piece_in + kWarpMaxHalf);
+    return cap < S_w ? cap : S_w;
+}
+
+// The plans of a batch from the durations [B][T] (any arithmetic type: frames) and the rows' valid input samples: plan_row plans
+// one row into its records.  segs / first / spans [B][T] / rows are filled; returns "" or "row b, ..." - what is wrong.
+template <class Seg, class Dur, class PlanRow>
+inline std::string warp_plan_rows(const Dur *durations, const int64_t *lens, const int64_t *n_in, int B, int T, int hop, PlanRow plan_row,
+                                  std::vector<Seg> &segs, std::vector<int32_t> &first, std::vector<int64_t> &spans, std::vector<WarpRow> &rows,
+                                  int64_t &S_w) {
+    segs.clear();
+    first.assign((size_t)B + 1, 0);
+    spans.assign((size_t)B * T, 0);
+    std::vector<int64_t> dur((size_t)T);
+    for (int b = 0; b < B; b++) {
+        const int L = (int)lens[b];
+        for (int t = 0; t < L; t++) dur[t] = (int64_t)durations[(size_t)b * T + t];
+        const size_t at = segs.size();
+        segs.resize(at + (size_t)L);
+        int64_t ns = 0, N = 0;
+        const std::string e = plan_row(b, dur.data(), L, hop, segs.data() + at, spans.data() + (size_t)b * T, ns, N);
+        if (!e.empty()) return "row " + std::to_string(b) + ", " + e;
+        segs.resize(at + (size_t)ns);
+        first[(size_t)b + 1] = (int32_t)segs.size();
+    }
+    S_w = warp_rows(segs.data(), first.data(), n_in, B, rows);
+    return "";
+}
+
 }  // namespace vitsmi

@@ -381,6 +381,35 @@ inline WarpBufs carve_warp(Carver &cv, int B, int S_w, int64_t n_segs) {
     return w;
 }
 
+// A streamed run with pitch (vits_run_chunked_glided, "streamed pitch") has these in front of carve_stream's in the same walk:
+// the history - the run's native waveform [B][row_in], appended to piece by piece: rows at different speeds need different
+// amounts of past input, without `compensate` unboundedly much -, the output of one windowed launch [B][n_cap], the rows'
+// output counts (what the pack stage masks by) and the plan block of carve_warp.  vits_reserve does not count it.
+struct WarpStreamBufs {
+    float *hist;
+    int64_t hist_pitch;
+    float *out;
+    int *n_out;
+    vits_warp_seg *segs;
+    WarpRow *rows;
+    size_t plan_bytes;  // segs | rows
+};
+
+inline WarpStreamBufs carve_warp_stream(Carver &cv, int B, int64_t row_in, int64_t n_cap, int64_t n_segs) {
+    WarpStreamBufs w{};
+    w.hist_pitch = row_in;
+    w.hist = cv.take<float>((size_t)B * row_in);
+    w.out = cv.take<float>((size_t)B * n_cap);
+    w.n_out = cv.take<int>(B);
+    w.plan_bytes = (size_t)n_segs * sizeof(vits_warp_seg) + (size_t)B * sizeof(WarpRow);
+    char *p = cv.take<char>(w.plan_bytes);
+    if (p) {
+        w.segs = reinterpret_cast<vits_warp_seg *>(p);
+        w.rows = reinterpret_cast<WarpRow *>(p + (size_t)n_segs * sizeof(vits_warp_seg));
+    }
+    return w;
+}
+
 // The buffers of ONE delivery call, whichever entry it came through, and the one walk that carves them: the delivery's own
 // (carved here, or - `front` - those a carve_resample in the same walk has just carved behind the resampled waveform), then
 // what the call's stages need, in this order: the trim slots of a call that scans (every one but vits_deliver), the level

@@ -250,6 +250,14 @@ def _contour(token_semitones, token_semitones_end, lens, B, T):
     return (np.zeros((B, T), np.float32) if st0 is None else st0), st1
 
 
+def _pitched(semitones, semitones_end, lens) -> bool:
+    """does a run with these (start, end) values of _contour warp at all - some value in front of lens[b] that is not 0"""
+    if semitones is None:
+        return False
+    live = np.arange(semitones.shape[1])[None, :] < np.asarray(lens)[:, None]
+    return bool((live & ((semitones != 0) | (False if semitones_end is None else (semitones_end != 0)))).any())
+
+
 def token_span_bounds(spans, count) -> np.ndarray:
     """token_bounds of a warped row: the boundaries of its tokens in delivered samples from the warp's own spans (k per
     token, last_token_spans()) -> int64 [len(spans) + 1]; a row's last boundary is its count N."""
@@ -1296,7 +1304,8 @@ class MiSession:
             t.join()
 
     def synthesize_stream(self, ids, lens, scales, sid=None, chunk_frames: int = 64, noise_dp=None, noise_z=None,
-                          seeds=None, durations=None, token_rate=None):
+                          seeds=None, durations=None, token_rate=None, token_semitones=None, compensate=True,
+                          token_semitones_end=None):
         """The whole path with the waveform delivered in chunks of `chunk_frames` frames (hop samples each): yields
         (first_sample, float32 [B, n], total_samples).  Concatenated, the chunks are bit-identical to
         synthesize_batch(...)["output"][:, 0, 0, :]; frame counts afterwards from last_y_lengths().  Chunks are handed out
@@ -1304,10 +1313,15 @@ class MiSession:
         RangeError at the end (no bf16x6 fallback here; reopen with gen_precision="bf16x6").  Closing the generator
         early stops the engine after the chunk in flight.  scales [3] or [B, 3], seeds, durations and token_rate as
         synthesize_batch.  The consumer may call last_durations() - like last_y_lengths() - from the first chunk on: the
-        timing of the whole utterance is known before most of its audio exists."""
+        timing of the whole utterance is known before most of its audio exists.
+        token_semitones, compensate, token_semitones_end - as synthesize_batch (vitsmi.h, "streamed pitch"): the chunks, joined,
+        are that run's warped "output"; their ranges lie on the warped timeline and follow what the rows' plans have completed -
+        a chunk of the run may deliver nothing, or several ranges -, total_samples is the longest warped row, and
+        last_sample_counts() / last_token_spans() answer from the first chunk on.  Not covered with an output rate set."""
         ids = np.ascontiguousarray(ids, np.int64)
         lens = np.ascontiguousarray(lens, np.int64)
         B, T = ids.shape
+        semitones, semitones_end = _contour(token_semitones, token_semitones_end, lens, B, T)
         scales, seeds = _settings(np.ascontiguousarray(scales, np.float32), B, seeds)
         durations, token_rate = _timing(durations, token_rate, lens, B, T)
         sid = None if sid is None else np.ascontiguousarray(sid, np.int64)
@@ -1323,6 +1337,15 @@ class MiSession:
             keep.append(np.ascontiguousarray(noise_z, np.float32))
             noise.noise_z = keep[-1].ctypes.data
             noise.noise_z_stride = keep[-1].shape[2]
+        if semitones is not None:
+            self._pitch_admit("synthesize_stream", durations, compensate, semitones, semitones_end, lens)
+            ctl = _controls(_rows(scales, B), seeds, durations, token_rate)
+            contour = _ffi.VitsContour(semitones.ctypes.data, None if semitones_end is None else semitones_end.ctypes.data,
+                                       1 if compensate else 0)
+            contour._keep = (semitones, semitones_end)
+            return self._stream(lambda cb: self._lib.vits_run_chunked_glided(
+                self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(sid), C.byref(noise), C.byref(ctl), C.byref(contour),
+                int(chunk_frames), cb, None))
         if durations is not None or token_rate is not None:
             rows = _rows(scales, B)
             ctl = _controls(rows, seeds, durations, token_rate)
@@ -1371,7 +1394,8 @@ class MiSession:
 
     def synthesize_stream_encoded(self, ids, lens, scales, sid=None, chunk_frames: int = 64, encoding="pcm16", ref_peak=None,
                                   volume=None, noise_dp=None, noise_z=None, seeds=None, durations=None, token_rate=None,
-                                  shapes=None, token_gain_db=None, gain_ramp=0.01, limit=None, onsets=None):
+                                  shapes=None, token_gain_db=None, gain_ramp=0.01, limit=None, onsets=None, token_semitones=None,
+                                  compensate=True, token_semitones_end=None):
         """synthesize_stream with every chunk post-processed, encoded and masked to each row's own length on the device
         (vitsmi.h, "encoded streaming"): yields EncodedChunk.  encoding "pcm16" / "ulaw" / "alaw" / "f32"; `volume` and
         `ref_peak` None, a scalar or [B]: row b is scaled by volume[b] and - with ref_peak - normalised by ref_peak[b] (a
@@ -1389,12 +1413,19 @@ class MiSession:
         onsets (one Onset or one per row, None for a row that is not trimmed) cuts the leading silence of every row on the
         device (vitsmi.h, "trimmed streaming"): EncodedChunk.skip[b] elements of row b lie in front of its kept range; fades
         and limiter count from there, and data[b, skip[b]:valid[b]], joined, is what the delivery gives under the equivalent
-        Trim.  The chunk ranges do not change."""
+        Trim.  The chunk ranges do not change.
+        token_semitones, compensate, token_semitones_end - as synthesize_stream (vitsmi.h, "streamed pitch"): everything above
+        then works on the warped audio - valid counts, fades and the limiter by each row's warped length, token_gain_db's
+        breakpoints on the warp's own token spans -, and every chunk carries `skip` (zeros without onsets): data[b,
+        skip[b]:valid[b]], joined, is what synthesize_delivered(token_semitones=...) gives for the row."""
         ids = np.ascontiguousarray(ids, np.int64)
         lens = np.ascontiguousarray(lens, np.int64)
         B, T = ids.shape
+        semitones, semitones_end = _contour(token_semitones, token_semitones_end, lens, B, T)
+        if semitones is not None:
+            self._pitch_admit("synthesize_stream_encoded", durations, compensate, semitones, semitones_end, lens)
         fmt, dtype = _stream_format(encoding, ref_peak, volume, B)
-        shaping = self._stream_plan(shapes, token_gain_db, gain_ramp, limit, lens, B, T)
+        shaping = self._stream_plan(shapes, token_gain_db, gain_ramp, limit, lens, B, T, semitones, semitones_end)
         scales, seeds = _settings(np.ascontiguousarray(scales, np.float32), B, seeds)
         durations, token_rate = _timing(durations, token_rate, lens, B, T)
         sid = None if sid is None else np.ascontiguousarray(sid, np.int64)
@@ -1411,6 +1442,18 @@ class MiSession:
             noise.noise_z_stride = keep[-1].shape[2]
         ctl = _controls(_rows(scales, B), seeds, durations, token_rate)
         trim = _stream_onsets(onsets, B)
+        if semitones is not None:
+            if shaping is not None:
+                self._shaping_check(shaping, fmt, B)
+            if trim is not None:
+                self._onsets_check(trim, fmt, B)
+            contour = _ffi.VitsContour(semitones.ctypes.data, None if semitones_end is None else semitones_end.ctypes.data,
+                                       1 if compensate else 0)
+            contour._keep = (semitones, semitones_end)
+            return self._stream(lambda cb: self._lib.vits_run_chunked_enc_glided(
+                self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(sid), C.byref(noise), C.byref(ctl), C.byref(fmt),
+                None if shaping is None else C.byref(shaping), trim, C.byref(contour), int(chunk_frames), cb, None),
+                self._trimmed_items(dtype))
         if trim is not None:  # (passed down only when asked for)
             if shaping is not None:
                 self._shaping_check(shaping, fmt, B)
@@ -1427,12 +1470,22 @@ class MiSession:
             self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(sid), C.byref(noise), C.byref(ctl), C.byref(fmt),
             C.byref(shaping), int(chunk_frames), cb, None), self._encoded_items(dtype))
 
+    def _pitch_admit(self, name, durations, compensate, semitones, semitones_end, lens):
+        """what the engine refuses of a stream with pitch, raised by the call itself: nothing was started (all zeros: the
+        unwarped stream, which refuses nothing)"""
+        if not _pitched(semitones, semitones_end, lens):
+            return
+        if self.resampling or self.output_rates is not None:
+            raise SessionError(f"{name}(token_semitones=...) is not covered with an output rate set")
+        if compensate and durations is not None:
+            raise SessionError("compensate and forced durations are contradictory: forced durations are the rendered ones")
+
     def _shaping_check(self, shaping, fmt, B):
         """a shaping the engine would refuse up front raises here, by the call itself: nothing was started"""
         if self._lib.vits_stream_shaping_check(C.byref(shaping), C.byref(fmt), B) != 0:
             raise SessionError(f"shaped stream refused: {_ffi.last_error(None)}")
 
-    def _stream_plan(self, shapes, token_gain_db, gain_ramp, limit, lens, B, T):
+    def _stream_plan(self, shapes, token_gain_db, gain_ramp, limit, lens, B, T, semitones=None, semitones_end=None):
         """_stream_shaping with the plan callback of a per-token volume: the callback builds every row's envelope from the
         run's own durations and sample counts (token_bounds / token_envelope: what synthesize_delivered(token_gain_db=)
         computes between its run and its delivery) and hands the engine the shapes that carry them."""
@@ -1454,13 +1507,19 @@ class MiSession:
             ratio = resample_plan(self.input_rate or int(self.meta("sample_rate") or 22050), self.output_rate)[:2]
         ramp = int(self.delivered_rate * float(gain_ramp))
         keep = shaping._keep
+        pitched = _pitched(semitones, semitones_end, lens)
 
         @_ffi.STREAM_PLAN_FN
         def plan(user, Bc, Tc, dur, counts, inout):
             try:
                 d = np.ctypeslib.as_array(dur, shape=(Bc * Tc,)).reshape(Bc, Tc)
                 n = np.ctypeslib.as_array(counts, shape=(Bc,))
-                bounds = [token_bounds(d[b], lens[b], hop, n[b], ratio) for b in range(Bc)]
+                if pitched:  # the boundaries are the warp's: the host plan over THIS run's durations (counts are its N_b)
+                    plans = [warp_plan(d[b, :lens[b]], semitones[b, :lens[b]], hop) if semitones_end is None else
+                             glide_plan(d[b, :lens[b]], semitones[b, :lens[b]], semitones_end[b, :lens[b]], hop) for b in range(Bc)]
+                    bounds = [token_span_bounds(plans[b][1], n[b]) for b in range(Bc)]
+                else:
+                    bounds = [token_bounds(d[b], lens[b], hop, n[b], ratio) for b in range(Bc)]
                 used = token_gain_shapes([Segment(b) for b in range(Bc)], base, tgains, bounds, ramp)
                 arr, points, n_points = _shapes(used, Bc)
                 keep.extend([arr, points])
@@ -2942,6 +3001,69 @@ def test_glide(x, counts, row_segs, device_id=0):
     if rc != 0:
         raise SessionError(f"vits_test_glide failed [{rc}]: {_ffi.last_error(None)}")
     return y
+
+
+def _emit_end(fn, segs, n_in, n_out, X):
+    ready = C.c_int64()
+    rc = getattr(_ffi.load(), fn)(segs, len(segs), int(n_in), int(n_out), int(X), C.byref(ready))
+    if rc != 0:
+        raise SessionError(f"{fn} failed [{rc}]: {_ffi.last_error(None)}")
+    return ready.value
+
+
+def warp_emit_end(segs, n_in, n_out, X):
+    """The emit rule of one row (vits_warp_emit_end: pure host code; vitsmi.h, "streamed pitch"): segs a ctypes array of
+    _ffi.VitsWarpSeg (warp_plan's), n_in / n_out the row's valid input and output samples -> how many output samples exist
+    once input samples [0, X) do (n_out where X >= n_in)."""
+    return _emit_end("vits_warp_emit_end", segs, n_in, n_out, X)
+
+
+def glide_emit_end(segs, n_in, n_out, X):
+    """warp_emit_end over _ffi.VitsGlideSeg records (glide_plan's)"""
+    return _emit_end("vits_glide_emit_end", segs, n_in, n_out, X)
+
+
+def warp_stream_cap(piece_samples, S_w):
+    """n_cap: the output samples one delivery of a streamed run with pitch holds at most (vits_warp_stream_cap)"""
+    cap = _ffi.load().vits_warp_stream_cap(int(piece_samples), int(S_w))
+    if cap < 0:
+        raise SessionError(f"vits_warp_stream_cap failed [{cap}]: {_ffi.last_error(None)}")
+    return int(cap)
+
+
+def _test_pieces(fn, seg_type, x, counts, row_segs, piece_bounds, device_id):
+    x = np.ascontiguousarray(x, np.float32)
+    counts = np.ascontiguousarray(counts, np.int64)
+    bounds = np.ascontiguousarray(piece_bounds, np.int64)
+    if x.ndim != 2 or counts.shape != (x.shape[0],) or len(row_segs) != x.shape[0] or bounds.ndim != 1 or not len(bounds):
+        raise SessionError(f"x must be [B, S], counts [B], row_segs B sequences and piece_bounds [P], got {x.shape} / {counts.shape} / "
+                           f"{len(row_segs)} / {bounds.shape}")
+    B, S = x.shape
+    flat = [g for row in row_segs for g in row]
+    first = np.cumsum([0] + [len(row) for row in row_segs]).astype(np.int32)
+    segs = (seg_type * max(len(flat), 1))(*flat)
+    n_out = [int(row[-1].n0 + row[-1].k) if len(row) else int(min(max(counts[b], 0), S)) for b, row in enumerate(row_segs)]
+    S_w = max(1, max(n_out))
+    y = np.full((B, S_w), np.nan, np.float32)
+    cap = len(bounds) + S_w + 2  # (more windows than any schedule has)
+    ranges = np.zeros((cap, 2), np.int64)
+    rc = getattr(_ffi.load(), fn)(device_id, _ffi.ptr(x), _ffi.ptr(counts), B, S, segs, _ffi.ptr(first), _ffi.ptr(bounds), len(bounds),
+                                  _ffi.ptr(y), S_w, _ffi.ptr(ranges), cap)
+    if rc < 0:
+        raise SessionError(f"{fn} failed [{rc}]: {_ffi.last_error(None)}")
+    return y, ranges[:rc]
+
+
+def test_warp_pieces(x, counts, row_segs, piece_bounds, device_id=0):
+    """The streamed warp by value (vits_test_warp_pieces): test_warp's arguments with the input cut at piece_bounds (ascending
+    piece ends, the last one S) and sent through the pipeline's stage -> (y float32 [B, S_w]: the windows joined, ranges
+    int64 [calls, 2]: {first, n} of every window in order)."""
+    return _test_pieces("vits_test_warp_pieces", _ffi.VitsWarpSeg, x, counts, row_segs, piece_bounds, device_id)
+
+
+def test_glide_pieces(x, counts, row_segs, piece_bounds, device_id=0):
+    """test_warp_pieces over rows of _ffi.VitsGlideSeg (glide_plan's)"""
+    return _test_pieces("vits_test_glide_pieces", _ffi.VitsGlideSeg, x, counts, row_segs, piece_bounds, device_id)
 
 
 def test_resample_pieces(x, lens, in_rate, out_rate, piece_samples, device_id=0):

@@ -893,14 +893,27 @@ class TTSVoice:
         limiter start there.  A stream keeps as much of keep_lead as it has not handed over yet: with keep_lead <=
         limit_lookahead, or an onset within the first chunk, the bytes are synthesize_encoded's under the same leading trim.
         The trailing silence stays: a stream learns where its audio ends only at the end.
-        phoneme_pitch and pitch_contour are refused (ValueError): the chunked entries have no warped form."""
+        phoneme_pitch and pitch_contour have the meanings and refusals of synthesize_encoded, for every sentence (vitsmi.h,
+        "streamed pitch"): the sentences are warped and glided piece by piece on the device - joined, still
+        synthesize_encoded's bytes.  They need a session whose synthesize_stream_encoded takes token_semitones /
+        token_semitones_end (ValueError otherwise: such a session's chunked entries have no warped form) and are refused with
+        an output rate set."""
+        import inspect
         from . import audio_encoding as ae
+        fn = getattr(self.session, "synthesize_stream_encoded", None)
+        takes = inspect.signature(fn).parameters if fn is not None else {}
         if pitch_contour is not None:
-            raise ValueError("pitch_contour is not covered by stream_encoded: the chunked entries have no warped form "
-                             "(synthesize_encoded takes it)")
+            if "token_semitones_end" not in takes:
+                raise ValueError("pitch_contour is not covered by stream_encoded: the chunked entries have no warped form "
+                                 "(synthesize_encoded takes it)")
+            if self._ratio() is not None:
+                raise ValueError("pitch_contour is not covered with an output rate set")
         if phoneme_pitch is not None:
-            raise ValueError("phoneme_pitch is not covered by stream_encoded: the chunked entries have no warped form "
-                             "(synthesize_encoded takes it)")
+            if "token_semitones" not in takes:
+                raise ValueError("phoneme_pitch is not covered by stream_encoded: the chunked entries have no warped form "
+                                 "(synthesize_encoded takes it)")
+            if self._ratio() is not None:
+                raise ValueError("phoneme_pitch is not covered with an output rate set")
         cfg = syn_config if syn_config is not None else SynthesisConfig()
         ae._check(encoding)
         lead = self._lead_samples(sentence_silence)
@@ -914,7 +927,8 @@ class TTSVoice:
                              "normalize_audio off")
         if int(chunk_frames) < 1:
             raise ValueError(f"chunk_frames must be >= 1 (got {chunk_frames})")
-        return self._stream_encoded(text, cfg, encoding, int(chunk_frames), lead, ref_peak, shape, phoneme_gain_db, limit, onset)
+        return self._stream_encoded(text, cfg, encoding, int(chunk_frames), lead, ref_peak, shape, phoneme_gain_db, limit, onset,
+                                    phoneme_pitch, pitch_contour)
 
     def _onset(self, trim_silence, cfg, ref_peak):
         """trim_silence of stream_encoded -> a session.Onset in samples at the delivered rate, or None.  A float is a threshold
@@ -938,14 +952,20 @@ class TTSVoice:
         return o if o.mode else None
 
     def _stream_encoded(self, text, cfg, encoding, chunk_frames, lead, ref_peak, shape=None, phoneme_gain_db=None, limit=None,
-                        onset=None):
+                        onset=None, phoneme_pitch=None, pitch_contour=None):
         from . import audio_encoding as ae
         from .sharding import pad_batch
-        token_db = None
-        if phoneme_gain_db is not None:
+        token_db = token_st = token_st_end = None
+        pitched = phoneme_pitch is not None or pitch_contour is not None
+        if phoneme_gain_db is not None or pitched:
             groups = self._sentence_groups(text, cfg)
             all_ids = [[i for _, ids in g for i in ids] for g in groups]
-            token_db = [self._group_db(phoneme_gain_db, k, g) for k, g in enumerate(groups)]
+            if phoneme_gain_db is not None:
+                token_db = [self._group_db(phoneme_gain_db, k, g) for k, g in enumerate(groups)]
+            if pitched:
+                pairs = [self._sentence_semitones(phoneme_pitch, pitch_contour, k, g) for k, g in enumerate(groups)]
+                token_st = [a for a, _ in pairs]
+                token_st_end = None if pitch_contour is None else [b for _, b in pairs]
         else:
             all_ids = self._sentence_ids(text, cfg)
         B = len(all_ids)
@@ -1004,6 +1024,10 @@ class TTSVoice:
                 more["limit"] = limit
             if onset is not None:
                 more["onsets"] = onset
+            if token_st is not None:
+                more["token_semitones"] = self._padded_db(token_st)
+            if token_st_end is not None:
+                more["token_semitones_end"] = self._padded_db(token_st_end)
 
             def skipped(c, b):  # (a stream that is not trimmed has nothing to skip)
                 skip = getattr(c, "skip", None)
