@@ -1131,6 +1131,69 @@ int vits_run_chunked_enc_glided(vits_handle *h, const int64_t *ids, const int64_
                                 const vits_stream_shaping *shaping, const vits_stream_onset *onsets, const vits_contour *contour,
                                 int chunk_frames, vits_enc_chunk_trim_fn fn, void *user);
 
+/* ---- fitted durations: speech fitted to a requested number of frames --------------------------
+ * SSML's <prosody duration>: a line that has to fill, or stay within, a slot.  The model's own rule is
+ * d_t = ceil(w_t * length_scale); a fit keeps the rule and looks for THE MULTIPLIER s AT WHICH THE RULE'S OWN FRAME COUNT IS
+ * THE TARGET (Adams' apportionment): a fitted run is what the model renders at another length scale, not a proportional
+ * rounding with a bias of its own.  Everything behind w is IEEE double and integers, so host, device and a NumPy restatement
+ * (tests/fit_ref.py) agree on every bit.
+ *
+ * Weights.  w_t is the fp32 value the duration kernel hands to ceilf, ((expf(logw) * mask) * length_scale[b]) * token_rate[b][t]
+ *   in this order, 0 behind lens[b].  Cleaned: a value that is not finite or not > 0 counts as 0, a value above 2^24 as 2^24.
+ * Count.  count_g(s) = sum over the rows b of group g, t < lens[b], of (int64) ceil((double) w_t * s): one double product,
+ *   nothing fused into it; the sum is an integer sum, so its order is free.
+ * Range.  S = the doubles of [2^-4, 2^4] (positive doubles order like their bit patterns).
+ * Groups.  A group is a set of rows of one run that share one s and one target F, the sum of the group's token durations: one
+ *   sentence is a group of one row, a text of several sentences rendered as one batch is one group.  Rows of no group
+ *   (group[b] = -1) keep what the duration kernel gave them.
+ * Mode 1 (exact).  count(2^-4) > F: s* = 2^-4, durations ceil(w s*), VITS_FIT_FLOOR.  Otherwise s* = the largest s of S with
+ *   count(s) <= F.  s* = 2^4 and count < F: VITS_FIT_CEIL, nothing more is handed out.  Otherwise R = F - count(s*); the
+ *   candidates are the tokens with ceil(w s+) > ceil(w s*), s+ the next double, and the first R of them - ascending row, then
+ *   ascending t - take one more frame: VITS_FIT_MET, the group's durations sum to F exactly.  (With w <= 2^24 and s <= 16 one
+ *   ulp of s moves a product by less than 2^-25: no token gains two frames between s* and s+, and there are more than R
+ *   candidates.)
+ * Mode 2 (at most).  count(1.0) <= F: s* = 1.0, durations ceil(w), VITS_FIT_KEPT.  Otherwise mode 1.
+ * Per row, as ever: y_len = max(1, row sum), cum the inclusive prefix sums, w_ceil the durations as float.
+ * A target equal to the free run's own count reproduces the free run's durations token for token.  A VITS_FIT_FLOOR outcome is
+ * not capped (as a free run is not): its rows are as long as ceil(w / 16) makes them.
+ *
+ * vits_fit: group host int32 [B] in [-1, n_groups), target_frames host int64 [n_groups], mode host int32 [n_groups].  Checked
+ * on the host before anything is enqueued or allocated - VITS_E_ARG naming the group or row and the value, the previous run
+ * stays readable: 1 <= F <= min(VITS_MAX_FORCED_FRAMES, INT_MAX / hop); mode in {1, 2}; group ids in [-1, n_groups); no group
+ * without rows; ctl->durations together with a fit (contradictory); a host-only handle, behind those.
+ * vits_run_async_fitted / vits_run_chunked_fitted / vits_run_chunked_enc_fitted are vits_run_async_ctl / vits_run_chunked_ctl /
+ * vits_run_chunked_enc_trimmed with a fit: with fit == NULL or every row at -1 each IS that entry - the same bits, the same
+ * launches.  A fitted run launches the duration kernel as ever, then one elementwise kernel that writes w and one workgroup
+ * per group that overwrites the fitted rows; the per-group results ride in the one mid-run readback, [w_ceil | y_len | fit]:
+ * no copy and no synchronisation is added.  vits_tap "w" answers the [B][T] weights after a fitted run ("not computed"
+ * after any other).  vits_last_fit: s*, the achieved frames and the status per group of the last run, from host state, valid
+ * as soon as the run call returns and from a chunked run's first callback (or its plan callback) on; writes min(n, G) values
+ * per array (each may be NULL), returns G; VITS_E_ARG after a run without a fit.
+ * vits_fit_plan: the plan without a handle - weights host fp32 [B][T], lens [B] in [0, T]; durations int64 [B][T] (fitted rows
+ * only: 0 behind lens[b]; rows of no group are not written), scale / frames / status [n_groups] (each may be NULL).  Targets
+ * are bounded by VITS_MAX_FORCED_FRAMES here.
+ * Out of scope: a fit together with semitones or contours (no fitted form of the warped and glided entries); tokens exempt
+ * from the fit; groups that span runs; the device-pointer entries; the vocoder-only entries. */
+enum { VITS_FIT_MET = 0, VITS_FIT_FLOOR = 1, VITS_FIT_CEIL = 2, VITS_FIT_KEPT = 3 };
+typedef struct {
+    const int32_t *group;           /* host [B]: the row's group, or -1 */
+    int n_groups;
+    const int64_t *target_frames;   /* host [n_groups] */
+    const int32_t *mode;            /* host [n_groups]: 1 exact, 2 at most */
+} vits_fit;
+int vits_fit_plan(const float *w, const int64_t *lens, int B, int T, const vits_fit *fit, int64_t *durations, double *scale,
+                  int64_t *frames, int32_t *status);
+int vits_run_async_fitted(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
+                          const vits_noise *noise, const vits_controls *ctl, const vits_fit *fit);
+int vits_run_chunked_fitted(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
+                            const vits_noise *noise, const vits_controls *ctl, const vits_fit *fit, int chunk_frames,
+                            vits_chunk_fn fn, void *user);
+int vits_run_chunked_enc_fitted(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
+                                const vits_noise *noise, const vits_controls *ctl, const vits_stream_format *fmt,
+                                const vits_stream_shaping *shaping, const vits_stream_onset *onsets, const vits_fit *fit,
+                                int chunk_frames, vits_enc_chunk_trim_fn fn, void *user);
+int vits_last_fit(vits_handle *h, double *scale, int64_t *frames, int32_t *status, int n);
+
 /* Size the handle's device workspaces NOW for requests of up to B utterances x T tokens that render up to F frames each
  * (the batch's longest utterance; T = 0 or F = 0 leaves that domain alone).  A run grows a workspace when a request
  * needs more than any before it - hipFree + hipMalloc of tens of GB at batch 32, a device-wide synchronisation that was
@@ -1428,6 +1491,10 @@ int vits_test_glide_pieces(int device_id, const float *x, const int64_t *counts,
  * lens [B] within [0, T].  Out: w_ceil [B][T], cum int32 [B][T] (inclusive running sum), y_len int32 [B] (max(sum, 1)). */
 int vits_test_durations(int device_id, const float *logw, const int64_t *dur, const int64_t *lens, int B, int T, float length_scale,
                         const float *rows, const float *token_rate, float *w_ceil, int32_t *cum, int32_t *y_len);
+/* The fit kernel ("fitted durations") over weights w [B][T]: w_ceil / cum / y_len come in holding what the caller wants
+ * rows of no group to keep (they are uploaded, the kernel runs, they are downloaded), scale / frames / status [n_groups]. */
+int vits_test_fit_durations(int device_id, const float *w, const int64_t *lens, int B, int T, const vits_fit *fit, float *w_ceil,
+                            int32_t *cum, int32_t *y_len, double *scale, int64_t *frames, int32_t *status);
 /* Length regulator and prior sample: m_logs [B][2C][T] (m_p in the first C channels, logs_p in the second), cum / y_len as
  * vits_test_durations leaves them (y_len[b] <= F), noise (nullable) [B][C][noise_stride] of which the first noise_frames
  * <= noise_stride frames are read (zeros behind), else seeds (nullable) uint64 [B]: stream 2 of each utterance; noise_scale

@@ -88,6 +88,14 @@ class VitsControls(C.Structure):
     _fields_ = [("scales_rows", C.c_void_p), ("seeds", C.c_void_p), ("durations", C.c_void_p), ("token_rate", C.c_void_p)]
 
 
+class VitsFit(C.Structure):
+    """vits_fit (vitsmi.h, "fitted durations"): group int32 [B], target_frames int64 [n_groups], mode int32 [n_groups]"""
+    _fields_ = [("group", C.c_void_p), ("n_groups", C.c_int), ("target_frames", C.c_void_p), ("mode", C.c_void_p)]
+
+
+VITS_FIT_MET, VITS_FIT_FLOOR, VITS_FIT_CEIL, VITS_FIT_KEPT = 0, 1, 2, 3
+
+
 class VitsWarpSeg(C.Structure):
     """vits_warp_seg: one token's segment of a warped row (vitsmi.h, "intonation"); 40 bytes"""
     _fields_ = [("n0", C.c_int64), ("pos0", C.c_int64), ("k", C.c_int64), ("step", C.c_int32), ("c", C.c_int32),
@@ -196,6 +204,8 @@ EXPORTS = [
     "vits_run_async_glided", "vits_glide_token", "vits_glide_cutoff", "vits_glide_plan", "vits_test_glide",
     "vits_warp_emit_end", "vits_glide_emit_end", "vits_warp_stream_cap", "vits_run_chunked_glided", "vits_run_chunked_enc_glided",
     "vits_test_warp_pieces", "vits_test_glide_pieces",
+    "vits_fit_plan", "vits_run_async_fitted", "vits_run_chunked_fitted", "vits_run_chunked_enc_fitted", "vits_last_fit",
+    "vits_test_fit_durations",
     "vits_test_durations", "vits_test_expand_prior", "vits_test_fill_normal", "vits_test_fill_normal_rows", "vits_test_post_conv",
     "vits_delivery_plan", "vits_deliver", "vits_test_deliver",
     "vits_trim_range", "vits_delivery_plan_trimmed", "vits_deliver_trimmed", "vits_test_deliver_trimmed",
@@ -332,6 +342,16 @@ def load():
                                                 C.POINTER(VitsContour), C.c_int, ENC_CHUNK_TRIM_FN, vp]
     for name in ("vits_test_warp_pieces", "vits_test_glide_pieces"):
         getattr(lib, name).argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, vp, C.c_int]
+    lib.vits_fit_plan.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(VitsFit), vp, vp, vp, vp]
+    lib.vits_run_async_fitted.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.POINTER(VitsNoise), C.POINTER(VitsControls),
+                                          C.POINTER(VitsFit)]
+    lib.vits_run_chunked_fitted.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.POINTER(VitsNoise), C.POINTER(VitsControls),
+                                            C.POINTER(VitsFit), C.c_int, CHUNK_FN, vp]
+    lib.vits_run_chunked_enc_fitted.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.POINTER(VitsNoise), C.POINTER(VitsControls),
+                                                C.POINTER(VitsStreamFormat), C.POINTER(VitsStreamShaping), C.POINTER(VitsStreamOnset),
+                                                C.POINTER(VitsFit), C.c_int, ENC_CHUNK_TRIM_FN, vp]
+    lib.vits_last_fit.argtypes = [vp, vp, vp, vp, C.c_int]
+    lib.vits_test_fit_durations.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.POINTER(VitsFit), vp, vp, vp, vp, vp, vp]
     lib.vits_test_durations.argtypes = [C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp, vp]
     lib.vits_test_expand_prior.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int64, C.c_int,
                                            C.c_float, vp, vp, vp]

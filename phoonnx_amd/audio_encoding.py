@@ -520,6 +520,10 @@ class EncodedAudio:
     # loudness_scope="text" the text's, repeated; -inf below 400 ms) and the gain applied
     loudness: Optional[List[float]] = None
     gain: Optional[List[float]] = None
+    # synthesize_encoded(..., duration=): the multiplier s* the text's durations were fitted with and the outcome (vitsmi.h,
+    # "fitted durations": 0 met, 1 floor, 2 ceiling, 3 kept)
+    fit_scale: Optional[float] = None
+    fit_status: Optional[int] = None
 
     def tobytes(self) -> bytes:
         return np.ascontiguousarray(self.data).tobytes()

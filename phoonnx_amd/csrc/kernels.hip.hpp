@@ -939,6 +939,15 @@ __global__ void add_bias_b_kernel(const float *in, float *out, const float *bias
 // (length_scale: the utterance's row of `rows` when given)
 // token_rate (nullable, [B][T]): w_ceil = ceil(((exp(logw) * mask) * length_scale) * token_rate[b][t]) for t < len[b], in
 // exactly this order of fp32 operations (vitsmi.h, vits_controls); NULL is the code path without the last product.
+// the value ceilf takes, token i = b * T + t (in: t < len[b]): stated once, for this kernel and for the fit's weights
+// (fit.hip.hpp), whose bits must be these
+__device__ __forceinline__ float duration_weight(const float *logw, const float *token_rate, int64_t i, bool in, float length_scale) {
+    float mk = in ? 1.f : 0.f;
+    float w = expf(logw[i]) * mk * length_scale;
+    if (token_rate && in) w = w * token_rate[i];
+    return w;
+}
+
 __global__ void duration_kernel(const float *logw, const int *len, float length_scale_all, const float *rows,
                                 const float *token_rate, float *w_ceil, int *cum, int *y_len, int T) {
     __shared__ int sh[256];
@@ -952,10 +961,7 @@ __global__ void duration_kernel(const float *logw, const int *len, float length_
         int t = base + tid;
         int v = 0;
         if (t < T) {
-            float mk = t < L ? 1.f : 0.f;
-            float w = expf(logw[(int64_t)b * T + t]) * mk * length_scale;
-            if (token_rate && t < L) w = w * token_rate[(int64_t)b * T + t];
-            float c = ceilf(w);
+            float c = ceilf(duration_weight(logw, token_rate, (int64_t)b * T + t, t < L, length_scale));
             w_ceil[(int64_t)b * T + t] = c;
             v = (int)c;
         }

@@ -26,6 +26,7 @@
 #include "conv_sx_small.hip.hpp"
 #include "delivery.hip.hpp"
 #include "delivery_run.hip.hpp"
+#include "fit.hip.hpp"
 #include "shape.hip.hpp"
 #include "kernels.hip.hpp"
 #include "loudness.hip.hpp"
@@ -91,6 +92,10 @@ struct vits_handle {
     size_t h_rb_pin_n = 0;         // makes the copy a staged, synchronous one: the stream then waits for the host twice)
     int h_dur_B = 0, h_dur_T = 0;
     bool last_forced = false;      // the last run took its durations from the caller: no logw to tap
+    // vits_last_fit / tap "w": the per-group results of the last run when it was fitted (they ride in the readback block
+    // behind y_len), and its weights [B][T] in the token slab
+    std::vector<FitResult> h_fit;
+    float *d_fit_w = nullptr;
     // stats
     int timing = 0;  // vits_set_timing: 0 off, 1 stage marks + events around every conv launch, 2 stage marks only
     vits_stats stats{};
@@ -275,7 +280,7 @@ int range_check(vits_handle *h) {
 // freed device memory (a run that grows a slab sets them again itself, behind the growth).
 void forget_results_in(vits_handle *h, const Slab &s) {
     if (&s == &h->tok) {
-        h->d_emb = h->d_x = h->d_mp = h->d_logs = h->d_logw = h->d_wceil = nullptr;
+        h->d_emb = h->d_x = h->d_mp = h->d_logs = h->d_logw = h->d_wceil = h->d_fit_w = nullptr;
         h->d_len = h->d_ylen = h->d_cum = nullptr;
         h->d_ylen64 = nullptr;
         h->h_dur_B = h->h_dur_T = 0;
@@ -728,6 +733,18 @@ hipError_t launch_attention16(hipStream_t st, int B, int T, int n_heads, int dk,
 void launch_durations(hipStream_t st, int B, int T, const float *logw, const int *len, float length_scale, const float *rows,
                       const float *token_rate, float *w_ceil, int *cum, int *y_len) {
     duration_kernel<<<B, 256, 0, st>>>(logw, len, length_scale, rows, token_rate, w_ceil, cum, y_len, T);
+}
+
+// fitted durations (fit.hip.hpp): w from logw by duration_kernel's own expression ...
+void launch_fit_weights(hipStream_t st, int B, int T, const float *logw, const int *len, float length_scale, const float *rows,
+                        const float *token_rate, float *w) {
+    fit_weight_kernel<<<dim3((T + 255) / 256, B), 256, 0, st>>>(logw, len, length_scale, rows, token_rate, w, T);
+}
+
+// ... and the fit itself, one workgroup per group, over the rows the groups name
+void launch_fit_durations(hipStream_t st, int B, int T, int G, const float *w, const int *len, const int *group, const int64_t *target,
+                          const int *mode, float *w_ceil, int *cum, int *y_len, FitResult *res) {
+    fit_duration_kernel<<<G, 256, 0, st>>>(w, len, group, target, mode, B, T, w_ceil, cum, y_len, res);
 }
 
 void launch_forced_durations(hipStream_t st, int B, int T, const int64_t *dur, const int *len, float *w_ceil, int *cum, int *y_len) {
@@ -1304,6 +1321,8 @@ struct RunRows {
     const float *semitones = nullptr;
     const float *semitones_end = nullptr;
     const int64_t *semitone_lens = nullptr;
+    // vits_fit (validated by host_fit; NULL when no row belongs to a group: the run is then the entry without a fit)
+    const vits_fit *fit = nullptr;
     float at(int b, int col) const { return scales[(rows ? (int64_t)b * 3 : 0) + col]; }
     bool any(int B, int col) const {  // some utterance's value is not 0
         for (int b = 0; b < (rows ? B : 1); b++)
@@ -1351,6 +1370,18 @@ int run_tokens(vits_handle *h, const int64_t *d_ids, const int64_t *d_lens, int 
     const bool forced = rr.d_durations != nullptr;
     h->last_forced = forced;
     h->h_dur_B = h->h_dur_T = 0;
+    h->h_fit.clear();
+    h->d_fit_w = nullptr;
+    const int G = rr.fit ? rr.fit->n_groups : 0;  // (host_fit: G <= B, every id and target checked)
+    std::vector<int64_t> in;  // (pageable, and read by the copy below: it lives until this function's one synchronisation)
+    if (G > 0) {
+        // [target int64 B | group int32 B | mode int32 B] gathered on the host and sent as one copy
+        in.assign((size_t)B * 2, 0);
+        int32_t *gm = reinterpret_cast<int32_t *>(in.data() + B);
+        for (int g = 0; g < G; g++) in[g] = rr.fit->target_frames[g], gm[B + g] = rr.fit->mode[g];
+        for (int b = 0; b < B; b++) gm[b] = rr.fit->group[b];
+        HIPCHECK(h, hipMemcpyAsync(w.fit_in, in.data(), sizeof(int64_t) * 2 * B, hipMemcpyHostToDevice, st));
+    }
     lens_to_i32<<<(B + 63) / 64, 64, 0, st>>>(d_lens, h->d_len, B, T);
     const int *len = h->d_len;
     h->cur_stage = 0;
@@ -1512,9 +1543,20 @@ int run_tokens(vits_handle *h, const int64_t *d_ids, const int64_t *d_lens, int 
         launch_durations(st, B, T, h->d_logw, len, rr.at(0, 1), rr.d_rows, rr.d_token_rate, h->d_wceil, h->d_cum, h->d_ylen);
     h->stats.total_launches++;
     c.note(hipGetLastError());
+    const size_t nBT = (size_t)B * T;
+    if (G > 0) {
+        // fitted durations: the weights duration_kernel ceiled, then one workgroup per group that overwrites the fitted rows
+        const int *gm = reinterpret_cast<const int *>(w.fit_in + B);
+        launch_fit_weights(st, B, T, h->d_logw, len, rr.at(0, 1), rr.d_rows, rr.d_token_rate, w.fit_w);
+        launch_fit_durations(st, B, T, G, w.fit_w, len, gm, w.fit_in, gm + B, h->d_wceil, h->d_cum, h->d_ylen,
+                             reinterpret_cast<FitResult *>(h->d_wceil + fit_block_offset(nBT, B)));
+        h->stats.total_launches += 2;
+        c.note(hipGetLastError());
+        h->d_fit_w = w.fit_w;
+    }
     if (c.err != hipSuccess) return fail(h, VITS_E_DEVICE, "kernel launch failed: %s", hipGetErrorString(c.err));
     // the one data-dependent readback: the frame counts (output length) and, in the same copy, the durations themselves
-    const size_t nBT = (size_t)B * T, nrb = nBT + B;
+    const size_t nrb = G > 0 ? fit_block_floats(nBT, B, G) : nBT + B;
     h->h_ylen.resize(B);
     h->h_dur.resize(nBT);
     if (h->h_rb_pin_n < nrb) {
@@ -1529,7 +1571,15 @@ int run_tokens(vits_handle *h, const int64_t *d_ids, const int64_t *d_lens, int 
         HIPCHECK(h, hipStreamSynchronize(st));
         std::memcpy(h->h_dur.data(), h->h_rb_pin, sizeof(float) * nBT);
         std::memcpy(h->h_ylen.data(), h->h_rb_pin + nBT, sizeof(int) * B);
+        if (G > 0) {
+            h->h_fit.resize(G);
+            std::memcpy(h->h_fit.data(), h->h_rb_pin + fit_block_offset(nBT, B), sizeof(FitResult) * G);
+        }
     } else {
+        if (G > 0) {
+            h->h_fit.resize(G);
+            HIPCHECK(h, hipMemcpyAsync(h->h_fit.data(), h->d_wceil + fit_block_offset(nBT, B), sizeof(FitResult) * G, hipMemcpyDeviceToHost, st));
+        }
         HIPCHECK(h, hipMemcpyAsync(h->h_dur.data(), h->d_wceil, sizeof(float) * nBT, hipMemcpyDeviceToHost, st));
         HIPCHECK(h, hipMemcpyAsync(h->h_ylen.data(), h->d_ylen, sizeof(int) * B, hipMemcpyDeviceToHost, st));
         HIPCHECK(h, hipStreamSynchronize(st));
@@ -3152,6 +3202,22 @@ static int host_controls(vits_handle *h, const vits_controls *ctl, const int64_t
     return VITS_OK;
 }
 
+// ... and a vits_fit on top of the controls (vitsmi.h, "fitted durations"): pure host code, answered before the device is
+// looked at.  No row in any group: rr.fit stays NULL, and the run is the entry without a fit.
+static int host_fit(vits_handle *h, const vits_controls *ctl, const vits_fit *fit, int B, RunRows &rr) {
+    if (!fit) return VITS_OK;
+    if (B <= 0) return fail(h, VITS_E_ARG, "empty batch (B=%d)", B);
+    const int64_t hop = h->model.hop > 0 ? h->model.hop : 1;
+    const int64_t max_frames = VITS_MAX_FORCED_FRAMES < INT_MAX / hop ? VITS_MAX_FORCED_FRAMES : INT_MAX / hop;
+    const std::string e = fit_fault(fit, B, max_frames);
+    if (!e.empty()) return fail(h, VITS_E_ARG, "%s", e.c_str());
+    if (!fit_on(fit, B)) return VITS_OK;
+    if (ctl && ctl->durations)
+        return fail(h, VITS_E_ARG, "durations and a fit are contradictory: forced durations leave nothing to fit");
+    rr.fit = fit;
+    return VITS_OK;
+}
+
 static int run_device_locked(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T,
                              RunRows rr, const int64_t *sid, const vits_noise *noise, vits_output *out,
                              const ChunkSink *sink = nullptr) {
@@ -3230,6 +3296,37 @@ int vits_last_durations(vits_handle *h, int64_t *buf, size_t n_elems) {
     if (n == 0 || h->h_dur.size() < n) return fail(h, VITS_E_ARG, "no completed run to report durations of");
     for (size_t i = 0; i < n && i < n_elems && buf; i++) buf[i] = (int64_t)h->h_dur[i];
     return (int)n;
+}
+
+int vits_last_fit(vits_handle *h, double *scale, int64_t *frames, int32_t *status, int n) {
+    if (!h) return VITS_E_ARG;
+    const int G = (int)h->h_fit.size();
+    if (G == 0 || h->h_dur_B == 0) return fail(h, VITS_E_ARG, "the last run was not fitted: no fit to report");
+    for (int g = 0; g < G && g < n; g++) {
+        if (scale) scale[g] = h->h_fit[g].scale;
+        if (frames) frames[g] = h->h_fit[g].frames;
+        if (status) status[g] = h->h_fit[g].status;
+    }
+    return G;
+}
+
+int vits_fit_plan(const float *w, const int64_t *lens, int B, int T, const vits_fit *fit, int64_t *durations, double *scale,
+                  int64_t *frames, int32_t *status) {
+    if (!w || !lens || !fit || !durations || B <= 0 || T <= 0) return fail(nullptr, VITS_E_ARG, "bad fit plan arguments (B=%d, T=%d) or a null pointer", B, T);
+    for (int b = 0; b < B; b++)
+        if (lens[b] < 0 || lens[b] > T) return fail(nullptr, VITS_E_ARG, "input_lengths[%d]=%lld outside [0,%d]", b, (long long)lens[b], T);
+    const std::string e = fit_fault(fit, B, VITS_MAX_FORCED_FRAMES);
+    if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
+    for (int g = 0; g < fit->n_groups; g++) {
+        double s;
+        int64_t f;
+        int32_t st;
+        fit_plan_group(w, lens, fit->group, B, T, g, fit->target_frames[g], fit->mode[g], durations, s, f, st);
+        if (scale) scale[g] = s;
+        if (frames) frames[g] = f;
+        if (status) status[g] = st;
+    }
+    return VITS_OK;
 }
 
 int vits_sync(vits_handle *h) {
@@ -3463,14 +3560,16 @@ int vits_stream_onset_start(int64_t f, int64_t keep_lead, int64_t delivered_befo
 // the three encoded entries of the whole path: fn without, tfn with the rows' skips
 static int run_chunked_enc(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid, const vits_noise *noise,
                            const vits_controls *ctl, const vits_stream_format *fmt, const vits_stream_shaping *shaping,
-                           const vits_stream_onset *onsets, int chunk_frames, vits_enc_chunk_fn fn, vits_enc_chunk_trim_fn tfn, void *user) {
+                           const vits_stream_onset *onsets, int chunk_frames, vits_enc_chunk_fn fn, vits_enc_chunk_trim_fn tfn, void *user,
+                           const vits_fit *fit = nullptr) {
     if (!h) return VITS_E_ARG;
     std::lock_guard<std::mutex> lk(h->mu);
     if (int rc = host_stream_format(h, fmt, B)) return rc;  // (pure host code: a host-only handle answers it too)
     if (int rc = host_stream_shaping(h, shaping, fmt, B)) return rc;
     if (int rc = host_stream_onsets(h, onsets, fmt, B)) return rc;
-    if (int rc = check_dev(h)) return rc;
     RunRows rr;
+    if (int rc = host_fit(h, ctl, fit, B, rr)) return rc;
+    if (int rc = check_dev(h)) return rc;
     if (int rc = host_controls(h, ctl, lens, B, T, rr)) return rc;
     ChunkSink sink{chunk_frames, nullptr, user};
     sink.fmt = fmt;
@@ -3486,6 +3585,13 @@ int vits_run_chunked_enc_trimmed(vits_handle *h, const int64_t *ids, const int64
                                  const vits_stream_shaping *shaping, const vits_stream_onset *onsets, int chunk_frames,
                                  vits_enc_chunk_trim_fn fn, void *user) {
     return run_chunked_enc(h, ids, lens, B, T, sid, noise, ctl, fmt, shaping, onsets, chunk_frames, nullptr, fn, user);
+}
+
+int vits_run_chunked_enc_fitted(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
+                                const vits_noise *noise, const vits_controls *ctl, const vits_stream_format *fmt,
+                                const vits_stream_shaping *shaping, const vits_stream_onset *onsets, const vits_fit *fit,
+                                int chunk_frames, vits_enc_chunk_trim_fn fn, void *user) {
+    return run_chunked_enc(h, ids, lens, B, T, sid, noise, ctl, fmt, shaping, onsets, chunk_frames, nullptr, fn, user, fit);
 }
 
 int vits_run_chunked_enc_shaped(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
@@ -3525,6 +3631,31 @@ int vits_run_async_ctl(vits_handle *h, const int64_t *ids, const int64_t *lens, 
     if (int rc = host_controls(h, ctl, lens, B, T, rr)) return rc;
     vits_output dev{};
     return run_async_locked(h, ids, lens, B, T, rr, sid, noise, &dev);
+}
+
+// vits_run_async_ctl / vits_run_chunked_ctl with a fit on top (vitsmi.h, "fitted durations")
+int vits_run_async_fitted(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
+                          const vits_noise *noise, const vits_controls *ctl, const vits_fit *fit) {
+    if (!h) return VITS_E_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    RunRows rr;
+    if (int rc = host_fit(h, ctl, fit, B, rr)) return rc;
+    if (int rc = check_dev(h)) return rc;
+    if (int rc = host_controls(h, ctl, lens, B, T, rr)) return rc;
+    vits_output dev{};
+    return run_async_locked(h, ids, lens, B, T, rr, sid, noise, &dev);
+}
+
+int vits_run_chunked_fitted(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
+                            const vits_noise *noise, const vits_controls *ctl, const vits_fit *fit, int chunk_frames,
+                            vits_chunk_fn fn, void *user) {
+    if (!h) return VITS_E_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    RunRows rr;
+    if (int rc = host_fit(h, ctl, fit, B, rr)) return rc;
+    if (int rc = check_dev(h)) return rc;
+    if (int rc = host_controls(h, ctl, lens, B, T, rr)) return rc;
+    return run_chunked_locked(h, ids, lens, B, T, rr, sid, noise, chunk_frames, fn, user);
 }
 
 // vits_run_async_ctl with the intonation on top (vitsmi.h, "intonation").  What is pure host code - the semitones, the
@@ -4178,11 +4309,13 @@ int vits_tap(vits_handle *h, const char *name, float *buf, size_t buf_elems, int
     else if (k == "logs_p") { src = h->d_logs; C = m.C; L = T; bstride = (int64_t)2 * C * L; }
     else if (k == "logw") { src = h->d_logw; C = 1; L = T; bstride = L; }
     else if (k == "w_ceil") { src = h->d_wceil; C = 1; L = T; bstride = L; nd = 2; }
+    else if (k == "w") { src = h->d_fit_w; C = 1; L = T; bstride = L; nd = 2; }
     else if (k == "z_p") { src = h->d_zp; C = m.C; L = F; cstride = h->Fpitch; bstride = (int64_t)C * cstride; }
     else if (k == "z") { src = h->d_z; C = m.C; L = F; cstride = h->Fpitch; bstride = (int64_t)C * cstride; }
     else return fail(h, VITS_E_ARG, "unknown tap %s", name);
     if (k == "logw" && h->last_forced && h->d_wceil)
         return fail(h, VITS_E_ARG, "logw is not computed in a forced-duration run");
+    if (k == "w" && !src && h->d_wceil) return fail(h, VITS_E_ARG, "w is not computed in a run without a fit");
     if (!src || B == 0) return fail(h, VITS_E_ARG, "no completed run to tap");
     if (nd == 2) { dims[0] = B; dims[1] = L; }
     else { dims[0] = B; dims[1] = C; dims[2] = L; }
@@ -5931,6 +6064,42 @@ int vits_test_durations(int device_id, const float *logw, const int64_t *dur, co
     TCHECK(download(w_ceil, dw, nBT));
     TCHECK(download(cum, dcum, nBT));
     TCHECK(download(y_len, dyl, (size_t)B));
+    return VITS_OK;
+}
+
+int vits_test_fit_durations(int device_id, const float *w, const int64_t *lens, int B, int T, const vits_fit *fit, float *w_ceil,
+                            int32_t *cum, int32_t *y_len, double *scale, int64_t *frames, int32_t *status) {
+    if (int rc = test_dev(device_id)) return rc;
+    std::vector<int> l32;
+    if (int rc = glue_test_lens(lens, B, T, l32)) return rc;
+    if (!w || !fit || !w_ceil || !cum || !y_len) return fail(nullptr, VITS_E_ARG, "weights, a fit and three outputs are needed");
+    const std::string e = fit_fault(fit, B, VITS_MAX_FORCED_FRAMES);
+    if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
+    const int G = fit->n_groups;
+    if (G < 1) return fail(nullptr, VITS_E_ARG, "fit n_groups = %d: nothing to launch", G);
+    const size_t nBT = (size_t)B * T;
+    std::vector<int> g32(fit->group, fit->group + B), m32(fit->mode, fit->mode + G);
+    std::vector<FitResult> res((size_t)G);
+    DevBufs D;
+    const float *dwt = D.up(w, nBT);
+    int *dlen = D.up(l32.data(), (size_t)B), *dg = D.up(g32.data(), (size_t)B), *dm = D.up(m32.data(), (size_t)G);
+    int64_t *dt = D.up(fit->target_frames, (size_t)G);
+    float *dw = D.up(w_ceil, nBT);
+    int *dcum = D.up(cum, nBT), *dyl = D.up(y_len, (size_t)B);
+    FitResult *dres = D.fill<FitResult>((size_t)G, 0xff);
+    TCHECK(D.err);
+    launch_fit_durations(nullptr, B, T, G, dwt, dlen, dg, dt, dm, dw, dcum, dyl, dres);
+    TCHECK(hipGetLastError());
+    TCHECK(hipDeviceSynchronize());
+    TCHECK(download(w_ceil, dw, nBT));
+    TCHECK(download(cum, dcum, nBT));
+    TCHECK(download(y_len, dyl, (size_t)B));
+    TCHECK(download(res.data(), dres, (size_t)G));
+    for (int g = 0; g < G; g++) {
+        if (scale) scale[g] = res[g].scale;
+        if (frames) frames[g] = res[g].frames;
+        if (status) status[g] = res[g].status;
+    }
     return VITS_OK;
 }
 

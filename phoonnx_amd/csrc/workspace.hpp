@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "delivery.hpp"
+#include "fit.hpp"
 #include "limit.hpp"
 #include "loudness.hpp"
 #include "model.hpp"
@@ -39,10 +40,12 @@ struct TokenBufs {
     int *len, *cum;
     int64_t *ylen64;
     float *x, *att, *xe, *qkv, *ffh, *stats, *logw;
-    float *wceil;     // [w_ceil B*T | y_len B]: one block, read back with one copy
+    float *wceil;     // [w_ceil B*T | y_len B | fit results, B records at the most]: one block, read back with one copy
     float *rows;      // per-utterance settings [B][3]
     uint64_t *seeds;  // per-utterance noise seeds [B]
     int64_t *ctl;     // forced durations (int64 [B][T]) or, in the same buffer, per-token rates (float [B][T])
+    float *fit_w;     // a fitted run's weights [B][T] (tap "w")
+    int64_t *fit_in;  // a fitted run's [target int64 B | group int32 B | mode int32 B], sent as one copy
     uint16_t *x_pl, *att_pl, *ff_pl, *qkv_pl;  // Model::enc_sx: operand planes of x, attn out, ffn hidden and q | k | v
     float *dp_cond;                            // Model::gin
     int pr_rows;  // spline parameters per position: 3 * bins - 1 (29 for the reference's 10 bins, up to 47)
@@ -63,10 +66,12 @@ inline TokenBufs carve_tokens(Carver &cv, const Model &m, int B, int T) {
     t.ffh = cv.take<float>(nBT * m.FF);
     t.stats = cv.take<float>(nBT * 2 * m.C);
     t.logw = cv.take<float>(nBT);
-    t.wceil = cv.take<float>(nBT + B);
+    t.wceil = cv.take<float>(fit_block_floats(nBT, B, B));
     t.rows = cv.take<float>((size_t)B * 3);
     t.seeds = cv.take<uint64_t>(B);
     t.ctl = cv.take<int64_t>(nBT);
+    t.fit_w = cv.take<float>(nBT);
+    t.fit_in = cv.take<int64_t>((size_t)B * 2);
     if (m.enc_sx) {
         t.x_pl = take_planes(cv, plane_floats(nHT));
         t.att_pl = take_planes(cv, plane_floats(nHT));

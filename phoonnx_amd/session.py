@@ -221,6 +221,86 @@ def _controls(rows, seeds, durations, token_rate):
     return c
 
 
+FIT_MODES = {"exact": 1, "at_most": 2}
+VITS_MAX_FORCED_FRAMES = 1 << 24
+
+
+class Fit:
+    """Fitted durations of a run (vitsmi.h, "fitted durations"): `groups` - one entry per row, the row's group or -1 for a row
+    that keeps its own durations; `target_frames` - one frame count per group, the sum of the durations of all the group's
+    tokens; `modes` - "exact" (1) or "at_most" (2), one for all groups or one per group.  Fit.one_group(B, frames) puts all
+    rows of a batch - the sentences of a text - into one group."""
+
+    def __init__(self, groups, target_frames, modes="exact"):
+        self.groups = np.atleast_1d(np.asarray(groups))
+        self.target_frames = np.atleast_1d(np.asarray(target_frames))
+        m = [modes] * len(self.target_frames) if isinstance(modes, (str, int, np.integer)) else list(modes)
+        self.modes = np.array([FIT_MODES.get(v, v) if isinstance(v, str) else v for v in m], dtype=object)
+
+    @classmethod
+    def one_group(cls, B, target_frames, mode="exact"):
+        return cls(np.zeros(int(B), np.int32), [int(target_frames)], mode)
+
+
+def _fit(fit, B, hop, durations=None, semitones=None):
+    """fit= of a run -> the vits_fit struct over validated host arrays (None: no fit, or no row in any group - the entry
+    without a fit).  What the engine would refuse is raised here, by the call, in the engine's words: nothing was started."""
+    if fit is None:
+        return None
+    if not isinstance(fit, Fit):
+        raise SessionError(f"Unexpected input: 'fit' must be a session.Fit, got {type(fit).__name__}")
+    if durations is not None:
+        raise ValueError("fit= and durations= are contradictory: forced durations leave nothing to fit")
+    if semitones is not None:
+        raise ValueError("fit= together with token_semitones= / token_semitones_end= is not covered: with compensate the "
+                         "delivered length is not the native frame count")
+    g, t, m = fit.groups, fit.target_frames, fit.modes
+    G = len(t)
+    if g.ndim != 1 or g.dtype.kind not in "iu" or g.shape[0] != B:
+        raise SessionError(f"Invalid shape for 'fit.groups': {g.shape} {g.dtype}, expected [batch_size] = ({B},) integers")
+    if t.ndim != 1 or t.dtype.kind not in "iu" or len(m) != G:
+        raise SessionError(f"'fit.target_frames' must be integers [n_groups] with one mode per group (got {t.shape} {t.dtype}, "
+                           f"{len(m)} modes)")
+    for b in range(B):
+        if not -1 <= int(g[b]) < G:
+            raise SessionError(f"fit group[{b}]={int(g[b])} outside [-1,{G})")
+    max_frames = min(VITS_MAX_FORCED_FRAMES, (2 ** 31 - 1) // max(int(hop), 1))
+    for k in range(G):
+        if not 1 <= int(t[k]) <= max_frames:
+            raise SessionError(f"fit target_frames[{k}]={int(t[k])} outside [1,{max_frames}] (VITS_MAX_FORCED_FRAMES, INT_MAX / hop)")
+        if m[k] not in (1, 2):
+            raise SessionError(f"fit mode[{k}]={m[k]!r} is neither 1 (exact) nor 2 (at most)")
+        if not (g == k).any():
+            raise SessionError(f"fit group {k} has no rows")
+    if G == 0 or not (g >= 0).any():
+        return None
+    g32, t64, m32 = np.ascontiguousarray(g, np.int32), np.ascontiguousarray(t, np.int64), np.array([int(v) for v in m], np.int32)
+    c = _ffi.VitsFit(g32.ctypes.data, G, t64.ctypes.data, m32.ctypes.data)
+    c._keep = (g32, t64, m32)
+    return c
+
+
+def fit_plan(w, lens, fit):
+    """The plan of a fit over weights float32 [B, T] (vits_fit_plan: pure host code) -> (durations int64 [B, T] with -1 in
+    the rows of no group, scale float64 [G], frames int64 [G], status int32 [G])"""
+    w = np.ascontiguousarray(w, np.float32)
+    lens = np.ascontiguousarray(lens, np.int64)
+    if w.ndim != 2 or lens.shape != (w.shape[0],):
+        raise SessionError(f"fit_plan: w must be [B, T] and lens [B] (got {w.shape}, {lens.shape})")
+    B, T = w.shape
+    g32, t64 = np.ascontiguousarray(fit.groups, np.int32), np.ascontiguousarray(fit.target_frames, np.int64)
+    m32 = np.array([int(v) for v in fit.modes], np.int32)
+    G = len(t64)
+    c = _ffi.VitsFit(g32.ctypes.data, G, t64.ctypes.data, m32.ctypes.data)
+    dur = np.full((B, T), -1, np.int64)
+    scale, frames, status = np.zeros(G, np.float64), np.zeros(G, np.int64), np.zeros(G, np.int32)
+    rc = _ffi.load().vits_fit_plan(_ffi.ptr(w), _ffi.ptr(lens), B, T, C.byref(c), _ffi.ptr(dur), _ffi.ptr(scale), _ffi.ptr(frames),
+                                   _ffi.ptr(status))
+    if rc != 0:
+        raise SessionError(f"vits_fit_plan failed [{rc}]: {_ffi.last_error(None)}")
+    return dur, scale, frames, status
+
+
 def _semitones(token_semitones, lens, B, T, name="token_semitones"):
     """token_semitones - None, or floats [B, T] within [-12, 12] in front of lens[b] (vitsmi.h, "intonation") -> float32
     [B, T], contiguous"""
@@ -1078,7 +1158,7 @@ class MiSession:
 
     def synthesize_batch(self, ids, lens, scales, sid=None, noise_dp=None, noise_z=None, taps=(), seeds=None,
                          durations=None, token_rate=None, return_durations=False, output_rates=None, token_semitones=None,
-                         compensate=True, token_semitones_end=None):
+                         compensate=True, token_semitones_end=None, fit=None):
         """One batched run.  Returns {"output": [B,1,1,S] float32, "y_lengths": int64 [B], taps...}.
         output_rates: None, or a rate per row for this call (set_output_rates; what was set before is put back afterwards);
         with row rates the result also holds "sample_rates" (int32 [B]).
@@ -1099,17 +1179,23 @@ class MiSession:
         [B, T]: the output samples of each token; "durations" stay the rendered frames).
         token_semitones_end: None or floats [B, T] within [-12, 12] - token t GLIDES from token_semitones[b, t] (zeros where
         that is None) to this value across its output samples (vitsmi.h, "pitch contours"); compensate=True renders it longer
-        by the mean of 2^(st/12) at its two ends.  Equal ends everywhere are the token_semitones run, bit for bit."""
+        by the mean of 2^(st/12) at its two ends.  Equal ends everywhere are the token_semitones run, bit for bit.
+        fit: None or a session.Fit - the durations of its groups of rows are rescaled on the device so that each group renders
+        its target number of frames (vitsmi.h, "fitted durations"); the result then holds "fit_scale" (float64 [G]: the
+        multiplier s*), "fit_frames" (int64 [G]: the frames achieved) and "fit_status" (int32 [G]: 0 met, 1 floor, 2 ceiling,
+        3 kept).  Not together with durations or token_semitones (ValueError)."""
         ids, lens, scales, sid, noise_dp, noise_z, noise, seeds, durations, token_rate = self._run_arguments(
             ids, lens, scales, sid, noise_dp, noise_z, seeds, durations, token_rate)
         B = ids.shape[0]
         semitones, semitones_end = _contour(token_semitones, token_semitones_end, lens, B, ids.shape[1])
+        cfit = _fit(fit, B, self.hparam("hop"), durations, semitones)
         # enqueue -> frame counts -> copy-out -> taps all use this handle's one workspace
         with self._locked(), self._rates_for_call(output_rates):
             try:
-                self._begin(ids, lens, scales, sid, noise, seeds, durations, token_rate, semitones, compensate, semitones_end)
+                self._begin(ids, lens, scales, sid, noise, seeds, durations, token_rate, semitones, compensate, semitones_end, cfit)
                 ylen = self.last_y_lengths()
                 dur = self.last_durations() if return_durations else None
+                fitted = self.last_fit() if cfit is not None else None
                 counts = self.last_sample_counts() if self.resampling or self.output_rates is not None or semitones is not None else None
                 spans = self._token_spans(semitones, lens, semitones_end) if return_durations and semitones is not None else None
                 S = int(ylen.max()) * self.hparam("hop") if counts is None else int(counts.max())
@@ -1120,8 +1206,10 @@ class MiSession:
                 return self.synthesize_batch(ids, lens, scales, sid, noise_dp, noise_z, taps, seeds=seeds,
                                              durations=durations, token_rate=token_rate, return_durations=return_durations,
                                              token_semitones=token_semitones, compensate=compensate,
-                                             token_semitones_end=token_semitones_end)
+                                             token_semitones_end=token_semitones_end, fit=fit)
             res = {"output": audio, "y_lengths": ylen}
+            if fitted is not None:
+                res["fit_scale"], res["fit_frames"], res["fit_status"] = fitted
             if counts is not None:
                 res["sample_lengths"] = counts
             if self.output_rates is not None:
@@ -1166,12 +1254,16 @@ class MiSession:
         return ids, lens, scales, sid, noise_dp, noise_z, noise, seeds, durations, token_rate
 
     def _begin(self, ids, lens, scales, sid, noise, seeds=None, durations=None, token_rate=None, semitones=None, compensate=True,
-               semitones_end=None):
+               semitones_end=None, fit=None):
         """vits_run_async: validated host arrays in, the whole path enqueued; frame counts and durations are known on
         return.  ([B, 3] scales or seeds: vits_run_async_rows; durations or token_rate: vits_run_async_ctl; semitones:
         vits_run_async_warped; semitones_end too: vits_run_async_glided.)"""
         B, T = ids.shape
-        if semitones_end is not None:
+        if fit is not None:  # (a vits_fit struct of _fit: vits_run_async_fitted)
+            ctl = _controls(_rows(scales, B), seeds, durations, token_rate)
+            rc = self._lib.vits_run_async_fitted(self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(sid), C.byref(noise),
+                                                 C.byref(ctl), C.byref(fit))
+        elif semitones_end is not None:
             rows = _rows(scales, B)
             ctl = _controls(rows, seeds, durations, token_rate)
             contour = _ffi.VitsContour(semitones.ctypes.data, semitones_end.ctypes.data, 1 if compensate else 0)
@@ -1305,7 +1397,7 @@ class MiSession:
 
     def synthesize_stream(self, ids, lens, scales, sid=None, chunk_frames: int = 64, noise_dp=None, noise_z=None,
                           seeds=None, durations=None, token_rate=None, token_semitones=None, compensate=True,
-                          token_semitones_end=None):
+                          token_semitones_end=None, fit=None):
         """The whole path with the waveform delivered in chunks of `chunk_frames` frames (hop samples each): yields
         (first_sample, float32 [B, n], total_samples).  Concatenated, the chunks are bit-identical to
         synthesize_batch(...)["output"][:, 0, 0, :]; frame counts afterwards from last_y_lengths().  Chunks are handed out
@@ -1317,13 +1409,16 @@ class MiSession:
         token_semitones, compensate, token_semitones_end - as synthesize_batch (vitsmi.h, "streamed pitch"): the chunks, joined,
         are that run's warped "output"; their ranges lie on the warped timeline and follow what the rows' plans have completed -
         a chunk of the run may deliver nothing, or several ranges -, total_samples is the longest warped row, and
-        last_sample_counts() / last_token_spans() answer from the first chunk on.  Not covered with an output rate set."""
+        last_sample_counts() / last_token_spans() answer from the first chunk on.  Not covered with an output rate set.
+        fit - as synthesize_batch (vitsmi.h, "fitted durations"): the chunks, joined, are the fitted run's "output"; last_fit()
+        answers from the first chunk on.  Not together with durations or token_semitones (ValueError)."""
         ids = np.ascontiguousarray(ids, np.int64)
         lens = np.ascontiguousarray(lens, np.int64)
         B, T = ids.shape
         semitones, semitones_end = _contour(token_semitones, token_semitones_end, lens, B, T)
         scales, seeds = _settings(np.ascontiguousarray(scales, np.float32), B, seeds)
         durations, token_rate = _timing(durations, token_rate, lens, B, T)
+        cfit = _fit(fit, B, self.hparam("hop"), durations, semitones)
         sid = None if sid is None else np.ascontiguousarray(sid, np.int64)
         noise = _ffi.VitsNoise()
         noise.seed = self._seed
@@ -1337,6 +1432,11 @@ class MiSession:
             keep.append(np.ascontiguousarray(noise_z, np.float32))
             noise.noise_z = keep[-1].ctypes.data
             noise.noise_z_stride = keep[-1].shape[2]
+        if cfit is not None:
+            ctl = _controls(_rows(scales, B), seeds, durations, token_rate)
+            return self._stream(lambda cb: self._lib.vits_run_chunked_fitted(
+                self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(sid), C.byref(noise), C.byref(ctl), C.byref(cfit),
+                int(chunk_frames), cb, None))
         if semitones is not None:
             self._pitch_admit("synthesize_stream", durations, compensate, semitones, semitones_end, lens)
             ctl = _controls(_rows(scales, B), seeds, durations, token_rate)
@@ -1395,7 +1495,7 @@ class MiSession:
     def synthesize_stream_encoded(self, ids, lens, scales, sid=None, chunk_frames: int = 64, encoding="pcm16", ref_peak=None,
                                   volume=None, noise_dp=None, noise_z=None, seeds=None, durations=None, token_rate=None,
                                   shapes=None, token_gain_db=None, gain_ramp=0.01, limit=None, onsets=None, token_semitones=None,
-                                  compensate=True, token_semitones_end=None):
+                                  compensate=True, token_semitones_end=None, fit=None):
         """synthesize_stream with every chunk post-processed, encoded and masked to each row's own length on the device
         (vitsmi.h, "encoded streaming"): yields EncodedChunk.  encoding "pcm16" / "ulaw" / "alaw" / "f32"; `volume` and
         `ref_peak` None, a scalar or [B]: row b is scaled by volume[b] and - with ref_peak - normalised by ref_peak[b] (a
@@ -1417,11 +1517,15 @@ class MiSession:
         token_semitones, compensate, token_semitones_end - as synthesize_stream (vitsmi.h, "streamed pitch"): everything above
         then works on the warped audio - valid counts, fades and the limiter by each row's warped length, token_gain_db's
         breakpoints on the warp's own token spans -, and every chunk carries `skip` (zeros without onsets): data[b,
-        skip[b]:valid[b]], joined, is what synthesize_delivered(token_semitones=...) gives for the row."""
+        skip[b]:valid[b]], joined, is what synthesize_delivered(token_semitones=...) gives for the row.
+        fit - as synthesize_batch (vitsmi.h, "fitted durations"): everything above then works on the fitted run - joined, the
+        rows are what synthesize_delivered(fit=...) gives -, every chunk carries `skip` (zeros without onsets), and last_fit()
+        answers from the first chunk on.  Not together with durations or token_semitones (ValueError)."""
         ids = np.ascontiguousarray(ids, np.int64)
         lens = np.ascontiguousarray(lens, np.int64)
         B, T = ids.shape
         semitones, semitones_end = _contour(token_semitones, token_semitones_end, lens, B, T)
+        cfit = _fit(fit, B, self.hparam("hop"), durations, semitones)
         if semitones is not None:
             self._pitch_admit("synthesize_stream_encoded", durations, compensate, semitones, semitones_end, lens)
         fmt, dtype = _stream_format(encoding, ref_peak, volume, B)
@@ -1442,6 +1546,15 @@ class MiSession:
             noise.noise_z_stride = keep[-1].shape[2]
         ctl = _controls(_rows(scales, B), seeds, durations, token_rate)
         trim = _stream_onsets(onsets, B)
+        if cfit is not None:
+            if shaping is not None:
+                self._shaping_check(shaping, fmt, B)
+            if trim is not None:
+                self._onsets_check(trim, fmt, B)
+            return self._stream(lambda cb: self._lib.vits_run_chunked_enc_fitted(
+                self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(sid), C.byref(noise), C.byref(ctl), C.byref(fmt),
+                None if shaping is None else C.byref(shaping), trim, C.byref(cfit), int(chunk_frames), cb, None),
+                self._trimmed_items(dtype))
         if semitones is not None:
             if shaping is not None:
                 self._shaping_check(shaping, fmt, B)
@@ -1796,6 +1909,19 @@ class MiSession:
                 raise SessionError(f"vits_last_durations: the run changed between two calls ({n} != {buf.size})")
             return buf
 
+    def last_fit(self):
+        """(scale float64 [G], frames int64 [G], status int32 [G]) of the last FITTED run: per group the multiplier s*, the
+        frames achieved and the status (0 met, 1 floor, 2 ceiling, 3 kept).  Host state like last_durations(): valid from
+        the first chunk of a stream on.  SessionError after a run that was not fitted."""
+        with self._locked(read_only=True):
+            G = self._lib.vits_last_fit(self._h, None, None, None, 0)
+            if G < 0:
+                raise SessionError(f"vits_last_fit failed [{G}]: {self._err()}")
+            scale, frames, status = np.zeros(G, np.float64), np.zeros(G, np.int64), np.zeros(G, np.int32)
+            if self._lib.vits_last_fit(self._h, _ffi.ptr(scale), _ffi.ptr(frames), _ffi.ptr(status), G) != G:
+                raise SessionError("vits_last_fit: the run changed between two calls")
+            return scale, frames, status
+
     def last_token_spans(self) -> np.ndarray:
         """int64 [B, T]: the output samples each token of the last WARPED run occupies (k of the warp's plan; 0 for a dropped
         token and behind lens[b]); row sums = last_sample_counts().  Host state like last_durations().  SessionError after a
@@ -1955,7 +2081,7 @@ class MiSession:
                              normalize=True, volume=1.0, seeds=None, durations=None, token_rate=None, noise_dp=None,
                              noise_z=None, return_durations=False, trim=None, levels=None, shapes=None, token_gain_db=None,
                              gain_ramp=0.01, limits=None, output_rates=None, token_semitones=None, compensate=True,
-                             token_semitones_end=None):
+                             token_semitones_end=None, fit=None):
         """One batched run and its delivery under one hold of the session lock: what leaves the GPU is the encoded audio
         of the plan and nothing else - the fp32 waveform is never copied to the host.  segments=None: one stream per row,
         with `normalize` / `volume` as scalars or [B] arrays (row b's own).  Everything in front of the delivery is
@@ -1977,6 +2103,8 @@ class MiSession:
         token_semitones, compensate - as synthesize_batch: the delivery then works on the warped waveform and its counts; the
         token gains' breakpoints lie on the warp's own token spans, and with return_durations the result holds "token_spans".
         token_semitones_end - as synthesize_batch: the tokens glide ("pitch contours"); everything behind the run is the same.
+        fit - as synthesize_batch ("fitted durations"): the run is fitted, everything behind it is the same, and the result
+        holds "fit_scale", "fit_frames" and "fit_status".
         Returns {"streams": [array per stream], "stream_samples": int64 [J], "y_lengths": int64 [B], "sample_lengths":
         int64 [B] (each row's valid samples at the delivered rate), "kept_first" / "kept_count": int64 [G] (what each
         segment delivers of its row: all of it without a trim)[, "durations"]}."""
@@ -1984,6 +2112,7 @@ class MiSession:
             ids, lens, scales, sid, noise_dp, noise_z, seeds, durations, token_rate)
         B = ids.shape[0]
         semitones, semitones_end = _contour(token_semitones, token_semitones_end, lens, B, ids.shape[1])
+        cfit = _fit(fit, B, self.hparam("hop"), durations, semitones)
         if segments is None:
             try:
                 nz = np.broadcast_to(np.asarray(normalize, bool), (B,))
@@ -2018,9 +2147,10 @@ class MiSession:
                     raise SessionError(f"segment {i}: token_gain_db and explicit points on the same segment")
         with self._locked(), self._rates_for_call(output_rates):
             try:
-                self._begin(ids, lens, scales, sid, noise, seeds, durations, token_rate, semitones, compensate, semitones_end)
+                self._begin(ids, lens, scales, sid, noise, seeds, durations, token_rate, semitones, compensate, semitones_end, cfit)
                 ylen = self.last_y_lengths()
                 dur = self.last_durations() if return_durations or tgains is not None else None
+                fitted = self.last_fit() if cfit is not None else None
                 counts = self.last_sample_counts()
                 rates = self.last_sample_rates() if self.output_rates is not None else None
                 spans = self._token_spans(semitones, lens, semitones_end) if semitones is not None and (return_durations or tgains is not None) else None
@@ -2046,7 +2176,7 @@ class MiSession:
                                                  noise_dp=noise_dp, noise_z=noise_z, return_durations=return_durations,
                                                  trim=trim, levels=levels, shapes=shapes, token_gain_db=token_gain_db,
                                                  gain_ramp=gain_ramp, limits=limits, token_semitones=token_semitones,
-                                                 compensate=compensate, token_semitones_end=token_semitones_end)
+                                                 compensate=compensate, token_semitones_end=token_semitones_end, fit=fit)
         res = {"streams": streams, "stream_samples": np.array([a.size for a in streams], np.int64), "y_lengths": ylen,
                "sample_lengths": counts, "kept_first": kept_first, "kept_count": kept_count}
         if levels is not None:
@@ -2055,6 +2185,8 @@ class MiSession:
             res["sample_rates"] = rates
         if used is not None:
             res["shapes"] = used
+        if fitted is not None:
+            res["fit_scale"], res["fit_frames"], res["fit_status"] = fitted
         if return_durations:
             res["durations"] = dur
             if spans is not None:
@@ -2322,7 +2454,7 @@ class PipelinedSession:
 
     def synthesize_batch(self, ids, lens, scales, sid=None, seeds=None, durations=None, token_rate=None,
                          return_durations=False, noise_dp=None, noise_z=None, token_semitones=None, compensate=True,
-                         token_semitones_end=None):
+                         token_semitones_end=None, fit=None):
         """Host arrays in, host arrays out, like MiSession.synthesize_batch (scales [3] or [B, 3], seeds, durations [B, T],
         token_rate [B, T], injected noise_dp [B, 2, T] / noise_z [B, inter, >= F]: each part gets its own rows of all of
         them; return_durations adds "durations" [B, T], the parts' rows in request order).  One worker thread per sub-batch (the C
@@ -2335,6 +2467,8 @@ class PipelinedSession:
             # (the parts' warped rows have lengths of their own behind the barrier that sizes the one result: not a pass-through)
             raise SessionError("Unexpected input: 'token_semitones' / 'compensate' are not covered by PipelinedSession "
                                "(MiSession.synthesize_batch takes them)")
+        if fit is not None:  # (a group may span the parts, and each part is a run of its own)
+            raise SessionError("Unexpected input: 'fit' is not covered by PipelinedSession (MiSession.synthesize_batch takes it)")
         if token_semitones_end is not None:  # (for the same reason)
             raise SessionError("Unexpected input: 'token_semitones_end' is not covered by PipelinedSession "
                                "(MiSession.synthesize_batch takes it)")
@@ -3312,6 +3446,29 @@ def test_durations(logw=None, dur=None, lens=None, length_scale=1.0, rows=None, 
                                          _ffi.ptr(w_ceil), _ffi.ptr(cum), _ffi.ptr(y_len))
     _glue_check(rc, "vits_test_durations")
     return w_ceil, cum, y_len
+
+
+def test_fit_durations(w, lens, fit, w_ceil=None, cum=None, y_len=None, device_id=0):
+    """fit_duration_kernel by value (vits_test_fit_durations): weights float32 [B, T], lens [B], a Fit; w_ceil / cum / y_len -
+    what rows of no group hold before the launch (default: a canary of -1s).  Returns (w_ceil float32 [B, T], cum int32
+    [B, T], y_len int32 [B], scale float64 [G], frames int64 [G], status int32 [G])."""
+    w = np.ascontiguousarray(w, np.float32)
+    lens = np.ascontiguousarray(lens, np.int64)
+    B, T = w.shape
+    g32, t64 = np.ascontiguousarray(fit.groups, np.int32), np.ascontiguousarray(fit.target_frames, np.int64)
+    m32 = np.array([int(v) for v in fit.modes], np.int32)
+    G = len(t64)
+    if g32.shape != (B,) or len(m32) != G:
+        raise SessionError(f"test_fit_durations: groups {g32.shape} for {B} rows, {len(m32)} modes for {G} groups")
+    c = _ffi.VitsFit(g32.ctypes.data, G, t64.ctypes.data, m32.ctypes.data)
+    wc = np.full((B, T), -1, np.float32) if w_ceil is None else np.array(w_ceil, np.float32).reshape(B, T)
+    cm = np.full((B, T), -1, np.int32) if cum is None else np.array(cum, np.int32).reshape(B, T)
+    yl = np.full(B, -1, np.int32) if y_len is None else np.array(y_len, np.int32).reshape(B)
+    scale, frames, status = np.zeros(G, np.float64), np.zeros(G, np.int64), np.zeros(G, np.int32)
+    _glue_check(_ffi.load().vits_test_fit_durations(device_id, _ffi.ptr(w), _ffi.ptr(lens), B, T, C.byref(c), _ffi.ptr(wc), _ffi.ptr(cm),
+                                                    _ffi.ptr(yl), _ffi.ptr(scale), _ffi.ptr(frames), _ffi.ptr(status)),
+                "vits_test_fit_durations")
+    return wc, cm, yl, scale, frames, status
 
 
 def test_expand_prior(m_logs, cum, lens, y_len, F, noise=None, noise_scale=0.667, rows=None, seeds=None, noise_frames=None,

@@ -664,6 +664,32 @@ class TTSVoice:
         if self._ratio() is not None or any(self._ratio(r) is not None for r in rates or ()):
             raise ValueError("phoneme_pitch is not covered with an output rate set")
 
+    def _duration_fit(self, duration, duration_mode: str, n_sentences: int, pauses: int, entry: str, pitched: bool):
+        """duration= / duration_mode= of the encoded entries -> a session.Fit with all sentences in one group, or None.
+        `pauses`: the samples of silence the call itself adds, at the delivered rate.  The target is
+        round((duration * delivered_rate - pauses) * native_rate / (delivered_rate * hop)) frames."""
+        import inspect
+        import math
+        if duration is None:
+            return None
+        from .session import FIT_MODES, Fit
+        if duration_mode not in FIT_MODES:
+            raise ValueError(f"duration_mode must be 'exact' or 'at_most' (got {duration_mode!r})")
+        if not (isinstance(duration, (int, float, np.integer, np.floating)) and np.isfinite(duration) and duration > 0):
+            raise ValueError(f"duration must be a finite number of seconds > 0 (got {duration!r})")
+        if pitched:
+            raise ValueError("duration together with phoneme_pitch / pitch_contour is not covered: the warped length is not the "
+                             "native frame count")
+        fn = getattr(self.session, entry, None)
+        if fn is None or "fit" not in inspect.signature(fn).parameters:
+            raise ValueError(f"duration needs a session that fits durations on the device ({entry}(fit=))")
+        rate, native, hop = self.sample_rate, int(self.config.sample_rate), int(self.session.hparam("hop"))
+        frames = int(math.floor((float(duration) * rate - pauses) * native / (rate * hop) + 0.5))
+        if frames < 1:
+            raise ValueError(f"duration {duration} s leaves {frames} frames for the speech behind {pauses} samples of pauses: "
+                             "below 1 frame")
+        return Fit.one_group(n_sentences, frames, duration_mode)
+
     @staticmethod
     def _padded_db(token_db) -> np.ndarray:
         """per-row dB lists -> [B, T], 0 dB behind each row's end (tokens of no frames: they never show)"""
@@ -710,7 +736,8 @@ class TTSVoice:
                            alignments: bool = False, trim_silence=None, trailing_silence: float = 0.0, loudness=None,
                            loudness_scope: str = "sentence", peak_ceiling: float = 0.0, max_gain_db: float = 30.0,
                            fade_in: float = 0.0, fade_out: float = 0.0, fade_curve: str = "linear", phoneme_gain_db=None,
-                           limit_ceiling: float = 0.0, limit_lookahead: float = 0.005, phoneme_pitch=None, pitch_contour=None):
+                           limit_ceiling: float = 0.0, limit_lookahead: float = 0.005, phoneme_pitch=None, pitch_contour=None,
+                           duration: Optional[float] = None, duration_mode: str = "exact"):
         """Extension: the whole text as ONE stream of encoded audio ("pcm16", "ulaw", "alaw", "f32"; audio_encoding).  All
         sentences render in one batch; with a session that delivers (MiSession.synthesize_delivered) post-processing,
         encoding and the packing happen on the device and only the encoded audio crosses the bus; any other session
@@ -757,6 +784,14 @@ class TTSVoice:
         (i + 1) / n.  phoneme_pitch, if given too, is added to both ends; a sum outside [-12, 12] is a ValueError naming the
         sentence.  Tempo, alignments and sample-valued options as for phoneme_pitch.  It needs a session that glides
         (ValueError otherwise) and is refused with an output rate set as phoneme_pitch is.
+        duration - SSML's <prosody duration>, in seconds: the text is FITTED to that length on the device (vitsmi.h, "fitted
+        durations": all sentences form one group and share one multiplier on the model's own durations, so the speech is what
+        the model renders at another length scale).  duration_mode "exact" meets it - to within half a frame, plus one sample
+        per sentence at an output rate -, "at_most" leaves a text alone that is already shorter.  The duration is that of the
+        RENDERED audio, the pauses this call adds included, BEFORE trim_silence: trimming shortens it further.  The model's
+        multiplier stays within [1/16, 16].  It needs a session whose synthesize_delivered takes fit= (ValueError otherwise), is
+        not covered together with phoneme_pitch / pitch_contour (ValueError), and a target below one frame is a ValueError.
+        The result's fit_scale and fit_status hold the multiplier and the outcome (session.last_fit()).
         Returns an audio_encoding.EncodedAudio."""
         from . import audio_encoding as ae
         from .sharding import pad_batch
@@ -788,6 +823,8 @@ class TTSVoice:
             token_st = [a for a, _ in pairs]
             token_st_end = None if pitch_contour is None else [b for _, b in pairs]
         durs = frames = spans = None
+        fit = self._duration_fit(duration, duration_mode, len(all_ids), len(all_ids) * (lead + tail), "synthesize_delivered", pitched)
+        fit_scale = fit_status = None
         if hasattr(self.session, "synthesize_delivered"):
             from .session import Segment
             ids, lens = pad_batch(all_ids)
@@ -812,10 +849,14 @@ class TTSVoice:
                 more["token_semitones"] = self._padded_db(token_st)
             if token_st_end is not None:
                 more["token_semitones_end"] = self._padded_db(token_st_end)
+            if fit is not None:
+                more["fit"] = fit
             out = self.session.synthesize_delivered(ids, lens, self._scales(cfg), sid, segments=segs, n_streams=1,
                                                     encoding=encoding, return_durations=want_dur, **more)
             data = out["streams"][0]
             counts = [int(n) for n in out["sample_lengths"]]
+            if fit is not None:
+                fit_scale, fit_status = float(out["fit_scale"][0]), int(out["fit_status"][0])
             if token_st is not None and want_dur:
                 spans = out["token_spans"]
             if trim is not None:
@@ -866,12 +907,13 @@ class TTSVoice:
                 for a in al:
                     a.start_sample += starts[b]
                 aligned.append(al)
-        return ae.EncodedAudio(data, encoding, self.sample_rate, starts, counts, aligned, loud, gains)
+        return ae.EncodedAudio(data, encoding, self.sample_rate, starts, counts, aligned, loud, gains, fit_scale, fit_status)
 
     def stream_encoded(self, text: str, syn_config: Optional[SynthesisConfig] = None, encoding: str = "pcm16",
                        chunk_frames: int = 64, sentence_silence: float = 0.0, ref_peak=None, fade_in: float = 0.0,
                        fade_out: float = 0.0, fade_curve: str = "linear", phoneme_gain_db=None, limit_ceiling: float = 0.0,
-                       limit_lookahead: float = 0.005, trim_silence=None, phoneme_pitch=None, pitch_contour=None):
+                       limit_lookahead: float = 0.005, trim_silence=None, phoneme_pitch=None, pitch_contour=None,
+                       duration: Optional[float] = None, duration_mode: str = "exact"):
         """Extension: synthesize_encoded's ONE stream as a generator of `bytes`, handed out while the audio still renders.
         All sentences render as one chunked batch (MiSession.synthesize_stream_encoded: post-processing, encoding and the
         masking to each sentence's own length happen on the device, per chunk).  Sentence 0's chunks are yielded as they
@@ -897,7 +939,10 @@ class TTSVoice:
         "streamed pitch"): the sentences are warped and glided piece by piece on the device - joined, still
         synthesize_encoded's bytes.  They need a session whose synthesize_stream_encoded takes token_semitones /
         token_semitones_end (ValueError otherwise: such a session's chunked entries have no warped form) and are refused with
-        an output rate set."""
+        an output rate set.
+        duration / duration_mode have the meanings and refusals of synthesize_encoded (vitsmi.h, "fitted durations"): the
+        duration is that of the rendered audio with its pauses, before trim_silence - joined, still synthesize_encoded's bytes.
+        They need a session whose synthesize_stream_encoded takes fit= (ValueError otherwise)."""
         import inspect
         from . import audio_encoding as ae
         fn = getattr(self.session, "synthesize_stream_encoded", None)
@@ -927,8 +972,10 @@ class TTSVoice:
                              "normalize_audio off")
         if int(chunk_frames) < 1:
             raise ValueError(f"chunk_frames must be >= 1 (got {chunk_frames})")
+        if duration is not None:  # (what does not depend on the text is refused by the call itself)
+            self._duration_fit(duration, duration_mode, 1, 0, "synthesize_stream_encoded", phoneme_pitch is not None or pitch_contour is not None)
         return self._stream_encoded(text, cfg, encoding, int(chunk_frames), lead, ref_peak, shape, phoneme_gain_db, limit, onset,
-                                    phoneme_pitch, pitch_contour)
+                                    phoneme_pitch, pitch_contour, duration, duration_mode)
 
     def _onset(self, trim_silence, cfg, ref_peak):
         """trim_silence of stream_encoded -> a session.Onset in samples at the delivered rate, or None.  A float is a threshold
@@ -952,7 +999,7 @@ class TTSVoice:
         return o if o.mode else None
 
     def _stream_encoded(self, text, cfg, encoding, chunk_frames, lead, ref_peak, shape=None, phoneme_gain_db=None, limit=None,
-                        onset=None, phoneme_pitch=None, pitch_contour=None):
+                        onset=None, phoneme_pitch=None, pitch_contour=None, duration=None, duration_mode="exact"):
         from . import audio_encoding as ae
         from .sharding import pad_batch
         token_db = token_st = token_st_end = None
@@ -971,6 +1018,7 @@ class TTSVoice:
         B = len(all_ids)
         if not B:
             return
+        fit = self._duration_fit(duration, duration_mode, B, B * lead, "synthesize_stream_encoded", pitched)
         shaped = shape is not None or token_db is not None or limit is not None or onset is not None
         peaks = None
         if cfg.normalize_audio:
@@ -1028,6 +1076,8 @@ class TTSVoice:
                 more["token_semitones"] = self._padded_db(token_st)
             if token_st_end is not None:
                 more["token_semitones_end"] = self._padded_db(token_st_end)
+            if fit is not None:
+                more["fit"] = fit
 
             def skipped(c, b):  # (a stream that is not trimmed has nothing to skip)
                 skip = getattr(c, "skip", None)
