@@ -3164,6 +3164,12 @@ static int host_rows(vits_handle *h, const float *scales, int B, const uint64_t 
     return VITS_OK;
 }
 
+// frames per utterance of a forced or fitted run: VITS_MAX_FORCED_FRAMES, and no more than keep its SAMPLES (frames * hop) in int
+static int64_t max_forced_frames(const vits_handle *h) {
+    const int64_t hop = h->model.hop > 0 ? h->model.hop : 1;
+    return VITS_MAX_FORCED_FRAMES < INT_MAX / hop ? VITS_MAX_FORCED_FRAMES : INT_MAX / hop;
+}
+
 // ... with vits_controls on top: forced durations or per-token rates, host [B][T].  Everything is checked here, on the
 // host, before anything is enqueued or allocated; a rejected call leaves the previous run's results readable.
 static int host_controls(vits_handle *h, const vits_controls *ctl, const int64_t *lens, int B, int T, RunRows &rr) {
@@ -3173,9 +3179,7 @@ static int host_controls(vits_handle *h, const vits_controls *ctl, const int64_t
     if (int rc = host_rows(h, ctl->scales_rows, B, ctl->seeds, rr)) return rc;
     if (ctl->durations && ctl->token_rate)
         return fail(h, VITS_E_ARG, "durations and token_rate are contradictory: forced durations leave nothing to scale");
-    // frames per utterance of a forced run: VITS_MAX_FORCED_FRAMES, and no more than keep its SAMPLES (frames * hop) in int
-    const int64_t hop = h->model.hop > 0 ? h->model.hop : 1;
-    const int64_t max_frames = VITS_MAX_FORCED_FRAMES < INT_MAX / hop ? VITS_MAX_FORCED_FRAMES : INT_MAX / hop;
+    const int64_t max_frames = max_forced_frames(h);
     for (int b = 0; b < B; b++) {
         if (lens[b] < 0 || lens[b] > T)
             return fail(h, VITS_E_ARG, "input_lengths[%d]=%lld outside [0,%d]", b, (long long)lens[b], T);
@@ -3207,9 +3211,7 @@ static int host_controls(vits_handle *h, const vits_controls *ctl, const int64_t
 static int host_fit(vits_handle *h, const vits_controls *ctl, const vits_fit *fit, int B, RunRows &rr) {
     if (!fit) return VITS_OK;
     if (B <= 0) return fail(h, VITS_E_ARG, "empty batch (B=%d)", B);
-    const int64_t hop = h->model.hop > 0 ? h->model.hop : 1;
-    const int64_t max_frames = VITS_MAX_FORCED_FRAMES < INT_MAX / hop ? VITS_MAX_FORCED_FRAMES : INT_MAX / hop;
-    const std::string e = fit_fault(fit, B, max_frames);
+    const std::string e = fit_fault(fit, B, max_forced_frames(h));
     if (!e.empty()) return fail(h, VITS_E_ARG, "%s", e.c_str());
     if (!fit_on(fit, B)) return VITS_OK;
     if (ctl && ctl->durations)
@@ -3430,61 +3432,6 @@ static int run_async_locked(vits_handle *h, const int64_t *ids, const int64_t *l
     return rc;
 }
 
-int vits_run_async(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const float scales[3],
-                   const int64_t *sid, const vits_noise *noise) {
-    if (int rc = check_dev(h)) return rc;
-    std::lock_guard<std::mutex> lk(h->mu);
-    vits_output dev{};
-    return run_async_locked(h, ids, lens, B, T, one_row(scales), sid, noise, &dev);
-}
-
-int vits_run_async_rows(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const float *scales,
-                        const int64_t *sid, const vits_noise *noise, const uint64_t *seeds) {
-    if (int rc = check_dev(h)) return rc;
-    std::lock_guard<std::mutex> lk(h->mu);
-    RunRows rr;
-    if (int rc = host_rows(h, scales, B, seeds, rr)) return rc;
-    vits_output dev{};
-    return run_async_locked(h, ids, lens, B, T, rr, sid, noise, &dev);
-}
-
-int vits_run(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const float scales[3],
-             const int64_t *sid, const vits_noise *noise, vits_output *out) {
-    if (int rc = check_dev(h)) return rc;
-    std::lock_guard<std::mutex> lk(h->mu);
-    hipStream_t st = h->stream;
-    vits_output dev{};
-    int rc = run_async_locked(h, ids, lens, B, T, one_row(scales), sid, noise, &dev);  // (out == NULL: run only)
-    if (rc == VITS_OK && !out) {
-        // run only: the caller fetches what it needs afterwards (vits_last_pcm16, vits_last_y_lengths, vits_tap)
-        if (hipStreamSynchronize(st) != hipSuccess)
-            rc = fail(h, VITS_E_DEVICE, "synchronisation failed: %s", hipGetErrorString(hipGetLastError()));
-        else
-            rc = range_check(h);
-    } else if (rc == VITS_OK) {
-        // one pinned block: [samples | frame counts]
-        const size_t n = (size_t)B * h->S, ybase = (n * 4 + 63) & ~size_t(63);
-        char *host = (char *)pinned_get(h, ybase + (size_t)B * 8);
-        if (!host)
-            rc = fail(h, VITS_E_NOMEM, "cannot allocate pinned output (%zu bytes)", n * 4);
-        else if (hipMemcpyAsync(host, dev.data, n * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                 hipStreamSynchronize(st) != hipSuccess) {
-            pinned_put(h, host);
-            rc = fail(h, VITS_E_DEVICE, "device-to-host copy failed: %s", hipGetErrorString(hipGetLastError()));
-        } else if ((rc = range_check(h)) != VITS_OK) {
-            pinned_put(h, host);  // clamped audio is not handed out
-        } else {
-            int64_t *hy = (int64_t *)(host + ybase);
-            for (int b = 0; b < B; b++) hy[b] = h->h_ylen[b];
-            out->data = (float *)host;
-            std::memcpy(out->dims, dev.dims, sizeof dev.dims);
-            out->y_lengths = hy;
-        }
-        if (rc != VITS_OK) hipStreamSynchronize(st);
-    }
-    return rc;
-}
-
 static int run_chunked_sink(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const RunRows &rr,
                             const int64_t *sid, const vits_noise *noise, const ChunkSink &sink) {
     if (!rr.scales || sink.chunk_frames < 1) return fail(h, VITS_E_ARG, "bad chunked-run arguments");
@@ -3498,11 +3445,6 @@ static int run_chunked_sink(vits_handle *h, const int64_t *ids, const int64_t *l
     // (chunks are handed out as they finish; a range violation is therefore reported after the fact)
     if (rc == VITS_OK) rc = range_check(h);
     return rc;
-}
-
-static int run_chunked_locked(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const RunRows &rr,
-                              const int64_t *sid, const vits_noise *noise, int chunk_frames, vits_chunk_fn fn, void *user) {
-    return run_chunked_sink(h, ids, lens, B, T, rr, sid, noise, ChunkSink{chunk_frames, fn, user});
 }
 
 // vits_stream_format, checked on the host before anything else looks at the call (vitsmi.h, "encoded streaming")
@@ -3557,111 +3499,23 @@ int vits_stream_onset_start(int64_t f, int64_t keep_lead, int64_t delivered_befo
     return VITS_OK;
 }
 
-// the three encoded entries of the whole path: fn without, tfn with the rows' skips
-static int run_chunked_enc(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid, const vits_noise *noise,
-                           const vits_controls *ctl, const vits_stream_format *fmt, const vits_stream_shaping *shaping,
-                           const vits_stream_onset *onsets, int chunk_frames, vits_enc_chunk_fn fn, vits_enc_chunk_trim_fn tfn, void *user,
-                           const vits_fit *fit = nullptr) {
-    if (!h) return VITS_E_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (int rc = host_stream_format(h, fmt, B)) return rc;  // (pure host code: a host-only handle answers it too)
-    if (int rc = host_stream_shaping(h, shaping, fmt, B)) return rc;
-    if (int rc = host_stream_onsets(h, onsets, fmt, B)) return rc;
-    RunRows rr;
-    if (int rc = host_fit(h, ctl, fit, B, rr)) return rc;
-    if (int rc = check_dev(h)) return rc;
-    if (int rc = host_controls(h, ctl, lens, B, T, rr)) return rc;
-    ChunkSink sink{chunk_frames, nullptr, user};
-    sink.fmt = fmt;
-    sink.efn = fn;
-    sink.shaping = shaping;
-    sink.onsets = onsets;
-    sink.tfn = tfn;
-    return run_chunked_sink(h, ids, lens, B, T, rr, sid, noise, sink);
+// the sink of an encoded entry, whole path or vocoder: its chunks go to the entry's one callback - `fn`, or `tfn` with the rows' skips
+static ChunkSink encoded_sink(int chunk_frames, const vits_stream_format *fmt, const vits_stream_shaping *shaping,
+                              const vits_stream_onset *onsets, vits_enc_chunk_fn fn, vits_enc_chunk_trim_fn tfn, void *user) {
+    return ChunkSink{chunk_frames, nullptr, user, fmt, fn, shaping, onsets, tfn};
 }
 
-int vits_run_chunked_enc_trimmed(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
-                                 const vits_noise *noise, const vits_controls *ctl, const vits_stream_format *fmt,
-                                 const vits_stream_shaping *shaping, const vits_stream_onset *onsets, int chunk_frames,
-                                 vits_enc_chunk_trim_fn fn, void *user) {
-    return run_chunked_enc(h, ids, lens, B, T, sid, noise, ctl, fmt, shaping, onsets, chunk_frames, nullptr, fn, user);
-}
-
-int vits_run_chunked_enc_fitted(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
-                                const vits_noise *noise, const vits_controls *ctl, const vits_stream_format *fmt,
-                                const vits_stream_shaping *shaping, const vits_stream_onset *onsets, const vits_fit *fit,
-                                int chunk_frames, vits_enc_chunk_trim_fn fn, void *user) {
-    return run_chunked_enc(h, ids, lens, B, T, sid, noise, ctl, fmt, shaping, onsets, chunk_frames, nullptr, fn, user, fit);
-}
-
-int vits_run_chunked_enc_shaped(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
-                                const vits_noise *noise, const vits_controls *ctl, const vits_stream_format *fmt,
-                                const vits_stream_shaping *shaping, int chunk_frames, vits_enc_chunk_fn fn, void *user) {
-    return run_chunked_enc(h, ids, lens, B, T, sid, noise, ctl, fmt, shaping, nullptr, chunk_frames, fn, nullptr, user);
-}
-
-int vits_run_chunked_enc(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
-                         const vits_noise *noise, const vits_controls *ctl, const vits_stream_format *fmt, int chunk_frames,
-                         vits_enc_chunk_fn fn, void *user) {
-    return vits_run_chunked_enc_shaped(h, ids, lens, B, T, sid, noise, ctl, fmt, nullptr, chunk_frames, fn, user);
-}
-
-int vits_run_chunked(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const float scales[3],
-                     const int64_t *sid, const vits_noise *noise, int chunk_frames, vits_chunk_fn fn, void *user) {
-    if (int rc = check_dev(h)) return rc;
-    std::lock_guard<std::mutex> lk(h->mu);
-    return run_chunked_locked(h, ids, lens, B, T, one_row(scales), sid, noise, chunk_frames, fn, user);
-}
-
-int vits_run_chunked_rows(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const float *scales,
-                          const int64_t *sid, const vits_noise *noise, const uint64_t *seeds, int chunk_frames,
-                          vits_chunk_fn fn, void *user) {
-    if (int rc = check_dev(h)) return rc;
-    std::lock_guard<std::mutex> lk(h->mu);
-    RunRows rr;
-    if (int rc = host_rows(h, scales, B, seeds, rr)) return rc;
-    return run_chunked_locked(h, ids, lens, B, T, rr, sid, noise, chunk_frames, fn, user);
-}
-
-int vits_run_async_ctl(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
-                       const vits_noise *noise, const vits_controls *ctl) {
-    if (int rc = check_dev(h)) return rc;
-    std::lock_guard<std::mutex> lk(h->mu);
-    RunRows rr;
-    if (int rc = host_controls(h, ctl, lens, B, T, rr)) return rc;
-    vits_output dev{};
-    return run_async_locked(h, ids, lens, B, T, rr, sid, noise, &dev);
-}
-
-// vits_run_async_ctl / vits_run_chunked_ctl with a fit on top (vitsmi.h, "fitted durations")
-int vits_run_async_fitted(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
-                          const vits_noise *noise, const vits_controls *ctl, const vits_fit *fit) {
-    if (!h) return VITS_E_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    RunRows rr;
-    if (int rc = host_fit(h, ctl, fit, B, rr)) return rc;
-    if (int rc = check_dev(h)) return rc;
-    if (int rc = host_controls(h, ctl, lens, B, T, rr)) return rc;
-    vits_output dev{};
-    return run_async_locked(h, ids, lens, B, T, rr, sid, noise, &dev);
-}
-
-int vits_run_chunked_fitted(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
-                            const vits_noise *noise, const vits_controls *ctl, const vits_fit *fit, int chunk_frames,
-                            vits_chunk_fn fn, void *user) {
-    if (!h) return VITS_E_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    RunRows rr;
-    if (int rc = host_fit(h, ctl, fit, B, rr)) return rc;
-    if (int rc = check_dev(h)) return rc;
-    if (int rc = host_controls(h, ctl, lens, B, T, rr)) return rc;
-    return run_chunked_locked(h, ids, lens, B, T, rr, sid, noise, chunk_frames, fn, user);
+// ... and its stream arguments, checked in their one order (pure host code: a host-only handle answers it too)
+static int host_stream(vits_handle *h, const ChunkSink &sink, int B) {
+    if (int rc = host_stream_format(h, sink.fmt, B)) return rc;
+    if (int rc = host_stream_shaping(h, sink.shaping, sink.fmt, B)) return rc;
+    return host_stream_onsets(h, sink.onsets, sink.fmt, B);
 }
 
 // vits_run_async_ctl with the intonation on top (vitsmi.h, "intonation").  What is pure host code - the semitones, the
 // contradictions, the rates that are set - is answered before the device is looked at: a host-only handle answers it too.
-// One body serves both entries: st0 the start values (NULL: zeros), st1 the end values (NULL: every token keeps its speed - the
-// warp's entry); `entry` names the caller in the refusal of an output rate.
+// One body serves every entry with pitch: st0 the start values (NULL: zeros), st1 the end values (NULL: every token keeps its
+// speed - the warp's entry); `entry` names the caller in the refusal of an output rate.
 // what host_intonation makes of a call: the controls with compensate's duration multiplier folded in, and the values a warped run plans from
 struct Intoned {
     vits_controls ctl{};
@@ -3724,34 +3578,203 @@ static int host_intonation(vits_handle *h, const vits_controls *ctl, const int64
     return VITS_OK;
 }
 
-static int run_intoned_locked(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
-                              const vits_noise *noise, const vits_controls *ctl, const float *st0, const float *st1, int compensate,
-                              const char *entry) {
-    Intoned in;
-    if (int rc = host_intonation(h, ctl, lens, B, T, st0, st1, compensate, entry, in)) return rc;
-    if (int rc = check_dev(h)) return rc;
+// One request of the whole path: what a vits_run / vits_run_async* / vits_run_chunked* entry may pass, and where its audio goes.
+// Every such entry fills one - the head by position, the rest through the setters - and hands it to run_call.
+struct RunCall {
+    const int64_t *ids, *lens;
+    int B, T;
+    const int64_t *sid;
+    const vits_noise *noise;
+    // the settings: one [3] vector for the whole batch, or [B][3] rows and seeds, or a vits_controls
+    enum { kScales, kRows, kControls } settings = kScales;
+    const float *scales = nullptr;
+    const uint64_t *seeds = nullptr;
+    const vits_controls *ctl = nullptr;
+    const vits_fit *fit = nullptr;  // on top of the controls, nullable (vitsmi.h, "fitted durations")
+    // ... or the intonation on top of them: `entry` names an entry that takes one, st0 / st1 as host_intonation
+    const char *entry = nullptr;
+    const float *st0 = nullptr, *st1 = nullptr;
+    int compensate = 0;
+    // where the audio goes: it stays on the device (`dev`, if set, learns where), or fp32 chunks, or encoded ones (encoded_sink)
+    enum { kAsync, kChunks, kEncoded } out = kAsync;
+    vits_output *dev = nullptr;
+    ChunkSink sink{};
+
+    RunCall &one_row(const float *s) { scales = s; return *this; }
+    RunCall &rows(const float *s, const uint64_t *sd) { settings = kRows; scales = s; seeds = sd; return *this; }
+    RunCall &controls(const vits_controls *c, const vits_fit *f = nullptr) { settings = kControls; ctl = c; fit = f; return *this; }
+    RunCall &contour(const char *name, const float *a, const float *b, int comp) { entry = name; st0 = a; st1 = b; compensate = comp; return *this; }
+    RunCall &glided(const char *name, const vits_contour *c) {
+        return c ? contour(name, c->token_semitones, c->token_semitones_end, c->compensate) : contour(name, nullptr, nullptr, 0);
+    }
+    RunCall &chunks(int chunk_frames, vits_chunk_fn fn, void *user) { out = kChunks; sink = ChunkSink{chunk_frames, fn, user}; return *this; }
+    RunCall &encoded(const ChunkSink &s) { out = kEncoded; sink = s; return *this; }
+};
+
+// The one order in which a call's faults are reported; a step is taken by the entries that have its argument.  What is pure
+// host code about the stream, the fit and the intonation is answered before the device is looked at - a host-only handle
+// answers it too -; the settings themselves (host_controls / host_rows) are looked at behind the device.
+static int run_call_locked(vits_handle *h, const RunCall &c) {
+    if (c.out == RunCall::kEncoded)
+        if (int rc = host_stream(h, c.sink, c.B)) return rc;
     RunRows rr;
-    if (int rc = host_controls(h, &in.ctl, lens, B, T, rr)) return rc;
-    in.apply(rr, lens);
+    if (int rc = host_fit(h, c.ctl, c.fit, c.B, rr)) return rc;
+    Intoned in;
+    if (c.entry)
+        if (int rc = host_intonation(h, c.ctl, c.lens, c.B, c.T, c.st0, c.st1, c.compensate, c.entry, in)) return rc;
+    if (int rc = check_dev(h)) return rc;
+    if (c.settings == RunCall::kScales) rr = one_row(c.scales);
+    else if (c.settings == RunCall::kRows) {
+        if (int rc = host_rows(h, c.scales, c.B, c.seeds, rr)) return rc;
+    } else if (int rc = host_controls(h, c.entry ? &in.ctl : c.ctl, c.lens, c.B, c.T, rr)) return rc;
+    in.apply(rr, c.lens);
+    if (c.out != RunCall::kAsync) return run_chunked_sink(h, c.ids, c.lens, c.B, c.T, rr, c.sid, c.noise, c.sink);
     vits_output dev{};
-    return run_async_locked(h, ids, lens, B, T, rr, sid, noise, &dev);
+    return run_async_locked(h, c.ids, c.lens, c.B, c.T, rr, c.sid, c.noise, c.dev ? c.dev : &dev);
+}
+
+static int run_call(vits_handle *h, const RunCall &c) {
+    if (!h) return VITS_E_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    return run_call_locked(h, c);
+}
+
+int vits_run_async(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const float scales[3],
+                   const int64_t *sid, const vits_noise *noise) {
+    return run_call(h, RunCall{ids, lens, B, T, sid, noise}.one_row(scales));
+}
+
+int vits_run_async_rows(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const float *scales,
+                        const int64_t *sid, const vits_noise *noise, const uint64_t *seeds) {
+    return run_call(h, RunCall{ids, lens, B, T, sid, noise}.rows(scales, seeds));
+}
+
+int vits_run_async_ctl(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
+                       const vits_noise *noise, const vits_controls *ctl) {
+    return run_call(h, RunCall{ids, lens, B, T, sid, noise}.controls(ctl));
+}
+
+// vits_run_async_ctl / vits_run_chunked_ctl with a fit on top (vitsmi.h, "fitted durations")
+int vits_run_async_fitted(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
+                          const vits_noise *noise, const vits_controls *ctl, const vits_fit *fit) {
+    return run_call(h, RunCall{ids, lens, B, T, sid, noise}.controls(ctl, fit));
 }
 
 int vits_run_async_warped(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
                           const vits_noise *noise, const vits_controls *ctl, const vits_intonation *into) {
-    if (!h) return VITS_E_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    return run_intoned_locked(h, ids, lens, B, T, sid, noise, ctl, into ? into->token_semitones : nullptr, nullptr,
-                              into ? into->compensate : 0, "vits_run_async_warped");
+    return run_call(h, RunCall{ids, lens, B, T, sid, noise}.controls(ctl).contour(
+                           "vits_run_async_warped", into ? into->token_semitones : nullptr, nullptr, into ? into->compensate : 0));
 }
 
 // ... and with a start and an end value per token (vitsmi.h, "pitch contours"): equal ends everywhere are the call above
 int vits_run_async_glided(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
                           const vits_noise *noise, const vits_controls *ctl, const vits_contour *contour) {
+    return run_call(h, RunCall{ids, lens, B, T, sid, noise}.controls(ctl).glided("vits_run_async_glided", contour));
+}
+
+int vits_run(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const float scales[3],
+             const int64_t *sid, const vits_noise *noise, vits_output *out) {
     if (!h) return VITS_E_ARG;
     std::lock_guard<std::mutex> lk(h->mu);
-    return run_intoned_locked(h, ids, lens, B, T, sid, noise, ctl, contour ? contour->token_semitones : nullptr,
-                              contour ? contour->token_semitones_end : nullptr, contour ? contour->compensate : 0, "vits_run_async_glided");
+    vits_output dev{};
+    RunCall c = RunCall{ids, lens, B, T, sid, noise}.one_row(scales);
+    c.dev = &dev;
+    int rc = run_call_locked(h, c);  // (out == NULL: run only)
+    hipStream_t st = h->stream;
+    if (rc == VITS_OK && !out) {
+        // run only: the caller fetches what it needs afterwards (vits_last_pcm16, vits_last_y_lengths, vits_tap)
+        if (hipStreamSynchronize(st) != hipSuccess)
+            rc = fail(h, VITS_E_DEVICE, "synchronisation failed: %s", hipGetErrorString(hipGetLastError()));
+        else
+            rc = range_check(h);
+    } else if (rc == VITS_OK) {
+        // one pinned block: [samples | frame counts]
+        const size_t n = (size_t)B * h->S, ybase = (n * 4 + 63) & ~size_t(63);
+        char *host = (char *)pinned_get(h, ybase + (size_t)B * 8);
+        if (!host)
+            rc = fail(h, VITS_E_NOMEM, "cannot allocate pinned output (%zu bytes)", n * 4);
+        else if (hipMemcpyAsync(host, dev.data, n * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                 hipStreamSynchronize(st) != hipSuccess) {
+            pinned_put(h, host);
+            rc = fail(h, VITS_E_DEVICE, "device-to-host copy failed: %s", hipGetErrorString(hipGetLastError()));
+        } else if ((rc = range_check(h)) != VITS_OK) {
+            pinned_put(h, host);  // clamped audio is not handed out
+        } else {
+            int64_t *hy = (int64_t *)(host + ybase);
+            for (int b = 0; b < B; b++) hy[b] = h->h_ylen[b];
+            out->data = (float *)host;
+            std::memcpy(out->dims, dev.dims, sizeof dev.dims);
+            out->y_lengths = hy;
+        }
+        if (rc != VITS_OK) hipStreamSynchronize(st);
+    }
+    return rc;
+}
+
+int vits_run_chunked(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const float scales[3],
+                     const int64_t *sid, const vits_noise *noise, int chunk_frames, vits_chunk_fn fn, void *user) {
+    return run_call(h, RunCall{ids, lens, B, T, sid, noise}.one_row(scales).chunks(chunk_frames, fn, user));
+}
+
+int vits_run_chunked_rows(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const float *scales,
+                          const int64_t *sid, const vits_noise *noise, const uint64_t *seeds, int chunk_frames,
+                          vits_chunk_fn fn, void *user) {
+    return run_call(h, RunCall{ids, lens, B, T, sid, noise}.rows(scales, seeds).chunks(chunk_frames, fn, user));
+}
+
+int vits_run_chunked_ctl(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
+                         const vits_noise *noise, const vits_controls *ctl, int chunk_frames, vits_chunk_fn fn, void *user) {
+    return run_call(h, RunCall{ids, lens, B, T, sid, noise}.controls(ctl).chunks(chunk_frames, fn, user));
+}
+
+int vits_run_chunked_fitted(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
+                            const vits_noise *noise, const vits_controls *ctl, const vits_fit *fit, int chunk_frames,
+                            vits_chunk_fn fn, void *user) {
+    return run_call(h, RunCall{ids, lens, B, T, sid, noise}.controls(ctl, fit).chunks(chunk_frames, fn, user));
+}
+
+// The chunked entries with pitch (vitsmi.h, "streamed pitch"): the checks are the whole run's (host_intonation), before anything is
+// enqueued.  All-zero semitones leave rr without them: the call then is vits_run_chunked_ctl / vits_run_chunked_enc* itself.
+int vits_run_chunked_glided(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid, const vits_noise *noise,
+                            const vits_controls *ctl, const vits_contour *contour, int chunk_frames, vits_chunk_fn fn, void *user) {
+    return run_call(h, RunCall{ids, lens, B, T, sid, noise}.controls(ctl).glided("vits_run_chunked_glided", contour).chunks(chunk_frames, fn, user));
+}
+
+// The encoded entries of the whole path: the plain callback without onsets, the trimmed one with the rows' skips
+int vits_run_chunked_enc_shaped(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
+                                const vits_noise *noise, const vits_controls *ctl, const vits_stream_format *fmt,
+                                const vits_stream_shaping *shaping, int chunk_frames, vits_enc_chunk_fn fn, void *user) {
+    return run_call(h, RunCall{ids, lens, B, T, sid, noise}.controls(ctl).encoded(
+                           encoded_sink(chunk_frames, fmt, shaping, nullptr, fn, nullptr, user)));
+}
+
+int vits_run_chunked_enc(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
+                         const vits_noise *noise, const vits_controls *ctl, const vits_stream_format *fmt, int chunk_frames,
+                         vits_enc_chunk_fn fn, void *user) {
+    return vits_run_chunked_enc_shaped(h, ids, lens, B, T, sid, noise, ctl, fmt, nullptr, chunk_frames, fn, user);
+}
+
+int vits_run_chunked_enc_fitted(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
+                                const vits_noise *noise, const vits_controls *ctl, const vits_stream_format *fmt,
+                                const vits_stream_shaping *shaping, const vits_stream_onset *onsets, const vits_fit *fit,
+                                int chunk_frames, vits_enc_chunk_trim_fn fn, void *user) {
+    return run_call(h, RunCall{ids, lens, B, T, sid, noise}.controls(ctl, fit).encoded(
+                           encoded_sink(chunk_frames, fmt, shaping, onsets, nullptr, fn, user)));
+}
+
+int vits_run_chunked_enc_trimmed(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
+                                 const vits_noise *noise, const vits_controls *ctl, const vits_stream_format *fmt,
+                                 const vits_stream_shaping *shaping, const vits_stream_onset *onsets, int chunk_frames,
+                                 vits_enc_chunk_trim_fn fn, void *user) {
+    return vits_run_chunked_enc_fitted(h, ids, lens, B, T, sid, noise, ctl, fmt, shaping, onsets, nullptr, chunk_frames, fn, user);
+}
+
+int vits_run_chunked_enc_glided(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
+                                const vits_noise *noise, const vits_controls *ctl, const vits_stream_format *fmt,
+                                const vits_stream_shaping *shaping, const vits_stream_onset *onsets, const vits_contour *contour,
+                                int chunk_frames, vits_enc_chunk_trim_fn fn, void *user) {
+    return run_call(h, RunCall{ids, lens, B, T, sid, noise}.controls(ctl).glided("vits_run_chunked_enc_glided", contour).encoded(
+                           encoded_sink(chunk_frames, fmt, shaping, onsets, nullptr, fn, user)));
 }
 
 int vits_last_token_spans(vits_handle *h, int64_t *buf, size_t n_elems) {
@@ -3840,57 +3863,6 @@ int vits_glide_emit_end(const vits_glide_seg *segs, int n_segs, int64_t n_in, in
 int64_t vits_warp_stream_cap(int64_t piece_samples, int64_t S_w) {
     if (piece_samples < 1 || S_w < 1) return fail(nullptr, VITS_E_ARG, "bad stream cap arguments (%lld, %lld)", (long long)piece_samples, (long long)S_w);
     return warp_stream_cap(piece_samples, S_w);
-}
-
-int vits_run_chunked_ctl(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
-                         const vits_noise *noise, const vits_controls *ctl, int chunk_frames, vits_chunk_fn fn, void *user) {
-    if (int rc = check_dev(h)) return rc;
-    std::lock_guard<std::mutex> lk(h->mu);
-    RunRows rr;
-    if (int rc = host_controls(h, ctl, lens, B, T, rr)) return rc;
-    return run_chunked_locked(h, ids, lens, B, T, rr, sid, noise, chunk_frames, fn, user);
-}
-
-// The chunked entries with pitch (vitsmi.h, "streamed pitch"): the checks are the whole run's (host_intonation), before anything is
-// enqueued.  All-zero semitones leave rr without them: the call then is vits_run_chunked_ctl / vits_run_chunked_enc* itself.
-int vits_run_chunked_glided(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid, const vits_noise *noise,
-                            const vits_controls *ctl, const vits_contour *contour, int chunk_frames, vits_chunk_fn fn, void *user) {
-    if (!h) return VITS_E_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    Intoned in;
-    if (int rc = host_intonation(h, ctl, lens, B, T, contour ? contour->token_semitones : nullptr, contour ? contour->token_semitones_end : nullptr,
-                                 contour ? contour->compensate : 0, "vits_run_chunked_glided", in))
-        return rc;
-    if (int rc = check_dev(h)) return rc;
-    RunRows rr;
-    if (int rc = host_controls(h, &in.ctl, lens, B, T, rr)) return rc;
-    in.apply(rr, lens);
-    return run_chunked_locked(h, ids, lens, B, T, rr, sid, noise, chunk_frames, fn, user);
-}
-
-int vits_run_chunked_enc_glided(vits_handle *h, const int64_t *ids, const int64_t *lens, int B, int T, const int64_t *sid,
-                                const vits_noise *noise, const vits_controls *ctl, const vits_stream_format *fmt,
-                                const vits_stream_shaping *shaping, const vits_stream_onset *onsets, const vits_contour *contour,
-                                int chunk_frames, vits_enc_chunk_trim_fn fn, void *user) {
-    if (!h) return VITS_E_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (int rc = host_stream_format(h, fmt, B)) return rc;
-    if (int rc = host_stream_shaping(h, shaping, fmt, B)) return rc;
-    if (int rc = host_stream_onsets(h, onsets, fmt, B)) return rc;
-    Intoned in;
-    if (int rc = host_intonation(h, ctl, lens, B, T, contour ? contour->token_semitones : nullptr, contour ? contour->token_semitones_end : nullptr,
-                                 contour ? contour->compensate : 0, "vits_run_chunked_enc_glided", in))
-        return rc;
-    if (int rc = check_dev(h)) return rc;
-    RunRows rr;
-    if (int rc = host_controls(h, &in.ctl, lens, B, T, rr)) return rc;
-    in.apply(rr, lens);
-    ChunkSink sink{chunk_frames, nullptr, user};
-    sink.fmt = fmt;
-    sink.shaping = shaping;
-    sink.onsets = onsets;
-    sink.tfn = fn;
-    return run_chunked_sink(h, ids, lens, B, T, rr, sid, noise, sink);
 }
 
 void vits_free_output(vits_handle *h, vits_output *out) {
@@ -4249,43 +4221,31 @@ int vits_run_vocoder(vits_handle *h, const float *z, int B, int F, const int64_t
     return vocoder_common(h, z, B, F, sid, out, nullptr);
 }
 
-int vits_run_vocoder_chunked(vits_handle *h, const float *z, int B, int F, const int64_t *sid, int chunk_frames,
-                             vits_chunk_fn fn, void *user) {
-    if (int rc = check_dev(h)) return rc;
+// the chunked vocoder entries, in the order of run_call_locked: the stream arguments of an encoded sink, then the device
+static int run_vocoder_chunked(vits_handle *h, const float *z, int B, int F, const int64_t *sid, bool encoded, const ChunkSink &sink) {
+    if (!h) return VITS_E_ARG;
     std::lock_guard<std::mutex> lk(h->mu);
-    if (chunk_frames < 1) return fail(h, VITS_E_ARG, "bad vocoder arguments");
-    const ChunkSink sink{chunk_frames, fn, user};
+    if (encoded)
+        if (int rc = host_stream(h, sink, B)) return rc;
+    if (int rc = check_dev(h)) return rc;
+    if (sink.chunk_frames < 1) return fail(h, VITS_E_ARG, "bad vocoder arguments");
     return vocoder_common(h, z, B, F, sid, nullptr, &sink);
 }
 
-static int run_vocoder_chunked_enc(vits_handle *h, const float *z, int B, int F, const int64_t *sid, const vits_stream_format *fmt,
-                                   const vits_stream_shaping *shaping, const vits_stream_onset *onsets, int chunk_frames, vits_enc_chunk_fn fn,
-                                   vits_enc_chunk_trim_fn tfn, void *user) {
-    if (!h) return VITS_E_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (int rc = host_stream_format(h, fmt, B)) return rc;
-    if (int rc = host_stream_shaping(h, shaping, fmt, B)) return rc;
-    if (int rc = host_stream_onsets(h, onsets, fmt, B)) return rc;
-    if (int rc = check_dev(h)) return rc;
-    if (chunk_frames < 1) return fail(h, VITS_E_ARG, "bad vocoder arguments");
-    ChunkSink sink{chunk_frames, nullptr, user};
-    sink.fmt = fmt;
-    sink.efn = fn;
-    sink.shaping = shaping;
-    sink.onsets = onsets;
-    sink.tfn = tfn;
-    return vocoder_common(h, z, B, F, sid, nullptr, &sink);
+int vits_run_vocoder_chunked(vits_handle *h, const float *z, int B, int F, const int64_t *sid, int chunk_frames,
+                             vits_chunk_fn fn, void *user) {
+    return run_vocoder_chunked(h, z, B, F, sid, false, ChunkSink{chunk_frames, fn, user});
 }
 
 int vits_run_vocoder_chunked_enc_trimmed(vits_handle *h, const float *z, int B, int F, const int64_t *sid, const vits_stream_format *fmt,
                                          const vits_stream_shaping *shaping, const vits_stream_onset *onsets, int chunk_frames,
                                          vits_enc_chunk_trim_fn fn, void *user) {
-    return run_vocoder_chunked_enc(h, z, B, F, sid, fmt, shaping, onsets, chunk_frames, nullptr, fn, user);
+    return run_vocoder_chunked(h, z, B, F, sid, true, encoded_sink(chunk_frames, fmt, shaping, onsets, nullptr, fn, user));
 }
 
 int vits_run_vocoder_chunked_enc_shaped(vits_handle *h, const float *z, int B, int F, const int64_t *sid, const vits_stream_format *fmt,
                                         const vits_stream_shaping *shaping, int chunk_frames, vits_enc_chunk_fn fn, void *user) {
-    return run_vocoder_chunked_enc(h, z, B, F, sid, fmt, shaping, nullptr, chunk_frames, fn, nullptr, user);
+    return run_vocoder_chunked(h, z, B, F, sid, true, encoded_sink(chunk_frames, fmt, shaping, nullptr, fn, nullptr, user));
 }
 
 int vits_run_vocoder_chunked_enc(vits_handle *h, const float *z, int B, int F, const int64_t *sid, const vits_stream_format *fmt,

@@ -221,6 +221,19 @@ def _controls(rows, seeds, durations, token_rate):
     return c
 
 
+def _noise(seed, noise_dp=None, noise_z=None):
+    """The vits_noise struct of a call: the session's seed and, for parity runs, the injected noise as contiguous float32.
+    Like _controls, the struct holds the arrays it points into (`_keep`)."""
+    n = _ffi.VitsNoise()
+    n.seed = seed
+    n._keep = [None if a is None else np.ascontiguousarray(a, np.float32) for a in (noise_dp, noise_z)]
+    if noise_dp is not None:
+        n.noise_dp = n._keep[0].ctypes.data
+    if noise_z is not None:
+        n.noise_z, n.noise_z_stride = n._keep[1].ctypes.data, n._keep[1].shape[2]
+    return n
+
+
 FIT_MODES = {"exact": 1, "at_most": 2}
 VITS_MAX_FORCED_FRAMES = 1 << 24
 
@@ -1238,20 +1251,15 @@ class MiSession:
             sid = np.ascontiguousarray(sid)
             if sid.dtype != np.int64 or sid.shape != (B,):
                 raise SessionError("Unexpected input: 'sid' must be int64 of shape [batch_size]")
-        noise = _ffi.VitsNoise()
-        noise.seed = self._seed
         if noise_dp is not None:
             noise_dp = np.ascontiguousarray(noise_dp, np.float32)
             if noise_dp.shape != (B, 2, T):
                 raise SessionError(f"noise_dp must be [B,2,T], got {noise_dp.shape}")
-            noise.noise_dp = noise_dp.ctypes.data
         if noise_z is not None:
             noise_z = np.ascontiguousarray(noise_z, np.float32)
             if noise_z.ndim != 3 or noise_z.shape[0] != B or noise_z.shape[1] != self.hparam("inter"):
                 raise SessionError(f"noise_z must be [B,inter,F], got {noise_z.shape}")
-            noise.noise_z = noise_z.ctypes.data
-            noise.noise_z_stride = noise_z.shape[2]
-        return ids, lens, scales, sid, noise_dp, noise_z, noise, seeds, durations, token_rate
+        return ids, lens, scales, sid, noise_dp, noise_z, _noise(self._seed, noise_dp, noise_z), seeds, durations, token_rate
 
     def _begin(self, ids, lens, scales, sid, noise, seeds=None, durations=None, token_rate=None, semitones=None, compensate=True,
                semitones_end=None, fit=None):
@@ -1259,34 +1267,24 @@ class MiSession:
         return.  ([B, 3] scales or seeds: vits_run_async_rows; durations or token_rate: vits_run_async_ctl; semitones:
         vits_run_async_warped; semitones_end too: vits_run_async_glided.)"""
         B, T = ids.shape
-        if fit is not None:  # (a vits_fit struct of _fit: vits_run_async_fitted)
-            ctl = _controls(_rows(scales, B), seeds, durations, token_rate)
-            rc = self._lib.vits_run_async_fitted(self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(sid), C.byref(noise),
-                                                 C.byref(ctl), C.byref(fit))
+        head = (self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T)
+        rows = _rows(scales, B)
+        ctl = _controls(rows, seeds, durations, token_rate)
+        with_ctl = head + (_ffi.ptr(sid), C.byref(noise), C.byref(ctl))
+        if fit is not None:  # (a vits_fit struct of _fit)
+            rc = self._lib.vits_run_async_fitted(*with_ctl, C.byref(fit))
         elif semitones_end is not None:
-            rows = _rows(scales, B)
-            ctl = _controls(rows, seeds, durations, token_rate)
             contour = _ffi.VitsContour(semitones.ctypes.data, semitones_end.ctypes.data, 1 if compensate else 0)
-            rc = self._lib.vits_run_async_glided(self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(sid), C.byref(noise),
-                                                 C.byref(ctl), C.byref(contour))
+            rc = self._lib.vits_run_async_glided(*with_ctl, C.byref(contour))
         elif semitones is not None:
-            rows = _rows(scales, B)
-            ctl = _controls(rows, seeds, durations, token_rate)
             into = _ffi.VitsIntonation(semitones.ctypes.data, 1 if compensate else 0)
-            rc = self._lib.vits_run_async_warped(self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(sid), C.byref(noise),
-                                                 C.byref(ctl), C.byref(into))
+            rc = self._lib.vits_run_async_warped(*with_ctl, C.byref(into))
         elif durations is not None or token_rate is not None:
-            rows = _rows(scales, B)
-            ctl = _controls(rows, seeds, durations, token_rate)
-            rc = self._lib.vits_run_async_ctl(self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(sid), C.byref(noise),
-                                              C.byref(ctl))
+            rc = self._lib.vits_run_async_ctl(*with_ctl)
         elif scales.ndim == 1 and seeds is None:
-            rc = self._lib.vits_run_async(self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(scales), _ffi.ptr(sid),
-                                          C.byref(noise))
+            rc = self._lib.vits_run_async(*head, _ffi.ptr(scales), _ffi.ptr(sid), C.byref(noise))
         else:
-            rows = _rows(scales, B)
-            rc = self._lib.vits_run_async_rows(self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(rows), _ffi.ptr(sid),
-                                               C.byref(noise), _ffi.ptr(seeds))
+            rc = self._lib.vits_run_async_rows(*head, _ffi.ptr(rows), _ffi.ptr(sid), C.byref(noise), _ffi.ptr(seeds))
         if rc != 0:
             self._raise("vits_run", rc)
 
@@ -1412,6 +1410,31 @@ class MiSession:
         last_sample_counts() / last_token_spans() answer from the first chunk on.  Not covered with an output rate set.
         fit - as synthesize_batch (vitsmi.h, "fitted durations"): the chunks, joined, are the fitted run's "output"; last_fit()
         answers from the first chunk on.  Not together with durations or token_semitones (ValueError)."""
+        ids, lens, scales, seeds, sid, noise, ctl, on_top, _, _ = self._stream_arguments(
+            "synthesize_stream", ids, lens, scales, sid, noise_dp, noise_z, seeds, durations, token_rate, token_semitones,
+            compensate, token_semitones_end, fit)
+        B, T = ids.shape
+
+        def start(cb):
+            def call(name, *args):
+                return getattr(self._lib, name)(self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, *args, int(chunk_frames), cb, None)
+            if on_top is not None:
+                return call("vits_run_chunked" + on_top[0], _ffi.ptr(sid), C.byref(noise), C.byref(ctl), C.byref(on_top[1]))
+            if ctl.durations or ctl.token_rate:
+                return call("vits_run_chunked_ctl", _ffi.ptr(sid), C.byref(noise), C.byref(ctl))
+            if scales.ndim == 1 and seeds is None:
+                return call("vits_run_chunked", _ffi.ptr(scales), _ffi.ptr(sid), C.byref(noise))
+            return call("vits_run_chunked_rows", ctl.scales_rows, _ffi.ptr(sid), C.byref(noise), _ffi.ptr(seeds))
+
+        return self._stream(start)
+
+    def _stream_arguments(self, name, ids, lens, scales, sid, noise_dp, noise_z, seeds, durations, token_rate, token_semitones,
+                          compensate, token_semitones_end, fit):
+        """The arguments that synthesize_stream and synthesize_stream_encoded (`name`) share, validated and made contiguous -
+        the C call runs on _stream's worker thread after the method has returned: every host array it reads must belong to
+        its closure, the converted ones ride on the struct that points into them (`_keep`).  `on_top`: None, or what goes on
+        top of the controls as (the suffix of the entry that takes it, the struct) - ("_fitted", vits_fit) or ("_glided",
+        vits_contour); behind it the (start, end) semitones of _contour."""
         ids = np.ascontiguousarray(ids, np.int64)
         lens = np.ascontiguousarray(lens, np.int64)
         B, T = ids.shape
@@ -1420,46 +1443,16 @@ class MiSession:
         durations, token_rate = _timing(durations, token_rate, lens, B, T)
         cfit = _fit(fit, B, self.hparam("hop"), durations, semitones)
         sid = None if sid is None else np.ascontiguousarray(sid, np.int64)
-        noise = _ffi.VitsNoise()
-        noise.seed = self._seed
-        # (the C call runs on _stream's worker thread after this function has returned: every host array it reads must
-        # belong to the closure - the converted noise arrays ride on the struct that points into them)
-        keep = noise._keep = []
-        if noise_dp is not None:
-            keep.append(np.ascontiguousarray(noise_dp, np.float32))
-            noise.noise_dp = keep[-1].ctypes.data
-        if noise_z is not None:
-            keep.append(np.ascontiguousarray(noise_z, np.float32))
-            noise.noise_z = keep[-1].ctypes.data
-            noise.noise_z_stride = keep[-1].shape[2]
-        if cfit is not None:
-            ctl = _controls(_rows(scales, B), seeds, durations, token_rate)
-            return self._stream(lambda cb: self._lib.vits_run_chunked_fitted(
-                self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(sid), C.byref(noise), C.byref(ctl), C.byref(cfit),
-                int(chunk_frames), cb, None))
-        if semitones is not None:
-            self._pitch_admit("synthesize_stream", durations, compensate, semitones, semitones_end, lens)
-            ctl = _controls(_rows(scales, B), seeds, durations, token_rate)
+        noise = _noise(self._seed, noise_dp, noise_z)
+        ctl = _controls(_rows(scales, B), seeds, durations, token_rate)
+        on_top = None if cfit is None else ("_fitted", cfit)
+        if semitones is not None:  # (never with a fit: _fit has refused that)
+            self._pitch_admit(name, durations, compensate, semitones, semitones_end, lens)
             contour = _ffi.VitsContour(semitones.ctypes.data, None if semitones_end is None else semitones_end.ctypes.data,
                                        1 if compensate else 0)
             contour._keep = (semitones, semitones_end)
-            return self._stream(lambda cb: self._lib.vits_run_chunked_glided(
-                self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(sid), C.byref(noise), C.byref(ctl), C.byref(contour),
-                int(chunk_frames), cb, None))
-        if durations is not None or token_rate is not None:
-            rows = _rows(scales, B)
-            ctl = _controls(rows, seeds, durations, token_rate)
-            return self._stream(lambda cb: self._lib.vits_run_chunked_ctl(
-                self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(sid), C.byref(noise), C.byref(ctl),
-                int(chunk_frames), cb, None))
-        if scales.ndim == 1 and seeds is None:
-            return self._stream(lambda cb: self._lib.vits_run_chunked(
-                self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(scales), _ffi.ptr(sid), C.byref(noise),
-                int(chunk_frames), cb, None))
-        rows = _rows(scales, B)
-        return self._stream(lambda cb: self._lib.vits_run_chunked_rows(
-            self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(rows), _ffi.ptr(sid), C.byref(noise), _ffi.ptr(seeds),
-            int(chunk_frames), cb, None))
+            on_top = ("_glided", contour)
+        return ids, lens, scales, seeds, sid, noise, ctl, on_top, semitones, semitones_end
 
     @staticmethod
     def _encoded_items(dtype):
@@ -1521,67 +1514,33 @@ class MiSession:
         fit - as synthesize_batch (vitsmi.h, "fitted durations"): everything above then works on the fitted run - joined, the
         rows are what synthesize_delivered(fit=...) gives -, every chunk carries `skip` (zeros without onsets), and last_fit()
         answers from the first chunk on.  Not together with durations or token_semitones (ValueError)."""
-        ids = np.ascontiguousarray(ids, np.int64)
-        lens = np.ascontiguousarray(lens, np.int64)
+        ids, lens, _, _, sid, noise, ctl, on_top, semitones, semitones_end = self._stream_arguments(
+            "synthesize_stream_encoded", ids, lens, scales, sid, noise_dp, noise_z, seeds, durations, token_rate, token_semitones,
+            compensate, token_semitones_end, fit)
         B, T = ids.shape
-        semitones, semitones_end = _contour(token_semitones, token_semitones_end, lens, B, T)
-        cfit = _fit(fit, B, self.hparam("hop"), durations, semitones)
-        if semitones is not None:
-            self._pitch_admit("synthesize_stream_encoded", durations, compensate, semitones, semitones_end, lens)
         fmt, dtype = _stream_format(encoding, ref_peak, volume, B)
         shaping = self._stream_plan(shapes, token_gain_db, gain_ramp, limit, lens, B, T, semitones, semitones_end)
-        scales, seeds = _settings(np.ascontiguousarray(scales, np.float32), B, seeds)
-        durations, token_rate = _timing(durations, token_rate, lens, B, T)
-        sid = None if sid is None else np.ascontiguousarray(sid, np.int64)
-        noise = _ffi.VitsNoise()
-        noise.seed = self._seed
-        # (as synthesize_stream: every host array the C call reads on the worker thread belongs to the closure)
-        keep = noise._keep = []
-        if noise_dp is not None:
-            keep.append(np.ascontiguousarray(noise_dp, np.float32))
-            noise.noise_dp = keep[-1].ctypes.data
-        if noise_z is not None:
-            keep.append(np.ascontiguousarray(noise_z, np.float32))
-            noise.noise_z = keep[-1].ctypes.data
-            noise.noise_z_stride = keep[-1].shape[2]
-        ctl = _controls(_rows(scales, B), seeds, durations, token_rate)
-        trim = _stream_onsets(onsets, B)
-        if cfit is not None:
-            if shaping is not None:
-                self._shaping_check(shaping, fmt, B)
-            if trim is not None:
-                self._onsets_check(trim, fmt, B)
-            return self._stream(lambda cb: self._lib.vits_run_chunked_enc_fitted(
-                self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(sid), C.byref(noise), C.byref(ctl), C.byref(fmt),
-                None if shaping is None else C.byref(shaping), trim, C.byref(cfit), int(chunk_frames), cb, None),
-                self._trimmed_items(dtype))
-        if semitones is not None:
-            if shaping is not None:
-                self._shaping_check(shaping, fmt, B)
-            if trim is not None:
-                self._onsets_check(trim, fmt, B)
-            contour = _ffi.VitsContour(semitones.ctypes.data, None if semitones_end is None else semitones_end.ctypes.data,
-                                       1 if compensate else 0)
-            contour._keep = (semitones, semitones_end)
-            return self._stream(lambda cb: self._lib.vits_run_chunked_enc_glided(
-                self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(sid), C.byref(noise), C.byref(ctl), C.byref(fmt),
-                None if shaping is None else C.byref(shaping), trim, C.byref(contour), int(chunk_frames), cb, None),
-                self._trimmed_items(dtype))
-        if trim is not None:  # (passed down only when asked for)
-            if shaping is not None:
-                self._shaping_check(shaping, fmt, B)
+        suffix, rest, wrap = self._encoded_entry(fmt, dtype, shaping, _stream_onsets(onsets, B), B, on_top)
+        return self._stream(lambda cb: getattr(self._lib, "vits_run_chunked_enc" + suffix)(
+            self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(sid), C.byref(noise), C.byref(ctl), C.byref(fmt), *rest,
+            int(chunk_frames), cb, None), wrap)
+
+    def _encoded_entry(self, fmt, dtype, shaping, trim, B, on_top=None):
+        """Which encoded entry a stream reaches - whole path or vocoder -, after the pre-checks of what it passes down: (the
+        entry's suffix, its arguments between the format and chunk_frames, _stream's `wrap`).  on_top as _stream_arguments
+        makes it; those entries and the trimmed one hand out chunks with `skip`."""
+        if shaping is not None:
+            self._shaping_check(shaping, fmt, B)
+        if trim is not None:
             self._onsets_check(trim, fmt, B)
-            return self._stream(lambda cb: self._lib.vits_run_chunked_enc_trimmed(
-                self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(sid), C.byref(noise), C.byref(ctl), C.byref(fmt),
-                None if shaping is None else C.byref(shaping), trim, int(chunk_frames), cb, None), self._trimmed_items(dtype))
+        rest = (None if shaping is None else C.byref(shaping), trim)
+        if on_top is not None:
+            return on_top[0], rest + (C.byref(on_top[1]),), self._trimmed_items(dtype)
+        if trim is not None:  # (passed down only when asked for)
+            return "_trimmed", rest, self._trimmed_items(dtype)
         if shaping is None:  # (nothing asked for: the call made before there was any shaping)
-            return self._stream(lambda cb: self._lib.vits_run_chunked_enc(
-                self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(sid), C.byref(noise), C.byref(ctl), C.byref(fmt),
-                int(chunk_frames), cb, None), self._encoded_items(dtype))
-        self._shaping_check(shaping, fmt, B)
-        return self._stream(lambda cb: self._lib.vits_run_chunked_enc_shaped(
-            self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(sid), C.byref(noise), C.byref(ctl), C.byref(fmt),
-            C.byref(shaping), int(chunk_frames), cb, None), self._encoded_items(dtype))
+            return "", (), self._encoded_items(dtype)
+        return "_shaped", rest[:1], self._encoded_items(dtype)
 
     def _pitch_admit(self, name, durations, compensate, semitones, semitones_end, lens):
         """what the engine refuses of a stream with pitch, raised by the call itself: nothing was started (all zeros: the
@@ -1658,21 +1617,9 @@ class MiSession:
         if Cc != self.hparam("inter"):
             raise SessionError(f"z must have {self.hparam('inter')} channels")
         sid = None if sid is None else np.ascontiguousarray(sid, np.int64)
-        trim = _stream_onsets(onsets, B)
-        if trim is not None:
-            if shaping is not None:
-                self._shaping_check(shaping, fmt, B)
-            self._onsets_check(trim, fmt, B)
-            return self._stream(lambda cb: self._lib.vits_run_vocoder_chunked_enc_trimmed(
-                self._h, _ffi.ptr(z), B, F, _ffi.ptr(sid), C.byref(fmt), None if shaping is None else C.byref(shaping), trim,
-                int(chunk_frames), cb, None), self._trimmed_items(dtype))
-        if shaping is None:
-            return self._stream(lambda cb: self._lib.vits_run_vocoder_chunked_enc(
-                self._h, _ffi.ptr(z), B, F, _ffi.ptr(sid), C.byref(fmt), int(chunk_frames), cb, None), self._encoded_items(dtype))
-        self._shaping_check(shaping, fmt, B)
-        return self._stream(lambda cb: self._lib.vits_run_vocoder_chunked_enc_shaped(
-            self._h, _ffi.ptr(z), B, F, _ffi.ptr(sid), C.byref(fmt), C.byref(shaping), int(chunk_frames), cb, None),
-            self._encoded_items(dtype))
+        suffix, rest, wrap = self._encoded_entry(fmt, dtype, shaping, _stream_onsets(onsets, B), B)
+        return self._stream(lambda cb: getattr(self._lib, "vits_run_vocoder_chunked_enc" + suffix)(
+            self._h, _ffi.ptr(z), B, F, _ffi.ptr(sid), C.byref(fmt), *rest, int(chunk_frames), cb, None), wrap)
 
     def vocoder_stream(self, z, sid=None, chunk_frames: int = 64):
         """Vocoder only, chunked: yields (first_sample, float32 [B, n], total_samples)."""
@@ -1970,8 +1917,7 @@ class MiSession:
         B, T = ids.shape
         if sid is not None:
             sid = np.ascontiguousarray(sid, np.int64)
-        noise = _ffi.VitsNoise()
-        noise.seed = self._seed
+        noise = _noise(self._seed)
         with self._locked():
             rc = self._lib.vits_run(self._h, _ffi.ptr(ids), _ffi.ptr(lens), B, T, _ffi.ptr(scales), _ffi.ptr(sid),
                                     C.byref(noise), None)
@@ -2517,15 +2463,8 @@ class PipelinedSession:
             b0, b1 = bnd[i], bnd[i + 1]
             p = self.parts[i]
             try:
-                noise = _ffi.VitsNoise()
-                noise.seed = p._seed
                 # (this part's rows of the injected noise: contiguous slices, alive until _begin has copied them)
-                nd = None if noise_dp is None else noise_dp[b0:b1]
-                nz = None if noise_z is None else noise_z[b0:b1]
-                if nd is not None:
-                    noise.noise_dp = nd.ctypes.data
-                if nz is not None:
-                    noise.noise_z, noise.noise_z_stride = nz.ctypes.data, nz.shape[2]
+                noise = _noise(p._seed, None if noise_dp is None else noise_dp[b0:b1], None if noise_z is None else noise_z[b0:b1])
                 with p._mu:  # (a part may also be used on its own, e.g. bench.py's measure(): same per-session lock)
                     sc, sd = _part(scales, seeds, b0, b1)
                     p._begin(ids[b0:b1], lens[b0:b1], sc, None if sid is None else sid[b0:b1], noise, sd,
