@@ -1386,6 +1386,40 @@ int vits_bench_conv1d_sx(int device_id, int B, int Cin, int Cout, int T, int K, 
 int vits_test_conv_pair_sx(int device_id, const float *x, int B, int C, int T, const float *w1, const float *b1,
                            const float *w2, const float *b2, int K, int dil1, int dil2, int chain, float slope, float *out,
                            float *ms_out);
+/* conv_sx_pair_kernel with the whole argument set the generator's conv_sx_pair() gives it: one launch of the kernel's own
+ * launcher, its arguments filled by the function the generator fills them with.  Every pointer is a host pointer, tensors are
+ * dense [B][C][T]; convs, `chain` (0 / 1) and `slope` as vits_test_conv_pair_sx.  Utterance b's tensors end at end_b = lens[b]
+ * columns (T without lens): x and c1's result are zero at columns >= end_b, and those columns of out are not written.
+ *   value = (the step's result) [+ out_init (ACC)] [/ div (DIV; only with ACC)]
+ * out starts as out_init, else as zeros.  Refused with VITS_E_ARG, never launched: what sx_pair_supported() refuses, ACC
+ * without out_init, lens outside [0, T]; what launch_conv_sx_pair() itself refuses comes back as VITS_E_DEVICE. */
+enum { VITS_PAIR_EPI_ACC = 1, VITS_PAIR_EPI_DIV = 2 };
+typedef struct {
+    int B, C, T, K, dil1, dil2, chain;
+    int flags;               /* VITS_PAIR_EPI_* */
+    float slope, div;
+    const float *x;          /* [B][C][T] */
+    const float *w1, *b1, *w2, *b2;  /* w [C][C][K]; b [C] or NULL */
+    const int64_t *lens;     /* [B] in [0, T], or NULL: every utterance spans T */
+    const float *out_init;   /* [B][C][T] previous contents of the raw tensor (the ACC operand), or NULL */
+    float *out;              /* [B][C][T] the raw tensor as the launch left it */
+    char kernel[128];        /* out: the instantiation launched (as in vits_launch_record) */
+    int BNo;                 /* out: kept columns per tile */
+} vits_test_conv_pair_sx_epi_args;
+int vits_test_conv_pair_sx_epi(int device_id, vits_test_conv_pair_sx_epi_args *a);
+/* The identity the fused low-plane form rests on, evaluated on the host (_Float16 / fmaf; no device): with v = x clamped to
+ * +-65504 and h0 = f16(v), old = f16((v - h0) * 2048) and fused = f16(fmaf(h0, -2048, v * 2048)) as fp16 bits.
+ * _sweep: the same over the fp32 bit patterns first, first + 1, .. (count of them; wraps at 2^32): returns the number that
+ * differ (NaN against NaN counts as equal), the first one in *first_bad (nullable). */
+int vits_test_split_identity(const float *x, int64_t n, uint16_t *h1_old, uint16_t *h1_fused);
+int64_t vits_test_split_identity_sweep(uint32_t first, uint64_t count, uint32_t *first_bad);
+/* The activation -> operand-plane helpers of csrc/sx_split.hip.hpp on n host values (n even; pair i = values 2 i, 2 i + 1):
+ * a = leaky_relu(x, slope) as the fused ResBlock-step kernel computes it, clamped to +-65504, split into h0 = f16(a) and
+ * h1 = f16((a - h0) * 2048).  form 0: the engine-wide split; form 1: the one conv_sx_pair_kernel uses.  h0, h1 [n]: the planes'
+ * fp16 bits; pk [n / 2]: the range guard's magnitude of each pair, max(|a|, |b|) before the clamp; rec [n]: h0 with the
+ * leaky-ReLU undone (v < 0 ? v * (1 / slope) : v). */
+int vits_test_split_forms(int device_id, const float *x, int n, float slope, int form, uint16_t *h0, uint16_t *h1, float *pk,
+                          float *rec);
 /* The fused ResBlock step (csrc/conv_sx_pair16.hip.hpp, conv_sx_pair16_kernel) with the whole argument set the generator's
  * conv_sx_pair16() gives it: one launch of the kernel's own launcher, its arguments filled by the function the generator
  * fills them with.  Every pointer is a host pointer, tensors are dense [B][C][T]; c1 = Conv1d(C, C, K, dilation dil1),

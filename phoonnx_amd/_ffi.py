@@ -70,6 +70,14 @@ class VitsTestConvPair16EpiArgs(C.Structure):
                [(n, C.c_int) for n in ("BN", "BNo", "ovl")] + [("peak", C.c_float), ("guard_ok", C.c_int)]
 
 
+class VitsTestConvPairSxEpiArgs(C.Structure):
+    """vits_test_conv_pair_sx_epi_args of include/vitsmi.h"""
+    _fields_ = [(n, C.c_int) for n in ("B", "C", "T", "K", "dil1", "dil2", "chain", "flags")] + \
+               [(n, C.c_float) for n in ("slope", "div")] + \
+               [(n, C.c_void_p) for n in ("x", "w1", "b1", "w2", "b2", "lens", "out_init", "out")] + \
+               [("kernel", C.c_char * 128), ("BNo", C.c_int)]
+
+
 class VitsTestAttentionFormArgs(C.Structure):
     """vits_test_attention_form_args of include/vitsmi.h"""
     _fields_ = [("kernel", C.c_int), ("qkv", C.c_void_p), ("qkv_planes", C.c_void_p)] + \
@@ -220,7 +228,7 @@ EXPORTS = [
     "vits_test_stream_pack_trimmed",
     "vits_test_layernorm", "vits_test_dds", "vits_test_cf_pre", "vits_test_rqs_inverse", "vits_test_ea_logw",
     "vits_test_conv1d_epi", "vits_test_wn_gate", "vits_test_cond_matvec", "vits_test_conv1d_sx_epi",
-    "vits_test_conv_pair16_epi", "vits_test_attention_form",
+    "vits_test_conv_pair16_epi", "vits_test_attention_form", "vits_test_conv_pair_sx_epi", "vits_test_split_forms", "vits_test_split_identity", "vits_test_split_identity_sweep",
 ]
 
 
@@ -431,6 +439,11 @@ def load():
     lib.vits_test_conv1d_epi.argtypes = [C.c_int, C.POINTER(VitsTestConvEpiArgs)]
     lib.vits_test_conv1d_sx_epi.argtypes = [C.c_int, C.POINTER(VitsTestConvSxEpiArgs)]
     lib.vits_test_conv_pair16_epi.argtypes = [C.c_int, C.POINTER(VitsTestConvPair16EpiArgs)]
+    lib.vits_test_conv_pair_sx_epi.argtypes = [C.c_int, C.POINTER(VitsTestConvPairSxEpiArgs)]
+    lib.vits_test_split_identity.argtypes = [vp, C.c_int64, vp, vp]
+    lib.vits_test_split_identity_sweep.argtypes = [C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32)]
+    lib.vits_test_split_identity_sweep.restype = C.c_int64
+    lib.vits_test_split_forms.argtypes = [C.c_int, vp, C.c_int, C.c_float, C.c_int, vp, vp, vp, vp]
     lib.vits_test_attention_form.argtypes = [C.c_int, C.POINTER(VitsTestAttentionFormArgs)]
     lib.vits_test_wn_gate.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     lib.vits_test_cond_matvec.argtypes = [C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp]

@@ -105,6 +105,9 @@ struct SxPairArgs {
 #ifndef SX_PAIR_ST_SC1
 #define SX_PAIR_ST_SC1 0
 #endif
+#ifndef SX_PAIR_INTERIOR
+#define SX_PAIR_INTERIOR 1  // interior tiles run the body without per-column predicates (conv_sx_pair_body, INTR); 0 = every tile the edge body
+#endif
 // Prologue in the accumulator layout (default, both variants): every thread loads the 16-byte half cells of x it will add as
 // the residual (the 256 columns the waves produce) straight into `pre`, converts THOSE registers into the LDS operand planes,
 // and keeps them; only the halo columns left and right of the 256 go through transient whole-cell registers.  x crosses the
@@ -128,8 +131,14 @@ struct SxPairArgs {
 // cells further right - and their results meet in registers, in the order the separate launches added them (bit-identical).
 // As three launches the stage's tensor is read 3 + 2 times (x three times, the running sum twice) and written three
 // times; here once each.
-template <int MW, int NW, int WM, int WN, int EPI, bool CHAIN, int NCH = 1>
-__global__ __launch_bounds__(256, (NW == 2 && !SX_PAIR_EARLY_ACC && NCH == 1) ? SX_PAIR_WGS32 : 2) void conv_sx_pair_kernel(SxPairArgs a) {
+//
+// INTR (interior tile): every column the tile reads or writes - the kept columns and pad1 + pad2 more on each side - lies
+// inside [0, TV), this utterance's tensor.  Decided once per workgroup from scalars (conv_sx_pair_kernel); such a tile needs
+// no clamped load column, no zero fill, no `live ? v : 0` at the hand-over and no tensor-end store predicate, and the body
+// is compiled without them.  Every other tile (the first and last of an utterance, short tensors) runs INTR = false: the
+// code as it was.  Same loads, same arithmetic, same stores - on an interior tile every dropped predicate is true.
+template <int MW, int NW, int WM, int WN, int EPI, bool CHAIN, int NCH, bool INTR>
+__device__ __forceinline__ void conv_sx_pair_body(const SxPairArgs &a, const int b, const int t0, const int TV, float &pk) {
     constexpr int BN = NW * WN * 32, NH = NW / 2;
     static_assert(NCH == 1 || (CHAIN && NW == 2 && (EPI & EPI_ACC) == 0), "fused chains: 32 channels, no external running sum");
     // The residual is in registers from the prologue on: loaded there as the x tile itself (ONE_READ), or (the earlier form
@@ -151,20 +160,13 @@ __global__ __launch_bounds__(256, (NW == 2 && !SX_PAIR_EARLY_ACC && NCH == 1) ? 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
     const int l31 = lane & 31, hi = lane >> 5;
-    const int wg_xcd = blockIdx.x & 7, wg_seq = blockIdx.x >> 3;
-    const int tile_nb = __builtin_amdgcn_readfirstlane(sx_xcd_tile(wg_seq, wg_xcd, a.xgs));
-    if (tile_nb >= a.NT * a.B) return;
-    const int b = tile_nb / a.NT, t0 = (tile_nb - b * a.NT) * a.BNo;  // first kept output column
-    const int t1 = t0 - a.pad2;                                        // first column phase 1 computes
+    const int t1 = t0 - a.pad2;  // first column phase 1 computes (t0: first kept output column)
     const int T = a.T, LW = a.LW1;
-    const int TV = __builtin_amdgcn_readfirstlane(sx_valid_cols(a.rag, b, T));  // this utterance's tensor end (SxRagged); T = row pitch
-    if (t0 >= TV) return;                                                        // (uniform exit) no kept column lies inside it
     const uint32_t lds0 = (uint32_t)(uintptr_t)lds_sx;
     const uint32_t XB = a.x_bytes;
     const char *wbase1 = reinterpret_cast<const char *>(a.wp1) + wm * (MW * NPW * 1024);
     const char *wbase2 = reinterpret_cast<const char *>(a.wp2) + wm * (MW * NPW * 1024);
     const float *xrb = a.xr + (int64_t)b * a.C * T;
-    float pk = 0.f;
 
     struct ASet {
         u32x4 fa[2];
@@ -189,6 +191,13 @@ __global__ __launch_bounds__(256, (NW == 2 && !SX_PAIR_EARLY_ACC && NCH == 1) ? 
                 const int tl = t < 0 ? 0 : (t < T ? t : T - 1);  // (clamped columns are never kept)
 #pragma unroll
                 for (int q = 0; q < 4; q++) {
+                    if constexpr (INTR && EARLY) {
+                        // (interior: 0 <= t < T, and T * 64 + 64 < 2^32 by the launcher) the row's scalar base + one 32-bit lane
+                        // offset per block column, instead of a 64-bit address per load
+                        const char *rowb = reinterpret_cast<const char *>(base + (int64_t)((row0 >> 3) + q) * T * 8);
+                        dst[rr][j][q] = __builtin_bit_cast(f32x4, global_read128<0>(((uint32_t)t * 8u + 4u * (uint32_t)hi) * 4u, rowb));
+                        continue;
+                    }
                     const float *p = base + ((int64_t)((row0 >> 3) + q) * T + tl) * 8 + 4 * hi;
                     if constexpr (EARLY) dst[rr][j][q] = __builtin_bit_cast(f32x4, global_read128_v<0>(p));
                     else dst[rr][j][q] = *reinterpret_cast<const f32x4 *>(p);
@@ -267,7 +276,7 @@ __global__ __launch_bounds__(256, (NW == 2 && !SX_PAIR_EARLY_ACC && NCH == 1) ? 
             const int c = hin[it] ? h - g * HW : 0;
             const int col = c < pad1 ? c : c + 256;
             const int t = t1 - pad1 + col;
-            hok[it] = hin[it] && t >= 0 && t < TV;
+            hok[it] = hin[it] && (INTR || (t >= 0 && t < TV));
             hp[it] = xrb + (hok[it] ? ((int64_t)g * T + t) * 8 : (int64_t)0);
             hlds[it] = lds0 + (uint32_t)(g >> 1) * XB + (uint32_t)((g & 1) * LW + col) * 16u;
         }
@@ -294,12 +303,12 @@ __global__ __launch_bounds__(256, (NW == 2 && !SX_PAIR_EARLY_ACC && NCH == 1) ? 
                         float v[8];
 #pragma unroll
                         for (int e = 0; e < 8; e++) {
-                            const float x = hok[it] ? __uint_as_float(hst[it][e >> 2][e & 3]) : 0.f;
-                            v[e] = fmaxf(x, x * isl);
+                            const float x = (INTR || hok[it]) ? __uint_as_float(hst[it][e >> 2][e & 3]) : 0.f;  // (INTR: hin[it] holds here)
+                            v[e] = lrelu_max(x, isl);
                         }
                         unsigned p0[4], p1[4];
 #pragma unroll
-                        for (int e = 0; e < 4; e++) split2h_pair_pk(v[2 * e], v[2 * e + 1], p0[e], p1[e], pk);
+                        for (int e = 0; e < 4; e++) sx_pair_split(v[2 * e], v[2 * e + 1], p0[e], p1[e], pk);
                         ds_write128(hlds[it], u32x4{p0[0], p0[1], p0[2], p0[3]});
                         ds_write128(hlds[it] + (uint32_t)(2 * LW) * 16u, u32x4{p1[0], p1[1], p1[2], p1[3]});
                     }
@@ -307,18 +316,18 @@ __global__ __launch_bounds__(256, (NW == 2 && !SX_PAIR_EARLY_ACC && NCH == 1) ? 
             }
             const int col = (wn * NW + n) * 32 + l31;
             const int t = t1 + col;
-            const bool ok = t >= 0 && t < TV;  // outside the tensor: zeros in LDS; `pre` keeps what the clamped load returned
+            const bool ok = INTR || (t >= 0 && t < TV);  // outside the tensor: zeros in LDS; `pre` keeps what the clamped load returned
 #pragma unroll
             for (int q = 0; q < 4; q++) {
                 float v[4];
 #pragma unroll
                 for (int e = 0; e < 4; e++) {
                     const float x = ok ? pre[n / 2][n % 2][q][e] : 0.f;
-                    v[e] = fmaxf(x, x * isl);
+                    v[e] = lrelu_max(x, isl);
                 }
                 unsigned wa[2], wb[2];
-                split2h_pair_pk(v[0], v[1], wa[0], wa[1], pk);
-                split2h_pair_pk(v[2], v[3], wb[0], wb[1], pk);
+                sx_pair_split(v[0], v[1], wa[0], wa[1], pk);
+                sx_pair_split(v[2], v[3], wb[0], wb[1], pk);
                 // channel group g = 4 * wm + q -> chunk g / 2, half g % 2; 4 channels = 8 bytes of the 16-byte cell
                 const int g = 4 * wm + q;
                 const uint32_t cell = lds0 + (uint32_t)(g >> 1) * XB + (uint32_t)((g & 1) * LW + pad1 + col) * 16u + 8u * hi;
@@ -343,7 +352,7 @@ __global__ __launch_bounds__(256, (NW == 2 && !SX_PAIR_EARLY_ACC && NCH == 1) ? 
             const int t = t1 - a.pad1 + col;
             xkh[it] = kh;
             xcol[it] = col;
-            xrok[it] = it < nxc && kh < 2 && t >= 0 && t < TV;
+            xrok[it] = it < nxc && kh < 2 && (INTR || (t >= 0 && t < TV));
             xroff[it] = xrok[it] ? (uint32_t)(((int64_t)kh * T + t) * 32) : 0u;
         }
         static_for<MAXCH>([&](auto CH) {
@@ -379,11 +388,11 @@ __global__ __launch_bounds__(256, (NW == 2 && !SX_PAIR_EARLY_ACC && NCH == 1) ? 
 #pragma unroll
                     for (int e = 0; e < 8; e++) {
                         const float x = xrok[it] ? __uint_as_float(xst[ch][it][e >> 2][e & 3]) : 0.f;
-                        v[e] = fmaxf(x, x * isl);
+                        v[e] = lrelu_max(x, isl);
                     }
                     unsigned p0[4], p1[4];
 #pragma unroll
-                    for (int e = 0; e < 4; e++) split2h_pair_pk(v[2 * e], v[2 * e + 1], p0[e], p1[e], pk);
+                    for (int e = 0; e < 4; e++) sx_pair_split(v[2 * e], v[2 * e + 1], p0[e], p1[e], pk);
                     const uint32_t ad = lds0 + (uint32_t)ch * XB + (uint32_t)(xkh[it] * LW + xcol[it]) * 16u;
                     ds_write128(ad, u32x4{p0[0], p0[1], p0[2], p0[3]});
                     ds_write128(ad + (uint32_t)(2 * LW) * 16u, u32x4{p1[0], p1[1], p1[2], p1[3]});
@@ -694,7 +703,7 @@ __global__ __launch_bounds__(256, (NW == 2 && !SX_PAIR_EARLY_ACC && NCH == 1) ? 
         for (int n = 0; n < NW; n++) {
             const int col = (wn * NW + n) * 32 + l31;
             const int t = t1 + col;
-            const bool live = t >= 0 && t < TV;  // outside the tensor c2 sees zero padding, not c1 evaluated there
+            const bool live = INTR || (t >= 0 && t < TV);  // outside the tensor c2 sees zero padding, not c1 evaluated there
 #pragma unroll
             for (int q = 0; q < 4; q++) {
                 float o[4];
@@ -711,8 +720,8 @@ __global__ __launch_bounds__(256, (NW == 2 && !SX_PAIR_EARLY_ACC && NCH == 1) ? 
                     o[e] = live ? fmaxf(v, v * msl) : 0.f;
                 }
                 unsigned wa[2], wb[2];
-                split2h_pair_pk(o[0], o[1], wa[0], wa[1], pk);
-                split2h_pair_pk(o[2], o[3], wb[0], wb[1], pk);
+                sx_pair_split(o[0], o[1], wa[0], wa[1], pk);
+                sx_pair_split(o[2], o[3], wb[0], wb[1], pk);
                 // channel group g = 4 * wm + q -> chunk g / 2, half g % 2; 4 channels = 8 bytes of the 16-byte cell
                 const int g = 4 * wm + q;
                 const uint32_t cell = ylds + (uint32_t)(g >> 1) * YC + ((uint32_t)(g & 1) * LW2 + (uint32_t)(col + a.pad2)) * 16u + 8u * hi;
@@ -765,10 +774,14 @@ __global__ __launch_bounds__(256, (NW == 2 && !SX_PAIR_EARLY_ACC && NCH == 1) ? 
 #pragma unroll
                 for (int j = 0; j < 2; j++) {
                     const int t = t1 + (wn * NW + rr * 2 + j) * 32 + l31;
-                    const int tl = t < 0 ? 0 : (t < T ? t : T - 1);
+                    const int tl = INTR ? t : (t < 0 ? 0 : (t < T ? t : T - 1));
 #pragma unroll
-                    for (int q = 0; q < 4; q++)
-                        adl[j][q] = *reinterpret_cast<const f32x4 *>(rawb + ((int64_t)((row0 >> 3) + q) * T + tl) * 8 + 4 * hi);
+                    for (int q = 0; q < 4; q++) {
+                        if constexpr (INTR)  // (as load_res: scalar row base + 32-bit lane offset)
+                            adl[j][q] = *reinterpret_cast<const f32x4 *>(reinterpret_cast<const char *>(rawb + (int64_t)((row0 >> 3) + q) * T * 8) +
+                                                                         ((uint32_t)t * 8u + 4u * (uint32_t)hi) * 4u);
+                        else adl[j][q] = *reinterpret_cast<const f32x4 *>(rawb + ((int64_t)((row0 >> 3) + q) * T + tl) * 8 + 4 * hi);
+                    }
                 }
             }
 #pragma unroll
@@ -776,7 +789,7 @@ __global__ __launch_bounds__(256, (NW == 2 && !SX_PAIR_EARLY_ACC && NCH == 1) ? 
                 const int n = rr * 2 + j;
                 const int col = (wn * NW + n) * 32 + l31;
                 const int t = t1 + col;
-                const bool kept = !(col < a.pad2 || col >= a.pad2 + a.BNo || t >= TV);  // overlap columns belong to the neighbours
+                const bool kept = !(col < a.pad2 || col >= a.pad2 + a.BNo || (!INTR && t >= TV));  // overlap columns belong to the neighbours
                 if constexpr (NCH == 1) {
                     if (!kept) continue;
                 }
@@ -807,7 +820,10 @@ __global__ __launch_bounds__(256, (NW == 2 && !SX_PAIR_EARLY_ACC && NCH == 1) ? 
                         asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(sp), "v"(sv) : "memory");
                     }
 #else
-                    *reinterpret_cast<f32x4 *>(rawb + ((int64_t)((row0 >> 3) + q) * T + t) * 8 + 4 * hi) = v;
+                    if constexpr (INTR)
+                        *reinterpret_cast<f32x4 *>(reinterpret_cast<char *>(rawb + (int64_t)((row0 >> 3) + q) * T * 8) +
+                                                   ((uint32_t)t * 8u + 4u * (uint32_t)hi) * 4u) = v;
+                    else *reinterpret_cast<f32x4 *>(rawb + ((int64_t)((row0 >> 3) + q) * T + t) * 8 + 4 * hi) = v;
 #endif
                 }
             }
@@ -822,6 +838,22 @@ __global__ __launch_bounds__(256, (NW == 2 && !SX_PAIR_EARLY_ACC && NCH == 1) ? 
         atomicAdd(a.prof + 7, 1ull);
     }
 #endif
+}
+
+template <int MW, int NW, int WM, int WN, int EPI, bool CHAIN, int NCH = 1>
+__global__ __launch_bounds__(256, (NW == 2 && !SX_PAIR_EARLY_ACC && NCH == 1) ? SX_PAIR_WGS32 : 2) void conv_sx_pair_kernel(SxPairArgs a) {
+    const int wg_xcd = blockIdx.x & 7, wg_seq = blockIdx.x >> 3;
+    const int tile_nb = __builtin_amdgcn_readfirstlane(sx_xcd_tile(wg_seq, wg_xcd, a.xgs));
+    if (tile_nb >= a.NT * a.B) return;
+    const int b = tile_nb / a.NT, t0 = (tile_nb - b * a.NT) * a.BNo;  // first kept output column
+    const int TV = __builtin_amdgcn_readfirstlane(sx_valid_cols(a.rag, b, a.T));  // this utterance's tensor end (SxRagged); T = row pitch
+    if (t0 >= TV) return;                                                          // (uniform exit) no kept column lies inside it
+    // the x tile is columns [t0 - pad2 - pad1, .. + LW1); everything else the tile touches lies inside it
+    const int xl = t0 - a.pad2 - a.pad1;
+    const bool interior = SX_PAIR_INTERIOR != 0 && xl >= 0 && xl + a.LW1 <= TV;  // (scalar: one branch per workgroup)
+    float pk = 0.f;
+    if (interior) conv_sx_pair_body<MW, NW, WM, WN, EPI, CHAIN, NCH, true>(a, b, t0, TV, pk);
+    else conv_sx_pair_body<MW, NW, WM, WN, EPI, CHAIN, NCH, false>(a, b, t0, TV, pk);
     if (a.peak) sx_publish_peak(a.peak, (int)blockIdx.x, pk);  // (uniform branch; every thread arrives)
 }
 

@@ -51,6 +51,48 @@ __device__ __forceinline__ void split2h_pair_pk(float x, float y, unsigned &w0, 
     pk = __builtin_fmaxf(pk, __builtin_fmaxf(__builtin_fabsf(x), __builtin_fabsf(y)));
     split2h_pair(x, y, w0, w1);
 }
+// split2h_pair_pk in fewer instructions (the fused ResBlock-step kernel's prologue and hand-over).  The low plane
+// h1' = f16((x - h0) * 2048) as t = x * 2048 (one packed multiply per pair), h1' = f16(fma(h0, -2048, t)) with the fp16 -> fp32
+// conversion of h0, the fma and the rounding to fp16 in ONE v_fma_mixlo_f16 / v_fma_mixhi_f16 per value: 3 instructions per
+// pair instead of 5.  Equal by construction: x - h0 and the scalings by 2048 are exact in fp32 (h0 is x rounded to 11 bits,
+// |x| <= 65504), so fma(h0, -2048, t) IS (x - h0) * 2048, and both forms round that one real number once to fp16.
+// The guard's magnitude as one v_max3_f32 with |.| operand modifiers (x, y come out of a v_max / v_fma here, never NaN-
+// signalling: the nested fmaxf form costs two instructions per pair).
+__device__ __forceinline__ void split2h_pair_pk_mix(float x, float y, unsigned &w0, unsigned &w1, float &pk) {
+    asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(pk) : "v"(x), "v"(y));
+    x = __builtin_amdgcn_fmed3f(x, -65504.f, 65504.f);
+    y = __builtin_amdgcn_fmed3f(y, -65504.f, 65504.f);
+    w0 = cvt_pk_f16(x, y);
+    const sxf32x2 t = sxf32x2{x, y} * 2048.f;
+    const float c = -2048.f;
+    unsigned r;
+    asm("v_fma_mixlo_f16 %0, %1, %2, %3 op_sel_hi:[1,0,0]" : "=v"(r) : "v"(w0), "v"(c), "v"(t.x));
+    asm("v_fma_mixhi_f16 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(r) : "v"(w0), "v"(c), "v"(t.y));
+    w1 = r;
+}
+// what conv_sx_pair_kernel splits with (and the split-forms test kernel pins, test_dev.hip.hpp)
+#ifndef SX_PAIR_MIX
+#define SX_PAIR_MIX 1  // the fp16 split with the low plane by v_fma_mix and the guard's magnitude by one v_max3 (sx_split.hip.hpp); 0 = split2h_pair_pk
+#endif
+__device__ __forceinline__ void sx_pair_split(float x, float y, unsigned &w0, unsigned &w1, float &pk) {
+#if SX_PAIR_MIX
+    split2h_pair_pk_mix(x, y, w0, w1, pk);
+#else
+    split2h_pair_pk(x, y, w0, w1, pk);
+#endif
+}
+
+// leaky-ReLU of a value that comes straight from memory, 0 < slope <= 1: max(x, x * slope) as ONE v_max_f32.  Written as
+// fmaxf() hipcc puts a second v_max_f32 x, x, x in front (it quiets a signalling NaN, which C's fmax would otherwise have to
+// treat as missing).  The kernels run in IEEE mode, where v_max_f32 quiets a signalling operand itself; and x * slope is a
+// NaN whenever x is one, so no operand is ever "missing": x finite or infinite -> the same maximum; x a quiet NaN -> the same
+// instruction on the same operands; x a signalling NaN -> its quieted self either way.  Bit-identical for every input.
+__device__ __forceinline__ float lrelu_max(float x, float slope) {
+    const float m = x * slope;
+    float r;
+    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(m));
+    return r;
+}
 // ---- f16 single-plane storage (NP = 1, the reduced-precision vocoder of BASELINE config 4): an activation IS its fp16
 // rounding (clamped to +-65504, range-tracked like the two-plane split); one MFMA product per fp32 product.
 __device__ __forceinline__ unsigned cvt1h_pair_pk(float x, float y, float &pk) {

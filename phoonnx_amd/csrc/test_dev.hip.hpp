@@ -1,12 +1,38 @@
 // test_dev.hip.hpp — what the kernel-level test hooks (vitsmi.hip, g2p.hip) share on the host side: an owner of their
-// device buffers and one event timer.  Nothing here runs on the device.
+// device buffers and one event timer - and one kernel, which applies the device helpers of sx_split.hip.hpp to an array.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 #include <vector>
 
+#include "sx_split.hip.hpp"
+
 namespace vitsmi {
+
+// The activation -> operand-plane path of the fused ResBlock-step kernel on an array, helper by helper as that kernel calls them:
+// a = lrelu_max(x, slope), then FORM 0: split2h_pair_pk (the engine-wide form), FORM 1: sx_pair_split (conv_sx_pair_kernel's).
+// Pair i = elements 2 i, 2 i + 1 (n even).  Out: the two planes' fp16 bits per element, the guard magnitude per pair, and the
+// reconstruction of the high plane (unact4h with unslope: what a consumer of activated planes recovers), per element.
+template <int FORM>
+__global__ void split_forms_kernel(const float *x, int n, float slope, float unslope, uint16_t *h0, uint16_t *h1, float *pk_out, float *rec) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (2 * i + 1 >= n) return;
+    const float a = lrelu_max(x[2 * i], slope), b = lrelu_max(x[2 * i + 1], slope);
+    unsigned w0, w1;
+    float pk = 0.f;
+    if constexpr (FORM == 0) split2h_pair_pk(a, b, w0, w1, pk);
+    else sx_pair_split(a, b, w0, w1, pk);
+    h0[2 * i] = (uint16_t)(w0 & 0xffffu);
+    h0[2 * i + 1] = (uint16_t)(w0 >> 16);
+    h1[2 * i] = (uint16_t)(w1 & 0xffffu);
+    h1[2 * i + 1] = (uint16_t)(w1 >> 16);
+    pk_out[i] = pk;
+    float o[4];
+    unact4h(u32x2{w0, w0}, unslope, o);
+    rec[2 * i] = o[0];
+    rec[2 * i + 1] = o[1];
+}
 
 // Owner of a hook's device buffers: whatever it handed out is freed when it goes out of scope, whichever way the hook
 // returns.  The first failure stays in `err`; every call after it does nothing and returns nullptr, so a hook asks for all

@@ -831,21 +831,25 @@ bool sx_pair_ok(const vits_handle *h, const ConvDesc &c1, const ConvDesc &c2) {
            sx_pair_supported(c1.Cin, c1.cfg, c1.K, c1.dil, c2.K, c2.dil);
 }
 
-void conv_sx_pair(Ctx &c, const ConvDesc &c1, const ConvDesc &c2, const float *x, int T, float *out, int flags, float div,
-                  float slope, bool chain = false) {
+// What a call site decides of a fused launch - the generator below and the kernel-level test hook (vits_test_conv_pair_sx_epi)
+// fill SxPairArgs here and nowhere else; the tile geometry is launch_conv_sx_pair()'s.  A: the arena the convs were packed into,
+// zeros: >= 1 KiB of zeros.
+static SxPairArgs sx_pair_args(const ConvDesc &c1, const ConvDesc &c2, const float *A, const float *zeros, const float *x, int T, float *out,
+                               int flags, float div, float slope, SxRagged rag, unsigned *peak) {
     SxPairArgs a{};
+    const auto P = [A](int64_t off) { return off >= 0 ? A + off : nullptr; };
     a.xr = x;
     a.islope = slope;
     a.mslope = slope;
     a.T = T;
-    a.wp1 = reinterpret_cast<const u32x4 *>(c.P(c1.w_off));
-    a.wp2 = reinterpret_cast<const u32x4 *>(c.P(c2.w_off));
-    a.bias1 = c.P(c1.b_off);
-    a.bias2 = c.P(c2.b_off);
+    a.wp1 = reinterpret_cast<const u32x4 *>(P(c1.w_off));
+    a.wp2 = reinterpret_cast<const u32x4 *>(P(c2.w_off));
+    a.bias1 = P(c1.b_off);
+    a.bias2 = P(c2.b_off);
     a.wscale1 = c1.wscale;
     a.wscale2 = c2.wscale;
     a.out_raw = out;
-    a.zeros = c.P(c.m.zeros_off);
+    a.zeros = zeros;
     a.C = c1.Cin;
     a.K1 = c1.K;
     a.dil1 = c1.dil;
@@ -855,9 +859,15 @@ void conv_sx_pair(Ctx &c, const ConvDesc &c1, const ConvDesc &c2, const float *x
     a.pad2 = c2.padL;
     a.flags = flags & (EPI_ACC | EPI_DIV);
     a.div = div;
+    a.rag = rag;
+    a.peak = peak;
+    return a;
+}
+
+void conv_sx_pair(Ctx &c, const ConvDesc &c1, const ConvDesc &c2, const float *x, int T, float *out, int flags, float div,
+                  float slope, bool chain = false) {
     vits_handle *h = c.h;
-    a.rag = c.rag_at(T);
-    a.peak = range_slots(h, true);
+    SxPairArgs a = sx_pair_args(c1, c2, c.A, c.P(c.m.zeros_off), x, T, out, flags, div, slope, c.rag_at(T), range_slots(h, true));
 #if SX_PAIR_PROF
     {
         // diagnostic build: one row of 8 counters per pair launch of a run, printed by the next launch_table / bench run
@@ -5211,6 +5221,118 @@ int vits_test_conv_pair_sx(int device_id, const float *x, int B, int C, int T, c
     TCHECK(hipGetLastError());
     TCHECK(hipDeviceSynchronize());
     TCHECK(download(out, dout, n));
+    return VITS_OK;
+}
+
+// conv_sx_pair_kernel with the argument set the generator's conv_sx_pair() gives it (include/vitsmi.h): SxPairArgs from
+// sx_pair_args(), the generator's own filler, one launch_conv_sx_pair().  The raw output tensor starts as out_init (the ACC
+// operand), else as zeros; what the launch does not write reads back unchanged.
+int vits_test_conv_pair_sx_epi(int device_id, vits_test_conv_pair_sx_epi_args *p) {
+    if (int rc = test_dev(device_id)) return rc;
+    if (!p) return fail(nullptr, VITS_E_ARG, "no arguments");
+    const auto bad = [](const char *why) { return fail(nullptr, VITS_E_ARG, "pair epilogue hook: %s", why); };
+    const int B = p->B, C = p->C, T = p->T, K = p->K;
+    if (B < 1 || C < 1 || T < 1 || K < 1 || p->dil1 < 1 || p->dil2 < 1 || !p->x || !p->w1 || !p->w2 || !p->out) return bad("bad shape or missing tensor");
+    if (p->flags & ~(VITS_PAIR_EPI_ACC | VITS_PAIR_EPI_DIV)) return bad("unknown flag");
+    if ((p->flags & VITS_PAIR_EPI_ACC) && !p->out_init) return bad("acc without out_init (the accumulate operand is the raw tensor's previous contents)");
+    if (p->lens)
+        for (int b = 0; b < B; b++)
+            if (p->lens[b] < 0 || p->lens[b] > T) return bad("lens outside [0, T]");
+    ConvDesc d1, d2;
+    std::vector<float> arena;
+    const TestPack o = sx_test_pack(SxPack::F16X2);
+    std::string e = pack_test_conv(p->w1, p->b1, C, C, K, p->dil1, p->dil1 * (K - 1) / 2, 3, &d1, &arena, o);
+    if (e.empty()) e = pack_test_conv(p->w2, p->b2, C, C, K, p->dil2, p->dil2 * (K - 1) / 2, 3, &d2, &arena, o);
+    if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
+    if (!d1.rawin || !d2.rawin || d1.cfg != d2.cfg || !sx_pair_supported(C, d1.cfg, d1.K, d1.dil, d2.K, d2.dil))
+        return fail(nullptr, VITS_E_ARG, "this conv pair cannot run fused (C %d, kernel %d, dilations %d, %d)", C, K, p->dil1, p->dil2);
+    const size_t n = (size_t)B * C * T;
+    std::vector<int> l32(B);
+    for (int b = 0; b < B; b++) l32[b] = p->lens ? (int)p->lens[b] : T;
+    DevBufs D;
+    float *dA = D.up(arena.data(), arena.size());
+    float *dx = D.up(p->x, n, 16);
+    float *dxr = D.alloc<float>(n, 16);
+    float *dimg = p->out_init ? D.up(p->out_init, n, 16) : D.fill<float>(n, 0, 16);
+    float *draw = D.alloc<float>(n, 16);
+    float *dout = D.alloc<float>(n, 16);
+    int *dlen = p->lens ? D.up(l32.data(), (size_t)B) : nullptr;
+    TCHECK(D.err);
+    const dim3 grid((T + 255) / 256, C / 8, B);
+    sx_block_kernel<<<grid, 256>>>(dx, (int64_t)C * T, T, nullptr, dxr, C, T);
+    sx_block_kernel<<<grid, 256>>>(dimg, (int64_t)C * T, T, nullptr, draw, C, T);
+    TCHECK(hipGetLastError());
+    const int kflags = ((p->flags & VITS_PAIR_EPI_ACC) ? EPI_ACC : 0) | ((p->flags & VITS_PAIR_EPI_DIV) ? EPI_DIV : 0);
+    const SxRagged rag = dlen ? SxRagged{dlen, 0, 1} : SxRagged{nullptr, 0, 0};  // (utterance b's tensors end at lens[b] columns)
+    const SxPairArgs a = sx_pair_args(d1, d2, dA, dA, dxr, T, draw, kflags, p->div == 0.f ? 1.f : p->div, p->slope, rag, nullptr);  // (pack_test_* reserve a zero page at offset 0)
+    const bool name_was_on = g_launch_name_on;
+    g_launch_name_on = true;
+    g_launch_name[0] = 0;
+    const hipError_t le = launch_conv_sx_pair(a, d1.cfg, B, nullptr, p->chain != 0);
+    g_launch_name_on = name_was_on;
+    if (le != hipSuccess) return fail(nullptr, VITS_E_DEVICE, "pair epilogue hook: launch_conv_sx_pair: %s", hipGetErrorString(le));
+    TCHECK(hipDeviceSynchronize());
+    std::snprintf(p->kernel, sizeof p->kernel, "%s", g_launch_name);
+    p->BNo = 256 - (d2.K - 1) * d2.dil;
+    sx_unblock_kernel<<<grid, 256>>>(draw, nullptr, dout, C, T, 1);
+    TCHECK(hipGetLastError());
+    TCHECK(hipDeviceSynchronize());
+    TCHECK(download(p->out, dout, n));
+    return VITS_OK;
+}
+
+// The identity behind split2h_pair_pk_mix (sx_split.hip.hpp), on the HOST in _Float16 / fmaf: for a value v (clamped to
+// +-65504 as the split clamps it) and h0 = f16(v), the low plane in the two-rounding-free forms
+//   old   f16((v - h0) * 2048)        fused   f16(fmaf(h0, -2048, v * 2048))
+// Array form: both low planes' bits for x[0 .. n).  Sweep form: every fp32 bit pattern first, first + 1, .. (count of them):
+// returns how many differ (two NaNs count as equal), *first_bad = the first such pattern.  No device is touched.
+static inline void split_identity_one(float x, uint16_t *o, uint16_t *f) {
+    const float v = std::fmin(std::fmax(x, -kF16Max), kF16Max);
+    const _Float16 h0 = (_Float16)v;
+    const _Float16 a = (_Float16)((v - (float)h0) * 2048.f);
+    const _Float16 b = (_Float16)std::fmaf((float)h0, -2048.f, v * 2048.f);
+    *o = __builtin_bit_cast(uint16_t, a);
+    *f = __builtin_bit_cast(uint16_t, b);
+}
+int vits_test_split_identity(const float *x, int64_t n, uint16_t *h1_old, uint16_t *h1_fused) {
+    if (!x || n < 0 || !h1_old || !h1_fused) return fail(nullptr, VITS_E_ARG, "split identity: missing array");
+    for (int64_t i = 0; i < n; i++) split_identity_one(x[i], h1_old + i, h1_fused + i);
+    return VITS_OK;
+}
+int64_t vits_test_split_identity_sweep(uint32_t first, uint64_t count, uint32_t *first_bad) {
+    int64_t bad = 0;
+    for (uint64_t k = 0; k < count; k++) {
+        const uint32_t bits = first + (uint32_t)k;
+        uint16_t o, f;
+        split_identity_one(__builtin_bit_cast(float, bits), &o, &f);
+        const bool nan_o = (o & 0x7fffu) > 0x7c00u, nan_f = (f & 0x7fffu) > 0x7c00u;
+        if (o != f && !(nan_o && nan_f)) {
+            if (bad == 0 && first_bad) *first_bad = bits;
+            bad++;
+        }
+    }
+    return bad;
+}
+
+// split_forms_kernel (test_dev.hip.hpp) on n values (n even): form 0 = split2h_pair_pk, 1 = conv_sx_pair_kernel's split.
+int vits_test_split_forms(int device_id, const float *x, int n, float slope, int form, uint16_t *h0, uint16_t *h1, float *pk, float *rec) {
+    if (int rc = test_dev(device_id)) return rc;
+    if (!x || n < 2 || (n & 1) || !(slope > 0.f) || slope > 1.f || form < 0 || form > 1 || !h0 || !h1 || !pk || !rec)
+        return fail(nullptr, VITS_E_ARG, "split forms hook: n even and >= 2, 0 < slope <= 1, form 0 or 1, every output given");
+    DevBufs D;
+    float *dx = D.up(x, (size_t)n);
+    uint16_t *d0 = D.alloc<uint16_t>((size_t)n), *d1 = D.alloc<uint16_t>((size_t)n);
+    float *dpk = D.alloc<float>((size_t)n / 2), *drec = D.alloc<float>((size_t)n);
+    TCHECK(D.err);
+    const unsigned blocks = (unsigned)((n / 2 + 255) / 256);
+    if (form == 0) split_forms_kernel<0><<<blocks, 256>>>(dx, n, slope, 1.f / slope, d0, d1, dpk, drec);
+    else split_forms_kernel<1><<<blocks, 256>>>(dx, n, slope, 1.f / slope, d0, d1, dpk, drec);
+    TCHECK(hipGetLastError());
+    TCHECK(hipDeviceSynchronize());
+    TCHECK(download(h0, d0, (size_t)n));
+    TCHECK(download(h1, d1, (size_t)n));
+    TCHECK(download(pk, dpk, (size_t)n / 2));
+    TCHECK(download(rec, drec, (size_t)n));
     return VITS_OK;
 }
 

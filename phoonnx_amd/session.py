@@ -2817,6 +2817,56 @@ def test_conv_pair16_epi(x, w1, b1, w2, b2, flags=("raw",), dil1=1, dil2=1, chai
             "peak": float(a.peak), "guard_ok": bool(a.guard_ok)}
 
 
+def test_split_forms(x, slope=0.1, form="pair", device_id=0):
+    """The activation -> operand-plane helpers on an array (include/vitsmi.h vits_test_split_forms): x [n], n even.
+    form: "engine" = split2h_pair_pk, "pair" = what conv_sx_pair_kernel uses.  Returns a dict: h0, h1 (float16 views of the
+    planes' bits), pk [n / 2], rec [n]."""
+    lib = _ffi.load()
+    x = np.ascontiguousarray(x, np.float32)
+    if x.ndim != 1 or x.size < 2 or x.size % 2:
+        raise ValueError("x: one dimension, an even number of values")
+    n = x.size
+    h0, h1 = np.empty(n, np.uint16), np.empty(n, np.uint16)
+    pk, rec = np.empty(n // 2, np.float32), np.empty(n, np.float32)
+    rc = lib.vits_test_split_forms(device_id, _ffi.ptr(x), n, float(slope), {"engine": 0, "pair": 1}[form], _ffi.ptr(h0), _ffi.ptr(h1),
+                                   _ffi.ptr(pk), _ffi.ptr(rec))
+    if rc != 0:
+        raise SessionError(_ffi.last_error(None))
+    return {"h0": h0.view(np.float16), "h1": h1.view(np.float16), "pk": pk, "rec": rec}
+
+
+# conv_sx_pair_kernel's launch flags by name (include/vitsmi.h VITS_PAIR_EPI_*)
+PAIR_EPI_FLAGS = {"acc": 1, "div": 2}
+
+
+def test_conv_pair_sx_epi(x, w1, b1, w2, b2, flags=(), dil1=1, dil2=1, chain=False, slope=0.1, div=1.0, out_init=None, lens=None,
+                          device_id=0):
+    """conv_sx_pair_kernel with the argument set the generator's conv_sx_pair() gives it (include/vitsmi.h
+    vits_test_conv_pair_sx_epi): one launch.  flags: names of PAIR_EPI_FLAGS.  lens [B]: utterance b's tensors end at lens[b]
+    columns.  The raw tensor starts as out_init, else as zeros.  Returns a dict: out (the raw tensor after the launch), kernel,
+    BNo."""
+    lib = _ffi.load()
+    f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+    x, w1, b1, w2, b2, out_init = (f32(a) for a in (x, w1, b1, w2, b2, out_init))
+    B, Cc, T = x.shape
+    K = w1.shape[2]
+    ln = None if lens is None else np.ascontiguousarray(lens, np.int64)
+    for name, arr, shape in (("w1", w1, (Cc, Cc, K)), ("w2", w2, (Cc, Cc, K)), ("b1", b1, (Cc,)), ("b2", b2, (Cc,)),
+                             ("out_init", out_init, (B, Cc, T)), ("lens", ln, (B,))):
+        if arr is not None and arr.shape != shape:
+            raise ValueError(f"{name} has shape {arr.shape}, the launch needs {shape}")
+    out = np.empty((B, Cc, T), np.float32)
+    a = _ffi.VitsTestConvPairSxEpiArgs()
+    a.B, a.C, a.T, a.K, a.dil1, a.dil2, a.chain = B, Cc, T, K, dil1, dil2, int(bool(chain))
+    a.flags = sum(PAIR_EPI_FLAGS[f] for f in flags)
+    a.slope, a.div = slope, div
+    a.x, a.w1, a.b1, a.w2, a.b2, a.lens, a.out_init, a.out = (_ffi.ptr(v) for v in (x, w1, b1, w2, b2, ln, out_init, out))
+    rc = lib.vits_test_conv_pair_sx_epi(device_id, C.byref(a))
+    if rc != 0:
+        raise SessionError(_ffi.last_error(None))
+    return {"out": out, "kernel": a.kernel.decode(), "BNo": a.BNo}
+
+
 def bench_conv1d_sx(B, Cin, Cout, T, K, dil=1, dbg=0, iters=20, device_id=0):
     """Average launch time (ms) of one conv shape on the split-exact engine -> (ms, tile config)."""
     lib = _ffi.load()
