@@ -478,8 +478,9 @@ int vits_last_sample_rates(vits_handle *h, int32_t *buf, int n);
  *   vits_last_sample_counts (N_b), vits_fetch_output, vits_last_pcm16 and every vits_deliver* work on the warped buffer as
  *     they stand; vits_last_y_lengths, vits_last_durations and vits_tap stay in frames;
  *   vits_last_token_spans answers k per token.
- * Out of scope: a warped run with an output rate or per-row output rates set is VITS_E_ARG ("not covered with an output
- * rate set") - folding the rate into step is a follow-up; the device-pointer entries and the vocoder-only chunked ones have no warped
+ * A warped run with an output rate or per-row output rates set is VITS_E_ARG ("not covered with an output rate set") unless
+ * vits_set_pitch_at_rate asked for the rate to be folded into step ("pitch at an output rate" below).
+ * Out of scope: the device-pointer entries and the vocoder-only chunked ones have no warped
  * form (the chunked entries with tokens: "streamed pitch" below); the speed is constant per token: no glides between tokens here ("pitch contours" below adds them); formants are not preserved;
  * vits_reserve does not count the warped buffer: a warped run grows the staging slab on demand, as any unreserved run does. */
 typedef struct {
@@ -548,10 +549,11 @@ int vits_warp_plan(const int64_t *durations, const float *semitones, int len, in
  *     2^(st / 12): the arithmetic mean, because k = L / mean step.  With equal ends that is (float)r.  The rest of the
  *     compensate contract - the refusal with forced durations, compensate = 0 passing ctl through - is "intonation"'s.
  *   Refusals, all before anything is enqueued, the previous run stays readable: an output rate or per-row rates set ("not
- *     covered with an output rate set"); a value that is not finite within [-12, 12], naming token_semitones[b,t] or
+ *     covered with an output rate set"; with vits_set_pitch_at_rate: only a pitched row whose ratio to the native rate lies
+ *     outside [1/4, 4], "pitch at an output rate" below); a value that is not finite within [-12, 12], naming token_semitones[b,t] or
  *     token_semitones_end[b,t]; compensate with forced durations; a host-only handle.
- * Out of scope: glides with an output rate (chunked runs: "streamed pitch" below); curves other than linear in the output index; formant
- * preservation; contour positions in time (the Python pitch_contour= places its points by phoneme count); vits_reserve does
+ * Chunked runs are "streamed pitch" below, an output rate "pitch at an output rate" below.
+ * Out of scope: curves other than linear in the output index; formant preservation; contour positions in time (the Python pitch_contour= places its points by phoneme count); vits_reserve does
  * not count the buffer, as for the warp. */
 typedef struct {
     int64_t n0;          /* first output sample of the segment */
@@ -575,6 +577,65 @@ int vits_glide_token(float st0, float st1, int64_t *step0, int64_t *step1, float
 int vits_glide_cutoff(int64_t step, int64_t *c, int32_t *half_taps);
 int vits_glide_plan(const int64_t *durations, const float *st0, const float *st1, int len, int hop, vits_glide_seg *segs,
                     int64_t *spans, int64_t *n_out);
+
+/* ---- pitch at an output rate: the rate folded into the warp's step ---------------------------------------------------------
+ * vits_set_pitch_at_rate(h, 1) - handle state for the following runs, like vits_set_tails; 0, the default, keeps every pitched
+ * entry's refusal "not covered with an output rate set" - makes the pitched entries take an output rate.
+ * The warp is a windowed-sinc resampler with a step per token, so a pitched run with an output rate (vits_set_output_rate) or
+ * per-row rates (vits_set_output_rates) set renders in ONE filter pass: with the row's plan (L, M) - fo = fi * L / M -
+ *   Folded token: step = llrint(2^(st / 12) * (double)M / (double)L * ONE); c and Kh from the step by vits_warp_token's rule.
+ *     A gliding token's a and b are the folded steps of st0 and st1; the closed forms and the cutoff rule of "pitch contours"
+ *     are used unchanged - the integer rule equals the double rule on all 516 097 steps of [ONE / 8, 8 ONE].
+ *   Row plans: those of "intonation" / "pitch contours" given the steps.  P = (cum * hop) << FB stays a NATIVE input position,
+ *     the overshoot is carried; n0, k and N_b are then delivered samples: vits_last_token_spans, vits_last_sample_counts, the
+ *     fades, per-token volume and alignments work on them as they stand.  compensate is unchanged: the duration multiplier
+ *     is r_t without the ratio, because durations are native frames.
+ *   Admitted: 1/4 <= M / L <= 4 on every PITCHED row, so steps lie in [ONE / 8, 8 ONE] and Kh <= 151 (c = 6963 at 8 ONE).  A
+ *     pitched row at a rate outside that is VITS_E_ARG naming the rates, before anything is enqueued.
+ *   A gliding token of a folded plan has at most 2^22 output samples (VITS_E_ARG naming the token): |b - a| < 2^19, so
+ *     |b - a| * j * (j - 1) < 2^19 * 2^44 stays inside 64 bits; 2^23 would not.  Plans without a rate keep 2^23.
+ *   Identity rows: a row whose tokens all have st == 0 (both ends) is not rendered by the folded plan but by the resampler's
+ *     rule, bit for bit the row of a run at that rate without pitch: N_b = ceil(n_b * L / M), token spans the differences of
+ *     ceil(cum_t * hop * L / M) clamped to N_b.  An unpitched request does not change because it was batched with a pitched
+ *     one.  With L == M everything is "intonation" / "pitch contours".
+ * The run makes one launch of the wide kernels (warp_rate_kernel / glide_rate_kernel) from the native waveform into the
+ * staging slab in place of the resampler's launch and the warp's; with per-row rates every row is folded by its own (L_b,
+ * M_b).  Afterwards everything that works behind a warped run works as it stands, and vits_last_sample_rates answers the
+ * output rate(s).
+ * (In float64, over 22050 -> 8000 / 11025 / 16000 / 24000 / 44100 / 48000, 16000 -> 8000 / 48000, 24000 -> 8000, 32000 -> 8000
+ *   and 8000 -> 32000 at -12, -5, 0, +3 and +12 semitones: max s * sum|w| is 1.947, and a tone at 0.15 * min(1, 1 / step)
+ *   cycles per sample lands at step times its frequency within 1.83e-5.)
+ * Chunked runs (vits_run_chunked_glided / _enc_glided) with ONE output rate run the warp stage of "streamed pitch" with the folded
+ * plan on the native pieces and no resampler stage; total = S_w at the output rate, and pack, shaping, limiter and leading trim
+ * work on it unchanged.  The pieces joined are the whole run's [B][S_w], bit for bit.
+ * Out of scope: pitch together with a fitted duration; chunked runs with per-row rates ("not covered with an output rate set
+ * per row"); the device-pointer entries; ratios outside
+ * [1/4, 4]; formant preservation.  vits_reserve does not count the buffer, as for the warp.
+ *
+ * The plan - pure host code.  vits_warp_token_rate / vits_warp_plan_rate / vits_glide_plan_rate: vits_warp_token /
+ * vits_warp_plan / vits_glide_plan with (L, M) folded in (VITS_E_ARG for a ratio outside [1/4, 4]).  vits_glide_cutoff_rate:
+ * c and Kh of a step within [ONE / 8, 8 ONE].  vits_glide_pos_rate: pos_j and (step nullable) s_j of one record within the
+ * folded limits, 0 <= j <= k.  vits_rate_identity_spans: an identity row's spans [len] (nullable) and N_b from n_in valid
+ * input samples. */
+int vits_set_pitch_at_rate(vits_handle *h, int on);
+int vits_warp_token_rate(float semitones, int64_t L, int64_t M, int64_t *step, int64_t *cutoff, int32_t *half_taps);
+int vits_warp_plan_rate(const int64_t *durations, const float *semitones, int len, int hop, int64_t L, int64_t M, vits_warp_seg *segs,
+                        int64_t *spans, int64_t *n_out);
+int vits_glide_plan_rate(const int64_t *durations, const float *st0, const float *st1, int len, int hop, int64_t L, int64_t M,
+                         vits_glide_seg *segs, int64_t *spans, int64_t *n_out);
+int vits_glide_cutoff_rate(int64_t step, int64_t *c, int32_t *half_taps);
+int vits_glide_pos_rate(const vits_glide_seg *seg, int64_t j, int64_t *pos, int64_t *step);
+int vits_rate_identity_spans(const int64_t *durations, int len, int hop, int64_t L, int64_t M, int64_t n_in, int64_t *spans,
+                             int64_t *n_out);
+/* Streams of a folded plan ("streamed pitch" gives the rules): the emit rule counts with the PLAN's largest Kh - `half`, the
+ * largest over every row's records - in place of 38, and n_cap with its least step in place of ONE / 2:
+ * n_cap = min(S_w, ceil((piece_samples + half) * ONE / min_step)).  An identity row is the resampler's: ready(X) =
+ * min(N_b, ceil((X - K / 2) * L / M)) (0 while X <= K / 2) - every output whose K inputs exist; its step floor(M * ONE / L)
+ * joins the least.  A plan without a rate gets exactly the values of vits_warp_emit_end / vits_warp_stream_cap. */
+int vits_warp_emit_end_rate(const vits_warp_seg *segs, int n_segs, int64_t n_in, int64_t n_out, int64_t X, int half, int64_t *ready);
+int vits_glide_emit_end_rate(const vits_glide_seg *segs, int n_segs, int64_t n_in, int64_t n_out, int64_t X, int half, int64_t *ready);
+int vits_identity_emit_end_rate(int64_t L, int64_t M, int64_t K, int64_t n_in, int64_t X, int64_t *ready);
+int64_t vits_warp_stream_cap_rate(int64_t piece_samples, int64_t S_w, int64_t min_step, int half);
 
 /* ---- delivery: the last run's audio packed per request on the device - PCM16, G.711, F32, pauses -------------------
  * The reference post-processes and frames every sentence on the host (phoonnx/voice.py:271-282 peak-normalise / volume /
@@ -1115,9 +1176,11 @@ int vits_run_vocoder_chunked_enc_trimmed(vits_handle *h, const float *z, int B, 
  *   otherwise the glide's.  All-zero semitones make the call vits_run_chunked_ctl / vits_run_chunked_enc* exactly: the same chunk
  *   ranges, bits and total_launches, no history, no plan.  compensate is "intonation"'s / "pitch contours"'.
  *   Refusals, before anything is enqueued, the previous run stays readable: an output rate or per-row rates set ("not covered
- *   with an output rate set"); a bad value, naming [b,t]; compensate with forced durations; a host-only handle.
+ *   with an output rate set"; with vits_set_pitch_at_rate: per-row rates, "... per row", and one rate whose ratio to the
+ *   native rate lies outside [1/4, 4]); a bad value, naming [b,t]; compensate with forced durations; a host-only handle.
  *   vits_last_sample_counts (N_b) and vits_last_token_spans answer from the plan callback on, and after the run.
- * Out of scope: pitch with an output rate, whole or streamed; the vocoder-only chunked entries (no tokens: no warped form);
+ * With one output rate set and vits_set_pitch_at_rate on, the plan is the folded one ("pitch at an output rate").
+ * Out of scope: pitch with per-row output rates in a chunked run; the vocoder-only chunked entries (no tokens: no warped form);
  * vits_reserve does not count the history; formant preservation. */
 int vits_warp_emit_end(const vits_warp_seg *segs, int n_segs, int64_t n_in, int64_t n_out, int64_t X, int64_t *ready);
 int vits_glide_emit_end(const vits_glide_seg *segs, int n_segs, int64_t n_in, int64_t n_out, int64_t X, int64_t *ready);
@@ -1517,6 +1580,26 @@ int vits_test_warp_pieces(int device_id, const float *x, const int64_t *counts, 
 int vits_test_glide_pieces(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_glide_seg *segs,
                            const int32_t *seg_first /* [B+1] */, const int64_t *piece_bounds, int n_pieces, float *y, int S_w,
                            int64_t *ranges, int max_ranges);
+/* The wide kernels by value ("pitch at an output rate"): x [B][S] host, row b at in_rates[b], counts [B], the rows' records within the
+ * FOLDED limits (steps in [ONE / 8, 8 ONE], Kh <= 151, a gliding token at most 2^22 samples; vits_test_warp / vits_test_glide
+ * keep refusing records outside the unfolded ones), out_rates [B] the rate each row is delivered at (0 or in_rates[b]: native).
+ * A row without a record is an identity row: ceil(n_b * L / M) samples by the resampler's rule.  The launch renders output
+ * samples [n_lo, n_hi) of every row into y [B][n_hi - n_lo]; every column is written, zeros behind N_b. */
+int vits_test_warp_rate(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_warp_seg *segs,
+                        const int32_t *seg_first /* [B+1] */, const int32_t *in_rates, const int32_t *out_rates, int n_lo, int n_hi,
+                        float *y);
+int vits_test_glide_rate(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_glide_seg *segs,
+                         const int32_t *seg_first /* [B+1] */, const int32_t *in_rates, const int32_t *out_rates, int n_lo, int n_hi,
+                        float *y);
+
+/* ... and the wide streamed stage: vits_test_warp_pieces' walk over a folded plan at one pair of rates - what a chunked run
+ * has - with n_cap = vits_warp_stream_cap_rate(longest piece, S_w, the plan's least step, its largest Kh). */
+int vits_test_warp_rate_pieces(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_warp_seg *segs,
+                               const int32_t *seg_first /* [B+1] */, int in_rate, int out_rate, const int64_t *piece_bounds,
+                               int n_pieces, float *y, int S_w, int64_t *ranges, int max_ranges);
+int vits_test_glide_rate_pieces(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_glide_seg *segs,
+                                const int32_t *seg_first /* [B+1] */, int in_rate, int out_rate, const int64_t *piece_bounds,
+                                int n_pieces, float *y, int S_w, int64_t *ranges, int max_ranges);
 
 /* The kernels that turn tokens into frames and frames into samples, by value.  Every hook checks its sizes and extents on the
  * host (VITS_E_ARG) and launches the pipeline's kernel with the pipeline's grid.

@@ -212,6 +212,10 @@ EXPORTS = [
     "vits_run_async_glided", "vits_glide_token", "vits_glide_cutoff", "vits_glide_plan", "vits_test_glide",
     "vits_warp_emit_end", "vits_glide_emit_end", "vits_warp_stream_cap", "vits_run_chunked_glided", "vits_run_chunked_enc_glided",
     "vits_test_warp_pieces", "vits_test_glide_pieces",
+    "vits_set_pitch_at_rate", "vits_warp_token_rate", "vits_warp_plan_rate", "vits_glide_plan_rate", "vits_glide_cutoff_rate", "vits_glide_pos_rate",
+    "vits_rate_identity_spans", "vits_test_warp_rate", "vits_test_glide_rate",
+    "vits_warp_emit_end_rate", "vits_glide_emit_end_rate", "vits_identity_emit_end_rate", "vits_warp_stream_cap_rate",
+    "vits_test_warp_rate_pieces", "vits_test_glide_rate_pieces",
     "vits_fit_plan", "vits_run_async_fitted", "vits_run_chunked_fitted", "vits_run_chunked_enc_fitted", "vits_last_fit",
     "vits_test_fit_durations",
     "vits_test_durations", "vits_test_expand_prior", "vits_test_fill_normal", "vits_test_fill_normal_rows", "vits_test_post_conv",
@@ -350,6 +354,22 @@ def load():
                                                 C.POINTER(VitsContour), C.c_int, ENC_CHUNK_TRIM_FN, vp]
     for name in ("vits_test_warp_pieces", "vits_test_glide_pieces"):
         getattr(lib, name).argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, vp, C.c_int]
+    lib.vits_set_pitch_at_rate.argtypes = [vp, C.c_int]
+    lib.vits_warp_token_rate.argtypes = [C.c_float, C.c_int64, C.c_int64, i64p, i64p, C.POINTER(C.c_int32)]
+    lib.vits_warp_plan_rate.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int64, C.c_int64, vp, vp, i64p]
+    lib.vits_glide_plan_rate.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int64, C.c_int64, vp, vp, i64p]
+    lib.vits_glide_cutoff_rate.argtypes = [C.c_int64, i64p, C.POINTER(C.c_int32)]
+    lib.vits_glide_pos_rate.argtypes = [vp, C.c_int64, i64p, i64p]
+    lib.vits_rate_identity_spans.argtypes = [vp, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, vp, i64p]
+    for name in ("vits_warp_emit_end_rate", "vits_glide_emit_end_rate"):
+        getattr(lib, name).argtypes = [vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int, i64p]
+    lib.vits_identity_emit_end_rate.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, i64p]
+    lib.vits_warp_stream_cap_rate.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int]
+    lib.vits_warp_stream_cap_rate.restype = C.c_int64
+    for name in ("vits_test_warp_rate_pieces", "vits_test_glide_rate_pieces"):
+        getattr(lib, name).argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int]
+    for name in ("vits_test_warp_rate", "vits_test_glide_rate"):
+        getattr(lib, name).argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, vp]
     lib.vits_fit_plan.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(VitsFit), vp, vp, vp, vp]
     lib.vits_run_async_fitted.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.POINTER(VitsNoise), C.POINTER(VitsControls),
                                           C.POINTER(VitsFit)]

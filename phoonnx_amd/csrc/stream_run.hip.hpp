@@ -82,6 +82,13 @@ struct WarpRun {
     WarpStreamBufs wb{};
     const float *G = nullptr;
     std::vector<char> up;               // (pageable source of the plan's upload where the caller has no pinned block)
+    // a folded plan ("pitch at an output rate"): its rows in place of `rows`, the largest Kh the emit rule counts with, and the
+    // wide kernels in the windows
+    bool folded = false;
+    std::vector<WarpRateRow> rrows;     // [B]
+    int64_t half = kWarpMaxHalf;
+    size_t row_bytes() const { return folded ? sizeof(WarpRateRow) : sizeof(WarpRow); }
+    int32_t row_out(int b) const { return folded ? rrows[(size_t)b].n_out : rows[(size_t)b].n_out; }
     int64_t n_segs() const { return glide ? (int64_t)gsegs.size() : (int64_t)wsegs.size(); }
 };
 
@@ -97,9 +104,9 @@ inline hipError_t warp_run_begin(WarpRun &r, const WarpStreamBufs &wb, const flo
         pin = r.up.data();
     }
     if (seg_bytes) std::memcpy(pin, r.glide ? (const void *)r.gsegs.data() : (const void *)r.wsegs.data(), seg_bytes);
-    std::memcpy(pin + seg_bytes, r.rows.data(), (size_t)B * sizeof(WarpRow));
+    std::memcpy(pin + seg_bytes, r.folded ? (const void *)r.rrows.data() : (const void *)r.rows.data(), (size_t)B * r.row_bytes());
     int *pin_nout = reinterpret_cast<int *>(pin + wb.plan_bytes);
-    for (int b = 0; b < B; b++) pin_nout[b] = r.rows[(size_t)b].n_out;
+    for (int b = 0; b < B; b++) pin_nout[b] = r.row_out(b);
     hipError_t e = hipMemcpyAsync(wb.segs, pin, wb.plan_bytes, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(wb.n_out, pin_nout, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st);
     return e;
@@ -111,8 +118,13 @@ inline hipError_t warp_run_piece(WarpRun &r, const float *x, int64_t x_pitch, in
     hipError_t e = hipSuccess;
     if (n > 0)
         e = hipMemcpy2DAsync(r.wb.hist + first, (size_t)r.wb.hist_pitch * 4, x, (size_t)x_pitch * 4, (size_t)n * 4, B, hipMemcpyDeviceToDevice, st);
-    const int64_t end = r.glide ? warp_emit_end(r.gsegs.data(), r.rows, r.S_w, first + n, is_last)
-                                : warp_emit_end(r.wsegs.data(), r.rows, r.S_w, first + n, is_last);
+    int64_t end;
+    if (r.folded)
+        end = r.glide ? warp_rate_emit_end(r.gsegs.data(), r.rrows, r.S_w, first + n, is_last, r.half)
+                      : warp_rate_emit_end(r.wsegs.data(), r.rrows, r.S_w, first + n, is_last, r.half);
+    else
+        end = r.glide ? warp_emit_end(r.gsegs.data(), r.rows, r.S_w, first + n, is_last)
+                      : warp_emit_end(r.wsegs.data(), r.rows, r.S_w, first + n, is_last);
     r.e_end = end > r.e_end ? end : r.e_end;
     return e;
 }
@@ -132,7 +144,7 @@ inline hipError_t warp_run_window(WarpRun &r, int B, hipStream_t st, const float
     launches = 1;
     r.emitted += e_n;
     const auto args = [&](auto &a) {
-        a.rows = r.wb.rows;
+        a.rows = static_cast<decltype(a.rows)>(r.wb.rows);
         a.G = r.G;
         a.x = r.wb.hist;
         a.x_pitch = r.wb.hist_pitch;
@@ -141,6 +153,18 @@ inline hipError_t warp_run_window(WarpRun &r, int B, hipStream_t st, const float
         a.n_lo = (int)e_first;
         a.n_hi = (int)(e_first + e_n);
     };
+    if (r.folded && r.glide) {
+        GlideRateArgs a{};
+        a.segs = reinterpret_cast<const vits_glide_seg *>(r.wb.segs);
+        args(a);
+        return launch_glide_rate(a, B, st);
+    }
+    if (r.folded) {
+        WarpRateArgs a{};
+        a.segs = r.wb.segs;
+        args(a);
+        return launch_warp_rate(a, B, st);
+    }
     if (r.glide) {
         GlideArgs a{};
         a.segs = reinterpret_cast<const vits_glide_seg *>(r.wb.segs);

@@ -164,6 +164,9 @@ struct vits_handle {
     size_t warp_pin_cap = 0;
     std::vector<int64_t> warp_counts, warp_spans;
     int warp_T = 0;
+    // vits_set_pitch_at_rate: a pitched run with an output rate set folds the rate into the warp's step ("pitch at an output
+    // rate").  Off - the default -, such a run is refused as it always was.
+    bool pitch_at_rate = false;
 };
 
 // chunked rendering (vits_run_chunked / vits_run_vocoder_chunked): where the audio goes
@@ -2197,7 +2200,7 @@ int warp_run_as(vits_handle *h, const RunRows &rr, int B, int T, PlanRow plan_ro
     HIPCHECK(h, hipMemcpyAsync(wb.front.n_out, pin_nout, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
     WarpArgsT<Seg> a{};
     a.segs = reinterpret_cast<const Seg *>(wb.segs);
-    a.rows = wb.rows;
+    a.rows = static_cast<const WarpRow *>(wb.rows);
     a.G = h->warp_G;
     a.x = h->d_out;
     a.x_pitch = S;
@@ -2221,6 +2224,121 @@ int warp_run_as(vits_handle *h, const RunRows &rr, int B, int T, PlanRow plan_ro
 int warp_run(vits_handle *h, const RunRows &rr, int B, int T) {
     if (!rr.semitones_end) return warp_run_as<vits_warp_seg>(h, rr, B, T, warp_plan_row(rr, T), launch_warp);
     return warp_run_as<vits_glide_seg>(h, rr, B, T, glide_plan_row(rr, T), launch_glide);
+}
+
+// ---- pitch at an output rate (vitsmi.h, "pitch at an output rate"): the rate folded into the warp's steps, one launch from the
+// native waveform into the staging slab in place of resample_run / resample_rows_run + warp_run.
+
+// the resampler's plan of row b under the handle's rate or the rows' rates (nullptr: a native row)
+const ResampleDev *rate_of_row(const vits_handle *h, int b) {
+    if (h->rs.plan.on()) return &h->rs;
+    if (h->rows.on() && b < (int)h->rows.plan_of.size() && h->rows.plan_of[b] >= 0) return &h->rows.plans[h->rows.plan_of[b]];
+    return nullptr;
+}
+
+// The folded plans of a run's rows from the host copy of the durations: warp_plan_run's sibling.  row_in: the input samples a
+// row has at most.  An unpitched row leaves no record - it is an identity row, its spans the resampler's rule -; every other
+// row is planned with its own (L_b, M_b) folded in.  The whole run and the streamed one plan HERE.
+template <class Seg>
+int warp_rate_plan_run(vits_handle *h, const RunRows &rr, int B, int T, int64_t row_in, std::vector<Seg> &segs, std::vector<int32_t> &first,
+                       std::vector<int64_t> &spans, std::vector<WarpRateRow> &rows, int64_t &S_w) {
+    const int hop = h->model.hop;
+    if (h->h_dur_B != B || h->h_dur_T != T) return fail(h, VITS_E_ARG, "no durations to plan the warp from");
+    std::vector<int64_t> n_in((size_t)B), L((size_t)B, 1), M((size_t)B, 1);
+    for (int b = 0; b < B; b++) {
+        const int64_t n = (int64_t)h->h_ylen[b] * hop;
+        n_in[b] = n < 0 ? 0 : (n > row_in ? row_in : n);
+        if (const ResampleDev *d = rate_of_row(h, b)) {
+            L[b] = d->plan.L;
+            M[b] = d->plan.M;
+        }
+    }
+    auto plan_row = [&](int b, const int64_t *dur, int len, int hp, Seg *sg, int64_t *sp, int64_t &ns, int64_t &N) -> std::string {
+        const float *s0 = rr.semitones + (size_t)b * T, *s1 = rr.semitones_end ? rr.semitones_end + (size_t)b * T : nullptr;
+        if (warp_rate_unpitched(s0, s1, len)) {
+            ns = 0;
+            N = warp_rate_identity(dur, len, hp, L[b], M[b], n_in[b], sp);
+            return "";
+        }
+        if constexpr (std::is_same_v<Seg, vits_warp_seg>) return warp_plan_rate(dur, s0, len, hp, L[b], M[b], sg, sp, ns, N);
+        else return glide_plan_rate(dur, s0, s1, len, hp, L[b], M[b], sg, sp, ns, N);
+    };
+    std::vector<WarpRow> narrow;
+    const std::string e = warp_plan_rows(h->h_dur.data(), rr.semitone_lens, n_in.data(), B, T, hop, plan_row, segs, first, spans, narrow, S_w);
+    if (!e.empty()) return fail(h, VITS_E_ARG, "%s", e.c_str());
+    S_w = warp_rate_rows(segs.data(), first.data(), n_in.data(), L.data(), M.data(), B, rows);
+    if (S_w > INT_MAX) return fail(h, VITS_E_ARG, "a warped row of %lld samples: more than a row admits (%d)", (long long)S_w, INT_MAX);
+    for (int b = 0; b < B; b++)
+        if (const ResampleDev *d = rate_of_row(h, b)) {
+            rows[(size_t)b].table = d->table;
+            rows[(size_t)b].Kp = d->Kp;
+            rows[(size_t)b].K = (int32_t)d->plan.K;
+        }
+    return 0;
+}
+
+template <class Seg, class Launch>
+int warp_rate_run_as(vits_handle *h, const RunRows &rr, int B, int T, Launch launch) {
+    const int S = h->S;
+    std::vector<Seg> segs;
+    std::vector<int32_t> first;
+    std::vector<int64_t> spans;
+    std::vector<WarpRateRow> rows;
+    int64_t S_w = 1;
+    if (int rc = warp_rate_plan_run(h, rr, B, T, S, segs, first, spans, rows, S_w)) return rc;
+    WarpBufs wb;
+    if (int rc = slab_carve(h, h->io, "staging", [&](Carver &cv) { wb = carve_warp(cv, B, (int)S_w, (int64_t)segs.size(), sizeof(WarpRateRow)); }))
+        return rc;
+    hipStream_t st = h->stream;
+    // [segs | rows | n_out] in pinned memory
+    if (int rc = warp_device_begin(h, wb.plan_bytes + (size_t)B * sizeof(int))) return rc;
+    const size_t seg_bytes = segs.size() * sizeof(Seg);
+    if (seg_bytes) std::memcpy(h->warp_pin, segs.data(), seg_bytes);
+    std::memcpy(h->warp_pin + seg_bytes, rows.data(), (size_t)B * sizeof(WarpRateRow));
+    int *pin_nout = reinterpret_cast<int *>(h->warp_pin + wb.plan_bytes);
+    for (int b = 0; b < B; b++) pin_nout[b] = rows[(size_t)b].n_out;
+    HIPCHECK(h, hipMemcpyAsync(wb.segs, h->warp_pin, wb.plan_bytes, hipMemcpyHostToDevice, st));
+    HIPCHECK(h, hipMemcpyAsync(wb.front.n_out, pin_nout, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
+    WarpRateArgsT<Seg> a{};
+    a.segs = reinterpret_cast<const Seg *>(wb.segs);
+    a.rows = static_cast<const WarpRateRow *>(wb.rows);
+    a.G = h->warp_G;
+    a.x = h->d_out;
+    a.x_pitch = S;
+    a.y = wb.front.out;
+    a.y_pitch = S_w;
+    a.n_hi = (int)S_w;
+    const hipError_t le = launch(a, B, st);
+    if (le != hipSuccess) return fail(h, VITS_E_DEVICE, "warp launch failed: %s", hipGetErrorString(le));
+    h->stats.total_launches += 1;
+    h->d_out = wb.front.out;
+    h->S = (int)S_w;
+    h->d_nout = wb.front.n_out;
+    h->rs_run_K = 0;  // (carve_warp's walk: no carry)
+    h->rs_run_L = h->rs.plan.on() ? h->rs.plan.L : 1;
+    h->rs_run_M = h->rs.plan.on() ? h->rs.plan.M : 1;
+    h->out_resampled = true;
+    if (h->rows.on()) {  // what resample_rows_run leaves about the rows of a run
+        h->run_rates.assign(B, h->rows.fi);
+        h->run_L.assign(B, 1);
+        h->run_M.assign(B, 1);
+        for (int b = 0; b < B; b++)
+            if (const ResampleDev *d = rate_of_row(h, b)) {
+                h->run_rates[b] = d->plan.fo;
+                h->run_L[b] = d->plan.L;
+                h->run_M[b] = d->plan.M;
+            }
+    }
+    h->warp_counts.resize((size_t)B);
+    for (int b = 0; b < B; b++) h->warp_counts[(size_t)b] = rows[(size_t)b].n_out;
+    h->warp_spans = std::move(spans);
+    h->warp_T = T;
+    return 0;
+}
+
+int warp_rate_run(vits_handle *h, const RunRows &rr, int B, int T) {
+    if (!rr.semitones_end) return warp_rate_run_as<vits_warp_seg>(h, rr, B, T, launch_warp_rate);
+    return warp_rate_run_as<vits_glide_seg>(h, rr, B, T, launch_glide_rate);
 }
 
 // The two pinned buffers (vits_handle::ring) finished pieces reach the host through.  A piece is copied into slot(); queue()
@@ -2264,21 +2382,33 @@ int render_chunks(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int
     const int ov = m.gen_rf_frames, hop = m.hop;
     const int chunk = sink.chunk_frames;
     const ResamplePlan &rp = h->rs.plan;
-    const bool rs = rp.on();             // an output rate: the batch path's [B][S_out], bit for bit
+    // an output rate: the batch path's [B][S_out], bit for bit - but a pitched stream folds the rate into the warp's steps
+    // ("pitch at an output rate") and runs no resampler stage: the two are never both on
+    const bool folded = pitch != nullptr && rp.on();
+    const bool rs = rp.on() && !folded;
     const bool enc = sink.fmt != nullptr;  // the encoded form of the sink; false executes what it always executed
-    // Streamed pitch (vitsmi.h, "streamed pitch"; the entries refuse it at an output rate): the rows' plans first, from the
+    // Streamed pitch (vitsmi.h, "streamed pitch"; at an output rate the folded plan: "pitch at an output rate"): the rows' plans first, from the
     // durations on the host - the whole run's planning -, so that everything below sees the OUTPUT timeline: S_w, N_b.
     const bool warp = pitch != nullptr;
     WarpRun wrun;
     if (warp) {
         h->d_out = nullptr;  // (as under a plan callback: the run has begun, the host's counts are this run's from here on)
         wrun.glide = pitch->semitones_end != nullptr;
-        const int rc = wrun.glide ? warp_plan_run(h, *pitch, B, T, (int64_t)F * hop, glide_plan_row(*pitch, T), wrun.gsegs, wrun.first,
+        wrun.folded = folded;
+        const int rc = folded ? (wrun.glide ? warp_rate_plan_run(h, *pitch, B, T, (int64_t)F * hop, wrun.gsegs, wrun.first, wrun.spans, wrun.rrows, wrun.S_w)
+                                            : warp_rate_plan_run(h, *pitch, B, T, (int64_t)F * hop, wrun.wsegs, wrun.first, wrun.spans, wrun.rrows, wrun.S_w))
+                       : wrun.glide ? warp_plan_run(h, *pitch, B, T, (int64_t)F * hop, glide_plan_row(*pitch, T), wrun.gsegs, wrun.first,
                                                   wrun.spans, wrun.rows, wrun.S_w)
                                   : warp_plan_run(h, *pitch, B, T, (int64_t)F * hop, warp_plan_row(*pitch, T), wrun.wsegs, wrun.first,
                                                   wrun.spans, wrun.rows, wrun.S_w);
         if (rc) return rc;
-        warp_remember(h, wrun.rows, std::vector<int64_t>(wrun.spans), T);
+        if (folded) {
+            h->warp_counts.resize((size_t)B);
+            for (int b = 0; b < B; b++) h->warp_counts[(size_t)b] = wrun.row_out(b);
+            h->warp_spans = wrun.spans;
+            h->warp_T = T;
+        } else
+            warp_remember(h, wrun.rows, std::vector<int64_t>(wrun.spans), T);
     }
     // encoded form: the rows' valid samples (host: the callback's valid[]; device: the kernel's)
     std::vector<int64_t> row_n;
@@ -2286,7 +2416,7 @@ int render_chunks(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int
         row_n.resize((size_t)B);
         for (int b = 0; b < B; b++) {
             const int64_t nb = (int64_t)(ylen ? h->h_ylen[b] : F) * hop;
-            row_n[b] = warp ? (int64_t)wrun.rows[(size_t)b].n_out : rs ? rp.count(nb) : nb;
+            row_n[b] = warp ? (int64_t)wrun.row_out(b) : rs ? rp.count(nb) : nb;
         }
     }
     // The shaped form of the encoded sink (vitsmi.h, "shaped streaming"): the plan callback first - the durations and the
@@ -2322,13 +2452,18 @@ int render_chunks(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int
     int S_out = 0;
     if (rs)
         if (int rc = resample_count(h, (int64_t)F * hop, S_out)) return rc;
-    const int64_t n_cap = warp ? warp_stream_cap((int64_t)(chunk < F ? chunk : F) * hop, wrun.S_w) : 0;
+    int64_t cap_step = kWarpMinStep;  // a folded plan's cap counts with its own least step and largest Kh
+    if (folded) {
+        if (wrun.glide) warp_rate_plan_extent(wrun.gsegs.data(), wrun.rrows, wrun.half, cap_step);
+        else warp_rate_plan_extent(wrun.wsegs.data(), wrun.rrows, wrun.half, cap_step);
+    }
+    const int64_t n_cap = warp ? warp_stream_cap((int64_t)(chunk < F ? chunk : F) * hop, wrun.S_w, cap_step, wrun.half) : 0;
     const int64_t total = warp ? wrun.S_w : rs ? (int64_t)S_out : (int64_t)F * hop;
     const int64_t n_max = warp ? (n_cap + sL < total ? n_cap + sL : total) : stream_n_max(rp, chunk, F, hop, sL, total);
     StreamBufs sb{};
     WarpStreamBufs wsb{};
     if (int rc = slab_carve(h, h->io, "staging", [&](Carver &cv) {
-            if (warp) wsb = carve_warp_stream(cv, B, (int64_t)F * hop, n_cap, wrun.n_segs());
+            if (warp) wsb = carve_warp_stream(cv, B, (int64_t)F * hop, n_cap, wrun.n_segs(), wrun.row_bytes());
             sb = carve_stream(cv, B, total, n_max, rs ? (int)rp.K : 0, enc, shaped, sL, shaped ? stream_knot_count(&shp, B) : 0, trimmed);
         }))
         return rc;
@@ -2871,6 +3006,13 @@ int vits_set_timing(vits_handle *h, int enable) {
     return VITS_OK;
 }
 
+int vits_set_pitch_at_rate(vits_handle *h, int on) {
+    if (!h) return VITS_E_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    h->pitch_at_rate = on != 0;
+    return VITS_OK;
+}
+
 int vits_set_tails(vits_handle *h, int reference) {
     if (!h) return VITS_E_ARG;
     std::lock_guard<std::mutex> lk(h->mu);
@@ -3254,12 +3396,14 @@ static int run_device_locked(vits_handle *h, const int64_t *ids, const int64_t *
     if (int rc = run_frames(h, B, T, rr, sid, noise ? noise->noise_z : nullptr, noise ? noise->noise_z_stride : 0,
                             seed, sink))
         return rc;
-    if (h->rs.plan.on() && !sink)
+    // a pitched run at an output rate: no resampler stage - the rate is folded into the warp's one launch
+    const bool folded = rr.semitones && !sink && (h->rs.plan.on() || h->rows.on());
+    if (h->rs.plan.on() && !sink && !folded)
         if (int rc = resample_run(h, h->d_ylen, B)) return rc;
-    if (h->rows.on() && !sink)
+    if (h->rows.on() && !sink && !folded)
         if (int rc = resample_rows_run(h, h->d_ylen, B)) return rc;
     if (rr.semitones && !sink)
-        if (int rc = warp_run(h, rr, B, T)) return rc;
+        if (int rc = folded ? warp_rate_run(h, rr, B, T) : warp_run(h, rr, B, T)) return rc;
     ylen_to_i64<<<(B + 63) / 64, 64, 0, h->stream>>>(h->d_ylen, h->d_ylen64, B);
     range_end(h);
     if (out) {
@@ -3541,7 +3685,7 @@ struct Intoned {
 };
 
 static int host_intonation(vits_handle *h, const vits_controls *ctl, const int64_t *lens, int B, int T, const float *st0, const float *st1,
-                           int compensate, const char *entry, Intoned &in) {
+                           int compensate, const char *entry, bool chunked, Intoned &in) {
     if (!ctl) return fail(h, VITS_E_ARG, "null argument");
     bool warped = false, glided = false;
     if (st0 || st1) {
@@ -3567,7 +3711,19 @@ static int host_intonation(vits_handle *h, const vits_controls *ctl, const int64
     if (!warped) return VITS_OK;
     if (compensate && ctl->durations)
         return fail(h, VITS_E_ARG, "compensate and forced durations are contradictory: forced durations are the rendered ones");
-    if (h->rs.plan.on() || h->rows.on()) return fail(h, VITS_E_ARG, "%s is not covered with an output rate set", entry);
+    // An output rate is refused unless the handle asked for it to be folded into the steps (vits_set_pitch_at_rate; "pitch at an
+    // output rate"): then a whole run takes it where every PITCHED row's ratio lies within [1/4, 4]; a chunked run takes one rate
+    // for all rows, not a rate per row.
+    if ((h->rs.plan.on() || h->rows.on()) && !h->pitch_at_rate) return fail(h, VITS_E_ARG, "%s is not covered with an output rate set", entry);
+    if (chunked && h->rows.on()) return fail(h, VITS_E_ARG, "%s is not covered with an output rate set per row", entry);
+    for (int b = 0; b < B && (h->rs.plan.on() || h->rows.on()); b++) {
+        const ResampleDev *d = rate_of_row(h, b);
+        if (!d || warp_rate_ok(d->plan.L, d->plan.M)) continue;
+        const float *r0 = st0 ? st0 + (int64_t)b * T : nullptr, *r1 = st1 ? st1 + (int64_t)b * T : nullptr;
+        if (!warp_rate_unpitched(r0, r1 ? r1 : r0, (int)lens[b]))
+            return fail(h, VITS_E_ARG, "row %d: pitch at %d -> %d Hz is not covered: the ratio of the rates lies outside [1/4, 4]", b, d->plan.fi,
+                        d->plan.fo);
+    }
     if (!st0) {
         in.zeros.assign((size_t)B * T, 0.f);
         st0 = in.zeros.data();
@@ -3631,7 +3787,7 @@ static int run_call_locked(vits_handle *h, const RunCall &c) {
     if (int rc = host_fit(h, c.ctl, c.fit, c.B, rr)) return rc;
     Intoned in;
     if (c.entry)
-        if (int rc = host_intonation(h, c.ctl, c.lens, c.B, c.T, c.st0, c.st1, c.compensate, c.entry, in)) return rc;
+        if (int rc = host_intonation(h, c.ctl, c.lens, c.B, c.T, c.st0, c.st1, c.compensate, c.entry, c.out != RunCall::kAsync, in)) return rc;
     if (int rc = check_dev(h)) return rc;
     if (c.settings == RunCall::kScales) rr = one_row(c.scales);
     else if (c.settings == RunCall::kRows) {
@@ -3873,6 +4029,123 @@ int vits_glide_emit_end(const vits_glide_seg *segs, int n_segs, int64_t n_in, in
 int64_t vits_warp_stream_cap(int64_t piece_samples, int64_t S_w) {
     if (piece_samples < 1 || S_w < 1) return fail(nullptr, VITS_E_ARG, "bad stream cap arguments (%lld, %lld)", (long long)piece_samples, (long long)S_w);
     return warp_stream_cap(piece_samples, S_w);
+}
+
+// ---- the folded plan (vitsmi.h, "pitch at an output rate"), without a handle
+
+static int rate_ratio_fault(int64_t L, int64_t M) {
+    if (warp_rate_ok(L, M)) return VITS_OK;
+    return fail(nullptr, VITS_E_ARG, "rate ratio L / M = %lld / %lld outside [1/4, 4]", (long long)L, (long long)M);
+}
+
+int vits_warp_token_rate(float semitones, int64_t L, int64_t M, int64_t *step, int64_t *cutoff, int32_t *half_taps) {
+    if (int rc = rate_ratio_fault(L, M)) return rc;
+    int64_t s, c;
+    int32_t Kh;
+    if (!warp_token_rate(semitones, L, M, s, c, Kh))
+        return fail(nullptr, VITS_E_ARG, "semitones %g is not a finite value within [-12, 12]", (double)semitones);
+    if (step) *step = s;
+    if (cutoff) *cutoff = c;
+    if (half_taps) *half_taps = Kh;
+    return VITS_OK;
+}
+
+int vits_warp_plan_rate(const int64_t *durations, const float *semitones, int len, int hop, int64_t L, int64_t M, vits_warp_seg *segs,
+                        int64_t *spans, int64_t *n_out) {
+    if (len < 0 || hop < 1 || (len > 0 && !durations)) return fail(nullptr, VITS_E_ARG, "bad warp plan arguments (len = %d, hop = %d)", len, hop);
+    if (int rc = rate_ratio_fault(L, M)) return rc;
+    int64_t ns = 0, N = 0;
+    const std::string e = warp_plan_rate(durations, semitones, len, hop, L, M, segs, spans, ns, N);
+    if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
+    if (n_out) *n_out = N;
+    return (int)ns;
+}
+
+int vits_glide_plan_rate(const int64_t *durations, const float *st0, const float *st1, int len, int hop, int64_t L, int64_t M,
+                         vits_glide_seg *segs, int64_t *spans, int64_t *n_out) {
+    if (len < 0 || hop < 1 || (len > 0 && !durations)) return fail(nullptr, VITS_E_ARG, "bad glide plan arguments (len = %d, hop = %d)", len, hop);
+    if (int rc = rate_ratio_fault(L, M)) return rc;
+    int64_t ns = 0, N = 0;
+    const std::string e = glide_plan_rate(durations, st0, st1, len, hop, L, M, segs, spans, ns, N);
+    if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
+    if (n_out) *n_out = N;
+    return (int)ns;
+}
+
+int vits_glide_cutoff_rate(int64_t step, int64_t *c, int32_t *half_taps) {
+    if (step < kWarpRateMinStep || step > kWarpRateMaxStep)
+        return fail(nullptr, VITS_E_ARG, "step %lld outside [%lld, %lld]", (long long)step, (long long)kWarpRateMinStep, (long long)kWarpRateMaxStep);
+    int32_t c32, Kh;
+    glide_cutoff(step, c32, Kh);
+    if (c) *c = c32;
+    if (half_taps) *half_taps = Kh;
+    return VITS_OK;
+}
+
+int vits_glide_pos_rate(const vits_glide_seg *seg, int64_t j, int64_t *pos, int64_t *step) {
+    if (!seg || !pos) return fail(nullptr, VITS_E_ARG, "null argument");
+    vits_glide_seg g = *seg;
+    g.n0 = 0;
+    g.pos0 = 0;
+    const std::string e = glide_rate_segs_fault(&g, 1);
+    if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
+    if (j < 0 || j > g.k) return fail(nullptr, VITS_E_ARG, "sample %lld outside [0, %lld]", (long long)j, (long long)g.k);
+    *pos = glide_pos(seg->pos0, g.k, g.step0, g.step1, j);
+    if (step) *step = glide_step(g.k, g.step0, g.step1, j < g.k ? j : g.k);
+    return VITS_OK;
+}
+
+// the emit rule of a row of a folded plan and the cap, without a handle: half / min_step are the PLAN's largest Kh and least step
+extern "C++" {
+template <class Seg, class Fault>
+static int rate_emit_end_as(const Seg *segs, int n_segs, int64_t n_in, int64_t n_out, int64_t X, int half, int64_t *ready, Fault fault) {
+    if (n_segs < 1 || !segs || n_in < 0 || n_out < 0 || X < 0 || half < 1 || half > kWarpRateMaxHalf || !ready)
+        return fail(nullptr, VITS_E_ARG, "bad emit end arguments (n_segs = %d, n_in = %lld, n_out = %lld, X = %lld, half = %d)", n_segs,
+                    (long long)n_in, (long long)n_out, (long long)X, half);
+    const std::string e = fault(segs, n_segs);
+    if (!e.empty()) return fail(nullptr, VITS_E_ARG, "%s", e.c_str());
+    const int64_t N = segs[n_segs - 1].n0 + segs[n_segs - 1].k;
+    if (n_out != N) return fail(nullptr, VITS_E_ARG, "n_out = %lld, the row's records give %lld", (long long)n_out, (long long)N);
+    *ready = warp_emit_row(segs, n_segs, n_in, n_out, X, half);
+    return VITS_OK;
+}
+}  // extern "C++"
+
+int vits_warp_emit_end_rate(const vits_warp_seg *segs, int n_segs, int64_t n_in, int64_t n_out, int64_t X, int half, int64_t *ready) {
+    return rate_emit_end_as(segs, n_segs, n_in, n_out, X, half, ready, warp_rate_segs_fault);
+}
+
+int vits_glide_emit_end_rate(const vits_glide_seg *segs, int n_segs, int64_t n_in, int64_t n_out, int64_t X, int half, int64_t *ready) {
+    return rate_emit_end_as(segs, n_segs, n_in, n_out, X, half, ready, glide_rate_segs_fault);
+}
+
+int vits_identity_emit_end_rate(int64_t L, int64_t M, int64_t K, int64_t n_in, int64_t X, int64_t *ready) {
+    if (L < 1 || M < 1 || K < 0 || n_in < 0 || X < 0 || !ready)
+        return fail(nullptr, VITS_E_ARG, "bad emit end arguments (L = %lld, M = %lld, K = %lld, n_in = %lld, X = %lld)", (long long)L, (long long)M,
+                    (long long)K, (long long)n_in, (long long)X);
+    WarpRateRow r{};
+    r.L = L;
+    r.M = M;
+    r.K = (int32_t)K;
+    r.n_out = (int32_t)((n_in * L + M - 1) / M);
+    *ready = X >= n_in ? (int64_t)r.n_out : warp_rate_identity_ready(r, X);
+    return VITS_OK;
+}
+
+int64_t vits_warp_stream_cap_rate(int64_t piece_samples, int64_t S_w, int64_t min_step, int half) {
+    if (piece_samples < 1 || S_w < 1 || min_step < kWarpRateMinStep || min_step > kWarpRateMaxStep || half < 1 || half > kWarpRateMaxHalf)
+        return fail(nullptr, VITS_E_ARG, "bad stream cap arguments (%lld, %lld, %lld, %d)", (long long)piece_samples, (long long)S_w,
+                    (long long)min_step, half);
+    return warp_stream_cap(piece_samples, S_w, min_step, half);
+}
+
+int vits_rate_identity_spans(const int64_t *durations, int len, int hop, int64_t L, int64_t M, int64_t n_in, int64_t *spans, int64_t *n_out) {
+    if (len < 0 || hop < 1 || (len > 0 && !durations) || L < 1 || M < 1 || n_in < 0)
+        return fail(nullptr, VITS_E_ARG, "bad identity row arguments (len = %d, hop = %d, L = %lld, M = %lld, n_in = %lld)", len, hop, (long long)L,
+                    (long long)M, (long long)n_in);
+    const int64_t N = warp_rate_identity(durations, len, hop, L, M, n_in, spans);
+    if (n_out) *n_out = N;
+    return VITS_OK;
 }
 
 void vits_free_output(vits_handle *h, vits_output *out) {
@@ -5682,47 +5955,108 @@ int vits_test_glide(int device_id, const float *x, const int64_t *counts, int B,
     return test_warp_as(device_id, x, counts, B, S, segs, seg_first, y, S_w, glide_segs_fault, launch_glide);
 }
 
-// Streamed pitch by value: the input cut at piece_bounds (increasing piece ends, the last one S), every piece through the
-// pipeline's stage (warp_run_begin / _piece / _window) on the pipeline's walk; n_cap is warp_stream_cap of the longest piece.
+// The wide kernels ("pitch at an output rate") by value: the caller's records under the folded limits, a pair of rates per row
+// (in_rates[b] -> out_rates[b]; 0 or in_rates[b]: native), output samples [n_lo, n_hi) of every row through the pipeline's launch into y [B][n_hi - n_lo].
+// A row without a record is an identity row: ceil(n_b * L / M) samples by the resampler's rule.
 extern "C++" {
 namespace {
-template <class Seg, class Fault>
-int test_warp_pieces_as(int device_id, const float *x, const int64_t *counts, int B, int S, const Seg *segs, const int32_t *seg_first,
-                        const int64_t *piece_bounds, int n_pieces, float *y, int S_w, int64_t *ranges, int max_ranges, Fault fault,
-                        std::vector<Seg> WarpRun::*mine, bool glide) {
+template <class Seg, class Fault, class Launch>
+int test_warp_rate_as(int device_id, const float *x, const int64_t *counts, int B, int S, const Seg *segs, const int32_t *seg_first,
+                      const int32_t *in_rates, const int32_t *out_rates, int n_lo, int n_hi, float *y, Fault fault, Launch launch) {
     if (int rc = test_dev(device_id)) return rc;
-    if (!x || !y || !counts || !seg_first || !piece_bounds || B <= 0 || S <= 0 || S_w < 1 || n_pieces < 1)
+    if (!x || !y || !counts || !seg_first || !in_rates || !out_rates || B <= 0 || S <= 0 || n_lo < 0 || n_hi <= n_lo)
         return fail(nullptr, VITS_E_ARG, "bad warp test arguments");
     if (seg_first[0] != 0) return fail(nullptr, VITS_E_ARG, "seg_first[0] = %d, not 0", (int)seg_first[0]);
-    int64_t longest = 0;
-    for (int i = 0; i < n_pieces; i++) {
-        const int64_t lo = i ? piece_bounds[i - 1] : 0;
-        if (piece_bounds[i] <= lo || piece_bounds[i] > S) return fail(nullptr, VITS_E_ARG, "piece_bounds[%d] = %lld does not ascend within (0, %d]", i, (long long)piece_bounds[i], S);
-        longest = piece_bounds[i] - lo > longest ? piece_bounds[i] - lo : longest;
-    }
-    if (piece_bounds[n_pieces - 1] != S) return fail(nullptr, VITS_E_ARG, "the last piece ends at %lld, not at S = %d", (long long)piece_bounds[n_pieces - 1], S);
-    std::vector<int64_t> n_in((size_t)B);
+    std::vector<int64_t> n_in((size_t)B), L((size_t)B, 1), M((size_t)B, 1);
+    std::vector<ResamplePlan> plans((size_t)B);
     for (int b = 0; b < B; b++) {
         const int32_t ns = seg_first[b + 1] - seg_first[b];
         if (ns < 0 || (ns > 0 && !segs)) return fail(nullptr, VITS_E_ARG, "row %d: seg_first is not ascending", b);
         const std::string e = fault(segs + seg_first[b], ns);
         if (!e.empty()) return fail(nullptr, VITS_E_ARG, "row %d: %s", b, e.c_str());
         n_in[(size_t)b] = counts[b] < 0 ? 0 : (counts[b] > S ? S : counts[b]);
+        const int in_rate = in_rates[b];
+        if (out_rates[b] != 0 && out_rates[b] != in_rate) {
+            const std::string pe = resample_plan(in_rate, out_rates[b], plans[(size_t)b]);
+            if (!pe.empty()) return fail(nullptr, VITS_E_ARG, "row %d: %s", b, pe.c_str());
+            L[(size_t)b] = plans[(size_t)b].L;
+            M[(size_t)b] = plans[(size_t)b].M;
+            if (ns > 0 && !warp_rate_ok(L[(size_t)b], M[(size_t)b]))
+                return fail(nullptr, VITS_E_ARG, "row %d: pitch at %d -> %d Hz: the ratio of the rates lies outside [1/4, 4]", b, in_rate, (int)out_rates[b]);
+        }
     }
-    WarpRun run;
-    run.glide = glide;
-    const size_t n_segs = (size_t)seg_first[B];
-    (run.*mine).assign(segs, segs + n_segs);
-    run.first.assign(seg_first, seg_first + B + 1);
-    run.S_w = warp_rows(segs, seg_first, n_in.data(), B, run.rows);
-    if (S_w != run.S_w) return fail(nullptr, VITS_E_ARG, "S_w = %d, the rows give %lld", S_w, (long long)run.S_w);
-    const int64_t n_cap = warp_stream_cap(longest, run.S_w);
+    std::vector<WarpRateRow> rows;
+    const int64_t need = warp_rate_rows(segs, seg_first, n_in.data(), L.data(), M.data(), B, rows);
+    if (need > INT_MAX) return fail(nullptr, VITS_E_ARG, "the longest row has %lld output samples", (long long)need);
     std::vector<float> G(kWarpTable);
     warp_table(G.data());
     DevBufs D;
-    const float *dG = D.up(G.data(), G.size());
-    const float *dx = D.up(x, (size_t)B * S);
-    const auto walk = [&](Carver &cv) { return carve_warp_stream(cv, B, S, n_cap, (int64_t)n_segs); };
+    for (int b = 0; b < B; b++) {  // the table of every resampled row (rows at one rate share it)
+        if (!plans[(size_t)b].on()) continue;
+        WarpRateRow &r = rows[(size_t)b];
+        r.Kp = resample_pitch(plans[(size_t)b]);
+        r.K = (int32_t)plans[(size_t)b].K;
+        for (int q = 0; q < b && !r.table; q++)
+            if (out_rates[q] == out_rates[b] && in_rates[q] == in_rates[b]) r.table = rows[(size_t)q].table;
+        if (r.table) continue;
+        std::vector<float> t((size_t)r.L * r.Kp);
+        resample_table(plans[(size_t)b], t.data(), r.Kp);
+        r.table = D.up(t.data(), t.size());
+    }
+    const size_t n_segs = (size_t)seg_first[B];
+    const Seg none{};
+    WarpRateArgsT<Seg> a{};
+    a.segs = D.up(n_segs ? segs : &none, n_segs ? n_segs : 1);
+    a.rows = D.up(rows.data(), rows.size());
+    a.G = D.up(G.data(), G.size());
+    a.x = D.up(x, (size_t)B * S);
+    a.x_pitch = S;
+    const int64_t W = (int64_t)n_hi - n_lo;
+    float *dy = D.fill<float>((size_t)B * W, 0xff);
+    a.y = dy;
+    a.y_pitch = W;
+    a.n_lo = n_lo;
+    a.n_hi = n_hi;
+    TCHECK(D.err);
+    TCHECK(launch(a, B, nullptr));
+    TCHECK(hipDeviceSynchronize());
+    TCHECK(download(y, dy, (size_t)B * W));
+    return VITS_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int vits_test_warp_rate(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_warp_seg *segs, const int32_t *seg_first,
+                        const int32_t *in_rates, const int32_t *out_rates, int n_lo, int n_hi, float *y) {
+    return test_warp_rate_as(device_id, x, counts, B, S, segs, seg_first, in_rates, out_rates, n_lo, n_hi, y, warp_rate_segs_fault, launch_warp_rate);
+}
+
+int vits_test_glide_rate(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_glide_seg *segs, const int32_t *seg_first,
+                         const int32_t *in_rates, const int32_t *out_rates, int n_lo, int n_hi, float *y) {
+    return test_warp_rate_as(device_id, x, counts, B, S, segs, seg_first, in_rates, out_rates, n_lo, n_hi, y, glide_rate_segs_fault, launch_glide_rate);
+}
+
+// Streamed pitch by value: the input cut at piece_bounds (increasing piece ends, the last one S), every piece through the
+// pipeline's stage (warp_run_begin / _piece / _window) on the pipeline's walk; n_cap is warp_stream_cap of the longest piece.
+extern "C++" {
+namespace {
+// "" or what is wrong with the piece ends; longest: the longest piece
+int piece_bounds_check(const int64_t *piece_bounds, int n_pieces, int S, int64_t &longest) {
+    longest = 0;
+    for (int i = 0; i < n_pieces; i++) {
+        const int64_t lo = i ? piece_bounds[i - 1] : 0;
+        if (piece_bounds[i] <= lo || piece_bounds[i] > S) return fail(nullptr, VITS_E_ARG, "piece_bounds[%d] = %lld does not ascend within (0, %d]", i, (long long)piece_bounds[i], S);
+        longest = piece_bounds[i] - lo > longest ? piece_bounds[i] - lo : longest;
+    }
+    if (piece_bounds[n_pieces - 1] != S) return fail(nullptr, VITS_E_ARG, "the last piece ends at %lld, not at S = %d", (long long)piece_bounds[n_pieces - 1], S);
+    return 0;
+}
+
+// The planned run through the pipeline's stage on the pipeline's walk of a poisoned buffer: every piece of dx [B][S] joins the
+// history, every window it completes is copied into y [B][S_w].  Returns the number of windows.
+int walk_warp_pieces(WarpRun &run, DevBufs &D, const float *dG, const float *dx, int B, int S, size_t n_segs, int64_t n_cap,
+                     const int64_t *piece_bounds, int n_pieces, float *y, int S_w, int64_t *ranges, int max_ranges) {
+    const auto walk = [&](Carver &cv) { return carve_warp_stream(cv, B, S, n_cap, (int64_t)n_segs, run.row_bytes()); };
     const size_t bytes = carved_bytes(walk);
     Carver cv(D.fill<unsigned char>(bytes, 0xff), bytes);  // (poisoned: what a window must not read is NaN)
     TCHECK(D.err);
@@ -5754,6 +6088,40 @@ int test_warp_pieces_as(int device_id, const float *x, const int64_t *counts, in
     TCHECK(hipDeviceSynchronize());
     return calls;
 }
+
+template <class Seg, class Fault>
+int test_warp_pieces_as(int device_id, const float *x, const int64_t *counts, int B, int S, const Seg *segs, const int32_t *seg_first,
+                        const int64_t *piece_bounds, int n_pieces, float *y, int S_w, int64_t *ranges, int max_ranges, Fault fault,
+                        std::vector<Seg> WarpRun::*mine, bool glide) {
+    if (int rc = test_dev(device_id)) return rc;
+    if (!x || !y || !counts || !seg_first || !piece_bounds || B <= 0 || S <= 0 || S_w < 1 || n_pieces < 1)
+        return fail(nullptr, VITS_E_ARG, "bad warp test arguments");
+    if (seg_first[0] != 0) return fail(nullptr, VITS_E_ARG, "seg_first[0] = %d, not 0", (int)seg_first[0]);
+    int64_t longest = 0;
+    if (int rc = piece_bounds_check(piece_bounds, n_pieces, S, longest)) return rc;
+    std::vector<int64_t> n_in((size_t)B);
+    for (int b = 0; b < B; b++) {
+        const int32_t ns = seg_first[b + 1] - seg_first[b];
+        if (ns < 0 || (ns > 0 && !segs)) return fail(nullptr, VITS_E_ARG, "row %d: seg_first is not ascending", b);
+        const std::string e = fault(segs + seg_first[b], ns);
+        if (!e.empty()) return fail(nullptr, VITS_E_ARG, "row %d: %s", b, e.c_str());
+        n_in[(size_t)b] = counts[b] < 0 ? 0 : (counts[b] > S ? S : counts[b]);
+    }
+    WarpRun run;
+    run.glide = glide;
+    const size_t n_segs = (size_t)seg_first[B];
+    (run.*mine).assign(segs, segs + n_segs);
+    run.first.assign(seg_first, seg_first + B + 1);
+    run.S_w = warp_rows(segs, seg_first, n_in.data(), B, run.rows);
+    if (S_w != run.S_w) return fail(nullptr, VITS_E_ARG, "S_w = %d, the rows give %lld", S_w, (long long)run.S_w);
+    const int64_t n_cap = warp_stream_cap(longest, run.S_w);
+    std::vector<float> G(kWarpTable);
+    warp_table(G.data());
+    DevBufs D;
+    const float *dG = D.up(G.data(), G.size());
+    const float *dx = D.up(x, (size_t)B * S);
+    return walk_warp_pieces(run, D, dG, dx, B, S, n_segs, n_cap, piece_bounds, n_pieces, y, S_w, ranges, max_ranges);
+}
 }  // namespace
 }  // extern "C++"
 
@@ -5767,6 +6135,81 @@ int vits_test_glide_pieces(int device_id, const float *x, const int64_t *counts,
                            const int64_t *piece_bounds, int n_pieces, float *y, int S_w, int64_t *ranges, int max_ranges) {
     return test_warp_pieces_as(device_id, x, counts, B, S, segs, seg_first, piece_bounds, n_pieces, y, S_w, ranges, max_ranges, glide_segs_fault,
                                &WarpRun::gsegs, true);
+}
+
+// The wide streamed stage by value ("pitch at an output rate"): vits_test_warp_pieces' walk over a folded plan at ONE pair of rates -
+// what a chunked run has -, n_cap = warp_stream_cap(longest piece, S_w, the plan's least step, its largest Kh).
+extern "C++" {
+namespace {
+template <class Seg, class Fault>
+int test_warp_rate_pieces_as(int device_id, const float *x, const int64_t *counts, int B, int S, const Seg *segs, const int32_t *seg_first,
+                             int in_rate, int out_rate, const int64_t *piece_bounds, int n_pieces, float *y, int S_w, int64_t *ranges,
+                             int max_ranges, Fault fault, std::vector<Seg> WarpRun::*mine, bool glide) {
+    if (int rc = test_dev(device_id)) return rc;
+    if (!x || !y || !counts || !seg_first || !piece_bounds || B <= 0 || S <= 0 || S_w < 1 || n_pieces < 1)
+        return fail(nullptr, VITS_E_ARG, "bad warp test arguments");
+    if (seg_first[0] != 0) return fail(nullptr, VITS_E_ARG, "seg_first[0] = %d, not 0", (int)seg_first[0]);
+    int64_t longest = 0;
+    if (int rc = piece_bounds_check(piece_bounds, n_pieces, S, longest)) return rc;
+    ResamplePlan plan;
+    if (out_rate != 0 && out_rate != in_rate) {
+        const std::string pe = resample_plan(in_rate, out_rate, plan);
+        if (!pe.empty()) return fail(nullptr, VITS_E_ARG, "%s", pe.c_str());
+        if (seg_first[B] > 0 && !warp_rate_ok(plan.L, plan.M))
+            return fail(nullptr, VITS_E_ARG, "pitch at %d -> %d Hz: the ratio of the rates lies outside [1/4, 4]", in_rate, out_rate);
+    }
+    std::vector<int64_t> n_in((size_t)B), L((size_t)B, plan.L), M((size_t)B, plan.M);
+    for (int b = 0; b < B; b++) {
+        const int32_t ns = seg_first[b + 1] - seg_first[b];
+        if (ns < 0 || (ns > 0 && !segs)) return fail(nullptr, VITS_E_ARG, "row %d: seg_first is not ascending", b);
+        const std::string e = fault(segs + seg_first[b], ns);
+        if (!e.empty()) return fail(nullptr, VITS_E_ARG, "row %d: %s", b, e.c_str());
+        n_in[(size_t)b] = counts[b] < 0 ? 0 : (counts[b] > S ? S : counts[b]);
+    }
+    WarpRun run;
+    run.glide = glide;
+    run.folded = true;
+    const size_t n_segs = (size_t)seg_first[B];
+    (run.*mine).assign(segs, segs + n_segs);
+    run.first.assign(seg_first, seg_first + B + 1);
+    run.S_w = warp_rate_rows(segs, seg_first, n_in.data(), L.data(), M.data(), B, run.rrows);
+    if (S_w != run.S_w) return fail(nullptr, VITS_E_ARG, "S_w = %d, the rows give %lld", S_w, (long long)run.S_w);
+    int64_t min_step = kWarpMinStep;
+    warp_rate_plan_extent((run.*mine).data(), run.rrows, run.half, min_step);
+    const int64_t n_cap = warp_stream_cap(longest, run.S_w, min_step, run.half);
+    std::vector<float> G(kWarpTable);
+    warp_table(G.data());
+    DevBufs D;
+    if (plan.on()) {
+        const int Kp = resample_pitch(plan);
+        std::vector<float> t((size_t)plan.L * Kp);
+        resample_table(plan, t.data(), Kp);
+        const float *dt = D.up(t.data(), t.size());
+        for (WarpRateRow &r : run.rrows) {
+            r.table = dt;
+            r.Kp = Kp;
+            r.K = (int32_t)plan.K;
+        }
+    }
+    const float *dG = D.up(G.data(), G.size());
+    const float *dx = D.up(x, (size_t)B * S);
+    return walk_warp_pieces(run, D, dG, dx, B, S, n_segs, n_cap, piece_bounds, n_pieces, y, S_w, ranges, max_ranges);
+}
+}  // namespace
+}  // extern "C++"
+
+int vits_test_warp_rate_pieces(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_warp_seg *segs,
+                               const int32_t *seg_first, int in_rate, int out_rate, const int64_t *piece_bounds, int n_pieces, float *y, int S_w,
+                               int64_t *ranges, int max_ranges) {
+    return test_warp_rate_pieces_as(device_id, x, counts, B, S, segs, seg_first, in_rate, out_rate, piece_bounds, n_pieces, y, S_w, ranges,
+                                    max_ranges, warp_rate_segs_fault, &WarpRun::wsegs, false);
+}
+
+int vits_test_glide_rate_pieces(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_glide_seg *segs,
+                                const int32_t *seg_first, int in_rate, int out_rate, const int64_t *piece_bounds, int n_pieces, float *y, int S_w,
+                                int64_t *ranges, int max_ranges) {
+    return test_warp_rate_pieces_as(device_id, x, counts, B, S, segs, seg_first, in_rate, out_rate, piece_bounds, n_pieces, y, S_w, ranges,
+                                    max_ranges, glide_rate_segs_fault, &WarpRun::gsegs, true);
 }
 
 // The rows entry by value: the plans of the distinct rates among out_rates (0 or in_rate: a native row), one record per row,

@@ -16,6 +16,7 @@
 
 #include <cstdint>
 
+#include "resample.hip.hpp"
 #include "warp.hpp"
 
 namespace vitsmi {
@@ -186,6 +187,123 @@ inline hipError_t launch_glide(const GlideArgs &a, int B, hipStream_t st) {
     if (B <= 0 || a.n_hi <= a.n_lo || a.n_lo < 0) return hipSuccess;
     const dim3 grid((unsigned)(((int64_t)a.n_hi - a.n_lo + kWarpBlock - 1) / kWarpBlock), (unsigned)B);
     glide_kernel<<<grid, kWarpBlock, 0, st>>>(a);
+    return hipGetLastError();
+}
+
+// ---- pitch at an output rate (include/vitsmi.h, "pitch at an output rate"): the two kernels' wide siblings.
+//
+// The rate is folded into the records' steps (warp.hpp), so positions advance by up to eight input samples an output and a
+// sample has up to 2 * 151 taps: a tile stages at most 255 * 8 + 2 + 2 * 151 floats, sized statically - 9.4 KB beside the
+// 32 KB of G.  What it stages on either side of its positions is the ROW's largest Kh (WarpRateRow::half_max), not the
+// family's: a row delivered upwards has some 19 half-taps, and staging 151 for it would read eight times what it uses.
+// Geometry, the two searches, the walk to a lane's segment, the per-lane fence and warp_sample are the kernels' above.
+//
+// An identity row - every token at 0 semitones - is not rendered by its records but by the resampler's rule, so that it is
+// resample_kernel's / resample_rows_kernel's row bit for bit: resample_sample over the row's table line h[p], t = n * M,
+// i = t / L, p = t - i * L, the masked native row read straight from memory (the function gives the same bits on every input
+// path: resample.hip.hpp).  Without a table (L == M) it is the masked copy.  That branch, like the zeros behind a row's end,
+// returns in front of the barrier: whether a workgroup takes it depends on blockIdx and values indexed by it alone.
+constexpr int kWarpRateSpan = (kWarpBlock - 1) * 8 + 2 + 2 * kWarpRateMaxHalf;  // 2344
+
+template <class Seg>
+struct WarpRateArgsT {
+    const Seg *segs;
+    const WarpRateRow *rows;  // [B]: the row's records, counts, largest Kh and its resampler plan (table, Kp, K, L, M)
+    const float *G;           // [kWarpTable]
+    const float *x;           // native input samples of row b at x + b * x_pitch
+    int64_t x_pitch;
+    float *y;                 // [B][y_pitch]: row b's output sample n_lo at y + b * y_pitch
+    int64_t y_pitch;
+    int n_hi, n_lo;           // the launch renders output samples [n_lo, n_hi) of every row, as WarpArgsT
+};
+using WarpRateArgs = WarpRateArgsT<vits_warp_seg>;
+using GlideRateArgs = WarpRateArgsT<vits_glide_seg>;
+
+// position, cutoff and half-taps of sample j of a record, by the closed forms of its family
+__device__ __forceinline__ int64_t warp_rate_at(const vits_warp_seg &g, int64_t j, int32_t &c, int32_t &Kh) {
+    c = g.c;
+    Kh = g.half_taps;
+    return g.pos0 + j * (int64_t)g.step;
+}
+__device__ __forceinline__ int64_t warp_rate_at(const vits_glide_seg &g, int64_t j, int32_t &c, int32_t &Kh) {
+    glide_cutoff(glide_step(g.k, g.step0, g.step1, j), c, Kh);
+    return glide_pos(g.pos0, g.k, g.step0, g.step1, j);
+}
+
+template <class Seg>
+__device__ __forceinline__ void warp_rate_tile(const WarpRateArgsT<Seg> &a) {
+    __shared__ float xs[kWarpRateSpan];
+    __shared__ float gs[kWarpTable];
+    const int b = blockIdx.y;
+    const WarpRateRow r = a.rows[b];
+    const int64_t n0 = a.n_lo + (int64_t)blockIdx.x * kWarpBlock, n = n0 + threadIdx.x;
+    const float *xrow = a.x + (int64_t)b * a.x_pitch;
+    float *yrow = a.y + (int64_t)b * a.y_pitch - a.n_lo;  // indexed by n
+    if (n0 >= r.n_out || r.identity || r.n_segs <= 0) {  // behind the row's end: zeros; an identity row: the resampler's sample
+        if (n >= a.n_hi) return;
+        float v = 0.f;
+        if (r.identity && n < r.n_out) {
+            if (!r.table) v = n < r.n_in ? xrow[n] : 0.f;
+            else {
+                const int64_t t = n * r.M, i = t / r.L, p = t - i * r.L;
+                const int64_t m0 = i - r.K / 2 + 1;
+                const int n_in = r.n_in;
+                v = resample_sample(r.table + p * r.Kp, r.K, [&](int j) {
+                    const int64_t m = m0 + j;
+                    return m >= 0 && m < n_in ? xrow[m] : 0.f;
+                });
+            }
+        }
+        yrow[n] = v;
+        return;
+    }
+    const Seg *sg = a.segs + r.seg0;
+    // the tile's last sample: clipped by the row and by the window, so that nothing behind the window's last position is staged
+    const int64_t n_end = n0 + kWarpBlock < a.n_hi ? n0 + kWarpBlock : (int64_t)a.n_hi;
+    const int64_t n_last = (n_end < r.n_out ? n_end : (int64_t)r.n_out) - 1;
+    const int j0 = warp_find(sg, r.n_segs, n0), j1 = warp_find(sg, r.n_segs, n_last);
+    int32_t c, Kh;
+    const int64_t i_lo = warp_rate_at(sg[j0], n0 - sg[j0].n0, c, Kh) >> kWarpFB;
+    const int64_t i_hi = warp_rate_at(sg[j1], n_last - sg[j1].n0, c, Kh) >> kWarpFB;
+    const int64_t m_base = i_lo - r.half_max + 1;
+    int64_t len = i_hi - i_lo + 2 * (int64_t)r.half_max;
+    len = len > kWarpRateSpan ? kWarpRateSpan : len;  // (never: positions advance by at most eight samples an output, half_max <= 151)
+    for (int q = threadIdx.x; q < (int)len; q += kWarpBlock) {
+        const int64_t m = m_base + q;
+        xs[q] = m >= 0 && m < r.n_in ? xrow[m] : 0.f;
+    }
+    for (int q = threadIdx.x; q < kWarpTable; q += kWarpBlock) gs[q] = a.G[q];
+    __syncthreads();
+    if (n >= a.n_hi) return;
+    float v = 0.f;
+    if (n < r.n_out) {
+        int j = j0;
+        while (j < j1 && sg[j + 1].n0 <= n) j++;
+        const Seg g = sg[j];
+        const int64_t pos = warp_rate_at(g, n - g.n0, c, Kh);
+        const int64_t at = (pos >> kWarpFB) - m_base;  // the tap m = i0 in the staged span
+        // the fence of warp_kernel: a record whose Kh exceeds the row's half_max, or a clipped span, renders 0 and reads nothing outside
+        if (at - Kh + 1 >= 0 && at + Kh < len) {
+            const float *w = xs + at;
+            v = warp_sample(gs, pos, c, Kh, [&](int d) { return w[d]; });
+        }
+    }
+    yrow[n] = v;
+}
+
+__global__ void __launch_bounds__(kWarpBlock) warp_rate_kernel(WarpRateArgs a) { warp_rate_tile(a); }
+__global__ void __launch_bounds__(kWarpBlock) glide_rate_kernel(GlideRateArgs a) { warp_rate_tile(a); }
+
+inline hipError_t launch_warp_rate(const WarpRateArgs &a, int B, hipStream_t st) {
+    if (B <= 0 || a.n_hi <= a.n_lo || a.n_lo < 0) return hipSuccess;
+    const dim3 grid((unsigned)(((int64_t)a.n_hi - a.n_lo + kWarpBlock - 1) / kWarpBlock), (unsigned)B);
+    warp_rate_kernel<<<grid, kWarpBlock, 0, st>>>(a);
+    return hipGetLastError();
+}
+inline hipError_t launch_glide_rate(const GlideRateArgs &a, int B, hipStream_t st) {
+    if (B <= 0 || a.n_hi <= a.n_lo || a.n_lo < 0) return hipSuccess;
+    const dim3 grid((unsigned)(((int64_t)a.n_hi - a.n_lo + kWarpBlock - 1) / kWarpBlock), (unsigned)B);
+    glide_rate_kernel<<<grid, kWarpBlock, 0, st>>>(a);
     return hipGetLastError();
 }
 

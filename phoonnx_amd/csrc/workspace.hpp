@@ -370,18 +370,19 @@ inline ResampleBufs carve_resample(Carver &cv, int B, int S_out, int K) {
 struct WarpBufs {
     ResampleBufs front;
     vits_warp_seg *segs;
-    WarpRow *rows;
+    void *rows;  // [B] WarpRow records, or - a folded launch - WarpRateRow ones (row_bytes each)
     size_t plan_bytes;  // segs | rows
 };
 
-inline WarpBufs carve_warp(Carver &cv, int B, int S_w, int64_t n_segs) {
+// (row_bytes: the size of a row's record - a folded launch's rows are WarpRateRow)
+inline WarpBufs carve_warp(Carver &cv, int B, int S_w, int64_t n_segs, size_t row_bytes = sizeof(WarpRow)) {
     WarpBufs w{};
     w.front = carve_resample(cv, B, S_w, 0);
-    w.plan_bytes = (size_t)n_segs * sizeof(vits_warp_seg) + (size_t)B * sizeof(WarpRow);
+    w.plan_bytes = (size_t)n_segs * sizeof(vits_warp_seg) + (size_t)B * row_bytes;
     char *p = cv.take<char>(w.plan_bytes);
     if (p) {
         w.segs = reinterpret_cast<vits_warp_seg *>(p);
-        w.rows = reinterpret_cast<WarpRow *>(p + (size_t)n_segs * sizeof(vits_warp_seg));
+        w.rows = p + (size_t)n_segs * sizeof(vits_warp_seg);
     }
     return w;
 }
@@ -396,21 +397,21 @@ struct WarpStreamBufs {
     float *out;
     int *n_out;
     vits_warp_seg *segs;
-    WarpRow *rows;
+    void *rows;  // [B] WarpRow records, or - a folded launch - WarpRateRow ones (row_bytes each)
     size_t plan_bytes;  // segs | rows
 };
 
-inline WarpStreamBufs carve_warp_stream(Carver &cv, int B, int64_t row_in, int64_t n_cap, int64_t n_segs) {
+inline WarpStreamBufs carve_warp_stream(Carver &cv, int B, int64_t row_in, int64_t n_cap, int64_t n_segs, size_t row_bytes = sizeof(WarpRow)) {
     WarpStreamBufs w{};
     w.hist_pitch = row_in;
     w.hist = cv.take<float>((size_t)B * row_in);
     w.out = cv.take<float>((size_t)B * n_cap);
     w.n_out = cv.take<int>(B);
-    w.plan_bytes = (size_t)n_segs * sizeof(vits_warp_seg) + (size_t)B * sizeof(WarpRow);
+    w.plan_bytes = (size_t)n_segs * sizeof(vits_warp_seg) + (size_t)B * row_bytes;
     char *p = cv.take<char>(w.plan_bytes);
     if (p) {
         w.segs = reinterpret_cast<vits_warp_seg *>(p);
-        w.rows = reinterpret_cast<WarpRow *>(p + (size_t)n_segs * sizeof(vits_warp_seg));
+        w.rows = p + (size_t)n_segs * sizeof(vits_warp_seg);
     }
     return w;
 }

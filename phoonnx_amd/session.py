@@ -974,7 +974,8 @@ class MiSession:
     def __init__(self, path_or_bytes, sess_options=None, providers=None, provider_options=None, device_id: int = 0,
                  arena_device_ptr: Optional[int] = None, arena_bytes: int = 0, host_only: bool = False,
                  gen_precision: Optional[str] = None, range_fallback: bool = True, layout_only: bool = False,
-                 pinned_results: bool = True, tails: Optional[str] = None, output_rate: Optional[int] = None, **kwargs):
+                 pinned_results: bool = True, tails: Optional[str] = None, output_rate: Optional[int] = None,
+                 pitch_at_rate: bool = False, **kwargs):
         """tails: what a padded batch (B > 1, unequal frame counts) holds behind each utterance's end - None (VITSMI_TAILS or
         the default "zero"), "zero" (those samples are not rendered at all and read 0.0; every valid sample is bit-identical to
         the padded rendering), "reference" (the exported graph's own padded rendering: its generator is not masked,
@@ -986,6 +987,9 @@ class MiSession:
         with "bf16x6" and repeat the call (never silently clamped audio).
         output_rate: None (the voice's own rate) or the sample rate in Hz every result is delivered at, resampled on the device
         (set_output_rate; vitsmi.h, "output rate").
+        pitch_at_rate: True makes the pitched calls (token_semitones= / token_semitones_end=) take an output rate or per-row
+        rates - the rate is folded into the warp's step on the device (set_pitch_at_rate; vitsmi.h, "pitch at an output rate");
+        False, the default, keeps their refusal "not covered with an output rate set".
         pinned_results: run() / synthesize_batch() return arrays that VIEW page-locked host memory (the DMA engine's
         target; recycled when the array is garbage-collected).  An application that keeps many results alive thereby pins
         that much host RAM: pass False to get ordinary pageable arrays (one extra host copy per call).
@@ -1015,6 +1019,7 @@ class MiSession:
         self.output_rate = None if output_rate is None else int(output_rate)
         self.input_rate = None   # (None: the file's sample_rate metadata)
         self.output_rates = None  # (set_output_rates: a rate per row, in the place of output_rate)
+        self.pitch_at_rate = bool(pitch_at_rate)
         self._seed = 0
         self.range_fallbacks = 0  # times this session reopened itself with bf16x6 after a RangeError (stats())
         self._open(gen_precision)
@@ -1036,6 +1041,8 @@ class MiSession:
         self.gen_precision = gen_precision
         if self.tails is not None:
             self._lib.vits_set_tails(self._h, 1 if self.tails == "reference" else 0)
+        if self.pitch_at_rate:  # (a reopened session keeps it)
+            self._lib.vits_set_pitch_at_rate(self._h, 1)
         if self.output_rate is not None:
             rc = self._lib.vits_set_output_rate(self._h, self.input_rate or 0, self.output_rate)
             if rc != 0:
@@ -1407,7 +1414,9 @@ class MiSession:
         token_semitones, compensate, token_semitones_end - as synthesize_batch (vitsmi.h, "streamed pitch"): the chunks, joined,
         are that run's warped "output"; their ranges lie on the warped timeline and follow what the rows' plans have completed -
         a chunk of the run may deliver nothing, or several ranges -, total_samples is the longest warped row, and
-        last_sample_counts() / last_token_spans() answer from the first chunk on.  Not covered with an output rate set.
+        last_sample_counts() / last_token_spans() answer from the first chunk on.  Not covered with an output rate set, unless
+        the session was opened with pitch_at_rate (set_pitch_at_rate): then one rate is folded into the warp (vitsmi.h, "pitch at
+        an output rate") and the chunks are that run's at the rate; a rate per row stays refused.
         fit - as synthesize_batch (vitsmi.h, "fitted durations"): the chunks, joined, are the fitted run's "output"; last_fit()
         answers from the first chunk on.  Not together with durations or token_semitones (ValueError)."""
         ids, lens, scales, seeds, sid, noise, ctl, on_top, _, _ = self._stream_arguments(
@@ -1547,8 +1556,16 @@ class MiSession:
         unwarped stream, which refuses nothing)"""
         if not _pitched(semitones, semitones_end, lens):
             return
-        if self.resampling or self.output_rates is not None:
+        if (self.resampling or self.output_rates is not None) and not self.pitch_at_rate:
             raise SessionError(f"{name}(token_semitones=...) is not covered with an output rate set")
+        if self.output_rates is not None:  # (one output rate is folded into the warp: vitsmi.h, "pitch at an output rate")
+            raise SessionError(f"{name}(token_semitones=...) is not covered with an output rate set per row")
+        if self.resampling:
+            fi = self.input_rate or int(self.meta("sample_rate") or 22050)
+            L, M = resample_plan(fi, self.output_rate)[:2]
+            if M > 4 * L or L > 4 * M:
+                raise SessionError(f"{name}(token_semitones=...): pitch at {fi} -> {self.output_rate} Hz is not covered: the ratio of the "
+                                   "rates lies outside [1/4, 4]")
         if compensate and durations is not None:
             raise SessionError("compensate and forced durations are contradictory: forced durations are the rendered ones")
 
@@ -1587,9 +1604,9 @@ class MiSession:
                 d = np.ctypeslib.as_array(dur, shape=(Bc * Tc,)).reshape(Bc, Tc)
                 n = np.ctypeslib.as_array(counts, shape=(Bc,))
                 if pitched:  # the boundaries are the warp's: the host plan over THIS run's durations (counts are its N_b)
-                    plans = [warp_plan(d[b, :lens[b]], semitones[b, :lens[b]], hop) if semitones_end is None else
-                             glide_plan(d[b, :lens[b]], semitones[b, :lens[b]], semitones_end[b, :lens[b]], hop) for b in range(Bc)]
-                    bounds = [token_span_bounds(plans[b][1], n[b]) for b in range(Bc)]
+                    bounds = [token_span_bounds(_pitched_spans(d[b, :lens[b]], semitones[b, :lens[b]],
+                                                               None if semitones_end is None else semitones_end[b, :lens[b]], hop, ratio),
+                                                  n[b]) for b in range(Bc)]
                 else:
                     bounds = [token_bounds(d[b], lens[b], hop, n[b], ratio) for b in range(Bc)]
                 used = token_gain_shapes([Segment(b) for b in range(Bc)], base, tgains, bounds, ramp)
@@ -1678,6 +1695,16 @@ class MiSession:
             self.output_rate = None if rate is None else int(rate)
             self.input_rate = None if input_rate is None else int(input_rate)
             self.output_rates = None  # (a handle rate, or none, replaces a rate per row)
+
+    def set_pitch_at_rate(self, on: bool = True):
+        """Whether the pitched calls take an output rate or per-row rates (vits_set_pitch_at_rate; vitsmi.h, "pitch at an output
+        rate"): on, the rate is folded into the warp's step - one filter pass, token spans in delivered samples -; off, the
+        default, they are refused with "not covered with an output rate set"."""
+        with self._locked():
+            rc = self._lib.vits_set_pitch_at_rate(self._h, 1 if on else 0)
+            if rc != 0:
+                self._raise("vits_set_pitch_at_rate", rc)
+            self.pitch_at_rate = bool(on)
 
     def set_output_rates(self, rates, input_rate: Optional[int] = None):
         """Deliver row b of the following runs at rates[b] Hz (vitsmi.h, "output rate per row"): one entry per row of the
@@ -3124,6 +3151,189 @@ def test_glide(x, counts, row_segs, device_id=0):
     if rc != 0:
         raise SessionError(f"vits_test_glide failed [{rc}]: {_ffi.last_error(None)}")
     return y
+
+
+def _pitched_spans(durations, st0, st1, hop, ratio):
+    """the token spans of one row of a pitched run, in delivered samples: the plan without a rate, or - ratio (L, M) - the folded
+    one, whose unpitched rows follow the resampler's rule over the row's n_b = y_len * hop valid samples, y_len = max(sum of the
+    durations, 1) as the engine counts it"""
+    if ratio is None:
+        return warp_plan(durations, st0, hop)[1] if st1 is None else glide_plan(durations, st0, st1, hop)[1]
+    L, M = ratio
+    if not np.any(st0) and (st1 is None or not np.any(st1)):
+        return rate_identity_spans(durations, hop, L, M, max(int(np.sum(durations)), 1) * hop)[0]
+    return warp_plan_rate(durations, st0, hop, L, M)[1] if st1 is None else glide_plan_rate(durations, st0, st1, hop, L, M)[1]
+
+
+def warp_token_rate(semitones, L, M):
+    """(step, c, half_taps) of a token at `semitones` delivered at fi * L / M (vits_warp_token_rate: pure host code)"""
+    step, c, Kh = C.c_int64(), C.c_int64(), C.c_int32()
+    rc = _ffi.load().vits_warp_token_rate(float(semitones), int(L), int(M), C.byref(step), C.byref(c), C.byref(Kh))
+    if rc != 0:
+        raise SessionError(f"vits_warp_token_rate failed [{rc}]: {_ffi.last_error(None)}")
+    return step.value, c.value, Kh.value
+
+
+def warp_plan_rate(durations, semitones, hop, L, M):
+    """warp_plan with the output rate fi * L / M folded into the steps (vits_warp_plan_rate: pure host code): n0, k and N are
+    delivered samples."""
+    D = np.ascontiguousarray(durations, np.int64)
+    st = None if semitones is None else np.ascontiguousarray(semitones, np.float32)
+    if D.ndim != 1 or (st is not None and st.shape != D.shape):
+        raise SessionError(f"durations must be [T] and semitones [T] or None, got {D.shape} / {None if st is None else st.shape}")
+    segs = (_ffi.VitsWarpSeg * max(len(D), 1))()
+    spans = np.zeros(len(D), np.int64)
+    n = C.c_int64()
+    count = _ffi.load().vits_warp_plan_rate(_ffi.ptr(D), _ffi.ptr(st), len(D), int(hop), int(L), int(M), segs, _ffi.ptr(spans), C.byref(n))
+    if count < 0:
+        raise SessionError(f"vits_warp_plan_rate failed [{count}]: {_ffi.last_error(None)}")
+    return (_ffi.VitsWarpSeg * count)(*segs[:count]), spans, n.value
+
+
+def glide_plan_rate(durations, st0, st1, hop, L, M):
+    """glide_plan with the output rate fi * L / M folded into the steps (vits_glide_plan_rate: pure host code)"""
+    D = np.ascontiguousarray(durations, np.int64)
+    a = None if st0 is None else np.ascontiguousarray(st0, np.float32)
+    b = None if st1 is None else np.ascontiguousarray(st1, np.float32)
+    if D.ndim != 1 or any(v is not None and v.shape != D.shape for v in (a, b)):
+        raise SessionError(f"durations must be [T] and st0 / st1 [T] or None, got {D.shape}")
+    segs = (_ffi.VitsGlideSeg * max(len(D), 1))()
+    spans = np.zeros(len(D), np.int64)
+    n = C.c_int64()
+    count = _ffi.load().vits_glide_plan_rate(_ffi.ptr(D), _ffi.ptr(a), _ffi.ptr(b), len(D), int(hop), int(L), int(M), segs, _ffi.ptr(spans),
+                                             C.byref(n))
+    if count < 0:
+        raise SessionError(f"vits_glide_plan_rate failed [{count}]: {_ffi.last_error(None)}")
+    return (_ffi.VitsGlideSeg * count)(*segs[:count]), spans, n.value
+
+
+def glide_cutoff_rate(step):
+    """glide_cutoff over the steps a folded plan admits, [ONE / 8, 8 ONE] (vits_glide_cutoff_rate: pure host code)"""
+    c, Kh = C.c_int64(), C.c_int32()
+    rc = _ffi.load().vits_glide_cutoff_rate(int(step), C.byref(c), C.byref(Kh))
+    if rc != 0:
+        raise SessionError(f"vits_glide_cutoff_rate failed [{rc}]: {_ffi.last_error(None)}")
+    return c.value, Kh.value
+
+
+def rate_identity_spans(durations, hop, L, M, n_in):
+    """(spans int64 [T], N) of an identity row - every token at 0 semitones - delivered at fi * L / M: the resampler's rule
+    (vits_rate_identity_spans: pure host code)"""
+    D = np.ascontiguousarray(durations, np.int64)
+    spans = np.zeros(len(D), np.int64)
+    n = C.c_int64()
+    rc = _ffi.load().vits_rate_identity_spans(_ffi.ptr(D), len(D), int(hop), int(L), int(M), int(n_in), _ffi.ptr(spans), C.byref(n))
+    if rc != 0:
+        raise SessionError(f"vits_rate_identity_spans failed [{rc}]: {_ffi.last_error(None)}")
+    return spans, n.value
+
+
+def _test_rate(fn, seg_type, x, counts, row_segs, in_rates, out_rates, window, device_id):
+    x = np.ascontiguousarray(x, np.float32)
+    counts = np.ascontiguousarray(counts, np.int64)
+    B = len(counts)
+    fis = np.full(B, int(in_rates), np.int32) if np.ndim(in_rates) == 0 else np.ascontiguousarray(in_rates, np.int32)
+    fos = np.asarray([int(r or 0) for r in out_rates], np.int32)
+    if x.ndim != 2 or counts.shape != (x.shape[0],) or len(row_segs) != B or fis.shape != counts.shape or fos.shape != counts.shape:
+        raise SessionError(f"x must be [B, S], counts, in_rates and out_rates [B] and row_segs B sequences, got {x.shape} / {counts.shape} / "
+                           f"{fis.shape} / {fos.shape} / {len(row_segs)}")
+    S = x.shape[1]
+    flat = [g for row in row_segs for g in row]
+    first = np.cumsum([0] + [len(row) for row in row_segs]).astype(np.int32)
+    segs = (seg_type * max(len(flat), 1))(*flat)
+    n_out = []
+    for b, row in enumerate(row_segs):
+        if len(row):
+            n_out.append(int(row[-1].n0 + row[-1].k))
+        else:  # an identity row: ceil(n_b * L / M)
+            n = int(min(max(counts[b], 0), S))
+            fi, fo = int(fis[b]), int(fos[b]) or int(fis[b])
+            g = int(np.gcd(fi, fo))
+            n_out.append(-(-n * (fo // g) // (fi // g)))
+    n_lo, n_hi = window if window is not None else (0, max(1, max(n_out)))
+    y = np.full((B, n_hi - n_lo), np.nan, np.float32)
+    rc = getattr(_ffi.load(), fn)(device_id, _ffi.ptr(x), _ffi.ptr(counts), B, S, segs, _ffi.ptr(first), _ffi.ptr(fis), _ffi.ptr(fos),
+                                  int(n_lo), int(n_hi), _ffi.ptr(y))
+    if rc != 0:
+        raise SessionError(f"{fn} failed [{rc}]: {_ffi.last_error(None)}")
+    return y, np.asarray(n_out, np.int64)
+
+
+def test_warp_rate(x, counts, row_segs, in_rates, out_rates, window=None, device_id=0):
+    """The wide warp by value (vits_test_warp_rate; vitsmi.h, "pitch at an output rate"): x float32 [B, S], counts [B], row_segs -
+    per row the _ffi.VitsWarpSeg records of warp_plan_rate at the row's rates, none for an identity row -, in_rates one rate or
+    [B], out_rates [B] (None, 0 or the row's in_rate: native).  window (n_lo, n_hi): the output samples rendered; None: [0, max(1, max_b N_b)).
+    -> (y float32 [B, n_hi - n_lo], N int64 [B])."""
+    return _test_rate("vits_test_warp_rate", _ffi.VitsWarpSeg, x, counts, row_segs, in_rates, out_rates, window, device_id)
+
+
+def test_glide_rate(x, counts, row_segs, in_rates, out_rates, window=None, device_id=0):
+    """test_warp_rate over rows of _ffi.VitsGlideSeg (glide_plan_rate's)"""
+    return _test_rate("vits_test_glide_rate", _ffi.VitsGlideSeg, x, counts, row_segs, in_rates, out_rates, window, device_id)
+
+
+def warp_emit_end_rate(segs, n_in, n_out, X, half):
+    """warp_emit_end / glide_emit_end over the records of a folded plan whose largest Kh is `half` (vits_warp_emit_end_rate /
+    vits_glide_emit_end_rate: pure host code)"""
+    fn = "vits_glide_emit_end_rate" if isinstance(segs[0], _ffi.VitsGlideSeg) else "vits_warp_emit_end_rate"
+    ready = C.c_int64()
+    rc = getattr(_ffi.load(), fn)(segs, len(segs), int(n_in), int(n_out), int(X), int(half), C.byref(ready))
+    if rc != 0:
+        raise SessionError(f"{fn} failed [{rc}]: {_ffi.last_error(None)}")
+    return ready.value
+
+
+def identity_emit_end_rate(L, M, K, n_in, X):
+    """the emit rule of an identity row of a folded plan: the resampler's (vits_identity_emit_end_rate: pure host code)"""
+    ready = C.c_int64()
+    rc = _ffi.load().vits_identity_emit_end_rate(int(L), int(M), int(K), int(n_in), int(X), C.byref(ready))
+    if rc != 0:
+        raise SessionError(f"vits_identity_emit_end_rate failed [{rc}]: {_ffi.last_error(None)}")
+    return ready.value
+
+
+def warp_stream_cap_rate(piece_samples, S_w, min_step, half):
+    """n_cap of a streamed run with a folded plan: its least step and largest Kh (vits_warp_stream_cap_rate)"""
+    cap = _ffi.load().vits_warp_stream_cap_rate(int(piece_samples), int(S_w), int(min_step), int(half))
+    if cap < 0:
+        raise SessionError(f"vits_warp_stream_cap_rate failed [{cap}]: {_ffi.last_error(None)}")
+    return int(cap)
+
+
+def _test_rate_pieces(fn, seg_type, x, counts, row_segs, in_rate, out_rate, piece_bounds, device_id):
+    x = np.ascontiguousarray(x, np.float32)
+    counts = np.ascontiguousarray(counts, np.int64)
+    bounds = np.ascontiguousarray(piece_bounds, np.int64)
+    if x.ndim != 2 or counts.shape != (x.shape[0],) or len(row_segs) != x.shape[0] or bounds.ndim != 1 or not len(bounds):
+        raise SessionError(f"x must be [B, S], counts [B], row_segs B sequences and piece_bounds [P], got {x.shape} / {counts.shape} / "
+                           f"{len(row_segs)} / {bounds.shape}")
+    B, S = x.shape
+    flat = [g for row in row_segs for g in row]
+    first = np.cumsum([0] + [len(row) for row in row_segs]).astype(np.int32)
+    segs = (seg_type * max(len(flat), 1))(*flat)
+    fo = int(out_rate or in_rate)
+    g = int(np.gcd(int(in_rate), fo))
+    L, M = fo // g, int(in_rate) // g
+    n_out = [int(row[-1].n0 + row[-1].k) if len(row) else -(-int(min(max(counts[b], 0), S)) * L // M) for b, row in enumerate(row_segs)]
+    S_w = max(1, max(n_out))
+    y = np.full((B, S_w), np.nan, np.float32)
+    cap = len(bounds) + S_w + 2  # (more windows than any schedule has)
+    ranges = np.zeros((cap, 2), np.int64)
+    rc = getattr(_ffi.load(), fn)(device_id, _ffi.ptr(x), _ffi.ptr(counts), B, S, segs, _ffi.ptr(first), int(in_rate), fo, _ffi.ptr(bounds),
+                                  len(bounds), _ffi.ptr(y), S_w, _ffi.ptr(ranges), cap)
+    if rc < 0:
+        raise SessionError(f"{fn} failed [{rc}]: {_ffi.last_error(None)}")
+    return y, ranges[:rc]
+
+
+def test_warp_rate_pieces(x, counts, row_segs, in_rate, out_rate, piece_bounds, device_id=0):
+    """The wide streamed stage by value (vits_test_warp_rate_pieces): test_warp_pieces over a folded plan at one pair of rates"""
+    return _test_rate_pieces("vits_test_warp_rate_pieces", _ffi.VitsWarpSeg, x, counts, row_segs, in_rate, out_rate, piece_bounds, device_id)
+
+
+def test_glide_rate_pieces(x, counts, row_segs, in_rate, out_rate, piece_bounds, device_id=0):
+    """test_warp_rate_pieces over rows of _ffi.VitsGlideSeg (glide_plan_rate's)"""
+    return _test_rate_pieces("vits_test_glide_rate_pieces", _ffi.VitsGlideSeg, x, counts, row_segs, in_rate, out_rate, piece_bounds, device_id)
 
 
 def _emit_end(fn, segs, n_in, n_out, X):

@@ -204,8 +204,16 @@ class TTSVoice:
     dedupe_sentences: bool = False  # False = reference behaviour (every sentence list is doubled)
     # extension: deliver audio at this rate instead of config.sample_rate, resampled on the device by the session
     output_sample_rate: Optional[int] = None
+    # extension: phoneme_pitch / pitch_contour together with an output rate - the session folds the rate into the warp on the
+    # device (MiSession.set_pitch_at_rate).  False: they are refused with an output rate set, as they always were.
+    pitch_at_rate: bool = False
 
     def __post_init__(self):
+        if self.pitch_at_rate:
+            if not hasattr(self.session, "set_pitch_at_rate"):
+                raise ValueError("pitch_at_rate needs a session that folds an output rate into the warp on the device "
+                                 f"(MiSession.set_pitch_at_rate); {type(self.session).__name__} has none")
+            self.session.set_pitch_at_rate(True)
         if self.output_sample_rate is not None:
             if not hasattr(self.session, "set_output_rate"):
                 raise ValueError("output_sample_rate needs a session that resamples on the device (MiSession.set_output_rate); "
@@ -221,13 +229,14 @@ class TTSVoice:
              phonemes_txt: Optional[str] = None, phoneme_map: Optional[str] = None, lang_code: Optional[str] = None,
              phoneme_type_str: Optional[str] = None, use_cuda: bool = False, device_id: int = 0,
              phonemizer: Optional[Any] = None, strict: bool = True, output_sample_rate: Optional[int] = None,
-             session: Optional[Any] = None) -> "TTSVoice":
+             session: Optional[Any] = None, pitch_at_rate: bool = False) -> "TTSVoice":
         """Load a voice: `<model>.onnx` + `<model>.onnx.json` (voice.py:125-172).  `use_cuda` is
         accepted for signature compatibility; the engine always runs on the MI355X `device_id`.
         strict (extension): raise ValueError when JSON, .onnx metadata and graph disagree (check_consistency).
         output_sample_rate (extension): deliver every chunk, WAV header included, at this rate: the session resamples on the
         device from config.sample_rate (MiSession.set_output_rate); ValueError with a session that cannot.
-        session (extension): an already opened session to use instead of opening `model_path`."""
+        session (extension): an already opened session to use instead of opening `model_path`.
+        pitch_at_rate (extension): phoneme_pitch / pitch_contour take an output rate (MiSession.set_pitch_at_rate)."""
         import os
         from .session import MiSession
         if config_path is None:
@@ -255,7 +264,8 @@ class TTSVoice:
                 raise
         config = VoiceConfig.from_dict(config_dict, phonemes_txt=phonemes_txt, lang_code=lang_code,
                                        phoneme_type_str=phoneme_type_str)
-        return TTSVoice(session=session, config=config, phonemizer=phonemizer, output_sample_rate=output_sample_rate)
+        return TTSVoice(session=session, config=config, phonemizer=phonemizer, output_sample_rate=output_sample_rate,
+                        pitch_at_rate=pitch_at_rate)
 
     @property
     def sample_rate(self) -> int:
@@ -643,26 +653,41 @@ class TTSVoice:
         return st0, st1
 
     def _contour_check(self, pitch_contour, rates=None) -> None:
-        """pitch_contour needs a session whose delivery takes end values, and audio at the voice's own rate"""
+        """pitch_contour needs a session whose delivery takes end values, and audio at the voice's own rate - or a voice with
+        pitch_at_rate: the output rate is then folded into the glide on the device (vitsmi.h, "pitch at an output rate"; the
+        engine refuses a rate outside a quarter .. four times the voice's own)"""
         import inspect
         if pitch_contour is None:
             return
         fn = getattr(self.session, "synthesize_delivered", None)
         if fn is None or "token_semitones_end" not in inspect.signature(fn).parameters:
             raise ValueError("pitch_contour needs a session that glides on the device (synthesize_delivered(token_semitones_end=))")
-        if self._ratio() is not None or any(self._ratio(r) is not None for r in rates or ()):
+        if not self.pitch_at_rate and (self._ratio() is not None or any(self._ratio(r) is not None for r in rates or ())):
             raise ValueError("pitch_contour is not covered with an output rate set")
+        if self.pitch_at_rate:
+            self._rate_admitted("pitch_contour", rates)
+
+    def _rate_admitted(self, what: str, rates=None) -> None:
+        """with pitch_at_rate: the rates pitch can be folded into lie within a quarter .. four times the voice's own"""
+        for r in [None] + list(rates or ()):
+            lm = self._ratio(r)
+            if lm is not None and (lm[1] > 4 * lm[0] or lm[0] > 4 * lm[1]):
+                raise ValueError(f"{what} is not covered at {self.sample_rate if r is None else int(r)} Hz: the ratio to the voice's "
+                                 f"{int(self.config.sample_rate)} Hz lies outside [1/4, 4]")
 
     def _pitch_check(self, phoneme_pitch, rates=None) -> None:
-        """phoneme_pitch needs a session whose delivery takes semitones, and audio at the voice's own rate"""
+        """phoneme_pitch needs a session whose delivery takes semitones, and audio at the voice's own rate - or a voice with
+        pitch_at_rate, as for pitch_contour"""
         import inspect
         if phoneme_pitch is None:
             return
         fn = getattr(self.session, "synthesize_delivered", None)
         if fn is None or "token_semitones" not in inspect.signature(fn).parameters:
             raise ValueError("phoneme_pitch needs a session that warps on the device (synthesize_delivered(token_semitones=))")
-        if self._ratio() is not None or any(self._ratio(r) is not None for r in rates or ()):
+        if not self.pitch_at_rate and (self._ratio() is not None or any(self._ratio(r) is not None for r in rates or ())):
             raise ValueError("phoneme_pitch is not covered with an output rate set")
+        if self.pitch_at_rate:
+            self._rate_admitted("phoneme_pitch", rates)
 
     def _duration_fit(self, duration, duration_mode: str, n_sentences: int, pauses: int, entry: str, pitched: bool):
         """duration= / duration_mode= of the encoded entries -> a session.Fit with all sentences in one group, or None.
@@ -775,7 +800,10 @@ class TTSVoice:
         (vitsmi.h, "intonation": the resampling shift - formants move along; good for a few semitones).  The tempo is kept.
         Alignments then come from the warp's token spans, and every sample-valued option - fades, per-phoneme volume, trims,
         look-ahead - is laid out over the warped audio.  It needs a session that warps (ValueError otherwise) and a voice
-        without an output_sample_rate (ValueError "not covered with an output rate set").
+        without an output_sample_rate (ValueError "not covered with an output rate set") - unless the voice was made with
+        pitch_at_rate=True: an output_sample_rate (or output_sample_rates per request) is then folded into the warp on the device (vitsmi.h,
+        "pitch at an output rate"): one filter pass, spans and alignments in delivered samples; a rate outside a quarter .. four
+        times the voice's own is refused by the engine for a pitched sentence.
         pitch_contour - SSML's contour, applied to each sentence: a sequence of (position in [0, 1], semitones within
         [-12, 12]) points with non-decreasing positions, or a callable (sentence_index, tokens) -> such a sequence.  The pitch
         GLIDES through the points (vitsmi.h, "pitch contours"): linear in semitones between them, the first and the last
@@ -783,7 +811,7 @@ class TTSVoice:
         exist before the run: with n phoneme groups, group i glides from the contour's value at i / n to its value at
         (i + 1) / n.  phoneme_pitch, if given too, is added to both ends; a sum outside [-12, 12] is a ValueError naming the
         sentence.  Tempo, alignments and sample-valued options as for phoneme_pitch.  It needs a session that glides
-        (ValueError otherwise) and is refused with an output rate set as phoneme_pitch is.
+        (ValueError otherwise) and is refused with an output rate set, or takes it, as phoneme_pitch does.
         duration - SSML's <prosody duration>, in seconds: the text is FITTED to that length on the device (vitsmi.h, "fitted
         durations": all sentences form one group and share one multiplier on the model's own durations, so the speech is what
         the model renders at another length scale).  duration_mode "exact" meets it - to within half a frame, plus one sample
@@ -939,7 +967,7 @@ class TTSVoice:
         "streamed pitch"): the sentences are warped and glided piece by piece on the device - joined, still
         synthesize_encoded's bytes.  They need a session whose synthesize_stream_encoded takes token_semitones /
         token_semitones_end (ValueError otherwise: such a session's chunked entries have no warped form) and are refused with
-        an output rate set.
+        an output rate set unless the voice has pitch_at_rate, as in synthesize_encoded.
         duration / duration_mode have the meanings and refusals of synthesize_encoded (vitsmi.h, "fitted durations"): the
         duration is that of the rendered audio with its pauses, before trim_silence - joined, still synthesize_encoded's bytes.
         They need a session whose synthesize_stream_encoded takes fit= (ValueError otherwise)."""
@@ -951,14 +979,18 @@ class TTSVoice:
             if "token_semitones_end" not in takes:
                 raise ValueError("pitch_contour is not covered by stream_encoded: the chunked entries have no warped form "
                                  "(synthesize_encoded takes it)")
-            if self._ratio() is not None:
+            if self._ratio() is not None and not self.pitch_at_rate:
                 raise ValueError("pitch_contour is not covered with an output rate set")
+            if self.pitch_at_rate:
+                self._rate_admitted("pitch_contour")
         if phoneme_pitch is not None:
             if "token_semitones" not in takes:
                 raise ValueError("phoneme_pitch is not covered by stream_encoded: the chunked entries have no warped form "
                                  "(synthesize_encoded takes it)")
-            if self._ratio() is not None:
+            if self._ratio() is not None and not self.pitch_at_rate:
                 raise ValueError("phoneme_pitch is not covered with an output rate set")
+            if self.pitch_at_rate:
+                self._rate_admitted("phoneme_pitch")
         cfg = syn_config if syn_config is not None else SynthesisConfig()
         ae._check(encoding)
         lead = self._lead_samples(sentence_silence)

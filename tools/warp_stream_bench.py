@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """What pitch costs a stream (vitsmi.h, "streamed pitch"), on bench.py's voice:
     python tools/warp_stream_bench.py [--preset high] [--batch 32] [--tokens 256] [--chunk-frames 64] [--warmup 2]
-                                      [--repeats 3] [--runs 6] [--only plain|warp2|glide04]
+                                      [--repeats 3] [--runs 6] [--only plain|warp2|glide04] [--output-rate HZ]
 One handle, fixed seeds, fp32 chunks through MiSession.synthesize_stream; the consumer only takes the time of every chunk.
 The kinds alternate inside every repeat (the machine is shared: a drift hits all of them alike):
   plain     the unwarped stream (vits_run_chunked_ctl)
@@ -10,6 +10,8 @@ The kinds alternate inside every repeat (the machine is shared: a drift hits all
 Per kind and repeat: the mean ms from the call to the first delivered chunk, and the mean ms per run.  --only times one kind
 alone: the windowed launches' own times come from a kernel trace of such a run
 (rocprofv3 --kernel-trace --stats -- python tools/warp_stream_bench.py --only warp2).
+--output-rate sets the session's output rate: plain is then the resampled stream, warp2 / glide04 the folded ones (vitsmi.h,
+"pitch at an output rate": windowed warp_rate_kernel / glide_rate_kernel launches, no resampler stage).
 Prints one JSON line."""
 import argparse
 import json
@@ -33,6 +35,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--runs", type=int, default=6)
     ap.add_argument("--only", choices=["plain", "warp2", "glide04"], default=None)
+    ap.add_argument("--output-rate", type=int, default=None)
     a = ap.parse_args()
     from bench import LENGTH_SCALE, voice_cache
     from phoonnx_amd import MiSession
@@ -44,7 +47,9 @@ def main():
         os.makedirs(cache, exist_ok=True)
         write_voice(path + ".tmp", a.preset, seed=1234)
         os.replace(path + ".tmp", path)
-    s = MiSession(path)
+    s = MiSession(path, pitch_at_rate=True)
+    if a.output_rate:
+        s.set_output_rate(a.output_rate)
     rng = np.random.default_rng(2024)
     ids = rng.integers(1, s.hparam("n_vocab"), (B, T)).astype(np.int64)
     lens = np.full(B, T, np.int64)
@@ -72,7 +77,7 @@ def main():
         return first * 1e3, (time.perf_counter() - t0) * 1e3, n_chunks, int(samples)
 
     out = {"tool": "warp_stream_bench", "preset": a.preset, "batch": B, "tokens": T, "chunk_frames": a.chunk_frames,
-           "runs_per_repeat": a.runs, "first_chunk_ms": {k: [] for k in kinds}, "ms_per_run": {k: [] for k in kinds},
+           "output_rate": a.output_rate, "runs_per_repeat": a.runs, "first_chunk_ms": {k: [] for k in kinds}, "ms_per_run": {k: [] for k in kinds},
            "chunks": {}, "total_samples": {}, "launches": {}}
     for k, kw in kinds.items():
         for _ in range(a.warmup):
