@@ -24,17 +24,25 @@ from onnx_walk import OnnxModel  # noqa: E402
 from vits_oracle import resolve_weights  # noqa: E402  (pure-Python graph walk; no C involved)
 
 
-def _seq_mask(lens, T):
-    return (torch.arange(T)[None, :] < lens[:, None]).to(torch.float32)[:, None, :]  # commons.py:109-113
+def _seq_mask(lens, T, dtype=torch.float32):
+    return (torch.arange(T)[None, :] < lens[:, None]).to(dtype)[:, None, :]  # commons.py:109-113
 
 
 class TorchVits:
-    def __init__(self, onnx_path, threads=None):
+    def __init__(self, onnx_path, threads=None, dtype=torch.float32):
+        """dtype=torch.float64 evaluates the same graph in double precision (the fp32 weights and inputs convert exactly;
+        masks, noise and every returned tap are float64): the high-precision reference of tests/fullwidth_ref.py.  The
+        process-wide default dtype is never touched."""
         if threads:
             torch.set_num_threads(int(threads))
+        if dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"dtype must be torch.float32 or torch.float64 (got {dtype!r})")
+        self.dtype = dtype
         model = OnnxModel(onnx_path)
         tensors, self.ints = resolve_weights(model)
         self.t = {k: torch.from_numpy(np.array(v, dtype=np.float32, copy=True)) for k, v in tensors.items()}
+        if dtype != torch.float32:
+            self.t = {k: v.to(dtype) for k, v in self.t.items()}
         t = self.t
         self.H = t["enc_p.emb.weight"].shape[1]
         self.C = t["enc_p.proj.weight"].shape[0] // 2
@@ -53,6 +61,10 @@ class TorchVits:
         self.hop = 1
         for i in range(self.n_ups):
             self.hop *= self.ints[f"dec.ups.{i}.stride"]
+
+    def _in(self, a):
+        """a float32 input in this object's dtype (float32: the tensor itself, as before the float64 mode existed)"""
+        return a if self.dtype == torch.float32 else a.to(self.dtype)
 
     # ------------------------------------------------------------------ primitives
     def conv(self, name, x, dil=None, pad=None):
@@ -80,21 +92,22 @@ class TorchVits:
         idx = torch.arange(T)
         d = idx[None, :] - idx[:, None]                                            # j - i
         near = (d.abs() <= w)
-        scores = scores + torch.where(near, rel.gather(3, (d.clamp(-w, w) + w).expand(B, h, T, T)), torch.zeros(()))
+        scores = scores + torch.where(near, rel.gather(3, (d.clamp(-w, w) + w).expand(B, h, T, T)),
+                                     torch.zeros((), dtype=self.dtype))
         am = (mask.unsqueeze(2) * mask.unsqueeze(-1))                              # [B,1,T,T]
         scores = scores.masked_fill(am == 0, -1e4)
         p = torch.softmax(scores, dim=-1)
         out = p @ v
         # relative values: out_i += sum_{|j-i|<=w} p[i,j] E_v[j-i+w]
-        pw = torch.zeros(B, h, T, 2 * w + 1)
-        pw.scatter_add_(3, (d.clamp(-w, w) + w).expand(B, h, T, T), torch.where(near, p, torch.zeros(())))
+        pw = torch.zeros(B, h, T, 2 * w + 1, dtype=self.dtype)
+        pw.scatter_add_(3, (d.clamp(-w, w) + w).expand(B, h, T, T), torch.where(near, p, torch.zeros((), dtype=self.dtype)))
         out = out + pw @ ev
         out = out.transpose(2, 3).reshape(B, H, T)
         return self.conv(pfx + ".conv_o", out)
 
     def text_encoder(self, ids, lens):
         T = ids.shape[1]
-        mask = _seq_mask(lens, T)
+        mask = _seq_mask(lens, T, self.dtype)
         x = (self.t["enc_p.emb.weight"][ids] * math.sqrt(self.H)).transpose(1, 2) * mask   # models.py:199-203
         for l in range(self.n_layers):
             x = self.ln(f"enc_p.encoder.norm_layers_1.{l}", x + self.mha(f"enc_p.encoder.attn_layers.{l}", x, mask))
@@ -215,7 +228,7 @@ class TorchVits:
         return z
 
     # ------------------------------------------------------------------ A8 generator
-    def generator(self, z, g):  # models.py:348-368
+    def generator(self, z, g):  # models.py:348-368; z and g in this object's dtype
         x = self.conv("dec.conv_pre", z)
         if g is not None:
             x = x + self.conv("dec.cond", g)
@@ -255,24 +268,25 @@ class TorchVits:
                 raise RuntimeError("Missing speaker id")
             g = self.t["emb_g.weight"][torch.as_tensor(np.asarray(sid, np.int64))].unsqueeze(-1)
         if self.use_sdp:
-            ndp = torch.zeros(B, 2, T) if noise_dp is None else torch.as_tensor(np.asarray(noise_dp, np.float32))
+            ndp = torch.zeros(B, 2, T, dtype=self.dtype) if noise_dp is None else \
+                self._in(torch.as_tensor(np.asarray(noise_dp, np.float32)))
             logw = self.sdp_reverse(x, mask, g, ndp, noise_w)
         else:
             logw = self.dp_plain(x, mask, g)
         w_ceil = torch.ceil(torch.exp(logw) * mask * length_scale)
         y_len = torch.clamp_min(w_ceil.sum((1, 2)), 1).long()
         Fm = int(y_len.max())
-        y_mask = _seq_mask(y_len, Fm)
+        y_mask = _seq_mask(y_len, Fm, self.dtype)
         cum = torch.cumsum(w_ceil[:, 0], 1)                                   # [B,T]
-        f = torch.arange(Fm, dtype=torch.float32)
+        f = torch.arange(Fm, dtype=self.dtype)
         tok = (f[None, :, None] >= cum[:, None, :]).sum(-1).clamp(max=T - 1)  # frame -> token (commons.py:116-129)
         valid = y_mask * mask.gather(2, tok[:, None, :])
         m_e = m_p.gather(2, tok[:, None, :].expand(B, self.C, Fm)) * valid
         l_e = logs_p.gather(2, tok[:, None, :].expand(B, self.C, Fm)) * valid
         if noise_z is None:
-            eps = torch.zeros(B, self.C, Fm)
+            eps = torch.zeros(B, self.C, Fm, dtype=self.dtype)
         else:
-            eps = torch.as_tensor(np.asarray(noise_z, np.float32))[:, :, :Fm]
+            eps = self._in(torch.as_tensor(np.asarray(noise_z, np.float32))[:, :, :Fm])
         z_p = m_e + eps * torch.exp(l_e) * noise_scale
         z = self.flow_reverse(z_p, y_mask, g)
         o = self.generator(z * y_mask, g)
