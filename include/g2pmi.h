@@ -88,6 +88,28 @@ int g2p_test_linear(int device, int njobs, const float *const *W, const int *out
 int g2p_test_step(int device, int NB, int njobs, const float *const *W, const float *const *W2, const int *out, int in,
                   const float *x, const float *g, int act, float eps, float post, const float *const *res, float *const *y);
 
+/* Test hook: one launch of the attention kernel, as the engine launches it, on host buffers.  Query / output element
+ * (channel ch of heads * dk, column c of cols) at ch * q_cs + c * q_ts; q and out hold (heads * dk - 1) * q_cs + (cols - 1) * q_ts
+ * + 1 floats, and out comes back with everything the kernel does not write unchanged.  Column c is query i = c % seg of
+ * sequence b = c / seg, at position i + q_off; its keys / values (kv_n floats each) start b * kv_bs floats into k / v, channel
+ * stride kp, and number lens[b] (lens NULL: Tk), of which a causal launch takes those at positions <= i + q_off.
+ * score_j = q . k_j + bias[lut[j - (i + q_off) + max_positions - 1]][head]: bias [num_buckets][heads], lut 2 * max_positions - 1
+ * buckets, both NULL for no bias.  Refused: Tk outside [1, max_positions), lens outside [1, Tk], cols not whole sequences,
+ * a lut index or a bucket outside its table, q / out strides that make two elements one, k / v too short. */
+int g2p_test_attention(int device, const float *q, float *out, int q_cs, int q_ts, const float *k, const float *v, int64_t kv_n,
+                       int kp, int64_t kv_bs, const float *bias, int num_buckets, const int *lut, int heads, int dk, int cols, int seg,
+                       const int *lens, int Tk, int q_off, int causal);
+
+/* Test hook: the RMS-norm kernel.  y[c][t] = x[c][t] * rsqrt(mean_c(x[.][t]^2) + eps) * g[c] for t < T; x [C][xpitch], y [C][ypitch]
+ * (in and out: columns T .. ypitch - 1 come back unchanged). */
+int g2p_test_rmsnorm(int device, const float *x, const float *g, float *y, int C, int T, int xpitch, int ypitch, float eps);
+
+/* Test hook: the argmax kernel for NB sequences.  Logit v of sequence b at logits[b * lb + v * pitch + t] (the wide step:
+ * pitch NB, lb 1; the narrow one: pitch 1, lb V); the first maximum goes to ids[b * ib + slot] and to the same place of host_copy
+ * (both [NB][ib], in and out). */
+int g2p_test_argmax(int device, const float *logits, int V, int pitch, int t, int64_t lb, int NB, int64_t *ids, int64_t *host_copy,
+                    int64_t ib, int slot);
+
 #ifdef __cplusplus
 }
 #endif

@@ -237,7 +237,8 @@ EXPORTS = [
 
 
 G2P_EXPORTS = ["g2p_open", "g2p_close", "g2p_last_error", "g2p_hparam", "g2p_num_outputs", "g2p_output_name", "g2p_bucket",
-               "g2p_run", "g2p_generate", "g2p_generate_batch", "g2p_test_forced_steps", "g2p_test_linear", "g2p_test_step"]
+               "g2p_run", "g2p_generate", "g2p_generate_batch", "g2p_test_forced_steps", "g2p_test_linear", "g2p_test_step",
+               "g2p_test_attention", "g2p_test_rmsnorm", "g2p_test_argmax"]
 
 
 def lib_path():
@@ -485,6 +486,10 @@ def load():
     lib.g2p_test_forced_steps.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, vp]
     lib.g2p_test_linear.argtypes = [C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int64, C.c_int64, C.c_int, vp]
     lib.g2p_test_step.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, C.c_int, C.c_float, C.c_float, vp, vp]
+    lib.g2p_test_attention.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int64, C.c_int, C.c_int64, vp, C.c_int, vp,
+                                       C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int]
+    lib.g2p_test_rmsnorm.argtypes = [C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float]
+    lib.g2p_test_argmax.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, vp, vp, C.c_int64, C.c_int]
     _LIB = lib
     return lib
 

@@ -631,7 +631,9 @@ __global__ void g2p_scale_kernel(float *x, int64_t n, float s) {
 
 // argmax over the vocabulary (first maximum, as np.argmax), one workgroup per sequence b = blockIdx.x:
 // logits element v of sequence b at b * lb + v * pitch + t  ->  ids[b * ib + slot] (int64) and, if given, the same
-// place of the pinned host copy
+// place of the pinned host copy.  -0.0 and +0.0 are equal (the lower index wins).  A NaN compares with nothing and is
+// passed over: a row with some NaNs yields the first maximum among its other entries, a row of nothing but NaNs yields 0
+// (an id inside [0, V) whatever the logits hold; np.argmax returns 0 for a constant row too).
 __device__ __forceinline__ void g2p_argmax_body(const float *logits, int V, int pitch, int t, int64_t lb, int64_t *ids, int64_t ib,
                                                 int slot, int64_t *host_copy, int b, float *bv, int *bi) {
     const int tid = threadIdx.x;
@@ -656,8 +658,9 @@ __device__ __forceinline__ void g2p_argmax_body(const float *logits, int V, int 
         __syncthreads();
     }
     if (tid == 0) {
-        ids[(int64_t)b * ib + slot] = bi[0];
-        if (host_copy) host_copy[(int64_t)b * ib + slot] = bi[0];  // (pinned, mapped: visible once the step's event has fired)
+        const int64_t id = bi[0] < V ? bi[0] : 0;  // (no entry compared - every one NaN: 0, as for any constant row)
+        ids[(int64_t)b * ib + slot] = id;
+        if (host_copy) host_copy[(int64_t)b * ib + slot] = id;  // (pinned, mapped: visible once the step's event has fired)
     }
 }
 __global__ __launch_bounds__(256) void g2p_argmax_kernel(const float *logits, int V, int pitch, int t, int64_t lb, int64_t *ids,
@@ -1542,6 +1545,94 @@ int g2p_test_step(int device, int NB, int njobs, const float *const *W, const fl
     for (int j = 0; j < njobs && e == hipSuccess; j++)
         e = download(y[j], a.job[j].y, (size_t)NB * out[j]);
     if (e != hipSuccess) return gfail(nullptr, VITS_E_DEVICE, "g2p_test_step failed: %s", hipGetErrorString(e));
+    return VITS_OK;
+}
+
+// g2p_attention_kernel as attention() launches it: grid (cols, heads), 256 threads, (Tk + dk) floats of LDS, lut_zero = kMaxPos - 1.
+// Everything the kernel takes on trust from the engine is checked here, so that no argument can make it read or write
+// outside the buffers given.
+int g2p_test_attention(int device, const float *q, float *out, int q_cs, int q_ts, const float *k, const float *v, int64_t kv_n,
+                       int kp, int64_t kv_bs, const float *bias, int num_buckets, const int *lut, int heads, int dk, int cols, int seg,
+                       const int *lens, int Tk, int q_off, int causal) {
+    constexpr int KM = G2PModel::kMaxPos;
+    if (!q || !out || !k || !v || heads < 1 || heads > 64 || dk < 1 || dk > 1024 || cols < 1 || cols > (1 << 16) || seg < 1 ||
+        (causal != 0 && causal != 1) || q_off < 0 || q_off >= KM || kv_bs < 0 || kv_n < 1 || kv_n > ((int64_t)1 << 28))
+        return gfail(nullptr, VITS_E_ARG, "bad g2p_test_attention arguments");
+    if (Tk < 1 || Tk >= KM) return gfail(nullptr, VITS_E_ARG, "g2p_test_attention: Tk %d not in [1, %d)", Tk, KM);
+    if (cols % seg != 0) return gfail(nullptr, VITS_E_ARG, "g2p_test_attention: %d columns are not whole sequences of %d", cols, seg);
+    if ((bias == nullptr) != (lut == nullptr)) return gfail(nullptr, VITS_E_ARG, "g2p_test_attention: bias and lut go together");
+    const int nseq = cols / seg;
+    if (lens)
+        for (int b = 0; b < nseq; b++)
+            if (lens[b] < 1 || lens[b] > Tk) return gfail(nullptr, VITS_E_ARG, "g2p_test_attention: lens[%d]=%d not in [1, %d]", b, lens[b], Tk);
+    if (lut) {
+        // index j - (i + q_off) + kMaxPos - 1 for j in [0, Tk), i in [0, seg): its smallest value must not be negative (its
+        // largest, Tk - 1 - q_off + kMaxPos - 1, is inside the table for every Tk < kMaxPos)
+        if (q_off + seg > KM) return gfail(nullptr, VITS_E_ARG, "g2p_test_attention: q_off %d + seg %d leaves the bucket table", q_off, seg);
+        if (num_buckets < 1 || num_buckets > (1 << 16)) return gfail(nullptr, VITS_E_ARG, "g2p_test_attention: num_buckets");
+        for (int i = 0; i < 2 * KM - 1; i++)
+            if (lut[i] < 0 || lut[i] >= num_buckets) return gfail(nullptr, VITS_E_ARG, "g2p_test_attention: lut[%d]=%d is no bucket", i, lut[i]);
+    }
+    const int64_t C = (int64_t)heads * dk;
+    // every (channel, column) its own element: columns inside a channel's row, or channels inside a column's vector
+    const bool ch_outer = q_ts >= 1 && q_cs >= (int64_t)q_ts * (cols - 1) + 1, col_outer = q_cs >= 1 && q_ts >= (int64_t)q_cs * (C - 1) + 1;
+    if (!ch_outer && !col_outer) return gfail(nullptr, VITS_E_ARG, "g2p_test_attention: q / out strides overlap");
+    const int64_t nq = (C - 1) * q_cs + (int64_t)(cols - 1) * q_ts + 1;
+    if (nq > ((int64_t)1 << 28)) return gfail(nullptr, VITS_E_ARG, "g2p_test_attention: q / out too large");
+    if (kp < Tk || (nseq - 1) * kv_bs + (C - 1) * kp + Tk > kv_n)
+        return gfail(nullptr, VITS_E_ARG, "g2p_test_attention: %lld floats of k / v do not hold %d sequences (kp %d, kv_bs %lld, Tk %d)",
+                     (long long)kv_n, nseq, kp, (long long)kv_bs, Tk);
+    if (hipSetDevice(device) != hipSuccess) return gfail(nullptr, VITS_E_DEVICE, "hipSetDevice(%d) failed", device);
+    DevBufs B;
+    const float *dq = B.up(q, (size_t)nq), *dk_ = B.up(k, (size_t)kv_n), *dv = B.up(v, (size_t)kv_n);
+    float *dout = B.up(out, (size_t)nq);  // (what the kernel does not write comes back as it went in)
+    const float *dbias = bias ? B.up(bias, (size_t)num_buckets * heads) : nullptr;
+    const int *dlut = lut ? B.up(lut, (size_t)(2 * KM - 1)) : nullptr, *dlens = lens ? B.up(lens, (size_t)nseq) : nullptr;
+    if (!B.ok()) return gfail(nullptr, VITS_E_NOMEM, "g2p_test_attention: device buffers");
+    g2p_attention_kernel<<<dim3(cols, heads), 256, (size_t)(Tk + dk) * sizeof(float), nullptr>>>(
+        dq, q_cs, q_ts, dk_, dv, kp, kv_bs, dbias, dlut, KM - 1, dout, heads, dk, seg, dlens, Tk, q_off, causal);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = download(out, dout, (size_t)nq);
+    if (e != hipSuccess) return gfail(nullptr, VITS_E_DEVICE, "g2p_test_attention failed: %s", hipGetErrorString(e));
+    return VITS_OK;
+}
+
+int g2p_test_rmsnorm(int device, const float *x, const float *g, float *y, int C, int T, int xpitch, int ypitch, float eps) {
+    if (!x || !g || !y || C < 1 || C > (1 << 20) || T < 1 || T > (1 << 16) || xpitch < T || ypitch < T || xpitch > (1 << 20) ||
+        ypitch > (1 << 20) || !(eps >= 0.f) || (int64_t)C * xpitch > ((int64_t)1 << 28) || (int64_t)C * ypitch > ((int64_t)1 << 28))
+        return gfail(nullptr, VITS_E_ARG, "bad g2p_test_rmsnorm arguments");
+    if (hipSetDevice(device) != hipSuccess) return gfail(nullptr, VITS_E_DEVICE, "hipSetDevice(%d) failed", device);
+    DevBufs B;
+    const float *dx = B.up(x, (size_t)C * xpitch), *dg = B.up(g, (size_t)C);
+    float *dy = B.up(y, (size_t)C * ypitch);
+    if (!B.ok()) return gfail(nullptr, VITS_E_NOMEM, "g2p_test_rmsnorm: device buffers");
+    g2p_rmsnorm_kernel<<<T, 256, 0, nullptr>>>(dx, dg, dy, C, T, xpitch, ypitch, eps);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = download(y, dy, (size_t)C * ypitch);
+    if (e != hipSuccess) return gfail(nullptr, VITS_E_DEVICE, "g2p_test_rmsnorm failed: %s", hipGetErrorString(e));
+    return VITS_OK;
+}
+
+int g2p_test_argmax(int device, const float *logits, int V, int pitch, int t, int64_t lb, int NB, int64_t *ids, int64_t *host_copy,
+                    int64_t ib, int slot) {
+    if (!logits || !ids || !host_copy || V < 1 || V > (1 << 20) || pitch < 1 || pitch > (1 << 16) || t < 0 || t >= (1 << 16) || lb < 0 ||
+        lb > (1 << 20) || NB < 1 || NB > (1 << 16) || ib < 1 || ib > (1 << 16) || slot < 0 || slot >= ib)
+        return gfail(nullptr, VITS_E_ARG, "bad g2p_test_argmax arguments");
+    const int64_t nl = (int64_t)(NB - 1) * lb + (int64_t)(V - 1) * pitch + t + 1, ni = (int64_t)NB * ib;
+    if (nl > ((int64_t)1 << 28)) return gfail(nullptr, VITS_E_ARG, "g2p_test_argmax: logits too large");
+    if (hipSetDevice(device) != hipSuccess) return gfail(nullptr, VITS_E_DEVICE, "hipSetDevice(%d) failed", device);
+    DevBufs B;
+    const float *dl = B.up(logits, (size_t)nl);
+    int64_t *di = B.up(ids, (size_t)ni), *dh = B.up(host_copy, (size_t)ni);
+    if (!B.ok()) return gfail(nullptr, VITS_E_NOMEM, "g2p_test_argmax: device buffers");
+    g2p_argmax_kernel<<<NB, 256, 0, nullptr>>>(dl, V, pitch, t, lb, di, ib, slot, dh);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = download(ids, di, (size_t)ni);
+    if (e == hipSuccess) e = download(host_copy, dh, (size_t)ni);
+    if (e != hipSuccess) return gfail(nullptr, VITS_E_DEVICE, "g2p_test_argmax failed: %s", hipGetErrorString(e));
     return VITS_OK;
 }
 

@@ -307,7 +307,73 @@ def test_step(Ws, x, W2s=None, g=None, act=-1, eps=1e-6, post=1.0, res=None, dev
     return ys
 
 
-test_linear.__test__ = test_step.__test__ = False  # (helpers, not test cases)
+MAX_POSITIONS = 1024  # G2PModel::kMaxPos (hparam "max_positions"): the bucket table holds 2 * MAX_POSITIONS - 1 entries
+
+
+def test_attention(q, out, q_cs, q_ts, k, v, kp, kv_bs, heads, dk, cols, seg, Tk, bias=None, lut=None, lens=None, q_off=0,
+                   causal=False, device_id=0):
+    """Kernel test (g2p_test_attention): one launch of the attention kernel as the engine launches it.  q, out: flat float32
+    buffers of (heads * dk - 1) * q_cs + (cols - 1) * q_ts + 1 elements (element (channel, column) at channel * q_cs + column
+    * q_ts); k, v: flat float32 buffers of one size (sequence b at b * kv_bs, channel stride kp); bias [num_buckets, heads] and
+    lut (int32, 2 * MAX_POSITIONS - 1) or neither; lens: per sequence of `seg` columns, or None (Tk keys each).  Returns a copy
+    of `out` with what the kernel wrote."""
+    lib = _ffi.load()
+    f32 = lambda a: np.ascontiguousarray(a, np.float32).reshape(-1)
+    q, k, v, y = f32(q), f32(k), f32(v), np.array(out, np.float32).reshape(-1)
+    n = (heads * dk - 1) * int(q_cs) + (cols - 1) * int(q_ts) + 1
+    if q.size != n or y.size != n or k.size != v.size:
+        raise SessionError(f"test_attention: q / out must hold {n} floats, k and v the same number")
+    nb = 0
+    if bias is not None:
+        bias = np.ascontiguousarray(bias, np.float32)
+        if bias.ndim != 2 or bias.shape[1] != heads:
+            raise SessionError("test_attention: bias must be [num_buckets, heads]")
+        nb = bias.shape[0]
+    if lut is not None:
+        lut = np.ascontiguousarray(lut, np.int32).reshape(-1)
+        if lut.size != 2 * MAX_POSITIONS - 1:
+            raise SessionError(f"test_attention: lut must hold {2 * MAX_POSITIONS - 1} buckets")
+    if lens is not None:
+        lens = np.ascontiguousarray(lens, np.int32).reshape(-1)
+        if seg < 1 or lens.size != cols // seg:
+            raise SessionError("test_attention: one length per sequence")
+    rc = lib.g2p_test_attention(device_id, _ffi.ptr(q), _ffi.ptr(y), int(q_cs), int(q_ts), _ffi.ptr(k), _ffi.ptr(v), k.size, int(kp),
+                                int(kv_bs), _ffi.ptr(bias), nb, _ffi.ptr(lut), int(heads), int(dk), int(cols), int(seg),
+                                _ffi.ptr(lens), int(Tk), int(q_off), 1 if causal else 0)
+    if rc != 0:
+        raise SessionError(f"g2p_test_attention failed [{rc}]: {lib.g2p_last_error(None).decode()}")
+    return y
+
+
+def test_rmsnorm(x, g, y, T, eps=1e-6, device_id=0):
+    """Kernel test (g2p_test_rmsnorm): x [C, xpitch], g [C], y [C, ypitch] (the buffer the kernel writes into), the first T
+    columns normalised over the channels.  Returns a copy of y with what the kernel wrote."""
+    lib = _ffi.load()
+    x, g, y = np.ascontiguousarray(x, np.float32), np.ascontiguousarray(g, np.float32).reshape(-1), np.array(y, np.float32)
+    if x.ndim != 2 or y.ndim != 2 or y.shape[0] != x.shape[0] or g.size != x.shape[0]:
+        raise SessionError("test_rmsnorm: x [C, xpitch], g [C], y [C, ypitch]")
+    rc = lib.g2p_test_rmsnorm(device_id, _ffi.ptr(x), _ffi.ptr(g), _ffi.ptr(y), x.shape[0], int(T), x.shape[1], y.shape[1], float(eps))
+    if rc != 0:
+        raise SessionError(f"g2p_test_rmsnorm failed [{rc}]: {lib.g2p_last_error(None).decode()}")
+    return y
+
+
+def test_argmax(logits, V, pitch, t, lb, NB, ids, slot, device_id=0):
+    """Kernel test (g2p_test_argmax): logit v of sequence b at flat index b * lb + v * pitch + t of `logits`; ids int64 [NB, ib].
+    Returns (ids, host copy) after the launch: two copies of `ids` with column `slot` written by the kernel's two stores."""
+    lib = _ffi.load()
+    lg = np.ascontiguousarray(logits, np.float32).reshape(-1)
+    a, b = np.array(ids, np.int64), np.array(ids, np.int64)
+    if a.ndim != 2 or a.shape[0] != NB or lg.size != (NB - 1) * int(lb) + (V - 1) * int(pitch) + int(t) + 1:
+        raise SessionError("test_argmax: ids must be [NB, ib], logits (NB - 1) * lb + (V - 1) * pitch + t + 1 floats")
+    rc = lib.g2p_test_argmax(device_id, _ffi.ptr(lg), int(V), int(pitch), int(t), int(lb), int(NB), _ffi.ptr(a), _ffi.ptr(b),
+                             a.shape[1], int(slot))
+    if rc != 0:
+        raise SessionError(f"g2p_test_argmax failed [{rc}]: {lib.g2p_last_error(None).decode()}")
+    return a, b
+
+
+test_linear.__test__ = test_step.__test__ = test_attention.__test__ = test_rmsnorm.__test__ = test_argmax.__test__ = False  # (helpers, not test cases)
 
 
 class ByT5Phonemizer(SimplePhonemizer):

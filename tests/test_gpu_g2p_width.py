@@ -5,7 +5,9 @@ rows of the matrix-vector step kernel, and the wide decoder step (more than four
 
 Three layers: the linear and step kernels through the engine's own dispatch (g2p_test_linear / g2p_test_step) against exact
 integer products and float64; then the whole engine on seeded full-width models (phoonnx_amd.synth.write_t5, itself pinned to
-transformers in test_g2p_oracle.py) against the float64 oracle."""
+transformers in test_g2p_oracle.py) against the float64 oracle - at the end also across the boundaries of the attention bodies
+(more than 64 and 256 keys in one-query attention, a padded batch with a 700-byte input, 1023 keys), which
+test_gpu_g2p_kernels.py tests launch by launch."""
 import os
 
 import numpy as np
@@ -26,8 +28,10 @@ LOGIT_TOL = 2e-3   # test_gpu_g2p.py's bound, for logits O(30)
 F32_GAP = {
     "w1472_2x2": 3.30e-5,    # measured 3.29e-5 (logits up to 37): bound 1.32e-4; engine: run 2.2e-5, narrow 1.5e-5, wide 2.3e-5
     "w1472_12x4": 3.70e-5,   # measured 3.69e-5 (logits up to 32): bound 1.48e-4; engine: run 2.2e-5, narrow 2.9e-5, wide 2.8e-5
-    "relu_tied": 7.3e-6,     # measured 7.27e-6 (logits up to 12): bound 2.9e-5; engine: run 2.4e-6, steps 2.1e-6
-    "gelu_erf": 2.56e-5,     # measured 2.55e-5 (logits up to 34): bound 1.02e-4; engine: run 1.0e-5, steps 1.3e-5
+    # (the two small models also run the long inputs below - LONG_LENS, LONG_RUN_SHAPES - where the gap is larger: 7.27e-6 and
+    # 2.55e-5 over the short ones)
+    "relu_tied": 8.2e-6,     # measured 8.18e-6 (logits up to 13): bound 3.3e-5; engine: run 2.4e-6, steps 2.1e-6, long steps 2.7e-6
+    "gelu_erf": 3.55e-5,     # measured 3.54e-5 (logits up to 38): bound 1.42e-4; engine: run 1.0e-5, steps 1.3e-5, long steps 1.2e-5
 }
 MODELS = {
     "w1472_2x2": dict(d_model=1472, d_ff=3584, num_heads=6, d_kv=64, num_layers=2, num_decoder_layers=2),
@@ -73,6 +77,22 @@ def pool(seed=102):
     rng = np.random.default_rng(seed)
     seqs = [rng.integers(3, 259, n).astype(np.int64) for n in POOL_LENS]
     decs = np.concatenate((np.zeros((64, 1), np.int64), rng.integers(3, 259, (64, NARROW_STEPS - 1))), axis=1)
+    return seqs, decs
+
+
+# Across the boundaries of the attention bodies (the small models only: a case costs little on them).  Input lengths on both
+# sides of 64 and 256 keys, one of 700 bytes beside one of 1 (the batched encoder pads to the longest; cross attention runs under
+# `lens`), and enough forced steps that self attention crosses 64 and 256 keys too.
+LONG_LENS = (300, 257, 256, 65, 64, 3, 1, 129, 700)
+LONG_STEPS = 270
+LONG_RUN_SHAPES = ((1023, 5), (40, 300))
+
+
+def long_pool(seed=103):
+    """the LONG_LENS inputs and their given decoder inputs [9, LONG_STEPS] (column 0 = the start token)"""
+    rng = np.random.default_rng(seed)
+    seqs = [rng.integers(3, 259, n).astype(np.int64) for n in LONG_LENS]
+    decs = np.concatenate((np.zeros((len(seqs), 1), np.int64), rng.integers(3, 259, (len(seqs), LONG_STEPS - 1))), axis=1)
     return seqs, decs
 
 
@@ -404,3 +424,48 @@ def test_relu_tied_and_erf_gelu_models_match_the_float64_oracle(name):
         got = s.forced_step_logits(seqs[:B], decs[:B, :WIDE_STEPS])
         for b in range(B):
             _check(name, got[b], _pool_ref(name, b, WIDE_STEPS), f"forced B {B} seq {b}")
+
+
+def _long_ref(name, b):
+    """float64 logits [LONG_STEPS, vocab] of long_pool sequence b (computed once, shared by every test below)"""
+    key = (name, "long", b)
+    if key not in _REFS:
+        seqs, decs = long_pool()
+        _REFS[key] = _oracle(name).logits(seqs[b], decs[b])[0]
+    return _REFS[key]
+
+
+@pytest.mark.parametrize("B", [1, 2, 4, 5, 9])
+@pytest.mark.parametrize("name", ["relu_tied", "gelu_erf"])
+def test_decoder_steps_across_64_and_256_keys_match_the_float64_oracle(name, B):
+    """Inputs of 300, 257, 256, 65, 64, 3, 1, 129 and 700 bytes, 270 forced steps: one-query self attention from 1 to 270 keys
+    (the second lane round, the whole value prefetch and the loop behind it, the second pass of the score loop), cross
+    attention over 1 .. 700 keys under `lens`, and the batched encoder over a padded batch with its longest sequence beside its
+    shortest - narrow (NB 1, 2, 4: the [NB][C] query strides) and wide (NB 8, 16: [C][NB])."""
+    s = _sess(name)
+    seqs, decs = long_pool()
+    got = s.forced_step_logits(seqs[:B], decs[:B])
+    for b in range(B):
+        _check(name, got[b], _long_ref(name, b), f"long forced B {B} seq {b} (input {LONG_LENS[b]})")
+
+
+@pytest.mark.parametrize("name", ["relu_tied", "gelu_erf"])
+def test_run_across_the_far_end_of_the_bucket_table_matches_the_float64_oracle(name):
+    """The prefill at (S, T) = (1023, 5) - the longest input the engine takes: encoder self attention and cross attention over
+    1023 keys, relative positions to the ends of the bucket table - and (40, 300): causal self attention over 300 columns."""
+    s, o = _sess(name), _oracle(name)
+    for ids, dec in run_cases(LONG_RUN_SHAPES, seed=104):
+        got = s.run(None, {"input_ids": ids[None], "decoder_input_ids": dec[None]})[0]
+        _check(name, got, o.logits(ids, dec), f"run S {len(ids)} T {len(dec)}")
+
+
+def test_the_one_launch_decoder_step_is_bit_identical_past_256_keys(monkeypatch):
+    """The B = 2 case above once more through the opt-in persistent step (VITSMI_G2P_PERSIST=1): its LDS is sized by max(S, TM)
+    (cross attention over 300 keys, self attention over up to 270), the attention phases are virtual blocks of the same bodies -
+    the same logits bit for bit."""
+    s = _sess("gelu_erf")
+    seqs, decs = long_pool()
+    want = s.forced_step_logits(seqs[:2], decs[:2])
+    monkeypatch.setenv("VITSMI_G2P_PERSIST", "1")
+    got = s.forced_step_logits(seqs[:2], decs[:2])
+    assert np.array_equal(got, want)
