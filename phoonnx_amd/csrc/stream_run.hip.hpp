@@ -8,6 +8,7 @@
 
 #include <cstdint>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "resample.hip.hpp"
@@ -70,26 +71,34 @@ inline hipError_t resample_run_piece(ResampleRun &r, const float *x, int64_t x_p
 
 // ---- warped pieces ("streamed pitch"): the whole run's [B][S_w], bit for bit, whatever the pieces.  The stage in FRONT of the others:
 // it keeps the native waveform (the history), and what a piece completes by the emit rule (warp.hpp) leaves it on the output timeline.
+
+// A WarpRun's plan is one of four: records of either family (`glide`: which kernel a window launches) under native or folded
+// rows (`folded`, "pitch at an output rate": WarpRateRow in place of WarpRow, the wide kernels).  One record vector and one row
+// vector are in use.  THE choice among the four: f(the run's records, the run's rows), both as their typed vectors - nothing
+// else looks at the flags.  (r: a WarpRun, const or not.)
+template <class Run, class F>
+inline auto warp_run_visit(Run &r, F f) {
+    if (r.folded) return r.glide ? f(r.gsegs, r.rrows) : f(r.wsegs, r.rrows);
+    return r.glide ? f(r.gsegs, r.rows) : f(r.wsegs, r.rows);
+}
+
 struct WarpRun {
-    bool glide = false;                 // which family's records the plan holds - and which kernel a window launches
+    bool glide = false, folded = false;
     std::vector<vits_warp_seg> wsegs;
-    std::vector<vits_glide_seg> gsegs;  // (one of the two is empty)
-    std::vector<int32_t> first;         // [B + 1]
+    std::vector<vits_glide_seg> gsegs;
     std::vector<WarpRow> rows;          // [B]
+    std::vector<WarpRateRow> rrows;     // [B]
+    std::vector<int32_t> first;         // [B + 1]
     std::vector<int64_t> spans;         // [B][T]: k per token, as vits_last_token_spans reports it
     int64_t S_w = 0, n_cap = 0;
+    int64_t half = kWarpMaxHalf;        // the largest Kh the emit rule counts with (warp_plan_extent)
     int64_t emitted = 0, e_end = 0;     // output samples delivered so far / complete behind the last piece
     WarpStreamBufs wb{};
     const float *G = nullptr;
     std::vector<char> up;               // (pageable source of the plan's upload where the caller has no pinned block)
-    // a folded plan ("pitch at an output rate"): its rows in place of `rows`, the largest Kh the emit rule counts with, and the
-    // wide kernels in the windows
-    bool folded = false;
-    std::vector<WarpRateRow> rrows;     // [B]
-    int64_t half = kWarpMaxHalf;
-    size_t row_bytes() const { return folded ? sizeof(WarpRateRow) : sizeof(WarpRow); }
-    int32_t row_out(int b) const { return folded ? rrows[(size_t)b].n_out : rows[(size_t)b].n_out; }
-    int64_t n_segs() const { return glide ? (int64_t)gsegs.size() : (int64_t)wsegs.size(); }
+    size_t row_bytes() const { return warp_run_visit(*this, [](auto &, auto &rows) { return sizeof(rows[0]); }); }
+    int32_t row_out(int b) const { return warp_run_visit(*this, [b](auto &, auto &rows) { return rows[(size_t)b].n_out; }); }
+    int64_t n_segs() const { return warp_run_visit(*this, [](auto &segs, auto &) { return (int64_t)segs.size(); }); }
 };
 
 // The plan [segs | rows] and the rows' output counts, uploaded once; pin (nullable): plan_bytes + 4 B bytes of pinned memory.
@@ -98,15 +107,17 @@ inline hipError_t warp_run_begin(WarpRun &r, const WarpStreamBufs &wb, const flo
     r.G = G;
     r.n_cap = n_cap;
     r.emitted = r.e_end = 0;
-    const size_t seg_bytes = (size_t)r.n_segs() * sizeof(vits_warp_seg);
     if (!pin) {
         r.up.resize(wb.plan_bytes + (size_t)B * sizeof(int));
         pin = r.up.data();
     }
-    if (seg_bytes) std::memcpy(pin, r.glide ? (const void *)r.gsegs.data() : (const void *)r.wsegs.data(), seg_bytes);
-    std::memcpy(pin + seg_bytes, r.folded ? (const void *)r.rrows.data() : (const void *)r.rows.data(), (size_t)B * r.row_bytes());
     int *pin_nout = reinterpret_cast<int *>(pin + wb.plan_bytes);
-    for (int b = 0; b < B; b++) pin_nout[b] = r.row_out(b);
+    warp_run_visit(r, [&](auto &segs, auto &rows) {
+        const size_t seg_bytes = segs.size() * sizeof(segs[0]);
+        if (seg_bytes) std::memcpy(pin, segs.data(), seg_bytes);
+        std::memcpy(pin + seg_bytes, rows.data(), (size_t)B * sizeof(rows[0]));
+        for (int b = 0; b < B; b++) pin_nout[b] = rows[(size_t)b].n_out;
+    });
     hipError_t e = hipMemcpyAsync(wb.segs, pin, wb.plan_bytes, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(wb.n_out, pin_nout, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st);
     return e;
@@ -118,13 +129,7 @@ inline hipError_t warp_run_piece(WarpRun &r, const float *x, int64_t x_pitch, in
     hipError_t e = hipSuccess;
     if (n > 0)
         e = hipMemcpy2DAsync(r.wb.hist + first, (size_t)r.wb.hist_pitch * 4, x, (size_t)x_pitch * 4, (size_t)n * 4, B, hipMemcpyDeviceToDevice, st);
-    int64_t end;
-    if (r.folded)
-        end = r.glide ? warp_rate_emit_end(r.gsegs.data(), r.rrows, r.S_w, first + n, is_last, r.half)
-                      : warp_rate_emit_end(r.wsegs.data(), r.rrows, r.S_w, first + n, is_last, r.half);
-    else
-        end = r.glide ? warp_emit_end(r.gsegs.data(), r.rows, r.S_w, first + n, is_last)
-                      : warp_emit_end(r.wsegs.data(), r.rows, r.S_w, first + n, is_last);
+    const int64_t end = warp_run_visit(r, [&](auto &segs, auto &rows) { return warp_emit_end(segs.data(), rows, r.S_w, first + n, is_last, r.half); });
     r.e_end = end > r.e_end ? end : r.e_end;
     return e;
 }
@@ -143,8 +148,12 @@ inline hipError_t warp_run_window(WarpRun &r, int B, hipStream_t st, const float
     y = r.wb.out;
     launches = 1;
     r.emitted += e_n;
-    const auto args = [&](auto &a) {
-        a.rows = static_cast<decltype(a.rows)>(r.wb.rows);
+    return warp_run_visit(r, [&](auto &segs, auto &rows) {
+        using Seg = std::decay_t<decltype(segs[0])>;
+        using Row = std::decay_t<decltype(rows[0])>;
+        WarpArgsT<Seg, Row> a{};
+        a.segs = reinterpret_cast<const Seg *>(r.wb.segs);
+        a.rows = static_cast<const Row *>(r.wb.rows);
         a.G = r.G;
         a.x = r.wb.hist;
         a.x_pitch = r.wb.hist_pitch;
@@ -152,29 +161,8 @@ inline hipError_t warp_run_window(WarpRun &r, int B, hipStream_t st, const float
         a.y_pitch = e_n;
         a.n_lo = (int)e_first;
         a.n_hi = (int)(e_first + e_n);
-    };
-    if (r.folded && r.glide) {
-        GlideRateArgs a{};
-        a.segs = reinterpret_cast<const vits_glide_seg *>(r.wb.segs);
-        args(a);
-        return launch_glide_rate(a, B, st);
-    }
-    if (r.folded) {
-        WarpRateArgs a{};
-        a.segs = r.wb.segs;
-        args(a);
-        return launch_warp_rate(a, B, st);
-    }
-    if (r.glide) {
-        GlideArgs a{};
-        a.segs = reinterpret_cast<const vits_glide_seg *>(r.wb.segs);
-        args(a);
-        return launch_glide(a, B, st);
-    }
-    WarpArgs a{};
-    a.segs = r.wb.segs;
-    args(a);
-    return launch_warp(a, B, st);
+        return launch_warp_tile(a, B, st);
+    });
 }
 
 // ---- packed pieces: the encoded sink.  A piece reaches sp's chunk buffer as [B][pitch] bytes that end at the running peaks.

@@ -2117,9 +2117,8 @@ int resample_rows_run(vits_handle *h, const int *ylen, int B) {
 
 // The whole waveform a run has just rendered (h->d_out, rows of h->S samples) -> [B][S_w], every token played back at its own
 // speed.  The plans come from the host copy of the durations, which the run's one readback left: no synchronisation.
-// d_out / S describe the warped buffer afterwards, as after resample_run.
-// One body serves the warp (Seg = vits_warp_seg) and the glide ("pitch contours", Seg = vits_glide_seg: a record of the same
-// size, so carve_warp carves either plan block): plan_row plans a row into its records, launch is the family's launch.
+// d_out / S describe the warped buffer afterwards, as after resample_run.  (warp_run_planned, below.)
+
 // the prototype table on the device (made by the first warped run) and the pinned block a plan is uploaded from
 int warp_device_begin(vits_handle *h, size_t pin_bytes) {
     if (!h->warp_G) {
@@ -2141,89 +2140,36 @@ int warp_device_begin(vits_handle *h, size_t pin_bytes) {
 }
 
 // The plans of a run's rows from the host copy of the durations, which the run's one readback left: no synchronisation.
-// row_in: the input samples a row has at most.  The whole run (warp_run_as) and the streamed one (render_chunks) plan HERE.
-template <class Seg, class PlanRow>
-int warp_plan_run(vits_handle *h, const RunRows &rr, int B, int T, int64_t row_in, PlanRow plan_row, std::vector<Seg> &segs,
-                  std::vector<int32_t> &first, std::vector<int64_t> &spans, std::vector<WarpRow> &rows, int64_t &S_w) {
+// row_in: the input samples a row has at most.  The whole run (warp_run_planned) and the streamed one (render_chunks) plan
+// HERE, through one of the two warp_plan_run below, chosen by the rows' type.  What they share: the durations must be the
+// run's, a row's valid input is clamped to row_in, `plan` makes the records and S_w of it - "" or what is wrong -, and S_w
+// must be a row's length.
+template <class Plan>
+int warp_plan_checked(vits_handle *h, int B, int T, int64_t row_in, int64_t &S_w, Plan plan) {
     if (h->h_dur_B != B || h->h_dur_T != T) return fail(h, VITS_E_ARG, "no durations to plan the warp from");
     std::vector<int64_t> n_in((size_t)B);
     for (int b = 0; b < B; b++) {
         const int64_t n = (int64_t)h->h_ylen[b] * h->model.hop;
         n_in[b] = n < 0 ? 0 : (n > row_in ? row_in : n);
     }
-    const std::string e = warp_plan_rows(h->h_dur.data(), rr.semitone_lens, n_in.data(), B, T, h->model.hop, plan_row, segs, first, spans, rows, S_w);
+    const std::string e = plan(n_in);
     if (!e.empty()) return fail(h, VITS_E_ARG, "%s", e.c_str());
     if (S_w > INT_MAX) return fail(h, VITS_E_ARG, "a warped row of %lld samples: more than a row admits (%d)", (long long)S_w, INT_MAX);
     return 0;
 }
 
-// the two families' plan_row over a run's semitones
-auto warp_plan_row(const RunRows &rr, int T) {
-    return [&rr, T](int b, const int64_t *dur, int L, int hop, vits_warp_seg *segs, int64_t *spans, int64_t &ns, int64_t &N) {
-        return warp_plan(dur, rr.semitones + (size_t)b * T, L, hop, segs, spans, ns, N);
+// native rows: constant tokens plan with warp_plan, gliding ones (rr.semitones_end) with glide_plan
+template <class Seg>
+int warp_plan_run(vits_handle *h, const RunRows &rr, int B, int T, int64_t row_in, std::vector<Seg> &segs, std::vector<int32_t> &first,
+                  std::vector<int64_t> &spans, std::vector<WarpRow> &rows, int64_t &S_w) {
+    auto plan_row = [&](int b, const int64_t *dur, int len, int hp, Seg *sg, int64_t *sp, int64_t &ns, int64_t &N) -> std::string {
+        const float *s0 = rr.semitones + (size_t)b * T;
+        if constexpr (std::is_same_v<Seg, vits_warp_seg>) return warp_plan(dur, s0, len, hp, sg, sp, ns, N);
+        else return glide_plan(dur, s0, rr.semitones_end + (size_t)b * T, len, hp, sg, sp, ns, N);
     };
-}
-auto glide_plan_row(const RunRows &rr, int T) {
-    return [&rr, T](int b, const int64_t *dur, int L, int hop, vits_glide_seg *segs, int64_t *spans, int64_t &ns, int64_t &N) {
-        return glide_plan(dur, rr.semitones + (size_t)b * T, rr.semitones_end + (size_t)b * T, L, hop, segs, spans, ns, N);
-    };
-}
-
-// what a warped run leaves for the host: the rows' output counts and k per token
-void warp_remember(vits_handle *h, const std::vector<WarpRow> &rows, std::vector<int64_t> &&spans, int T) {
-    h->warp_counts.resize(rows.size());
-    for (size_t b = 0; b < rows.size(); b++) h->warp_counts[b] = rows[b].n_out;
-    h->warp_spans = std::move(spans);
-    h->warp_T = T;
-}
-
-template <class Seg, class PlanRow, class Launch>
-int warp_run_as(vits_handle *h, const RunRows &rr, int B, int T, PlanRow plan_row, Launch launch) {
-    const int S = h->S;
-    std::vector<Seg> segs;
-    std::vector<int32_t> first;
-    std::vector<int64_t> spans;
-    std::vector<WarpRow> rows;
-    int64_t S_w = 1;
-    if (int rc = warp_plan_run(h, rr, B, T, S, plan_row, segs, first, spans, rows, S_w)) return rc;
-    WarpBufs wb;
-    if (int rc = slab_carve(h, h->io, "staging", [&](Carver &cv) { wb = carve_warp(cv, B, (int)S_w, (int64_t)segs.size()); })) return rc;
-    hipStream_t st = h->stream;
-    // [segs | rows | n_out] in pinned memory
-    if (int rc = warp_device_begin(h, wb.plan_bytes + (size_t)B * sizeof(int))) return rc;
-    const size_t seg_bytes = segs.size() * sizeof(Seg);
-    if (seg_bytes) std::memcpy(h->warp_pin, segs.data(), seg_bytes);
-    std::memcpy(h->warp_pin + seg_bytes, rows.data(), (size_t)B * sizeof(WarpRow));
-    int *pin_nout = reinterpret_cast<int *>(h->warp_pin + wb.plan_bytes);
-    for (int b = 0; b < B; b++) pin_nout[b] = rows[(size_t)b].n_out;
-    HIPCHECK(h, hipMemcpyAsync(wb.segs, h->warp_pin, wb.plan_bytes, hipMemcpyHostToDevice, st));
-    HIPCHECK(h, hipMemcpyAsync(wb.front.n_out, pin_nout, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
-    WarpArgsT<Seg> a{};
-    a.segs = reinterpret_cast<const Seg *>(wb.segs);
-    a.rows = static_cast<const WarpRow *>(wb.rows);
-    a.G = h->warp_G;
-    a.x = h->d_out;
-    a.x_pitch = S;
-    a.y = wb.front.out;
-    a.y_pitch = S_w;
-    a.n_hi = (int)S_w;
-    const hipError_t e = launch(a, B, st);
-    if (e != hipSuccess) return fail(h, VITS_E_DEVICE, "warp launch failed: %s", hipGetErrorString(e));
-    h->stats.total_launches += 1;
-    h->d_out = wb.front.out;
-    h->S = (int)S_w;
-    h->d_nout = wb.front.n_out;
-    h->rs_run_K = 0;
-    h->rs_run_L = h->rs_run_M = 1;
-    h->out_resampled = true;
-    warp_remember(h, rows, std::move(spans), T);
-    return 0;
-}
-
-// constant tokens: warp_kernel; some token glides (rr.semitones_end): glide_kernel in its slot
-int warp_run(vits_handle *h, const RunRows &rr, int B, int T) {
-    if (!rr.semitones_end) return warp_run_as<vits_warp_seg>(h, rr, B, T, warp_plan_row(rr, T), launch_warp);
-    return warp_run_as<vits_glide_seg>(h, rr, B, T, glide_plan_row(rr, T), launch_glide);
+    return warp_plan_checked(h, B, T, row_in, S_w, [&](const std::vector<int64_t> &n_in) {
+        return warp_plan_rows(h->h_dur.data(), rr.semitone_lens, n_in.data(), B, T, h->model.hop, plan_row, segs, first, spans, rows, S_w);
+    });
 }
 
 // ---- pitch at an output rate (vitsmi.h, "pitch at an output rate"): the rate folded into the warp's steps, one launch from the
@@ -2236,38 +2182,34 @@ const ResampleDev *rate_of_row(const vits_handle *h, int b) {
     return nullptr;
 }
 
-// The folded plans of a run's rows from the host copy of the durations: warp_plan_run's sibling.  row_in: the input samples a
-// row has at most.  An unpitched row leaves no record - it is an identity row, its spans the resampler's rule -; every other
-// row is planned with its own (L_b, M_b) folded in.  The whole run and the streamed one plan HERE.
+// folded rows: an unpitched row leaves no record - it is an identity row, its spans the resampler's rule -; every other row is
+// planned with its own (L_b, M_b) folded in
 template <class Seg>
-int warp_rate_plan_run(vits_handle *h, const RunRows &rr, int B, int T, int64_t row_in, std::vector<Seg> &segs, std::vector<int32_t> &first,
-                       std::vector<int64_t> &spans, std::vector<WarpRateRow> &rows, int64_t &S_w) {
-    const int hop = h->model.hop;
-    if (h->h_dur_B != B || h->h_dur_T != T) return fail(h, VITS_E_ARG, "no durations to plan the warp from");
-    std::vector<int64_t> n_in((size_t)B), L((size_t)B, 1), M((size_t)B, 1);
-    for (int b = 0; b < B; b++) {
-        const int64_t n = (int64_t)h->h_ylen[b] * hop;
-        n_in[b] = n < 0 ? 0 : (n > row_in ? row_in : n);
+int warp_plan_run(vits_handle *h, const RunRows &rr, int B, int T, int64_t row_in, std::vector<Seg> &segs, std::vector<int32_t> &first,
+                  std::vector<int64_t> &spans, std::vector<WarpRateRow> &rows, int64_t &S_w) {
+    std::vector<int64_t> L((size_t)B, 1), M((size_t)B, 1);
+    for (int b = 0; b < B; b++)
         if (const ResampleDev *d = rate_of_row(h, b)) {
             L[b] = d->plan.L;
             M[b] = d->plan.M;
         }
-    }
-    auto plan_row = [&](int b, const int64_t *dur, int len, int hp, Seg *sg, int64_t *sp, int64_t &ns, int64_t &N) -> std::string {
-        const float *s0 = rr.semitones + (size_t)b * T, *s1 = rr.semitones_end ? rr.semitones_end + (size_t)b * T : nullptr;
-        if (warp_rate_unpitched(s0, s1, len)) {
-            ns = 0;
-            N = warp_rate_identity(dur, len, hp, L[b], M[b], n_in[b], sp);
-            return "";
-        }
-        if constexpr (std::is_same_v<Seg, vits_warp_seg>) return warp_plan_rate(dur, s0, len, hp, L[b], M[b], sg, sp, ns, N);
-        else return glide_plan_rate(dur, s0, s1, len, hp, L[b], M[b], sg, sp, ns, N);
-    };
-    std::vector<WarpRow> narrow;
-    const std::string e = warp_plan_rows(h->h_dur.data(), rr.semitone_lens, n_in.data(), B, T, hop, plan_row, segs, first, spans, narrow, S_w);
-    if (!e.empty()) return fail(h, VITS_E_ARG, "%s", e.c_str());
-    S_w = warp_rate_rows(segs.data(), first.data(), n_in.data(), L.data(), M.data(), B, rows);
-    if (S_w > INT_MAX) return fail(h, VITS_E_ARG, "a warped row of %lld samples: more than a row admits (%d)", (long long)S_w, INT_MAX);
+    const int rc = warp_plan_checked(h, B, T, row_in, S_w, [&](const std::vector<int64_t> &n_in) {
+        auto plan_row = [&](int b, const int64_t *dur, int len, int hp, Seg *sg, int64_t *sp, int64_t &ns, int64_t &N) -> std::string {
+            const float *s0 = rr.semitones + (size_t)b * T, *s1 = rr.semitones_end ? rr.semitones_end + (size_t)b * T : nullptr;
+            if (warp_rate_unpitched(s0, s1, len)) {
+                ns = 0;
+                N = warp_rate_identity(dur, len, hp, L[b], M[b], n_in[b], sp);
+                return "";
+            }
+            if constexpr (std::is_same_v<Seg, vits_warp_seg>) return warp_plan_rate(dur, s0, len, hp, L[b], M[b], sg, sp, ns, N);
+            else return glide_plan_rate(dur, s0, s1, len, hp, L[b], M[b], sg, sp, ns, N);
+        };
+        std::vector<WarpRow> narrow;
+        const std::string e = warp_plan_rows(h->h_dur.data(), rr.semitone_lens, n_in.data(), B, T, h->model.hop, plan_row, segs, first, spans, narrow, S_w);
+        if (e.empty()) S_w = warp_rate_rows(segs.data(), first.data(), n_in.data(), L.data(), M.data(), B, rows);
+        return e;
+    });
+    if (rc) return rc;
     for (int b = 0; b < B; b++)
         if (const ResampleDev *d = rate_of_row(h, b)) {
             rows[(size_t)b].table = d->table;
@@ -2277,48 +2219,72 @@ int warp_rate_plan_run(vits_handle *h, const RunRows &rr, int B, int T, int64_t 
     return 0;
 }
 
-template <class Seg, class Launch>
-int warp_rate_run_as(vits_handle *h, const RunRows &rr, int B, int T, Launch launch) {
+// what a warped run leaves for the host: the rows' output counts and k per token
+template <class Row>
+void warp_remember(vits_handle *h, const std::vector<Row> &rows, std::vector<int64_t> &&spans, int T) {
+    h->warp_counts.resize(rows.size());
+    for (size_t b = 0; b < rows.size(); b++) h->warp_counts[b] = rows[b].n_out;
+    h->warp_spans = std::move(spans);
+    h->warp_T = T;
+}
+
+// One body serves both record families (vits_glide_seg is a record of vits_warp_seg's size, so carve_warp carves either plan
+// block) and both row widths: plan, carve, upload, the one launch, and what the run leaves - at the native rate.
+template <class Seg, class Row>
+int warp_run_planned(vits_handle *h, const RunRows &rr, int B, int T) {
     const int S = h->S;
     std::vector<Seg> segs;
     std::vector<int32_t> first;
     std::vector<int64_t> spans;
-    std::vector<WarpRateRow> rows;
+    std::vector<Row> rows;
     int64_t S_w = 1;
-    if (int rc = warp_rate_plan_run(h, rr, B, T, S, segs, first, spans, rows, S_w)) return rc;
+    if (int rc = warp_plan_run(h, rr, B, T, S, segs, first, spans, rows, S_w)) return rc;
     WarpBufs wb;
-    if (int rc = slab_carve(h, h->io, "staging", [&](Carver &cv) { wb = carve_warp(cv, B, (int)S_w, (int64_t)segs.size(), sizeof(WarpRateRow)); }))
-        return rc;
+    if (int rc = slab_carve(h, h->io, "staging", [&](Carver &cv) { wb = carve_warp(cv, B, (int)S_w, (int64_t)segs.size(), sizeof(Row)); })) return rc;
     hipStream_t st = h->stream;
     // [segs | rows | n_out] in pinned memory
     if (int rc = warp_device_begin(h, wb.plan_bytes + (size_t)B * sizeof(int))) return rc;
     const size_t seg_bytes = segs.size() * sizeof(Seg);
     if (seg_bytes) std::memcpy(h->warp_pin, segs.data(), seg_bytes);
-    std::memcpy(h->warp_pin + seg_bytes, rows.data(), (size_t)B * sizeof(WarpRateRow));
+    std::memcpy(h->warp_pin + seg_bytes, rows.data(), (size_t)B * sizeof(Row));
     int *pin_nout = reinterpret_cast<int *>(h->warp_pin + wb.plan_bytes);
     for (int b = 0; b < B; b++) pin_nout[b] = rows[(size_t)b].n_out;
     HIPCHECK(h, hipMemcpyAsync(wb.segs, h->warp_pin, wb.plan_bytes, hipMemcpyHostToDevice, st));
     HIPCHECK(h, hipMemcpyAsync(wb.front.n_out, pin_nout, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
-    WarpRateArgsT<Seg> a{};
+    WarpArgsT<Seg, Row> a{};
     a.segs = reinterpret_cast<const Seg *>(wb.segs);
-    a.rows = static_cast<const WarpRateRow *>(wb.rows);
+    a.rows = static_cast<const Row *>(wb.rows);
     a.G = h->warp_G;
     a.x = h->d_out;
     a.x_pitch = S;
     a.y = wb.front.out;
     a.y_pitch = S_w;
     a.n_hi = (int)S_w;
-    const hipError_t le = launch(a, B, st);
-    if (le != hipSuccess) return fail(h, VITS_E_DEVICE, "warp launch failed: %s", hipGetErrorString(le));
+    const hipError_t e = launch_warp_tile(a, B, st);
+    if (e != hipSuccess) return fail(h, VITS_E_DEVICE, "warp launch failed: %s", hipGetErrorString(e));
     h->stats.total_launches += 1;
     h->d_out = wb.front.out;
     h->S = (int)S_w;
     h->d_nout = wb.front.n_out;
     h->rs_run_K = 0;  // (carve_warp's walk: no carry)
+    h->rs_run_L = h->rs_run_M = 1;
+    h->out_resampled = true;
+    warp_remember(h, rows, std::move(spans), T);
+    return 0;
+}
+
+// constant tokens: warp_kernel; some token glides (rr.semitones_end): glide_kernel in its slot
+int warp_run(vits_handle *h, const RunRows &rr, int B, int T) {
+    return rr.semitones_end ? warp_run_planned<vits_glide_seg, WarpRow>(h, rr, B, T) : warp_run_planned<vits_warp_seg, WarpRow>(h, rr, B, T);
+}
+
+// ... at an output rate: the wide kernels, and what resample_run / resample_rows_run leave about the rates of a run
+int warp_rate_run(vits_handle *h, const RunRows &rr, int B, int T) {
+    if (int rc = rr.semitones_end ? warp_run_planned<vits_glide_seg, WarpRateRow>(h, rr, B, T) : warp_run_planned<vits_warp_seg, WarpRateRow>(h, rr, B, T))
+        return rc;
     h->rs_run_L = h->rs.plan.on() ? h->rs.plan.L : 1;
     h->rs_run_M = h->rs.plan.on() ? h->rs.plan.M : 1;
-    h->out_resampled = true;
-    if (h->rows.on()) {  // what resample_rows_run leaves about the rows of a run
+    if (h->rows.on()) {
         h->run_rates.assign(B, h->rows.fi);
         h->run_L.assign(B, 1);
         h->run_M.assign(B, 1);
@@ -2329,16 +2295,7 @@ int warp_rate_run_as(vits_handle *h, const RunRows &rr, int B, int T, Launch lau
                 h->run_M[b] = d->plan.M;
             }
     }
-    h->warp_counts.resize((size_t)B);
-    for (int b = 0; b < B; b++) h->warp_counts[(size_t)b] = rows[(size_t)b].n_out;
-    h->warp_spans = std::move(spans);
-    h->warp_T = T;
     return 0;
-}
-
-int warp_rate_run(vits_handle *h, const RunRows &rr, int B, int T) {
-    if (!rr.semitones_end) return warp_rate_run_as<vits_warp_seg>(h, rr, B, T, launch_warp_rate);
-    return warp_rate_run_as<vits_glide_seg>(h, rr, B, T, launch_glide_rate);
 }
 
 // The two pinned buffers (vits_handle::ring) finished pieces reach the host through.  A piece is copied into slot(); queue()
@@ -2391,24 +2348,18 @@ int render_chunks(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int
     // durations on the host - the whole run's planning -, so that everything below sees the OUTPUT timeline: S_w, N_b.
     const bool warp = pitch != nullptr;
     WarpRun wrun;
+    int64_t cap_step = kWarpMinStep;  // what the cap of a delivery counts with: the plan's least step and (wrun.half) its largest Kh
     if (warp) {
         h->d_out = nullptr;  // (as under a plan callback: the run has begun, the host's counts are this run's from here on)
         wrun.glide = pitch->semitones_end != nullptr;
         wrun.folded = folded;
-        const int rc = folded ? (wrun.glide ? warp_rate_plan_run(h, *pitch, B, T, (int64_t)F * hop, wrun.gsegs, wrun.first, wrun.spans, wrun.rrows, wrun.S_w)
-                                            : warp_rate_plan_run(h, *pitch, B, T, (int64_t)F * hop, wrun.wsegs, wrun.first, wrun.spans, wrun.rrows, wrun.S_w))
-                       : wrun.glide ? warp_plan_run(h, *pitch, B, T, (int64_t)F * hop, glide_plan_row(*pitch, T), wrun.gsegs, wrun.first,
-                                                  wrun.spans, wrun.rows, wrun.S_w)
-                                  : warp_plan_run(h, *pitch, B, T, (int64_t)F * hop, warp_plan_row(*pitch, T), wrun.wsegs, wrun.first,
-                                                  wrun.spans, wrun.rows, wrun.S_w);
+        const int rc = warp_run_visit(wrun, [&](auto &segs, auto &rows) {
+            if (int rc = warp_plan_run(h, *pitch, B, T, (int64_t)F * hop, segs, wrun.first, wrun.spans, rows, wrun.S_w)) return rc;
+            warp_remember(h, rows, std::vector<int64_t>(wrun.spans), T);
+            warp_plan_extent(segs.data(), rows, wrun.half, cap_step);
+            return 0;
+        });
         if (rc) return rc;
-        if (folded) {
-            h->warp_counts.resize((size_t)B);
-            for (int b = 0; b < B; b++) h->warp_counts[(size_t)b] = wrun.row_out(b);
-            h->warp_spans = wrun.spans;
-            h->warp_T = T;
-        } else
-            warp_remember(h, wrun.rows, std::vector<int64_t>(wrun.spans), T);
     }
     // encoded form: the rows' valid samples (host: the callback's valid[]; device: the kernel's)
     std::vector<int64_t> row_n;
@@ -2452,11 +2403,6 @@ int render_chunks(vits_handle *h, Ctx &c, const float *z, int64_t z_bstride, int
     int S_out = 0;
     if (rs)
         if (int rc = resample_count(h, (int64_t)F * hop, S_out)) return rc;
-    int64_t cap_step = kWarpMinStep;  // a folded plan's cap counts with its own least step and largest Kh
-    if (folded) {
-        if (wrun.glide) warp_rate_plan_extent(wrun.gsegs.data(), wrun.rrows, wrun.half, cap_step);
-        else warp_rate_plan_extent(wrun.wsegs.data(), wrun.rrows, wrun.half, cap_step);
-    }
     const int64_t n_cap = warp ? warp_stream_cap((int64_t)(chunk < F ? chunk : F) * hop, wrun.S_w, cap_step, wrun.half) : 0;
     const int64_t total = warp ? wrun.S_w : rs ? (int64_t)S_out : (int64_t)F * hop;
     const int64_t n_max = warp ? (n_cap + sL < total ? n_cap + sL : total) : stream_n_max(rp, chunk, F, hop, sL, total);
@@ -5904,55 +5850,80 @@ int vits_test_resample(int device_id, const float *x, const int64_t *lens, int B
 // The time warp and the glide by value: the rows' records from the caller's segments, the pipeline's launch.
 extern "C++" {
 namespace {
-template <class Seg, class Fault, class Launch>
-int test_warp_as(int device_id, const float *x, const int64_t *counts, int B, int S, const Seg *segs, const int32_t *seg_first,
-                 float *y, int S_w, Fault fault, Launch launch) {
-    if (int rc = test_dev(device_id)) return rc;
-    if (!x || !y || !counts || !seg_first || B <= 0 || S <= 0 || S_w < 1) return fail(nullptr, VITS_E_ARG, "bad warp test arguments");
-    if (seg_first[0] != 0) return fail(nullptr, VITS_E_ARG, "seg_first[0] = %d, not 0", (int)seg_first[0]);
-    std::vector<int64_t> n_in((size_t)B);
+// The front matter of every warp hook, row by row: seg_first ascends, the row's records pass the family's `fault`, its valid
+// input is counts[b] clamped to [0, S] -> n_in[b]; then per_row(b, the row's record count) - what the hook checks of a row
+// besides, 0 or its failure.  The first thing wrong is the answer.
+template <class Seg, class Fault, class PerRow>
+int warp_test_rows(const Seg *segs, const int32_t *seg_first, const int64_t *counts, int B, int S, Fault fault, std::vector<int64_t> &n_in,
+                   PerRow per_row) {
+    n_in.assign((size_t)B, 0);
     for (int b = 0; b < B; b++) {
         const int32_t ns = seg_first[b + 1] - seg_first[b];
         if (ns < 0 || (ns > 0 && !segs)) return fail(nullptr, VITS_E_ARG, "row %d: seg_first is not ascending", b);
         const std::string e = fault(segs + seg_first[b], ns);
         if (!e.empty()) return fail(nullptr, VITS_E_ARG, "row %d: %s", b, e.c_str());
         n_in[(size_t)b] = counts[b] < 0 ? 0 : (counts[b] > S ? S : counts[b]);
+        if (int rc = per_row(b, ns)) return rc;
     }
-    std::vector<WarpRow> rows;
-    const int64_t need = warp_rows(segs, seg_first, n_in.data(), B, rows);
-    if (S_w < need) return fail(nullptr, VITS_E_ARG, "S_w = %d, the longest row has %lld output samples", S_w, (long long)need);
+    return 0;
+}
+template <class Seg, class Fault>
+int warp_test_rows(const Seg *segs, const int32_t *seg_first, const int64_t *counts, int B, int S, Fault fault, std::vector<int64_t> &n_in) {
+    return warp_test_rows(segs, seg_first, counts, B, S, fault, n_in, [](int, int32_t) { return 0; });
+}
+
+// G, the records, the rows and x [B][S] on the device, y poisoned; output samples [n_lo, n_hi) of every row through the
+// pipeline's launch into y [B][n_hi - n_lo]
+template <class Seg, class Row>
+int warp_test_launch(DevBufs &D, const Seg *segs, size_t n_segs, const std::vector<Row> &rows, const float *x, int B, int S, int n_lo, int n_hi,
+                     float *y) {
     std::vector<float> G(kWarpTable);
     warp_table(G.data());
-    DevBufs D;
-    const size_t n_segs = (size_t)seg_first[B];
     const Seg none{};
-    WarpArgsT<Seg> a{};
+    WarpArgsT<Seg, Row> a{};
     a.segs = D.up(n_segs ? segs : &none, n_segs ? n_segs : 1);
     a.rows = D.up(rows.data(), rows.size());
     a.G = D.up(G.data(), G.size());
     a.x = D.up(x, (size_t)B * S);
     a.x_pitch = S;
-    float *dy = D.fill<float>((size_t)B * S_w, 0xff);
+    const int64_t W = (int64_t)n_hi - n_lo;
+    float *dy = D.fill<float>((size_t)B * W, 0xff);
     a.y = dy;
-    a.y_pitch = S_w;
-    a.n_hi = S_w;
+    a.y_pitch = W;
+    a.n_lo = n_lo;
+    a.n_hi = n_hi;
     TCHECK(D.err);
-    TCHECK(launch(a, B, nullptr));
+    TCHECK(launch_warp_tile(a, B, nullptr));
     TCHECK(hipDeviceSynchronize());
-    TCHECK(download(y, dy, (size_t)B * S_w));
+    TCHECK(download(y, dy, (size_t)B * W));
     return VITS_OK;
+}
+
+template <class Seg, class Fault>
+int test_warp_as(int device_id, const float *x, const int64_t *counts, int B, int S, const Seg *segs, const int32_t *seg_first,
+                 float *y, int S_w, Fault fault) {
+    if (int rc = test_dev(device_id)) return rc;
+    if (!x || !y || !counts || !seg_first || B <= 0 || S <= 0 || S_w < 1) return fail(nullptr, VITS_E_ARG, "bad warp test arguments");
+    if (seg_first[0] != 0) return fail(nullptr, VITS_E_ARG, "seg_first[0] = %d, not 0", (int)seg_first[0]);
+    std::vector<int64_t> n_in;
+    if (int rc = warp_test_rows(segs, seg_first, counts, B, S, fault, n_in)) return rc;
+    std::vector<WarpRow> rows;
+    const int64_t need = warp_rows(segs, seg_first, n_in.data(), B, rows);
+    if (S_w < need) return fail(nullptr, VITS_E_ARG, "S_w = %d, the longest row has %lld output samples", S_w, (long long)need);
+    DevBufs D;
+    return warp_test_launch(D, segs, (size_t)seg_first[B], rows, x, B, S, 0, S_w, y);
 }
 }  // namespace
 }  // extern "C++"
 
 int vits_test_warp(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_warp_seg *segs, const int32_t *seg_first,
                    float *y, int S_w) {
-    return test_warp_as(device_id, x, counts, B, S, segs, seg_first, y, S_w, warp_segs_fault, launch_warp);
+    return test_warp_as(device_id, x, counts, B, S, segs, seg_first, y, S_w, warp_segs_fault);
 }
 
 int vits_test_glide(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_glide_seg *segs, const int32_t *seg_first,
                     float *y, int S_w) {
-    return test_warp_as(device_id, x, counts, B, S, segs, seg_first, y, S_w, glide_segs_fault, launch_glide);
+    return test_warp_as(device_id, x, counts, B, S, segs, seg_first, y, S_w, glide_segs_fault);
 }
 
 // The wide kernels ("pitch at an output rate") by value: the caller's records under the folded limits, a pair of rates per row
@@ -5960,36 +5931,30 @@ int vits_test_glide(int device_id, const float *x, const int64_t *counts, int B,
 // A row without a record is an identity row: ceil(n_b * L / M) samples by the resampler's rule.
 extern "C++" {
 namespace {
-template <class Seg, class Fault, class Launch>
+template <class Seg, class Fault>
 int test_warp_rate_as(int device_id, const float *x, const int64_t *counts, int B, int S, const Seg *segs, const int32_t *seg_first,
-                      const int32_t *in_rates, const int32_t *out_rates, int n_lo, int n_hi, float *y, Fault fault, Launch launch) {
+                      const int32_t *in_rates, const int32_t *out_rates, int n_lo, int n_hi, float *y, Fault fault) {
     if (int rc = test_dev(device_id)) return rc;
     if (!x || !y || !counts || !seg_first || !in_rates || !out_rates || B <= 0 || S <= 0 || n_lo < 0 || n_hi <= n_lo)
         return fail(nullptr, VITS_E_ARG, "bad warp test arguments");
     if (seg_first[0] != 0) return fail(nullptr, VITS_E_ARG, "seg_first[0] = %d, not 0", (int)seg_first[0]);
-    std::vector<int64_t> n_in((size_t)B), L((size_t)B, 1), M((size_t)B, 1);
+    std::vector<int64_t> n_in, L((size_t)B, 1), M((size_t)B, 1);
     std::vector<ResamplePlan> plans((size_t)B);
-    for (int b = 0; b < B; b++) {
-        const int32_t ns = seg_first[b + 1] - seg_first[b];
-        if (ns < 0 || (ns > 0 && !segs)) return fail(nullptr, VITS_E_ARG, "row %d: seg_first is not ascending", b);
-        const std::string e = fault(segs + seg_first[b], ns);
-        if (!e.empty()) return fail(nullptr, VITS_E_ARG, "row %d: %s", b, e.c_str());
-        n_in[(size_t)b] = counts[b] < 0 ? 0 : (counts[b] > S ? S : counts[b]);
+    const auto rates = [&](int b, int32_t ns) {  // the row's pair of rates -> its plan
         const int in_rate = in_rates[b];
-        if (out_rates[b] != 0 && out_rates[b] != in_rate) {
-            const std::string pe = resample_plan(in_rate, out_rates[b], plans[(size_t)b]);
-            if (!pe.empty()) return fail(nullptr, VITS_E_ARG, "row %d: %s", b, pe.c_str());
-            L[(size_t)b] = plans[(size_t)b].L;
-            M[(size_t)b] = plans[(size_t)b].M;
-            if (ns > 0 && !warp_rate_ok(L[(size_t)b], M[(size_t)b]))
-                return fail(nullptr, VITS_E_ARG, "row %d: pitch at %d -> %d Hz: the ratio of the rates lies outside [1/4, 4]", b, in_rate, (int)out_rates[b]);
-        }
-    }
+        if (out_rates[b] == 0 || out_rates[b] == in_rate) return 0;
+        const std::string pe = resample_plan(in_rate, out_rates[b], plans[(size_t)b]);
+        if (!pe.empty()) return fail(nullptr, VITS_E_ARG, "row %d: %s", b, pe.c_str());
+        L[(size_t)b] = plans[(size_t)b].L;
+        M[(size_t)b] = plans[(size_t)b].M;
+        if (ns > 0 && !warp_rate_ok(L[(size_t)b], M[(size_t)b]))
+            return fail(nullptr, VITS_E_ARG, "row %d: pitch at %d -> %d Hz: the ratio of the rates lies outside [1/4, 4]", b, in_rate, (int)out_rates[b]);
+        return 0;
+    };
+    if (int rc = warp_test_rows(segs, seg_first, counts, B, S, fault, n_in, rates)) return rc;
     std::vector<WarpRateRow> rows;
     const int64_t need = warp_rate_rows(segs, seg_first, n_in.data(), L.data(), M.data(), B, rows);
     if (need > INT_MAX) return fail(nullptr, VITS_E_ARG, "the longest row has %lld output samples", (long long)need);
-    std::vector<float> G(kWarpTable);
-    warp_table(G.data());
     DevBufs D;
     for (int b = 0; b < B; b++) {  // the table of every resampled row (rows at one rate share it)
         if (!plans[(size_t)b].on()) continue;
@@ -6003,41 +5968,25 @@ int test_warp_rate_as(int device_id, const float *x, const int64_t *counts, int 
         resample_table(plans[(size_t)b], t.data(), r.Kp);
         r.table = D.up(t.data(), t.size());
     }
-    const size_t n_segs = (size_t)seg_first[B];
-    const Seg none{};
-    WarpRateArgsT<Seg> a{};
-    a.segs = D.up(n_segs ? segs : &none, n_segs ? n_segs : 1);
-    a.rows = D.up(rows.data(), rows.size());
-    a.G = D.up(G.data(), G.size());
-    a.x = D.up(x, (size_t)B * S);
-    a.x_pitch = S;
-    const int64_t W = (int64_t)n_hi - n_lo;
-    float *dy = D.fill<float>((size_t)B * W, 0xff);
-    a.y = dy;
-    a.y_pitch = W;
-    a.n_lo = n_lo;
-    a.n_hi = n_hi;
-    TCHECK(D.err);
-    TCHECK(launch(a, B, nullptr));
-    TCHECK(hipDeviceSynchronize());
-    TCHECK(download(y, dy, (size_t)B * W));
-    return VITS_OK;
+    return warp_test_launch(D, segs, (size_t)seg_first[B], rows, x, B, S, n_lo, n_hi, y);
 }
 }  // namespace
 }  // extern "C++"
 
 int vits_test_warp_rate(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_warp_seg *segs, const int32_t *seg_first,
                         const int32_t *in_rates, const int32_t *out_rates, int n_lo, int n_hi, float *y) {
-    return test_warp_rate_as(device_id, x, counts, B, S, segs, seg_first, in_rates, out_rates, n_lo, n_hi, y, warp_rate_segs_fault, launch_warp_rate);
+    return test_warp_rate_as(device_id, x, counts, B, S, segs, seg_first, in_rates, out_rates, n_lo, n_hi, y, warp_rate_segs_fault);
 }
 
 int vits_test_glide_rate(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_glide_seg *segs, const int32_t *seg_first,
                          const int32_t *in_rates, const int32_t *out_rates, int n_lo, int n_hi, float *y) {
-    return test_warp_rate_as(device_id, x, counts, B, S, segs, seg_first, in_rates, out_rates, n_lo, n_hi, y, glide_rate_segs_fault, launch_glide_rate);
+    return test_warp_rate_as(device_id, x, counts, B, S, segs, seg_first, in_rates, out_rates, n_lo, n_hi, y, glide_rate_segs_fault);
 }
 
 // Streamed pitch by value: the input cut at piece_bounds (increasing piece ends, the last one S), every piece through the
 // pipeline's stage (warp_run_begin / _piece / _window) on the pipeline's walk; n_cap is warp_stream_cap of the longest piece.
+// With a pair of rates ("pitch at an output rate") the wide stage: the same walk over a folded plan at ONE pair of rates - what a
+// chunked run has -, n_cap = warp_stream_cap(longest piece, S_w, the plan's least step, its largest Kh).
 extern "C++" {
 namespace {
 // "" or what is wrong with the piece ends; longest: the longest piece
@@ -6052,11 +6001,15 @@ int piece_bounds_check(const int64_t *piece_bounds, int n_pieces, int S, int64_t
     return 0;
 }
 
-// The planned run through the pipeline's stage on the pipeline's walk of a poisoned buffer: every piece of dx [B][S] joins the
+// The planned run through the pipeline's stage on the pipeline's walk of a poisoned buffer: every piece of x [B][S] joins the
 // history, every window it completes is copied into y [B][S_w].  Returns the number of windows.
-int walk_warp_pieces(WarpRun &run, DevBufs &D, const float *dG, const float *dx, int B, int S, size_t n_segs, int64_t n_cap,
-                     const int64_t *piece_bounds, int n_pieces, float *y, int S_w, int64_t *ranges, int max_ranges) {
-    const auto walk = [&](Carver &cv) { return carve_warp_stream(cv, B, S, n_cap, (int64_t)n_segs, run.row_bytes()); };
+int walk_warp_pieces(WarpRun &run, DevBufs &D, const float *x, int B, int S, int64_t n_cap, const int64_t *piece_bounds, int n_pieces, float *y,
+                     int S_w, int64_t *ranges, int max_ranges) {
+    std::vector<float> G(kWarpTable);
+    warp_table(G.data());
+    const float *dG = D.up(G.data(), G.size());
+    const float *dx = D.up(x, (size_t)B * S);
+    const auto walk = [&](Carver &cv) { return carve_warp_stream(cv, B, S, n_cap, run.n_segs(), run.row_bytes()); };
     const size_t bytes = carved_bytes(walk);
     Carver cv(D.fill<unsigned char>(bytes, 0xff), bytes);  // (poisoned: what a window must not read is NaN)
     TCHECK(D.err);
@@ -6089,62 +6042,11 @@ int walk_warp_pieces(WarpRun &run, DevBufs &D, const float *dG, const float *dx,
     return calls;
 }
 
+// rates: nullptr - the native stage -, or {in_rate, out_rate} - the folded one (out_rate 0 or in_rate: at the native rate)
 template <class Seg, class Fault>
 int test_warp_pieces_as(int device_id, const float *x, const int64_t *counts, int B, int S, const Seg *segs, const int32_t *seg_first,
-                        const int64_t *piece_bounds, int n_pieces, float *y, int S_w, int64_t *ranges, int max_ranges, Fault fault,
-                        std::vector<Seg> WarpRun::*mine, bool glide) {
-    if (int rc = test_dev(device_id)) return rc;
-    if (!x || !y || !counts || !seg_first || !piece_bounds || B <= 0 || S <= 0 || S_w < 1 || n_pieces < 1)
-        return fail(nullptr, VITS_E_ARG, "bad warp test arguments");
-    if (seg_first[0] != 0) return fail(nullptr, VITS_E_ARG, "seg_first[0] = %d, not 0", (int)seg_first[0]);
-    int64_t longest = 0;
-    if (int rc = piece_bounds_check(piece_bounds, n_pieces, S, longest)) return rc;
-    std::vector<int64_t> n_in((size_t)B);
-    for (int b = 0; b < B; b++) {
-        const int32_t ns = seg_first[b + 1] - seg_first[b];
-        if (ns < 0 || (ns > 0 && !segs)) return fail(nullptr, VITS_E_ARG, "row %d: seg_first is not ascending", b);
-        const std::string e = fault(segs + seg_first[b], ns);
-        if (!e.empty()) return fail(nullptr, VITS_E_ARG, "row %d: %s", b, e.c_str());
-        n_in[(size_t)b] = counts[b] < 0 ? 0 : (counts[b] > S ? S : counts[b]);
-    }
-    WarpRun run;
-    run.glide = glide;
-    const size_t n_segs = (size_t)seg_first[B];
-    (run.*mine).assign(segs, segs + n_segs);
-    run.first.assign(seg_first, seg_first + B + 1);
-    run.S_w = warp_rows(segs, seg_first, n_in.data(), B, run.rows);
-    if (S_w != run.S_w) return fail(nullptr, VITS_E_ARG, "S_w = %d, the rows give %lld", S_w, (long long)run.S_w);
-    const int64_t n_cap = warp_stream_cap(longest, run.S_w);
-    std::vector<float> G(kWarpTable);
-    warp_table(G.data());
-    DevBufs D;
-    const float *dG = D.up(G.data(), G.size());
-    const float *dx = D.up(x, (size_t)B * S);
-    return walk_warp_pieces(run, D, dG, dx, B, S, n_segs, n_cap, piece_bounds, n_pieces, y, S_w, ranges, max_ranges);
-}
-}  // namespace
-}  // extern "C++"
-
-int vits_test_warp_pieces(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_warp_seg *segs, const int32_t *seg_first,
-                          const int64_t *piece_bounds, int n_pieces, float *y, int S_w, int64_t *ranges, int max_ranges) {
-    return test_warp_pieces_as(device_id, x, counts, B, S, segs, seg_first, piece_bounds, n_pieces, y, S_w, ranges, max_ranges, warp_segs_fault,
-                               &WarpRun::wsegs, false);
-}
-
-int vits_test_glide_pieces(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_glide_seg *segs, const int32_t *seg_first,
-                           const int64_t *piece_bounds, int n_pieces, float *y, int S_w, int64_t *ranges, int max_ranges) {
-    return test_warp_pieces_as(device_id, x, counts, B, S, segs, seg_first, piece_bounds, n_pieces, y, S_w, ranges, max_ranges, glide_segs_fault,
-                               &WarpRun::gsegs, true);
-}
-
-// The wide streamed stage by value ("pitch at an output rate"): vits_test_warp_pieces' walk over a folded plan at ONE pair of rates -
-// what a chunked run has -, n_cap = warp_stream_cap(longest piece, S_w, the plan's least step, its largest Kh).
-extern "C++" {
-namespace {
-template <class Seg, class Fault>
-int test_warp_rate_pieces_as(int device_id, const float *x, const int64_t *counts, int B, int S, const Seg *segs, const int32_t *seg_first,
-                             int in_rate, int out_rate, const int64_t *piece_bounds, int n_pieces, float *y, int S_w, int64_t *ranges,
-                             int max_ranges, Fault fault, std::vector<Seg> WarpRun::*mine, bool glide) {
+                        const int *rates, const int64_t *piece_bounds, int n_pieces, float *y, int S_w, int64_t *ranges, int max_ranges,
+                        Fault fault, std::vector<Seg> WarpRun::*mine) {
     if (int rc = test_dev(device_id)) return rc;
     if (!x || !y || !counts || !seg_first || !piece_bounds || B <= 0 || S <= 0 || S_w < 1 || n_pieces < 1)
         return fail(nullptr, VITS_E_ARG, "bad warp test arguments");
@@ -6152,33 +6054,28 @@ int test_warp_rate_pieces_as(int device_id, const float *x, const int64_t *count
     int64_t longest = 0;
     if (int rc = piece_bounds_check(piece_bounds, n_pieces, S, longest)) return rc;
     ResamplePlan plan;
-    if (out_rate != 0 && out_rate != in_rate) {
-        const std::string pe = resample_plan(in_rate, out_rate, plan);
+    if (rates && rates[1] != 0 && rates[1] != rates[0]) {
+        const std::string pe = resample_plan(rates[0], rates[1], plan);
         if (!pe.empty()) return fail(nullptr, VITS_E_ARG, "%s", pe.c_str());
         if (seg_first[B] > 0 && !warp_rate_ok(plan.L, plan.M))
-            return fail(nullptr, VITS_E_ARG, "pitch at %d -> %d Hz: the ratio of the rates lies outside [1/4, 4]", in_rate, out_rate);
+            return fail(nullptr, VITS_E_ARG, "pitch at %d -> %d Hz: the ratio of the rates lies outside [1/4, 4]", rates[0], rates[1]);
     }
-    std::vector<int64_t> n_in((size_t)B), L((size_t)B, plan.L), M((size_t)B, plan.M);
-    for (int b = 0; b < B; b++) {
-        const int32_t ns = seg_first[b + 1] - seg_first[b];
-        if (ns < 0 || (ns > 0 && !segs)) return fail(nullptr, VITS_E_ARG, "row %d: seg_first is not ascending", b);
-        const std::string e = fault(segs + seg_first[b], ns);
-        if (!e.empty()) return fail(nullptr, VITS_E_ARG, "row %d: %s", b, e.c_str());
-        n_in[(size_t)b] = counts[b] < 0 ? 0 : (counts[b] > S ? S : counts[b]);
-    }
+    std::vector<int64_t> n_in;
+    if (int rc = warp_test_rows(segs, seg_first, counts, B, S, fault, n_in)) return rc;
     WarpRun run;
-    run.glide = glide;
-    run.folded = true;
-    const size_t n_segs = (size_t)seg_first[B];
-    (run.*mine).assign(segs, segs + n_segs);
+    run.glide = std::is_same_v<Seg, vits_glide_seg>;
+    run.folded = rates != nullptr;
+    (run.*mine).assign(segs, segs + seg_first[B]);
     run.first.assign(seg_first, seg_first + B + 1);
-    run.S_w = warp_rate_rows(segs, seg_first, n_in.data(), L.data(), M.data(), B, run.rrows);
+    if (rates) {
+        const std::vector<int64_t> L((size_t)B, plan.L), M((size_t)B, plan.M);
+        run.S_w = warp_rate_rows(segs, seg_first, n_in.data(), L.data(), M.data(), B, run.rrows);
+    } else
+        run.S_w = warp_rows(segs, seg_first, n_in.data(), B, run.rows);
     if (S_w != run.S_w) return fail(nullptr, VITS_E_ARG, "S_w = %d, the rows give %lld", S_w, (long long)run.S_w);
     int64_t min_step = kWarpMinStep;
-    warp_rate_plan_extent((run.*mine).data(), run.rrows, run.half, min_step);
+    warp_run_visit(run, [&](auto &sg, auto &rows) { warp_plan_extent(sg.data(), rows, run.half, min_step); });
     const int64_t n_cap = warp_stream_cap(longest, run.S_w, min_step, run.half);
-    std::vector<float> G(kWarpTable);
-    warp_table(G.data());
     DevBufs D;
     if (plan.on()) {
         const int Kp = resample_pitch(plan);
@@ -6191,25 +6088,37 @@ int test_warp_rate_pieces_as(int device_id, const float *x, const int64_t *count
             r.K = (int32_t)plan.K;
         }
     }
-    const float *dG = D.up(G.data(), G.size());
-    const float *dx = D.up(x, (size_t)B * S);
-    return walk_warp_pieces(run, D, dG, dx, B, S, n_segs, n_cap, piece_bounds, n_pieces, y, S_w, ranges, max_ranges);
+    return walk_warp_pieces(run, D, x, B, S, n_cap, piece_bounds, n_pieces, y, S_w, ranges, max_ranges);
 }
 }  // namespace
 }  // extern "C++"
 
+int vits_test_warp_pieces(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_warp_seg *segs, const int32_t *seg_first,
+                          const int64_t *piece_bounds, int n_pieces, float *y, int S_w, int64_t *ranges, int max_ranges) {
+    return test_warp_pieces_as(device_id, x, counts, B, S, segs, seg_first, nullptr, piece_bounds, n_pieces, y, S_w, ranges, max_ranges,
+                               warp_segs_fault, &WarpRun::wsegs);
+}
+
+int vits_test_glide_pieces(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_glide_seg *segs, const int32_t *seg_first,
+                           const int64_t *piece_bounds, int n_pieces, float *y, int S_w, int64_t *ranges, int max_ranges) {
+    return test_warp_pieces_as(device_id, x, counts, B, S, segs, seg_first, nullptr, piece_bounds, n_pieces, y, S_w, ranges, max_ranges,
+                               glide_segs_fault, &WarpRun::gsegs);
+}
+
 int vits_test_warp_rate_pieces(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_warp_seg *segs,
                                const int32_t *seg_first, int in_rate, int out_rate, const int64_t *piece_bounds, int n_pieces, float *y, int S_w,
                                int64_t *ranges, int max_ranges) {
-    return test_warp_rate_pieces_as(device_id, x, counts, B, S, segs, seg_first, in_rate, out_rate, piece_bounds, n_pieces, y, S_w, ranges,
-                                    max_ranges, warp_rate_segs_fault, &WarpRun::wsegs, false);
+    const int rates[2] = {in_rate, out_rate};
+    return test_warp_pieces_as(device_id, x, counts, B, S, segs, seg_first, rates, piece_bounds, n_pieces, y, S_w, ranges, max_ranges,
+                               warp_rate_segs_fault, &WarpRun::wsegs);
 }
 
 int vits_test_glide_rate_pieces(int device_id, const float *x, const int64_t *counts, int B, int S, const vits_glide_seg *segs,
                                 const int32_t *seg_first, int in_rate, int out_rate, const int64_t *piece_bounds, int n_pieces, float *y, int S_w,
                                 int64_t *ranges, int max_ranges) {
-    return test_warp_rate_pieces_as(device_id, x, counts, B, S, segs, seg_first, in_rate, out_rate, piece_bounds, n_pieces, y, S_w, ranges,
-                                    max_ranges, glide_rate_segs_fault, &WarpRun::gsegs, true);
+    const int rates[2] = {in_rate, out_rate};
+    return test_warp_pieces_as(device_id, x, counts, B, S, segs, seg_first, rates, piece_bounds, n_pieces, y, S_w, ranges, max_ranges,
+                               glide_rate_segs_fault, &WarpRun::gsegs);
 }
 
 // The rows entry by value: the plans of the distinct rates among out_rates (0 or in_rate: a native row), one record per row,

@@ -362,6 +362,13 @@ inline int64_t warp_emit_end(const Seg *segs, const std::vector<WarpRow> &rows, 
     return e;
 }
 
+// the largest Kh and the least step a plan's emit rule and cap count with: an unfolded plan's are the family's
+template <class Seg>
+inline void warp_plan_extent(const Seg *, const std::vector<WarpRow> &, int64_t &half, int64_t &min_step) {
+    half = kWarpMaxHalf;
+    min_step = kWarpMinStep;
+}
+
 // n_cap: output samples one delivery of a streamed run holds at most.  A piece of `piece_in` input samples moves every position's
 // bound by that much, which at the least step ONE / 2 completes 2 * piece_in outputs, and the uniform kWarpMaxHalf of the rule may
 // fall on either side of it: 2 * (piece_in + kWarpMaxHalf).  Longer ranges - a slow row's end releasing the others - are cut.
@@ -534,7 +541,7 @@ inline int64_t warp_rate_rows(const Seg *segs, const int32_t *seg_first, const i
 // row advances by M / L input samples an output: its step, rounded down, joins the least.  (A native identity row - a masked
 // copy - has K == 0: sample n is ready once input n exists.)
 template <class Seg>
-inline void warp_rate_plan_extent(const Seg *segs, const std::vector<WarpRateRow> &rows, int64_t &half, int64_t &min_step) {
+inline void warp_plan_extent(const Seg *segs, const std::vector<WarpRateRow> &rows, int64_t &half, int64_t &min_step) {
     half = 1;
     min_step = kWarpRateMaxStep;
     for (const WarpRateRow &r : rows) {
@@ -558,7 +565,7 @@ inline int64_t warp_rate_identity_ready(const WarpRateRow &r, int64_t X) {
 
 // warp_emit_end over the rows of a folded plan
 template <class Seg>
-inline int64_t warp_rate_emit_end(const Seg *segs, const std::vector<WarpRateRow> &rows, int64_t S_w, int64_t X, bool is_last, int64_t half) {
+inline int64_t warp_emit_end(const Seg *segs, const std::vector<WarpRateRow> &rows, int64_t S_w, int64_t X, bool is_last, int64_t half) {
     int64_t e = S_w;
     if (is_last) return e;
     for (const WarpRateRow &r : rows) {

@@ -370,11 +370,10 @@ inline ResampleBufs carve_resample(Carver &cv, int B, int S_out, int K) {
 struct WarpBufs {
     ResampleBufs front;
     vits_warp_seg *segs;
-    void *rows;  // [B] WarpRow records, or - a folded launch - WarpRateRow ones (row_bytes each)
+    void *rows;  // [B] records of row_bytes each: WarpRow, or - a folded launch ("pitch at an output rate") - WarpRateRow
     size_t plan_bytes;  // segs | rows
 };
 
-// (row_bytes: the size of a row's record - a folded launch's rows are WarpRateRow)
 inline WarpBufs carve_warp(Carver &cv, int B, int S_w, int64_t n_segs, size_t row_bytes = sizeof(WarpRow)) {
     WarpBufs w{};
     w.front = carve_resample(cv, B, S_w, 0);
@@ -397,7 +396,7 @@ struct WarpStreamBufs {
     float *out;
     int *n_out;
     vits_warp_seg *segs;
-    void *rows;  // [B] WarpRow records, or - a folded launch - WarpRateRow ones (row_bytes each)
+    void *rows;  // [B] records of row_bytes each, as WarpBufs::rows
     size_t plan_bytes;  // segs | rows
 };
 
